@@ -36,6 +36,12 @@ A "step" is one whole-table pass of the placement solver (every row of the table
   cpu_baseline = the CPU oracle port of the reference's per-object path, on a bounded sample: 1 thread, and as many threads as
                  the process may use CPUs (the cgroup's quota: 16 on this pool, where 256 hardware threads are visible); `value`
                  is the faster of the two, both are in the record
+
+A plain run measures the headline only: set-up, W warm-up steps, the K timed steps, the line (`metric`, `value`, `unit`,
+`ms_per_step`, `higher_is_better`, `dtype`, the workload's `config`, the last step's counters).  Everything else above — parity,
+roofline, cpu_baseline, the cold re-solves, the dependent tick, the other configurations (N = 1), the weak-scaled config 3
+and the churn tick streams of the sharded table (N > 1) — runs with --full.  --dump-outputs DIR (N = 1) writes what
+the timed path's last step handed its caller as DIR/<name>.npy (dump_outputs); the inputs are the same on every run.
 """
 import argparse
 import json
@@ -66,6 +72,7 @@ DEF_STRONG = "BASELINE config 4, strong scaling: ONE table of 100 M objects x 4 
 DEF_WEAK = "BASELINE config 3, weak scaling: 10 M objects x 1 024 nodes PER GPU (one N x 10 M-row table, capacities from the global load); " + DEF_TICK
 HBM_PEAK_GBPS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 C4_ROWS, C4_NODES = 100_000_000, 4096
+DUMP_MAX_ROWS = 12_000_000    # --dump-outputs: rows of the assignment column written in full (float32: 48 MB)
 
 
 def parse():
@@ -103,11 +110,40 @@ def parse():
     ap.add_argument("--no-c5", action="store_true", help="N=1: skip the config-5 record (10 %% churn per tick, 110 ticks + oracle replay)")
     ap.add_argument("--no-weak", action="store_true", help="N>1: skip the weak-scaled config-3 second measurement")
     ap.add_argument("--no-sharded-churn", action="store_true", help="N>1: skip the committed / churn tick streams of the sharded table")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline's timed steps, also run every other measurement and check of the line (parity, "
+                         "roofline and PMC passes, cpu_baseline, cold re-solves, the other configurations); the --no-* "
+                         "options above trim such a run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: after the timed steps, write what the last step returned to its caller as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB)")
     import glob
     newest = (sorted(glob.glob(os.path.join(ROOT, "profiles", "round*_traffic.json"))) or [os.path.join(ROOT, "profiles", "round5_traffic.json")])[-1]
     ap.add_argument("--traffic-json", default=newest,
                     help="fallback for roofline.traffic when the in-run PMC passes are skipped or fail (default: the newest profiles/round*_traffic.json)")
     return ap.parse_args()
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+
+def dump_outputs(d, g, st):
+    """What the timed path's last step handed its caller, read back right after the timed steps and written as d/<name>.npy:
+      assign  the committed assignment column (rio_gp_get_assign), float32: node ids are exact, NONE becomes 2^32.  A table of
+              more than DUMP_MAX_ROWS rows is written as a fixed sample: the rows synth.r(i, 7) % n for i < DUMP_MAX_ROWS,
+              deduplicated and in row order
+      used    the per-node used load (rio_gp_get_nodes), float64
+      stats   the last step's counters (rio_gp_tick_wait) in rio_gp_stats field order, float64"""
+    import rio_gp
+    import synth
+    os.makedirs(d, exist_ok=True)
+    col = g.get_assign()
+    if len(col) > DUMP_MAX_ROWS:
+        rows = synth.r(np.arange(DUMP_MAX_ROWS, dtype=np.uint64), 7) % np.uint64(len(col))
+        col = col[np.unique(rows).astype(np.int64)]
+    keys = [k for k, _ in rio_gp.Stats._fields_ if k != "reserved"]
+    np.save(os.path.join(d, "assign.npy"), col.astype(np.float32))
+    np.save(os.path.join(d, "used.npy"), g.get_nodes()[2].astype(np.float64))
+    np.save(os.path.join(d, "stats.npy"), np.array([st[k] for k in keys], np.float64))
 
 
 # ------------------------------------------------------------------------------------------------ CPU baseline
@@ -413,12 +449,15 @@ def pmc_traffic_in_run(n_rows, timeout=240):
 
 # ------------------------------------------------------------------------------------------------ config 5 (churn)
 
-def churn_record(a, g, cfg, rio_gp, local_rank, steps=None, warmup=None):
+def churn_record(a, g, cfg, rio_gp, local_rank, steps=None, warmup=None, lean=False, dump=None):
     """BASELINE.json config 5: the config-3 table, warm; every step = one liveness push (10 % of the nodes down, the
     previous casualties back) + one committed whole-table tick (evict + re-place through the fix-up path).  Two timed
     streams over the same masks: synchronous ticks (the host reads every tick's counters before the next push) and pipelined
     ticks (rio_gp_tick_async: the counters are read back later; results identical).  Parity: the oracle replays the whole
-    stream at full size.  Returns the record (also used as the `config5_churn` entry of the default line)."""
+    stream at full size.  Returns the record (also used as the `config5_churn` entry of the --full line).  `slow_path_ticks`
+    counts the synchronous stream's ticks that took the fix-up path, `pipelined.slow_path_ticks` the pipelined stream's.
+    lean: the pipelined stream alone (the line's `value`), no synchronous stream, parity or kernel spans.  dump: a
+    --dump-outputs directory, written right after the pipelined stream's timed ticks."""
     import pyoracle
     import synth
     steps = steps or a.steps
@@ -433,23 +472,24 @@ def churn_record(a, g, cfg, rio_gp, local_rank, steps=None, warmup=None):
         g.set_assign(warm)
         g.tick()
 
-    reset()
-    for k in range(warmup):
-        g.set_alive_all(masks[k])
-        g.tick()
-    g.sync()
-    moved = slow = 0
-    t0 = time.perf_counter()
-    for k in range(steps):
-        g.set_alive_all(masks[warmup + k])
-        st = g.tick()
-        moved += st["claimed"] + st["spilled"]
-        slow += st["slow_path"]
-    dt = time.perf_counter() - t0
-    final_sync = g.get_assign()
-    used_sync = g.get_nodes()[2]
+    if not lean:
+        reset()
+        for k in range(warmup):
+            g.set_alive_all(masks[k])
+            g.tick()
+        g.sync()
+        moved = slow = 0
+        t0 = time.perf_counter()
+        for k in range(steps):
+            g.set_alive_all(masks[warmup + k])
+            st = g.tick()
+            moved += st["claimed"] + st["spilled"]
+            slow += st["slow_path"]
+        dt = time.perf_counter() - t0
+        final_sync = g.get_assign()
+        used_sync = g.get_nodes()[2]
     parity = None
-    if not a.no_parity:
+    if not lean and not a.no_parity:
         ref = warm.copy()
         t1 = time.perf_counter()
         ref, used, ost = pyoracle.tick(ref, cfg["load"], cfg["aff"], cfg["cap"], np.ones(m, np.uint8), 2)
@@ -472,6 +512,8 @@ def churn_record(a, g, cfg, rio_gp, local_rank, steps=None, warmup=None):
         g.tick_async()
     sts = g.tick_wait()
     dtp = time.perf_counter() - t0
+    if dump:
+        dump_outputs(dump, g, sts[-1])
     frac = lambda sec: ALGO_BYTES_PER_DECISION * n * steps / sec / 1e9 / HBM_PEAK_GBPS
     # SURVEY.md section 8d's own accounting for config 5: the clean_server scan (4 B per object) + 4 B per evicted row + a placement
     # decision (16 B) per re-placed row — what the reference's clean_server + per-request path would move for the same
@@ -480,14 +522,21 @@ def churn_record(a, g, cfg, rio_gp, local_rank, steps=None, warmup=None):
     re_rows = sum(x["claimed"] + x["spilled"] + x["unplaced"] for x in sts)
     survey_bytes = 4 * n * steps + 4 * ev_rows + 16 * re_rows
     piped = {"ms_per_tick": dtp / steps * 1e3, "value": n * steps / dtp, "unit": "decisions/s", "frac_of_roofline": frac(dtp),
+             "slow_path_ticks": int(sum(x["slow_path"] for x in sts)),
              "frac_survey_accounting": survey_bytes / dtp / 1e9 / HBM_PEAK_GBPS,
              "survey_accounting": {"bytes_per_tick": survey_bytes / steps, "evicted_rows_per_tick": ev_rows / steps,
                                    "replaced_rows_per_tick": re_rows / steps,
                                    "definition": "SURVEY.md 8d, config 5: 4 B/object scan + 4 B per evicted row + 16 B per re-placed row"},
-             "equal_to_synchronous_stream": bool(np.array_equal(g.get_assign(), final_sync)) and
+             "equal_to_synchronous_stream": None if lean else bool(np.array_equal(g.get_assign(), final_sync)) and
              bool(np.array_equal(g.get_nodes()[2], used_sync)) and sts[-1] == st,
              "step": "rio_gp_set_alive_all + rio_gp_tick_async: nothing waits on the host between ticks, every tick's "
                      "counters are read afterwards (rio_gp_tick_wait)"}
+    what = ("config 5: %d objects x %d nodes, Zipf(1.1) load, cap 1.25x, warm; per tick 10 %% of the nodes flip and one "
+            "committed tick evicts and re-places their objects (~1 M rows, hundreds of cut nodes)" % (n, m))
+    if lean:
+        return {"workload": what, "ticks": steps, "warmup": warmup, "slow_path_ticks": None,   # (the synchronous stream's: not run)
+                "pipelined": piped, "objects_moved_per_s": sum(x["claimed"] + x["spilled"] for x in sts) / dtp,
+                "stats_last_tick": sts[-1], "parity": None}
     spans = None
     try:  # where a tick's time goes, measured by the kernels themselves (lab build: wall_clock64 phase traces)
         gl = rio_gp.LabPlacement(n, m, device=local_rank)
@@ -514,8 +563,7 @@ def churn_record(a, g, cfg, rio_gp, local_rank, steps=None, warmup=None):
     except Exception as e:  # measurement aid only
         spans = {"error": repr(e)}
     return {
-        "workload": "config 5: %d objects x %d nodes, Zipf(1.1) load, cap 1.25x, warm; per tick 10 %% of the nodes flip and one "
-                    "committed tick evicts and re-places their objects (~1 M rows, hundreds of cut nodes)" % (n, m),
+        "workload": what,
         "ticks": steps, "warmup": warmup, "slow_path_ticks": slow,
         "synchronous": {"ms_per_tick": dt / steps * 1e3, "value": n * steps / dt, "unit": "decisions/s", "frac_of_roofline": frac(dt),
                         "frac_survey_accounting": survey_bytes / dt / 1e9 / HBM_PEAK_GBPS,
@@ -601,23 +649,20 @@ def binding_record(a, cfg, rio_gp, local_rank, which, reps=30, warmup=4):
 
 def bench_churn(a, g, cfg, saved_stdout, rio_gp, local_rank):
     """--workload c5: config 5 as the bench line of its own."""
-    rec = churn_record(a, g, cfg, rio_gp, local_rank)
-    n = cfg["n"]
+    rec = churn_record(a, g, cfg, rio_gp, local_rank, lean=not a.full, dump=a.dump_outputs)
     out = {
         "metric": "placement decisions/sec, 10M objects x 1 024 nodes with 10 % node-failure churn per tick",
         "value": rec["pipelined"]["value"], "unit": "decisions/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": rec["pipelined"]["ms_per_tick"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u32", "data": "synthetic",
-        "config": {"workload": rec["workload"], "step": rec["pipelined"]["step"], "slow_path_steps": rec["slow_path_ticks"]},
+        "dtype": "u32", "data": "synthetic", "full": a.full,
+        "config": {"workload": rec["workload"], "step": rec["pipelined"]["step"], "slow_path_steps": rec["pipelined"]["slow_path_ticks"]},
         "config5_churn": rec, "parity": rec["parity"],
         "roofline": {"bound": "hbm", "achieved": ALGO_BYTES_PER_DECISION * rec["pipelined"]["value"] / 1e9, "peak": HBM_PEAK_GBPS,
                      "unit": "GB/s", "frac": rec["pipelined"]["frac_of_roofline"], "traffic": None,
                      "traffic_source": "not measured for this workload (profiles/ holds the per-kernel summaries of the fix-up path)",
                      "kernel": "whole committed tick (5 dependent launches; latency-bound, DESIGN.md section 5)"},
     }
-    sys.stdout.flush()
-    os.dup2(saved_stdout, 1)
-    print(json.dumps(out), flush=True)
+    emit_line(out, saved_stdout)
     if rec["parity"] is not None and not rec["parity"]["equal"]:
         sys.exit(3)
 
@@ -764,13 +809,20 @@ def run_sharded(a, dist, torch, rio_gp, synth, workload, rank, world, local_rank
     st = sts[-1]
     assert st["kept"] + st["claimed"] + st["spilled"] + st["unplaced"] == n_total
     # ---- (2) round 2's quantity, kept under its own name: the cold table re-solved back to back WITHOUT committing
-    g.set_assign(none_col)
-    cdt, cgpu_ms, cst, cslow = timed_steps(a, g, dist, torch, sol.solve_async, sol.solve_wait)
+    cold = None
+    if a.full:
+        g.set_assign(none_col)
+        cdt, cgpu_ms, cst, cslow = timed_steps(a, g, dist, torch, sol.solve_async, sol.solve_wait)
+        cold = {"value": n_total * a.steps / cdt, "unit": "decisions/s", "ms_per_step": cdt / a.steps * 1e3,
+                "gpu_ms_per_step_events": cgpu_ms / a.steps, "slow_path_steps": cslow,
+                "stats_last_step": cst,
+                "note": "rio_gp_shard_solve_async of the SAME cold table back to back, never committed "
+                        "(what rounds 2-3 reported as `value` at N > 1)"}
     parity = None
-    if not a.no_parity:
+    if a.full and not a.no_parity:
         parity = parity_sharded(dist, a.backend, g, sol, workload, n_total, m, bounds, rank, world, cfg["cap"])
     ticks = None
-    if not a.no_sharded_churn:
+    if a.full and not a.no_sharded_churn:
         if a.no_parity:
             sol.tick()   # the committed (warm) table the tick streams start from
         phase = []
@@ -804,11 +856,7 @@ def run_sharded(a, dist, torch, rio_gp, synth, workload, rank, world, local_rank
                     "data_path_comm_ranks": [x["native_rung_comm_ranks"] for x in infos],
                     "note": "p2p rung: no collective on the data path (stores into the peers' IPC-mapped windows); native rung: ONE "
                             "ncclComm of the library's own, world ranks; torch rung: the control plane's group carries the records"},
-           "cold_resolve_uncommitted": {"value": n_total * a.steps / cdt, "unit": "decisions/s", "ms_per_step": cdt / a.steps * 1e3,
-                                        "gpu_ms_per_step_events": cgpu_ms / a.steps, "slow_path_steps": cslow,
-                                        "stats_last_step": cst,
-                                        "note": "rio_gp_shard_solve_async of the SAME cold table back to back, never committed "
-                                                "(what rounds 2-3 reported as `value` at N > 1)"},
+           "cold_resolve_uncommitted": cold,
            "whole_step_achieved_GBps": ALGO_BYTES_PER_DECISION * n / (gpu_ms / a.steps * 1e-3) / 1e9}
     g.close()
     return rec
@@ -828,21 +876,28 @@ def peer_matrix(torch, world, same_device):
 # ------------------------------------------------------------------------------------------------ main
 
 def visible_devices():
-    """HIP devices this process can see (hipGetDeviceCount through ctypes: no torch import in the launcher)."""
-    import ctypes
+    """HIP devices this process can see (hipGetDeviceCount through ctypes), counted in a short-lived child process: the
+    launcher itself never brings a HIP runtime up, so it holds no GPU while its ranks run."""
+    code = ("import ctypes\n"
+            "try:\n"
+            "    hip = ctypes.CDLL('libamdhip64.so')\n"
+            "except OSError:\n"
+            "    print(0)\n"
+            "else:\n"
+            "    n = ctypes.c_int(0)\n"
+            "    print(int(n.value) if hip.hipGetDeviceCount(ctypes.byref(n)) == 0 else 0)\n")
     try:
-        hip = ctypes.CDLL("libamdhip64.so")
-        n = ctypes.c_int(0)
-        return int(n.value) if hip.hipGetDeviceCount(ctypes.byref(n)) == 0 else 0
-    except OSError:
+        r = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, timeout=120)
+        return int(r.stdout.split()[-1]) if r.returncode == 0 and r.stdout.split() else 0
+    except (OSError, ValueError, subprocess.TimeoutExpired):
         return 0
 
 
 def spawn_ranks(a):
     """`python bench.py --gpus N` with N > 1 and no launcher around it (no WORLD_SIZE in the environment): become the launcher —
-    re-exec under torch.distributed.run with one rank per GPU (rank i -> device i) and the same arguments, so that the command
-    prints ONE line with n_gpus = N.  Fewer than N visible devices is an error, never a silent one-GPU line (unless
-    --same-device, the one-GPU flow test)."""
+    run torch.distributed.run as a child process with one rank per GPU (rank i -> device i) and the same arguments, so that the
+    command prints ONE line with n_gpus = N, and exit with its status.  Fewer than N visible devices is an error, never a silent
+    one-GPU line (unless --same-device, the one-GPU flow test)."""
     have = visible_devices()
     if not a.same_device and have < a.gpus:
         sys.stderr.write("bench.py: --gpus %d asked for, %d HIP device(s) visible: refusing to run (a line measured on fewer GPUs than "
@@ -857,13 +912,28 @@ def spawn_ranks(a):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stderr.write("bench.py: --gpus %d without a launcher: starting %d ranks myself: %s\n" % (a.gpus, a.gpus, " ".join(cmd)))
     sys.stdout.flush(); sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd).returncode
+    raise SystemExit(rc if rc >= 0 else 128 - rc)
+
+
+def emit_line(out, saved_stdout):
+    """The line on the real stdout: Python's and C's buffered output (pointed at stderr for the run) flushed first."""
+    sys.stdout.flush()
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+    os.dup2(saved_stdout, 1)
+    print(json.dumps(out), flush=True)
 
 
 def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.dump_outputs and (a.gpus > 1 or a.force_sharded):
+        raise SystemExit("--dump-outputs writes the outputs of a single-GPU line (--gpus 1, not --force-sharded)")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(a)  # (does not return)
     # stdout carries exactly ONE line, the JSON: libraries that write to C stdout (RCCL prints a version banner from
@@ -904,7 +974,7 @@ def main():
         # ---- row-sharded runs: the primary measurement, then (N>1, c4) the weak-scaled config 3 in the same run
         prim = run_sharded(a, dist, torch, rio_gp, synth, workload, rank, world, local_rank)
         weak = None
-        if workload == "c4" and world > 1 and not a.no_weak:
+        if workload == "c4" and world > 1 and a.full and not a.no_weak:
             weak = run_sharded(a, dist, torch, rio_gp, synth, "c3", rank, world, local_rank)
         dist.barrier()
         dist.destroy_process_group()
@@ -917,7 +987,7 @@ def main():
                       "placement decisions/sec + achieved HBM GB/s, 100M objects x 4 096 nodes row-sharded across the GPUs",
             "value": prim["value"], "unit": "decisions/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": prim["ms_per_step"], "higher_is_better": True, "scaling": "strong" if strong else "weak",
-            "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "u32", "data": "synthetic", "full": a.full,
             "config": {"workload": ("config 4: %d objects x %d nodes, %d per GPU (ONE table, rows sharded over %d ranks), Zipf(1.1) "
                                     "load, cap 1.25x of the global load, cold start" % (prim["rows_total"], m, prim["rows_this_rank"], world))
                        if strong else ("%s: %d objects x %d nodes per GPU of one %d-row table, cap from the global load, cold start"
@@ -963,9 +1033,7 @@ def main():
                                    "exchange": weak["exchange"], "slow_path_steps": weak["slow_path_steps"], "parity": weak["parity"],
                                    "value_is": DEF_WEAK, "cold_resolve_uncommitted": weak["cold_resolve_uncommitted"],
                                    "committed_ticks": weak["committed_ticks"]}
-        sys.stdout.flush()
-        os.dup2(saved_stdout, 1)
-        print(json.dumps(out), flush=True)
+        emit_line(out, saved_stdout)
         bad = [p for p in (prim["parity"], weak["parity"] if weak else None) if p is not None and not p["equal"]]
         for r_ in (prim, weak):
             cp = ((r_ or {}).get("committed_ticks") or {}).get("parity") if r_ else None
@@ -1001,6 +1069,33 @@ def main():
     n_slow = sum(x["slow_path"] for x in sts)
     assert st["kept"] + st["claimed"] + st["spilled"] + st["unplaced"] == n
     total_decisions = n * a.steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, g, st)
+    fr = lambda sec: ALGO_BYTES_PER_DECISION * n / sec / 1e9 / HBM_PEAK_GBPS
+    tick_s = dt / a.steps
+    config = {"workload": "config 3: %d objects x %d nodes, Zipf(1.1) load, cap 1.25x; a stream of committed ticks that "
+                          "starts from the cold table (all pending)" % (n, m) if workload == "c3" else workload,
+              "objects_per_gpu": n, "nodes": m, "parallelism": "rows sharded x1",
+              "step": "rio_gp_tick_async = k_scan + k_resolve (+ the fix-up, guarded on the device) + commit; nothing waits on the "
+                      "host between ticks, every tick's counters are read at the end.  Once a tick's verdict says nothing is "
+                      "left to fix and nothing has changed since, the following ticks are k_scan + k_resolve only: the scans "
+                      "alternate between two streams and hand their rows over wave range by wave range (wave w of tick "
+                      "k + 1 waits for wave w of tick k, not for its launch), k_resolve runs on a third stream behind "
+                      "its scan",
+              "exchange": None, "slow_path_steps": n_slow}
+    if not a.full:
+        g.close()
+        out = {
+            "metric": "placement decisions/sec + achieved HBM GB/s, 10M objects x 1 024 nodes",
+            "value": total_decisions / dt, "unit": "decisions/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": tick_s * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u32", "data": "synthetic", "full": False, "config": config,
+            "gpu_ms_per_step_events": gpu_ms / a.steps,
+            "committed_tick_frac": fr(tick_s),   # the whole tick against the HBM roofline; the per-kernel figures need --full
+            "stats_last_step": st,
+        }
+        emit_line(out, saved_stdout)
+        return
     # the synchronous form of the same tick (the host reads every tick's counters before the next one)
     dep = None
     try:
@@ -1087,10 +1182,10 @@ def main():
             gb.tick_wait()
             gb.close()
             cms = float(np.mean(cs))
-            fr = lambda ms_: ALGO_BYTES_PER_DECISION * k * n / (ms_ * 1e-3) / 1e9 / HBM_PEAK_GBPS
+            frk = lambda ms_: ALGO_BYTES_PER_DECISION * k * n / (ms_ * 1e-3) / 1e9 / HBM_PEAK_GBPS
             cold = {"rows": k * n, "column_bytes": 16 * k * n, "kernel_ms": cms,
-                    "achieved": ALGO_BYTES_PER_DECISION * k * n / (cms * 1e-3) / 1e9, "unit": "GB/s", "frac": fr(cms),
-                    "whole_step_ms": wms, "whole_step_frac": fr(wms), "committed_tick_ms": tms, "committed_tick_frac": fr(tms),
+                    "achieved": ALGO_BYTES_PER_DECISION * k * n / (cms * 1e-3) / 1e9, "unit": "GB/s", "frac": frk(cms),
+                    "whole_step_ms": wms, "whole_step_frac": frk(wms), "committed_tick_ms": tms, "committed_tick_frac": frk(tms),
                     "stream_probe_GBps": ALGO_BYTES_PER_DECISION * k * n / pm / 1e6,
                     "note": "the headline rows tiled 4x: beyond the 256 MiB Infinity Cache; kernel = k_scan alone (dispatch events), "
                             "whole step = k_scan + k_resolve back to back, committed tick = rio_gp_tick_async (30 pipelined steps "
@@ -1251,23 +1346,12 @@ def main():
             traffic = tj.get("hbm_bytes_per_launch")
             traffic_source += "; value replayed from %s (rocprofv3 PMC passes of an earlier run of this build)" % \
                 os.path.relpath(a.traffic_json, ROOT)
-    fr = lambda sec: ALGO_BYTES_PER_DECISION * n / sec / 1e9 / HBM_PEAK_GBPS
-    tick_s = dt / a.steps
     out = {
         "metric": "placement decisions/sec + achieved HBM GB/s, 10M objects x 1 024 nodes",
         "value": total_decisions / dt, "unit": "decisions/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": tick_s * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u32", "data": "synthetic",
-        "config": {"workload": "config 3: %d objects x %d nodes, Zipf(1.1) load, cap 1.25x; a stream of committed ticks that "
-                               "starts from the cold table (all pending)" % (n, m) if workload == "c3" else workload,
-                   "objects_per_gpu": n, "nodes": m, "parallelism": "rows sharded x1",
-                   "step": "rio_gp_tick_async = k_scan + k_resolve (+ the fix-up, guarded on the device) + commit; nothing waits on the "
-                           "host between ticks, every tick's counters are read at the end.  Once a tick's verdict says nothing is "
-                           "left to fix and nothing has changed since, the following ticks are k_scan + k_resolve only: the scans "
-                           "alternate between two streams and hand their rows over wave range by wave range (wave w of tick "
-                           "k + 1 waits for wave w of tick k, not for its launch), k_resolve runs on a third stream behind "
-                           "its scan",
-                   "exchange": None, "slow_path_steps": n_slow},
+        "dtype": "u32", "data": "synthetic", "full": True,
+        "config": config,
         "gpu_ms_per_step_events": gpu_ms / a.steps,
         "committed_tick_frac": fr(tick_s),
         "dependent_tick_ms": dep,
@@ -1315,14 +1399,7 @@ def main():
             parity["against_reference_port"] = port_parity
             parity["equal"] = parity["equal"] and port_parity["equal"]
     g.close()
-    sys.stdout.flush()
-    try:
-        import ctypes
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
-    os.dup2(saved_stdout, 1)
-    print(json.dumps(out), flush=True)
+    emit_line(out, saved_stdout)
     bad = [p for p in (parity, (c4one or {}).get("parity"), ((c4one or {}).get("churn_tick_pipelined") or {}).get("parity"),
                        (c2rec or {}).get("parity"), (c5rec or {}).get("parity"),
                        (bind.get("contended") or {}).get("parity"), (bind.get("skew") or {}).get("parity"))

@@ -21,7 +21,7 @@ def _one_json_line(out):
 
 def test_bench_line_n1():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--workload", "c2",
-                        "--cpu-sample", "20000"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--cpu-sample", "20000", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_json_line(r.stdout)
     assert d["n_gpus"] == 1 and d["unit"] == "decisions/s" and d["value"] > 1e9
@@ -43,10 +43,35 @@ def test_bench_line_n1():
     assert d["roofline"]["gpu_ms_per_step_events"] > 0
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path, oracle):
+    """Without --full the line is the headline alone: K timed committed ticks, no parity, roofline or second measurement.
+    --dump-outputs writes what the last timed tick left for its caller; from the cold table the first tick places every row
+    and the later ones keep it, so the column, `used` and the counters are the oracle's."""
+    import numpy as np
+    import synth
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--workload", "c2", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _one_json_line(r.stdout)
+    assert d["full"] is False and d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "decisions/s" and d["dtype"] == "u32"
+    assert d["higher_is_better"] is True and abs(d["value"] - 1_000_000 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    assert not {"parity", "roofline", "cpu_baseline", "cold_resolve_uncommitted", "config2", "config5_churn"} & set(d)
+    c = synth.config("c2")
+    want, used, st = oracle.tick(c["cur"], c["load"], c["aff"], c["cap"], c["alive"], 2)
+    assign = np.load(out / "assign.npy")
+    assert assign.dtype == np.float32 and np.array_equal(assign, want.astype(np.float32))
+    assert np.array_equal(np.load(out / "used.npy"), used.astype(np.float64))
+    last = d["stats_last_step"]
+    assert last["kept"] == 1_000_000
+    assert np.load(out / "stats.npy").tolist() == [float(last[k]) for k in last]
+
+
 def test_bench_headline_line_has_parity_traffic_and_config4():
     """The default command line of the driver at N=1, shortened: config 3 at full size with the in-run parity check, the
     in-run PMC passes and the config-4-on-one-GPU data point (100 M x 4 096, parity at size)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--cpu-sample", "200000"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--cpu-sample", "200000",
+                        "--full"],
                        capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_json_line(r.stdout)
@@ -118,6 +143,36 @@ def test_bench_gpus_2_without_a_launcher_spawns_its_own_ranks():
         assert r.returncode == 2 and r.stdout.strip() == "" and "refusing to run" in r.stderr
 
 
+def _ranks_on_one_gpu(world, args, tmp_path, timeout=900):
+    """`world` ranks of bench.py sharing device 0 (--same-device, gloo control plane), each started with the environment a
+    launcher gives its ranks (RANK, LOCAL_RANK, WORLD_SIZE, MASTER_ADDR, MASTER_PORT) and no launcher process: the test
+    process and the ranks are all that hold the GPU.  Returns (returncodes, rank 0's stdout, the ranks' stderr tails)."""
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world)] + args + ["--backend", "gloo", "--same-device", "--full"]
+    procs, errs = [], []
+    try:
+        for r in range(world):
+            env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), LOCAL_WORLD_SIZE=str(world),
+                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+            errs.append(open(tmp_path / ("rank%d.err" % r), "w+"))
+            procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, stderr=errs[-1],
+                                          text=True, cwd=ROOT, env=env))
+        out = procs[0].communicate(timeout=timeout)[0]
+        for p in procs[1:]:
+            p.wait(timeout=120)
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
+    tails = []
+    for r, f in enumerate(errs):
+        f.seek(0)
+        tails.append("rank %d: %s" % (r, f.read()[-1500:]))
+        f.close()
+    return [p.returncode for p in procs], out, "\n".join(tails)
+
+
 def _check_scaling_fields(d, world, exchange):
     """What every N > 1 line says about itself, in the same words at every N: `value` = committed ticks of the ONE config-4
     table (the definition string is the N = 1 line's), who ran where, and what RCCL was asked for."""
@@ -151,7 +206,8 @@ def test_bench_ladder_one_rank_fails_p2p_every_rank_lands_on_the_same_rung():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--total-objects", "600000", "--no-weak", "--no-sharded-churn", "--no-cpu-baseline", "--backend", "gloo", "--same-device"]
+           "--total-objects", "600000", "--no-weak", "--no-sharded-churn", "--no-cpu-baseline", "--backend", "gloo", "--same-device",
+           "--full"]
     env = dict(os.environ, RIO_GP_BENCH_FAIL_RUNG="p2p", RIO_GP_BENCH_FAIL_RANK="1")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -174,7 +230,7 @@ def test_bench_config4_strong_scaling_two_ranks(exchange):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2",
-           "--total-objects", "2000000", "--objects", "300000", "--backend", "gloo", "--same-device", "--exchange", exchange]
+           "--total-objects", "2000000", "--objects", "300000", "--backend", "gloo", "--same-device", "--exchange", exchange, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _one_json_line(r.stdout)
@@ -201,48 +257,45 @@ def test_bench_config4_strong_scaling_two_ranks(exchange):
         assert rec["parity"]["equal"] is True, rec["parity"]
 
 
-def test_bench_config4_eight_ranks_p2p_on_one_gpu():
-    """Config 4's node count (4 096) over EIGHT ranks on the one GPU, the driver's command line with its default exchange:
-    eight exchange kernels of 512 node groups each, kept to 64 workgroups a rank by the co-residency rule."""
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "6", "--warmup", "2",
-           "--total-objects", "4000000", "--objects", "200000", "--no-cpu-baseline", "--backend", "gloo", "--same-device"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
-    assert r.returncode == 0, r.stderr[-3000:]
-    d = _one_json_line(r.stdout)
-    assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["config"]["nodes"] == 4096
+def test_bench_config4_four_ranks_p2p_on_one_gpu(tmp_path):
+    """Config 4's node count (4 096) over FOUR ranks on the one GPU with the driver's default exchange: four exchange kernels
+    of 1 024 node groups each, kept co-resident by the grid bound of ranks that share a device.  The tables are those of the
+    eight-rank form this test had (4 M rows of config 4, 1.6 M of the weak config 3): four ranks, the test process, and with
+    a launcher its agent too, are as many processes as may hold one GPU at once."""
+    rcs, out, err = _ranks_on_one_gpu(4, ["--steps", "6", "--warmup", "2", "--total-objects", "4000000", "--objects", "400000",
+                                          "--no-cpu-baseline"], tmp_path)
+    assert rcs == [0, 0, 0, 0], err
+    d = _one_json_line(out)
+    assert d["n_gpus"] == 4 and d["scaling"] == "strong" and d["config"]["nodes"] == 4096
     assert d["config"]["exchange"] == "p2p" and d["config"]["exchange_ladder"][0]["ok"] is True, d["config"]
     assert d["parity"]["equal"] is True and d["parity"]["checked_rows"] == 4_000_000
-    assert d["weak_config3"]["parity"]["equal"] is True
-    _check_scaling_fields(d, 8, "p2p")
-    # the committed / churn tick streams, synchronous and asynchronous, between eight processes: every tick of a quiet
+    assert d["weak_config3"]["parity"]["equal"] is True and d["weak_config3"]["objects_total"] == 1_600_000
+    _check_scaling_fields(d, 4, "p2p")
+    # the committed / churn tick streams, synchronous and asynchronous, between the processes: every tick of a quiet
     # asynchronous stream lands in the next window slot (a rank that is through a tick must not overwrite what a slower one
-    # has not read — found exactly here, with a tick that took four sequence numbers and four slots)
+    # has not read — found with eight ranks, a tick that took four sequence numbers and four slots)
     for rec in (d["committed_ticks"], d["weak_config3"]["committed_ticks"]):
         assert "error" not in rec, rec
         assert rec["parity"]["equal"] is True and rec["churn_async"]["slow_path_ticks"] == rec["ticks"]
 
 
-def test_bench_eight_ranks_on_one_gpu():
-    """The driver's N=8 command line, all eight ranks on the one GPU of the box: eight processes exchanging through each
-    other's IPC-mapped windows, global capacities, one JSON line (workload c2, 256 nodes)."""
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "3",
-           "--workload", "c2", "--objects", "1000000", "--no-cpu-baseline", "--backend", "gloo", "--same-device"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
-    assert r.returncode == 0, r.stderr[-3000:]
-    d = _one_json_line(r.stdout)
-    assert d["n_gpus"] == 8 and d["config"]["exchange"] == "p2p", d["config"]
+def test_bench_four_ranks_on_one_gpu(tmp_path):
+    """The N > 1 line with four ranks on the one GPU: four processes exchanging through each other's IPC-mapped windows,
+    global capacities, one JSON line (workload c2, 256 nodes; the 8 M rows of the eight-rank form this test had)."""
+    rcs, out, err = _ranks_on_one_gpu(4, ["--steps", "20", "--warmup", "3", "--workload", "c2", "--objects", "2000000",
+                                          "--no-cpu-baseline"], tmp_path)
+    assert rcs == [0, 0, 0, 0], err
+    d = _one_json_line(out)
+    assert d["n_gpus"] == 4 and d["config"]["exchange"] == "p2p", d["config"]
     st = d["stats_last_step"]
     assert st["n_objects"] == 8_000_000 and st["kept"] == 8_000_000 and d["config"]["slow_path_steps"] == 0   # committed ticks
     assert d["cold_resolve_uncommitted"]["stats_last_step"]["claimed"] == 8_000_000
+    assert all(r["device"] == 0 for r in d["config"]["ranks"])
 
 
 def test_bench_config5_churn_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--steps", "12", "--warmup", "3",
-                        "--objects", "1000000"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--objects", "1000000", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_json_line(r.stdout)
     rec = d["config5_churn"]
@@ -251,3 +304,21 @@ def test_bench_config5_churn_line():
     assert st["kept"] + st["claimed"] + st["spilled"] + st["unplaced"] == 1000000 and st["evicted"] > 0
     assert d["parity"]["equal"] is True and rec["pipelined"]["equal_to_synchronous_stream"] is True
 
+
+
+def test_bench_config5_plain_line(tmp_path):
+    """--workload c5 without --full: the pipelined churn stream alone is the line; its dump is the table after the last tick."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--steps", "12", "--warmup", "3",
+                        "--objects", "1000000", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _one_json_line(r.stdout)
+    rec = d["config5_churn"]
+    assert d["full"] is False and d["parity"] is None and d["value"] == rec["pipelined"]["value"] and d["value"] > 1e8
+    assert d["ms_per_step"] == rec["pipelined"]["ms_per_tick"] and rec["ticks"] == 12
+    assert rec["slow_path_ticks"] is None and rec["pipelined"]["slow_path_ticks"] == d["config"]["slow_path_steps"] > 0
+    assert "synchronous" not in rec and rec["pipelined"]["equal_to_synchronous_stream"] is None
+    st = rec["stats_last_tick"]
+    assert st["kept"] + st["claimed"] + st["spilled"] + st["unplaced"] == 1000000 and st["evicted"] > 0
+    assert np.load(out / "assign.npy").shape == (1000000,) and np.load(out / "stats.npy").tolist() == [float(st[k]) for k in st]

@@ -105,12 +105,15 @@ def test_script_round_trip_and_pg_dump_shape(tmp_path):
 
 
 def test_the_schema_is_the_reference_migration():
-    """Where the reference is at hand (this container, not the GPU box): PG_SCHEMA is the migration's statements."""
-    ref = "/root/reference/rio-rs/src/object_placement/migrations/0001-postgres-init.sql"
-    if not os.path.exists(ref):
-        pytest.skip("no reference tree here")
+    """PG_SCHEMA is the migration's statements: its whitespace-normalised text against the digest of the reference's
+    migration, stored under tests/golden/ (pg_schema_digest.json)."""
+    import hashlib
+    import json
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "pg_schema_digest.json")))
     norm = lambda t: re.sub(r"\s+", " ", t).strip().lower()
-    assert norm(open(ref).read()) == norm(snapshot.PG_SCHEMA)
+    mine = norm(snapshot.PG_SCHEMA).encode("utf-8")
+    assert len(mine) == gold["normalised_length"]
+    assert hashlib.sha256(mine).hexdigest() == gold["sha256"]
 
 
 def test_dbapi_transport_with_the_reference_statements(tmp_path):

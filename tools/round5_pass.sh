@@ -17,8 +17,8 @@ export TMPDIR=/tmp
 if [ "$HALF" = "a" ]; then
   ( timeout 1700 python -m pytest tests -m gpu -q -rf --timeout=900 2>&1 | tail -60 ) > $OUT/${TAG}_pytest_gpu.log
   ( timeout 300 python __graft_entry__.py smoke 2>&1 | tail -5 ) > $OUT/${TAG}_smoke.log
-  timeout 1200 python bench.py --steps 200 --warmup 20 > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err
-  timeout 600 python bench.py --workload c5 --steps 100 --warmup 10 > $OUT/${TAG}_bench_c5.json 2> $OUT/${TAG}_bench_c5.err
+  timeout 1200 python bench.py --steps 200 --warmup 20 --full > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err
+  timeout 600 python bench.py --workload c5 --steps 100 --warmup 10 --full > $OUT/${TAG}_bench_c5.json 2> $OUT/${TAG}_bench_c5.err
   cd /tmp
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -o ${TAG} -- python $ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-cold --no-c4 --no-c2 --no-c5 --no-pmc --no-parity > $OUT/${TAG}_prof_bench.json 2> $OUT/${TAG}_prof.err
   cd $ROOT
@@ -50,8 +50,8 @@ else
   for w in churn contended skew; do
     timeout 300 python tools/slowpath_workload.py $w 40 > $OUT/${TAG}_slowpath_$w.json 2> $OUT/${TAG}_slowpath_$w.err
   done
-  for nr in 2 8; do   # (started plainly: bench.py starts its own ranks)
-    timeout 900 python bench.py --gpus $nr --steps 10 --warmup 3 --total-objects 8000000 --objects 1000000 --backend gloo --same-device > $OUT/${TAG}_bench_sharded_${nr}ranks_one_gpu.json 2> $OUT/${TAG}_bench_sharded_${nr}ranks_one_gpu.err
+  for nr in 2 4; do   # (started plainly: bench.py starts its own ranks)
+    timeout 900 python bench.py --gpus $nr --steps 10 --warmup 3 --total-objects 8000000 --objects 1000000 --backend gloo --same-device --full > $OUT/${TAG}_bench_sharded_${nr}ranks_one_gpu.json 2> $OUT/${TAG}_bench_sharded_${nr}ranks_one_gpu.err
   done
   timeout 600 python tools/soak_sharded.py 3 150 150000 96 5 > $OUT/${TAG}_soak_sharded.json 2> $OUT/${TAG}_soak_sharded.err
   echo "---- kernel roofline"; cat $OUT/${TAG}_kernel_roofline.txt
@@ -62,7 +62,7 @@ else
   echo "---- fuzz"; cat $OUT/${TAG}_fuzz.json; tail -5 $OUT/${TAG}_fuzz.err
   echo "---- churn variants, config 4"; cut -c1-1200 $OUT/${TAG}_c4_variants.json
   echo "---- latencies"; cat $OUT/${TAG}_latency.txt
-  echo "---- sharded, ranks on one GPU"; for nr in 2 8; do cut -c1-900 $OUT/${TAG}_bench_sharded_${nr}ranks_one_gpu.json; tail -2 $OUT/${TAG}_bench_sharded_${nr}ranks_one_gpu.err; done
+  echo "---- sharded, ranks on one GPU"; for nr in 2 4; do cut -c1-900 $OUT/${TAG}_bench_sharded_${nr}ranks_one_gpu.json; tail -2 $OUT/${TAG}_bench_sharded_${nr}ranks_one_gpu.err; done
   echo "---- soak"; tail -3 $OUT/${TAG}_soak_sharded.json; tail -3 $OUT/${TAG}_soak_sharded.err
 fi
 find $OUT -name "*kernel_trace.csv" -size +4M -delete
