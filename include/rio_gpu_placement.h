@@ -88,7 +88,8 @@ extern "C" {
 #define RIO_GP_EUPSTREAM 2 /* -> ObjectPlacementError::Upstream (errors.rs:137-138) */
 #define RIO_GP_ENODEV 3    /* no HIP device / not gfx950: the product path fails loudly */
 #define RIO_GP_ENOMEM 4
-#define RIO_GP_ERANGE 5    /* string layer: the caller's output buffer is too small (nothing is truncated) */
+#define RIO_GP_ERANGE 5    /* string layer, and rio_gp_rows_on_nodes: the caller's output buffer is too small (nothing is
+                            * truncated; the sizes needed are reported) */
 #define RIO_GP_EAGAIN 6    /* string layer, rio_op_try_*: the host shadow cannot answer without the device (or without a lock a device
                             * call may hold): nothing was done, make the blocking call */
 
@@ -211,6 +212,29 @@ int rio_gp_remove_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx);
 int rio_gp_clean_server(rio_gp_t* h, uint32_t node, uint64_t* evicted);
 /* Same for any number of failed nodes in ONE pass: bit j of dead_bitmap (ceil(m/64) words). */
 int rio_gp_clean_servers(rio_gp_t* h, const uint64_t* dead_bitmap, uint64_t* evicted);
+
+/* ---- reverse index: the rows on given nodes ------------------------------------------------ */
+
+/* Reverse index of the assignment column: the object_placement(server_address) index (idx_object_placement_server_address,
+ * rio-rs/src/object_placement/migrations/0001-sqlite-init.sql:9) and the Redis backend's reverse set per address
+ * (rio-rs/src/object_placement/redis.rs:46-52,68-72), built on demand.  For every node j < m selected by node_bitmap (bit j of
+ * word j/64; NULL = every node; bits >= m are ignored, as rio_gp_clean_servers does) the rows whose assignment is j, ascending,
+ * concatenated in node order: node j's rows are out_rows[out_offsets[j] .. out_offsets[j+1]).  out_offsets has m + 1 entries
+ * (an unselected node: an empty range); *n_rows = out_offsets[m].
+ *   - The index of exactly the column rio_gp_get_assign returns at the same point: rows 0 .. n-1 whatever their affinity or
+ *     lifecycle state; a row holding RIO_GP_NONE, or any node id >= m (rows a shrinking rio_gp_set_nodes left behind), is listed
+ *     nowhere.  The output is one fixed byte string for a given column.
+ *   - Read-only: no table, counter, `used` vector or pending solve changes.
+ *   - out_rows == NULL with rows_cap == 0: counts only (the offsets).  *n_rows > rows_cap: RIO_GP_ERANGE with the offsets and
+ *     *n_rows filled, out_rows untouched.
+ *   - Scratch, allocated with the first call and kept until rio_gp_destroy: 8 MiB + 100 KiB of device memory and 64 KiB of
+ *     mapped pinned host memory for every (n, m) up to RIO_GP_MAX_OBJECTS x RIO_GP_MAX_NODES; the host-pointer form also
+ *     stages its listing in device memory (4 B per listed row, kept at the largest answer so far).
+ * The _dev form takes device pointers (d_offsets: m + 1 u64, d_rows: rows_cap u32) and waits once. */
+int rio_gp_rows_on_nodes(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t* out_offsets, uint32_t* out_rows,
+                         uint64_t rows_cap, uint64_t* n_rows);
+int rio_gp_rows_on_nodes_dev(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t* d_offsets, uint32_t* d_rows,
+                             uint64_t rows_cap, uint64_t* n_rows);
 
 /* ---- the placement policy, batched ------------------------------------------------------ */
 

@@ -41,6 +41,11 @@ uint64_t rio_gp_debug_chained_scans(rio_gp_t* h);
 /* speculative enqueue of the fix-up behind k_resolve, without waiting for the verdict: 0 (default) = when the previous
  * solve needed it | 1 = always | 2 = never. */
 int rio_gp_debug_set_speculate(rio_gp_t* h, int speculate);
+/* rio_gp_rows_on_nodes: rows per wave tile (rounded up to 256; 0 = by table size, the default).  A tile of more than 65 535 rows
+ * counts in u32 instead of u16.  rio_gp_debug_node_index_geometry: out4 = rows per tile | tiles | bytes per count-pass counter
+ * (2 | 4) | waves per workgroup (4 | 8), as the next call with that selection would run. */
+int rio_gp_debug_set_node_index(rio_gp_t* h, uint32_t tile_rows);
+int rio_gp_debug_node_index_geometry(rio_gp_t* h, const uint64_t* node_bitmap, uint32_t* out4);
 /* non-temporal column streams in k_scan: 0 = by table size (default) | 1 = always | 2 = never; process-wide. */
 void rio_gp_debug_set_scan_nt(int mode);
 /* window of the partitioned update / remove batches: 1 << shift rows, shift 12..14 (default 14); process-wide. */

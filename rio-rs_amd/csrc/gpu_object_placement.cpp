@@ -52,6 +52,11 @@
 
 #include "../../include/rio_gpu_object_placement.h"
 
+// Weak: the dense layer's reverse index is optional to this file — the host-memory stubs the string layer is tested against
+// without a GPU need not define it (rio_op_objects_on_server reports RIO_GP_EUPSTREAM then).
+extern "C" int rio_gp_rows_on_nodes(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t* out_offsets, uint32_t* out_rows,
+                                    uint64_t rows_cap, uint64_t* n_rows) __attribute__((weak));
+
 namespace {
 
 // one spin-wait step that tells the core (and its sibling thread) that this is one
@@ -81,6 +86,12 @@ thread_local size_t t_addr_len = 0;
 thread_local std::vector<std::string> t_snap_store;
 thread_local std::vector<const char*> t_snap_ty, t_snap_id, t_snap_addr;
 thread_local std::vector<size_t> t_snap_tylen, t_snap_idlen;
+
+// rio_op_objects_on_server's arrays, the same way
+thread_local std::vector<std::string> t_on_store;
+thread_local std::vector<const char*> t_on_ty, t_on_id;
+thread_local std::vector<size_t> t_on_tylen, t_on_idlen;
+thread_local std::vector<uint32_t> t_on_rows;
 
 // One single-object call waiting for its device round trip (see run_combined).
 // One single-object call waiting for its device round trip (see run_combined).  The struct is a cache line of its own: its
@@ -1346,6 +1357,56 @@ int rio_op_snapshot(rio_op_t* p, uint64_t* n_out, const char* const** struct_nam
     *struct_names = t_snap_ty.data();
     *object_ids = t_snap_id.data();
     *server_addresses = t_snap_addr.data();
+    return RIO_GP_OK;
+}
+
+int rio_op_objects_on_server(rio_op_t* p, const char* address, uint64_t* n_out, const char* const** struct_names,
+                             const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens) {
+    if (!p || !address || !n_out || !struct_names || !struct_name_lens || !object_ids || !object_id_lens) return RIO_GP_EINVAL;
+    State* s = p->s;
+    t_on_store.clear();
+    t_on_ty.clear(); t_on_id.clear(); t_on_tylen.clear(); t_on_idlen.clear();
+    {
+        DevLock g(s);
+        std::shared_lock<TableLock> gi(s->imu);
+        int rc;
+        if ((rc = sync_device(s, true))) return rc;
+        const auto it = s->nodes.find(address);
+        if (it != s->nodes.end()) {  // (an address never seen holds nothing: 0 objects)
+            if (!rio_gp_rows_on_nodes) return fail(RIO_GP_EUPSTREAM, "dense layer has no reverse index");
+            const uint32_t node = it->second, m = (uint32_t)s->node_addr.size();
+            std::vector<uint64_t> bitmap((m + 63) / 64 + 1, 0), off(m + 1);
+            bitmap[node >> 6] |= 1ull << (node & 63);
+            uint64_t n = 0;
+            // the thread's buffer from its last call first (an empty one: counts only); one more round with the exact size when
+            // it is too small
+            rc = rio_gp_rows_on_nodes(s->gp, bitmap.data(), off.data(), t_on_rows.empty() ? nullptr : t_on_rows.data(),
+                                      t_on_rows.size(), &n);
+            if (rc == RIO_GP_ERANGE || (rc == RIO_GP_OK && n > t_on_rows.size())) {
+                t_on_rows.resize(n);
+                rc = rio_gp_rows_on_nodes(s->gp, bitmap.data(), off.data(), t_on_rows.data(), t_on_rows.size(), &n);
+            }
+            if (rc) return gp_fail(s, rc);
+            // copies: keys can be reclaimed as soon as the locks are released
+            for (uint64_t k = 0; k < n; ++k) {
+                const uint32_t row = t_on_rows[k];
+                if (row >= s->row_live.size() || !s->row_live[row]) continue;
+                t_on_store.push_back(s->row_key[row].first);
+                t_on_store.push_back(s->row_key[row].second);
+            }
+        }
+    }
+    for (size_t k = 0; k + 1 < t_on_store.size(); k += 2) {
+        t_on_ty.push_back(t_on_store[k].data());
+        t_on_tylen.push_back(t_on_store[k].size());
+        t_on_id.push_back(t_on_store[k + 1].data());
+        t_on_idlen.push_back(t_on_store[k + 1].size());
+    }
+    *n_out = t_on_ty.size();
+    *struct_names = t_on_ty.data();
+    *struct_name_lens = t_on_tylen.data();
+    *object_ids = t_on_id.data();
+    *object_id_lens = t_on_idlen.data();
     return RIO_GP_OK;
 }
 

@@ -387,4 +387,33 @@ void launch_shard_tick_stats(const Plan& p, const SolveBufs& b, u64* out_host, u
 void launch_shard_import_delta(const Plan& p, const SolveBufs& b, const u64* Yg, u32 rank, u32 R, u64* gprev,
                                u64* verdict_dev, u64* verdict_host, hipStream_t s);
 
+// --- reverse placement index (rio_gp_rows_on_nodes): count -> scan -> scatter, each pass its own launch ---
+constexpr u32 kNiIdentity = 0, kNiSingle = 1, kNiMap = 2;  // node -> slot: every node selected | one node | map[node] (kNone: not)
+constexpr int kNiMaxWaves = 8;                   // waves per workgroup of the count / scatter passes (NiPlan::W is 4 or 8)
+constexpr u32 kNiChunk = 4096;                   // matrix entries per workgroup of the scan
+constexpr u64 kNiMaxEntries = (u64)1 << 21;      // slots x tiles: the matrix is at most 8 MiB of u32
+constexpr u64 kNiMaxTiles = 8192;
+constexpr u32 kNiMaxParts = (u32)(kNiMaxEntries / kNiChunk);  // chunk sums (+ 1 word: the total)
+struct NiPlan {
+    u64 n;     // rows considered: 0 .. n-1
+    u64 T;     // rows per tile (a multiple of 256; one tile per wave)
+    u32 m;     // nodes
+    u32 s;     // selected nodes = slots
+    u32 mode;  // kNi*
+    u32 node;  // kNiSingle: the one node
+    u32 nt;    // tiles (<= kNiMaxEntries / s)
+    u32 nb;    // bits of a slot id (0 .. 13): ballots per position to rank equal slots
+    u32 cb;    // bytes per LDS counter of the count pass: 2 while T <= 65 535, else 4
+    u32 W;     // waves per workgroup
+};
+NiPlan ni_plan(u64 n, u32 m, u32 s, u32 mode, u32 node, u32 force_tile /* 0: by size */);
+// cnt: kNiMaxEntries u32; map: kNiMap only, m words in device memory
+void launch_ni_count(const u32* assign, const NiPlan& p, const u32* map, u32* cnt, hipStream_t s);
+// part: kNiMaxParts + 1 u32; rank: kNiMap only, m + 1 words in device memory; off: m + 1 u64 (device)
+void launch_ni_scan(u32* cnt, const NiPlan& p, u32* part, const u32* rank, u64* off, hipStream_t s);
+const u32* ni_total(const NiPlan& p, const u32* part);  // device word: rows listed
+// nothing is written when *ni_total > cap
+void launch_ni_scatter(const u32* assign, const NiPlan& p, const u32* map, const u32* cnt, const u32* part, u64 cap, u32* rows,
+                       hipStream_t s);
+
 }  // namespace riogp

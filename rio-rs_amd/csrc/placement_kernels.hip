@@ -18,6 +18,7 @@
 //   * all cross-row decisions are integer sums and index-ordered prefixes: results do not depend
 //     on dispatch order, so the output is bit-identical to the sequential oracle.
 #include "placement_kernels.h"
+#include <algorithm>
 #include <cstdlib>
 
 #include <hip/hip_ext.h>
@@ -5887,5 +5888,249 @@ void launch_shard_import_delta(const Plan& p, const SolveBufs& b, const u64* Yg,
     hipLaunchKernelGGL(k_shard_import_delta, dim3(1), dim3(kBlock), 0, s, Yg, rank, R, p.m, gprev, b.used_cur,
                        b.rank_base, verdict_dev, verdict_host);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Reverse placement index (rio_gp_rows_on_nodes): a stable counting sort of the selected rows by node, three passes, each its
+// own launch — count per wave tile, exclusive scan of the (slot x tile) matrix (reduce, partials, apply), scatter.  The
+// selected nodes are dense slots 0 .. s-1: NiMode says how a node id becomes a slot (identity | the one node | a map).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 ni_key(u32 a, const NiPlan& p, const u32* __restrict__ map) {
+    if (a >= p.m) return kNone;  // RIO_GP_NONE, and any row a shrinking set_nodes left behind
+    if (p.mode == kNiIdentity) return a;
+    if (p.mode == kNiSingle) return a == p.node ? 0u : kNone;
+    return map[a];
+}
+// lanes whose key equals this lane's (this lane included when its key is valid): the valid ballot, then one ballot per key bit
+template <int NB>
+__device__ __forceinline__ u64 ni_peers(u32 key) {
+    u64 eq = __ballot(key != kNone);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const u32 bit = (key >> b) & 1u;
+        const u64 bb = __ballot(bit);
+        eq &= bit ? bb : ~bb;
+    }
+    return eq;
+}
+// peers of `key` among the keys OTHER lanes hold in one of their four positions (ballots of that position's bits; the key may be
+// any lane's value of any position)
+template <int NB>
+__device__ __forceinline__ u64 ni_match(u32 key, u64 valid, const u64 (&bits)[NB > 0 ? NB : 1]) {
+    u64 eq = valid;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) eq &= ((key >> b) & 1u) ? bits[b] : ~bits[b];
+    return eq;
+}
+
+// Pass 1: wave w of the grid counts the selected rows of tile w (rows [w T, min((w+1) T, n))) per slot in LDS (C = u16 while a tile
+// has at most 65 535 rows) and writes the counts node-major: cnt[slot * nt + tile].  Equal slots are aggregated inside the wave
+// first (one LDS add per distinct slot and position), so a table whose rows all sit on one node does not serialise on one address.
+template <int NB, typename C>
+__global__ __launch_bounds__(kNiMaxWaves * 64) void k_ni_count(const u32* __restrict__ assign, const NiPlan p,
+                                                               const u32* __restrict__ map, u32* __restrict__ cnt) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u32 tile = blockIdx.x * p.W + wv;
+    if (tile >= p.nt) return;  // (no workgroup barrier below: every wave owns its own counters)
+    C* c = reinterpret_cast<C*>(smem) + (size_t)wv * p.s;
+    for (u32 k = lane; k < p.s; k += 64) c[k] = 0;
+    __builtin_amdgcn_wave_barrier();
+    const u64 lo = (u64)tile * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
+    for (u64 b0 = lo; b0 < hi; b0 += 256) {  // wave-uniform
+        const u64 i0 = b0 + lane * 4;
+        const uint4 a = i0 < hi ? *reinterpret_cast<const uint4*>(assign + i0) : make_uint4(kNone, kNone, kNone, kNone);
+        const u32 k[4] = {ni_key(a.x, p, map), i0 + 1 < hi ? ni_key(a.y, p, map) : kNone,
+                          i0 + 2 < hi ? ni_key(a.z, p, map) : kNone, i0 + 3 < hi ? ni_key(a.w, p, map) : kNone};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const u64 eq = ni_peers<NB>(k[j]);
+            if (k[j] != kNone && lane == (u32)__builtin_ctzll(eq)) c[k[j]] = (C)(c[k[j]] + (C)__builtin_popcountll(eq));
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (u32 k = lane; k < p.s; k += 64) cnt[(u64)k * p.nt + tile] = c[k];
+}
+
+// Pass 2a: sums of chunks of kNiChunk matrix entries
+__global__ __launch_bounds__(256) void k_ni_reduce(const u32* __restrict__ cnt, u64 E, u32* __restrict__ part) {
+    __shared__ u32 ws[4];
+    const u64 base = (u64)blockIdx.x * kNiChunk + threadIdx.x * (kNiChunk / 256);
+    u32 v = 0;
+#pragma unroll
+    for (int q = 0; q < (int)(kNiChunk / 256); ++q) v += base + q < E ? cnt[base + q] : 0u;
+    v = wave_sum32(v);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+}
+// exclusive scan of one value per thread across a workgroup of 256 (lds: 4 words); returns the workgroup total in *tot
+__device__ __forceinline__ u32 ni_block_excl(u32 v, u32* lds, u32* tot) {
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    u32 inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u32 t = __shfl_up(inc, d);
+        if (lane >= (u32)d) inc += t;
+    }
+    if (lane == 63) lds[wv] = inc;
+    __syncthreads();
+    u32 before = 0;
+    for (u32 w = 0; w < wv; ++w) before += lds[w];
+    *tot = lds[0] + lds[1] + lds[2] + lds[3];
+    __syncthreads();
+    return before + inc - v;
+}
+// Pass 2b: exclusive scan of the chunk sums (P <= kNiMaxParts, one workgroup); part[P] = the total
+__global__ __launch_bounds__(256) void k_ni_scan_parts(u32* __restrict__ part, u32 P) {
+    __shared__ u32 lds[4];
+    constexpr u32 per = kNiMaxParts / 256;
+    u32 v[per], sum = 0;
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) { const u32 i = threadIdx.x * per + q; v[q] = i < P ? part[i] : 0u; sum += v[q]; }
+    u32 tot;
+    u32 run = ni_block_excl(sum, lds, &tot);
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) { const u32 i = threadIdx.x * per + q; if (i < P) part[i] = run; run += v[q]; }
+    if (threadIdx.x == 0) part[P] = tot;
+}
+// Pass 2c: the chunk's entries become their exclusive prefix in (slot, tile) order: the first output position of each tile's rows
+// of each slot
+__global__ __launch_bounds__(256) void k_ni_scan_apply(u32* __restrict__ cnt, u64 E, const u32* __restrict__ part) {
+    __shared__ u32 lds[4];
+    constexpr u32 per = kNiChunk / 256;
+    const u64 base = (u64)blockIdx.x * kNiChunk + threadIdx.x * per;
+    u32 v[per], sum = 0;
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) { v[q] = base + q < E ? cnt[base + q] : 0u; sum += v[q]; }
+    u32 tot;
+    u32 run = part[blockIdx.x] + ni_block_excl(sum, lds, &tot);
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) if (base + q < E) { cnt[base + q] = run; run += v[q]; }
+}
+// offsets[j], j = 0..m: the first position of node j's rows = the scanned entry (rank(j), tile 0), rank(j) = selected nodes below
+// j (an unselected node: an empty range at the next selected node's start); rank(j) >= s: the total
+__global__ __launch_bounds__(256) void k_ni_offsets(const u32* __restrict__ cnt, const NiPlan p, const u32* __restrict__ rank,
+                                                    const u32* __restrict__ total, u64* __restrict__ off) {
+    const u32 j = blockIdx.x * 256 + threadIdx.x;
+    if (j > p.m) return;
+    const u32 r = p.mode == kNiIdentity ? j : p.mode == kNiSingle ? (j <= p.node ? 0u : 1u) : rank[j];
+    off[j] = r < p.s ? (u64)cnt[(u64)r * p.nt] : (u64)*total;
+}
+
+// Pass 3: wave w walks tile w in row order, 256 rows a step (lane l holds rows 4l .. 4l+3), keeping the next output position
+// of every slot in LDS (the tile's scanned entries to begin with).  A row's rank among the step's rows of its slot = the rows
+// of that slot in lower lanes (ballots over the slot bits of each of the four positions) + those of its own lane in front of it.
+// The first row of a slot in the step advances the slot's position by the step's count.  Nothing is written when the listing
+// does not fit: *total > cap (the host reports RIO_GP_ERANGE).
+template <int NB>
+__global__ __launch_bounds__(kNiMaxWaves * 64) void k_ni_scatter(const u32* __restrict__ assign, const NiPlan p,
+                                                                 const u32* __restrict__ map, const u32* __restrict__ cnt,
+                                                                 const u32* __restrict__ total, u64 cap, u32* __restrict__ rows) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if ((u64)*total > cap) return;
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u32 tile = blockIdx.x * p.W + wv;
+    if (tile >= p.nt) return;
+    u32* c = reinterpret_cast<u32*>(smem) + (size_t)wv * p.s;
+    for (u32 k = lane; k < p.s; k += 64) c[k] = cnt[(u64)k * p.nt + tile];
+    __builtin_amdgcn_wave_barrier();
+    const u64 lt = (1ull << lane) - 1ull;
+    const u64 lo = (u64)tile * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
+    for (u64 b0 = lo; b0 < hi; b0 += 256) {  // wave-uniform
+        const u64 i0 = b0 + lane * 4;
+        const uint4 a = i0 < hi ? *reinterpret_cast<const uint4*>(assign + i0) : make_uint4(kNone, kNone, kNone, kNone);
+        const u32 k[4] = {ni_key(a.x, p, map), i0 + 1 < hi ? ni_key(a.y, p, map) : kNone,
+                          i0 + 2 < hi ? ni_key(a.z, p, map) : kNone, i0 + 3 < hi ? ni_key(a.w, p, map) : kNone};
+        u32 below[4] = {0, 0, 0, 0}, all[4] = {0, 0, 0, 0};
+        u64 where[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {  // position q of every lane
+            const u64 valid = __ballot(k[q] != kNone);
+            u64 bits[NB > 0 ? NB : 1];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) bits[b] = __ballot((k[q] >> b) & 1u);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const u64 eq = ni_match<NB>(k[j], valid, bits);
+                below[j] += __builtin_popcountll(eq & lt);
+                all[j] += __builtin_popcountll(eq);
+                where[j] |= eq;
+            }
+        }
+        u32 pos[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pos[j] = k[j] != kNone ? c[k[j]] : 0u;
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (k[j] == kNone) continue;
+            u32 own = 0;
+#pragma unroll
+            for (int q = 0; q < j; ++q) own += k[q] == k[j];
+            const u64 r = (u64)pos[j] + below[j] + own;
+            if (r < cap) rows[r] = (u32)(i0 + j);
+            if (own == 0 && lane == (u32)__builtin_ctzll(where[j])) c[k[j]] = pos[j] + all[j];
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+NiPlan ni_plan(u64 n, u32 m, u32 s, u32 mode, u32 node, u32 force_tile) {
+    NiPlan p{};
+    p.n = n; p.m = m; p.s = s; p.mode = mode; p.node = node;
+    p.nb = s > 1 ? 32u - (u32)__builtin_clz(s - 1) : 0u;
+    // tiles: at least 1 024 rows each, at most kNiMaxTiles of them, and the matrix within kNiMaxEntries
+    u64 nt = (n + 1023) / 1024;
+    const u64 nt_cap = std::max<u64>(1, std::min<u64>(kNiMaxTiles, kNiMaxEntries / (s ? s : 1)));
+    if (nt > nt_cap) nt = nt_cap;
+    if (nt < 1) nt = 1;
+    u64 T = ((n + nt - 1) / nt + 255) / 256 * 256;
+    if (force_tile) {  // lab builds: a tile size of the caller's (rounded to the step), never more tiles than the bound allows
+        const u64 f = ((u64)force_tile + 255) / 256 * 256;
+        if (f > T) T = f;
+    }
+    if (T < 256) T = 256;
+    p.T = T;
+    p.nt = (u32)std::max<u64>(1, (n + T - 1) / T);
+    p.cb = T <= 65535 ? 2u : 4u;
+    p.W = (u64)s * 4 * 8 <= 64 * 1024 ? 8u : 4u;  // the scatter's u32 positions: 8 waves up to 2 048 slots, 4 beyond (128 KiB)
+    return p;
+}
+
+#define RIOGP_NI_NB(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13)
+void launch_ni_count(const u32* assign, const NiPlan& p, const u32* map, u32* cnt, hipStream_t s) {
+    const dim3 g((p.nt + p.W - 1) / p.W), b(p.W * 64);
+    const size_t lds = (size_t)p.W * p.s * p.cb;
+    switch (p.nb * 2 + (p.cb == 4)) {
+#define RIOGP_NI_C(NB)                                                                                                 \
+    case NB * 2: hipLaunchKernelGGL((k_ni_count<NB, unsigned short>), g, b, lds, s, assign, p, map, cnt); break;     \
+    case NB * 2 + 1: hipLaunchKernelGGL((k_ni_count<NB, u32>), g, b, lds, s, assign, p, map, cnt); break;
+        RIOGP_NI_NB(RIOGP_NI_C)
+#undef RIOGP_NI_C
+    }
+}
+void launch_ni_scan(u32* cnt, const NiPlan& p, u32* part, const u32* rank, u64* off, hipStream_t s) {
+    const u64 E = (u64)p.s * p.nt;
+    const u32 P = (u32)((E + kNiChunk - 1) / kNiChunk);
+    hipLaunchKernelGGL(k_ni_reduce, dim3(P), dim3(256), 0, s, cnt, E, part);
+    hipLaunchKernelGGL(k_ni_scan_parts, dim3(1), dim3(256), 0, s, part, P);
+    hipLaunchKernelGGL(k_ni_scan_apply, dim3(P), dim3(256), 0, s, cnt, E, part);
+    hipLaunchKernelGGL(k_ni_offsets, dim3((p.m + 1 + 255) / 256), dim3(256), 0, s, cnt, p, rank, part + P, off);
+}
+const u32* ni_total(const NiPlan& p, const u32* part) { return part + ((u64)p.s * p.nt + kNiChunk - 1) / kNiChunk; }
+void launch_ni_scatter(const u32* assign, const NiPlan& p, const u32* map, const u32* cnt, const u32* part, u64 cap, u32* rows,
+                       hipStream_t s) {
+    const dim3 g((p.nt + p.W - 1) / p.W), b(p.W * 64);
+    const size_t lds = (size_t)p.W * p.s * sizeof(u32);
+    const u32* total = ni_total(p, part);
+    switch (p.nb) {
+#define RIOGP_NI_S(NB) \
+    case NB: hipLaunchKernelGGL((k_ni_scatter<NB>), g, b, lds, s, assign, p, map, cnt, total, cap, rows); break;
+        RIOGP_NI_NB(RIOGP_NI_S)
+#undef RIOGP_NI_S
+    }
+}
+#undef RIOGP_NI_NB
 
 }  // namespace riogp

@@ -284,6 +284,13 @@ struct rio_gp {
     bool timer_stopped = false;  // rio_gp_timer_stop has recorded the closing event of the measurement in progress
     u32 sh_tick_n = 0;    // asynchronous row-sharded ticks in flight (their records: verdict slots of the tick ring, h_fx slots)
     u64 sh_tick_mark[kRing] = {};
+    // reverse placement index (rio_gp_rows_on_nodes), allocated on first use: the (slot x tile) matrix, chunk sums + total, the
+    // node -> slot map on the device, the offsets of the host-pointer form; the map and the ranks are built in mapped pinned memory
+    u32 *ni_cnt = nullptr, *ni_part = nullptr, *ni_map = nullptr;
+    u64* ni_off = nullptr;
+    u32 *h_ni = nullptr, *d_ni = nullptr;  // [RIO_GP_MAX_NODES] map | [RIO_GP_MAX_NODES + 1] ranks | [1] total read back
+    DevBuf ni_rows;                        // the host-pointer form's listing (grows to the largest answer: 4 B per listed row)
+    u32 ni_force_tile = 0;                 // lab builds: rows per tile (rio_gp_debug_set_node_index)
     std::vector<void*> allocs;
 };
 
@@ -1152,6 +1159,8 @@ void rio_gp_destroy(rio_gp_t* h) {
     for (auto& b : h->rq) if (b.p) (void)hipFree(b.p);
     if (h->vrec.p) (void)hipFree(h->vrec.p);
     if (h->part.p) (void)hipFree(h->part.p);
+    if (h->ni_rows.p) (void)hipFree(h->ni_rows.p);
+    if (h->h_ni) (void)hipHostFree(h->h_ni);
     if (h->h_stats) (void)hipHostFree(h->h_stats);
     if (h->h_chain_err) (void)hipHostFree(h->h_chain_err);
     if (h->h_slots) (void)hipHostFree(h->h_slots);
@@ -1379,6 +1388,113 @@ int rio_gp_count_placed(rio_gp_t* h, uint64_t* out) {
     launch_count_placed(h->assign[h->cur], h->n, h->dstats, h->stream);
     if ((rc = read_stats(h))) return rc;
     *out = h->h_stats[0].evicted_clean;
+    return RIO_GP_OK;
+}
+
+// ---- reverse placement index --------------------------------------------------------------
+
+// The scratch of rio_gp_rows_on_nodes, on first use: kNiMaxEntries u32 of matrix (8 MiB), kNiMaxParts + 1 chunk sums, the map (32 KiB),
+// RIO_GP_MAX_NODES + 1 offsets (64 KiB), and 2 * RIO_GP_MAX_NODES + 2 words of mapped pinned memory.  Fixed sizes: they hold for every (n, m).
+static int ni_scratch(rio_gp* h) {
+    if (h->ni_cnt) return RIO_GP_OK;
+    int rc;
+    if ((rc = dalloc(h, &h->ni_part, kNiMaxParts + 1)) || (rc = dalloc(h, &h->ni_map, RIO_GP_MAX_NODES)) ||
+        (rc = dalloc(h, &h->ni_off, RIO_GP_MAX_NODES + 1)))
+        return rc;
+    if (!h->h_ni) {
+        if (hipHostMalloc(reinterpret_cast<void**>(&h->h_ni), (2 * RIO_GP_MAX_NODES + 2) * sizeof(u32), hipHostMallocMapped) !=
+                hipSuccess ||
+            hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_ni), h->h_ni, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, RIO_GP_ENOMEM, "hipHostMalloc(node index map) failed");
+        }
+    }
+    if ((rc = dalloc(h, &h->ni_cnt, kNiMaxEntries))) return rc;  // (last: it is what says the scratch is complete)
+    if (!h->ni_part || !h->ni_map || !h->ni_off || !h->d_ni) {
+        h->ni_cnt = nullptr;
+        return fail(h, RIO_GP_ENOMEM, "rio_gp_rows_on_nodes: scratch allocation failed");
+    }
+    return RIO_GP_OK;
+}
+
+// Count (and scan) the selected rows of the committed column; offsets into `off` (device).  Leaves the plan in *p (p->s == 0 or
+// p->n == 0: nothing was launched, the offsets are zeros).
+// (the scratch must exist: ni_scratch first — `off` may be h->ni_off)
+static int ni_count_scan(rio_gp* h, const uint64_t* node_bitmap, u64* off, NiPlan* p) {
+    const u32 m = h->m;
+    u32* map = h->h_ni;
+    u32* rank = h->h_ni + RIO_GP_MAX_NODES;
+    u32 s = 0, single = 0;
+    for (u32 j = 0; j < m; ++j) {
+        rank[j] = s;
+        const bool sel = !node_bitmap || ((node_bitmap[j >> 6] >> (j & 63)) & 1ull);
+        map[j] = sel ? s : kNone;
+        if (sel) { single = j; ++s; }
+    }
+    rank[m] = s;
+    const u32 mode = s == m ? kNiIdentity : s == 1 ? kNiSingle : kNiMap;
+    *p = ni_plan(h->n, m, s, mode, single, h->ni_force_tile);
+    if (s == 0 || h->n == 0) {  // nothing to list: the offsets are zeros
+        p->s = 0;
+        launch_fill_u32(reinterpret_cast<u32*>(off), 2 * ((u64)m + 1), 0, h->stream);
+        HIPCHK(h, hipGetLastError());
+        return RIO_GP_OK;
+    }
+    if (mode == kNiMap) HIPCHK(h, hipMemcpyAsync(h->ni_map, map, (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    launch_ni_count(h->assign[h->cur], *p, h->ni_map, h->ni_cnt, h->stream);
+    launch_ni_scan(h->ni_cnt, *p, h->ni_part, h->d_ni + RIO_GP_MAX_NODES, off, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return RIO_GP_OK;
+}
+
+static int ni_erange(rio_gp* h, u64 total, u64 cap) {
+    return fail(h, RIO_GP_ERANGE, "rio_gp_rows_on_nodes: " + std::to_string(total) + " rows do not fit rows_cap = " + std::to_string(cap));
+}
+
+// Read-only: nothing here changes the tables, the epochs, `used` or the chain; it reads the column rio_gp_get_assign reads.
+int rio_gp_rows_on_nodes(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t* out_offsets, uint32_t* out_rows, uint64_t rows_cap,
+                         uint64_t* n_rows) {
+    if (!h || !out_offsets || !n_rows || (!out_rows && rows_cap)) return RIO_GP_EINVAL;
+    Locked g(h);
+    HIPCHK(h, hipSetDevice(h->device));
+    NiPlan p;
+    int rc;
+    if ((rc = ni_scratch(h)) || (rc = ni_count_scan(h, node_bitmap, h->ni_off, &p))) return rc;
+    const u32 m = h->m;
+    HIPCHK(h, hipMemcpyAsync(out_offsets, h->ni_off, (size_t)(m + 1) * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 total = out_offsets[m];
+    *n_rows = total;
+    if (!out_rows || total == 0) return RIO_GP_OK;  // counts only (or nothing to list)
+    if (total > rows_cap) return ni_erange(h, total, rows_cap);
+    if ((rc = ensure(h, h->ni_rows, total * sizeof(u32)))) return rc;
+    launch_ni_scatter(h->assign[h->cur], p, h->ni_map, h->ni_cnt, h->ni_part, total, (u32*)h->ni_rows.p, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out_rows, h->ni_rows.p, total * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RIO_GP_OK;
+}
+
+int rio_gp_rows_on_nodes_dev(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t* d_offsets, uint32_t* d_rows, uint64_t rows_cap,
+                             uint64_t* n_rows) {
+    if (!h || !d_offsets || !n_rows || (!d_rows && rows_cap)) return RIO_GP_EINVAL;
+    Locked g(h);
+    HIPCHK(h, hipSetDevice(h->device));
+    NiPlan p;
+    int rc;
+    if ((rc = ni_scratch(h)) || (rc = ni_count_scan(h, node_bitmap, reinterpret_cast<u64*>(d_offsets), &p))) return rc;
+    u32* h_total = h->h_ni + 2 * RIO_GP_MAX_NODES + 1;
+    *h_total = 0;
+    if (p.s) {
+        // the scatter checks the total against rows_cap on the device: one wait for the whole call
+        if (d_rows) launch_ni_scatter(h->assign[h->cur], p, h->ni_map, h->ni_cnt, h->ni_part, rows_cap, d_rows, h->stream);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(h_total, ni_total(p, h->ni_part), sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 total = *h_total;
+    *n_rows = total;
+    if (d_rows && total > rows_cap) return ni_erange(h, total, rows_cap);
     return RIO_GP_OK;
 }
 
@@ -2876,6 +2992,21 @@ uint64_t rio_gp_debug_chained_scans(rio_gp_t* h) {
     return h->chain_total;
 }
 
+int rio_gp_debug_set_node_index(rio_gp_t* h, uint32_t tile_rows) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    h->ni_force_tile = tile_rows;
+    return RIO_GP_OK;
+}
+int rio_gp_debug_node_index_geometry(rio_gp_t* h, const uint64_t* node_bitmap, uint32_t* out4) {
+    if (!h || !out4) return RIO_GP_EINVAL;
+    Locked g(h);
+    u32 s = 0;
+    for (u32 j = 0; j < h->m; ++j) s += !node_bitmap || ((node_bitmap[j >> 6] >> (j & 63)) & 1ull);
+    const NiPlan p = ni_plan(h->n, h->m, s, 0, 0, h->ni_force_tile);
+    out4[0] = (u32)p.T; out4[1] = p.nt; out4[2] = p.cb; out4[3] = p.W;
+    return RIO_GP_OK;
+}
 int rio_gp_debug_set_speculate(rio_gp_t* h, int speculate) {
     if (!h || speculate < 0 || speculate > 2) return RIO_GP_EINVAL;
     Locked g(h);

@@ -158,6 +158,8 @@ def _load(lab):
         L.rio_gp_set_num_objects.argtypes = [_vp, C.c_uint64]
         L.rio_gp_place_pending_dev.argtypes = [_vp, C.c_uint64, _vp, _vp, _vp, _vp]
         L.rio_gp_mixed_batch.argtypes = [_vp, C.POINTER(Mixed)]
+        for nm in ("rio_gp_rows_on_nodes", "rio_gp_rows_on_nodes_dev"):
+            getattr(L, nm).argtypes = [_vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]
         if lab:
             L.rio_gp_debug_set_scan_nt.argtypes = [C.c_int]
             L.rio_gp_debug_set_scan_nt.restype = None
@@ -171,6 +173,8 @@ def _load(lab):
             L.rio_gp_debug_ktrace.argtypes = [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
             L.rio_gp_debug_wave_row_lo.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
             L.rio_gp_debug_wave_row_lo.restype = C.c_uint64
+            L.rio_gp_debug_set_node_index.argtypes = [_vp, C.c_uint32]
+            L.rio_gp_debug_node_index_geometry.argtypes = [_vp, _vp, _vp]
         L.rio_gp_timer_begin.argtypes = [_vp]
         L.rio_gp_timer_stop.argtypes = [_vp]
         L.rio_gp_timer_end.argtypes = [_vp, C.POINTER(C.c_float)]
@@ -320,6 +324,66 @@ class GpuPlacement:
         self._chk(self._L.rio_gp_clean_servers(self._h, _ptr(bm), C.byref(ev)))
         return int(ev.value)
 
+    # -- reverse index (rows per node) --
+    def _node_bitmap(self, nodes):
+        """None -> NULL (every node); else the words of a bitmap with bit j set for every j in `nodes` (ids >= m allowed:
+        ignored by the library)."""
+        if nodes is None:
+            return None
+        nodes = np.asarray(list(nodes), np.int64)
+        top = int(nodes.max()) + 1 if len(nodes) else 0
+        bits = np.zeros((max(top, self.num_nodes) // 64 + 2) * 64, np.uint8)
+        bits[nodes] = 1
+        return np.packbits(bits, bitorder="little").view(np.uint64)
+
+    def rows_on_nodes(self, nodes=None, _cap=None):
+        """rio_gp_rows_on_nodes: (offsets[m + 1] uint64, rows uint32) — node j's rows, ascending, are
+        rows[offsets[j]:offsets[j + 1]]; nodes = iterable of node ids (None: every node).  One call when the listing fits the
+        first guess (the rows ever listed by this handle, at least 4 096), else the RIO_GP_ERANGE round and a second call."""
+        bm = self._node_bitmap(nodes)
+        off = np.empty(self.num_nodes + 1, np.uint64)
+        cap = int(_cap) if _cap is not None else max(4096, getattr(self, "_ni_guess", 0))
+        n = C.c_uint64(0)
+        while True:
+            rows = np.empty(cap, np.uint32)
+            rc = self._L.rio_gp_rows_on_nodes(self._h, _ptr(bm), _ptr(off), _ptr(rows), cap, C.byref(n))
+            if rc == ERANGE:
+                cap = int(n.value)
+                continue
+            self._chk(rc)
+            self._ni_guess = max(getattr(self, "_ni_guess", 0), int(n.value))
+            return off, rows[:int(n.value)]
+
+    def rows_on_nodes_try(self, nodes, rows):
+        """One rio_gp_rows_on_nodes call into a caller-held uint32 array: (rc, offsets, n_rows) — rc OK or ERANGE (then `rows` is
+        untouched)."""
+        bm = self._node_bitmap(nodes)
+        off = np.empty(self.num_nodes + 1, np.uint64)
+        n = C.c_uint64(0)
+        rc = self._L.rio_gp_rows_on_nodes(self._h, _ptr(bm), _ptr(off), _ptr(rows), len(rows), C.byref(n))
+        if rc not in (OK, ERANGE):
+            self._chk(rc)
+        return rc, off, int(n.value)
+
+    def count_on_nodes(self, nodes=None):
+        """Counts only: offsets[m + 1] (node j holds offsets[j + 1] - offsets[j] rows); no listing."""
+        bm = self._node_bitmap(nodes)
+        off = np.empty(self.num_nodes + 1, np.uint64)
+        n = C.c_uint64(0)
+        self._chk(self._L.rio_gp_rows_on_nodes(self._h, _ptr(bm), _ptr(off), None, 0, C.byref(n)))
+        return off
+
+    def rows_on_nodes_dev(self, d_offsets, d_rows, rows_cap, nodes=None):
+        """Device pointers (ints): d_offsets m + 1 u64, d_rows rows_cap u32 (0 / 0: counts only).  Returns (rc, n_rows): rc OK,
+        or ERANGE when the listing does not fit (d_rows untouched, the offsets written)."""
+        bm = self._node_bitmap(nodes)
+        n = C.c_uint64(0)
+        rc = self._L.rio_gp_rows_on_nodes_dev(self._h, _ptr(bm), _vp(d_offsets), _vp(d_rows) if d_rows else None, rows_cap,
+                                              C.byref(n))
+        if rc not in (OK, ERANGE):
+            self._chk(rc)
+        return rc, int(n.value)
+
     # -- policy --
     def place_pending(self, idx, requester):
         idx, requester = _u32(idx), _u32(requester)
@@ -443,6 +507,18 @@ class GpuPlacement:
         self._need_lab()
         return int(self._L.rio_gp_debug_chained_scans(self._h))
 
+    def set_node_index(self, tile_rows=0):
+        """rows per wave tile of rio_gp_rows_on_nodes (0: by table size); geometry of the reverse index for a selection."""
+        self._need_lab()
+        self._chk(self._L.rio_gp_debug_set_node_index(self._h, int(tile_rows)))
+
+    def node_index_geometry(self, nodes=None):
+        """(rows per tile, tiles, bytes per count-pass counter, waves per workgroup) of the next rows_on_nodes(nodes)."""
+        self._need_lab()
+        out = np.zeros(4, np.uint32)
+        self._chk(self._L.rio_gp_debug_node_index_geometry(self._h, _ptr(self._node_bitmap(nodes)), _ptr(out)))
+        return tuple(int(x) for x in out)
+
     def set_speculate(self, speculate="auto"):
         """speculative enqueue of the fix-up behind k_resolve: auto | always | never (results identical in every mode)."""
         self._need_lab()
@@ -517,6 +593,9 @@ def _oplib():
         L.rio_op_tick.argtypes = [_vp, C.POINTER(Stats)]
         L.rio_op_snapshot.argtypes = [_vp, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_char_p)),
                                       C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_char_p))]
+        L.rio_op_objects_on_server.argtypes = [_vp, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_char_p)),
+                                               C.POINTER(C.POINTER(C.c_size_t)), C.POINTER(C.POINTER(C.c_char_p)),
+                                               C.POINTER(C.POINTER(C.c_size_t))]
         L.rio_op_dense.argtypes = [_vp]
         L.rio_op_dense.restype = _vp
         L.rio_op_invalidate_cache.argtypes = [_vp]
@@ -706,3 +785,14 @@ class GpuObjectPlacement:
         tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))   # (c_char_p would stop at a NUL)
         return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), addr[k].decode())
                 for k in range(n.value)]
+
+    def objects_on_server(self, address):
+        """rio_op_objects_on_server: every (struct_name, object_id) placed on `address` (the reverse index; [] for an address
+        never seen), key lengths read as snapshot() does."""
+        n = C.c_uint64(0)
+        ty, oid = C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)()
+        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+        self._chk(_oplib().rio_op_objects_on_server(self._h, address.encode(), C.byref(n), C.byref(ty), C.byref(tl), C.byref(oid),
+                                                    C.byref(il)))
+        tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
+        return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode()) for k in range(n.value)]
