@@ -137,6 +137,18 @@ int rio_op_snapshot(rio_op_t* p, uint64_t* n_out, const char* const** struct_nam
 int rio_op_objects_on_server(rio_op_t* p, const char* address, uint64_t* n_out, const char* const** struct_names,
                              const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens);
 
+/* Bounded rebalance (rio_gp_rebalance, DESIGN.md section 2 "rebalance"): moves at most max_moves objects (~0: no limit) off
+ * the servers that hold more load than their capacity — the capacity given to rio_op_set_member — onto servers with room, in
+ * the dense layer's row order; objects of servers that are not active members do not move, and nothing is placed, evicted or
+ * removed.  The moved objects come back with their old and new addresses; the arrays are owned by the calling thread until its
+ * next call of this function, as rio_op_snapshot's (a key may hold NUL bytes: its lengths come with it).  The call takes the
+ * write side of the table lock and invalidates the host shadow, so no later lookup answers a moved object with its old
+ * address.  To spread onto a server that joined empty (scale-out), lower the members' capacities to the level wanted
+ * (rio_op_set_member), rebalance, then restore them.  A dense layer without the rebalance: RIO_GP_EUPSTREAM. */
+int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const char* const** struct_names,
+                     const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens,
+                     const char* const** from_addresses, const char* const** to_addresses);
+
 /* Keys with their lengths.  ObjectId(String, String) (service_object.rs:19-26) holds any Rust string, a NUL byte included;
  * the entry points above take NUL-terminated strings and would cut such a key short.  These take struct_name / object_id
  * as (pointer, length) and are otherwise the same calls (the Rust adapter binds THESE: rio-rs_amd/rust/src/gpu.rs).

@@ -236,6 +236,50 @@ int rio_gp_rows_on_nodes(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t* out
 int rio_gp_rows_on_nodes_dev(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t* d_offsets, uint32_t* d_rows,
                              uint64_t rows_cap, uint64_t* n_rows);
 
+/* ---- bounded rebalance: move objects off nodes over their load target ------------------------ */
+
+typedef struct rio_gp_rebalance_cfg {
+    uint32_t struct_size;    /* = sizeof(rio_gp_rebalance_cfg); ABI guard */
+    uint32_t rounds;         /* water-fill rounds; 0 = the handle's spill_rounds; <= 8 */
+    uint64_t max_moves;      /* B: rows selected at most; ~0 = no limit */
+    const uint64_t* target;  /* host array of m u64 (T[j]; ~0 = never over); NULL = the capacities */
+} rio_gp_rebalance_cfg;
+
+typedef struct rio_gp_rebalance_stats {
+    uint64_t surplus_rows, surplus_load;          /* R1: candidates beyond the cut of their node */
+    uint64_t selected_rows, selected_load;        /* R2: the first B of them */
+    uint64_t moved_rows, moved_load;              /* rows whose node changed */
+    uint64_t stayed_rows;                         /* selected, no place found: kept where they were (R4) */
+    uint32_t nodes_over_before, nodes_over_after; /* live nodes j with used[j] > T[j] */
+} rio_gp_rebalance_stats;
+
+/* Bounded rebalance of the COMMITTED column ("rebalance"): the rule is the sticky rule's missing half —
+ * capacity is enforced on objects already placed.  A row on a live node is a candidate (an object) or pinned (a non-object,
+ * affinity RIO_GP_AFF_INACTIVE); every other row (unplaced, on a dead node, on a node >= m) is left exactly as it is.
+ *   R1  per live node j, free_j = T[j] -sat (pinned load on j); j's candidates in row order are kept while the inclusive prefix
+ *       of their loads stays <= free_j; the first that overflows and every later one are surplus.
+ *   R2  the first B surplus rows in row order are selected.
+ *   R3  the selected rows are water-filled in row order exactly as in rule 3, with free = T -sat used' on live nodes (used' =
+ *       the load of every row that is not selected) in place of cap - used, `rounds` rounds; a row's own node is a legal target.
+ *   R4  a selected row that finds no node keeps its node.
+ * Nothing else changes (load, affinity, row lifecycle, n); `used` is the one of the new column on return.  It never places,
+ * evicts or cleans: that is the tick's and clean_server's work.
+ *   - out_rows / out_from / out_to: the moves (rows whose node changed), ascending by row, with the old and the new node; the
+ *     three are given together or not at all (RIO_GP_EINVAL).  With them B = min(max_moves, moves_cap), so the listing always
+ *     fits; without them moves_cap must be 0.  *n_moves (may be NULL) = the number of moves.  st may be NULL.
+ *   - RIO_GP_EINVAL (nothing changed): bad cfg / struct_size, rounds > 8, the output rule above, or a handle of the row-sharded
+ *     solve (rio_gp_shard_*, rio_gp_p2p_*; rebalancing across row shards is not implemented).
+ *   - Like rio_gp_update_batch: it joins rio_gp_tick_async work in flight, drops an uncommitted rio_gp_solve, and counts as a
+ *     change of the inputs (the next tick takes neither the quiet nor the chained form over the old column).
+ *   - Cost: one streaming pass over the column, load and affinity when no live node is over its target; otherwise three more
+ *     passes over the table and a few over the selected rows.  Scratch grows with the first calls and is kept until
+ *     rio_gp_destroy.
+ * The _dev form takes device pointers for the three move arrays. */
+int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebalance_stats* st, uint32_t* out_rows,
+                     uint32_t* out_from, uint32_t* out_to, uint64_t moves_cap, uint64_t* n_moves);
+int rio_gp_rebalance_dev(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebalance_stats* st, uint32_t* d_rows,
+                         uint32_t* d_from, uint32_t* d_to, uint64_t moves_cap, uint64_t* n_moves);
+
 /* ---- the placement policy, batched ------------------------------------------------------ */
 
 /* Service::get_or_create_placement + check_address_mismatch (service.rs:193-298) for a batch

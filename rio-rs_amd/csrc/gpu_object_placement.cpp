@@ -56,6 +56,9 @@
 // without a GPU need not define it (rio_op_objects_on_server reports RIO_GP_EUPSTREAM then).
 extern "C" int rio_gp_rows_on_nodes(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t* out_offsets, uint32_t* out_rows,
                                     uint64_t rows_cap, uint64_t* n_rows) __attribute__((weak));
+// Weak for the same reason: the bounded rebalance (rio_op_rebalance reports RIO_GP_EUPSTREAM without it).
+extern "C" int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebalance_stats* st, uint32_t* out_rows,
+                                uint32_t* out_from, uint32_t* out_to, uint64_t moves_cap, uint64_t* n_moves) __attribute__((weak));
 
 namespace {
 
@@ -92,6 +95,12 @@ thread_local std::vector<std::string> t_on_store;
 thread_local std::vector<const char*> t_on_ty, t_on_id;
 thread_local std::vector<size_t> t_on_tylen, t_on_idlen;
 thread_local std::vector<uint32_t> t_on_rows;
+
+// rio_op_rebalance's arrays, the same way (keys, then the two addresses, as copies)
+thread_local std::vector<std::string> t_rb_store;
+thread_local std::vector<const char*> t_rb_ty, t_rb_id, t_rb_from, t_rb_to;
+thread_local std::vector<size_t> t_rb_tylen, t_rb_idlen;
+thread_local std::vector<uint32_t> t_rb_rows, t_rb_src, t_rb_dst;
 
 // One single-object call waiting for its device round trip (see run_combined).
 // One single-object call waiting for its device round trip (see run_combined).  The struct is a cache line of its own: its
@@ -1407,6 +1416,58 @@ int rio_op_objects_on_server(rio_op_t* p, const char* address, uint64_t* n_out, 
     *struct_name_lens = t_on_tylen.data();
     *object_ids = t_on_id.data();
     *object_id_lens = t_on_idlen.data();
+    return RIO_GP_OK;
+}
+
+int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const char* const** struct_names,
+                     const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens,
+                     const char* const** from_addresses, const char* const** to_addresses) {
+    if (!p || !n_out || !struct_names || !struct_name_lens || !object_ids || !object_id_lens || !from_addresses || !to_addresses)
+        return RIO_GP_EINVAL;
+    State* s = p->s;
+    t_rb_store.clear();
+    t_rb_ty.clear(); t_rb_id.clear(); t_rb_from.clear(); t_rb_to.clear(); t_rb_tylen.clear(); t_rb_idlen.clear();
+    {
+        DevLock g(s);
+        std::lock_guard<TableLock> gi(s->imu);  // the write side: no lookup is answered while keys change their address
+        int rc;
+        if ((rc = sync_device(s, true))) return rc;
+        if (!rio_gp_rebalance) return fail(RIO_GP_EUPSTREAM, "dense layer has no rebalance");
+        // a move is a row that is handed out: at most as many as rows were ever interned
+        const uint64_t cap = std::min<uint64_t>(max_moves, s->row_key.size());
+        t_rb_rows.resize(cap ? cap : 1); t_rb_src.resize(cap ? cap : 1); t_rb_dst.resize(cap ? cap : 1);
+        rio_gp_rebalance_cfg cfg{};
+        cfg.struct_size = sizeof cfg;
+        cfg.max_moves = cap;  // targets: the capacities of rio_op_set_member
+        uint64_t n = 0;
+        rc = rio_gp_rebalance(s->gp, &cfg, nullptr, t_rb_rows.data(), t_rb_src.data(), t_rb_dst.data(), cap, &n);
+        s->shadow.invalidate_all();  // moved rows must not be answered from their old address (also when the call failed)
+        if (rc) return gp_fail(s, rc);
+        // copies: keys can be reclaimed as soon as the locks are released
+        for (uint64_t k = 0; k < n; ++k) {
+            const uint32_t row = t_rb_rows[k];
+            if (row >= s->row_live.size() || !s->row_live[row]) continue;
+            t_rb_store.push_back(s->row_key[row].first);
+            t_rb_store.push_back(s->row_key[row].second);
+            t_rb_store.push_back(t_rb_src[k] < s->node_addr.size() ? s->node_addr[t_rb_src[k]] : std::string());
+            t_rb_store.push_back(t_rb_dst[k] < s->node_addr.size() ? s->node_addr[t_rb_dst[k]] : std::string());
+        }
+    }
+    for (size_t k = 0; k + 3 < t_rb_store.size(); k += 4) {
+        t_rb_ty.push_back(t_rb_store[k].data());
+        t_rb_tylen.push_back(t_rb_store[k].size());
+        t_rb_id.push_back(t_rb_store[k + 1].data());
+        t_rb_idlen.push_back(t_rb_store[k + 1].size());
+        t_rb_from.push_back(t_rb_store[k + 2].c_str());
+        t_rb_to.push_back(t_rb_store[k + 3].c_str());
+    }
+    *n_out = t_rb_ty.size();
+    *struct_names = t_rb_ty.data();
+    *struct_name_lens = t_rb_tylen.data();
+    *object_ids = t_rb_id.data();
+    *object_id_lens = t_rb_idlen.data();
+    *from_addresses = t_rb_from.data();
+    *to_addresses = t_rb_to.data();
     return RIO_GP_OK;
 }
 

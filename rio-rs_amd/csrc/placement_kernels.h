@@ -416,4 +416,36 @@ const u32* ni_total(const NiPlan& p, const u32* part);  // device word: rows lis
 void launch_ni_scatter(const u32* assign, const NiPlan& p, const u32* map, const u32* cnt, const u32* part, u64 cap, u32* rows,
                        hipStream_t s);
 
+// --- bounded rebalance (rio_gp_rebalance): shed the candidates beyond a node's target, water-fill them (kernels: k_shed_*) ---
+constexpr u32 kShChunk = 4 * kBlock;          // rows (packed rows) per workgroup step: 1 024 lanes x 4
+constexpr u64 kShMaxEntries = (u64)1 << 22;   // (over node x tile) matrix of candidate loads: at most 32 MiB of u64
+constexpr int kShAccSurplusRows = 0, kShAccSurplusLoad = 1, kShAccSelectedLoad = 2, kShAccMovedRows = 3, kShAccMovedLoad = 4,
+              kShAccStayed = 5, kShAcc = 8;  // device counters of one call (u64 [kShAcc])
+struct ShPlan {
+    u64 n;   // rows
+    u64 T;   // rows per tile (a multiple of kShChunk; one workgroup per tile)
+    u32 nt;  // tiles (s * nt <= kShMaxEntries)
+    u32 m;   // nodes
+    u32 s;   // over-target nodes = slots of the matrix
+};
+ShPlan sh_plan(u64 n, u32 m, u32 s);
+size_t shed_order_lds(u32 m);
+// used, pin: m u64 each (zeroed here): the load of every row on node j, the load of the non-object rows on it
+void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u64* used, u64* pin, hipStream_t s);
+// map: node -> slot (kNone: not over); slot_node / slot_free: per slot; mat: s * nt u64; cut: m u32 (kNone where nothing is cut)
+void launch_shed_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
+                     const u64* slot_free, u64* mat, u32* cut, hipStream_t s);
+// tcnt: nt u32 -> the exclusive scan of the per-tile surplus counts; acc[kShAccSurplusRows / SurplusLoad]
+void launch_shed_count(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, u32* tcnt, u64* acc,
+                       hipStream_t s);
+// the first `budget` surplus rows into pk_* (row, load, node = kNone); used[j] -= their load; acc[kShAccSelectedLoad]
+void launch_shed_pack(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* toff,
+                      u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s);
+// one water-fill round over the K packed rows against free = tgt -sat used; csum: ceil(K / kShChunk) u64; C: m + 1 u64; ord: m u32
+void launch_shed_round(u64 K, const u32* pk_load, u32* pk_node, const u64* tgt, u32 m, u64* used, u64* csum, u64* C, u32* ord,
+                       u32* cntp, hipStream_t s);
+// R4 + the column + the move list (out_rows NULL: counts only); mc: ceil(K / kShChunk) u32
+void launch_shed_finish(u64 K, const u32* pk_row, const u32* pk_load, const u32* pk_node, u32* assign, u64* used, u32* mc,
+                        u64* acc, u32* out_rows, u32* out_from, u32* out_to, hipStream_t s);
+
 }  // namespace riogp

@@ -6133,4 +6133,484 @@ void launch_ni_scatter(const u32* assign, const NiPlan& p, const u32* map, const
 }
 #undef RIOGP_NI_NB
 
+// ------------------------------------------------------------------------------------------------
+// Bounded rebalance (rio_gp_rebalance; DESIGN.md section 2 "rebalance"): move the candidates beyond a node's target elsewhere.
+// A candidate is an object (affinity != RIO_GP_AFF_INACTIVE) placed on a live node; a pinned row is a non-object on one.
+//   k_shed_hist    one streaming pass: per node the load of every row on it (= `used`, what k_used gives) and the load of its
+//                  non-object rows.  The host reads both and decides which live nodes are over (candidates > T -sat pinned):
+//                  none -> the call ends after this pass.
+//   k_shed_tile    per (over node x tile) the candidates' load, node-major: a matrix of at most kShMaxEntries u64
+//   k_shed_cut     one workgroup per over node: the first tile whose inclusive prefix passes free, then the exact row inside
+//                  it (R1, the strict prefix cut of rule 2 over the rows already on the node): cut[j] (kNone elsewhere)
+//   k_shed_count   per tile: the surplus rows (candidate on j, row >= cut[j]) and their load
+//   k_shed_scan    one workgroup: exclusive scan of per-tile / per-chunk values
+//   k_shed_pack    the first B surplus rows in row order (R2) into the packed columns; `used` loses their load
+//   k_shed_csum + k_shed_scan + k_shed_order + k_shed_fill   one water-fill round over the packed rows (R3): the pending
+//                  load per chunk of packed rows and its prefix, the node order (rank_by_class) and C[] from free = T -sat used
+//                  (dead nodes: T = 0), then the interval rule for every pending row
+//   k_shed_mcount + k_shed_scan + k_shed_finish   the rows the fill left without a node give their load back to their own node
+//                  (R4); the moved rows go into the column and, in row order, into the move list
+// All sums are integers: the atomics make no result depend on scheduling.  Packed arrays are read with scalar loads (the
+// packed rows are a few percent of the table); the table passes stream `dwordx4`.
+// ------------------------------------------------------------------------------------------------
+
+// Add v (negated when `neg`) to arr[key] for every active lane, one atomic per distinct key of the wave.  Wave-uniform call.
+__device__ __forceinline__ void shed_agg_add(u64* arr, u32 key, u64 v, bool act, bool neg) {
+    u64 mask = __ballot(act);
+    while (mask) {
+        const int lead = __ffsll((long long)mask) - 1;
+        const u32 k0 = (u32)__shfl((int)key, lead, 64);
+        const bool mine = act && key == k0;
+        const u64 mm = __ballot(mine);
+        const u64 s = wave_sum(mine ? v : 0ull);
+        if ((int)(threadIdx.x & 63) == lead) atomicAdd(&arr[k0], neg ? 0ull - s : s);
+        act = act && !mine;
+        mask &= ~mm;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_shed_hist(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                      const u32* __restrict__ aff, u64 n, u32 m, u64* __restrict__ used,
+                                                      u64* __restrict__ pin) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64* hu = reinterpret_cast<u64*>(smem);  // [m]
+    u64* hp = hu + m;                        // [m]
+    const int tid = threadIdx.x;
+    for (u32 k = tid; k < 2 * m; k += kBlock) hu[k] = 0;
+    __syncthreads();
+    const u64 nvec = (n + 3) / 4;
+    for (u64 v = (u64)blockIdx.x * kBlock + tid; v < nvec; v += (u64)gridDim.x * kBlock) {
+        const u64 i0 = v * 4;
+        const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
+        const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
+        const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
+        const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i0 + k < n && cc[k] < m && ll[k]) {
+                atomicAdd(&hu[cc[k]], (u64)ll[k]);
+                if (aa[k] == kAffInactive) atomicAdd(&hp[cc[k]], (u64)ll[k]);
+            }
+    }
+    __syncthreads();
+    for (u32 k = tid; k < m; k += kBlock) {
+        if (hu[k]) atomicAdd(&used[k], hu[k]);
+        if (hp[k]) atomicAdd(&pin[k], hp[k]);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_shed_tile(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                      const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ map,
+                                                      u64* __restrict__ mat) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64* h = reinterpret_cast<u64*>(smem);           // [s]
+    u32* mp = reinterpret_cast<u32*>(h + p.s);       // [m]
+    const int tid = threadIdx.x;
+    const u32 t = blockIdx.x;
+    for (u32 k = tid; k < p.s; k += kBlock) h[k] = 0;
+    for (u32 k = tid; k < p.m; k += kBlock) mp[k] = map[k];
+    __syncthreads();
+    const u64 lo = (u64)t * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
+    for (u64 base = lo; base < hi; base += kShChunk) {
+        const u64 i0 = base + (u64)tid * 4;
+        if (i0 >= hi) continue;
+        const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
+        const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
+        const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
+        const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i0 + k < hi && cc[k] < p.m && aa[k] != kAffInactive && ll[k]) {
+                const u32 sl = mp[cc[k]];
+                if (sl != kNone) atomicAdd(&h[sl], (u64)ll[k]);
+            }
+    }
+    __syncthreads();
+    for (u32 k = tid; k < p.s; k += kBlock) mat[(size_t)k * p.nt + t] = h[k];
+}
+
+__global__ __launch_bounds__(kBlock) void k_shed_cut(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                     const u32* __restrict__ aff, ShPlan p, const u64* __restrict__ mat,
+                                                     const u32* __restrict__ slot_node, const u64* __restrict__ slot_free,
+                                                     u32* __restrict__ cut) {
+    __shared__ u64 part[16];
+    __shared__ u64 s_base;
+    __shared__ u32 s_tile, s_row;
+    const int tid = threadIdx.x;
+    const u32 sl = blockIdx.x, j = slot_node[sl];
+    const u64 fr = slot_free[sl];
+    const u64* row = mat + (size_t)sl * p.nt;
+    if (tid == 0) { s_tile = kNone; s_row = kNone; s_base = 0; }
+    __syncthreads();
+    // the tile: the first inclusive prefix > free (the prefix never decreases: exactly one tile starts at or below free and ends
+    // above it)
+    u64 carry = 0;
+    for (u32 t0 = 0; t0 < p.nt; t0 += kBlock) {
+        const u32 t = t0 + tid;
+        const u64 v = t < p.nt ? row[t] : 0ull;
+        u64 tot;
+        const u64 ex = carry + block_excl_scan_1024(v, false, part, &tot);
+        if (t < p.nt && ex <= fr && ex + v > fr) { s_tile = t; s_base = ex; }
+        carry += tot;
+        __syncthreads();
+        if (s_tile != kNone) break;
+    }
+    const u32 t = s_tile;
+    if (t == kNone) return;  // (the host counted more than free: cannot happen)
+    // the row inside the tile, the same way over the rows in order
+    carry = s_base;
+    const u64 lo = (u64)t * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
+    for (u64 base = lo; base < hi; base += kShChunk) {
+        const u64 i0 = base + (u64)tid * 4;
+        u32 ll[4] = {0, 0, 0, 0};
+        if (i0 < hi) {
+            const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
+            const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
+            const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
+            const u32 cc[4] = {c.x, c.y, c.z, c.w}, l4[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ll[k] = (i0 + k < hi && cc[k] == j && aa[k] != kAffInactive) ? l4[k] : 0u;
+        }
+        u64 tot;
+        u64 run = carry + block_excl_scan_1024((u64)ll[0] + ll[1] + ll[2] + ll[3], false, part, &tot);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (run <= fr && run + ll[k] > fr) s_row = (u32)(i0 + k);
+            run += ll[k];
+        }
+        carry += tot;
+        __syncthreads();
+        if (s_row != kNone) break;
+    }
+    if (tid == 0) cut[j] = s_row;
+}
+
+__global__ __launch_bounds__(kBlock) void k_shed_count(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                       const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ cut,
+                                                       u32* __restrict__ tcnt, u64* __restrict__ acc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32* ct = reinterpret_cast<u32*>(smem);  // [m]
+    __shared__ u64 s_sum;
+    __shared__ u32 s_cnt;
+    const int tid = threadIdx.x;
+    const u32 t = blockIdx.x;
+    for (u32 k = tid; k < p.m; k += kBlock) ct[k] = cut[k];
+    if (tid == 0) { s_sum = 0; s_cnt = 0; }
+    __syncthreads();
+    u64 sum = 0;
+    u32 cnt = 0;
+    const u64 lo = (u64)t * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
+    for (u64 base = lo; base < hi; base += kShChunk) {
+        const u64 i0 = base + (u64)tid * 4;
+        if (i0 >= hi) continue;
+        const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
+        const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
+        const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
+        const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i0 + k < hi && cc[k] < p.m && aa[k] != kAffInactive && i0 + k >= (u64)ct[cc[k]]) { ++cnt; sum += ll[k]; }
+    }
+    sum = wave_sum(sum);
+    cnt = wave_sum32(cnt);
+    if ((tid & 63) == 0 && cnt) { atomicAdd(&s_sum, sum); atomicAdd(&s_cnt, cnt); }
+    __syncthreads();
+    if (tid == 0) {
+        tcnt[t] = s_cnt;
+        if (s_sum) atomicAdd(&acc[kShAccSurplusLoad], s_sum);
+    }
+}
+
+// exclusive scan of len values (in may be out), one workgroup; the total into *total
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_shed_scan(const T* in, T* out, u64 len, u64* __restrict__ total) {
+    __shared__ u64 part[16];
+    const int tid = threadIdx.x;
+    u64 carry = 0;
+    for (u64 b = 0; b < len; b += kShChunk) {
+        u64 v[4], loc = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const u64 i = b + (u64)tid * 4 + k;
+            v[k] = i < len ? (u64)in[i] : 0ull;
+            loc += v[k];
+        }
+        u64 tot;
+        u64 ex = carry + block_excl_scan_1024(loc, false, part, &tot);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const u64 i = b + (u64)tid * 4 + k;
+            if (i < len) out[i] = (T)ex;
+            ex += v[k];
+        }
+        carry += tot;
+    }
+    if (tid == 0 && total) *total = carry;
+}
+
+__global__ __launch_bounds__(kBlock) void k_shed_pack(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                      const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ cut,
+                                                      const u32* __restrict__ toff, u64 budget, u32* __restrict__ pk_row,
+                                                      u32* __restrict__ pk_load, u32* __restrict__ pk_node, u64* __restrict__ used,
+                                                      u64* __restrict__ acc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32* ct = reinterpret_cast<u32*>(smem);  // [m]
+    __shared__ u64 part[16];
+    const int tid = threadIdx.x;
+    const u32 t = blockIdx.x;
+    u64 pos = toff[t];
+    if (pos >= budget) return;  // (uniform) every surplus row of this tile lies beyond the budget
+    for (u32 k = tid; k < p.m; k += kBlock) ct[k] = cut[k];
+    __syncthreads();
+    u64 sel = 0;
+    const u64 lo = (u64)t * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
+    for (u64 base = lo; base < hi && pos < budget; base += kShChunk) {
+        const u64 i0 = base + (u64)tid * 4;
+        u32 cc[4] = {kNone, kNone, kNone, kNone}, ll[4] = {0, 0, 0, 0};
+        bool sp[4] = {false, false, false, false};
+        if (i0 < hi) {
+            const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
+            const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
+            const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
+            const u32 c4[4] = {c.x, c.y, c.z, c.w}, l4[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                cc[k] = c4[k]; ll[k] = l4[k];
+                sp[k] = i0 + k < hi && c4[k] < p.m && aa[k] != kAffInactive && i0 + k >= (u64)ct[c4[k]];
+            }
+        }
+        u64 tot;
+        u64 q = pos + block_excl_scan_1024((u64)sp[0] + sp[1] + sp[2] + sp[3], false, part, &tot);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool s = sp[k] && q < budget;
+            if (s) {
+                pk_row[q] = (u32)(i0 + k);
+                pk_load[q] = ll[k];
+                pk_node[q] = kNone;
+                sel += ll[k];
+            }
+            shed_agg_add(used, cc[k], ll[k], s && ll[k] != 0, true);
+            q += sp[k];
+        }
+        pos += tot;
+    }
+    sel = wave_sum(sel);
+    if ((tid & 63) == 0 && sel) atomicAdd(&acc[kShAccSelectedLoad], sel);
+}
+
+// per chunk of kShChunk packed rows: the load of the rows still without a node
+__global__ __launch_bounds__(kBlock) void k_shed_csum(u64 K, const u32* __restrict__ pk_load, const u32* __restrict__ pk_node,
+                                                      u64* __restrict__ csum) {
+    __shared__ u64 part[16];
+    const u64 r0 = (u64)blockIdx.x * kShChunk + (u64)threadIdx.x * 4;
+    u64 loc = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (r0 + k < K && pk_node[r0 + k] == kNone) loc += pk_load[r0 + k];
+    u64 tot;
+    (void)block_excl_scan_1024(loc, false, part, &tot);
+    if (threadIdx.x == 0) csum[blockIdx.x] = tot;
+}
+
+// the water-fill order of the nodes from free = tgt -sat used (rule 3: capacity class desc, index asc) and C[0..cnt]
+__global__ __launch_bounds__(kBlock) void k_shed_order(const u64* __restrict__ tgt, const u64* __restrict__ used, u32 m,
+                                                       u64* __restrict__ C, u32* __restrict__ ord, u32* __restrict__ cntp) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const size_t tb = (rank_tab_bytes(m) + 15) & ~(size_t)15;
+    unsigned short* tab = reinterpret_cast<unsigned short*>(smem);
+    u64* Cs = reinterpret_cast<u64*>(smem + tb);  // [m] free capacity by rank
+    u64* part = Cs + m;                           // [16]
+    const int tid = threadIdx.x;
+    const u32 per = (m + kBlock - 1) / kBlock;
+    for (u32 k = tid; k < (u32)(rank_tab_bytes(m) / 4); k += kBlock) reinterpret_cast<u32*>(smem)[k] = 0;
+    u64 fr[8];
+    u32 rk[8];
+#pragma unroll
+    for (u32 q = 0; q < 8; ++q) {
+        const u32 j = tid + q * kBlock;
+        fr[q] = 0;
+        if (q < per && j < m) { const u64 T = tgt[j], u = used[j]; fr[q] = T > u ? T - u : 0ull; }
+    }
+    __syncthreads();
+    Plan pl{};
+    const u32 cnt = rank_by_class(tab, per, fr, rk, pl);
+#pragma unroll
+    for (u32 q = 0; q < 8; ++q)
+        if (q < per && fr[q] != 0) { Cs[rk[q]] = fr[q]; ord[rk[q]] = tid + q * kBlock; }
+    __syncthreads();
+    u64 fk[8], loc = 0;
+#pragma unroll
+    for (u32 q = 0; q < 8; ++q) {
+        const u32 k = tid * per + q;
+        fk[q] = (q < per && k < cnt) ? Cs[k] : 0ull;
+        loc = sat_add(loc, fk[q]);
+    }
+    u64 ex = block_excl_scan_1024(loc, true, part, nullptr);
+#pragma unroll
+    for (u32 q = 0; q < 8; ++q) {
+        const u32 k = tid * per + q;
+        ex = sat_add(ex, fk[q]);
+        if (q < per && k < cnt) C[k + 1] = ex;
+    }
+    if (tid == 0) { C[0] = 0; *cntp = cnt; }
+}
+
+// one water-fill round over the packed rows still without a node: exclusive prefix Q in packed (= row) order; the node whose
+// interval [C[k], C[k+1]) holds Q takes the row iff Q + load <= C[k+1]
+__global__ __launch_bounds__(kBlock) void k_shed_fill(u64 K, const u32* __restrict__ pk_load, u32* __restrict__ pk_node,
+                                                      const u64* __restrict__ cpre, const u64* __restrict__ C,
+                                                      const u32* __restrict__ ord, const u32* __restrict__ cntp,
+                                                      u64* __restrict__ used) {
+    __shared__ u64 part[16];
+    const u64 r0 = (u64)blockIdx.x * kShChunk + (u64)threadIdx.x * 4;
+    const u32 cnt = *cntp;
+    const u64 F = C[cnt];
+    u32 l[4];
+    bool pend[4];
+    u64 loc = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        pend[k] = r0 + k < K && pk_node[r0 + k] == kNone;
+        l[k] = pend[k] ? pk_load[r0 + k] : 0u;
+        loc += l[k];
+    }
+    u64 Q = cpre[blockIdx.x] + block_excl_scan_1024(loc, false, part, nullptr);
+    u32 nd[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        nd[k] = kNone;
+        if (pend[k] && cnt && Q < F) {
+            u32 lo = 0, hi = cnt;  // largest k with C[k] <= Q
+            while (hi - lo > 1) {
+                const u32 mid = lo + (hi - lo) / 2;
+                if (C[mid] <= Q) lo = mid; else hi = mid;
+            }
+            if (Q + (u64)l[k] <= C[lo + 1]) { nd[k] = ord[lo]; pk_node[r0 + k] = nd[k]; }
+        }
+        Q += l[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) shed_agg_add(used, nd[k], l[k], nd[k] != kNone && l[k] != 0, false);
+}
+
+// per chunk of packed rows: the rows that move (a node other than their own); rows left without one give their load back
+__global__ __launch_bounds__(kBlock) void k_shed_mcount(u64 K, const u32* __restrict__ pk_row, const u32* __restrict__ pk_load,
+                                                        const u32* __restrict__ pk_node, const u32* __restrict__ assign,
+                                                        u64* __restrict__ used, u32* __restrict__ mc, u64* __restrict__ acc) {
+    __shared__ u64 part[16];
+    const u64 r0 = (u64)blockIdx.x * kShChunk + (u64)threadIdx.x * 4;
+    u32 mv = 0, st = 0;
+    u64 mvl = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const u64 r = r0 + k;
+        u32 from = kNone, l = 0;
+        bool stay = false;
+        if (r < K) {
+            const u32 to = pk_node[r];
+            from = assign[pk_row[r]];
+            l = pk_load[r];
+            stay = to == kNone;
+            if (!stay && to != from) { ++mv; mvl += l; }
+            st += stay;
+        }
+        shed_agg_add(used, from, l, stay && l != 0, false);
+    }
+    u64 tot;
+    (void)block_excl_scan_1024(mv, false, part, &tot);
+    if (threadIdx.x == 0) mc[blockIdx.x] = (u32)tot;
+    mvl = wave_sum(mvl);
+    st = wave_sum32(st);
+    if ((threadIdx.x & 63) == 0) {
+        if (mvl) atomicAdd(&acc[kShAccMovedLoad], mvl);
+        if (st) atomicAdd(&acc[kShAccStayed], (u64)st);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_shed_finish(u64 K, const u32* __restrict__ pk_row, const u32* __restrict__ pk_node,
+                                                        const u32* __restrict__ moff, u32* __restrict__ assign,
+                                                        u32* __restrict__ out_rows, u32* __restrict__ out_from,
+                                                        u32* __restrict__ out_to) {
+    __shared__ u64 part[16];
+    const u64 r0 = (u64)blockIdx.x * kShChunk + (u64)threadIdx.x * 4;
+    u32 row[4], from[4], to[4];
+    bool mv[4];
+    u64 loc = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        mv[k] = false;
+        if (r0 + k < K) {
+            row[k] = pk_row[r0 + k];
+            to[k] = pk_node[r0 + k];
+            from[k] = assign[row[k]];
+            mv[k] = to[k] != kNone && to[k] != from[k];
+        }
+        loc += mv[k];
+    }
+    u64 q = moff[blockIdx.x] + block_excl_scan_1024(loc, false, part, nullptr);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (mv[k]) {
+            assign[row[k]] = to[k];
+            if (out_rows) { out_rows[q] = row[k]; out_from[q] = from[k]; out_to[q] = to[k]; }
+            ++q;
+        }
+}
+
+ShPlan sh_plan(u64 n, u32 m, u32 s) {
+    ShPlan p{};
+    p.n = n; p.m = m; p.s = s;
+    u64 nt = (n + kShChunk - 1) / kShChunk;
+    const u64 nt_cap = std::max<u64>(1, kShMaxEntries / (s ? s : 1));
+    if (nt > nt_cap) nt = nt_cap;
+    if (nt < 1) nt = 1;
+    u64 T = ((n + nt - 1) / nt + kShChunk - 1) / kShChunk * kShChunk;
+    if (T < kShChunk) T = kShChunk;
+    p.T = T;
+    p.nt = (u32)std::max<u64>(1, (n + T - 1) / T);
+    return p;
+}
+size_t shed_order_lds(u32 m) { return ((rank_tab_bytes(m) + 15) & ~(size_t)15) + ((size_t)m + 16) * sizeof(u64); }
+
+void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u64* used, u64* pin, hipStream_t s) {
+    (void)hipMemsetAsync(used, 0, (size_t)m * sizeof(u64), s);
+    (void)hipMemsetAsync(pin, 0, (size_t)m * sizeof(u64), s);
+    if (!n || !m) return;
+    hipLaunchKernelGGL(k_shed_hist, dim3(grid_for((n + 3) / 4, kBlock, 256)), dim3(kBlock), 2 * (size_t)m * sizeof(u64), s,
+                       assign, load, aff, n, m, used, pin);
+}
+void launch_shed_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
+                     const u64* slot_free, u64* mat, u32* cut, hipStream_t s) {
+    launch_fill_u32(cut, p.m, kNone, s);
+    hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), (size_t)p.s * sizeof(u64) + (size_t)p.m * sizeof(u32), s, assign,
+                       load, aff, p, map, mat);
+    hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, cut);
+}
+void launch_shed_count(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, u32* tcnt, u64* acc,
+                       hipStream_t s) {
+    hipLaunchKernelGGL(k_shed_count, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32), s, assign, load, aff, p, cut, tcnt, acc);
+    hipLaunchKernelGGL((k_shed_scan<u32>), dim3(1), dim3(kBlock), 0, s, tcnt, tcnt, (u64)p.nt, acc + kShAccSurplusRows);
+}
+void launch_shed_pack(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* toff,
+                      u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s) {
+    hipLaunchKernelGGL(k_shed_pack, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32), s, assign, load, aff, p, cut, toff,
+                       budget, pk_row, pk_load, pk_node, used, acc);
+}
+void launch_shed_round(u64 K, const u32* pk_load, u32* pk_node, const u64* tgt, u32 m, u64* used, u64* csum, u64* C, u32* ord,
+                       u32* cntp, hipStream_t s) {
+    const u32 nc = (u32)((K + kShChunk - 1) / kShChunk);
+    hipLaunchKernelGGL(k_shed_csum, dim3(nc), dim3(kBlock), 0, s, K, pk_load, pk_node, csum);
+    hipLaunchKernelGGL((k_shed_scan<u64>), dim3(1), dim3(kBlock), 0, s, csum, csum, (u64)nc, nullptr);
+    hipLaunchKernelGGL(k_shed_order, dim3(1), dim3(kBlock), shed_order_lds(m), s, tgt, used, m, C, ord, cntp);
+    hipLaunchKernelGGL(k_shed_fill, dim3(nc), dim3(kBlock), 0, s, K, pk_load, pk_node, csum, C, ord, cntp, used);
+}
+void launch_shed_finish(u64 K, const u32* pk_row, const u32* pk_load, const u32* pk_node, u32* assign, u64* used, u32* mc,
+                        u64* acc, u32* out_rows, u32* out_from, u32* out_to, hipStream_t s) {
+    const u32 nc = (u32)((K + kShChunk - 1) / kShChunk);
+    hipLaunchKernelGGL(k_shed_mcount, dim3(nc), dim3(kBlock), 0, s, K, pk_row, pk_load, pk_node, assign, used, mc, acc);
+    hipLaunchKernelGGL((k_shed_scan<u32>), dim3(1), dim3(kBlock), 0, s, mc, mc, (u64)nc, acc + kShAccMovedRows);
+    hipLaunchKernelGGL(k_shed_finish, dim3(nc), dim3(kBlock), 0, s, K, pk_row, pk_node, mc, assign, out_rows, out_from, out_to);
+}
+
 }  // namespace riogp

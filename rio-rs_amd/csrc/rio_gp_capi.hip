@@ -291,6 +291,9 @@ struct rio_gp {
     u32 *h_ni = nullptr, *d_ni = nullptr;  // [RIO_GP_MAX_NODES] map | [RIO_GP_MAX_NODES + 1] ranks | [1] total read back
     DevBuf ni_rows;                        // the host-pointer form's listing (grows to the largest answer: 4 B per listed row)
     u32 ni_force_tile = 0;                 // lab builds: rows per tile (rio_gp_debug_set_node_index)
+    // bounded rebalance (rio_gp_rebalance), grown on use: per-node arrays + counters, the (over node x tile) matrix, per-tile and
+    // per-chunk counts, the packed rows (row | load | node), the host-pointer form's move listing (row | from | to)
+    DevBuf sh_nodes, sh_mat, sh_tile, sh_chunk, sh_pk, sh_mv;
     std::vector<void*> allocs;
 };
 
@@ -1160,6 +1163,8 @@ void rio_gp_destroy(rio_gp_t* h) {
     if (h->vrec.p) (void)hipFree(h->vrec.p);
     if (h->part.p) (void)hipFree(h->part.p);
     if (h->ni_rows.p) (void)hipFree(h->ni_rows.p);
+    for (DevBuf* b : {&h->sh_nodes, &h->sh_mat, &h->sh_tile, &h->sh_chunk, &h->sh_pk, &h->sh_mv})
+        if (b->p) (void)hipFree(b->p);
     if (h->h_ni) (void)hipHostFree(h->h_ni);
     if (h->h_stats) (void)hipHostFree(h->h_stats);
     if (h->h_chain_err) (void)hipHostFree(h->h_chain_err);
@@ -1496,6 +1501,183 @@ int rio_gp_rows_on_nodes_dev(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t*
     *n_rows = total;
     if (d_rows && total > rows_cap) return ni_erange(h, total, rows_cap);
     return RIO_GP_OK;
+}
+
+// ---- bounded rebalance ----------------------------------------------------------------------
+
+// The device-side work of rio_gp_rebalance[_dev] (validated, locked).  d_rows / d_from / d_to: device arrays of at least
+// `budget` entries, or all NULL.
+static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 rounds, u64 budget, rio_gp_rebalance_stats* st,
+                            u32* d_rows, u32* d_from, u32* d_to, uint64_t* n_moves) {
+    rio_gp_rebalance_stats s{};
+    if (n_moves) *n_moves = 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    // a change of the inputs, like every CRUD call: an uncommitted solve is dropped, the next tick is neither quiet nor chained
+    h->have_solved = false; ++h->mut_epoch;
+    const u32 m = h->m, M = h->cap_nodes;
+    const u64 n = h->n;
+    // per-node arrays: pin | tgt (0 on dead nodes) | slot_free | C [M + 1] | acc [kShAcc] (u64), then map | slot_node | cut |
+    // ord | cnt (u32)
+    int rc;
+    const size_t u64s = 4 * (size_t)M + 1 + kShAcc, u32s = 4 * (size_t)M + 4;
+    if ((rc = ensure(h, h->sh_nodes, u64s * sizeof(u64) + u32s * sizeof(u32)))) return rc;
+    u64* pin = (u64*)h->sh_nodes.p;
+    u64* tgt = pin + M;
+    u64* slot_free = tgt + M;
+    u64* C = slot_free + M;
+    u64* acc = C + M + 1;
+    u32* map = (u32*)(acc + kShAcc);
+    u32* slot_node = map + M;
+    u32* cut = slot_node + M;
+    u32* ord = cut + M;
+    u32* cntp = ord + M;
+    // the targets (the capacities by default) and the live nodes
+    std::vector<u64> T(m ? m : 1), used(m ? m : 1), pn(m ? m : 1);
+    if (cfg->target) memcpy(T.data(), cfg->target, (size_t)m * sizeof(u64));
+    else if (m) HIPCHK(h, hipMemcpyAsync(T.data(), h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    // R0: one pass — every node's load (the `used` vector of this column, rebuilt: nothing left to fold) and its pinned load
+    h->used_parts = false;
+    launch_shed_hist(h->assign[h->cur], h->load, h->aff, n, m, h->used, pin, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->used_valid = true;
+    if (m) {
+        HIPCHK(h, hipMemcpyAsync(used.data(), h->used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(pn.data(), pin, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // R1 on the host's side: which live nodes hold more candidate load than T -sat pinned
+    std::vector<u32> hmap(m ? m : 1, kNone), snode;
+    std::vector<u64> sfree, tl(m ? m : 1, 0);
+    for (u32 j = 0; j < m; ++j) {
+        if (!h->h_alive[j]) continue;
+        tl[j] = T[j];
+        s.nodes_over_before += used[j] > T[j];
+        const u64 fr = T[j] > pn[j] ? T[j] - pn[j] : 0, cand = used[j] - pn[j];
+        if (cand > fr) { hmap[j] = (u32)snode.size(); snode.push_back(j); sfree.push_back(fr); }
+    }
+    const u32 S = (u32)snode.size();
+    if (S == 0 || budget == 0) {  // nothing over target (or nothing may move): one pass, nothing changed
+        if (S) {  // (budget 0: the surplus is still counted)
+            const ShPlan p = sh_plan(n, m, S);
+            if ((rc = ensure(h, h->sh_mat, (size_t)S * p.nt * sizeof(u64))) || (rc = ensure(h, h->sh_tile, (size_t)p.nt * sizeof(u32))))
+                return rc;
+            HIPCHK(h, hipMemcpyAsync(map, hmap.data(), (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(slot_node, snode.data(), (size_t)S * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(slot_free, sfree.data(), (size_t)S * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemsetAsync(acc, 0, kShAcc * sizeof(u64), h->stream));
+            launch_shed_cut(h->assign[h->cur], h->load, h->aff, p, map, slot_node, slot_free, (u64*)h->sh_mat.p, cut, h->stream);
+            launch_shed_count(h->assign[h->cur], h->load, h->aff, p, cut, (u32*)h->sh_tile.p, acc, h->stream);
+            HIPCHK(h, hipGetLastError());
+            u64 a[kShAcc];
+            HIPCHK(h, hipMemcpyAsync(a, acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            s.surplus_rows = a[kShAccSurplusRows];
+            s.surplus_load = a[kShAccSurplusLoad];
+        }
+        s.nodes_over_after = s.nodes_over_before;
+        if (st) *st = s;
+        return RIO_GP_OK;
+    }
+    // R1 on the device: the exact cut of every over node; the surplus per tile
+    const ShPlan p = sh_plan(n, m, S);
+    if ((rc = ensure(h, h->sh_mat, (size_t)S * p.nt * sizeof(u64))) || (rc = ensure(h, h->sh_tile, (size_t)p.nt * sizeof(u32))))
+        return rc;
+    HIPCHK(h, hipMemcpyAsync(map, hmap.data(), (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(slot_node, snode.data(), (size_t)S * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(slot_free, sfree.data(), (size_t)S * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(tgt, tl.data(), (size_t)m * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(acc, 0, kShAcc * sizeof(u64), h->stream));
+    launch_shed_cut(h->assign[h->cur], h->load, h->aff, p, map, slot_node, slot_free, (u64*)h->sh_mat.p, cut, h->stream);
+    launch_shed_count(h->assign[h->cur], h->load, h->aff, p, cut, (u32*)h->sh_tile.p, acc, h->stream);
+    HIPCHK(h, hipGetLastError());
+    u64 a[kShAcc];
+    HIPCHK(h, hipMemcpyAsync(a, acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    s.surplus_rows = a[kShAccSurplusRows];
+    s.surplus_load = a[kShAccSurplusLoad];
+    const u64 K = std::min<u64>(s.surplus_rows, budget);
+    s.selected_rows = K;
+    if (K) {
+        // R2: the first K surplus rows, packed in row order; R3: the water-fill rounds; R4 + the column + the moves
+        const u64 nc = (K + kShChunk - 1) / kShChunk;
+        if ((rc = ensure(h, h->sh_pk, 3 * K * sizeof(u32))) || (rc = ensure(h, h->sh_chunk, nc * sizeof(u64)))) return rc;
+        u32* pk_row = (u32*)h->sh_pk.p;
+        u32* pk_load = pk_row + K;
+        u32* pk_node = pk_load + K;
+        launch_shed_pack(h->assign[h->cur], h->load, h->aff, p, cut, (const u32*)h->sh_tile.p, K, pk_row, pk_load, pk_node, h->used,
+                         acc, h->stream);
+        for (u32 r = 0; r < rounds; ++r)
+            launch_shed_round(K, pk_load, pk_node, tgt, m, h->used, (u64*)h->sh_chunk.p, C, ord, cntp, h->stream);
+        launch_shed_finish(K, pk_row, pk_load, pk_node, h->assign[h->cur], h->used, (u32*)h->sh_chunk.p, acc, d_rows, d_from, d_to,
+                           h->stream);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(a, acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(used.data(), h->used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        s.selected_load = a[kShAccSelectedLoad];
+        s.moved_rows = a[kShAccMovedRows];
+        s.moved_load = a[kShAccMovedLoad];
+        s.stayed_rows = a[kShAccStayed];
+    }
+    for (u32 j = 0; j < m; ++j) s.nodes_over_after += h->h_alive[j] && used[j] > T[j];
+    if (n_moves) *n_moves = s.moved_rows;
+    if (st) *st = s;
+    return RIO_GP_OK;
+}
+
+// checks shared by both forms: nothing is changed before they pass
+static int rebalance_args(rio_gp* h, const rio_gp_rebalance_cfg* cfg, const void* r, const void* f, const void* t, uint64_t cap,
+                          u32* rounds, u64* budget) {
+    if (!cfg || cfg->struct_size != sizeof(rio_gp_rebalance_cfg))
+        return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: cfg missing or struct_size differs");
+    if (cfg->rounds > 8) return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: rounds above the solver limit (8)");
+    if ((r != nullptr) != (f != nullptr) || (r != nullptr) != (t != nullptr))
+        return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: out_rows / out_from / out_to are given together or not at all");
+    if (!r && cap) return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: moves_cap without a move listing");
+    if (h->sc || h->p2p || h->sh_tick_n)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: not implemented on a handle of the row-sharded solve");
+    *rounds = cfg->rounds ? cfg->rounds : h->rounds;
+    *budget = r ? std::min<u64>(cfg->max_moves, cap) : cfg->max_moves;
+    return RIO_GP_OK;
+}
+
+int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebalance_stats* st, uint32_t* out_rows,
+                     uint32_t* out_from, uint32_t* out_to, uint64_t moves_cap, uint64_t* n_moves) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    u32 rounds;
+    u64 budget;
+    int rc;
+    if ((rc = rebalance_args(h, cfg, out_rows, out_from, out_to, moves_cap, &rounds, &budget))) return rc;
+    // the listing is staged on the device (moves <= selected <= budget <= min(n, moves_cap))
+    u32* d = nullptr;
+    u64 stage = 0;
+    if (out_rows) {
+        stage = std::min<u64>(budget, h->n);
+        if ((rc = ensure(h, h->sh_mv, 3 * std::max<u64>(stage, 1) * sizeof(u32)))) return rc;
+        d = (u32*)h->sh_mv.p;
+    }
+    uint64_t nm = 0;
+    if ((rc = rebalance_locked(h, cfg, rounds, budget, st, d, d ? d + stage : nullptr, d ? d + 2 * stage : nullptr, &nm))) return rc;
+    if (n_moves) *n_moves = nm;
+    if (out_rows && nm) {
+        HIPCHK(h, hipMemcpyAsync(out_rows, d, nm * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(out_from, d + stage, nm * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(out_to, d + 2 * stage, nm * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return RIO_GP_OK;
+}
+
+int rio_gp_rebalance_dev(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebalance_stats* st, uint32_t* d_rows,
+                         uint32_t* d_from, uint32_t* d_to, uint64_t moves_cap, uint64_t* n_moves) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    u32 rounds;
+    u64 budget;
+    int rc;
+    if ((rc = rebalance_args(h, cfg, d_rows, d_from, d_to, moves_cap, &rounds, &budget))) return rc;
+    return rebalance_locked(h, cfg, rounds, budget, st, d_rows, d_from, d_to, n_moves);
 }
 
 int rio_gp_set_num_objects(rio_gp_t* h, uint64_t n) {

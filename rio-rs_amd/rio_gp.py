@@ -58,6 +58,46 @@ class Stats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
+class RebalanceCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("rounds", C.c_uint32), ("max_moves", C.c_uint64), ("target", C.c_void_p)]
+
+
+class RebalanceStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("surplus_rows", "surplus_load", "selected_rows", "selected_load", "moved_rows",
+                                         "moved_load", "stayed_rows")] + [("nodes_over_before", C.c_uint32),
+                                                                          ("nodes_over_after", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def balanced_targets(cap, used, alive, slack_permille=0):
+    """Per-node targets for spreading onto live nodes that hold little (scale-out): every live node's capacity times the live
+    nodes' mean utilisation (sum used / sum cap), plus slack_permille of it, never above its capacity.  With unbounded
+    capacities (any live cap = CAP_INF) every live node's target is the mean load per live node plus the slack.  Nodes that
+    are not alive get CAP_INF (they take no part in a rebalance)."""
+    cap = np.asarray(cap, np.uint64)
+    used = np.asarray(used, np.uint64)
+    live = np.asarray(alive, np.uint8) != 0
+    t = np.full(len(cap), CAP_INF, np.uint64)
+    if not live.any():
+        return t
+    total = sum(int(u) for u in used[live])
+    caps = [int(c) for c in cap[live]]
+    scale = 1000 + int(slack_permille)
+    if any(c == CAP_INF for c in caps):
+        per = -(-total * scale // (1000 * len(caps)))  # ceil(mean * (1 + slack))
+        t[live] = np.uint64(min(per, CAP_INF))
+        return t
+    sc = sum(caps)
+    out = []
+    for c in caps:  # ceil(c * total / sc * (1 + slack)), in integers
+        v = -(-c * total * scale // (sc * 1000)) if sc else 0
+        out.append(min(v, c))
+    t[live] = np.array(out, np.uint64)
+    return t
+
+
 class Mixed(C.Structure):
     """rio_gp_mixed (include/rio_gpu_placement.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_update", C.c_uint32), ("update_idx", C.c_void_p), ("update_node", C.c_void_p),
@@ -160,6 +200,9 @@ def _load(lab):
         L.rio_gp_mixed_batch.argtypes = [_vp, C.POINTER(Mixed)]
         for nm in ("rio_gp_rows_on_nodes", "rio_gp_rows_on_nodes_dev"):
             getattr(L, nm).argtypes = [_vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        for nm in ("rio_gp_rebalance", "rio_gp_rebalance_dev"):
+            getattr(L, nm).argtypes = [_vp, C.POINTER(RebalanceCfg), C.POINTER(RebalanceStats), _vp, _vp, _vp, C.c_uint64,
+                                       C.POINTER(C.c_uint64)]
         if lab:
             L.rio_gp_debug_set_scan_nt.argtypes = [C.c_int]
             L.rio_gp_debug_set_scan_nt.restype = None
@@ -384,6 +427,50 @@ class GpuPlacement:
             self._chk(rc)
         return rc, int(n.value)
 
+    # -- bounded rebalance --
+    def _rebalance_cfg(self, target, max_moves, rounds):
+        t = None if target is None else np.ascontiguousarray(target, np.uint64)
+        if t is not None and len(t) < self.num_nodes:
+            raise ValueError("target needs one entry per node")
+        cfg = RebalanceCfg(C.sizeof(RebalanceCfg), int(rounds), CAP_INF if max_moves is None else int(max_moves),
+                           None if t is None else t.ctypes.data)
+        return cfg, t
+
+    def rebalance(self, target=None, max_moves=None, rounds=0, list_moves=True, moves_cap=None):
+        """rio_gp_rebalance: (stats dict, rows, from, to) — the moves in row order (uint32 arrays; empty with
+        list_moves=False).  target: m u64 (None: the capacities); max_moves None: no limit; rounds 0: the handle's
+        spill_rounds.  moves_cap: the listing's capacity (default: max_moves bounded by the table size)."""
+        cfg, _keep = self._rebalance_cfg(target, max_moves, rounds)
+        st, nm = RebalanceStats(), C.c_uint64(0)
+        if list_moves:
+            cap = moves_cap if moves_cap is not None else min(cfg.max_moves, self.num_objects)
+            cap = int(cap)
+            buf = np.empty((3, max(min(cap, self.num_objects), 1)), np.uint32)
+            self._chk(self._L.rio_gp_rebalance(self._h, C.byref(cfg), C.byref(st), _ptr(buf[0]), _ptr(buf[1]), _ptr(buf[2]), cap,
+                                               C.byref(nm)))
+            k = int(nm.value)
+            return st.as_dict(), buf[0, :k].copy(), buf[1, :k].copy(), buf[2, :k].copy()
+        self._chk(self._L.rio_gp_rebalance(self._h, C.byref(cfg), C.byref(st), None, None, None, 0, C.byref(nm)))
+        e = np.empty(0, np.uint32)
+        return st.as_dict(), e, e, e
+
+    def rebalance_dev(self, d_rows=None, d_from=None, d_to=None, moves_cap=0, target=None, max_moves=None, rounds=0):
+        """rio_gp_rebalance_dev: the moves into device arrays (ints, e.g. torch tensors' data_ptr(); all None: counts only).
+        Returns (stats dict, n_moves)."""
+        cfg, _keep = self._rebalance_cfg(target, max_moves, rounds)
+        st, nm = RebalanceStats(), C.c_uint64(0)
+        self._chk(self._L.rio_gp_rebalance_dev(self._h, C.byref(cfg), C.byref(st), _vp(d_rows) if d_rows else None,
+                                               _vp(d_from) if d_from else None, _vp(d_to) if d_to else None, int(moves_cap),
+                                               C.byref(nm)))
+        return st.as_dict(), int(nm.value)
+
+    def rebalance_raw(self, cfg, out_rows=None, out_from=None, out_to=None, moves_cap=0):
+        """One rio_gp_rebalance call as given (tests of the argument checks): (rc, stats dict, n_moves); no exception."""
+        st, nm = RebalanceStats(), C.c_uint64(0)
+        rc = self._L.rio_gp_rebalance(self._h, C.byref(cfg) if cfg is not None else None, C.byref(st), _ptr(out_rows),
+                                      _ptr(out_from), _ptr(out_to), int(moves_cap), C.byref(nm))
+        return rc, st.as_dict(), int(nm.value)
+
     # -- policy --
     def place_pending(self, idx, requester):
         idx, requester = _u32(idx), _u32(requester)
@@ -596,6 +683,10 @@ def _oplib():
         L.rio_op_objects_on_server.argtypes = [_vp, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_char_p)),
                                                C.POINTER(C.POINTER(C.c_size_t)), C.POINTER(C.POINTER(C.c_char_p)),
                                                C.POINTER(C.POINTER(C.c_size_t))]
+        L.rio_op_rebalance.argtypes = [_vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_char_p)),
+                                       C.POINTER(C.POINTER(C.c_size_t)), C.POINTER(C.POINTER(C.c_char_p)),
+                                       C.POINTER(C.POINTER(C.c_size_t)), C.POINTER(C.POINTER(C.c_char_p)),
+                                       C.POINTER(C.POINTER(C.c_char_p))]
         L.rio_op_dense.argtypes = [_vp]
         L.rio_op_dense.restype = _vp
         L.rio_op_invalidate_cache.argtypes = [_vp]
@@ -784,6 +875,18 @@ class GpuObjectPlacement:
         self._chk(_oplib().rio_op_snapshot_key_lengths(self._h, C.byref(tl), C.byref(il)))
         tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))   # (c_char_p would stop at a NUL)
         return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), addr[k].decode())
+                for k in range(n.value)]
+
+    def rebalance(self, max_moves=None):
+        """rio_op_rebalance: [(struct_name, object_id, from_address, to_address)] of the objects moved off servers over their
+        member capacity (max_moves None: no limit), in the dense layer's row order."""
+        n = C.c_uint64(0)
+        ty, oid, fa, ta = (C.POINTER(C.c_char_p)() for _ in range(4))
+        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+        self._chk(_oplib().rio_op_rebalance(self._h, CAP_INF if max_moves is None else int(max_moves), C.byref(n), C.byref(ty),
+                                            C.byref(tl), C.byref(oid), C.byref(il), C.byref(fa), C.byref(ta)))
+        tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
+        return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), fa[k].decode(), ta[k].decode())
                 for k in range(n.value)]
 
     def objects_on_server(self, address):
