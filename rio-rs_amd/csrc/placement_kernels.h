@@ -176,12 +176,22 @@ struct NodeTab {
 // two streams and hand their rows over wave range by wave range (per workgroup in the other form) — workgroup b of tick k + 1 reads what workgroup b of tick k
 // wrote (and writes what it read), so it waits for THAT workgroup's flag instead of for the whole launch; the ramp-down of
 // one scan and the ramp-up of the next overlap.  flags[b] = `set` of the last chained scan whose workgroup b is through.
+// The chained scan is the whole tick: no claim can occur and kept rows are never cut, so every workgroup adds its kept loads
+// into the tick's `used` buffer and stores its own verdict row (no k_resolve behind it).  The buffers rotate through a ring of
+// four: link k adds into buffer k and zeroes buffer k + 2, which link k - 2 — finished before link k started, on the same
+// stream — added into last; the host zeroes the first two links' buffers in front of the run.
 struct ScanChain {
-    u32* flags;   // [kMaxBlocks] per workgroup, then [kMaxBlocks * kWaves] per wave range; device memory
-    u32* err;     // one word of mapped host memory: raised when a wait gave up (the tables are then stale)
-    u32 wait;     // sequence number of the scan to wait for (0: none — the stream orders this scan behind what it depends on)
-    u32 set;      // this scan's sequence number
-    u32 per_wave; // the hand-over is per wave range (a flag per wave, no barrier on its path) instead of per workgroup
+    u32* flags = nullptr;   // [kMaxBlocks] per workgroup, then [kMaxBlocks * kWaves] per wave range; device memory
+    u32* err = nullptr;     // one word of mapped host memory: raised when a wait gave up (the tables are then stale)
+    u32 wait = 0;     // sequence number of the scan to wait for (0: none — the stream orders this scan behind what it depends on)
+    u32 set = 0;      // this scan's sequence number
+    u32 per_wave = 0; // the hand-over is per wave range (a flag per wave, no barrier on its path) instead of per workgroup
+    u64* used = nullptr;       // [reps][m] this tick's `used` as `reps` replicas (zero before the first add): workgroup b adds into
+                               // replica b % reps, the committed vector is their sum (the host folds replicas 1.. into replica 0 later)
+    u64* used_zero = nullptr;  // [reps][m] the buffer of the link two ahead: each workgroup zeroes its slice
+    u32 reps = 1;
+    u64* rows = nullptr;       // [G][8] pinned verdict rows, word 7 = Plan::mark: {load_kept, 0, 0, kept, evicted, claimants,
+                               // spill candidates + claimants (rows the tick cannot settle), mark}
 };
 
 bool scan_chain_fits(u32 m);  // two workgroups of the chained scan per CU (what makes the in-kernel wait deadlock-free)
@@ -197,9 +207,10 @@ void launch_scan(const Plan& p, const Table& t, const NodeTab& nt, const SolveBu
 // b.D is zeroed), fold_rounds = that solve's rounds.
 // kept_from: the scan built no kept histogram (launch_inc_scan) — the kept load of a node is the committed vector's entry
 // where the node is alive (read after the fold when it is fold_into itself).
+// fold_from: where those rows are (nullptr: b.D).
 void launch_resolve(const Plan& p, const NodeTab& nt, const SolveBufs& b, u64* host_partial, hipStream_t s,
                     hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, const PackOut* search = nullptr,
-                    u64* fold_into = nullptr, u32 fold_rounds = 0, const u64* kept_from = nullptr);
+                    u64* fold_into = nullptr, u32 fold_rounds = 0, const u64* kept_from = nullptr, const u64* fold_from = nullptr);
 // The scan of a COMMITTED tick over a mostly-placed table (k_inc_scan): cur / load / aff are streamed like k_scan does, the
 // assignment column is updated in place and only where a row's value changes, no histogram is built; the pending rows ->
 // pack (per wave range of p).  launch_rebal deals them out evenly over rebal_plan(p) into `dst` and builds the fix-up's

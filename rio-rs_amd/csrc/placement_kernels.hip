@@ -191,9 +191,11 @@ u64 plan_wave_row_lo(u64 n, u32 m, u32 gw, u32* nw_out) {
     return wave_row_lo(p, gw);
 }
 
-__host__ __device__ __forceinline__ size_t scan_lds_bytes_dev(u32 m) {
+// histogram bins of k_scan: kept-by-cur | claim-by-aff | trash; the chained form (a quiet tick) keeps the kept half and the trash bin
+__host__ __device__ __forceinline__ size_t scan_hist_words(u32 m, bool chain) { return chain ? (size_t)m + 1 : (size_t)2 * m + 2; }
+__host__ __device__ __forceinline__ size_t scan_lds_bytes_dev(u32 m, bool chain = false) {
     const u32 mwords = (m + 31) / 32;
-    const size_t b = kSmall + ((size_t)2 * m + 2) * sizeof(u64) + (size_t)((mwords + 3) & ~3u) * sizeof(u32) + 64;
+    const size_t b = kSmall + scan_hist_words(m, chain) * sizeof(u64) + (size_t)((mwords + 3) & ~3u) * sizeof(u32) + 64;
     return (b + 15) & ~(size_t)15;
 }
 size_t scan_lds_bytes(u32 m) { return scan_lds_bytes_dev(m); }
@@ -320,7 +322,7 @@ __device__ __forceinline__ void scan_tile(const uint4 cv, const uint4 av, const 
         const bool kept = inr && cin && (VIRT || ALLALIVE || bit_of(alv, cc));                         \
         const bool cl = inr && !kept && !skip && ain && (ALLALIVE || sa || bit_of(alv, aa));           \
         const bool sp = inr && !kept && !cl && !skip && !dead;                                         \
-        const u32 bin = (kept && !VIRT) ? cc : (cl ? m + aa : 2 * m);                                  \
+        const u32 bin = (kept && !VIRT) ? cc : CHAIN ? m : (cl ? m + aa : 2 * m);                      \
         atomicAdd(&hist[bin], (u64)L);                                                                 \
         O = kept ? C : (cl ? A : (skip ? kSkipMark : (dead ? kNone : kSpillMark)));                    \
         kept_cnt += (u32)__popcll(__ballot(kept));                                                     \
@@ -426,8 +428,9 @@ __global__ __launch_bounds__(kBlock, CHAIN ? 8 : 1) void k_scan(const u32* __res
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const u32 m = p.m;
     u32* bst = reinterpret_cast<u32*>(smem);                 // [4] (first 128 B: small scratch, G17)
-    u64* hist = reinterpret_cast<u64*>(smem + kSmall);       // [2m + 2] kept-by-cur | claim-by-aff | trash
-    u32* alv = reinterpret_cast<u32*>(hist + 2 * m + 2);     // [mwords]
+    u64* hist = reinterpret_cast<u64*>(smem + kSmall);       // [2m + 2] kept-by-cur | claim-by-aff | trash  (CHAIN: [m + 1] kept | trash)
+    const u32 hwords = (u32)scan_hist_words(m, CHAIN);
+    u32* alv = reinterpret_cast<u32*>(hist + hwords);        // [mwords]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: row ranges in SGPRs
     RIOGP_KT(p, 3, 0);
@@ -471,7 +474,7 @@ __global__ __launch_bounds__(kBlock, CHAIN ? 8 : 1) void k_scan(const u32* __res
         *reinterpret_cast<uint4*>(const_cast<u32*>(load) + i) = l;
     };
 
-    for (u32 k = tid; k < 2 * m + 2; k += kBlock) hist[k] = 0;
+    for (u32 k = tid; k < hwords; k += kBlock) hist[k] = 0;
     if (!ALLALIVE || (p.alive_dst && blockIdx.x == 0))
         for (u32 k = tid; k < p.mwords; k += kBlock) {
             const u32 w = alive_bits[k];
@@ -480,7 +483,12 @@ __global__ __launch_bounds__(kBlock, CHAIN ? 8 : 1) void k_scan(const u32* __res
         }
     if (tid < 4) bst[tid] = 0;
     u64& bsum = *reinterpret_cast<u64*>(smem + 32);          // spill-candidate load of the whole block
-    if (tid == 0) bsum = 0;
+    u64& bkept = *reinterpret_cast<u64*>(smem + 40);         // CHAIN: kept load of the whole block
+    if (tid == 0) { bsum = 0; bkept = 0; }
+    if (CHAIN) {  // this workgroup's slice of the `used` buffer the link two ahead adds into (ScanChain::used_zero, every replica)
+        const u32 zw = ch.reps * m, zlo = (u32)((u64)blockIdx.x * zw / p.G), zhi = (u32)((u64)(blockIdx.x + 1) * zw / p.G);
+        for (u32 j = zlo + tid; j < zhi; j += kBlock) __hip_atomic_store(ch.used_zero + j, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (fx.dev && tid < 8) fx.dev[(size_t)blockIdx.x * 8 + tid] = 0;  // this workgroup's row of the fix-up counters
     // claim load the cuts reject, for k_fill's ordered spill prefix: row blockIdx.x of RP (by node group, written by k_resolve
     // workgroups that own cut nodes) and the cut block's correction R[blockIdx.x] (k_cut_find) start at zero
@@ -588,8 +596,10 @@ __global__ __launch_bounds__(kBlock, CHAIN ? 8 : 1) void k_scan(const u32* __res
         if (ch.per_wave && lane == 0) __hip_atomic_store(ch.flags + kMaxBlocks + gw, ch.set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (lane == 0) {
-        wsp_sum[gw] = sp_sum;
-        wsp_cnt[gw] = sp_cnt;
+        if (!CHAIN) {
+            wsp_sum[gw] = sp_sum;
+            wsp_cnt[gw] = sp_cnt;
+        }
         if (COMPACT == 1 || COMPACT == 2) pko.wcnt[gw] = (u32)(pk_pos - wstart);
         atomicAdd(&bst[0], kept_cnt);
         atomicAdd(&bst[1], evict_cnt);
@@ -601,6 +611,36 @@ __global__ __launch_bounds__(kBlock, CHAIN ? 8 : 1) void k_scan(const u32* __res
     if (CHAIN && tid == 0 && !ch.per_wave)  // this workgroup's rows are done, read and written (every wave has drained its stores in front of the
                             // barrier, and they went through to the fabric): the next tick's workgroup blockIdx.x may go
         __hip_atomic_store(ch.flags + blockIdx.x, ch.set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (CHAIN) {
+        // A quiet tick ends here: no claims, no cut, kept rows are never cut, so node j's `used` is the kept load on it — this
+        // workgroup's non-zero bins go into the tick's buffer as no-return agent-scope adds (integer sums: any order is exact) —
+        // into replica b % reps of it: the adds execute at the memory side, one at a time per line, and G workgroups adding
+        // into the same m words serialise there (ScanChain::reps)
+        u64 kl = 0;
+        u64* const ub = ch.reps ? ch.used + (size_t)(blockIdx.x % ch.reps) * m : nullptr;  // (reps 0: lab timing runs, no adds)
+        for (u32 j = tid; j < m; j += kBlock) {
+            const u64 v = hist[j];
+            if (v && ub) __hip_atomic_fetch_add(ub + j, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            kl += v;
+        }
+        kl = wave_sum(kl);
+        if (lane == 0 && kl) atomicAdd(&bkept, kl);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this thread's adds have landed (same-run: without the wait 0.1-0.3 us
+                                                          // per tick less, within the noise)
+        __syncthreads();
+        // the verdict row of this workgroup, {load_kept, 0, 0, kept, evicted, claimants, spill candidates, mark}: one 64-byte store
+        // of eight lanes, as k_resolve stores its rows (a store per word is a transaction per word to host memory: same-run, 8 of
+        // them per workgroup and a wait for the first seven took the tick from 26 to 60 us).  A claimant cannot occur under the
+        // quiet rule; if one does, its claim is in no sum — it is counted as a row to settle, so that the host refuses the tick
+        // instead of committing a wrong `used`.
+        if (tid < 8) {
+            const u64 x = tid == 0 ? bkept : tid == 3 ? (u64)bst[0] : tid == 4 ? (u64)bst[1] : tid == 5 ? (u64)bst[2]
+                        : tid == 6 ? (u64)bst[3] + bst[2] : tid == 7 ? p.mark : 0ull;
+            ch.rows[(size_t)blockIdx.x * 8 + tid] = x;
+        }
+        RIOGP_KT(p, 3, 7);
+        return;
+    }
     if (tid == 0) { bsp_sum[blockIdx.x] = bsum; bsp_cnt[blockIdx.x] = bst[3]; }
     // this block's sums, node-group major: line (g, b) = {kept of nodes 8g..8g+7 | their claim loads} — 16 consecutive
     // threads store one 128-byte line, so k_resolve's workgroup g reads G contiguous lines and nothing else
@@ -1022,6 +1062,7 @@ struct ResolveArgs {
     u64* D;            // [kFillRounds][m] per-round admitted loads of k_fill: zeroed here (nullptr: none)
     u64* fold_into;    // committed `used` still waiting for the previous committed solve's D rows: folded in before they are zeroed
     u32 fold_rounds;
+    const u64* fold_from;  // where those rows are: D, or the replicas of a chained tick's `used` buffer
     // SEARCH: the packed pending rows (affinity, load) of every wave range
     const u32* pk_aff; const u32* pk_load;
     u64* Tg;           // [m][16] claim load of a cut node's undecided rows per wave of its cut block (k_cut_apply adds, k_cut_settle
@@ -1061,7 +1102,7 @@ __global__ __launch_bounds__(SEARCH ? kBlock : 256) void k_resolve(const Resolve
         if (a.D) {
             if (a.fold_into) {
                 u64 f = a.fold_into[j];
-                for (u32 r = 0; r < a.fold_rounds; ++r) f += a.D[(size_t)r * m + j];
+                for (u32 r = 0; r < a.fold_rounds; ++r) f += a.fold_from[(size_t)r * m + j];
                 a.fold_into[j] = f;
                 if (a.kept_from == a.fold_into) kf = f;
             }
@@ -5164,8 +5205,8 @@ static inline unsigned grid_for(u64 n, unsigned block, unsigned cap) {
 template <bool VIRT, bool AA, int TPI, int COMPACT = 0, bool NT = false, bool CHAIN = false>
 static void launch_scan_t(const Plan& p, const Table& t, const NodeTab& nt, const SolveBufs& b, hipStream_t s,
                           hipEvent_t e0, hipEvent_t e1, const PackOut* pack = nullptr, const ScanChain* chain = nullptr) {
-    const ScanChain ch = chain ? *chain : ScanChain{nullptr, nullptr, 0, 0, 0};
-    const size_t lds = scan_lds_bytes(p.m) + (COMPACT == 2 ? (size_t)kWaves * 4 * kStageCap * sizeof(u32) : 0);
+    const ScanChain ch = chain ? *chain : ScanChain{};
+    const size_t lds = scan_lds_bytes_dev(p.m, CHAIN) + (COMPACT == 2 ? (size_t)kWaves * 4 * kStageCap * sizeof(u32) : 0);
     const PackOut pko = pack ? *pack : PackOut{nullptr, nullptr, nullptr, nullptr, nullptr};
     Plan pp = p;
     pp.alive_dst = nt.alive_src ? const_cast<u32*>(nt.alive_bits) : nullptr;
@@ -5207,7 +5248,7 @@ static int chain_tpi() {
 #endif
 }
 bool scan_chain_fits(u32 m) {
-    const size_t lds = scan_lds_bytes(m);
+    const size_t lds = scan_lds_bytes_dev(m, true);
     int nb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     hipError_t e = hipSuccess;
 #define RIOGP_OCC(K, AA, TPI_, NT_) if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[K], k_scan<false, AA, TPI_, 0, NT_, true>, kBlock, lds)
@@ -5313,7 +5354,8 @@ unsigned resolve_blocks(u32 m) {
 }
 
 void launch_resolve(const Plan& p, const NodeTab& nt, const SolveBufs& b, u64* host_partial, hipStream_t s,
-                    hipEvent_t e0, hipEvent_t e1, const PackOut* search, u64* fold_into, u32 fold_rounds, const u64* kept_from) {
+                    hipEvent_t e0, hipEvent_t e1, const PackOut* search, u64* fold_into, u32 fold_rounds, const u64* kept_from,
+                    const u64* fold_from) {
     const unsigned grid = resolve_blocks(p.m);
     ResolveArgs a;
     a.H = b.H; a.blkstat = b.blkstat; a.p = p;
@@ -5321,6 +5363,7 @@ void launch_resolve(const Plan& p, const NodeTab& nt, const SolveBufs& b, u64* h
     a.used_kept = b.used_kept; a.used_cur = b.used_cur; a.claim_tot = b.claim_tot; a.cutblk = b.cutblk; a.cutidx = b.cutidx;
     a.partial = b.partial; a.host_partial = host_partial; a.budget = b.budget; a.admpre = b.admpre; a.stats = b.stats;
     a.RP = b.RP; a.D = b.D; a.fold_into = b.D ? fold_into : nullptr; a.fold_rounds = fold_rounds;
+    a.fold_from = fold_from ? fold_from : b.D;
     a.pk_aff = search ? search->aff : nullptr; a.pk_load = search ? search->load : nullptr;
     a.Tg = b.Tg;
     a.kept_from = kept_from;

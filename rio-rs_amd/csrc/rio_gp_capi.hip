@@ -31,6 +31,8 @@ namespace {
 thread_local std::string g_create_error;
 struct RioGpNcclId { char internal[128]; };  // ncclUniqueId, passed BY VALUE to ncclCommInitRank
 constexpr int kRing = 64;  // in-flight async solves whose verdicts we keep
+constexpr u32 kUsedRing = 4;  // `used` buffers (rio_gp::used_ring): two chained ticks in flight, the buffers they add into and zero
+constexpr u32 kUsedReps = 32; // replicas per buffer at most (ScanChain::reps)
 
 struct DevBuf {
     void* p = nullptr;
@@ -145,6 +147,7 @@ struct rio_gp {
     u64* D = nullptr;
     bool used_parts = false;
     u32 parts_rounds = 0;
+    const u64* parts = nullptr;  // ... or the rows are here instead of D (a chained tick: replicas 1.. of its `used` buffer)
     bool solve_used_D = false;  // the solve waiting for its commit ran with sb.D set
     // solve scratch
     SolveBufs sb{};
@@ -163,6 +166,7 @@ struct rio_gp {
     // copies, so that synchronous calls made while ticks are in flight do not touch what has not been harvested yet
     u32 tick_n = 0;
     u32 tick_G[kRing] = {};  // workgroups of the streaming grid of asynchronous tick k (how many counter rows to fold)
+    u32 tick_rows[kRing] = {};  // verdict rows of asynchronous tick k: resolve_blocks(m), or G (a chained quiet tick: a row per workgroup)
     std::vector<rio_gp_stats> tick_done;
     // fix-up counters as per-workgroup rows (FxRows, placement_kernels.h): device rows + pinned slots [1 + kRing][kMaxBlocks][8]
     // (slot 0: synchronous solves, slots 1..kRing: asynchronous ticks)
@@ -206,41 +210,30 @@ struct rio_gp {
     Plan vplan{};               // the plan of the packed table the fix-up of the solve in flight runs over
     int cutpack_mode = 0;  // the same for packing at the cut pass of whole-table solves (bits 5-6 of rio_gp_debug_set_compact)
     bool ca_now = false;   // the whole-table fix-up of the solve being enqueued is k_cut_apply (set by the caller of enqueue_scan_resolve)
-    // Quiet ticks overlap (round 6): a tick that cannot need the fix-up is k_scan + k_resolve, and the NEXT tick's scan reads
-    // nothing this tick's k_resolve writes — so k_resolve runs on a stream of its own, behind an event of its scan, while the
-    // next scan already streams (H / blkstat alternate between two buffers).  Every other entry point first makes the main
-    // stream wait for the last such k_resolve (side_join, in the Locked guard every entry takes).
-    // The main stream carries nothing but the scans: each scan's completion IS its event (hipExtLaunchKernel's stop event: no
-    // marker packet behind it), and the histograms rotate through a ring of buffers as long as the ticks' ring, so a scan never
-    // has to wait for the k_resolve that read its buffer last (checked on the host; a wait is enqueued only if it is not done).
-    hipStream_t side = nullptr;
-    hipEvent_t ev_scan[kRing] = {}, ev_res[kRing] = {};
-    bool ev_res_valid[kRing] = {};
-    bool side_pending = false;
-    u32 side_last = 0, ov_count = 0, ov_bufs = 0;
-    u64* H_ring[kRing] = {}; u64* blk_ring[kRing] = {};
+    // Quiet ticks CHAIN (ScanChain, placement_kernels.h): a tick that cannot need the fix-up is one launch of the chained k_scan,
+    // which adds the per-node kept loads into the tick's `used` buffer and stores its verdict rows itself.  The scans of a run of
+    // quiet ticks alternate between the main stream and `scan2` and hand their rows over wave range by wave range (a flag per
+    // wave; per workgroup in the other form), so the ramp-down of one scan and the ramp-up of the next overlap.  A run starts on
+    // the main stream (which orders it behind everything else) and ends with the first side_join (in the Locked guard every
+    // entry takes): the main stream waits for `scan2`, and the last scan's workgroups have waited for every earlier one.
     int overlap_mode = 0;  // 0 on | 2 never (lab builds: bit 11 of rio_gp_debug_set_compact)
-    // ... and CHAIN (ScanChain, placement_kernels.h): the scans of a run of overlapped quiet ticks alternate between the main
-    // stream and `scan2` and hand their rows over wave range by wave range (a flag per wave; per workgroup in the other form), so the ramp-down of one scan and
-    // the ramp-up of the next overlap.  A run starts on the main stream (which orders it behind everything else) and ends with
-    // the first side_join: the last k_resolve waits for the last scan, and that scan's workgroups have waited for every earlier one.
     hipStream_t scan2 = nullptr;
     u32* chain_flags = nullptr;                       // [kMaxBlocks] per workgroup + [kMaxBlocks * kWaves] per wave range
     u32 *h_chain_err = nullptr, *d_chain_err = nullptr;  // mapped host word: a chained wait gave up
     u32 chain_seq = 0, chain_prev = 0, chain_pos = 0;  // last sequence number handed out | the run's last scan (0: no run) | its length
     hipEvent_t ev_run = nullptr;  // recorded on the main stream in front of a run's first scan: the run's first scan on `scan2` waits for
                                   // it, so that nothing but the two scans of the chain competes for the chip while one of them waits
-    u64 overlap_event_min_rows = (u64)1 << 22;  // ... and with its k_resolve behind events on the side stream from here on
-    u64 overlap_min_rows = (u64)1 << 18;  // (2^22 until the in-line form of the chain: below it the events cost more than they hid; lab builds,
-                                          //  RIO_GP_OVERLAP_MIN_ROWS: the parity tests run the overlapped / chained ticks on small tables)
-    // Small tables (below `inline_below` rows): the k_resolve of a chained tick goes onto ITS SCAN'S stream, right behind the scan —
-    // no event ties the two together and none ties the histogram ring to the resolves (a buffer comes round again on the same
-    // stream, 64 ticks later): a tick is two plain launches, and the host's enqueue (15.7 us per tick with the events, 7.1
-    // without) stops being what bounds a 6 us scan.  On big tables it is the wrong trade: the next scan on that stream then sits
-    // behind the resolve while its waves are needed resident (10 M rows: 28.6 against 25.5 us per tick).
-    u64 inline_below = (u64)5 << 20;  // (same-run A/Bs at 0.26 / 0.5 / 1 / 2 / 4 / 10 M rows: the two forms cross at ~5 M; lab builds: RIO_GP_CHAIN_INLINE_BELOW)
-    bool side_inline = false;     // what side_join has to join is the second scan stream (a chained run), not a k_resolve's event
+    u64 overlap_min_rows = (u64)1 << 18;  // quiet ticks of smaller tables: k_scan + k_resolve on the main stream (lab builds,
+                                          //  RIO_GP_OVERLAP_MIN_ROWS: the parity tests run the chained ticks on small tables)
     hipEvent_t ev_join = nullptr;
+    // The `used` buffers: h->used (committed) and sb.used_cur (the solve's) are the first vectors of two of the kUsedRing slots of
+    // used_ring (kUsedReps vectors each); link c of a chained run adds into slot used_base + c and zeroes slot used_base + c + 2
+    // (mod kUsedRing: ScanChain), `used_reps` replicas of m words each
+    u64* used_ring = nullptr;
+    size_t used_slot_words = 0;  // kUsedReps * cap_nodes where the chain can run, cap_nodes elsewhere
+    u32 used_base = 0;
+    u32 used_reps = 16;  // (lab builds: RIO_GP_CHAIN_REPS; 0 = no adds at all, timing runs only)
+    u64* solve_used = nullptr;  // the solve waiting for its commit built its `used` here instead of in sb.used_cur (a chained tick)
     u32 chain_per_wave = 1;       // ScanChain::per_wave: the hand-over per wave range (same-run A/B: 25.6-25.9 against 26.2-26.5 us per tick per
                                   // workgroup; lab builds: RIO_GP_CHAIN_PER_WAVE=0 for the other form)
     int chain_diag = 0;           // lab builds, RIO_GP_CHAIN_DIAG: 1 = the chained kernel on the main stream, no waits | 2 = alternating streams, no waits | 3 = every link waits
@@ -438,25 +431,18 @@ void chain_end(rio_gp* h) {
     rio_gp* me = h;
     (void)chain_owner(h).compare_exchange_strong(me, nullptr, std::memory_order_acq_rel);
 }
-// the main stream waits for the k_resolve of the last overlapped quiet tick (no-op when there is none in flight)
+// the main stream waits for the chained run in progress: what of it is not on the main stream is on `scan2` (no-op without a run)
 void side_join(rio_gp* h) {
-    if (!h->side_pending) return;
+    if (!h->chain_prev) return;
     (void)hipSetDevice(h->device);
-    if (h->side_inline) {  // a chained run with its resolves in line: what is not on the main stream is on `scan2`
-        if (h->chain_pos >= 2 &&
-            (hipEventRecord(h->ev_join, h->scan2) != hipSuccess || hipStreamWaitEvent(h->stream, h->ev_join, 0) != hipSuccess)) {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(h->scan2);
-        }
-    } else if (hipStreamWaitEvent(h->stream, h->ev_res[h->side_last], 0) != hipSuccess) {
+    if (h->chain_pos >= 2 &&
+        (hipEventRecord(h->ev_join, h->scan2) != hipSuccess || hipStreamWaitEvent(h->stream, h->ev_join, 0) != hipSuccess)) {
         (void)hipGetLastError();
-        (void)hipStreamSynchronize(h->side);
+        (void)hipStreamSynchronize(h->scan2);
     }
-    h->side_pending = false;
-    h->side_inline = false;
     chain_end(h);  // (the run of chained scans ends here: the next one starts on the main stream, behind this wait)
 }
-// what every entry point holds: the handle's mutex, with the side stream joined (rio_gp_tick_async joins only when it must)
+// what every entry point holds: the handle's mutex, with the chained run joined (rio_gp_tick_async joins only when it must)
 struct Locked {
     std::unique_lock<std::mutex> l;
     explicit Locked(rio_gp* h, bool join = true) : l(h->mu) { if (join) side_join(h); }
@@ -509,15 +495,15 @@ void enqueue_slow(rio_gp* h, const Plan& p, const Table& t, const NodeTab& nt, b
 
 // committed `used` = h->used + the D rows of the last committed solve, until they are folded in: by the next solve's
 // k_resolve (for free), or here when somebody needs the vector first
+const u64* parts_src(rio_gp* h) { return h->parts ? h->parts : h->D; }
 void fold_used(rio_gp* h) {
     if (!h->used_parts) return;
-    launch_used_fold(h->used, h->D, h->m, h->parts_rounds, h->stream);
+    launch_used_fold(h->used, parts_src(h), h->m, h->parts_rounds, h->stream);
     h->used_parts = false;
 }
 // scan + resolve of one solve over the REAL table: the packed pending rows' cuts are searched inside k_resolve, the previous
 // committed solve's D rows are folded into the committed vector before k_resolve zeroes them
-void enqueue_scan_resolve(rio_gp* h, const Table& t, const NodeTab& nt, bool compact, u64* host_rows, int inc = 0, bool overlap = false,
-                          bool chained = false) {
+void enqueue_scan_resolve(rio_gp* h, const Table& t, const NodeTab& nt, bool compact, u64* host_rows, int inc = 0) {
     h->sb.D = h->D;
     h->solve_used_D = h->sb.D != nullptr;
     h->inc_now = inc;
@@ -529,45 +515,13 @@ void enqueue_scan_resolve(rio_gp* h, const Table& t, const NodeTab& nt, bool com
     SolveBufs rb = h->sb;
     h->ca_now = h->ca_now && !compact && !inc;
     if (h->ca_now) { rb.R = nullptr; rb.RP = nullptr; rb.Tg = h->Tg; }
-    hipStream_t rs = h->stream;  // where k_resolve goes
-    hipStream_t ss = h->stream;  // where the scan goes
-    ScanChain ch{h->chain_flags, h->d_chain_err, 0, 0, h->chain_per_wave};
-    if (chained) {
-        if (!h->chain_prev) {
-            (void)hipEventRecord(h->ev_run, h->stream);
-        } else if ((h->chain_pos & 1u) && h->chain_diag != 1) {
-            ss = h->scan2;
-            if (h->chain_pos == 1) (void)hipStreamWaitEvent(ss, h->ev_run, 0);
-        }
-        ch.wait = (h->chain_diag == 3 && h->chain_prev) ? h->chain_prev + 1000u : h->chain_diag ? 0 : h->chain_prev;  // (3: a predecessor that never comes)
-        ch.set = ++h->chain_seq;
-        ++h->chain_total;
-        h->chain_prev = ch.set;
-        ++h->chain_pos;
-    }
-    u32 par = 0;
-    const bool inl = chained && h->n < h->inline_below && h->ev_join && h->chain_diag == 0;
-    if (overlap) {  // (a quiet tick: plain k_scan, no fix-up behind it — the cuts' tables are not maintained)
-        par = h->ov_count++ % h->ov_bufs;
-        rb.R = nullptr; rb.RP = nullptr; rb.Tg = nullptr;
-        rb.H = h->H_ring[par]; rb.blkstat = h->blk_ring[par];
-        // this scan rewrites the histograms the k_resolve of ov_bufs ticks ago read: done long ago (the ring of ticks is harvested
-        // at least as often) — if the runtime does not say so, the main stream waits for it
-        if (h->ev_res_valid[par] && hipEventQuery(h->ev_res[par]) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipStreamWaitEvent(ss, h->ev_res[par], 0);
-        }
-        rs = inl ? ss : h->side;
-        if (inl) h->ev_res_valid[par] = false;  // (nothing of this tick is behind an event: stream order and the run's join order it)
-    }
     if (inc) {
         // (t.cur is read AND written: the tick is committed, nobody is promised the table as it was)
         launch_inc_scan(h->plan, h->assign[h->cur], h->load, h->aff, nt, h->sb, h->pk, h->stream);
         h->vplan = rebal_plan(h->plan);
         launch_rebal(h->plan, h->vplan, h->pk, nt, h->pk2, h->sb, h->stream);
     } else {
-        launch_scan(h->plan, t, nt, rb, false, h->all_alive, ss, nullptr, (overlap && !inl) ? h->ev_scan[par] : nullptr,
-                    compact ? &h->pk : nullptr, chained ? &ch : nullptr);
+        launch_scan(h->plan, t, nt, rb, false, h->all_alive, h->stream, nullptr, nullptr, compact ? &h->pk : nullptr);
     }
     h->vplan.wcnt = compact ? pkx.wcnt : nullptr;
     // The exact cut search rides in k_resolve when a block's packed rows are few enough for a wave pair per node to stream
@@ -577,19 +531,49 @@ void enqueue_scan_resolve(rio_gp* h, const Table& t, const NodeTab& nt, bool com
     h->searched = compact && h->plan.G && h->n / h->plan.G <= kSearchMaxBlockRows;
     Plan rp = h->vplan;
     if (!h->searched) rp.wcnt = nullptr;
-    if (overlap && !inl) (void)hipStreamWaitEvent(rs, h->ev_scan[par], 0);  // (the scan's own stop event)
-    launch_resolve(rp, nt, rb, host_rows, rs, nullptr, nullptr, h->searched ? &pkx : nullptr,
-                   h->used_parts ? h->used : nullptr, h->parts_rounds, inc ? h->used : nullptr);
-    if (overlap && inl) {
-        h->side_pending = true;
-        h->side_inline = true;
-    } else if (overlap) {
-        (void)hipEventRecord(h->ev_res[par], rs);
-        h->ev_res_valid[par] = true;
-        h->side_pending = true;
-        h->side_last = par;
-    }
+    launch_resolve(rp, nt, rb, host_rows, h->stream, nullptr, nullptr, h->searched ? &pkx : nullptr,
+                   h->used_parts ? h->used : nullptr, h->parts_rounds, inc ? h->used : nullptr, parts_src(h));
     h->used_parts = false;
+}
+u64* used_slot(rio_gp* h, u32 q) { return h->used_ring + (size_t)(q % kUsedRing) * h->used_slot_words; }
+// A quiet tick as one link of a chained run: the chained k_scan alone (ScanChain, placement_kernels.h) — its workgroups add the
+// kept loads into this link's `used` buffer and store the tick's verdict rows (`rows`, one per workgroup) themselves.  Nothing of
+// the fix-up's scratch is written; the vector it builds replaces the committed one whole (commit_enqueue: its replicas 1.. are
+// folded into replica 0 later, like a solve's D rows — whatever D rows were pending are superseded).
+void enqueue_chained(rio_gp* h, const Table& t, const NodeTab& nt, u64* rows) {
+    h->solve_used_D = false;
+    h->inc_now = 0;
+    h->solve_inplace = false;
+    h->ca_now = false;
+    h->searched = false;
+    h->vplan = h->plan;
+    h->vplan.wcnt = nullptr;
+    hipStream_t ss = h->stream;
+    ScanChain ch{h->chain_flags, h->d_chain_err, 0, 0, h->chain_per_wave};
+    if (!h->chain_prev) {
+        // the run's buffers start behind the committed one; its first two links add into buffers nothing zeroes inside the run
+        h->used_base = (u32)((h->used - h->used_ring) / h->used_slot_words) + 1;
+        const size_t zb = (size_t)std::max(h->used_reps, 1u) * h->m * sizeof(u64);
+        (void)hipMemsetAsync(used_slot(h, h->used_base), 0, zb, h->stream);
+        (void)hipMemsetAsync(used_slot(h, h->used_base + 1), 0, zb, h->stream);
+        (void)hipEventRecord(h->ev_run, h->stream);
+    } else if ((h->chain_pos & 1u) && h->chain_diag != 1) {
+        ss = h->scan2;
+        if (h->chain_pos == 1) (void)hipStreamWaitEvent(ss, h->ev_run, 0);
+    }
+    ch.wait = (h->chain_diag == 3 && h->chain_prev) ? h->chain_prev + 1000u : h->chain_diag ? 0 : h->chain_prev;  // (3: a predecessor that never comes)
+    ch.set = ++h->chain_seq;
+    ch.used = used_slot(h, h->used_base + h->chain_pos);
+    ch.used_zero = used_slot(h, h->used_base + h->chain_pos + 2);
+    ch.rows = rows;
+    ch.reps = h->used_reps;
+    ++h->chain_total;
+    h->chain_prev = ch.set;
+    ++h->chain_pos;
+    SolveBufs rb = h->sb;
+    rb.R = nullptr; rb.RP = nullptr; rb.Tg = nullptr;
+    launch_scan(h->plan, t, nt, rb, false, h->all_alive, ss, nullptr, nullptr, nullptr, &ch);
+    h->solve_used = ch.used;
 }
 // the fix-up over the rows the scan packed (compact): the water-fill writes every decision through the packed rows' indices
 // into the real column itself — the other assignment column, or (k_inc_scan) the committed one
@@ -604,17 +588,21 @@ void enqueue_slow_packed(rio_gp* h, const NodeTab& nt) {
 u64* slot_dev(rio_gp* h, u32 k) { return h->d_slots + (size_t)(k % kRing) * h->slot_rows * 8; }
 constexpr u32 kTickSlot0 = (u32)kRing;  // slot index k >= kRing: the asynchronous ticks' half of the slot table
 
-// host-side fold of the per-workgroup partial rows k_resolve stored into a pinned slot
-DevStats reduce_rows(rio_gp* h, size_t slot, u32 m);
-DevStats reduce_slot(rio_gp* h, u32 k, u32 m) { return reduce_rows(h, k % kRing, m); }                    // solve ring
-DevStats reduce_tick_slot(rio_gp* h, u32 k, u32 m) { return reduce_rows(h, kTickSlot0 + k % kRing, m); }  // tick ring
-DevStats reduce_rows(rio_gp* h, size_t slot, u32 m) {
+// host-side fold of the per-workgroup partial rows k_resolve (or a chained scan) stored into a pinned slot; mark != 0: every row
+// must carry it (*bad is set where one does not)
+DevStats reduce_rows(rio_gp* h, size_t slot, u32 nrows, u64 mark = 0, bool* bad = nullptr);
+DevStats reduce_slot(rio_gp* h, u32 k, u32 m) { return reduce_rows(h, k % kRing, resolve_blocks(m)); }  // solve ring
+u64* tick_rows_host(rio_gp* h, u32 k) { return h->h_slots + (size_t)(kTickSlot0 + k % kRing) * h->slot_rows * 8; }
+DevStats reduce_tick_slot(rio_gp* h, u32 k, bool* bad) {  // tick ring
+    return reduce_rows(h, kTickSlot0 + k % kRing, h->tick_rows[k % kRing], h->tick_mark[k % kRing], bad);
+}
+DevStats reduce_rows(rio_gp* h, size_t slot, u32 nrows, u64 mark, bool* bad) {
     DevStats d;
     memset(&d, 0, sizeof d);
     const u64* rows = h->h_slots + slot * h->slot_rows * 8;
-    const unsigned nb = resolve_blocks(m);
-    for (unsigned r = 0; r < nb; ++r) {
+    for (u32 r = 0; r < nrows; ++r) {
         const u64* x = rows + (size_t)r * 8;
+        if (mark && x[7] != mark && bad) *bad = true;
         d.load_kept += x[0]; d.load_claim_tot += x[1]; d.n_cut += x[2];
         d.kept += x[3]; d.evicted += x[4]; d.claimants += x[5]; d.spillcand += x[6];
     }
@@ -675,6 +663,7 @@ struct InplaceGuard {
         h->solve_inplace = false;
         h->inc_now = 0;
         h->have_solved = false;
+        h->solve_used = nullptr;
     }
 };
 // every solve entry point that does not go through enqueue_scan_resolve starts from "not in place"
@@ -684,10 +673,20 @@ int commit_enqueue(rio_gp* h) {
     if (!h->have_solved) return fail(h, RIO_GP_EINVAL, "rio_gp_commit: no solve to commit");
     if (!h->solve_inplace) h->cur ^= 1;  // (k_inc_scan and its fix-up wrote the committed column itself)
     h->solve_inplace = false;
-    std::swap(h->used, h->sb.used_cur);  // publication = two pointer swaps: the solve's `used` vector becomes the committed one
     h->used_valid = true;
-    h->used_parts = h->solve_used_D;     // ... plus what its water-fill rounds admitted (D rows), folded in later
-    h->parts_rounds = h->rounds;
+    if (h->solve_used) {  // a chained tick: its buffer of the ring becomes the committed vector, the last committed one the solve's scratch
+        h->sb.used_cur = h->used;
+        h->used = h->solve_used;
+        h->solve_used = nullptr;
+        h->parts = h->used + h->m;  // ... plus its other replicas, folded in later
+        h->parts_rounds = h->used_reps > 1 ? h->used_reps - 1 : 0;
+        h->used_parts = h->parts_rounds > 0;
+    } else {
+        std::swap(h->used, h->sb.used_cur);  // publication = two pointer swaps: the solve's `used` vector becomes the committed one
+        h->used_parts = h->solve_used_D;     // ... plus what its water-fill rounds admitted (D rows), folded in later
+        h->parts_rounds = h->rounds;
+        h->parts = nullptr;
+    }
     h->have_solved = false;  // (not an input change: mut_epoch stays)
     return RIO_GP_OK;
 }
@@ -781,14 +780,14 @@ int commit_locked(rio_gp* h) { return commit_enqueue(h); }
 // wait for the asynchronous ticks in flight and turn their verdict slots + device-stats copies into rio_gp_stats
 // verdicts of enqueued ticks that have already landed in their pinned slots (every row carries the tick's mark): no wait
 void peek_ticks(rio_gp* h) {
-    const unsigned nb = resolve_blocks(h->m);
     for (; h->tick_peeked < h->tick_n; ++h->tick_peeked) {
         const u32 k = h->tick_peeked;
-        const volatile u64* rows = h->h_slots + (size_t)(kTickSlot0 + k) * h->slot_rows * 8;
-        for (unsigned r = 0; r < nb; ++r)
+        if (h->tick_quiet[k]) continue;  // (a quiet tick was enqueued under the quiet rule already: its verdict cannot start it)
+        const volatile u64* rows = tick_rows_host(h, k);
+        for (u32 r = 0; r < h->tick_rows[k]; ++r)
             if (rows[(size_t)r * 8 + 7] != h->tick_mark[k]) return;
         std::atomic_thread_fence(std::memory_order_acquire);
-        const DevStats v = reduce_tick_slot(h, k, h->m);
+        const DevStats v = reduce_tick_slot(h, k, nullptr);
         if (!(v.n_cut > 0 || v.spillcand > 0) && h->tick_epoch[k] == h->mut_epoch) h->quiet_epoch = h->mut_epoch;
     }
 }
@@ -796,14 +795,15 @@ void peek_ticks(rio_gp* h) {
 int harvest_ticks(rio_gp* h) {
     if (!h->tick_n) return RIO_GP_OK;
     side_join(h);
-    // When the last tick in flight is a quiet one, its k_resolve is the last kernel of everything in flight (it waited for its
-    // scan, the scan's waves for every earlier link of the chain, and the run's first link sat behind everything older on the
-    // main stream) and its verdict rows carry the tick's mark: spin on them in mapped memory instead of asking the runtime
-    // (launch + hipStreamSynchronize 12.6 us, launch + spin 7.3: tools/sync_probe.py).  Not there after 50 ms: the stream is asked.
+    // When the last tick in flight is a quiet one, the verdict rows are the last thing every tick writes (a chained scan's
+    // workgroups store theirs behind their adds; the k_resolve of a quiet tick on the main stream is its tick's last kernel) and
+    // the last tick's kernels ran behind everything older: spin on the rows of EVERY tick in flight in mapped memory instead of
+    // asking the runtime (launch + hipStreamSynchronize 12.6 us, launch + spin 7.3: tools/sync_probe.py) — the rows of two chained
+    // links land in any order.  Not there after 50 ms: the stream is asked.
     const u32 last = h->tick_n - 1;
-    if (!(h->tick_quiet[last] &&
-          spin_rows(h->h_slots + (size_t)(kTickSlot0 + last) * h->slot_rows * 8, resolve_blocks(h->m), h->tick_mark[last])))
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+    bool landed = h->tick_quiet[last];
+    for (u32 k = 0; landed && k < h->tick_n; ++k) landed = spin_rows(tick_rows_host(h, k), h->tick_rows[k], h->tick_mark[k]);
+    if (!landed) HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (h->h_chain_err && *reinterpret_cast<volatile u32*>(h->h_chain_err)) {  // never seen; must not pass silently if it happens
         *h->h_chain_err = 0;
@@ -812,7 +812,12 @@ int harvest_ticks(rio_gp* h) {
     }
     h->tick_peeked = 0;
     for (u32 k = 0; k < h->tick_n; ++k) {
-        DevStats v = reduce_tick_slot(h, k, h->m);
+        bool bad = false;
+        DevStats v = reduce_tick_slot(h, k, &bad);
+        if (bad) {  // a verdict row without its tick's mark after the stream is done: never seen; must not pass silently
+            h->tick_n = 0;
+            return fail(h, RIO_GP_EUPSTREAM, "rio_gp_tick_wait: a tick's verdict rows are incomplete (tables are stale: reload them)");
+        }
         const bool slow = v.n_cut > 0 || v.spillcand > 0;
         if (slow && h->tick_quiet[k]) {  // cannot happen (see mut_epoch); if it ever does it must not pass silently
             h->tick_n = 0;
@@ -844,27 +849,21 @@ int tick_async_locked(rio_gp* h) {
     // nothing has changed since a tick that left every object placed: this one keeps every row, no fix-up can be needed
     // (lab builds: rio_gp_debug_set_speculate(always) keeps the launches)
     const bool quiet = h->quiet_epoch == h->mut_epoch && h->spec_mode != 1;
-    // ... where it pays: the scan long enough to hide the event's cost behind it (config 2's 6 us scan lost 3-8 us per tick to it)
-    // and a histogram ring as long as the ticks' ring (64 buffers within 256 MiB: up to 1 024 nodes), so that no scan ever waits
-    // for a resolve.  Config 4 on one GPU (4 096 nodes: 16 MB of histograms per tick) was measured both ways — 16 buffers: the
-    // host runs 64 ticks ahead and every scan waits for a resolve that is itself starved beside a scan; 64 buffers (1 GB): no
-    // waits, and still 330 against 313 us per tick: a k_resolve of 512 workgroups over 16 MB beside a DRAM-bound scan costs the
-    // scan more than it saves.
-    // Tables below 2^22 rows overlap only as links of a chain with the resolves in line (two plain launches a tick: 9.4-11.5 us
-    // against 11.2-14.5 at 0.26-2 M rows); with the events of the other form they lose (15.8-17.7).
-    const bool ov_can = quiet && h->overlap_mode != 2 && h->side && h->stream == h->own_stream && h->n >= h->overlap_min_rows &&
-                        h->ov_bufs >= (u32)kRing;
+    // ... and it is one launch of the chained scan, a link of a run, on tables from overlap_min_rows rows on (below, the plain
+    // k_scan + k_resolve on the main stream)
+    const bool ov_can = quiet && h->overlap_mode != 2 && h->stream == h->own_stream && h->n >= h->overlap_min_rows;
     if (ov_can && h->chain_seq >= 0x70000000u) {  // (sequence numbers compare by signed difference: start over long before they wrap)
         side_join(h);
         (void)hipMemsetAsync(h->chain_flags, 0, (size_t)kMaxBlocks * (1 + kWaves) * sizeof(u32), h->stream);
         h->chain_seq = 0;
     }
     // (chained: a pushed liveness bitmap rides in a scan that nothing behind it may overtake — a quiet tick has none; the chained
-    //  scan addresses its columns by 32-bit byte offsets: tables below 2^30 rows, 4 GiB a column)
+    //  scan addresses its columns by 32-bit byte offsets: tables below 2^30 rows, 4 GiB a column.  Not under
+    //  RIO_GP_CFG_REF_SELF_ASSIGN: there a row whose affinity node is dead claims it again every tick — a quiet tick has
+    //  claimants, and their cut needs k_resolve)
     const bool chained = ov_can && h->chain_mode != 2 && h->scan2 && h->chain_ok && !h->alive_dirty && h->cap_rows < ((size_t)1 << 30) &&
-                         chain_begin(h);
-    const bool overlap = ov_can && (chained || h->n >= h->overlap_event_min_rows);
-    if (!overlap || (!chained && h->chain_prev)) side_join(h);
+                         !h->sa && chain_begin(h);
+    if (!chained) side_join(h);
     InplaceGuard ipg{h};
     h->plan = hplan(h, h->n);
     const Table t = real_table(h);
@@ -877,11 +876,16 @@ int tick_async_locked(rio_gp* h) {
     h->tick_epoch[k] = h->mut_epoch;
     h->tick_quiet[k] = quiet;
     h->tick_mark[k] = h->plan.mark = (1ull << 40) | ++h->wait_seq;  // column 7 of the verdict rows: peek_ticks knows them by it
-    h->ca_now = cut_apply_for(h, false);
-    enqueue_scan_resolve(h, t, nt, compact, h->d_slots + (size_t)(kTickSlot0 + k) * h->slot_rows * 8, inc_choice(h, compact, true),
-                         overlap, chained);
+    u64* const rows = h->d_slots + (size_t)(kTickSlot0 + k) * h->slot_rows * 8;
+    h->tick_rows[k] = chained ? h->plan.G : resolve_blocks(h->m);
+    if (chained) {
+        enqueue_chained(h, t, nt, rows);
+    } else {
+        h->ca_now = cut_apply_for(h, false);
+        enqueue_scan_resolve(h, t, nt, compact, rows, inc_choice(h, compact, true));
+    }
     if (quiet) {
-        // (k_scan + k_resolve only)
+        // (the chained scan, or k_scan + k_resolve)
     } else if (compact) {
         enqueue_slow_packed(h, nt);
     } else {
@@ -1007,17 +1011,9 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
         h->err = "stream/event creation failed";
         return bail(RIO_GP_EUPSTREAM);
     }
-    if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); h->side = nullptr; }
-    for (int q = 0; q < kRing && h->side; ++q)
-        if (hipEventCreate(&h->ev_scan[q]) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_res[q], hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipStreamDestroy(h->side);
-            h->side = nullptr;  // (no overlap: everything else works)
-        }
-    if (h->side && (hipStreamCreateWithFlags(&h->scan2, hipStreamNonBlocking) != hipSuccess ||
-                    hipEventCreateWithFlags(&h->ev_run, hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess)) {
+    if (hipStreamCreateWithFlags(&h->scan2, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&h->ev_run, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
         (void)hipGetLastError();
         if (h->scan2) (void)hipStreamDestroy(h->scan2);
         h->scan2 = nullptr;  // (no chain: everything else works)
@@ -1026,8 +1022,8 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
 #ifdef RIO_GP_LAB
     if (const char* e = getenv("RIO_GP_CHAIN_DIAG")) h->chain_diag = atoi(e);  // (1, 2: timing experiments only — the waits are what makes the chain correct)
     if (const char* e = getenv("RIO_GP_CHAIN_PER_WAVE")) h->chain_per_wave = (u32)atoi(e);
-    if (const char* e = getenv("RIO_GP_CHAIN_INLINE_BELOW")) h->inline_below = strtoull(e, nullptr, 10);
-    if (const char* e = getenv("RIO_GP_OVERLAP_MIN_ROWS")) h->overlap_min_rows = h->overlap_event_min_rows = strtoull(e, nullptr, 10);
+    if (const char* e = getenv("RIO_GP_OVERLAP_MIN_ROWS")) h->overlap_min_rows = strtoull(e, nullptr, 10);
+    if (const char* e = getenv("RIO_GP_CHAIN_REPS")) h->used_reps = std::min((u32)atoi(e), kUsedReps);
 #endif
     const size_t R = h->cap_rows, M = h->cap_nodes, W = (size_t)kMaxBlocks * kWaves;
     // the balanced pack columns (k_rebal) have uniform wave ranges: up to a tile per wave range more than the table; the
@@ -1035,21 +1031,14 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
     const size_t R2 = std::max((size_t)rebal_rows(h->cap_obj) + 8 * kTile, R);
 #define A(ptr, cnt) if ((rc = dalloc(h, &(ptr), (cnt))) != RIO_GP_OK) return bail(rc)
     A(h->assign[0], R); A(h->assign[1], R); A(h->load, R); A(h->aff, R); A(h->pos, R2);
-    A(h->cap, M); A(h->used, M); A(h->alive_bits, (M + 31) / 32 + 4); A(h->dead_bits, (M + 31) / 32 + 4);
+    h->used_slot_words = (h->chain_ok ? (size_t)kUsedReps : 1) * M;
+    A(h->cap, M); A(h->used_ring, kUsedRing * h->used_slot_words); A(h->alive_bits, (M + 31) / 32 + 4); A(h->dead_bits, (M + 31) / 32 + 4);
     A(h->alive_bytes, M);
     A(h->sb.H, (size_t)((M + 7) / 8) * kMaxBlocks * 16); A(h->sb.blkstat, (size_t)kMaxBlocks * 4);
-    {   // the histogram ring of overlapped quiet ticks: as many buffers as ticks may be in flight, within 256 MiB
-        const size_t hwords = (size_t)((M + 7) / 8) * kMaxBlocks * 16;
-        size_t nb = ((size_t)256 << 20) / (hwords * sizeof(u64));
-        nb = nb > (size_t)kRing ? (size_t)kRing : nb < 2 ? 2 : nb;
-        h->H_ring[0] = h->sb.H; h->blk_ring[0] = h->sb.blkstat;
-        for (size_t q = 1; q < nb; ++q) { A(h->H_ring[q], hwords); A(h->blk_ring[q], (size_t)kMaxBlocks * 4); }
-        h->ov_bufs = (u32)nb;
-    }
     A(h->sb.partial, (size_t)resolve_blocks((u32)M) * 8 + 8);
     A(h->sb.wsp_sum[0], W); A(h->sb.wsp_sum[1], W); A(h->sb.wsp_cnt[0], W); A(h->sb.wsp_cnt[1], W);
     A(h->sb.bsp_sum[0], (size_t)kMaxBlocks); A(h->sb.bsp_sum[1], (size_t)kMaxBlocks); A(h->sb.bsp_cnt[0], (size_t)kMaxBlocks); A(h->sb.bsp_cnt[1], (size_t)kMaxBlocks);
-    A(h->sb.used_kept, M); A(h->sb.used_cur, M); A(h->sb.claim_tot, M); A(h->sb.cutblk, M); A(h->sb.budget, M);
+    A(h->sb.used_kept, M); A(h->sb.claim_tot, M); A(h->sb.cutblk, M); A(h->sb.budget, M);
     A(h->sb.admpre, M); A(h->sb.cutidx, M); A(h->dstats, 1); A(h->fx_dev, (size_t)kMaxBlocks * 8);
     A(h->sb.R, (size_t)kMaxBlocks); A(h->sb.RP, (size_t)kMaxBlocks * resolve_blocks((u32)M)); A(h->D, (size_t)kFillRounds * M);
     A(h->pk.idx, R); A(h->pk.load, R); A(h->pk.aff, R); A(h->pk.next, R); A(h->pk.wcnt, W);
@@ -1059,6 +1048,8 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
     A(h->sh_lkept, M); A(h->sh_lclaim, M); A(h->sh_lcur, M); A(h->sh_lcutblk, M); A(h->sh_lcutidx, M);
     A(h->sh_gprev, M); A(h->sh_gfinal, M); A(h->sh_rank_base, 2); A(h->sh_verdict, 8); A(h->sh_forced, (M + 31) / 32 + 4);
 #undef A
+    h->used = h->used_ring;
+    h->sb.used_cur = h->used_ring + h->used_slot_words;
     h->sb.stats = h->dstats;
     if (hipHostMalloc(reinterpret_cast<void**>(&h->h_stats), sizeof(DevStats) * kRing, hipHostMallocMapped) !=
         hipSuccess) {
@@ -1071,7 +1062,7 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
         return bail(RIO_GP_ENOMEM);
     }
     memset(h->h_chain_err, 0, 64);
-    h->slot_rows = resolve_blocks(h->cap_nodes);
+    h->slot_rows = std::max<size_t>(resolve_blocks(h->cap_nodes), kMaxBlocks);  // (k_resolve's rows, or a chained scan's: one per workgroup)
     if (hipHostMalloc(reinterpret_cast<void**>(&h->h_slots), (size_t)2 * kRing * h->slot_rows * 8 * sizeof(u64),
                       hipHostMallocMapped) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(&h->h_fx), (size_t)(1 + kRing) * kMaxBlocks * 8 * sizeof(u64), hipHostMallocMapped) != hipSuccess ||
@@ -1136,7 +1127,7 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
     launch_fill_u32(h->pos, R2, kNone, h->stream);
     launch_fill_u32(h->load, R, 0, h->stream);
     launch_fill_u32(h->aff, R, kNone, h->stream);
-    (void)hipMemsetAsync(h->used, 0, M * sizeof(u64), h->stream);
+    (void)hipMemsetAsync(h->used_ring, 0, kUsedRing * h->used_slot_words * sizeof(u64), h->stream);
     (void)hipMemsetAsync(h->alive_bits, 0, ((M + 31) / 32 + 4) * sizeof(u32), h->stream);
     (void)hipMemsetAsync(h->dstats, 0, sizeof(DevStats), h->stream);
     (void)hipMemsetAsync(h->D, 0, (size_t)kFillRounds * M * sizeof(u64), h->stream);
@@ -1155,6 +1146,7 @@ void rio_gp_destroy(rio_gp_t* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->own_stream && h->own_stream != h->stream) (void)hipStreamSynchronize(h->own_stream);
+    if (h->scan2) (void)hipStreamSynchronize(h->scan2);  // (a chained run's links on the second stream, before anything is freed)
     shard_comm_free(h);
     for (void* p : h->allocs) (void)hipFree(p);
     for (auto& b : h->vt) if (b.p) (void)hipFree(b.p);
@@ -1179,11 +1171,6 @@ void rio_gp_destroy(rio_gp_t* h) {
     if (h->scan2) { (void)hipStreamSynchronize(h->scan2); (void)hipStreamDestroy(h->scan2); }
     if (h->ev_run) (void)hipEventDestroy(h->ev_run);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->side) { (void)hipStreamSynchronize(h->side); (void)hipStreamDestroy(h->side); }
-    for (int q = 0; q < kRing; ++q) {
-        if (h->ev_scan[q]) (void)hipEventDestroy(h->ev_scan[q]);
-        if (h->ev_res[q]) (void)hipEventDestroy(h->ev_res[q]);
-    }
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev2) (void)hipEventDestroy(h->ev2);
@@ -2034,6 +2021,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
         std::swap(h->used, h->sb.used_cur);
         h->used_parts = vslow;
         h->parts_rounds = h->rounds;
+        h->parts = nullptr;
         h->have_solved = false; ++h->mut_epoch;
         return RIO_GP_OK;
     }
@@ -2097,6 +2085,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
     std::swap(h->used, h->sb.used_cur);  // the solve's `used` vector becomes the committed one (as commit does): no copy
     h->used_parts = vslow && h->sb.D != nullptr;  // + what the water-fill rounds admitted (D rows), folded in later
     h->parts_rounds = h->rounds;
+    h->parts = nullptr;
     h->have_solved = false; ++h->mut_epoch;
     return RIO_GP_OK;
 }
