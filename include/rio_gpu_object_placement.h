@@ -149,6 +149,24 @@ int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const cha
                      const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens,
                      const char* const** from_addresses, const char* const** to_addresses);
 
+/* Change feed (rio_gp_changes): every placement change since this handle's last call, its creation or rio_op_changes_reset —
+ * what keeps a write-behind copy of the object_placement table (migrations/0001-sqlite-init.sql:1-9, sqlite.rs:68-85) in step
+ * without a snapshot.  Entry k is (struct_names[k], object_ids[k], old_addresses[k], new_addresses[k]); an address is NULL when
+ * the key was not placed (a node id without an address counts as not placed, as in rio_op_snapshot), so a NULL new address
+ * means "delete the key".  All entries with a NULL new address come first, then the others, each group in row order: applied
+ * in order to a mirror that equals rio_op_snapshot as of the previous call, they yield rio_op_snapshot as of now (as a set of
+ * (struct_name, object_id, server_address)).  A row handed to a new key by the table's reclaiming of dead keys gives a delete
+ * of the key the mirror holds for it and, if the row is placed, an upsert of its new key.
+ *   *full = 1 on the first call and on the first call after rio_op_changes_reset: the listing holds every placed key and no
+ *   deletes — replace the mirror instead of applying it.
+ * The arrays are owned by the calling thread until its next call of this function, as rio_op_rebalance's; key lengths come with
+ * them (a key may hold NUL bytes).  The host shadow is not touched.  A dense layer without the feed: RIO_GP_EUPSTREAM. */
+int rio_op_changes(rio_op_t* p, uint64_t* n_out, int* full, const char* const** struct_names, const size_t** struct_name_lens,
+                   const char* const** object_ids, const size_t** object_id_lens, const char* const** old_addresses,
+                   const char* const** new_addresses);
+/* Forget what the consumer was told: the next rio_op_changes is a full listing (a mirror that failed to apply a listing). */
+int rio_op_changes_reset(rio_op_t* p);
+
 /* Keys with their lengths.  ObjectId(String, String) (service_object.rs:19-26) holds any Rust string, a NUL byte included;
  * the entry points above take NUL-terminated strings and would cut such a key short.  These take struct_name / object_id
  * as (pointer, length) and are otherwise the same calls (the Rust adapter binds THESE: rio-rs_amd/rust/src/gpu.rs).

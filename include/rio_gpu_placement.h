@@ -280,6 +280,41 @@ int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebala
 int rio_gp_rebalance_dev(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebalance_stats* st, uint32_t* d_rows,
                          uint32_t* d_from, uint32_t* d_to, uint64_t moves_cap, uint64_t* n_moves);
 
+/* ---- change feed: the placements changed since the last read ---------------------------------- */
+
+#define RIO_GP_CHANGES_PEEK 1u
+
+/* The rows whose node changed since the consumer last looked: what a write-behind mirror of the table (the object_placement
+ * rows of rio-rs/src/object_placement/sqlite.rs:68-85, or a Redis / Postgres copy) needs to stay in step without reading the
+ * whole column.  The handle keeps a checkpoint column B, one u32 per row: the node the consumer was last told for that row.  B
+ * starts as RIO_GP_NONE everywhere, so the first listing holds every placed row.  A = the column rio_gp_get_assign returns at
+ * the point of the call (raw values: node ids >= m count like any other).
+ *   - A change is a row r < n with A[r] != B[r].  The listing is the first min(total, cap) changes in ascending row order:
+ *     out_rows[k] = r, out_old[k] = B[r], out_new[k] = A[r].  *n_changes = total, every change, listed or not.
+ *   - Unless flags has RIO_GP_CHANGES_PEEK, B[r] := A[r] for exactly the listed rows.  A small cap therefore pages through the
+ *     changes (every page a prefix, never RIO_GP_ERANGE), and a mirror that applies the pages in order stays consistent.
+ *   - The three arrays are given together or not at all (RIO_GP_EINVAL); without them cap must be 0: count only, nothing is
+ *     advanced.
+ *   - Nothing else changes: the table, `used`, the quiet and chained tick state, the counters and an uncommitted solve stay as
+ *     they were; B is not an input of any solve (a quiet tick before a consuming call is still quiet and chained after it).
+ *   - Like rio_gp_rows_on_nodes it orders itself behind the work in flight: the listing reflects every tick enqueued before
+ *     it, rio_gp_tick_async ticks that have not been waited for included.
+ *   - Rows >= n are not listed and keep their B.  Shrinking n (rio_gp_set_num_objects) therefore HIDES rows from the feed until
+ *     n grows again; then they are compared as usual.
+ *   - RIO_GP_EINVAL on a handle of the row-sharded solve (rio_gp_shard_*, rio_gp_p2p_*): a per-shard feed is not implemented.
+ *   - Memory: B takes 4 B per row of max_objects, allocated (filled with RIO_GP_NONE) by the first feed call and kept until
+ *     rio_gp_destroy, plus 4 B per 1 024 rows of tile counts; a handle that never calls the feed pays nothing.  The host-pointer
+ *     form also stages its listing in device memory (12 B per listed row, kept at the largest listing so far).
+ *   - Cost: one streaming pass over A and B (8 B per row) to count; a listing re-reads only the tiles of 1 024 rows that hold a
+ *     change and writes 12 B per listed row (and B for them).
+ * The _dev form writes into device arrays of cap entries and waits once.  rio_gp_changes_reset sets B := RIO_GP_NONE for every
+ * row: the next listing is complete again (a consumer that lost its mirror). */
+int rio_gp_changes(rio_gp_t* h, uint32_t flags, uint32_t* out_rows, uint32_t* out_old, uint32_t* out_new, uint64_t cap,
+                   uint64_t* n_changes);
+int rio_gp_changes_dev(rio_gp_t* h, uint32_t flags, uint32_t* d_rows, uint32_t* d_old, uint32_t* d_new, uint64_t cap,
+                       uint64_t* n_changes);
+int rio_gp_changes_reset(rio_gp_t* h);
+
 /* ---- the placement policy, batched ------------------------------------------------------ */
 
 /* Service::get_or_create_placement + check_address_mismatch (service.rs:193-298) for a batch

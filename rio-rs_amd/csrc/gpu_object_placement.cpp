@@ -59,6 +59,10 @@ extern "C" int rio_gp_rows_on_nodes(rio_gp_t* h, const uint64_t* node_bitmap, ui
 // Weak for the same reason: the bounded rebalance (rio_op_rebalance reports RIO_GP_EUPSTREAM without it).
 extern "C" int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebalance_stats* st, uint32_t* out_rows,
                                 uint32_t* out_from, uint32_t* out_to, uint64_t moves_cap, uint64_t* n_moves) __attribute__((weak));
+// Weak for the same reason: the change feed (rio_op_changes reports RIO_GP_EUPSTREAM without it).
+extern "C" int rio_gp_changes(rio_gp_t* h, uint32_t flags, uint32_t* out_rows, uint32_t* out_old, uint32_t* out_new, uint64_t cap,
+                              uint64_t* n_changes) __attribute__((weak));
+extern "C" int rio_gp_changes_reset(rio_gp_t* h) __attribute__((weak));
 
 namespace {
 
@@ -101,6 +105,12 @@ thread_local std::vector<std::string> t_rb_store;
 thread_local std::vector<const char*> t_rb_ty, t_rb_id, t_rb_from, t_rb_to;
 thread_local std::vector<size_t> t_rb_tylen, t_rb_idlen;
 thread_local std::vector<uint32_t> t_rb_rows, t_rb_src, t_rb_dst;
+
+// rio_op_changes' arrays, the same way (keys as copies; the addresses point into the node table, whose strings never change)
+thread_local std::vector<std::string> t_ch_store;
+thread_local std::vector<const char*> t_ch_ty, t_ch_id, t_ch_old, t_ch_new;
+thread_local std::vector<size_t> t_ch_tylen, t_ch_idlen;
+thread_local std::vector<uint32_t> t_ch_rows, t_ch_src, t_ch_dst;
 
 // One single-object call waiting for its device round trip (see run_combined).
 // One single-object call waiting for its device round trip (see run_combined).  The struct is a cache line of its own: its
@@ -294,6 +304,11 @@ struct State {
     uint64_t pushed_shape = 0;
     uint32_t pushed_nodes = 0;
     uint64_t pushed_rows = 0;                         // row count the device holds (rio_gp_set_num_objects)
+    // change feed (rio_op_changes): on from its first call; `full` until a listing after creation or a reset; `retired`: for
+    // every row reclaim() handed back since the last listing, the key the consumer's mirror knows for it — the FIRST key retired
+    // from the row (a later one never reached the mirror)
+    bool feed_on = false, feed_full = true;
+    std::unordered_map<uint32_t, std::pair<std::string, std::string>> retired;
     // ---
     std::atomic<int> inflight{0};                     // single-object calls between their intern and their return
     std::atomic<int> refs{1};
@@ -483,6 +498,7 @@ int reclaim(State* s) {
         if (rc == RIO_GP_OK) {
             for (uint64_t r = 0; r < n; ++r)
                 if (s->row_live[r] && !s->row_keep[r] && assign[r] == RIO_GP_NONE && aff[r] == RIO_GP_AFF_INACTIVE) {
+                    if (s->feed_on) s->retired.emplace((uint32_t)r, s->row_key[r]);  // (kept if the row was retired before)
                     s->rows.erase(key_of(s->row_key[r].first, s->row_key[r].second));
                     s->row_key[r] = std::pair<std::string, std::string>();
                     s->row_live[r] = 0;
@@ -1469,6 +1485,123 @@ int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const cha
     *from_addresses = t_rb_from.data();
     *to_addresses = t_rb_to.data();
     return RIO_GP_OK;
+}
+
+int rio_op_changes(rio_op_t* p, uint64_t* n_out, int* full, const char* const** struct_names, const size_t** struct_name_lens,
+                   const char* const** object_ids, const size_t** object_id_lens, const char* const** old_addresses,
+                   const char* const** new_addresses) {
+    if (!p || !n_out || !full || !struct_names || !struct_name_lens || !object_ids || !object_id_lens || !old_addresses ||
+        !new_addresses)
+        return RIO_GP_EINVAL;
+    State* s = p->s;
+    t_ch_store.clear();
+    t_ch_ty.clear(); t_ch_id.clear(); t_ch_old.clear(); t_ch_new.clear(); t_ch_tylen.clear(); t_ch_idlen.clear();
+    std::vector<const char*> del_old, up_old, up_new;  // addresses of the deletes / upserts (their keys: t_ch_store, deletes first)
+    std::vector<std::string> up_keys;
+    {
+        // mu keeps every device change (and reclaim()) out until the listing is matched with its keys; the shared table lock keeps
+        // the keys and the node table as they are
+        DevLock g(s);
+        std::shared_lock<TableLock> gi(s->imu);
+        int rc;
+        if ((rc = sync_device(s, true))) return rc;
+        if (!rio_gp_changes || !rio_gp_changes_reset) return fail(RIO_GP_EUPSTREAM, "dense layer has no change feed");
+        s->feed_on = true;
+        // a listing the caller does not get must not stay consumed: the next call is a full one instead
+        auto lost = [&](int code) {
+            (void)rio_gp_changes_reset(s->gp);
+            s->retired.clear();
+            s->feed_full = true;
+            return gp_fail(s, code);
+        };
+        // every change, consumed: into the thread's buffers from its last call first, the rest (a second page) with the exact size
+        uint64_t total = 0, rest = 0;
+        uint64_t cap = std::max<uint64_t>(t_ch_rows.size(), 4096);
+        t_ch_rows.resize(cap); t_ch_src.resize(cap); t_ch_dst.resize(cap);
+        if ((rc = rio_gp_changes(s->gp, 0, t_ch_rows.data(), t_ch_src.data(), t_ch_dst.data(), cap, &total))) return lost(rc);
+        uint64_t got = std::min(total, cap);
+        if (total > got) {
+            t_ch_rows.resize(total); t_ch_src.resize(total); t_ch_dst.resize(total);
+            if ((rc = rio_gp_changes(s->gp, 0, t_ch_rows.data() + got, t_ch_src.data() + got, t_ch_dst.data() + got, total - got, &rest)))
+                return lost(rc);
+            got += std::min(rest, total - got);
+        }
+        // retired rows the listing does not hold have B == A: their node now is their old node as well
+        std::vector<uint32_t> rr, rr_node;
+        for (const auto& kv : s->retired) rr.push_back(kv.first);
+        std::sort(rr.begin(), rr.end());
+        {
+            std::vector<uint32_t> miss;
+            for (uint32_t r : rr)
+                if (!std::binary_search(t_ch_rows.begin(), t_ch_rows.begin() + got, r)) miss.push_back(r);
+            rr_node.assign(miss.size(), RIO_GP_NONE);
+            if (!miss.empty() && (rc = rio_gp_lookup_batch(s->gp, miss.size(), miss.data(), rr_node.data()))) return lost(rc);
+            rr.swap(miss);
+        }
+        const uint32_t m = (uint32_t)s->node_addr.size();
+        auto addr = [&](uint32_t nd) -> const char* { return nd < m ? s->node_addr[nd].c_str() : nullptr; };
+        // one row: a retired row deletes the mirror's key and upserts its new key; any other row upserts or deletes its key
+        auto row = [&](uint32_t r, uint32_t from, uint32_t to) {
+            const char* a0 = addr(from);
+            const char* a1 = addr(to);
+            const auto it = s->retired.find(r);
+            if (it != s->retired.end()) {
+                if (a0) { t_ch_store.push_back(it->second.first); t_ch_store.push_back(it->second.second); del_old.push_back(a0); }
+                if (a1 && s->row_live[r]) {
+                    up_keys.push_back(s->row_key[r].first); up_keys.push_back(s->row_key[r].second);
+                    up_old.push_back(nullptr); up_new.push_back(a1);
+                }
+                return;
+            }
+            if (r >= s->row_live.size() || !s->row_live[r]) return;  // (a free row that was never the mirror's: unplaced on both sides)
+            if (a1) {
+                up_keys.push_back(s->row_key[r].first); up_keys.push_back(s->row_key[r].second);
+                up_old.push_back(a0); up_new.push_back(a1);
+            } else if (a0) {
+                t_ch_store.push_back(s->row_key[r].first); t_ch_store.push_back(s->row_key[r].second); del_old.push_back(a0);
+            }
+        };
+        // both lists in row order
+        size_t k = 0;
+        for (uint64_t i = 0; i < got; ++i) {
+            for (; k < rr.size() && rr[k] < t_ch_rows[i]; ++k) row(rr[k], rr_node[k], rr_node[k]);
+            row(t_ch_rows[i], t_ch_src[i], t_ch_dst[i]);
+        }
+        for (; k < rr.size(); ++k) row(rr[k], rr_node[k], rr_node[k]);
+        s->retired.clear();
+        *full = s->feed_full ? 1 : 0;
+        s->feed_full = false;
+    }
+    // deletes first, then upserts
+    const size_t nd = del_old.size();
+    for (std::string& key : up_keys) t_ch_store.push_back(std::move(key));
+    for (size_t k = 0; k + 1 < t_ch_store.size(); k += 2) {
+        t_ch_ty.push_back(t_ch_store[k].data());
+        t_ch_tylen.push_back(t_ch_store[k].size());
+        t_ch_id.push_back(t_ch_store[k + 1].data());
+        t_ch_idlen.push_back(t_ch_store[k + 1].size());
+    }
+    for (size_t k = 0; k < nd; ++k) { t_ch_old.push_back(del_old[k]); t_ch_new.push_back(nullptr); }
+    for (size_t k = 0; k < up_new.size(); ++k) { t_ch_old.push_back(up_old[k]); t_ch_new.push_back(up_new[k]); }
+    *n_out = t_ch_ty.size();
+    *struct_names = t_ch_ty.data();
+    *struct_name_lens = t_ch_tylen.data();
+    *object_ids = t_ch_id.data();
+    *object_id_lens = t_ch_idlen.data();
+    *old_addresses = t_ch_old.data();
+    *new_addresses = t_ch_new.data();
+    return RIO_GP_OK;
+}
+
+int rio_op_changes_reset(rio_op_t* p) {
+    if (!p) return RIO_GP_EINVAL;
+    State* s = p->s;
+    DevLock g(s);
+    if (!rio_gp_changes_reset) return fail(RIO_GP_EUPSTREAM, "dense layer has no change feed");
+    const int rc = rio_gp_changes_reset(s->gp);
+    s->retired.clear();
+    s->feed_full = true;
+    return rc ? gp_fail(s, rc) : RIO_GP_OK;
 }
 
 int rio_op_tick(rio_op_t* p, rio_gp_stats* stats) {

@@ -459,4 +459,23 @@ void launch_shed_round(u64 K, const u32* pk_load, u32* pk_node, const u64* tgt, 
 void launch_shed_finish(u64 K, const u32* pk_row, const u32* pk_load, const u32* pk_node, u32* assign, u64* used, u32* mc,
                         u64* acc, u32* out_rows, u32* out_from, u32* out_to, hipStream_t s);
 
+// --- change feed (rio_gp_changes): count A != B per tile, then list the changed rows of the tiles that hold one ---
+constexpr u32 kChgTile = 1024;       // rows per tile: one wave, four steps of 256 rows (lane l: rows 4l .. 4l+3 of a step)
+constexpr u32 kChgWaves = 4;         // waves per workgroup; a workgroup owns `tpg` consecutive tiles, its waves take every 4th
+constexpr u32 kChgMaxGroups = 2048;  // workgroups of a pass (k_chg_scan scans their sums)
+constexpr u32 kChgMaxTpg = 1024;     // tiles per workgroup at RIO_GP_MAX_OBJECTS rows
+struct ChgPlan {
+    u64 n;    // rows compared: 0 .. n-1
+    u32 nt;   // tiles
+    u32 tpg;  // tiles per workgroup (a multiple of kChgWaves)
+    u32 G;    // workgroups
+};
+ChgPlan chg_plan(u64 n);
+// cnt: nt u32 (per-tile counts); gsum: kChgMaxGroups + 1 u32 -> the exclusive prefix of the workgroup sums, gsum[G] = total;
+// total: a word of mapped pinned memory (the host reads it after the wait).  Two launches: the count pass, a one-workgroup scan.
+void launch_chg_count(const u32* A, const u32* B, const ChgPlan& p, u32* cnt, u32* gsum, u32* total, hipStream_t s);
+// the first `cap` changes as (row, B[row], A[row]); consume: B[row] := A[row] for the listed rows
+void launch_chg_list(const u32* A, u32* B, const ChgPlan& p, const u32* cnt, const u32* gsum, u64 cap, bool consume, u32* rows,
+                     u32* old_node, u32* new_node, hipStream_t s);
+
 }  // namespace riogp

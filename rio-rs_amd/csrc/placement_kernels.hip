@@ -6656,4 +6656,178 @@ void launch_shed_finish(u64 K, const u32* pk_row, const u32* pk_load, const u32*
     hipLaunchKernelGGL(k_shed_finish, dim3(nc), dim3(kBlock), 0, s, K, pk_row, pk_node, mc, assign, out_rows, out_from, out_to);
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Change feed (rio_gp_changes): the rows r < n whose committed node A[r] differs from the consumer's checkpoint B[r].  Three
+// launches, and no workgroup ever waits for another (nor fences: a compaction needs neither):
+//   k_chg_count  every wave counts A != B over its tiles of kChgTile rows (dwordx4 loads of both columns, ballots over the
+//                lanes' counts) and stores the per-tile counts; every workgroup stores the sum of its tiles.
+//   k_chg_scan   one workgroup: the exclusive scan of the workgroup sums, in place; the total also into mapped pinned memory.
+//   k_chg_list   a workgroup whose changes are not all past `cap` scans its own tile counts in LDS and re-streams only the tiles
+//                that hold a change.  A changed row's position = its tile's offset + the changed rows of the lower lanes in the
+//                step (three ballots over each lane's 0..4) + those of its own lane in front of it; positions >= cap are dropped.
+//                Consuming, a lane that listed a row stores its four B words back (dwordx4) with the listed ones advanced.
+// (A first form let the last workgroup of the count pass scan the sums behind an agent-scope ticket: the release / acquire
+//  around it wrote back and invalidated L2 once per workgroup, 53 us for the 80 MB of config 3.)
+// ------------------------------------------------------------------------------------------------
+// Whole tiles are read: both columns hold cap_rows = max_objects rounded up to kTile plus 8 kTile (2 048 rows) of padding, so
+// every tile of kChgTile rows that starts below n lies inside them; rows >= n are masked in chg_flags.
+__device__ __forceinline__ void chg_load(const u32* __restrict__ A, const u32* __restrict__ B, u64 lo, u32 lane, uint4 (&a)[4],
+                                         uint4 (&b)[4]) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const u64 i0 = lo + (u64)s * 256 + lane * 4;
+        a[s] = *reinterpret_cast<const uint4*>(A + i0);
+        b[s] = *reinterpret_cast<const uint4*>(B + i0);
+    }
+}
+// bit j: row i0 + j is a change (rows >= n never are)
+__device__ __forceinline__ u32 chg_flags(const uint4& a, const uint4& b, u64 i0, u64 n) {
+    return (u32)(i0 < n && a.x != b.x) | ((u32)(i0 + 1 < n && a.y != b.y) << 1) | ((u32)(i0 + 2 < n && a.z != b.z) << 2) |
+           ((u32)(i0 + 3 < n && a.w != b.w) << 3);
+}
+
+__global__ __launch_bounds__(kChgWaves * 64) void k_chg_count(const u32* __restrict__ A, const u32* __restrict__ B, const ChgPlan p,
+                                                               u32* __restrict__ cnt, u32* __restrict__ gsum) {
+    __shared__ u32 ws[kChgWaves];
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u32 t0 = blockIdx.x * p.tpg, t1 = t0 + p.tpg < p.nt ? t0 + p.tpg : p.nt;
+    u32 mine = 0;
+    for (u32 t = t0 + wv; t < t1; t += kChgWaves) {  // wave-uniform
+        const u64 lo = (u64)t * kChgTile;
+        uint4 a[4], b[4];
+        chg_load(A, B, lo, lane, a, b);
+        u32 c = 0;  // 0 .. 16
+#pragma unroll
+        for (int s = 0; s < 4; ++s) c += __builtin_popcount(chg_flags(a[s], b[s], lo + (u64)s * 256 + lane * 4, p.n));
+        u32 tc = 0;
+#pragma unroll
+        for (int bit = 0; bit < 5; ++bit) tc += (u32)__builtin_popcountll(__ballot((c >> bit) & 1u)) << bit;
+        if (lane == 0) cnt[t] = tc;
+        mine += tc;
+    }
+    if (lane == 0) ws[wv] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) gsum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+}
+
+// One workgroup: the exclusive scan of the G workgroup sums in place, gsum[G] = the total, also into the mapped word
+__global__ __launch_bounds__(kChgWaves * 64) void k_chg_scan(u32* __restrict__ gsum, u32 G, u32* total) {
+    __shared__ u32 lds[4];
+    constexpr u32 per = kChgMaxGroups / (kChgWaves * 64);
+    u32 v[per], sum = 0;
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        const u32 i = threadIdx.x * per + q;
+        v[q] = i < G ? gsum[i] : 0u;
+        sum += v[q];
+    }
+    u32 tot;
+    u32 run = ni_block_excl(sum, lds, &tot);
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        const u32 i = threadIdx.x * per + q;
+        if (i < G) gsum[i] = run;
+        run += v[q];
+    }
+    if (threadIdx.x == 0) {
+        gsum[G] = tot;
+        *total = tot;
+    }
+}
+
+__global__ __launch_bounds__(kChgWaves * 64) void k_chg_list(const u32* __restrict__ A, u32* __restrict__ B, const ChgPlan p,
+                                                              const u32* __restrict__ cnt, const u32* __restrict__ gsum, u64 cap,
+                                                              u32 consume, u32* __restrict__ rows, u32* __restrict__ old_node,
+                                                              u32* __restrict__ new_node) {
+    __shared__ u32 toff[kChgMaxTpg];
+    __shared__ u32 lds[4];
+    const u64 base = gsum[blockIdx.x];
+    if (base >= cap || gsum[blockIdx.x + 1] == base) return;  // everything past the listing, or nothing here
+    const u32 t0 = blockIdx.x * p.tpg, k = p.tpg < p.nt - t0 ? p.tpg : p.nt - t0;
+    constexpr u32 per = kChgMaxTpg / (kChgWaves * 64);
+    u32 v[per], sum = 0;
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        const u32 i = threadIdx.x * per + q;
+        v[q] = i < k ? cnt[t0 + i] : 0u;
+        sum += v[q];
+    }
+    u32 tot;
+    u32 run = ni_block_excl(sum, lds, &tot);
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        const u32 i = threadIdx.x * per + q;
+        if (i < k) toff[i] = run;
+        run += v[q];
+    }
+    __syncthreads();
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u64 lt = (1ull << lane) - 1ull;
+    for (u32 i = wv; i < k; i += kChgWaves) {  // wave-uniform
+        u64 off = base + toff[i];
+        const u32 c = (i + 1 < k ? toff[i + 1] : tot) - toff[i];
+        if (c == 0 || off >= cap) continue;
+        const u64 lo = (u64)(t0 + i) * kChgTile;
+        uint4 a[4], b[4];
+        chg_load(A, B, lo, lane, a, b);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const u64 i0 = lo + (u64)s * 256 + lane * 4;
+            const u32 f = chg_flags(a[s], b[s], i0, p.n);
+            const u32 lc = (u32)__builtin_popcount(f);  // 0 .. 4
+            u32 below = 0, all = 0;
+#pragma unroll
+            for (int bit = 0; bit < 3; ++bit) {
+                const u64 bb = __ballot((lc >> bit) & 1u);
+                below += (u32)__builtin_popcountll(bb & lt) << bit;
+                all += (u32)__builtin_popcountll(bb) << bit;
+            }
+            if (f) {
+                const u32 av[4] = {a[s].x, a[s].y, a[s].z, a[s].w};
+                u32 bv[4] = {b[s].x, b[s].y, b[s].z, b[s].w};
+                u64 r = off + below;
+                bool listed = false;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!((f >> j) & 1u)) continue;
+                    if (r < cap) {
+                        rows[r] = (u32)(i0 + j);
+                        old_node[r] = bv[j];
+                        new_node[r] = av[j];
+                        bv[j] = av[j];
+                        listed = true;
+                    }
+                    ++r;
+                }
+                if (consume && listed) *reinterpret_cast<uint4*>(B + i0) = make_uint4(bv[0], bv[1], bv[2], bv[3]);
+            }
+            off += all;
+            if (off >= cap) break;  // (wave-uniform)
+        }
+    }
+}
+
+ChgPlan chg_plan(u64 n) {
+    ChgPlan p{};
+    p.n = n;
+    p.nt = (u32)((n + kChgTile - 1) / kChgTile);
+    u32 tpg = (p.nt + kChgMaxGroups - 1) / kChgMaxGroups;
+    tpg = (tpg + kChgWaves - 1) / kChgWaves * kChgWaves;
+    p.tpg = tpg ? tpg : kChgWaves;
+    p.G = (p.nt + p.tpg - 1) / p.tpg;
+    return p;
+}
+void launch_chg_count(const u32* A, const u32* B, const ChgPlan& p, u32* cnt, u32* gsum, u32* total, hipStream_t s) {
+    if (!p.G) return;
+    hipLaunchKernelGGL(k_chg_count, dim3(p.G), dim3(kChgWaves * 64), 0, s, A, B, p, cnt, gsum);
+    hipLaunchKernelGGL(k_chg_scan, dim3(1), dim3(kChgWaves * 64), 0, s, gsum, p.G, total);
+}
+void launch_chg_list(const u32* A, u32* B, const ChgPlan& p, const u32* cnt, const u32* gsum, u64 cap, bool consume, u32* rows,
+                     u32* old_node, u32* new_node, hipStream_t s) {
+    if (!p.G || !cap) return;
+    hipLaunchKernelGGL(k_chg_list, dim3(p.G), dim3(kChgWaves * 64), 0, s, A, B, p, cnt, gsum, cap, consume ? 1u : 0u, rows,
+                       old_node, new_node);
+}
+
 }  // namespace riogp

@@ -287,6 +287,13 @@ struct rio_gp {
     // bounded rebalance (rio_gp_rebalance), grown on use: per-node arrays + counters, the (over node x tile) matrix, per-tile and
     // per-chunk counts, the packed rows (row | load | node), the host-pointer form's move listing (row | from | to)
     DevBuf sh_nodes, sh_mat, sh_tile, sh_chunk, sh_pk, sh_mv;
+    // change feed (rio_gp_changes), allocated on first use: the checkpoint column B (cap_rows u32, RIO_GP_NONE to begin with), the
+    // per-tile counts, the workgroup sums + total, a mapped word the total arrives in; the host-pointer form's staged listing
+    // (row | old | new, grows to the largest listing)
+    u32 *chg_B = nullptr, *chg_cnt = nullptr, *chg_gsum = nullptr;
+    u32* chg_Bmem = nullptr;  // B's memory, allocated; chg_B is set once it has been filled
+    u32 *h_chg = nullptr, *d_chg = nullptr;
+    DevBuf chg_stage;
     std::vector<void*> allocs;
 };
 
@@ -1157,7 +1164,9 @@ void rio_gp_destroy(rio_gp_t* h) {
     if (h->ni_rows.p) (void)hipFree(h->ni_rows.p);
     for (DevBuf* b : {&h->sh_nodes, &h->sh_mat, &h->sh_tile, &h->sh_chunk, &h->sh_pk, &h->sh_mv})
         if (b->p) (void)hipFree(b->p);
+    if (h->chg_stage.p) (void)hipFree(h->chg_stage.p);
     if (h->h_ni) (void)hipHostFree(h->h_ni);
+    if (h->h_chg) (void)hipHostFree(h->h_chg);
     if (h->h_stats) (void)hipHostFree(h->h_stats);
     if (h->h_chain_err) (void)hipHostFree(h->h_chain_err);
     if (h->h_slots) (void)hipHostFree(h->h_slots);
@@ -1665,6 +1674,113 @@ int rio_gp_rebalance_dev(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_re
     int rc;
     if ((rc = rebalance_args(h, cfg, d_rows, d_from, d_to, moves_cap, &rounds, &budget))) return rc;
     return rebalance_locked(h, cfg, rounds, budget, st, d_rows, d_from, d_to, n_moves);
+}
+
+// ---- change feed -----------------------------------------------------------------------------
+
+// The feed's state, on first use: B (RIO_GP_NONE everywhere: the first listing is complete), 4 B per tile of counts, the
+// workgroup sums and one mapped pinned word.
+static int chg_scratch(rio_gp* h) {
+    if (h->chg_B) return RIO_GP_OK;
+    const u64 tiles = (h->cap_rows + kChgTile - 1) / kChgTile;
+    int rc;
+    // (each piece once: a call after a failed allocation or fill allocates only what is still missing)
+    if (!h->chg_cnt && (rc = dalloc(h, &h->chg_cnt, tiles))) return rc;
+    if (!h->chg_gsum && (rc = dalloc(h, &h->chg_gsum, kChgMaxGroups + 1))) return rc;
+    if (!h->h_chg) {
+        if (hipHostMalloc(reinterpret_cast<void**>(&h->h_chg), 64, hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_chg), h->h_chg, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h->h_chg) (void)hipHostFree(h->h_chg);
+            h->h_chg = nullptr;
+            return fail(h, RIO_GP_ENOMEM, "hipHostMalloc(change feed word) failed");
+        }
+    }
+    if (!h->chg_Bmem && (rc = dalloc(h, &h->chg_Bmem, h->cap_rows))) return rc;
+    launch_fill_u32(h->chg_Bmem, h->cap_rows, kNone, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->chg_B = h->chg_Bmem;  // (last: it is what says the state is complete)
+    return RIO_GP_OK;
+}
+
+// checks shared by both forms: nothing is changed before they pass
+static int chg_args(rio_gp* h, uint32_t flags, const void* r, const void* o, const void* w, uint64_t cap, const uint64_t* n_changes) {
+    if (flags & ~RIO_GP_CHANGES_PEEK) return fail(h, RIO_GP_EINVAL, "rio_gp_changes: unknown flags");
+    if (!n_changes) return fail(h, RIO_GP_EINVAL, "rio_gp_changes: n_changes is NULL");
+    if ((r != nullptr) != (o != nullptr) || (r != nullptr) != (w != nullptr))
+        return fail(h, RIO_GP_EINVAL, "rio_gp_changes: out_rows / out_old / out_new are given together or not at all");
+    if (!r && cap) return fail(h, RIO_GP_EINVAL, "rio_gp_changes: cap without a listing");
+    if (h->sc || h->p2p || h->sh_tick_n)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_changes: not implemented on a handle of the row-sharded solve");
+    return RIO_GP_OK;
+}
+
+// The count pass over the committed column and B (rows 0 .. n-1); the total lands in the mapped word.  Nothing here touches the
+// table, `used`, the epochs or the chain: B is the feed's own.
+static int chg_count(rio_gp* h, const ChgPlan& p) {
+    *h->h_chg = 0;
+    launch_chg_count(h->assign[h->cur], h->chg_B, p, h->chg_cnt, h->chg_gsum, h->d_chg, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return RIO_GP_OK;
+}
+
+int rio_gp_changes(rio_gp_t* h, uint32_t flags, uint32_t* out_rows, uint32_t* out_old, uint32_t* out_new, uint64_t cap,
+                   uint64_t* n_changes) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = chg_args(h, flags, out_rows, out_old, out_new, cap, n_changes))) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = chg_scratch(h))) return rc;
+    const ChgPlan p = chg_plan(h->n);
+    if ((rc = chg_count(h, p))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 total = p.G ? *h->h_chg : 0;
+    *n_changes = total;
+    const u64 L = std::min<u64>(total, cap);
+    if (!out_rows || L == 0) return RIO_GP_OK;
+    if ((rc = ensure(h, h->chg_stage, 3 * L * sizeof(u32)))) return rc;
+    u32* d = (u32*)h->chg_stage.p;
+    launch_chg_list(h->assign[h->cur], h->chg_B, p, h->chg_cnt, h->chg_gsum, L, !(flags & RIO_GP_CHANGES_PEEK), d, d + L, d + 2 * L,
+                    h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out_rows, d, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out_old, d + L, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out_new, d + 2 * L, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RIO_GP_OK;
+}
+
+int rio_gp_changes_dev(rio_gp_t* h, uint32_t flags, uint32_t* d_rows, uint32_t* d_old, uint32_t* d_new, uint64_t cap,
+                       uint64_t* n_changes) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = chg_args(h, flags, d_rows, d_old, d_new, cap, n_changes))) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = chg_scratch(h))) return rc;
+    const ChgPlan p = chg_plan(h->n);
+    if ((rc = chg_count(h, p))) return rc;
+    // the list pass reads the prefix the count pass left on the device and drops ranks >= cap itself: one wait for the call
+    if (d_rows) launch_chg_list(h->assign[h->cur], h->chg_B, p, h->chg_cnt, h->chg_gsum, cap, !(flags & RIO_GP_CHANGES_PEEK), d_rows,
+                                d_old, d_new, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *n_changes = p.G ? *h->h_chg : 0;
+    return RIO_GP_OK;
+}
+
+int rio_gp_changes_reset(rio_gp_t* h) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (h->sc || h->p2p || h->sh_tick_n)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_changes_reset: not implemented on a handle of the row-sharded solve");
+    if (!h->chg_B) return RIO_GP_OK;  // (never used: the first listing is complete anyway)
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_fill_u32(h->chg_B, h->cap_rows, kNone, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RIO_GP_OK;
 }
 
 int rio_gp_set_num_objects(rio_gp_t* h, uint64_t n) {

@@ -22,6 +22,7 @@ OP_CFG_LIVE_FIRST_TOUCH = 4     # RIO_OP_CFG_LIVE_FIRST_TOUCH (string layer, who
 FLAG_LOCAL, FLAG_REDIRECT, FLAG_PLACED, FLAG_SPILLED, FLAG_UNPLACED = range(5)
 FLAG_REPLACED = 0x10   # OR-ed on: the object was found on a dead server, cleaned and re-placed by this request
 FLAG_MASK = 0x0F
+CHANGES_PEEK = 1       # RIO_GP_CHANGES_PEEK: list the changes without advancing the checkpoint
 OK, EINVAL, EUPSTREAM, ENODEV, ENOMEM, ERANGE, EAGAIN = range(7)
 ABI_VERSION = 2    # include/rio_gpu_placement.h RIO_GP_ABI_VERSION
 
@@ -203,6 +204,9 @@ def _load(lab):
         for nm in ("rio_gp_rebalance", "rio_gp_rebalance_dev"):
             getattr(L, nm).argtypes = [_vp, C.POINTER(RebalanceCfg), C.POINTER(RebalanceStats), _vp, _vp, _vp, C.c_uint64,
                                        C.POINTER(C.c_uint64)]
+        for nm in ("rio_gp_changes", "rio_gp_changes_dev"):
+            getattr(L, nm).argtypes = [_vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.rio_gp_changes_reset.argtypes = [_vp]
         if lab:
             L.rio_gp_debug_set_scan_nt.argtypes = [C.c_int]
             L.rio_gp_debug_set_scan_nt.restype = None
@@ -471,6 +475,45 @@ class GpuPlacement:
                                       _ptr(out_from), _ptr(out_to), int(moves_cap), C.byref(nm))
         return rc, st.as_dict(), int(nm.value)
 
+    # -- change feed --
+    def changes(self, cap=None, peek=False):
+        """rio_gp_changes: (rows, old, new, total) — the first min(total, cap) rows whose node differs from the checkpoint, in row
+        order, with the checkpoint's node and the current one (uint32 arrays); total counts every change.  cap None: all of them
+        (a count-only call first); a cap above the row count lists them all.  peek: the checkpoint does not advance.  cap 0:
+        counts only."""
+        n = C.c_uint64(0)
+        fl = CHANGES_PEEK if peek else 0
+        if cap is None:
+            self._chk(self._L.rio_gp_changes(self._h, CHANGES_PEEK, None, None, None, 0, C.byref(n)))
+            cap = int(n.value)
+        cap = min(int(cap), self.num_objects)   # a listing never holds more than n rows: no staging beyond that
+        if cap == 0:
+            self._chk(self._L.rio_gp_changes(self._h, fl, None, None, None, 0, C.byref(n)))
+            e = np.empty(0, np.uint32)
+            return e, e, e, int(n.value)
+        buf = np.empty((3, cap), np.uint32)
+        self._chk(self._L.rio_gp_changes(self._h, fl, _ptr(buf[0]), _ptr(buf[1]), _ptr(buf[2]), cap, C.byref(n)))
+        k = min(int(n.value), cap)
+        return buf[0, :k].copy(), buf[1, :k].copy(), buf[2, :k].copy(), int(n.value)
+
+    def changes_dev(self, d_rows=None, d_old=None, d_new=None, cap=0, peek=False):
+        """rio_gp_changes_dev: the first min(total, cap) changes into device arrays (ints, e.g. torch tensors' data_ptr(); all
+        None with cap 0: counts only).  Returns total."""
+        n = C.c_uint64(0)
+        self._chk(self._L.rio_gp_changes_dev(self._h, CHANGES_PEEK if peek else 0, _vp(d_rows) if d_rows else None,
+                                             _vp(d_old) if d_old else None, _vp(d_new) if d_new else None, int(cap), C.byref(n)))
+        return int(n.value)
+
+    def changes_raw(self, flags, out_rows=None, out_old=None, out_new=None, cap=0):
+        """One rio_gp_changes call as given (tests of the argument checks): (rc, total); no exception."""
+        n = C.c_uint64(0)
+        rc = self._L.rio_gp_changes(self._h, int(flags), _ptr(out_rows), _ptr(out_old), _ptr(out_new), int(cap), C.byref(n))
+        return rc, int(n.value)
+
+    def changes_reset(self):
+        """rio_gp_changes_reset: the checkpoint forgets everything; the next listing holds every placed row."""
+        self._chk(self._L.rio_gp_changes_reset(self._h))
+
     # -- policy --
     def place_pending(self, idx, requester):
         idx, requester = _u32(idx), _u32(requester)
@@ -687,12 +730,36 @@ def _oplib():
                                        C.POINTER(C.POINTER(C.c_size_t)), C.POINTER(C.POINTER(C.c_char_p)),
                                        C.POINTER(C.POINTER(C.c_size_t)), C.POINTER(C.POINTER(C.c_char_p)),
                                        C.POINTER(C.POINTER(C.c_char_p))]
+        bind_op_changes(L)
         L.rio_op_dense.argtypes = [_vp]
         L.rio_op_dense.restype = _vp
         L.rio_op_invalidate_cache.argtypes = [_vp]
         L.rio_op_device_round_trips.argtypes = [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         _op_ready = True
     return L
+
+
+def bind_op_changes(L):
+    """argtypes of rio_op_changes / rio_op_changes_reset on a library that has them (the product, or a stub-linked test build)."""
+    pp, psz = C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_size_t))
+    L.rio_op_changes.argtypes = [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), pp, psz, pp, psz, pp, pp]
+    L.rio_op_changes_reset.argtypes = [_vp]
+
+
+def op_changes(L, h):
+    """One rio_op_changes call on handle h of library L: (rc, full, [(struct_name, object_id, old_address, new_address)]) —
+    addresses None where the key was / is not placed; deletes first."""
+    n, full = C.c_uint64(0), C.c_int(0)
+    ty, oid, oa, na = (C.POINTER(C.c_char_p)() for _ in range(4))
+    tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+    rc = L.rio_op_changes(h, C.byref(n), C.byref(full), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il), C.byref(oa),
+                          C.byref(na))
+    if rc != OK:
+        return rc, False, []
+    tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))   # (c_char_p would stop at a NUL)
+    out = [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(),
+            None if oa[k] is None else oa[k].decode(), None if na[k] is None else na[k].decode()) for k in range(n.value)]
+    return rc, bool(full.value), out
 
 
 def _cstrs(items):
@@ -888,6 +955,18 @@ class GpuObjectPlacement:
         tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
         return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), fa[k].decode(), ta[k].decode())
                 for k in range(n.value)]
+
+    def changes(self):
+        """rio_op_changes: (full, [(struct_name, object_id, old_address, new_address)]) — every placement change since the last
+        call (or creation / changes_reset), deletes (new_address None) first.  full: the listing holds every placed key; replace
+        the mirror with it."""
+        rc, full, out = op_changes(_oplib(), self._h)
+        self._chk(rc)
+        return full, out
+
+    def changes_reset(self):
+        """rio_op_changes_reset: the next changes() is a full listing."""
+        self._chk(_oplib().rio_op_changes_reset(self._h))
 
     def objects_on_server(self, address):
         """rio_op_objects_on_server: every (struct_name, object_id) placed on `address` (the reverse index; [] for an address

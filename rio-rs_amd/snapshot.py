@@ -10,7 +10,8 @@ decode them either (sqlite.rs:99) and no in-tree caller writes them (service.rs:
 
 The Postgres twin (migrations/0001-postgres-init.sql) is at the end of the file.
 
-Not on the hot path: one D2H copy of the assignment column and a host loop over the interned keys.
+Not on the hot path: one D2H copy of the assignment column and a host loop over the interned keys.  sync_sqlite /
+sync_postgres are the write-behind form: they apply only what changed since the last sync (rio_op_changes).
 """
 import re
 import sqlite3
@@ -38,6 +39,45 @@ def dump_sqlite(placement, path, replace=True):
     finally:
         db.close()
     return len(rows)
+
+
+SQLITE_UPSERT = ("INSERT INTO object_placement(struct_name, object_id, server_address) VALUES (?, ?, ?) "
+                 "ON CONFLICT(struct_name, object_id) DO UPDATE SET server_address = excluded.server_address")
+SQLITE_DELETE = "DELETE FROM object_placement WHERE struct_name = ? AND object_id = ?"
+
+
+def _split_changes(entries):
+    """placement.changes() entries -> (deletes [(struct_name, object_id)], upserts [(struct_name, object_id, address)])."""
+    dels = [(e[0], e[1]) for e in entries if e[3] is None]
+    ups = [(e[0], e[1], e[3]) for e in entries if e[3] is not None]
+    return dels, ups
+
+
+def sync_sqlite(placement, path):
+    """Write-behind: apply placement.changes() (rio_op_changes) to the file in one transaction — the deletes, then the upserts
+    of sqlite.rs:68-85; a full listing (the first one, or after a reset) replaces the table's rows instead.  If anything
+    raises, the placement's feed is reset before the exception goes on, so the next sync rewrites the file in full: a change
+    is never lost silently.  Returns (upserted, deleted, full)."""
+    full, entries = placement.changes()
+    try:
+        dels, ups = _split_changes(entries)
+        db = sqlite3.connect(path)
+        try:
+            db.executescript(SCHEMA)
+            if full:
+                db.execute("DELETE FROM object_placement")
+            db.executemany(SQLITE_DELETE, dels)
+            db.executemany(SQLITE_UPSERT, ups)
+            db.commit()
+        except BaseException:
+            db.rollback()
+            raise
+        finally:
+            db.close()
+    except BaseException:
+        placement.changes_reset()
+        raise
+    return len(ups), len(dels), full
 
 
 def load_sqlite(placement, path, batch=65536):
@@ -162,6 +202,39 @@ def dump_postgres(placement, conn, replace=True, batch=65536):
         cur.executemany(PG_UPSERT, rows[i:i + batch])
     conn.commit()
     return len(rows)
+
+
+PG_DELETE = "DELETE FROM object_placement WHERE struct_name = %s AND object_id = %s"
+
+
+def sync_postgres(placement, conn, batch=65536):
+    """sync_sqlite through a DB-API connection (%s parameters): placement.changes() applied in one transaction, the feed reset
+    when the write or the commit raises.  Returns (upserted, deleted, full)."""
+    full, entries = placement.changes()
+    try:
+        dels, ups = _split_changes(entries)
+        _no_nul(ups)
+        _no_nul(dels)
+        cur = conn.cursor()
+        try:
+            for stmt in PG_SCHEMA.split(";\n"):
+                if stmt.strip():
+                    cur.execute(stmt)
+            if full:
+                cur.execute("DELETE FROM object_placement")
+            for i in range(0, len(dels), batch):
+                cur.executemany(PG_DELETE, dels[i:i + batch])
+            for i in range(0, len(ups), batch):
+                cur.executemany(PG_UPSERT, ups[i:i + batch])
+            conn.commit()
+        except BaseException:
+            if hasattr(conn, "rollback"):
+                conn.rollback()
+            raise
+    except BaseException:
+        placement.changes_reset()
+        raise
+    return len(ups), len(dels), full
 
 
 def load_postgres(placement, conn, batch=65536):
