@@ -26,15 +26,14 @@ extern "C" {
  * + (ca << 9): the whole-table fix-up by k_cut_apply + k_cut_settle (the exact cuts and the re-marking in one pass over the wave
  * ranges that have work) — 0 = when the solve packs at the cut pass (default) | 1 = always | 2 = never: k_cut_find, then the
  * re-marking pass inside round 0 of k_fill (two passes: round 5's form).
- * + 2048: the k_resolve of a quiet asynchronous tick (rio_gp_tick_async on a table nothing has changed in: k_scan + k_resolve,
- * no fix-up) stays on the main stream; by default it runs on a stream of its own beside the next tick's k_scan.
- * + 4096: the scans of such ticks are not CHAINED (every scan on the main stream, one launch after the other); by default they
- * alternate between two streams and hand their rows over wave range by wave range (ScanChain, placement_kernels.h).
+ * + 4096: a quiet asynchronous tick (rio_gp_tick_async on a table nothing has changed in) is not CHAINED: k_scan + k_resolve on
+ * the main stream, one launch after the other.  By default it is one launch of the chained k_scan, which adds the kept loads
+ * into `used` and stores the verdict rows itself; the scans of such ticks alternate between two streams and hand their rows
+ * over wave range by wave range (ScanChain, placement_kernels.h).  Bit 11 is refused (EINVAL), like every unknown bit.
  * Environment, read when a handle of the lab build is created: RIO_GP_OVERLAP_MIN_ROWS (the smallest table whose quiet ticks
- * overlap / chain; 2^18 rows in the product, 2^22 for the form without the chain), RIO_GP_CHAIN_INLINE_BELOW (tables below this
- * many rows run a chained tick's k_resolve in line behind its scan: 5 * 2^20 in the product, 0 = never), RIO_GP_CHAIN_PER_WAVE
- * (0: the hand-over per workgroup instead of per wave range), RIO_GP_CHAIN_TPI (1 | 2 tiles per wave-iteration of the chained scan),
- * RIO_GP_CHAIN_DIAG (timing experiments without the waits: NOT correct, tools/quiet_overlap_ab.py). */
+ * chain; 2^18 rows in the product), RIO_GP_CHAIN_DIAG (1: every chained scan on the main stream without the waits — NOT
+ * correct, for PMC passes, whose profiler serialises dispatches; 3: every link waits for a scan that never comes — the bounded
+ * wait's error path, tests/test_gpu_parity.py). */
 int rio_gp_debug_set_compact(rio_gp_t* h, int mode);
 /* chained scans enqueued by this handle so far (0: its quiet ticks have never met the conditions) */
 uint64_t rio_gp_debug_chained_scans(rio_gp_t* h);

@@ -173,23 +173,22 @@ struct NodeTab {
 };
 
 // Chained quiet ticks (rio_gp_tick_async over a table nothing has changed in): the scans of consecutive ticks alternate between
-// two streams and hand their rows over wave range by wave range (per workgroup in the other form) — workgroup b of tick k + 1 reads what workgroup b of tick k
-// wrote (and writes what it read), so it waits for THAT workgroup's flag instead of for the whole launch; the ramp-down of
-// one scan and the ramp-up of the next overlap.  flags[b] = `set` of the last chained scan whose workgroup b is through.
+// two streams and hand their rows over wave range by wave range — wave range w of tick k + 1 reads what wave range w of tick k
+// wrote (and writes what it read), so it waits for THAT wave's flag instead of for the whole launch; the ramp-down of
+// one scan and the ramp-up of the next overlap.  flags[w] = `set` of the last chained scan whose wave range w is through.
 // The chained scan is the whole tick: no claim can occur and kept rows are never cut, so every workgroup adds its kept loads
 // into the tick's `used` buffer and stores its own verdict row (no k_resolve behind it).  The buffers rotate through a ring of
 // four: link k adds into buffer k and zeroes buffer k + 2, which link k - 2 — finished before link k started, on the same
 // stream — added into last; the host zeroes the first two links' buffers in front of the run.
+constexpr u32 kChainReps = 16;  // replicas of a chained tick's `used` buffer (8, 16 and 32 measured within 0.5 us per tick)
 struct ScanChain {
-    u32* flags = nullptr;   // [kMaxBlocks] per workgroup, then [kMaxBlocks * kWaves] per wave range; device memory
+    u32* flags = nullptr;   // [kMaxBlocks * kWaves] one per wave range; device memory
     u32* err = nullptr;     // one word of mapped host memory: raised when a wait gave up (the tables are then stale)
     u32 wait = 0;     // sequence number of the scan to wait for (0: none — the stream orders this scan behind what it depends on)
     u32 set = 0;      // this scan's sequence number
-    u32 per_wave = 0; // the hand-over is per wave range (a flag per wave, no barrier on its path) instead of per workgroup
-    u64* used = nullptr;       // [reps][m] this tick's `used` as `reps` replicas (zero before the first add): workgroup b adds into
-                               // replica b % reps, the committed vector is their sum (the host folds replicas 1.. into replica 0 later)
-    u64* used_zero = nullptr;  // [reps][m] the buffer of the link two ahead: each workgroup zeroes its slice
-    u32 reps = 1;
+    u64* used = nullptr;       // [kChainReps][m] this tick's `used` as replicas (zero before the first add): workgroup b adds into
+                               // replica b % kChainReps, the committed vector is their sum (the host folds replicas 1.. into replica 0 later)
+    u64* used_zero = nullptr;  // [kChainReps][m] the buffer of the link two ahead: each workgroup zeroes its slice
     u64* rows = nullptr;       // [G][8] pinned verdict rows, word 7 = Plan::mark: {load_kept, 0, 0, kept, evicted, claimants,
                                // spill candidates + claimants (rows the tick cannot settle), mark}
 };

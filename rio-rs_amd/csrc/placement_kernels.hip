@@ -486,7 +486,7 @@ __global__ __launch_bounds__(kBlock, CHAIN ? 8 : 1) void k_scan(const u32* __res
     u64& bkept = *reinterpret_cast<u64*>(smem + 40);         // CHAIN: kept load of the whole block
     if (tid == 0) { bsum = 0; bkept = 0; }
     if (CHAIN) {  // this workgroup's slice of the `used` buffer the link two ahead adds into (ScanChain::used_zero, every replica)
-        const u32 zw = ch.reps * m, zlo = (u32)((u64)blockIdx.x * zw / p.G), zhi = (u32)((u64)(blockIdx.x + 1) * zw / p.G);
+        const u32 zw = kChainReps * m, zlo = (u32)((u64)blockIdx.x * zw / p.G), zhi = (u32)((u64)(blockIdx.x + 1) * zw / p.G);
         for (u32 j = zlo + tid; j < zhi; j += kBlock) __hip_atomic_store(ch.used_zero + j, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (fx.dev && tid < 8) fx.dev[(size_t)blockIdx.x * 8 + tid] = 0;  // this workgroup's row of the fix-up counters
@@ -513,16 +513,15 @@ __global__ __launch_bounds__(kBlock, CHAIN ? 8 : 1) void k_scan(const u32* __res
                 __hip_atomic_store(ch.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 break;
             }
-            if (ch.per_wave) __builtin_amdgcn_s_sleep(16); else __builtin_amdgcn_s_sleep(1);
+            __builtin_amdgcn_s_sleep(16);
         }
     };
-    // Chained quiet ticks: this workgroup's rows of `cur` are what workgroup blockIdx.x of the previous tick's scan wrote (the same
-    // plan), and its rows of `next` are what that workgroup read — it may still be running, on the other scan stream.  Wait for
-    // ITS flag, not for its launch.  (It is resident or finished: two workgroups of this kernel fit a CU and at most two launches
-    // of the chain are in flight.)  per_wave: the same per wave range — a flag per wave, no barrier on the hand-over's path.
-    if (CHAIN && tid == 0 && ch.wait && !ch.per_wave) chain_wait(ch.flags + blockIdx.x);
-    __syncthreads();
-    if (CHAIN && ch.per_wave && ch.wait && lane == 0) chain_wait(ch.flags + kMaxBlocks + gw);
+    __syncthreads();  // (the LDS set-up above is done)
+    // Chained quiet ticks: this wave's rows of `cur` are what wave range gw of the previous tick's scan wrote (the same plan), and
+    // its rows of `next` are what that wave read — it may still be running, on the other scan stream.  Wait for ITS flag, not for
+    // its launch.  (It is resident or finished: two workgroups of this kernel fit a CU and at most two launches of the chain are
+    // in flight.)  A flag per wave: no barrier on the hand-over's path.
+    if (CHAIN && ch.wait && lane == 0) chain_wait(ch.flags + gw);
     if (CHAIN && it < wgrp) {
 #pragma unroll
         for (int q = 0; q < TPI; ++q) cv[q] = ld4_fabric(crs, it + (u64)q * kTile + (u64)lane * 4);
@@ -593,7 +592,7 @@ __global__ __launch_bounds__(kBlock, CHAIN ? 8 : 1) void k_scan(const u32* __res
     if (CHAIN) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's row stores (through to the fabric) have landed — inline asm: no
                                                           // pass may decide the counter is known to be empty and drop the wait
-        if (ch.per_wave && lane == 0) __hip_atomic_store(ch.flags + kMaxBlocks + gw, ch.set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 0) __hip_atomic_store(ch.flags + gw, ch.set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the next tick's wave gw may go
     }
     if (lane == 0) {
         if (!CHAIN) {
@@ -608,19 +607,16 @@ __global__ __launch_bounds__(kBlock, CHAIN ? 8 : 1) void k_scan(const u32* __res
         if (sp_sum) atomicAdd(&bsum, sp_sum);
     }
     __syncthreads();
-    if (CHAIN && tid == 0 && !ch.per_wave)  // this workgroup's rows are done, read and written (every wave has drained its stores in front of the
-                            // barrier, and they went through to the fabric): the next tick's workgroup blockIdx.x may go
-        __hip_atomic_store(ch.flags + blockIdx.x, ch.set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (CHAIN) {
         // A quiet tick ends here: no claims, no cut, kept rows are never cut, so node j's `used` is the kept load on it — this
         // workgroup's non-zero bins go into the tick's buffer as no-return agent-scope adds (integer sums: any order is exact) —
-        // into replica b % reps of it: the adds execute at the memory side, one at a time per line, and G workgroups adding
-        // into the same m words serialise there (ScanChain::reps)
+        // into replica b % kChainReps of it: the adds execute at the memory side, one at a time per line, and G workgroups adding
+        // into the same m words serialise there
         u64 kl = 0;
-        u64* const ub = ch.reps ? ch.used + (size_t)(blockIdx.x % ch.reps) * m : nullptr;  // (reps 0: lab timing runs, no adds)
+        u64* const ub = ch.used + (size_t)(blockIdx.x % kChainReps) * m;
         for (u32 j = tid; j < m; j += kBlock) {
             const u64 v = hist[j];
-            if (v && ub) __hip_atomic_fetch_add(ub + j, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (v) __hip_atomic_fetch_add(ub + j, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             kl += v;
         }
         kl = wave_sum(kl);
@@ -5228,49 +5224,38 @@ static void launch_scan_t(const Plan& p, const Table& t, const NodeTab& nt, cons
 constexpr u64 kScanNtRows = (u64)20 << 20;  // 16 B/row * 20 Mi rows = 320 MiB of columns
 int g_scan_nt_mode = 0;  // 0 by size | 1 always | 2 never (lab builds: rio_gp_debug_set_scan_nt, A/B runs)
 int g_scan_stage = 1;    // packing through LDS rings (0: straight from registers; lab builds, A/B runs)
-int g_inc_tpi = 2;       // tiles per wave-iteration of k_inc_scan: 1 | 2 | 4 (lab builds: bits 5-6 of rio_gp_debug_set_scan_nt, A/B runs)
 void set_scan_nt(int mode) {
     g_scan_nt_mode = mode & 3;
     g_scan_stage = (mode & 16) ? 0 : 1;
-    g_inc_tpi = ((mode >> 5) & 3) == 1 ? 1 : ((mode >> 5) & 3) == 2 ? 4 : 2;
 }
 
 // Two launches of the chain are in flight at any time and the later one's workgroups WAIT, resident, for the earlier one's:
 // that cannot deadlock only if both fit the chip at once — two workgroups per CU (64 VGPRs: __launch_bounds__(kBlock, 8)).
-// Tiles per wave-iteration of the chained scan: 1 (measured, same run: 26.7-27.0 us per tick against 28.9-29.4 with 2, whose
-// 64-register form waits for a group's loads before it requests the next one)
-static int chain_tpi() {
-#ifdef RIO_GP_LAB
-    static const int v = [] { const char* e = getenv("RIO_GP_CHAIN_TPI"); return e && atoi(e) == 2 ? 2 : 1; }();
-    return v;
-#else
-    return 1;
-#endif
-}
+// One tile per wave-iteration (measured, same run: 26.7-27.0 us per tick against 28.9-29.4 with 2, whose 64-register form
+// waits for a group's loads before it requests the next one)
 bool scan_chain_fits(u32 m) {
     const size_t lds = scan_lds_bytes_dev(m, true);
-    int nb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int nb[4] = {0, 0, 0, 0};
     hipError_t e = hipSuccess;
-#define RIOGP_OCC(K, AA, TPI_, NT_) if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[K], k_scan<false, AA, TPI_, 0, NT_, true>, kBlock, lds)
-    RIOGP_OCC(0, true, 2, false); RIOGP_OCC(1, false, 2, false); RIOGP_OCC(2, true, 2, true); RIOGP_OCC(3, false, 2, true);
-    RIOGP_OCC(4, true, 1, false); RIOGP_OCC(5, false, 1, false); RIOGP_OCC(6, true, 1, true); RIOGP_OCC(7, false, 1, true);
+#define RIOGP_OCC(K, AA, NT_) if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[K], k_scan<false, AA, 1, 0, NT_, true>, kBlock, lds)
+    RIOGP_OCC(0, true, false); RIOGP_OCC(1, false, false); RIOGP_OCC(2, true, true); RIOGP_OCC(3, false, true);
 #undef RIOGP_OCC
     if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    for (int k = 0; k < 8; ++k) if (nb[k] < 2) return false;
+    for (int k = 0; k < 4; ++k) if (nb[k] < 2) return false;
     return true;
 }
 
 void launch_scan(const Plan& p, const Table& t, const NodeTab& nt, const SolveBufs& b, bool virt, bool all_alive,
                  hipStream_t s, hipEvent_t e0, hipEvent_t e1, const PackOut* pack, const ScanChain* chain) {
-    if (chain && !pack && !virt) {  // a chained quiet tick: the plain whole-table scan, handed over workgroup by workgroup
+    if (chain && !pack && !virt) {  // a chained quiet tick: the plain whole-table scan, handed over wave range by wave range
         const bool ntl = g_scan_nt_mode == 1 || (g_scan_nt_mode == 0 && p.n >= kScanNtRows);
-#define RIOGP_CH(TPI_) do { \
-            if (ntl) { if (all_alive) launch_scan_t<false, true, TPI_, 0, true, true>(p, t, nt, b, s, e0, e1, nullptr, chain); \
-                       else launch_scan_t<false, false, TPI_, 0, true, true>(p, t, nt, b, s, e0, e1, nullptr, chain); } \
-            else { if (all_alive) launch_scan_t<false, true, TPI_, 0, false, true>(p, t, nt, b, s, e0, e1, nullptr, chain); \
-                   else launch_scan_t<false, false, TPI_, 0, false, true>(p, t, nt, b, s, e0, e1, nullptr, chain); } } while (0)
-        if (chain_tpi() == 1) RIOGP_CH(1); else RIOGP_CH(2);
-#undef RIOGP_CH
+        if (ntl) {
+            if (all_alive) launch_scan_t<false, true, 1, 0, true, true>(p, t, nt, b, s, e0, e1, nullptr, chain);
+            else launch_scan_t<false, false, 1, 0, true, true>(p, t, nt, b, s, e0, e1, nullptr, chain);
+        } else {
+            if (all_alive) launch_scan_t<false, true, 1, 0, false, true>(p, t, nt, b, s, e0, e1, nullptr, chain);
+            else launch_scan_t<false, false, 1, 0, false, true>(p, t, nt, b, s, e0, e1, nullptr, chain);
+        }
         return;
     }
     if (pack && !virt) {  // k_scan that also packs the pending rows of every wave (adaptive fix-up, rio_gp_capi.hip)
@@ -5321,11 +5306,9 @@ void launch_inc_scan(const Plan& p, u32* assign, const u32* load, const u32* aff
     pp.alive_dst = nt.alive_src ? const_cast<u32*>(nt.alive_bits) : nullptr;
     const u32* abits = nt.alive_src ? nt.alive_src : nt.alive_bits;
     const bool ntl = g_scan_nt_mode == 1 || (g_scan_nt_mode == 0 && p.n >= kScanNtRows);
-#define RIOGP_INC(TPI_, NT_) hipLaunchKernelGGL((k_inc_scan<TPI_, NT_>), dim3(p.G), dim3(kBlock), lds, s, assign, load, aff, abits, pp, \
-                                                b.blkstat, b.stats, pack, b.fx, b.R, b.RP)
-    if (g_inc_tpi == 1) { if (ntl) RIOGP_INC(1, true); else RIOGP_INC(1, false); }
-    else if (g_inc_tpi == 4) { if (ntl) RIOGP_INC(4, true); else RIOGP_INC(4, false); }
-    else { if (ntl) RIOGP_INC(2, true); else RIOGP_INC(2, false); }
+#define RIOGP_INC(NT_) hipLaunchKernelGGL((k_inc_scan<2, NT_>), dim3(p.G), dim3(kBlock), lds, s, assign, load, aff, abits, pp, \
+                                          b.blkstat, b.stats, pack, b.fx, b.R, b.RP)
+    if (ntl) RIOGP_INC(true); else RIOGP_INC(false);
 #undef RIOGP_INC
 }
 // The balanced table of the rows k_inc_scan packed: uniform wave ranges of ceil(tiles / nw) tiles each, as many

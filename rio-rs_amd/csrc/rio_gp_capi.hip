@@ -32,7 +32,6 @@ thread_local std::string g_create_error;
 struct RioGpNcclId { char internal[128]; };  // ncclUniqueId, passed BY VALUE to ncclCommInitRank
 constexpr int kRing = 64;  // in-flight async solves whose verdicts we keep
 constexpr u32 kUsedRing = 4;  // `used` buffers (rio_gp::used_ring): two chained ticks in flight, the buffers they add into and zero
-constexpr u32 kUsedReps = 32; // replicas per buffer at most (ScanChain::reps)
 
 struct DevBuf {
     void* p = nullptr;
@@ -213,12 +212,11 @@ struct rio_gp {
     // Quiet ticks CHAIN (ScanChain, placement_kernels.h): a tick that cannot need the fix-up is one launch of the chained k_scan,
     // which adds the per-node kept loads into the tick's `used` buffer and stores its verdict rows itself.  The scans of a run of
     // quiet ticks alternate between the main stream and `scan2` and hand their rows over wave range by wave range (a flag per
-    // wave; per workgroup in the other form), so the ramp-down of one scan and the ramp-up of the next overlap.  A run starts on
-    // the main stream (which orders it behind everything else) and ends with the first side_join (in the Locked guard every
-    // entry takes): the main stream waits for `scan2`, and the last scan's workgroups have waited for every earlier one.
-    int overlap_mode = 0;  // 0 on | 2 never (lab builds: bit 11 of rio_gp_debug_set_compact)
+    // wave), so the ramp-down of one scan and the ramp-up of the next overlap.  A run starts on the main stream (which orders it
+    // behind everything else) and ends with the first chain_join (in the Locked guard every entry takes): the main stream waits
+    // for `scan2`, and the last scan's waves have waited for every earlier one.
     hipStream_t scan2 = nullptr;
-    u32* chain_flags = nullptr;                       // [kMaxBlocks] per workgroup + [kMaxBlocks * kWaves] per wave range
+    u32* chain_flags = nullptr;                       // [kMaxBlocks * kWaves] one per wave range
     u32 *h_chain_err = nullptr, *d_chain_err = nullptr;  // mapped host word: a chained wait gave up
     u32 chain_seq = 0, chain_prev = 0, chain_pos = 0;  // last sequence number handed out | the run's last scan (0: no run) | its length
     hipEvent_t ev_run = nullptr;  // recorded on the main stream in front of a run's first scan: the run's first scan on `scan2` waits for
@@ -227,17 +225,15 @@ struct rio_gp {
                                           //  RIO_GP_OVERLAP_MIN_ROWS: the parity tests run the chained ticks on small tables)
     hipEvent_t ev_join = nullptr;
     // The `used` buffers: h->used (committed) and sb.used_cur (the solve's) are the first vectors of two of the kUsedRing slots of
-    // used_ring (kUsedReps vectors each); link c of a chained run adds into slot used_base + c and zeroes slot used_base + c + 2
-    // (mod kUsedRing: ScanChain), `used_reps` replicas of m words each
+    // used_ring; link c of a chained run adds into slot used_base + c and zeroes slot used_base + c + 2 (mod kUsedRing:
+    // ScanChain), kChainReps replicas of m words each
     u64* used_ring = nullptr;
-    size_t used_slot_words = 0;  // kUsedReps * cap_nodes where the chain can run, cap_nodes elsewhere
+    size_t used_slot_words = 0;  // kChainReps * cap_nodes where the chain can run, cap_nodes elsewhere
     u32 used_base = 0;
-    u32 used_reps = 16;  // (lab builds: RIO_GP_CHAIN_REPS; 0 = no adds at all, timing runs only)
     u64* solve_used = nullptr;  // the solve waiting for its commit built its `used` here instead of in sb.used_cur (a chained tick)
-    u32 chain_per_wave = 1;       // ScanChain::per_wave: the hand-over per wave range (same-run A/B: 25.6-25.9 against 26.2-26.5 us per tick per
-                                  // workgroup; lab builds: RIO_GP_CHAIN_PER_WAVE=0 for the other form)
-    int chain_diag = 0;           // lab builds, RIO_GP_CHAIN_DIAG: 1 = the chained kernel on the main stream, no waits | 2 = alternating streams, no waits | 3 = every link waits
-                                  // for a sequence number nobody will ever store (the bounded spin and the error path under test)
+    int chain_diag = 0;           // lab builds, RIO_GP_CHAIN_DIAG: 1 = the chained kernel on the main stream, no waits (PMC passes: the
+                                  // profiler serialises dispatches) | 3 = every link waits for a sequence number nobody will ever
+                                  // store (the bounded spin and the error path under test)
     bool chain_ok = false;        // two workgroups of the chained scan fit a CU (scan_chain_fits at the table's node count)
     u64 chain_total = 0;   // chained scans enqueued so far (lab builds: rio_gp_debug_chained_scans)
     int chain_mode = 0;    // 0 on | 2 never (lab builds: bit 12 of rio_gp_debug_set_compact)
@@ -439,7 +435,7 @@ void chain_end(rio_gp* h) {
     (void)chain_owner(h).compare_exchange_strong(me, nullptr, std::memory_order_acq_rel);
 }
 // the main stream waits for the chained run in progress: what of it is not on the main stream is on `scan2` (no-op without a run)
-void side_join(rio_gp* h) {
+void chain_join(rio_gp* h) {
     if (!h->chain_prev) return;
     (void)hipSetDevice(h->device);
     if (h->chain_pos >= 2 &&
@@ -452,7 +448,7 @@ void side_join(rio_gp* h) {
 // what every entry point holds: the handle's mutex, with the chained run joined (rio_gp_tick_async joins only when it must)
 struct Locked {
     std::unique_lock<std::mutex> l;
-    explicit Locked(rio_gp* h, bool join = true) : l(h->mu) { if (join) side_join(h); }
+    explicit Locked(rio_gp* h, bool join = true) : l(h->mu) { if (join) chain_join(h); }
 };
 bool use_cut_apply(rio_gp* h, u32 m) { return h->cutapply_mode != 2 && !h->sb.forced_bits && cut_apply_fits(m); }
 // ... which it is when the solve packs at the cut pass (few rows go on to the water-fill: the ranges with work are a fraction of
@@ -556,11 +552,11 @@ void enqueue_chained(rio_gp* h, const Table& t, const NodeTab& nt, u64* rows) {
     h->vplan = h->plan;
     h->vplan.wcnt = nullptr;
     hipStream_t ss = h->stream;
-    ScanChain ch{h->chain_flags, h->d_chain_err, 0, 0, h->chain_per_wave};
+    ScanChain ch{h->chain_flags, h->d_chain_err};
     if (!h->chain_prev) {
         // the run's buffers start behind the committed one; its first two links add into buffers nothing zeroes inside the run
         h->used_base = (u32)((h->used - h->used_ring) / h->used_slot_words) + 1;
-        const size_t zb = (size_t)std::max(h->used_reps, 1u) * h->m * sizeof(u64);
+        const size_t zb = (size_t)kChainReps * h->m * sizeof(u64);
         (void)hipMemsetAsync(used_slot(h, h->used_base), 0, zb, h->stream);
         (void)hipMemsetAsync(used_slot(h, h->used_base + 1), 0, zb, h->stream);
         (void)hipEventRecord(h->ev_run, h->stream);
@@ -568,12 +564,11 @@ void enqueue_chained(rio_gp* h, const Table& t, const NodeTab& nt, u64* rows) {
         ss = h->scan2;
         if (h->chain_pos == 1) (void)hipStreamWaitEvent(ss, h->ev_run, 0);
     }
-    ch.wait = (h->chain_diag == 3 && h->chain_prev) ? h->chain_prev + 1000u : h->chain_diag ? 0 : h->chain_prev;  // (3: a predecessor that never comes)
+    ch.wait = !h->chain_prev || h->chain_diag == 1 ? 0 : h->chain_diag == 3 ? h->chain_prev + 1000u : h->chain_prev;  // (3: a predecessor that never comes)
     ch.set = ++h->chain_seq;
     ch.used = used_slot(h, h->used_base + h->chain_pos);
     ch.used_zero = used_slot(h, h->used_base + h->chain_pos + 2);
     ch.rows = rows;
-    ch.reps = h->used_reps;
     ++h->chain_total;
     h->chain_prev = ch.set;
     ++h->chain_pos;
@@ -686,8 +681,8 @@ int commit_enqueue(rio_gp* h) {
         h->used = h->solve_used;
         h->solve_used = nullptr;
         h->parts = h->used + h->m;  // ... plus its other replicas, folded in later
-        h->parts_rounds = h->used_reps > 1 ? h->used_reps - 1 : 0;
-        h->used_parts = h->parts_rounds > 0;
+        h->parts_rounds = kChainReps - 1;
+        h->used_parts = true;
     } else {
         std::swap(h->used, h->sb.used_cur);  // publication = two pointer swaps: the solve's `used` vector becomes the committed one
         h->used_parts = h->solve_used_D;     // ... plus what its water-fill rounds admitted (D rows), folded in later
@@ -801,7 +796,7 @@ void peek_ticks(rio_gp* h) {
 
 int harvest_ticks(rio_gp* h) {
     if (!h->tick_n) return RIO_GP_OK;
-    side_join(h);
+    chain_join(h);
     // When the last tick in flight is a quiet one, the verdict rows are the last thing every tick writes (a chained scan's
     // workgroups store theirs behind their adds; the k_resolve of a quiet tick on the main stream is its tick's last kernel) and
     // the last tick's kernels ran behind everything older: spin on the rows of EVERY tick in flight in mapped memory instead of
@@ -858,10 +853,10 @@ int tick_async_locked(rio_gp* h) {
     const bool quiet = h->quiet_epoch == h->mut_epoch && h->spec_mode != 1;
     // ... and it is one launch of the chained scan, a link of a run, on tables from overlap_min_rows rows on (below, the plain
     // k_scan + k_resolve on the main stream)
-    const bool ov_can = quiet && h->overlap_mode != 2 && h->stream == h->own_stream && h->n >= h->overlap_min_rows;
+    const bool ov_can = quiet && h->stream == h->own_stream && h->n >= h->overlap_min_rows;
     if (ov_can && h->chain_seq >= 0x70000000u) {  // (sequence numbers compare by signed difference: start over long before they wrap)
-        side_join(h);
-        (void)hipMemsetAsync(h->chain_flags, 0, (size_t)kMaxBlocks * (1 + kWaves) * sizeof(u32), h->stream);
+        chain_join(h);
+        (void)hipMemsetAsync(h->chain_flags, 0, (size_t)kMaxBlocks * kWaves * sizeof(u32), h->stream);
         h->chain_seq = 0;
     }
     // (chained: a pushed liveness bitmap rides in a scan that nothing behind it may overtake — a quiet tick has none; the chained
@@ -870,7 +865,7 @@ int tick_async_locked(rio_gp* h) {
     //  claimants, and their cut needs k_resolve)
     const bool chained = ov_can && h->chain_mode != 2 && h->scan2 && h->chain_ok && !h->alive_dirty && h->cap_rows < ((size_t)1 << 30) &&
                          !h->sa && chain_begin(h);
-    if (!chained) side_join(h);
+    if (!chained) chain_join(h);
     InplaceGuard ipg{h};
     h->plan = hplan(h, h->n);
     const Table t = real_table(h);
@@ -1027,10 +1022,8 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
     }
     h->chain_ok = h->scan2 && scan_chain_fits((u32)h->cap_nodes);
 #ifdef RIO_GP_LAB
-    if (const char* e = getenv("RIO_GP_CHAIN_DIAG")) h->chain_diag = atoi(e);  // (1, 2: timing experiments only — the waits are what makes the chain correct)
-    if (const char* e = getenv("RIO_GP_CHAIN_PER_WAVE")) h->chain_per_wave = (u32)atoi(e);
+    if (const char* e = getenv("RIO_GP_CHAIN_DIAG")) h->chain_diag = atoi(e);  // (1: PMC passes only — the waits are what makes the chain correct)
     if (const char* e = getenv("RIO_GP_OVERLAP_MIN_ROWS")) h->overlap_min_rows = strtoull(e, nullptr, 10);
-    if (const char* e = getenv("RIO_GP_CHAIN_REPS")) h->used_reps = std::min((u32)atoi(e), kUsedReps);
 #endif
     const size_t R = h->cap_rows, M = h->cap_nodes, W = (size_t)kMaxBlocks * kWaves;
     // the balanced pack columns (k_rebal) have uniform wave ranges: up to a tile per wave range more than the table; the
@@ -1038,7 +1031,7 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
     const size_t R2 = std::max((size_t)rebal_rows(h->cap_obj) + 8 * kTile, R);
 #define A(ptr, cnt) if ((rc = dalloc(h, &(ptr), (cnt))) != RIO_GP_OK) return bail(rc)
     A(h->assign[0], R); A(h->assign[1], R); A(h->load, R); A(h->aff, R); A(h->pos, R2);
-    h->used_slot_words = (h->chain_ok ? (size_t)kUsedReps : 1) * M;
+    h->used_slot_words = (h->chain_ok ? (size_t)kChainReps : 1) * M;
     A(h->cap, M); A(h->used_ring, kUsedRing * h->used_slot_words); A(h->alive_bits, (M + 31) / 32 + 4); A(h->dead_bits, (M + 31) / 32 + 4);
     A(h->alive_bytes, M);
     A(h->sb.H, (size_t)((M + 7) / 8) * kMaxBlocks * 16); A(h->sb.blkstat, (size_t)kMaxBlocks * 4);
@@ -1051,7 +1044,7 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
     A(h->pk.idx, R); A(h->pk.load, R); A(h->pk.aff, R); A(h->pk.next, R); A(h->pk.wcnt, W);
     A(h->pk2.idx, R2); A(h->pk2.load, R2); A(h->pk2.aff, R2); A(h->pk2.next, R2); A(h->pk2.wcnt, W);
     A(h->Tg, M * kWaves);
-    A(h->chain_flags, (size_t)kMaxBlocks * (1 + kWaves));
+    A(h->chain_flags, W);
     A(h->sh_lkept, M); A(h->sh_lclaim, M); A(h->sh_lcur, M); A(h->sh_lcutblk, M); A(h->sh_lcutidx, M);
     A(h->sh_gprev, M); A(h->sh_gfinal, M); A(h->sh_rank_base, 2); A(h->sh_verdict, 8); A(h->sh_forced, (M + 31) / 32 + 4);
 #undef A
@@ -1139,7 +1132,7 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
     (void)hipMemsetAsync(h->dstats, 0, sizeof(DevStats), h->stream);
     (void)hipMemsetAsync(h->D, 0, (size_t)kFillRounds * M * sizeof(u64), h->stream);
     (void)hipMemsetAsync(h->sb.R, 0, (size_t)kMaxBlocks * sizeof(u64), h->stream);
-    (void)hipMemsetAsync(h->chain_flags, 0, (size_t)kMaxBlocks * (1 + kWaves) * sizeof(u32), h->stream);
+    (void)hipMemsetAsync(h->chain_flags, 0, W * sizeof(u32), h->stream);
     if (hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
         h->err = "initial fill failed (no gfx950 code object loaded?)";
         return bail(RIO_GP_EUPSTREAM);
@@ -3259,7 +3252,7 @@ uint64_t rio_gp_debug_wave_row_lo(uint64_t n_objects, uint32_t n_nodes, uint32_t
 }
 
 int rio_gp_debug_set_compact(rio_gp_t* h, int mode) {
-    if (!h || mode < 0 || mode >= 8192 || (mode & 15) > 2 || ((mode >> 5) & 3) == 3) return RIO_GP_EINVAL;  // nothing is changed
+    if (!h || mode < 0 || mode >= 8192 || (mode & 2048) || (mode & 15) > 2 || ((mode >> 5) & 3) == 3) return RIO_GP_EINVAL;  // nothing is changed
     Locked g(h);
     h->part_mode = (mode & 16) ? 2 : 0;  // bit 4: big update / remove batches through the plain kernels (A/B runs, parity tests)
     h->cutpack_mode = (mode >> 5) & 3;   // bits 5-6: packing at the cut pass of whole-table solves, 0 auto | 1 always | 2 never
@@ -3268,8 +3261,7 @@ int rio_gp_debug_set_compact(rio_gp_t* h, int mode) {
     if (h->inc_mode == 3) h->inc_mode = 0;
     h->cutapply_mode = (mode >> 9) & 3;  // bits 9-10: 0 = k_cut_apply when the solve packs at the cut pass | 1 = always | 2 = never
     if (h->cutapply_mode == 3) h->cutapply_mode = 0;
-    h->overlap_mode = (mode & 2048) ? 2 : 0;  // bit 11: quiet ticks do not overlap (k_resolve on the main stream, as before round 6)
-    h->chain_mode = (mode & 4096) ? 2 : 0;    // bit 12: overlapped quiet ticks are not chained (every scan on the main stream)
+    h->chain_mode = (mode & 4096) ? 2 : 0;  // bit 12: quiet ticks are not chained (k_scan + k_resolve on the main stream)
     return RIO_GP_OK;
 }
 

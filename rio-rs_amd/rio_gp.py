@@ -613,7 +613,7 @@ class GpuPlacement:
         self._chk(self._L.rio_gp_debug_ktrace(self._h, 1 if enable else 0, 0 if table is None else table, out))
         return np.ctypeslib.as_array(out).reshape(256, 8).copy() if table is not None else None
 
-    def set_compact(self, mode, partitioned_crud=True, cut_pack="auto", inc="auto", cut_apply="auto", overlap=True, chain=True):
+    def set_compact(self, mode, partitioned_crud=True, cut_pack="auto", inc="auto", cut_apply="auto", chain=True):
         """0 adaptive | 1 always | 2 never: packed fix-up (results identical in every mode).  partitioned_crud=False: big
         update / remove batches through the plain per-entry kernels (A/B runs, parity tests).  cut_pack: the same three
         modes for packing at the cut pass of whole-table solves (round 0 of k_fill packs).  inc: the in-place scan of
@@ -621,19 +621,18 @@ class GpuPlacement:
         fix-up's workgroups) — "auto": whenever the packed fix-up is used and `used` is valid | "never": k_scan<COMPACT>.
         cut_apply: whole-table fix-up — "auto": k_cut_apply + k_cut_settle (exact cuts + re-marking in one pass over the wave
         ranges that have work) when the solve packs at the cut pass | "always" | "never": k_cut_find, then the re-marking pass
-        inside round 0 of k_fill (round 5's form).  overlap=False: the k_resolve of a quiet asynchronous tick stays on the main
-        stream (it runs beside the next tick's scan otherwise).  chain=False: the scans of overlapped quiet ticks all go onto
-        the main stream (by default they alternate between two streams and hand their rows over workgroup by workgroup)."""
+        inside round 0 of k_fill (round 5's form).  chain=False: a quiet asynchronous tick is k_scan + k_resolve on the main
+        stream (by default it is one launch of the chained scan: the scans of such ticks alternate between two streams and hand
+        their rows over wave range by wave range)."""
         self._need_lab()
         modes = {"auto": 0, "always": 1, "never": 2}
         incs = {"auto": 0, "always": 1, "never": 2}   # ("always" = "auto" since the size limit of the in-place tick went)
         self._chk(self._L.rio_gp_debug_set_compact(self._h, modes.get(mode, mode) | (0 if partitioned_crud else 16) |
                                                    (modes.get(cut_pack, cut_pack) << 5) | (incs.get(inc, inc) << 7) |
-                                                   (modes.get(cut_apply, cut_apply) << 9) | (0 if overlap else 2048) |
-                                                   (0 if chain else 4096)))
+                                                   (modes.get(cut_apply, cut_apply) << 9) | (0 if chain else 4096)))
 
     def chained_scans(self):
-        """scans of quiet asynchronous ticks this handle has enqueued as links of a chain (two streams, workgroup-by-workgroup hand-over)"""
+        """scans of quiet asynchronous ticks this handle has enqueued as links of a chain (two streams, wave-range-by-wave-range hand-over)"""
         self._need_lab()
         return int(self._L.rio_gp_debug_chained_scans(self._h))
 

@@ -67,17 +67,14 @@ class Scenario:
             self.ref[rng.random(n) < (0.02 if start == 1 else 0.5)] = NONE
         self.lab = seed % 3 == 2
         # half of the lab scenarios: the quiet asynchronous ticks overlap / chain whatever the table's size (the product's rule
-        # needs 2^22 rows) — their scans alternate between two streams and hand the rows over workgroup by workgroup
+        # needs 2^22 rows) — their scans alternate between two streams and hand the rows over wave range by wave range
         self.chain_small = self.lab and (seed // 3) % 2 == 1
         if self.chain_small:
             os.environ["RIO_GP_OVERLAP_MIN_ROWS"] = "1"
-            if (seed // 6) % 2:   # ... in the form big tables use (k_resolve on the side stream behind the scan's stop event)
-                os.environ["RIO_GP_CHAIN_INLINE_BELOW"] = "0"
         try:
             g = self.g = gp.GpuPlacement(n, m, spill_rounds=self.rounds, flags=self.flags, lab=self.lab)
         finally:
             os.environ.pop("RIO_GP_OVERLAP_MIN_ROWS", None)
-            os.environ.pop("RIO_GP_CHAIN_INLINE_BELOW", None)
         g.set_nodes(self.cap, self.alive, m=m)
         g.set_objects(n, self.load, self.aff)
         g.set_assign(self.ref)
