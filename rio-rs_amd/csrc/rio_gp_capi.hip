@@ -124,6 +124,7 @@ struct rio_gp {
     u64 cap_obj = 0, cap_rows = 0;
     u32 cap_nodes = 0, rounds = 2;
     u64 n = 0;
+    u64 n_hi = 0;  // the largest n since creation: rows >= n_hi hold RIO_GP_NONE in both assignment columns (see commit_enqueue)
     u32 m = 0;
     // object table (HBM): two assignment columns (ping-pong), load, affinity, position scratch
     u32* assign[2] = {nullptr, nullptr};
@@ -673,7 +674,15 @@ void reset_inplace(rio_gp* h) { h->solve_inplace = false; h->inc_now = 0; }
 
 int commit_enqueue(rio_gp* h) {
     if (!h->have_solved) return fail(h, RIO_GP_EINVAL, "rio_gp_commit: no solve to commit");
-    if (!h->solve_inplace) h->cur ^= 1;  // (k_inc_scan and its fix-up wrote the committed column itself)
+    if (!h->solve_inplace) {  // (k_inc_scan and its fix-up wrote the committed column itself)
+        // rows >= n keep their contents (rio_gp_set_num_objects), and a solve writes rows < n of the other column only: the rows
+        // above n that were ever in use go over with the swap.  Nothing to copy while n is at its high-water mark (the string
+        // layer, every table that does not shrink).
+        if (h->n < h->n_hi)
+            HIPCHK(h, hipMemcpyAsync(h->assign[h->cur ^ 1] + h->n, h->assign[h->cur] + h->n, (size_t)(h->n_hi - h->n) * sizeof(u32),
+                                     hipMemcpyDeviceToDevice, h->stream));
+        h->cur ^= 1;
+    }
     h->solve_inplace = false;
     h->used_valid = true;
     if (h->solve_used) {  // a chained tick: its buffer of the ring becomes the committed vector, the last committed one the solve's scratch
@@ -1294,6 +1303,7 @@ static int set_objects_impl(rio_gp_t* h, uint64_t n, const uint32_t* load, const
     HIPCHK(h, hipMemsetAsync(h->used, 0, (size_t)h->cap_nodes * sizeof(u64), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->n = n;
+    h->n_hi = std::max<u64>(h->n_hi, n);
     h->used_valid = true;
     h->used_parts = false;
     h->have_solved = false; ++h->mut_epoch;
@@ -1784,6 +1794,7 @@ int rio_gp_set_num_objects(rio_gp_t* h, uint64_t n) {
     // placed row that drops out (or comes back) changes what `used` must count, so the vector is rebuilt before its next use
     if (n != h->n) h->used_valid = false;
     h->n = n;
+    h->n_hi = std::max<u64>(h->n_hi, n);
     h->have_solved = false; ++h->mut_epoch;
     h->last_pending_valid = false;
     return RIO_GP_OK;

@@ -1,0 +1,437 @@
+"""A CPU stand-in for the rio_gp binding, FOR TESTS ONLY: the surface tests/test_gpu_fuzz.py's scenarios use, implemented over
+the CPU oracle (oracle/pyoracle.py), tests/rebalance_ref.py and tests/spec_changes.py.  It lets the fuzz driver itself be tested
+without a GPU (tests/test_fuzz_driver.py): its bookkeeping (n, the feed's checkpoint, the mirror, the uncommitted solve) and its
+sensitivity — `fault=` makes exactly one behaviour of the handle wrong, and the scenarios must notice.
+
+It is not a CPU backend: nothing under rio-rs_amd/ imports it, and the product has no fallback.
+
+"Device" buffers are host arrays whose address stands for the device pointer, so pointer arithmetic on `.ptr` works as it does
+with tools/hipbuf.DevBuf.
+"""
+import ctypes as C
+import types
+
+import numpy as np
+
+import rebalance_ref
+import spec_changes
+
+NONE = 0xFFFFFFFF
+CAP_INF = 0xFFFFFFFFFFFFFFFF
+AFF_INACTIVE = 0xFFFFFFFE
+CFG_REF_SELF_ASSIGN = 2
+CHANGES_PEEK = 1
+OK, EINVAL, EUPSTREAM, ENODEV, ENOMEM, ERANGE, EAGAIN = range(7)
+
+FAULTS = (
+    "feed_keeps_last_row",         # a consuming listing does not advance the checkpoint for its last listed row
+    "feed_lists_hidden_rows",      # the feed lists rows >= n
+    "rebalance_stale_alive",       # the rebalance uses the liveness of before the last set_alive*
+    "rebalance_stale_used",        # the rebalance leaves `used` of the old column
+    "rebalance_keeps_solve",       # the rebalance keeps an uncommitted solve committable
+    "index_drops_last_row",        # the index drops the last row of a node's range
+    "index_reads_solved",          # the index reads the uncommitted column
+    "num_objects_stale_used",      # set_num_objects leaves `used` as it was
+)
+
+
+class ObjectPlacementError(Exception):
+    def __init__(self, kind, text, rc):
+        super().__init__("%s(%s)" % (kind, text))
+        self.kind, self.text, self.rc = kind, text, rc
+
+
+def _einval(text):
+    return ObjectPlacementError("Unknown", text, EINVAL)
+
+
+def _oracle():
+    import pyoracle
+    return pyoracle
+
+
+def build(*a, **k):
+    return None
+
+
+def balanced_targets(cap, used, alive, slack_permille=0):
+    """rio_gp.balanced_targets restated (integers throughout)."""
+    cap = np.asarray(cap, np.uint64)
+    used = np.asarray(used, np.uint64)
+    live = np.asarray(alive, np.uint8) != 0
+    t = np.full(len(cap), CAP_INF, np.uint64)
+    if not live.any():
+        return t
+    total = sum(int(u) for u in used[live])
+    caps = [int(c) for c in cap[live]]
+    scale = 1000 + int(slack_permille)
+    if any(c == CAP_INF for c in caps):
+        per = -(-total * scale // (1000 * len(caps)))
+        t[live] = np.uint64(min(per, CAP_INF))
+        return t
+    sc = sum(caps)
+    t[live] = np.array([min(-(-c * total * scale // (sc * 1000)) if sc else 0, c) for c in caps], np.uint64)
+    return t
+
+
+class DevBuf:
+    """tools/hipbuf.DevBuf over host memory."""
+
+    def __init__(self, arr=None, nbytes=None):
+        self.nbytes = int(arr.nbytes if arr is not None else nbytes)
+        self._mem = np.zeros(max(self.nbytes, 16), np.uint8)
+        if arr is not None:
+            self._mem[:self.nbytes] = np.ascontiguousarray(arr).view(np.uint8).ravel()
+
+    @property
+    def ptr(self):
+        return self._mem.ctypes.data
+
+    def to_host(self, dtype=np.uint32):
+        return self._mem[:self.nbytes - self.nbytes % np.dtype(dtype).itemsize].view(dtype).copy()
+
+    def free(self):
+        self._mem = None
+
+
+def _at(ptr, count, dtype=np.uint32):
+    """The `count` entries at "device" address ptr, as a writable array."""
+    if not count:
+        return np.zeros(0, dtype)
+    ct = {np.uint32: C.c_uint32, np.uint64: C.c_uint64}[dtype]
+    return np.ctypeslib.as_array((ct * int(count)).from_address(int(ptr)))
+
+
+class GpuPlacement:
+    def __init__(self, max_objects, max_nodes, device=0, spill_rounds=2, flags=0, lab=False, fault=None):
+        assert fault is None or fault in FAULTS, fault
+        self._fault = fault
+        self._lab = bool(lab)
+        self._cap_rows, self._cap_nodes = int(max_objects), int(max_nodes)
+        self._rounds = int(spill_rounds)
+        self._oflags = _oracle().REF_SELF_ASSIGN if flags & CFG_REF_SELF_ASSIGN else 0
+        self._n, self._m = 0, 0
+        self._col = np.full(self._cap_rows, NONE, np.uint32)
+        self._load = np.ones(self._cap_rows, np.uint32)
+        self._aff = np.full(self._cap_rows, NONE, np.uint32)
+        self._cap = np.zeros(0, np.uint64)
+        self._alive = np.zeros(0, np.uint8)
+        self._alive_seen = self._alive.copy()   # the liveness the "device" has consumed (a set_alive* only pushes)
+        self._B = np.full(self._cap_rows, NONE, np.uint32)
+        self._solved = None
+        self._stale_used = None
+        self._done = []
+
+    # ---- helpers
+    def _view(self):
+        n = self._n
+        return self._col[:n], self._load[:n], self._aff[:n]
+
+    def _changed(self):
+        """Every call that changes an input of the solve: the uncommitted solve is dropped."""
+        self._solved = None
+        self._stale_used = None
+
+    def _sync_alive(self):
+        self._alive_seen = self._alive.copy()
+
+    def close(self):
+        self._col = None
+
+    @property
+    def num_objects(self):
+        return self._n
+
+    @property
+    def num_nodes(self):
+        return self._m
+
+    # ---- tables
+    def set_nodes(self, cap=None, alive=None, m=None):
+        if m is None:
+            m = len(cap) if cap is not None else len(alive)
+        if m > self._cap_nodes:
+            raise _einval("m exceeds max_nodes")
+        self._cap = np.full(m, CAP_INF, np.uint64) if cap is None else np.array(cap, np.uint64)[:m].copy()
+        self._alive = np.ones(m, np.uint8) if alive is None else (np.asarray(alive)[:m] != 0).astype(np.uint8)
+        self._m = m
+        self._sync_alive()
+        self._changed()
+
+    def set_alive(self, node, alive):
+        if node >= self._m:
+            raise _einval("node out of range")
+        self._alive[node] = 1 if alive else 0
+        self._changed()
+
+    def set_alive_all(self, alive):
+        if len(alive) != self._m:
+            raise _einval("m differs")
+        self._alive = (np.asarray(alive) != 0).astype(np.uint8)
+        self._changed()
+
+    def get_nodes(self):
+        col, load, _ = self._view()
+        used = self._stale_used if self._stale_used is not None else _oracle().recompute_used(col, load, self._m)
+        return self._cap.copy(), self._alive.copy(), used.copy()
+
+    def set_objects(self, n, load=None, aff=None):
+        if n > self._cap_rows:
+            raise _einval("n exceeds max_objects")
+        self._load[:n] = 1 if load is None else np.asarray(load, np.uint32)[:n]
+        self._aff[:n] = NONE if aff is None else np.asarray(aff, np.uint32)[:n]
+        self._col[:] = NONE
+        self._n = int(n)
+        self._changed()
+
+    def set_object_attrs(self, idx, load=None, aff=None):
+        idx = np.asarray(idx, np.uint32)
+        if len(idx) and int(idx.max()) >= self._n:
+            raise _einval("object index out of range")
+        if load is not None:
+            self._load[idx] = np.asarray(load, np.uint32)
+        if aff is not None:
+            self._aff[idx] = np.asarray(aff, np.uint32)
+        self._changed()
+
+    def set_num_objects(self, n):
+        if n > self._cap_rows:
+            raise _einval("n exceeds max_objects")
+        before = self.get_nodes()[2]
+        self._n = int(n)
+        self._changed()
+        if self._fault == "num_objects_stale_used":
+            self._stale_used = before
+
+    def set_assign(self, assign):
+        assign = np.asarray(assign, np.uint32)
+        if len(assign) != self._n:
+            raise _einval("n differs from the object table")
+        self._col[:self._n] = assign
+        self._changed()
+
+    def get_assign(self):
+        return self._col[:self._n].copy()
+
+    def get_solved(self):
+        if self._solved is None or len(self._solved) != self._n:
+            raise _einval("no solve / size mismatch")
+        return self._solved.copy()
+
+    # ---- CRUD
+    def lookup_batch(self, idx):
+        return _oracle().lookup_batch(self._view()[0], idx)
+
+    def update_batch(self, idx, node):
+        if _oracle().update_batch(self._view()[0], self._m, idx, node):
+            raise _einval("update_batch")
+        self._changed()
+
+    def remove_batch(self, idx):
+        if _oracle().remove_batch(self._view()[0], idx):
+            raise _einval("remove_batch")
+        self._changed()
+
+    def clean_server(self, node):
+        col = self._view()[0]
+        hit = col == np.uint32(node)
+        col[hit] = NONE
+        self._changed()
+        return int(hit.sum())
+
+    def clean_servers(self, dead_nodes):
+        ev = _oracle().clean_servers(self._view()[0], self._m, [int(j) for j in dead_nodes])
+        self._changed()
+        return ev
+
+    # ---- policy
+    def place_pending(self, idx, requester):
+        col, load, _ = self._view()
+        used = _oracle().recompute_used(col, load, self._m)
+        out = _oracle().place_pending(col, load, self._cap, self._alive, used, idx, requester, self._rounds, self._oflags)
+        self._sync_alive()
+        self._changed()
+        return out
+
+    def place_pending_dev(self, n, d_idx, d_requester, d_out_node, d_out_flag=None):
+        node, flag = self.place_pending(_at(d_idx, n).copy(), _at(d_requester, n).copy())
+        _at(d_out_node, n)[:] = node
+        if d_out_flag:
+            _at(d_out_flag, n)[:] = flag
+        return None
+
+    def mixed_batch(self, update=None, remove=None, lookup=None, place=None):
+        e = np.empty(0, np.uint32)
+        lo, pn, pf = e, e, e
+        if update is not None:
+            self.update_batch(update[0], update[1])
+        if remove is not None:
+            self.remove_batch(remove)
+        if lookup is not None:
+            lo = self.lookup_batch(lookup)
+        if place is not None:
+            pn, pf = self.place_pending(place[0], place[1])
+        return [0, 0, 0, 0], lo, pn, pf
+
+    # ---- solves
+    def _tick(self):
+        col, load, aff = self._view()
+        self._sync_alive()
+        return _oracle().tick(col, load, aff, self._cap, self._alive, self._rounds, self._oflags)
+
+    def solve(self):
+        nxt, _, st = self._tick()
+        self._stale_used = None
+        self._solved = nxt
+        return st
+
+    def commit(self):
+        if self._solved is None or len(self._solved) != self._n:
+            raise _einval("rio_gp_commit: no solve to commit")
+        self._col[:self._n] = self._solved
+        self._solved = None
+        self._stale_used = None
+
+    def tick(self):
+        st = self.solve()
+        self.commit()
+        return st
+
+    def tick_async(self):
+        self._done.append(self.tick())
+
+    def tick_wait(self, cap=4096):
+        out, self._done = self._done[-cap:], []
+        return out
+
+    # ---- reverse index
+    def _index(self, nodes):
+        m = self._m
+        a = self._col[:self._n]
+        if self._fault == "index_reads_solved" and self._solved is not None and len(self._solved) == self._n:
+            a = self._solved
+        sel = np.ones(m, bool)
+        if nodes is not None:
+            sel[:] = False
+            ids = np.asarray(list(nodes), np.int64)
+            sel[ids[ids < m]] = True
+        parts, off = [], np.zeros(m + 1, np.uint64)
+        on = a < m
+        order = np.flatnonzero(on)
+        order = order[np.argsort(a[order], kind="stable")]
+        cnt = np.bincount(a[on], minlength=m) if m else np.zeros(0, np.int64)
+        start = np.concatenate([[0], np.cumsum(cnt)])
+        for j in np.flatnonzero(sel & (cnt > 0)) if m else []:
+            r = order[start[j]:start[j + 1]]
+            if self._fault == "index_drops_last_row":
+                r = r[:-1]
+            parts.append(r)
+            off[j + 1] = len(r)
+        off = np.cumsum(off).astype(np.uint64)
+        rows = np.concatenate(parts).astype(np.uint32) if parts else np.zeros(0, np.uint32)
+        return off, rows
+
+    def rows_on_nodes(self, nodes=None, _cap=None):
+        return self._index(nodes)
+
+    def rows_on_nodes_try(self, nodes, rows):
+        off, r = self._index(nodes)
+        if len(r) > len(rows):
+            return ERANGE, off, len(r)
+        rows[:len(r)] = r
+        return OK, off, len(r)
+
+    def count_on_nodes(self, nodes=None):
+        return self._index(nodes)[0]
+
+    def rows_on_nodes_dev(self, d_offsets, d_rows, rows_cap, nodes=None):
+        off, r = self._index(nodes)
+        _at(d_offsets, self._m + 1, np.uint64)[:] = off
+        if d_rows and len(r) > rows_cap:
+            return ERANGE, len(r)
+        if d_rows:
+            _at(d_rows, len(r))[:] = r
+        return OK, len(r)
+
+    # ---- bounded rebalance
+    def _rebalance(self, target, budget, rounds):
+        col, load, aff = self._view()
+        alive = self._alive_seen if self._fault == "rebalance_stale_alive" and len(self._alive_seen) == self._m else self._alive
+        before = self.get_nodes()[2]
+        solved = self._solved
+        nxt, used, st, rows, frm, to = rebalance_ref.rebalance(col, load, aff, self._cap, alive, target, budget, rounds or self._rounds)
+        col[:] = nxt
+        self._changed()
+        if self._fault == "rebalance_keeps_solve":
+            self._solved = solved
+        if self._fault == "rebalance_stale_used":
+            self._stale_used = before
+        return st, rows, frm, to
+
+    def rebalance(self, target=None, max_moves=None, rounds=0, list_moves=True, moves_cap=None):
+        if list_moves:
+            mm = CAP_INF if max_moves is None else int(max_moves)
+            cap = int(moves_cap if moves_cap is not None else min(mm, self._n))
+            return self._rebalance(target, min(mm, cap), rounds)
+        st, _, _, _ = self._rebalance(target, max_moves, rounds)
+        e = np.empty(0, np.uint32)
+        return st, e, e, e
+
+    def rebalance_dev(self, d_rows=None, d_from=None, d_to=None, moves_cap=0, target=None, max_moves=None, rounds=0):
+        if bool(d_rows) != bool(d_from) or bool(d_rows) != bool(d_to) or (not d_rows and moves_cap):
+            raise _einval("rio_gp_rebalance: the output rule")
+        mm = CAP_INF if max_moves is None else int(max_moves)
+        budget = min(mm, int(moves_cap)) if d_rows else (None if max_moves is None else mm)
+        st, rows, frm, to = self._rebalance(target, budget, rounds)
+        if d_rows:
+            _at(d_rows, len(rows))[:] = rows
+            _at(d_from, len(rows))[:] = frm
+            _at(d_to, len(rows))[:] = to
+        return st, len(rows)
+
+    # ---- change feed
+    def _changes(self, cap, peek):
+        n = self._cap_rows if self._fault == "feed_lists_hidden_rows" else self._n
+        rows, old, new, total, B = spec_changes.dense(self._B, self._col, n, cap, peek)
+        if self._fault == "feed_keeps_last_row" and not peek and len(rows):
+            B[rows[-1]] = self._B[rows[-1]]
+        self._B = B
+        return rows, old, new, total
+
+    def changes(self, cap=None, peek=False):
+        if cap is not None:
+            cap = min(int(cap), self._n)
+        return self._changes(cap, peek)
+
+    def changes_dev(self, d_rows=None, d_old=None, d_new=None, cap=0, peek=False):
+        if bool(d_rows) != bool(d_old) or bool(d_rows) != bool(d_new) or (not d_rows and cap):
+            raise _einval("rio_gp_changes: the output rule")
+        rows, old, new, total = self._changes(int(cap), peek)
+        if d_rows:
+            _at(d_rows, len(rows))[:] = rows
+            _at(d_old, len(rows))[:] = old
+            _at(d_new, len(rows))[:] = new
+        return total
+
+    def changes_reset(self):
+        self._B[:] = NONE
+
+    # ---- lab calls: no-ops
+    def set_compact(self, *a, **k):
+        return None
+
+    def set_speculate(self, *a, **k):
+        return None
+
+    def chained_scans(self):
+        return 0
+
+
+def module(fault=None):
+    """The surface of this module with every handle created under `fault` (one of FAULTS, or None)."""
+    def make(*a, **k):
+        k.setdefault("fault", fault)
+        return GpuPlacement(*a, **k)
+    return types.SimpleNamespace(GpuPlacement=make, CFG_REF_SELF_ASSIGN=CFG_REF_SELF_ASSIGN, balanced_targets=balanced_targets,
+                                 DevBuf=DevBuf, ObjectPlacementError=ObjectPlacementError, build=build, NONE=NONE,
+                                 CAP_INF=CAP_INF, OK=OK, EINVAL=EINVAL, ERANGE=ERANGE, fault=fault)

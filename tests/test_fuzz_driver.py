@@ -1,0 +1,103 @@
+"""The fuzz driver itself (tests/test_gpu_fuzz.py's Scenario), without a GPU: the scenarios run against a CPU stand-in for the
+handle (tests/fake_rio_gp.py).
+
+  - replay: the old family's seeds draw the tables and operations they drew before the extended op table existed
+    (tests/golden/fuzz_old_family_ops.json, recorded from the earlier Scenario against the same stand-in);
+  - the extended seeds run clean: the model's own bookkeeping (n, the feed's checkpoint, the mirror, the uncommitted solve) holds;
+  - the coverage floor: what the extended family exists for does happen in its default seeds;
+  - sensitivity: with exactly one behaviour of the stand-in made wrong, the default extended seeds fail, naming the operation.
+"""
+import json
+import os
+
+import pytest
+
+import fake_rio_gp
+import test_gpu_fuzz as fuzz
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fuzz_old_family_ops.json")
+
+FLOOR = (
+    "rebalance moved rows",
+    "rebalance selected rows that all stayed",
+    "rebalance with max_moves 0 and a surplus",
+    "rebalance with dead nodes right after a flip",
+    "rebalance under self-assign",
+    "rebalance while a solve is uncommitted",
+    "rebalance between tick_async and tick_wait",
+    "paged feed with a writer before the next page",
+    "feed with hidden rows that differ from the checkpoint",
+    "feed reset",
+    "index answered with ERANGE",
+    "index while a solve is uncommitted",
+)
+
+# fault of the stand-in -> the operation the failure must name
+FAULTS = {
+    "feed_keeps_last_row": "changes",
+    "feed_lists_hidden_rows": "changes",
+    "rebalance_stale_alive": "rebalance",
+    "rebalance_stale_used": "rebalance",
+    "rebalance_keeps_solve": "rebalance",
+    "index_drops_last_row": "index",
+    "index_reads_solved": "index",
+    "num_objects_stale_used": "num_objects",
+}
+
+
+def test_old_family_replays_its_recorded_operations(oracle):
+    want = json.load(open(GOLDEN))
+    assert sorted(int(k) for k in want) == list(range(36))
+    for seed in range(36):
+        sc = fuzz.Scenario(fake_rio_gp.module(), oracle, seed)
+        sc.run()
+        assert {"n": sc.n, "m": sc.m, "ops": sc.log} == want[str(seed)], seed
+
+
+def test_op_tables():
+    """The old table is what it was; the extended one is the old entries plus the new operations."""
+    assert fuzz.Scenario.OPS == (("tick", 5), ("solve", 2), ("async", 3), ("flip", 4), ("update", 2), ("remove", 2), ("lookup", 1),
+                                 ("clean", 2), ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
+    assert fuzz.Scenario.OPS_EXT[:len(fuzz.Scenario.OPS)] == fuzz.Scenario.OPS
+    assert [a for a, _ in fuzz.Scenario.OPS_EXT[len(fuzz.Scenario.OPS):]] == ["index", "rebalance", "changes", "changes_reset",
+                                                                            "num_objects"]
+
+
+@pytest.fixture(scope="module")
+def clean_run(oracle):
+    """The default extended seeds against the stand-in: (coverage counters, operation counts)."""
+    cov, count = {}, {}
+    for seed in range(fuzz.EXT_SEEDS):
+        sc = fuzz.Scenario(fake_rio_gp.module(), oracle, seed, ext=True)
+        sc.run()
+        for k, v in sc.cov.items():
+            cov[k] = cov.get(k, 0) + v
+        for k, v in sc.count.items():
+            count[k] = count.get(k, 0) + v
+    return cov, count
+
+
+def test_extended_seeds_run_clean_and_use_every_new_operation(clean_run):
+    cov, count = clean_run
+    for op in ("index", "rebalance", "changes", "changes_reset", "num_objects", "in flight: index", "in flight: changes",
+               "in flight: rebalance"):
+        assert count.get(op, 0) > 0, (op, count)
+
+
+def test_coverage_floor(clean_run):
+    cov, count = clean_run
+    missing = [k for k in FLOOR if cov.get(k, 0) < 1]
+    assert not missing, (missing, cov, count)
+
+
+@pytest.mark.parametrize("fault", sorted(FAULTS))
+def test_a_wrong_handle_is_noticed(oracle, fault):
+    assert set(FAULTS) == set(fake_rio_gp.FAULTS)
+    for seed in range(fuzz.EXT_SEEDS):
+        sc = fuzz.Scenario(fake_rio_gp.module(fault), oracle, seed, ext=True)
+        try:
+            sc.run()
+        except AssertionError as e:
+            assert FAULTS[fault] in repr(e.args), (fault, seed, e.args)
+            return
+    pytest.fail("no default extended seed noticed the fault %r" % fault)

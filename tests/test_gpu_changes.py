@@ -103,6 +103,31 @@ def test_dense_feed_matches_the_spec(gp, n):
         g.close()
 
 
+@pytest.mark.gpu
+def test_rows_hidden_by_a_smaller_n_survive_the_ticks_in_between(gp):
+    """rio_gp_set_num_objects keeps the contents of rows >= n, and the feed compares them as usual once n grows again.  A tick
+    while they are hidden publishes the other assignment column: the hidden rows have to be in it.  (They were not: the
+    operation-sequence fuzz, extended seed 41, read rows of an older column after n grew back.)"""
+    n, m = 6000, 8
+    g = gp.GpuPlacement(n, m)
+    try:
+        g.set_nodes(None, np.ones(m, np.uint8), m=m)
+        g.set_objects(n)
+        a = (np.arange(n) % m).astype(np.uint32)
+        g.set_assign(a)
+        f = Fed(g, n)
+        assert f.check() == n                    # the consumer knows every row
+        for k in (n // 2, 1, 0, n - 1):          # one column swap, then more of them at other sizes
+            g.set_num_objects(k)
+            g.tick()                             # every node alive, every row placed: the tick keeps rows < k where they are
+            assert f.check() == 0
+            g.set_num_objects(n)
+            assert np.array_equal(g.get_assign(), a), k
+            assert f.check() == 0, k             # nothing changed for the consumer either
+    finally:
+        g.close()
+
+
 def _churned(gp, n=200_000, m=64, seed=5):
     rng, load, aff, cap = _table(gp, n, m, seed)
     g = gp.GpuPlacement(n, m)

@@ -9,7 +9,16 @@ affinities / capacities.  A second kind of scenario drives the ROW-SHARDED solve
 boundaries with empty shards, streams of committed ticks with liveness changes) against the whole-table oracle.  The fix-up policies the product picks adaptively are also forced through the lab build's knobs, by
 seed.  The seeds are fixed: a failure names the seed and the operation.
 
-    python tests/test_gpu_fuzz.py <seconds> [first_seed]     # a longer campaign (tools/round5_pass.sh runs one)
+A second family of scenarios ("extended": Scenario(..., ext=True), seeds and generator of its own) draws from OPS_EXT: the old
+operations plus the reverse index (rio_gp_rows_on_nodes[_dev], every call form), the bounded rebalance (rio_gp_rebalance[_dev],
+against tests/rebalance_ref.py and, up to 4 096 rows, tests/spec_rebalance.py), the change feed (rio_gp_changes[_dev] / _reset
+against tests/spec_changes.py, plus a mirror fed by the consuming listings that must equal the column at the end) and
+rio_gp_set_num_objects.  It also checks that calls which promise to change nothing leave an uncommitted solve as it was (and
+committable), that every other call drops it, that the index and the feed leave quiet ticks chained while a rebalance ends the
+chain, and calls all three between rio_gp_tick_async and rio_gp_tick_wait.  The old family's tables, operations and draws are
+untouched (tests/test_fuzz_driver.py replays them against a CPU stand-in and a recorded log).
+
+    python tests/test_gpu_fuzz.py <seconds> [first_seed]     # a longer campaign: old and extended scenarios alternate
 """
 import os
 import sys
@@ -37,9 +46,11 @@ def _pick(rng, table, hi):
 
 
 class Scenario:
-    def __init__(self, gp, oracle, seed, big=False):
-        self.gp, self.oracle, self.seed = gp, oracle, seed
-        rng = self.rng = np.random.default_rng(0x5EED0000 + seed)
+    def __init__(self, gp, oracle, seed, big=False, ext=False):
+        """ext: the operations are drawn from OPS_EXT (the reverse index, the rebalance, the change feed and set_num_objects beside
+        the old ones), from a generator of its own, and the scenario keeps what their checks need (see "extended scenarios")."""
+        self.gp, self.oracle, self.seed, self.ext = gp, oracle, seed, bool(ext)
+        rng = self.rng = np.random.default_rng((0xE87E0000 if ext else 0x5EED0000) + seed)
         self.n = n = _pick(rng, _SIZES + (524288, 1_000_000), 2_000_000 if big else 300_000)
         if big and rng.random() < 0.3:   # a campaign spends a third of its scenarios on tables of 10^5 .. 2 x 10^6 rows
             self.n = n = int(np.exp(rng.uniform(np.log(100_000), np.log(2_000_000))))
@@ -86,10 +97,22 @@ class Scenario:
             g.set_speculate(("never", "always", "auto")[(seed // 18) % 3])
         self.log = []
         self.count = {}
+        # extended scenarios: the handle's max_objects (n shrinks and grows below it: the arrays keep their full length, every
+        # operation works on [:n]); the feed's checkpoint column and a mirror fed by consuming listings only; the expected column
+        # of an uncommitted solve (None: there is none); whether liveness changed with no tick since; the coverage-floor counters
+        self.nmax = n
+        self.B = np.full(n, NONE, np.uint32)
+        self.mirror = np.full(n, NONE, np.uint32)
+        self.pending = None
+        self.fresh_flip = False
+        self.in_flight = False
+        self.page_open = self.page_writer = False
+        self.paging_out = self.mixed_wrote = False
+        self.cov = {}
 
     def _caps(self):
         rng, m = self.rng, self.m
-        total = int(self.load.sum())
+        total = int(self.load[:self.n].sum())
         k = rng.integers(4)
         if k == 0:
             return np.full(m, INF, np.uint64)
@@ -104,20 +127,29 @@ class Scenario:
 
     # ---- checks -------------------------------------------------------------------------------------------------------
     def check_table(self, what):
-        got = self.g.get_assign()
-        assert np.array_equal(got, self.ref), (self.seed, what, self.log[-6:], np.flatnonzero(got != self.ref)[:8])
-        used = self.oracle.recompute_used(self.ref, self.load, self.m)
+        got, ref = self.g.get_assign(), self.ref[:self.n]
+        assert np.array_equal(got, ref), (self.seed, what, self.log[-6:], np.flatnonzero(got != ref)[:8])
+        used = self.oracle.recompute_used(ref, self.load[:self.n], self.m)
         gu = self.g.get_nodes()[2]
         assert np.array_equal(gu, used), (self.seed, what, self.log[-6:], np.flatnonzero(gu != used)[:8])
 
     def otick(self):
-        return self.oracle.tick(self.ref, self.load, self.aff, self.cap, self.alive, self.rounds, self.oflags)
+        n = self.n
+        return self.oracle.tick(self.ref[:n], self.load[:n], self.aff[:n], self.cap, self.alive, self.rounds, self.oflags)
+
+    def _set_col(self, want):
+        """The model's column after a commit: rows >= n keep what they hold."""
+        if len(want) == len(self.ref):
+            self.ref = want
+        else:
+            self.ref[:self.n] = want
 
     # ---- operations ---------------------------------------------------------------------------------------------------
     def op_tick(self):
         st = self.g.tick()
         want, used, ost = self.otick()
-        self.ref = want
+        self._set_col(want)
+        self.pending, self.fresh_flip = None, False
         assert st == ost, (self.seed, "tick", self.log[-6:], st, ost)
 
     def op_solve(self):
@@ -126,29 +158,78 @@ class Scenario:
         got = self.g.get_solved()
         assert st == ost, (self.seed, "solve", self.log[-6:], st, ost)
         assert np.array_equal(got, want), (self.seed, "solve", self.log[-6:], np.flatnonzero(got != want)[:8])
+        self.fresh_flip = False
         if self.rng.random() < 0.5:
             self.g.commit()
-            self.ref = want
+            self._set_col(want)
+            self.pending = None
+        else:
+            self.pending = want
 
     def op_async(self):
         k = int(self.rng.integers(1, 5))
         quiet_run = self.chain_small and self.rng.random() < 0.5   # a longer stream without changes: verdicts land, the ticks chain
         if quiet_run:
             k += 6
+        last_chained = False
         want_st = []
+        # extended scenarios, a quiet run: a call in the middle of it (see _mid_call); any run: a call between the last tick_async
+        # and tick_wait, whose answer reflects every enqueued tick
+        mid = ("none", "index", "changes", "rebalance")[int(self.rng.integers(4))] if self.ext and quiet_run else "none"
+        watch = None
         for i in range(k):
             if i and not quiet_run and self.rng.random() < 0.5:
                 self.op_flip()
+            if mid != "none" and i == k - 4:
+                watch = self._mid_call(mid, last_chained)
+            c0 = self.g.chained_scans() if self.lab and mid != "none" else 0
             self.g.tick_async()
-            self.ref, used, ost = self.otick()
+            want, used, ost = self.otick()
+            self._set_col(want)
+            self.pending, self.fresh_flip = None, False
             want_st.append(ost)
+            if self.lab and mid != "none":
+                last_chained = self.g.chained_scans() - c0 == 1
+                if watch is not None and watch[0] == "rebalance" and i == k - 4:
+                    # a rebalance is a change of the inputs: the tick after it does not chain
+                    assert not last_chained, (self.seed, "rebalance", "the tick after a rebalance chained", self.log[-6:])
             if self.rng.random() < 0.3 or (quiet_run and i < 3):
                 time.sleep(0.002)
+        if watch is not None and watch[0] != "rebalance" and watch[1]:
+            # the tick before the call was a link of a chain and nothing has changed since: the 4 ticks after it are links too,
+            # as they are in the same run without the call
+            c = self.g.chained_scans() - watch[2]
+            assert c == 4, (self.seed, watch[0], "quiet ticks after the call did not stay chained", c, self.log[-6:])
+            self.cov["chained across a call"] = self.cov.get("chained across a call", 0) + 1
+        if self.ext and self.rng.random() < 0.5:
+            self.in_flight = True
+            try:
+                what = ("index", "changes", "rebalance")[int(self.rng.integers(3))]
+                self.log.append("in flight: " + what)
+                self.count["in flight: " + what] = self.count.get("in flight: " + what, 0) + 1
+                getattr(self, "op_" + what)()
+            finally:
+                self.in_flight = False
         got = self.g.tick_wait()
         assert got == want_st, (self.seed, "tick_async", self.log[-6:], got, want_st)
 
+    def _mid_call(self, what, last_chained):
+        """A call between the quiet asynchronous ticks of a run (lab build, every tick may chain).  The index and a consuming feed
+        call change nothing a tick reads: if the tick before was a link of a chain, the ticks after are.  A rebalance ends the
+        chain.  -> (what, the tick before chained, chained_scans() after the call)"""
+        self.log.append("mid run: " + what)
+        self.count["mid run: " + what] = self.count.get("mid run: " + what, 0) + 1
+        if what == "index":
+            self.op_index()
+        elif what == "changes":
+            self._feed(None if self.rng.random() < 0.5 else int(self.rng.integers(1, 50)), False, False)
+        else:
+            self.op_rebalance()
+        return what, last_chained, self.g.chained_scans() if self.lab else 0
+
     def op_flip(self):
         rng, m = self.rng, self.m
+        self.pending, self.fresh_flip = None, True   # (a liveness push is a change of the inputs: an uncommitted solve is dropped)
         k = rng.integers(3)
         if k == 0:
             j = int(rng.integers(m))
@@ -181,29 +262,30 @@ class Scenario:
         node = self.rng.integers(0, self.m, idx.size).astype(np.uint32)
         node[self.rng.random(idx.size) < 0.05] = NONE      # Option::None deletes (local.rs:36-37)
         self.g.update_batch(idx, node)
-        self.oracle.update_batch(self.ref, self.m, idx, node)
+        self.oracle.update_batch(self.ref[:self.n], self.m, idx, node)
 
     def op_remove(self):
         idx = self._idx()
         self.g.remove_batch(idx)
-        self.oracle.remove_batch(self.ref, idx)
+        self.oracle.remove_batch(self.ref[:self.n], idx)
 
     def op_lookup(self):
         idx = self._idx()
         got = self.g.lookup_batch(idx)
-        assert np.array_equal(got, self.oracle.lookup_batch(self.ref, idx)), (self.seed, "lookup", self.log[-6:])
+        assert np.array_equal(got, self.oracle.lookup_batch(self.ref[:self.n], idx)), (self.seed, "lookup", self.log[-6:])
 
     def op_clean(self):
         rng, m = self.rng, self.m
         if rng.random() < 0.5:
             j = int(rng.integers(m))
             ev = self.g.clean_server(j)
-            want = int((self.ref == j).sum())
-            self.ref[self.ref == j] = NONE
+            a = self.ref[:self.n]
+            want = int((a == j).sum())
+            a[a == j] = NONE
         else:
             dead = sorted(set(int(x) for x in rng.integers(0, m, int(rng.integers(1, 8)))))
             ev = self.g.clean_servers(dead)
-            want = self.oracle.clean_servers(self.ref, m, dead)
+            want = self.oracle.clean_servers(self.ref[:self.n], m, dead)
         assert ev == want, (self.seed, "clean", self.log[-6:], ev, want)
 
     def op_place(self):
@@ -211,10 +293,10 @@ class Scenario:
         req = self.rng.integers(0, self.m, idx.size).astype(np.uint32)
         if self.rng.random() < 0.3:
             req[:] = int(self.rng.integers(self.m))
-        used = self.oracle.recompute_used(self.ref, self.load, self.m)
+        n = self.n
+        used = self.oracle.recompute_used(self.ref[:n], self.load[:n], self.m)
         if self.rng.random() < 0.3:   # the same call over device-resident arrays (validated on the device; sometimes not 16-byte aligned)
-            sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-            from hipbuf import DevBuf
+            DevBuf = self._devbuf()
             off = int(self.rng.integers(0, 2)) * int(self.rng.integers(1, 4))
             pad = np.zeros(off, np.uint32)
             d_idx, d_req = DevBuf(np.concatenate([pad, idx])), DevBuf(np.concatenate([pad, req]))
@@ -226,7 +308,8 @@ class Scenario:
             self.count["place_dev"] = self.count.get("place_dev", 0) + 1
         else:
             node, flag = self.g.place_pending(idx, req)
-        wnode, wflag = self.oracle.place_pending(self.ref, self.load, self.cap, self.alive, used, idx, req, self.rounds, self.oflags)
+        wnode, wflag = self.oracle.place_pending(self.ref[:n], self.load[:n], self.cap, self.alive, used, idx, req, self.rounds, self.oflags)
+        self.fresh_flip = False   # (a request batch delivers a pushed liveness bitmap to the device)
         bad = np.flatnonzero((node != wnode) | (flag != wflag))
         assert bad.size == 0, (self.seed, "place_pending", self.log[-6:], idx.size, bad[:8], node[bad[:8]], wnode[bad[:8]], flag[bad[:8]], wflag[bad[:8]])
 
@@ -245,15 +328,18 @@ class Scenario:
         rc, lo, pn, pf = self.g.mixed_batch(update=None if ui is None else (ui, un), remove=ri, lookup=li,
                                             place=None if pi is None else (pi, pr))
         assert rc == [0, 0, 0, 0], (self.seed, "mixed rc", rc)
+        self.mixed_wrote = ui is not None or ri is not None or pi is not None   # (lookups alone are a lookup: nothing changes)
         if ui is not None:
-            self.oracle.update_batch(self.ref, self.m, ui, un)
+            self.oracle.update_batch(self.ref[:self.n], self.m, ui, un)
         if ri is not None:
-            self.oracle.remove_batch(self.ref, ri)
+            self.oracle.remove_batch(self.ref[:self.n], ri)
         if li is not None:
-            assert np.array_equal(lo, self.oracle.lookup_batch(self.ref, li)), (self.seed, "mixed lookup", self.log[-6:])
+            assert np.array_equal(lo, self.oracle.lookup_batch(self.ref[:self.n], li)), (self.seed, "mixed lookup", self.log[-6:])
         if pi is not None:
-            used = self.oracle.recompute_used(self.ref, self.load, self.m)
-            wnode, wflag = self.oracle.place_pending(self.ref, self.load, self.cap, self.alive, used, pi, pr, self.rounds, self.oflags)
+            n = self.n
+            used = self.oracle.recompute_used(self.ref[:n], self.load[:n], self.m)
+            wnode, wflag = self.oracle.place_pending(self.ref[:n], self.load[:n], self.cap, self.alive, used, pi, pr, self.rounds, self.oflags)
+            self.fresh_flip = False
             bad = np.flatnonzero((pn != wnode) | (pf != wflag))
             assert bad.size == 0, (self.seed, "mixed place_pending", self.log[-6:], pi.size, bad[:8], pn[bad[:8]], wnode[bad[:8]])
 
@@ -269,20 +355,294 @@ class Scenario:
     def op_caps(self):
         self.cap = self._caps()
         self.g.set_nodes(self.cap, self.alive, m=self.m)
+        self.fresh_flip = False   # (the node table is uploaded whole, liveness included)
+
+
+    # ---- extended scenarios: the reverse index, the bounded rebalance, the change feed, set_num_objects ---------------------
+    def _devbuf(self):
+        """The device-buffer class of the binding module the scenario was given (a stand-in brings its own), else tools/hipbuf's."""
+        DevBuf = getattr(self.gp, "DevBuf", None)
+        if DevBuf is None:
+            sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+            from hipbuf import DevBuf
+        return DevBuf
+
+    def _hit(self, key, on=True):
+        self.cov[key] = self.cov.get(key, 0) + int(bool(on))
+
+    def _read_only(self, what):
+        """After a call that promises to change nothing: an uncommitted solve is still there, byte for byte, and can still be
+        committed (sometimes it is, and the model follows)."""
+        if self.pending is None:
+            return
+        got = self.g.get_solved()
+        assert np.array_equal(got, self.pending), (self.seed, what, "the uncommitted solve changed", self.log[-6:],
+                                                   np.flatnonzero(got != self.pending)[:8])
+        if not self.paging_out and self.rng.random() < 0.3:
+            self.g.commit()
+            self._set_col(self.pending)
+            self.pending = None
+            self.check_table(what + " + commit")
+
+    def _dropped(self, what):
+        """After a call that changes an input of the solve: the solve that was uncommitted is gone, commit() has nothing to publish."""
+        try:
+            self.g.commit()
+        except self.gp.ObjectPlacementError:
+            return
+        raise AssertionError((self.seed, what, "an uncommitted solve was still committable after the call", self.log[-6:]))
+
+    def _want_index(self, nodes):
+        a, m = self.ref[:self.n], self.m
+        sel = np.ones(m, bool)
+        if nodes is not None:
+            ids = np.asarray(list(nodes), np.int64)
+            sel[:] = False
+            sel[ids[ids < m]] = True
+        if nodes is not None and len(nodes) <= 8:   # the definition, node by node
+            parts = [np.flatnonzero(a == j) if sel[j] else np.zeros(0, np.int64) for j in range(m)] if m <= 64 else None
+            if parts is not None:
+                off = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.uint64)
+                return off, np.concatenate(parts).astype(np.uint32)
+        keep = np.flatnonzero((a < m) & sel[np.minimum(a, m - 1)])
+        rows = keep[np.argsort(a[keep], kind="stable")].astype(np.uint32)
+        off = np.zeros(m + 1, np.uint64)
+        off[1:] = np.cumsum(np.bincount(a[keep], minlength=m))
+        return off, rows
+
+    def op_index(self):
+        rng, m, g = self.rng, self.m, self.g
+        k = int(rng.integers(5))
+        if k == 0:
+            nodes = None
+        elif k == 1:
+            nodes = [int(rng.integers(m))]
+        elif k == 2:
+            nodes = sorted(set(int(x) for x in rng.integers(0, m, int(rng.integers(2, 9)))))
+        elif k == 3:
+            nodes = list(range(m))
+        else:      # ids >= m among them: ignored
+            nodes = sorted(set(int(x) for x in rng.integers(0, m + 70, int(rng.integers(1, 9))))) + [m, m + 64 + int(rng.integers(100))]
+        woff, wrows = self._want_index(nodes)
+        total = len(wrows)
+        form = ("host", "count", "try", "dev")[int(rng.integers(4))]
+        tag = (self.seed, "index", form, nodes if nodes is None or len(nodes) < 12 else len(nodes), self.log[-6:])
+        self._hit("index while a solve is uncommitted", self.pending is not None)
+        if form == "host":
+            off, rows = g.rows_on_nodes(nodes)
+            assert np.array_equal(off, woff) and np.array_equal(rows, wrows), tag
+        elif form == "count":
+            assert np.array_equal(g.count_on_nodes(nodes), woff), tag
+        elif form == "try":
+            short = total > 0           # one entry too small: ERANGE, the buffer untouched, the offsets right
+            buf = np.full(total - 1 if short else total, 0xDEADBEEF, np.uint32)
+            rc, off, nr = g.rows_on_nodes_try(nodes, buf)
+            assert nr == total and np.array_equal(off, woff), tag
+            if short:
+                assert rc == self.gp.ERANGE and (buf == 0xDEADBEEF).all(), tag + (rc,)
+                self._hit("index answered with ERANGE")
+            else:
+                assert rc == self.gp.OK, tag + (rc,)
+        else:
+            DevBuf = self._devbuf()
+            pad = int(rng.integers(0, 4))
+            d_off = DevBuf(np.full(m + 1, 0xDEADBEEFDEADBEEF, np.uint64))
+            d_rows = DevBuf(np.full(total + pad + 1, 0xDEADBEEF, np.uint32))
+            rc, nr = g.rows_on_nodes_dev(d_off.ptr, d_rows.ptr, total + pad, nodes)
+            off, rows = d_off.to_host(np.uint64), d_rows.to_host()
+            d_off.free()
+            d_rows.free()
+            assert rc == self.gp.OK and nr == total and np.array_equal(off, woff), tag + (rc, nr, total)
+            assert np.array_equal(rows[:total], wrows) and (rows[total:] == 0xDEADBEEF).all(), tag
+        self._read_only("index")
+
+    def _targets(self):
+        rng, m, n = self.rng, self.m, self.n
+        kind = ("capacities", "balanced", "tight", "zero", "inf")[int(rng.integers(5))]
+        if kind == "capacities":
+            return kind, None
+        if kind == "balanced":
+            used = self.oracle.recompute_used(self.ref[:n], self.load[:n], m)
+            return kind, self.gp.balanced_targets(self.cap, used, self.alive, int(rng.integers(0, 300)))
+        if kind == "tight":    # around the mean load, some nodes unbounded (as tests/rebalance_ref.random_table draws them)
+            per = int(self.load[:n].sum()) // max(m, 1)
+            T = rng.integers(max(per // 2, 0), per + per // 4 + 2, m).astype(np.uint64)
+            T[rng.random(m) < 0.05] = np.uint64(INF)
+            return kind, T
+        return kind, (np.zeros(m, np.uint64) if kind == "zero" else np.full(m, INF, np.uint64))
+
+    def op_rebalance(self):
+        import rebalance_ref
+        rng, m, n, g = self.rng, self.m, self.n, self.g
+        kind, T = self._targets()
+        max_moves = (None, 0, 1, max(1, n * int(rng.integers(1, 6)) // 100))[int(rng.integers(4))]
+        rounds = int(rng.integers(0, 4))
+        form = ("host", "dev", "count", "dev count")[int(rng.integers(4))]
+        listing = form in ("host", "dev")
+        moves_cap = None
+        if listing and rng.random() < 0.3:      # a listing smaller than max_moves: B = min(max_moves, moves_cap)
+            moves_cap = int(rng.integers(0, 1 + (max_moves if max_moves is not None else max(n // 50, 1))))
+        budget = max_moves
+        if listing:
+            cap = moves_cap if moves_cap is not None else min(INF if max_moves is None else max_moves, n)
+            budget = cap if max_moves is None else min(max_moves, cap)
+        had_solve, dead_unticked = self.pending is not None, self.fresh_flip and not self.alive.all()
+        cur, load, aff = self.ref[:n], self.load[:n], self.aff[:n]
+        nxt, used, wst, wrows, wfrom, wto = rebalance_ref.rebalance(cur, load, aff, self.cap, self.alive, T, budget, rounds or self.rounds)
+        tag = (self.seed, "rebalance", kind, form, max_moves, moves_cap, rounds, self.log[-6:])
+        if n <= 4096:    # the row-by-row restatement as well
+            import spec_rebalance
+            s_nxt, s_used, s_st, s_moves = spec_rebalance.rebalance([int(x) for x in cur], [int(x) for x in load], [int(x) for x in aff],
+                                                                    [int(x) for x in self.cap], [int(x) for x in self.alive],
+                                                                    None if T is None else [int(x) for x in T], budget, rounds or self.rounds)
+            assert s_st == wst and [int(x) for x in nxt] == s_nxt and [int(x) for x in used] == s_used, tag + ("the two references differ",)
+            assert s_moves == [(int(r), int(f), int(t)) for r, f, t in zip(wrows, wfrom, wto)], tag + ("the two references differ",)
+        if form == "host":
+            st, rows, frm, to = g.rebalance(T, max_moves, rounds, moves_cap=moves_cap)
+        elif form == "count":
+            st, rows, frm, to = g.rebalance(T, max_moves, rounds, list_moves=False)
+        elif form == "dev count":
+            st, nm = g.rebalance_dev(target=T, max_moves=max_moves, rounds=rounds)
+            assert nm == len(wrows), tag + (nm, len(wrows))
+        else:
+            DevBuf = self._devbuf()
+            cap = int(cap)
+            d = [DevBuf(np.full(cap + 2, 0xDEADBEEF, np.uint32)) for _ in range(3)]
+            st, nm = g.rebalance_dev(d[0].ptr, d[1].ptr, d[2].ptr, cap, target=T, max_moves=max_moves, rounds=rounds)
+            rows, frm, to = (x.to_host() for x in d)
+            for x in d:
+                x.free()
+            assert nm == len(wrows), tag + (nm, len(wrows))
+            assert all((x[nm:] == 0xDEADBEEF).all() for x in (rows, frm, to)), tag + ("written past the moves",)
+            rows, frm, to = rows[:nm], frm[:nm], to[:nm]
+        assert st == wst, tag + (st, wst)
+        if listing:
+            assert np.array_equal(rows, wrows) and np.array_equal(frm, wfrom) and np.array_equal(to, wto), tag + (rows[:8], wrows[:8])
+        self.ref[:n] = nxt
+        self.pending = None
+        if had_solve:
+            self._dropped("rebalance")
+        self._hit("rebalance moved rows", wst["moved_rows"] > 0)
+        self._hit("rebalance selected rows that all stayed", wst["selected_rows"] > 0 and wst["moved_rows"] == 0)
+        self._hit("rebalance with max_moves 0 and a surplus", budget == 0 and wst["surplus_rows"] > 0)
+        self._hit("rebalance with dead nodes right after a flip", dead_unticked)
+        self._hit("rebalance under self-assign", self.sa)
+        self._hit("rebalance while a solve is uncommitted", had_solve)
+        self._hit("rebalance between tick_async and tick_wait", self.in_flight)
+
+    def _feed(self, cap, peek, dev):
+        import spec_changes
+        g, n = self.g, self.n
+        self._hit("paged feed with a writer before the next page", self.page_open and self.page_writer)
+        self._hit("feed with hidden rows that differ from the checkpoint", n < self.nmax and (self.ref[n:] != self.B[n:]).any())
+        wr, wo, wn, wt, wB = spec_changes.dense(self.B, self.ref, n, cap, peek)
+        tag = (self.seed, "changes", cap, peek, dev, n, self.log[-6:])
+        if dev:
+            DevBuf = self._devbuf()
+            c = n + 5 if cap is None else int(cap)
+            if c == 0:
+                total = g.changes_dev(cap=0, peek=peek)
+                rows = old = new = np.zeros(0, np.uint32)
+            else:
+                size = min(c, n) + 2     # (a listing never holds more than n rows)
+                d = [DevBuf(np.full(size, 0xDEADBEEF, np.uint32)) for _ in range(3)]
+                total = g.changes_dev(d[0].ptr, d[1].ptr, d[2].ptr, cap=min(c, size - 1), peek=peek)
+                rows, old, new = (x.to_host() for x in d)
+                for x in d:
+                    x.free()
+                k = min(total, c)
+                assert all((x[k:] == 0xDEADBEEF).all() for x in (rows, old, new)), tag + ("written past the listing",)
+                rows, old, new = rows[:k], old[:k], new[:k]
+        else:
+            rows, old, new, total = g.changes(cap=cap, peek=peek)
+        assert total == wt, tag + (total, wt)
+        assert np.array_equal(rows, wr) and np.array_equal(old, wo) and np.array_equal(new, wn), tag + (rows[:8], wr[:8])
+        self.B = wB
+        consuming = not peek and cap != 0
+        if consuming:
+            assert np.array_equal(self.mirror[rows], old), tag + ("the listing's old nodes are not what the mirror holds",)
+            self.mirror[rows] = new
+            self.page_open, self.page_writer = len(rows) < total, False
+        self._read_only("changes")    # (consuming or not: the feed's checkpoint is no input of a solve)
+        return total
+
+    def op_changes(self):
+        rng, n = self.rng, self.n
+        cap = (None, 0, 1, int(rng.integers(2, 60)), n + 1 + int(rng.integers(1000)))[int(rng.integers(5))]
+        peek = bool(rng.random() < 0.3)
+        self._feed(cap, peek, bool(rng.random() < 0.3))
+
+    def op_changes_reset(self):
+        self.g.changes_reset()
+        self.B[:] = NONE
+        self.mirror[:] = NONE
+        self.page_open = False
+        self._hit("feed reset")
+
+    def op_num_objects(self):
+        rng = self.rng
+        k = rng.random()
+        if k < 0.1:
+            n = 0
+        elif k < 0.45:
+            n = self.nmax
+        elif k < 0.7:
+            n = _pick(rng, _SIZES, self.nmax)
+        else:
+            n = int(rng.integers(0, self.nmax + 1))
+        self.g.set_num_objects(n)
+        self.n = n
+
+    def finish_feed(self):
+        """The end of an extended scenario: the rest of the feed is paged out — three small pages, then pages of a third of what
+        is left, so that a table of 10^5 changed rows does not take 10^4 calls — and the mirror equals the column on rows < n."""
+        pages = 0
+        self.paging_out = True     # (no commit from here on: the column the mirror is compared with stays)
+        while True:
+            left = self._feed(0, True, False)
+            if left == 0:
+                break
+            self._feed(37 if pages < 3 else max(37, -(-left // 3)), False, False)
+            pages += 1
+        got = self.g.get_assign()
+        assert np.array_equal(self.mirror[:self.n], got), (self.seed, "changes", "the mirror differs from the column at the end",
+                                                           self.log[-6:], np.flatnonzero(self.mirror[:self.n] != got)[:8])
+
+    NEED_ROWS = ("update", "remove", "lookup", "place", "mixed", "attrs")                       # skipped while n == 0
+    WRITERS = ("tick", "solve", "async", "update", "remove", "clean", "place", "mixed", "rebalance", "num_objects")
+    DROPS_SOLVE = ("tick", "rebalance", "update", "remove", "clean", "place", "mixed", "attrs", "caps", "num_objects")
 
     OPS = (("tick", 5), ("solve", 2), ("async", 3), ("flip", 4), ("update", 2), ("remove", 2), ("lookup", 1), ("clean", 2),
            ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
 
+    OPS_EXT = OPS + (("index", 3), ("rebalance", 6), ("changes", 5), ("changes_reset", 1), ("num_objects", 2))
+
     def run(self):
-        names = [a for a, w in self.OPS for _ in range(w)]
+        names = [a for a, w in (self.OPS_EXT if self.ext else self.OPS) for _ in range(w)]
         k = int(self.rng.integers(12, 31))
         try:
             for _ in range(k):
                 op = names[int(self.rng.integers(len(names)))]
+                if self.ext and self.n == 0 and op in self.NEED_ROWS:
+                    self.log.append("skipped: " + op)
+                    continue
                 self.log.append(op)
                 self.count[op] = self.count.get(op, 0) + 1
+                had_solve = self.pending is not None
                 getattr(self, "op_" + op)()
+                if self.ext:
+                    if op in self.WRITERS:
+                        self.page_writer = True
+                    if op in self.DROPS_SOLVE and (op != "mixed" or self.mixed_wrote):
+                        self.pending = None
+                        if had_solve and op != "rebalance":    # (op_rebalance has asked already)
+                            self._dropped(op)
+                    elif op in ("mixed", "lookup"):
+                        self._read_only(op)
                 self.check_table(op)
+            if self.ext:
+                self.finish_feed()
+                self.check_table("the end")
             self.chained = self.g.chained_scans() if self.lab else 0
         finally:
             self.g.close()
@@ -299,6 +659,14 @@ def gp():
 @pytest.mark.parametrize("seed", range(int(os.environ.get("RIO_FUZZ_SEEDS", "36"))))
 def test_random_operation_sequences(gp, oracle, seed):
     Scenario(gp, oracle, seed).run()
+
+
+EXT_SEEDS = int(os.environ.get("RIO_FUZZ_EXT_SEEDS", "72"))
+
+
+@pytest.mark.parametrize("seed", range(EXT_SEEDS))
+def test_random_sequences_with_index_rebalance_and_feed(gp, oracle, seed):
+    Scenario(gp, oracle, seed, ext=True).run()
 
 
 def _sharded_scenario(gp, oracle, seed):
@@ -388,9 +756,10 @@ if __name__ == "__main__":
             cov["row-sharded tick streams"] = cov.get("row-sharded tick streams", 0) + 1
             seed += 1
             continue
-        sc = Scenario(rio_gp, pyoracle, seed, big=True)
+        sc = Scenario(rio_gp, pyoracle, seed, big=True, ext=seed % 2 == 1)   # old and extended scenarios alternate
         ops += sc.run()
-        for k, v in sc.count.items():
+        cov["extended scenarios"] = cov.get("extended scenarios", 0) + int(sc.ext)
+        for k, v in list(sc.count.items()) + list(sc.cov.items()):
             cov[k] = cov.get(k, 0) + v
         for k, on in (("tables >= 10^5 rows", sc.n >= 100_000), ("tables >= 2^19 rows", sc.n >= 524288), ("self-assign", sc.sa),
                       ("forced policies (lab build)", sc.lab), ("scenarios with chained quiet ticks", sc.chained > 0)):
