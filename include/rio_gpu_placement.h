@@ -268,7 +268,8 @@ typedef struct rio_gp_rebalance_stats {
  *     three are given together or not at all (RIO_GP_EINVAL).  With them B = min(max_moves, moves_cap), so the listing always
  *     fits; without them moves_cap must be 0.  *n_moves (may be NULL) = the number of moves.  st may be NULL.
  *   - RIO_GP_EINVAL (nothing changed): bad cfg / struct_size, rounds > 8, the output rule above, or a handle of the row-sharded
- *     solve (rio_gp_shard_*, rio_gp_p2p_*; rebalancing across row shards is not implemented).
+ *     solve (rio_gp_shard_comm_init / _p2p_connect / _tick_async: a row-sharded table is rebalanced through
+ *     rio_gp_shard_rebalance_*, below).
  *   - Like rio_gp_update_batch: it joins rio_gp_tick_async work in flight, drops an uncommitted rio_gp_solve, and counts as a
  *     change of the inputs (the next tick takes neither the quiet nor the chained form over the old column).
  *   - Cost: one streaming pass over the column, load and affinity when no live node is over its target; otherwise three more
@@ -489,6 +490,60 @@ int rio_gp_shard_comm_init(rio_gp_t* h, uint32_t rank, uint32_t n_ranks, const v
 uint32_t rio_gp_shard_comm_ranks(rio_gp_t* h);
 int rio_gp_shard_solve_async(rio_gp_t* h);
 int rio_gp_shard_exchange(rio_gp_t* h, const uint64_t* d_in, uint64_t* d_out, uint64_t words_per_rank);
+
+/* ---- row-sharded rebalance --------------------------------------------------------------- */
+/*
+ * rio_gp_rebalance of the CONCATENATED table (DESIGN.md section 2 rule 6 is stated over it), computed by the ranks of the
+ * row-sharded solve: rank r owns the rows [off_r, off_r + n_r), the node table, the targets and liveness are replicated, cfg is
+ * the same on every rank (max_moves and moves_cap are GLOBAL).  As above the library never talks to a peer: the caller
+ * all-gathers one small record between the steps, and every rank calls the same steps in the same order.  All reductions are
+ * integer sums in rank order, so the column, `used`, the counters and the moves equal the single-handle call's bit for bit.
+ *
+ *   begin -> [all-gather X] -> cut -> nodes_over == 0 ? finish
+ *         :  [all-gather S] -> select -> selected_total == 0 ? finish
+ *         :  [all-gather Y] -> merge -> { fill(round) -> [all-gather Y] -> merge } while rows are pending and round < rounds
+ *         -> finish
+ *
+ *   X (rio_gp_shard_words1 = 2m+8 u64): pinned load[m] | candidate load[m] of this rank's rows | 8 words (unused)
+ *   S (rio_gp_shard_words2 =  m+2 u64): this rank's surplus rows | their load | m words (zero)
+ *   Y (rio_gp_shard_words2) after select: used'_r[m] (the load of this rank's rows that are not selected) | selected load |
+ *       selected rows;  after fill: load admitted this round[m] | load still pending | rows still pending (the last round's
+ *       record also carries, per node, the load of the rows that found no node and keep theirs: R4)
+ *
+ *   R1 on rank r cuts the candidates of node j against free_j - (candidate load of j on ranks < r), free_j = T[j] -sat the pinned
+ *   load of all ranks; where the lower ranks' candidates alone exceed free_j every candidate of j on rank r is surplus, the
+ *   zero-load ones included.  R2: rank r selects its first clamp(B - surplus rows of ranks < r, 0, its own) surplus rows.  R3:
+ *   every round is one water-fill round over this rank's selected rows whose prefix starts at the pending load of the ranks
+ *   < r; `used` is rebuilt from the summed records between rounds.
+ *
+ * Handle state changes as in rio_gp_rebalance (joins rio_gp_tick_async work, drops an uncommitted solve, counts as a change of
+ * the inputs); `used` is the GLOBAL one of the new column on every rank after finish.  RIO_GP_EINVAL, nothing changed: bad cfg /
+ * struct_size, rounds > 8, rank >= n_ranks, moves_cap without list_moves, rio_gp_shard_tick_async ticks in flight, a step
+ * called out of order.  begin may be called at any step: it starts over.  Between begin and finish the handle belongs to the
+ * protocol: a call that changes an input of the solve (nodes, liveness, objects, CRUD, a solve, a tick, rio_gp_rebalance) or
+ * reads `used` (rio_gp_get_nodes) ends it, and the next step answers RIO_GP_EINVAL (the column is written by finish alone, so it
+ * is as it was).  d_* are DEVICE pointers owned by the caller.
+ */
+/* R0 over this rank's rows; d_x[words1] = X.  list_moves != 0: finish lists the moves and B = min(max_moves, moves_cap);
+ * *rounds_out (may be NULL) = the rounds that will run at most (cfg->rounds, 0 = the handle's spill_rounds).  Asynchronous. */
+int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, uint32_t rank, uint32_t n_ranks, int list_moves,
+                                 uint64_t moves_cap, uint64_t* d_x, uint32_t* rounds_out);
+/* d_xg[n_ranks][words1] gathered -> the global `used`, the cuts that fall on this rank, its surplus; d_s[words2] = S.
+ * *nodes_over = live nodes holding more candidate load than free_j, on all ranks: 0 ends the protocol (finish). */
+int rio_gp_shard_rebalance_cut(rio_gp_t* h, const uint64_t* d_xg, uint64_t* d_s, uint32_t* nodes_over);
+/* d_sg[n_ranks][words2] gathered -> R2, the selected rows packed; d_y[words2] = Y.  *selected_local sizes the move arrays of
+ * finish; *selected_total = min(B, surplus rows of all ranks): 0 ends the protocol (finish). */
+int rio_gp_shard_rebalance_select(rio_gp_t* h, const uint64_t* d_sg, uint64_t* d_y, uint64_t* selected_local,
+                                  uint64_t* selected_total);
+/* d_yg[n_ranks][words2] gathered -> the global `used`, this rank's prefix base; the rows / load pending on all ranks. */
+int rio_gp_shard_rebalance_merge(rio_gp_t* h, const uint64_t* d_yg, uint64_t* pending_rows, uint64_t* pending_load);
+/* Round `round` (0, 1, ... in order, while rows are pending and round < rounds) over this rank's selected rows; d_y = Y. */
+int rio_gp_shard_rebalance_fill(rio_gp_t* h, uint32_t round, uint64_t* d_y);
+/* R4, this rank's part of the column, its moves (HOST arrays of moves_cap >= *selected_local entries, given iff list_moves):
+ * ascending, with rank-LOCAL row numbers; add off_r and concatenate in rank order.  local_stats: surplus_*, selected_*, moved_*
+ * and stayed_rows of this rank's rows (sum them over the ranks); nodes_over_before / _after are global. */
+int rio_gp_shard_rebalance_finish(rio_gp_t* h, rio_gp_rebalance_stats* local_stats, uint32_t* out_rows, uint32_t* out_from,
+                                  uint32_t* out_to, uint64_t moves_cap, uint64_t* n_moves);
 
 /* ---- measurement hooks (HIP events on the handle's own stream) -------------------------- */
 int rio_gp_timer_begin(rio_gp_t* h);

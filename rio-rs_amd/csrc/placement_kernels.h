@@ -458,6 +458,39 @@ void launch_shed_round(u64 K, const u32* pk_load, u32* pk_node, const u64* tgt, 
 void launch_shed_finish(u64 K, const u32* pk_row, const u32* pk_load, const u32* pk_node, u32* assign, u64* used, u32* mc,
                         u64* acc, u32* out_rows, u32* out_from, u32* out_to, hipStream_t s);
 
+// --- row-sharded rebalance (rio_gp_shard_rebalance_*): the k_shed_* passes over one rank's rows; k_shrb_* carry the rank offsets ---
+constexpr int kShrbOver = 0, kShrbSlots = 1, kShrbForced = 2, kShrbOverBefore = 3, kShrbInfo = 4;  // u32 counters of k_shrb_import_x
+struct ShrbImport {
+    const u64* Xg;     // [R][2m + 8] gathered X records: pinned load | candidate load | counters
+    u32 rank, R, m;
+    const u64* T;      // [m] targets
+    const u32* live;   // [m] 0 / 1
+    u64* used;         // -> [m] global load per node
+    u64* tgt;          // -> [m] T on live nodes, 0 elsewhere
+    u32* map;          // -> [m] node -> slot where the cut falls on THIS rank (kNone elsewhere)
+    u32* slot_node;    // -> per slot
+    u64* slot_free;    // -> per slot: what the lower ranks' candidates left of free_j
+    u32* cut;          // -> [m] 0 where the cut fell on a lower rank (every candidate here is surplus), kNone elsewhere; the
+                       //    slots' nodes are filled in by k_shed_cut
+    u32* info;         // -> [kShrbInfo]
+};
+// X = pin | used - pin | 8 counters (0; the last one 1, as in the solve's record)
+void launch_shrb_export_x(const u64* used, const u64* pin, u32 m, u64* X, hipStream_t s);
+void launch_shrb_import_x(const ShrbImport& a, hipStream_t s);
+// launch_shed_cut without resetting `cut` (k_shrb_import_x wrote it)
+void launch_shrb_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
+                     const u64* slot_free, u64* mat, u32* cut, hipStream_t s);
+// Y = v[m] | *a | b
+void launch_shrb_export_y(const u64* v, u32 m, const u64* a, u64 b, u64* Y, hipStream_t s);
+// used = (first ? 0 : used) + sum of the gathered Y[q][0..m) in rank order; *base = sum of Y[q][m] over q < rank;
+// pend[0] = rows, pend[1] = load pending on all ranks
+void launch_shrb_merge(const u64* Yg, u32 rank, u32 R, u32 m, bool first, u64* used, u64* base, u64* pend, hipStream_t s);
+// launch_shed_round with the prefix starting at *base and the admissions going into Y (zeroed here) instead of `used`: Y =
+// admitted load[m] | load still pending | rows still pending.  last: the rows left without a node give their load back to their
+// own node in Y (R4), so that the sum over the ranks is the `used` of the new column.
+void launch_shrb_round(u64 K, const u32* pk_row, const u32* pk_load, u32* pk_node, const u32* assign, const u64* tgt, u32 m,
+                       const u64* used, const u64* base, bool last, u64* csum, u64* C, u32* ord, u32* cntp, u64* Y, hipStream_t s);
+
 // --- change feed (rio_gp_changes): count A != B per tile, then list the changed rows of the tiles that hold one ---
 constexpr u32 kChgTile = 1024;       // rows per tile: one wave, four steps of 256 rows (lane l: rows 4l .. 4l+3 of a step)
 constexpr u32 kChgWaves = 4;         // waves per workgroup; a workgroup owns `tpg` consecutive tiles, its waves take every 4th

@@ -6347,12 +6347,13 @@ __global__ __launch_bounds__(kBlock) void k_shed_count(const u32* __restrict__ a
     }
 }
 
-// exclusive scan of len values (in may be out), one workgroup; the total into *total
+// exclusive scan of len values (in may be out), one workgroup, starting at *init (NULL: 0); the total into *total
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_shed_scan(const T* in, T* out, u64 len, u64* __restrict__ total) {
+__global__ __launch_bounds__(kBlock) void k_shed_scan(const T* in, T* out, u64 len, u64* __restrict__ total,
+                                                      const u64* __restrict__ init = nullptr) {
     __shared__ u64 part[16];
     const int tid = threadIdx.x;
-    u64 carry = 0;
+    u64 carry = init ? *init : 0ull;
     for (u64 b = 0; b < len; b += kShChunk) {
         u64 v[4], loc = 0;
 #pragma unroll
@@ -6616,7 +6617,7 @@ void launch_shed_cut(const u32* assign, const u32* load, const u32* aff, const S
 void launch_shed_count(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, u32* tcnt, u64* acc,
                        hipStream_t s) {
     hipLaunchKernelGGL(k_shed_count, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32), s, assign, load, aff, p, cut, tcnt, acc);
-    hipLaunchKernelGGL((k_shed_scan<u32>), dim3(1), dim3(kBlock), 0, s, tcnt, tcnt, (u64)p.nt, acc + kShAccSurplusRows);
+    hipLaunchKernelGGL((k_shed_scan<u32>), dim3(1), dim3(kBlock), 0, s, tcnt, tcnt, (u64)p.nt, acc + kShAccSurplusRows, (const u64*)nullptr);
 }
 void launch_shed_pack(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* toff,
                       u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s) {
@@ -6627,7 +6628,7 @@ void launch_shed_round(u64 K, const u32* pk_load, u32* pk_node, const u64* tgt, 
                        u32* cntp, hipStream_t s) {
     const u32 nc = (u32)((K + kShChunk - 1) / kShChunk);
     hipLaunchKernelGGL(k_shed_csum, dim3(nc), dim3(kBlock), 0, s, K, pk_load, pk_node, csum);
-    hipLaunchKernelGGL((k_shed_scan<u64>), dim3(1), dim3(kBlock), 0, s, csum, csum, (u64)nc, nullptr);
+    hipLaunchKernelGGL((k_shed_scan<u64>), dim3(1), dim3(kBlock), 0, s, csum, csum, (u64)nc, nullptr, (const u64*)nullptr);
     hipLaunchKernelGGL(k_shed_order, dim3(1), dim3(kBlock), shed_order_lds(m), s, tgt, used, m, C, ord, cntp);
     hipLaunchKernelGGL(k_shed_fill, dim3(nc), dim3(kBlock), 0, s, K, pk_load, pk_node, csum, C, ord, cntp, used);
 }
@@ -6635,8 +6636,193 @@ void launch_shed_finish(u64 K, const u32* pk_row, const u32* pk_load, const u32*
                         u64* acc, u32* out_rows, u32* out_from, u32* out_to, hipStream_t s) {
     const u32 nc = (u32)((K + kShChunk - 1) / kShChunk);
     hipLaunchKernelGGL(k_shed_mcount, dim3(nc), dim3(kBlock), 0, s, K, pk_row, pk_load, pk_node, assign, used, mc, acc);
-    hipLaunchKernelGGL((k_shed_scan<u32>), dim3(1), dim3(kBlock), 0, s, mc, mc, (u64)nc, acc + kShAccMovedRows);
+    hipLaunchKernelGGL((k_shed_scan<u32>), dim3(1), dim3(kBlock), 0, s, mc, mc, (u64)nc, acc + kShAccMovedRows, (const u64*)nullptr);
     hipLaunchKernelGGL(k_shed_finish, dim3(nc), dim3(kBlock), 0, s, K, pk_row, pk_node, mc, assign, out_rows, out_from, out_to);
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// Row-sharded rebalance (rio_gp_shard_rebalance_*): rank r runs the k_shed_* passes over its own rows; what
+// couples the ranks travels in three small records and is reduced here, in rank order, one launch per gathered record:
+//   k_shrb_export_x   X = pinned load | candidate load of this rank's rows, per node
+//   k_shrb_import_x   per node: the global `used`, free_j = T -sat (pinned load of all ranks), and where the cut of an over node
+//                     falls: on a lower rank (cut[j] = 0: every candidate here is surplus, the zero-load ones included), on
+//                     this rank (a slot for k_shed_tile / k_shed_cut with free_j minus the lower ranks' candidates), or later
+//                     (nothing here is surplus)
+//   k_shrb_export_y   Y = a per-node vector and two scalars
+//   k_shrb_merge      `used` from the gathered Y records, this rank's prefix base, the rows / load pending on all ranks
+//   k_shrb_fill       k_shed_fill whose admissions go into the Y record; it counts what is still pending and, on the last
+//                     round, hands the load of the rows left over back to their own nodes
+// No kernel waits for another rank: the caller's all-gathers order everything.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_shrb_export_x(const u64* __restrict__ used, const u64* __restrict__ pin, u32 m,
+                                                          u64* __restrict__ X) {
+    const int tid = threadIdx.x;
+    for (u32 j = tid; j < m; j += kBlock) {
+        const u64 p = pin[j];
+        X[j] = p;
+        X[(size_t)m + j] = used[j] - p;
+    }
+    if (tid < 8) X[2 * (size_t)m + tid] = tid == 7 ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(kBlock) void k_shrb_import_x(const ShrbImport a) {
+    __shared__ u32 s_cnt[kShrbInfo];
+    const int tid = threadIdx.x;
+    if (tid < kShrbInfo) s_cnt[tid] = 0;
+    __syncthreads();
+    const size_t W = 2 * (size_t)a.m + 8;
+    u32 over = 0, forced = 0, before = 0;
+    for (u32 j = tid; j < a.m; j += kBlock) {
+        u64 P = 0, cpre = 0, ctot = 0, mine = 0;
+        for (u32 q = 0; q < a.R; ++q) {
+            const u64 p = a.Xg[q * W + j], c = a.Xg[q * W + a.m + j];
+            P += p;
+            if (q < a.rank) cpre += c;
+            if (q == a.rank) mine = c;
+            ctot += c;
+        }
+        const bool lv = a.live[j] != 0;
+        const u64 T = lv ? a.T[j] : 0ull;
+        a.used[j] = P + ctot;
+        a.tgt[j] = T;
+        u32 mp = kNone, ct = kNone;
+        if (lv) {
+            before += P + ctot > T;
+            const u64 fr = T > P ? T - P : 0ull;
+            if (ctot > fr) {
+                ++over;
+                if (cpre > fr) { ct = 0; ++forced; }
+                else if (cpre + mine > fr) {
+                    mp = atomicAdd(&s_cnt[kShrbSlots], 1u);  // (any order of the slots gives the same cuts)
+                    a.slot_node[mp] = j;
+                    a.slot_free[mp] = fr - cpre;
+                }
+            }
+        }
+        a.map[j] = mp;
+        a.cut[j] = ct;
+    }
+    over = wave_sum32(over);
+    forced = wave_sum32(forced);
+    before = wave_sum32(before);
+    if ((tid & 63) == 0) {
+        if (over) atomicAdd(&s_cnt[kShrbOver], over);
+        if (forced) atomicAdd(&s_cnt[kShrbForced], forced);
+        if (before) atomicAdd(&s_cnt[kShrbOverBefore], before);
+    }
+    __syncthreads();
+    if (tid < kShrbInfo) a.info[tid] = s_cnt[tid];
+}
+
+__global__ __launch_bounds__(kBlock) void k_shrb_export_y(const u64* __restrict__ v, u32 m, const u64* __restrict__ a, u64 b,
+                                                          u64* __restrict__ Y) {
+    const int tid = threadIdx.x;
+    for (u32 j = tid; j < m; j += kBlock) Y[j] = v[j];
+    if (tid == 0) { Y[m] = a ? *a : 0ull; Y[(size_t)m + 1] = b; }
+}
+
+__global__ __launch_bounds__(kBlock) void k_shrb_merge(const u64* __restrict__ Yg, u32 rank, u32 R, u32 m, bool first,
+                                                       u64* __restrict__ used, u64* __restrict__ base, u64* __restrict__ pend) {
+    const int tid = threadIdx.x;
+    const size_t W = (size_t)m + 2;
+    for (u32 j = tid; j < m; j += kBlock) {
+        u64 g = first ? 0ull : used[j];
+        for (u32 q = 0; q < R; ++q) g += Yg[q * W + j];
+        used[j] = g;
+    }
+    if (tid == 0) {
+        u64 b = 0, load = 0, rows = 0;
+        for (u32 q = 0; q < R; ++q) {
+            const u64 l = Yg[q * W + m];
+            if (q < rank) b += l;
+            load += l;
+            rows += Yg[q * W + m + 1];
+        }
+        *base = b;
+        pend[0] = rows;
+        pend[1] = load;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_shrb_fill(u64 K, const u32* __restrict__ pk_row, const u32* __restrict__ pk_load,
+                                                      u32* __restrict__ pk_node, const u32* __restrict__ assign,
+                                                      const u64* __restrict__ cpre, const u64* __restrict__ C,
+                                                      const u32* __restrict__ ord, const u32* __restrict__ cntp, bool last, u32 m,
+                                                      u64* __restrict__ Y) {
+    __shared__ u64 part[16];
+    const u64 r0 = (u64)blockIdx.x * kShChunk + (u64)threadIdx.x * 4;
+    const u32 cnt = *cntp;
+    const u64 F = C[cnt];
+    u32 l[4];
+    bool pend[4];
+    u64 loc = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        pend[k] = r0 + k < K && pk_node[r0 + k] == kNone;
+        l[k] = pend[k] ? pk_load[r0 + k] : 0u;
+        loc += l[k];
+    }
+    u64 Q = cpre[blockIdx.x] + block_excl_scan_1024(loc, false, part, nullptr);  // (cpre starts at this rank's base)
+    u32 nd[4];
+    u64 left_load = 0;
+    u32 left_rows = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        nd[k] = kNone;
+        if (pend[k] && cnt && Q < F) {
+            u32 lo = 0, hi = cnt;  // largest k with C[k] <= Q
+            while (hi - lo > 1) {
+                const u32 mid = lo + (hi - lo) / 2;
+                if (C[mid] <= Q) lo = mid; else hi = mid;
+            }
+            if (Q + (u64)l[k] <= C[lo + 1]) { nd[k] = ord[lo]; pk_node[r0 + k] = nd[k]; }
+        }
+        Q += l[k];
+        if (pend[k] && nd[k] == kNone) {
+            ++left_rows;
+            left_load += l[k];
+            if (last) nd[k] = assign[pk_row[r0 + k]];  // R4: its load stays on its own node (pk_node stays kNone)
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) shed_agg_add(Y, nd[k], l[k], nd[k] < m && l[k] != 0, false);
+    left_load = wave_sum(left_load);
+    left_rows = wave_sum32(left_rows);
+    if ((threadIdx.x & 63) == 0 && left_rows) {
+        atomicAdd(&Y[m], left_load);
+        atomicAdd(&Y[(size_t)m + 1], (u64)left_rows);
+    }
+}
+
+void launch_shrb_export_x(const u64* used, const u64* pin, u32 m, u64* X, hipStream_t s) {
+    hipLaunchKernelGGL(k_shrb_export_x, dim3(1), dim3(kBlock), 0, s, used, pin, m, X);
+}
+void launch_shrb_import_x(const ShrbImport& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_shrb_import_x, dim3(1), dim3(kBlock), 0, s, a);
+}
+void launch_shrb_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
+                     const u64* slot_free, u64* mat, u32* cut, hipStream_t s) {
+    if (!p.s || !p.n) return;
+    hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), (size_t)p.s * sizeof(u64) + (size_t)p.m * sizeof(u32), s, assign,
+                       load, aff, p, map, mat);
+    hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, cut);
+}
+void launch_shrb_export_y(const u64* v, u32 m, const u64* a, u64 b, u64* Y, hipStream_t s) {
+    hipLaunchKernelGGL(k_shrb_export_y, dim3(1), dim3(kBlock), 0, s, v, m, a, b, Y);
+}
+void launch_shrb_merge(const u64* Yg, u32 rank, u32 R, u32 m, bool first, u64* used, u64* base, u64* pend, hipStream_t s) {
+    hipLaunchKernelGGL(k_shrb_merge, dim3(1), dim3(kBlock), 0, s, Yg, rank, R, m, first, used, base, pend);
+}
+void launch_shrb_round(u64 K, const u32* pk_row, const u32* pk_load, u32* pk_node, const u32* assign, const u64* tgt, u32 m,
+                       const u64* used, const u64* base, bool last, u64* csum, u64* C, u32* ord, u32* cntp, u64* Y, hipStream_t s) {
+    (void)hipMemsetAsync(Y, 0, ((size_t)m + 2) * sizeof(u64), s);
+    if (!K) return;
+    const u32 nc = (u32)((K + kShChunk - 1) / kShChunk);
+    hipLaunchKernelGGL(k_shed_csum, dim3(nc), dim3(kBlock), 0, s, K, pk_load, pk_node, csum);
+    hipLaunchKernelGGL((k_shed_scan<u64>), dim3(1), dim3(kBlock), 0, s, csum, csum, (u64)nc, (u64*)nullptr, base);
+    hipLaunchKernelGGL(k_shed_order, dim3(1), dim3(kBlock), shed_order_lds(m), s, tgt, used, m, C, ord, cntp);
+    hipLaunchKernelGGL(k_shrb_fill, dim3(nc), dim3(kBlock), 0, s, K, pk_row, pk_load, pk_node, assign, csum, C, ord, cntp, last, m, Y);
 }
 
 

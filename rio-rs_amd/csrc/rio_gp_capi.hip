@@ -284,6 +284,17 @@ struct rio_gp {
     // bounded rebalance (rio_gp_rebalance), grown on use: per-node arrays + counters, the (over node x tile) matrix, per-tile and
     // per-chunk counts, the packed rows (row | load | node), the host-pointer form's move listing (row | from | to)
     DevBuf sh_nodes, sh_mat, sh_tile, sh_chunk, sh_pk, sh_mv;
+    // row-sharded rebalance (rio_gp_shard_rebalance_*): the protocol's step, what the gathered records said, the host's copies
+    // of the targets and the live flags (they outlive the calls that upload them)
+    int rb_state = 0;        // 0 idle | 1 begun (X out) | 2 cut (surplus record out) | 3 selected (Y out) | 4 merged | 5 round exported
+    u32 rb_rank = 0, rb_R = 1, rb_rounds = 0, rb_fills = 0;
+    bool rb_list = false, rb_first = false;
+    u64 rb_budget = 0, rb_K = 0, rb_sel_total = 0, rb_pending = 0;
+    u32 rb_over = 0, rb_over_before = 0;
+    u64 rb_epoch = 0;        // mut_epoch as rio_gp_shard_rebalance_begin left it: any other change of the inputs ends the protocol
+    ShPlan rb_plan{};
+    std::vector<u64> rb_T;
+    std::vector<u32> rb_live;
     // change feed (rio_gp_changes), allocated on first use: the checkpoint column B (cap_rows u32, RIO_GP_NONE to begin with), the
     // per-tile counts, the workgroup sums + total, a mapped word the total arrives in; the host-pointer form's staged listing
     // (row | old | new, grows to the largest listing)
@@ -2846,6 +2857,276 @@ int rio_gp_shard_finish(rio_gp_t* h, rio_gp_stats* local_stats) {
     h->have_solved = true;
     h->ring_n = 0;
     h->sh_state = 0;
+    return RIO_GP_OK;
+}
+
+// ---- row-sharded rebalance -------------------------------------------------------------------
+// The phases of rebalance_locked over one rank's rows, cut at the points where the single-handle call waits for the device: what
+// the host decided there from `used` and `pin` is decided here from the gathered records, on the device (k_shrb_import_x /
+// k_shrb_merge), in rank order.
+
+namespace {
+struct RbBufs {
+    u64 *pin, *tgt, *slot_free, *C, *acc, *lu, *tdev, *base;
+    u32 *map, *slot_node, *cut, *ord, *cntp, *live, *info;
+};
+constexpr int kRbPend = 6;  // acc[6], acc[7]: rows / load pending on all ranks (k_shrb_merge)
+RbBufs rb_bufs(rio_gp* h) {
+    const size_t M = h->cap_nodes;
+    RbBufs b;
+    b.pin = (u64*)h->sh_nodes.p;
+    b.tgt = b.pin + M;
+    b.slot_free = b.tgt + M;
+    b.C = b.slot_free + M;
+    b.acc = b.C + M + 1;
+    b.lu = b.acc + kShAcc;
+    b.tdev = b.lu + M;
+    b.base = b.tdev + M;
+    b.map = (u32*)(b.base + 1);
+    b.slot_node = b.map + M;
+    b.cut = b.slot_node + M;
+    b.ord = b.cut + M;
+    b.cntp = b.ord + M;
+    b.live = b.cntp + 4;
+    b.info = b.live + M;
+    return b;
+}
+// A step continues the protocol only on the handle as begin left it: no call that changes an input of the solve (they all
+// count in mut_epoch) and none that rebuilt or republished `used` (which holds the protocol's vectors) came between.
+bool rb_at(rio_gp* h, int state) {
+    if (h->rb_state != 0 && (h->mut_epoch != h->rb_epoch || h->used_valid)) h->rb_state = 0;
+    return h->rb_state == state;
+}
+int rb_ensure(rio_gp* h) {
+    const size_t M = h->cap_nodes;
+    return ensure(h, h->sh_nodes, (6 * M + 2 + kShAcc) * sizeof(u64) + (5 * M + 4 + kShrbInfo) * sizeof(u32));
+}
+}  // namespace
+
+int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, uint32_t rank, uint32_t n_ranks, int list_moves,
+                                 uint64_t moves_cap, uint64_t* d_x, uint32_t* rounds_out) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (!cfg || cfg->struct_size != sizeof(rio_gp_rebalance_cfg))
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: cfg missing or struct_size differs");
+    if (cfg->rounds > 8) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: rounds above the solver limit (8)");
+    if (!d_x || n_ranks == 0 || rank >= n_ranks) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: rank >= n_ranks, or no record");
+    if (!list_moves && moves_cap) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: moves_cap without a move listing");
+    if (h->sh_tick_n) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: rio_gp_shard_tick_async ticks in flight (rio_gp_shard_tick_wait first)");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = rb_ensure(h))) return rc;
+    const RbBufs b = rb_bufs(h);
+    const u32 m = h->m;
+    // a change of the inputs, like rio_gp_rebalance: an uncommitted solve (a sharded one half way included) is dropped
+    h->have_solved = false; ++h->mut_epoch;
+    h->sh_state = 0;
+    h->ring_n = 0;
+    h->used_parts = false;
+    h->used_valid = false;  // until rio_gp_shard_rebalance_finish: `used` holds the protocol's intermediate vectors
+    h->rb_rank = rank; h->rb_R = n_ranks;
+    h->rb_rounds = cfg->rounds ? cfg->rounds : h->rounds;
+    h->rb_list = list_moves != 0;
+    h->rb_budget = list_moves ? std::min<u64>(cfg->max_moves, moves_cap) : cfg->max_moves;
+    h->rb_K = h->rb_sel_total = h->rb_pending = 0;
+    h->rb_fills = 0;
+    h->rb_over = h->rb_over_before = 0;
+    h->rb_T.assign(m ? m : 1, 0);
+    h->rb_live.assign(m ? m : 1, 0);
+    for (u32 j = 0; j < m; ++j) h->rb_live[j] = h->h_alive[j] ? 1u : 0u;
+    if (cfg->target) {
+        memcpy(h->rb_T.data(), cfg->target, (size_t)m * sizeof(u64));
+        if (m) HIPCHK(h, hipMemcpyAsync(b.tdev, h->rb_T.data(), (size_t)m * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    } else if (m) {  // (read by the host in _finish, behind the waits of the steps between)
+        HIPCHK(h, hipMemcpyAsync(h->rb_T.data(), h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(b.tdev, h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
+    }
+    if (m) HIPCHK(h, hipMemcpyAsync(b.live, h->rb_live.data(), (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(b.acc, 0, kShAcc * sizeof(u64), h->stream));
+    // R0 over this rank's rows: the load per node (kept in lu: it becomes used'_r in _select) and the pinned load
+    launch_shed_hist(h->assign[h->cur], h->load, h->aff, h->n, m, b.lu, b.pin, h->stream);
+    launch_shrb_export_x(b.lu, b.pin, m, reinterpret_cast<u64*>(d_x), h->stream);
+    HIPCHK(h, hipGetLastError());
+    if (rounds_out) *rounds_out = h->rb_rounds;
+    h->rb_epoch = h->mut_epoch;
+    h->rb_state = 1;
+    return RIO_GP_OK;
+}
+
+int rio_gp_shard_rebalance_cut(rio_gp_t* h, const uint64_t* d_xg, uint64_t* d_s, uint32_t* nodes_over) {
+    if (!h || !d_xg || !d_s) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (!rb_at(h, 1)) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_cut: call rio_gp_shard_rebalance_begin first");
+    HIPCHK(h, hipSetDevice(h->device));
+    const RbBufs b = rb_bufs(h);
+    const u32 m = h->m;
+    ShrbImport a{};
+    a.Xg = reinterpret_cast<const u64*>(d_xg);
+    a.rank = h->rb_rank; a.R = h->rb_R; a.m = m;
+    a.T = b.tdev; a.live = b.live;
+    a.used = h->used; a.tgt = b.tgt; a.map = b.map; a.slot_node = b.slot_node; a.slot_free = b.slot_free; a.cut = b.cut;
+    a.info = b.info;
+    launch_shrb_import_x(a, h->stream);
+    HIPCHK(h, hipGetLastError());
+    u32 info[kShrbInfo];
+    HIPCHK(h, hipMemcpyAsync(info, b.info, sizeof info, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->rb_over = info[kShrbOver];
+    h->rb_over_before = info[kShrbOverBefore];
+    const u32 S = info[kShrbSlots];
+    const ShPlan p = sh_plan(h->n, m, S);
+    h->rb_plan = p;
+    HIPCHK(h, hipMemsetAsync(d_s, 0, ((size_t)m + 2) * sizeof(u64), h->stream));
+    if (h->n && (S || info[kShrbForced])) {  // R1 over this rank's rows: the exact cuts that fall here, the surplus per tile
+        int rc;
+        if ((rc = ensure(h, h->sh_mat, (size_t)std::max<u32>(S, 1) * p.nt * sizeof(u64))) ||
+            (rc = ensure(h, h->sh_tile, (size_t)p.nt * sizeof(u32))))
+            return rc;
+        launch_shrb_cut(h->assign[h->cur], h->load, h->aff, p, b.map, b.slot_node, b.slot_free, (u64*)h->sh_mat.p, b.cut, h->stream);
+        launch_shed_count(h->assign[h->cur], h->load, h->aff, p, b.cut, (u32*)h->sh_tile.p, b.acc, h->stream);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(d_s, b.acc, 2 * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));  // surplus rows | load
+    }
+    if (nodes_over) *nodes_over = h->rb_over;
+    h->rb_state = 2;
+    return RIO_GP_OK;
+}
+
+int rio_gp_shard_rebalance_select(rio_gp_t* h, const uint64_t* d_sg, uint64_t* d_y, uint64_t* selected_local,
+                                  uint64_t* selected_total) {
+    if (!h || !d_sg || !d_y) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (!rb_at(h, 2) || !h->rb_over)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_select: call rio_gp_shard_rebalance_cut first (and only when it reports nodes over)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const RbBufs b = rb_bufs(h);
+    const u32 m = h->m, R = h->rb_R;
+    const size_t W = (size_t)m + 2;
+    std::vector<u64> sg(2 * (size_t)R);
+    HIPCHK(h, hipMemcpy2DAsync(sg.data(), 2 * sizeof(u64), d_sg, W * sizeof(u64), 2 * sizeof(u64), R, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    u64 pre = 0, tot = 0;
+    for (u32 q = 0; q < R; ++q) {
+        if (q < h->rb_rank) pre += sg[2 * q];
+        tot += sg[2 * q];
+    }
+    const u64 mine = sg[2 * (size_t)h->rb_rank], B = h->rb_budget;
+    const u64 K = B > pre ? std::min<u64>(B - pre, mine) : 0;  // R2: this rank's share of the first B surplus rows
+    h->rb_K = K;
+    h->rb_sel_total = std::min<u64>(B, tot);
+    if (K) {
+        int rc;
+        const u64 nc = (K + kShChunk - 1) / kShChunk;
+        if ((rc = ensure(h, h->sh_pk, 3 * K * sizeof(u32))) || (rc = ensure(h, h->sh_chunk, nc * sizeof(u64)))) return rc;
+        u32* pk_row = (u32*)h->sh_pk.p;
+        launch_shed_pack(h->assign[h->cur], h->load, h->aff, h->rb_plan, b.cut, (const u32*)h->sh_tile.p, K, pk_row, pk_row + K,
+                         pk_row + 2 * K, b.lu, b.acc, h->stream);
+    }
+    launch_shrb_export_y(b.lu, m, b.acc + kShAccSelectedLoad, K, reinterpret_cast<u64*>(d_y), h->stream);
+    HIPCHK(h, hipGetLastError());
+    if (selected_local) *selected_local = K;
+    if (selected_total) *selected_total = h->rb_sel_total;
+    h->rb_first = true;
+    h->rb_state = 3;
+    return RIO_GP_OK;
+}
+
+int rio_gp_shard_rebalance_merge(rio_gp_t* h, const uint64_t* d_yg, uint64_t* pending_rows, uint64_t* pending_load) {
+    if (!h || !d_yg) return RIO_GP_EINVAL;
+    Locked g(h);
+    if ((!rb_at(h, 3) || !h->rb_sel_total) && !rb_at(h, 5))
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_merge: nothing exported (rio_gp_shard_rebalance_select with rows selected, or _fill, first)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const RbBufs b = rb_bufs(h);
+    launch_shrb_merge(reinterpret_cast<const u64*>(d_yg), h->rb_rank, h->rb_R, h->m, h->rb_first, h->used, b.base, b.acc + kRbPend,
+                      h->stream);
+    HIPCHK(h, hipGetLastError());
+    u64 pend[2];
+    HIPCHK(h, hipMemcpyAsync(pend, b.acc + kRbPend, sizeof pend, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->rb_first = false;
+    h->rb_pending = pend[0];
+    if (pending_rows) *pending_rows = pend[0];
+    if (pending_load) *pending_load = pend[1];
+    h->rb_state = 4;
+    return RIO_GP_OK;
+}
+
+int rio_gp_shard_rebalance_fill(rio_gp_t* h, uint32_t round, uint64_t* d_y) {
+    if (!h || !d_y) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (!rb_at(h, 4) || round != h->rb_fills || round >= h->rb_rounds || !h->rb_pending)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_fill: call rio_gp_shard_rebalance_merge first; rounds run in order while rows are pending");
+    HIPCHK(h, hipSetDevice(h->device));
+    const RbBufs b = rb_bufs(h);
+    const u64 K = h->rb_K;
+    u32* pk_row = (u32*)h->sh_pk.p;
+    launch_shrb_round(K, pk_row, pk_row + K, pk_row + 2 * K, h->assign[h->cur], b.tgt, h->m, h->used, b.base,
+                      round + 1 == h->rb_rounds, (u64*)h->sh_chunk.p, b.C, b.ord, b.cntp, reinterpret_cast<u64*>(d_y), h->stream);
+    HIPCHK(h, hipGetLastError());
+    ++h->rb_fills;
+    h->rb_state = 5;
+    return RIO_GP_OK;
+}
+
+int rio_gp_shard_rebalance_finish(rio_gp_t* h, rio_gp_rebalance_stats* local_stats, uint32_t* out_rows, uint32_t* out_from,
+                                  uint32_t* out_to, uint64_t moves_cap, uint64_t* n_moves) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    (void)rb_at(h, 0);
+    const bool done = (h->rb_state == 2 && !h->rb_over) || (h->rb_state == 3 && !h->rb_sel_total) ||
+                      (h->rb_state == 4 && (!h->rb_pending || h->rb_fills == h->rb_rounds));
+    if (!done) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_finish: the protocol has not reached its end");
+    if ((out_rows != nullptr) != (out_from != nullptr) || (out_rows != nullptr) != (out_to != nullptr))
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_finish: out_rows / out_from / out_to are given together or not at all");
+    if ((out_rows != nullptr) != h->rb_list)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_finish: the move listing is asked for in rio_gp_shard_rebalance_begin");
+    const u64 K = h->rb_state == 4 ? h->rb_K : 0;
+    if (out_rows ? moves_cap < K : moves_cap != 0)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_finish: moves_cap below this rank's selected rows (rio_gp_shard_rebalance_select)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const RbBufs b = rb_bufs(h);
+    const u32 m = h->m;
+    rio_gp_rebalance_stats s{};
+    int rc;
+    u32* d = nullptr;
+    if (K) {
+        if (out_rows) {
+            if ((rc = ensure(h, h->sh_mv, 3 * K * sizeof(u32)))) return rc;
+            d = (u32*)h->sh_mv.p;
+        }
+        u32* pk_row = (u32*)h->sh_pk.p;
+        // (the rows left without a node gave their load back in the last round's record: k_shed_mcount's returns go to scratch)
+        launch_shed_finish(K, pk_row, pk_row + K, pk_row + 2 * K, h->assign[h->cur], b.lu, (u32*)h->sh_chunk.p, b.acc, d,
+                           d ? d + K : nullptr, d ? d + 2 * K : nullptr, h->stream);
+        HIPCHK(h, hipGetLastError());
+    }
+    u64 a[kShAcc];
+    std::vector<u64> used(m ? m : 1);
+    HIPCHK(h, hipMemcpyAsync(a, b.acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
+    if (m) HIPCHK(h, hipMemcpyAsync(used.data(), h->used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    s.surplus_rows = a[kShAccSurplusRows];
+    s.surplus_load = a[kShAccSurplusLoad];
+    s.selected_rows = h->rb_state >= 3 ? h->rb_K : 0;
+    s.selected_load = a[kShAccSelectedLoad];
+    if (K) {
+        s.moved_rows = a[kShAccMovedRows];
+        s.moved_load = a[kShAccMovedLoad];
+        s.stayed_rows = a[kShAccStayed];
+    }
+    s.nodes_over_before = h->rb_over_before;
+    for (u32 j = 0; j < m; ++j) s.nodes_over_after += h->h_alive[j] && used[j] > h->rb_T[j];
+    if (out_rows && s.moved_rows) {
+        HIPCHK(h, hipMemcpyAsync(out_rows, d, s.moved_rows * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(out_from, d + K, s.moved_rows * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(out_to, d + 2 * K, s.moved_rows * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (n_moves) *n_moves = s.moved_rows;
+    if (local_stats) *local_stats = s;
+    h->used_valid = true;  // the global `used` of the new column, on every rank
+    h->rb_state = 0;
     return RIO_GP_OK;
 }
 

@@ -26,6 +26,7 @@ import rio_gp
 
 STAT_KEYS = ("n_objects", "kept", "evicted", "claimed", "spilled", "unplaced",
              "load_kept", "load_claimed", "load_spilled", "load_unplaced")
+REBALANCE_SUM_KEYS = ("surplus_rows", "surplus_load", "selected_rows", "selected_load", "moved_rows", "moved_load", "stayed_rows")
 
 
 class ShardInfo(C.Structure):
@@ -68,6 +69,14 @@ def _lib():
         L.rio_gp_shard_p2p_close.argtypes = [vp]
         L.rio_gp_shard_tick_async.argtypes = [vp]
         L.rio_gp_shard_tick_wait.argtypes = [vp, C.POINTER(ShardTickInfo), C.c_uint32, C.POINTER(C.c_uint32)]
+        u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        L.rio_gp_shard_rebalance_begin.argtypes = [vp, C.POINTER(rio_gp.RebalanceCfg), C.c_uint32, C.c_uint32, C.c_int,
+                                                   C.c_uint64, vp, u32p]
+        L.rio_gp_shard_rebalance_cut.argtypes = [vp, vp, vp, u32p]
+        L.rio_gp_shard_rebalance_select.argtypes = [vp, vp, vp, u64p, u64p]
+        L.rio_gp_shard_rebalance_merge.argtypes = [vp, vp, u64p, u64p]
+        L.rio_gp_shard_rebalance_fill.argtypes = [vp, C.c_uint32, vp]
+        L.rio_gp_shard_rebalance_finish.argtypes = [vp, C.POINTER(rio_gp.RebalanceStats), vp, vp, vp, C.c_uint64, u64p]
         _ready = True
     return L
 
@@ -141,6 +150,72 @@ class HipShardEngine:
                      rounds_run=int(buf[k].rounds_run))
             out.append(d)
         return out
+
+    # -- row-sharded rebalance: one method per step of rio_gp_shard_rebalance_* --
+    @property
+    def num_rows(self):
+        return self.g.num_objects
+
+    def _rb_words(self, t, per_node, n_ranks=1):
+        # The kernels stride the records by the handle's CURRENT node count, the exchange by the buffers' size: both must be
+        # what this engine was made with, or the gathered records would be read at the wrong offsets.
+        w1, w2 = int(_lib().rio_gp_shard_words1(self.g.handle)), int(_lib().rio_gp_shard_words2(self.g.handle))
+        if (w1, w2) != (self.words1, self.words2):
+            raise ValueError("the node count changed since this engine was made (records of %d / %d words, now %d / %d): make "
+                             "the engine and the solver again after rio_gp_set_nodes" % (self.words1, self.words2, w1, w2))
+        need = n_ranks * (w1 if per_node == 2 else w2)
+        if t.numel() != need:
+            raise ValueError("record buffer of %d words, %d expected" % (t.numel(), need))
+        return C.c_void_p(t.data_ptr())
+
+    def rebalance_begin(self, rank, n_ranks, target, max_moves, rounds, list_moves, x):
+        """R0 over this shard; x = its X record.  max_moves: the GLOBAL budget (an int; rio_gp.CAP_INF = no limit).  Returns
+        the number of water-fill rounds that run at most."""
+        self._rb_R = n_ranks
+        cfg, _keep = self.g._rebalance_cfg(target, max_moves, rounds)
+        nr = C.c_uint32(0)
+        self.g._chk(_lib().rio_gp_shard_rebalance_begin(self.g.handle, C.byref(cfg), rank, n_ranks, int(bool(list_moves)),
+                                                        int(max_moves) if list_moves else 0, self._rb_words(x, 2),
+                                                        C.byref(nr)))
+        return int(nr.value)
+
+    def rebalance_cut(self, xg, s):
+        over = C.c_uint32(0)
+        self.g._chk(_lib().rio_gp_shard_rebalance_cut(self.g.handle, self._rb_words(xg, 2, self._rb_R), self._rb_words(s, 1),
+                                                      C.byref(over)))
+        return int(over.value)
+
+    def rebalance_select(self, sg, y):
+        loc, tot = C.c_uint64(0), C.c_uint64(0)
+        self.g._chk(_lib().rio_gp_shard_rebalance_select(self.g.handle, self._rb_words(sg, 1, self._rb_R), self._rb_words(y, 1),
+                                                         C.byref(loc), C.byref(tot)))
+        self._rb_selected = int(loc.value)
+        return int(loc.value), int(tot.value)
+
+    def rebalance_merge(self, yg):
+        rows, load = C.c_uint64(0), C.c_uint64(0)
+        self.g._chk(_lib().rio_gp_shard_rebalance_merge(self.g.handle, self._rb_words(yg, 1, self._rb_R), C.byref(rows),
+                                                        C.byref(load)))
+        return int(rows.value), int(load.value)
+
+    def rebalance_fill(self, rnd, y):
+        self.g._chk(_lib().rio_gp_shard_rebalance_fill(self.g.handle, rnd, self._rb_words(y, 1)))
+
+    def rebalance_finish(self, list_moves):
+        """(local stats dict, rows, from, to): this shard's moves, ascending, with shard-local row numbers."""
+        st, nm = rio_gp.RebalanceStats(), C.c_uint64(0)
+        if list_moves:
+            cap = getattr(self, "_rb_selected", 0)
+            buf = np.empty((3, max(cap, 1)), np.uint32)
+            self.g._chk(_lib().rio_gp_shard_rebalance_finish(self.g.handle, C.byref(st), buf[0].ctypes.data, buf[1].ctypes.data,
+                                                             buf[2].ctypes.data, cap, C.byref(nm)))
+            k = int(nm.value)
+            self._rb_selected = 0
+            return st.as_dict(), buf[0, :k].copy(), buf[1, :k].copy(), buf[2, :k].copy()
+        self.g._chk(_lib().rio_gp_shard_rebalance_finish(self.g.handle, C.byref(st), None, None, None, 0, C.byref(nm)))
+        self._rb_selected = 0
+        e = np.empty(0, np.uint32)
+        return st.as_dict(), e, e, e
 
     def sync(self):
         self.g.sync()
@@ -384,6 +459,44 @@ class ShardedSolver:
         st = self.solve()
         self.commit()
         return st
+
+    # -- bounded rebalance of the row-sharded table (rio_gp_shard_rebalance_*): 3 + rounds exchanges at most --
+    def rebalance(self, target=None, max_moves=None, rounds=0, list_moves=True):
+        """rio_gp_rebalance of the concatenated table: (stats, rows, from, to) — global counters; the moves of THIS process's
+        shards in row order with global row numbers (every shard's, ascending, under LocalExchange).  target, max_moves and
+        rounds as in GpuPlacement.rebalance, the same on every rank; max_moves is the budget of the whole table."""
+        B = rio_gp.CAP_INF if max_moves is None else int(max_moves)
+        E = self.engines
+        nr = [e.rebalance_begin(r, self.R, target, B, rounds, list_moves, x) for e, r, x in zip(E, self.ranks, self.X)][0]
+        xg = self._gather(self.X, out=self.XG[0])
+        over = [e.rebalance_cut(xg, y) for e, y in zip(E, self.Y)][0]
+        if over:
+            sg = self._gather(self.Y)
+            total = [e.rebalance_select(sg, y) for e, y in zip(E, self.Y)][0][1]
+            if total:
+                yg = self._gather(self.Y)
+                pend = [e.rebalance_merge(yg) for e in E][0]
+                rnd = 0
+                while pend[0] and rnd < nr:
+                    for e, y in zip(E, self.Y):
+                        e.rebalance_fill(rnd, y)
+                    yg = self._gather(self.Y)
+                    pend = [e.rebalance_merge(yg) for e in E][0]
+                    rnd += 1
+        local = [e.rebalance_finish(list_moves) for e in E]
+        # the counters summed and the row offsets (an exclusive sum of n_r in rank order), in one exchange
+        nk = len(REBALANCE_SUM_KEYS)
+        for s_t, e, (st, _, _, _) in zip(self.S, E, local):
+            self._copy_in(s_t, torch.tensor([e.num_rows] + [st[k] for k in REBALANCE_SUM_KEYS] +
+                                            [0] * (len(STAT_KEYS) - nk - 1), dtype=torch.int64))
+        sg = self._gather(self.S).cpu().numpy().reshape(self.R, len(STAT_KEYS)).astype(np.uint64)
+        tot = sg.sum(axis=0)
+        stats = {k: int(tot[1 + i]) for i, k in enumerate(REBALANCE_SUM_KEYS)}
+        stats.update(nodes_over_before=local[0][0]["nodes_over_before"], nodes_over_after=local[0][0]["nodes_over_after"])
+        off = np.concatenate([[0], np.cumsum(sg[:, 0])]).astype(np.uint64)
+        rows = [(mv[1].astype(np.uint64) + off[r]).astype(np.uint32) for mv, r in zip(local, self.ranks)]
+        cat = lambda xs: np.concatenate(xs) if xs else np.empty(0, np.uint32)
+        return stats, cat(rows), cat([mv[2] for mv in local]), cat([mv[3] for mv in local])
 
     # -- committed ticks with nothing waiting on the host (HIP engines over peer-to-peer windows) --
     def tick_async(self):
