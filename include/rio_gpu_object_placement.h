@@ -188,7 +188,8 @@ int rio_op_get_or_create_placement_n(rio_op_t* p, const char* struct_name, size_
  * not an active, well-formed member, the table lock held by a writer — nothing was done, make the blocking call.  An async host
  * calls these inline on its worker thread and pays the hand-off to a blocking thread (tokio::task::spawn_blocking: several
  * microseconds) only on EAGAIN; LocalObjectPlacement::lookup never yields either (local.rs:42-49).  With
- * RIO_OP_CFG_NO_HOST_SHADOW every call is EAGAIN. */
+ * RIO_OP_CFG_NO_HOST_SHADOW every call about an interned key is EAGAIN (a lookup of a key nobody has interned is still Ok(None):
+ * that answer comes from the interning table, not from the shadow). */
 int rio_op_try_lookup_n(rio_op_t* p, const char* struct_name, size_t struct_name_len, const char* object_id, size_t object_id_len,
                         char* out, size_t out_cap, int* found);
 int rio_op_try_get_or_create_placement_n(rio_op_t* p, const char* struct_name, size_t struct_name_len, const char* object_id,

@@ -258,9 +258,17 @@ class GpuPlacement:
             text = (self._L.rio_gp_last_error(self._h) or b"").decode()
             raise ObjectPlacementError("Unknown" if rc == EINVAL else "Upstream", text, rc)
 
+    @classmethod
+    def borrowed(cls, handle):
+        """A GpuPlacement over a rio_gp_t* somebody else owns (rio_op_dense): close() forgets the handle, it does not destroy it."""
+        g = cls.__new__(cls)
+        g._lab, g._L, g._h, g._borrowed = False, lib(), _vp(handle), True
+        return g
+
     def close(self):
         if getattr(self, "_h", None):
-            self._L.rio_gp_destroy(self._h)
+            if not getattr(self, "_borrowed", False):
+                self._L.rio_gp_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -925,6 +933,11 @@ class GpuObjectPlacement:
 
     def invalidate_cache(self):
         self._chk(_oplib().rio_op_invalidate_cache(self._h))
+
+    def dense(self):
+        """rio_op_dense: the dense handle underneath, borrowed — valid while this provider (or a clone) lives; closing the
+        wrapper does not destroy it.  A mutation made through it bypasses the host shadow: follow it with invalidate_cache()."""
+        return GpuPlacement.borrowed(_oplib().rio_op_dense(self._h))
 
     def device_round_trips(self):
         """(combined batches, requests they carried) of the single-object calls so far."""

@@ -1,0 +1,597 @@
+"""A plain-Python stand-in for the string layer (rio_op_*, rio-rs_amd/csrc/gpu_object_placement.cpp), FOR TESTS ONLY: what
+include/rio_gpu_object_placement.h documents, over a row-lifecycle dense table built on tests/fake_rio_gp.py — a dict interner,
+lazy reclaim when the table runs full, rows kept for rio_op_set_object_load, a host shadow by stamp, the feed's retired rows.
+It lets tests/op_layer_driver.py be tested without a GPU (tests/test_op_layer_driver.py): `fault=` makes exactly one behaviour
+wrong, and the driver must notice.  It is not a CPU backend: nothing under rio-rs_amd/ imports it.
+
+It offers the surface the driver's adapter offers (op_layer_driver.RealProvider): return codes instead of exceptions, and
+`mid` callbacks where the real adapter reads thread-owned arrays after an intervening call.
+"""
+import numpy as np
+
+import fake_rio_gp
+from fake_rio_gp import AFF_INACTIVE, CAP_INF, EAGAIN, EINVAL, ERANGE, NONE, OK
+
+CFG_LIVE_FIRST_TOUCH, CFG_NO_HOST_SHADOW = 4, 8
+FLAG_REPLACED = 0x10
+
+FAULTS = (
+    "spill_wrong_node",            # a request whose first choice is full spills to another node than the solver says
+    "rebalance_key_order",         # rebalance lists its moves in key order, not row order
+    "rebalance_keeps_shadow",      # rebalance does not invalidate the host shadow
+    "feed_forgets_retired",        # a reclaimed row's old key is not deleted in the feed
+    "index_lists_reclaimed",       # objects_on_server names the key a reused row had before it was reclaimed
+    "kept_row_recycled",           # a row set aside by set_object_load is recycled
+    "update_batch_first_wins",     # update_batch applies duplicates in the wrong order
+    "reset_not_full",              # `full` is not raised after changes_reset
+)
+
+
+def _oracle():
+    import pyoracle
+    return pyoracle
+
+
+class LifeDense(fake_rio_gp.GpuPlacement):
+    """fake_rio_gp.GpuPlacement under RIO_GP_CFG_ROW_LIFECYCLE: the CRUD calls keep the affinity column (include/rio_gpu_placement.h)."""
+
+    def __init__(self, max_objects, max_nodes, spill_rounds, self_assign, fault=None):
+        super().__init__(max_objects, max_nodes, spill_rounds=spill_rounds, flags=fake_rio_gp.CFG_REF_SELF_ASSIGN if self_assign else 0)
+        self._op_fault = fault
+        self._aff[:] = AFF_INACTIVE
+        self._col[:] = NONE
+
+    def set_self_assign(self, on):
+        self._oflags = _oracle().REF_SELF_ASSIGN if on else 0
+
+    def update_batch(self, idx, node):
+        idx, node = np.asarray(idx, np.uint32), np.asarray(node, np.uint32)
+        super().update_batch(idx, node)
+        for i, nd in zip(idx, node):
+            self._aff[i] = AFF_INACTIVE if nd == NONE else nd
+
+    def remove_batch(self, idx):
+        super().remove_batch(idx)
+        self._aff[np.asarray(idx, np.uint32)] = AFF_INACTIVE
+
+    def clean_server(self, node):
+        hit = np.flatnonzero(self._col[:self._n] == np.uint32(node))
+        self._aff[hit] = AFF_INACTIVE
+        return super().clean_server(node)
+
+    def place_pending(self, idx, requester):
+        idx, requester = np.asarray(idx, np.uint32), np.asarray(requester, np.uint32)
+        col = self._col[:self._n]
+        before = col.copy()
+        node, flag = super().place_pending(idx, requester)
+        if self._op_fault == "spill_wrong_node":
+            live = np.flatnonzero(self._alive)
+            for k in range(len(idx)):
+                if flag[k] & 0xF == 3 and len(live) > 1:
+                    other = int(live[(int(np.searchsorted(live, node[k])) + 1) % len(live)])
+                    col[idx[k]] = other
+                    for q in range(len(idx)):
+                        if idx[q] == idx[k]:
+                            node[q] = other
+        dead = set()
+        seen = set()
+        for k in range(len(idx)):
+            c = before[idx[k]]
+            if c != NONE and c < self._m and not self._alive[c]:
+                dead.add(int(c))
+        if dead:
+            self._aff[:self._n][np.isin(before, list(dead))] = AFF_INACTIVE
+        for k in range(len(idx)):
+            i = int(idx[k])
+            if i in seen:
+                continue
+            seen.add(i)
+            c = before[i]
+            if c == NONE or int(c) in dead:
+                self._aff[i] = requester[k]
+        return node, flag
+
+    def get_objects(self):
+        return self._load[:self._n].copy(), self._aff[:self._n].copy()
+
+    def count_placed(self):
+        return int((self._col[:self._n] != NONE).sum())
+
+
+class _State:
+    pass
+
+
+class FakeObjectPlacement:
+    def __init__(self, max_objects, max_nodes=32, spill_rounds=2, flags=0, fault=None, _s=None):
+        if _s is not None:
+            self.s = _s
+            return
+        assert fault is None or fault in FAULTS, fault
+        s = self.s = _State()
+        s.fault = fault
+        s.max_objects, s.max_nodes = int(max_objects), int(max_nodes)
+        s.self_assign = not flags & CFG_LIVE_FIRST_TOUCH
+        s.shadow_on = not flags & CFG_NO_HOST_SHADOW
+        s.g = LifeDense(max_objects, max_nodes, spill_rounds or 2, s.self_assign, fault)
+        s.g.set_nodes(np.zeros(0, np.uint64), np.zeros(0, np.uint8), m=0)
+        s.g.set_num_objects(0)
+        s.rows, s.row_key, s.row_live, s.row_keep, s.free, s.stale_key = {}, [], [], [], [], []
+        s.nodes, s.addr, s.alive, s.cap, s.bad = {}, [], [], [], []
+        s.pushed = (0, 0)
+        s.shadow, s.clock, s.base, s.clean_stamp = {}, 1, 1, {}
+        s.feed_on, s.feed_full, s.retired = False, True, {}
+        s.trips = [0, 0]
+        s.last_len = 0
+
+    def clone(self):
+        return FakeObjectPlacement(0, _s=self.s)
+
+    def close(self):
+        pass
+
+    def dense(self):
+        return self.s.g
+
+    # ---- tables
+    @staticmethod
+    def _key(ty, oid):
+        return ty + "." + oid
+
+    def _sync(self):
+        s = self.s
+        if s.pushed != (len(s.addr), tuple(s.alive), tuple(s.cap)):
+            s.g.set_nodes(np.array(s.cap, np.uint64), np.array(s.alive, np.uint8), m=len(s.addr))
+            s.pushed = (len(s.addr), tuple(s.alive), tuple(s.cap))
+        if s.g.num_objects != len(s.row_key):
+            s.g.set_num_objects(len(s.row_key))
+
+    def _node(self, a, create, up=False):
+        s = self.s
+        if a in s.nodes:
+            return s.nodes[a]
+        if not create:
+            return NONE
+        if len(s.addr) >= s.max_nodes:
+            return EINVAL - 100
+        s.nodes[a] = len(s.addr)
+        s.addr.append(a)
+        s.alive.append(1 if up else 0)
+        s.cap.append(CAP_INF)
+        c = a.find(":")
+        s.bad.append(c < 0 or c == 0 or c + 1 >= len(a))
+        return s.nodes[a]
+
+    def _row(self, ty, oid, create, use=False):
+        """-> row, NONE (unknown, not created) or "full"."""
+        s = self.s
+        k = self._key(ty, oid)
+        if k in s.rows:
+            r = s.rows[k]
+            if use:
+                s.row_keep[r] = 0
+            return r
+        if not create:
+            return NONE
+        if s.free:
+            r = s.free.pop()
+        elif len(s.row_key) < s.max_objects:
+            r = len(s.row_key)
+            s.row_key.append(None)
+            s.row_live.append(0)
+            s.row_keep.append(0)
+            s.stale_key.append((ty, oid))
+        else:
+            return "full"
+        s.rows[k] = r
+        s.row_key[r] = (ty, oid)
+        s.row_live[r] = 1
+        s.row_keep[r] = 0 if use else 1
+        return r
+
+    def _reclaim(self):
+        s = self.s
+        self._sync()
+        col, (load, aff) = s.g.get_assign(), s.g.get_objects()
+        gone = []
+        for r in range(len(s.row_key)):
+            keep = s.row_keep[r] and s.fault != "kept_row_recycled"
+            if s.row_live[r] and not keep and col[r] == NONE and aff[r] == AFF_INACTIVE:
+                if s.feed_on and s.fault != "feed_forgets_retired":
+                    s.retired.setdefault(r, s.row_key[r])
+                del s.rows[self._key(*s.row_key[r])]
+                s.row_key[r], s.row_live[r], s.row_keep[r] = None, 0, 0
+                s.shadow.pop(r, None)
+                s.free.append(r)
+                gone.append(r)
+        if gone:
+            s.g.set_object_attrs(gone, load=np.ones(len(gone), np.uint32))
+        return bool(gone)
+
+    def _with_reclaim(self, body):
+        rc = body()
+        if rc == "full":
+            if not self._reclaim():
+                return EINVAL
+            rc = body()
+        return EINVAL if rc == "full" else rc
+
+    # ---- shadow
+    def _put(self, row, node):
+        if self.s.shadow_on:
+            self.s.shadow[int(row)] = (self.s.clock, int(node))
+
+    def _get(self, row):
+        s = self.s
+        e = s.shadow.get(int(row)) if s.shadow_on else None
+        if e is None or e[0] < s.base or (e[1] != NONE and e[0] < s.clean_stamp.get(e[1], 0)):
+            return None
+        return e[1]
+
+    def _invalidate(self):
+        self.s.clock += 1
+        self.s.base = self.s.clock
+
+    def invalidate_cache(self):
+        self._invalidate()
+        return OK
+
+    def device_round_trips(self):
+        return tuple(self.s.trips)
+
+    def _trip(self):
+        self.s.trips[0] += 1
+        self.s.trips[1] += 1
+
+    def _out(self, addr, cap):
+        self.s.last_len = len(addr.encode())
+        return (ERANGE, "") if cap < self.s.last_len + 1 else (OK, addr)
+
+    def last_address_len(self):
+        return self.s.last_len
+
+    # ---- the trait
+    def update(self, ty, oid, addr):
+        s = self.s
+        res = {}
+
+        def body():
+            if addr is None:
+                r = self._row(ty, oid, False, True)
+                res["v"] = None if r == NONE else (r, NONE)
+                return OK
+            r = self._row(ty, oid, True, True)
+            if r == "full":
+                return r
+            nd = self._node(addr, True)
+            if nd < 0:
+                return EINVAL
+            res["v"] = (r, nd)
+            return OK
+        rc = self._with_reclaim(body)
+        if rc or res.get("v") is None:
+            return rc
+        self._sync()
+        self._trip()
+        r, nd = res["v"]
+        s.g.update_batch([r], [nd])
+        self._put(r, nd)
+        return OK
+
+    def update_batch(self, keys, addrs):
+        s = self.s
+        out = {}
+
+        def body():
+            rows, nodes = [], []
+            for (ty, oid), a in zip(keys, addrs):
+                if a is None:
+                    r = self._row(ty, oid, False, True)
+                    if r == NONE:
+                        continue
+                    nd = NONE
+                else:
+                    r = self._row(ty, oid, True, True)
+                    if r == "full":
+                        return r
+                    nd = self._node(a, True)
+                    if nd < 0:
+                        return EINVAL
+                rows.append(r)
+                nodes.append(nd)
+            out["v"] = (rows, nodes)
+            return OK
+        rc = self._with_reclaim(body)
+        if rc:
+            return rc
+        self._sync()
+        rows, nodes = out["v"]
+        if rows:
+            if s.fault == "update_batch_first_wins":
+                rows, nodes = rows[::-1], nodes[::-1]
+            s.g.update_batch(rows, nodes)
+            for r, nd in zip(rows, nodes):
+                self._put(r, nd)
+        return OK
+
+    def remove(self, ty, oid):
+        r = self._row(ty, oid, False, True)
+        if r == NONE:
+            return OK
+        self._sync()
+        self._trip()
+        self.s.g.remove_batch([r])
+        self._put(r, NONE)
+        return OK
+
+    def clean_server(self, addr):
+        s = self.s
+        nd = s.nodes.get(addr)
+        if nd is None:
+            return OK
+        self._sync()
+        s.g.clean_server(nd)
+        s.clock += 1
+        s.clean_stamp[nd] = s.clock
+        return OK
+
+    def lookup(self, ty, oid, cap=512):
+        """-> (rc, found, address)"""
+        s = self.s
+        s.last_len = 0
+        r = self._row(ty, oid, False)
+        if r == NONE:
+            return OK, 0, ""
+        nd = self._get(r)
+        if nd is None:
+            self._sync()
+            self._trip()
+            nd = int(s.g.lookup_batch([r])[0])
+            self._put(r, nd)
+        if nd == NONE:
+            return OK, 0, ""
+        rc, a = self._out(s.addr[nd], cap)
+        return rc, 1, a
+
+    def try_lookup(self, ty, oid, cap=512):
+        s = self.s
+        s.last_len = 0
+        r = s.rows.get(self._key(ty, oid))
+        if r is None:
+            return OK, 0, ""
+        nd = self._get(r)
+        if nd is None:
+            return EAGAIN, 0, ""
+        if nd == NONE:
+            return OK, 0, ""
+        rc, a = self._out(s.addr[nd], cap)
+        return rc, 1, a
+
+    def _sticky(self, r, me):
+        s = self.s
+        nd = self._get(r)
+        if nd is None or nd == NONE or not s.alive[nd] or s.bad[nd]:
+            return None
+        return nd, (0 if nd == me else 1)
+
+    def try_get_or_create_placement(self, ty, oid, me, cap=512):
+        """-> (rc, address, flag)"""
+        s = self.s
+        s.last_len = 0
+        r = s.rows.get(self._key(ty, oid))
+        if r is None or s.row_keep[r] or me not in s.nodes:
+            return EAGAIN, "", 0
+        hit = self._sticky(r, s.nodes[me])
+        if hit is None:
+            return EAGAIN, "", 0
+        rc, a = self._out(s.addr[hit[0]], cap)
+        return rc, a, hit[1]
+
+    def _policy(self, rows, reqs):
+        s = self.s
+        if any(s.bad):
+            cur = s.g.lookup_batch(rows)
+            bad = [r for r, c in zip(rows, cur) if c != NONE and s.bad[c]]
+            if bad:
+                s.g.remove_batch(bad)
+        node, flag = s.g.place_pending(rows, reqs)
+        cleaned = any(int(f) & FLAG_REPLACED for f in flag)
+        if cleaned:
+            self._invalidate()
+        for r, nd in zip(rows, node):
+            if not cleaned or nd == NONE or s.alive[nd]:
+                self._put(r, nd)
+        return node, flag
+
+    def get_or_create_placement(self, ty, oid, me, cap=512):
+        """-> (rc, address, flag)"""
+        s = self.s
+        s.last_len = 0
+        res = {}
+
+        def body():
+            r = self._row(ty, oid, True, True)
+            if r == "full":
+                return r
+            nd = self._node(me, True, up=True)
+            if nd < 0:
+                return EINVAL
+            res["v"] = (r, nd)
+            return OK
+        rc = self._with_reclaim(body)
+        if rc:
+            return rc, "", 0
+        r, q = res["v"]
+        hit = self._sticky(r, q)
+        if hit is not None:
+            rc, a = self._out(s.addr[hit[0]], cap)
+            return rc, a, hit[1]
+        self._sync()
+        self._trip()
+        node, flag = self._policy([r], [q])
+        rc, a = self._out("" if node[0] == NONE else s.addr[node[0]], cap)
+        return rc, a, int(flag[0])
+
+    def get_or_create_placement_batch(self, keys, mes):
+        """-> (rc, node ids, flags)"""
+        out = {}
+
+        def body():
+            rows, reqs = [], []
+            for (ty, oid), me in zip(keys, mes):
+                r = self._row(ty, oid, True, True)
+                if r == "full":
+                    return r
+                nd = self._node(me, True, up=True)
+                if nd < 0:
+                    return EINVAL
+                rows.append(r)
+                reqs.append(nd)
+            out["v"] = (rows, reqs)
+            return OK
+        rc = self._with_reclaim(body)
+        if rc:
+            return rc, [], []
+        self._sync()
+        rows, reqs = out["v"]
+        if not rows:
+            return OK, [], []
+        node, flag = self._policy(rows, reqs)
+        return OK, [int(x) for x in node], [int(x) for x in flag]
+
+    def lookup_batch(self, keys):
+        s = self.s
+        rows = [self._row(ty, oid, False) for ty, oid in keys]
+        self._sync()
+        out = []
+        for r in rows:
+            if r == NONE:
+                out.append(NONE)
+            else:
+                nd = int(s.g.lookup_batch([r])[0])
+                self._put(r, nd)
+                out.append(nd)
+        return OK, out
+
+    def node_address(self, nid):
+        return self.s.addr[nid] if nid < len(self.s.addr) else None
+
+    def set_member(self, addr, active, capacity):
+        s = self.s
+        nd = self._node(addr, True)
+        if nd < 0:
+            return EINVAL
+        s.alive[nd] = 1 if active else 0
+        s.cap[nd] = int(capacity)
+        self._sync()
+        return OK
+
+    def set_object_load(self, ty, oid, load):
+        res = {}
+
+        def body():
+            r = self._row(ty, oid, True, False)
+            res["r"] = r
+            return r if r == "full" else OK
+        rc = self._with_reclaim(body)
+        if rc:
+            return rc
+        self._sync()
+        self.s.g.set_object_attrs([res["r"]], load=[load])
+        return OK
+
+    def len(self):
+        self._sync()
+        return OK, self.s.g.count_placed()
+
+    def tick(self):
+        s = self.s
+        self._sync()
+        s.g.set_self_assign(False)
+        st = s.g.tick()
+        s.g.set_self_assign(s.self_assign)
+        self._invalidate()
+        return OK, st
+
+    # ---- listings (mid: called between the call and the reading of its arrays)
+    def snapshot(self, mid=None):
+        s = self.s
+        self._sync()
+        col = s.g.get_assign()
+        out = [(s.row_key[r][0], s.row_key[r][1], s.addr[col[r]]) for r in range(len(col))
+               if s.row_live[r] and col[r] != NONE and col[r] < len(s.addr)]
+        if mid:
+            mid()
+        return OK, out
+
+    def objects_on_server(self, addr, mid=None):
+        s = self.s
+        self._sync()
+        out = []
+        if addr in s.nodes:
+            _, rows = s.g.rows_on_nodes([s.nodes[addr]])
+            names = s.stale_key if s.fault == "index_lists_reclaimed" else s.row_key
+            out = [names[r] for r in rows if s.row_live[r]]
+        if mid:
+            mid()
+        return OK, out
+
+    def rebalance(self, max_moves=None, mid=None):
+        s = self.s
+        self._sync()
+        cap = min(CAP_INF if max_moves is None else int(max_moves), len(s.row_key))
+        _, rows, frm, to = s.g.rebalance(None, cap, 0, moves_cap=cap)
+        if s.fault != "rebalance_keeps_shadow":
+            self._invalidate()
+        out = [(s.row_key[r][0], s.row_key[r][1], s.addr[f], s.addr[t]) for r, f, t in zip(rows, frm, to) if s.row_live[r]]
+        if s.fault == "rebalance_key_order":
+            out.sort()
+        if mid:
+            mid()
+        return OK, out
+
+    def changes(self, mid=None):
+        s = self.s
+        self._sync()
+        s.feed_on = True
+        rows, old, new, _ = s.g.changes(cap=None)
+        listed = {int(r): (int(o), int(n)) for r, o, n in zip(rows, old, new)}
+        for r in s.retired:
+            if r not in listed:
+                c = int(s.g.lookup_batch([r])[0])
+                listed[r] = (c, c)
+        dels, ups = [], []
+        A = lambda nd: s.addr[nd] if nd < len(s.addr) else None
+        for r in sorted(listed):
+            a0, a1 = A(listed[r][0]), A(listed[r][1])
+            if r in s.retired:
+                if a0:
+                    dels.append(s.retired[r] + (a0, None))
+                if a1 and s.row_live[r]:
+                    ups.append(s.row_key[r] + (None, a1))
+                continue
+            if not s.row_live[r]:
+                continue
+            if a1:
+                ups.append(s.row_key[r] + (a0, a1))
+            elif a0:
+                dels.append(s.row_key[r] + (a0, None))
+        s.retired = {}
+        full, s.feed_full = s.feed_full, False
+        if mid:
+            mid()
+        return OK, bool(full), dels + ups
+
+    def changes_reset(self):
+        s = self.s
+        s.g.changes_reset()
+        s.retired = {}
+        s.feed_full = s.fault != "reset_not_full"
+        return OK
+
+
+def module(fault=None):
+    """What the driver is given: make(max_objects, max_nodes, spill_rounds, flags) -> a provider."""
+    def make(max_objects, max_nodes=32, spill_rounds=2, flags=0):
+        return FakeObjectPlacement(max_objects, max_nodes, spill_rounds, flags, fault)
+    return make

@@ -7,9 +7,15 @@
 //   phase 3  object-id churn on a small table: removed keys must be reclaimed when the table runs full, a table full
 //            of LIVE objects must fail with its own error, and a failing request must not fail its batch-mates
 //   phase 4  tick: removed and never-inserted rows do not come back (phantom rows)
+//   phase 5  rio_op_rebalance, rio_op_changes / _reset and rio_op_objects_on_server beside the callers of phase 1: the calls
+//            that hold the device lock across a listing, take the write side of the table lock and hand out per-thread arrays
+//            — every array is read after other threads have made their calls
+//   phase 6  the same on a tiny table, so that keys are reclaimed while the feed is on: a mirror fed by rio_op_changes alone
+//            (every old address = what the mirror held) equals rio_op_snapshot at quiescence
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <string>
 #include <thread>
 #include <vector>
@@ -228,8 +234,167 @@ int main() {
     rio_op_release(p);
     const int bad4 = bad.load() - bad1 - bad2 - bad3;
 
+
+    // ---------------------------------------------------------------- phase 5: rebalance, feed and index beside the callers
+    p = make(4096, 16);
+    if (!p) return 1;
+    for (int j = 0; j < 4; ++j) rio_op_set_member(p, ("10.5.0." + std::to_string(j) + ":5000").c_str(), 1, j == 0 ? 40 : RIO_GP_CAP_INF);
+    std::atomic<int> running{0};
+    std::atomic<long> moves_seen{0}, listed_seen{0}, fulls{0};
+    std::atomic<long> calls_done{0};  // calls the caller threads have completed (let_others_run waits on it)
+    auto caller = [&](int tid, rio_op_t* base, int keys, int rounds, const char* self_prefix) {
+        rio_op_t* mine = rio_op_clone(base);
+        char out[64];
+        const std::string self = std::string(self_prefix) + std::to_string(tid % 4) + ":5000";
+        for (int k = 0; k < rounds; ++k) {
+            const std::string id = "k" + std::to_string(tid) + "_" + std::to_string(k % keys);
+            uint32_t flag = 0;
+            int found = 0;
+            if (rio_op_get_or_create_placement(mine, "P", id.c_str(), self.c_str(), out, sizeof out, &flag) != RIO_GP_OK || !out[0]) ++bad;
+            if (rio_op_lookup(mine, "P", id.c_str(), out, sizeof out, &found) != RIO_GP_OK) ++bad;
+            else if (found && strncmp(out, self_prefix, strlen(self_prefix)) != 0) ++bad;   // wherever a rebalance put it: a member
+            if (k % 3 == 0 && rio_op_remove(mine, "P", id.c_str()) != RIO_GP_OK) ++bad;
+            ++calls_done;
+        }
+        rio_op_release(mine);
+        --running;
+    };
+    // the arrays a call handed out are read only after other threads have completed calls of their own: until the callers' counter
+    // has moved on by four rounds (or no caller is left)
+    auto let_others_run = [&] {
+        const long c0 = calls_done.load();
+        while (running.load() > 0 && calls_done.load() < c0 + 4) std::this_thread::yield();
+    };
+    auto rebalancer = [&](rio_op_t* base, const char* self_prefix) {
+        rio_op_t* mine = rio_op_clone(base);
+        while (running.load() > 0) {
+            uint64_t n = 0;
+            const char *const *ty, *const *oid, *const *fa, *const *ta;
+            const size_t *tl, *il;
+            if (rio_op_rebalance(mine, 5, &n, &ty, &tl, &oid, &il, &fa, &ta) != RIO_GP_OK) { ++bad; continue; }
+            let_others_run();
+            if (n > 5) ++bad;
+            for (uint64_t q = 0; q < n; ++q) {
+                if (tl[q] != 1 || ty[q][0] != 'P' || il[q] < 3 || oid[q][0] != 'k') ++bad;
+                if (strncmp(fa[q], self_prefix, strlen(self_prefix)) != 0 || strncmp(ta[q], self_prefix, strlen(self_prefix)) != 0 || !strcmp(fa[q], ta[q])) ++bad;
+            }
+            moves_seen += (long)n;
+        }
+        rio_op_release(mine);
+    };
+    auto indexer = [&](rio_op_t* base, const char* self_prefix) {
+        rio_op_t* mine = rio_op_clone(base);
+        for (int k = 0; running.load() > 0; ++k) {
+            uint64_t n = 0;
+            const char *const *ty, *const *oid;
+            const size_t *tl, *il;
+            const std::string a = std::string(self_prefix) + std::to_string(k % 4) + ":5000";
+            if (rio_op_objects_on_server(mine, a.c_str(), &n, &ty, &tl, &oid, &il) != RIO_GP_OK) { ++bad; continue; }
+            let_others_run();
+            for (uint64_t q = 0; q < n; ++q)
+                if (tl[q] != 1 || ty[q][0] != 'P' || il[q] != strlen(oid[q]) || oid[q][0] != 'k') ++bad;
+            listed_seen += (long)n;
+            if (rio_op_objects_on_server(mine, "10.99.0.1:1", &n, &ty, &tl, &oid, &il) != RIO_GP_OK || n != 0) ++bad;  // never seen
+        }
+        rio_op_release(mine);
+    };
+    // the feed's one consumer: a mirror fed by the listings alone; `reset_every`: forget and expect a full listing
+    std::map<std::string, std::string> mirror;
+    auto feed_once = [&](rio_op_t* mine, bool expect_full) {
+        uint64_t n = 0;
+        int full = -1;
+        const char *const *ty, *const *oid, *const *oa, *const *na;
+        const size_t *tl, *il;
+        if (rio_op_changes(mine, &n, &full, &ty, &tl, &oid, &il, &oa, &na) != RIO_GP_OK) { ++bad; return; }
+        let_others_run();
+        if (full != (expect_full ? 1 : 0)) ++bad;
+        if (full) { mirror.clear(); ++fulls; }
+        bool upserts = false;
+        for (uint64_t q = 0; q < n; ++q) {
+            const std::string key = std::string(ty[q], tl[q]) + "." + std::string(oid[q], il[q]);
+            const auto it = mirror.find(key);
+            if (oa[q] ? (it == mirror.end() || it->second != oa[q]) : it != mirror.end()) ++bad;  // old address = what the mirror held
+            if (!na[q]) { if (upserts || full || !oa[q]) ++bad; mirror.erase(key); }              // deletes first, none in a full listing
+            else { upserts = true; mirror[key] = na[q]; }
+        }
+    };
+    auto feeder = [&](rio_op_t* base, int reset_every) {
+        rio_op_t* mine = rio_op_clone(base);
+        bool expect_full = true;
+        for (int k = 1; running.load() > 0; ++k) {
+            feed_once(mine, expect_full);
+            expect_full = false;
+            if (reset_every && k % reset_every == 0) {
+                if (rio_op_changes_reset(mine) != RIO_GP_OK) ++bad;
+                expect_full = true;
+            }
+        }
+        feed_once(mine, expect_full);  // at quiescence
+        rio_op_release(mine);
+    };
+    auto mirror_is_snapshot = [&](rio_op_t* h) {
+        uint64_t n = 0;
+        const char *const *ty, *const *oid, *const *ad;
+        if (rio_op_snapshot(h, &n, &ty, &oid, &ad) != RIO_GP_OK) { ++bad; return; }
+        if (n != mirror.size()) ++bad;
+        for (uint64_t q = 0; q < n; ++q) {
+            const auto it = mirror.find(std::string(ty[q]) + "." + oid[q]);
+            if (it == mirror.end() || it->second != ad[q]) ++bad;
+        }
+    };
+    {
+        running = 6;
+        std::vector<std::thread> th;
+        for (int t = 0; t < 6; ++t) th.emplace_back(caller, t, p, 150, 1500, "10.5.0.");
+        th.emplace_back(rebalancer, p, "10.5.0.");
+        th.emplace_back(indexer, p, "10.5.0.");
+        th.emplace_back(feeder, p, 3);
+        for (auto& t : th) t.join();
+        mirror_is_snapshot(p);
+    }
+    rio_op_release(p);
+    const int bad5 = bad.load() - bad1 - bad2 - bad3 - bad4;
+
+    // ---------------------------------------------------------------- phase 6: a tiny table: reclaim() while the feed is on
+    p = make(48, 8);
+    if (!p) return 1;
+    mirror.clear();
+    for (int j = 0; j < 4; ++j) rio_op_set_member(p, ("10.6.0." + std::to_string(j) + ":5000").c_str(), 1, RIO_GP_CAP_INF);
+    {
+        running = 4;
+        std::vector<std::thread> th;
+        // 4 threads x 300 distinct keys through 48 rows: each thread places a key and removes the one it placed eight rounds
+        // before, so it holds at most 9 placed keys (36 of the 48 rows in all) and the other 1 168 keys only fit because the
+        // rows of removed keys are reclaimed; 8 keys per thread stay placed at the end
+        for (int t = 0; t < 4; ++t)
+            th.emplace_back([&, t] {
+                rio_op_t* mine = rio_op_clone(p);
+                char out[64];
+                const std::string self = "10.6.0." + std::to_string(t) + ":5000";
+                for (int k = 0; k < 300; ++k) {
+                    const std::string id = "k" + std::to_string(t) + "_" + std::to_string(k);
+                    uint32_t flag = 0;
+                    if (rio_op_get_or_create_placement(mine, "P", id.c_str(), self.c_str(), out, sizeof out, &flag) != RIO_GP_OK || self != out) ++bad;
+                    if (k >= 8 && rio_op_remove(mine, "P", ("k" + std::to_string(t) + "_" + std::to_string(k - 8)).c_str()) != RIO_GP_OK) ++bad;
+                    ++calls_done;
+                }
+                rio_op_release(mine);
+                --running;
+            });
+        th.emplace_back(rebalancer, p, "10.6.0.");
+        th.emplace_back(indexer, p, "10.6.0.");
+        th.emplace_back(feeder, p, 0);
+        for (auto& t : th) t.join();
+        mirror_is_snapshot(p);
+        uint64_t len = 0;
+        if (rio_op_len(p, &len) != RIO_GP_OK || len != 4 * 8) ++bad;
+    }
+    rio_op_release(p);
+    const int bad6 = bad.load() - bad1 - bad2 - bad3 - bad4 - bad5;
+    if (fulls.load() < 2 || listed_seen.load() == 0) ++bad;  // (both feeds began with a full listing; the index listed something)
+
     if (try_hits.load() == 0) ++bad;  // (the shadow answered none of thousands of repeated lookups: the try calls are dead)
-    printf("wrong=%d (phase1 %d phase2 %d phase3 %d phase4 %d) nonok=%d placed=%llu try_hits=%ld\n", bad.load(), bad1, bad2, bad3, bad4,
-           nonok.load(), (unsigned long long)n, try_hits.load());
+    printf("wrong=%d (phase1 %d phase2 %d phase3 %d phase4 %d phase5 %d phase6 %d) nonok=%d placed=%llu try_hits=%ld moves=%ld listed=%ld\n", bad.load(),
+           bad1, bad2, bad3, bad4, bad5, bad6, nonok.load(), (unsigned long long)n, try_hits.load(), moves_seen.load(), listed_seen.load());
     return (bad.load() || nonok.load()) ? 2 : 0;
 }

@@ -1,0 +1,1018 @@
+"""The string layer (rio_op_*, include/rio_gpu_object_placement.h) fuzzed as what it is: a translation.  It decides nothing — it
+turns strings into rows and node ids, calls the dense layer and turns the answers back — so one random sequence of EVERY call
+is checked, after every call, against a translation model over the dense layer's own CPU references.
+
+What the driver keeps, none of it taken from the layer's internals:
+  addr -> node id   learnt through rio_op_node_address, checked to be a stable injection;
+  key  -> row       learnt from public listings only: rio_op_objects_on_server(a) zipped with rio_gp_rows_on_nodes of that node on
+                    the rio_op_dense handle (both in row order), or the one row whose load changed for rio_op_set_object_load.  A
+                    key whose row cannot be seen (it is not placed) is carried as "row unknown": unplaced, load 1.  The references
+                    that take requests in array order (place_pending, update_batch) give such keys rows past the table's end;
+  the documented lifetime of a key: created by update(Some) / a request / set_object_load, dropped — when the table runs full
+                    and only then — if it is unplaced with affinity RIO_GP_AFF_INACTIVE and not set aside by set_object_load;
+  the dense state before each call (column, load, affinity, capacity, liveness, used), read through rio_op_dense's getters,
+                    which tests/test_gpu_fuzz.py holds to the oracle.
+Per call the expected dense state comes from pyoracle / tests/rebalance_ref.py / tests/spec_rebalance.py / tests/spec_changes.py
+with translated arguments; the column and `used`, every answer, the index, the snapshot, the feed's mirror, the shadow's answers,
+what a clone sees and every refusal are compared bit for bit / string for string.  No tolerance anywhere.
+
+The provider under test is given as make(max_objects, max_nodes, spill_rounds, flags): RealProvider.make over rio_gp (the GPU
+test, tests/test_gpu_op_layer_fuzz.py) or tests/fake_rio_op.py (the driver's own test, tests/test_op_layer_driver.py).
+"""
+import ctypes as C
+
+import numpy as np
+
+import spec_changes
+
+NONE = 0xFFFFFFFF
+INF = 0xFFFFFFFFFFFFFFFF
+AFF_INACTIVE = 0xFFFFFFFE
+OK, EINVAL, EUPSTREAM, ENODEV, ENOMEM, ERANGE, EAGAIN = range(7)
+CFG_LIVE_FIRST_TOUCH, CFG_NO_HOST_SHADOW = 4, 8
+LOCAL, REDIRECT, PLACED, SPILLED, UNPLACED = range(5)
+REPLACED = 0x10
+
+FLOOR = (
+    "reclaim between two feed reads",
+    "rebalance moved keys of rows that had changed hands",
+    "tick evicted from a member turned inactive",
+    "spilled request",
+    "UNPLACED request",
+    "REPLACED request",
+    "try_* answered from the shadow",
+    "ERANGE",
+    "table-full EINVAL",
+    "request from an inactive requester under the default flags",
+)
+
+SIZES = ("tiny", "tiny", "edge", "tiny", "4096", "bulk")      # by seed % 6
+FLAGS = (0, CFG_LIVE_FIRST_TOUCH, CFG_NO_HOST_SHADOW)            # by (seed // 6) % 3: every size meets every flag in 18 seeds
+
+
+def config_of(seed):
+    """(size class, provider flags) of a seed: drawn independently of each other, the whole cross product every 18 seeds."""
+    return SIZES[seed % len(SIZES)], FLAGS[(seed // len(SIZES)) % 3]
+
+
+class RealProvider:
+    """rio_gp.GpuObjectPlacement seen as return codes and decoded listings.  `mid` is called between a listing call and the
+    reading of the arrays it handed out: they belong to the calling thread until its next call of the same function."""
+
+    def __init__(self, gp, p):
+        self.gp, self.p, self.L = gp, p, gp._oplib()
+
+    @classmethod
+    def make(cls, gp):
+        return lambda max_objects, max_nodes=32, spill_rounds=2, flags=0: cls(
+            gp, gp.GpuObjectPlacement(max_objects=max_objects, max_nodes=max_nodes, spill_rounds=spill_rounds, flags=flags))
+
+    def clone(self):
+        return RealProvider(self.gp, self.p.clone())
+
+    def close(self):
+        self.p.close()
+
+    def dense(self):
+        return self.p.dense()
+
+    def _rc(self, f, *a):
+        try:
+            return OK, f(*a)
+        except self.gp.ObjectPlacementError as e:
+            return e.rc, None
+
+    def update(self, ty, oid, addr):
+        return self._rc(self.p.update, ty, oid, addr)[0]
+
+    def update_batch(self, keys, addrs):
+        return self._rc(self.p.update_batch, keys, addrs)[0]
+
+    def remove(self, ty, oid):
+        return self._rc(self.p.remove, ty, oid)[0]
+
+    def clean_server(self, addr):
+        return self._rc(self.p.clean_server, addr)[0]
+
+    def last_address_len(self):
+        return int(self.L.rio_op_last_address_len(self.p._h))
+
+    def _lookup(self, fn, ty, oid, cap):
+        buf, found = C.create_string_buffer(b"\xAA" * max(cap, 1), max(cap, 1)), C.c_int(0)
+        t, i = ty.encode(), oid.encode()
+        rc = fn(self.p._h, t, len(t), i, len(i), buf, cap, C.byref(found))
+        # (out_cap 0: the layer may not touch `out` at all — there is nothing to read)
+        return rc, int(found.value), (buf.value.decode() if cap and rc in (OK, ERANGE) and found.value else "")
+
+    def lookup(self, ty, oid, cap=512):
+        return self._lookup(self.L.rio_op_lookup_n, ty, oid, cap)
+
+    def try_lookup(self, ty, oid, cap=512):
+        return self._lookup(self.L.rio_op_try_lookup_n, ty, oid, cap)
+
+    def _request(self, fn, ty, oid, me, cap):
+        buf, flag = C.create_string_buffer(b"\xAA" * max(cap, 1), max(cap, 1)), C.c_uint32(0)
+        t, i = ty.encode(), oid.encode()
+        rc = fn(self.p._h, t, len(t), i, len(i), me.encode(), buf, cap, C.byref(flag))
+        return rc, (buf.value.decode() if cap and rc in (OK, ERANGE) else ""), int(flag.value)
+
+    def get_or_create_placement(self, ty, oid, me, cap=512):
+        return self._request(self.L.rio_op_get_or_create_placement_n, ty, oid, me, cap)
+
+    def try_get_or_create_placement(self, ty, oid, me, cap=512):
+        return self._request(self.L.rio_op_try_get_or_create_placement_n, ty, oid, me, cap)
+
+    def _batch(self, fn, keys, *more):
+        gp = self.gp
+        tys, tyl, _t = gp._keys([k[0] for k in keys])
+        ids, idl, _i = gp._keys([k[1] for k in keys])
+        return fn(self.p._h, len(keys), tys, tyl, ids, idl, *more)
+
+    def get_or_create_placement_batch(self, keys, mes):
+        node, flag = np.empty(len(keys), np.uint32), np.empty(len(keys), np.uint32)
+        rc = self._batch(self.L.rio_op_get_or_create_placement_batch_n, keys, self.gp._cstrs(mes), self.gp._ptr(node), self.gp._ptr(flag))
+        return rc, [int(x) for x in node], [int(x) for x in flag]
+
+    def lookup_batch(self, keys):
+        out = np.empty(len(keys), np.uint32)
+        rc = self._batch(self.L.rio_op_lookup_batch_n, keys, self.gp._ptr(out))
+        return rc, [int(x) for x in out]
+
+    def node_address(self, nid):
+        return self.p.node_address(nid)
+
+    def set_member(self, addr, active, capacity):
+        return self._rc(self.p.set_member, addr, active, capacity)[0]
+
+    def set_object_load(self, ty, oid, load):
+        return self._rc(self.p.set_object_load, ty, oid, load)[0]
+
+    def len(self):
+        return self._rc(self.p.__len__)
+
+    def tick(self):
+        return self._rc(self.p.tick)
+
+    def invalidate_cache(self):
+        return self._rc(self.p.invalidate_cache)[0]
+
+    def device_round_trips(self):
+        return self.p.device_round_trips()
+
+    def changes_reset(self):
+        return self._rc(self.p.changes_reset)[0]
+
+    @staticmethod
+    def _strs(ptr, lens, n):
+        v = C.cast(ptr, C.POINTER(C.c_void_p))
+        return [C.string_at(v[k], lens[k]).decode() for k in range(n)]
+
+    def snapshot(self, mid=None):
+        n = C.c_uint64(0)
+        ty, oid, addr = (C.POINTER(C.c_char_p)() for _ in range(3))
+        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+        rc = self.L.rio_op_snapshot(self.p._h, C.byref(n), C.byref(ty), C.byref(oid), C.byref(addr))
+        if rc == OK:
+            rc = self.L.rio_op_snapshot_key_lengths(self.p._h, C.byref(tl), C.byref(il))
+        if rc:
+            return rc, []
+        if mid:
+            mid()
+        k = int(n.value)
+        return OK, list(zip(self._strs(ty, tl, k), self._strs(oid, il, k), [addr[q].decode() for q in range(k)]))
+
+    def objects_on_server(self, address, mid=None):
+        n = C.c_uint64(0)
+        ty, oid = C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)()
+        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+        rc = self.L.rio_op_objects_on_server(self.p._h, address.encode(), C.byref(n), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il))
+        if rc:
+            return rc, []
+        if mid:
+            mid()
+        k = int(n.value)
+        return OK, list(zip(self._strs(ty, tl, k), self._strs(oid, il, k)))
+
+    def rebalance(self, max_moves=None, mid=None):
+        n = C.c_uint64(0)
+        ty, oid, fa, ta = (C.POINTER(C.c_char_p)() for _ in range(4))
+        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+        rc = self.L.rio_op_rebalance(self.p._h, INF if max_moves is None else int(max_moves), C.byref(n), C.byref(ty), C.byref(tl),
+                                     C.byref(oid), C.byref(il), C.byref(fa), C.byref(ta))
+        if rc:
+            return rc, []
+        if mid:
+            mid()
+        k = int(n.value)
+        return OK, list(zip(self._strs(ty, tl, k), self._strs(oid, il, k), [fa[q].decode() for q in range(k)],
+                            [ta[q].decode() for q in range(k)]))
+
+    def changes(self, mid=None):
+        n, full = C.c_uint64(0), C.c_int(0)
+        ty, oid, oa, na = (C.POINTER(C.c_char_p)() for _ in range(4))
+        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+        rc = self.L.rio_op_changes(self.p._h, C.byref(n), C.byref(full), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il),
+                                   C.byref(oa), C.byref(na))
+        if rc:
+            return rc, False, []
+        if mid:
+            mid()
+        k = int(n.value)
+        dec = lambda v: None if v is None else v.decode()
+        return OK, bool(full.value), list(zip(self._strs(ty, tl, k), self._strs(oid, il, k), [dec(oa[q]) for q in range(k)],
+                                             [dec(na[q]) for q in range(k)]))
+
+
+class Key:
+    """One interned key as the documentation describes its life: (ty, oid) as first handed over, its row once a listing showed
+    it, whether it is set aside by set_object_load, and — while its row is unknown — whether a request has made it an object."""
+    __slots__ = ("ty", "oid", "row", "keep", "obj")
+
+    def __init__(self, ty, oid, keep):
+        self.ty, self.oid, self.row, self.keep, self.obj = ty, oid, None, keep, False
+
+
+class Scenario:
+    OPS = (("update", 8), ("update_none", 2), ("update_batch", 3), ("remove", 5), ("clean_server", 2), ("lookup", 6),
+           ("lookup_batch", 2), ("request", 10), ("request_batch", 4), ("try_lookup", 4), ("try_request", 4), ("set_member", 5),
+           ("set_object_load", 3), ("tick", 3), ("rebalance", 4), ("changes", 5), ("changes_reset", 1), ("invalidate_cache", 1),
+           ("objects_on_server", 2), ("snapshot", 2), ("len", 1))
+
+    def __init__(self, make, oracle, seed, steps=None):
+        self.oracle, self.seed = oracle, seed
+        rng = self.rng = np.random.default_rng(0x0B1A0000 + seed)
+        kind, self.flags = config_of(seed)
+        self.kind = kind
+        self.rows_max = {"tiny": int(rng.integers(8, 49)), "edge": int(rng.choice([255, 256, 257])), "4096": 4096,
+                         "bulk": 1 << 14}[kind]
+        self.sa = not self.flags & CFG_LIVE_FIRST_TOUCH
+        self.oflags = oracle.REF_SELF_ASSIGN if self.sa else 0
+        self.rounds = int(rng.choice([1, 2, 2, 3]))
+        self.max_nodes = 32
+        self.steps = steps if steps is not None else {"tiny": 160, "edge": 110, "4096": 70, "bulk": 40}[kind]
+        self.handles = [make(self.rows_max, self.max_nodes, self.rounds, self.flags)]
+        self.handles.append(self.handles[0].clone())
+        self.g = self.handles[0].dense()
+        nm = int(rng.integers(3, 9))
+        self.members = ["10.0.%d.%d:%d" % (seed % 200, k, 5000 + k) for k in range(nm)]
+        self.odd = ["nocolon", "a-host-name-that-is-much-longer-than-thirty-two-bytes.example.org:65535"]
+        self.crowd = ["10.9.0.%d:1" % k for k in range(40)] if seed % 5 == 3 else []     # more addresses than max_nodes holds
+        nk = {"tiny": 3 * self.rows_max, "edge": 400, "4096": 1500, "bulk": 3000}[kind]
+        self.pool = [("T%d" % (k % 3), str(k)) for k in range(nk)] + [("a.b", "c"), ("a", "b.c"), ("T0", ""), ("nul\0ty", "x"),
+                                                                     ("T1", "i\0d"), ("T1", "i")]
+        self.addr, self.aid, self.alive, self.cap = [], {}, [], []        # node table as documented: by id
+        self.keys, self.row2key = {}, {}                                  # "ty.oid" -> Key ; row -> "ty.oid"
+        self.handed = set()                                               # rows that have had more than one key
+        self.dropped_since_feed = {}                                      # "ty.oid" -> row (if known) of keys reclaimed since the last read
+        self.mirror, self.feed_state = {}, "first"                        # the feed's consumer
+        self.ref, self.ref_on = None, True                                # LocalObjectPlacement cross-check
+        self.inactive_since = set()                                       # members turned inactive that still hold objects
+        self.log, self.count, self.cov = [], {}, {k: 0 for k in FLOOR}
+        self.step = 0
+        self.checked = 0
+
+    # ---- small helpers ------------------------------------------------------------------------------------------------
+    def fail(self, what, *more):
+        raise AssertionError(("seed", self.seed, "step", self.step, what, "last ops", self.log[-6:]) + more)
+
+    def want(self, cond, what, *more):
+        self.checked += 1
+        if not cond:
+            self.fail(what, *more)
+
+    def hit(self, name, on=True):
+        if on:
+            self.cov[name] += 1
+
+    def h(self):
+        """The clone this call goes through, and the other one."""
+        k = int(self.rng.integers(2))
+        return self.handles[k], self.handles[1 - k]
+
+    def read(self):
+        g = self.g
+        n = g.num_objects
+        col = g.get_assign() if n else np.zeros(0, np.uint32)
+        load, aff = g.get_objects() if n else (np.zeros(0, np.uint32), np.zeros(0, np.uint32))
+        cap, alive, used = g.get_nodes() if g.num_nodes else (np.zeros(0, np.uint64), np.zeros(0, np.uint8), np.zeros(0, np.uint64))
+        return {"n": n, "col": col, "load": load, "aff": aff, "cap": cap, "alive": alive, "used": used, "m": g.num_nodes}
+
+    def kstr(self, key):
+        return key[0] + "." + key[1]
+
+    def pick_key(self, known=0.6):
+        rng = self.rng
+        if self.keys and rng.random() < known:
+            ks = list(self.keys.values())
+            k = ks[int(rng.integers(len(ks)))]
+            return (k.ty, k.oid)
+        return self.pool[int(rng.integers(len(self.pool)))]
+
+    def pick_addr(self, odd=0.1):
+        rng = self.rng
+        r = rng.random()
+        if r < odd:
+            return self.odd[int(rng.integers(2))]
+        if self.crowd and r < odd + 0.25:
+            return self.crowd[int(rng.integers(len(self.crowd)))]
+        return self.members[int(rng.integers(len(self.members)))]
+
+    def is_bad(self, a):
+        c = a.find(":")
+        return c < 0 or c == 0 or c + 1 >= len(a)
+
+    def model_snapshot(self, st):
+        """{(ty, oid): address} from the dense column and the row map."""
+        out = {}
+        for r in np.flatnonzero(st["col"] != NONE):
+            ks = self.row2key.get(int(r))
+            if ks is None:
+                self.fail("a placed row has no key in the model", int(r))
+            k = self.keys[ks]
+            nd = int(st["col"][r])
+            if nd < len(self.addr):
+                out[(k.ty, k.oid)] = self.addr[nd]
+        return out
+
+    def where(self, st, key):
+        """Address the model says `key` lives on (None: not placed)."""
+        k = self.keys.get(self.kstr(key))
+        if k is None or k.row is None:
+            return None
+        nd = int(st["col"][k.row])
+        return None if nd == NONE else self.addr[nd]
+
+    # ---- the documented lifetime of keys ------------------------------------------------------------------------------
+    def droppable(self, st, k):
+        if k.keep:
+            return False
+        if k.row is None:
+            return not k.obj
+        return st["col"][k.row] == NONE and st["aff"][k.row] == AFF_INACTIVE
+
+    def intern(self, st, wanted):
+        """`wanted`: [(key, create, use, address or None, requester)] in the call's order.  Runs the documented interning on
+        the model: keys are created, the table reclaims when it is full, a second failure is the refusal.  -> True, or False when
+        the call must answer EINVAL (table full of live keys, or a 33rd address); the model keeps what the call interned."""
+        for attempt in range(2):
+            full = False
+            for key, create, use, address, up in wanted:
+                ks = self.kstr(key)
+                k = self.keys.get(ks)
+                if k is None and create:
+                    if len(self.keys) >= self.rows_max:
+                        full = True
+                        break
+                    k = self.keys[ks] = Key(key[0], key[1], not use)
+                    self.created.append(ks)
+                if k is not None and use:
+                    k.keep = False
+                if address is not None and address not in self.aid and address not in self.pending_addr:
+                    if len(self.addr) + len(self.pending_addr) >= self.max_nodes:
+                        self.refused = "33rd address"
+                        return False
+                    self.pending_addr[address] = 1 if up else 0
+            if not full:
+                return True
+            gone = [ks for ks, k in self.keys.items() if self.droppable(st, k)]
+            if attempt or not gone:
+                self.refused = "table full"
+                return False
+            self.reclaims += 1
+            for ks in gone:
+                k = self.keys.pop(ks)
+                if k.row is not None:
+                    del self.row2key[k.row]
+                    self.reset_rows.add(k.row)
+                self.dropped_since_feed.setdefault(ks, k.row)
+            if self.feed_state == "open":
+                self.hit("reclaim between two feed reads")
+        return True
+
+    def learn_nodes(self, is_request):
+        """New ids handed out by the call: addresses in the order rio_op_node_address names them."""
+        h = self.handles[0]
+        while True:
+            a = h.node_address(len(self.addr))
+            if a is None:
+                break
+            self.want(a not in self.aid, "two node ids for one address", a)
+            self.want(a in self.pending_addr, "an address the call did not carry got an id", a)
+            self.aid[a] = len(self.addr)
+            self.addr.append(a)
+            self.alive.append(self.pending_addr.pop(a))
+            self.cap.append(INF)
+        for j in (0, len(self.addr) // 2, len(self.addr) - 1):
+            if 0 <= j < len(self.addr):
+                self.want(h.node_address(j) == self.addr[j], "a node id changed its address", j)
+        self.want(h.node_address(len(self.addr) + 3) is None, "an id nobody was given has an address")
+
+    def learn_rows(self, before, after, nodes=None):
+        """Listings of the nodes whose rows changed (or hold rows without a key): objects_on_server zipped with rows_on_nodes."""
+        col = after["col"]
+        if nodes is None:
+            nb = before["n"]
+            ch = np.flatnonzero(col[:nb] != before["col"])
+            cand = set(int(x) for x in col[ch]) | set(int(x) for x in col[nb:])
+            cand |= set(int(col[r]) for r in np.flatnonzero(col != NONE) if int(r) not in self.row2key)
+            nodes = sorted(j for j in cand if j != NONE and j < len(self.addr))
+        for j in nodes:
+            rc, objs = self.handles[int(self.rng.integers(2))].objects_on_server(self.addr[j])
+            self.want(rc == OK, "objects_on_server failed", rc)
+            _, rows = self.g.rows_on_nodes([j])
+            self.want(len(objs) == len(rows), "objects_on_server and rows_on_nodes differ in length", self.addr[j], len(objs), len(rows))
+            self.want(np.array_equal(rows, np.flatnonzero(col == j)), "rows_on_nodes differs from the column", j)
+            for (ty, oid), r in zip(objs, rows):
+                r = int(r)
+                ks = self.kstr((ty, oid))
+                k = self.keys.get(ks)
+                self.want(k is not None, "a listed key is not one the documented lifetime keeps", (ty, oid), r)
+                self.want((k.ty, k.oid) == (ty, oid), "a key is listed under another spelling than it was created with", (ty, oid))
+                if k.row is None:
+                    old = self.row2key.get(r)
+                    self.want(old is None, "a row changed key without a reclaim", r, old, ks)
+                    if r in self.ever_rows:
+                        self.handed.add(r)
+                    self.ever_rows.add(r)
+                    k.row = r
+                    self.row2key[r] = ks
+                else:
+                    self.want(k.row == r, "a key changed its row", ks, k.row, r)
+
+    # ---- one step: before -> call -> expected -> after ------------------------------------------------------------------
+    def virtual(self, st, klist):
+        """Row indices for the reference: the known row, or one past the table's end per key whose row is unknown (unplaced,
+        load 1).  -> (idx, col, load, extra keys in order)"""
+        extra, idx = [], []
+        for key in klist:
+            k = self.keys.get(self.kstr(key))
+            if k is not None and k.row is not None:
+                idx.append(k.row)
+            else:
+                ks = self.kstr(key)
+                if ks not in extra:
+                    extra.append(ks)
+                idx.append(st["n"] + extra.index(ks))
+        col = np.concatenate([st["col"], np.full(len(extra), NONE, np.uint32)])
+        load = np.concatenate([st["load"], np.ones(len(extra), np.uint32)])
+        return np.array(idx, np.uint32), col, load, extra
+
+    def node_arrays(self):
+        return np.array(self.cap, np.uint64), np.array(self.alive, np.uint8)
+
+    def settle(self, before, xcol, extra, what):
+        """After the call: new node ids, new rows, then the whole column and `used` against the reference's."""
+        after = self.read()
+        self.want(after["n"] >= before["n"] and after["n"] <= self.rows_max, "the row count shrank or overflowed", after["n"])
+        self.learn_rows(before, after)
+        exp = np.full(after["n"], NONE, np.uint32)
+        exp[:before["n"]] = xcol[:before["n"]]
+        for t, ks in enumerate(extra):
+            nd = xcol[before["n"] + t]
+            k = self.keys.get(ks)
+            if nd != NONE:
+                self.want(k is not None and k.row is not None, "a key the reference placed is in no listing", ks, int(nd))
+                self.want(exp[k.row] == NONE, "a new key was given a row that was placed", ks, k.row)
+                exp[k.row] = nd
+            if k is not None and k.row is None:
+                k.obj = self.extra_obj.get(ks, k.obj)
+        bad = np.flatnonzero(after["col"] != exp)
+        self.want(bad.size == 0, what + ": the dense column differs from the reference's", bad[:8], after["col"][bad[:8]], exp[bad[:8]])
+        self.check_nodes_and_load(before, after, what)
+        if self.reclaims:      # rows changed hands: no call answers a new key with what the shadow held for the row's old key
+            self.probe(after, [ks for ks in dict.fromkeys(self.created) if ks in self.keys][:4])
+        return after
+
+    def check_nodes_and_load(self, before, after, what):
+        m = after["m"]
+        self.want(m <= len(self.addr), "the dense layer holds more nodes than ids were handed out")
+        cap, alive = self.node_arrays()
+        self.want(np.array_equal(after["cap"], cap[:m]) and np.array_equal(after["alive"], alive[:m]),
+                  what + ": the node table differs from what set_member / the requests said", after["alive"], alive[:m])
+        used = self.oracle.recompute_used(after["col"], after["load"], m) if m else np.zeros(0, np.uint64)
+        self.want(np.array_equal(after["used"], used), what + ": `used` differs", after["used"], used)
+        nb = before["n"]
+        ch = [int(r) for r in np.flatnonzero(after["load"][:nb] != before["load"])]
+        for r in ch:
+            ok = (r in self.reset_rows and after["load"][r] == 1) or (self.load_row == r)
+            self.want(ok, what + ": the load of a row changed that was neither reclaimed nor named", r, int(before["load"][r]), int(after["load"][r]))
+        self.want((after["load"][nb:] == 1).all() or self.load_row is not None, what + ": a fresh row does not start with load 1")
+
+    def begin(self):
+        self.pending_addr, self.refused, self.reclaims, self.created = {}, None, 0, []
+        self.reset_rows, self.load_row, self.extra_obj = set(), None, {}
+        return self.read()
+
+    def refused_unchanged(self, before, rc, what):
+        self.want(rc == EINVAL, what + ": the refusal is not EINVAL", rc, self.refused)
+        self.learn_nodes(False)
+        self.pending_addr = {}
+        after = self.read()
+        self.want(np.array_equal(after["col"][:before["n"]], before["col"]) and (after["col"][before["n"]:] == NONE).all(),
+                  what + ": a refused call changed the column")
+        self.check_nodes_and_load(before, after, what)
+        if self.refused == "table full":
+            self.hit("table-full EINVAL")
+        return after
+
+    # ---- operations ---------------------------------------------------------------------------------------------------
+    def op_update(self, addr_none=False):
+        p, other = self.h()
+        key = self.pick_key(0.4)
+        a = None if addr_none else self.pick_addr()
+        st = self.begin()
+        ok = self.intern(st, [(key, a is not None, True, a, False)])
+        rc = p.update(key[0], key[1], a)
+        if not ok:
+            return self.refused_unchanged(st, rc, "update")
+        self.want(rc == OK, "update failed", rc)
+        self.learn_nodes(False)
+        idx, col, load, extra = self.virtual(st, [key])
+        if a is not None or self.kstr(key) in self.keys:
+            self.want(self.oracle.update_batch(col, len(self.addr), idx, [NONE if a is None else self.aid[a]]) == 0, "reference refused")
+        self.ref_key(key)
+        if self.ref_on:
+            self.ref[0].update(key[0], key[1], a)
+        return self.settle(st, col, extra, "update")
+
+    def ref_key(self, key):
+        """The restatement takes NUL-terminated keys: a key with a NUL byte in a writing call ends the cross-check."""
+        if "\0" in key[0] + key[1]:
+            self.ref_on = False
+
+    def op_update_none(self):
+        return self.op_update(True)
+
+    def op_update_batch(self, n=None):
+        p, other = self.h()
+        rng = self.rng
+        n = n or int(rng.choice([1, 2, 5, 40, 257]))
+        keys = [self.pick_key(0.3) for _ in range(n)]
+        if n > 1 and rng.random() < 0.7:          # duplicates: the last writer of a key wins
+            for _ in range(max(1, n // 4)):
+                keys[int(rng.integers(n))] = keys[int(rng.integers(n))]
+        addrs = [None if rng.random() < 0.1 else self.pick_addr(0.03) for _ in range(n)]
+        st = self.begin()
+        ok = self.intern(st, [(k, a is not None, True, a, False) for k, a in zip(keys, addrs)])
+        rc = p.update_batch(keys, addrs)
+        if not ok:
+            return self.refused_unchanged(st, rc, "update_batch")
+        self.want(rc == OK, "update_batch failed", rc)
+        self.learn_nodes(False)
+        sel = [q for q in range(n) if addrs[q] is not None or self.kstr(keys[q]) in self.keys]
+        idx, col, load, extra = self.virtual(st, [keys[q] for q in sel])
+        nodes = [NONE if addrs[q] is None else self.aid[addrs[q]] for q in sel]
+        if sel:
+            self.want(self.oracle.update_batch(col, len(self.addr), idx, nodes) == 0, "reference refused")
+        for k in keys:
+            self.ref_key(k)
+        if self.ref_on:
+            for k, a in zip(keys, addrs):
+                self.ref[0].update(k[0], k[1], a)
+        return self.settle(st, col, extra, "update_batch")
+
+    def op_remove(self):
+        p, other = self.h()
+        key = self.pick_key(0.8)
+        st = self.begin()
+        self.intern(st, [(key, False, True, None, False)])
+        rc = p.remove(key[0], key[1])
+        self.want(rc == OK, "remove failed", rc)
+        idx, col, load, extra = self.virtual(st, [key])
+        k = self.keys.get(self.kstr(key))
+        if k is not None:
+            self.oracle.remove_batch(col, idx)
+            if k.row is None:
+                self.extra_obj[self.kstr(key)] = False
+        self.ref_key(key)
+        if self.ref_on:
+            self.ref[0].remove(key[0], key[1])
+        return self.settle(st, col, extra, "remove")
+
+    def op_clean_server(self):
+        p, other = self.h()
+        a = self.pick_addr() if self.rng.random() < 0.9 else "10.200.0.1:9"     # sometimes an address nobody has seen
+        st = self.begin()
+        rc = p.clean_server(a)
+        self.want(rc == OK, "clean_server failed", rc)
+        col = st["col"].copy()
+        if a in self.aid:
+            self.oracle.clean_servers(col, len(self.addr), [self.aid[a]])
+        if self.ref_on:
+            self.ref[0].clean_server(a)
+        after = self.settle(st, col, [], "clean_server")
+        self.probe(after, [self.row2key[int(r)] for r in np.flatnonzero(st["col"] == self.aid.get(a, NONE - 1))[:3] if int(r) in self.row2key])
+        return after
+
+    def check_lookup(self, st, p, other, key, fn, what):
+        want = self.where(st, key)
+        cap = 512 if self.rng.random() < 0.8 or want is None else int(self.rng.integers(0, len(want) + 1))
+        rc, found, out = fn(key[0], key[1], cap)
+        if what == "try_lookup" and rc == EAGAIN:
+            return False
+        _, cnt = other.len()                                    # a call on the other clone, then the length this thread was left
+        ln = p.last_address_len()
+        self.want(cnt == int((st["col"] != NONE).sum()), "len differs from the placed rows", cnt)
+        if want is None:
+            self.want(rc == OK and not found and ln == 0, what + ": a key that is not placed was found", rc, found, out, key)
+        elif cap < len(want.encode()) + 1:
+            self.want(rc == ERANGE and found and out == "" and ln == len(want.encode()), what + ": ERANGE form", rc, found, out, ln, want)
+            self.hit("ERANGE")
+        else:
+            self.want(rc == OK and found and out == want and ln == len(want.encode()), what + ": wrong address", rc, found, out, want, key)
+        if self.ref_on and "\0" not in key[0] + key[1]:
+            self.want(self.ref[0].lookup(key[0], key[1]) == want, "the reference restatement disagrees with the model", key, want)
+        return True
+
+    def op_lookup(self):
+        p, other = self.h()
+        st = self.begin()
+        self.check_lookup(st, p, other, self.pick_key(0.8), p.lookup, "lookup")
+        self.unchanged(st, "lookup")
+
+    def op_try_lookup(self):
+        p, other = self.h()
+        st = self.begin()
+        key = self.pick_key(0.9)
+        if self.rng.random() < 0.5:
+            p.lookup(key[0], key[1])                            # (what fills the shadow)
+        t0 = p.device_round_trips()
+        if self.check_lookup(st, p, other, key, p.try_lookup, "try_lookup"):
+            self.want(p.device_round_trips() == t0, "try_lookup went to the device")
+            self.want(not self.flags & CFG_NO_HOST_SHADOW or self.kstr(key) not in self.keys, "the shadow answered although it is off")
+            self.hit("try_* answered from the shadow", self.kstr(key) in self.keys)
+        self.unchanged(st, "try_lookup")
+
+    def unchanged(self, st, what):
+        after = self.read()
+        n = st["n"]     # (rows a refused call interned reach the device with the next call: unplaced rows past the old end)
+        self.want(after["n"] >= n and np.array_equal(after["col"][:n], st["col"]) and (after["col"][n:] == NONE).all() and
+                  np.array_equal(after["used"][:st["m"]], st["used"]) and not after["used"][st["m"]:].any(), what + " changed the table")
+
+    def op_lookup_batch(self):
+        p, other = self.h()
+        st = self.begin()
+        keys = [self.pick_key(0.7) for _ in range(int(self.rng.choice([1, 3, 50, 300])))]
+        rc, ids = p.lookup_batch(keys)
+        self.want(rc == OK, "lookup_batch failed", rc)
+        want = [self.where(st, k) for k in keys]
+        got = [None if v == NONE else self.addr[v] for v in ids]
+        self.want(got == want, "lookup_batch: wrong node ids", [(k, g, w) for k, g, w in zip(keys, got, want) if g != w][:4])
+        self.unchanged(st, "lookup_batch")
+
+    def expect_requests(self, st, keys, mes):
+        """The policy for requests in array order, on the state before: the malformed-record rule, then place_pending."""
+        idx, col, load, extra = self.virtual(st, keys)
+        cap, alive = self.node_arrays()
+        m = len(self.addr)
+        if any(self.is_bad(a) for a in self.addr):
+            bad = [int(i) for i in idx if col[i] != NONE and self.is_bad(self.addr[col[i]])]
+            if bad:
+                self.oracle.remove_batch(col, bad)
+        used = self.oracle.recompute_used(col, load, m)
+        req = np.array([self.aid[a] for a in mes], np.uint32)
+        node, flag = self.oracle.place_pending(col, load, cap, alive, used, idx, req, self.rounds, self.oflags)
+        for q, ks in enumerate(extra):
+            self.extra_obj[ks] = True
+        return col, extra, node, flag
+
+    def note_flags(self, flags, mes):
+        for f, me in zip(flags, mes):
+            self.hit("spilled request", f & 0xF == SPILLED)
+            self.hit("UNPLACED request", f & 0xF == UNPLACED)
+            self.hit("REPLACED request", f & REPLACED)
+            self.hit("request from an inactive requester under the default flags", self.sa and not self.alive[self.aid[me]])
+
+    def op_request(self):
+        p, other = self.h()
+        key, me = self.pick_key(0.6), self.pick_addr(0.05)
+        st = self.begin()
+        ok = self.intern(st, [(key, True, True, me, True)])
+        cap = 512 if self.rng.random() < 0.85 else 8
+        rc, out, flag = p.get_or_create_placement(key[0], key[1], me, cap)
+        if not ok:
+            return self.refused_unchanged(st, rc, "request")
+        self.learn_nodes(True)
+        col, extra, node, wflag = self.expect_requests(st, [key], [me])
+        want = "" if node[0] == NONE else self.addr[node[0]]
+        _, cnt = other.len()
+        ln = p.last_address_len()
+        if cap < len(want.encode()) + 1:
+            self.want(rc == ERANGE and out == "", "request: ERANGE form", rc, out, want)
+            self.hit("ERANGE")
+        else:
+            self.want(rc == OK and out == want, "request: wrong address", rc, out, want, key, me)
+        self.want(ln == len(want.encode()), "request: last_address_len", ln, want)
+        self.want(flag == int(wflag[0]), "request: wrong flag", flag, int(wflag[0]), key, me)
+        self.note_flags([flag], [me])
+        if self.ref_on:
+            self.cross_request(key, me, want, flag)
+        return self.settle(st, col, extra, "request")
+
+    def cross_request(self, key, me, want, flag):
+        """The restated get_or_create_placement of the reference, while nothing it lacks is in play."""
+        if "\0" in key[0] + key[1] or self.is_bad(me) or (not self.sa and not self.alive[self.aid[me]]):
+            self.ref_on = False
+            return
+        ip, port = me.rsplit(":", 1)
+        if me not in self.ref[2]:
+            self.ref[1].push(ip, port, bool(self.alive[self.aid[me]]))
+            self.ref[2].add(me)
+        got = self.oracle.get_or_create_placement(self.ref[0], self.ref[1], me, key[0], key[1])
+        self.want(got == want, "the reference restatement places the object elsewhere", key, me, got, want)
+
+    def op_request_batch(self):
+        p, other = self.h()
+        rng = self.rng
+        n = int(rng.choice([2, 3, 7, 40, 256, 257]))
+        keys = [self.pick_key(0.5) for _ in range(n)]
+        for _ in range(n // 5):
+            keys[int(rng.integers(n))] = keys[int(rng.integers(n))]
+        mes = [self.pick_addr(0.02) for _ in range(n)]
+        st = self.begin()
+        ok = self.intern(st, [(k, True, True, me, True) for k, me in zip(keys, mes)])
+        rc, ids, flags = p.get_or_create_placement_batch(keys, mes)
+        if not ok:
+            return self.refused_unchanged(st, rc, "request_batch")
+        self.want(rc == OK, "request_batch failed", rc)
+        self.learn_nodes(True)
+        col, extra, node, wflag = self.expect_requests(st, keys, mes)
+        self.want(ids == [int(x) for x in node], "request_batch: wrong node ids", [(q, ids[q], int(node[q])) for q in range(n) if ids[q] != node[q]][:4])
+        self.want(flags == [int(x) for x in wflag], "request_batch: wrong flags", [(q, flags[q], int(wflag[q])) for q in range(n) if flags[q] != wflag[q]][:4])
+        self.note_flags(flags, mes)
+        self.ref_on = False            # (a batch cleans first and places then: not the reference's order request by request)
+        return self.settle(st, col, extra, "request_batch")
+
+    def op_try_request(self):
+        p, other = self.h()
+        key, me = self.pick_key(0.95), self.pick_addr(0.0)
+        st = self.begin()
+        if self.rng.random() < 0.5:
+            p.lookup(key[0], key[1])
+        t0 = p.device_round_trips()
+        rc, out, flag = p.try_get_or_create_placement(key[0], key[1], me, 512)
+        if rc != EAGAIN:
+            want = self.where(st, key)
+            self.want(rc == OK and want is not None and out == want, "try_request: wrong address", rc, out, want)
+            self.want(self.alive[self.aid[want]] and not self.is_bad(want), "try_request answered for a server that is not an active member")
+            self.want(flag == (LOCAL if want == me else REDIRECT), "try_request: wrong flag", flag)
+            self.want(p.device_round_trips() == t0, "try_request went to the device")
+            self.want(not self.flags & CFG_NO_HOST_SHADOW, "the shadow answered although it is off")
+            self.hit("try_* answered from the shadow")
+        self.unchanged(st, "try_request")
+
+    def op_set_member(self):
+        p, other = self.h()
+        rng = self.rng
+        a = self.pick_addr(0.08)
+        active = bool(rng.random() < 0.65)
+        st = self.begin()
+        total = int(st["load"][st["col"] != NONE].sum()) if st["n"] else 0
+        capv = [INF, INF, max(1, total // max(1, len(self.members))), int(rng.integers(1, 6)), 0][int(rng.integers(5))]
+        ok = self.intern(st, [(("", ""), False, False, a, False)])
+        rc = p.set_member(a, active, capv)
+        if not ok:
+            return self.refused_unchanged(st, rc, "set_member")
+        self.want(rc == OK, "set_member failed", rc)
+        self.learn_nodes(False)
+        j = self.aid[a]
+        if self.alive[j] and not active and (st["col"] == j).any():
+            self.inactive_since.add(j)
+        self.alive[j], self.cap[j] = int(active), capv
+        if capv != INF:
+            self.ref_on = False
+        elif self.ref_on and not self.is_bad(a):
+            ip, port = a.rsplit(":", 1)
+            (self.ref[1].set_is_active if a in self.ref[2] else self.ref[1].push)(ip, port, active)
+            self.ref[2].add(a)
+        return self.settle(st, st["col"].copy(), [], "set_member")
+
+    def op_set_object_load(self):
+        p, other = self.h()
+        rng = self.rng
+        ahead = rng.random() < 0.5
+        key = self.pick_key(0.1 if ahead else 0.95)
+        load = int(rng.choice([0, 2, 3, 5, 9])) if self.kstr(key) not in self.keys or self.keys[self.kstr(key)].row is None \
+            else int(rng.choice([0, 1, 2, 3, 5, 9]))
+        st = self.begin()
+        ok = self.intern(st, [(key, True, False, None, False)])
+        rc = p.set_object_load(key[0], key[1], load)
+        if not ok:
+            return self.refused_unchanged(st, rc, "set_object_load")
+        self.want(rc == OK, "set_object_load failed", rc)
+        self.ref_on = False
+        k = self.keys[self.kstr(key)]
+        after = self.read()
+        if k.row is None:      # the one row whose load is now `load` and was not: that is the key's row
+            nb = st["n"]
+            was = np.concatenate([st["load"], np.ones(after["n"] - nb, np.uint32)])
+            ch = [int(r) for r in np.flatnonzero((after["load"] != was) & (after["load"] == load))]
+            self.want(len(ch) == 1, "set_object_load changed not exactly one row's load", ch)
+            self.want(ch[0] not in self.row2key, "set_object_load of a new key wrote the row of another key", ch[0])
+            if ch[0] in self.ever_rows:
+                self.handed.add(ch[0])
+            self.ever_rows.add(ch[0])
+            k.row = ch[0]
+            self.row2key[k.row] = self.kstr(key)
+        self.load_row = k.row
+        self.want(after["load"][k.row] == load, "set_object_load: the load is not on the key's row", k.row)
+        return self.settle(st, st["col"].copy(), [], "set_object_load")
+
+    def op_tick(self):
+        p, other = self.h()
+        st = self.begin()
+        rc, stats = p.tick()
+        self.want(rc == OK, "tick failed", rc)
+        self.ref_on = False
+        cap, alive = self.node_arrays()
+        if st["n"] and len(self.addr):
+            nxt, used, ost = self.oracle.tick(st["col"], st["load"], st["aff"], cap, alive, self.rounds, 0)
+            self.want(stats == ost, "tick: the counters differ", stats, ost)
+        else:
+            nxt = st["col"].copy()
+        moved = [int(r) for r in np.flatnonzero(nxt != st["col"])]
+        for j in list(self.inactive_since):
+            if any(st["col"][r] == j for r in moved):
+                self.hit("tick evicted from a member turned inactive")
+        self.inactive_since = set()
+        after = self.settle(st, nxt, [], "tick")
+        self.probe(after, [self.row2key[r] for r in moved[:4] if r in self.row2key])
+        return after
+
+    def probe(self, st, kss):
+        """Right after a call that moved rows the layer cannot name one by one: no call answers a moved key with its old address."""
+        for ks in kss:
+            k = self.keys.get(ks)
+            if k is None:
+                continue
+            key = (k.ty, k.oid)
+            for p in self.handles:
+                self.check_lookup(st, p, self.handles[0], key, p.try_lookup, "try_lookup")
+                self.check_lookup(st, p, self.handles[0], key, p.lookup, "lookup")
+
+    def op_rebalance(self):
+        import rebalance_ref
+        p, other = self.h()
+        rng = self.rng
+        st = self.begin()
+        for ks in list(self.keys)[:6]:           # (the shadow holds answers a rebalance must void)
+            p.lookup(self.keys[ks].ty, self.keys[ks].oid)
+        mm = (None, 0, 1, int(rng.integers(2, 6)), int(rng.integers(2, 40)))[int(rng.integers(5))]
+        rc, moves = p.rebalance(mm, mid=lambda: other.len())
+        self.want(rc == OK, "rebalance failed", rc)
+        self.ref_on = False
+        cap, alive = self.node_arrays()
+        budget = min(INF if mm is None else mm, st["n"])
+        if st["n"] and len(self.addr):
+            nxt, used, wst, rows, frm, to = rebalance_ref.rebalance(st["col"], st["load"], st["aff"], cap, alive, None, budget, self.rounds)
+            if st["n"] <= 4096:
+                import spec_rebalance
+                L = lambda a: [int(x) for x in a]
+                s_nxt, _, _, s_moves = spec_rebalance.rebalance(L(st["col"]), L(st["load"]), L(st["aff"]), L(cap), L(alive), None, budget, self.rounds)
+                self.want(s_nxt == L(nxt) and s_moves == [(int(r), int(f), int(t)) for r, f, t in zip(rows, frm, to)], "the two rebalance references differ")
+        else:
+            nxt, rows, frm, to = st["col"].copy(), [], [], []
+        want = []
+        for r, f, t in zip(rows, frm, to):
+            k = self.keys[self.row2key[int(r)]]
+            want.append((k.ty, k.oid, self.addr[f], self.addr[t]))
+            self.hit("rebalance moved keys of rows that had changed hands", int(r) in self.handed)
+        self.want(moves == want, "rebalance: the moves are not the reference's, key for key in row order", moves[:4], want[:4])
+        after = self.settle(st, nxt, [], "rebalance")
+        self.probe(after, [self.row2key[int(r)] for r in rows[:4]])
+        return after
+
+    def op_changes(self):
+        p, other = self.h()
+        st = self.begin()
+        rc, full, entries = p.changes(mid=lambda: other.lookup("T0", "0"))
+        self.want(rc == OK, "changes failed", rc)
+        self.want(full == (self.feed_state != "open"), "changes: `full` is 1 exactly on the first read and the first after a reset", full, self.feed_state)
+        try:
+            self.mirror = spec_changes.apply(self.mirror, full, entries, strict=True)
+        except AssertionError as e:
+            self.fail("changes: the listing does not apply to the mirror", e.args)
+        snap = self.model_snapshot(st)
+        self.want(self.mirror == snap, "changes: the mirror differs from the snapshot",
+                  sorted(set(self.mirror.items()) ^ set(snap.items()), key=repr)[:6])
+        # deletes first (apply checked it), each group in row order: by the rows the model knows
+        for group in ([e for e in entries if e[3] is None], [e for e in entries if e[3] is not None]):
+            rows = []
+            for ty, oid, old, new in group:
+                ks = self.kstr((ty, oid))
+                r = self.keys[ks].row if ks in self.keys and new is not None else self.dropped_since_feed.get(ks, self.keys[ks].row if ks in self.keys else None)
+                if r is not None:
+                    rows.append(r)
+            self.want(rows == sorted(rows), "changes: a group is not in row order", rows[:12])
+        self.dropped_since_feed = {}
+        self.feed_state = "open"
+        self.unchanged(st, "changes")
+
+    def op_changes_reset(self):
+        p, other = self.h()
+        self.want(p.changes_reset() == OK, "changes_reset failed")
+        self.feed_state = "reset"
+        self.dropped_since_feed = {}
+
+    def op_invalidate_cache(self):
+        p, other = self.h()
+        st = self.begin()
+        self.want(p.invalidate_cache() == OK, "invalidate_cache failed")
+        key = self.pick_key(1.0)
+        rc, _, _ = p.try_lookup(key[0], key[1], 512)
+        self.want(rc == EAGAIN or self.kstr(key) not in self.keys, "try_lookup answered right after invalidate_cache", rc)
+        self.unchanged(st, "invalidate_cache")
+
+    def op_objects_on_server(self, st=None):
+        """The index for every known address, one address that is not a member, and one never seen."""
+        p, other = self.h()
+        st = st or self.begin()
+        for a in list(self.addr) + ["10.250.0.1:1"]:
+            rc, objs = p.objects_on_server(a, mid=lambda: other.len())
+            self.want(rc == OK, "objects_on_server failed", rc)
+            j = self.aid.get(a, NONE - 1)
+            want = []
+            for r in np.flatnonzero(st["col"] == j):
+                k = self.keys[self.row2key[int(r)]]
+                want.append((k.ty, k.oid))
+            self.want(objs == want, "objects_on_server differs from the model", a, objs[:4], want[:4])
+
+    def op_snapshot(self, st=None):
+        p, other = self.h()
+        st = st or self.begin()
+        rc, snap = p.snapshot(mid=lambda: other.len())
+        self.want(rc == OK, "snapshot failed", rc)
+        want = self.model_snapshot(st)
+        self.want(len(snap) == len(want) and {(a, b): c for a, b, c in snap} == want, "snapshot differs from the model",
+                  sorted(set((a, b, c) for a, b, c in snap) ^ spec_changes.as_set(want), key=repr)[:6])
+
+    def op_len(self):
+        p, other = self.h()
+        st = self.begin()
+        rc, n = p.len()
+        self.want(rc == OK and n == int((st["col"] != NONE).sum()), "len differs from the placed rows", rc, n)
+        if self.ref_on:
+            self.want(n == len(self.ref[0]), "len differs from the reference restatement's", n, len(self.ref[0]))
+
+    # ---- the run ------------------------------------------------------------------------------------------------------
+    def setup(self):
+        rng = self.rng
+        self.ever_rows = set()
+        self.ref = (self.oracle.LocalObjectPlacement(), self.oracle.LocalStorage(), set())
+        self.begin()
+        caps = int(rng.integers(3))      # 0: unbounded for a while (the reference cross-check), 1: tight from the start, 2: mixed
+        for a in self.members:
+            self.log.append("set_member")
+            st = self.begin()
+            self.intern(st, [(("", ""), False, False, a, False)])
+            capv = INF if caps == 0 else int(rng.integers(1, 5)) if caps == 1 else [INF, 3, 0][int(rng.integers(3))]
+            self.want(self.handles[0].set_member(a, True, capv) == OK, "set_member failed")
+            self.learn_nodes(False)
+            self.alive[self.aid[a]], self.cap[self.aid[a]] = 1, capv
+            ip, port = a.rsplit(":", 1)
+            self.ref[1].push(ip, port, True)
+            self.ref[2].add(a)
+            if capv != INF:
+                self.ref_on = False
+            self.settle(st, st["col"].copy(), [], "set_member")
+        if self.kind == "bulk":          # the table loaded in one update_batch, as a snapshot is
+            n = self.rows_max - 200
+            keys = [("B", str(k)) for k in range(n)]
+            addrs = [self.members[k % len(self.members)] for k in range(n)]
+            self.log.append("update_batch (bulk)")
+            st = self.begin()
+            self.intern(st, [(k, True, True, a, False) for k, a in zip(keys, addrs)])
+            self.want(self.handles[0].update_batch(keys, addrs) == OK, "bulk update_batch failed")
+            idx, col, load, extra = self.virtual(st, keys)
+            self.oracle.update_batch(col, len(self.addr), idx, [self.aid[a] for a in addrs])
+            for k, a in zip(keys, addrs):
+                self.ref[0].update(k[0], k[1], a)
+            self.settle(st, col, extra, "update_batch (bulk)")
+
+    def run(self):
+        names = [a for a, w in self.OPS for _ in range(w)]
+        try:
+            self.setup()
+            for self.step in range(self.steps):
+                op = names[int(self.rng.integers(len(names)))]
+                self.log.append(op)
+                self.count[op] = self.count.get(op, 0) + 1
+                getattr(self, "op_" + op)()
+                if self.kind == "tiny" or self.step % 8 == 7:
+                    st = self.read()
+                    self.op_objects_on_server(st)
+                    self.op_snapshot(st)
+            st = self.read()
+            self.op_objects_on_server(st)
+            self.op_snapshot(st)
+            self.op_changes()
+        finally:
+            for h in self.handles[::-1]:
+                h.close()
+        return self.steps
+
+
+def run_seed(make, oracle, seed, steps=None):
+    sc = Scenario(make, oracle, seed, steps)
+    sc.run()
+    return sc

@@ -6,6 +6,8 @@
 // RIO_GP_CFG_REF_SELF_ASSIGN, whatever membership says).  Like the real library it VALIDATES every index against the row count
 // and the node table it was given (RIO_GP_EINVAL, nothing mutated) — which is what exposes an id that reaches the
 // "device" ahead of the table entry it refers to — and it keeps the row-lifecycle column (RIO_GP_CFG_ROW_LIFECYCLE).
+#ifndef STUB_RIO_GP_CPP  // (stub_rio_gp_all.cpp includes the stubs that each include this file: once is enough)
+#define STUB_RIO_GP_CPP
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -205,3 +207,4 @@ int rio_gp_tick(rio_gp_t* h, rio_gp_stats* st) {
     return RIO_GP_OK;
 }
 }  // extern "C"
+#endif  // STUB_RIO_GP_CPP

@@ -1,6 +1,7 @@
 """Race detection for the host side of the boundary: the string layer's interning, combining front-end
 and reference counting (rio-rs_amd/csrc/gpu_object_placement.cpp) compiled with ThreadSanitizer against a host-memory
-stub of the dense C ABI (tests/stub_rio_gp.cpp — test infrastructure, not a product path) and hammered by 12 threads."""
+stub of the dense C ABI (tests/stub_rio_gp_all.cpp: the base stub plus the reverse index, the rebalance and the change feed — test
+infrastructure, not a product path) and hammered by up to 16 threads."""
 import os
 import shutil
 import subprocess
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_string_layer_under_thread_sanitizer(tmp_path):
     exe = tmp_path / "race_driver"
     srcs = [os.path.join(ROOT, "rio-rs_amd", "csrc", "gpu_object_placement.cpp"),
-            os.path.join(ROOT, "tests", "stub_rio_gp.cpp"), os.path.join(ROOT, "tests", "host_layer_race_driver.cpp")]
+            os.path.join(ROOT, "tests", "stub_rio_gp_all.cpp"), os.path.join(ROOT, "tests", "host_layer_race_driver.cpp")]
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-pthread", "-I", os.path.join(ROOT, "include")]
                    + srcs + ["-o", str(exe)], check=True)
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66")
