@@ -102,6 +102,19 @@ const char* rio_op_node_address(rio_op_t* p, uint32_t node_id);
  * only ever seen through `update` is not a member, i.e. not active, as in the reference.
  * capacity: load units, RIO_GP_CAP_INF = unbounded (the reference has no capacity). */
 int rio_op_set_member(rio_op_t* p, const char* address, int active, uint64_t capacity);
+/* MembershipStorage::remove (cluster/storage/mod.rs:77, next to push :74 and set_is_active :80) for any number of addresses at
+ * once: every object on them is un-placed as by rio_op_clean_server (local.rs:51-58), then the addresses and their node ids are
+ * forgotten — the ids are handed back, so a cluster whose servers come back under new addresses never fills the node table
+ * (max_nodes).  The surviving nodes keep their relative order and are renumbered 0 .. m-1 (rio_gp_remap_nodes).  An address
+ * never seen, or given twice, is ignored.  *removed = ids freed, *evicted = objects un-placed (either may be NULL).
+ *   - Node ids obtained earlier (rio_op_lookup_batch, rio_op_get_or_create_placement_batch) are VOID after the call: resolve
+ *     them with rio_op_node_address before removing members, or ask again.  Pointers rio_op_node_address returned earlier stay
+ *     valid until rio_op_release, those of removed addresses included.
+ *   - A removed address may be seen again later (update, set_member, a requester): it gets a fresh id and holds no objects.
+ *   - rio_op_changes lists the un-placed keys as deletes whose old address is NULL (the address is gone).
+ *   - It takes the write side of the table lock, waits for the single-object calls in flight and invalidates the host shadow.
+ *   - A dense layer without rio_gp_remap_nodes: RIO_GP_EUPSTREAM, nothing changed. */
+int rio_op_remove_members(rio_op_t* p, uint64_t n, const char* const* addresses, uint64_t* removed, uint64_t* evicted);
 /* per-object load (default 1; new behaviour, the reference has none).  A key first seen here keeps its row (and the
  * load) until its first update / request makes it an object; from then on it is reclaimed like any other key. */
 int rio_op_set_object_load(rio_op_t* p, const char* struct_name, const char* object_id, uint32_t load);
@@ -153,7 +166,8 @@ int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const cha
  * what keeps a write-behind copy of the object_placement table (migrations/0001-sqlite-init.sql:1-9, sqlite.rs:68-85) in step
  * without a snapshot.  Entry k is (struct_names[k], object_ids[k], old_addresses[k], new_addresses[k]); an address is NULL when
  * the key was not placed (a node id without an address counts as not placed, as in rio_op_snapshot), so a NULL new address
- * means "delete the key".  All entries with a NULL new address come first, then the others, each group in row order: applied
+ * means "delete the key".  A key whose server was removed (rio_op_remove_members) is such a delete with a NULL old address as
+ * well: the address it was on is no longer known.  All entries with a NULL new address come first, then the others, each group in row order: applied
  * in order to a mirror that equals rio_op_snapshot as of the previous call, they yield rio_op_snapshot as of now (as a set of
  * (struct_name, object_id, server_address)).  A row handed to a new key by the table's reclaiming of dead keys gives a delete
  * of the key the mirror holds for it and, if the row is placed, an upsert of its new key.

@@ -213,6 +213,36 @@ int rio_gp_clean_server(rio_gp_t* h, uint32_t node, uint64_t* evicted);
 /* Same for any number of failed nodes in ONE pass: bit j of dead_bitmap (ceil(m/64) words). */
 int rio_gp_clean_servers(rio_gp_t* h, const uint64_t* dead_bitmap, uint64_t* evicted);
 
+/* ---- node removal: renumber the node table and every column that names a node --------------- */
+
+/* change feed only: out_old of a row whose last-told node has since been removed */
+#define RIO_GP_NODE_GONE 0xFFFFFFFCu
+
+/* MembershipStorage::remove (rio-rs/src/cluster/storage/mod.rs:77, next to push :74 and set_is_active :80) for the dense
+ * table: node ids are handed back.  m = rio_gp_num_nodes(h); map has m entries: map[j] = the new id of node j, or RIO_GP_NONE
+ * when node j is removed.  The kept entries hit every value of 0 .. m_new-1 exactly once (so m_new <= m; m_new == m is a pure
+ * permutation).  The rule (DESIGN.md section 2 rule 8) is exactly rio_gp_clean_servers over the removed nodes, then a
+ * renumbering, over every row the handle holds — the rows >= n that rio_gp_set_num_objects hides included:
+ *   - assignment: a value v < m becomes map[v]; a row on a removed node becomes RIO_GP_NONE (and, under
+ *     RIO_GP_CFG_ROW_LIFECYCLE, a non-object, as clean_server makes it: local.rs:51-58); values >= m (RIO_GP_NONE, ids a
+ *     shrinking rio_gp_set_nodes left behind) stay.  *evicted (may be NULL) = the rows < n un-placed this way: what
+ *     rio_gp_clean_servers would report.
+ *   - affinity: v < m becomes map[v], an affinity naming a removed node becomes RIO_GP_NONE ("no preferred node");
+ *     RIO_GP_AFF_INACTIVE and every other value >= m stay.
+ *   - the feed's checkpoint B (only if the feed has been used; nothing is allocated otherwise): v < m becomes map[v], a
+ *     removed node becomes RIO_GP_NODE_GONE.  A row last told "on j" and now un-placed is listed by the next rio_gp_changes
+ *     as (r, RIO_GP_NODE_GONE, RIO_GP_NONE); a row whose node was only renumbered is not listed.
+ *   - node table: cap and alive of node j move to map[j] (a rio_gp_set_alive* push still waiting is applied first); the node
+ *     count becomes m_new; `used` is the one of the new column on return.
+ *   - Like rio_gp_update_batch: it joins rio_gp_tick_async work in flight, drops an uncommitted rio_gp_solve and counts as a
+ *     change of the inputs.  Load, n, the counters and the index scratch are untouched.  Node ids handed out before the call
+ *     (lookups, listings) are void after it.
+ *   - RIO_GP_EINVAL, nothing changed: map == NULL, a kept value >= m_new, a value that appears twice, fewer than m_new kept
+ *     entries, or a handle of the row-sharded solve.
+ *   - Cost: one streaming pass, 8 B read per row (12 B with the feed in use); a column's tile of 256 rows is written only
+ *     where one of its values changes. */
+int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* map, uint64_t* evicted);
+
 /* ---- reverse index: the rows on given nodes ------------------------------------------------ */
 
 /* Reverse index of the assignment column: the object_placement(server_address) index (idx_object_placement_server_address,
@@ -303,6 +333,9 @@ int rio_gp_rebalance_dev(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_re
  *   - Rows >= n are not listed and keep their B.  Shrinking n (rio_gp_set_num_objects) therefore HIDES rows from the feed until
  *     n grows again; then they are compared as usual.
  *   - RIO_GP_EINVAL on a handle of the row-sharded solve (rio_gp_shard_*, rio_gp_p2p_*): a per-shard feed is not implemented.
+ *   - out_old may be RIO_GP_NODE_GONE: the node the consumer was last told for that row has since been removed
+ *     (rio_gp_remap_nodes) and has no id any more; a mirror treats it as "was placed, on a node that is gone".  Checkpoints
+ *     naming a node that was merely renumbered follow the renumbering: such a row is not listed.
  *   - Memory: B takes 4 B per row of max_objects, allocated (filled with RIO_GP_NONE) by the first feed call and kept until
  *     rio_gp_destroy, plus 4 B per 1 024 rows of tile counts; a handle that never calls the feed pays nothing.  The host-pointer
  *     form also stages its listing in device memory (12 B per listed row, kept at the largest listing so far).

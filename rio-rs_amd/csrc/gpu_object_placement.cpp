@@ -63,6 +63,8 @@ extern "C" int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, ri
 extern "C" int rio_gp_changes(rio_gp_t* h, uint32_t flags, uint32_t* out_rows, uint32_t* out_old, uint32_t* out_new, uint64_t cap,
                               uint64_t* n_changes) __attribute__((weak));
 extern "C" int rio_gp_changes_reset(rio_gp_t* h) __attribute__((weak));
+// Weak for the same reason: node removal (rio_op_remove_members reports RIO_GP_EUPSTREAM without it).
+extern "C" int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* map, uint64_t* evicted) __attribute__((weak));
 
 namespace {
 
@@ -255,6 +257,20 @@ class TableLock {
     }
 };
 
+// node id -> address.  The strings live in `store`, which never moves or frees one: rio_op_node_address and rio_op_changes hand
+// out their c_str(), valid until rio_op_release.  Removing nodes (rio_op_remove_members) rebuilds the id table only; the strings
+// of removed nodes stay behind in `store` (the graveyard), and an address that comes back gets a new string with its new id.
+struct NodeAddrs {
+    std::deque<std::string> store;
+    std::vector<const std::string*> by_id;
+    size_t size() const { return by_id.size(); }
+    const std::string& operator[](size_t id) const { return *by_id[id]; }
+    void push_back(const std::string& a) {
+        store.push_back(a);
+        by_id.push_back(&store.back());
+    }
+};
+
 struct State {
     // (the words many threads hammer at once sit on cache lines of their own: 64 waiters trying the device lock on the line the
     //  publishers' list head and the table lock's reader count live on cost 50 us per combined batch, measured)
@@ -291,13 +307,14 @@ struct State {
     std::atomic<uint64_t> hi_rows{0};                 // rows ever handed out: every row id is < hi_rows (atomic: sync_device looks
                                                       // at it and at the two versions below without the table lock)
     std::unordered_map<std::string, uint32_t> nodes;  // address -> node id
-    std::deque<std::string> node_addr;                // deque: element addresses are stable (rio_op_node_address)
+    NodeAddrs node_addr;                              // the strings never move (rio_op_node_address)
     std::vector<uint8_t> node_alive, node_malformed;
     std::vector<uint64_t> node_cap;
     uint32_t n_malformed = 0;
     std::atomic<uint64_t> node_version{1};            // bumped on every change of the node table
     std::atomic<uint64_t> shape_version{1};           // bumped when a node is added or a capacity changes (not on liveness flips)
-    bool reclaiming = false;                          // single-object calls wait (rcv) while keys are being reclaimed
+    bool reclaiming = false;                          // single-object calls wait (rcv) while keys are being reclaimed, or nodes
+                                                      // removed (rio_op_remove_members: the node ids they carry are renumbered)
     std::condition_variable_any rcv;
     // --- under mu ---
     uint64_t pushed_version = 0;                      // node_version the device holds
@@ -872,8 +889,11 @@ int run_combined(State* s, Req* mine) {
 // waits for that count to drain before it forgets any key).
 // `intern(excl)` fills the request and returns RIO_GP_OK, kFull, an error, kNoop = "nothing to do" (e.g. lookup of an unknown
 // key), kHit = answered, or (excl == false only) kUpgrade.
-template <typename F>
-int single_call(State* s, Req* r, F intern) {
+// `done(rc)` runs after the round trip and BEFORE the call stops counting as in flight: what still needs the node id the device
+// answered with (its address) happens there — rio_op_remove_members renumbers the ids only once nothing is in flight.
+struct NoDone { int operator()(int rc) const { return rc; } };
+template <typename F, typename D = NoDone>
+int single_call(State* s, Req* r, F intern, D done = D()) {
     for (int attempt = 0;; ++attempt) {
         int rc;
         {
@@ -895,8 +915,9 @@ int single_call(State* s, Req* r, F intern) {
         if (rc == kFull) return fail(RIO_GP_EINVAL, "object table full (max_objects live objects)");
         if (rc != RIO_GP_OK) return rc;
         rc = run_combined(s, r);
-        s->inflight.fetch_sub(1, std::memory_order_acq_rel);  // what the caller still holds are node ids: never reclaimed
         if (rc) t_err = r->err;
+        rc = done(rc);
+        s->inflight.fetch_sub(1, std::memory_order_acq_rel);
         return rc;
     }
 }
@@ -997,7 +1018,7 @@ rio_gp_t* rio_op_dense(rio_op_t* p) { return p ? p->s->gp : nullptr; }
 const char* rio_op_node_address(rio_op_t* p, uint32_t node_id) {
     if (!p) return nullptr;
     std::shared_lock<TableLock> gi(p->s->imu);
-    // node_addr is a deque of strings that are never modified: the pointer stays valid for the life of the provider
+    // the strings are never modified, moved or freed (NodeAddrs): the pointer stays valid for the life of the provider
     return node_id < p->s->node_addr.size() ? p->s->node_addr[node_id].c_str() : nullptr;
 }
 
@@ -1120,17 +1141,19 @@ static int op_lookup(rio_op_t* p, const Part& ty, const Part& id, char* out, siz
             return kHit;
         }
         return RIO_GP_OK;
+    }, [&](int rc) -> int {  // (still in flight: the node id is the one the address table knows)
+        if (rc) return rc;
+        *found = r.node != RIO_GP_NONE;
+        t_addr_len = 0;
+        if (*found) {
+            std::shared_lock<TableLock> gi(s->imu);
+            return copy_out(s->node_addr[r.node], out, cap);  // RIO_GP_ERANGE: *found is set, nothing was copied
+        }
+        return RIO_GP_OK;
     });
     if (rc == kNoop) return RIO_GP_OK;
     if (rc == kHit) return hit_rc;
-    if (rc) return rc;
-    *found = r.node != RIO_GP_NONE;
-    t_addr_len = 0;
-    if (*found) {
-        std::shared_lock<TableLock> gi(s->imu);
-        return copy_out(s->node_addr[r.node], out, cap);  // RIO_GP_ERANGE: *found is set, nothing was copied
-    }
-    return RIO_GP_OK;
+    return rc;
 }
 
 int rio_op_lookup(rio_op_t* p, const char* ty, const char* id, char* out, size_t cap, int* found) {
@@ -1250,6 +1273,85 @@ int rio_op_set_member(rio_op_t* p, const char* address, int active, uint64_t cap
     return sync_device(s, true);
 }
 
+// MembershipStorage::remove (cluster/storage/mod.rs:77), mu + the write side of the table lock held, nothing in flight
+static int remove_members_locked(State* s, uint64_t n, const char* const* addresses, uint64_t* removed, uint64_t* evicted) {
+    if (!rio_gp_remap_nodes) return fail(RIO_GP_EUPSTREAM, "dense layer has no node removal");
+    const uint32_t m = (uint32_t)s->node_addr.size();
+    std::vector<uint32_t> map(m ? m : 1, 0);
+    uint32_t gone = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+        const auto it = s->nodes.find(addresses[k]);
+        if (it == s->nodes.end() || map[it->second] == RIO_GP_NONE) continue;  // never seen, or given twice
+        map[it->second] = RIO_GP_NONE;
+        ++gone;
+    }
+    if (!gone) return RIO_GP_OK;
+    // stable compaction: the surviving nodes keep their relative order
+    uint32_t m_new = 0;
+    for (uint32_t j = 0; j < m; ++j)
+        if (map[j] != RIO_GP_NONE) map[j] = m_new++;
+    // the device holds the table as it is (no rio_gp_set_nodes of the old shape may follow the renumbering), then renumbers
+    int rc;
+    if ((rc = sync_device(s, true))) return rc;
+    uint64_t ev = 0;
+    if ((rc = rio_gp_remap_nodes(s->gp, m_new, map.data(), &ev))) return gp_fail(s, rc);
+    std::vector<const std::string*> by_id(m_new);
+    std::vector<uint8_t> alive(m_new), bad(m_new);
+    std::vector<uint64_t> cap(m_new), stamp(m_new);
+    s->n_malformed = 0;
+    for (uint32_t j = 0; j < m; ++j) {
+        const uint32_t k = map[j];
+        if (k == RIO_GP_NONE) { s->nodes.erase(s->node_addr[j]); continue; }
+        s->nodes[s->node_addr[j]] = k;
+        by_id[k] = s->node_addr.by_id[j];
+        alive[k] = s->node_alive[j];
+        bad[k] = s->node_malformed[j];
+        cap[k] = s->node_cap[j];
+        stamp[k] = s->shadow.clean_stamp[j].load(std::memory_order_relaxed);
+        s->n_malformed += bad[k];
+    }
+    s->node_addr.by_id.swap(by_id);
+    s->node_alive.swap(alive);
+    s->node_malformed.swap(bad);
+    s->node_cap.swap(cap);
+    // the shadow's entries name old ids: all of them are void (as after a tick); the per-node stamps follow their nodes
+    for (uint32_t k = 0; k < m; ++k) s->shadow.clean_stamp[k].store(k < m_new ? stamp[k] : 0, std::memory_order_relaxed);
+    s->shadow.invalidate_all();
+    // the device already holds this table
+    s->pushed_version = ++s->node_version;
+    s->pushed_shape = ++s->shape_version;
+    s->pushed_nodes = m_new;
+    if (removed) *removed = gone;
+    if (evicted) *evicted = ev;
+    return RIO_GP_OK;
+}
+
+int rio_op_remove_members(rio_op_t* p, uint64_t n, const char* const* addresses, uint64_t* removed, uint64_t* evicted) {
+    if (!p || (n && !addresses)) return RIO_GP_EINVAL;
+    for (uint64_t k = 0; k < n; ++k)
+        if (!addresses[k]) return RIO_GP_EINVAL;
+    if (removed) *removed = 0;
+    if (evicted) *evicted = 0;
+    State* s = p->s;
+    // node ids live in single-object calls between their intern and their return: hold new ones off and drain those in flight,
+    // as reclaim() does for row ids
+    {
+        std::unique_lock<TableLock> li(s->imu);
+        while (s->reclaiming) s->rcv.wait(li);
+        s->reclaiming = true;
+    }
+    while (s->inflight.load(std::memory_order_acquire) != 0) sched_yield();
+    int rc;
+    {
+        DevLock g(s);
+        std::lock_guard<TableLock> gi(s->imu);
+        rc = remove_members_locked(s, n, addresses, removed, evicted);
+        s->reclaiming = false;
+    }
+    s->rcv.notify_all();
+    return rc;
+}
+
 static int op_set_object_load(rio_op_t* p, const Part& ty, const Part& id, uint32_t load) {
     if (!p) return RIO_GP_EINVAL;
     State* s = p->s;
@@ -1320,13 +1422,15 @@ static int op_get_or_create(rio_op_t* p, const Part& ty, const Part& id, const c
             return kHit;
         }
         return RIO_GP_OK;
+    }, [&](int rc) -> int {  // (still in flight: the node id is the one the address table knows)
+        if (rc) return rc;
+        if (flag) *flag = r.flag;
+        std::shared_lock<TableLock> gi(s->imu);
+        // RIO_GP_ERANGE: the decision is made and *flag is set; the address is one rio_op_lookup away (a pure read)
+        return copy_out(r.node == RIO_GP_NONE ? std::string() : s->node_addr[r.node], out, cap);
     });
     if (rc == kHit) return hit_rc;
-    if (rc) return rc;
-    if (flag) *flag = r.flag;
-    std::shared_lock<TableLock> gi(s->imu);
-    // RIO_GP_ERANGE: the decision is made and *flag is set; the address is one rio_op_lookup away (a pure read)
-    return copy_out(r.node == RIO_GP_NONE ? std::string() : s->node_addr[r.node], out, cap);
+    return rc;
 }
 
 int rio_op_get_or_create_placement(rio_op_t* p, const char* ty, const char* id, const char* self_address, char* out,
@@ -1544,9 +1648,11 @@ int rio_op_changes(rio_op_t* p, uint64_t* n_out, int* full, const char* const** 
         auto row = [&](uint32_t r, uint32_t from, uint32_t to) {
             const char* a0 = addr(from);
             const char* a1 = addr(to);
+            // (RIO_GP_NODE_GONE: the mirror holds the key on an address that has been removed — placed, address no longer known)
+            const bool was = a0 || from == RIO_GP_NODE_GONE;
             const auto it = s->retired.find(r);
             if (it != s->retired.end()) {
-                if (a0) { t_ch_store.push_back(it->second.first); t_ch_store.push_back(it->second.second); del_old.push_back(a0); }
+                if (was) { t_ch_store.push_back(it->second.first); t_ch_store.push_back(it->second.second); del_old.push_back(a0); }
                 if (a1 && s->row_live[r]) {
                     up_keys.push_back(s->row_key[r].first); up_keys.push_back(s->row_key[r].second);
                     up_old.push_back(nullptr); up_new.push_back(a1);
@@ -1557,7 +1663,7 @@ int rio_op_changes(rio_op_t* p, uint64_t* n_out, int* full, const char* const** 
             if (a1) {
                 up_keys.push_back(s->row_key[r].first); up_keys.push_back(s->row_key[r].second);
                 up_old.push_back(a0); up_new.push_back(a1);
-            } else if (a0) {
+            } else if (was) {
                 t_ch_store.push_back(s->row_key[r].first); t_ch_store.push_back(s->row_key[r].second); del_old.push_back(a0);
             }
         };

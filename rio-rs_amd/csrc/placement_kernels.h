@@ -510,4 +510,12 @@ void launch_chg_count(const u32* A, const u32* B, const ChgPlan& p, u32* cnt, u3
 void launch_chg_list(const u32* A, u32* B, const ChgPlan& p, const u32* cnt, const u32* gsum, u64 cap, bool consume, u32* rows,
                      u32* old_node, u32* new_node, hipStream_t s);
 
+// --- node removal (rio_gp_remap_nodes): clean the removed nodes' rows and renumber the kept nodes, one pass (k_remap) ---
+constexpr u32 kRemapMaxNodes = 8192;     // = RIO_GP_MAX_NODES: the map's LDS image
+constexpr u32 kNodeGone = 0xFFFFFFFCu;   // RIO_GP_NODE_GONE: checkpoint of a row whose last-told node has been removed
+// map: m u32 in device memory (new id, kNone = removed).  Rows 0 .. rows-1 of assign / aff / B (B may be nullptr) are rewritten
+// where a value changes; life: a row that loses its node also becomes a non-object.  blk: [G][4] u64, workgroup b stores
+// {0, rows < n_count it un-placed, 0, 0}; returns G.
+u32 launch_remap(u32* assign, u32* aff, u32* B, u64 rows, u64 n_count, u32 m, const u32* map, bool life, u64* blk, hipStream_t s);
+
 }  // namespace riogp

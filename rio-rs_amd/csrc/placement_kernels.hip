@@ -6999,4 +6999,82 @@ void launch_chg_list(const u32* A, u32* B, const ChgPlan& p, const u32* cnt, con
                        old_node, new_node);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Node removal (rio_gp_remap_nodes, DESIGN.md section 2 rule 8): MembershipStorage::remove (rio-rs/src/cluster/storage/mod.rs:77)
+// for the dense table — clean_server (local.rs:51-58) over the removed nodes and a renumbering of the kept ones, in ONE streaming
+// pass over the assignment column, the affinity column and, when the change feed is in use, its checkpoint column B.
+//   * the map (new id of node j, kNone = removed) sits in LDS, loaded once per workgroup: at most 8 192 entries = 32 KiB, two
+//     1 024-thread workgroups per CU still fit (launch bound 8 waves per SIMD = 64 VGPRs);
+//   * the usual split: wave gw owns the tiles of 256 rows of [wave_row_lo(gw), wave_row_lo(gw + 1)); one dwordx4 load per lane,
+//     column and tile, the next tile's loads in flight while this one's values go through the map;
+//   * a column's tile is stored (whole: 1 KiB per wave-instruction) only where the ballot says one of its values changed — the
+//     removal of one node of a thousand leaves most tiles of the assignment column and almost all of the other two alone, a pure
+//     permutation rewrites all three (8 or 12 B read per row, 0 .. 8 or 12 B written);
+//   * whole tiles are read and written: the columns are padded past max_objects (k_chg_count's note), and rows past `rows` hold
+//     kNone, which maps to itself;
+//   * the evicted count (rows < n_count only: hidden rows are cleaned but are no objects of the table) is summed per wave, then
+//     per workgroup in LDS, and leaves as workgroup b's row of the per-workgroup counter rows blk[G][4] (the solve's blkstat: kept |
+//     evicted | claimants | -), plain stores; the host adds the rows up.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock, 8) void k_remap(u32* __restrict__ assign, u32* __restrict__ aff, u32* __restrict__ B,
+                                                     const Plan p, u64 n_count, const u32* __restrict__ map, u32 life,
+                                                     u64* __restrict__ blk) {
+    __shared__ u32 mp[kRemapMaxNodes];
+    __shared__ u32 ev_total;
+    const u32 tid = threadIdx.x, lane = tid & 63, m = p.m;
+    u64 ws, we;
+    wave_range_plain(p, (u64)blockIdx.x * kWaves + (tid >> 6), ws, we);
+    // (an empty range reads tile 0 of the padded columns and judges nothing)
+    const u64 first = (ws < we ? ws : 0) + (u64)lane * 4;
+    uint4 c = *reinterpret_cast<const uint4*>(assign + first);
+    uint4 a = *reinterpret_cast<const uint4*>(aff + first);
+    uint4 b = make_uint4(kNone, kNone, kNone, kNone);
+    if (B) b = *reinterpret_cast<const uint4*>(B + first);
+    for (u32 k = tid; k < m; k += kBlock) mp[k] = map[k];
+    if (tid == 0) ev_total = 0;
+    __syncthreads();
+    u32 ev = 0;
+    for (u64 it = ws; it < we; it += kTile) {  // wave-uniform
+        const u64 i0 = it + (u64)lane * 4;
+        const u64 nx = (it + kTile < we ? it + kTile : it) + (u64)lane * 4;  // next tile in flight (the last re-reads its own)
+        const uint4 cn = *reinterpret_cast<const uint4*>(assign + nx);
+        const uint4 an = *reinterpret_cast<const uint4*>(aff + nx);
+        uint4 bn = b;
+        if (B) bn = *reinterpret_cast<const uint4*>(B + nx);
+        uint4 c2 = c, a2 = a, b2 = b;
+#define RIOGP_RM(C, A, Bv, E)                                                                          \
+        {                                                                                              \
+            const bool cin = C < m, ain = A < m, bin = Bv < m;                                         \
+            const u32 cm = mp[cin ? C : 0u], am = mp[ain ? A : 0u], bm = mp[bin ? Bv : 0u];           \
+            const bool gone = cin && cm == kNone;                                                      \
+            ev += (u32)(gone && i0 + E < n_count);                                                     \
+            C = cin ? cm : C;                                                                          \
+            A = (gone && life) ? kAffInactive : (ain ? am : A);                                        \
+            Bv = bin ? (bm == kNone ? kNodeGone : bm) : Bv;                                            \
+        }
+        RIOGP_RM(c2.x, a2.x, b2.x, 0)
+        RIOGP_RM(c2.y, a2.y, b2.y, 1)
+        RIOGP_RM(c2.z, a2.z, b2.z, 2)
+        RIOGP_RM(c2.w, a2.w, b2.w, 3)
+#undef RIOGP_RM
+        const bool dc = (c2.x != c.x) | (c2.y != c.y) | (c2.z != c.z) | (c2.w != c.w);
+        const bool da = (a2.x != a.x) | (a2.y != a.y) | (a2.z != a.z) | (a2.w != a.w);
+        const bool db = (b2.x != b.x) | (b2.y != b.y) | (b2.z != b.z) | (b2.w != b.w);
+        if (__ballot(dc)) *reinterpret_cast<uint4*>(assign + i0) = c2;
+        if (__ballot(da)) *reinterpret_cast<uint4*>(aff + i0) = a2;
+        if (B && __ballot(db)) *reinterpret_cast<uint4*>(B + i0) = b2;
+        c = cn; a = an; b = bn;
+    }
+    ev = wave_sum32(ev);
+    if (lane == 0 && ev) atomicAdd(&ev_total, ev);
+    __syncthreads();
+    if (tid < 4) blk[(size_t)blockIdx.x * 4 + tid] = tid == 1 ? (u64)ev_total : 0ull;
+}
+
+u32 launch_remap(u32* assign, u32* aff, u32* B, u64 rows, u64 n_count, u32 m, const u32* map, bool life, u64* blk, hipStream_t s) {
+    const Plan p = make_plan(rows, m, 0);
+    hipLaunchKernelGGL(k_remap, dim3(p.G), dim3(kBlock), 0, s, assign, aff, B, p, n_count, map, life ? 1u : 0u, blk);
+    return p.G;
+}
+
 }  // namespace riogp

@@ -2067,6 +2067,78 @@ int rio_gp_clean_server(rio_gp_t* h, uint32_t node, uint64_t* evicted) {
     return rio_gp_clean_servers(h, bm.data(), evicted);
 }
 
+// MembershipStorage::remove (cluster/storage/mod.rs:77) for the dense table: DESIGN.md section 2 rule 8.  The map is checked on
+// the host (at most RIO_GP_MAX_NODES entries) before anything changes; then one launch of k_remap over the committed column, the
+// affinity column and the feed's checkpoint, rows 0 .. n_hi-1.  The other assignment column needs no pass: the solve it may hold
+// is dropped, a later solve writes its rows < n, and commit_enqueue copies the rows [n, n_hi) over from the committed column
+// before it swaps.
+int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* map, uint64_t* evicted) {
+    static_assert(kRemapMaxNodes == RIO_GP_MAX_NODES && kNodeGone == RIO_GP_NODE_GONE, "k_remap's constants follow the header");
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (!map) return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: map is NULL");
+    if (h->sc || h->p2p || h->sh_tick_n)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: not implemented on a handle of the row-sharded solve");
+    const u32 m = h->m;
+    if (m_new > m) return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: m_new exceeds the node count");
+    std::vector<u32> from(m_new ? m_new : 1, kNone);  // new id -> old id
+    u32 kept = 0;
+    for (u32 j = 0; j < m; ++j) {
+        if (map[j] == RIO_GP_NONE) continue;
+        if (map[j] >= m_new) return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: a kept node's new id is not below m_new");
+        if (from[map[j]] != kNone) return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: two nodes map to the same id");
+        from[map[j]] = j;
+        ++kept;
+    }
+    if (kept != m_new) return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: fewer than m_new nodes are kept");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (evicted) *evicted = 0;
+    // a change of the inputs, like every CRUD call: an uncommitted solve is dropped, the next tick is neither quiet nor chained
+    h->have_solved = false; ++h->mut_epoch;
+    h->last_pending_valid = false;
+    int rc;
+    u32 G = 0;
+    if (m && h->n_hi) {
+        if ((rc = ensure(h, h->stage[0], (size_t)m * sizeof(u32)))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->stage[0].p, map, (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+        G = launch_remap(h->assign[h->cur], h->aff, h->chg_B, h->n_hi, h->n, m, (const u32*)h->stage[0].p, h->lifecycle,
+                         h->sb.blkstat, h->stream);
+        HIPCHK(h, hipGetLastError());
+        // `used` is the one of the new column: rebuilt from it before its next use (nothing left to fold)
+        h->used_valid = false;
+        h->used_parts = false;
+    }
+    // the node table: cap and alive of node j move to map[j]; h_alive already holds every liveness push, delivered or not, so
+    // the device bitmap is written whole from it
+    std::vector<u64> cap(m ? m : 1), cap2(m_new ? m_new : 1);
+    std::vector<u64> blk((size_t)(G ? G : 1) * 4, 0);
+    if (m) HIPCHK(h, hipMemcpyAsync(cap.data(), h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    if (G) HIPCHK(h, hipMemcpyAsync(blk.data(), h->sb.blkstat, (size_t)G * 4 * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<uint8_t> alive2(m_new);
+    h->all_alive = true;
+    for (u32 k = 0; k < m_new; ++k) {
+        cap2[k] = cap[from[k]];
+        alive2[k] = h->h_alive[from[k]];
+        h->all_alive = h->all_alive && alive2[k];
+    }
+    h->h_alive.swap(alive2);
+    h->m = m_new;
+    h->alive_dirty = false;
+    if (m_new) {
+        HIPCHK(h, hipMemcpyAsync(h->cap, cap2.data(), (size_t)m_new * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->alive_bytes, h->h_alive.data(), m_new, hipMemcpyHostToDevice, h->stream));
+    }
+    launch_pack_alive(h->alive_bytes, m_new, h->alive_bits, h->stream);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    if (m_new != m) { h->used_valid = false; h->used_parts = false; }
+    u64 ev = 0;
+    for (u32 b = 0; b < G; ++b) ev += blk[(size_t)b * 4 + 1];
+    if (evicted) *evicted = ev;
+    return RIO_GP_OK;
+}
+
 // ---- policy -------------------------------------------------------------------------------
 
 // The general path of place_pending (any batch the one-workgroup kernels do not finish): the window-sorted form for big dense

@@ -23,6 +23,7 @@ FLAG_LOCAL, FLAG_REDIRECT, FLAG_PLACED, FLAG_SPILLED, FLAG_UNPLACED = range(5)
 FLAG_REPLACED = 0x10   # OR-ed on: the object was found on a dead server, cleaned and re-placed by this request
 FLAG_MASK = 0x0F
 CHANGES_PEEK = 1       # RIO_GP_CHANGES_PEEK: list the changes without advancing the checkpoint
+NODE_GONE = 0xFFFFFFFC  # RIO_GP_NODE_GONE: change feed, old node of a row whose last-told node has been removed
 OK, EINVAL, EUPSTREAM, ENODEV, ENOMEM, ERANGE, EAGAIN = range(7)
 ABI_VERSION = 2    # include/rio_gpu_placement.h RIO_GP_ABI_VERSION
 
@@ -207,6 +208,7 @@ def _load(lab):
         for nm in ("rio_gp_changes", "rio_gp_changes_dev"):
             getattr(L, nm).argtypes = [_vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.rio_gp_changes_reset.argtypes = [_vp]
+        L.rio_gp_remap_nodes.argtypes = [_vp, C.c_uint32, _vp, C.POINTER(C.c_uint64)]
         if lab:
             L.rio_gp_debug_set_scan_nt.argtypes = [C.c_int]
             L.rio_gp_debug_set_scan_nt.restype = None
@@ -438,6 +440,33 @@ class GpuPlacement:
         if rc not in (OK, ERANGE):
             self._chk(rc)
         return rc, int(n.value)
+
+    # -- node removal --
+    def remap_nodes(self, map):
+        """rio_gp_remap_nodes: map[j] = the new id of node j, NONE = removed (the kept ids are 0 .. m_new-1, each once).  Returns
+        the rows un-placed."""
+        map = _u32(map)
+        m_new = int(np.count_nonzero(map != NONE))
+        ev = C.c_uint64(0)
+        arg = map if len(map) else np.zeros(1, np.uint32)   # (an empty node table: the pointer must still not be NULL)
+        self._chk(self._L.rio_gp_remap_nodes(self._h, m_new, _ptr(arg), C.byref(ev)))
+        return int(ev.value)
+
+    def remap_nodes_raw(self, m_new, map):
+        """One rio_gp_remap_nodes call as given (tests of the argument checks): (rc, evicted); no exception."""
+        map = _u32(map)
+        ev = C.c_uint64(0)
+        rc = self._L.rio_gp_remap_nodes(self._h, int(m_new), _ptr(map), C.byref(ev))
+        return rc, int(ev.value)
+
+    def drop_nodes(self, nodes):
+        """Remove the given nodes; the others keep their relative order (stable compaction).  Returns (map, evicted)."""
+        m = self.num_nodes
+        keep = np.ones(m, bool)
+        keep[np.asarray(list(nodes), np.int64)] = False
+        map = np.full(m, NONE, np.uint32)
+        map[keep] = np.arange(int(keep.sum()), dtype=np.uint32)
+        return map, self.remap_nodes(map)
 
     # -- bounded rebalance --
     def _rebalance_cfg(self, target, max_moves, rounds):
@@ -719,6 +748,7 @@ def _oplib():
         L.rio_op_node_address.argtypes = [_vp, C.c_uint32]
         L.rio_op_node_address.restype = C.c_char_p
         L.rio_op_set_member.argtypes = [_vp, C.c_char_p, C.c_int, C.c_uint64]
+        L.rio_op_remove_members.argtypes = [_vp, C.c_uint64, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.rio_op_set_object_load.argtypes = [_vp, C.c_char_p, C.c_char_p, C.c_uint32]
         L.rio_op_get_or_create_placement.argtypes = [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t,
                                                      C.POINTER(C.c_uint32)]
@@ -903,6 +933,15 @@ class GpuObjectPlacement:
 
     def set_member(self, address, active=True, capacity=CAP_INF):
         self._chk(_oplib().rio_op_set_member(self._h, address.encode(), int(bool(active)), capacity))
+
+    def remove_members(self, addresses):
+        """rio_op_remove_members (MembershipStorage::remove, cluster/storage/mod.rs:77): (removed, evicted) — the node ids freed
+        and the objects un-placed.  Node ids obtained before the call are void after it."""
+        enc = [a.encode() for a in addresses]
+        arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        removed, evicted = C.c_uint64(0), C.c_uint64(0)
+        self._chk(_oplib().rio_op_remove_members(self._h, len(enc), arr, C.byref(removed), C.byref(evicted)))
+        return int(removed.value), int(evicted.value)
 
     def set_object_load(self, struct_name, object_id, load):
         t, i = struct_name.encode(), object_id.encode()

@@ -96,6 +96,7 @@ extern "C" {
     fn rio_op_clean_server(p: *mut c_void, addr: *const c_char) -> c_int;
     fn rio_op_remove_n(p: *mut c_void, ty: *const c_char, ty_len: usize, id: *const c_char, id_len: usize) -> c_int;
     fn rio_op_set_member(p: *mut c_void, addr: *const c_char, active: c_int, capacity: u64) -> c_int;
+    fn rio_op_remove_members(p: *mut c_void, n: u64, addrs: *const *const c_char, removed: *mut u64, evicted: *mut u64) -> c_int;
     fn rio_op_tick(p: *mut c_void, stats: *mut RioGpStats) -> c_int;
     fn rio_op_snapshot(p: *mut c_void, n_out: *mut u64, tys: *mut *const *const c_char, ids: *mut *const *const c_char,
                        addrs: *mut *const *const c_char) -> c_int;
@@ -231,7 +232,7 @@ fn key_arrays(keys: &[ObjectId]) -> KeyArrays {
 impl GpuObjectPlacement {
     fn node_address(&self, node: u32) -> Option<String> {
         if node == u32::MAX { return None; }
-        let p = unsafe { rio_op_node_address(self.inner.0, node) };  // storage that never moves (a deque of immutable strings)
+        let p = unsafe { rio_op_node_address(self.inner.0, node) };  // storage that never moves (immutable strings, kept for removed nodes too)
         if p.is_null() { None } else { Some(unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned()) }
     }
 
@@ -268,6 +269,21 @@ impl GpuObjectPlacement {
                                                               ka.id.as_ptr(), ka.il.as_ptr(), mp.as_ptr(), node.as_mut_ptr(),
                                                               flag.as_mut_ptr()) }, self)?;
         Ok(node.into_iter().zip(flag).map(|(n, f)| (self.node_address(n), f)).collect())
+    }
+
+    /// Forget members for good: call after `MembershipStorage::remove` (rio-rs/src/cluster/storage/mod.rs:77).  Every object
+    /// on the addresses is un-placed as by `clean_server`, and their node ids are handed back, so servers that come back under
+    /// new addresses never fill the node table.  Returns (addresses forgotten, objects un-placed).
+    pub async fn remove_members(&self, addresses: Vec<String>) -> Result<(u64, u64), ObjectPlacementError> {
+        let addrs: Vec<CString> = addresses.iter().map(|a| cstr(a)).collect::<Result<_, _>>()?;
+        let me = self.clone();
+        blocking(move || {
+            let ap: Vec<*const c_char> = addrs.iter().map(|c| c.as_ptr()).collect();
+            let (mut removed, mut evicted) = (0u64, 0u64);
+            check(unsafe { rio_op_remove_members(me.inner.0, ap.len() as u64, ap.as_ptr(), &mut removed, &mut evicted) }, &me)?;
+            Ok((removed, evicted))
+        })
+        .await
     }
 
     /// Eager rebalance (the batched form of the lazy `clean_server` + first-touch path):
