@@ -110,6 +110,24 @@ struct StepGuard {  // see P2P::out_of_step
 static const char* const kOutOfStep = "the peer-to-peer session lost step with its peers in an earlier failed call: close it on every rank "
                                       "(rio_gp_shard_p2p_close), then export and connect fresh windows";
 
+// How one solve of the REAL table is enqueued (solve_form computes it; the enqueue functions take it and keep nothing).
+struct SolveForm {
+    bool compact = false;    // the scan packs the pending rows per wave, the fix-up runs over the packed rows only
+    bool cutpack = false;    // whole-table fix-up: the cut pass packs the rows that go on to the water-fill
+    int inc = 0;             // 0 k_scan | 2 k_inc_scan + k_rebal: the scan and its fix-up write the committed column itself
+    bool cut_apply = false;  // the whole-table fix-up is k_cut_apply (cuts + re-marking in one pass)
+    bool resolve_searches = false;  // k_resolve searches the cuts of the packed rows itself (no k_cut_find launch)
+    Plan fix_plan{};         // the plan of the table the fix-up runs over: the real one, or the packed rows'
+    const PackOut* pkx = nullptr;  // where the fix-up finds the packed rows: the scan's pack columns | the balanced ones (k_rebal)
+};
+// The solve that waits for its commit.  commit_enqueue consumes it; a change of the solve's inputs drops it.
+struct PendingSolve {
+    bool have = false;
+    bool inplace = false;  // it wrote its decisions into the committed column itself: the commit swaps no columns
+    bool used_D = false;   // it ran with sb.D set: what its water-fill rounds admitted is in the D rows
+    u64* used = nullptr;   // it built its `used` here instead of in sb.used_cur (a chained tick)
+};
+
 struct rio_gp {
     ShardComm* sc = nullptr;
     P2P* p2p = nullptr;
@@ -148,7 +166,6 @@ struct rio_gp {
     bool used_parts = false;
     u32 parts_rounds = 0;
     const u64* parts = nullptr;  // ... or the rows are here instead of D (a chained tick: replicas 1.. of its `used` buffer)
-    bool solve_used_D = false;  // the solve waiting for its commit ran with sb.D set
     // solve scratch
     SolveBufs sb{};
     DevStats* dstats = nullptr;
@@ -158,10 +175,12 @@ struct rio_gp {
     size_t slot_rows = 0;
     bool all_alive = true;
     Plan plan{};
-    bool have_solved = false;
+    PendingSolve pending{};
     u32 ring_n = 0;
     u32 ring_slow = 0;     // fix-up verdicts among the rio_gp_solve_async solves whose ring slots were recycled
     bool ring_any = false; // a rio_gp_solve_async solve has been enqueued since the last rio_gp_solve_wait
+    SolveForm ring_form{};      // ... the form of the last one: rio_gp_solve_wait enqueues its fix-up
+    PendingSolve ring_last{};   // ... and what it becomes once rio_gp_solve_wait has finished it (in flight, not yet pending)
     // asynchronous committed ticks (rio_gp_tick_async): verdict slots [kRing, 2 kRing) and their own ring of device-stats
     // copies, so that synchronous calls made while ticks are in flight do not touch what has not been harvested yet
     u32 tick_n = 0;
@@ -189,7 +208,6 @@ struct rio_gp {
     // packed fix-up (PackOut, placement_kernels.h): scratch columns + per-wave counts; chosen adaptively per tick
     PackOut pk{};
     bool last_pending_valid = false;
-    bool searched = false;             // the last enqueue_scan_resolve had k_resolve search the cuts itself
     // A tick that took the fast path leaves every object placed; until the next call that changes an input of the solve
     // (mut_epoch counts those) every further tick keeps every row where it is, and rio_gp_tick_async enqueues no speculative
     // fix-up behind it: two launches a tick instead of five.  quiet_epoch = the mut_epoch such a tick was enqueued under.
@@ -203,13 +221,9 @@ struct rio_gp {
     // (k_inc_scan), then k_rebal deals the pending rows out evenly to the fix-up's workgroups: 0 auto | 2 never (bits 7-8
     // of rio_gp_debug_set_compact; A/B runs, parity tests)
     int inc_mode = 0;
-    int inc_now = 0;            // how the solve waiting for its commit scanned: 0 k_scan | 2 k_inc_scan + k_rebal
-    bool solve_inplace = false; // ... and wrote its decisions into the committed column itself: the commit swaps no columns
     PackOut pk2{};              // the balanced pack columns (k_rebal); the undecided rows' lists of k_cut_apply
     u64* Tg = nullptr;          // [max_nodes][16] k_cut_apply's wave sums of the undecided rows (placement_kernels.h, SolveBufs::Tg)
-    Plan vplan{};               // the plan of the packed table the fix-up of the solve in flight runs over
     int cutpack_mode = 0;  // the same for packing at the cut pass of whole-table solves (bits 5-6 of rio_gp_debug_set_compact)
-    bool ca_now = false;   // the whole-table fix-up of the solve being enqueued is k_cut_apply (set by the caller of enqueue_scan_resolve)
     // Quiet ticks CHAIN (ScanChain, placement_kernels.h): a tick that cannot need the fix-up is one launch of the chained k_scan,
     // which adds the per-node kept loads into the tick's `used` buffer and stores its verdict rows itself.  The scans of a run of
     // quiet ticks alternate between the main stream and `scan2` and hand their rows over wave range by wave range (a flag per
@@ -231,7 +245,6 @@ struct rio_gp {
     u64* used_ring = nullptr;
     size_t used_slot_words = 0;  // kChainReps * cap_nodes where the chain can run, cap_nodes elsewhere
     u32 used_base = 0;
-    u64* solve_used = nullptr;  // the solve waiting for its commit built its `used` here instead of in sb.used_cur (a chained tick)
     int chain_diag = 0;           // lab builds, RIO_GP_CHAIN_DIAG: 1 = the chained kernel on the main stream, no waits (PMC passes: the
                                   // profiler serialises dispatches) | 3 = every link waits for a sequence number nobody will ever
                                   // store (the bounded spin and the error path under test)
@@ -462,23 +475,77 @@ struct Locked {
     std::unique_lock<std::mutex> l;
     explicit Locked(rio_gp* h, bool join = true) : l(h->mu) { if (join) chain_join(h); }
 };
-bool use_cut_apply(rio_gp* h, u32 m) { return h->cutapply_mode != 2 && !h->sb.forced_bits && cut_apply_fits(m); }
-// ... which it is when the solve packs at the cut pass (few rows go on to the water-fill: the ranges with work are a fraction of
-// the table and k_cut_apply deals them out over the chip); a solve that re-marks most of the table keeps the two-pass form
-bool cut_apply_for(rio_gp* h, bool cutpack) {
-    return use_cut_apply(h, h->m) && (h->cutapply_mode == 1 || (cutpack && h->rounds >= 1 && fill_can_pack(h->m)));
+// a change of the solve's inputs: the solve waiting for its commit no longer describes them, and no tick is quiet any more
+void inputs_changed(rio_gp* h) {
+    h->pending = PendingSolve{};
+    ++h->mut_epoch;
+}
+
+// The form of one solve of the real table (h->plan is that table's, mark included), from the handle's knobs and statistics and
+// from what the caller knows:
+//   commit   the solve is published in this call (a tick)
+//   sync     this call reads the verdict on the host (rio_gp_solve, rio_gp_tick): only those calls keep last_fix_* current
+//   quiet    nothing has changed since a tick that left every object placed: no fix-up can be needed
+//   chained  ... and the tick is the chained k_scan alone, a link of a run
+// This is the only place where compact_mode, cutpack_mode, inc_mode, cutapply_mode, last_pending* and last_fix_* choose a form.
+// spec_mode and chain_mode stay with their readers: spec_mode decides WHEN solve_locked enqueues the fix-up, which shapes that
+// function's host waits and nothing of the form; chain_mode is one of tick_async_locked's conditions for a link of a run, next
+// to the stream's and the table's, and must be decided before the run is joined — `chained` is its outcome.
+SolveForm solve_form(const rio_gp* h, bool commit, bool sync, bool quiet = false, bool chained = false) {
+    SolveForm f;
+    f.fix_plan = h->plan;
+    f.pkx = &h->pk;
+    if (chained) return f;  // (nothing packs, nothing searches, k_scan maintains no rejected-load tables)
+    // Adaptive packed fix-up: when the previous solve left few rows pending — but some: a stream without churn keeps the
+    // plain scan, two tiles in flight — (a churn stream: most rows are kept),
+    // k_scan also packs this solve's pending rows per wave, and — if the verdict then asks for the fix-up — the cut
+    // and water-fill kernels run over the packed rows only (O(pending) passes instead of O(rows)); results identical.
+    // (A solve that is neither published nor waited for here — rio_gp_solve_async — gets its fix-up from a later call, over
+    // the table as it is then: it packs nothing.)
+    f.compact = !quiet && (commit || sync) &&
+                (h->compact_mode == 1 ||
+                 (h->compact_mode == 0 && h->last_pending_valid && h->last_pending > 0 && h->last_pending * 4 <= h->n && h->n >= 65536));
+    // Packing at the cut pass: a whole-table solve (nothing known to be kept) whose previous solve sent few rows to the
+    // water-fill — a contended table re-solved: ~10 % of the rows — lets round 0 of k_fill pack those rows on its way, and
+    // the later rounds run over them instead of streaming the table again.  Results identical.
+    f.cutpack = sync && !f.compact && h->rounds >= 1 && fill_can_pack(h->m) &&
+                (h->cutpack_mode == 1 || (h->cutpack_mode == 0 && h->last_fix_valid && h->last_fix_rows * 4 <= h->n && h->n >= 65536));
+    // ... and when the tick is committed and the library's `used` vector is valid, the scan streams the assignment column
+    // alone and works in place (k_inc_scan + k_rebal).  Only a COMMITTED tick may work in place, only a
+    // valid `used` vector can stand in for the kept histogram, and the rings of pending rows must fit the LDS next to the
+    // liveness bitmap.
+    // (Tables whose blocks are beyond the in-resolve cut search — config 4 on one GPU, 390 K rows a block — take this path too:
+    // 100 M x 4 096, three boxes, same-run A/B: 700-720 us pipelined against 734-797 with k_scan<COMPACT>; round 0 of the
+    // water-fill alone is 60-90 us shorter over the balanced rows.  The cut search stays k_cut_find's launch there.)
+    if (f.compact && commit && h->used_valid && h->inc_mode != 2 && inc_scan_fits(h->m) && h->m != 0) {
+        f.inc = 2;
+        f.fix_plan = rebal_plan(h->plan);
+        f.pkx = &h->pk2;
+    }
+    f.fix_plan.wcnt = f.compact ? f.pkx->wcnt : nullptr;
+    // The whole-table fix-up is k_cut_apply when the solve packs at the cut pass (few rows go on to the water-fill: the ranges
+    // with work are a fraction of the table and k_cut_apply deals them out over the chip); a solve that re-marks most of the
+    // table keeps the two-pass form.  Never over packed rows (f.inc implies f.compact).
+    f.cut_apply = !f.compact && h->cutapply_mode != 2 && !h->sb.forced_bits && cut_apply_fits(h->m) && (h->cutapply_mode == 1 || f.cutpack);
+    // The exact cut search rides in k_resolve when a block's packed rows are few enough for a wave pair per node to stream
+    // (config 3: 39 K rows a block, 18 us against 6 + 14 for a resolve and a search launch of their own); on big blocks
+    // (config 4 on one GPU: 390 K rows, ~39 K packed) a wave pair per node takes 91 us where k_cut_find's (block, node slice)
+    // work items spread over the chip take 36: there the search stays a launch of its own.
+    f.resolve_searches = f.compact && h->plan.G && h->n / h->plan.G <= kSearchMaxBlockRows;
+    return f;
 }
 
 // The fix-up of a solve whose fast path said it needs one (or may need one: every kernel here guards itself on the
 // device, so the sequence can be enqueued before the host has read the verdict):
-//   the exact cut search — k_cut_find, unless launch_resolve already searched (packed pending rows: `searched`);
+//   the exact cut search — k_cut_find, unless launch_resolve already searched (packed pending rows: f.resolve_searches);
 //   round 0 = k_fill<APPLY, FILL> (re-mark + water-fill; cutpack: it also packs the rows that go on to the water-fill, and
 //   the later rounds run over those rows only); rounds 1.. = k_fill<FILL>.
-void enqueue_slow(rio_gp* h, const Plan& p, const Table& t, const NodeTab& nt, bool virt, bool searched, bool cutpack = false) {
-    cutpack = cutpack && !virt && !p.wcnt && h->rounds >= 1 && fill_can_pack(p.m);
+// A virtual table (the request path) runs the plain form: SolveForm{}.
+void enqueue_slow(rio_gp* h, const SolveForm& f, const Plan& p, const Table& t, const NodeTab& nt, bool virt) {
+    const bool cutpack = f.cutpack && !virt && !p.wcnt;
     // Whole-table solve of the real table: ONE pass finds the exact cuts, re-marks and (cutpack) packs — k_cut_apply — and
     // every round, the first included, is a plain water-fill round (over the packed rows / over the table).
-    if (!virt && !searched && !p.wcnt && h->ca_now) {
+    if (!virt && !f.resolve_searches && !p.wcnt && f.cut_apply) {
         launch_cut_apply(p, t, nt, h->sb, h->pk, h->pk2, h->Tg, cutpack, h->all_alive, h->stream);
         if (cutpack) {
             Plan pp = p;
@@ -493,7 +560,7 @@ void enqueue_slow(rio_gp* h, const Plan& p, const Table& t, const NodeTab& nt, b
         }
         return;
     }
-    if (!searched) launch_cut_find(p, t, nt, h->sb, virt, h->stream, true);
+    if (!f.resolve_searches) launch_cut_find(p, t, nt, h->sb, virt, h->stream, true);
     launch_fill(p, t, nt, h->sb, virt, true, true, 0, h->rounds == 1, h->stream, cutpack ? &h->pk : nullptr);
     if (cutpack) {
         Plan pp = p;
@@ -517,52 +584,34 @@ void fold_used(rio_gp* h) {
     h->used_parts = false;
 }
 // scan + resolve of one solve over the REAL table: the packed pending rows' cuts are searched inside k_resolve, the previous
-// committed solve's D rows are folded into the committed vector before k_resolve zeroes them
-void enqueue_scan_resolve(rio_gp* h, const Table& t, const NodeTab& nt, bool compact, u64* host_rows, int inc = 0) {
+// committed solve's D rows are folded into the committed vector before k_resolve zeroes them.  Returns what the solve is once
+// it waits for its commit; the enqueue functions keep nothing of a solve on the handle themselves.
+PendingSolve enqueue_scan_resolve(rio_gp* h, const SolveForm& f, const Table& t, const NodeTab& nt, u64* host_rows) {
     h->sb.D = h->D;
-    h->solve_used_D = h->sb.D != nullptr;
-    h->inc_now = inc;
-    h->solve_inplace = inc != 0;
-    const PackOut& pkx = inc == 2 ? h->pk2 : h->pk;  // where the fix-up finds the packed rows
-    h->vplan = h->plan;
     // a whole-table fix-up by k_cut_apply takes its ordered spill totals from its own pass: k_scan / k_resolve need not
     // maintain the rejected-load tables R / RP (k_resolve: one prefix over the blocks per node group that owns a cut)
     SolveBufs rb = h->sb;
-    h->ca_now = h->ca_now && !compact && !inc;
-    if (h->ca_now) { rb.R = nullptr; rb.RP = nullptr; rb.Tg = h->Tg; }
-    if (inc) {
+    if (f.cut_apply) { rb.R = nullptr; rb.RP = nullptr; rb.Tg = h->Tg; }
+    if (f.inc) {
         // (t.cur is read AND written: the tick is committed, nobody is promised the table as it was)
         launch_inc_scan(h->plan, h->assign[h->cur], h->load, h->aff, nt, h->sb, h->pk, h->stream);
-        h->vplan = rebal_plan(h->plan);
-        launch_rebal(h->plan, h->vplan, h->pk, nt, h->pk2, h->sb, h->stream);
+        launch_rebal(h->plan, f.fix_plan, h->pk, nt, h->pk2, h->sb, h->stream);
     } else {
-        launch_scan(h->plan, t, nt, rb, false, h->all_alive, h->stream, nullptr, nullptr, compact ? &h->pk : nullptr);
+        launch_scan(h->plan, t, nt, rb, false, h->all_alive, h->stream, nullptr, nullptr, f.compact ? &h->pk : nullptr);
     }
-    h->vplan.wcnt = compact ? pkx.wcnt : nullptr;
-    // The exact cut search rides in k_resolve when a block's packed rows are few enough for a wave pair per node to stream
-    // (config 3: 39 K rows a block, 18 us against 6 + 14 for a resolve and a search launch of their own); on big blocks
-    // (config 4 on one GPU: 390 K rows, ~39 K packed) a wave pair per node takes 91 us where k_cut_find's (block, node slice)
-    // work items spread over the chip take 36: there the search stays a launch of its own.
-    h->searched = compact && h->plan.G && h->n / h->plan.G <= kSearchMaxBlockRows;
-    Plan rp = h->vplan;
-    if (!h->searched) rp.wcnt = nullptr;
-    launch_resolve(rp, nt, rb, host_rows, h->stream, nullptr, nullptr, h->searched ? &pkx : nullptr,
-                   h->used_parts ? h->used : nullptr, h->parts_rounds, inc ? h->used : nullptr, parts_src(h));
+    Plan rp = f.fix_plan;
+    if (!f.resolve_searches) rp.wcnt = nullptr;
+    launch_resolve(rp, nt, rb, host_rows, h->stream, nullptr, nullptr, f.resolve_searches ? f.pkx : nullptr,
+                   h->used_parts ? h->used : nullptr, h->parts_rounds, f.inc ? h->used : nullptr, parts_src(h));
     h->used_parts = false;
+    return PendingSolve{true, f.inc != 0, h->sb.D != nullptr, nullptr};
 }
 u64* used_slot(rio_gp* h, u32 q) { return h->used_ring + (size_t)(q % kUsedRing) * h->used_slot_words; }
 // A quiet tick as one link of a chained run: the chained k_scan alone (ScanChain, placement_kernels.h) — its workgroups add the
 // kept loads into this link's `used` buffer and store the tick's verdict rows (`rows`, one per workgroup) themselves.  Nothing of
 // the fix-up's scratch is written; the vector it builds replaces the committed one whole (commit_enqueue: its replicas 1.. are
 // folded into replica 0 later, like a solve's D rows — whatever D rows were pending are superseded).
-void enqueue_chained(rio_gp* h, const Table& t, const NodeTab& nt, u64* rows) {
-    h->solve_used_D = false;
-    h->inc_now = 0;
-    h->solve_inplace = false;
-    h->ca_now = false;
-    h->searched = false;
-    h->vplan = h->plan;
-    h->vplan.wcnt = nullptr;
+PendingSolve enqueue_chained(rio_gp* h, const Table& t, const NodeTab& nt, u64* rows) {
     hipStream_t ss = h->stream;
     ScanChain ch{h->chain_flags, h->d_chain_err};
     if (!h->chain_prev) {
@@ -587,16 +636,16 @@ void enqueue_chained(rio_gp* h, const Table& t, const NodeTab& nt, u64* rows) {
     SolveBufs rb = h->sb;
     rb.R = nullptr; rb.RP = nullptr; rb.Tg = nullptr;
     launch_scan(h->plan, t, nt, rb, false, h->all_alive, ss, nullptr, nullptr, nullptr, &ch);
-    h->solve_used = ch.used;
+    return PendingSolve{true, false, false, ch.used};
 }
 // the fix-up over the rows the scan packed (compact): the water-fill writes every decision through the packed rows' indices
 // into the real column itself — the other assignment column, or (k_inc_scan) the committed one
-void enqueue_slow_packed(rio_gp* h, const NodeTab& nt) {
-    const PackOut& pkx = h->inc_now == 2 ? h->pk2 : h->pk;
+void enqueue_slow_packed(rio_gp* h, const SolveForm& f, const NodeTab& nt) {
+    const PackOut& pkx = *f.pkx;
     Table vt{h->pos /* all-NONE column: every packed row is pending */, pkx.load, pkx.aff, pkx.next};
     vt.pk_idx = pkx.idx;
-    vt.real_next = h->solve_inplace ? h->assign[h->cur] : h->assign[h->cur ^ 1];
-    enqueue_slow(h, h->vplan, vt, nt, true, h->searched, false);
+    vt.real_next = f.inc ? h->assign[h->cur] : h->assign[h->cur ^ 1];
+    enqueue_slow(h, f, f.fix_plan, vt, nt, true);
 }
 
 u64* slot_dev(rio_gp* h, u32 k) { return h->d_slots + (size_t)(k % kRing) * h->slot_rows * 8; }
@@ -664,28 +713,23 @@ int merge_slow(rio_gp* h, DevStats* v) {
 }
 
 // A solve that works in place (k_inc_scan) has rewritten part of the committed column by the time anything behind it can
-// fail.  If the call does not reach its commit, the flags must not outlive it (a later solve that does not pass through
-// enqueue_scan_resolve — the row-sharded calls, rio_gp_solve_wait + rio_gp_commit — would skip its column swap and publish a
-// stale column), and the table is no longer what the `used` vector and the pending-row statistics describe: the next tick
-// re-solves it from scratch (plain k_scan: the kept histogram is rebuilt from the rows).
+// fail.  If the call does not reach its end, the solve is abandoned, and the table is no longer what the `used` vector and
+// the pending-row statistics describe: the next tick re-solves it from scratch (plain k_scan: the kept histogram is rebuilt
+// from the rows).
 struct InplaceGuard {
     rio_gp* h;
     bool ok = false;
     ~InplaceGuard() {
         if (ok) return;
-        if (h->solve_inplace) { h->used_valid = false; h->used_parts = false; h->last_pending_valid = false; h->last_fix_valid = false; }
-        h->solve_inplace = false;
-        h->inc_now = 0;
-        h->have_solved = false;
-        h->solve_used = nullptr;
+        if (h->pending.inplace) { h->used_valid = false; h->used_parts = false; h->last_pending_valid = false; h->last_fix_valid = false; }
+        h->pending = PendingSolve{};
     }
 };
-// every solve entry point that does not go through enqueue_scan_resolve starts from "not in place"
-void reset_inplace(rio_gp* h) { h->solve_inplace = false; h->inc_now = 0; }
 
 int commit_enqueue(rio_gp* h) {
-    if (!h->have_solved) return fail(h, RIO_GP_EINVAL, "rio_gp_commit: no solve to commit");
-    if (!h->solve_inplace) {  // (k_inc_scan and its fix-up wrote the committed column itself)
+    const PendingSolve ps = h->pending;
+    if (!ps.have) return fail(h, RIO_GP_EINVAL, "rio_gp_commit: no solve to commit");
+    if (!ps.inplace) {  // (k_inc_scan and its fix-up wrote the committed column itself)
         // rows >= n keep their contents (rio_gp_set_num_objects), and a solve writes rows < n of the other column only: the rows
         // above n that were ever in use go over with the swap.  Nothing to copy while n is at its high-water mark (the string
         // layer, every table that does not shrink).
@@ -694,33 +738,21 @@ int commit_enqueue(rio_gp* h) {
                                      hipMemcpyDeviceToDevice, h->stream));
         h->cur ^= 1;
     }
-    h->solve_inplace = false;
     h->used_valid = true;
-    if (h->solve_used) {  // a chained tick: its buffer of the ring becomes the committed vector, the last committed one the solve's scratch
+    if (ps.used) {  // a chained tick: its buffer of the ring becomes the committed vector, the last committed one the solve's scratch
         h->sb.used_cur = h->used;
-        h->used = h->solve_used;
-        h->solve_used = nullptr;
+        h->used = ps.used;
         h->parts = h->used + h->m;  // ... plus its other replicas, folded in later
         h->parts_rounds = kChainReps - 1;
         h->used_parts = true;
     } else {
         std::swap(h->used, h->sb.used_cur);  // publication = two pointer swaps: the solve's `used` vector becomes the committed one
-        h->used_parts = h->solve_used_D;     // ... plus what its water-fill rounds admitted (D rows), folded in later
+        h->used_parts = ps.used_D;           // ... plus what its water-fill rounds admitted (D rows), folded in later
         h->parts_rounds = h->rounds;
         h->parts = nullptr;
     }
-    h->have_solved = false;  // (not an input change: mut_epoch stays)
+    h->pending = PendingSolve{};  // (consumed; not an input change: mut_epoch stays)
     return RIO_GP_OK;
-}
-
-// 0 k_scan | 2 k_inc_scan + k_rebal.  Only a COMMITTED tick may work in place, only a valid `used` vector can stand in for
-// the kept histogram, and the rings of pending rows must fit the LDS next to the liveness bitmap.
-int inc_choice(rio_gp* h, bool compact, bool commit) {
-    if (!compact || !commit || !h->used_valid || h->inc_mode == 2 || !inc_scan_fits(h->m) || h->m == 0) return 0;
-    // (Tables whose blocks are beyond the in-resolve cut search — config 4 on one GPU, 390 K rows a block — take this path too:
-    // 100 M x 4 096, three boxes, same-run A/B: 700-720 us pipelined against 734-797 with k_scan<COMPACT>; round 0 of the
-    // water-fill alone is 60-90 us shorter over the balanced rows.  The cut search stays k_cut_find's launch there.)
-    return 2;
 }
 
 // One whole-table solve; with `commit` the publication (two pointer swaps) happens before the last wait.
@@ -738,27 +770,13 @@ int solve_locked(rio_gp* h, rio_gp_stats* stats, bool commit = false) {
     if (fx_last) h->sb.fx.seq = seq;
     const Table t = real_table(h);
     const NodeTab nt = scan_nodes(h);
-    // Adaptive packed fix-up: when the previous solve left few rows pending — but some: a stream without churn keeps the
-    // plain scan, two tiles in flight — (a churn stream: most rows are kept),
-    // k_scan also packs this solve's pending rows per wave, and — if the verdict then asks for the fix-up — the cut
-    // and water-fill kernels run over the packed rows only (O(pending) passes instead of O(rows)); results identical.
-    const bool compact = h->compact_mode == 1 ||
-                         (h->compact_mode == 0 && h->last_pending_valid && h->last_pending > 0 && h->last_pending * 4 <= h->n && h->n >= 65536);
     // Speculative fix-up: when the previous solve needed the fix-up (a churn stream needs it every tick), its kernels
     // are enqueued right behind k_resolve instead of after a host round trip for the verdict.  Every fix-up kernel
     // guards itself on device (the cut search: stats->n_cut; the water-fill rounds: pending-row count), so a solve that
     // turns out not to need them pays a few no-op launches and gets the same result.
     const bool spec = h->spec_mode != 2 && (h->spec_mode == 1 || h->last_slow);
-    // Packing at the cut pass: a whole-table solve (nothing known to be kept) whose previous solve sent few rows to the
-    // water-fill — a contended table re-solved: ~10 % of the rows — lets round 0 of k_fill pack those rows on its way, and
-    // the later rounds run over them instead of streaming the table again.  Results identical.
-    const bool cutpack = !compact && (h->cutpack_mode == 1 ||
-                                      (h->cutpack_mode == 0 && h->last_fix_valid && h->last_fix_rows * 4 <= h->n && h->n >= 65536));
-    // ... and when the tick is committed and the library's `used` vector is valid, the scan streams the assignment column
-    // alone and works in place (k_inc_scan)
-    const int inc = inc_choice(h, compact, commit);
-    h->ca_now = cut_apply_for(h, cutpack);
-    enqueue_scan_resolve(h, t, nt, compact, slot_dev(h, 0), inc);
+    const SolveForm f = solve_form(h, commit, true);
+    h->pending = enqueue_scan_resolve(h, f, t, nt, slot_dev(h, 0));  // (a call that fails from here on abandons it: InplaceGuard)
     DevStats v;
     bool slow = false;
     const u64* vrows = h->h_slots;  // slot 0 of the solve ring
@@ -768,10 +786,9 @@ int solve_locked(rio_gp* h, rio_gp_stats* stats, bool commit = false) {
         slow = v.n_cut > 0 || v.spillcand > 0;
     }
     if (spec || slow) {
-        if (compact) enqueue_slow_packed(h, nt);
-        else enqueue_slow(h, h->plan, t, nt, false, false, cutpack);
+        if (f.compact) enqueue_slow_packed(h, f, nt);
+        else enqueue_slow(h, f, h->plan, t, nt, false);
     }
-    h->have_solved = true;
     h->ring_n = 0; h->ring_slow = 0; h->ring_any = false;
     if (commit) {
         int rc = commit_enqueue(h);
@@ -796,8 +813,6 @@ int solve_locked(rio_gp* h, rio_gp_stats* stats, bool commit = false) {
     ipg.ok = true;
     return RIO_GP_OK;
 }
-
-int commit_locked(rio_gp* h) { return commit_enqueue(h); }
 
 // wait for the asynchronous ticks in flight and turn their verdict slots + device-stats copies into rio_gp_stats
 // verdicts of enqueued ticks that have already landed in their pinned slots (every row carries the tick's mark): no wait
@@ -890,8 +905,6 @@ int tick_async_locked(rio_gp* h) {
     h->plan = hplan(h, h->n);
     const Table t = real_table(h);
     const NodeTab nt = scan_nodes(h);
-    const bool compact = !quiet && (h->compact_mode == 1 ||
-                         (h->compact_mode == 0 && h->last_pending_valid && h->last_pending > 0 && h->last_pending * 4 <= h->n && h->n >= 65536));
     const u32 k = h->tick_n;
     use_fx_slot(h, 1 + k);
     h->tick_G[k] = h->plan.G;
@@ -900,20 +913,15 @@ int tick_async_locked(rio_gp* h) {
     h->tick_mark[k] = h->plan.mark = (1ull << 40) | ++h->wait_seq;  // column 7 of the verdict rows: peek_ticks knows them by it
     u64* const rows = h->d_slots + (size_t)(kTickSlot0 + k) * h->slot_rows * 8;
     h->tick_rows[k] = chained ? h->plan.G : resolve_blocks(h->m);
-    if (chained) {
-        enqueue_chained(h, t, nt, rows);
-    } else {
-        h->ca_now = cut_apply_for(h, false);
-        enqueue_scan_resolve(h, t, nt, compact, rows, inc_choice(h, compact, true));
-    }
+    const SolveForm f = solve_form(h, true, false, quiet, chained);
+    h->pending = chained ? enqueue_chained(h, t, nt, rows) : enqueue_scan_resolve(h, f, t, nt, rows);
     if (quiet) {
         // (the chained scan, or k_scan + k_resolve)
-    } else if (compact) {
-        enqueue_slow_packed(h, nt);
+    } else if (f.compact) {
+        enqueue_slow_packed(h, f, nt);
     } else {
-        enqueue_slow(h, h->plan, t, nt, false, false);
+        enqueue_slow(h, f, h->plan, t, nt, false);
     }
-    h->have_solved = true;
     int rc = commit_enqueue(h);
     if (rc) return rc;
     HIPCHK(h, hipGetLastError());
@@ -1208,7 +1216,7 @@ int rio_gp_set_flags(rio_gp_t* h, uint32_t flags) {
     if ((flags & ~RIO_GP_CFG_REF_SELF_ASSIGN) != fixed) return fail(h, RIO_GP_EINVAL, "rio_gp_set_flags: only RIO_GP_CFG_REF_SELF_ASSIGN may change");
     const u32 sa = (flags & RIO_GP_CFG_REF_SELF_ASSIGN) ? 1u : 0u;
     if (sa && (h->p2p || h->sc)) return fail(h, RIO_GP_EINVAL, "rio_gp_set_flags: row-sharded handles do not implement RIO_GP_CFG_REF_SELF_ASSIGN");
-    if (sa != h->sa) { h->sa = sa; h->have_solved = false; ++h->mut_epoch; }
+    if (sa != h->sa) { h->sa = sa; inputs_changed(h); }
     return RIO_GP_OK;
 }
 
@@ -1244,7 +1252,7 @@ int rio_gp_set_nodes(rio_gp_t* h, uint32_t m, const uint64_t* cap, const uint8_t
     for (uint32_t j = 0; j < m; ++j) h->all_alive = h->all_alive && h->h_alive[j];
     if (m != h->m) { h->used_valid = false; h->used_parts = false; }
     h->m = m;
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     return RIO_GP_OK;
 }
 
@@ -1264,7 +1272,7 @@ static int push_alive_bits(rio_gp* h) {
     }
     std::atomic_thread_fence(std::memory_order_release);
     h->alive_dirty = true;
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     return RIO_GP_OK;
 }
 
@@ -1317,7 +1325,7 @@ static int set_objects_impl(rio_gp_t* h, uint64_t n, const uint32_t* load, const
     h->n_hi = std::max<u64>(h->n_hi, n);
     h->used_valid = true;
     h->used_parts = false;
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     return RIO_GP_OK;
 }
 int rio_gp_set_objects(rio_gp_t* h, uint64_t n, const uint32_t* load, const uint32_t* aff) {
@@ -1339,7 +1347,7 @@ static int set_assign_impl(rio_gp_t* h, uint64_t n, const uint32_t* assign, hipM
     if (n) HIPCHK(h, hipMemcpyAsync(h->assign[h->cur], assign, n * sizeof(u32), kind, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->used_valid = false;
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     return RIO_GP_OK;
 }
 int rio_gp_set_assign(rio_gp_t* h, uint64_t n, const uint32_t* a) { return set_assign_impl(h, n, a, hipMemcpyHostToDevice); }
@@ -1357,7 +1365,7 @@ int rio_gp_get_assign(rio_gp_t* h, uint64_t n, uint32_t* out) {
 int rio_gp_get_solved(rio_gp_t* h, uint64_t n, uint32_t* out) {
     if (!h || !out) return RIO_GP_EINVAL;
     Locked g(h);
-    if (n != h->n || !h->have_solved) return fail(h, RIO_GP_EINVAL, "rio_gp_get_solved: no solve / size mismatch");
+    if (n != h->n || !h->pending.have) return fail(h, RIO_GP_EINVAL, "rio_gp_get_solved: no solve / size mismatch");
     HIPCHK(h, hipSetDevice(h->device));
     if (n) HIPCHK(h, hipMemcpyAsync(out, h->assign[h->cur ^ 1], n * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1390,7 +1398,7 @@ int rio_gp_set_object_attrs(rio_gp_t* h, uint64_t n, const uint32_t* idx, const 
     launch_set_attrs(h->load, h->aff, h->n, (const u32*)h->stage[0].p, load ? (const u32*)h->stage[1].p : nullptr,
                      aff ? (const u32*)h->stage[2].p : nullptr, n, h->dstats, h->stream);
     if (load) h->used_valid = false;
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     return read_stats(h);
 }
 
@@ -1523,7 +1531,7 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 roun
     if (n_moves) *n_moves = 0;
     HIPCHK(h, hipSetDevice(h->device));
     // a change of the inputs, like every CRUD call: an uncommitted solve is dropped, the next tick is neither quiet nor chained
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     const u32 m = h->m, M = h->cap_nodes;
     const u64 n = h->n;
     // per-node arrays: pin | tgt (0 on dead nodes) | slot_free | C [M + 1] | acc [kShAcc] (u64), then map | slot_node | cut |
@@ -1806,7 +1814,7 @@ int rio_gp_set_num_objects(rio_gp_t* h, uint64_t n) {
     if (n != h->n) h->used_valid = false;
     h->n = n;
     h->n_hi = std::max<u64>(h->n_hi, n);
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     h->last_pending_valid = false;
     return RIO_GP_OK;
 }
@@ -1887,13 +1895,13 @@ static int update_dev_locked(rio_gp* h, uint64_t n, const uint32_t* d_idx, const
         if ((rc = ensure(h, h->part, part_scratch_words(h->n, n) * sizeof(u32)))) return rc;
         launch_update_part(h->assign[h->cur], h->n, h->m, d_idx, d_node, n, (u32*)h->part.p, h->dstats, h->stream, aff_life(h));
         h->used_valid = false;
-        h->have_solved = false; ++h->mut_epoch;
+        inputs_changed(h);
         return finish_err(h, "rio_gp_update_batch: invalid entries were skipped");
     } else {
         launch_update(h->assign[h->cur], h->n, h->m, d_idx, d_node, n, h->pos, h->dstats, h->stream, aff_life(h));
     }
     h->used_valid = false;
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     if ((rc = read_stats(h))) return rc;
     if (h->h_stats[0].err) return fail(h, RIO_GP_EINVAL, "rio_gp_update_batch: invalid entries were skipped");
     return RIO_GP_OK;
@@ -1930,7 +1938,7 @@ int rio_gp_update_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint
         fold_used(h);
         launch_update_small(h->assign[h->cur], h->d_small, h->d_small + kSmallBatch, (u32)n, h->stream, aff_life(h),
                             small_done_dev(h), seq, in_args ? &inl : nullptr, h->used_valid ? h->used : nullptr, h->load, h->m);
-        h->have_solved = false; ++h->mut_epoch;
+        inputs_changed(h);
         return small_wait(h, seq);
     }
     if (n <= (uint64_t)kMidBatch) {
@@ -1942,7 +1950,7 @@ int rio_gp_update_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint
         fold_used(h);
         launch_update(h->assign[h->cur], h->n, h->m, h->d_mid, h->d_mid + kMidBatch, n, h->pos, h->dstats, h->stream, aff_life(h),
                       h->mid_ticket, small_done_dev(h), seq, h->used_valid ? h->used : nullptr, h->load);
-        h->have_solved = false; ++h->mut_epoch;
+        inputs_changed(h);
         return small_wait(h, seq);
     }
     if ((rc = ensure(h, h->stage[0], n * sizeof(u32))) || (rc = ensure(h, h->stage[1], n * sizeof(u32)))) return rc;
@@ -1959,13 +1967,13 @@ static int remove_dev_locked(rio_gp* h, uint64_t n, const uint32_t* d_idx) {
         if ((rc = ensure(h, h->part, part_scratch_words(h->n, n) * sizeof(u32)))) return rc;
         launch_remove_part(h->assign[h->cur], h->n, h->m, h->load, d_idx, n, (u32*)h->part.p, h->used_valid ? h->used : nullptr,
                            h->dstats, h->stream, aff_life(h));
-        h->have_solved = false; ++h->mut_epoch;
+        inputs_changed(h);
         return finish_err(h, "rio_gp_remove_batch: invalid entries were skipped");
     } else {
         launch_remove(h->assign[h->cur], h->n, h->m, h->load, d_idx, n, h->used_valid ? h->used : nullptr, h->dstats,
                       h->stream, aff_life(h));
     }
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     if ((rc = read_stats(h))) return rc;
     if (h->h_stats[0].err) return fail(h, RIO_GP_EINVAL, "rio_gp_remove_batch: invalid entries were skipped");
     return RIO_GP_OK;
@@ -1994,7 +2002,7 @@ int rio_gp_remove_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx) {
         fold_used(h);
         launch_remove_small(h->assign[h->cur], h->m, h->load, h->d_small, (u32)n, h->used_valid ? h->used : nullptr, h->stream,
                             aff_life(h), small_done_dev(h), seq, in_args ? &inl : nullptr);
-        h->have_solved = false; ++h->mut_epoch;
+        inputs_changed(h);
         return small_wait(h, seq);
     }
     if (n <= (uint64_t)kMidBatch) {  // medium batch, validated above: as update_batch
@@ -2003,7 +2011,7 @@ int rio_gp_remove_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx) {
         fold_used(h);
         launch_remove(h->assign[h->cur], h->n, h->m, h->load, h->d_mid, n, h->used_valid ? h->used : nullptr, h->dstats,
                       h->stream, aff_life(h), small_done_dev(h), seq, nullptr, h->mid_ticket);
-        h->have_solved = false; ++h->mut_epoch;
+        inputs_changed(h);
         return small_wait(h, seq);
     }
     if ((rc = ensure(h, h->stage[0], n * sizeof(u32)))) return rc;
@@ -2026,7 +2034,7 @@ int rio_gp_clean_servers(rio_gp_t* h, const uint64_t* dead_bitmap, uint64_t* evi
     for (u32 w = 0; w < words32; ++w) h->h_cs[w] = 0;
     for (u32 j = 0; j < h->m; ++j)
         if ((dead_bitmap[j >> 6] >> (j & 63)) & 1ull) { h->h_cs[j >> 5] |= 1u << (j & 31); any = true; }
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     if (!any || h->n == 0) return RIO_GP_OK;  // retain() with a predicate nothing matches, or over an empty map
     const u32 seq = (small_begin(h) & 0xFFFFFFu) | 0x800000u;  // 24 bits, never 0
     fold_used(h);  // (k_clean zeroes the dead nodes' entries: what the last solve's rounds admitted there must be in first)
@@ -2094,7 +2102,7 @@ int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* map, uint64_
     HIPCHK(h, hipSetDevice(h->device));
     if (evicted) *evicted = 0;
     // a change of the inputs, like every CRUD call: an uncommitted solve is dropped, the next tick is neither quiet nor chained
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     h->last_pending_valid = false;
     int rc;
     u32 G = 0;
@@ -2190,7 +2198,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
         HIPCHK(h, hipGetLastError());
         if (*h_bad || *h_status == 3) return fail(h, RIO_GP_EINVAL, std::string(who) + ": object index or requester out of range (nothing was changed)");
         if (*h_status == 1) {  // final: `used` has taken the claims in place
-            h->have_solved = false; ++h->mut_epoch;
+            inputs_changed(h);
             return RIO_GP_OK;
         }
         if (*h_status != 2) return fail(h, RIO_GP_EUPSTREAM, std::string(who) + ": the window kernels left no verdict");
@@ -2214,7 +2222,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
         h->sb.D = h->D;
         launch_scan(vp, vtab, vnt, h->sb, true, h->all_alive, h->stream);
         launch_resolve(vp, vnt, h->sb, slot_dev(h, 0), h->stream);
-        enqueue_slow(h, vp, vtab, vnt, true, false);  // ahead of the verdict: its kernels guard themselves on the device
+        enqueue_slow(h, SolveForm{}, vp, vtab, vnt, true);  // ahead of the verdict: its kernels guard themselves on the device
         launch_pp_win_output(d_idx, d_req, n, vcur, vload, vnext, h->alive_bits, h->sb.cutidx, h->m, d_out, d_flag, aff_life(h), h->dstats,
                              h->stream, h->sa, (const uint2*)h->vrec.p);
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2225,7 +2233,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
         h->used_parts = vslow;
         h->parts_rounds = h->rounds;
         h->parts = nullptr;
-        h->have_solved = false; ++h->mut_epoch;
+        inputs_changed(h);
         return RIO_GP_OK;
     }
     // The library's own (padded) copies of the requests, made by the first kernel on its way: requests in mapped host memory
@@ -2264,14 +2272,14 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
     // the fix-up ahead of the verdict when the last batch needed it (its kernels guard themselves on the device); otherwise the
     // output kernel finds out on the device and hands back status 1 having changed nothing
     bool fixed = h->spec_mode != 2 && (h->spec_mode == 1 || h->pp_last_slow);
-    if (fixed) enqueue_slow(h, vp, vtab, vnt, true, false);
+    if (fixed) enqueue_slow(h, SolveForm{}, vp, vtab, vnt, true);
     // (5) publish, outputs, scratch reset, completion word
     u32 seq = small_begin(h);
     launch_ppm_output(assign, h->n, k_idx, k_req, n, vcur, vnext, vaff, vflag, h->pos, h->alive_bits, h->sb, vp, d_out, d_flag,
                       aff_life(h), h->pp_bad, fixed, d_status, h->mid_ticket, small_done_dev(h), seq, h->stream);
     if ((rc = small_wait(h, seq))) return rc;
     if (*h_status == 1 && !fixed) {
-        enqueue_slow(h, vp, vtab, vnt, true, false);
+        enqueue_slow(h, SolveForm{}, vp, vtab, vnt, true);
         fixed = true;
         *h_status = 2;
         seq = small_begin(h);
@@ -2289,7 +2297,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
     h->used_parts = vslow && h->sb.D != nullptr;  // + what the water-fill rounds admitted (D rows), folded in later
     h->parts_rounds = h->rounds;
     h->parts = nullptr;
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     return RIO_GP_OK;
 }
 
@@ -2343,7 +2351,7 @@ static int place_pending_host_locked(rio_gp* h, uint64_t n, const uint32_t* idx,
         if (status == 0) {
             memcpy(out_node, hs + 2 * kSmallBatch, n * sizeof(u32));
             if (out_flag) memcpy(out_flag, hs + 3 * kSmallBatch, n * sizeof(u32));
-            h->have_solved = false; ++h->mut_epoch;
+            inputs_changed(h);
             return RIO_GP_OK;
         }
         if (status != 1) return fail(h, RIO_GP_EUPSTREAM, "rio_gp_place_pending: micro-batch kernel left no status");
@@ -2371,7 +2379,7 @@ static int place_pending_host_locked(rio_gp* h, uint64_t n, const uint32_t* idx,
             if (status == 0) {
                 memcpy(out_node, hm + 2 * kMidBatch, bytes);
                 if (out_flag) memcpy(out_flag, hm + 3 * kMidBatch, bytes);
-                h->have_solved = false; ++h->mut_epoch;
+                inputs_changed(h);
                 return RIO_GP_OK;
             }
             if (status != 1) return fail(h, RIO_GP_EUPSTREAM, "rio_gp_place_pending: one-workgroup kernel left no status");
@@ -2502,7 +2510,7 @@ int rio_gp_mixed_batch(rio_gp_t* h, rio_gp_mixed* ops) {
             if (small_inline(&il, nl, ops->lookup_idx, nullptr)) c.l_inl = &il;
             else memcpy(hm + 3 * kSmallBatch, ops->lookup_idx, nl * sizeof(u32));
         }
-        if (run[0] || run[1] || run[3]) { h->have_solved = false; ++h->mut_epoch; }
+        if (run[0] || run[1] || run[3]) { inputs_changed(h); }
         if (run[3]) {
             const bool in_args = small_inline(&ip, np, ops->place_idx, ops->place_requester);
             if (!in_args) {
@@ -2528,7 +2536,7 @@ int rio_gp_mixed_batch(rio_gp_t* h, rio_gp_mixed* ops) {
         fold_used(h);
         launch_update_small(h->assign[h->cur], dm, dm + kSmallBatch, nu, h->stream, aff_life(h), small_done_dev(h),
                             seq, in_args ? &inl : nullptr, h->used_valid ? h->used : nullptr, h->load, h->m);
-        h->have_solved = false; ++h->mut_epoch;
+        inputs_changed(h);
     }
     if (run[1]) {
         const bool in_args = small_inline(&inl, nr, ops->remove_idx, nullptr);
@@ -2536,7 +2544,7 @@ int rio_gp_mixed_batch(rio_gp_t* h, rio_gp_mixed* ops) {
         fold_used(h);
         launch_remove_small(h->assign[h->cur], h->m, h->load, dm + 2 * kSmallBatch, nr, h->used_valid ? h->used : nullptr, h->stream,
                             aff_life(h), small_done_dev(h), seq, in_args ? &inl : nullptr);
-        h->have_solved = false; ++h->mut_epoch;
+        inputs_changed(h);
     }
     if (run[2]) {
         const bool in_args = small_inline(&inl, nl, ops->lookup_idx, nullptr);
@@ -2565,7 +2573,7 @@ int rio_gp_mixed_batch(rio_gp_t* h, rio_gp_mixed* ops) {
         if (status == 0) {
             memcpy(ops->place_node, hs + 2 * kSmallBatch, np * sizeof(u32));
             if (ops->place_flag) memcpy(ops->place_flag, hs + 3 * kSmallBatch, np * sizeof(u32));
-            h->have_solved = false; ++h->mut_epoch;
+            inputs_changed(h);
         } else if (status == 1) {
             // a dead node / a dead or full requester is involved: nothing of the place_pending part was changed, the general path
             ops->rc[3] = place_pending_host_locked(h, np, ops->place_idx, ops->place_requester, ops->place_node, ops->place_flag, true);
@@ -2602,7 +2610,7 @@ int rio_gp_place_pending_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, con
         if ((rc = small_wait(h, seq))) return rc;
         const u32 status = h->h_small[4 * kSmallBatch];
         if (status == 0) {
-            h->have_solved = false; ++h->mut_epoch;
+            inputs_changed(h);
             return RIO_GP_OK;
         }
         if (status == 3)
@@ -2623,7 +2631,7 @@ int rio_gp_commit(rio_gp_t* h) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = commit_locked(h);
+    int rc = commit_enqueue(h);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RIO_GP_OK;
@@ -2672,17 +2680,14 @@ int rio_gp_solve_async(rio_gp_t* h) {
         }
         h->ring_n = 0;
     }
-    reset_inplace(h);
     h->plan = hplan(h, h->n);
     use_fx_slot(h, 0);
-    const Table t = real_table(h);
-    const NodeTab nt = scan_nodes(h);
-    h->ca_now = cut_apply_for(h, false);
-    enqueue_scan_resolve(h, t, nt, false, slot_dev(h, h->ring_n));
+    h->ring_form = solve_form(h, false, false);
+    h->ring_last = enqueue_scan_resolve(h, h->ring_form, real_table(h), scan_nodes(h), slot_dev(h, h->ring_n));
     HIPCHK(h, hipGetLastError());
     h->ring_n++;
     h->ring_any = true;
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     return RIO_GP_OK;
 }
 
@@ -2704,7 +2709,7 @@ int rio_gp_solve_wait(rio_gp_t* h, rio_gp_stats* stats, uint32_t* n_slow) {
     h->ring_slow = 0;
     h->ring_any = false;
     if (last.n_cut > 0 || last.spillcand > 0) {
-        enqueue_slow(h, h->plan, real_table(h), real_nodes(h), false, false);
+        enqueue_slow(h, h->ring_form, h->plan, real_table(h), real_nodes(h), false);
         int rc = merge_slow(h, &last);
         if (rc) return rc;
         HIPCHK(h, hipGetLastError());
@@ -2712,7 +2717,7 @@ int rio_gp_solve_wait(rio_gp_t* h, rio_gp_stats* stats, uint32_t* n_slow) {
     fill_stats(last, h->n, stats);
     if (n_slow) *n_slow = slow;
     h->ring_n = 0;
-    h->have_solved = true;
+    h->pending = h->ring_last;  // the last solve of the ring is finished: it waits for its commit
     return RIO_GP_OK;
 }
 
@@ -2721,7 +2726,6 @@ int rio_gp_solve_profiled(rio_gp_t* h, float* scan_ms, float* resolve_ms) {
     Locked g(h);
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->ev2) { HIPCHK(h, hipEventCreate(&h->ev2)); HIPCHK(h, hipEventCreate(&h->ev3)); }
-    reset_inplace(h);
     h->plan = hplan(h, h->n);
     use_fx_slot(h, 0);
     const Table t = real_table(h);
@@ -2729,14 +2733,13 @@ int rio_gp_solve_profiled(rio_gp_t* h, float* scan_ms, float* resolve_ms) {
     // hipExtLaunchKernelGGL start/stop events = the dispatch's own begin/end timestamps
     fold_used(h);
     h->sb.D = h->D;
-    h->solve_used_D = h->sb.D != nullptr;
     launch_scan(h->plan, t, nt, h->sb, false, h->all_alive, h->stream, h->ev0, h->ev1);
     launch_resolve(h->plan, nt, h->sb, slot_dev(h, 0), h->stream, h->ev2, h->ev3);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventElapsedTime(scan_ms, h->ev0, h->ev1));
     HIPCHK(h, hipEventElapsedTime(resolve_ms, h->ev2, h->ev3));
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     h->ring_n = 0; h->ring_slow = 0; h->ring_any = false;
     const DevStats v = reduce_slot(h, 0, h->m);
     if (v.n_cut > 0 || v.spillcand > 0)
@@ -2785,22 +2788,27 @@ static SolveBufs shard_bufs(rio_gp* h) {
     return b;
 }
 
+// What every row-sharded solve starts with: the plan, the committed `used` whole, k_scan over this rank's rows.  Such a solve
+// never works in place and never runs with sb.D (local_bufs / shard_bufs): once finished it is a plain PendingSolve{true}.
+struct ShardScan { Table t; NodeTab nt; };
+static ShardScan shard_scan_begin(rio_gp* h) {
+    h->plan = hplan(h, h->n);
+    h->sb.fx = FxRows{};  // row-sharded solve: the fix-up counters are summed in DevStats (rio_gp_shard_finish reads them)
+    fold_used(h);
+    const ShardScan s{real_table(h), real_nodes(h)};
+    launch_scan(h->plan, s.t, s.nt, h->sb, false, h->all_alive, h->stream);
+    return s;
+}
+
 int rio_gp_shard_scan(rio_gp_t* h, uint64_t* d_x) {
     if (!h || !d_x) return RIO_GP_EINVAL;
     Locked g(h);
     if (h->sa) return fail(h, RIO_GP_EINVAL, "row-sharded solves do not implement RIO_GP_CFG_REF_SELF_ASSIGN (single-GPU handles only)");
-    reset_inplace(h);
-    h->plan = hplan(h, h->n);
-    h->sb.fx = FxRows{};  // row-sharded solve: the fix-up counters are summed in DevStats (rio_gp_shard_finish reads them)
-    fold_used(h);
-    h->solve_used_D = false;
-    const Table t = real_table(h);
-    const NodeTab nt = real_nodes(h);
-    launch_scan(h->plan, t, nt, h->sb, false, h->all_alive, h->stream);
+    const NodeTab nt = shard_scan_begin(h).nt;
     const SolveBufs lb = local_bufs(h);
     launch_resolve(h->plan, nt, lb, nullptr, h->stream);  // used_base = nullptr: purely local sums
     launch_shard_pack1(h->plan, lb, reinterpret_cast<u64*>(d_x), h->stream);
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     h->sh_state = 1;
     return RIO_GP_OK;
 }
@@ -2926,7 +2934,7 @@ int rio_gp_shard_finish(rio_gp_t* h, rio_gp_stats* local_stats) {
         v.unplaced = d.unplaced; v.load_unplaced = d.load_unplaced;
     }
     fill_stats(v, h->n, local_stats);  // cut_nodes / slow_path / rounds_run are global: the caller has them
-    h->have_solved = true;
+    h->pending = PendingSolve{true};
     h->ring_n = 0;
     h->sh_state = 0;
     return RIO_GP_OK;
@@ -2991,7 +2999,7 @@ int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, u
     const RbBufs b = rb_bufs(h);
     const u32 m = h->m;
     // a change of the inputs, like rio_gp_rebalance: an uncommitted solve (a sharded one half way included) is dropped
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     h->sh_state = 0;
     h->ring_n = 0;
     h->used_parts = false;
@@ -3405,14 +3413,7 @@ int rio_gp_shard_solve_async(rio_gp_t* h) {
         StepGuard step{q};
         const u64 seq = ++q->seq;
         const u32 slot = (u32)(q->xslot_n++ % kP2PSlots);
-        reset_inplace(h);
-        h->plan = hplan(h, h->n);
-        h->sb.fx = FxRows{};
-        fold_used(h);
-        h->solve_used_D = false;
-        const Table t = real_table(h);
-        const NodeTab nt = real_nodes(h);
-        launch_scan(h->plan, t, nt, h->sb, false, h->all_alive, h->stream);
+        const NodeTab nt = shard_scan_begin(h).nt;
         h->sh_rank = q->rank;
         h->sh_R = q->R;
         h->sh_slot = h->ring_n;
@@ -3427,7 +3428,7 @@ int rio_gp_shard_solve_async(rio_gp_t* h) {
                             slot_dev(h, h->ring_n), q->co_resident, h->stream);
         h->sh_rows = resolve_blocks(h->m);
         h->ring_n++;
-        h->have_solved = false; ++h->mut_epoch;
+        inputs_changed(h);
         h->sh_state = 2;
         HIPCHK(h, hipGetLastError());
         step.done = true;
@@ -3437,14 +3438,7 @@ int rio_gp_shard_solve_async(rio_gp_t* h) {
     if (!sc) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_solve_async: set up rio_gp_shard_p2p_connect or rio_gp_shard_comm_init first");
     const int q = (int)(sc->k++ % kShardRing);
     if (sc->done_valid[q]) HIPCHK(h, hipStreamWaitEvent(h->stream, sc->done[q], 0));
-    reset_inplace(h);
-    h->plan = hplan(h, h->n);
-    h->sb.fx = FxRows{};
-    fold_used(h);
-    h->solve_used_D = false;
-    const Table t = real_table(h);
-    const NodeTab nt = real_nodes(h);
-    launch_scan(h->plan, t, nt, h->sb, false, h->all_alive, h->stream);
+    const NodeTab nt = shard_scan_begin(h).nt;
     const SolveBufs lb = local_bufs(h);
     launch_resolve(h->plan, nt, lb, nullptr, h->stream);
     launch_shard_pack1(h->plan, lb, sc->X[q], h->stream);
@@ -3462,7 +3456,7 @@ int rio_gp_shard_solve_async(rio_gp_t* h) {
     HIPCHK(h, hipEventRecord(sc->done[q], sc->side));
     sc->done_valid[q] = true;
     h->ring_n++;
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     h->sh_state = 2;
     return RIO_GP_OK;
 }
@@ -3497,14 +3491,9 @@ int rio_gp_shard_tick_async(rio_gp_t* h) {
     StepGuard step{q};  // (every sequence number this tick takes — its own and its exchanges' — is taken before any check below)
     const u64 seq = ++q->seq;
     const u32 slot = (u32)(q->xslot_n++ % kP2PSlots);
-    reset_inplace(h);
-    h->plan = hplan(h, h->n);
-    h->sb.fx = FxRows{};
-    fold_used(h);
-    h->solve_used_D = false;
-    const Table t = real_table(h);
-    const NodeTab nt = real_nodes(h);
-    launch_scan(h->plan, t, nt, h->sb, false, h->all_alive, h->stream);
+    const ShardScan sc0 = shard_scan_begin(h);
+    const Table& t = sc0.t;
+    const NodeTab& nt = sc0.nt;
     h->sh_rank = q->rank;
     h->sh_R = q->R;
     h->sh_side = nullptr;
@@ -3531,7 +3520,7 @@ int rio_gp_shard_tick_async(rio_gp_t* h) {
     h->sh_tick_mark[k] = (1ull << 41) | ++h->wait_seq;
     launch_shard_tick_stats(h->plan, b, rec, h->sh_tick_mark[k], h->stream);
     HIPCHK(h, hipGetLastError());
-    h->have_solved = true;
+    h->pending = PendingSolve{true};
     if ((rc = commit_enqueue(h))) return rc;
     h->sh_tick_n = k + 1;
     h->sh_state = 0;
@@ -3679,7 +3668,7 @@ int rio_gp_debug_stream_probe(rio_gp_t* h, int mode, int reps, float* ms) {
     // same columns the solve streams: cur/load/aff in, the ping-pong column out (an uncommitted solve is lost)
     *ms = stream_probe(mode, h->assign[h->cur], h->load, h->aff, h->assign[h->cur ^ 1], h->n, reps, h->stream, h->ev0,
                        h->ev1);
-    h->have_solved = false; ++h->mut_epoch;
+    inputs_changed(h);
     if (*ms < 0) return fail(h, RIO_GP_EUPSTREAM, "stream probe failed");
     return RIO_GP_OK;
 }

@@ -747,6 +747,109 @@ def test_committed_ticks_in_place_scan_every_variant(gp, oracle, seed, n, m):
         g.close()
 
 
+@pytest.mark.parametrize("seed,n,m", [(2, 4097, 64), (3, 70_001, 33)])
+def test_hand_offs_between_entry_point_families_on_one_handle(gp, oracle, seed, n, m, monkeypatch):
+    """One handle, walked from one family of solve entry points into the next: what a solve leaves behind for its commit
+    (in place or not, whose `used` buffer, D rows or not) and what rio_gp_solve_wait needs of the solve rio_gp_solve_async
+    enqueued must follow the solve, not the call that happened to write the handle last.
+      a. in-place committed ticks -> solve_async / solve_wait / commit (must swap the columns again) -> a tick in place
+      b. solve_async with the one-pass whole-table fix-up (k_cut_apply), which solve_wait enqueues in a later call -> commit
+         -> a packed tick
+      c. chained quiet ticks still in flight -> a synchronous un-committed solve (the committed column stays) -> commit ->
+         tick_wait -> tick
+    The test cannot see which kernels ran: the lab knobs are what force each form (c also checks the chain's launch counter).
+    Shapes of the in-place test that span more than one tile and more than one block; after every step the column, `used`
+    and the counters against the oracle.tick chain, in which at least one tick of every sequence takes the fix-up path."""
+    rng = np.random.default_rng(8800 + seed)
+    cur, load, aff, cap, alive = _rand_case(rng, n, m, p_none=0.1, cap_scale=1.3, p_alive=0.9, max_load=300 if seed % 2 else 3)
+    aff[rng.random(n) < 0.05] = 0xFFFFFFFE   # rows that are not objects
+    masks = [(rng.random(m) < 0.88).astype(np.uint8) for _ in range(4)]
+    ones = np.ones(m, np.uint8)
+
+    class Chain:
+        """the handle and the oracle's table side by side"""
+        def __init__(self, cap, alive):
+            self.g = _mk(gp, n, m, load, aff, cap, alive, cur, 2, lab=True)
+            self.cap, self.alive, self.ref, self.used, self.slow = cap, alive, cur.copy(), None, 0
+
+        def push(self, mask):
+            self.alive = mask
+            self.g.set_alive_all(mask)
+
+        def oracle(self):
+            nxt, used, ost = oracle.tick(self.ref, load, aff, self.cap, self.alive, 2)
+            self.slow += ost["slow_path"]
+            return nxt, used, ost
+
+        def committed(self, what):
+            got = self.g.get_assign()
+            assert np.array_equal(got, self.ref), (what, np.flatnonzero(got != self.ref)[:10])
+            if self.used is not None:
+                assert np.array_equal(self.g.get_nodes()[2], self.used), what
+
+        def tick(self, what):
+            self.ref, self.used, ost = self.oracle()
+            st = self.g.tick()
+            assert st == ost, (what, st, ost)
+            self.committed(what)
+
+        def uncommitted(self, what, ring):
+            """a solve that is not published (ring: solve_async + solve_wait | solve), then its commit"""
+            nxt, used, ost = self.oracle()
+            if ring:
+                self.g.solve_async()
+                st, n_slow = self.g.solve_wait()
+                assert n_slow == ost["slow_path"], (what, n_slow)
+            else:
+                st = self.g.solve()
+            assert st == ost, (what, st, ost)
+            assert np.array_equal(self.g.get_solved(), nxt), what
+            self.committed(what + ": the committed table stays")
+            self.g.commit()
+            self.ref, self.used = nxt, used
+            self.committed(what + ": committed")
+
+    a = Chain(cap, alive)
+    a.g.set_compact("always", inc="auto")
+    for t in (0, 1):
+        a.push(masks[t])
+        a.tick(("a: tick in place", t))
+    a.push(masks[2])
+    a.uncommitted("a: solve_async + solve_wait behind in-place ticks", ring=True)
+    a.push(masks[3])
+    a.tick("a: tick behind the ring solve")
+    assert a.slow >= 1
+    a.g.close()
+
+    b = Chain(cap // np.uint64(4), alive)
+    b.g.set_compact("never", cut_apply="always")
+    b.uncommitted("b: solve_async, its one-pass fix-up enqueued by solve_wait", ring=True)
+    assert b.slow == 1           # (n_slow == 1 was checked against it)
+    b.g.set_compact("always")
+    b.push(masks[0])
+    b.tick("b: packed tick behind the ring solve")
+    b.g.close()
+
+    monkeypatch.setenv("RIO_GP_OVERLAP_MIN_ROWS", "1")
+    c = Chain(cap * np.uint64(8), ones)   # room for everybody: from the second tick on nothing is pending
+    want = []
+    for k in range(5):
+        if k == 2:   # the second tick's verdict (fast path) is in: the three ticks from here on are quiet, links of one run
+            assert c.g.tick_wait() == want
+            want = []
+        c.g.tick_async()
+        c.ref, c.used, ost = c.oracle()
+        want.append(ost)
+    assert c.g.chained_scans() == 3 and [w["slow_path"] for w in want] == [0, 0, 0]
+    c.push(masks[0])
+    c.uncommitted("c: solve() with chained ticks in flight", ring=False)
+    assert c.g.tick_wait() == want
+    c.push(masks[1])
+    c.tick("c: tick behind all of it")
+    assert c.slow >= 1
+    c.g.close()
+
+
 def test_async_ticks_equal_the_synchronous_stream(gp, oracle):
     """rio_gp_tick_async: committed ticks enqueued back to back with liveness pushes in between, nothing waits on the host;
     tables and counters must be exactly those of the same sequence of rio_gp_tick calls (= the oracle chain), including
