@@ -1,5 +1,5 @@
 """A CPU stand-in for the rio_gp binding, FOR TESTS ONLY: the surface tests/test_gpu_fuzz.py's scenarios use, implemented over
-the CPU oracle (oracle/pyoracle.py), tests/rebalance_ref.py and tests/spec_changes.py.  It lets the fuzz driver itself be tested
+the CPU oracle (oracle/pyoracle.py), tests/rebalance_ref.py, tests/spec_changes.py and tests/spec_remap.py.  It lets the fuzz driver itself be tested
 without a GPU (tests/test_fuzz_driver.py): its bookkeeping (n, the feed's checkpoint, the mirror, the uncommitted solve) and its
 sensitivity — `fault=` makes exactly one behaviour of the handle wrong, and the scenarios must notice.
 
@@ -15,6 +15,7 @@ import numpy as np
 
 import rebalance_ref
 import spec_changes
+import spec_remap
 
 NONE = 0xFFFFFFFF
 CAP_INF = 0xFFFFFFFFFFFFFFFF
@@ -32,6 +33,12 @@ FAULTS = (
     "index_drops_last_row",        # the index drops the last row of a node's range
     "index_reads_solved",          # the index reads the uncommitted column
     "num_objects_stale_used",      # set_num_objects leaves `used` as it was
+    "remap_keeps_solve",           # a node removal keeps an uncommitted solve committable
+    "remap_skips_hidden_rows",     # a node removal leaves the rows >= n as they were
+    "remap_counts_hidden_rows",    # a node removal counts the rows >= n it un-places as evicted
+    "remap_checkpoint_none_not_gone",   # a checkpoint naming a removed node becomes NONE, not RIO_GP_NODE_GONE
+    "remap_stale_node_table",      # a node removal leaves cap and alive at their old ids
+    "remap_affinity_not_renumbered",    # the committed ticks read the affinity of before the removal (the getter does not)
 )
 
 
@@ -120,6 +127,7 @@ class GpuPlacement:
         self._B = np.full(self._cap_rows, NONE, np.uint32)
         self._solved = None
         self._stale_used = None
+        self._stale_aff = None
         self._done = []
 
     # ---- helpers
@@ -192,7 +200,12 @@ class GpuPlacement:
             self._load[idx] = np.asarray(load, np.uint32)
         if aff is not None:
             self._aff[idx] = np.asarray(aff, np.uint32)
+            if self._stale_aff is not None:
+                self._stale_aff[idx] = np.asarray(aff, np.uint32)
         self._changed()
+
+    def get_objects(self):
+        return self._load[:self._n].copy(), self._aff[:self._n].copy()
 
     def set_num_objects(self, n):
         if n > self._cap_rows:
@@ -293,7 +306,13 @@ class GpuPlacement:
         self._stale_used = None
 
     def tick(self):
-        st = self.solve()
+        aff = self._aff
+        if self._stale_aff is not None:
+            self._aff = self._stale_aff
+        try:
+            st = self.solve()
+        finally:
+            self._aff = aff
         self.commit()
         return st
 
@@ -303,6 +322,39 @@ class GpuPlacement:
     def tick_wait(self, cap=4096):
         out, self._done = self._done[-cap:], []
         return out
+
+    # ---- node removal
+    def remap_nodes_raw(self, m_new, map):
+        m, n, f = self._m, self._n, self._fault
+        if not spec_remap.check_map(m, m_new, map):
+            return EINVAL, 0
+        map = np.asarray(map, np.uint32)
+        rows = n if f == "remap_skips_hidden_rows" else self._cap_rows
+        solved, old_aff = self._solved, self._aff.copy()
+        out = spec_remap.remap(self._col[:rows], self._aff[:rows], self._cap_rows if f == "remap_counts_hidden_rows" else n, m, map,
+                               False, B=self._B[:rows], cap=self._cap, alive=self._alive)
+        self._col[:rows], self._aff[:rows], self._B[:rows] = out["assign"], out["aff"], out["B"]
+        if f == "remap_checkpoint_none_not_gone":
+            self._B[self._B == spec_remap.NODE_GONE] = NONE
+        if f == "remap_stale_node_table":
+            self._cap, self._alive = self._cap[:m_new].copy(), self._alive[:m_new].copy()
+        else:
+            self._cap, self._alive = out["cap"].copy(), out["alive"].copy()
+        self._m = int(m_new)
+        self._sync_alive()
+        self._changed()
+        if f == "remap_keeps_solve":
+            self._solved = solved
+        if f == "remap_affinity_not_renumbered":
+            self._stale_aff = old_aff if self._stale_aff is None else self._stale_aff
+        return OK, out["evicted"]
+
+    def remap_nodes(self, map):
+        map = np.asarray(map, np.uint32)
+        rc, ev = self.remap_nodes_raw(int(np.count_nonzero(map != NONE)), map)
+        if rc != OK:
+            raise _einval("rio_gp_remap_nodes: not a legal map")
+        return ev
 
     # ---- reverse index
     def _index(self, nodes):

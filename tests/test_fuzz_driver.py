@@ -30,6 +30,17 @@ FLOOR = (
     "feed reset",
     "index answered with ERANGE",
     "index while a solve is uncommitted",
+    "remap removed nodes that held rows",
+    "remap pure permutation",
+    "remap while a solve is uncommitted",
+    "remap refused with a solve uncommitted",
+    "remap between tick_async and tick_wait",
+    "remap with a checkpoint naming a removed node",
+    "remap with hidden rows on a removed node",
+    "remap right after a flip",
+    "remap down to a kernel's node-count boundary",
+    "rebalance on a handle whose m is below max_nodes",
+    "place_pending on a handle whose m is below max_nodes",
 )
 
 # fault of the stand-in -> the operation the failure must name
@@ -42,6 +53,12 @@ FAULTS = {
     "index_drops_last_row": "index",
     "index_reads_solved": "index",
     "num_objects_stale_used": "num_objects",
+    "remap_keeps_solve": "remap",
+    "remap_skips_hidden_rows": "remap",
+    "remap_counts_hidden_rows": "remap",
+    "remap_checkpoint_none_not_gone": "changes",
+    "remap_stale_node_table": "remap",
+    "remap_affinity_not_renumbered": "tick",
 }
 
 
@@ -60,7 +77,7 @@ def test_op_tables():
                                  ("clean", 2), ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
     assert fuzz.Scenario.OPS_EXT[:len(fuzz.Scenario.OPS)] == fuzz.Scenario.OPS
     assert [a for a, _ in fuzz.Scenario.OPS_EXT[len(fuzz.Scenario.OPS):]] == ["index", "rebalance", "changes", "changes_reset",
-                                                                            "num_objects"]
+                                                                            "num_objects", "remap"]
 
 
 @pytest.fixture(scope="module")
@@ -79,8 +96,8 @@ def clean_run(oracle):
 
 def test_extended_seeds_run_clean_and_use_every_new_operation(clean_run):
     cov, count = clean_run
-    for op in ("index", "rebalance", "changes", "changes_reset", "num_objects", "in flight: index", "in flight: changes",
-               "in flight: rebalance"):
+    for op in ("index", "rebalance", "changes", "changes_reset", "num_objects", "remap", "in flight: index", "in flight: changes",
+               "in flight: rebalance", "in flight: remap"):
         assert count.get(op, 0) > 0, (op, count)
 
 

@@ -18,6 +18,16 @@ committable), that every other call drops it, that the index and the feed leave 
 chain, and calls all three between rio_gp_tick_async and rio_gp_tick_wait.  The old family's tables, operations and draws are
 untouched (tests/test_fuzz_driver.py replays them against a CPU stand-in and a recorded log).
 
+Node removal (rio_gp_remap_nodes, against tests/spec_remap.py over every row the model holds, the hidden ones included) is one of
+the extended operations: the identity, a permutation, a swap, one node, several nodes with stable compaction or with the survivors
+shuffled, exactly the dead nodes, the node most rows are on — at least one node is kept, and a third of the removals end on a node
+count at which a kernel changes its per-node form, on a handle that keeps its larger max_nodes.  After a legal map: the evicted
+count (rows < n), num_nodes, cap and alive at their new ids, the renumbered affinity, the column and `used`; an uncommitted solve
+is gone; the consumer's mirror is renumbered by the scenario (RIO_GP_NODE_GONE for a removed node), so the feed's old nodes stay
+checked; rows hidden at the time are compared when n grows again and at the end.  About one map in ten is illegal (a duplicate, a
+kept value >= m_new, too few kept entries, m_new > m): RIO_GP_EINVAL and nothing changed, an uncommitted solve included.  It is
+also called between tick_async and tick_wait and in the middle of a chained quiet run, where the tick after it must not chain.
+
     python tests/test_gpu_fuzz.py <seconds> [first_seed]     # a longer campaign: old and extended scenarios alternate
 """
 import os
@@ -35,6 +45,8 @@ INF = 0xFFFFFFFFFFFFFFFF
 
 _SIZES = (1, 2, 3, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 16383, 16384, 16385, 65536, 262143, 262144, 262145)
 _BATCHES = (1, 2, 4, 5, 255, 256, 257, 1000, 1024, 1025, 4095, 4096, 4097, 20000, 65535, 65536, 65537, 131072)
+# the node counts a scenario draws its m from (Scenario.__init__ keeps its own literal: the old family's draws stay as recorded)
+_NODES = (1, 2, 3, 7, 31, 32, 33, 64, 100, 255, 256, 257, 1000, 1024, 1025, 4096, 5000, 8191, 8192)
 
 
 def _pick(rng, table, hi):
@@ -108,6 +120,8 @@ class Scenario:
         self.in_flight = False
         self.page_open = self.page_writer = False
         self.paging_out = self.mixed_wrote = False
+        self.m0 = m                # the handle's max_nodes: a removal leaves m below it
+        self.remapped = self.remap_refused = False
         self.cov = {}
 
     def _caps(self):
@@ -175,7 +189,7 @@ class Scenario:
         want_st = []
         # extended scenarios, a quiet run: a call in the middle of it (see _mid_call); any run: a call between the last tick_async
         # and tick_wait, whose answer reflects every enqueued tick
-        mid = ("none", "index", "changes", "rebalance")[int(self.rng.integers(4))] if self.ext and quiet_run else "none"
+        mid = ("none", "index", "changes", "rebalance", "remap")[int(self.rng.integers(5))] if self.ext and quiet_run else "none"
         watch = None
         for i in range(k):
             if i and not quiet_run and self.rng.random() < 0.5:
@@ -190,12 +204,12 @@ class Scenario:
             want_st.append(ost)
             if self.lab and mid != "none":
                 last_chained = self.g.chained_scans() - c0 == 1
-                if watch is not None and watch[0] == "rebalance" and i == k - 4:
-                    # a rebalance is a change of the inputs: the tick after it does not chain
-                    assert not last_chained, (self.seed, "rebalance", "the tick after a rebalance chained", self.log[-6:])
+                if watch is not None and watch[0] in ("rebalance", "remap") and i == k - 4:
+                    # a rebalance and a node removal (the identity map too) change the inputs: the tick after does not chain
+                    assert not last_chained, (self.seed, watch[0], "the tick after a %s chained" % watch[0], self.log[-6:])
             if self.rng.random() < 0.3 or (quiet_run and i < 3):
                 time.sleep(0.002)
-        if watch is not None and watch[0] != "rebalance" and watch[1]:
+        if watch is not None and watch[0] not in ("rebalance", "remap") and watch[1]:
             # the tick before the call was a link of a chain and nothing has changed since: the 4 ticks after it are links too,
             # as they are in the same run without the call
             c = self.g.chained_scans() - watch[2]
@@ -204,7 +218,7 @@ class Scenario:
         if self.ext and self.rng.random() < 0.5:
             self.in_flight = True
             try:
-                what = ("index", "changes", "rebalance")[int(self.rng.integers(3))]
+                what = ("index", "changes", "rebalance", "remap")[int(self.rng.integers(4))]
                 self.log.append("in flight: " + what)
                 self.count["in flight: " + what] = self.count.get("in flight: " + what, 0) + 1
                 getattr(self, "op_" + what)()
@@ -216,15 +230,17 @@ class Scenario:
     def _mid_call(self, what, last_chained):
         """A call between the quiet asynchronous ticks of a run (lab build, every tick may chain).  The index and a consuming feed
         call change nothing a tick reads: if the tick before was a link of a chain, the ticks after are.  A rebalance ends the
-        chain.  -> (what, the tick before chained, chained_scans() after the call)"""
+        chain, and so does a node removal.  -> (what, the tick before chained, chained_scans() after the call)"""
         self.log.append("mid run: " + what)
         self.count["mid run: " + what] = self.count.get("mid run: " + what, 0) + 1
         if what == "index":
             self.op_index()
         elif what == "changes":
             self._feed(None if self.rng.random() < 0.5 else int(self.rng.integers(1, 50)), False, False)
-        else:
+        elif what == "rebalance":
             self.op_rebalance()
+        else:
+            self.op_remap(legal=True)     # (a refused map changes nothing: only a legal one must end the chain)
         return what, last_chained, self.g.chained_scans() if self.lab else 0
 
     def op_flip(self):
@@ -310,6 +326,7 @@ class Scenario:
             node, flag = self.g.place_pending(idx, req)
         wnode, wflag = self.oracle.place_pending(self.ref[:n], self.load[:n], self.cap, self.alive, used, idx, req, self.rounds, self.oflags)
         self.fresh_flip = False   # (a request batch delivers a pushed liveness bitmap to the device)
+        self._hit("place_pending on a handle whose m is below max_nodes", self.m < self.m0)
         bad = np.flatnonzero((node != wnode) | (flag != wflag))
         assert bad.size == 0, (self.seed, "place_pending", self.log[-6:], idx.size, bad[:8], node[bad[:8]], wnode[bad[:8]], flag[bad[:8]], wflag[bad[:8]])
 
@@ -529,6 +546,7 @@ class Scenario:
         self._hit("rebalance under self-assign", self.sa)
         self._hit("rebalance while a solve is uncommitted", had_solve)
         self._hit("rebalance between tick_async and tick_wait", self.in_flight)
+        self._hit("rebalance on a handle whose m is below max_nodes", self.m < self.m0)
 
     def _feed(self, cap, peek, dev):
         import spec_changes
@@ -590,8 +608,135 @@ class Scenario:
             n = _pick(rng, _SIZES, self.nmax)
         else:
             n = int(rng.integers(0, self.nmax + 1))
+        self._set_n(n)
+
+    def _set_n(self, n):
+        grew = n > self.n
         self.g.set_num_objects(n)
         self.n = n
+        if grew and self.remapped:     # rows a removal found hidden are back: cleaned and renumbered, in both columns
+            tag = (self.seed, "num_objects", "hidden rows after a remap", self.log[-6:])
+            got, aff = self.g.get_assign(), self.g.get_objects()[1]
+            assert np.array_equal(got, self.ref[:n]), tag + ("assignment", np.flatnonzero(got != self.ref[:n])[:8])
+            assert np.array_equal(aff, self.aff[:n]), tag + ("affinity", np.flatnonzero(aff != self.aff[:n])[:8])
+
+    def _remap_draw(self):
+        """A legal map for rio_gp_remap_nodes, at least one node kept: identity | permutation | swap | drop one | drop several
+        (stable) | drop several (survivors shuffled) | drop exactly the dead nodes | drop the node most rows are on.  Where the
+        count is free, half the time it is chosen so that m_new is the nearest smaller entry of _NODES (about a third of the
+        removals): the kernels pick their per-node forms there, and the handle keeps its larger max_nodes."""
+        import spec_remap
+        rng, m = self.rng, self.m
+        ident = np.arange(m, dtype=np.uint32)
+        kind = ("identity", "permutation", "swap", "drop one", "drop several", "drop and shuffle", "drop the dead",
+                "drop the fullest")[int(rng.integers(8))]
+        if kind == "identity" or m == 1:
+            return "identity", ident
+        if kind == "permutation":
+            return kind, rng.permutation(m).astype(np.uint32)
+        if kind == "swap":
+            a, b = (int(x) for x in rng.choice(m, 2, replace=False))
+            ident[[a, b]] = ident[[b, a]]
+            return kind, ident
+        below = [v for v in _NODES if v < m]
+        if kind == "drop one":
+            gone = [int(rng.integers(m))]
+        elif kind == "drop the dead":
+            gone = np.flatnonzero(self.alive == 0)
+            if len(gone) == 0:
+                return "identity", ident
+            gone = gone[:m - 1]
+        else:
+            if rng.random() < (0.5 if kind != "drop the fullest" else 1 / 3):
+                count = m - below[-1]
+            else:
+                count = int(rng.integers(1, max(2, m // 3 + 1)))
+            count = min(count, m - 1)
+            first = []
+            if kind == "drop the fullest":
+                a = self.ref[:self.n]
+                first = [int(np.bincount(a[a < m], minlength=m).argmax())]
+                count -= 1
+            rest = np.setdiff1d(np.arange(m), first)
+            gone = first + [int(x) for x in rng.choice(rest, count, replace=False)]
+        map = spec_remap.stable_map(m, gone)
+        if kind == "drop and shuffle":
+            kept = map != NONE
+            map[kept] = rng.permutation(int(kept.sum())).astype(np.uint32)
+        return kind, map
+
+    def _remap_refused(self):
+        """The four kinds of illegal map: RIO_GP_EINVAL, and nothing changed — an uncommitted solve included."""
+        import spec_remap
+        rng, m = self.rng, self.m
+        _, map = self._remap_draw()
+        m_new = int((map != NONE).sum())
+        kept = np.flatnonzero(map != NONE)
+        kind = ("duplicate", "kept value >= m_new", "fewer than m_new kept", "m_new > m")[int(rng.integers(4))]
+        if kind == "duplicate" and m_new < 2:
+            kind = "m_new > m"
+        if kind == "duplicate":
+            a, b = (int(x) for x in rng.choice(kept, 2, replace=False))
+            map[a] = map[b]
+        elif kind == "kept value >= m_new":
+            map[int(rng.choice(kept))] = m_new + int(rng.integers(0, 3))
+        elif kind == "fewer than m_new kept":
+            map[int(rng.choice(kept))] = NONE
+        else:
+            map, m_new = np.arange(m, dtype=np.uint32), m + 1 + int(rng.integers(0, 3))
+        tag = (self.seed, "remap", "refused", kind, m, m_new, self.log[-6:])
+        assert not spec_remap.check_map(m, m_new, map), tag
+        rc, ev = self.g.remap_nodes_raw(m_new, map)
+        assert rc == self.gp.EINVAL and ev == 0, tag + (rc, ev)
+        assert self.g.num_nodes == m, tag + (self.g.num_nodes,)
+        self.remap_refused = True
+        self._hit("remap refused with a solve uncommitted", self.pending is not None)
+        self._read_only("remap refused")
+        self.check_table("remap refused")
+
+    def op_remap(self, legal=False):
+        """rio_gp_remap_nodes against tests/spec_remap.py over every row the model holds (the hidden ones too); the consumer's
+        mirror is renumbered by the scenario, as the header asks of whoever holds node ids from before the call."""
+        import spec_remap
+        self.remap_refused = False
+        if not legal and self.rng.random() < (1 / 3 if self.pending is not None else 0.1):   # (about 10 % of all draws)
+            return self._remap_refused()
+        m, n, g = self.m, self.n, self.g
+        kind, map = self._remap_draw()
+        m_new = int((map != NONE).sum())
+        assert spec_remap.check_map(m, m_new, map), (self.seed, "remap", kind, "the draw is not a legal map")
+        had_solve = self.pending is not None
+        removed = np.zeros(m + 1, bool)
+        removed[:m] = map == NONE
+        on_removed = lambda col: removed[np.minimum(col, m)]
+        self._hit("remap pure permutation", m_new == m and kind != "identity")
+        self._hit("remap while a solve is uncommitted", had_solve)
+        self._hit("remap between tick_async and tick_wait", self.in_flight)
+        self._hit("remap with a checkpoint naming a removed node", on_removed(self.B).any())
+        self._hit("remap with hidden rows on a removed node", on_removed(self.ref[n:]).any())
+        self._hit("remap right after a flip", self.fresh_flip)
+        self._hit("remap down to a kernel's node-count boundary", m_new < m and m_new in _NODES)
+        want = spec_remap.remap(self.ref, self.aff, n, m, map, False, B=self.B, cap=self.cap, alive=self.alive)
+        ev = g.remap_nodes(map)
+        self.ref, self.aff, self.B, self.cap, self.alive = want["assign"], want["aff"], want["B"], want["cap"], want["alive"]
+        self.m = m_new
+        self.pending, self.fresh_flip, self.remapped = None, False, True   # (the call writes the liveness bitmap whole)
+        known = self.mirror < m                 # the consumer's duty: ids handed out before the call are void
+        v = map[self.mirror[known]]
+        v[v == NONE] = spec_remap.NODE_GONE
+        self.mirror[known] = v
+        tag = (self.seed, "remap", kind, m, m_new, self.log[-6:])
+        assert ev == want["evicted"], tag + ("evicted", ev, want["evicted"])
+        assert g.num_nodes == m_new, tag + ("num_nodes", g.num_nodes)
+        cap, alive, _ = g.get_nodes()
+        assert np.array_equal(cap, self.cap) and np.array_equal(alive, self.alive), tag + ("the node table did not move with the ids",)
+        load, aff = g.get_objects()
+        assert np.array_equal(load, self.load[:n]), tag + ("load changed",)
+        assert np.array_equal(aff, self.aff[:n]), tag + ("affinity", np.flatnonzero(aff != self.aff[:n])[:8])
+        self.check_table("remap")
+        if had_solve:
+            self._dropped("remap")
+        self._hit("remap removed nodes that held rows", ev > 0)
 
     def finish_feed(self):
         """The end of an extended scenario: the rest of the feed is paged out — three small pages, then pages of a third of what
@@ -609,13 +754,13 @@ class Scenario:
                                                            self.log[-6:], np.flatnonzero(self.mirror[:self.n] != got)[:8])
 
     NEED_ROWS = ("update", "remove", "lookup", "place", "mixed", "attrs")                       # skipped while n == 0
-    WRITERS = ("tick", "solve", "async", "update", "remove", "clean", "place", "mixed", "rebalance", "num_objects")
-    DROPS_SOLVE = ("tick", "rebalance", "update", "remove", "clean", "place", "mixed", "attrs", "caps", "num_objects")
+    WRITERS = ("tick", "solve", "async", "update", "remove", "clean", "place", "mixed", "rebalance", "num_objects", "remap")
+    DROPS_SOLVE = ("tick", "rebalance", "update", "remove", "clean", "place", "mixed", "attrs", "caps", "num_objects", "remap")
 
     OPS = (("tick", 5), ("solve", 2), ("async", 3), ("flip", 4), ("update", 2), ("remove", 2), ("lookup", 1), ("clean", 2),
            ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
 
-    OPS_EXT = OPS + (("index", 3), ("rebalance", 6), ("changes", 5), ("changes_reset", 1), ("num_objects", 2))
+    OPS_EXT = OPS + (("index", 3), ("rebalance", 6), ("changes", 5), ("changes_reset", 1), ("num_objects", 2), ("remap", 3))
 
     def run(self):
         names = [a for a, w in (self.OPS_EXT if self.ext else self.OPS) for _ in range(w)]
@@ -623,6 +768,10 @@ class Scenario:
         try:
             for _ in range(k):
                 op = names[int(self.rng.integers(len(names)))]
+                if self.ext and self.pending is not None and self.rng.random() < 0.5:
+                    # an uncommitted solve lives until the next writer: half the time the calls that must keep it, or must drop
+                    # it themselves, come right behind it (the table's weights alone bring them there a few times in 72 seeds)
+                    op = ("index", "remap", "rebalance", "remap")[int(self.rng.integers(4))]
                 if self.ext and self.n == 0 and op in self.NEED_ROWS:
                     self.log.append("skipped: " + op)
                     continue
@@ -631,11 +780,12 @@ class Scenario:
                 had_solve = self.pending is not None
                 getattr(self, "op_" + op)()
                 if self.ext:
-                    if op in self.WRITERS:
+                    did = (op != "mixed" or self.mixed_wrote) and (op != "remap" or not self.remap_refused)
+                    if op in self.WRITERS and (op != "remap" or did):
                         self.page_writer = True
-                    if op in self.DROPS_SOLVE and (op != "mixed" or self.mixed_wrote):
+                    if op in self.DROPS_SOLVE and did:
                         self.pending = None
-                        if had_solve and op != "rebalance":    # (op_rebalance has asked already)
+                        if had_solve and op not in ("rebalance", "remap"):    # (op_rebalance and op_remap have asked already)
                             self._dropped(op)
                     elif op in ("mixed", "lookup"):
                         self._read_only(op)
@@ -643,6 +793,9 @@ class Scenario:
             if self.ext:
                 self.finish_feed()
                 self.check_table("the end")
+                if self.remapped and self.n < self.nmax:    # the rows still hidden come back as the removals left them
+                    self._set_n(self.nmax)
+                    self.check_table("the end, every row back")
             self.chained = self.g.chained_scans() if self.lab else 0
         finally:
             self.g.close()
