@@ -128,6 +128,74 @@ struct PendingSolve {
     u64* used = nullptr;   // it built its `used` here instead of in sb.used_cur (a chained tick)
 };
 
+// The committed per-node load vector `used`.  Water-fill rounds keep what they admit apart from the solve's vector (the D rows,
+// SolveBufs::D) and a chained tick adds into kChainReps replicas, so the committed vector is its first vector PLUS `rounds` rows
+// of `parts` until somebody folds them in: the next solve's k_resolve for free (take_parts_for_resolve), or live() / ensure()
+// when somebody needs the vector first.  Nothing outside this class reads or writes that state; the call sites say what they mean:
+//   invalidate()   the column no longer matches: rebuild before the next use (pending parts are dropped with it)
+//   live()         the pointer for a kernel that updates `used` in place, parts folded in; nullptr while it is invalid
+//   ensure()       the pointer for a reader: folded, or rebuilt from the committed column (k_recompute_used)
+//   fold_pending() the fold alone, for a solve about to zero the D rows or to publish without them
+//   publish(...)   a solve's vector becomes the committed one: the only place where that happens
+//   rebuilt()      the caller has just written the vector of the committed column into storage() itself
+//   borrow()       storage() holds something else until the next rebuilt() / publish() / ensure() (the row-sharded rebalance)
+struct rio_gp;
+class UsedVec {
+  public:
+    struct Parts { u64* into; u32 rounds; const u64* src; };
+    void init(rio_gp* owner, u64* first) { h = owner; vec = first; }
+    u64* storage() const { return vec; }  // the first vector, whatever it holds (its writers; readers behind an ensure())
+    bool valid() const { return state == kValid; }
+    bool borrowed() const { return state == kBorrowed; }
+    void invalidate() { if (state == kValid) state = kInvalid; pending = false; }
+    void rebuilt() { state = kValid; pending = false; }
+    void borrow() { state = kBorrowed; pending = false; }
+    void fold_pending();  // pending parts in now (before something overwrites their source, or drops them)
+    u64* live();
+    u64* ensure();
+    Parts take_parts_for_resolve();  // what launch_resolve folds (into == nullptr: nothing); they are no longer pending
+    void publish(const PendingSolve& ps);  // a whole-table solve: its vector + its D rows | a chained tick's ring slot + its replicas
+    void publish_request(bool vslow);      // a request-path solve: its vector, + its D rows when it took the fix-up
+
+  private:
+    enum State { kInvalid, kValid, kBorrowed };
+    void swap_in(bool parts_in_D);
+    rio_gp* h = nullptr;
+    u64* vec = nullptr;
+    State state = kValid;
+    bool pending = false;        // `rounds` rows of `parts` are still to be added
+    u32 rounds = 0;
+    const u64* parts = nullptr;  // the handle's D rows | replicas 1.. of a chained tick's buffer
+};
+
+// What the last solves said, for the heuristics that choose the next one's form (solve_form: pending, fix_rows) and decide
+// whether its fix-up is enqueued speculatively (solve_locked: slow).
+struct SolveStats {
+    u64 pending = 0;   // rows the previous solve found pending (claimants + spill candidates)
+    bool pending_valid = false;
+    u64 fix_rows = 0;  // rows it sent to the water-fill (spill candidates + rejected claimants)
+    bool fix_valid = false;
+    bool slow = false;
+    // sync: the call read the fix-up's counters on the host (rio_gp_solve, rio_gp_tick): only those keep fix_rows current
+    void record(const DevStats& v, bool slow_, bool sync) {
+        pending = v.claimants + v.spillcand;
+        pending_valid = true;
+        if (sync) { fix_rows = v.spillcand + (slow_ ? v.rejected : 0); fix_valid = true; }
+        slow = slow_;
+    }
+    void forget_pending() { pending_valid = false; }  // the table changed size or node ids
+    void forget() { pending_valid = false; fix_valid = false; }  // an in-place solve was abandoned: the table is not what they describe
+};
+
+// One asynchronous committed tick in flight (rio_gp_tick_async fills it, rio_gp_tick_wait harvests it)
+struct TickSlot {
+    u32 G = 0;       // workgroups of its streaming grid (how many fix-up counter rows to fold)
+    u32 rows = 0;    // its verdict rows: resolve_blocks(m), or G (a chained quiet tick: a row per workgroup)
+    u64 mark = 0;    // column 7 of those rows
+    u64 epoch = 0;   // mut_epoch it was enqueued under
+    bool quiet = false;  // it was enqueued without its fix-up (checked against its verdict when harvested)
+};
+
 struct rio_gp {
     ShardComm* sc = nullptr;
     P2P* p2p = nullptr;
@@ -149,7 +217,8 @@ struct rio_gp {
     int cur = 0;
     u32 *load = nullptr, *aff = nullptr, *pos = nullptr;
     // node table
-    u64 *cap = nullptr, *used = nullptr;
+    u64* cap = nullptr;
+    UsedVec used;  // the committed per-node loads (above)
     u32 *alive_bits = nullptr, *dead_bits = nullptr;
     // A liveness push is a bitmap written into a ring slot of mapped pinned memory (no launch).  It reaches alive_bits with
     // the next whole-table scan, which reads it from the slot (scan_nodes), or through flush_alive when something else
@@ -159,13 +228,7 @@ struct rio_gp {
     bool alive_dirty = false;
     uint8_t* alive_bytes = nullptr;
     std::vector<uint8_t> h_alive;
-    bool used_valid = true;
-    // water-fill rounds keep what they admit apart from the solve's `used` vector (SolveBufs::D): the committed vector is
-    // h->used + the first parts_rounds rows of D until somebody folds them in (the next solve's k_resolve, or fold_used)
-    u64* D = nullptr;
-    bool used_parts = false;
-    u32 parts_rounds = 0;
-    const u64* parts = nullptr;  // ... or the rows are here instead of D (a chained tick: replicas 1.. of its `used` buffer)
+    u64* D = nullptr;  // [kFillRounds][max_nodes] what a solve's water-fill rounds admit (SolveBufs::D; UsedVec folds them in)
     // solve scratch
     SolveBufs sb{};
     DevStats* dstats = nullptr;
@@ -184,8 +247,7 @@ struct rio_gp {
     // asynchronous committed ticks (rio_gp_tick_async): verdict slots [kRing, 2 kRing) and their own ring of device-stats
     // copies, so that synchronous calls made while ticks are in flight do not touch what has not been harvested yet
     u32 tick_n = 0;
-    u32 tick_G[kRing] = {};  // workgroups of the streaming grid of asynchronous tick k (how many counter rows to fold)
-    u32 tick_rows[kRing] = {};  // verdict rows of asynchronous tick k: resolve_blocks(m), or G (a chained quiet tick: a row per workgroup)
+    TickSlot tick_ring[kRing];
     std::vector<rio_gp_stats> tick_done;
     // fix-up counters as per-workgroup rows (FxRows, placement_kernels.h): device rows + pinned slots [1 + kRing][kMaxBlocks][8]
     // (slot 0: synchronous solves, slots 1..kRing: asynchronous ticks)
@@ -207,15 +269,12 @@ struct rio_gp {
     hipStream_t sh_side = nullptr;  // stream the last rio_gp_shard_resolve ran on, when not the handle's
     // packed fix-up (PackOut, placement_kernels.h): scratch columns + per-wave counts; chosen adaptively per tick
     PackOut pk{};
-    bool last_pending_valid = false;
+    SolveStats last{};
     // A tick that took the fast path leaves every object placed; until the next call that changes an input of the solve
     // (mut_epoch counts those) every further tick keeps every row where it is, and rio_gp_tick_async enqueues no speculative
     // fix-up behind it: two launches a tick instead of five.  quiet_epoch = the mut_epoch such a tick was enqueued under.
     u64 mut_epoch = 0, quiet_epoch = ~0ull;
-    u64 tick_mark[kRing] = {}, tick_epoch[kRing] = {};
-    bool tick_quiet[kRing] = {};       // the tick was enqueued without its fix-up (checked against its verdict when harvested)
     u32 tick_peeked = 0;               // ticks [0, tick_peeked) of the ring have had their verdicts looked at
-    u64 last_pending = 0;
     int compact_mode = 0;  // 0 auto | 1 always | 2 never (rio_gp_debug_set_compact)
     // A committed tick over a mostly-placed table updates the assignment column in place and builds no kept histogram
     // (k_inc_scan), then k_rebal deals the pending rows out evenly to the fix-up's workgroups: 0 auto | 2 never (bits 7-8
@@ -239,7 +298,7 @@ struct rio_gp {
     u64 overlap_min_rows = (u64)1 << 18;  // quiet ticks of smaller tables: k_scan + k_resolve on the main stream (lab builds,
                                           //  RIO_GP_OVERLAP_MIN_ROWS: the parity tests run the chained ticks on small tables)
     hipEvent_t ev_join = nullptr;
-    // The `used` buffers: h->used (committed) and sb.used_cur (the solve's) are the first vectors of two of the kUsedRing slots of
+    // The `used` buffers: the committed one (h->used) and the solve's (sb.used_cur) are the first vectors of two of the kUsedRing slots of
     // used_ring; link c of a chained run adds into slot used_base + c and zeroes slot used_base + c + 2 (mod kUsedRing:
     // ScanChain), kChainReps replicas of m words each
     u64* used_ring = nullptr;
@@ -253,11 +312,8 @@ struct rio_gp {
     int chain_mode = 0;    // 0 on | 2 never (lab builds: bit 12 of rio_gp_debug_set_compact)
     int cutapply_mode = 0; // whole-table fix-up by k_cut_apply (cuts + re-marking in one pass): 0 when the solve packs at the cut pass
                            // | 1 always | 2 never (k_cut_find + k_fill<APPLY>) (bits 9-10 of rio_gp_debug_set_compact)
-    u64 last_fix_rows = 0;  // rows the previous solve sent to the water-fill (spill candidates + rejected claimants)
-    bool last_fix_valid = false;
     int spec_mode = 0;     // speculative fix-up enqueue: 0 auto (after a solve that needed it) | 1 always | 2 never
     int part_mode = 0;     // partitioned CRUD batches: 0 when the batch qualifies | 2 never (rio_gp_debug_set_compact bit 4)
-    bool last_slow = false;
     // clean_server(s): dead bitmap + evicted count in mapped pinned memory, self-resetting device counter + ticket
     u32* h_cs = nullptr;
     u32* d_cs = nullptr;
@@ -317,6 +373,46 @@ struct rio_gp {
     DevBuf chg_stage;
     std::vector<void*> allocs;
 };
+
+void UsedVec::fold_pending() {
+    if (!pending) return;
+    launch_used_fold(vec, parts, h->m, rounds, h->stream);
+    pending = false;
+}
+u64* UsedVec::live() {
+    if (state != kValid) return nullptr;
+    fold_pending();
+    return vec;
+}
+u64* UsedVec::ensure() {
+    if (state == kValid) { fold_pending(); return vec; }
+    launch_recompute_used(h->assign[h->cur], h->load, h->n, h->m, vec, h->stream);
+    rebuilt();  // from the assignment column: nothing to fold
+    return vec;
+}
+UsedVec::Parts UsedVec::take_parts_for_resolve() {
+    const Parts p{pending ? vec : nullptr, rounds, parts ? parts : h->D};  // (parts: nullptr until the first publication)
+    pending = false;
+    return p;
+}
+// the solve's vector (sb.used_cur) becomes the committed one and the last committed one the next solve's scratch: no copy
+void UsedVec::swap_in(bool parts_in_D) {
+    std::swap(vec, h->sb.used_cur);
+    state = kValid;
+    pending = parts_in_D;  // + what its water-fill rounds admitted (D rows), folded in later
+    rounds = h->rounds;
+    parts = h->D;
+}
+void UsedVec::publish(const PendingSolve& ps) {
+    if (!ps.used) return swap_in(ps.used_D);
+    h->sb.used_cur = vec;  // a chained tick: its buffer of the ring is the new vector
+    vec = ps.used;
+    state = kValid;
+    pending = true;  // + its other replicas, folded in later
+    rounds = kChainReps - 1;
+    parts = vec + h->m;
+}
+void UsedVec::publish_request(bool vslow) { swap_in(vslow); }
 
 namespace {
 
@@ -484,10 +580,10 @@ void inputs_changed(rio_gp* h) {
 // The form of one solve of the real table (h->plan is that table's, mark included), from the handle's knobs and statistics and
 // from what the caller knows:
 //   commit   the solve is published in this call (a tick)
-//   sync     this call reads the verdict on the host (rio_gp_solve, rio_gp_tick): only those calls keep last_fix_* current
+//   sync     this call reads the verdict on the host (rio_gp_solve, rio_gp_tick): only those calls keep last.fix_rows current
 //   quiet    nothing has changed since a tick that left every object placed: no fix-up can be needed
 //   chained  ... and the tick is the chained k_scan alone, a link of a run
-// This is the only place where compact_mode, cutpack_mode, inc_mode, cutapply_mode, last_pending* and last_fix_* choose a form.
+// This is the only place where compact_mode, cutpack_mode, inc_mode, cutapply_mode, last.pending and last.fix_rows choose a form.
 // spec_mode and chain_mode stay with their readers: spec_mode decides WHEN solve_locked enqueues the fix-up, which shapes that
 // function's host waits and nothing of the form; chain_mode is one of tick_async_locked's conditions for a link of a run, next
 // to the stream's and the table's, and must be decided before the run is joined — `chained` is its outcome.
@@ -504,12 +600,12 @@ SolveForm solve_form(const rio_gp* h, bool commit, bool sync, bool quiet = false
     // the table as it is then: it packs nothing.)
     f.compact = !quiet && (commit || sync) &&
                 (h->compact_mode == 1 ||
-                 (h->compact_mode == 0 && h->last_pending_valid && h->last_pending > 0 && h->last_pending * 4 <= h->n && h->n >= 65536));
+                 (h->compact_mode == 0 && h->last.pending_valid && h->last.pending > 0 && h->last.pending * 4 <= h->n && h->n >= 65536));
     // Packing at the cut pass: a whole-table solve (nothing known to be kept) whose previous solve sent few rows to the
     // water-fill — a contended table re-solved: ~10 % of the rows — lets round 0 of k_fill pack those rows on its way, and
     // the later rounds run over them instead of streaming the table again.  Results identical.
     f.cutpack = sync && !f.compact && h->rounds >= 1 && fill_can_pack(h->m) &&
-                (h->cutpack_mode == 1 || (h->cutpack_mode == 0 && h->last_fix_valid && h->last_fix_rows * 4 <= h->n && h->n >= 65536));
+                (h->cutpack_mode == 1 || (h->cutpack_mode == 0 && h->last.fix_valid && h->last.fix_rows * 4 <= h->n && h->n >= 65536));
     // ... and when the tick is committed and the library's `used` vector is valid, the scan streams the assignment column
     // alone and works in place (k_inc_scan + k_rebal).  Only a COMMITTED tick may work in place, only a
     // valid `used` vector can stand in for the kept histogram, and the rings of pending rows must fit the LDS next to the
@@ -517,7 +613,7 @@ SolveForm solve_form(const rio_gp* h, bool commit, bool sync, bool quiet = false
     // (Tables whose blocks are beyond the in-resolve cut search — config 4 on one GPU, 390 K rows a block — take this path too:
     // 100 M x 4 096, three boxes, same-run A/B: 700-720 us pipelined against 734-797 with k_scan<COMPACT>; round 0 of the
     // water-fill alone is 60-90 us shorter over the balanced rows.  The cut search stays k_cut_find's launch there.)
-    if (f.compact && commit && h->used_valid && h->inc_mode != 2 && inc_scan_fits(h->m) && h->m != 0) {
+    if (f.compact && commit && h->used.valid() && h->inc_mode != 2 && inc_scan_fits(h->m) && h->m != 0) {
         f.inc = 2;
         f.fix_plan = rebal_plan(h->plan);
         f.pkx = &h->pk2;
@@ -575,14 +671,6 @@ void enqueue_slow(rio_gp* h, const SolveForm& f, const Plan& p, const Table& t, 
     for (u32 r = 1; r < h->rounds; ++r) launch_fill(p, t, nt, h->sb, virt, false, true, (int)r, r + 1 == h->rounds, h->stream);
 }
 
-// committed `used` = h->used + the D rows of the last committed solve, until they are folded in: by the next solve's
-// k_resolve (for free), or here when somebody needs the vector first
-const u64* parts_src(rio_gp* h) { return h->parts ? h->parts : h->D; }
-void fold_used(rio_gp* h) {
-    if (!h->used_parts) return;
-    launch_used_fold(h->used, parts_src(h), h->m, h->parts_rounds, h->stream);
-    h->used_parts = false;
-}
 // scan + resolve of one solve over the REAL table: the packed pending rows' cuts are searched inside k_resolve, the previous
 // committed solve's D rows are folded into the committed vector before k_resolve zeroes them.  Returns what the solve is once
 // it waits for its commit; the enqueue functions keep nothing of a solve on the handle themselves.
@@ -601,9 +689,9 @@ PendingSolve enqueue_scan_resolve(rio_gp* h, const SolveForm& f, const Table& t,
     }
     Plan rp = f.fix_plan;
     if (!f.resolve_searches) rp.wcnt = nullptr;
+    const UsedVec::Parts fold = h->used.take_parts_for_resolve();
     launch_resolve(rp, nt, rb, host_rows, h->stream, nullptr, nullptr, f.resolve_searches ? f.pkx : nullptr,
-                   h->used_parts ? h->used : nullptr, h->parts_rounds, f.inc ? h->used : nullptr, parts_src(h));
-    h->used_parts = false;
+                   fold.into, fold.rounds, f.inc ? h->used.storage() : nullptr, fold.src);
     return PendingSolve{true, f.inc != 0, h->sb.D != nullptr, nullptr};
 }
 u64* used_slot(rio_gp* h, u32 q) { return h->used_ring + (size_t)(q % kUsedRing) * h->used_slot_words; }
@@ -616,7 +704,7 @@ PendingSolve enqueue_chained(rio_gp* h, const Table& t, const NodeTab& nt, u64* 
     ScanChain ch{h->chain_flags, h->d_chain_err};
     if (!h->chain_prev) {
         // the run's buffers start behind the committed one; its first two links add into buffers nothing zeroes inside the run
-        h->used_base = (u32)((h->used - h->used_ring) / h->used_slot_words) + 1;
+        h->used_base = (u32)((h->used.storage() - h->used_ring) / h->used_slot_words) + 1;
         const size_t zb = (size_t)kChainReps * h->m * sizeof(u64);
         (void)hipMemsetAsync(used_slot(h, h->used_base), 0, zb, h->stream);
         (void)hipMemsetAsync(used_slot(h, h->used_base + 1), 0, zb, h->stream);
@@ -657,7 +745,7 @@ DevStats reduce_rows(rio_gp* h, size_t slot, u32 nrows, u64 mark = 0, bool* bad 
 DevStats reduce_slot(rio_gp* h, u32 k, u32 m) { return reduce_rows(h, k % kRing, resolve_blocks(m)); }  // solve ring
 u64* tick_rows_host(rio_gp* h, u32 k) { return h->h_slots + (size_t)(kTickSlot0 + k % kRing) * h->slot_rows * 8; }
 DevStats reduce_tick_slot(rio_gp* h, u32 k, bool* bad) {  // tick ring
-    return reduce_rows(h, kTickSlot0 + k % kRing, h->tick_rows[k % kRing], h->tick_mark[k % kRing], bad);
+    return reduce_rows(h, kTickSlot0 + k % kRing, h->tick_ring[k % kRing].rows, h->tick_ring[k % kRing].mark, bad);
 }
 DevStats reduce_rows(rio_gp* h, size_t slot, u32 nrows, u64 mark, bool* bad) {
     DevStats d;
@@ -721,7 +809,7 @@ struct InplaceGuard {
     bool ok = false;
     ~InplaceGuard() {
         if (ok) return;
-        if (h->pending.inplace) { h->used_valid = false; h->used_parts = false; h->last_pending_valid = false; h->last_fix_valid = false; }
+        if (h->pending.inplace) { h->used.invalidate(); h->last.forget(); }
         h->pending = PendingSolve{};
     }
 };
@@ -738,19 +826,7 @@ int commit_enqueue(rio_gp* h) {
                                      hipMemcpyDeviceToDevice, h->stream));
         h->cur ^= 1;
     }
-    h->used_valid = true;
-    if (ps.used) {  // a chained tick: its buffer of the ring becomes the committed vector, the last committed one the solve's scratch
-        h->sb.used_cur = h->used;
-        h->used = ps.used;
-        h->parts = h->used + h->m;  // ... plus its other replicas, folded in later
-        h->parts_rounds = kChainReps - 1;
-        h->used_parts = true;
-    } else {
-        std::swap(h->used, h->sb.used_cur);  // publication = two pointer swaps: the solve's `used` vector becomes the committed one
-        h->used_parts = ps.used_D;           // ... plus what its water-fill rounds admitted (D rows), folded in later
-        h->parts_rounds = h->rounds;
-        h->parts = nullptr;
-    }
+    h->used.publish(ps);  // publication = two pointer swaps: the columns' above, the `used` vectors' in there
     h->pending = PendingSolve{};  // (consumed; not an input change: mut_epoch stays)
     return RIO_GP_OK;
 }
@@ -774,7 +850,7 @@ int solve_locked(rio_gp* h, rio_gp_stats* stats, bool commit = false) {
     // are enqueued right behind k_resolve instead of after a host round trip for the verdict.  Every fix-up kernel
     // guards itself on device (the cut search: stats->n_cut; the water-fill rounds: pending-row count), so a solve that
     // turns out not to need them pays a few no-op launches and gets the same result.
-    const bool spec = h->spec_mode != 2 && (h->spec_mode == 1 || h->last_slow);
+    const bool spec = h->spec_mode != 2 && (h->spec_mode == 1 || h->last.slow);
     const SolveForm f = solve_form(h, commit, true);
     h->pending = enqueue_scan_resolve(h, f, t, nt, slot_dev(h, 0));  // (a call that fails from here on abandons it: InplaceGuard)
     DevStats v;
@@ -804,11 +880,7 @@ int solve_locked(rio_gp* h, rio_gp_stats* stats, bool commit = false) {
         if (rc) return rc;
     }  // (fast path: k_resolve was the last kernel and its rows are here; the publication is two host-side swaps)
     HIPCHK(h, hipGetLastError());
-    h->last_pending = v.claimants + v.spillcand;
-    h->last_pending_valid = true;
-    h->last_fix_rows = v.spillcand + (slow ? v.rejected : 0);
-    h->last_fix_valid = true;
-    h->last_slow = slow;
+    h->last.record(v, slow, true);
     fill_stats(v, h->n, stats);
     ipg.ok = true;
     return RIO_GP_OK;
@@ -819,13 +891,14 @@ int solve_locked(rio_gp* h, rio_gp_stats* stats, bool commit = false) {
 void peek_ticks(rio_gp* h) {
     for (; h->tick_peeked < h->tick_n; ++h->tick_peeked) {
         const u32 k = h->tick_peeked;
-        if (h->tick_quiet[k]) continue;  // (a quiet tick was enqueued under the quiet rule already: its verdict cannot start it)
+        const TickSlot& tk = h->tick_ring[k];
+        if (tk.quiet) continue;  // (a quiet tick was enqueued under the quiet rule already: its verdict cannot start it)
         const volatile u64* rows = tick_rows_host(h, k);
-        for (u32 r = 0; r < h->tick_rows[k]; ++r)
-            if (rows[(size_t)r * 8 + 7] != h->tick_mark[k]) return;
+        for (u32 r = 0; r < tk.rows; ++r)
+            if (rows[(size_t)r * 8 + 7] != tk.mark) return;
         std::atomic_thread_fence(std::memory_order_acquire);
         const DevStats v = reduce_tick_slot(h, k, nullptr);
-        if (!(v.n_cut > 0 || v.spillcand > 0) && h->tick_epoch[k] == h->mut_epoch) h->quiet_epoch = h->mut_epoch;
+        if (!(v.n_cut > 0 || v.spillcand > 0) && tk.epoch == h->mut_epoch) h->quiet_epoch = h->mut_epoch;
     }
 }
 
@@ -838,8 +911,8 @@ int harvest_ticks(rio_gp* h) {
     // asking the runtime (launch + hipStreamSynchronize 12.6 us, launch + spin 7.3: tools/sync_probe.py) — the rows of two chained
     // links land in any order.  Not there after 50 ms: the stream is asked.
     const u32 last = h->tick_n - 1;
-    bool landed = h->tick_quiet[last];
-    for (u32 k = 0; landed && k < h->tick_n; ++k) landed = spin_rows(tick_rows_host(h, k), h->tick_rows[k], h->tick_mark[k]);
+    bool landed = h->tick_ring[last].quiet;
+    for (u32 k = 0; landed && k < h->tick_n; ++k) landed = spin_rows(tick_rows_host(h, k), h->tick_ring[k].rows, h->tick_ring[k].mark);
     if (!landed) HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (h->h_chain_err && *reinterpret_cast<volatile u32*>(h->h_chain_err)) {  // never seen; must not pass silently if it happens
@@ -856,18 +929,16 @@ int harvest_ticks(rio_gp* h) {
             return fail(h, RIO_GP_EUPSTREAM, "rio_gp_tick_wait: a tick's verdict rows are incomplete (tables are stale: reload them)");
         }
         const bool slow = v.n_cut > 0 || v.spillcand > 0;
-        if (slow && h->tick_quiet[k]) {  // cannot happen (see mut_epoch); if it ever does it must not pass silently
+        if (slow && h->tick_ring[k].quiet) {  // cannot happen (see mut_epoch); if it ever does it must not pass silently
             h->tick_n = 0;
             return fail(h, RIO_GP_EUPSTREAM, "rio_gp_tick_wait: a tick that was enqueued without its fix-up needed one (tables are stale: reload them)");
         }
-        if (!slow && h->tick_epoch[k] == h->mut_epoch) h->quiet_epoch = h->mut_epoch;
-        if (slow) fold_fx(h, 1 + k, h->tick_G[k], &v);
+        if (!slow && h->tick_ring[k].epoch == h->mut_epoch) h->quiet_epoch = h->mut_epoch;
+        if (slow) fold_fx(h, 1 + k, h->tick_ring[k].G, &v);
         rio_gp_stats st;
         fill_stats(v, h->n, &st);
         h->tick_done.push_back(st);
-        h->last_pending = v.claimants + v.spillcand;
-        h->last_pending_valid = true;
-        h->last_slow = slow;
+        h->last.record(v, slow, false);
     }
     h->tick_n = 0;
     return RIO_GP_OK;
@@ -907,12 +978,9 @@ int tick_async_locked(rio_gp* h) {
     const NodeTab nt = scan_nodes(h);
     const u32 k = h->tick_n;
     use_fx_slot(h, 1 + k);
-    h->tick_G[k] = h->plan.G;
-    h->tick_epoch[k] = h->mut_epoch;
-    h->tick_quiet[k] = quiet;
-    h->tick_mark[k] = h->plan.mark = (1ull << 40) | ++h->wait_seq;  // column 7 of the verdict rows: peek_ticks knows them by it
+    h->plan.mark = (1ull << 40) | ++h->wait_seq;  // column 7 of the verdict rows: peek_ticks knows them by it
+    h->tick_ring[k] = TickSlot{h->plan.G, chained ? h->plan.G : resolve_blocks(h->m), h->plan.mark, h->mut_epoch, quiet};
     u64* const rows = h->d_slots + (size_t)(kTickSlot0 + k) * h->slot_rows * 8;
-    h->tick_rows[k] = chained ? h->plan.G : resolve_blocks(h->m);
     const SolveForm f = solve_form(h, true, false, quiet, chained);
     h->pending = chained ? enqueue_chained(h, t, nt, rows) : enqueue_scan_resolve(h, f, t, nt, rows);
     if (quiet) {
@@ -960,14 +1028,6 @@ int small_wait(rio_gp* h, u32 seq, volatile u32* w = nullptr) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (*w != seq) return fail(h, RIO_GP_EUPSTREAM, "micro-batch kernel left no completion word");
-    return RIO_GP_OK;
-}
-
-int ensure_used(rio_gp* h) {
-    if (h->used_valid) { fold_used(h); return RIO_GP_OK; }
-    h->used_parts = false;  // rebuilt from the assignment column: nothing to fold
-    launch_recompute_used(h->assign[h->cur], h->load, h->n, h->m, h->used, h->stream);
-    h->used_valid = true;
     return RIO_GP_OK;
 }
 
@@ -1076,7 +1136,7 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
     A(h->sh_lkept, M); A(h->sh_lclaim, M); A(h->sh_lcur, M); A(h->sh_lcutblk, M); A(h->sh_lcutidx, M);
     A(h->sh_gprev, M); A(h->sh_gfinal, M); A(h->sh_rank_base, 2); A(h->sh_verdict, 8); A(h->sh_forced, (M + 31) / 32 + 4);
 #undef A
-    h->used = h->used_ring;
+    h->used.init(h, h->used_ring);
     h->sb.used_cur = h->used_ring + h->used_slot_words;
     h->sb.stats = h->dstats;
     if (hipHostMalloc(reinterpret_cast<void**>(&h->h_stats), sizeof(DevStats) * kRing, hipHostMallocMapped) !=
@@ -1250,7 +1310,7 @@ int rio_gp_set_nodes(rio_gp_t* h, uint32_t m, const uint64_t* cap, const uint8_t
     h->alive_dirty = false;
     h->all_alive = true;
     for (uint32_t j = 0; j < m; ++j) h->all_alive = h->all_alive && h->h_alive[j];
-    if (m != h->m) { h->used_valid = false; h->used_parts = false; }
+    if (m != h->m) h->used.invalidate();
     h->m = m;
     inputs_changed(h);
     return RIO_GP_OK;
@@ -1299,9 +1359,9 @@ int rio_gp_get_nodes(rio_gp_t* h, uint32_t m, uint64_t* cap, uint8_t* alive, uin
     Locked g(h);
     if (m != h->m) return fail(h, RIO_GP_EINVAL, "rio_gp_get_nodes: m differs from the node table");
     HIPCHK(h, hipSetDevice(h->device));
-    if (used) { int rc = ensure_used(h); if (rc) return rc; }
+    const u64* const d_used = used ? h->used.ensure() : nullptr;
     if (cap && m) HIPCHK(h, hipMemcpyAsync(cap, h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-    if (used && m) HIPCHK(h, hipMemcpyAsync(used, h->used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    if (used && m) HIPCHK(h, hipMemcpyAsync(used, d_used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (alive) memcpy(alive, h->h_alive.data(), m);
     return RIO_GP_OK;
@@ -1319,12 +1379,11 @@ static int set_objects_impl(rio_gp_t* h, uint64_t n, const uint32_t* load, const
     if (aff) { if (n) HIPCHK(h, hipMemcpyAsync(h->aff, aff, n * sizeof(u32), kind, h->stream)); }
     else launch_fill_u32(h->aff, n, h->lifecycle ? kAffInactive : kNone, h->stream);
     launch_fill_u32(h->assign[h->cur], h->cap_rows, kNone, h->stream);
-    HIPCHK(h, hipMemsetAsync(h->used, 0, (size_t)h->cap_nodes * sizeof(u64), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->used.storage(), 0, (size_t)h->cap_nodes * sizeof(u64), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->n = n;
     h->n_hi = std::max<u64>(h->n_hi, n);
-    h->used_valid = true;
-    h->used_parts = false;
+    h->used.rebuilt();  // (all zero: no row is placed)
     inputs_changed(h);
     return RIO_GP_OK;
 }
@@ -1346,7 +1405,7 @@ static int set_assign_impl(rio_gp_t* h, uint64_t n, const uint32_t* assign, hipM
     HIPCHK(h, hipSetDevice(h->device));
     if (n) HIPCHK(h, hipMemcpyAsync(h->assign[h->cur], assign, n * sizeof(u32), kind, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->used_valid = false;
+    h->used.invalidate();
     inputs_changed(h);
     return RIO_GP_OK;
 }
@@ -1397,7 +1456,7 @@ int rio_gp_set_object_attrs(rio_gp_t* h, uint64_t n, const uint32_t* idx, const 
     if ((rc = zero_stats(h))) return rc;
     launch_set_attrs(h->load, h->aff, h->n, (const u32*)h->stage[0].p, load ? (const u32*)h->stage[1].p : nullptr,
                      aff ? (const u32*)h->stage[2].p : nullptr, n, h->dstats, h->stream);
-    if (load) h->used_valid = false;
+    if (load) h->used.invalidate();
     inputs_changed(h);
     return read_stats(h);
 }
@@ -1554,12 +1613,12 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 roun
     if (cfg->target) memcpy(T.data(), cfg->target, (size_t)m * sizeof(u64));
     else if (m) HIPCHK(h, hipMemcpyAsync(T.data(), h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     // R0: one pass — every node's load (the `used` vector of this column, rebuilt: nothing left to fold) and its pinned load
-    h->used_parts = false;
-    launch_shed_hist(h->assign[h->cur], h->load, h->aff, n, m, h->used, pin, h->stream);
+    u64* const d_used = h->used.storage();
+    launch_shed_hist(h->assign[h->cur], h->load, h->aff, n, m, d_used, pin, h->stream);
     HIPCHK(h, hipGetLastError());
-    h->used_valid = true;
+    h->used.rebuilt();
     if (m) {
-        HIPCHK(h, hipMemcpyAsync(used.data(), h->used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(used.data(), d_used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(pn.data(), pin, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1622,15 +1681,15 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 roun
         u32* pk_row = (u32*)h->sh_pk.p;
         u32* pk_load = pk_row + K;
         u32* pk_node = pk_load + K;
-        launch_shed_pack(h->assign[h->cur], h->load, h->aff, p, cut, (const u32*)h->sh_tile.p, K, pk_row, pk_load, pk_node, h->used,
+        launch_shed_pack(h->assign[h->cur], h->load, h->aff, p, cut, (const u32*)h->sh_tile.p, K, pk_row, pk_load, pk_node, d_used,
                          acc, h->stream);
         for (u32 r = 0; r < rounds; ++r)
-            launch_shed_round(K, pk_load, pk_node, tgt, m, h->used, (u64*)h->sh_chunk.p, C, ord, cntp, h->stream);
-        launch_shed_finish(K, pk_row, pk_load, pk_node, h->assign[h->cur], h->used, (u32*)h->sh_chunk.p, acc, d_rows, d_from, d_to,
+            launch_shed_round(K, pk_load, pk_node, tgt, m, d_used, (u64*)h->sh_chunk.p, C, ord, cntp, h->stream);
+        launch_shed_finish(K, pk_row, pk_load, pk_node, h->assign[h->cur], d_used, (u32*)h->sh_chunk.p, acc, d_rows, d_from, d_to,
                            h->stream);
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(a, acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(used.data(), h->used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(used.data(), d_used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         s.selected_load = a[kShAccSelectedLoad];
         s.moved_rows = a[kShAccMovedRows];
@@ -1811,11 +1870,11 @@ int rio_gp_set_num_objects(rio_gp_t* h, uint64_t n) {
     if (n > h->cap_obj) return fail(h, RIO_GP_EINVAL, "rio_gp_set_num_objects: n exceeds max_objects");
     // rows keep their contents: rows >= n simply take no part (and are rejected as indices) until n grows again — but a
     // placed row that drops out (or comes back) changes what `used` must count, so the vector is rebuilt before its next use
-    if (n != h->n) h->used_valid = false;
+    if (n != h->n) h->used.invalidate();
     h->n = n;
     h->n_hi = std::max<u64>(h->n_hi, n);
     inputs_changed(h);
-    h->last_pending_valid = false;
+    h->last.forget_pending();
     return RIO_GP_OK;
 }
 
@@ -1894,13 +1953,13 @@ static int update_dev_locked(rio_gp* h, uint64_t n, const uint32_t* d_idx, const
     if (h->part_mode != 2 && part_applicable(h->n, n, d_idx, d_node)) {  // big batch: binned by row window, elected in LDS, written densely
         if ((rc = ensure(h, h->part, part_scratch_words(h->n, n) * sizeof(u32)))) return rc;
         launch_update_part(h->assign[h->cur], h->n, h->m, d_idx, d_node, n, (u32*)h->part.p, h->dstats, h->stream, aff_life(h));
-        h->used_valid = false;
+        h->used.invalidate();
         inputs_changed(h);
         return finish_err(h, "rio_gp_update_batch: invalid entries were skipped");
     } else {
         launch_update(h->assign[h->cur], h->n, h->m, d_idx, d_node, n, h->pos, h->dstats, h->stream, aff_life(h));
     }
-    h->used_valid = false;
+    h->used.invalidate();
     inputs_changed(h);
     if ((rc = read_stats(h))) return rc;
     if (h->h_stats[0].err) return fail(h, RIO_GP_EINVAL, "rio_gp_update_batch: invalid entries were skipped");
@@ -1935,9 +1994,9 @@ int rio_gp_update_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint
         const u32 seq = small_begin(h);
         // `used` follows the writes when it is valid (k_remove_small does the same): a server that mixes single updates with
         // policy calls does not re-stream the whole table before every place_pending
-        fold_used(h);
+        u64* const used = h->used.live();
         launch_update_small(h->assign[h->cur], h->d_small, h->d_small + kSmallBatch, (u32)n, h->stream, aff_life(h),
-                            small_done_dev(h), seq, in_args ? &inl : nullptr, h->used_valid ? h->used : nullptr, h->load, h->m);
+                            small_done_dev(h), seq, in_args ? &inl : nullptr, used, h->load, h->m);
         inputs_changed(h);
         return small_wait(h, seq);
     }
@@ -1947,9 +2006,9 @@ int rio_gp_update_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint
         memcpy(h->h_mid, idx, n * sizeof(u32));
         memcpy(h->h_mid + kMidBatch, node, n * sizeof(u32));
         const u32 seq = small_begin(h);
-        fold_used(h);
+        u64* const used = h->used.live();
         launch_update(h->assign[h->cur], h->n, h->m, h->d_mid, h->d_mid + kMidBatch, n, h->pos, h->dstats, h->stream, aff_life(h),
-                      h->mid_ticket, small_done_dev(h), seq, h->used_valid ? h->used : nullptr, h->load);
+                      h->mid_ticket, small_done_dev(h), seq, used, h->load);
         inputs_changed(h);
         return small_wait(h, seq);
     }
@@ -1962,15 +2021,15 @@ int rio_gp_update_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint
 static int remove_dev_locked(rio_gp* h, uint64_t n, const uint32_t* d_idx) {
     int rc = zero_stats(h);
     if (rc) return rc;
-    fold_used(h);
+    u64* const used = h->used.live();
     if (h->part_mode != 2 && part_applicable(h->n, n, d_idx, nullptr)) {
         if ((rc = ensure(h, h->part, part_scratch_words(h->n, n) * sizeof(u32)))) return rc;
-        launch_remove_part(h->assign[h->cur], h->n, h->m, h->load, d_idx, n, (u32*)h->part.p, h->used_valid ? h->used : nullptr,
+        launch_remove_part(h->assign[h->cur], h->n, h->m, h->load, d_idx, n, (u32*)h->part.p, used,
                            h->dstats, h->stream, aff_life(h));
         inputs_changed(h);
         return finish_err(h, "rio_gp_remove_batch: invalid entries were skipped");
     } else {
-        launch_remove(h->assign[h->cur], h->n, h->m, h->load, d_idx, n, h->used_valid ? h->used : nullptr, h->dstats,
+        launch_remove(h->assign[h->cur], h->n, h->m, h->load, d_idx, n, used, h->dstats,
                       h->stream, aff_life(h));
     }
     inputs_changed(h);
@@ -1999,8 +2058,8 @@ int rio_gp_remove_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx) {
         const bool in_args = small_inline(&inl, n, idx, nullptr);
         if (!in_args) memcpy(h->h_small, idx, n * sizeof(u32));
         const u32 seq = small_begin(h);
-        fold_used(h);
-        launch_remove_small(h->assign[h->cur], h->m, h->load, h->d_small, (u32)n, h->used_valid ? h->used : nullptr, h->stream,
+        u64* const used = h->used.live();
+        launch_remove_small(h->assign[h->cur], h->m, h->load, h->d_small, (u32)n, used, h->stream,
                             aff_life(h), small_done_dev(h), seq, in_args ? &inl : nullptr);
         inputs_changed(h);
         return small_wait(h, seq);
@@ -2008,8 +2067,8 @@ int rio_gp_remove_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx) {
     if (n <= (uint64_t)kMidBatch) {  // medium batch, validated above: as update_batch
         memcpy(h->h_mid, idx, n * sizeof(u32));
         const u32 seq = small_begin(h);
-        fold_used(h);
-        launch_remove(h->assign[h->cur], h->n, h->m, h->load, h->d_mid, n, h->used_valid ? h->used : nullptr, h->dstats,
+        u64* const used = h->used.live();
+        launch_remove(h->assign[h->cur], h->n, h->m, h->load, h->d_mid, n, used, h->dstats,
                       h->stream, aff_life(h), small_done_dev(h), seq, nullptr, h->mid_ticket);
         inputs_changed(h);
         return small_wait(h, seq);
@@ -2037,8 +2096,8 @@ int rio_gp_clean_servers(rio_gp_t* h, const uint64_t* dead_bitmap, uint64_t* evi
     inputs_changed(h);
     if (!any || h->n == 0) return RIO_GP_OK;  // retain() with a predicate nothing matches, or over an empty map
     const u32 seq = (small_begin(h) & 0xFFFFFFu) | 0x800000u;  // 24 bits, never 0
-    fold_used(h);  // (k_clean zeroes the dead nodes' entries: what the last solve's rounds admitted there must be in first)
-    launch_clean(h->assign[h->cur], h->n, h->m, h->d_cs, h->used_valid ? h->used : nullptr, h->dstats, h->stream,
+    u64* const used = h->used.live();  // (k_clean zeroes the dead nodes' entries: what the last solve's rounds admitted there must be in first)
+    launch_clean(h->assign[h->cur], h->n, h->m, h->d_cs, used, h->dstats, h->stream,
                  h->cs_cnt, h->cs_ticket, reinterpret_cast<u64*>(h->d_cs + h->cs_words), aff_life(h), seq);
     {   // the last workgroup stores total | seq << 40 into mapped pinned memory: spin on the tag, ask the stream after 50 ms
         volatile u64* w = h_count;
@@ -2103,7 +2162,7 @@ int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* map, uint64_
     if (evicted) *evicted = 0;
     // a change of the inputs, like every CRUD call: an uncommitted solve is dropped, the next tick is neither quiet nor chained
     inputs_changed(h);
-    h->last_pending_valid = false;
+    h->last.forget_pending();
     int rc;
     u32 G = 0;
     if (m && h->n_hi) {
@@ -2113,8 +2172,7 @@ int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* map, uint64_
                          h->sb.blkstat, h->stream);
         HIPCHK(h, hipGetLastError());
         // `used` is the one of the new column: rebuilt from it before its next use (nothing left to fold)
-        h->used_valid = false;
-        h->used_parts = false;
+        h->used.invalidate();
     }
     // the node table: cap and alive of node j move to map[j]; h_alive already holds every liveness push, delivered or not, so
     // the device bitmap is written whole from it
@@ -2140,7 +2198,7 @@ int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* map, uint64_
     launch_pack_alive(h->alive_bytes, m_new, h->alive_bits, h->stream);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
-    if (m_new != m) { h->used_valid = false; h->used_parts = false; }
+    if (m_new != m) h->used.invalidate();
     u64 ev = 0;
     for (u32 b = 0; b < G; ++b) ev += blk[(size_t)b * 4 + 1];
     if (evicted) *evicted = ev;
@@ -2165,7 +2223,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
     u32 *vcur = (u32*)h->vt[0].p, *vload = (u32*)h->vt[1].p, *vaff = (u32*)h->vt[2].p, *vnext = (u32*)h->vt[3].p;
     u32* assign = h->assign[h->cur];
     h->sb.fx = FxRows{};  // nobody reads the fix-up counters of the virtual-table solve: plain DevStats atomics, no pinned slot touched
-    if ((rc = ensure_used(h))) return rc;
+    u64* const used = h->used.ensure();
     const char* const who = dev_api ? "rio_gp_place_pending_dev" : "rio_gp_place_pending";
     if (h->part_mode != 2 && !host_io && pp_win_applicable(h->n, n, d_idx, d_req) &&
         (((uintptr_t)d_out | (uintptr_t)d_flag) & 15u) == 0) {  // (its output kernels store whole vectors)
@@ -2189,8 +2247,8 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
         launch_pp_win_gather(assign, h->load, h->n, h->m, h->alive_bits, n, (const u32*)h->part.p, vaff, vnext, h->dead_bits,
                              aff_life(h), h->dstats, h->pp_claim, h->stream);
         if (!h->all_alive)  // service.rs:227-237: every object of a dead node a request ran into is un-placed
-            launch_clean(assign, h->n, h->m, h->dead_bits, h->used, h->dstats, h->stream, nullptr, nullptr, nullptr, aff_life(h));
-        launch_pp_win_verdict(h->m, h->cap, h->alive_bits, h->used, h->pp_claim, h->dstats, h->pp_bad + 1, h->d_small + 4 * kSmallBatch,
+            launch_clean(assign, h->n, h->m, h->dead_bits, used, h->dstats, h->stream, nullptr, nullptr, nullptr, aff_life(h));
+        launch_pp_win_verdict(h->m, h->cap, h->alive_bits, used, h->pp_claim, h->dstats, h->pp_bad + 1, h->d_small + 4 * kSmallBatch,
                               h->stream);
         // (the answers' two words sit in vaff / vnext, in the sorted order, until here: the solve below writes vnext afterwards)
         launch_pp_win_unsort(h->n, (const u32*)h->part.p, vaff, vnext, n, (uint2*)h->vrec.p, d_out, d_flag, h->pp_bad + 1, h->stream);
@@ -2218,7 +2276,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
         vtab.real_next = assign;  // (in place: the rows that change are pending, nothing else reads them before the outputs)
         vtab.vrec = (const uint2*)h->vrec.p;  // the scan reads the records and writes vcur / vload for the kernels behind it
         vtab.prewritten = true;               // k_pp_win_gather has put the alive requesters' first touches into the column
-        const NodeTab vnt{h->cap, h->alive_bits, h->used};
+        const NodeTab vnt{h->cap, h->alive_bits, used};
         h->sb.D = h->D;
         launch_scan(vp, vtab, vnt, h->sb, true, h->all_alive, h->stream);
         launch_resolve(vp, vnt, h->sb, slot_dev(h, 0), h->stream);
@@ -2229,10 +2287,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
         HIPCHK(h, hipGetLastError());
         const DevStats v = reduce_slot(h, 0, h->m);
         const bool vslow = v.n_cut > 0 || v.spillcand > 0;
-        std::swap(h->used, h->sb.used_cur);
-        h->used_parts = vslow;
-        h->parts_rounds = h->rounds;
-        h->parts = nullptr;
+        h->used.publish_request(vslow);
         inputs_changed(h);
         return RIO_GP_OK;
     }
@@ -2256,7 +2311,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
     const u32* const k_idx = s_idx;
     const u32* const k_req = s_req;
     (void)host_io;
-    if (mark) launch_clean(assign, h->n, h->m, h->dead_bits, h->used, h->dstats, h->stream, nullptr, nullptr, nullptr, aff_life(h), 0, h->pp_bad);
+    if (mark) launch_clean(assign, h->n, h->m, h->dead_bits, used, h->dstats, h->stream, nullptr, nullptr, nullptr, aff_life(h), 0, h->pp_bad);
     // (2)(3) the virtual table (rows = requests): the first request per row decides
     launch_ppm_gather(assign, h->load, k_idx, n, h->pos, vcur, vload, vaff /* position of the row's first request */, h->pp_bad, h->stream);
     // (4) solve it against the committed `used`
@@ -2265,7 +2320,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
     vp.mark = mk;
     Table vtab{vcur, vload, k_req /* the requesters ARE the affinity column of the virtual table */, vnext};
     vtab.skip_if = h->pp_bad;
-    const NodeTab vnt{h->cap, h->alive_bits, h->used};  // (ensure_used above folded whatever the last solve's rounds had left)
+    const NodeTab vnt{h->cap, h->alive_bits, used};  // (ensure() above folded whatever the last solve's rounds had left)
     h->sb.D = h->D;
     launch_scan(vp, vtab, vnt, h->sb, true, h->all_alive, h->stream);
     launch_resolve(vp, vnt, h->sb, slot_dev(h, 0), h->stream);
@@ -2293,10 +2348,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
     const DevStats v = reduce_slot(h, 0, h->m);  // (k_resolve's pinned rows landed before the completion word)
     const bool vslow = v.n_cut > 0 || v.spillcand > 0;
     h->pp_last_slow = vslow;
-    std::swap(h->used, h->sb.used_cur);  // the solve's `used` vector becomes the committed one (as commit does): no copy
-    h->used_parts = vslow && h->sb.D != nullptr;  // + what the water-fill rounds admitted (D rows), folded in later
-    h->parts_rounds = h->rounds;
-    h->parts = nullptr;
+    h->used.publish_request(vslow);
     inputs_changed(h);
     return RIO_GP_OK;
 }
@@ -2333,7 +2385,7 @@ static int place_pending_host_locked(rio_gp* h, uint64_t n, const uint32_t* idx,
     }
     if (n <= (uint64_t)kSmallBatch && !micro_tried) {
         // micro-batch: one workgroup, one launch, request/result arrays in mapped pinned memory (no staging copies)
-        if ((rc = ensure_used(h))) return rc;
+        u64* const used = h->used.ensure();
         u32 *hs = h->h_small, *ds = h->d_small;
         SmallInline inl;
         const bool in_args = small_inline(&inl, n, idx, requester);
@@ -2343,7 +2395,7 @@ static int place_pending_host_locked(rio_gp* h, uint64_t n, const uint32_t* idx,
         }
         hs[4 * kSmallBatch] = 2;  // neither 0 nor 1: the kernel must write it
         const u32 seq = small_begin(h);
-        launch_pp_one(h->assign[h->cur], h->load, h->m, h->cap, h->alive_bits, h->used, ds, ds + kSmallBatch,
+        launch_pp_one(h->assign[h->cur], h->load, h->m, h->cap, h->alive_bits, used, ds, ds + kSmallBatch,
                       (u32)n, ds + 2 * kSmallBatch, ds + 3 * kSmallBatch, ds + 4 * kSmallBatch, h->stream, aff_life(h),
                       small_done_dev(h), seq, in_args ? &inl : nullptr, 0, nullptr, nullptr, h->sa);
         if ((rc = small_wait(h, seq))) return rc;
@@ -2368,10 +2420,10 @@ static int place_pending_host_locked(rio_gp* h, uint64_t n, const uint32_t* idx,
         if (n > (uint64_t)kSmallBatch) {
             // first the one-workgroup kernel (k_pp_one, 1024 threads x 4 requests): sticky hits and first touches that fit —
             // the whole call is ONE launch and one wait (4 096 requests: 46 -> ~15 us); anything heavier hands over untouched
-            if ((rc = ensure_used(h))) return rc;
+            u64* const used = h->used.ensure();
             h->h_small[4 * kSmallBatch] = 2;
             const u32 seq1 = small_begin(h);
-            launch_pp_one(h->assign[h->cur], h->load, h->m, h->cap, h->alive_bits, h->used, dm, dm + kMidBatch, (u32)n,
+            launch_pp_one(h->assign[h->cur], h->load, h->m, h->cap, h->alive_bits, used, dm, dm + kMidBatch, (u32)n,
                           dm + 2 * kMidBatch, dm + 3 * kMidBatch, h->d_small + 4 * kSmallBatch, h->stream, aff_life(h),
                           small_done_dev(h), seq1, nullptr, 0, h->pp_stage, h->mid_ticket, h->sa, true);
             if ((rc = small_wait(h, seq1))) return rc;
@@ -2487,11 +2539,8 @@ int rio_gp_mixed_batch(rio_gp_t* h, rio_gp_mixed* ops) {
         SmallInline iu, ir, il, ip;
         CrudSmallArgs c;
         c.n_obj = h->n; c.st = h->dstats;
-        fold_used(h);
-        if (run[3]) {
-            flush_alive(h);
-            if ((rc = ensure_used(h))) return rc;
-        }
+        if (run[3]) flush_alive(h);
+        u64* const used = run[3] ? h->used.ensure() : h->used.live();  // (the request kernel reads it; the others update it)
         if (run[0]) {
             c.nu = nu; c.u_idx = dm; c.u_node = dm + kSmallBatch;
             if (small_inline(&iu, nu, ops->update_idx, ops->update_node)) c.u_inl = &iu;
@@ -2518,11 +2567,11 @@ int rio_gp_mixed_batch(rio_gp_t* h, rio_gp_mixed* ops) {
                 memcpy(hs + kSmallBatch, ops->place_requester, np * sizeof(u32));
             }
             hs[4 * kSmallBatch] = 2;  // neither 0 nor 1: the kernel must write it
-            launch_pp_one(h->assign[h->cur], h->load, h->m, h->cap, h->alive_bits, h->used, ds, ds + kSmallBatch, np,
+            launch_pp_one(h->assign[h->cur], h->load, h->m, h->cap, h->alive_bits, used, ds, ds + kSmallBatch, np,
                           ds + 2 * kSmallBatch, ds + 3 * kSmallBatch, ds + 4 * kSmallBatch, h->stream, aff_life(h), small_done_dev(h), seq,
                           in_args ? &ip : nullptr, 0, nullptr, nullptr, h->sa, false, &c);
         } else {
-            launch_crud_small(c, h->assign[h->cur], h->load, h->m, h->used_valid ? h->used : nullptr, aff_life(h), small_done_dev(h), seq,
+            launch_crud_small(c, h->assign[h->cur], h->load, h->m, used, aff_life(h), small_done_dev(h), seq,
                               h->stream);
         }
     } else {
@@ -2533,16 +2582,16 @@ int rio_gp_mixed_batch(rio_gp_t* h, rio_gp_mixed* ops) {
             memcpy(hm, ops->update_idx, nu * sizeof(u32));
             memcpy(hm + kSmallBatch, ops->update_node, nu * sizeof(u32));
         }
-        fold_used(h);
+        u64* const used = h->used.live();
         launch_update_small(h->assign[h->cur], dm, dm + kSmallBatch, nu, h->stream, aff_life(h), small_done_dev(h),
-                            seq, in_args ? &inl : nullptr, h->used_valid ? h->used : nullptr, h->load, h->m);
+                            seq, in_args ? &inl : nullptr, used, h->load, h->m);
         inputs_changed(h);
     }
     if (run[1]) {
         const bool in_args = small_inline(&inl, nr, ops->remove_idx, nullptr);
         if (!in_args) memcpy(hm + 2 * kSmallBatch, ops->remove_idx, nr * sizeof(u32));
-        fold_used(h);
-        launch_remove_small(h->assign[h->cur], h->m, h->load, dm + 2 * kSmallBatch, nr, h->used_valid ? h->used : nullptr, h->stream,
+        u64* const used = h->used.live();
+        launch_remove_small(h->assign[h->cur], h->m, h->load, dm + 2 * kSmallBatch, nr, used, h->stream,
                             aff_life(h), small_done_dev(h), seq, in_args ? &inl : nullptr);
         inputs_changed(h);
     }
@@ -2554,14 +2603,14 @@ int rio_gp_mixed_batch(rio_gp_t* h, rio_gp_mixed* ops) {
     }
     if (run[3]) {
         flush_alive(h);
-        if ((rc = ensure_used(h))) return rc;
+        u64* const used = h->used.ensure();
         const bool in_args = small_inline(&inl, np, ops->place_idx, ops->place_requester);
         if (!in_args) {
             memcpy(hs, ops->place_idx, np * sizeof(u32));
             memcpy(hs + kSmallBatch, ops->place_requester, np * sizeof(u32));
         }
         hs[4 * kSmallBatch] = 2;  // neither 0 nor 1: the kernel must write it
-        launch_pp_one(h->assign[h->cur], h->load, h->m, h->cap, h->alive_bits, h->used, ds, ds + kSmallBatch, np,
+        launch_pp_one(h->assign[h->cur], h->load, h->m, h->cap, h->alive_bits, used, ds, ds + kSmallBatch, np,
                       ds + 2 * kSmallBatch, ds + 3 * kSmallBatch, ds + 4 * kSmallBatch, h->stream, aff_life(h), small_done_dev(h), seq,
                       in_args ? &inl : nullptr, 0, nullptr, nullptr, h->sa);
     }
@@ -2601,10 +2650,10 @@ int rio_gp_place_pending_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, con
         (((uintptr_t)d_idx | (uintptr_t)d_requester | (uintptr_t)d_out_node | (uintptr_t)d_out_flag) & 15u) == 0) {
         // up to 4 096 requests: the one-workgroup kernel first, reading the caller's device arrays in place (it validates the
         // entries itself) — ONE launch and one wait when the batch is sticky hits and first touches that fit
-        if ((rc = ensure_used(h))) return rc;
+        u64* const used = h->used.ensure();
         h->h_small[4 * kSmallBatch] = 2;
         const u32 seq = small_begin(h);
-        launch_pp_one(h->assign[h->cur], h->load, h->m, h->cap, h->alive_bits, h->used, d_idx, d_requester, (u32)n, d_out_node,
+        launch_pp_one(h->assign[h->cur], h->load, h->m, h->cap, h->alive_bits, used, d_idx, d_requester, (u32)n, d_out_node,
                       d_out_flag ? d_out_flag : h->d_mid + 3 * kMidBatch, h->d_small + 4 * kSmallBatch, h->stream, aff_life(h),
                       small_done_dev(h), seq, nullptr, (u32)h->n, h->pp_stage, h->mid_ticket, h->sa);
         if ((rc = small_wait(h, seq))) return rc;
@@ -2731,7 +2780,7 @@ int rio_gp_solve_profiled(rio_gp_t* h, float* scan_ms, float* resolve_ms) {
     const Table t = real_table(h);
     const NodeTab nt = scan_nodes(h);
     // hipExtLaunchKernelGGL start/stop events = the dispatch's own begin/end timestamps
-    fold_used(h);
+    h->used.fold_pending();  // (before k_resolve zeroes the D rows)
     h->sb.D = h->D;
     launch_scan(h->plan, t, nt, h->sb, false, h->all_alive, h->stream, h->ev0, h->ev1);
     launch_resolve(h->plan, nt, h->sb, slot_dev(h, 0), h->stream, h->ev2, h->ev3);
@@ -2794,7 +2843,7 @@ struct ShardScan { Table t; NodeTab nt; };
 static ShardScan shard_scan_begin(rio_gp* h) {
     h->plan = hplan(h, h->n);
     h->sb.fx = FxRows{};  // row-sharded solve: the fix-up counters are summed in DevStats (rio_gp_shard_finish reads them)
-    fold_used(h);
+    h->used.fold_pending();  // (nothing stays pending over a solve that publishes without D rows)
     const ShardScan s{real_table(h), real_nodes(h)};
     launch_scan(h->plan, s.t, s.nt, h->sb, false, h->all_alive, h->stream);
     return s;
@@ -2974,7 +3023,7 @@ RbBufs rb_bufs(rio_gp* h) {
 // A step continues the protocol only on the handle as begin left it: no call that changes an input of the solve (they all
 // count in mut_epoch) and none that rebuilt or republished `used` (which holds the protocol's vectors) came between.
 bool rb_at(rio_gp* h, int state) {
-    if (h->rb_state != 0 && (h->mut_epoch != h->rb_epoch || h->used_valid)) h->rb_state = 0;
+    if (h->rb_state != 0 && (h->mut_epoch != h->rb_epoch || !h->used.borrowed())) h->rb_state = 0;
     return h->rb_state == state;
 }
 int rb_ensure(rio_gp* h) {
@@ -3002,8 +3051,7 @@ int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, u
     inputs_changed(h);
     h->sh_state = 0;
     h->ring_n = 0;
-    h->used_parts = false;
-    h->used_valid = false;  // until rio_gp_shard_rebalance_finish: `used` holds the protocol's intermediate vectors
+    h->used.borrow();  // until rio_gp_shard_rebalance_finish: its storage holds the protocol's intermediate vectors
     h->rb_rank = rank; h->rb_R = n_ranks;
     h->rb_rounds = cfg->rounds ? cfg->rounds : h->rounds;
     h->rb_list = list_moves != 0;
@@ -3044,7 +3092,7 @@ int rio_gp_shard_rebalance_cut(rio_gp_t* h, const uint64_t* d_xg, uint64_t* d_s,
     a.Xg = reinterpret_cast<const u64*>(d_xg);
     a.rank = h->rb_rank; a.R = h->rb_R; a.m = m;
     a.T = b.tdev; a.live = b.live;
-    a.used = h->used; a.tgt = b.tgt; a.map = b.map; a.slot_node = b.slot_node; a.slot_free = b.slot_free; a.cut = b.cut;
+    a.used = h->used.storage(); a.tgt = b.tgt; a.map = b.map; a.slot_node = b.slot_node; a.slot_free = b.slot_free; a.cut = b.cut;
     a.info = b.info;
     launch_shrb_import_x(a, h->stream);
     HIPCHK(h, hipGetLastError());
@@ -3118,7 +3166,7 @@ int rio_gp_shard_rebalance_merge(rio_gp_t* h, const uint64_t* d_yg, uint64_t* pe
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_merge: nothing exported (rio_gp_shard_rebalance_select with rows selected, or _fill, first)");
     HIPCHK(h, hipSetDevice(h->device));
     const RbBufs b = rb_bufs(h);
-    launch_shrb_merge(reinterpret_cast<const u64*>(d_yg), h->rb_rank, h->rb_R, h->m, h->rb_first, h->used, b.base, b.acc + kRbPend,
+    launch_shrb_merge(reinterpret_cast<const u64*>(d_yg), h->rb_rank, h->rb_R, h->m, h->rb_first, h->used.storage(), b.base, b.acc + kRbPend,
                       h->stream);
     HIPCHK(h, hipGetLastError());
     u64 pend[2];
@@ -3141,7 +3189,7 @@ int rio_gp_shard_rebalance_fill(rio_gp_t* h, uint32_t round, uint64_t* d_y) {
     const RbBufs b = rb_bufs(h);
     const u64 K = h->rb_K;
     u32* pk_row = (u32*)h->sh_pk.p;
-    launch_shrb_round(K, pk_row, pk_row + K, pk_row + 2 * K, h->assign[h->cur], b.tgt, h->m, h->used, b.base,
+    launch_shrb_round(K, pk_row, pk_row + K, pk_row + 2 * K, h->assign[h->cur], b.tgt, h->m, h->used.storage(), b.base,
                       round + 1 == h->rb_rounds, (u64*)h->sh_chunk.p, b.C, b.ord, b.cntp, reinterpret_cast<u64*>(d_y), h->stream);
     HIPCHK(h, hipGetLastError());
     ++h->rb_fills;
@@ -3184,7 +3232,7 @@ int rio_gp_shard_rebalance_finish(rio_gp_t* h, rio_gp_rebalance_stats* local_sta
     u64 a[kShAcc];
     std::vector<u64> used(m ? m : 1);
     HIPCHK(h, hipMemcpyAsync(a, b.acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
-    if (m) HIPCHK(h, hipMemcpyAsync(used.data(), h->used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    if (m) HIPCHK(h, hipMemcpyAsync(used.data(), h->used.storage(), (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     s.surplus_rows = a[kShAccSurplusRows];
     s.surplus_load = a[kShAccSurplusLoad];
@@ -3205,7 +3253,7 @@ int rio_gp_shard_rebalance_finish(rio_gp_t* h, rio_gp_rebalance_stats* local_sta
     }
     if (n_moves) *n_moves = s.moved_rows;
     if (local_stats) *local_stats = s;
-    h->used_valid = true;  // the global `used` of the new column, on every rank
+    h->used.rebuilt();  // the global `used` of the new column, on every rank
     h->rb_state = 0;
     return RIO_GP_OK;
 }

@@ -2,6 +2,7 @@
 same seeded inputs — bit-exact (integer/index work).  Run on the GPU box: pytest -m gpu."""
 import json
 import os
+import types
 
 import numpy as np
 import pytest
@@ -848,6 +849,224 @@ def test_hand_offs_between_entry_point_families_on_one_handle(gp, oracle, seed, 
     c.tick("c: tick behind all of it")
     assert c.slow >= 1
     c.g.close()
+
+
+def _check_column_and_used(g, ref, load, m, what):
+    """the committed column against the reference, and `used` against the load sums of the column the handle itself returns"""
+    got = g.get_assign()
+    assert np.array_equal(got, ref), (what, np.flatnonzero(got != ref)[:10])
+    on = got < m
+    sums = np.bincount(got[on], weights=load[:len(got)][on].astype(np.float64), minlength=m).astype(np.uint64)   # (exact: < 2^53)
+    assert np.array_equal(g.get_nodes()[2], sums), what
+
+
+@pytest.mark.parametrize("seed,n,m", [(2, 4097, 64), (3, 70_001, 33)])
+def test_used_follows_every_publisher_into_every_reader(gp, oracle, seed, n, m, monkeypatch):
+    """The committed `used` vector is published by whole-table solves (with their D rows), in-place ticks, chained quiet ticks
+    (with their replicas), request-path solves and the rebalance, and is invalidated by everything that rewrites the column or
+    the loads behind its back.  Whatever state one of those leaves, every call that updates the vector in place or reads it must
+    find it whole: after each (state, reader) pair the column equals the reference and get_nodes()'s `used` equals the load
+    sums of get_assign() over the rows below n.
+      states   a. a committed tick that takes the fix-up  b. an in-place tick  c. three chained quiet ticks still in flight
+               d. a place_pending batch on the general path whose requesters run full  e. rebalance
+               f. the invalidators: update_batch above the medium-batch limit, set_assign, set_object_attrs with loads,
+                  set_num_objects down, and up again, remap_nodes dropping one node
+      readers  remove_batch of 3 / 200 / 5 000 entries, update_batch of 3 / 5 000, clean_server, mixed_batch with one entry of
+               each kind, place_pending of 100 requests, a tick
+    The test cannot see which kernels ran: the lab knobs force the forms (c checks the chain's launch counter, a / b / d the
+    oracle's verdict).  Shapes of the hand-off test above."""
+    import rebalance_ref
+    import spec_remap
+    monkeypatch.setenv("RIO_GP_OVERLAP_MIN_ROWS", "1")
+    rng = np.random.default_rng(9900 + seed)
+    cur, load, aff, cap0, alive0 = _rand_case(rng, n, m, p_none=0.1, cap_scale=1.3, p_alive=0.9, max_load=300 if seed % 2 else 3)
+    aff[rng.random(n) < 0.05] = 0xFFFFFFFE   # rows that are not objects
+    SPILLED, UNPLACED = 3, 4
+
+    # the handle and the reference's tables side by side (every row the handle holds: rows >= n are hidden, not gone)
+    T = types.SimpleNamespace(g=_mk(gp, n, m, load, aff, cap0, alive0, cur, 2, lab=True), ref=cur.copy(), load=load.copy(),
+                              aff=aff.copy(), cap=cap0.copy(), alive=alive0.copy(), n=n, m=m, in_flight=None)
+
+    def rows(k, unique=False):
+        return rng.choice(T.n, k, replace=False).astype(np.uint32) if unique else rng.integers(0, T.n, k).astype(np.uint32)
+
+    def set_nodes(cap, alive):
+        T.cap, T.alive = cap.copy(), alive.copy()
+        T.g.set_nodes(T.cap, T.alive)
+
+    def churn():
+        """tight capacities and a fresh tenth of the nodes down: the next tick evicts and spills"""
+        alive = (rng.random(T.m) < 0.88).astype(np.uint8)
+        alive[int(rng.integers(0, T.m))] = 0
+        total = int(T.load[:T.n].sum())
+        set_nodes(rng.integers(0, int(total * 1.3 / T.m) + 2, T.m).astype(np.uint64), alive)
+
+    def tick(what, slow=None):
+        nxt, used, ost = oracle.tick(T.ref[:T.n], T.load[:T.n], T.aff[:T.n], T.cap, T.alive, 2)
+        st = T.g.tick()
+        assert st == ost, (what, st, ost)
+        assert slow is None or ost["slow_path"] == slow, (what, ost)
+        T.ref[:T.n] = nxt
+
+    def place(idx, req):
+        used = oracle.recompute_used(T.ref[:T.n], T.load[:T.n], T.m)
+        node, flag = T.g.place_pending(idx, req)
+        wnode, wflag = oracle.place_pending(T.ref[:T.n], T.load[:T.n], T.cap, T.alive, used, idx, req)
+        assert np.array_equal(node, wnode) and np.array_equal(flag, wflag)
+        return wflag
+
+    def update(idx):
+        node = ((idx.astype(np.uint64) * 7 + 3) % T.m).astype(np.uint32)   # (a row named twice gets the same node twice)
+        T.g.update_batch(idx, node)
+        T.ref[idx] = node
+
+    # -- states --
+    def st_fixup_tick():
+        T.g.set_compact("never")
+        churn()
+        tick("a", slow=1)
+
+    def st_inplace_tick():
+        T.g.set_compact("always", inc="auto")
+        churn()
+        tick("b", slow=1)
+
+    def st_chained_ticks():
+        T.g.set_compact("auto")
+        set_nodes(np.full(T.m, int(T.load.sum()) + 1, np.uint64), np.ones(T.m, np.uint8))   # room for everybody: the second tick is quiet
+        want, before = [], T.g.chained_scans()
+        for k in range(5):
+            if k == 2:   # the second tick's verdict (fast path) is in: the three ticks from here on are links of one run
+                assert T.g.tick_wait() == want
+                want = []
+            T.g.tick_async()
+            nxt, used, ost = oracle.tick(T.ref[:T.n], T.load[:T.n], T.aff[:T.n], T.cap, T.alive, 2)
+            T.ref[:T.n] = nxt
+            want.append(ost)
+        assert T.g.chained_scans() == before + 3 and [w["slow_path"] for w in want] == [0, 0, 0]
+        T.in_flight = want
+
+    def st_request_solve():
+        used = oracle.recompute_used(T.ref[:T.n], T.load[:T.n], T.m)
+        set_nodes(used + np.uint64(2), np.ones(T.m, np.uint8))      # every node two units short of full
+        idx = rows(1500, unique=True)
+        T.g.remove_batch(idx)
+        T.ref[idx] = NONE
+        wflag = place(idx, rng.integers(0, max(T.m // 4, 1), 1500).astype(np.uint32))   # ... and a quarter of them asked for all of it
+        assert np.isin(wflag & 0x0F, (SPILLED, UNPLACED)).any()
+
+    def st_rebalance():
+        used = oracle.recompute_used(T.ref[:T.n], T.load[:T.n], T.m)
+        target = np.full(T.m, int(used.sum()) // T.m + 1, np.uint64)
+        nxt, _, wst, wrows, _, _ = rebalance_ref.rebalance(T.ref[:T.n], T.load[:T.n], T.aff[:T.n], T.cap, T.alive, target, None, 2)
+        gst, grows, _, _ = T.g.rebalance(target=target)
+        assert gst == wst and np.array_equal(grows, wrows) and wst["moved_rows"] > 0
+        T.ref[:T.n] = nxt
+
+    def st_big_update():
+        update(rows(20_000))
+
+    def st_set_assign():
+        col = rng.integers(0, T.m, T.n).astype(np.uint32)
+        col[rng.random(T.n) < 0.1] = NONE
+        T.g.set_assign(col)
+        T.ref[:T.n] = col
+
+    def st_set_loads():
+        idx = rows(1000, unique=True)
+        T.load[idx] = rng.integers(0, 300 if seed % 2 else 3, 1000).astype(np.uint32)
+        T.g.set_object_attrs(idx, load=T.load[idx])
+
+    def st_fewer_rows():
+        T.n = n - n // 3
+        T.g.set_num_objects(T.n)
+
+    def st_all_rows():
+        T.n = n
+        T.g.set_num_objects(T.n)
+
+    def st_drop_node():
+        map = spec_remap.stable_map(T.m, [int(rng.integers(0, T.m))])
+        w = spec_remap.remap(T.ref, T.aff, T.n, T.m, map, False, cap=T.cap, alive=T.alive)
+        assert T.g.remap_nodes(map) == w["evicted"]
+        T.ref, T.aff = np.ascontiguousarray(w["assign"], np.uint32), np.ascontiguousarray(w["aff"], np.uint32)
+        T.cap, T.alive, T.m = w["cap"], w["alive"], len(w["cap"])
+
+    # -- readers --
+    def rd_remove(k):
+        idx = rows(k)
+        T.g.remove_batch(idx)
+        T.ref[idx] = NONE
+
+    def rd_clean_server():
+        on = T.ref[:T.n][T.ref[:T.n] < T.m]
+        j = int(on[0]) if len(on) else 0
+        assert T.g.clean_server(j) == int((T.ref[:T.n] == j).sum())
+        T.ref[:T.n][T.ref[:T.n] == j] = NONE
+
+    def rd_mixed():
+        i = rows(4, unique=True)
+        node, req = np.uint32(int(rng.integers(0, T.m))), np.uint32(int(rng.integers(0, T.m)))
+        want_look = T.ref[i[2]]
+        T.ref[i[0]] = node
+        T.ref[i[1]] = NONE
+        used = oracle.recompute_used(T.ref[:T.n], T.load[:T.n], T.m)
+        wnode, wflag = oracle.place_pending(T.ref[:T.n], T.load[:T.n], T.cap, T.alive, used, i[3:4], np.array([req], np.uint32))
+        rc, look, pnode, pflag = T.g.mixed_batch(update=(i[0:1], [node]), remove=i[1:2], lookup=i[2:3], place=(i[3:4], [req]))
+        assert rc == [0, 0, 0, 0] and look[0] == want_look and pnode[0] == wnode[0] and pflag[0] == wflag[0]
+
+    states = [("a fix-up tick", st_fixup_tick), ("b in-place tick", st_inplace_tick), ("c chained ticks", st_chained_ticks),
+              ("d request solve", st_request_solve), ("e rebalance", st_rebalance), ("f big update", st_big_update),
+              ("f set_assign", st_set_assign), ("f set_object_attrs", st_set_loads), ("f fewer rows", st_fewer_rows),
+              ("f all rows again", st_all_rows), ("f remap_nodes", st_drop_node)]
+    readers = [("remove 3", lambda: rd_remove(3)), ("remove 200", lambda: rd_remove(200)), ("remove 5000", lambda: rd_remove(5000)),
+               ("update 3", lambda: update(rows(3, unique=True))), ("update 5000", lambda: update(rows(5000))),
+               ("clean_server", rd_clean_server), ("mixed_batch", rd_mixed),
+               ("place_pending 100", lambda: place(rows(100), rng.integers(0, T.m, 100).astype(np.uint32))),
+               ("tick", lambda: tick("reader"))]
+    try:
+        for rname, reader in readers:
+            for sname, state in states:
+                state()
+                reader()
+                _check_column_and_used(T.g, T.ref[:T.n], T.load, T.m, (sname, rname))
+                if T.in_flight is not None:
+                    assert T.g.tick_wait() == T.in_flight, (sname, rname)
+                    T.in_flight = None
+    finally:
+        T.g.close()
+
+
+def test_used_follows_the_window_sorted_request_solve(gp, oracle):
+    """The same for the third publisher of a solve's vector, the window-sorted request path: it needs 2^18 requests over 32 row
+    windows (pp_win_applicable), device resident, and capacities cut so that the window kernels' verdict is "needs the solve"
+    (requesters run full: spills).  Behind it a 200-entry remove_batch, which updates `used` in place."""
+    from hipbuf import DevBuf
+    rng = np.random.default_rng(9910)
+    n, m = 1 << 18, 64
+    load = rng.integers(0, 30, n).astype(np.uint32)
+    cap = np.full(m, int(load.sum()) // (2 * m), np.uint64)       # room for half of the load
+    alive = np.ones(m, np.uint8)
+    g = gp.GpuPlacement(n, m)
+    g.set_nodes(cap, alive)
+    g.set_objects(n, load, None)
+    ref, used = np.full(n, NONE, np.uint32), np.zeros(m, np.uint64)
+    idx, req = rng.permutation(n).astype(np.uint32), rng.integers(0, m, n).astype(np.uint32)
+    d_idx, d_req, d_node, d_flag = DevBuf(idx), DevBuf(req), DevBuf(nbytes=4 * n), DevBuf(nbytes=4 * n)
+    try:
+        g.place_pending_dev(n, d_idx.ptr, d_req.ptr, d_node.ptr, d_flag.ptr)
+        node, flag = d_node.to_host(), d_flag.to_host()
+        wnode, wflag = oracle.place_pending(ref, load, cap, alive, used, idx, req)
+        assert np.array_equal(node, wnode) and np.array_equal(flag, wflag)
+        assert np.isin(wflag & 0x0F, (3, 4)).any()                 # spilled / unplaced: the solve ran and took its fix-up
+        rm = rng.integers(0, n, 200).astype(np.uint32)
+        g.remove_batch(rm)
+        ref[rm] = NONE
+        _check_column_and_used(g, ref, load, m, "window-sorted request solve, remove 200")
+    finally:
+        for x in (d_idx, d_req, d_node, d_flag):
+            x.free()
+        g.close()
 
 
 def test_async_ticks_equal_the_synchronous_stream(gp, oracle):
