@@ -196,6 +196,179 @@ struct TickSlot {
     bool quiet = false;  // it was enqueued without its fix-up (checked against its verdict when harvested)
 };
 
+// host-side fold of the per-workgroup partial rows k_resolve (or a chained scan) stored into a pinned slot; mark != 0: every row
+// must carry it (*bad is set where one does not)
+static DevStats reduce_rows(const u64* rows, u32 nrows, u64 mark = 0, bool* bad = nullptr) {
+    DevStats d;
+    memset(&d, 0, sizeof d);
+    for (u32 r = 0; r < nrows; ++r) {
+        const u64* x = rows + (size_t)r * 8;
+        if (mark && x[7] != mark && bad) *bad = true;
+        d.load_kept += x[0]; d.load_claim_tot += x[1]; d.n_cut += x[2];
+        d.kept += x[3]; d.evicted += x[4]; d.claimants += x[5]; d.spillcand += x[6];
+    }
+    return d;
+}
+static bool needs_fixup(const DevStats& v) { return v.n_cut > 0 || v.spillcand > 0; }
+
+// What is in flight on the pinned verdict slots (h_slots / d_slots: 2 kRing slots of slot_rows rows of 8 words).  The table has two
+// halves, each with ONE cursor, and the fix-up counter rows (h_fx) have a slot per half-slot that needs one:
+//
+//   client                                        verdict slots              counter rows (fx)    cursor
+//   rio_gp_solve, _tick, _solve_profiled, the     0                          0                    none: they abandon() the solve
+//     request path (synchronous: they wait)                                                        half; whatever it held is lost
+//   rio_gp_solve_async                            [0, kRing), n % kRing      0 (rio_gp_solve_wait) SolveRing, Owner::solves
+//   rio_gp_shard_resolve, _shard_solve_async      [0, kRing), n % kRing      none (DevStats)      SolveRing, Owner::shard
+//     (rio_gp_shard_merge: slot 0, read at once)
+//   rio_gp_tick_async                             kRing + k                  1 + k                TickRing, Owner::ticks
+//   rio_gp_shard_tick_async                       kRing + k                  1 + k (its record)   TickRing, Owner::shard_ticks
+//
+// Who may start while what is in flight (may_start; every refusal is RIO_GP_EINVAL and changes nothing):
+//   * The two owners of the tick half exclude each other: the same slots, the same counter rows.  rio_gp_tick_async harvests
+//     its own ring when it is full; rio_gp_shard_tick_async refuses at kRing in flight (a harvest would need its peers).
+//   * A tick of either kind does not start while the solve half's cursor is off 0: it publishes (the columns swap), and the
+//     solves in flight still have their fix-up and their commit to come (rio_gp_solve_wait, rio_gp_shard_cut ... _finish).
+//   * Row-sharded ticks in flight keep out the calls that start another asynchronous solve or reset the row-sharded
+//     protocol: rio_gp_solve_async, rio_gp_shard_solve_async, rio_gp_shard_rebalance_begin.
+//   * Everything else coexists.  Synchronous solves and rio_gp_solve_async run beside ticks in flight: they use the other
+//     half and fx slot 0, and stream order puts them behind the ticks.  A synchronous solve abandons asynchronous solves in
+//     flight (their verdicts are never read); rio_gp_tick_async ticks stay in flight across any other call until harvested.
+//   * Not decided here, and not refused today: the two owners of the solve half advance the one cursor (rio_gp_solve_async with
+//     a row-sharded solve at "resolved", and the other way round); rio_gp_shard_scan / _resolve with ticks in flight.
+struct SolveRing {
+    enum class Owner { none, solves, shard };
+    // rio_gp_solve_async:
+    SolveForm form{};           // the form of the last one: rio_gp_solve_wait enqueues its fix-up
+    PendingSolve last{};        // ... and what it becomes once rio_gp_solve_wait has finished it (in flight, not yet pending)
+
+    void init(const u64* host_slots, size_t slot_words) { host = host_slots; words = slot_words; }
+    Owner owned_by() const { return owner; }
+    bool in_flight() const { return n != 0; }
+    bool any_solves() const { return any; }
+    bool full() const { return n >= (u32)kRing; }            // rio_gp_solve_async recycles; row-sharded enqueues wrap
+    u32 next_slot() const { return n % kRing; }               // where the next enqueue stores its verdict rows
+    const u64* rows_host(u32 k) const { return host + (size_t)(k % kRing) * words; }
+    void pushed(Owner o) { owner = o; ++n; if (o == Owner::solves) any = true; }
+    void pushed_shard(u32 rows) { sh_slot = n; sh_rows = rows; pushed(Owner::shard); }
+    // the ring is full: the verdicts of the solves in it are folded into the running count before their slots are overwritten
+    void recycle(u32 nrows) {
+        for (u32 k = 0; k < n; ++k) slow += needs_fixup(verdict(k, nrows));
+        n = 0;
+    }
+    // The synchronous solves: whatever was in flight is never waited for.
+    void abandon() { rewind(); slow = 0; any = false; }
+    // The cursor alone (row-sharded protocol resets, rio_gp_shard_verdict): a rio_gp_solve_async count survives it, as it always has.
+    void rewind() { n = 0; owner = Owner::none; }
+    // rio_gp_solve_wait, after the stream: the last solve's verdict + how many of ALL the solves since the last wait took the fix-up
+    // path.  (n == 0 with solves enqueued: only behind a rewind(); the last slot is read, as it always has been.)
+    DevStats fold(u32 nrows, uint32_t* n_slow) {
+        DevStats v;
+        memset(&v, 0, sizeof v);
+        if (n == 0) v = verdict(kRing - 1, nrows);
+        for (u32 k = 0; k < n; ++k) {
+            v = verdict(k, nrows);
+            slow += needs_fixup(v);
+        }
+        *n_slow = slow;
+        slow = 0;
+        any = false;
+        return v;
+    }
+    PendingSolve finish() { rewind(); return last; }  // the last solve of the ring is finished: it waits for its commit
+    // rio_gp_shard_verdict, after the streams: x = the column sums of the last resolve's rows (0: cut nodes, 1: spill rows); returns
+    // how many of the (at most kRing) resolves since the last verdict need the fix-up.  Ends with the cursor at 0.
+    uint32_t shard_fold(u64 x[8]) {
+        uint32_t cnt = 0;
+        for (u32 k = n > (u32)kRing ? n - kRing : 0; k < n; ++k) {
+            shard_sums(k, x);
+            cnt += (x[0] > 0 || x[1] > 0);
+        }
+        shard_sums(sh_slot, x);
+        rewind();
+        return cnt;
+    }
+
+  private:
+    DevStats verdict(u32 k, u32 nrows) const { return reduce_rows(rows_host(k), nrows); }
+    void shard_sums(u32 k, u64 x[8]) const {  // one verdict row (k_shard_import) or one partial row per workgroup (k_resolve_xchg)
+        for (int c = 0; c < 8; ++c) x[c] = 0;
+        for (u32 r = 0; r < sh_rows; ++r)
+            for (int c = 0; c < 8; ++c) x[c] += rows_host(k)[(size_t)r * 8 + c];
+    }
+    const u64* host = nullptr;  // h_slots
+    size_t words = 0;           // u64 words per slot
+    Owner owner = Owner::none;  // whose enqueue moved the cursor last (none: the cursor is at 0)
+    u32 n = 0;                  // the cursor: the next enqueue stores its verdict rows into slot n % kRing
+    u32 sh_slot = 0;            // row-sharded solves: verdict slot of the last resolve
+    u32 sh_rows = 1;            // ... and its verdict rows there: 1 (k_shard_import) | resolve_blocks(m) (k_resolve_xchg)
+    u32 slow = 0;      // fix-up verdicts among the rio_gp_solve_async solves whose ring slots were recycled
+    bool any = false;  // a rio_gp_solve_async solve has been enqueued since the last rio_gp_solve_wait / abandon()
+};
+
+struct TickRing {
+    enum class Owner { none, ticks, shard_ticks };
+    u32 peeked = 0;             // Owner::ticks: ticks [0, peeked) have had their verdicts looked at (peek_ticks)
+    TickSlot slot[kRing];       // Owner::ticks
+    u64 shard_mark[kRing] = {}; // Owner::shard_ticks: word 15 of tick k's record (k_shard_tick_stats)
+    std::vector<rio_gp_stats> done;  // harvested rio_gp_tick_async ticks rio_gp_tick_wait has not handed out yet
+
+    void init(u64* host_slots, u64* dev_slots, size_t slot_words) {
+        host = host_slots + (size_t)kRing * slot_words;
+        dev = dev_slots + (size_t)kRing * slot_words;
+        words = slot_words;
+    }
+    u32 count(Owner o) const { return owner == o ? n : 0; }  // ticks of that owner in flight: [0, count)
+    bool full() const { return n == (u32)kRing; }
+    u32 next_slot() const { return n; }                       // the tick the next enqueue becomes
+    void pushed(Owner o) { owner = o; ++n; }
+    void clear() { owner = Owner::none; n = 0; peeked = 0; }
+    static u32 fx_slot(u32 k) { return 1 + k; }
+    u64* rows_dev(u32 k) const { return dev + (size_t)(k % kRing) * words; }
+    const u64* rows_host(u32 k) const { return host + (size_t)(k % kRing) * words; }
+    DevStats reduce(u32 k, bool* bad) const { return reduce_rows(rows_host(k), slot[k % kRing].rows, slot[k % kRing].mark, bad); }
+
+  private:
+    u64 *host = nullptr, *dev = nullptr;  // the tick half of h_slots / d_slots
+    size_t words = 0;
+    Owner owner = Owner::none;  // none <=> n == 0
+    u32 n = 0;                  // in flight: ticks [0, n), tick k in verdict slot kRing + k and fx slot fx_slot(k)
+};
+
+// The row-sharded solve (rio_gp_shard_*): the step the protocol is at and what travels with it.
+enum class ShStep { idle, scanned, resolved, cut_exported, merged, spill_exported };
+struct ShardSolve {
+    ShStep step = ShStep::idle;
+    bool slow = false;   // the solve in flight took the fix-up path (rio_gp_shard_verdict)
+    u32 rank = 0, R = 1;
+    hipStream_t side = nullptr;  // stream the last resolve ran on, when not the handle's
+    bool at(ShStep s) const { return step == s; }
+    void bind(u32 rank_, u32 R_, hipStream_t side_) { rank = rank_; R = R_; side = side_; }  // what the next resolve runs as
+};
+
+// The row-sharded rebalance (rio_gp_shard_rebalance_*): the step, what the gathered records said, the host's copies of the
+// targets and the live flags (they outlive the calls that upload them).  rio_gp_shard_rebalance_begin assigns a fresh one.
+enum class RbStep { idle, begun /* X out */, cut /* surplus record out */, selected /* Y out */, merged, round_exported };
+struct RbSession {
+    RbStep step = RbStep::idle;
+    u32 rank = 0, R = 1, rounds = 0, fills = 0;
+    bool list = false, first = false;
+    u64 budget = 0, K = 0, sel_total = 0, pending = 0;
+    u32 over = 0, over_before = 0;
+    u64 epoch = 0;  // mut_epoch as rio_gp_shard_rebalance_begin left it: any other change of the inputs ends the protocol
+    ShPlan plan{};
+    std::vector<u64> T;
+    std::vector<u32> live;
+    // A step continues the protocol only on the handle as begin left it: no call that changes an input of the solve (they all
+    // count in mut_epoch) and none that rebuilt or republished `used` (which holds the protocol's vectors) came between.
+    bool at(const rio_gp* h, RbStep s);
+    bool finished() const {
+        return (step == RbStep::cut && !over) || (step == RbStep::selected && !sel_total) ||
+               (step == RbStep::merged && (!pending || fills == rounds));
+    }
+    u64 listed_rows() const { return step == RbStep::merged ? K : 0; }    // rows whose moves _finish applies and lists
+    u64 selected_rows() const { return step == RbStep::selected || step == RbStep::merged || step == RbStep::round_exported ? K : 0; }
+};
+
 struct rio_gp {
     ShardComm* sc = nullptr;
     P2P* p2p = nullptr;
@@ -239,16 +412,9 @@ struct rio_gp {
     bool all_alive = true;
     Plan plan{};
     PendingSolve pending{};
-    u32 ring_n = 0;
-    u32 ring_slow = 0;     // fix-up verdicts among the rio_gp_solve_async solves whose ring slots were recycled
-    bool ring_any = false; // a rio_gp_solve_async solve has been enqueued since the last rio_gp_solve_wait
-    SolveForm ring_form{};      // ... the form of the last one: rio_gp_solve_wait enqueues its fix-up
-    PendingSolve ring_last{};   // ... and what it becomes once rio_gp_solve_wait has finished it (in flight, not yet pending)
-    // asynchronous committed ticks (rio_gp_tick_async): verdict slots [kRing, 2 kRing) and their own ring of device-stats
-    // copies, so that synchronous calls made while ticks are in flight do not touch what has not been harvested yet
-    u32 tick_n = 0;
-    TickSlot tick_ring[kRing];
-    std::vector<rio_gp_stats> tick_done;
+    // what is in flight on the two halves of the slot table (above): asynchronous / row-sharded solves, ticks of either kind
+    SolveRing solves;
+    TickRing ticks;
     // fix-up counters as per-workgroup rows (FxRows, placement_kernels.h): device rows + pinned slots [1 + kRing][kMaxBlocks][8]
     // (slot 0: synchronous solves, slots 1..kRing: asynchronous ticks)
     u64* fx_dev = nullptr;
@@ -261,12 +427,7 @@ struct rio_gp {
     // global resolve of the PREVIOUS solve may still be writing on the exchange stream
     u64 *sh_lkept = nullptr, *sh_lclaim = nullptr, *sh_lcur = nullptr;
     u32 *sh_lcutblk = nullptr, *sh_lcutidx = nullptr;
-    u32 sh_rows = 1;        // verdict rows of the last shard resolve in its pinned slot (1 | resolve_blocks(m))
-    u32 sh_rank = 0, sh_R = 1;
-    int sh_state = 0;       // 0 idle | 1 scanned | 2 resolved | 3 cut exported | 4 merged | 5 spill exported
-    bool sh_slow = false;   // the solve in flight took the fix-up path
-    u32 sh_slot = 0;        // verdict slot of the last rio_gp_shard_resolve
-    hipStream_t sh_side = nullptr;  // stream the last rio_gp_shard_resolve ran on, when not the handle's
+    ShardSolve sh;  // ... and the protocol's step
     // packed fix-up (PackOut, placement_kernels.h): scratch columns + per-wave counts; chosen adaptively per tick
     PackOut pk{};
     SolveStats last{};
@@ -274,7 +435,6 @@ struct rio_gp {
     // (mut_epoch counts those) every further tick keeps every row where it is, and rio_gp_tick_async enqueues no speculative
     // fix-up behind it: two launches a tick instead of five.  quiet_epoch = the mut_epoch such a tick was enqueued under.
     u64 mut_epoch = 0, quiet_epoch = ~0ull;
-    u32 tick_peeked = 0;               // ticks [0, tick_peeked) of the ring have had their verdicts looked at
     int compact_mode = 0;  // 0 auto | 1 always | 2 never (rio_gp_debug_set_compact)
     // A committed tick over a mostly-placed table updates the assignment column in place and builds no kept histogram
     // (k_inc_scan), then k_rebal deals the pending rows out evenly to the fix-up's workgroups: 0 auto | 2 never (bits 7-8
@@ -341,8 +501,6 @@ struct rio_gp {
     DevBuf vrec;  // big place_pending batches: virtual-table records {cur | load}, 8 bytes per request
     DevBuf part;  // scratch of the partitioned update / remove batches (records + fragment tables)
     bool timer_stopped = false;  // rio_gp_timer_stop has recorded the closing event of the measurement in progress
-    u32 sh_tick_n = 0;    // asynchronous row-sharded ticks in flight (their records: verdict slots of the tick ring, h_fx slots)
-    u64 sh_tick_mark[kRing] = {};
     // reverse placement index (rio_gp_rows_on_nodes), allocated on first use: the (slot x tile) matrix, chunk sums + total, the
     // node -> slot map on the device, the offsets of the host-pointer form; the map and the ranks are built in mapped pinned memory
     u32 *ni_cnt = nullptr, *ni_part = nullptr, *ni_map = nullptr;
@@ -353,17 +511,7 @@ struct rio_gp {
     // bounded rebalance (rio_gp_rebalance), grown on use: per-node arrays + counters, the (over node x tile) matrix, per-tile and
     // per-chunk counts, the packed rows (row | load | node), the host-pointer form's move listing (row | from | to)
     DevBuf sh_nodes, sh_mat, sh_tile, sh_chunk, sh_pk, sh_mv;
-    // row-sharded rebalance (rio_gp_shard_rebalance_*): the protocol's step, what the gathered records said, the host's copies
-    // of the targets and the live flags (they outlive the calls that upload them)
-    int rb_state = 0;        // 0 idle | 1 begun (X out) | 2 cut (surplus record out) | 3 selected (Y out) | 4 merged | 5 round exported
-    u32 rb_rank = 0, rb_R = 1, rb_rounds = 0, rb_fills = 0;
-    bool rb_list = false, rb_first = false;
-    u64 rb_budget = 0, rb_K = 0, rb_sel_total = 0, rb_pending = 0;
-    u32 rb_over = 0, rb_over_before = 0;
-    u64 rb_epoch = 0;        // mut_epoch as rio_gp_shard_rebalance_begin left it: any other change of the inputs ends the protocol
-    ShPlan rb_plan{};
-    std::vector<u64> rb_T;
-    std::vector<u32> rb_live;
+    RbSession rb;  // row-sharded rebalance (rio_gp_shard_rebalance_*)
     // change feed (rio_gp_changes), allocated on first use: the checkpoint column B (cap_rows u32, RIO_GP_NONE to begin with), the
     // per-tile counts, the workgroup sums + total, a mapped word the total arrives in; the host-pointer form's staged listing
     // (row | old | new, grows to the largest listing)
@@ -413,6 +561,11 @@ void UsedVec::publish(const PendingSolve& ps) {
     parts = vec + h->m;
 }
 void UsedVec::publish_request(bool vslow) { swap_in(vslow); }
+
+bool RbSession::at(const rio_gp* h, RbStep s) {
+    if (step != RbStep::idle && (h->mut_epoch != epoch || !h->used.borrowed())) step = RbStep::idle;
+    return step == s;
+}
 
 namespace {
 
@@ -502,7 +655,7 @@ void fill_stats(const DevStats& d, u64 n, rio_gp_stats* s) {
     s->load_spilled = d.load_spilled;
     s->load_unplaced = d.load_unplaced;
     s->cut_nodes = (uint32_t)d.n_cut;
-    s->slow_path = (d.n_cut > 0 || d.spillcand > 0) ? 1u : 0u;
+    s->slow_path = needs_fixup(d) ? 1u : 0u;
     s->rounds_run = (uint32_t)d.rounds_run;
 }
 
@@ -736,29 +889,29 @@ void enqueue_slow_packed(rio_gp* h, const SolveForm& f, const NodeTab& nt) {
     enqueue_slow(h, f, f.fix_plan, vt, nt, true);
 }
 
-u64* slot_dev(rio_gp* h, u32 k) { return h->d_slots + (size_t)(k % kRing) * h->slot_rows * 8; }
-constexpr u32 kTickSlot0 = (u32)kRing;  // slot index k >= kRing: the asynchronous ticks' half of the slot table
+u64* slot_dev(rio_gp* h, u32 k) { return h->d_slots + (size_t)(k % kRing) * h->slot_rows * 8; }  // solve half
+DevStats reduce_slot(rio_gp* h, u32 k, u32 m) { return reduce_rows(h->solves.rows_host(k), resolve_blocks(m)); }
 
-// host-side fold of the per-workgroup partial rows k_resolve (or a chained scan) stored into a pinned slot; mark != 0: every row
-// must carry it (*bad is set where one does not)
-DevStats reduce_rows(rio_gp* h, size_t slot, u32 nrows, u64 mark = 0, bool* bad = nullptr);
-DevStats reduce_slot(rio_gp* h, u32 k, u32 m) { return reduce_rows(h, k % kRing, resolve_blocks(m)); }  // solve ring
-u64* tick_rows_host(rio_gp* h, u32 k) { return h->h_slots + (size_t)(kTickSlot0 + k % kRing) * h->slot_rows * 8; }
-DevStats reduce_tick_slot(rio_gp* h, u32 k, bool* bad) {  // tick ring
-    return reduce_rows(h, kTickSlot0 + k % kRing, h->tick_ring[k % kRing].rows, h->tick_ring[k % kRing].mark, bad);
+// May `who` start now?  The one place that decides it, and that words the refusals (the table above SolveRing says why).
+enum class Client { tick_async, solve_async, shard_solve_async, shard_tick_async, shard_rebalance_begin };
+int may_start(rio_gp* h, Client who) {
+    static const char* const name[] = {"rio_gp_tick_async", "rio_gp_solve_async", "rio_gp_shard_solve_async", "rio_gp_shard_tick_async",
+                                       "rio_gp_shard_rebalance_begin"};
+    const bool tick = who == Client::tick_async || who == Client::shard_tick_async;
+    const char* why = nullptr;
+    if (tick && h->solves.in_flight())
+        why = h->solves.owned_by() == SolveRing::Owner::shard ? "a row-sharded solve is in flight (finish it: rio_gp_shard_verdict ... rio_gp_shard_finish)"
+                                                         : "rio_gp_solve_async solves are in flight (call rio_gp_solve_wait)";
+    else if (who != Client::shard_tick_async && h->ticks.count(TickRing::Owner::shard_ticks))
+        why = "row-sharded ticks are in flight (call rio_gp_shard_tick_wait)";
+    else if (who == Client::shard_tick_async && h->ticks.count(TickRing::Owner::ticks))
+        why = "rio_gp_tick_async ticks are in flight (call rio_gp_tick_wait)";
+    else if (who == Client::shard_tick_async && h->ticks.full())
+        why = "64 ticks in flight (call rio_gp_shard_tick_wait)";
+    return why ? fail(h, RIO_GP_EINVAL, std::string(name[(int)who]) + ": " + why) : RIO_GP_OK;
 }
-DevStats reduce_rows(rio_gp* h, size_t slot, u32 nrows, u64 mark, bool* bad) {
-    DevStats d;
-    memset(&d, 0, sizeof d);
-    const u64* rows = h->h_slots + slot * h->slot_rows * 8;
-    for (u32 r = 0; r < nrows; ++r) {
-        const u64* x = rows + (size_t)r * 8;
-        if (mark && x[7] != mark && bad) *bad = true;
-        d.load_kept += x[0]; d.load_claim_tot += x[1]; d.n_cut += x[2];
-        d.kept += x[3]; d.evicted += x[4]; d.claimants += x[5]; d.spillcand += x[6];
-    }
-    return d;
-}
+// rio_gp_rebalance, rio_gp_changes, rio_gp_changes_reset and rio_gp_remap_nodes work on a whole table: not on one rank's rows
+bool row_sharded(const rio_gp* h) { return h->sc || h->p2p || h->ticks.count(TickRing::Owner::shard_ticks); }
 
 // the fix-up kernels of the next solve write their per-workgroup counter rows into pinned slot `slot` (0: synchronous
 // solves, 1 + k: asynchronous tick k)
@@ -837,7 +990,7 @@ int commit_enqueue(rio_gp* h) {
 int solve_locked(rio_gp* h, rio_gp_stats* stats, bool commit = false) {
     InplaceGuard ipg{h};
     h->plan = hplan(h, h->n);
-    h->ring_n = 0; h->ring_slow = 0; h->ring_any = false;
+    h->solves.abandon();
     use_fx_slot(h, 0);
     const u64 seq = ++h->wait_seq;
     h->plan.mark = seq;  // k_resolve's partial rows carry it ...
@@ -859,13 +1012,13 @@ int solve_locked(rio_gp* h, rio_gp_stats* stats, bool commit = false) {
     if (!spec) {
         if (!spin_rows(vrows, resolve_blocks(h->m), seq)) HIPCHK(h, hipStreamSynchronize(h->stream));
         v = reduce_slot(h, 0, h->m);
-        slow = v.n_cut > 0 || v.spillcand > 0;
+        slow = needs_fixup(v);
     }
     if (spec || slow) {
         if (f.compact) enqueue_slow_packed(h, f, nt);
         else enqueue_slow(h, f, h->plan, t, nt, false);
     }
-    h->ring_n = 0; h->ring_slow = 0; h->ring_any = false;
+    h->solves.abandon();
     if (commit) {
         int rc = commit_enqueue(h);
         if (rc) return rc;
@@ -873,7 +1026,7 @@ int solve_locked(rio_gp* h, rio_gp_stats* stats, bool commit = false) {
     if (spec) {
         if (!(fx_last && spin_rows(h->h_fx, h->plan.G, seq))) HIPCHK(h, hipStreamSynchronize(h->stream));
         v = reduce_slot(h, 0, h->m);
-        slow = v.n_cut > 0 || v.spillcand > 0;
+        slow = needs_fixup(v);
         if (slow) fold_fx(h, 0, h->plan.G, &v);  // the water-fill rounds stored every workgroup's row into the pinned slot
     } else if (slow) {
         int rc = merge_slow(h, &v);  // waits for the last round's rows (or the stream)
@@ -889,58 +1042,58 @@ int solve_locked(rio_gp* h, rio_gp_stats* stats, bool commit = false) {
 // wait for the asynchronous ticks in flight and turn their verdict slots + device-stats copies into rio_gp_stats
 // verdicts of enqueued ticks that have already landed in their pinned slots (every row carries the tick's mark): no wait
 void peek_ticks(rio_gp* h) {
-    for (; h->tick_peeked < h->tick_n; ++h->tick_peeked) {
-        const u32 k = h->tick_peeked;
-        const TickSlot& tk = h->tick_ring[k];
+    TickRing& tr = h->ticks;
+    for (const u32 n = tr.count(TickRing::Owner::ticks); tr.peeked < n; ++tr.peeked) {
+        const u32 k = tr.peeked;
+        const TickSlot& tk = tr.slot[k];
         if (tk.quiet) continue;  // (a quiet tick was enqueued under the quiet rule already: its verdict cannot start it)
-        const volatile u64* rows = tick_rows_host(h, k);
+        const volatile u64* rows = tr.rows_host(k);
         for (u32 r = 0; r < tk.rows; ++r)
             if (rows[(size_t)r * 8 + 7] != tk.mark) return;
         std::atomic_thread_fence(std::memory_order_acquire);
-        const DevStats v = reduce_tick_slot(h, k, nullptr);
-        if (!(v.n_cut > 0 || v.spillcand > 0) && tk.epoch == h->mut_epoch) h->quiet_epoch = h->mut_epoch;
+        if (!needs_fixup(tr.reduce(k, nullptr)) && tk.epoch == h->mut_epoch) h->quiet_epoch = h->mut_epoch;
     }
 }
 
 int harvest_ticks(rio_gp* h) {
-    if (!h->tick_n) return RIO_GP_OK;
+    TickRing& tr = h->ticks;
+    const u32 n = tr.count(TickRing::Owner::ticks);
+    if (!n) return RIO_GP_OK;
     chain_join(h);
     // When the last tick in flight is a quiet one, the verdict rows are the last thing every tick writes (a chained scan's
     // workgroups store theirs behind their adds; the k_resolve of a quiet tick on the main stream is its tick's last kernel) and
     // the last tick's kernels ran behind everything older: spin on the rows of EVERY tick in flight in mapped memory instead of
     // asking the runtime (launch + hipStreamSynchronize 12.6 us, launch + spin 7.3: tools/sync_probe.py) — the rows of two chained
     // links land in any order.  Not there after 50 ms: the stream is asked.
-    const u32 last = h->tick_n - 1;
-    bool landed = h->tick_ring[last].quiet;
-    for (u32 k = 0; landed && k < h->tick_n; ++k) landed = spin_rows(tick_rows_host(h, k), h->tick_ring[k].rows, h->tick_ring[k].mark);
+    bool landed = tr.slot[n - 1].quiet;
+    for (u32 k = 0; landed && k < n; ++k) landed = spin_rows(tr.rows_host(k), tr.slot[k].rows, tr.slot[k].mark);
     if (!landed) HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (h->h_chain_err && *reinterpret_cast<volatile u32*>(h->h_chain_err)) {  // never seen; must not pass silently if it happens
         *h->h_chain_err = 0;
-        h->tick_n = 0;
+        tr.clear();
         return fail(h, RIO_GP_EUPSTREAM, "rio_gp_tick_wait: a chained scan gave up waiting for the previous tick's rows (tables are stale: reload them)");
     }
-    h->tick_peeked = 0;
-    for (u32 k = 0; k < h->tick_n; ++k) {
+    for (u32 k = 0; k < n; ++k) {
         bool bad = false;
-        DevStats v = reduce_tick_slot(h, k, &bad);
+        DevStats v = tr.reduce(k, &bad);
         if (bad) {  // a verdict row without its tick's mark after the stream is done: never seen; must not pass silently
-            h->tick_n = 0;
+            tr.clear();
             return fail(h, RIO_GP_EUPSTREAM, "rio_gp_tick_wait: a tick's verdict rows are incomplete (tables are stale: reload them)");
         }
-        const bool slow = v.n_cut > 0 || v.spillcand > 0;
-        if (slow && h->tick_ring[k].quiet) {  // cannot happen (see mut_epoch); if it ever does it must not pass silently
-            h->tick_n = 0;
+        const bool slow = needs_fixup(v);
+        if (slow && tr.slot[k].quiet) {  // cannot happen (see mut_epoch); if it ever does it must not pass silently
+            tr.clear();
             return fail(h, RIO_GP_EUPSTREAM, "rio_gp_tick_wait: a tick that was enqueued without its fix-up needed one (tables are stale: reload them)");
         }
-        if (!slow && h->tick_ring[k].epoch == h->mut_epoch) h->quiet_epoch = h->mut_epoch;
-        if (slow) fold_fx(h, 1 + k, h->tick_ring[k].G, &v);
+        if (!slow && tr.slot[k].epoch == h->mut_epoch) h->quiet_epoch = h->mut_epoch;
+        if (slow) fold_fx(h, TickRing::fx_slot(k), tr.slot[k].G, &v);
         rio_gp_stats st;
         fill_stats(v, h->n, &st);
-        h->tick_done.push_back(st);
+        tr.done.push_back(st);
         h->last.record(v, slow, false);
     }
-    h->tick_n = 0;
+    tr.clear();
     return RIO_GP_OK;
 }
 
@@ -949,10 +1102,9 @@ int harvest_ticks(rio_gp* h) {
 // the publication (two pointer swaps, host side) and an asynchronous copy of the device accumulators into this tick's
 // pinned record.  The result is the one rio_gp_tick computes; only the counters arrive later (rio_gp_tick_wait).
 int tick_async_locked(rio_gp* h) {
-    if (h->ring_n) return fail(h, RIO_GP_EINVAL, "rio_gp_tick_async: rio_gp_solve_async solves are in flight (call rio_gp_solve_wait)");
-    // (the row-sharded ticks keep their records in the same verdict slots and counter rows)
-    if (h->sh_tick_n) return fail(h, RIO_GP_EINVAL, "rio_gp_tick_async: row-sharded ticks are in flight (call rio_gp_shard_tick_wait)");
-    if (h->tick_n == (u32)kRing) { int rc = harvest_ticks(h); if (rc) return rc; }
+    int rc = may_start(h, Client::tick_async);
+    if (rc) return rc;
+    if (h->ticks.full() && (rc = harvest_ticks(h))) return rc;
     peek_ticks(h);
     // nothing has changed since a tick that left every object placed: this one keeps every row, no fix-up can be needed
     // (lab builds: rio_gp_debug_set_speculate(always) keeps the launches)
@@ -976,11 +1128,11 @@ int tick_async_locked(rio_gp* h) {
     h->plan = hplan(h, h->n);
     const Table t = real_table(h);
     const NodeTab nt = scan_nodes(h);
-    const u32 k = h->tick_n;
-    use_fx_slot(h, 1 + k);
+    const u32 k = h->ticks.next_slot();
+    use_fx_slot(h, TickRing::fx_slot(k));
     h->plan.mark = (1ull << 40) | ++h->wait_seq;  // column 7 of the verdict rows: peek_ticks knows them by it
-    h->tick_ring[k] = TickSlot{h->plan.G, chained ? h->plan.G : resolve_blocks(h->m), h->plan.mark, h->mut_epoch, quiet};
-    u64* const rows = h->d_slots + (size_t)(kTickSlot0 + k) * h->slot_rows * 8;
+    h->ticks.slot[k] = TickSlot{h->plan.G, chained ? h->plan.G : resolve_blocks(h->m), h->plan.mark, h->mut_epoch, quiet};
+    u64* const rows = h->ticks.rows_dev(k);
     const SolveForm f = solve_form(h, true, false, quiet, chained);
     h->pending = chained ? enqueue_chained(h, t, nt, rows) : enqueue_scan_resolve(h, f, t, nt, rows);
     if (quiet) {
@@ -990,10 +1142,9 @@ int tick_async_locked(rio_gp* h) {
     } else {
         enqueue_slow(h, f, h->plan, t, nt, false);
     }
-    int rc = commit_enqueue(h);
-    if (rc) return rc;
+    if ((rc = commit_enqueue(h))) return rc;
     HIPCHK(h, hipGetLastError());
-    h->tick_n = k + 1;
+    h->ticks.pushed(TickRing::Owner::ticks);
     ipg.ok = true;
     return RIO_GP_OK;
 }
@@ -1160,6 +1311,8 @@ int rio_gp_create(const rio_gp_cfg* cfg, rio_gp_t** out) {
         return bail(RIO_GP_ENOMEM);
     }
     memset(h->h_slots, 0, (size_t)2 * kRing * h->slot_rows * 8 * sizeof(u64));
+    h->solves.init(h->h_slots, h->slot_rows * 8);
+    h->ticks.init(h->h_slots, h->d_slots, h->slot_rows * 8);
     memset(h->h_fx, 0, (size_t)(1 + kRing) * kMaxBlocks * 8 * sizeof(u64));
     h->cs_words = (((size_t)h->cap_nodes + 31) / 32 + 8 + 1) & ~(size_t)1;  // bitmap words, then the u64 count (8 B aligned)
     if (hipHostMalloc(reinterpret_cast<void**>(&h->h_cs), (h->cs_words + 4) * sizeof(u32), hipHostMallocMapped) != hipSuccess ||
@@ -1711,7 +1864,7 @@ static int rebalance_args(rio_gp* h, const rio_gp_rebalance_cfg* cfg, const void
     if ((r != nullptr) != (f != nullptr) || (r != nullptr) != (t != nullptr))
         return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: out_rows / out_from / out_to are given together or not at all");
     if (!r && cap) return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: moves_cap without a move listing");
-    if (h->sc || h->p2p || h->sh_tick_n)
+    if (row_sharded(h))
         return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: not implemented on a handle of the row-sharded solve");
     *rounds = cfg->rounds ? cfg->rounds : h->rounds;
     *budget = r ? std::min<u64>(cfg->max_moves, cap) : cfg->max_moves;
@@ -1791,7 +1944,7 @@ static int chg_args(rio_gp* h, uint32_t flags, const void* r, const void* o, con
     if ((r != nullptr) != (o != nullptr) || (r != nullptr) != (w != nullptr))
         return fail(h, RIO_GP_EINVAL, "rio_gp_changes: out_rows / out_old / out_new are given together or not at all");
     if (!r && cap) return fail(h, RIO_GP_EINVAL, "rio_gp_changes: cap without a listing");
-    if (h->sc || h->p2p || h->sh_tick_n)
+    if (row_sharded(h))
         return fail(h, RIO_GP_EINVAL, "rio_gp_changes: not implemented on a handle of the row-sharded solve");
     return RIO_GP_OK;
 }
@@ -1854,7 +2007,7 @@ int rio_gp_changes_dev(rio_gp_t* h, uint32_t flags, uint32_t* d_rows, uint32_t* 
 int rio_gp_changes_reset(rio_gp_t* h) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    if (h->sc || h->p2p || h->sh_tick_n)
+    if (row_sharded(h))
         return fail(h, RIO_GP_EINVAL, "rio_gp_changes_reset: not implemented on a handle of the row-sharded solve");
     if (!h->chg_B) return RIO_GP_OK;  // (never used: the first listing is complete anyway)
     HIPCHK(h, hipSetDevice(h->device));
@@ -2144,7 +2297,7 @@ int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* map, uint64_
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
     if (!map) return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: map is NULL");
-    if (h->sc || h->p2p || h->sh_tick_n)
+    if (row_sharded(h))
         return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: not implemented on a handle of the row-sharded solve");
     const u32 m = h->m;
     if (m_new > m) return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: m_new exceeds the node count");
@@ -2286,7 +2439,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
         HIPCHK(h, hipStreamSynchronize(h->stream));
         HIPCHK(h, hipGetLastError());
         const DevStats v = reduce_slot(h, 0, h->m);
-        const bool vslow = v.n_cut > 0 || v.spillcand > 0;
+        const bool vslow = needs_fixup(v);
         h->used.publish_request(vslow);
         inputs_changed(h);
         return RIO_GP_OK;
@@ -2346,7 +2499,7 @@ static int place_pending_general(rio_gp* h, uint64_t n, const u32* d_idx, const 
     if (*h_status == 3) return fail(h, RIO_GP_EINVAL, std::string(who) + ": object index or requester out of range (nothing was changed)");
     if (*h_status != 0) return fail(h, RIO_GP_EUPSTREAM, std::string(who) + ": the output kernel left no status");
     const DevStats v = reduce_slot(h, 0, h->m);  // (k_resolve's pinned rows landed before the completion word)
-    const bool vslow = v.n_cut > 0 || v.spillcand > 0;
+    const bool vslow = needs_fixup(v);
     h->pp_last_slow = vslow;
     h->used.publish_request(vslow);
     inputs_changed(h);
@@ -2706,11 +2859,12 @@ int rio_gp_tick_wait(rio_gp_t* h, rio_gp_stats* out, uint32_t cap, uint32_t* n_o
     HIPCHK(h, hipSetDevice(h->device));
     int rc = harvest_ticks(h);
     if (rc) return rc;
-    const size_t n = h->tick_done.size();
+    std::vector<rio_gp_stats>& done = h->ticks.done;
+    const size_t n = done.size();
     const size_t take = n < cap ? n : cap;
-    for (size_t k = 0; k < take; ++k) out[k] = h->tick_done[n - take + k];  // the most recent `take`, oldest first
+    for (size_t k = 0; k < take; ++k) out[k] = done[n - take + k];  // the most recent `take`, oldest first
     *n_out = (uint32_t)n;
-    h->tick_done.clear();
+    done.clear();
     return RIO_GP_OK;
 }
 
@@ -2718,24 +2872,21 @@ int rio_gp_solve_async(rio_gp_t* h) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
     HIPCHK(h, hipSetDevice(h->device));  // a host with several handles (one per GPU) calls from any thread
-    if (h->sh_tick_n) return fail(h, RIO_GP_EINVAL, "rio_gp_solve_async: row-sharded ticks are in flight (call rio_gp_shard_tick_wait)");
-    // the verdict ring holds kRing solves: fold the oldest slot's verdict into the running count before it is overwritten
+    SolveRing& ring = h->solves;
+    int rc = may_start(h, Client::solve_async);
+    if (rc) return rc;
+    // the verdict ring holds kRing solves: fold their verdicts into the running count before the slots are overwritten
     // (rio_gp_solve_wait reports how many of ALL the solves since the last wait took the fix-up path)
-    if (h->ring_n >= (u32)kRing) {
+    if (ring.full()) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (u32 k = 0; k < h->ring_n; ++k) {
-            const DevStats v = reduce_slot(h, k, h->m);
-            h->ring_slow += (v.n_cut > 0 || v.spillcand > 0);
-        }
-        h->ring_n = 0;
+        ring.recycle(resolve_blocks(h->m));
     }
     h->plan = hplan(h, h->n);
     use_fx_slot(h, 0);
-    h->ring_form = solve_form(h, false, false);
-    h->ring_last = enqueue_scan_resolve(h, h->ring_form, real_table(h), scan_nodes(h), slot_dev(h, h->ring_n));
+    ring.form = solve_form(h, false, false);
+    ring.last = enqueue_scan_resolve(h, ring.form, real_table(h), scan_nodes(h), slot_dev(h, ring.next_slot()));
     HIPCHK(h, hipGetLastError());
-    h->ring_n++;
-    h->ring_any = true;
+    ring.pushed(SolveRing::Owner::solves);
     inputs_changed(h);
     return RIO_GP_OK;
 }
@@ -2746,27 +2897,18 @@ int rio_gp_solve_wait(rio_gp_t* h, rio_gp_stats* stats, uint32_t* n_slow) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
-    if (!h->ring_any) return fail(h, RIO_GP_EINVAL, "rio_gp_solve_wait: nothing enqueued");
-    uint32_t slow = h->ring_slow;  // solves whose slots were recycled (rio_gp_solve_async folds them in)
-    DevStats last;
-    memset(&last, 0, sizeof last);
-    if (h->ring_n == 0) last = reduce_slot(h, kRing - 1, h->m);  // exactly a multiple of kRing: the last solve sits in the last slot
-    for (u32 k = 0; k < h->ring_n; ++k) {
-        last = reduce_slot(h, k, h->m);
-        slow += (last.n_cut > 0 || last.spillcand > 0);
-    }
-    h->ring_slow = 0;
-    h->ring_any = false;
-    if (last.n_cut > 0 || last.spillcand > 0) {
-        enqueue_slow(h, h->ring_form, h->plan, real_table(h), real_nodes(h), false);
+    if (!h->solves.any_solves()) return fail(h, RIO_GP_EINVAL, "rio_gp_solve_wait: nothing enqueued");
+    uint32_t slow = 0;
+    DevStats last = h->solves.fold(resolve_blocks(h->m), &slow);
+    if (needs_fixup(last)) {
+        enqueue_slow(h, h->solves.form, h->plan, real_table(h), real_nodes(h), false);
         int rc = merge_slow(h, &last);
         if (rc) return rc;
         HIPCHK(h, hipGetLastError());
     }
     fill_stats(last, h->n, stats);
     if (n_slow) *n_slow = slow;
-    h->ring_n = 0;
-    h->pending = h->ring_last;  // the last solve of the ring is finished: it waits for its commit
+    h->pending = h->solves.finish();
     return RIO_GP_OK;
 }
 
@@ -2789,9 +2931,9 @@ int rio_gp_solve_profiled(rio_gp_t* h, float* scan_ms, float* resolve_ms) {
     HIPCHK(h, hipEventElapsedTime(scan_ms, h->ev0, h->ev1));
     HIPCHK(h, hipEventElapsedTime(resolve_ms, h->ev2, h->ev3));
     inputs_changed(h);
-    h->ring_n = 0; h->ring_slow = 0; h->ring_any = false;
+    h->solves.abandon();
     const DevStats v = reduce_slot(h, 0, h->m);
-    if (v.n_cut > 0 || v.spillcand > 0)
+    if (needs_fixup(v))
         return fail(h, RIO_GP_EINVAL, "rio_gp_solve_profiled: this table needs the cut/spill fix-up");
     return RIO_GP_OK;
 }
@@ -2858,57 +3000,40 @@ int rio_gp_shard_scan(rio_gp_t* h, uint64_t* d_x) {
     launch_resolve(h->plan, nt, lb, nullptr, h->stream);  // used_base = nullptr: purely local sums
     launch_shard_pack1(h->plan, lb, reinterpret_cast<u64*>(d_x), h->stream);
     inputs_changed(h);
-    h->sh_state = 1;
+    h->sh.step = ShStep::scanned;
     return RIO_GP_OK;
 }
 
 int rio_gp_shard_resolve(rio_gp_t* h, uint32_t rank, uint32_t n_ranks, const uint64_t* d_xg, void* on_stream) {
     if (!h || !d_xg || n_ranks == 0 || rank >= n_ranks) return RIO_GP_EINVAL;
     Locked g(h);
-    if (h->sh_state != 1) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_resolve: call rio_gp_shard_scan first");
-    h->sh_rank = rank;
-    h->sh_R = n_ranks;
-    h->sh_slot = h->ring_n;
-    h->sh_rows = 1;
+    if (!h->sh.at(ShStep::scanned)) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_resolve: call rio_gp_shard_scan first");
     hipStream_t st = on_stream ? static_cast<hipStream_t>(on_stream) : h->stream;
-    h->sh_side = on_stream ? st : nullptr;
+    h->sh.bind(rank, n_ranks, on_stream ? st : nullptr);
     launch_shard_import(h->plan, real_nodes(h), shard_bufs(h), reinterpret_cast<const u64*>(d_xg), rank, n_ranks,
-                        h->sh_gprev, h->sh_gfinal, h->sh_verdict, slot_dev(h, h->ring_n), st);
-    h->ring_n++;
-    h->sh_state = 2;
+                        h->sh_gprev, h->sh_gfinal, h->sh_verdict, slot_dev(h, h->solves.next_slot()), st);
+    h->solves.pushed_shard(1);
+    h->sh.step = ShStep::resolved;
     return RIO_GP_OK;
 }
 
 int rio_gp_shard_verdict(rio_gp_t* h, rio_gp_shard_info* out, uint32_t* n_slow) {
     if (!h || !out) return RIO_GP_EINVAL;
     Locked g(h);
-    if (h->sh_state != 2) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_verdict: call rio_gp_shard_resolve first");
+    if (!h->sh.at(ShStep::resolved)) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_verdict: call rio_gp_shard_resolve first");
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->sh_side) HIPCHK(h, hipStreamSynchronize(h->sh_side));  // the exchange stream of a pipelined caller
-    h->sh_side = nullptr;
+    if (h->sh.side) HIPCHK(h, hipStreamSynchronize(h->sh.side));  // the exchange stream of a pipelined caller
+    h->sh.side = nullptr;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->p2p && h->p2p->d_peers) { int rc = p2p_check(h); if (rc) return rc; }
     HIPCHK(h, hipGetLastError());
-    uint32_t slow = 0;
-    const u32 lo = h->ring_n > (u32)kRing ? h->ring_n - kRing : 0;
-    auto fold = [&](u32 k, u64* x) {  // one verdict row (k_shard_import) or one partial row per workgroup (k_resolve_xchg)
-        const u64* rows = h->h_slots + (size_t)(k % kRing) * h->slot_rows * 8;
-        for (int c = 0; c < 8; ++c) x[c] = 0;
-        for (u32 r = 0; r < h->sh_rows; ++r)
-            for (int c = 0; c < 8; ++c) x[c] += rows[(size_t)r * 8 + c];
-    };
     u64 x[8];
-    for (u32 k = lo; k < h->ring_n; ++k) {
-        fold(k, x);
-        slow += (x[0] > 0 || x[1] > 0);
-    }
-    fold(h->sh_slot, x);
+    const uint32_t slow = h->solves.shard_fold(x);
     out->cut_nodes = x[0]; out->spill_rows = x[1]; out->local_fixup = x[2]; out->kept = x[3];
     out->evicted = x[4]; out->claimants = x[5]; out->load_kept = x[6]; out->load_claim = x[7];
     if (n_slow) *n_slow = slow;
-    h->sh_slow = (x[0] > 0 || x[1] > 0);
-    h->ring_n = 0;
-    if (!h->sh_slow)  // fast path: the committed `used` is the global kept + claimed load
+    h->sh.slow = (x[0] > 0 || x[1] > 0);
+    if (!h->sh.slow)  // fast path: the committed `used` is the global kept + claimed load
         HIPCHK(h, hipMemcpyAsync(h->sb.used_cur, h->sh_gfinal, (size_t)(h->m ? h->m : 1) * sizeof(u64),
                                  hipMemcpyDeviceToDevice, h->stream));
     return RIO_GP_OK;
@@ -2917,7 +3042,7 @@ int rio_gp_shard_verdict(rio_gp_t* h, rio_gp_shard_info* out, uint32_t* n_slow) 
 int rio_gp_shard_cut(rio_gp_t* h, int run_local_fixup, uint64_t* d_y) {
     if (!h || !d_y) return RIO_GP_EINVAL;
     Locked g(h);
-    if (h->sh_state != 2 || !h->sh_slow) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_cut: no fix-up pending");
+    if (!h->sh.at(ShStep::resolved) || !h->sh.slow) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_cut: no fix-up pending");
     HIPCHK(h, hipSetDevice(h->device));
     const SolveBufs b = shard_bufs(h);
     if (run_local_fixup) {
@@ -2925,42 +3050,42 @@ int rio_gp_shard_cut(rio_gp_t* h, int run_local_fixup, uint64_t* d_y) {
         launch_fill(h->plan, real_table(h), real_nodes(h), b, false, true, false, 0, false, h->stream);
     }
     launch_shard_export_delta(h->plan, b, h->sb.used_kept, 0, reinterpret_cast<u64*>(d_y), h->stream);
-    h->sh_state = 3;
+    h->sh.step = ShStep::cut_exported;
     return RIO_GP_OK;
 }
 
 int rio_gp_shard_merge(rio_gp_t* h, const uint64_t* d_yg, uint64_t* pending_rows, uint64_t* pending_load) {
     if (!h || !d_yg) return RIO_GP_EINVAL;
     Locked g(h);
-    if (h->sh_state != 3 && h->sh_state != 5) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_merge: nothing exported");
+    if (!h->sh.at(ShStep::cut_exported) && !h->sh.at(ShStep::spill_exported)) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_merge: nothing exported");
     HIPCHK(h, hipSetDevice(h->device));
-    launch_shard_import_delta(h->plan, shard_bufs(h), reinterpret_cast<const u64*>(d_yg), h->sh_rank, h->sh_R,
+    launch_shard_import_delta(h->plan, shard_bufs(h), reinterpret_cast<const u64*>(d_yg), h->sh.rank, h->sh.R,
                               h->sh_gprev, h->sh_verdict, slot_dev(h, 0), h->stream);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     const u64* x = h->h_slots;
     if (pending_rows) *pending_rows = x[0];
     if (pending_load) *pending_load = x[1];
-    h->sh_state = 4;
+    h->sh.step = ShStep::merged;
     return RIO_GP_OK;
 }
 
 int rio_gp_shard_spill(rio_gp_t* h, uint32_t round, int last, uint64_t* d_y) {
     if (!h || !d_y) return RIO_GP_EINVAL;
     Locked g(h);
-    if (h->sh_state != 4) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_spill: call rio_gp_shard_merge first");
+    if (!h->sh.at(ShStep::merged)) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_spill: call rio_gp_shard_merge first");
     HIPCHK(h, hipSetDevice(h->device));
     const SolveBufs b = shard_bufs(h);
     launch_fill(h->plan, real_table(h), real_nodes(h), b, false, false, true, (int)round, last != 0, h->stream);
     launch_shard_export_delta(h->plan, b, h->sh_gprev, (int)((round & 1) ^ 1), reinterpret_cast<u64*>(d_y), h->stream);
-    h->sh_state = 5;
+    h->sh.step = ShStep::spill_exported;
     return RIO_GP_OK;
 }
 
 int rio_gp_shard_finish(rio_gp_t* h, rio_gp_stats* local_stats) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    if (h->sh_state != 2 && h->sh_state != 4)
+    if (!h->sh.at(ShStep::resolved) && !h->sh.at(ShStep::merged))
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_finish: solve not resolved / last exchange not merged");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(h->h_stats, h->dstats, sizeof(DevStats), hipMemcpyDeviceToHost, h->stream));
@@ -2976,7 +3101,7 @@ int rio_gp_shard_finish(rio_gp_t* h, rio_gp_stats* local_stats) {
         v.load_kept += x[0]; v.load_claim_tot += x[1];
         v.kept += x[3]; v.evicted += x[4]; v.claimants += x[5]; v.spillcand += x[6];
     }
-    if (h->sh_slow) {
+    if (h->sh.slow) {
         const DevStats& d = h->h_stats[0];
         v.rejected = d.rejected; v.load_rejected = d.load_rejected;
         v.spilled = d.spilled; v.load_spilled = d.load_spilled;
@@ -2984,8 +3109,8 @@ int rio_gp_shard_finish(rio_gp_t* h, rio_gp_stats* local_stats) {
     }
     fill_stats(v, h->n, local_stats);  // cut_nodes / slow_path / rounds_run are global: the caller has them
     h->pending = PendingSolve{true};
-    h->ring_n = 0;
-    h->sh_state = 0;
+    h->solves.rewind();
+    h->sh.step = ShStep::idle;
     return RIO_GP_OK;
 }
 
@@ -3020,12 +3145,6 @@ RbBufs rb_bufs(rio_gp* h) {
     b.info = b.live + M;
     return b;
 }
-// A step continues the protocol only on the handle as begin left it: no call that changes an input of the solve (they all
-// count in mut_epoch) and none that rebuilt or republished `used` (which holds the protocol's vectors) came between.
-bool rb_at(rio_gp* h, int state) {
-    if (h->rb_state != 0 && (h->mut_epoch != h->rb_epoch || !h->used.borrowed())) h->rb_state = 0;
-    return h->rb_state == state;
-}
 int rb_ensure(rio_gp* h) {
     const size_t M = h->cap_nodes;
     return ensure(h, h->sh_nodes, (6 * M + 2 + kShAcc) * sizeof(u64) + (5 * M + 4 + kShrbInfo) * sizeof(u32));
@@ -3041,56 +3160,58 @@ int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, u
     if (cfg->rounds > 8) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: rounds above the solver limit (8)");
     if (!d_x || n_ranks == 0 || rank >= n_ranks) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: rank >= n_ranks, or no record");
     if (!list_moves && moves_cap) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: moves_cap without a move listing");
-    if (h->sh_tick_n) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: rio_gp_shard_tick_async ticks in flight (rio_gp_shard_tick_wait first)");
+    int rc = may_start(h, Client::shard_rebalance_begin);
+    if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
     if ((rc = rb_ensure(h))) return rc;
     const RbBufs b = rb_bufs(h);
     const u32 m = h->m;
     // a change of the inputs, like rio_gp_rebalance: an uncommitted solve (a sharded one half way included) is dropped
     inputs_changed(h);
-    h->sh_state = 0;
-    h->ring_n = 0;
+    h->sh.step = ShStep::idle;
+    h->solves.rewind();
     h->used.borrow();  // until rio_gp_shard_rebalance_finish: its storage holds the protocol's intermediate vectors
-    h->rb_rank = rank; h->rb_R = n_ranks;
-    h->rb_rounds = cfg->rounds ? cfg->rounds : h->rounds;
-    h->rb_list = list_moves != 0;
-    h->rb_budget = list_moves ? std::min<u64>(cfg->max_moves, moves_cap) : cfg->max_moves;
-    h->rb_K = h->rb_sel_total = h->rb_pending = 0;
-    h->rb_fills = 0;
-    h->rb_over = h->rb_over_before = 0;
-    h->rb_T.assign(m ? m : 1, 0);
-    h->rb_live.assign(m ? m : 1, 0);
-    for (u32 j = 0; j < m; ++j) h->rb_live[j] = h->h_alive[j] ? 1u : 0u;
+    RbSession fresh;
+    fresh.T = std::move(h->rb.T);  // (in the last session's host arrays: a copy it enqueued may still be on its way into them)
+    fresh.live = std::move(h->rb.live);
+    fresh.rank = rank; fresh.R = n_ranks;
+    fresh.rounds = cfg->rounds ? cfg->rounds : h->rounds;
+    fresh.list = list_moves != 0;
+    fresh.budget = list_moves ? std::min<u64>(cfg->max_moves, moves_cap) : cfg->max_moves;
+    fresh.T.assign(m ? m : 1, 0);
+    fresh.live.assign(m ? m : 1, 0);
+    for (u32 j = 0; j < m; ++j) fresh.live[j] = h->h_alive[j] ? 1u : 0u;
+    RbSession& rb = h->rb = std::move(fresh);
     if (cfg->target) {
-        memcpy(h->rb_T.data(), cfg->target, (size_t)m * sizeof(u64));
-        if (m) HIPCHK(h, hipMemcpyAsync(b.tdev, h->rb_T.data(), (size_t)m * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+        memcpy(rb.T.data(), cfg->target, (size_t)m * sizeof(u64));
+        if (m) HIPCHK(h, hipMemcpyAsync(b.tdev, rb.T.data(), (size_t)m * sizeof(u64), hipMemcpyHostToDevice, h->stream));
     } else if (m) {  // (read by the host in _finish, behind the waits of the steps between)
-        HIPCHK(h, hipMemcpyAsync(h->rb_T.data(), h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(rb.T.data(), h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(b.tdev, h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
     }
-    if (m) HIPCHK(h, hipMemcpyAsync(b.live, h->rb_live.data(), (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    if (m) HIPCHK(h, hipMemcpyAsync(b.live, rb.live.data(), (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(b.acc, 0, kShAcc * sizeof(u64), h->stream));
     // R0 over this rank's rows: the load per node (kept in lu: it becomes used'_r in _select) and the pinned load
     launch_shed_hist(h->assign[h->cur], h->load, h->aff, h->n, m, b.lu, b.pin, h->stream);
     launch_shrb_export_x(b.lu, b.pin, m, reinterpret_cast<u64*>(d_x), h->stream);
     HIPCHK(h, hipGetLastError());
-    if (rounds_out) *rounds_out = h->rb_rounds;
-    h->rb_epoch = h->mut_epoch;
-    h->rb_state = 1;
+    if (rounds_out) *rounds_out = rb.rounds;
+    rb.epoch = h->mut_epoch;
+    rb.step = RbStep::begun;
     return RIO_GP_OK;
 }
 
 int rio_gp_shard_rebalance_cut(rio_gp_t* h, const uint64_t* d_xg, uint64_t* d_s, uint32_t* nodes_over) {
     if (!h || !d_xg || !d_s) return RIO_GP_EINVAL;
     Locked g(h);
-    if (!rb_at(h, 1)) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_cut: call rio_gp_shard_rebalance_begin first");
+    RbSession& rb = h->rb;
+    if (!rb.at(h, RbStep::begun)) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_cut: call rio_gp_shard_rebalance_begin first");
     HIPCHK(h, hipSetDevice(h->device));
     const RbBufs b = rb_bufs(h);
     const u32 m = h->m;
     ShrbImport a{};
     a.Xg = reinterpret_cast<const u64*>(d_xg);
-    a.rank = h->rb_rank; a.R = h->rb_R; a.m = m;
+    a.rank = rb.rank; a.R = rb.R; a.m = m;
     a.T = b.tdev; a.live = b.live;
     a.used = h->used.storage(); a.tgt = b.tgt; a.map = b.map; a.slot_node = b.slot_node; a.slot_free = b.slot_free; a.cut = b.cut;
     a.info = b.info;
@@ -3099,11 +3220,11 @@ int rio_gp_shard_rebalance_cut(rio_gp_t* h, const uint64_t* d_xg, uint64_t* d_s,
     u32 info[kShrbInfo];
     HIPCHK(h, hipMemcpyAsync(info, b.info, sizeof info, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->rb_over = info[kShrbOver];
-    h->rb_over_before = info[kShrbOverBefore];
+    rb.over = info[kShrbOver];
+    rb.over_before = info[kShrbOverBefore];
     const u32 S = info[kShrbSlots];
     const ShPlan p = sh_plan(h->n, m, S);
-    h->rb_plan = p;
+    rb.plan = p;
     HIPCHK(h, hipMemsetAsync(d_s, 0, ((size_t)m + 2) * sizeof(u64), h->stream));
     if (h->n && (S || info[kShrbForced])) {  // R1 over this rank's rows: the exact cuts that fall here, the surplus per tile
         int rc;
@@ -3115,8 +3236,8 @@ int rio_gp_shard_rebalance_cut(rio_gp_t* h, const uint64_t* d_xg, uint64_t* d_s,
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(d_s, b.acc, 2 * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));  // surplus rows | load
     }
-    if (nodes_over) *nodes_over = h->rb_over;
-    h->rb_state = 2;
+    if (nodes_over) *nodes_over = rb.over;
+    rb.step = RbStep::cut;
     return RIO_GP_OK;
 }
 
@@ -3124,76 +3245,79 @@ int rio_gp_shard_rebalance_select(rio_gp_t* h, const uint64_t* d_sg, uint64_t* d
                                   uint64_t* selected_total) {
     if (!h || !d_sg || !d_y) return RIO_GP_EINVAL;
     Locked g(h);
-    if (!rb_at(h, 2) || !h->rb_over)
+    RbSession& rb = h->rb;
+    if (!rb.at(h, RbStep::cut) || !rb.over)
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_select: call rio_gp_shard_rebalance_cut first (and only when it reports nodes over)");
     HIPCHK(h, hipSetDevice(h->device));
     const RbBufs b = rb_bufs(h);
-    const u32 m = h->m, R = h->rb_R;
+    const u32 m = h->m, R = rb.R;
     const size_t W = (size_t)m + 2;
     std::vector<u64> sg(2 * (size_t)R);
     HIPCHK(h, hipMemcpy2DAsync(sg.data(), 2 * sizeof(u64), d_sg, W * sizeof(u64), 2 * sizeof(u64), R, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     u64 pre = 0, tot = 0;
     for (u32 q = 0; q < R; ++q) {
-        if (q < h->rb_rank) pre += sg[2 * q];
+        if (q < rb.rank) pre += sg[2 * q];
         tot += sg[2 * q];
     }
-    const u64 mine = sg[2 * (size_t)h->rb_rank], B = h->rb_budget;
+    const u64 mine = sg[2 * (size_t)rb.rank], B = rb.budget;
     const u64 K = B > pre ? std::min<u64>(B - pre, mine) : 0;  // R2: this rank's share of the first B surplus rows
-    h->rb_K = K;
-    h->rb_sel_total = std::min<u64>(B, tot);
+    rb.K = K;
+    rb.sel_total = std::min<u64>(B, tot);
     if (K) {
         int rc;
         const u64 nc = (K + kShChunk - 1) / kShChunk;
         if ((rc = ensure(h, h->sh_pk, 3 * K * sizeof(u32))) || (rc = ensure(h, h->sh_chunk, nc * sizeof(u64)))) return rc;
         u32* pk_row = (u32*)h->sh_pk.p;
-        launch_shed_pack(h->assign[h->cur], h->load, h->aff, h->rb_plan, b.cut, (const u32*)h->sh_tile.p, K, pk_row, pk_row + K,
+        launch_shed_pack(h->assign[h->cur], h->load, h->aff, rb.plan, b.cut, (const u32*)h->sh_tile.p, K, pk_row, pk_row + K,
                          pk_row + 2 * K, b.lu, b.acc, h->stream);
     }
     launch_shrb_export_y(b.lu, m, b.acc + kShAccSelectedLoad, K, reinterpret_cast<u64*>(d_y), h->stream);
     HIPCHK(h, hipGetLastError());
     if (selected_local) *selected_local = K;
-    if (selected_total) *selected_total = h->rb_sel_total;
-    h->rb_first = true;
-    h->rb_state = 3;
+    if (selected_total) *selected_total = rb.sel_total;
+    rb.first = true;
+    rb.step = RbStep::selected;
     return RIO_GP_OK;
 }
 
 int rio_gp_shard_rebalance_merge(rio_gp_t* h, const uint64_t* d_yg, uint64_t* pending_rows, uint64_t* pending_load) {
     if (!h || !d_yg) return RIO_GP_EINVAL;
     Locked g(h);
-    if ((!rb_at(h, 3) || !h->rb_sel_total) && !rb_at(h, 5))
+    RbSession& rb = h->rb;
+    if ((!rb.at(h, RbStep::selected) || !rb.sel_total) && !rb.at(h, RbStep::round_exported))
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_merge: nothing exported (rio_gp_shard_rebalance_select with rows selected, or _fill, first)");
     HIPCHK(h, hipSetDevice(h->device));
     const RbBufs b = rb_bufs(h);
-    launch_shrb_merge(reinterpret_cast<const u64*>(d_yg), h->rb_rank, h->rb_R, h->m, h->rb_first, h->used.storage(), b.base, b.acc + kRbPend,
+    launch_shrb_merge(reinterpret_cast<const u64*>(d_yg), rb.rank, rb.R, h->m, rb.first, h->used.storage(), b.base, b.acc + kRbPend,
                       h->stream);
     HIPCHK(h, hipGetLastError());
     u64 pend[2];
     HIPCHK(h, hipMemcpyAsync(pend, b.acc + kRbPend, sizeof pend, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->rb_first = false;
-    h->rb_pending = pend[0];
+    rb.first = false;
+    rb.pending = pend[0];
     if (pending_rows) *pending_rows = pend[0];
     if (pending_load) *pending_load = pend[1];
-    h->rb_state = 4;
+    rb.step = RbStep::merged;
     return RIO_GP_OK;
 }
 
 int rio_gp_shard_rebalance_fill(rio_gp_t* h, uint32_t round, uint64_t* d_y) {
     if (!h || !d_y) return RIO_GP_EINVAL;
     Locked g(h);
-    if (!rb_at(h, 4) || round != h->rb_fills || round >= h->rb_rounds || !h->rb_pending)
+    RbSession& rb = h->rb;
+    if (!rb.at(h, RbStep::merged) || round != rb.fills || round >= rb.rounds || !rb.pending)
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_fill: call rio_gp_shard_rebalance_merge first; rounds run in order while rows are pending");
     HIPCHK(h, hipSetDevice(h->device));
     const RbBufs b = rb_bufs(h);
-    const u64 K = h->rb_K;
+    const u64 K = rb.K;
     u32* pk_row = (u32*)h->sh_pk.p;
     launch_shrb_round(K, pk_row, pk_row + K, pk_row + 2 * K, h->assign[h->cur], b.tgt, h->m, h->used.storage(), b.base,
-                      round + 1 == h->rb_rounds, (u64*)h->sh_chunk.p, b.C, b.ord, b.cntp, reinterpret_cast<u64*>(d_y), h->stream);
+                      round + 1 == rb.rounds, (u64*)h->sh_chunk.p, b.C, b.ord, b.cntp, reinterpret_cast<u64*>(d_y), h->stream);
     HIPCHK(h, hipGetLastError());
-    ++h->rb_fills;
-    h->rb_state = 5;
+    ++rb.fills;
+    rb.step = RbStep::round_exported;
     return RIO_GP_OK;
 }
 
@@ -3201,15 +3325,14 @@ int rio_gp_shard_rebalance_finish(rio_gp_t* h, rio_gp_rebalance_stats* local_sta
                                   uint32_t* out_to, uint64_t moves_cap, uint64_t* n_moves) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    (void)rb_at(h, 0);
-    const bool done = (h->rb_state == 2 && !h->rb_over) || (h->rb_state == 3 && !h->rb_sel_total) ||
-                      (h->rb_state == 4 && (!h->rb_pending || h->rb_fills == h->rb_rounds));
-    if (!done) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_finish: the protocol has not reached its end");
+    RbSession& rb = h->rb;
+    (void)rb.at(h, RbStep::idle);  // (a session whose inputs moved is over)
+    if (!rb.finished()) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_finish: the protocol has not reached its end");
     if ((out_rows != nullptr) != (out_from != nullptr) || (out_rows != nullptr) != (out_to != nullptr))
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_finish: out_rows / out_from / out_to are given together or not at all");
-    if ((out_rows != nullptr) != h->rb_list)
+    if ((out_rows != nullptr) != rb.list)
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_finish: the move listing is asked for in rio_gp_shard_rebalance_begin");
-    const u64 K = h->rb_state == 4 ? h->rb_K : 0;
+    const u64 K = rb.listed_rows();
     if (out_rows ? moves_cap < K : moves_cap != 0)
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_finish: moves_cap below this rank's selected rows (rio_gp_shard_rebalance_select)");
     HIPCHK(h, hipSetDevice(h->device));
@@ -3236,15 +3359,15 @@ int rio_gp_shard_rebalance_finish(rio_gp_t* h, rio_gp_rebalance_stats* local_sta
     HIPCHK(h, hipStreamSynchronize(h->stream));
     s.surplus_rows = a[kShAccSurplusRows];
     s.surplus_load = a[kShAccSurplusLoad];
-    s.selected_rows = h->rb_state >= 3 ? h->rb_K : 0;
+    s.selected_rows = rb.selected_rows();
     s.selected_load = a[kShAccSelectedLoad];
     if (K) {
         s.moved_rows = a[kShAccMovedRows];
         s.moved_load = a[kShAccMovedLoad];
         s.stayed_rows = a[kShAccStayed];
     }
-    s.nodes_over_before = h->rb_over_before;
-    for (u32 j = 0; j < m; ++j) s.nodes_over_after += h->h_alive[j] && used[j] > h->rb_T[j];
+    s.nodes_over_before = rb.over_before;
+    for (u32 j = 0; j < m; ++j) s.nodes_over_after += h->h_alive[j] && used[j] > rb.T[j];
     if (out_rows && s.moved_rows) {
         HIPCHK(h, hipMemcpyAsync(out_rows, d, s.moved_rows * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(out_from, d + K, s.moved_rows * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
@@ -3254,7 +3377,7 @@ int rio_gp_shard_rebalance_finish(rio_gp_t* h, rio_gp_rebalance_stats* local_sta
     if (n_moves) *n_moves = s.moved_rows;
     if (local_stats) *local_stats = s;
     h->used.rebuilt();  // the global `used` of the new column, on every rank
-    h->rb_state = 0;
+    rb.step = RbStep::idle;
     return RIO_GP_OK;
 }
 
@@ -3360,8 +3483,8 @@ int rio_gp_shard_p2p_close(rio_gp_t* h) {
     (void)hipStreamSynchronize(h->stream);
     (void)hipGetLastError();
     p2p_free(h);
-    h->sh_state = 0;
-    h->ring_n = 0;
+    h->sh.step = ShStep::idle;
+    h->solves.rewind();
     return RIO_GP_OK;
 }
 
@@ -3449,7 +3572,7 @@ int rio_gp_shard_solve_async(rio_gp_t* h) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
     if (h->sa) return fail(h, RIO_GP_EINVAL, "row-sharded solves do not implement RIO_GP_CFG_REF_SELF_ASSIGN (single-GPU handles only)");
-    if (h->sh_tick_n) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_solve_async: row-sharded ticks are in flight (call rio_gp_shard_tick_wait)");
+    if (int rc = may_start(h, Client::shard_solve_async)) return rc;
     if (h->p2p && h->p2p->d_peers) {
         // peer-to-peer, ONE stream, two launches, no collective call and no host wait: k_scan -> k_resolve_xchg.
         // Stream order is the flow control: a rank's record j+1 leaves only after it consumed everyone's record j,
@@ -3462,10 +3585,7 @@ int rio_gp_shard_solve_async(rio_gp_t* h) {
         const u64 seq = ++q->seq;
         const u32 slot = (u32)(q->xslot_n++ % kP2PSlots);
         const NodeTab nt = shard_scan_begin(h).nt;
-        h->sh_rank = q->rank;
-        h->sh_R = q->R;
-        h->sh_slot = h->ring_n;
-        h->sh_side = nullptr;
+        h->sh.bind(q->rank, q->R, nullptr);
         // ONE launch behind the scan: every workgroup exchanges and resolves its own node group (k_resolve_xchg);
         // the verdict arrives as resolve_blocks(m) partial rows in the pinned slot
         SolveBufs xb = shard_bufs(h);
@@ -3473,11 +3593,10 @@ int rio_gp_shard_solve_async(rio_gp_t* h) {
         xb.blkstat = h->sb.blkstat;
         launch_resolve_xchg(h->plan, nt, xb, q->d_peers, q->R, q->rank, q->xdata_off(slot, q->rank),
                             q->win + q->xdata_off(slot, 0), q->Wx, seq, q->d_err, h->sh_gprev, h->sh_gfinal,
-                            slot_dev(h, h->ring_n), q->co_resident, h->stream);
-        h->sh_rows = resolve_blocks(h->m);
-        h->ring_n++;
+                            slot_dev(h, h->solves.next_slot()), q->co_resident, h->stream);
+        h->solves.pushed_shard(resolve_blocks(h->m));
         inputs_changed(h);
-        h->sh_state = 2;
+        h->sh.step = ShStep::resolved;
         HIPCHK(h, hipGetLastError());
         step.done = true;
         return RIO_GP_OK;
@@ -3494,18 +3613,14 @@ int rio_gp_shard_solve_async(rio_gp_t* h) {
     HIPCHK(h, hipStreamWaitEvent(sc->side, sc->ready[q], 0));
     const int rc = sc->api.AllGather(sc->X[q], sc->XG[q], shard_words1(h->m), kNcclUint64, sc->comm, sc->side);
     if (rc != 0) return fail(h, RIO_GP_EUPSTREAM, std::string("ncclAllGather: ") + (sc->api.GetErrorString ? sc->api.GetErrorString(rc) : "failed"));
-    h->sh_rank = sc->rank;
-    h->sh_R = sc->R;
-    h->sh_slot = h->ring_n;
-    h->sh_rows = 1;
-    h->sh_side = sc->side;
+    h->sh.bind(sc->rank, sc->R, sc->side);
     launch_shard_import(h->plan, nt, shard_bufs(h), sc->XG[q], sc->rank, sc->R, h->sh_gprev, h->sh_gfinal, h->sh_verdict,
-                        slot_dev(h, h->ring_n), sc->side);
+                        slot_dev(h, h->solves.next_slot()), sc->side);
     HIPCHK(h, hipEventRecord(sc->done[q], sc->side));
     sc->done_valid[q] = true;
-    h->ring_n++;
+    h->solves.pushed_shard(1);
     inputs_changed(h);
-    h->sh_state = 2;
+    h->sh.step = ShStep::resolved;
     return RIO_GP_OK;
 }
 
@@ -3520,7 +3635,7 @@ static void shard_exchange_y(rio_gp* h, const SolveBufs& b, const u64* base, int
     launch_shard_export_put(h->plan, b, base, wsp_sel, q->d_peers, q->R, q->data_off(slot, q->rank), q->flag_off(slot, q->rank), seq,
                             h->stream);
     launch_shard_wait_import(h->plan, b, q->win + q->data_off(slot, 0), q->W, q->win + q->flag_off(slot, 0), seq, q->d_err,
-                             h->sh_rank, h->sh_R, h->sh_gprev, h->sh_gfinal, h->sh_verdict, verdict_host, h->stream);
+                             h->sh.rank, h->sh.R, h->sh_gprev, h->sh_gfinal, h->sh_verdict, verdict_host, h->stream);
 }
 
 int rio_gp_shard_tick_async(rio_gp_t* h) {
@@ -3529,12 +3644,11 @@ int rio_gp_shard_tick_async(rio_gp_t* h) {
     if (h->sa) return fail(h, RIO_GP_EINVAL, "row-sharded solves do not implement RIO_GP_CFG_REF_SELF_ASSIGN (single-GPU handles only)");
     P2P* q = h->p2p;
     if (!q || !q->d_peers) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_tick_async: peer-to-peer windows only (rio_gp_shard_p2p_connect first)");
-    if (h->ring_n || h->tick_n) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_tick_async: other asynchronous solves are in flight");
-    if (h->sh_tick_n == (u32)kRing) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_tick_async: 64 ticks in flight (call rio_gp_shard_tick_wait)");
+    int rc = may_start(h, Client::shard_tick_async);
+    if (rc) return rc;
     if (q->out_of_step) return fail(h, RIO_GP_EUPSTREAM, kOutOfStep);
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    const u32 k = h->sh_tick_n;
+    const u32 k = h->ticks.next_slot();
     // (1) the fast path: k_scan -> k_resolve_xchg, verdict rows into this tick's slot of the tick ring
     StepGuard step{q};  // (every sequence number this tick takes — its own and its exchanges' — is taken before any check below)
     const u64 seq = ++q->seq;
@@ -3542,14 +3656,12 @@ int rio_gp_shard_tick_async(rio_gp_t* h) {
     const ShardScan sc0 = shard_scan_begin(h);
     const Table& t = sc0.t;
     const NodeTab& nt = sc0.nt;
-    h->sh_rank = q->rank;
-    h->sh_R = q->R;
-    h->sh_side = nullptr;
+    h->sh.bind(q->rank, q->R, nullptr);
     SolveBufs b = shard_bufs(h);
     b.H = h->sb.H;
     b.blkstat = h->sb.blkstat;
-    u64* rows = h->d_slots + (size_t)(kTickSlot0 + k) * h->slot_rows * 8;
-    u64* rec = h->d_fx + (size_t)(1 + k) * kMaxBlocks * 8;
+    u64* rows = h->ticks.rows_dev(k);
+    u64* rec = h->d_fx + (size_t)TickRing::fx_slot(k) * kMaxBlocks * 8;
     launch_resolve_xchg(h->plan, nt, b, q->d_peers, q->R, q->rank, q->xdata_off(slot, q->rank), q->win + q->xdata_off(slot, 0),
                         q->Wx, seq, q->d_err, h->sh_gprev, h->sh_gfinal, rows, q->co_resident, h->stream);
     // (2) exact cut on this rank: k_cutblk + k_cut_find guard themselves on the cut flag, the re-marking pass on the number
@@ -3565,13 +3677,13 @@ int rio_gp_shard_tick_async(rio_gp_t* h) {
         shard_exchange_y(h, b, h->sh_gprev, (int)((r & 1) ^ 1), rec + 8 * (size_t)(3 + r));
     }
     // (5) this rank's counters, (6) publication
-    h->sh_tick_mark[k] = (1ull << 41) | ++h->wait_seq;
-    launch_shard_tick_stats(h->plan, b, rec, h->sh_tick_mark[k], h->stream);
+    h->ticks.shard_mark[k] = (1ull << 41) | ++h->wait_seq;
+    launch_shard_tick_stats(h->plan, b, rec, h->ticks.shard_mark[k], h->stream);
     HIPCHK(h, hipGetLastError());
     h->pending = PendingSolve{true};
     if ((rc = commit_enqueue(h))) return rc;
-    h->sh_tick_n = k + 1;
-    h->sh_state = 0;
+    h->ticks.pushed(TickRing::Owner::shard_ticks);
+    h->sh.step = ShStep::idle;
     step.done = true;
     return RIO_GP_OK;
 }
@@ -3580,20 +3692,20 @@ int rio_gp_shard_tick_wait(rio_gp_t* h, rio_gp_shard_tick_info* out, uint32_t ca
     if (!h || !n_out || (cap && !out)) return RIO_GP_EINVAL;
     Locked g(h);
     *n_out = 0;
-    if (!h->sh_tick_n) return RIO_GP_OK;
+    const u32 n = h->ticks.count(TickRing::Owner::shard_ticks);
+    if (!n) return RIO_GP_OK;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
-    const u32 n = h->sh_tick_n;
-    h->sh_tick_n = 0;
+    h->ticks.clear();
     if (h->p2p && h->p2p->d_peers) { int rc = p2p_check(h); if (rc) return rc; }
     const u32 nb = resolve_blocks(h->m);
     const u32 take = n < cap ? n : cap;
     for (u32 k = n - take; k < n; ++k) {
         rio_gp_shard_tick_info& o = out[k - (n - take)];
-        const u64* rows = h->h_slots + (size_t)(kTickSlot0 + k) * h->slot_rows * 8;
-        const u64* rec = h->h_fx + (size_t)(1 + k) * kMaxBlocks * 8;
-        if (rec[15] != h->sh_tick_mark[k]) return fail(h, RIO_GP_EUPSTREAM, "rio_gp_shard_tick_wait: a tick left no record");
+        const u64* rows = h->ticks.rows_host(k);
+        const u64* rec = h->h_fx + (size_t)TickRing::fx_slot(k) * kMaxBlocks * 8;
+        if (rec[15] != h->ticks.shard_mark[k]) return fail(h, RIO_GP_EUPSTREAM, "rio_gp_shard_tick_wait: a tick left no record");
         u64 x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (u32 r = 0; r < nb; ++r)
             for (int c = 0; c < 8; ++c) x[c] += rows[(size_t)r * 8 + c];
