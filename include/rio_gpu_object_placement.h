@@ -181,6 +181,32 @@ int rio_op_changes(rio_op_t* p, uint64_t* n_out, int* full, const char* const** 
 /* Forget what the consumer was told: the next rio_op_changes is a full listing (a mirror that failed to apply a listing). */
 int rio_op_changes_reset(rio_op_t* p);
 
+/* Idle deactivation (rio_gp_touch_merge + rio_gp_expire, DESIGN.md section 2 rule 9; the reference's "TODO: ttl" / "TODO:
+ * last_seen", object_placement/mod.rs:23-24).  The host owns the clock: rio_op_set_clock sets the epoch every later call stamps
+ * with.  It is 0 at creation, which means stamping is off: every call then pays one relaxed load and nothing more.
+ *   - Once the clock is non-zero, every call that ANSWERS OR SETS AN ADDRESS for a key stamps that key with the clock: a lookup
+ *     or try_lookup that finds a placement (host-shadow hits included), an update with an address, a get_or_create_placement or
+ *     try_get_or_create_placement that returns an address, and the batch forms per entry.  remove, set_object_load, a lookup
+ *     that finds nothing and a call that fails do not stamp.  Stamps only rise.
+ *   - rio_op_expire un-places every placed key last stamped before `cutoff` (never stamped counts as 0), at most
+ *     max_objects_out of them (~0: no limit; 0: count only, nothing changes), in the dense layer's row order, and lists them
+ *     with the address each was on (NULL for a node id without an address, as in rio_op_snapshot).  *n_out = keys listed;
+ *     *n_idle (may be NULL) = every idle key, listed or not.  What the host does with a listed (object, address) is its own
+ *     business — typically it tells that server to shut the object down.
+ *   - With the clock never set, nothing was ever stamped: any cutoff > 0 lists everything that is placed.
+ *   - A key stamped with an epoch >= cutoff before the call took its locks is never listed.  (A call that overlaps the sweep
+ *     may be answered with the address and the key listed all the same: the host decides what an answer that old is worth.)
+ *   - The listed keys are un-placed exactly as rio_op_remove would: later lookups answer "none" (the host shadow is corrected
+ *     for exactly those keys; every other key is still answered from it), rio_op_changes lists them as deletes, and the table
+ *     may hand their rows to new keys.  A row handed on keeps its stamp until its new key's first call.
+ *   - The call holds the device lock and the write side of the table lock.  The arrays are owned by the calling thread until
+ *     its next call of this function, as rio_op_rebalance's; key lengths come with them (a key may hold NUL bytes).
+ *   - A dense layer without rio_gp_touch_merge / rio_gp_expire: RIO_GP_EUPSTREAM, nothing changed. */
+int rio_op_set_clock(rio_op_t* p, uint32_t now);
+int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64_t* n_out, uint64_t* n_idle,
+                  const char* const** struct_names, const size_t** struct_name_lens, const char* const** object_ids,
+                  const size_t** object_id_lens, const char* const** addresses);
+
 /* Keys with their lengths.  ObjectId(String, String) (service_object.rs:19-26) holds any Rust string, a NUL byte included;
  * the entry points above take NUL-terminated strings and would cut such a key short.  These take struct_name / object_id
  * as (pointer, length) and are otherwise the same calls (the Rust adapter binds THESE: rio-rs_amd/rust/src/gpu.rs).

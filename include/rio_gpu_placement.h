@@ -349,6 +349,57 @@ int rio_gp_changes_dev(rio_gp_t* h, uint32_t flags, uint32_t* d_rows, uint32_t* 
                        uint64_t* n_changes);
 int rio_gp_changes_reset(rio_gp_t* h);
 
+/* ---- idle expiry: last-seen stamps, and un-placing the rows nobody has asked for -------------- */
+
+/* ObjectPlacementItem's "TODO: ttl" and "TODO: last_seen" (rio-rs/src/object_placement/mod.rs:23-24) for the dense table.  The
+ * handle keeps a last-seen column S, one u32 per row of max_objects: the caller's epoch at which the row was last touched, 0 =
+ * never seen.  Epochs are the caller's numbers; the library reads no clock.  S is written by the touch calls only: ticks, the
+ * CRUD calls, rio_gp_place_pending, rio_gp_set_objects, rio_gp_set_num_objects and rio_gp_remap_nodes leave it alone (S names
+ * no node).
+ *   - rio_gp_touch_batch: S[idx[k]] = max(S[idx[k]], epoch).  A maximum: duplicates and ordering do not matter.  The host form
+ *     validates first (an idx[k] >= n is RIO_GP_EINVAL, nothing changes); the _dev form skips invalid entries and reports
+ *     RIO_GP_EINVAL, as rio_gp_remove_batch_dev does.
+ *   - rio_gp_touch_all: the same for every row r < n.
+ *   - rio_gp_touch_merge: S[r] = max(S[r], stamps[r]) for r < rows, rows <= n (RIO_GP_EINVAL otherwise): a host that keeps
+ *     stamps of its own hands them over in one streaming pass.
+ *   - rio_gp_get_seen: S[0 .. n-1]; n must be the row count, as for rio_gp_get_assign.
+ *   - Touch calls are no inputs of any solve: `used`, an uncommitted rio_gp_solve and the quiet and chained tick state stay as
+ *     they were.  They order themselves on the handle's stream; rio_gp_touch_all and rio_gp_touch_merge_dev do not wait.
+ *
+ * rio_gp_expire (DESIGN.md section 2 rule 9).  A = the column rio_gp_get_assign returns at the point of the call.  Row r < n is
+ * IDLE iff A[r] != RIO_GP_NONE and S[r] < cutoff (raw values: node ids >= m count as placed; affinity is not consulted).
+ *   - *n_idle = every idle row, listed or not.  The listing is the first L = min(n_idle, cap) idle rows in ascending row order:
+ *     out_rows[k] = r, out_node[k] = A[r].
+ *   - Exactly the listed rows are un-placed as rio_gp_remove_batch of those rows would do it: A[r] := RIO_GP_NONE; under
+ *     RIO_GP_CFG_ROW_LIFECYCLE the row becomes a non-object (affinity RIO_GP_AFF_INACTIVE); load and S stay.  `used` follows the
+ *     writes when it is valid, as the remove kernels keep it (it stays invalid otherwise and is rebuilt before its next use).
+ *     The change feed lists them as (r, old, RIO_GP_NONE) with no extra work.
+ *   - *load_freed (may be NULL) = the sum of the listed rows' loads.
+ *   - A small cap pages by prefix and bounds the work per sweep: a listed row is no longer idle.  Never RIO_GP_ERANGE.
+ *   - The two arrays are given together or not at all; without them cap must be 0: count only, nothing changes at all (the
+ *     quiet and chained tick state included, like the feed's count).  cutoff == 0 finds nothing.
+ *   - Like the feed it orders itself behind rio_gp_tick_async work in flight.  With L > 0 it behaves like rio_gp_remove_batch:
+ *     it drops an uncommitted rio_gp_solve and counts as a change of the inputs.  With L == 0 it changes nothing.
+ *   - Rows >= n are never idle and keep their S.
+ *   - RIO_GP_EINVAL, nothing changed: n_idle == NULL; the array rule; a handle of the row-sharded solve (rio_gp_shard_*,
+ *     rio_gp_p2p_*: a per-shard expiry is not implemented) — the touch calls and rio_gp_get_seen refuse the same way.
+ *   - Memory: S takes 4 B per row of max_objects, allocated (zero-filled) by the first call of this section and kept until
+ *     rio_gp_destroy, plus the feed's 4 B per 1 024 rows of tile counts; a handle that calls none of them pays nothing.  The
+ *     host-pointer form stages its listing in device memory (8 B per listed row).
+ *   - Cost: one streaming pass over A and S (8 B per row) to count; the apply pass re-reads only the tiles of 1 024 rows that
+ *     hold a listed row.
+ * The _dev form writes into device arrays of cap entries and waits once. */
+int rio_gp_touch_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, uint32_t epoch);
+int rio_gp_touch_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, uint32_t epoch);
+int rio_gp_touch_all(rio_gp_t* h, uint32_t epoch);
+int rio_gp_touch_merge(rio_gp_t* h, uint64_t rows, const uint32_t* stamps);
+int rio_gp_touch_merge_dev(rio_gp_t* h, uint64_t rows, const uint32_t* d_stamps);
+int rio_gp_get_seen(rio_gp_t* h, uint64_t n, uint32_t* out);
+int rio_gp_expire(rio_gp_t* h, uint32_t cutoff, uint32_t* out_rows, uint32_t* out_node, uint64_t cap, uint64_t* n_idle,
+                  uint64_t* load_freed);
+int rio_gp_expire_dev(rio_gp_t* h, uint32_t cutoff, uint32_t* d_rows, uint32_t* d_node, uint64_t cap, uint64_t* n_idle,
+                      uint64_t* load_freed);
+
 /* ---- the placement policy, batched ------------------------------------------------------ */
 
 /* Service::get_or_create_placement + check_address_mismatch (service.rs:193-298) for a batch

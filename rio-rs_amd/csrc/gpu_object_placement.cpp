@@ -65,6 +65,10 @@ extern "C" int rio_gp_changes(rio_gp_t* h, uint32_t flags, uint32_t* out_rows, u
 extern "C" int rio_gp_changes_reset(rio_gp_t* h) __attribute__((weak));
 // Weak for the same reason: node removal (rio_op_remove_members reports RIO_GP_EUPSTREAM without it).
 extern "C" int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* map, uint64_t* evicted) __attribute__((weak));
+// Weak for the same reason: idle expiry (rio_op_expire reports RIO_GP_EUPSTREAM without them).
+extern "C" int rio_gp_touch_merge(rio_gp_t* h, uint64_t rows, const uint32_t* stamps) __attribute__((weak));
+extern "C" int rio_gp_expire(rio_gp_t* h, uint32_t cutoff, uint32_t* out_rows, uint32_t* out_node, uint64_t cap, uint64_t* n_idle,
+                             uint64_t* load_freed) __attribute__((weak));
 
 namespace {
 
@@ -113,6 +117,12 @@ thread_local std::vector<std::string> t_ch_store;
 thread_local std::vector<const char*> t_ch_ty, t_ch_id, t_ch_old, t_ch_new;
 thread_local std::vector<size_t> t_ch_tylen, t_ch_idlen;
 thread_local std::vector<uint32_t> t_ch_rows, t_ch_src, t_ch_dst;
+
+// rio_op_expire's arrays, the same way (keys as copies; the addresses point into the node table, whose strings never change)
+thread_local std::vector<std::string> t_ex_store;
+thread_local std::vector<const char*> t_ex_ty, t_ex_id, t_ex_addr;
+thread_local std::vector<size_t> t_ex_tylen, t_ex_idlen;
+thread_local std::vector<uint32_t> t_ex_rows, t_ex_node, t_ex_stamps;
 
 // One single-object call waiting for its device round trip (see run_combined).
 // One single-object call waiting for its device round trip (see run_combined).  The struct is a cache line of its own: its
@@ -203,6 +213,57 @@ struct Shadow {
     void invalidate_all() { base.store(clock.fetch_add(1, std::memory_order_acq_rel) + 1, std::memory_order_release); }
 };
 
+// Last-seen stamps (rio_op_set_clock / rio_op_expire): the host's clock value at which a call last answered or set an address
+// for the row's key, one atomic u32 per row in chunks of 65 536 rows allocated by whoever stamps first (any thread: the chunk
+// pointer is installed with a compare-exchange).  While the clock is 0 a call pays one relaxed load of it and nothing more.  A
+// stamp is a maximum and is written only when the word is lower than the clock: a hot row costs one read-modify-write per clock
+// value, not one per call.  Stampers hold the shared side of the table lock, or count as in flight (their row id is theirs);
+// rio_op_expire reads the words under the exclusive side.  A row that reclaim() hands to another key keeps its stamp: stamps
+// only rise, on the host as on the device, so a recycled row counts as seen when its previous key was, until its own first call.
+struct Stamps {
+    static constexpr uint32_t kBits = 16;
+    std::atomic<uint32_t> now{0};
+    size_t nchunks = 0;
+    std::unique_ptr<std::atomic<std::atomic<uint32_t>*>[]> chunks;
+    void init(uint64_t max_objects) {
+        nchunks = (size_t)((max_objects + (1u << kBits) - 1) >> kBits);
+        chunks.reset(new std::atomic<std::atomic<uint32_t>*>[nchunks ? nchunks : 1]);
+        for (size_t c = 0; c < (nchunks ? nchunks : 1); ++c) chunks[c].store(nullptr, std::memory_order_relaxed);
+    }
+    ~Stamps() {
+        for (size_t c = 0; c < nchunks; ++c) delete[] chunks[c].load(std::memory_order_relaxed);
+    }
+    void stamp(uint32_t row) {
+        const uint32_t t = now.load(std::memory_order_relaxed);
+        if (!t) return;
+        std::atomic<std::atomic<uint32_t>*>& slot = chunks[row >> kBits];
+        std::atomic<uint32_t>* ch = slot.load(std::memory_order_acquire);
+        if (!ch) {
+            std::atomic<uint32_t>* fresh = new std::atomic<uint32_t>[1u << kBits];
+            for (uint32_t k = 0; k < (1u << kBits); ++k) fresh[k].store(0, std::memory_order_relaxed);
+            if (slot.compare_exchange_strong(ch, fresh, std::memory_order_acq_rel, std::memory_order_acquire)) ch = fresh;
+            else delete[] fresh;  // (somebody else's chunk is in: ch holds it)
+        }
+        std::atomic<uint32_t>& w = ch[row & ((1u << kBits) - 1)];
+        uint32_t cur = w.load(std::memory_order_relaxed);
+        while (cur < t && !w.compare_exchange_weak(cur, t, std::memory_order_relaxed)) {}
+    }
+    // the stamps of rows 0 .. n-1 (0: never stamped); false: nothing has ever been stamped (out is not written)
+    bool gather(uint64_t n, std::vector<uint32_t>& out) const {
+        bool any = false;
+        for (size_t c = 0; c < nchunks && !any; ++c) any = chunks[c].load(std::memory_order_acquire) != nullptr;
+        if (!any) return false;
+        out.assign(n, 0u);
+        for (uint64_t r0 = 0; r0 < n; r0 += (1u << kBits)) {
+            const std::atomic<uint32_t>* ch = chunks[r0 >> kBits].load(std::memory_order_acquire);
+            if (!ch) continue;
+            const uint64_t k1 = std::min<uint64_t>(n - r0, 1u << kBits);
+            for (uint64_t k = 0; k < k1; ++k) out[r0 + k] = ch[k].load(std::memory_order_relaxed);
+        }
+        return true;
+    }
+};
+
 // The table lock: readers are every single-object call (a shadow hit holds it for ~0.3 us and touches nothing else that is
 // shared), writers are rare (a key or an address nobody has seen, a reclaim, the batched calls' interning).  std::shared_mutex
 // keeps ONE reader count: two read-modify-writes of one cache line per call, 16 callers on two sockets spent most of a hit
@@ -288,6 +349,7 @@ struct State {
     std::vector<uint32_t> sv_row, sv_req;
     struct KindBuf { std::vector<uint32_t> rows, reqs, res, fl, who; } sv_kb[4];  // the batch split by kind
     Shadow shadow;
+    Stamps seen;
     uint64_t dev_batches = 0, dev_requests = 0;  // (under mu) device round trips of combined batches / requests they carried
     size_t last_batch = 0, prev_batch = 0;       // (under mu) requests of the last two combined batches
     uint32_t collect_ns = 0;                     // rio_op_cfg.collect_ns
@@ -986,6 +1048,7 @@ int rio_op_create(const rio_op_cfg* cfg, rio_op_t** out) {
     s->pushed_version = s->node_version.load();  // the empty node table is on the device
     s->pushed_shape = s->shape_version.load();
     s->shadow.init(cfg->max_objects, cfg->max_nodes, (cfg->flags & RIO_OP_CFG_NO_HOST_SHADOW) == 0);
+    s->seen.init(cfg->max_objects);
     s->collect_ns = cfg->collect_ns ? cfg->collect_ns : RIO_OP_DEFAULT_COLLECT_NS;
     s->cpus = usable_cpus();
     s->self_assign = (cfg->flags & RIO_OP_CFG_LIVE_FIRST_TOUCH) == 0;
@@ -1047,7 +1110,10 @@ static int op_update_batch(rio_op_t* p, uint64_t n, const Keys& ks, const char* 
         if (rows.empty()) return RIO_GP_OK;
         rc = rio_gp_update_batch(s->gp, rows.size(), rows.data(), nodes.data());
         if (rc) return gp_fail(s, rc);
-        for (size_t k = 0; k < rows.size(); ++k) s->shadow.put(rows[k], nodes[k]);  // (in order: the last writer of a row wins)
+        for (size_t k = 0; k < rows.size(); ++k) {  // (in order: the last writer of a row wins)
+            s->shadow.put(rows[k], nodes[k]);
+            if (nodes[k] != RIO_GP_NONE) s->seen.stamp(rows[k]);
+        }
         return RIO_GP_OK;
     });
 }
@@ -1076,6 +1142,9 @@ static int op_update(rio_op_t* p, const Part& ty, const Part& id, const char* ad
         // None: remove(key) (local.rs:36-37) — an unknown key stays unknown
         if ((rc = intern_row(s, ty, id, false, &r.row, true, excl))) return rc;
         return r.row == RIO_GP_NONE ? kNoop : RIO_GP_OK;
+    }, [&](int rc) -> int {  // (still in flight: the row is this key's)
+        if (!rc && addr) s->seen.stamp(r.row);
+        return rc;
     });
     return rc == kNoop ? RIO_GP_OK : rc;
 }
@@ -1102,7 +1171,11 @@ static int op_lookup_batch(rio_op_t* p, uint64_t n, const Keys& ks, uint32_t* ou
     std::vector<uint32_t> res(rows.size());
     rc = rio_gp_lookup_batch(s->gp, rows.size(), rows.data(), res.data());
     if (rc) return gp_fail(s, rc);
-    for (size_t q = 0; q < rows.size(); ++q) { out[where[q]] = res[q]; s->shadow.put(rows[q], res[q]); }
+    for (size_t q = 0; q < rows.size(); ++q) {
+        out[where[q]] = res[q];
+        s->shadow.put(rows[q], res[q]);
+        if (res[q] != RIO_GP_NONE) s->seen.stamp(rows[q]);
+    }
     return RIO_GP_OK;
 }
 
@@ -1137,7 +1210,7 @@ static int op_lookup(rio_op_t* p, const Part& ty, const Part& id, char* out, siz
         // (local.rs:42-49 is a hash-map read; so is this).  The address is copied out here, under the table lock.
         if (s->shadow.get(r.row, &r.node)) {
             *found = r.node != RIO_GP_NONE;
-            if (*found) hit_rc = copy_out(s->node_addr[r.node], out, cap);
+            if (*found && !(hit_rc = copy_out(s->node_addr[r.node], out, cap))) s->seen.stamp(r.row);
             return kHit;
         }
         return RIO_GP_OK;
@@ -1147,7 +1220,9 @@ static int op_lookup(rio_op_t* p, const Part& ty, const Part& id, char* out, siz
         t_addr_len = 0;
         if (*found) {
             std::shared_lock<TableLock> gi(s->imu);
-            return copy_out(s->node_addr[r.node], out, cap);  // RIO_GP_ERANGE: *found is set, nothing was copied
+            const int crc = copy_out(s->node_addr[r.node], out, cap);  // RIO_GP_ERANGE: *found is set, nothing was copied
+            if (!crc) s->seen.stamp(r.row);
+            return crc;
         }
         return RIO_GP_OK;
     });
@@ -1189,7 +1264,10 @@ int rio_op_try_lookup_n(rio_op_t* p, const char* ty, size_t ty_len, const char* 
     uint32_t node;
     if (!s->shadow.get(it->second, &node)) return RIO_GP_EAGAIN;
     *found = node != RIO_GP_NONE;
-    return *found ? copy_out(s->node_addr[node], out, cap) : RIO_GP_OK;
+    if (!*found) return RIO_GP_OK;
+    const int rc = copy_out(s->node_addr[node], out, cap);
+    if (!rc) s->seen.stamp(it->second);
+    return rc;
 }
 
 int rio_op_try_get_or_create_placement_n(rio_op_t* p, const char* ty, size_t ty_len, const char* id, size_t id_len,
@@ -1208,7 +1286,9 @@ int rio_op_try_get_or_create_placement_n(rio_op_t* p, const char* ty, size_t ty_
     if (!s->shadow.get(it->second, &nd) || nd == RIO_GP_NONE || nd >= s->node_alive.size() || !s->node_alive[nd] || s->node_malformed[nd])
         return RIO_GP_EAGAIN;
     if (flag) *flag = nd == rq->second ? RIO_GP_FLAG_LOCAL : RIO_GP_FLAG_REDIRECT;
-    return copy_out(s->node_addr[nd], out, cap);
+    const int rc = copy_out(s->node_addr[nd], out, cap);
+    if (!rc) s->seen.stamp(it->second);
+    return rc;
 }
 
 int rio_op_clean_server(rio_op_t* p, const char* address) {
@@ -1384,7 +1464,10 @@ static int op_get_or_create_batch(rio_op_t* p, uint64_t n, const Keys& ks, const
         }
         int rc;
         if ((rc = sync_device(s, true))) return rc;
-        return policy_batch(s, rows, reqs, out_node, out_flag);
+        if ((rc = policy_batch(s, rows, reqs, out_node, out_flag))) return rc;
+        for (uint64_t k = 0; k < n; ++k)
+            if (out_node[k] != RIO_GP_NONE) s->seen.stamp(rows[k]);
+        return RIO_GP_OK;
     });
 }
 
@@ -1418,7 +1501,7 @@ static int op_get_or_create(rio_op_t* p, const Part& ty, const Part& id, const c
             r.node = nd;
             r.flag = nd == r.req ? RIO_GP_FLAG_LOCAL : RIO_GP_FLAG_REDIRECT;
             if (flag) *flag = r.flag;
-            hit_rc = copy_out(s->node_addr[nd], out, cap);
+            if (!(hit_rc = copy_out(s->node_addr[nd], out, cap))) s->seen.stamp(r.row);
             return kHit;
         }
         return RIO_GP_OK;
@@ -1427,7 +1510,9 @@ static int op_get_or_create(rio_op_t* p, const Part& ty, const Part& id, const c
         if (flag) *flag = r.flag;
         std::shared_lock<TableLock> gi(s->imu);
         // RIO_GP_ERANGE: the decision is made and *flag is set; the address is one rio_op_lookup away (a pure read)
-        return copy_out(r.node == RIO_GP_NONE ? std::string() : s->node_addr[r.node], out, cap);
+        const int crc = copy_out(r.node == RIO_GP_NONE ? std::string() : s->node_addr[r.node], out, cap);
+        if (!crc && r.node != RIO_GP_NONE) s->seen.stamp(r.row);
+        return crc;
     });
     if (rc == kHit) return hit_rc;
     return rc;
@@ -1588,6 +1673,72 @@ int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const cha
     *object_id_lens = t_rb_idlen.data();
     *from_addresses = t_rb_from.data();
     *to_addresses = t_rb_to.data();
+    return RIO_GP_OK;
+}
+
+int rio_op_set_clock(rio_op_t* p, uint32_t now) {
+    if (!p) return RIO_GP_EINVAL;
+    p->s->seen.now.store(now, std::memory_order_relaxed);
+    return RIO_GP_OK;
+}
+
+int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64_t* n_out, uint64_t* n_idle,
+                  const char* const** struct_names, const size_t** struct_name_lens, const char* const** object_ids,
+                  const size_t** object_id_lens, const char* const** addresses) {
+    if (!p || !n_out || !struct_names || !struct_name_lens || !object_ids || !object_id_lens || !addresses) return RIO_GP_EINVAL;
+    State* s = p->s;
+    t_ex_store.clear();
+    t_ex_ty.clear(); t_ex_id.clear(); t_ex_addr.clear(); t_ex_tylen.clear(); t_ex_idlen.clear();
+    *n_out = 0;
+    if (n_idle) *n_idle = 0;
+    {
+        // mu keeps every device change out; the write side of the table lock keeps every stamper out: a stamp of an epoch >=
+        // cutoff that was written before this lock was taken is in the upload below, so its key cannot be listed
+        DevLock g(s);
+        std::lock_guard<TableLock> gi(s->imu);
+        int rc;
+        if ((rc = sync_device(s, true))) return rc;
+        if (!rio_gp_touch_merge || !rio_gp_expire) return fail(RIO_GP_EUPSTREAM, "dense layer has no idle expiry");
+        const uint64_t n = s->hi_rows;
+        if (s->seen.gather(n, t_ex_stamps) && (rc = rio_gp_touch_merge(s->gp, n, t_ex_stamps.data()))) return gp_fail(s, rc);
+        const uint64_t cap = std::min<uint64_t>(max_objects_out, n);  // a listed row is a row that is handed out
+        uint64_t idle = 0;
+        if (!cap) {  // count only: nothing changes
+            if ((rc = rio_gp_expire(s->gp, cutoff, nullptr, nullptr, 0, &idle, nullptr))) return gp_fail(s, rc);
+            if (n_idle) *n_idle = idle;
+        } else {
+            t_ex_rows.resize(cap); t_ex_node.resize(cap);
+            if ((rc = rio_gp_expire(s->gp, cutoff, t_ex_rows.data(), t_ex_node.data(), cap, &idle, nullptr))) {
+                s->shadow.invalidate_all();  // (nobody can tell which rows it un-placed before it failed)
+                return gp_fail(s, rc);
+            }
+            if (n_idle) *n_idle = idle;
+            const uint64_t got = std::min(idle, cap);
+            const uint32_t m = (uint32_t)s->node_addr.size();
+            // the shadow follows precisely: exactly the listed rows are un-placed; every other row's entry stands
+            for (uint64_t k = 0; k < got; ++k) {
+                const uint32_t row = t_ex_rows[k];
+                s->shadow.put(row, RIO_GP_NONE);
+                if (row >= s->row_live.size() || !s->row_live[row]) continue;
+                // copies: keys can be reclaimed as soon as the locks are released
+                t_ex_store.push_back(s->row_key[row].first);
+                t_ex_store.push_back(s->row_key[row].second);
+                t_ex_addr.push_back(t_ex_node[k] < m ? s->node_addr[t_ex_node[k]].c_str() : nullptr);
+            }
+        }
+    }
+    for (size_t k = 0; k + 1 < t_ex_store.size(); k += 2) {
+        t_ex_ty.push_back(t_ex_store[k].data());
+        t_ex_tylen.push_back(t_ex_store[k].size());
+        t_ex_id.push_back(t_ex_store[k + 1].data());
+        t_ex_idlen.push_back(t_ex_store[k + 1].size());
+    }
+    *n_out = t_ex_ty.size();
+    *struct_names = t_ex_ty.data();
+    *struct_name_lens = t_ex_tylen.data();
+    *object_ids = t_ex_id.data();
+    *object_id_lens = t_ex_idlen.data();
+    *addresses = t_ex_addr.data();
     return RIO_GP_OK;
 }
 

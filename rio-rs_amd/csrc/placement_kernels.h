@@ -518,4 +518,19 @@ constexpr u32 kNodeGone = 0xFFFFFFFCu;   // RIO_GP_NODE_GONE: checkpoint of a ro
 // {0, rows < n_count it un-placed, 0, 0}; returns G.
 u32 launch_remap(u32* assign, u32* aff, u32* B, u64 rows, u64 n_count, u32 m, const u32* map, bool life, u64* blk, hipStream_t s);
 
+// --- idle expiry (rio_gp_touch_*, rio_gp_expire): a last-seen column S; the placed rows with S < cutoff are listed and un-placed ---
+constexpr u32 kExpLdsNodes = 4096;  // node counts up to which k_exp_apply gathers the released load per workgroup in LDS (32 KiB)
+// the feed's plan, per-tile counts, workgroup sums and mapped total word (launch_chg_count), with the idle predicate over
+// (A, S, cutoff); *freed (device memory) is zeroed for launch_exp_apply
+void launch_exp_count(const u32* A, const u32* S, const ChgPlan& p, u32 cutoff, u32* cnt, u32* gsum, u32* total, u64* freed,
+                      hipStream_t s);
+// the first `cap` idle rows as (row, A[row]); each of them: A[row] := kNone, aff_life[row] := kAffInactive (aff_life != nullptr),
+// *freed += load[row], used[A[row]] -= load[row] (used != nullptr and A[row] < m)
+void launch_exp_apply(u32* A, const u32* S, const ChgPlan& p, u32 cutoff, const u32* cnt, const u32* gsum, u64 cap, u32* rows,
+                      u32* node, u32* aff_life, const u32* load, u32 m, u64* used, u64* freed, hipStream_t s);
+// S[idx[k]] = max(S[idx[k]], epoch) for k < n; entries >= n_obj are skipped and counted in st->err
+void launch_touch(u32* S, u64 n_obj, const u32* idx, u64 n, u32 epoch, DevStats* st, hipStream_t s);
+// S[r] = max(S[r], stamps ? stamps[r] : epoch) for r < rows (S is padded: whole quads are read and written)
+void launch_seen_merge(u32* S, const u32* stamps, u32 epoch, u64 rows, hipStream_t s);
+
 }  // namespace riogp

@@ -7077,4 +7077,208 @@ u32 launch_remap(u32* assign, u32* aff, u32* B, u64 rows, u64 n_count, u32 m, co
     return p.G;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Idle expiry (rio_gp_touch_*, rio_gp_expire; DESIGN.md section 2 rule 9): a last-seen column S, one u32 per row, and the rows
+// r < n that are placed (A[r] != kNone, raw values) with S[r] < cutoff.  The shape is the change feed's — a count pass, the
+// one-workgroup scan (k_chg_scan itself), a pass over the tiles that hold a hit — with the same plan, the same per-tile counts
+// and workgroup sums, and no fence and no workgroup waiting on another:
+//   k_exp_count  k_chg_count with the idle predicate over (A, S); workgroup 0 also zeroes the freed-load word.
+//   k_exp_apply  k_chg_list's ranking (ballots over each lane's 0..4); a listed row is written out as (row, A[row]), loses its
+//                node (the lane stores its four A words back, dwordx4) and, under the row lifecycle, becomes a non-object; its
+//                load goes into the freed-load sum and, when `used` is maintained, off its node: per workgroup through an LDS
+//                histogram (m <= kExpLdsNodes: a workgroup's rows share few nodes' words), else straight to `used` (more nodes
+//                than that spread the atomics over as many addresses; the histogram would not fit next to the tile offsets).
+//                Integer sums: the order of the additions does not show.
+//   k_touch      S[idx[k]] = max(S[idx[k]], epoch), a scatter of atomic maxima: duplicates and order do not matter.
+//   k_seen_merge S[r] = max(S[r], stamps ? stamps[r] : epoch) for r < rows, four rows per lane; a quad is stored only where it
+//                rose.  S is padded like the other columns; `stamps` is the caller's and is read by quads only where whole quads
+//                of it exist and it is 16-byte aligned (vec).
+// ------------------------------------------------------------------------------------------------
+// bit j: row i0 + j is idle (rows >= n never are)
+__device__ __forceinline__ u32 exp_flags(const uint4& a, const uint4& s, u32 cutoff, u64 i0, u64 n) {
+    return (u32)(i0 < n && a.x != kNone && s.x < cutoff) | ((u32)(i0 + 1 < n && a.y != kNone && s.y < cutoff) << 1) |
+           ((u32)(i0 + 2 < n && a.z != kNone && s.z < cutoff) << 2) | ((u32)(i0 + 3 < n && a.w != kNone && s.w < cutoff) << 3);
+}
+
+__global__ __launch_bounds__(kChgWaves * 64, 8) void k_exp_count(const u32* __restrict__ A, const u32* __restrict__ S, const ChgPlan p,
+                                                               u32 cutoff, u32* __restrict__ cnt, u32* __restrict__ gsum,
+                                                               u64* __restrict__ freed) {
+    __shared__ u32 ws[kChgWaves];
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u32 t0 = blockIdx.x * p.tpg, t1 = t0 + p.tpg < p.nt ? t0 + p.tpg : p.nt;
+    u32 mine = 0;
+    for (u32 t = t0 + wv; t < t1; t += kChgWaves) {  // wave-uniform
+        const u64 lo = (u64)t * kChgTile;
+        uint4 a[4], sv[4];
+        chg_load(A, S, lo, lane, a, sv);
+        u32 c = 0;  // 0 .. 16
+#pragma unroll
+        for (int s = 0; s < 4; ++s) c += __builtin_popcount(exp_flags(a[s], sv[s], cutoff, lo + (u64)s * 256 + lane * 4, p.n));
+        u32 tc = 0;
+#pragma unroll
+        for (int bit = 0; bit < 5; ++bit) tc += (u32)__builtin_popcountll(__ballot((c >> bit) & 1u)) << bit;
+        if (lane == 0) cnt[t] = tc;
+        mine += tc;
+    }
+    if (lane == 0) ws[wv] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        gsum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+        if (blockIdx.x == 0) *freed = 0;  // (k_exp_apply, a later launch, adds into it)
+    }
+}
+
+__global__ __launch_bounds__(kChgWaves * 64, 8) void k_exp_apply(u32* __restrict__ A, const u32* __restrict__ S, const ChgPlan p,
+                                                               u32 cutoff, const u32* __restrict__ cnt,
+                                                               const u32* __restrict__ gsum, u64 cap, u32* __restrict__ rows,
+                                                               u32* __restrict__ node, u32* __restrict__ aff_life,
+                                                               const u32* __restrict__ load, u32 m, u64* __restrict__ used,
+                                                               u32 hist, u64* __restrict__ freed) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64* rel = reinterpret_cast<u64*>(smem);  // [m] load released per node (hist only)
+    __shared__ u32 toff[kChgMaxTpg];
+    __shared__ u32 lds[4];
+    __shared__ u64 gfree;
+    const u64 base = gsum[blockIdx.x];
+    if (base >= cap || gsum[blockIdx.x + 1] == base) return;  // everything past the listing, or nothing here
+    const u32 t0 = blockIdx.x * p.tpg, k = p.tpg < p.nt - t0 ? p.tpg : p.nt - t0;
+    constexpr u32 per = kChgMaxTpg / (kChgWaves * 64);
+    u32 v[per], sum = 0;
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        const u32 i = threadIdx.x * per + q;
+        v[q] = i < k ? cnt[t0 + i] : 0u;
+        sum += v[q];
+    }
+    u32 tot;
+    u32 run = ni_block_excl(sum, lds, &tot);
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        const u32 i = threadIdx.x * per + q;
+        if (i < k) toff[i] = run;
+        run += v[q];
+    }
+    if (hist)
+        for (u32 j = threadIdx.x; j < m; j += kChgWaves * 64) rel[j] = 0;
+    if (threadIdx.x == 0) gfree = 0;
+    __syncthreads();
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u64 lt = (1ull << lane) - 1ull;
+    u64 fr = 0;
+    for (u32 i = wv; i < k; i += kChgWaves) {  // wave-uniform
+        u64 off = base + toff[i];
+        const u32 c = (i + 1 < k ? toff[i + 1] : tot) - toff[i];
+        if (c == 0 || off >= cap) continue;
+        const u64 lo = (u64)(t0 + i) * kChgTile;
+        u32 fl = 0;  // the four steps' flags, a nibble each; a lane with a hit reads its quad of A again (a cache hit), so that
+                     // no tile is held in registers across the listing (it spilled to scratch at eight waves per SIMD)
+        {
+            uint4 a[4], sv[4];
+            chg_load(A, S, lo, lane, a, sv);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) fl |= exp_flags(a[s], sv[s], cutoff, lo + (u64)s * 256 + lane * 4, p.n) << (4 * s);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const u64 i0 = lo + (u64)s * 256 + lane * 4;
+            const u32 f = (fl >> (4 * s)) & 15u;
+            const u32 lc = (u32)__builtin_popcount(f);  // 0 .. 4
+            u32 below = 0, all = 0;
+#pragma unroll
+            for (int bit = 0; bit < 3; ++bit) {
+                const u64 bb = __ballot((lc >> bit) & 1u);
+                below += (u32)__builtin_popcountll(bb & lt) << bit;
+                all += (u32)__builtin_popcountll(bb) << bit;
+            }
+            if (f) {
+                const uint4 q = *reinterpret_cast<const uint4*>(A + i0);
+                u32 av[4] = {q.x, q.y, q.z, q.w};
+                u64 r = off + below;
+                bool listed = false;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!((f >> j) & 1u)) continue;
+                    if (r < cap) {
+                        const u32 li = load[i0 + j];
+                        rows[r] = (u32)(i0 + j);
+                        node[r] = av[j];
+                        fr += li;
+                        if (used && av[j] < m) {
+                            if (hist) atomicAdd(&rel[av[j]], (u64)li);
+                            else atomicAdd(&used[av[j]], (u64)0 - (u64)li);
+                        }
+                        if (aff_life) aff_life[i0 + j] = kAffInactive;  // row lifecycle: an expired row is no longer an object
+                        av[j] = kNone;
+                        listed = true;
+                    }
+                    ++r;
+                }
+                if (listed) *reinterpret_cast<uint4*>(A + i0) = make_uint4(av[0], av[1], av[2], av[3]);
+            }
+            off += all;
+            if (off >= cap) break;  // (wave-uniform)
+        }
+    }
+    if (fr) atomicAdd(&gfree, fr);
+    __syncthreads();
+    if (threadIdx.x == 0 && gfree) atomicAdd(freed, gfree);
+    if (hist)
+        for (u32 j = threadIdx.x; j < m; j += kChgWaves * 64)
+            if (rel[j]) atomicAdd(&used[j], (u64)0 - rel[j]);
+}
+
+__global__ __launch_bounds__(256) void k_touch(u32* __restrict__ S, u64 n_obj, const u32* __restrict__ idx, u64 n, u32 epoch,
+                                               DevStats* st) {
+    u32 bad = 0;
+    for (u64 k = (u64)blockIdx.x * 256 + threadIdx.x; k < n; k += (u64)gridDim.x * 256) {
+        const u32 i = idx[k];
+        if (i >= n_obj) { ++bad; continue; }
+        atomicMax(&S[i], epoch);
+    }
+    if (bad) atomicAdd(&st->err, (u64)bad);
+}
+
+__global__ __launch_bounds__(256) void k_seen_merge(u32* __restrict__ S, const u32* __restrict__ stamps, u32 epoch, u64 rows,
+                                                    u32 vec) {
+    for (u64 i0 = ((u64)blockIdx.x * 256 + threadIdx.x) * 4; i0 < rows; i0 += (u64)gridDim.x * 1024) {
+        const uint4 s = *reinterpret_cast<const uint4*>(S + i0);
+        uint4 e = make_uint4(epoch, i0 + 1 < rows ? epoch : 0u, i0 + 2 < rows ? epoch : 0u, i0 + 3 < rows ? epoch : 0u);
+        if (stamps) {
+            if (vec && i0 + 4 <= rows) {
+                e = *reinterpret_cast<const uint4*>(stamps + i0);
+            } else {
+                e.x = stamps[i0];
+                if (i0 + 1 < rows) e.y = stamps[i0 + 1];
+                if (i0 + 2 < rows) e.z = stamps[i0 + 2];
+                if (i0 + 3 < rows) e.w = stamps[i0 + 3];
+            }
+        }
+        const uint4 o = make_uint4(s.x > e.x ? s.x : e.x, s.y > e.y ? s.y : e.y, s.z > e.z ? s.z : e.z, s.w > e.w ? s.w : e.w);
+        if ((o.x != s.x) | (o.y != s.y) | (o.z != s.z) | (o.w != s.w)) *reinterpret_cast<uint4*>(S + i0) = o;
+    }
+}
+
+void launch_exp_count(const u32* A, const u32* S, const ChgPlan& p, u32 cutoff, u32* cnt, u32* gsum, u32* total, u64* freed,
+                      hipStream_t s) {
+    if (!p.G) return;
+    hipLaunchKernelGGL(k_exp_count, dim3(p.G), dim3(kChgWaves * 64), 0, s, A, S, p, cutoff, cnt, gsum, freed);
+    hipLaunchKernelGGL(k_chg_scan, dim3(1), dim3(kChgWaves * 64), 0, s, gsum, p.G, total);
+}
+void launch_exp_apply(u32* A, const u32* S, const ChgPlan& p, u32 cutoff, const u32* cnt, const u32* gsum, u64 cap, u32* rows,
+                      u32* node, u32* aff_life, const u32* load, u32 m, u64* used, u64* freed, hipStream_t s) {
+    if (!p.G || !cap) return;
+    const bool hist = used && m <= kExpLdsNodes;
+    hipLaunchKernelGGL(k_exp_apply, dim3(p.G), dim3(kChgWaves * 64), hist ? (size_t)m * sizeof(u64) : 0, s, A, S, p, cutoff, cnt,
+                       gsum, cap, rows, node, aff_life, load, m, used, hist ? 1u : 0u, freed);
+}
+void launch_touch(u32* S, u64 n_obj, const u32* idx, u64 n, u32 epoch, DevStats* st, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_touch, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, S, n_obj, idx, n, epoch, st);
+}
+void launch_seen_merge(u32* S, const u32* stamps, u32 epoch, u64 rows, hipStream_t s) {
+    if (!rows) return;
+    const u32 vec = stamps && (reinterpret_cast<uintptr_t>(stamps) & 15u) == 0 ? 1u : 0u;
+    hipLaunchKernelGGL(k_seen_merge, dim3(grid_for((rows + 3) / 4, 256, 8192)), dim3(256), 0, s, S, stamps, epoch, rows, vec);
+}
+
 }  // namespace riogp

@@ -519,6 +519,11 @@ struct rio_gp {
     u32* chg_Bmem = nullptr;  // B's memory, allocated; chg_B is set once it has been filled
     u32 *h_chg = nullptr, *d_chg = nullptr;
     DevBuf chg_stage;
+    // idle expiry (rio_gp_touch_*, rio_gp_expire), allocated on first use: the last-seen column S (cap_rows u32, 0 to begin with)
+    // and the freed-load word; the passes use the feed's counts, sums and mapped words (no two calls overlap on the stream)
+    u32* exp_S = nullptr;
+    u32* exp_Smem = nullptr;  // S's memory, allocated; exp_S is set once it has been filled
+    u64* exp_freed = nullptr;
     std::vector<void*> allocs;
 };
 
@@ -1913,9 +1918,8 @@ int rio_gp_rebalance_dev(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_re
 // ---- change feed -----------------------------------------------------------------------------
 
 // The feed's state, on first use: B (RIO_GP_NONE everywhere: the first listing is complete), 4 B per tile of counts, the
-// workgroup sums and one mapped pinned word.
-static int chg_scratch(rio_gp* h) {
-    if (h->chg_B) return RIO_GP_OK;
+// workgroup sums and one mapped pinned line (chg_counters: idle expiry counts with them too).
+static int chg_counters(rio_gp* h) {
     const u64 tiles = (h->cap_rows + kChgTile - 1) / kChgTile;
     int rc;
     // (each piece once: a call after a failed allocation or fill allocates only what is still missing)
@@ -1930,6 +1934,12 @@ static int chg_scratch(rio_gp* h) {
             return fail(h, RIO_GP_ENOMEM, "hipHostMalloc(change feed word) failed");
         }
     }
+    return RIO_GP_OK;
+}
+static int chg_scratch(rio_gp* h) {
+    if (h->chg_B) return RIO_GP_OK;
+    int rc;
+    if ((rc = chg_counters(h))) return rc;
     if (!h->chg_Bmem && (rc = dalloc(h, &h->chg_Bmem, h->cap_rows))) return rc;
     launch_fill_u32(h->chg_Bmem, h->cap_rows, kNone, h->stream);
     HIPCHK(h, hipGetLastError());
@@ -2014,6 +2024,182 @@ int rio_gp_changes_reset(rio_gp_t* h) {
     launch_fill_u32(h->chg_B, h->cap_rows, kNone, h->stream);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RIO_GP_OK;
+}
+
+// ---- idle expiry ------------------------------------------------------------------------------
+
+// The last-seen column on first use (0 everywhere: never seen), the freed-load word and the feed's counters.
+static int exp_scratch(rio_gp* h) {
+    if (h->exp_S) return RIO_GP_OK;
+    int rc;
+    if ((rc = chg_counters(h))) return rc;
+    if (!h->exp_freed && (rc = dalloc(h, &h->exp_freed, 1))) return rc;
+    if (!h->exp_Smem && (rc = dalloc(h, &h->exp_Smem, h->cap_rows))) return rc;
+    launch_fill_u32(h->exp_Smem, h->cap_rows, 0u, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->exp_S = h->exp_Smem;  // (last: it is what says the state is complete)
+    return RIO_GP_OK;
+}
+// what every call of the family does first (one rule: no last-seen column on a handle of the row-sharded solve)
+static int exp_begin(rio_gp* h, const char* who) {
+    if (row_sharded(h)) return fail(h, RIO_GP_EINVAL, std::string(who) + ": not implemented on a handle of the row-sharded solve");
+    HIPCHK(h, hipSetDevice(h->device));
+    return exp_scratch(h);
+}
+
+// Touch calls write S and nothing else: no inputs_changed, `used` and the solve in flight stay as they are.
+int rio_gp_touch_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, uint32_t epoch) {
+    if (!h || (n && !d_idx)) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = exp_begin(h, "rio_gp_touch_batch"))) return rc;
+    if (!n) return RIO_GP_OK;
+    if ((rc = zero_stats(h))) return rc;
+    launch_touch(h->exp_S, h->n, d_idx, n, epoch, h->dstats, h->stream);
+    if ((rc = read_stats(h))) return rc;
+    if (h->h_stats[0].err) return fail(h, RIO_GP_EINVAL, "rio_gp_touch_batch: invalid entries were skipped");
+    return RIO_GP_OK;
+}
+
+int rio_gp_touch_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, uint32_t epoch) {
+    if (!h || (n && !idx)) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (row_sharded(h)) return fail(h, RIO_GP_EINVAL, "rio_gp_touch_batch: not implemented on a handle of the row-sharded solve");
+    for (uint64_t k = 0; k < n; ++k)
+        if (idx[k] >= h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_touch_batch: object index out of range");
+    int rc;
+    if ((rc = exp_begin(h, "rio_gp_touch_batch"))) return rc;
+    if (!n) return RIO_GP_OK;
+    if ((rc = ensure(h, h->stage[0], n * sizeof(u32)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, idx, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    launch_touch(h->exp_S, h->n, (const u32*)h->stage[0].p, n, epoch, h->dstats, h->stream);  // (validated: nothing is counted)
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's array is read until here
+    return RIO_GP_OK;
+}
+
+int rio_gp_touch_all(rio_gp_t* h, uint32_t epoch) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = exp_begin(h, "rio_gp_touch_all"))) return rc;
+    launch_seen_merge(h->exp_S, nullptr, epoch, h->n, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return RIO_GP_OK;
+}
+
+int rio_gp_touch_merge_dev(rio_gp_t* h, uint64_t rows, const uint32_t* d_stamps) {
+    if (!h || (rows && !d_stamps)) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (rows > h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_touch_merge: rows exceeds the object table");
+    int rc;
+    if ((rc = exp_begin(h, "rio_gp_touch_merge"))) return rc;
+    launch_seen_merge(h->exp_S, d_stamps, 0u, rows, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return RIO_GP_OK;
+}
+
+int rio_gp_touch_merge(rio_gp_t* h, uint64_t rows, const uint32_t* stamps) {
+    if (!h || (rows && !stamps)) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (rows > h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_touch_merge: rows exceeds the object table");
+    int rc;
+    if ((rc = exp_begin(h, "rio_gp_touch_merge"))) return rc;
+    if (!rows) return RIO_GP_OK;
+    if ((rc = ensure(h, h->stage[0], rows * sizeof(u32)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, stamps, rows * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    launch_seen_merge(h->exp_S, (const u32*)h->stage[0].p, 0u, rows, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's array is read until here
+    return RIO_GP_OK;
+}
+
+int rio_gp_get_seen(rio_gp_t* h, uint64_t n, uint32_t* out) {
+    if (!h || !out) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (n != h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_get_seen: n differs from the object table");
+    int rc;
+    if ((rc = exp_begin(h, "rio_gp_get_seen"))) return rc;
+    if (n) HIPCHK(h, hipMemcpyAsync(out, h->exp_S, n * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RIO_GP_OK;
+}
+
+// checks shared by both forms: nothing is changed before they pass
+static int exp_args(rio_gp* h, const void* r, const void* o, uint64_t cap, const uint64_t* n_idle) {
+    if (!n_idle) return fail(h, RIO_GP_EINVAL, "rio_gp_expire: n_idle is NULL");
+    if ((r != nullptr) != (o != nullptr))
+        return fail(h, RIO_GP_EINVAL, "rio_gp_expire: out_rows / out_node are given together or not at all");
+    if (!r && cap) return fail(h, RIO_GP_EINVAL, "rio_gp_expire: cap without a listing");
+    return RIO_GP_OK;
+}
+// The count pass over the committed column and S; the total lands in the mapped word.  It changes nothing of the table.
+static int exp_count(rio_gp* h, const ChgPlan& p, u32 cutoff) {
+    *h->h_chg = 0;
+    launch_exp_count(h->assign[h->cur], h->exp_S, p, cutoff, h->chg_cnt, h->chg_gsum, h->d_chg, h->exp_freed, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return RIO_GP_OK;
+}
+// The apply pass for the first `cap` idle rows, and the freed load into the mapped line's second u64.  `used` follows the writes
+// when it is valid, as the remove kernels keep it.  The caller has not waited yet.
+static int exp_apply(rio_gp* h, const ChgPlan& p, u32 cutoff, u64 cap, u32* d_rows, u32* d_node) {
+    u64* const used = h->used.live();
+    launch_exp_apply(h->assign[h->cur], h->exp_S, p, cutoff, h->chg_cnt, h->chg_gsum, cap, d_rows, d_node, aff_life(h), h->load,
+                     h->m, used, h->exp_freed, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(reinterpret_cast<u64*>(h->h_chg) + 1, h->exp_freed, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    return RIO_GP_OK;
+}
+
+int rio_gp_expire(rio_gp_t* h, uint32_t cutoff, uint32_t* out_rows, uint32_t* out_node, uint64_t cap, uint64_t* n_idle,
+                  uint64_t* load_freed) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = exp_args(h, out_rows, out_node, cap, n_idle))) return rc;
+    if ((rc = exp_begin(h, "rio_gp_expire"))) return rc;
+    const ChgPlan p = chg_plan(h->n);
+    if ((rc = exp_count(h, p, cutoff))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 total = p.G ? *h->h_chg : 0;
+    *n_idle = total;
+    if (load_freed) *load_freed = 0;
+    const u64 L = std::min<u64>(total, cap);
+    if (!out_rows || L == 0) return RIO_GP_OK;
+    if ((rc = ensure(h, h->chg_stage, 2 * L * sizeof(u32)))) return rc;
+    u32* d = (u32*)h->chg_stage.p;
+    inputs_changed(h);  // from here on it is a rio_gp_remove_batch of the listed rows
+    if ((rc = exp_apply(h, p, cutoff, L, d, d + L))) return rc;
+    HIPCHK(h, hipMemcpyAsync(out_rows, d, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out_node, d + L, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (load_freed) *load_freed = reinterpret_cast<const u64*>(h->h_chg)[1];
+    return RIO_GP_OK;
+}
+
+int rio_gp_expire_dev(rio_gp_t* h, uint32_t cutoff, uint32_t* d_rows, uint32_t* d_node, uint64_t cap, uint64_t* n_idle,
+                      uint64_t* load_freed) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = exp_args(h, d_rows, d_node, cap, n_idle))) return rc;
+    if ((rc = exp_begin(h, "rio_gp_expire"))) return rc;
+    const ChgPlan p = chg_plan(h->n);
+    if ((rc = exp_count(h, p, cutoff))) return rc;
+    // the apply pass reads the prefix the count pass left on the device and drops ranks >= cap itself: one wait for the call
+    const bool apply = d_rows && cap && p.G;
+    reinterpret_cast<u64*>(h->h_chg)[1] = 0;
+    if (apply && (rc = exp_apply(h, p, cutoff, cap, d_rows, d_node))) {
+        inputs_changed(h);
+        return rc;
+    }
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    const u64 total = p.G ? *h->h_chg : 0;
+    if (apply && (e != hipSuccess || total)) inputs_changed(h);  // something was un-placed (or nobody can tell)
+    HIPCHK(h, e);
+    *n_idle = total;
+    if (load_freed) *load_freed = apply ? reinterpret_cast<const u64*>(h->h_chg)[1] : 0;
     return RIO_GP_OK;
 }
 

@@ -184,6 +184,7 @@ def _load(lab):
             getattr(L, nm).argtypes = [_vp, C.c_uint64, _vp, _vp]
         for nm in ("rio_gp_remove_batch", "rio_gp_remove_batch_dev"):
             getattr(L, nm).argtypes = [_vp, C.c_uint64, _vp]
+        L.rio_gp_count_placed.argtypes = [_vp, C.POINTER(C.c_uint64)]
         L.rio_gp_clean_server.argtypes = [_vp, C.c_uint32, C.POINTER(C.c_uint64)]
         L.rio_gp_clean_servers.argtypes = [_vp, _vp, C.POINTER(C.c_uint64)]
         L.rio_gp_place_pending.argtypes = [_vp, C.c_uint64, _vp, _vp, _vp, _vp]
@@ -208,6 +209,13 @@ def _load(lab):
         for nm in ("rio_gp_changes", "rio_gp_changes_dev"):
             getattr(L, nm).argtypes = [_vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.rio_gp_changes_reset.argtypes = [_vp]
+        for nm in ("rio_gp_touch_batch", "rio_gp_touch_batch_dev"):
+            getattr(L, nm).argtypes = [_vp, C.c_uint64, _vp, C.c_uint32]
+        L.rio_gp_touch_all.argtypes = [_vp, C.c_uint32]
+        for nm in ("rio_gp_touch_merge", "rio_gp_touch_merge_dev", "rio_gp_get_seen"):
+            getattr(L, nm).argtypes = [_vp, C.c_uint64, _vp]
+        for nm in ("rio_gp_expire", "rio_gp_expire_dev"):
+            getattr(L, nm).argtypes = [_vp, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.rio_gp_remap_nodes.argtypes = [_vp, C.c_uint32, _vp, C.POINTER(C.c_uint64)]
         if lab:
             L.rio_gp_debug_set_scan_nt.argtypes = [C.c_int]
@@ -366,6 +374,12 @@ class GpuPlacement:
     def remove_batch(self, idx):
         idx = _u32(idx)
         self._chk(self._L.rio_gp_remove_batch(self._h, len(idx), _ptr(idx)))
+
+    def count_placed(self):
+        """rio_gp_count_placed: rows r < n with a node."""
+        out = C.c_uint64(0)
+        self._chk(self._L.rio_gp_count_placed(self._h, C.byref(out)))
+        return int(out.value)
 
     def clean_server(self, node):
         ev = C.c_uint64(0)
@@ -550,6 +564,70 @@ class GpuPlacement:
     def changes_reset(self):
         """rio_gp_changes_reset: the checkpoint forgets everything; the next listing holds every placed row."""
         self._chk(self._L.rio_gp_changes_reset(self._h))
+
+    # -- idle expiry --
+    def touch(self, idx, epoch):
+        """rio_gp_touch_batch: S[idx[k]] = max(S[idx[k]], epoch)."""
+        idx = _u32(idx)
+        self._chk(self._L.rio_gp_touch_batch(self._h, len(idx), _ptr(idx), int(epoch)))
+
+    def touch_dev(self, d_idx, n, epoch):
+        """rio_gp_touch_batch_dev: the same from a device array of n row indices (an int, e.g. a torch tensor's data_ptr())."""
+        self._chk(self._L.rio_gp_touch_batch_dev(self._h, int(n), _vp(d_idx) if d_idx else None, int(epoch)))
+
+    def touch_raw(self, idx, epoch):
+        """One rio_gp_touch_batch call as given: rc; no exception."""
+        idx = _u32(idx)
+        return self._L.rio_gp_touch_batch(self._h, len(idx), _ptr(idx), int(epoch))
+
+    def touch_all(self, epoch):
+        """rio_gp_touch_all: every row r < n is seen at `epoch` at the least."""
+        self._chk(self._L.rio_gp_touch_all(self._h, int(epoch)))
+
+    def touch_merge(self, stamps):
+        """rio_gp_touch_merge: S[r] = max(S[r], stamps[r]) for r < len(stamps) <= n."""
+        stamps = _u32(stamps)
+        self._chk(self._L.rio_gp_touch_merge(self._h, len(stamps), _ptr(stamps)))
+
+    def touch_merge_dev(self, d_stamps, rows):
+        """rio_gp_touch_merge_dev: the same from a device array of `rows` stamps."""
+        self._chk(self._L.rio_gp_touch_merge_dev(self._h, int(rows), _vp(d_stamps) if d_stamps else None))
+
+    def get_seen(self):
+        """rio_gp_get_seen: the last-seen column S[0 .. n-1] (uint32; 0 = never seen)."""
+        out = np.empty(self.num_objects, np.uint32)
+        self._chk(self._L.rio_gp_get_seen(self._h, len(out), _ptr(out)))
+        return out
+
+    def expire(self, cutoff, cap=None, count_only=False):
+        """rio_gp_expire: (rows, nodes, n_idle, load_freed) — the first min(n_idle, cap) placed rows last seen before `cutoff`, in
+        row order, with the node each was on (uint32 arrays); exactly those rows are un-placed.  n_idle counts every idle row.
+        cap None: all of them; count_only (or cap 0): nothing is listed and nothing changes."""
+        n, fr = C.c_uint64(0), C.c_uint64(0)
+        cap = self.num_objects if cap is None else min(int(cap), self.num_objects)   # a listing never holds more than n rows
+        if count_only or cap == 0:
+            self._chk(self._L.rio_gp_expire(self._h, int(cutoff), None, None, 0, C.byref(n), C.byref(fr)))
+            e = np.empty(0, np.uint32)
+            return e, e, int(n.value), 0
+        buf = np.empty((2, cap), np.uint32)
+        self._chk(self._L.rio_gp_expire(self._h, int(cutoff), _ptr(buf[0]), _ptr(buf[1]), cap, C.byref(n), C.byref(fr)))
+        k = min(int(n.value), cap)
+        return buf[0, :k].copy(), buf[1, :k].copy(), int(n.value), int(fr.value)
+
+    def expire_dev(self, cutoff, d_rows=None, d_node=None, cap=0):
+        """rio_gp_expire_dev: the first min(n_idle, cap) idle rows into device arrays (ints; both None with cap 0: count only).
+        Returns (n_idle, load_freed)."""
+        n, fr = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.rio_gp_expire_dev(self._h, int(cutoff), _vp(d_rows) if d_rows else None,
+                                            _vp(d_node) if d_node else None, int(cap), C.byref(n), C.byref(fr)))
+        return int(n.value), int(fr.value)
+
+    def expire_raw(self, cutoff, out_rows=None, out_node=None, cap=0, want_n_idle=True):
+        """One rio_gp_expire call as given (tests of the argument checks): (rc, n_idle); no exception."""
+        n = C.c_uint64(0)
+        rc = self._L.rio_gp_expire(self._h, int(cutoff), _ptr(out_rows), _ptr(out_node), int(cap),
+                                   C.byref(n) if want_n_idle else None, None)
+        return rc, int(n.value)
 
     # -- policy --
     def place_pending(self, idx, requester):
@@ -768,6 +846,7 @@ def _oplib():
                                        C.POINTER(C.POINTER(C.c_size_t)), C.POINTER(C.POINTER(C.c_char_p)),
                                        C.POINTER(C.POINTER(C.c_char_p))]
         bind_op_changes(L)
+        bind_op_expire(L)
         L.rio_op_dense.argtypes = [_vp]
         L.rio_op_dense.restype = _vp
         L.rio_op_invalidate_cache.argtypes = [_vp]
@@ -797,6 +876,30 @@ def op_changes(L, h):
     out = [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(),
             None if oa[k] is None else oa[k].decode(), None if na[k] is None else na[k].decode()) for k in range(n.value)]
     return rc, bool(full.value), out
+
+
+def bind_op_expire(L):
+    """argtypes of rio_op_set_clock / rio_op_expire on a library that has them (the product, or a stub-linked test build)."""
+    pp, psz = C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_size_t))
+    L.rio_op_set_clock.argtypes = [_vp, C.c_uint32]
+    L.rio_op_expire.argtypes = [_vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), pp, psz, pp, psz, pp]
+
+
+def op_expire(L, h, cutoff, max_objects=None):
+    """One rio_op_expire call on handle h of library L: (rc, [(struct_name, object_id, address)], n_idle) — the keys un-placed,
+    in row order, with the address each was on (None: a node id without an address).  max_objects None: no limit; 0: count."""
+    n, idle = C.c_uint64(0), C.c_uint64(0)
+    ty, oid, ad = (C.POINTER(C.c_char_p)() for _ in range(3))
+    tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+    cap = 0xFFFFFFFFFFFFFFFF if max_objects is None else int(max_objects)
+    rc = L.rio_op_expire(h, int(cutoff), cap, C.byref(n), C.byref(idle), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il),
+                         C.byref(ad))
+    if rc != OK:
+        return rc, [], 0
+    tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))   # (c_char_p would stop at a NUL)
+    out = [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(),
+            None if ad[k] is None else ad[k].decode()) for k in range(n.value)]
+    return rc, out, int(idle.value)
 
 
 def _cstrs(items):
@@ -1018,6 +1121,17 @@ class GpuObjectPlacement:
     def changes_reset(self):
         """rio_op_changes_reset: the next changes() is a full listing."""
         self._chk(_oplib().rio_op_changes_reset(self._h))
+
+    def set_clock(self, now):
+        """rio_op_set_clock: the epoch every later call that answers or sets an address stamps its key with (0: stamping off)."""
+        self._chk(_oplib().rio_op_set_clock(self._h, int(now)))
+
+    def expire(self, cutoff, max_objects=None):
+        """rio_op_expire: ([(struct_name, object_id, address)], n_idle) — the placed keys last stamped before `cutoff`, at most
+        max_objects of them (None: no limit; 0: count only), un-placed and listed with the address each was on."""
+        rc, out, idle = op_expire(_oplib(), self._h, cutoff, max_objects)
+        self._chk(rc)
+        return out, idle
 
     def objects_on_server(self, address):
         """rio_op_objects_on_server: every (struct_name, object_id) placed on `address` (the reverse index; [] for an address

@@ -97,6 +97,10 @@ extern "C" {
     fn rio_op_remove_n(p: *mut c_void, ty: *const c_char, ty_len: usize, id: *const c_char, id_len: usize) -> c_int;
     fn rio_op_set_member(p: *mut c_void, addr: *const c_char, active: c_int, capacity: u64) -> c_int;
     fn rio_op_remove_members(p: *mut c_void, n: u64, addrs: *const *const c_char, removed: *mut u64, evicted: *mut u64) -> c_int;
+    fn rio_op_set_clock(p: *mut c_void, now: u32) -> c_int;
+    fn rio_op_expire(p: *mut c_void, cutoff: u32, max_objects_out: u64, n_out: *mut u64, n_idle: *mut u64,
+                     tys: *mut *const *const c_char, ty_lens: *mut *const usize, ids: *mut *const *const c_char,
+                     id_lens: *mut *const usize, addrs: *mut *const *const c_char) -> c_int;
     fn rio_op_tick(p: *mut c_void, stats: *mut RioGpStats) -> c_int;
     fn rio_op_snapshot(p: *mut c_void, n_out: *mut u64, tys: *mut *const *const c_char, ids: *mut *const *const c_char,
                        addrs: *mut *const *const c_char) -> c_int;
@@ -282,6 +286,40 @@ impl GpuObjectPlacement {
             let (mut removed, mut evicted) = (0u64, 0u64);
             check(unsafe { rio_op_remove_members(me.inner.0, ap.len() as u64, ap.as_ptr(), &mut removed, &mut evicted) }, &me)?;
             Ok((removed, evicted))
+        })
+        .await
+    }
+
+    /// The epoch every later call that answers or sets an address stamps its key with (`ObjectPlacementItem`'s "TODO:
+    /// last_seen", rio-rs/src/object_placement/mod.rs:24).  0, the value at creation, switches stamping off.  The host owns
+    /// the clock: e.g. seconds since start, advanced by the task that also sweeps.
+    pub fn set_clock(&self, now: u32) -> Result<(), ObjectPlacementError> {
+        check(unsafe { rio_op_set_clock(self.inner.0, now) }, self)
+    }
+
+    /// Idle sweep ("TODO: ttl", mod.rs:23): un-places every placed object last stamped before `cutoff`, at most `max_objects`
+    /// of them (`None`: no limit), and returns them with the address each was on, plus the number of idle objects in all.
+    /// What to do with a listed `(object, address)` is the host's to decide — typically it asks that server to shut the
+    /// object down (`ServiceObject::shutdown`, service_object.rs:100).
+    pub async fn expire(&self, cutoff: u32, max_objects: Option<u64>)
+        -> Result<(Vec<(ObjectId, Option<String>)>, u64), ObjectPlacementError> {
+        let me = self.clone();
+        blocking(move || {
+            let (mut n, mut idle) = (0u64, 0u64);
+            let (mut ty, mut id, mut ad) = (std::ptr::null(), std::ptr::null(), std::ptr::null());
+            let (mut tl, mut il) = (std::ptr::null(), std::ptr::null());
+            check(unsafe { rio_op_expire(me.inner.0, cutoff, max_objects.unwrap_or(u64::MAX), &mut n, &mut idle, &mut ty, &mut tl,
+                                         &mut id, &mut il, &mut ad) }, &me)?;
+            // the arrays are this thread's until its next call: read them here, before anything else can run
+            let key = |p: *const *const c_char, l: *const usize, k: usize| unsafe {
+                String::from_utf8_lossy(std::slice::from_raw_parts(*p.add(k) as *const u8, *l.add(k))).into_owned()
+            };
+            let out = (0..n as usize).map(|k| {
+                let a = unsafe { *ad.add(k) };
+                (ObjectId(key(ty, tl, k), key(id, il, k)),
+                 if a.is_null() { None } else { Some(unsafe { CStr::from_ptr(a) }.to_string_lossy().into_owned()) })
+            }).collect();
+            Ok((out, idle))
         })
         .await
     }
