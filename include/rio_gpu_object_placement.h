@@ -187,7 +187,9 @@ int rio_op_changes_reset(rio_op_t* p);
  *   - Once the clock is non-zero, every call that ANSWERS OR SETS AN ADDRESS for a key stamps that key with the clock: a lookup
  *     or try_lookup that finds a placement (host-shadow hits included), an update with an address, a get_or_create_placement or
  *     try_get_or_create_placement that returns an address, and the batch forms per entry.  remove, set_object_load, a lookup
- *     that finds nothing and a call that fails do not stamp.  Stamps only rise.
+ *     that finds nothing and a call that fails do not stamp.  Stamps only rise.  An RIO_GP_ERANGE answer is a call that fails
+ *     (no stamp, `found` set or not), and every entry of a batch is judged by itself: an entry that sets or answers an address
+ *     stamps its key whatever a later entry of the same batch does to that key.
  *   - rio_op_expire un-places every placed key last stamped before `cutoff` (never stamped counts as 0), at most
  *     max_objects_out of them (~0: no limit; 0: count only, nothing changes), in the dense layer's row order, and lists them
  *     with the address each was on (NULL for a node id without an address, as in rio_op_snapshot).  *n_out = keys listed;

@@ -1,5 +1,5 @@
 """A CPU stand-in for the rio_gp binding, FOR TESTS ONLY: the surface tests/test_gpu_fuzz.py's scenarios use, implemented over
-the CPU oracle (oracle/pyoracle.py), tests/rebalance_ref.py, tests/spec_changes.py and tests/spec_remap.py.  It lets the fuzz driver itself be tested
+the CPU oracle (oracle/pyoracle.py), tests/rebalance_ref.py, tests/spec_changes.py and tests/spec_remap.py; idle expiry is restated here in plain numpy.  It lets the fuzz driver itself be tested
 without a GPU (tests/test_fuzz_driver.py): its bookkeeping (n, the feed's checkpoint, the mirror, the uncommitted solve) and its
 sensitivity — `fault=` makes exactly one behaviour of the handle wrong, and the scenarios must notice.
 
@@ -39,6 +39,19 @@ FAULTS = (
     "remap_checkpoint_none_not_gone",   # a checkpoint naming a removed node becomes NONE, not RIO_GP_NODE_GONE
     "remap_stale_node_table",      # a node removal leaves cap and alive at their old ids
     "remap_affinity_not_renumbered",    # the committed ticks read the affinity of before the removal (the getter does not)
+    "expire_cutoff_inclusive",     # a row stamped exactly at the cutoff is idle
+    "expire_unplaces_past_cap",    # a sweep un-places every idle row, not only the listed ones
+    "expire_lists_hidden_rows",    # a sweep finds rows >= n idle
+    "expire_freed_counts_unlisted",     # load_freed sums every idle row's load
+    "expire_stale_used",           # a sweep leaves `used` of the old column
+    "expire_keeps_solve",          # a sweep that un-placed rows keeps an uncommitted solve committable
+    "expire_zero_hit_drops_solve",      # a sweep that un-placed nothing drops an uncommitted solve
+    "expire_count_only_writes",    # a count-only sweep un-places the idle rows
+    "touch_overwrites",            # a touch stores the epoch instead of the maximum
+    "touch_all_past_n",            # touch_all stamps the rows >= n too
+    "touch_dev_stops_at_invalid",  # the _dev batch stops at its first invalid entry instead of skipping it
+    "touch_drops_solve",           # a touch drops an uncommitted solve
+    "remap_moves_seen",            # a node removal clears the stamps of the rows < n
 )
 
 
@@ -125,6 +138,7 @@ class GpuPlacement:
         self._alive = np.zeros(0, np.uint8)
         self._alive_seen = self._alive.copy()   # the liveness the "device" has consumed (a set_alive* only pushes)
         self._B = np.full(self._cap_rows, NONE, np.uint32)
+        self._S = np.zeros(self._cap_rows, np.uint32)
         self._solved = None
         self._stale_used = None
         self._stale_aff = None
@@ -347,6 +361,8 @@ class GpuPlacement:
             self._solved = solved
         if f == "remap_affinity_not_renumbered":
             self._stale_aff = old_aff if self._stale_aff is None else self._stale_aff
+        if f == "remap_moves_seen":
+            self._S[:n] = 0
         return OK, out["evicted"]
 
     def remap_nodes(self, map):
@@ -467,6 +483,108 @@ class GpuPlacement:
 
     def changes_reset(self):
         self._B[:] = NONE
+
+    # ---- idle expiry
+    def _touch(self, idx, epoch):
+        if self._fault == "touch_overwrites":
+            self._S[idx] = np.uint32(epoch)
+        else:
+            np.maximum.at(self._S, np.asarray(idx, np.int64), np.uint32(epoch))
+        if self._fault == "touch_drops_solve":
+            self._changed()
+
+    def touch_raw(self, idx, epoch):
+        idx = np.asarray(idx, np.uint32)
+        if len(idx) and int(idx.max()) >= self._n:
+            return EINVAL
+        self._touch(idx, epoch)
+        return OK
+
+    def touch(self, idx, epoch):
+        if self.touch_raw(idx, epoch) != OK:
+            raise _einval("rio_gp_touch_batch: object index out of range")
+
+    def touch_dev(self, d_idx, n, epoch):
+        idx = _at(d_idx, n).copy()
+        bad = idx >= self._n
+        if self._fault == "touch_dev_stops_at_invalid" and bad.any():
+            self._touch(idx[:int(np.argmax(bad))], epoch)
+        else:
+            self._touch(idx[~bad], epoch)
+        if bad.any():
+            raise _einval("rio_gp_touch_batch: invalid entries were skipped")
+
+    def touch_all(self, epoch):
+        rows = self._cap_rows if self._fault == "touch_all_past_n" else self._n
+        self._touch(np.arange(rows), epoch)
+
+    def touch_merge(self, stamps):
+        stamps = np.asarray(stamps, np.uint32)
+        rows = len(stamps)
+        if rows > self._n:
+            raise _einval("rio_gp_touch_merge: rows exceeds the object table")
+        self._S[:rows] = np.maximum(self._S[:rows], stamps)
+        if self._fault == "touch_drops_solve":
+            self._changed()
+
+    def touch_merge_dev(self, d_stamps, rows):
+        if rows > self._n:
+            raise _einval("rio_gp_touch_merge: rows exceeds the object table")
+        self.touch_merge(_at(d_stamps, rows).copy())
+
+    def get_seen(self):
+        return self._S[:self._n].copy()
+
+    def _expire(self, cutoff, cap):
+        """cap None: count only.  -> rows, nodes, n_idle, load_freed"""
+        f = self._fault
+        n = self._cap_rows if f == "expire_lists_hidden_rows" else self._n
+        col = self._col
+        lim = int(cutoff) + (1 if f == "expire_cutoff_inclusive" else 0)
+        idle = np.flatnonzero((col[:n] != NONE) & (self._S[:n].astype(np.int64) < lim)).astype(np.uint32)
+        before, solved = self.get_nodes()[2], self._solved
+        e = np.empty(0, np.uint32)
+        if cap is None:
+            listed, gone = e, (idle if f == "expire_count_only_writes" else e)
+        else:
+            listed = idle[:int(cap)]
+            gone = idle if f == "expire_unplaces_past_cap" else listed
+        nodes = col[listed].copy()
+        freed = int(self._load[idle if f == "expire_freed_counts_unlisted" and cap is not None else listed].astype(np.uint64).sum())
+        col[gone] = NONE
+        if len(listed):        # as rio_gp_remove_batch of the listed rows
+            self._changed()
+            if f == "expire_keeps_solve":
+                self._solved = solved
+            if f == "expire_stale_used":
+                self._stale_used = before
+        elif f == "expire_zero_hit_drops_solve":
+            self._changed()
+        return listed, nodes, len(idle), freed
+
+    def expire(self, cutoff, cap=None, count_only=False):
+        cap = self._n if cap is None else min(int(cap), self._n)
+        if count_only or cap == 0:
+            return self._expire(cutoff, None)[:3] + (0,)
+        return self._expire(cutoff, cap)
+
+    def expire_dev(self, cutoff, d_rows=None, d_node=None, cap=0):
+        if bool(d_rows) != bool(d_node) or (not d_rows and cap):
+            raise _einval("rio_gp_expire: the output rule")
+        rows, nodes, n_idle, freed = self._expire(cutoff, int(cap) if d_rows and cap else None)
+        if len(rows):
+            _at(d_rows, len(rows))[:] = rows
+            _at(d_node, len(rows))[:] = nodes
+        return n_idle, freed
+
+    def expire_raw(self, cutoff, out_rows=None, out_node=None, cap=0, want_n_idle=True):
+        if not want_n_idle or (out_rows is None) != (out_node is None) or (out_rows is None and cap):
+            return EINVAL, 0
+        rows, nodes, n_idle, _ = self._expire(cutoff, int(cap) if out_rows is not None and cap else None)
+        if len(rows):
+            out_rows[:len(rows)] = rows
+            out_node[:len(rows)] = nodes
+        return OK, n_idle
 
     # ---- lab calls: no-ops
     def set_compact(self, *a, **k):

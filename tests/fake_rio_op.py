@@ -24,6 +24,15 @@ FAULTS = (
     "kept_row_recycled",           # a row set aside by set_object_load is recycled
     "update_batch_first_wins",     # update_batch applies duplicates in the wrong order
     "reset_not_full",              # `full` is not raised after changes_reset
+    "expire_keeps_shadow_entry",   # a sweep leaves the shadow's answer for the keys it listed
+    "expire_drops_whole_shadow",   # a sweep that listed keys voids every shadow entry, not only theirs
+    "shadow_hit_does_not_stamp",   # a lookup or request the shadow answers does not stamp
+    "remove_stamps",               # a remove stamps the key
+    "clone_has_its_own_clock",     # set_clock through one clone does not reach the calls made through the other
+    "reclaim_resets_stamp",        # a reclaimed row's stamp goes back to 0
+    "expire_cutoff_inclusive",     # a key stamped exactly at the cutoff is idle
+    "expire_listing_not_in_row_order",   # the listing comes out in reverse
+    "stamps_not_uploaded_on_count_only",  # a count-only sweep does not hand the stamps to the dense layer
 )
 
 
@@ -94,6 +103,11 @@ class LifeDense(fake_rio_gp.GpuPlacement):
     def get_objects(self):
         return self._load[:self._n].copy(), self._aff[:self._n].copy()
 
+    def _expire(self, cutoff, cap):
+        out = super()._expire(cutoff, cap)
+        self._aff[out[0]] = AFF_INACTIVE      # an expired row is no longer an object
+        return out
+
     def count_placed(self):
         return int((self._col[:self._n] != NONE).sum())
 
@@ -106,6 +120,7 @@ class FakeObjectPlacement:
     def __init__(self, max_objects, max_nodes=32, spill_rounds=2, flags=0, fault=None, _s=None):
         if _s is not None:
             self.s = _s
+            self.own_now = 0
             return
         assert fault is None or fault in FAULTS, fault
         s = self.s = _State()
@@ -123,6 +138,8 @@ class FakeObjectPlacement:
         s.feed_on, s.feed_full, s.retired = False, True, {}
         s.trips = [0, 0]
         s.last_len = 0
+        s.now, s.stamps = 0, np.zeros(s.max_objects, np.uint32)     # the clock every clone stamps with; one stamp per row
+        self.own_now = 0
 
     def clone(self):
         return FakeObjectPlacement(0, _s=self.s)
@@ -202,6 +219,8 @@ class FakeObjectPlacement:
                 del s.rows[self._key(*s.row_key[r])]
                 s.row_key[r], s.row_live[r], s.row_keep[r] = None, 0, 0
                 s.shadow.pop(r, None)
+                if s.fault == "reclaim_resets_stamp":
+                    s.stamps[r] = 0
                 s.free.append(r)
                 gone.append(r)
         if gone:
@@ -215,6 +234,47 @@ class FakeObjectPlacement:
                 return EINVAL
             rc = body()
         return EINVAL if rc == "full" else rc
+
+    # ---- last-seen stamps
+    def set_clock(self, now):
+        self.own_now = int(now)
+        if self.s.fault != "clone_has_its_own_clock":
+            self.s.now = int(now)
+        return OK
+
+    def _stamp(self, row, by_shadow=False):
+        s = self.s
+        t = self.own_now if s.fault == "clone_has_its_own_clock" else s.now
+        if t and not (by_shadow and s.fault == "shadow_hit_does_not_stamp"):
+            s.stamps[row] = max(int(s.stamps[row]), t)
+
+    def expire(self, cutoff, max_objects=None, mid=None):
+        """-> (rc, [(struct_name, object_id, address or None)], n_idle)"""
+        s = self.s
+        self._sync()
+        n = len(s.row_key)
+        cap = n if max_objects is None else min(int(max_objects), n)
+        if s.stamps.any() and not (cap == 0 and s.fault == "stamps_not_uploaded_on_count_only"):
+            s.g.touch_merge(s.stamps[:n])
+        if s.fault == "expire_cutoff_inclusive":
+            cutoff = min(int(cutoff) + 1, 0xFFFFFFFF)
+        if cap == 0:
+            rows, nodes, n_idle, _ = s.g.expire(cutoff, count_only=True)
+        else:
+            rows, nodes, n_idle, _ = s.g.expire(cutoff, cap)
+        out = []
+        for r, nd in zip(rows, nodes):
+            if s.fault != "expire_keeps_shadow_entry":
+                self._put(r, NONE)
+            if s.row_live[r]:
+                out.append(s.row_key[r] + (s.addr[nd] if nd < len(s.addr) else None,))
+        if len(rows) and s.fault == "expire_drops_whole_shadow":
+            self._invalidate()
+        if s.fault == "expire_listing_not_in_row_order":
+            out.reverse()
+        if mid:
+            mid()
+        return OK, out, n_idle
 
     # ---- shadow
     def _put(self, row, node):
@@ -276,6 +336,8 @@ class FakeObjectPlacement:
         r, nd = res["v"]
         s.g.update_batch([r], [nd])
         self._put(r, nd)
+        if nd != NONE:
+            self._stamp(r)
         return OK
 
     def update_batch(self, keys, addrs):
@@ -312,6 +374,8 @@ class FakeObjectPlacement:
             s.g.update_batch(rows, nodes)
             for r, nd in zip(rows, nodes):
                 self._put(r, nd)
+                if nd != NONE:         # per entry, whatever a later entry does to the key
+                    self._stamp(r)
         return OK
 
     def remove(self, ty, oid):
@@ -322,6 +386,8 @@ class FakeObjectPlacement:
         self._trip()
         self.s.g.remove_batch([r])
         self._put(r, NONE)
+        if self.s.fault == "remove_stamps":
+            self._stamp(r)
         return OK
 
     def clean_server(self, addr):
@@ -343,6 +409,7 @@ class FakeObjectPlacement:
         if r == NONE:
             return OK, 0, ""
         nd = self._get(r)
+        hit = nd is not None
         if nd is None:
             self._sync()
             self._trip()
@@ -351,6 +418,8 @@ class FakeObjectPlacement:
         if nd == NONE:
             return OK, 0, ""
         rc, a = self._out(s.addr[nd], cap)
+        if rc == OK:                   # (an ERANGE answer is a call that failed: no stamp)
+            self._stamp(r, hit)
         return rc, 1, a
 
     def try_lookup(self, ty, oid, cap=512):
@@ -365,6 +434,8 @@ class FakeObjectPlacement:
         if nd == NONE:
             return OK, 0, ""
         rc, a = self._out(s.addr[nd], cap)
+        if rc == OK:
+            self._stamp(r, True)
         return rc, 1, a
 
     def _sticky(self, r, me):
@@ -385,6 +456,8 @@ class FakeObjectPlacement:
         if hit is None:
             return EAGAIN, "", 0
         rc, a = self._out(s.addr[hit[0]], cap)
+        if rc == OK:
+            self._stamp(r, True)
         return rc, a, hit[1]
 
     def _policy(self, rows, reqs):
@@ -425,11 +498,15 @@ class FakeObjectPlacement:
         hit = self._sticky(r, q)
         if hit is not None:
             rc, a = self._out(s.addr[hit[0]], cap)
+            if rc == OK:
+                self._stamp(r, True)
             return rc, a, hit[1]
         self._sync()
         self._trip()
         node, flag = self._policy([r], [q])
         rc, a = self._out("" if node[0] == NONE else s.addr[node[0]], cap)
+        if rc == OK and node[0] != NONE:
+            self._stamp(r)
         return rc, a, int(flag[0])
 
     def get_or_create_placement_batch(self, keys, mes):
@@ -457,6 +534,9 @@ class FakeObjectPlacement:
         if not rows:
             return OK, [], []
         node, flag = self._policy(rows, reqs)
+        for r, nd in zip(rows, node):
+            if nd != NONE:
+                self._stamp(r)
         return OK, [int(x) for x in node], [int(x) for x in flag]
 
     def lookup_batch(self, keys):
@@ -470,6 +550,8 @@ class FakeObjectPlacement:
             else:
                 nd = int(s.g.lookup_batch([r])[0])
                 self._put(r, nd)
+                if nd != NONE:
+                    self._stamp(r)
                 out.append(nd)
         return OK, out
 

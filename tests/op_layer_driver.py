@@ -16,6 +16,14 @@ Per call the expected dense state comes from pyoracle / tests/rebalance_ref.py /
 with translated arguments; the column and `used`, every answer, the index, the snapshot, the feed's mirror, the shadow's answers,
 what a clone sees and every refusal are compared bit for bit / string for string.  No tolerance anywhere.
 
+Idle deactivation (rio_op_set_clock / rio_op_expire) is part of the sequence.  The model holds the clock the clones share and one
+stamp per ROW (a row handed to a new key keeps its stamp) and restates the header's stamping rule in every operation that can stamp
+— RIO_GP_ERANGE answers do not, every entry of a batch is judged by itself.  A sweep's listing, n_out and n_idle come from
+tests/spec_expire.py over the dense state read before the call, translated through row -> key and the node table; afterwards the
+column, `used` and the affinity are those of rio_gp_remove_batch of the listed rows under the row lifecycle, rio_gp_get_seen on the
+rio_op_dense handle equals the model's stamps (every sweep uploads them, a count-only one too), a listed key is gone through both
+clones and a key that was not listed is still answered from the shadow.
+
 The provider under test is given as make(max_objects, max_nodes, spill_rounds, flags): RealProvider.make over rio_gp (the GPU
 test, tests/test_gpu_op_layer_fuzz.py) or tests/fake_rio_op.py (the driver's own test, tests/test_op_layer_driver.py).
 """
@@ -24,6 +32,7 @@ import ctypes as C
 import numpy as np
 
 import spec_changes
+import spec_expire
 
 NONE = 0xFFFFFFFF
 INF = 0xFFFFFFFFFFFFFFFF
@@ -44,6 +53,14 @@ FLOOR = (
     "ERANGE",
     "table-full EINVAL",
     "request from an inactive requester under the default flags",
+    "expire listed keys",
+    "expire count only with idle keys",
+    "expire capped below n_idle",
+    "sweep with the clock never set listed everything placed",
+    "a key stamped only by a shadow hit survived a sweep",
+    "an expired key's row was handed to a new key before the next feed read",
+    "a sweep judged a key by a stamp its row's previous key left",
+    "expire listed a key set aside by set_object_load",
 )
 
 SIZES = ("tiny", "tiny", "edge", "tiny", "4096", "bulk")      # by seed % 6
@@ -222,6 +239,24 @@ class RealProvider:
         return OK, bool(full.value), list(zip(self._strs(ty, tl, k), self._strs(oid, il, k), [dec(oa[q]) for q in range(k)],
                                              [dec(na[q]) for q in range(k)]))
 
+    def set_clock(self, now):
+        return int(self.L.rio_op_set_clock(self.p._h, int(now)))
+
+    def expire(self, cutoff, max_objects=None, mid=None):
+        """-> (rc, [(struct_name, object_id, address or None)], n_idle)"""
+        n, idle = C.c_uint64(0), C.c_uint64(0)
+        ty, oid, ad = (C.POINTER(C.c_char_p)() for _ in range(3))
+        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+        rc = self.L.rio_op_expire(self.p._h, int(cutoff), INF if max_objects is None else int(max_objects), C.byref(n), C.byref(idle),
+                                  C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il), C.byref(ad))
+        if rc:
+            return rc, [], 0
+        if mid:
+            mid()
+        k = int(n.value)
+        return OK, list(zip(self._strs(ty, tl, k), self._strs(oid, il, k),
+                            [None if ad[q] is None else ad[q].decode() for q in range(k)])), int(idle.value)
+
 
 class Key:
     """One interned key as the documentation describes its life: (ty, oid) as first handed over, its row once a listing showed
@@ -236,7 +271,7 @@ class Scenario:
     OPS = (("update", 8), ("update_none", 2), ("update_batch", 3), ("remove", 5), ("clean_server", 2), ("lookup", 6),
            ("lookup_batch", 2), ("request", 10), ("request_batch", 4), ("try_lookup", 4), ("try_request", 4), ("set_member", 5),
            ("set_object_load", 3), ("tick", 3), ("rebalance", 4), ("changes", 5), ("changes_reset", 1), ("invalidate_cache", 1),
-           ("objects_on_server", 2), ("snapshot", 2), ("len", 1))
+           ("objects_on_server", 2), ("snapshot", 2), ("len", 1), ("set_clock", 4), ("expire", 4))
 
     def __init__(self, make, oracle, seed, steps=None):
         self.oracle, self.seed = oracle, seed
@@ -270,6 +305,16 @@ class Scenario:
         self.log, self.count, self.cov = [], {}, {k: 0 for k in FLOOR}
         self.step = 0
         self.checked = 0
+        # idle expiry (no draw from rng here: the earlier draws stay what they were).  The clock the clones share, 0 = stamping
+        # off; one stamp per ROW (a row handed to a new key keeps its stamp): S, and S_dev = what it would be without the stamps
+        # of shadow hits; rows whose present key has stamped itself; keys stamped while their row was unknown
+        self.clock, self.clock_top, self.clock_ever = 0, 0, False
+        self.S = np.zeros(self.rows_max, np.uint32)
+        self.S_dev = np.zeros(self.rows_max, np.uint32)
+        self.own = set()
+        self.unknown_stamped = set()
+        self.expired_since_feed = set()
+        self.set_aside = set()
 
     # ---- small helpers ------------------------------------------------------------------------------------------------
     def fail(self, what, *more):
@@ -384,6 +429,8 @@ class Scenario:
                 if k.row is not None:
                     del self.row2key[k.row]
                     self.reset_rows.add(k.row)
+                    self.own.discard(k.row)
+                self.unknown_stamped.discard(ks)     # (its row keeps the stamp: the next sweep's upload is compared as a whole)
                 self.dropped_since_feed.setdefault(ks, k.row)
             if self.feed_state == "open":
                 self.hit("reclaim between two feed reads")
@@ -431,13 +478,65 @@ class Scenario:
                 if k.row is None:
                     old = self.row2key.get(r)
                     self.want(old is None, "a row changed key without a reclaim", r, old, ks)
-                    if r in self.ever_rows:
-                        self.handed.add(r)
-                    self.ever_rows.add(r)
-                    k.row = r
-                    self.row2key[r] = ks
+                    self.new_row(k, ks, r)
                 else:
                     self.want(k.row == r, "a key changed its row", ks, k.row, r)
+
+    def new_row(self, k, ks, r):
+        """A listing showed the row of key k.  The row keeps the stamp its previous key left (the header: "a row handed on keeps
+        its stamp until its new key's first call")."""
+        if r in self.ever_rows:
+            self.handed.add(r)
+            self.own.discard(r)
+            self.hit("an expired key's row was handed to a new key before the next feed read", r in self.expired_since_feed)
+        self.ever_rows.add(r)
+        k.row = r
+        self.row2key[r] = ks
+
+    # ---- the stamping rule (include/rio_gpu_object_placement.h, "idle deactivation") ------------------------------------------
+    def stamp(self, key, shadow=False):
+        """A call has answered or set an address for `key` (it returned RIO_GP_OK — an RIO_GP_ERANGE answer is a call that failed):
+        with the clock non-zero the key's row is stamped, a maximum.  Called once the call's rows are learnt."""
+        if not self.clock:
+            return
+        ks = self.kstr(key)
+        k = self.keys.get(ks)
+        if k is None:
+            self.fail("a call answered with an address for a key the model does not hold", key)
+        if k.row is None:        # (a batch that set the key's address and removed it again: see stamps_of_unknown_rows)
+            self.unknown_stamped.add(ks)
+            return
+        r = k.row
+        self.S[r] = max(int(self.S[r]), self.clock)
+        if not shadow:
+            self.S_dev[r] = max(int(self.S_dev[r]), self.clock)
+        self.own.add(r)
+
+    def stamps_of_unknown_rows(self, p):
+        """Keys a batch stamped whose rows no listing shows (an entry set an address, a later entry of the same batch removed the
+        key: every entry is judged by itself).  A count-only sweep uploads the host's stamps; the rows whose stamp rose to the
+        clock — at most one per such key, none of them a row with a known key — are theirs."""
+        if not self.unknown_stamped:
+            return
+        rc, got, _ = p.expire(0, 0)
+        self.want(rc == OK and got == [], "a count-only sweep failed or listed something", rc, got[:4])
+        seen = self.g.get_seen()
+        diff = [int(r) for r in np.flatnonzero(seen != self.S[:len(seen)])]
+        self.want(len(diff) <= len(self.unknown_stamped) and all(int(seen[r]) == self.clock and r not in self.row2key for r in diff),
+                  "stamps rose that no call of the model explains", diff[:8], [int(seen[r]) for r in diff[:8]], self.clock)
+        for r in diff:
+            self.S[r] = self.S_dev[r] = self.clock
+            self.own.add(r)
+        self.unknown_stamped = set()
+
+    def plain_lookup(self, p, st, key):
+        """rio_op_lookup outside check_lookup (what fills the shadow): a found placement is stamped, shadow hit or not."""
+        t0 = p.device_round_trips()
+        rc, found, out = p.lookup(key[0], key[1])
+        if rc == OK and found:
+            self.want(out == self.where(st, key), "lookup: wrong address", out, self.where(st, key), key)
+            self.stamp(key, shadow=p.device_round_trips() == t0)
+        return rc, found, out
 
     # ---- one step: before -> call -> expected -> after ------------------------------------------------------------------
     def virtual(self, st, klist):
@@ -533,7 +632,10 @@ class Scenario:
         self.ref_key(key)
         if self.ref_on:
             self.ref[0].update(key[0], key[1], a)
-        return self.settle(st, col, extra, "update")
+        after = self.settle(st, col, extra, "update")
+        if a is not None:          # an update with an address stamps; Option::None is a remove and does not
+            self.stamp(key)
+        return after
 
     def ref_key(self, key):
         """The restatement takes NUL-terminated keys: a key with a NUL byte in a writing call ends the cross-check."""
@@ -569,7 +671,12 @@ class Scenario:
         if self.ref_on:
             for k, a in zip(keys, addrs):
                 self.ref[0].update(k[0], k[1], a)
-        return self.settle(st, col, extra, "update_batch")
+        after = self.settle(st, col, extra, "update_batch")
+        for k, a in zip(keys, addrs):      # per entry: an entry with an address stamps its key, whatever a later entry does
+            if a is not None:
+                self.stamp(k)
+        self.stamps_of_unknown_rows(p)
+        return after
 
     def op_remove(self):
         p, other = self.h()
@@ -607,9 +714,12 @@ class Scenario:
     def check_lookup(self, st, p, other, key, fn, what):
         want = self.where(st, key)
         cap = 512 if self.rng.random() < 0.8 or want is None else int(self.rng.integers(0, len(want) + 1))
+        t0 = p.device_round_trips()
         rc, found, out = fn(key[0], key[1], cap)
         if what == "try_lookup" and rc == EAGAIN:
             return False
+        if rc == OK and found:     # a lookup or try_lookup that finds a placement stamps, whoever answered; ERANGE is a failure
+            self.stamp(key, shadow=p.device_round_trips() == t0)
         _, cnt = other.len()                                    # a call on the other clone, then the length this thread was left
         ln = p.last_address_len()
         self.want(cnt == int((st["col"] != NONE).sum()), "len differs from the placed rows", cnt)
@@ -635,7 +745,7 @@ class Scenario:
         st = self.begin()
         key = self.pick_key(0.9)
         if self.rng.random() < 0.5:
-            p.lookup(key[0], key[1])                            # (what fills the shadow)
+            self.plain_lookup(p, st, key)                       # (what fills the shadow)
         t0 = p.device_round_trips()
         if self.check_lookup(st, p, other, key, p.try_lookup, "try_lookup"):
             self.want(p.device_round_trips() == t0, "try_lookup went to the device")
@@ -658,6 +768,9 @@ class Scenario:
         want = [self.where(st, k) for k in keys]
         got = [None if v == NONE else self.addr[v] for v in ids]
         self.want(got == want, "lookup_batch: wrong node ids", [(k, g, w) for k, g, w in zip(keys, got, want) if g != w][:4])
+        for k, v in zip(keys, ids):        # per entry: the ones that found a placement
+            if v != NONE:
+                self.stamp(k)
         self.unchanged(st, "lookup_batch")
 
     def expect_requests(self, st, keys, mes):
@@ -689,7 +802,9 @@ class Scenario:
         st = self.begin()
         ok = self.intern(st, [(key, True, True, me, True)])
         cap = 512 if self.rng.random() < 0.85 else 8
+        t0 = p.device_round_trips()
         rc, out, flag = p.get_or_create_placement(key[0], key[1], me, cap)
+        by_shadow = p.device_round_trips() == t0
         if not ok:
             return self.refused_unchanged(st, rc, "request")
         self.learn_nodes(True)
@@ -707,7 +822,10 @@ class Scenario:
         self.note_flags([flag], [me])
         if self.ref_on:
             self.cross_request(key, me, want, flag)
-        return self.settle(st, col, extra, "request")
+        after = self.settle(st, col, extra, "request")
+        if rc == OK and want:      # a request that returns an address stamps; UNPLACED and an ERANGE answer do not
+            self.stamp(key, shadow=by_shadow)
+        return after
 
     def cross_request(self, key, me, want, flag):
         """The restated get_or_create_placement of the reference, while nothing it lacks is in play."""
@@ -741,17 +859,22 @@ class Scenario:
         self.want(flags == [int(x) for x in wflag], "request_batch: wrong flags", [(q, flags[q], int(wflag[q])) for q in range(n) if flags[q] != wflag[q]][:4])
         self.note_flags(flags, mes)
         self.ref_on = False            # (a batch cleans first and places then: not the reference's order request by request)
-        return self.settle(st, col, extra, "request_batch")
+        after = self.settle(st, col, extra, "request_batch")
+        for k, nd in zip(keys, ids):       # per entry: the ones that were answered with a node
+            if nd != NONE:
+                self.stamp(k)
+        return after
 
     def op_try_request(self):
         p, other = self.h()
         key, me = self.pick_key(0.95), self.pick_addr(0.0)
         st = self.begin()
         if self.rng.random() < 0.5:
-            p.lookup(key[0], key[1])
+            self.plain_lookup(p, st, key)
         t0 = p.device_round_trips()
         rc, out, flag = p.try_get_or_create_placement(key[0], key[1], me, 512)
         if rc != EAGAIN:
+            self.stamp(key, shadow=True)   # (an EAGAIN answer does not stamp)
             want = self.where(st, key)
             self.want(rc == OK and want is not None and out == want, "try_request: wrong address", rc, out, want)
             self.want(self.alive[self.aid[want]] and not self.is_bad(want), "try_request answered for a server that is not an active member")
@@ -795,25 +918,26 @@ class Scenario:
         load = int(rng.choice([0, 2, 3, 5, 9])) if self.kstr(key) not in self.keys or self.keys[self.kstr(key)].row is None \
             else int(rng.choice([0, 1, 2, 3, 5, 9]))
         st = self.begin()
+        fresh = self.kstr(key) not in self.keys
         ok = self.intern(st, [(key, True, False, None, False)])
         rc = p.set_object_load(key[0], key[1], load)
         if not ok:
             return self.refused_unchanged(st, rc, "set_object_load")
         self.want(rc == OK, "set_object_load failed", rc)
         self.ref_on = False
+        if fresh:
+            self.set_aside.add(self.kstr(key))
         k = self.keys[self.kstr(key)]
         after = self.read()
         if k.row is None:      # the one row whose load is now `load` and was not: that is the key's row
             nb = st["n"]
             was = np.concatenate([st["load"], np.ones(after["n"] - nb, np.uint32)])
-            ch = [int(r) for r in np.flatnonzero((after["load"] != was) & (after["load"] == load))]
+            # (a row reclaimed by this very call was reset to load 1 first: it counts as changed even where its old key's load
+            #  was the same number)
+            ch = [int(r) for r in np.flatnonzero(after["load"] == load) if after["load"][r] != was[r] or int(r) in self.reset_rows]
             self.want(len(ch) == 1, "set_object_load changed not exactly one row's load", ch)
             self.want(ch[0] not in self.row2key, "set_object_load of a new key wrote the row of another key", ch[0])
-            if ch[0] in self.ever_rows:
-                self.handed.add(ch[0])
-            self.ever_rows.add(ch[0])
-            k.row = ch[0]
-            self.row2key[k.row] = self.kstr(key)
+            self.new_row(k, self.kstr(key), ch[0])
         self.load_row = k.row
         self.want(after["load"][k.row] == load, "set_object_load: the load is not on the key's row", k.row)
         return self.settle(st, st["col"].copy(), [], "set_object_load")
@@ -856,7 +980,7 @@ class Scenario:
         rng = self.rng
         st = self.begin()
         for ks in list(self.keys)[:6]:           # (the shadow holds answers a rebalance must void)
-            p.lookup(self.keys[ks].ty, self.keys[ks].oid)
+            self.plain_lookup(p, st, (self.keys[ks].ty, self.keys[ks].oid))
         mm = (None, 0, 1, int(rng.integers(2, 6)), int(rng.integers(2, 40)))[int(rng.integers(5))]
         rc, moves = p.rebalance(mm, mid=lambda: other.len())
         self.want(rc == OK, "rebalance failed", rc)
@@ -885,7 +1009,7 @@ class Scenario:
     def op_changes(self):
         p, other = self.h()
         st = self.begin()
-        rc, full, entries = p.changes(mid=lambda: other.lookup("T0", "0"))
+        rc, full, entries = p.changes(mid=lambda: self.plain_lookup(other, st, ("T0", "0")))
         self.want(rc == OK, "changes failed", rc)
         self.want(full == (self.feed_state != "open"), "changes: `full` is 1 exactly on the first read and the first after a reset", full, self.feed_state)
         try:
@@ -905,6 +1029,7 @@ class Scenario:
                     rows.append(r)
             self.want(rows == sorted(rows), "changes: a group is not in row order", rows[:12])
         self.dropped_since_feed = {}
+        self.expired_since_feed = set()
         self.feed_state = "open"
         self.unchanged(st, "changes")
 
@@ -913,14 +1038,16 @@ class Scenario:
         self.want(p.changes_reset() == OK, "changes_reset failed")
         self.feed_state = "reset"
         self.dropped_since_feed = {}
+        self.expired_since_feed = set()
 
     def op_invalidate_cache(self):
         p, other = self.h()
         st = self.begin()
         self.want(p.invalidate_cache() == OK, "invalidate_cache failed")
         key = self.pick_key(1.0)
-        rc, _, _ = p.try_lookup(key[0], key[1], 512)
+        rc, found, _ = p.try_lookup(key[0], key[1], 512)
         self.want(rc == EAGAIN or self.kstr(key) not in self.keys, "try_lookup answered right after invalidate_cache", rc)
+        self.want(not found, "try_lookup found a key nobody has interned", key)
         self.unchanged(st, "invalidate_cache")
 
     def op_objects_on_server(self, st=None):
@@ -953,6 +1080,93 @@ class Scenario:
         self.want(rc == OK and n == int((st["col"] != NONE).sum()), "len differs from the placed rows", rc, n)
         if self.ref_on:
             self.want(n == len(self.ref[0]), "len differs from the reference restatement's", n, len(self.ref[0]))
+
+    def op_set_clock(self):
+        """The clock the clones share, set through either: it mostly rises, sometimes repeats or falls, sometimes goes back to 0,
+        which turns stamping off."""
+        p, other = self.h()
+        r = self.rng.random()
+        if r < 0.15:
+            now = 0
+        elif r < 0.3:
+            now = int(self.rng.integers(0, self.clock_top + 1))
+        else:
+            now = self.clock_top = self.clock_top + int(self.rng.integers(1, 10))
+        self.want(p.set_clock(now) == OK, "set_clock failed")
+        self.clock = now
+        self.clock_ever = self.clock_ever or now != 0
+
+    def check_seen(self, what):
+        """Every sweep uploads the host's stamps (a count-only one too): the one place where they become visible."""
+        seen = self.g.get_seen() if self.g.num_objects else np.zeros(0, np.uint32)
+        bad = np.flatnonzero(seen != self.S[:len(seen)])
+        self.want(bad.size == 0, what + ": the stamps on the device differ from the model's", bad[:8], seen[bad[:8]], self.S[bad[:8]])
+
+    def op_expire(self):
+        p, other = self.h()
+        rng = self.rng
+        st = self.begin()
+        n, col = st["n"], st["col"]
+        placed = [int(r) for r in np.flatnonzero(col != NONE)]
+        # a witness: a placed key looked up right before the sweep (the shadow holds its answer, and the lookup stamps it)
+        wit = None
+        if placed:
+            k = self.keys[self.row2key[placed[int(rng.integers(len(placed)))]]]
+            wit = (k.ty, k.oid)
+            self.plain_lookup(p, st, wit)
+        cutoff = (0, self.clock, min(self.clock + 1, 0xFFFFFFFF), int(rng.integers(0, self.clock_top + 1)), 0xFFFFFFFF)[int(rng.integers(5))]
+        first = not self.clock_ever and rng.random() < 0.5      # (while the clock has never been set: any cutoff > 0, no limit)
+        if first:
+            cutoff = (1, 0xFFFFFFFF)[int(rng.integers(2))]
+        _, _, n_idle, _, _ = spec_expire.expire(col, self.S, st["load"], n, cutoff, None)
+        cap = (None, 0, 1, int(rng.integers(2, 9)), max(n_idle - 1, 0), n_idle, n_idle + 1)[int(rng.integers(7))]
+        if first:
+            cap = None
+        rows, nodes, w_idle, _, A2 = spec_expire.expire(col, self.S, st["load"], n, cutoff, cap)
+        want = []
+        for r, nd in zip(rows, nodes):
+            ks = self.row2key.get(int(r))
+            if ks is None:
+                self.fail("a placed row has no key in the model", int(r))
+            want.append((self.keys[ks].ty, self.keys[ks].oid, self.addr[nd] if nd < len(self.addr) else None))
+        rc, got, got_idle = p.expire(cutoff, cap, mid=lambda: other.len())
+        self.want(rc == OK, "expire failed", rc)
+        self.want(got == want, "expire: the listing is not the reference's, key for key in row order", cutoff, cap, got[:4], want[:4])
+        self.want(got_idle == w_idle, "expire: n_idle", got_idle, w_idle)
+        L = len(rows)
+        live = [r for r in placed if int(self.S[r]) >= cutoff]
+        self.hit("expire listed keys", L > 0)
+        self.hit("expire count only with idle keys", cap == 0 and n_idle > 0)
+        self.hit("expire capped below n_idle", 0 < L < n_idle)
+        self.hit("sweep with the clock never set listed everything placed", not self.clock_ever and cutoff > 0 and L == len(placed) > 0)
+        self.hit("a key stamped only by a shadow hit survived a sweep", cutoff > 0 and any(int(self.S_dev[r]) < cutoff for r in live))
+        self.hit("a sweep judged a key by a stamp its row's previous key left",
+                 cutoff > 0 and any(r not in self.own and self.S[r] > 0 for r in placed))
+        self.hit("expire listed a key set aside by set_object_load", any(self.row2key[int(r)] in self.set_aside for r in rows))
+        # the table: rio_op_remove of the listed keys, under the row lifecycle
+        xcol = col.copy()
+        if L:
+            self.oracle.remove_batch(xcol, rows)
+        self.want(np.array_equal(xcol, A2[:n]), "the two references differ")
+        for ty, oid, _ in want:
+            self.ref_key((ty, oid))
+            if self.ref_on:
+                self.ref[0].remove(ty, oid)
+        after = self.settle(st, xcol, [], "expire")
+        xaff = st["aff"].copy()
+        xaff[rows] = AFF_INACTIVE
+        self.want(np.array_equal(after["aff"][:n], xaff), "expire: the affinity column", np.flatnonzero(after["aff"][:n] != xaff)[:8])
+        self.check_seen("expire")
+        self.expired_since_feed |= set(int(r) for r in rows)
+        if L:
+            self.probe(after, [self.row2key[int(rows[int(rng.integers(L))])]])
+        if wit is not None and wit not in [(a, b) for a, b, _ in want]:
+            # a key that was not listed is answered as before — with the shadow on, without a device round trip
+            t0 = p.device_round_trips()
+            self.check_lookup(after, p, other, wit, p.lookup, "lookup")
+            self.want(self.flags & CFG_NO_HOST_SHADOW or p.device_round_trips() == t0,
+                      "expire: a key that was not listed lost its shadow entry", wit)
+        return after
 
     # ---- the run ------------------------------------------------------------------------------------------------------
     def setup(self):
@@ -1005,6 +1219,9 @@ class Scenario:
             st = self.read()
             self.op_objects_on_server(st)
             self.op_snapshot(st)
+            rc, got, _ = self.handles[0].expire(0, 0)       # the stamps of the whole run, uploaded by a count-only sweep
+            self.want(rc == OK and got == [], "a count-only sweep failed or listed something", rc, got[:4])
+            self.check_seen("the end")
             self.op_changes()
         finally:
             for h in self.handles[::-1]:

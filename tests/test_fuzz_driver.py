@@ -41,6 +41,21 @@ FLOOR = (
     "remap down to a kernel's node-count boundary",
     "rebalance on a handle whose m is below max_nodes",
     "place_pending on a handle whose m is below max_nodes",
+    "expire un-placed rows",
+    "expire capped below n_idle",
+    "expire with a placed row stamped exactly at the cutoff",
+    "expire as the first call of the family",
+    "expire listed rows while a solve was uncommitted",
+    "expire hit nothing while a solve was uncommitted",
+    "expire between tick_async and tick_wait",
+    "expire with hidden placed rows older than the cutoff",
+    "expire at n == 0",
+    "expire on a handle whose m is below max_nodes",
+    "expire between two pages of the feed",
+    "touch while a solve is uncommitted",
+    "touch with hidden rows",
+    "touch_dev skipped invalid entries",
+    "touch between tick_async and tick_wait",
 )
 
 # fault of the stand-in -> the operation the failure must name
@@ -59,6 +74,19 @@ FAULTS = {
     "remap_checkpoint_none_not_gone": "changes",
     "remap_stale_node_table": "remap",
     "remap_affinity_not_renumbered": "tick",
+    "expire_cutoff_inclusive": "expire",
+    "expire_unplaces_past_cap": "expire",
+    "expire_lists_hidden_rows": "expire",
+    "expire_freed_counts_unlisted": "expire",
+    "expire_stale_used": "expire",
+    "expire_keeps_solve": "expire",
+    "expire_zero_hit_drops_solve": "expire",
+    "expire_count_only_writes": "expire",
+    "touch_overwrites": "touch",
+    "touch_all_past_n": "num_objects",
+    "touch_dev_stops_at_invalid": "touch",
+    "touch_drops_solve": "touch",
+    "remap_moves_seen": "remap",
 }
 
 
@@ -77,7 +105,7 @@ def test_op_tables():
                                  ("clean", 2), ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
     assert fuzz.Scenario.OPS_EXT[:len(fuzz.Scenario.OPS)] == fuzz.Scenario.OPS
     assert [a for a, _ in fuzz.Scenario.OPS_EXT[len(fuzz.Scenario.OPS):]] == ["index", "rebalance", "changes", "changes_reset",
-                                                                            "num_objects", "remap"]
+                                                                            "num_objects", "remap", "touch", "expire"]
 
 
 @pytest.fixture(scope="module")
@@ -96,8 +124,9 @@ def clean_run(oracle):
 
 def test_extended_seeds_run_clean_and_use_every_new_operation(clean_run):
     cov, count = clean_run
-    for op in ("index", "rebalance", "changes", "changes_reset", "num_objects", "remap", "in flight: index", "in flight: changes",
-               "in flight: rebalance", "in flight: remap"):
+    for op in ("index", "rebalance", "changes", "changes_reset", "num_objects", "remap", "touch", "expire", "in flight: index",
+               "in flight: changes", "in flight: rebalance", "in flight: remap", "in flight: touch", "in flight: expire",
+               "mid run: touch", "mid run: expire count", "mid run: expire"):
         assert count.get(op, 0) > 0, (op, count)
 
 

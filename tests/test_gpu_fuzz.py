@@ -28,6 +28,19 @@ checked; rows hidden at the time are compared when n grows again and at the end.
 kept value >= m_new, too few kept entries, m_new > m): RIO_GP_EINVAL and nothing changed, an uncommitted solve included.  It is
 also called between tick_async and tick_wait and in the middle of a chained quiet run, where the tick after it must not chain.
 
+Idle expiry (tests/spec_expire.py) is fuzzed the same way: the scenario keeps a model S of the last-seen column over every row the
+handle holds and a clock of its own (epochs mostly rise, some repeat or fall, 0 and 0xFFFFFFFF now and then).  `touch` draws one of
+the family's writers — the host batch (and one refused for an index >= n), the _dev batch (sometimes not 16-byte aligned; with
+invalid entries it applies the rest and reports RIO_GP_EINVAL), touch_all, touch_merge host and _dev (rows 0, n, a boundary size,
+any; stamps below, at and above what S holds) and a merge of n + 1 rows, refused — and rio_gp_get_seen must equal S[:n] after each,
+an uncommitted solve still there.  `expire` draws a cutoff (0, a placed row's own stamp, one above the largest, 0xFFFFFFFF), a cap
+(none, 0, 1, small, n_idle - 1 / n_idle / n_idle + 1, one that ends the listing inside a tile of 1 024 rows) and a form (host,
+the call as given into sentinel-filled arrays, _dev, count-only host and _dev): rows, nodes, n_idle and load_freed are exact,
+nothing is written past the listing, the column and `used` follow, S does not change; a sweep that listed rows drops an
+uncommitted solve and ends a chained run, one that listed nothing (or only counted) leaves both alone.  Both are also called
+between tick_async and tick_wait and in the middle of chained quiet runs; S is compared again when hidden rows come back and after
+every node removal (S names no node).
+
     python tests/test_gpu_fuzz.py <seconds> [first_seed]     # a longer campaign: old and extended scenarios alternate
 """
 import os
@@ -122,6 +135,12 @@ class Scenario:
         self.paging_out = self.mixed_wrote = False
         self.m0 = m                # the handle's max_nodes: a removal leaves m below it
         self.remapped = self.remap_refused = False
+        # idle expiry: the model of the last-seen column (rows >= n keep their value), the scenario's own clock for epochs,
+        # whether a call of the family has been made (the first one allocates S), whether the last sweep un-placed anything
+        self.S = np.zeros(n, np.uint32)
+        self.clock = 0
+        self.seen_used = self.expire_listed = False
+        self.mids = 0              # quiet runs so far (op_async: which call goes into the middle of the next one)
         self.cov = {}
 
     def _caps(self):
@@ -182,14 +201,19 @@ class Scenario:
 
     def op_async(self):
         k = int(self.rng.integers(1, 5))
-        quiet_run = self.chain_small and self.rng.random() < 0.5   # a longer stream without changes: verdicts land, the ticks chain
+        # a longer stream without changes: verdicts land, the ticks chain (extended scenarios: more often, for the calls in its middle)
+        quiet_run = self.chain_small and self.rng.random() < (0.75 if self.ext else 0.5)
         if quiet_run:
             k += 6
         last_chained = False
         want_st = []
         # extended scenarios, a quiet run: a call in the middle of it (see _mid_call); any run: a call between the last tick_async
         # and tick_wait, whose answer reflects every enqueued tick
-        mid = ("none", "index", "changes", "rebalance", "remap")[int(self.rng.integers(5))] if self.ext and quiet_run else "none"
+        # (the calls take turns, from a start the seed sets: a dozen of the default seeds have such runs, and each call gets one)
+        mid = "none"
+        if self.ext and quiet_run:
+            mid = self.MID[(self.seed // 6 + self.mids) % len(self.MID)]
+            self.mids += 1
         watch = None
         for i in range(k):
             if i and not quiet_run and self.rng.random() < 0.5:
@@ -204,12 +228,13 @@ class Scenario:
             want_st.append(ost)
             if self.lab and mid != "none":
                 last_chained = self.g.chained_scans() - c0 == 1
-                if watch is not None and watch[0] in ("rebalance", "remap") and i == k - 4:
-                    # a rebalance and a node removal (the identity map too) change the inputs: the tick after does not chain
+                if watch is not None and watch[0] in self.ENDS_CHAIN and i == k - 4:
+                    # a rebalance, a node removal (the identity map too) and a sweep that un-placed a row change the inputs: the
+                    # tick after does not chain
                     assert not last_chained, (self.seed, watch[0], "the tick after a %s chained" % watch[0], self.log[-6:])
             if self.rng.random() < 0.3 or (quiet_run and i < 3):
                 time.sleep(0.002)
-        if watch is not None and watch[0] not in ("rebalance", "remap") and watch[1]:
+        if watch is not None and watch[0] not in self.ENDS_CHAIN and watch[1]:
             # the tick before the call was a link of a chain and nothing has changed since: the 4 ticks after it are links too,
             # as they are in the same run without the call
             c = self.g.chained_scans() - watch[2]
@@ -218,7 +243,7 @@ class Scenario:
         if self.ext and self.rng.random() < 0.5:
             self.in_flight = True
             try:
-                what = ("index", "changes", "rebalance", "remap")[int(self.rng.integers(4))]
+                what = ("index", "changes", "rebalance", "remap", "touch", "expire")[int(self.rng.integers(6))]
                 self.log.append("in flight: " + what)
                 self.count["in flight: " + what] = self.count.get("in flight: " + what, 0) + 1
                 getattr(self, "op_" + what)()
@@ -230,7 +255,9 @@ class Scenario:
     def _mid_call(self, what, last_chained):
         """A call between the quiet asynchronous ticks of a run (lab build, every tick may chain).  The index and a consuming feed
         call change nothing a tick reads: if the tick before was a link of a chain, the ticks after are.  A rebalance ends the
-        chain, and so does a node removal.  -> (what, the tick before chained, chained_scans() after the call)"""
+        chain, and so does a node removal.  A touch, a count-only sweep and a sweep that lists nothing change nothing either; a
+        sweep that un-placed a row ends the chain ("expire" comes back as "expire count" when it listed nothing).
+        -> (what, the tick before chained, chained_scans() after the call)"""
         self.log.append("mid run: " + what)
         self.count["mid run: " + what] = self.count.get("mid run: " + what, 0) + 1
         if what == "index":
@@ -239,6 +266,13 @@ class Scenario:
             self._feed(None if self.rng.random() < 0.5 else int(self.rng.integers(1, 50)), False, False)
         elif what == "rebalance":
             self.op_rebalance()
+        elif what == "touch":
+            self.op_touch()
+        elif what == "expire count":
+            self.op_expire(hit=False)
+        elif what == "expire":
+            if not self.op_expire(hit=True):
+                what = "expire count"
         else:
             self.op_remap(legal=True)     # (a refused map changes nothing: only a legal one must end the chain)
         return what, last_chained, self.g.chained_scans() if self.lab else 0
@@ -392,7 +426,10 @@ class Scenario:
         committed (sometimes it is, and the model follows)."""
         if self.pending is None:
             return
-        got = self.g.get_solved()
+        try:
+            got = self.g.get_solved()
+        except self.gp.ObjectPlacementError as e:
+            raise AssertionError((self.seed, what, "the uncommitted solve is gone", self.log[-6:], str(e)))
         assert np.array_equal(got, self.pending), (self.seed, what, "the uncommitted solve changed", self.log[-6:],
                                                    np.flatnonzero(got != self.pending)[:8])
         if not self.paging_out and self.rng.random() < 0.3:
@@ -619,6 +656,8 @@ class Scenario:
             got, aff = self.g.get_assign(), self.g.get_objects()[1]
             assert np.array_equal(got, self.ref[:n]), tag + ("assignment", np.flatnonzero(got != self.ref[:n])[:8])
             assert np.array_equal(aff, self.aff[:n]), tag + ("affinity", np.flatnonzero(aff != self.aff[:n])[:8])
+        if grew and self.seen_used:    # the stamps of the rows that were hidden: no touch, sweep or remap in between moved them
+            self._seen_check((self.seed, "num_objects", "the stamps of rows that were hidden", self.log[-6:]))
 
     def _remap_draw(self):
         """A legal map for rio_gp_remap_nodes, at least one node kept: identity | permutation | swap | drop one | drop several
@@ -734,9 +773,217 @@ class Scenario:
         assert np.array_equal(load, self.load[:n]), tag + ("load changed",)
         assert np.array_equal(aff, self.aff[:n]), tag + ("affinity", np.flatnonzero(aff != self.aff[:n])[:8])
         self.check_table("remap")
+        if self.seen_used:             # S names no node: it does not move with them
+            self._seen_check(tag + ("the last-seen column changed",))
         if had_solve:
             self._dropped("remap")
         self._hit("remap removed nodes that held rows", ev > 0)
+
+    # ---- idle expiry: the touch calls and rio_gp_expire against tests/spec_expire.py ---------------------------------------
+    def _seen_check(self, tag):
+        got = self.g.get_seen()
+        self.seen_used = True
+        assert np.array_equal(got, self.S[:self.n]), tag + ("get_seen differs from the model", np.flatnonzero(got != self.S[:self.n])[:8])
+
+    def _epoch(self):
+        """The scenario's clock: most epochs rise; some repeat or fall (the calls are maxima); now and then 0 and 0xFFFFFFFF."""
+        rng, k = self.rng, self.rng.random()
+        if k < 0.06:
+            return 0
+        if k < 0.10:
+            return 0xFFFFFFFF
+        if k < 0.30:
+            return int(rng.integers(0, self.clock + 1))
+        self.clock += int(rng.integers(1, 40))
+        return self.clock
+
+    def _beyond_n(self):
+        """A row index a call must refuse: n, n + 1, max_objects, NONE."""
+        n = self.n
+        return int((n, n + 1, max(self.nmax, n), NONE)[int(self.rng.integers(4))])
+
+    def _dev_offset(self, arr):
+        """arr on the device, sometimes behind 1 .. 3 words of padding so that it is not 16-byte aligned -> (buffer, address)."""
+        off = int(self.rng.integers(0, 2)) * int(self.rng.integers(1, 4))
+        d = self._devbuf()(np.concatenate([np.zeros(off, np.uint32), np.asarray(arr, np.uint32)]))
+        return d, d.ptr + 4 * off
+
+    def _refused(self, call, tag):
+        try:
+            call()
+        except self.gp.ObjectPlacementError as e:
+            assert e.rc == self.gp.EINVAL, tag + ("refused with", e.rc)
+            return
+        raise AssertionError(tag + ("the call was not refused",))
+
+    def op_touch(self):
+        import spec_expire
+        rng, n, g = self.rng, self.n, self.g
+        form = ("host", "host refused", "dev", "dev invalid", "all", "merge", "merge dev", "merge refused")[int(rng.integers(8))]
+        epoch = self._epoch()
+        tag = (self.seed, "touch", form, epoch, n, self.log[-6:])
+        self._hit("touch while a solve is uncommitted", self.pending is not None)
+        self._hit("touch with hidden rows", n < self.nmax)
+        self._hit("touch between tick_async and tick_wait", self.in_flight)
+        idx = self._idx(big_ok=False) if n else np.zeros(0, np.uint32)
+        bufs = []
+        if form == "host":
+            g.touch(idx, epoch)
+            self.S = spec_expire.touch(self.S, idx, epoch)
+        elif form == "host refused":          # validated first: one index >= n, nothing changes
+            bad = np.append(idx, np.uint32(0))
+            bad[int(rng.integers(bad.size))] = self._beyond_n()
+            rc = g.touch_raw(bad, epoch)
+            assert rc == self.gp.EINVAL, tag + (rc,)
+        elif form == "dev":
+            d, ptr = self._dev_offset(idx)
+            bufs.append(d)
+            g.touch_dev(ptr, idx.size, epoch)
+            self.S = spec_expire.touch(self.S, idx, epoch)
+        elif form == "dev invalid":           # the valid entries are applied, the call reports RIO_GP_EINVAL
+            bad = np.append(idx, np.uint32(0))
+            for k in rng.integers(0, bad.size, int(rng.integers(1, 5))):
+                bad[int(k)] = self._beyond_n()
+            d, ptr = self._dev_offset(bad)
+            bufs.append(d)
+            self._refused(lambda: g.touch_dev(ptr, bad.size, epoch), tag)
+            self.S = spec_expire.touch(self.S, bad[bad < n], epoch)
+            self._hit("touch_dev skipped invalid entries")
+        elif form == "all":
+            g.touch_all(epoch)
+            self.S = spec_expire.touch_all(self.S, n, epoch)
+        elif form == "merge refused":         # rows = n + 1
+            stamps = np.full(n + 1, epoch, np.uint32)
+            if rng.random() < 0.5:
+                self._refused(lambda: g.touch_merge(stamps), tag)
+            else:
+                d, ptr = self._dev_offset(stamps)
+                bufs.append(d)
+                self._refused(lambda: g.touch_merge_dev(ptr, n + 1), tag)
+        else:
+            rows = (0, n, _pick(rng, _SIZES, n) if n else 0, int(rng.integers(0, n + 1)))[int(rng.integers(4))]
+            # per row: 0 | below | equal to | above what S holds | 0xFFFFFFFF (rare: it ends the row's part in every later sweep)
+            have = self.S[:rows].astype(np.int64)
+            kind = rng.choice(5, rows, p=[0.15, 0.25, 0.2, 0.38, 0.02])
+            step = rng.integers(1, 40, rows)
+            stamps = np.select([kind == 0, kind == 1, kind == 2, kind == 3], [0, have - step, have, have + step], 0xFFFFFFFF)
+            stamps = np.clip(stamps, 0, 0xFFFFFFFF).astype(np.uint32)
+            if rows and epoch in (0, 0xFFFFFFFF):
+                stamps[int(rng.integers(rows))] = epoch
+            if form == "merge":
+                g.touch_merge(stamps)
+            else:
+                d, ptr = self._dev_offset(stamps)
+                bufs.append(d)
+                g.touch_merge_dev(ptr, rows)
+            self.S = spec_expire.touch_merge(self.S, stamps)
+        self._seen_check(tag)      # (it waits: rio_gp_touch_all and rio_gp_touch_merge_dev do not, and their buffer is freed below)
+        for d in bufs:
+            d.free()
+        self._read_only("touch")
+        self.check_table("touch")
+
+    def _expire_cap(self, idle, n_idle):
+        """None | 0 | 1 | a small number | n_idle - 1, n_idle, n_idle + 1 | a cap that ends the listing inside a tile of 1 024 rows
+        that holds more idle rows."""
+        rng = self.rng
+        k = int(rng.integers(8))
+        if k < 4:
+            return (None, 0, 1, int(rng.integers(2, 60)))[k]
+        if k < 7:
+            return max(n_idle + k - 5, 0)
+        _, first, count = np.unique(idle // 1024, return_index=True, return_counts=True)
+        many = np.flatnonzero(count >= 2)
+        if len(many) == 0:
+            return max(n_idle - 1, 0)
+        t = int(many[rng.integers(len(many))])
+        return int(first[t]) + int(rng.integers(1, count[t]))
+
+    def op_expire(self, hit=None):
+        """rio_gp_expire[_dev] against spec_expire.expire over the model's column, stamps and loads.  hit: None — cutoff, cap and
+        form are drawn; True — a listing that un-places at least one row when any placed row can be idle; False — a count-only
+        call or cutoff 0.  -> rows un-placed."""
+        import spec_expire
+        rng, n, g = self.rng, self.n, self.g
+        S, A = self.S, self.ref
+        placed = np.flatnonzero(A[:n] != NONE)
+        first, had_solve = not self.seen_used, self.pending is not None
+        form = ("host", "dev", "host", "dev", "count", "dev count")[int(rng.integers(6))]
+        if hit is True:
+            form = form if form in ("host", "dev") else ("host", "dev")[int(rng.integers(2))]
+            lo = int(S[placed].min()) if len(placed) else 0
+            cutoff = (min(lo + 1, 0xFFFFFFFF), min(int(S[placed].max()) + 1 if len(placed) else 1, 0xFFFFFFFF), 0xFFFFFFFF)[int(rng.integers(3))]
+        elif hit is False and rng.random() < 0.5:
+            cutoff = 0
+        else:
+            k = int(rng.integers(4))
+            if k == 0:
+                cutoff = 0
+            elif k == 1:      # a placed row's own stamp: the strict < decides that row
+                cutoff = int(S[placed[rng.integers(len(placed))]]) if len(placed) else int(S[:n].max()) if n else 0
+            elif k == 2:
+                cutoff = min(int(S[:n].max()) + 1 if n else 1, 0xFFFFFFFF)
+            else:
+                cutoff = 0xFFFFFFFF
+        if hit is False and cutoff != 0:
+            form = form if form in ("count", "dev count") else ("count", "dev count")[int(rng.integers(2))]
+        listing = form in ("host", "dev")
+        idle, _, n_idle, _, _ = spec_expire.expire(A, S, self.load, n, cutoff, None)
+        cap = self._expire_cap(idle, n_idle) if listing else None
+        if hit is True and cap == 0:
+            cap = 1
+        want_cap = cap if listing else 0
+        wrows, wnodes, w_idle, wfreed, A2 = spec_expire.expire(A, S, self.load, n, cutoff, want_cap)
+        L = len(wrows)
+        tag = (self.seed, "expire", form, cutoff, cap, n, self.log[-6:])
+        self._hit("expire un-placed rows", L > 0)
+        self._hit("expire capped below n_idle", 0 < L < n_idle)
+        self._hit("expire with a placed row stamped exactly at the cutoff", cutoff > 0 and bool((S[placed] == cutoff).any()))
+        self._hit("expire as the first call of the family", first)
+        self._hit("expire listed rows while a solve was uncommitted", had_solve and L > 0)
+        self._hit("expire hit nothing while a solve was uncommitted", had_solve and L == 0)
+        self._hit("expire between tick_async and tick_wait", self.in_flight)
+        self._hit("expire with hidden placed rows older than the cutoff", bool(((A[n:] != NONE) & (S[n:] < cutoff)).any()))
+        self._hit("expire at n == 0", n == 0)
+        self._hit("expire on a handle whose m is below max_nodes", self.m < self.m0)
+        self._hit("expire between two pages of the feed", self.page_open)
+        self.seen_used = True
+        if form == "count":
+            rows, nodes, got_idle, freed = g.expire(cutoff, count_only=True)
+        elif form == "dev count":
+            got_idle, freed = g.expire_dev(cutoff)
+            rows = nodes = np.zeros(0, np.uint32)
+        elif form == "host" and (cap is None or rng.random() < 0.5):
+            rows, nodes, got_idle, freed = g.expire(cutoff, cap)
+        elif form == "host":   # the call as given, into sentinel-filled arrays of cap + 2, without load_freed
+            out = [np.full(cap + 2, 0xDEADBEEF, np.uint32) for _ in range(2)]
+            rc, got_idle = g.expire_raw(cutoff, out[0], out[1], cap)
+            assert rc == self.gp.OK, tag + (rc,)
+            assert all((x[L:] == 0xDEADBEEF).all() for x in out), tag + ("written past the listing",)
+            rows, nodes, freed = out[0][:L], out[1][:L], wfreed
+        else:
+            c = n if cap is None else int(cap)
+            d = [self._devbuf()(np.full(c + 2, 0xDEADBEEF, np.uint32)) for _ in range(2)]
+            got_idle, freed = g.expire_dev(cutoff, d[0].ptr, d[1].ptr, c)
+            rows, nodes = (x.to_host() for x in d)
+            for x in d:
+                x.free()
+            assert all((x[L:] == 0xDEADBEEF).all() for x in (rows, nodes)), tag + ("written past the listing",)
+            rows, nodes = rows[:L], nodes[:L]
+        assert got_idle == w_idle == n_idle, tag + ("n_idle", got_idle, w_idle)
+        assert np.array_equal(rows, wrows) and np.array_equal(nodes, wnodes), tag + (rows[:8], wrows[:8], nodes[:8], wnodes[:8])
+        assert freed == wfreed, tag + ("load_freed", freed, wfreed)
+        self.ref = A2
+        self.expire_listed = L > 0
+        self._seen_check(tag)          # a sweep reads S and never writes it
+        if L > 0:
+            self.pending = None
+            if had_solve:
+                self._dropped("expire")
+        else:
+            self._read_only("expire")
+        self.check_table("expire")
+        return L
 
     def finish_feed(self):
         """The end of an extended scenario: the rest of the feed is paged out — three small pages, then pages of a third of what
@@ -754,13 +1001,16 @@ class Scenario:
                                                            self.log[-6:], np.flatnonzero(self.mirror[:self.n] != got)[:8])
 
     NEED_ROWS = ("update", "remove", "lookup", "place", "mixed", "attrs")                       # skipped while n == 0
-    WRITERS = ("tick", "solve", "async", "update", "remove", "clean", "place", "mixed", "rebalance", "num_objects", "remap")
-    DROPS_SOLVE = ("tick", "rebalance", "update", "remove", "clean", "place", "mixed", "attrs", "caps", "num_objects", "remap")
+    WRITERS = ("tick", "solve", "async", "update", "remove", "clean", "place", "mixed", "rebalance", "num_objects", "remap", "expire")
+    DROPS_SOLVE = ("tick", "rebalance", "update", "remove", "clean", "place", "mixed", "attrs", "caps", "num_objects", "remap", "expire")
+    MID = ("none", "index", "changes", "rebalance", "remap", "touch", "expire count", "expire")   # op_async: a call in a quiet run
+    ENDS_CHAIN = ("rebalance", "remap", "expire")    # ... after which the next tick must not chain (an "expire" un-placed a row)
 
     OPS = (("tick", 5), ("solve", 2), ("async", 3), ("flip", 4), ("update", 2), ("remove", 2), ("lookup", 1), ("clean", 2),
            ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
 
-    OPS_EXT = OPS + (("index", 3), ("rebalance", 6), ("changes", 5), ("changes_reset", 1), ("num_objects", 2), ("remap", 3))
+    OPS_EXT = OPS + (("index", 3), ("rebalance", 6), ("changes", 5), ("changes_reset", 1), ("num_objects", 2), ("remap", 3),
+                     ("touch", 4), ("expire", 4))
 
     def run(self):
         names = [a for a, w in (self.OPS_EXT if self.ext else self.OPS) for _ in range(w)]
@@ -771,7 +1021,7 @@ class Scenario:
                 if self.ext and self.pending is not None and self.rng.random() < 0.5:
                     # an uncommitted solve lives until the next writer: half the time the calls that must keep it, or must drop
                     # it themselves, come right behind it (the table's weights alone bring them there a few times in 72 seeds)
-                    op = ("index", "remap", "rebalance", "remap")[int(self.rng.integers(4))]
+                    op = ("index", "remap", "rebalance", "remap", "touch", "expire", "expire")[int(self.rng.integers(7))]
                 if self.ext and self.n == 0 and op in self.NEED_ROWS:
                     self.log.append("skipped: " + op)
                     continue
@@ -780,12 +1030,14 @@ class Scenario:
                 had_solve = self.pending is not None
                 getattr(self, "op_" + op)()
                 if self.ext:
-                    did = (op != "mixed" or self.mixed_wrote) and (op != "remap" or not self.remap_refused)
-                    if op in self.WRITERS and (op != "remap" or did):
+                    # (a sweep that listed nothing is treated as a refused remap is: it wrote nothing and drops nothing)
+                    did = ((op != "mixed" or self.mixed_wrote) and (op != "remap" or not self.remap_refused) and
+                           (op != "expire" or self.expire_listed))
+                    if op in self.WRITERS and (op not in ("remap", "expire") or did):
                         self.page_writer = True
                     if op in self.DROPS_SOLVE and did:
                         self.pending = None
-                        if had_solve and op not in ("rebalance", "remap"):    # (op_rebalance and op_remap have asked already)
+                        if had_solve and op not in ("rebalance", "remap", "expire"):    # (those three have asked already)
                             self._dropped(op)
                     elif op in ("mixed", "lookup"):
                         self._read_only(op)
@@ -793,7 +1045,8 @@ class Scenario:
             if self.ext:
                 self.finish_feed()
                 self.check_table("the end")
-                if self.remapped and self.n < self.nmax:    # the rows still hidden come back as the removals left them
+                if (self.remapped or self.seen_used) and self.n < self.nmax:
+                    # the rows still hidden come back as the removals left them, with the stamps they had
                     self._set_n(self.nmax)
                     self.check_table("the end, every row back")
             self.chained = self.g.chained_scans() if self.lab else 0
