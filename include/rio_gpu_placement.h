@@ -400,6 +400,55 @@ int rio_gp_expire(rio_gp_t* h, uint32_t cutoff, uint32_t* out_rows, uint32_t* ou
 int rio_gp_expire_dev(rio_gp_t* h, uint32_t cutoff, uint32_t* d_rows, uint32_t* d_node, uint64_t cap, uint64_t* n_idle,
                       uint64_t* load_freed);
 
+/* ---- measured load: per-row hit counters, and the fold that turns them into loads ------------- */
+
+/* The reference has no load at all (ObjectPlacementItem, rio-rs/src/object_placement/mod.rs:23-24, carries an id and an address;
+ * local.rs keeps a map of the two): like capacity, load is this library's extension, and so is measuring it.  The handle keeps a
+ * hit column H, one u32 per row of max_objects: requests counted for the row since the last fold.  H names no node and is
+ * written by the calls of this section only: ticks, the CRUD calls, rio_gp_place_pending, rio_gp_set_objects,
+ * rio_gp_set_num_objects, rio_gp_remap_nodes and rio_gp_expire leave it alone (a row handed to another object keeps its hits
+ * unless its owner folds or the row is hidden: the string layer zeroes its own counters, see rio_op_fold_loads).
+ * DESIGN.md section 2 rule 10 (frozen):
+ *   - rio_gp_hits_add_batch: H[idx[k]] = min(H[idx[k]] + w[k], 0xFFFFFFFF) for every k, w[k] = 1 when weight is NULL.
+ *     Duplicates sum; a saturating sum of non-negative numbers does not depend on the order, so the result is one fixed column.
+ *     The host form validates first (an idx[k] >= n is RIO_GP_EINVAL, nothing changes); the _dev form skips invalid entries and
+ *     reports RIO_GP_EINVAL, as rio_gp_touch_batch_dev does.
+ *   - rio_gp_hits_merge: H[r] = min(H[r] + counts[r], 0xFFFFFFFF) for r < rows, rows <= n (RIO_GP_EINVAL otherwise): a host that
+ *     counts for itself hands its counters over in one streaming pass.  d_counts may have any 4-byte alignment.
+ *   - rio_gp_get_hits: H[0 .. n-1]; n must be the row count, as for rio_gp_get_seen.
+ *   - The hits calls are no inputs of any solve: `used`, an uncommitted rio_gp_solve and the quiet and chained tick state stay as
+ *     they were.  They order themselves on the handle's stream; rio_gp_hits_merge_dev does not wait.
+ *   - rio_gp_load_fold, for every row r < n (affinity, lifecycle state and placement are not consulted), exact in u64:
+ *         x = floor(load[r] * keep / 65536) + H[r] * gain;   load[r] := clamp(x, min_load, max_load);   H[r] := 0
+ *     keep <= 65536 (65536 keeps the old load whole, 0 replaces it) and min_load <= max_load, else RIO_GP_EINVAL and nothing
+ *     changes.  x cannot overflow: load * keep <= (2^32-1) * 2^16 < 2^48, so the quotient is below 2^32; H * gain <= (2^32-1)^2 =
+ *     2^64 - 2^33 + 1; their sum is below 2^64 - 2^32.  Rows >= n keep both load and H.
+ *   - Statistics, over rows < n: rows_changed = rows whose load differs afterwards; hits_folded = the sum of H before;
+ *     load_before / load_after = the sums of load; max_load_after = the largest load afterwards (0 for n == 0).
+ *   - `used` is that of the new loads on return: rio_gp_get_nodes equals the sum of load over the rows r < n with
+ *     assign[r] == j < m.  When `used` is valid before the call the pass keeps it in step itself (it then reads the committed
+ *     column as well, 4 B per row more); when it is not, it stays invalid and is rebuilt before its next use.
+ *   - The fold behaves like rio_gp_set_object_attrs with loads: it orders itself behind rio_gp_tick_async work in flight, drops
+ *     an uncommitted rio_gp_solve and counts as a change of the inputs (no tick after it is quiet or chained over the old loads).
+ *     The change feed, S and the node index scratch are untouched.
+ *   - RIO_GP_EINVAL, nothing changed: a handle of the row-sharded solve (rio_gp_shard_*, rio_gp_p2p_*: a per-shard hit column
+ *     is not implemented), for every call of the section.
+ *   - Memory: H takes 4 B per row of max_objects, allocated (zero-filled) by the first call of this section and kept until
+ *     rio_gp_destroy; a handle that calls none of them pays nothing.
+ *   - Cost: the merge streams 8 B per row and writes only the quads that change; the fold streams load and H (8 B per row, 12
+ *     with `used` valid) and writes load where it differs and H where it held a hit. */
+typedef struct rio_gp_load_fold_stats {
+    uint64_t rows_changed, hits_folded, load_before, load_after;
+    uint32_t max_load_after, reserved;
+} rio_gp_load_fold_stats;
+int rio_gp_hits_add_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint32_t* weight /* NULL = 1 each */);
+int rio_gp_hits_add_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, const uint32_t* d_weight);
+int rio_gp_hits_merge(rio_gp_t* h, uint64_t rows, const uint32_t* counts);
+int rio_gp_hits_merge_dev(rio_gp_t* h, uint64_t rows, const uint32_t* d_counts);
+int rio_gp_get_hits(rio_gp_t* h, uint64_t n, uint32_t* out);
+int rio_gp_load_fold(rio_gp_t* h, uint32_t keep, uint32_t gain, uint32_t min_load, uint32_t max_load,
+                     rio_gp_load_fold_stats* st /* may be NULL */);
+
 /* ---- the placement policy, batched ------------------------------------------------------ */
 
 /* Service::get_or_create_placement + check_address_mismatch (service.rs:193-298) for a batch

@@ -69,6 +69,10 @@ extern "C" int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* m
 extern "C" int rio_gp_touch_merge(rio_gp_t* h, uint64_t rows, const uint32_t* stamps) __attribute__((weak));
 extern "C" int rio_gp_expire(rio_gp_t* h, uint32_t cutoff, uint32_t* out_rows, uint32_t* out_node, uint64_t cap, uint64_t* n_idle,
                              uint64_t* load_freed) __attribute__((weak));
+// Weak for the same reason: measured load (rio_op_fold_loads reports RIO_GP_EUPSTREAM without them).
+extern "C" int rio_gp_hits_merge(rio_gp_t* h, uint64_t rows, const uint32_t* counts) __attribute__((weak));
+extern "C" int rio_gp_load_fold(rio_gp_t* h, uint32_t keep, uint32_t gain, uint32_t min_load, uint32_t max_load,
+                                rio_gp_load_fold_stats* st) __attribute__((weak));
 
 namespace {
 
@@ -123,6 +127,8 @@ thread_local std::vector<std::string> t_ex_store;
 thread_local std::vector<const char*> t_ex_ty, t_ex_id, t_ex_addr;
 thread_local std::vector<size_t> t_ex_tylen, t_ex_idlen;
 thread_local std::vector<uint32_t> t_ex_rows, t_ex_node, t_ex_stamps;
+// rio_op_fold_loads' counters on their way to the device, and rio_op_get_object_load's copy of the load column
+thread_local std::vector<uint32_t> t_ld_hits, t_ld_col;
 
 // One single-object call waiting for its device round trip (see run_combined).
 // One single-object call waiting for its device round trip (see run_combined).  The struct is a cache line of its own: its
@@ -220,23 +226,46 @@ struct Shadow {
 // value, not one per call.  Stampers hold the shared side of the table lock, or count as in flight (their row id is theirs);
 // rio_op_expire reads the words under the exclusive side.  A row that reclaim() hands to another key keeps its stamp: stamps
 // only rise, on the host as on the device, so a recycled row counts as seen when its previous key was, until its own first call.
+//
+// Request counters (rio_op_set_load_tracking / rio_op_fold_loads) sit next to the stamps, in chunks installed the same way: the
+// sites that stamp a key are the sites that count a request for it, so stamp() does both and each is off behind one relaxed load.
+// A counter saturates at 2^32-1.  rio_op_fold_loads takes each word with an exchange: a request counted by a call in flight
+// (which holds no lock) lands in this fold or in the next one, never in both and never in neither.
 struct Stamps {
     static constexpr uint32_t kBits = 16;
-    std::atomic<uint32_t> now{0};
+    typedef std::atomic<std::atomic<uint32_t>*> Slot;
+    // the clock (low half; 0: stamping off) and the tracking switch (bit 32) in ONE word: with both off a call pays one relaxed
+    // load of it and nothing more, exactly what it paid for the clock alone
+    static constexpr uint64_t kTrack = 1ull << 32;
+    std::atomic<uint64_t> ctl{0};
+    void set_clock(uint32_t now) {
+        uint64_t c = ctl.load(std::memory_order_relaxed);
+        while (!ctl.compare_exchange_weak(c, (c & kTrack) | now, std::memory_order_relaxed)) {}
+    }
+    void set_tracking(bool on) {
+        if (on) ctl.fetch_or(kTrack, std::memory_order_relaxed);
+        else ctl.fetch_and(~kTrack, std::memory_order_relaxed);
+    }
     size_t nchunks = 0;
-    std::unique_ptr<std::atomic<std::atomic<uint32_t>*>[]> chunks;
+    std::unique_ptr<Slot[]> chunks, hit_chunks;
     void init(uint64_t max_objects) {
         nchunks = (size_t)((max_objects + (1u << kBits) - 1) >> kBits);
-        chunks.reset(new std::atomic<std::atomic<uint32_t>*>[nchunks ? nchunks : 1]);
-        for (size_t c = 0; c < (nchunks ? nchunks : 1); ++c) chunks[c].store(nullptr, std::memory_order_relaxed);
+        chunks.reset(new Slot[nchunks ? nchunks : 1]);
+        hit_chunks.reset(new Slot[nchunks ? nchunks : 1]);
+        for (size_t c = 0; c < (nchunks ? nchunks : 1); ++c) {
+            chunks[c].store(nullptr, std::memory_order_relaxed);
+            hit_chunks[c].store(nullptr, std::memory_order_relaxed);
+        }
     }
     ~Stamps() {
-        for (size_t c = 0; c < nchunks; ++c) delete[] chunks[c].load(std::memory_order_relaxed);
+        for (size_t c = 0; c < nchunks; ++c) {
+            delete[] chunks[c].load(std::memory_order_relaxed);
+            delete[] hit_chunks[c].load(std::memory_order_relaxed);
+        }
     }
-    void stamp(uint32_t row) {
-        const uint32_t t = now.load(std::memory_order_relaxed);
-        if (!t) return;
-        std::atomic<std::atomic<uint32_t>*>& slot = chunks[row >> kBits];
+    // the row's word of a column of chunks, its chunk installed (zero-filled) by whoever gets there first
+    static std::atomic<uint32_t>& word(Slot* col, uint32_t row) {
+        Slot& slot = col[row >> kBits];
         std::atomic<uint32_t>* ch = slot.load(std::memory_order_acquire);
         if (!ch) {
             std::atomic<uint32_t>* fresh = new std::atomic<uint32_t>[1u << kBits];
@@ -244,9 +273,52 @@ struct Stamps {
             if (slot.compare_exchange_strong(ch, fresh, std::memory_order_acq_rel, std::memory_order_acquire)) ch = fresh;
             else delete[] fresh;  // (somebody else's chunk is in: ch holds it)
         }
-        std::atomic<uint32_t>& w = ch[row & ((1u << kBits) - 1)];
+        return ch[row & ((1u << kBits) - 1)];
+    }
+    // a call answered or set an address for the row's key: one request counted (tracking on), the clock stamped (clock set)
+    void stamp(uint32_t row) {
+        const uint64_t c = ctl.load(std::memory_order_relaxed);
+        if (!c) return;
+        if (c & kTrack) {
+            std::atomic<uint32_t>& hc = word(hit_chunks.get(), row);
+            uint32_t cur = hc.load(std::memory_order_relaxed);
+            while (cur != 0xFFFFFFFFu && !hc.compare_exchange_weak(cur, cur + 1, std::memory_order_relaxed)) {}
+        }
+        const uint32_t t = (uint32_t)c;
+        if (!t) return;
+        std::atomic<uint32_t>& w = word(chunks.get(), row);
         uint32_t cur = w.load(std::memory_order_relaxed);
         while (cur < t && !w.compare_exchange_weak(cur, t, std::memory_order_relaxed)) {}
+    }
+    // the request counters of rows 0 .. n-1, each taken and left at 0; false: none was non-zero (out is not to be used)
+    bool take_hits(uint64_t n, std::vector<uint32_t>& out) {
+        bool any = false;
+        out.assign(n, 0u);
+        for (uint64_t r0 = 0; r0 < n; r0 += (1u << kBits)) {
+            std::atomic<uint32_t>* ch = hit_chunks[r0 >> kBits].load(std::memory_order_acquire);
+            if (!ch) continue;
+            const uint64_t k1 = std::min<uint64_t>(n - r0, 1u << kBits);
+            for (uint64_t k = 0; k < k1; ++k) {
+                if (!ch[k].load(std::memory_order_relaxed)) continue;
+                out[r0 + k] = ch[k].exchange(0u, std::memory_order_relaxed);
+                any = any || out[r0 + k] != 0;
+            }
+        }
+        return any;
+    }
+    // put counters taken by take_hits back (the device refused them): saturating, next to whatever was counted since
+    void give_back(const std::vector<uint32_t>& v) {
+        for (uint64_t r = 0; r < v.size(); ++r) {
+            if (!v[r]) continue;
+            std::atomic<uint32_t>& c = word(hit_chunks.get(), (uint32_t)r);
+            uint32_t cur = c.load(std::memory_order_relaxed);
+            while (!c.compare_exchange_weak(cur, cur + v[r] < cur ? 0xFFFFFFFFu : cur + v[r], std::memory_order_relaxed)) {}
+        }
+    }
+    // a row that changes hands starts at 0 requests
+    void clear_hits(uint32_t row) {
+        std::atomic<uint32_t>* ch = hit_chunks[row >> kBits].load(std::memory_order_acquire);
+        if (ch) ch[row & ((1u << kBits) - 1)].store(0u, std::memory_order_relaxed);
     }
     // the stamps of rows 0 .. n-1 (0: never stamped); false: nothing has ever been stamped (out is not written)
     bool gather(uint64_t n, std::vector<uint32_t>& out) const {
@@ -582,6 +654,7 @@ int reclaim(State* s) {
                     s->row_key[r] = std::pair<std::string, std::string>();
                     s->row_live[r] = 0;
                     s->shadow.erase((uint32_t)r);  // the row changes hands: what the shadow knew of it belonged to the old key
+                    s->seen.clear_hits((uint32_t)r);  // ... and so did the requests counted for it
                     s->free_rows.push_back((uint32_t)r);
                     gone.push_back((uint32_t)r);
                 }
@@ -1678,7 +1751,7 @@ int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const cha
 
 int rio_op_set_clock(rio_op_t* p, uint32_t now) {
     if (!p) return RIO_GP_EINVAL;
-    p->s->seen.now.store(now, std::memory_order_relaxed);
+    p->s->seen.set_clock(now);
     return RIO_GP_OK;
 }
 
@@ -1739,6 +1812,69 @@ int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64
     *object_ids = t_ex_id.data();
     *object_id_lens = t_ex_idlen.data();
     *addresses = t_ex_addr.data();
+    return RIO_GP_OK;
+}
+
+int rio_op_set_load_tracking(rio_op_t* p, int on) {
+    if (!p) return RIO_GP_EINVAL;
+    p->s->seen.set_tracking(on != 0);
+    return RIO_GP_OK;
+}
+
+int rio_op_fold_loads(rio_op_t* p, uint32_t keep, uint32_t gain, uint32_t min_load, uint32_t max_load, uint64_t* rows_changed,
+                      uint64_t* hits_folded) {
+    if (!p) return RIO_GP_EINVAL;
+    if (rows_changed) *rows_changed = 0;
+    if (hits_folded) *hits_folded = 0;
+    if (keep > 65536u || min_load > max_load) return fail(RIO_GP_EINVAL, "rio_op_fold_loads: keep above 65536 or min_load above max_load");
+    State* s = p->s;
+    // mu keeps every device change out; the write side of the table lock keeps the stampers that hold the shared side out.  A
+    // call in flight counts without a lock: take_hits takes each word with an exchange, so its request is in this fold or the next.
+    DevLock g(s);
+    std::lock_guard<TableLock> gi(s->imu);
+    int rc;
+    if ((rc = sync_device(s, true))) return rc;
+    if (!rio_gp_hits_merge || !rio_gp_load_fold) return fail(RIO_GP_EUPSTREAM, "dense layer has no measured load");
+    const uint64_t n = s->hi_rows;
+    if (s->seen.take_hits(n, t_ld_hits) && (rc = rio_gp_hits_merge(s->gp, n, t_ld_hits.data()))) {
+        s->seen.give_back(t_ld_hits);  // (nothing reached the device: the requests wait for the next fold)
+        return gp_fail(s, rc);
+    }
+    rio_gp_load_fold_stats st{};
+    if ((rc = rio_gp_load_fold(s->gp, keep, gain, min_load, max_load, &st))) return gp_fail(s, rc);
+    // Rows waiting on the free list belong to no key.  Each held load 1 and no request (reclaim() and this function leave them
+    // so), so the fold made clamp(keep == 65536 ? 1 : 0) of every one of them: where that is not 1 they are no key's change —
+    // they leave the count — and are put back to 1, what whoever gets one expects to find.
+    const uint32_t kept = keep == 65536u ? 1u : 0u;
+    const uint32_t free_load = kept < min_load ? min_load : (kept > max_load ? max_load : kept);
+    const uint64_t n_free = free_load != 1u ? s->free_rows.size() : 0;
+    if (rows_changed) *rows_changed = st.rows_changed - std::min<uint64_t>(n_free, st.rows_changed);
+    if (hits_folded) *hits_folded = st.hits_folded;
+    if (n_free) {  // (the fold has happened and is reported, whatever becomes of this call)
+        const std::vector<uint32_t> ones(n_free, 1u);
+        if ((rc = rio_gp_set_object_attrs(s->gp, n_free, s->free_rows.data(), ones.data(), nullptr))) return gp_fail(s, rc);
+    }
+    return RIO_GP_OK;  // (no address changed: the host shadow stands)
+}
+
+int rio_op_get_object_load(rio_op_t* p, const char* struct_name, size_t struct_name_len, const char* object_id,
+                           size_t object_id_len, uint32_t* load, int* found) {
+    if (!p || !struct_name || !object_id || !load || !found) return RIO_GP_EINVAL;
+    State* s = p->s;
+    *found = 0;
+    *load = 0;
+    DevLock g(s);
+    std::lock_guard<TableLock> gi(s->imu);
+    const auto it = s->rows.find(key_of(Part(struct_name, struct_name_len), Part(object_id, object_id_len)));
+    if (it == s->rows.end()) return RIO_GP_OK;
+    int rc;
+    if ((rc = sync_device(s, true))) return rc;
+    const uint64_t n = s->hi_rows;
+    t_ld_col.resize(n ? n : 1);
+    if ((rc = rio_gp_get_objects(s->gp, n, t_ld_col.data(), nullptr))) return gp_fail(s, rc);
+    *load = t_ld_col[it->second];
+    *found = 1;
+    if (t_ld_col.capacity() > (1u << 16)) std::vector<uint32_t>().swap(t_ld_col);  // (a big table's column does not stay with the thread)
     return RIO_GP_OK;
 }
 

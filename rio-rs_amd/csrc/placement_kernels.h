@@ -533,4 +533,15 @@ void launch_touch(u32* S, u64 n_obj, const u32* idx, u64 n, u32 epoch, DevStats*
 // S[r] = max(S[r], stamps ? stamps[r] : epoch) for r < rows (S is padded: whole quads are read and written)
 void launch_seen_merge(u32* S, const u32* stamps, u32 epoch, u64 rows, hipStream_t s);
 
+// --- measured load (rio_gp_hits_*, rio_gp_load_fold): a hit column H; the fold turns hits into loads, `used` following ---
+// H[idx[k]] = min(H[idx[k]] + (weight ? weight[k] : 1), 2^32-1) for k < n; entries >= n_obj are skipped and counted in st->err
+void launch_hits_add(u32* H, u64 n_obj, const u32* idx, const u32* weight, u64 n, DevStats* st, hipStream_t s);
+// H[r] = min(H[r] + counts[r], 2^32-1) for r < rows (H is padded: whole quads are read and written; counts: any alignment)
+void launch_hits_merge(u32* H, const u32* counts, u64 rows, hipStream_t s);
+// load[r] := clamp(floor(load[r] * keep / 65536) + H[r] * gain, lo, hi), H[r] := 0 for r < n; used != nullptr: used[A[r]] +=
+// new - old for A[r] < m (LDS accumulators for m <= kExpLdsNodes); the pass ADDS into st (5 u64 of device memory, zeroed by the
+// caller) = { rows changed, hits folded, load before, load after, largest load after }
+void launch_load_fold(u32* load, u32* H, const u32* A, u64 n, u32 keep, u32 gain, u32 lo, u32 hi, u32 m, u64* used, u64* st,
+                      hipStream_t s);
+
 }  // namespace riogp

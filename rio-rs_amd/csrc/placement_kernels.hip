@@ -7281,4 +7281,156 @@ void launch_seen_merge(u32* S, const u32* stamps, u32 epoch, u64 rows, hipStream
     hipLaunchKernelGGL(k_seen_merge, dim3(grid_for((rows + 3) / 4, 256, 8192)), dim3(256), 0, s, S, stamps, epoch, rows, vec);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Measured load (rio_gp_hits_*, rio_gp_load_fold; DESIGN.md section 2 rule 10): a hit column H, one u32 per row, and the pass
+// that turns hits into loads.
+//   k_hits_add    H[idx[k]] = min(H[idx[k]] + w[k], 2^32-1), a scatter: an atomic add, and where the word wrapped an atomic
+//                 maximum of 2^32-1 behind it.  Every wrap is followed by its thread's maximum, and after the last maximum any
+//                 further non-zero add wraps again: once all threads are through, the word holds the true sum if nothing ever
+//                 wrapped and 2^32-1 otherwise, in whatever order the entries ran.
+//   k_hits_merge  H[r] = min(H[r] + counts[r], 2^32-1) for r < rows, four rows per lane (k_seen_merge's shape, unaligned
+//                 `counts` included); a quad is stored only where it changed.
+//   k_load_fold   rows r < n: x = floor(load[r] * keep / 65536) + H[r] * gain in u64 (load * keep < 2^48 and its quotient
+//                 < 2^32; H * gain <= (2^32-1)^2 = 2^64 - 2^33 + 1: the sum stays below 2^64), load[r] := clamp(x, lo, hi),
+//                 H[r] := 0.  A load quad is stored where a load differs, an H quad where it held a hit; rows >= n keep both.
+//                 USED 0: `used` is not maintained (the committed column is not read).  USED 1: new - old of every row with
+//                 A[r] < m goes into a per-node LDS accumulator (m <= kExpLdsNodes) as a modular u64 delta and the non-zero
+//                 words to `used` at the end; USED 2: straight to `used` (k_exp_apply's two forms).  The statistics are
+//                 reduced per wave, then per workgroup in LDS, then one atomic per word and workgroup.
+//                 st = { rows changed, hits folded, load before, load after, largest load after }.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_hits_add(u32* __restrict__ H, u64 n_obj, const u32* __restrict__ idx,
+                                                  const u32* __restrict__ weight, u64 n, DevStats* st) {
+    u32 bad = 0;
+    for (u64 k = (u64)blockIdx.x * 256 + threadIdx.x; k < n; k += (u64)gridDim.x * 256) {
+        const u32 i = idx[k];
+        if (i >= n_obj) { ++bad; continue; }
+        const u32 w = weight ? weight[k] : 1u;
+        if (!w) continue;
+        const u32 old = atomicAdd(&H[i], w);
+        if (old + w < old) atomicMax(&H[i], 0xFFFFFFFFu);
+    }
+    if (bad) atomicAdd(&st->err, (u64)bad);
+}
+
+__device__ __forceinline__ u32 sat_add32(u32 a, u32 b) {
+    const u32 s = a + b;
+    return s < a ? 0xFFFFFFFFu : s;
+}
+
+__global__ __launch_bounds__(256) void k_hits_merge(u32* __restrict__ H, const u32* __restrict__ counts, u64 rows, u32 vec) {
+    for (u64 i0 = ((u64)blockIdx.x * 256 + threadIdx.x) * 4; i0 < rows; i0 += (u64)gridDim.x * 1024) {
+        const uint4 h = *reinterpret_cast<const uint4*>(H + i0);
+        uint4 c = make_uint4(0u, 0u, 0u, 0u);
+        if (vec && i0 + 4 <= rows) {
+            c = *reinterpret_cast<const uint4*>(counts + i0);
+        } else {
+            c.x = counts[i0];
+            if (i0 + 1 < rows) c.y = counts[i0 + 1];
+            if (i0 + 2 < rows) c.z = counts[i0 + 2];
+            if (i0 + 3 < rows) c.w = counts[i0 + 3];
+        }
+        const uint4 o = make_uint4(sat_add32(h.x, c.x), sat_add32(h.y, c.y), sat_add32(h.z, c.z), sat_add32(h.w, c.w));
+        if ((o.x != h.x) | (o.y != h.y) | (o.z != h.z) | (o.w != h.w)) *reinterpret_cast<uint4*>(H + i0) = o;
+    }
+}
+
+__device__ __forceinline__ u32 fold_one(u32 l, u32 h, u32 keep, u32 gain, u32 lo, u32 hi) {
+    const u64 x = (((u64)l * keep) >> 16) + (u64)h * gain;
+    return x < lo ? lo : (x > hi ? hi : (u32)x);
+}
+
+template <int USED>
+__global__ __launch_bounds__(256) void k_load_fold(u32* __restrict__ load, u32* __restrict__ H, const u32* __restrict__ A, u64 n,
+                                                   u32 keep, u32 gain, u32 lo, u32 hi, u32 m, u64* __restrict__ used,
+                                                   u64* __restrict__ st) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64* rel = reinterpret_cast<u64*>(smem);  // [m] new - old per node, modular (USED == 1 only)
+    __shared__ u64 ws[4];
+    __shared__ u32 wmax;
+    if (USED == 1)
+        for (u32 j = threadIdx.x; j < m; j += 256) rel[j] = 0;
+    if (threadIdx.x < 4) ws[threadIdx.x] = 0;
+    if (threadIdx.x == 4) wmax = 0;
+    __syncthreads();
+    u64 hits = 0, before = 0, after = 0;
+    u32 changed = 0, mx = 0;
+    for (u64 i0 = ((u64)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += (u64)gridDim.x * 1024) {
+        const uint4 lq = *reinterpret_cast<const uint4*>(load + i0);
+        const uint4 hq = *reinterpret_cast<const uint4*>(H + i0);
+        uint4 aq = make_uint4(kNone, kNone, kNone, kNone);
+        if (USED) aq = *reinterpret_cast<const uint4*>(A + i0);
+        const u32 l[4] = {lq.x, lq.y, lq.z, lq.w}, h[4] = {hq.x, hq.y, hq.z, hq.w}, a[4] = {aq.x, aq.y, aq.z, aq.w};
+        u32 nl[4], nh[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool in = i0 + j < n;  // (rows >= n keep their load and their hits)
+            nl[j] = in ? fold_one(l[j], h[j], keep, gain, lo, hi) : l[j];
+            nh[j] = in ? 0u : h[j];
+            if (in) {
+                hits += h[j];
+                before += l[j];
+                after += nl[j];
+                changed += nl[j] != l[j];
+                mx = nl[j] > mx ? nl[j] : mx;
+                if (USED && nl[j] != l[j] && a[j] < m) {
+                    const u64 d = (u64)nl[j] - (u64)l[j];
+                    if (USED == 1) atomicAdd(&rel[a[j]], d);
+                    else atomicAdd(&used[a[j]], d);
+                }
+            }
+        }
+        if ((nl[0] != l[0]) | (nl[1] != l[1]) | (nl[2] != l[2]) | (nl[3] != l[3]))
+            *reinterpret_cast<uint4*>(load + i0) = make_uint4(nl[0], nl[1], nl[2], nl[3]);
+        if ((nh[0] != h[0]) | (nh[1] != h[1]) | (nh[2] != h[2]) | (nh[3] != h[3]))
+            *reinterpret_cast<uint4*>(H + i0) = make_uint4(nh[0], nh[1], nh[2], nh[3]);
+    }
+    hits = wave_sum(hits);
+    before = wave_sum(before);
+    after = wave_sum(after);
+    changed = wave_sum32(changed);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const u32 o = (u32)__shfl_xor((int)mx, d, 64);
+        mx = o > mx ? o : mx;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (changed) atomicAdd(&ws[0], (u64)changed);
+        if (hits) atomicAdd(&ws[1], hits);
+        if (before) atomicAdd(&ws[2], before);
+        if (after) atomicAdd(&ws[3], after);
+        if (mx) atomicMax(&wmax, mx);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && ws[threadIdx.x]) atomicAdd(&st[threadIdx.x], ws[threadIdx.x]);
+    if (threadIdx.x == 4 && wmax) atomicMax(&st[4], (u64)wmax);
+    if (USED == 1)
+        for (u32 j = threadIdx.x; j < m; j += 256)
+            if (rel[j]) atomicAdd(&used[j], rel[j]);
+}
+
+void launch_hits_add(u32* H, u64 n_obj, const u32* idx, const u32* weight, u64 n, DevStats* st, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_hits_add, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, H, n_obj, idx, weight, n, st);
+}
+void launch_hits_merge(u32* H, const u32* counts, u64 rows, hipStream_t s) {
+    if (!rows) return;
+    const u32 vec = (reinterpret_cast<uintptr_t>(counts) & 15u) == 0 ? 1u : 0u;
+    hipLaunchKernelGGL(k_hits_merge, dim3(grid_for((rows + 3) / 4, 256, 8192)), dim3(256), 0, s, H, counts, rows, vec);
+}
+void launch_load_fold(u32* load, u32* H, const u32* A, u64 n, u32 keep, u32 gain, u32 lo, u32 hi, u32 m, u64* used, u64* st,
+                      hipStream_t s) {
+    if (!n) return;
+    const u64 quads = (n + 3) / 4;
+    if (!used)
+        hipLaunchKernelGGL(k_load_fold<0>, dim3(grid_for(quads, 256, 2048)), dim3(256), 0, s, load, H, A, n, keep, gain, lo, hi, m,
+                           used, st);
+    else if (m <= kExpLdsNodes)
+        hipLaunchKernelGGL(k_load_fold<1>, dim3(grid_for(quads, 256, 1024)), dim3(256), (size_t)m * sizeof(u64), s, load, H, A, n,
+                           keep, gain, lo, hi, m, used, st);
+    else
+        hipLaunchKernelGGL(k_load_fold<2>, dim3(grid_for(quads, 256, 2048)), dim3(256), 0, s, load, H, A, n, keep, gain, lo, hi, m,
+                           used, st);
+}
+
 }  // namespace riogp

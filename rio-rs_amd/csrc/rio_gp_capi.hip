@@ -524,6 +524,9 @@ struct rio_gp {
     u32* exp_S = nullptr;
     u32* exp_Smem = nullptr;  // S's memory, allocated; exp_S is set once it has been filled
     u64* exp_freed = nullptr;
+    // measured load (rio_gp_hits_*, rio_gp_load_fold), allocated on first use: the hit column H (cap_rows u32, 0 to begin with)
+    u32* hits_H = nullptr;
+    u32* hits_Hmem = nullptr;  // H's memory, allocated; hits_H is set once it has been filled
     std::vector<void*> allocs;
 };
 
@@ -2200,6 +2203,123 @@ int rio_gp_expire_dev(rio_gp_t* h, uint32_t cutoff, uint32_t* d_rows, uint32_t* 
     HIPCHK(h, e);
     *n_idle = total;
     if (load_freed) *load_freed = apply ? reinterpret_cast<const u64*>(h->h_chg)[1] : 0;
+    return RIO_GP_OK;
+}
+
+// ---- measured load ----------------------------------------------------------------------------
+
+// The hit column on first use (0 everywhere).
+static int hits_scratch(rio_gp* h) {
+    if (h->hits_H) return RIO_GP_OK;
+    int rc;
+    if (!h->hits_Hmem && (rc = dalloc(h, &h->hits_Hmem, h->cap_rows))) return rc;
+    launch_fill_u32(h->hits_Hmem, h->cap_rows, 0u, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->hits_H = h->hits_Hmem;  // (last: it is what says the state is complete)
+    return RIO_GP_OK;
+}
+// what every call of the family does first (one rule: no hit column on a handle of the row-sharded solve)
+static int hits_begin(rio_gp* h, const char* who) {
+    if (row_sharded(h)) return fail(h, RIO_GP_EINVAL, std::string(who) + ": not implemented on a handle of the row-sharded solve");
+    HIPCHK(h, hipSetDevice(h->device));
+    return hits_scratch(h);
+}
+
+// The hits calls write H and nothing else: no inputs_changed, `used` and the solve in flight stay as they are.
+int rio_gp_hits_add_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, const uint32_t* d_weight) {
+    if (!h || (n && !d_idx)) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = hits_begin(h, "rio_gp_hits_add_batch"))) return rc;
+    if (!n) return RIO_GP_OK;
+    if ((rc = zero_stats(h))) return rc;
+    launch_hits_add(h->hits_H, h->n, d_idx, d_weight, n, h->dstats, h->stream);
+    if ((rc = read_stats(h))) return rc;
+    if (h->h_stats[0].err) return fail(h, RIO_GP_EINVAL, "rio_gp_hits_add_batch: invalid entries were skipped");
+    return RIO_GP_OK;
+}
+
+int rio_gp_hits_add_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint32_t* weight) {
+    if (!h || (n && !idx)) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = hits_begin(h, "rio_gp_hits_add_batch"))) return rc;
+    for (uint64_t k = 0; k < n; ++k)
+        if (idx[k] >= h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_hits_add_batch: object index out of range");
+    if (!n) return RIO_GP_OK;
+    for (int q = 0; q < (weight ? 2 : 1); ++q)
+        if ((rc = ensure(h, h->stage[q], n * sizeof(u32)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, idx, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    if (weight) HIPCHK(h, hipMemcpyAsync(h->stage[1].p, weight, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    launch_hits_add(h->hits_H, h->n, (const u32*)h->stage[0].p, weight ? (const u32*)h->stage[1].p : nullptr, n, h->dstats,
+                    h->stream);  // (validated: nothing is counted)
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's arrays are read until here
+    return RIO_GP_OK;
+}
+
+int rio_gp_hits_merge_dev(rio_gp_t* h, uint64_t rows, const uint32_t* d_counts) {
+    if (!h || (rows && !d_counts)) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = hits_begin(h, "rio_gp_hits_merge"))) return rc;
+    if (rows > h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_hits_merge: rows exceeds the object table");
+    launch_hits_merge(h->hits_H, d_counts, rows, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return RIO_GP_OK;
+}
+
+int rio_gp_hits_merge(rio_gp_t* h, uint64_t rows, const uint32_t* counts) {
+    if (!h || (rows && !counts)) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = hits_begin(h, "rio_gp_hits_merge"))) return rc;
+    if (rows > h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_hits_merge: rows exceeds the object table");
+    if (!rows) return RIO_GP_OK;
+    if ((rc = ensure(h, h->stage[0], rows * sizeof(u32)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, counts, rows * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    launch_hits_merge(h->hits_H, (const u32*)h->stage[0].p, rows, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's array is read until here
+    return RIO_GP_OK;
+}
+
+int rio_gp_get_hits(rio_gp_t* h, uint64_t n, uint32_t* out) {
+    if (!h || !out) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = hits_begin(h, "rio_gp_get_hits"))) return rc;
+    if (n != h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_get_hits: n differs from the object table");
+    if (n) HIPCHK(h, hipMemcpyAsync(out, h->hits_H, n * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RIO_GP_OK;
+}
+
+// The fold is a rio_gp_set_object_attrs of every row's load: it drops an uncommitted solve and counts as a change of the inputs.
+// `used` follows inside the pass when it is valid (the pass then reads the committed column too); it stays invalid otherwise.
+int rio_gp_load_fold(rio_gp_t* h, uint32_t keep, uint32_t gain, uint32_t min_load, uint32_t max_load, rio_gp_load_fold_stats* st) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = hits_begin(h, "rio_gp_load_fold"))) return rc;
+    if (keep > 65536u) return fail(h, RIO_GP_EINVAL, "rio_gp_load_fold: keep above 65536");
+    if (min_load > max_load) return fail(h, RIO_GP_EINVAL, "rio_gp_load_fold: min_load above max_load");
+    u64* const used = h->used.live();
+    // the five statistics words are the first five of the handle's accumulators (zeroed here, read back into pinned memory)
+    if ((rc = zero_stats(h))) return rc;
+    inputs_changed(h);
+    launch_load_fold(h->load, h->hits_H, h->assign[h->cur], h->n, keep, gain, min_load, max_load, h->m, used,
+                     reinterpret_cast<u64*>(h->dstats), h->stream);
+    if ((rc = read_stats(h))) return rc;
+    const u64* const w = reinterpret_cast<const u64*>(h->h_stats);
+    if (st) {
+        st->rows_changed = w[0];
+        st->hits_folded = w[1];
+        st->load_before = w[2];
+        st->load_after = w[3];
+        st->max_load_after = (uint32_t)w[4];
+        st->reserved = 0;
+    }
     return RIO_GP_OK;
 }
 

@@ -60,6 +60,12 @@ class Stats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
+class LoadFoldStats(C.Structure):
+    """rio_gp_load_fold_stats."""
+    _fields_ = [(k, C.c_uint64) for k in ("rows_changed", "hits_folded", "load_before", "load_after")] + [
+        (k, C.c_uint32) for k in ("max_load_after", "reserved")]
+
+
 class RebalanceCfg(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("rounds", C.c_uint32), ("max_moves", C.c_uint64), ("target", C.c_void_p)]
 
@@ -216,6 +222,11 @@ def _load(lab):
             getattr(L, nm).argtypes = [_vp, C.c_uint64, _vp]
         for nm in ("rio_gp_expire", "rio_gp_expire_dev"):
             getattr(L, nm).argtypes = [_vp, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        for nm in ("rio_gp_hits_add_batch", "rio_gp_hits_add_batch_dev"):
+            getattr(L, nm).argtypes = [_vp, C.c_uint64, _vp, _vp]
+        for nm in ("rio_gp_hits_merge", "rio_gp_hits_merge_dev", "rio_gp_get_hits"):
+            getattr(L, nm).argtypes = [_vp, C.c_uint64, _vp]
+        L.rio_gp_load_fold.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(LoadFoldStats)]
         L.rio_gp_remap_nodes.argtypes = [_vp, C.c_uint32, _vp, C.POINTER(C.c_uint64)]
         if lab:
             L.rio_gp_debug_set_scan_nt.argtypes = [C.c_int]
@@ -629,6 +640,51 @@ class GpuPlacement:
                                    C.byref(n) if want_n_idle else None, None)
         return rc, int(n.value)
 
+    # -- measured load --
+    def hits_add(self, idx, weight=None):
+        """rio_gp_hits_add_batch: H[idx[k]] = min(H[idx[k]] + weight[k], 2^32-1); weight None: 1 each."""
+        idx = _u32(idx)
+        w = None if weight is None else _u32(weight)
+        self._chk(self._L.rio_gp_hits_add_batch(self._h, len(idx), _ptr(idx), None if w is None else _ptr(w)))
+
+    def hits_add_raw(self, idx, n=None, weight=None):
+        """One rio_gp_hits_add_batch call as given (idx None: a NULL pointer with n entries): rc; no exception."""
+        idx = None if idx is None else _u32(idx)
+        w = None if weight is None else _u32(weight)
+        return self._L.rio_gp_hits_add_batch(self._h, len(idx) if n is None else int(n), None if idx is None else _ptr(idx),
+                                             None if w is None else _ptr(w))
+
+    def hits_add_dev(self, d_idx, n, d_weight=None):
+        """rio_gp_hits_add_batch_dev: the same from device arrays of n entries (ints, e.g. a torch tensor's data_ptr())."""
+        self._chk(self._L.rio_gp_hits_add_batch_dev(self._h, int(n), _vp(d_idx) if d_idx else None,
+                                                    _vp(d_weight) if d_weight else None))
+
+    def hits_merge(self, counts):
+        """rio_gp_hits_merge: H[r] = min(H[r] + counts[r], 2^32-1) for r < len(counts) <= n."""
+        counts = _u32(counts)
+        self._chk(self._L.rio_gp_hits_merge(self._h, len(counts), _ptr(counts)))
+
+    def hits_merge_dev(self, d_counts, rows):
+        """rio_gp_hits_merge_dev: the same from a device array of `rows` counters (any 4-byte alignment)."""
+        self._chk(self._L.rio_gp_hits_merge_dev(self._h, int(rows), _vp(d_counts) if d_counts else None))
+
+    def get_hits(self):
+        """rio_gp_get_hits: the hit column H[0 .. n-1] (uint32)."""
+        out = np.empty(self.num_objects, np.uint32)
+        self._chk(self._L.rio_gp_get_hits(self._h, len(out), _ptr(out)))
+        return out
+
+    def load_fold(self, keep, gain, min_load=0, max_load=0xFFFFFFFF):
+        """rio_gp_load_fold: load := clamp(floor(load * keep / 65536) + H * gain, min_load, max_load), H := 0 for every row
+        r < n.  Returns the statistics as a dict."""
+        st = LoadFoldStats()
+        self._chk(self._L.rio_gp_load_fold(self._h, int(keep), int(gain), int(min_load), int(max_load), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in LoadFoldStats._fields_ if k != "reserved"}
+
+    def load_fold_raw(self, keep, gain, min_load, max_load):
+        """One rio_gp_load_fold call as given, without statistics: rc; no exception."""
+        return self._L.rio_gp_load_fold(self._h, int(keep), int(gain), int(min_load), int(max_load), None)
+
     # -- policy --
     def place_pending(self, idx, requester):
         idx, requester = _u32(idx), _u32(requester)
@@ -847,6 +903,7 @@ def _oplib():
                                        C.POINTER(C.POINTER(C.c_char_p))]
         bind_op_changes(L)
         bind_op_expire(L)
+        bind_op_loads(L)
         L.rio_op_dense.argtypes = [_vp]
         L.rio_op_dense.restype = _vp
         L.rio_op_invalidate_cache.argtypes = [_vp]
@@ -900,6 +957,32 @@ def op_expire(L, h, cutoff, max_objects=None):
     out = [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(),
             None if ad[k] is None else ad[k].decode()) for k in range(n.value)]
     return rc, out, int(idle.value)
+
+
+def bind_op_loads(L):
+    """argtypes of rio_op_set_load_tracking / rio_op_fold_loads / rio_op_get_object_load on a library that has them (the
+    product, or a stub-linked test build)."""
+    L.rio_op_set_load_tracking.argtypes = [_vp, C.c_int]
+    L.rio_op_fold_loads.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64)]
+    L.rio_op_get_object_load.argtypes = [_vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_int)]
+
+
+def op_fold_loads(L, h, keep, gain, min_load=0, max_load=0xFFFFFFFF):
+    """One rio_op_fold_loads call on handle h of library L: (rc, rows_changed, hits_folded)."""
+    ch, hf = C.c_uint64(0), C.c_uint64(0)
+    rc = L.rio_op_fold_loads(h, int(keep), int(gain), int(min_load), int(max_load), C.byref(ch), C.byref(hf))
+    return rc, int(ch.value), int(hf.value)
+
+
+def op_get_object_load(L, h, struct_name, object_id):
+    """One rio_op_get_object_load call: (rc, load or None for a key never seen).  Keys are str or bytes (NUL bytes allowed)."""
+    ty = struct_name.encode() if isinstance(struct_name, str) else struct_name
+    oid = object_id.encode() if isinstance(object_id, str) else object_id
+    load, found = C.c_uint32(0), C.c_int(0)
+    rc = L.rio_op_get_object_load(h, ty, len(ty), oid, len(oid), C.byref(load), C.byref(found))
+    return rc, (int(load.value) if found.value else None)
 
 
 def _cstrs(items):
@@ -1132,6 +1215,23 @@ class GpuObjectPlacement:
         rc, out, idle = op_expire(_oplib(), self._h, cutoff, max_objects)
         self._chk(rc)
         return out, idle
+
+    def set_load_tracking(self, on):
+        """rio_op_set_load_tracking: count one request per call that answers or sets an address for a key (off at creation)."""
+        self._chk(_oplib().rio_op_set_load_tracking(self._h, 1 if on else 0))
+
+    def fold_loads(self, keep, gain, min_load=0, max_load=0xFFFFFFFF):
+        """rio_op_fold_loads: (rows_changed, hits_folded) — every key's load becomes clamp(floor(load * keep / 65536) +
+        requests * gain, min_load, max_load) and its request counter starts again at 0."""
+        rc, ch, hf = op_fold_loads(_oplib(), self._h, keep, gain, min_load, max_load)
+        self._chk(rc)
+        return ch, hf
+
+    def get_object_load(self, struct_name, object_id):
+        """rio_op_get_object_load: the device's load of one key; None for a key never seen."""
+        rc, load = op_get_object_load(_oplib(), self._h, struct_name, object_id)
+        self._chk(rc)
+        return load
 
     def objects_on_server(self, address):
         """rio_op_objects_on_server: every (struct_name, object_id) placed on `address` (the reverse index; [] for an address

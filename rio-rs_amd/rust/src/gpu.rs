@@ -101,6 +101,9 @@ extern "C" {
     fn rio_op_expire(p: *mut c_void, cutoff: u32, max_objects_out: u64, n_out: *mut u64, n_idle: *mut u64,
                      tys: *mut *const *const c_char, ty_lens: *mut *const usize, ids: *mut *const *const c_char,
                      id_lens: *mut *const usize, addrs: *mut *const *const c_char) -> c_int;
+    fn rio_op_set_load_tracking(p: *mut c_void, on: c_int) -> c_int;
+    fn rio_op_fold_loads(p: *mut c_void, keep: u32, gain: u32, min_load: u32, max_load: u32, rows_changed: *mut u64,
+                         hits_folded: *mut u64) -> c_int;
     fn rio_op_tick(p: *mut c_void, stats: *mut RioGpStats) -> c_int;
     fn rio_op_snapshot(p: *mut c_void, n_out: *mut u64, tys: *mut *const *const c_char, ids: *mut *const *const c_char,
                        addrs: *mut *const *const c_char) -> c_int;
@@ -322,6 +325,21 @@ impl GpuObjectPlacement {
             Ok((out, idle))
         })
         .await
+    }
+
+    /// Measured load: while it is on, every call that answers or sets an address for an object counts one request for it
+    /// (the reference's `ObjectPlacementItem`, rio-rs/src/object_placement/mod.rs:23-24, has no load at all).  Off at creation.
+    pub fn set_load_tracking(&self, on: bool) -> Result<(), ObjectPlacementError> {
+        check(unsafe { rio_op_set_load_tracking(self.inner.0, on as c_int) }, self)
+    }
+
+    /// Folds the requests counted since the last call into every object's load:
+    /// `load = clamp(load * keep / 65536 + requests * gain, min_load, max_load)`, `keep <= 65536`.  Returns
+    /// `(rows_changed, hits_folded)`.  No address changes; `tick` and `rebalance` act on the new loads.
+    pub fn fold_loads(&self, keep: u32, gain: u32, min_load: u32, max_load: u32) -> Result<(u64, u64), ObjectPlacementError> {
+        let (mut changed, mut hits) = (0u64, 0u64);
+        check(unsafe { rio_op_fold_loads(self.inner.0, keep, gain, min_load, max_load, &mut changed, &mut hits) }, self)?;
+        Ok((changed, hits))
     }
 
     /// Eager rebalance (the batched form of the lazy `clean_server` + first-touch path):
