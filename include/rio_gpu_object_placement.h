@@ -240,6 +240,28 @@ int rio_op_fold_loads(rio_op_t* p, uint32_t keep, uint32_t gain, uint32_t min_lo
 int rio_op_get_object_load(rio_op_t* p, const char* struct_name, size_t struct_name_len, const char* object_id,
                            size_t object_id_len, uint32_t* load, int* found);
 
+/* Hot objects (rio_gp_top_rows, DESIGN.md section 2 rule 11): the placed keys with the largest loads, on one server or on all of
+ * them — the ORDER BY load DESC LIMIT k of the stores the reference can sit on, whose ObjectPlacementItem
+ * (object_placement/mod.rs:23-24) has no load to order by.
+ *   - Selection: placed keys whose load is >= min_load; address != NULL: only those on that server.  By load only: the request
+ *     counters of rio_op_set_load_tracking live on the host until rio_op_fold_loads, so the load after the last fold is the
+ *     measured quantity.  An address never seen gives 0 objects and RIO_GP_OK.
+ *   - Order: load descending; keys of equal load in the order of their rows (the order in which keys first reached the table).
+ *   - *n_candidates (may be NULL) = every key selected, listed or not; *n_out = keys listed = min(*n_candidates,
+ *     max_objects_out).  max_objects_out == 0 only counts (loads may then be NULL); above RIO_GP_TOP_MAX: RIO_GP_EINVAL.
+ *     (A placed row has a key in this layer.  Were the dense layer ever to list one without, it is left out and *n_out falls
+ *     short.)
+ *   - Output: keys with their lengths (a key may hold NUL bytes), addresses as in rio_op_snapshot (NULL for a node id without an
+ *     address); the string arrays belong to the calling thread until its next call of this function.  loads is the caller's
+ *     array of max_objects_out entries.
+ *   - It holds the device lock and the shared side of the table lock, as rio_op_objects_on_server does; it stamps nothing,
+ *     counts no request and leaves the host shadow alone.
+ *   - A dense layer without rio_gp_top_rows: RIO_GP_EUPSTREAM. */
+int rio_op_hottest_objects(rio_op_t* p, const char* address /* NULL: every server */, uint32_t min_load, uint64_t max_objects_out,
+                           uint64_t* n_out, uint64_t* n_candidates, const char* const** struct_names,
+                           const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens,
+                           const char* const** addresses, uint32_t* loads /* caller's, max_objects_out entries */);
+
 /* Keys with their lengths.  ObjectId(String, String) (service_object.rs:19-26) holds any Rust string, a NUL byte included;
  * the entry points above take NUL-terminated strings and would cut such a key short.  These take struct_name / object_id
  * as (pointer, length) and are otherwise the same calls (the Rust adapter binds THESE: rio-rs_amd/rust/src/gpu.rs).

@@ -449,6 +449,43 @@ int rio_gp_get_hits(rio_gp_t* h, uint64_t n, uint32_t* out);
 int rio_gp_load_fold(rio_gp_t* h, uint32_t keep, uint32_t gain, uint32_t min_load, uint32_t max_load,
                      rio_gp_load_fold_stats* st /* may be NULL */);
 
+/* ---- hot-object report: the k heaviest rows ---------------------------------------------------- */
+
+/* "What makes node X hot", "which objects are the hottest": the ORDER BY load DESC LIMIT k that every store the reference can sit
+ * on answers (its ObjectPlacementItem, rio-rs/src/object_placement/mod.rs:23-24, has no load to order by: load is this library's
+ * extension, and so is this report).  DESIGN.md section 2 rule 11 (frozen; tests/spec_top.py restates it):
+ *   - A is the column rio_gp_get_assign returns at the point of the call; K[r] = load[r], or H[r] (the hit column of
+ *     rio_gp_hits_*) under RIO_GP_TOP_BY_HITS.  On a handle that never called the hits family H is all zero, and this call does
+ *     not allocate it.
+ *   - Row r is a CANDIDATE iff r < n and K[r] >= min_key and, under RIO_GP_TOP_PLACED, A[r] != RIO_GP_NONE (raw values: ids >= m
+ *     count as placed, as in rule 9) and, under RIO_GP_TOP_ON_NODE, A[r] == node.  Affinity and lifecycle state are not
+ *     consulted; rows >= n are never candidates.
+ *   - *n_candidates = every candidate, listed or not; *key_sum = the sum of K over all candidates (fewer than 2^31 rows times
+ *     2^32: it cannot overflow).
+ *   - The listing is the first L = min(*n_candidates, cap) candidates in the total order (K descending, then r ascending):
+ *     out_rows[k] = r, out_key[k] = K[r], out_node[k] = A[r].  One fixed listing: ties at the cut go to the lowest rows.  Entries
+ *     from L on are not written.
+ *   - out_rows and out_key are given together or not at all; without them cap must be 0 (count only) and out_node NULL.
+ *   - RIO_GP_EINVAL: cap > RIO_GP_TOP_MAX, an unknown flag bit, RIO_GP_TOP_ON_NODE with node >= m (node is ignored without the
+ *     flag), n_candidates == NULL, a handle of the row-sharded solve (rio_gp_shard_*, rio_gp_p2p_*).
+ *   - Read-only: the table, `used`, H, S, the change feed's checkpoint, an uncommitted rio_gp_solve (it stays committable) and
+ *     the quiet and chained tick state are as they were.  Like rio_gp_changes it orders itself behind rio_gp_tick_async work in
+ *     flight.
+ *   - Memory: about 100 KB of device scratch (histograms, the selected rows, the listing), 48 KB of pinned host memory and the
+ *     change feed's per-tile counts (4 B per 1 024 rows), allocated by the first call; a handle that never calls pays nothing.
+ *   - Cost: an exact radix select on the device: three histogram passes over K (11 / 11 / 10 bits; the second and third are
+ *     skipped when everything fits the listing), one collecting pass and a pass over the tiles that hold a tie at the cut, each
+ *     4 B per row (8 B under a filter flag, which reads A too); then at most 4 096 rows are sorted and come back.  The _dev form
+ *     takes device arrays of cap entries; both forms wait once. */
+#define RIO_GP_TOP_BY_HITS 1u /* key = H[r]; without it key = load[r] */
+#define RIO_GP_TOP_PLACED 2u  /* only rows with A[r] != RIO_GP_NONE */
+#define RIO_GP_TOP_ON_NODE 4u /* only rows with A[r] == node */
+#define RIO_GP_TOP_MAX 4096u
+int rio_gp_top_rows(rio_gp_t* h, uint32_t flags, uint32_t node, uint32_t min_key, uint32_t* out_rows, uint32_t* out_key,
+                    uint32_t* out_node /* may be NULL */, uint64_t cap, uint64_t* n_candidates, uint64_t* key_sum /* may be NULL */);
+int rio_gp_top_rows_dev(rio_gp_t* h, uint32_t flags, uint32_t node, uint32_t min_key, uint32_t* d_rows, uint32_t* d_key,
+                        uint32_t* d_node /* may be NULL */, uint64_t cap, uint64_t* n_candidates, uint64_t* key_sum /* may be NULL */);
+
 /* ---- the placement policy, batched ------------------------------------------------------ */
 
 /* Service::get_or_create_placement + check_address_mismatch (service.rs:193-298) for a batch

@@ -73,6 +73,9 @@ extern "C" int rio_gp_expire(rio_gp_t* h, uint32_t cutoff, uint32_t* out_rows, u
 extern "C" int rio_gp_hits_merge(rio_gp_t* h, uint64_t rows, const uint32_t* counts) __attribute__((weak));
 extern "C" int rio_gp_load_fold(rio_gp_t* h, uint32_t keep, uint32_t gain, uint32_t min_load, uint32_t max_load,
                                 rio_gp_load_fold_stats* st) __attribute__((weak));
+// Weak for the same reason: the hot-object report (rio_op_hottest_objects reports RIO_GP_EUPSTREAM without it).
+extern "C" int rio_gp_top_rows(rio_gp_t* h, uint32_t flags, uint32_t node, uint32_t min_key, uint32_t* out_rows, uint32_t* out_key,
+                               uint32_t* out_node, uint64_t cap, uint64_t* n_candidates, uint64_t* key_sum) __attribute__((weak));
 
 namespace {
 
@@ -129,6 +132,11 @@ thread_local std::vector<size_t> t_ex_tylen, t_ex_idlen;
 thread_local std::vector<uint32_t> t_ex_rows, t_ex_node, t_ex_stamps;
 // rio_op_fold_loads' counters on their way to the device, and rio_op_get_object_load's copy of the load column
 thread_local std::vector<uint32_t> t_ld_hits, t_ld_col;
+// rio_op_hottest_objects' result: the strings stay valid until the calling thread's next call of that function
+thread_local std::vector<std::string> t_hot_store;
+thread_local std::vector<const char*> t_hot_ty, t_hot_id, t_hot_addr;
+thread_local std::vector<size_t> t_hot_tylen, t_hot_idlen;
+thread_local std::vector<uint32_t> t_hot_rows, t_hot_key, t_hot_node;
 
 // One single-object call waiting for its device round trip (see run_combined).
 // One single-object call waiting for its device round trip (see run_combined).  The struct is a cache line of its own: its
@@ -1875,6 +1883,80 @@ int rio_op_get_object_load(rio_op_t* p, const char* struct_name, size_t struct_n
     *load = t_ld_col[it->second];
     *found = 1;
     if (t_ld_col.capacity() > (1u << 16)) std::vector<uint32_t>().swap(t_ld_col);  // (a big table's column does not stay with the thread)
+    return RIO_GP_OK;
+}
+
+int rio_op_hottest_objects(rio_op_t* p, const char* address, uint32_t min_load, uint64_t max_objects_out, uint64_t* n_out,
+                           uint64_t* n_candidates, const char* const** struct_names, const size_t** struct_name_lens,
+                           const char* const** object_ids, const size_t** object_id_lens, const char* const** addresses,
+                           uint32_t* loads) {
+    if (!p || !n_out || !struct_names || !struct_name_lens || !object_ids || !object_id_lens || !addresses) return RIO_GP_EINVAL;
+    if (max_objects_out && !loads) return RIO_GP_EINVAL;
+    State* s = p->s;
+    t_hot_store.clear();
+    t_hot_ty.clear(); t_hot_id.clear(); t_hot_addr.clear(); t_hot_tylen.clear(); t_hot_idlen.clear();
+    *n_out = 0;
+    if (n_candidates) *n_candidates = 0;
+    if (max_objects_out > RIO_GP_TOP_MAX) return fail(RIO_GP_EINVAL, "rio_op_hottest_objects: max_objects_out above RIO_GP_TOP_MAX");
+    uint64_t listed = 0;
+    {
+        // rio_op_objects_on_server's locks: mu keeps every device change out and the shared side of the table lock keeps the
+        // rows with their keys, so no row changes hands between the dense call and the translation.  Nothing is stamped or
+        // counted, and the host shadow is not consulted: the loads are the device's.
+        DevLock g(s);
+        std::shared_lock<TableLock> gi(s->imu);
+        int rc;
+        if ((rc = sync_device(s, true))) return rc;
+        if (!rio_gp_top_rows) return fail(RIO_GP_EUPSTREAM, "dense layer has no hot-object report");
+        uint32_t flags = RIO_GP_TOP_PLACED, node = 0;
+        bool known = true;
+        if (address) {
+            const auto it = s->nodes.find(address);
+            known = it != s->nodes.end();  // (an address never seen holds nothing: 0 objects)
+            if (known) {
+                flags |= RIO_GP_TOP_ON_NODE;
+                node = it->second;
+            }
+        }
+        if (known) {
+            const uint64_t cap = max_objects_out;
+            uint64_t cand = 0;
+            if (!cap) {
+                rc = rio_gp_top_rows(s->gp, flags, node, min_load, nullptr, nullptr, nullptr, 0, &cand, nullptr);
+            } else {
+                t_hot_rows.resize(cap); t_hot_key.resize(cap); t_hot_node.resize(cap);
+                rc = rio_gp_top_rows(s->gp, flags, node, min_load, t_hot_rows.data(), t_hot_key.data(), t_hot_node.data(), cap, &cand,
+                                     nullptr);
+            }
+            if (rc) return gp_fail(s, rc);
+            if (n_candidates) *n_candidates = cand;
+            const uint64_t got = std::min(cand, cap);
+            const uint32_t m = (uint32_t)s->node_addr.size();
+            for (uint64_t k = 0; k < got; ++k) {
+                const uint32_t row = t_hot_rows[k];
+                // (a placed row has a key: rows on the free list are un-placed.  Were one ever not to, it is left out of the
+                //  listing, which then falls short of min(*n_candidates, max_objects_out).)
+                if (row >= s->row_live.size() || !s->row_live[row]) continue;
+                // copies: keys can be reclaimed as soon as the locks are released
+                t_hot_store.push_back(s->row_key[row].first);
+                t_hot_store.push_back(s->row_key[row].second);
+                t_hot_addr.push_back(t_hot_node[k] < m ? s->node_addr[t_hot_node[k]].c_str() : nullptr);
+                loads[listed++] = t_hot_key[k];
+            }
+        }
+    }
+    for (size_t k = 0; k + 1 < t_hot_store.size(); k += 2) {
+        t_hot_ty.push_back(t_hot_store[k].data());
+        t_hot_tylen.push_back(t_hot_store[k].size());
+        t_hot_id.push_back(t_hot_store[k + 1].data());
+        t_hot_idlen.push_back(t_hot_store[k + 1].size());
+    }
+    *n_out = listed;
+    *struct_names = t_hot_ty.data();
+    *struct_name_lens = t_hot_tylen.data();
+    *object_ids = t_hot_id.data();
+    *object_id_lens = t_hot_idlen.data();
+    *addresses = t_hot_addr.data();
     return RIO_GP_OK;
 }
 

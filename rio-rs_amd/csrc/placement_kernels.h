@@ -2,6 +2,7 @@
 // kernels (placement_kernels.hip).  Internal; the public boundary is include/rio_gpu_placement.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace riogp {
@@ -543,5 +544,26 @@ void launch_hits_merge(u32* H, const u32* counts, u64 rows, hipStream_t s);
 // caller) = { rows changed, hits folded, load before, load after, largest load after }
 void launch_load_fold(u32* load, u32* H, const u32* A, u64 n, u32 keep, u32 gain, u32 lo, u32 hi, u32 m, u64* used, u64* st,
                       hipStream_t s);
+
+// --- hot-object report (rio_gp_top_rows): the first `cap` candidates by (K descending, row ascending), an exact radix select ---
+constexpr u32 kTopMax = 4096;   // = RIO_GP_TOP_MAX: rows of one listing (their composites sort in 32 KiB of LDS)
+constexpr u32 kTopBins = 2048;  // bins of one digit's histogram (11 / 11 / 10 bits from the top)
+constexpr u32 kTopPlaced = 2u, kTopOnNode = 4u;  // = RIO_GP_TOP_PLACED / RIO_GP_TOP_ON_NODE (the key column is the caller's choice)
+// The call's device state, one allocation.  Everything in front of `pairs` is zeroed by every call.
+struct TopScratch {
+    u64 n_cand, key_sum;                             // pass 0: the candidates and the sum of their keys
+    u32 prefix, want, all, cursor, tie_total, pad[3];  // the digits chosen so far (at the end: T) / the rank left (at the end: t)
+    u32 hist[3][kTopBins];
+    u64 pairs[kTopMax];     // (K << 32) | ~row of the rows to list, unordered
+    u64 hdr[2];             // what the host reads back: n_candidates, key_sum ...
+    u32 out[3 * kTopMax];   // ... and, in the host-pointer form, rows | keys | nodes of `cap` entries each right behind them
+};
+constexpr u64 kTopZeroWords = 4 + 8 + 3 * (u64)kTopBins;
+static_assert(kTopZeroWords * sizeof(u32) == offsetof(TopScratch, pairs), "TopScratch: the zeroed head ends where pairs begins");
+// K: the key column (nullptr: every key is 0), A: the committed column; filt: kTopPlaced | kTopOnNode; cnt / gsum: the feed's
+// per-tile counts and workgroup sums (launch_chg_count's).  rows / key: cap entries; nodes: cap entries or nullptr.  sc->hdr holds
+// n_candidates and key_sum when the stream has run.
+void launch_top_rows(const u32* K, const u32* A, u64 n, u32 min_key, u32 filt, u32 node, u32 cap, TopScratch* sc, u32* cnt,
+                     u32* gsum, u32* rows, u32* key, u32* nodes, hipStream_t s);
 
 }  // namespace riogp

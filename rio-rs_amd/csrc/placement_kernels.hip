@@ -7433,4 +7433,322 @@ void launch_load_fold(u32* load, u32* H, const u32* A, u64 n, u32 keep, u32 gain
                            used, st);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Hot-object report (rio_gp_top_rows; DESIGN.md section 2 rule 11): the first `cap` candidates in the order (K descending, row
+// ascending), K = load or H.  An exact radix select over the key, then a sort of what was selected; every pass streams K (and A
+// under a filter flag) over the change feed's plan: a wave per tile of kChgTile rows, a dwordx4 load per lane, column and step.
+//   k_top_hist<FILT, PASS>  the candidates whose key agrees with the digits chosen so far count their next digit (11 / 11 / 10
+//                bits from the top) in an LDS histogram; a wave whose candidates of a step all share a digit (small loads: the
+//                top digits are 0 for everybody) adds once.  The non-zero bins go to the global histogram with vector atomics.
+//                Pass 0 also sums the candidates and their keys.
+//   k_top_select one workgroup, between the passes: n_candidates <= cap ends the selection (`all`: everything is listed);
+//                otherwise the digit whose bin holds rank `want` from the top, and the rank that remains inside that bin.  After
+//                the third digit `prefix` is the threshold T and `want` the number t of rows with K == T to list.
+//   k_top_collect  candidates with K > T (all of them under `all`) take a slot of `pairs` through an atomic cursor — their
+//                order does not matter — and the candidates with K == T are counted per tile and workgroup (k_chg_count's shape).
+//   k_chg_scan   the feed's one-workgroup scan of the workgroup sums.
+//   k_top_ties   k_chg_list's ranking over the tiles that hold a tie: the first t of them, by row, go behind the cap - t others.
+//   k_top_sort   one workgroup sorts the at most 4 096 composites (K << 32) | ~row, descending, in LDS (a bitonic network over the
+//                next power of two) and writes rows, keys and A[row]: the output does not depend on the order of any atomic.
+// No workgroup waits for another; the host enqueues all of it and waits once.
+// ------------------------------------------------------------------------------------------------
+template <bool FILT>
+__device__ __forceinline__ void top_load(const u32* __restrict__ K, const u32* __restrict__ A, u64 lo, u32 lane, uint4 (&k)[4],
+                                         uint4 (&a)[4]) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const u64 i0 = lo + (u64)s * 256 + lane * 4;
+        k[s] = K ? *reinterpret_cast<const uint4*>(K + i0) : make_uint4(0u, 0u, 0u, 0u);  // (no hit column yet: every key is 0)
+        if (FILT) a[s] = *reinterpret_cast<const uint4*>(A + i0);
+    }
+}
+// bit j: row i0 + j is a candidate (rows >= n never are)
+template <bool FILT>
+__device__ __forceinline__ u32 top_flags(const uint4& k, const uint4& a, u64 i0, u64 n, u32 min_key, u32 filt, u32 node) {
+    const u32 kv[4] = {k.x, k.y, k.z, k.w}, av[4] = {a.x, a.y, a.z, a.w};
+    u32 f = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        bool c = i0 + j < n && kv[j] >= min_key;
+        if (FILT) c = c && (!(filt & kTopPlaced) || av[j] != kNone) && (!(filt & kTopOnNode) || av[j] == node);
+        f |= (u32)c << j;
+    }
+    return f;
+}
+
+template <bool FILT, int PASS>
+__global__ __launch_bounds__(kChgWaves * 64, 8) void k_top_hist(const u32* __restrict__ K, const u32* __restrict__ A, const ChgPlan p,
+                                                              u32 min_key, u32 filt, u32 node, TopScratch* __restrict__ sc) {
+    __shared__ u32 h[kTopBins];
+    __shared__ u64 ws[2];
+    if (PASS && sc->all) return;  // (uniform: the selection ended after pass 0)
+    for (u32 b = threadIdx.x; b < kTopBins; b += kChgWaves * 64) h[b] = 0;
+    if (threadIdx.x < 2) ws[threadIdx.x] = 0;
+    const u32 prefix = PASS ? sc->prefix : 0u;
+    __syncthreads();
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u32 t0 = blockIdx.x * p.tpg, t1 = t0 + p.tpg < p.nt ? t0 + p.tpg : p.nt;
+    u64 ksum = 0;
+    u32 cands = 0;
+    for (u32 t = t0 + wv; t < t1; t += kChgWaves) {  // wave-uniform
+        const u64 lo = (u64)t * kChgTile;
+        uint4 k[4], a[4];
+        top_load<FILT>(K, A, lo, lane, k, a);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const u32 f = top_flags<FILT>(k[s], a[s], lo + (u64)s * 256 + lane * 4, p.n, min_key, filt, node);
+            const u32 kv[4] = {k[s].x, k[s].y, k[s].z, k[s].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const u32 key = kv[j];
+                bool on = (f >> j) & 1u;
+                if (PASS == 0 && on) {
+                    ++cands;
+                    ksum += key;
+                }
+                if (PASS == 1) on = on && (key >> 21) == prefix;
+                if (PASS == 2) on = on && (key >> 10) == prefix;
+                const u32 d = PASS == 0 ? key >> 21 : PASS == 1 ? (key >> 10) & 2047u : key & 1023u;
+                const u64 bal = __ballot(on);
+                if (!bal) continue;  // (wave-uniform)
+                const u32 first = (u32)__builtin_ctzll(bal);
+                const u32 d0 = (u32)__shfl((int)d, (int)first, 64);
+                if (__ballot(on && d == d0) == bal) {
+                    if (lane == first) atomicAdd(&h[d0], (u32)__builtin_popcountll(bal));
+                } else if (on) {
+                    atomicAdd(&h[d], 1u);
+                }
+            }
+        }
+    }
+    if (PASS == 0) {
+        ksum = wave_sum(ksum);
+        cands = wave_sum32(cands);
+        if (lane == 0 && cands) {
+            atomicAdd(&ws[0], (u64)cands);
+            atomicAdd(&ws[1], ksum);
+        }
+    }
+    __syncthreads();
+    for (u32 b = threadIdx.x; b < kTopBins; b += kChgWaves * 64)
+        if (h[b]) atomicAdd(&sc->hist[PASS][b], h[b]);
+    if (PASS == 0 && threadIdx.x == 0 && ws[0]) {
+        atomicAdd(&sc->n_cand, ws[0]);
+        atomicAdd(&sc->key_sum, ws[1]);
+    }
+}
+
+// One workgroup: the digit of pass `pass` that holds rank `want` counted from the top bin, and the rank left inside it.
+__global__ __launch_bounds__(kChgWaves * 64) void k_top_select(TopScratch* __restrict__ sc, u32 cap, u32 pass) {
+    __shared__ u32 lds[4];
+    if (pass == 0) {
+        if (sc->n_cand <= cap) {  // everything is listed: no threshold to find
+            if (threadIdx.x == 0) sc->all = 1u;
+            return;
+        }
+    } else if (sc->all) {
+        return;
+    }
+    const u32 want = pass == 0 ? cap : sc->want, prefix = sc->prefix;
+    constexpr u32 per = kTopBins / (kChgWaves * 64);
+    u32 v[per], sum = 0;
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {  // from the top bin down
+        v[q] = sc->hist[pass][kTopBins - 1 - (threadIdx.x * per + q)];
+        sum += v[q];
+    }
+    u32 tot;
+    u32 run = ni_block_excl(sum, lds, &tot);
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        if (run < want && want <= run + v[q]) {  // (one bin of one thread: the bins' counts reach `want` once)
+            const u32 bin = kTopBins - 1 - (threadIdx.x * per + q);
+            sc->prefix = pass == 0 ? bin : pass == 1 ? (prefix << 11) | bin : (prefix << 10) | bin;
+            sc->want = want - run;
+        }
+        run += v[q];
+    }
+}
+
+// bit j: row i0 + j is a candidate with K == T
+template <bool FILT>
+__device__ __forceinline__ u32 top_tie_flags(const uint4& k, const uint4& a, u64 i0, u64 n, u32 min_key, u32 filt, u32 node, u32 T) {
+    return top_flags<FILT>(k, a, i0, n, min_key, filt, node) &
+           ((u32)(k.x == T) | ((u32)(k.y == T) << 1) | ((u32)(k.z == T) << 2) | ((u32)(k.w == T) << 3));
+}
+
+template <bool FILT>
+__global__ __launch_bounds__(kChgWaves * 64, 8) void k_top_collect(const u32* __restrict__ K, const u32* __restrict__ A,
+                                                                 const ChgPlan p, u32 min_key, u32 filt, u32 node, u32 cap,
+                                                                 TopScratch* __restrict__ sc, u32* __restrict__ cnt,
+                                                                 u32* __restrict__ gsum) {
+    __shared__ u32 ws[kChgWaves];
+    const u32 all = sc->all, T = sc->prefix;
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u32 t0 = blockIdx.x * p.tpg, t1 = t0 + p.tpg < p.nt ? t0 + p.tpg : p.nt;
+    u32 mine = 0;
+    for (u32 t = t0 + wv; t < t1; t += kChgWaves) {  // wave-uniform
+        const u64 lo = (u64)t * kChgTile;
+        uint4 k[4], a[4];
+        top_load<FILT>(K, A, lo, lane, k, a);
+        u32 c = 0;  // 0 .. 16
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const u64 i0 = lo + (u64)s * 256 + lane * 4;
+            const u32 f = top_flags<FILT>(k[s], a[s], i0, p.n, min_key, filt, node);
+            const u32 kv[4] = {k[s].x, k[s].y, k[s].z, k[s].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (!((f >> j) & 1u)) continue;
+                if (all || kv[j] > T) {
+                    const u32 pos = atomicAdd(&sc->cursor, 1u);
+                    if (pos < cap) sc->pairs[pos] = ((u64)kv[j] << 32) | (u32)~(u32)(i0 + j);
+                } else if (kv[j] == T) {
+                    ++c;
+                }
+            }
+        }
+        u32 tc = 0;
+#pragma unroll
+        for (int bit = 0; bit < 5; ++bit) tc += (u32)__builtin_popcountll(__ballot((c >> bit) & 1u)) << bit;
+        if (lane == 0) cnt[t] = tc;
+        mine += tc;
+    }
+    if (lane == 0) ws[wv] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) gsum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+}
+
+template <bool FILT>
+__global__ __launch_bounds__(kChgWaves * 64, 8) void k_top_ties(const u32* __restrict__ K, const u32* __restrict__ A, const ChgPlan p,
+                                                              u32 min_key, u32 filt, u32 node, u32 cap,
+                                                              TopScratch* __restrict__ sc, const u32* __restrict__ cnt,
+                                                              const u32* __restrict__ gsum) {
+    __shared__ u32 toff[kChgMaxTpg];
+    __shared__ u32 lds[4];
+    if (sc->all) return;
+    const u32 T = sc->prefix, ties = sc->want < cap ? sc->want : cap;  // the first `ties` rows with K == T are listed,
+    const u32 first = cap - ties;                                      // behind the cap - ties rows with K > T
+    const u32 base = gsum[blockIdx.x];
+    if (base >= ties || gsum[blockIdx.x + 1] == base) return;  // everything past the listing, or nothing here
+    const u32 t0 = blockIdx.x * p.tpg, k = p.tpg < p.nt - t0 ? p.tpg : p.nt - t0;
+    constexpr u32 per = kChgMaxTpg / (kChgWaves * 64);
+    u32 v[per], sum = 0;
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        const u32 i = threadIdx.x * per + q;
+        v[q] = i < k ? cnt[t0 + i] : 0u;
+        sum += v[q];
+    }
+    u32 tot;
+    u32 run = ni_block_excl(sum, lds, &tot);
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        const u32 i = threadIdx.x * per + q;
+        if (i < k) toff[i] = run;
+        run += v[q];
+    }
+    __syncthreads();
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u64 lt = (1ull << lane) - 1ull;
+    for (u32 i = wv; i < k; i += kChgWaves) {  // wave-uniform
+        u32 off = base + toff[i];
+        const u32 c = (i + 1 < k ? toff[i + 1] : tot) - toff[i];
+        if (c == 0 || off >= ties) continue;
+        const u64 lo = (u64)(t0 + i) * kChgTile;
+        u32 fl = 0;  // the four steps' flags, a nibble each (k_exp_apply's form: no tile is held in registers across the listing)
+        {
+            uint4 kq[4], a[4];
+            top_load<FILT>(K, A, lo, lane, kq, a);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                fl |= top_tie_flags<FILT>(kq[s], a[s], lo + (u64)s * 256 + lane * 4, p.n, min_key, filt, node, T) << (4 * s);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const u64 i0 = lo + (u64)s * 256 + lane * 4;
+            const u32 f = (fl >> (4 * s)) & 15u;
+            const u32 lc = (u32)__builtin_popcount(f);  // 0 .. 4
+            u32 below = 0, allc = 0;
+#pragma unroll
+            for (int bit = 0; bit < 3; ++bit) {
+                const u64 bb = __ballot((lc >> bit) & 1u);
+                below += (u32)__builtin_popcountll(bb & lt) << bit;
+                allc += (u32)__builtin_popcountll(bb) << bit;
+            }
+            u32 r = off + below;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (!((f >> j) & 1u)) continue;
+                if (r < ties) sc->pairs[first + r] = ((u64)T << 32) | (u32)~(u32)(i0 + j);
+                ++r;
+            }
+            off += allc;
+            if (off >= ties) break;  // (wave-uniform)
+        }
+    }
+}
+
+// One workgroup: the L = min(n_candidates, cap) composites, descending, then rows / keys / nodes and the two sums for the host.
+__global__ __launch_bounds__(1024) void k_top_sort(TopScratch* __restrict__ sc, const u32* __restrict__ A, u64 n, u32 cap,
+                                                   u32* __restrict__ rows, u32* __restrict__ key, u32* __restrict__ node) {
+    __shared__ u64 s[kTopMax];
+    const u64 nc = sc->n_cand;
+    const u32 L = nc < cap ? (u32)nc : cap;
+    u32 P = 1;
+    while (P < L) P <<= 1;
+    for (u32 i = threadIdx.x; i < P; i += 1024) s[i] = i < L ? sc->pairs[i] : 0ull;  // (0 sorts behind every composite: ~row != 0)
+    __syncthreads();
+    for (u32 k = 2; k <= P; k <<= 1) {
+        for (u32 j = k >> 1; j > 0; j >>= 1) {
+            for (u32 q = threadIdx.x; q < (P >> 1); q += 1024) {  // pair q of the stage: i has bit j clear, o = i | j
+                const u32 i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), o = i | j;
+                const u64 x = s[i], y = s[o];
+                if (((i & k) == 0) ? x < y : x > y) {
+                    s[i] = y;
+                    s[o] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (u32 i = threadIdx.x; i < L; i += 1024) {
+        const u32 r = ~(u32)s[i];
+        rows[i] = r;
+        key[i] = (u32)(s[i] >> 32);
+        if (node) node[i] = r < n ? A[r] : kNone;
+    }
+    if (threadIdx.x == 0) {
+        sc->hdr[0] = nc;
+        sc->hdr[1] = sc->key_sum;
+    }
+}
+
+template <bool FILT>
+static void top_passes(const u32* K, const u32* A, const ChgPlan& p, u32 min_key, u32 filt, u32 node, u32 cap, TopScratch* sc,
+                       u32* cnt, u32* gsum, hipStream_t s) {
+    const dim3 g(p.G), b(kChgWaves * 64);
+    hipLaunchKernelGGL((k_top_hist<FILT, 0>), g, b, 0, s, K, A, p, min_key, filt, node, sc);
+    if (!cap) return;  // (count only)
+    hipLaunchKernelGGL(k_top_select, dim3(1), b, 0, s, sc, cap, 0u);
+    hipLaunchKernelGGL((k_top_hist<FILT, 1>), g, b, 0, s, K, A, p, min_key, filt, node, sc);
+    hipLaunchKernelGGL(k_top_select, dim3(1), b, 0, s, sc, cap, 1u);
+    hipLaunchKernelGGL((k_top_hist<FILT, 2>), g, b, 0, s, K, A, p, min_key, filt, node, sc);
+    hipLaunchKernelGGL(k_top_select, dim3(1), b, 0, s, sc, cap, 2u);
+    hipLaunchKernelGGL(k_top_collect<FILT>, g, b, 0, s, K, A, p, min_key, filt, node, cap, sc, cnt, gsum);
+    hipLaunchKernelGGL(k_chg_scan, dim3(1), b, 0, s, gsum, p.G, &sc->tie_total);
+    hipLaunchKernelGGL(k_top_ties<FILT>, g, b, 0, s, K, A, p, min_key, filt, node, cap, sc, cnt, gsum);
+}
+
+void launch_top_rows(const u32* K, const u32* A, u64 n, u32 min_key, u32 filt, u32 node, u32 cap, TopScratch* sc, u32* cnt,
+                     u32* gsum, u32* rows, u32* key, u32* nodes, hipStream_t s) {
+    launch_fill_u32(reinterpret_cast<u32*>(sc), kTopZeroWords, 0u, s);  // the sums, the selection's words and the histograms
+    const ChgPlan p = chg_plan(n);
+    if (p.G) {
+        if (filt) top_passes<true>(K, A, p, min_key, filt, node, cap, sc, cnt, gsum, s);
+        else top_passes<false>(K, A, p, min_key, filt, node, cap, sc, cnt, gsum, s);
+    }
+    hipLaunchKernelGGL(k_top_sort, dim3(1), dim3(1024), 0, s, sc, A, n, cap, rows, key, nodes);
+}
+
 }  // namespace riogp

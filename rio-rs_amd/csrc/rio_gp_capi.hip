@@ -527,6 +527,10 @@ struct rio_gp {
     // measured load (rio_gp_hits_*, rio_gp_load_fold), allocated on first use: the hit column H (cap_rows u32, 0 to begin with)
     u32* hits_H = nullptr;
     u32* hits_Hmem = nullptr;  // H's memory, allocated; hits_H is set once it has been filled
+    // hot-object report (rio_gp_top_rows), allocated on first use: the selection's device state, and pinned host memory for the
+    // two sums and the host-pointer form's listing (16 + 12 * RIO_GP_TOP_MAX bytes); the per-tile counts are the feed's
+    TopScratch* top_sc = nullptr;
+    unsigned char* h_top = nullptr;
     std::vector<void*> allocs;
 };
 
@@ -1409,6 +1413,7 @@ void rio_gp_destroy(rio_gp_t* h) {
     if (h->chg_stage.p) (void)hipFree(h->chg_stage.p);
     if (h->h_ni) (void)hipHostFree(h->h_ni);
     if (h->h_chg) (void)hipHostFree(h->h_chg);
+    if (h->h_top) (void)hipHostFree(h->h_top);
     if (h->h_stats) (void)hipHostFree(h->h_stats);
     if (h->h_chain_err) (void)hipHostFree(h->h_chain_err);
     if (h->h_slots) (void)hipHostFree(h->h_slots);
@@ -2321,6 +2326,99 @@ int rio_gp_load_fold(rio_gp_t* h, uint32_t keep, uint32_t gain, uint32_t min_loa
         st->reserved = 0;
     }
     return RIO_GP_OK;
+}
+
+// ---- hot-object report --------------------------------------------------------------------------
+
+constexpr size_t kTopHostBytes = 2 * sizeof(u64) + 3 * (size_t)RIO_GP_TOP_MAX * sizeof(u32);
+static_assert(RIO_GP_TOP_MAX == kTopMax && RIO_GP_TOP_PLACED == kTopPlaced && RIO_GP_TOP_ON_NODE == kTopOnNode,
+              "rio_gp_top_rows: the header's constants are the kernels'");
+
+// The selection's scratch on first use: the feed's per-tile counts and workgroup sums, the device state, the pinned read-back.
+static int top_scratch(rio_gp* h) {
+    int rc;
+    if ((rc = chg_counters(h))) return rc;
+    if (!h->h_top && hipHostMalloc(reinterpret_cast<void**>(&h->h_top), kTopHostBytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        h->h_top = nullptr;
+        return fail(h, RIO_GP_ENOMEM, "hipHostMalloc(hot-object report) failed");
+    }
+    if (!h->top_sc) {
+        unsigned char* mem = nullptr;
+        if ((rc = dalloc(h, &mem, sizeof(TopScratch)))) return rc;
+        // (once: `pairs` is read only where a pass of the same call wrote it, and the sort guards the rows it gathers anyway)
+        launch_fill_u32(reinterpret_cast<u32*>(mem), sizeof(TopScratch) / sizeof(u32), 0u, h->stream);
+        HIPCHK(h, hipGetLastError());
+        h->top_sc = reinterpret_cast<TopScratch*>(mem);
+    }
+    return RIO_GP_OK;
+}
+
+// checks shared by both forms: nothing is allocated or launched before they pass
+static int top_args(rio_gp* h, uint32_t flags, uint32_t node, const void* r, const void* k, const void* o, uint64_t cap,
+                    const uint64_t* n_candidates) {
+    if (flags & ~(RIO_GP_TOP_BY_HITS | RIO_GP_TOP_PLACED | RIO_GP_TOP_ON_NODE)) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: unknown flags");
+    if (!n_candidates) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: n_candidates is NULL");
+    if (cap > RIO_GP_TOP_MAX) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: cap above RIO_GP_TOP_MAX");
+    if ((r != nullptr) != (k != nullptr)) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: out_rows / out_key are given together or not at all");
+    if (!r && (cap || o)) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: cap or out_node without a listing");
+    if ((flags & RIO_GP_TOP_ON_NODE) && node >= h->m) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: node out of range");
+    if (row_sharded(h)) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: not implemented on a handle of the row-sharded solve");
+    return RIO_GP_OK;
+}
+
+// Both forms: every pass enqueued behind whatever the handle has in flight, the two sums (and, for the host form, the listing
+// behind them) copied into pinned memory, one wait.  Reads load or H and the committed column; writes its own scratch only.
+static int top_rows(rio_gp* h, uint32_t flags, uint32_t node, uint32_t min_key, u32* d_rows, u32* d_key, u32* d_node, bool to_host,
+                    uint32_t* out_rows, uint32_t* out_key, uint32_t* out_node, uint64_t cap, uint64_t* n_candidates, uint64_t* key_sum) {
+    int rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = top_scratch(h))) return rc;
+    TopScratch* const sc = h->top_sc;
+    const u32 c = (u32)cap;
+    if (to_host) {
+        d_rows = sc->out;
+        d_key = sc->out + c;
+        d_node = out_node ? sc->out + 2 * (size_t)c : nullptr;
+    }
+    // (a handle that never counted a hit has no H: every key is 0, and none is allocated for the question)
+    const u32* const K = (flags & RIO_GP_TOP_BY_HITS) ? h->hits_H : h->load;
+    launch_top_rows(K, h->assign[h->cur], h->n, min_key, flags & (RIO_GP_TOP_PLACED | RIO_GP_TOP_ON_NODE), node, c, sc, h->chg_cnt,
+                    h->chg_gsum, d_rows, d_key, d_node, h->stream);
+    HIPCHK(h, hipGetLastError());
+    const size_t bytes = 2 * sizeof(u64) + (to_host ? (out_node ? 3 : 2) * (size_t)c * sizeof(u32) : 0);
+    HIPCHK(h, hipMemcpyAsync(h->h_top, sc->hdr, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    u64 hdr[2];
+    memcpy(hdr, h->h_top, sizeof hdr);
+    *n_candidates = hdr[0];
+    if (key_sum) *key_sum = hdr[1];
+    const size_t L = (size_t)std::min<u64>(hdr[0], cap);
+    if (to_host && L) {
+        const u32* const o = reinterpret_cast<const u32*>(h->h_top + sizeof hdr);
+        memcpy(out_rows, o, L * sizeof(u32));
+        memcpy(out_key, o + c, L * sizeof(u32));
+        if (out_node) memcpy(out_node, o + 2 * (size_t)c, L * sizeof(u32));
+    }
+    return RIO_GP_OK;
+}
+
+int rio_gp_top_rows(rio_gp_t* h, uint32_t flags, uint32_t node, uint32_t min_key, uint32_t* out_rows, uint32_t* out_key,
+                    uint32_t* out_node, uint64_t cap, uint64_t* n_candidates, uint64_t* key_sum) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = top_args(h, flags, node, out_rows, out_key, out_node, cap, n_candidates))) return rc;
+    return top_rows(h, flags, node, min_key, nullptr, nullptr, nullptr, true, out_rows, out_key, out_node, cap, n_candidates, key_sum);
+}
+
+int rio_gp_top_rows_dev(rio_gp_t* h, uint32_t flags, uint32_t node, uint32_t min_key, uint32_t* d_rows, uint32_t* d_key,
+                        uint32_t* d_node, uint64_t cap, uint64_t* n_candidates, uint64_t* key_sum) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = top_args(h, flags, node, d_rows, d_key, d_node, cap, n_candidates))) return rc;
+    return top_rows(h, flags, node, min_key, d_rows, d_key, d_node, false, nullptr, nullptr, nullptr, cap, n_candidates, key_sum);
 }
 
 int rio_gp_set_num_objects(rio_gp_t* h, uint64_t n) {

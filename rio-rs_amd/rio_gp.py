@@ -14,6 +14,7 @@ _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_DIR, "librio_gp.so")
 NONE = 0xFFFFFFFF
 CAP_INF = 0xFFFFFFFFFFFFFFFF
+TOP_BY_HITS, TOP_PLACED, TOP_ON_NODE, TOP_MAX = 1, 2, 4, 4096   # RIO_GP_TOP_*
 AFF_INACTIVE = 0xFFFFFFFE       # RIO_GP_AFF_INACTIVE: affinity of a row that is not an object
 CFG_ROW_LIFECYCLE = 1           # RIO_GP_CFG_ROW_LIFECYCLE
 CFG_REF_SELF_ASSIGN = 2         # RIO_GP_CFG_REF_SELF_ASSIGN: claims / first touches do not need a live node (service.rs:244-252)
@@ -227,6 +228,11 @@ def _load(lab):
         for nm in ("rio_gp_hits_merge", "rio_gp_hits_merge_dev", "rio_gp_get_hits"):
             getattr(L, nm).argtypes = [_vp, C.c_uint64, _vp]
         L.rio_gp_load_fold.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(LoadFoldStats)]
+        for nm in ("rio_gp_top_rows", "rio_gp_top_rows_dev"):
+            if not hasattr(L, nm):   # (an older build under RIO_GP_LIB, the A/B aid: a call then fails as any missing symbol does)
+                continue
+            getattr(L, nm).argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]
         L.rio_gp_remap_nodes.argtypes = [_vp, C.c_uint32, _vp, C.POINTER(C.c_uint64)]
         if lab:
             L.rio_gp_debug_set_scan_nt.argtypes = [C.c_int]
@@ -685,6 +691,41 @@ class GpuPlacement:
         """One rio_gp_load_fold call as given, without statistics: rc; no exception."""
         return self._L.rio_gp_load_fold(self._h, int(keep), int(gain), int(min_load), int(max_load), None)
 
+    # -- hot-object report --
+    def top_rows(self, cap, by_hits=False, placed=False, node=None, min_key=0, want_node=True):
+        """rio_gp_top_rows: (rows, keys, nodes, n_candidates, key_sum) — the first min(n_candidates, cap) candidates by (key
+        descending, row ascending), key = load or (by_hits) the hit column; placed: only rows with a node; node: only rows on that
+        node.  cap 0: count only (empty arrays).  nodes is None with want_node False."""
+        flags = (TOP_BY_HITS if by_hits else 0) | (TOP_PLACED if placed else 0) | (TOP_ON_NODE if node is not None else 0)
+        nc, ks = C.c_uint64(0), C.c_uint64(0)
+        cap = int(cap)
+        if cap == 0:
+            self._chk(self._L.rio_gp_top_rows(self._h, flags, int(node or 0), int(min_key), None, None, None, 0, C.byref(nc),
+                                              C.byref(ks)))
+            e = np.empty(0, np.uint32)
+            return e, e, (e if want_node else None), int(nc.value), int(ks.value)
+        buf = np.empty((3, cap), np.uint32)
+        self._chk(self._L.rio_gp_top_rows(self._h, flags, int(node or 0), int(min_key), _ptr(buf[0]), _ptr(buf[1]),
+                                          _ptr(buf[2]) if want_node else None, cap, C.byref(nc), C.byref(ks)))
+        k = min(int(nc.value), cap)
+        return buf[0, :k].copy(), buf[1, :k].copy(), (buf[2, :k].copy() if want_node else None), int(nc.value), int(ks.value)
+
+    def top_rows_dev(self, flags, node, min_key, d_rows, d_key, d_node, cap):
+        """rio_gp_top_rows_dev: the listing into device arrays of cap entries (ints; d_node may be None; all None with cap 0:
+        count only).  Returns (n_candidates, key_sum)."""
+        nc, ks = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.rio_gp_top_rows_dev(self._h, int(flags), int(node), int(min_key), _vp(d_rows) if d_rows else None,
+                                              _vp(d_key) if d_key else None, _vp(d_node) if d_node else None, int(cap),
+                                              C.byref(nc), C.byref(ks)))
+        return int(nc.value), int(ks.value)
+
+    def top_rows_raw(self, flags, node=0, min_key=0, out_rows=None, out_key=None, out_node=None, cap=0, want_n=True):
+        """One rio_gp_top_rows call as given (tests of the argument checks): (rc, n_candidates); no exception."""
+        nc = C.c_uint64(0)
+        rc = self._L.rio_gp_top_rows(self._h, int(flags), int(node), int(min_key), _ptr(out_rows), _ptr(out_key), _ptr(out_node),
+                                     int(cap), C.byref(nc) if want_n else None, None)
+        return rc, int(nc.value)
+
     # -- policy --
     def place_pending(self, idx, requester):
         idx, requester = _u32(idx), _u32(requester)
@@ -904,6 +945,8 @@ def _oplib():
         bind_op_changes(L)
         bind_op_expire(L)
         bind_op_loads(L)
+        if hasattr(L, "rio_op_hottest_objects"):   # (as above)
+            bind_op_top(L)
         L.rio_op_dense.argtypes = [_vp]
         L.rio_op_dense.restype = _vp
         L.rio_op_invalidate_cache.argtypes = [_vp]
@@ -983,6 +1026,31 @@ def op_get_object_load(L, h, struct_name, object_id):
     load, found = C.c_uint32(0), C.c_int(0)
     rc = L.rio_op_get_object_load(h, ty, len(ty), oid, len(oid), C.byref(load), C.byref(found))
     return rc, (int(load.value) if found.value else None)
+
+
+def bind_op_top(L):
+    """argtypes of rio_op_hottest_objects on a library that has it (the product, or a stub-linked test build)."""
+    pp, psz = C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_size_t))
+    L.rio_op_hottest_objects.argtypes = [_vp, C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                         pp, psz, pp, psz, pp, _vp]
+
+
+def op_hottest_objects(L, h, address=None, min_load=0, max_objects=TOP_MAX):
+    """One rio_op_hottest_objects call on handle h of library L: (rc, [(struct_name, object_id, address, load)], n_candidates)
+    — the placed keys with the largest loads (on `address`; None: on every server), load descending.  max_objects 0: count."""
+    n, cand = C.c_uint64(0), C.c_uint64(0)
+    ty, oid, ad = (C.POINTER(C.c_char_p)() for _ in range(3))
+    tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+    cap = int(max_objects)
+    loads = (C.c_uint32 * max(min(cap, TOP_MAX), 1))()
+    rc = L.rio_op_hottest_objects(h, None if address is None else address.encode(), int(min_load), cap, C.byref(n),
+                                  C.byref(cand), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il), C.byref(ad), loads)
+    if rc != OK:
+        return rc, [], 0
+    tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))   # (c_char_p would stop at a NUL)
+    out = [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(),
+            None if ad[k] is None else ad[k].decode(), int(loads[k])) for k in range(n.value)]
+    return rc, out, int(cand.value)
 
 
 def _cstrs(items):
@@ -1232,6 +1300,13 @@ class GpuObjectPlacement:
         rc, load = op_get_object_load(_oplib(), self._h, struct_name, object_id)
         self._chk(rc)
         return load
+
+    def hottest_objects(self, address=None, min_load=0, max_objects=TOP_MAX):
+        """rio_op_hottest_objects: ([(struct_name, object_id, address, load)], n_candidates) — the placed keys with the largest
+        loads, load descending, on `address` or (None) on every server; at most max_objects (<= 4096; 0: count only)."""
+        rc, out, cand = op_hottest_objects(_oplib(), self._h, address, min_load, max_objects)
+        self._chk(rc)
+        return out, cand
 
     def objects_on_server(self, address):
         """rio_op_objects_on_server: every (struct_name, object_id) placed on `address` (the reverse index; [] for an address

@@ -104,6 +104,10 @@ extern "C" {
     fn rio_op_set_load_tracking(p: *mut c_void, on: c_int) -> c_int;
     fn rio_op_fold_loads(p: *mut c_void, keep: u32, gain: u32, min_load: u32, max_load: u32, rows_changed: *mut u64,
                          hits_folded: *mut u64) -> c_int;
+    fn rio_op_hottest_objects(p: *mut c_void, address: *const c_char, min_load: u32, max_objects_out: u64, n_out: *mut u64,
+                              n_candidates: *mut u64, tys: *mut *const *const c_char, ty_lens: *mut *const usize,
+                              ids: *mut *const *const c_char, id_lens: *mut *const usize, addrs: *mut *const *const c_char,
+                              loads: *mut u32) -> c_int;
     fn rio_op_tick(p: *mut c_void, stats: *mut RioGpStats) -> c_int;
     fn rio_op_snapshot(p: *mut c_void, n_out: *mut u64, tys: *mut *const *const c_char, ids: *mut *const *const c_char,
                        addrs: *mut *const *const c_char) -> c_int;
@@ -340,6 +344,36 @@ impl GpuObjectPlacement {
         let (mut changed, mut hits) = (0u64, 0u64);
         check(unsafe { rio_op_fold_loads(self.inner.0, keep, gain, min_load, max_load, &mut changed, &mut hits) }, self)?;
         Ok((changed, hits))
+    }
+
+    /// Hot objects: the placed objects with the largest loads (at least `min_load`), load descending, on `address` or (`None`)
+    /// on every server; at most `max` of them (`max <= 4096`; 0 only counts).  Returns the objects with the address each is on
+    /// and its load, plus the number of objects selected in all.  The stores the reference can sit on answer this with an
+    /// `ORDER BY ... LIMIT`; its `ObjectPlacementItem` (rio-rs/src/object_placement/mod.rs:23-24) has no load to order by.
+    pub async fn hottest(&self, address: Option<String>, min_load: u32, max: u64)
+        -> Result<(Vec<(ObjectId, Option<String>, u32)>, u64), ObjectPlacementError> {
+        let me = self.clone();
+        blocking(move || {
+            let addr: Option<CString> = address.as_deref().map(cstr).transpose()?;
+            let (mut n, mut cand) = (0u64, 0u64);
+            let (mut ty, mut id, mut ad) = (std::ptr::null(), std::ptr::null(), std::ptr::null());
+            let (mut tl, mut il) = (std::ptr::null(), std::ptr::null());
+            let mut loads = vec![0u32; max.min(4096) as usize + 1];
+            check(unsafe { rio_op_hottest_objects(me.inner.0, addr.as_ref().map_or(std::ptr::null(), |a| a.as_ptr()), min_load, max,
+                                                  &mut n, &mut cand, &mut ty, &mut tl, &mut id, &mut il, &mut ad,
+                                                  loads.as_mut_ptr()) }, &me)?;
+            // the arrays are this thread's until its next call: read them here, before anything else can run
+            let key = |p: *const *const c_char, l: *const usize, k: usize| unsafe {
+                String::from_utf8_lossy(std::slice::from_raw_parts(*p.add(k) as *const u8, *l.add(k))).into_owned()
+            };
+            let out = (0..n as usize).map(|k| {
+                let a = unsafe { *ad.add(k) };
+                (ObjectId(key(ty, tl, k), key(id, il, k)),
+                 if a.is_null() { None } else { Some(unsafe { CStr::from_ptr(a) }.to_string_lossy().into_owned()) }, loads[k])
+            }).collect();
+            Ok((out, cand))
+        })
+        .await
     }
 
     /// Eager rebalance (the batched form of the lazy `clean_server` + first-touch path):
