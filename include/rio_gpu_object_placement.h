@@ -162,6 +162,17 @@ int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const cha
                      const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens,
                      const char* const** from_addresses, const char* const** to_addresses);
 
+/* rio_op_rebalance with the cut of the dense layer chosen: order = RIO_GP_REBALANCE_ROW_ORDER (what rio_op_rebalance does) or
+ * RIO_GP_REBALANCE_BY_LOAD — every server over its capacity sheds its HEAVIEST objects first (rule R1' of rio_gp_rebalance: the
+ * fewest objects per server that bring it under its capacity; an object of load 0 never moves).  That is the call to make
+ * after rio_op_fold_loads: the folded loads are skewed, and a move is an actor deactivated on one server and activated on
+ * another.  max_moves still counts objects, taken in the dense layer's row order among those to shed.  Outputs, locks, shadow
+ * invalidation and ownership of the arrays are rio_op_rebalance's (the two calls share the calling thread's arrays).  Any
+ * other order: RIO_GP_EINVAL, nothing changed. */
+int rio_op_rebalance_ordered(rio_op_t* p, uint32_t order, uint64_t max_moves, uint64_t* n_out, const char* const** struct_names,
+                             const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens,
+                             const char* const** from_addresses, const char* const** to_addresses);
+
 /* Change feed (rio_gp_changes): every placement change since this handle's last call, its creation or rio_op_changes_reset —
  * what keeps a write-behind copy of the object_placement table (migrations/0001-sqlite-init.sql:1-9, sqlite.rs:68-85) in step
  * without a snapshot.  Entry k is (struct_names[k], object_ids[k], old_addresses[k], new_addresses[k]); an address is NULL when

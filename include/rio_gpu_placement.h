@@ -268,11 +268,18 @@ int rio_gp_rows_on_nodes_dev(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t*
 
 /* ---- bounded rebalance: move objects off nodes over their load target ------------------------ */
 
+#define RIO_GP_REBALANCE_ROW_ORDER 0u /* R1: a node's candidates are cut in row order */
+#define RIO_GP_REBALANCE_BY_LOAD 1u   /* R1': in (load, row) order: the heaviest are shed first */
+
 typedef struct rio_gp_rebalance_cfg {
-    uint32_t struct_size;    /* = sizeof(rio_gp_rebalance_cfg); ABI guard */
+    uint32_t struct_size;    /* = sizeof(rio_gp_rebalance_cfg); ABI guard.  24 (the struct up to `target`, as it was before
+                                `order` existed) is accepted too and means row order: the fields behind it are not read.  Every
+                                other size: RIO_GP_EINVAL */
     uint32_t rounds;         /* water-fill rounds; 0 = the handle's spill_rounds; <= 8 */
     uint64_t max_moves;      /* B: rows selected at most; ~0 = no limit */
     const uint64_t* target;  /* host array of m u64 (T[j]; ~0 = never over); NULL = the capacities */
+    uint32_t order;          /* RIO_GP_REBALANCE_ROW_ORDER / RIO_GP_REBALANCE_BY_LOAD; anything else: RIO_GP_EINVAL */
+    uint32_t reserved;       /* 0 (RIO_GP_EINVAL otherwise) */
 } rio_gp_rebalance_cfg;
 
 typedef struct rio_gp_rebalance_stats {
@@ -288,6 +295,16 @@ typedef struct rio_gp_rebalance_stats {
  * affinity RIO_GP_AFF_INACTIVE); every other row (unplaced, on a dead node, on a node >= m) is left exactly as it is.
  *   R1  per live node j, free_j = T[j] -sat (pinned load on j); j's candidates in row order are kept while the inclusive prefix
  *       of their loads stays <= free_j; the first that overflows and every later one are surplus.
+ *   R1' (cfg->order = RIO_GP_REBALANCE_BY_LOAD, in place of R1) j's candidates are taken in the order (load ascending, then
+ *       row ascending) and kept while the inclusive prefix of their loads stays <= free_j; the first that overflows and every
+ *       later one in that order are surplus: the heaviest rows are shed, and a node's surplus is the SMALLEST set of its
+ *       candidates whose removal leaves <= free_j.  Per node surplus_rows is therefore <= what R1 gives on the same table
+ *       (surplus_load may be larger: the heavy tail can overshoot), and a candidate of load 0 is never surplus.  As a
+ *       threshold: per over node a pair (tau_j >= 1, cutrow_j); candidate i is surplus iff load[i] > tau_j, or load[i] ==
+ *       tau_j and i >= cutrow_j.  tau_j is the load of the first overflowing candidate; with rem_j = free_j - (the load of
+ *       j's candidates below tau_j) and c_j = floor(rem_j / tau_j), cutrow_j is the row of the (c_j + 1)-th candidate of j
+ *       with load tau_j, in row order.  R1 is the case in which every key is 0.  R2, R3 and R4 do not change: the budget is
+ *       still the first B surplus rows in row order, and the fill runs in row order.
  *   R2  the first B surplus rows in row order are selected.
  *   R3  the selected rows are water-filled in row order exactly as in rule 3, with free = T -sat used' on live nodes (used' =
  *       the load of every row that is not selected) in place of cap - used, `rounds` rounds; a row's own node is a legal target.
@@ -297,14 +314,16 @@ typedef struct rio_gp_rebalance_stats {
  *   - out_rows / out_from / out_to: the moves (rows whose node changed), ascending by row, with the old and the new node; the
  *     three are given together or not at all (RIO_GP_EINVAL).  With them B = min(max_moves, moves_cap), so the listing always
  *     fits; without them moves_cap must be 0.  *n_moves (may be NULL) = the number of moves.  st may be NULL.
- *   - RIO_GP_EINVAL (nothing changed): bad cfg / struct_size, rounds > 8, the output rule above, or a handle of the row-sharded
+ *   - RIO_GP_EINVAL (nothing changed): bad cfg / struct_size, an unknown order, reserved != 0, rounds > 8, the output rule
+ *     above, or a handle of the row-sharded
  *     solve (rio_gp_shard_comm_init / _p2p_connect / _tick_async: a row-sharded table is rebalanced through
  *     rio_gp_shard_rebalance_*, below).
  *   - Like rio_gp_update_batch: it joins rio_gp_tick_async work in flight, drops an uncommitted rio_gp_solve, and counts as a
  *     change of the inputs (the next tick takes neither the quiet nor the chained form over the old column).
  *   - Cost: one streaming pass over the column, load and affinity when no live node is over its target; otherwise three more
- *     passes over the table and a few over the selected rows.  Scratch grows with the first calls and is kept until
- *     rio_gp_destroy.
+ *     passes over the table and a few over the selected rows.  By load, one more pass over the table per digit of the
+ *     threshold search (3 to 7: the digit is as wide as the over nodes' histograms allow).  Scratch grows with the first
+ *     calls and is kept until rio_gp_destroy.
  * The _dev form takes device pointers for the three move arrays. */
 int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebalance_stats* st, uint32_t* out_rows,
                      uint32_t* out_from, uint32_t* out_to, uint64_t moves_cap, uint64_t* n_moves);
@@ -689,7 +708,8 @@ int rio_gp_shard_exchange(rio_gp_t* h, const uint64_t* d_in, uint64_t* d_out, ui
  * Handle state changes as in rio_gp_rebalance (joins rio_gp_tick_async work, drops an uncommitted solve, counts as a change of
  * the inputs); `used` is the GLOBAL one of the new column on every rank after finish.  RIO_GP_EINVAL, nothing changed: bad cfg /
  * struct_size, rounds > 8, rank >= n_ranks, moves_cap without list_moves, rio_gp_shard_tick_async ticks in flight, a step
- * called out of order.  begin may be called at any step: it starts over.  Between begin and finish the handle belongs to the
+ * called out of order, or cfg->order != RIO_GP_REBALANCE_ROW_ORDER (the load-ordered cut R1' is not sharded: a node's
+ * threshold depends on its candidates on every rank).  begin may be called at any step: it starts over.  Between begin and finish the handle belongs to the
  * protocol: a call that changes an input of the solve (nodes, liveness, objects, CRUD, a solve, a tick, rio_gp_rebalance) or
  * reads `used` (rio_gp_get_nodes) ends it, and the next step answers RIO_GP_EINVAL (the column is written by finish alone, so it
  * is as it was).  d_* are DEVICE pointers owned by the caller.

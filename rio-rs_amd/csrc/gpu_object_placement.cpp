@@ -1708,8 +1708,17 @@ int rio_op_objects_on_server(rio_op_t* p, const char* address, uint64_t* n_out, 
 int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const char* const** struct_names,
                      const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens,
                      const char* const** from_addresses, const char* const** to_addresses) {
+    return rio_op_rebalance_ordered(p, RIO_GP_REBALANCE_ROW_ORDER, max_moves, n_out, struct_names, struct_name_lens, object_ids,
+                                    object_id_lens, from_addresses, to_addresses);
+}
+
+int rio_op_rebalance_ordered(rio_op_t* p, uint32_t order, uint64_t max_moves, uint64_t* n_out, const char* const** struct_names,
+                             const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens,
+                             const char* const** from_addresses, const char* const** to_addresses) {
     if (!p || !n_out || !struct_names || !struct_name_lens || !object_ids || !object_id_lens || !from_addresses || !to_addresses)
         return RIO_GP_EINVAL;
+    if (order != RIO_GP_REBALANCE_ROW_ORDER && order != RIO_GP_REBALANCE_BY_LOAD)
+        return fail(RIO_GP_EINVAL, "rio_op_rebalance_ordered: unknown order");
     State* s = p->s;
     t_rb_store.clear();
     t_rb_ty.clear(); t_rb_id.clear(); t_rb_from.clear(); t_rb_to.clear(); t_rb_tylen.clear(); t_rb_idlen.clear();
@@ -1725,6 +1734,7 @@ int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const cha
         rio_gp_rebalance_cfg cfg{};
         cfg.struct_size = sizeof cfg;
         cfg.max_moves = cap;  // targets: the capacities of rio_op_set_member
+        cfg.order = order;
         uint64_t n = 0;
         rc = rio_gp_rebalance(s->gp, &cfg, nullptr, t_rb_rows.data(), t_rb_src.data(), t_rb_dst.data(), cap, &n);
         s->shadow.invalidate_all();  // moved rows must not be answered from their old address (also when the call failed)

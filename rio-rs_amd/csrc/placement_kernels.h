@@ -443,15 +443,34 @@ ShPlan sh_plan(u64 n, u32 m, u32 s);
 size_t shed_order_lds(u32 m);
 // used, pin: m u64 each (zeroed here): the load of every row on node j, the load of the non-object rows on it
 void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u64* used, u64* pin, hipStream_t s);
-// map: node -> slot (kNone: not over); slot_node / slot_free: per slot; mat: s * nt u64; cut: m u32 (kNone where nothing is cut)
+// map: node -> slot (kNone: not over); slot_node / slot_free: per slot; mat: s * nt u64; cut: m u32 (kNone where nothing is cut).
+// thr (m u32, or nullptr = row order) in the four launches below: the load-ordered cut's threshold per node (kNone on a node
+// that is not over).  With it the cut walks only the candidates whose load == thr[node] — slot_free is then what
+// launch_shed_select left — and a candidate is surplus iff load > thr[node] || (load == thr[node] && row >= cut[node]).
 void launch_shed_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
-                     const u64* slot_free, u64* mat, u32* cut, hipStream_t s);
+                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, hipStream_t s);
 // tcnt: nt u32 -> the exclusive scan of the per-tile surplus counts; acc[kShAccSurplusRows / SurplusLoad]
-void launch_shed_count(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, u32* tcnt, u64* acc,
-                       hipStream_t s);
+void launch_shed_count(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* thr,
+                       u32* tcnt, u64* acc, hipStream_t s);
 // the first `budget` surplus rows into pk_* (row, load, node = kNone); used[j] -= their load; acc[kShAccSelectedLoad]
-void launch_shed_pack(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* toff,
-                      u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s);
+void launch_shed_pack(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* thr,
+                      const u32* toff, u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s);
+// The load-ordered cut (RIO_GP_REBALANCE_BY_LOAD; kernels: k_shed_sel_hist, k_shed_sel_pick): a segmented, weighted radix
+// selection, most significant digit first.  Per over node (slot) it finds the smallest load tau whose candidates, together with
+// every lighter one, weigh more than slot_free: thr[slot_node] = tau, slot_free[slot] -= the load of the candidates below tau.
+// The digit is `bits` wide (the last one may be narrower); the histogram is s << bits u64.
+constexpr u32 kShSelLdsBytes = 96 * 1024;        // LDS for a pass's histogram (k_shed_sel_hist<true>), beside the node map (4 B a
+                                                 // node) and the slots' prefixes (4 B a slot): 141 KiB of the CU's 160 at most
+constexpr u32 kShSelLdsSlots = kShSelLdsBytes / (4 * sizeof(u64));  // = 3 072: up to here a digit of >= 2 bits fits there
+struct ShSelPlan {
+    u32 bits;    // digit width
+    u32 passes;  // ceil(32 / bits)
+    bool lds;    // per-workgroup LDS histogram, flushed once (else: one global atomic per wave and distinct bin)
+};
+ShSelPlan sh_sel_plan(u32 s);
+// pre: s u32 of scratch; hist: (s << bits) u64 of scratch; thr: m u32 (kNone where the node is not over)
+void launch_shed_select(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u32 s, const u32* map,
+                        const u32* slot_node, u64* slot_free, u32* pre, u64* hist, u32* thr, hipStream_t st);
 // one water-fill round over the K packed rows against free = tgt -sat used; csum: ceil(K / kShChunk) u64; C: m + 1 u64; ord: m u32
 void launch_shed_round(u64 K, const u32* pk_load, u32* pk_node, const u64* tgt, u32 m, u64* used, u64* csum, u64* C, u32* ord,
                        u32* cntp, hipStream_t s);

@@ -6168,6 +6168,9 @@ void launch_ni_scatter(const u32* assign, const NiPlan& p, const u32* map, const
 //   k_shed_tile    per (over node x tile) the candidates' load, node-major: a matrix of at most kShMaxEntries u64
 //   k_shed_cut     one workgroup per over node: the first tile whose inclusive prefix passes free, then the exact row inside
 //                  it (R1, the strict prefix cut of rule 2 over the rows already on the node): cut[j] (kNone elsewhere)
+//   k_shed_sel_hist + k_shed_sel_pick   (RIO_GP_REBALANCE_BY_LOAD only, R1') the threshold thr[j] of every over node, one pass
+//                  per digit; k_shed_tile / k_shed_cut then walk only the candidates of load thr[j] against what is left of free,
+//                  and a candidate is surplus iff load > thr[j] || (load == thr[j] && row >= cut[j]).  thr == nullptr: row order
 //   k_shed_count   per tile: the surplus rows (candidate on j, row >= cut[j]) and their load
 //   k_shed_scan    one workgroup: exclusive scan of per-tile / per-chunk values
 //   k_shed_pack    the first B surplus rows in row order (R2) into the packed columns; `used` loses their load
@@ -6193,6 +6196,13 @@ __device__ __forceinline__ void shed_agg_add(u64* arr, u32 key, u64 v, bool act,
         act = act && !mine;
         mask &= ~mm;
     }
+}
+
+// R1 / R1' for one candidate of a node: row order (th == nullptr) cuts at the row; by load, at (*th, cut) in (load, row) order
+__device__ __forceinline__ bool shed_surplus(const u32* th, u32 l, u64 row, u32 cut) {
+    if (!th) return row >= (u64)cut;
+    const u32 t = *th;
+    return l > t || (l == t && row >= (u64)cut);
 }
 
 __global__ __launch_bounds__(kBlock) void k_shed_hist(const u32* __restrict__ assign, const u32* __restrict__ load,
@@ -6227,14 +6237,17 @@ __global__ __launch_bounds__(kBlock) void k_shed_hist(const u32* __restrict__ as
 
 __global__ __launch_bounds__(kBlock) void k_shed_tile(const u32* __restrict__ assign, const u32* __restrict__ load,
                                                       const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ map,
-                                                      u64* __restrict__ mat) {
+                                                      const u32* __restrict__ thr, u64* __restrict__ mat) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64* h = reinterpret_cast<u64*>(smem);           // [s]
     u32* mp = reinterpret_cast<u32*>(h + p.s);       // [m]
+    u32* th = mp + p.m;                              // [m] with thr only
     const int tid = threadIdx.x;
     const u32 t = blockIdx.x;
     for (u32 k = tid; k < p.s; k += kBlock) h[k] = 0;
     for (u32 k = tid; k < p.m; k += kBlock) mp[k] = map[k];
+    if (thr)
+        for (u32 k = tid; k < p.m; k += kBlock) th[k] = thr[k];
     __syncthreads();
     const u64 lo = (u64)t * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
     for (u64 base = lo; base < hi; base += kShChunk) {
@@ -6246,7 +6259,7 @@ __global__ __launch_bounds__(kBlock) void k_shed_tile(const u32* __restrict__ as
         const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (i0 + k < hi && cc[k] < p.m && aa[k] != kAffInactive && ll[k]) {
+            if (i0 + k < hi && cc[k] < p.m && aa[k] != kAffInactive && ll[k] && (!thr || ll[k] == th[cc[k]])) {
                 const u32 sl = mp[cc[k]];
                 if (sl != kNone) atomicAdd(&h[sl], (u64)ll[k]);
             }
@@ -6258,12 +6271,13 @@ __global__ __launch_bounds__(kBlock) void k_shed_tile(const u32* __restrict__ as
 __global__ __launch_bounds__(kBlock) void k_shed_cut(const u32* __restrict__ assign, const u32* __restrict__ load,
                                                      const u32* __restrict__ aff, ShPlan p, const u64* __restrict__ mat,
                                                      const u32* __restrict__ slot_node, const u64* __restrict__ slot_free,
-                                                     u32* __restrict__ cut) {
+                                                     const u32* __restrict__ thr, u32* __restrict__ cut) {
     __shared__ u64 part[16];
     __shared__ u64 s_base;
     __shared__ u32 s_tile, s_row;
     const int tid = threadIdx.x;
     const u32 sl = blockIdx.x, j = slot_node[sl];
+    const u32 tj = thr ? thr[j] : 0u;  // with thr: only the candidates of exactly this load are walked
     const u64 fr = slot_free[sl];
     const u64* row = mat + (size_t)sl * p.nt;
     if (tid == 0) { s_tile = kNone; s_row = kNone; s_base = 0; }
@@ -6295,7 +6309,8 @@ __global__ __launch_bounds__(kBlock) void k_shed_cut(const u32* __restrict__ ass
             const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
             const u32 cc[4] = {c.x, c.y, c.z, c.w}, l4[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) ll[k] = (i0 + k < hi && cc[k] == j && aa[k] != kAffInactive) ? l4[k] : 0u;
+            for (int k = 0; k < 4; ++k)
+                ll[k] = (i0 + k < hi && cc[k] == j && aa[k] != kAffInactive && (!thr || l4[k] == tj)) ? l4[k] : 0u;
         }
         u64 tot;
         u64 run = carry + block_excl_scan_1024((u64)ll[0] + ll[1] + ll[2] + ll[3], false, part, &tot);
@@ -6313,14 +6328,18 @@ __global__ __launch_bounds__(kBlock) void k_shed_cut(const u32* __restrict__ ass
 
 __global__ __launch_bounds__(kBlock) void k_shed_count(const u32* __restrict__ assign, const u32* __restrict__ load,
                                                        const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ cut,
-                                                       u32* __restrict__ tcnt, u64* __restrict__ acc) {
+                                                       const u32* __restrict__ thr, u32* __restrict__ tcnt,
+                                                       u64* __restrict__ acc) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32* ct = reinterpret_cast<u32*>(smem);  // [m]
+    u32* th = ct + p.m;                      // [m] with thr only
     __shared__ u64 s_sum;
     __shared__ u32 s_cnt;
     const int tid = threadIdx.x;
     const u32 t = blockIdx.x;
     for (u32 k = tid; k < p.m; k += kBlock) ct[k] = cut[k];
+    if (thr)
+        for (u32 k = tid; k < p.m; k += kBlock) th[k] = thr[k];
     if (tid == 0) { s_sum = 0; s_cnt = 0; }
     __syncthreads();
     u64 sum = 0;
@@ -6335,7 +6354,8 @@ __global__ __launch_bounds__(kBlock) void k_shed_count(const u32* __restrict__ a
         const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (i0 + k < hi && cc[k] < p.m && aa[k] != kAffInactive && i0 + k >= (u64)ct[cc[k]]) { ++cnt; sum += ll[k]; }
+            if (i0 + k < hi && cc[k] < p.m && aa[k] != kAffInactive &&
+                shed_surplus(thr ? th + cc[k] : nullptr, ll[k], i0 + k, ct[cc[k]])) { ++cnt; sum += ll[k]; }
     }
     sum = wave_sum(sum);
     cnt = wave_sum32(cnt);
@@ -6377,17 +6397,20 @@ __global__ __launch_bounds__(kBlock) void k_shed_scan(const T* in, T* out, u64 l
 
 __global__ __launch_bounds__(kBlock) void k_shed_pack(const u32* __restrict__ assign, const u32* __restrict__ load,
                                                       const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ cut,
-                                                      const u32* __restrict__ toff, u64 budget, u32* __restrict__ pk_row,
-                                                      u32* __restrict__ pk_load, u32* __restrict__ pk_node, u64* __restrict__ used,
-                                                      u64* __restrict__ acc) {
+                                                      const u32* __restrict__ thr, const u32* __restrict__ toff, u64 budget,
+                                                      u32* __restrict__ pk_row, u32* __restrict__ pk_load,
+                                                      u32* __restrict__ pk_node, u64* __restrict__ used, u64* __restrict__ acc) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32* ct = reinterpret_cast<u32*>(smem);  // [m]
+    u32* th = ct + p.m;                      // [m] with thr only
     __shared__ u64 part[16];
     const int tid = threadIdx.x;
     const u32 t = blockIdx.x;
     u64 pos = toff[t];
     if (pos >= budget) return;  // (uniform) every surplus row of this tile lies beyond the budget
     for (u32 k = tid; k < p.m; k += kBlock) ct[k] = cut[k];
+    if (thr)
+        for (u32 k = tid; k < p.m; k += kBlock) th[k] = thr[k];
     __syncthreads();
     u64 sel = 0;
     const u64 lo = (u64)t * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
@@ -6403,7 +6426,8 @@ __global__ __launch_bounds__(kBlock) void k_shed_pack(const u32* __restrict__ as
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 cc[k] = c4[k]; ll[k] = l4[k];
-                sp[k] = i0 + k < hi && c4[k] < p.m && aa[k] != kAffInactive && i0 + k >= (u64)ct[c4[k]];
+                sp[k] = i0 + k < hi && c4[k] < p.m && aa[k] != kAffInactive &&
+                        shed_surplus(thr ? th + c4[k] : nullptr, l4[k], i0 + k, ct[c4[k]]);
             }
         }
         u64 tot;
@@ -6585,6 +6609,132 @@ __global__ __launch_bounds__(kBlock) void k_shed_finish(u64 K, const u32* __rest
         }
 }
 
+// ---- the load-ordered cut (R1'): a segmented, weighted radix selection ----------------------------------------------------
+// Per over node (slot) the threshold tau is the smallest load with  sum{candidates of load <= tau} > free.  It is found digit
+// by digit from the top: a pass adds the LOAD of every candidate that agrees with the digits already chosen for its slot (pre)
+// into hist[slot][digit]; k_shed_sel_pick then takes the first bin whose inclusive sum passes rem, and rem loses the bins
+// below it.  Such a bin always exists: the host makes a slot only where the candidates exceed free, and the bin picked holds
+// more than the rem it leaves.  Zero loads add nothing, so tau >= 1.  All sums are integers (u32 loads over < 2^31 rows).
+//   k_shed_sel_hist<true>   slots <= kShSelLdsSlots: the (slot x digit) histogram of the pass in LDS, one LDS atomic per
+//                           candidate (as k_shed_tile), flushed once per workgroup with one global atomic per non-zero bin.
+//                           The digit is as wide as kShSelLdsBytes allow (11 bits for <= 6 slots, 2 bits for 3 072): narrow
+//                           digits mean more passes, but a pass over 10 M rows costs 22 us at 103 slots (6 bits) and 29 us
+//                           at 692 (4 bits), whereas ...
+//   k_shed_sel_hist<false>  more slots: with skewed loads nearly every candidate of a node falls into ONE bin (its top digits
+//                           are 0), so the lanes of a wave are summed by key first (shed_agg_add): one global atomic per wave
+//                           step and distinct (slot, digit).  ... a pass of this form cost ~460 us at the same 692 slots with
+//                           11-bit digits (not traced: a wave holds ~40 distinct slots, and every one is
+//                           a round of the aggregation loop), so it runs only where the LDS form cannot
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void k_shed_sel_hist(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                          const u32* __restrict__ aff, u64 n, u32 m, u32 S,
+                                                          const u32* __restrict__ map, const u32* __restrict__ pre, u32 himask,
+                                                          u32 shift, u32 bins, u32 stride, u64* __restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32* mp = reinterpret_cast<u32*>(smem);  // [m]
+    u32* pr = mp + m;                        // [S]
+    u64* h = reinterpret_cast<u64*>(smem + ((((size_t)m + S) * sizeof(u32) + 15) & ~(size_t)15));  // [S * bins], LDS form only
+    const int tid = threadIdx.x;
+    for (u32 k = tid; k < m; k += kBlock) mp[k] = map[k];
+    for (u32 k = tid; k < S; k += kBlock) pr[k] = pre[k];
+    if (LDS)
+        for (u32 k = tid; k < S * bins; k += kBlock) h[k] = 0;
+    __syncthreads();
+    const u64 nvec = (n + 3) / 4;
+    for (u64 v0 = (u64)blockIdx.x * kBlock; v0 < nvec; v0 += (u64)gridDim.x * kBlock) {  // (uniform: shed_agg_add needs the wave)
+        const u64 v = v0 + tid, i0 = v * 4;
+        u32 cc[4] = {kNone, kNone, kNone, kNone}, ll[4] = {0, 0, 0, 0}, aa[4] = {0, 0, 0, 0};
+        if (v < nvec) {
+            const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
+            const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
+            const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
+            cc[0] = c.x; cc[1] = c.y; cc[2] = c.z; cc[3] = c.w;
+            ll[0] = l.x; ll[1] = l.y; ll[2] = l.z; ll[3] = l.w;
+            aa[0] = a.x; aa[1] = a.y; aa[2] = a.z; aa[3] = a.w;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            bool act = i0 + k < n && cc[k] < m && aa[k] != kAffInactive && ll[k] != 0;
+            u32 sl = kNone;
+            if (act) sl = mp[cc[k]];
+            act = act && sl != kNone;
+            if (act) act = (ll[k] & himask) == pr[sl];
+            const u32 d = (ll[k] >> shift) & (bins - 1);
+            if (LDS) {
+                if (act) atomicAdd(&h[sl * bins + d], (u64)ll[k]);
+            } else {
+                shed_agg_add(hist, act ? sl * stride + d : 0u, (u64)ll[k], act, false);
+            }
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        for (u32 k = tid; k < S * bins; k += kBlock)
+            if (h[k]) atomicAdd(&hist[(size_t)(k / bins) * stride + (k % bins)], h[k]);
+    }
+}
+
+// One workgroup per slot: the first bin whose inclusive sum passes rem is the next digit; the row of bins is left zeroed for
+// the next pass.  last: thr[node] = the threshold; slot_free keeps rem = free - (the load of the candidates below it).
+__global__ __launch_bounds__(kBlock) void k_shed_sel_pick(u64* __restrict__ hist, u32 bins, u32 stride, u32 shift, bool last,
+                                                          const u32* __restrict__ slot_node, u64* __restrict__ slot_free,
+                                                          u32* __restrict__ pre, u32* __restrict__ thr) {
+    __shared__ u64 part[16];
+    const int tid = threadIdx.x;
+    const u32 sl = blockIdx.x;
+    u64* row = hist + (size_t)sl * stride;
+    const u64 rem = slot_free[sl];
+    const u32 b0 = 2 * tid, b1 = b0 + 1;  // bins <= 2 * kBlock
+    const u64 v0 = b0 < bins ? row[b0] : 0ull, v1 = b1 < bins ? row[b1] : 0ull;
+    const u64 ex = block_excl_scan_1024(v0 + v1, false, part, nullptr);
+    if (b0 < bins) row[b0] = 0;
+    if (b1 < bins) row[b1] = 0;
+    u32 d = kNone;
+    u64 below = 0;
+    if (ex <= rem && ex + v0 > rem) { d = b0; below = ex; }
+    else if (ex + v0 <= rem && ex + v0 + v1 > rem) { d = b1; below = ex + v0; }
+    if (d != kNone) {  // exactly one lane: the prefix never decreases and the row's total is above rem
+        const u32 p = pre[sl] | (d << shift);
+        pre[sl] = p;
+        slot_free[sl] = rem - below;
+        if (last) thr[slot_node[sl]] = p;
+    }
+}
+
+ShSelPlan sh_sel_plan(u32 s) {
+    ShSelPlan q{};
+    q.lds = s <= kShSelLdsSlots;
+    const u64 room = q.lds ? kShSelLdsBytes / sizeof(u64) : kShMaxEntries;
+    u32 bits = 1;
+    while (bits < 11 && ((u64)(s ? s : 1) << (bits + 1)) <= room) ++bits;
+    q.bits = bits;
+    q.passes = (32 + bits - 1) / bits;
+    return q;
+}
+
+void launch_shed_select(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u32 s, const u32* map,
+                        const u32* slot_node, u64* slot_free, u32* pre, u64* hist, u32* thr, hipStream_t st) {
+    launch_fill_u32(thr, m, kNone, st);
+    if (!s || !n) return;
+    const ShSelPlan q = sh_sel_plan(s);
+    const u32 stride = 1u << q.bits;
+    (void)hipMemsetAsync(pre, 0, (size_t)s * sizeof(u32), st);
+    (void)hipMemsetAsync(hist, 0, ((size_t)s << q.bits) * sizeof(u64), st);
+    const dim3 grid(grid_for((n + 3) / 4, kBlock, 256)), block(kBlock);
+    const size_t head = (((size_t)m + s) * sizeof(u32) + 15) & ~(size_t)15;
+    for (u32 pass = 0; pass < q.passes; ++pass) {
+        const u32 hi = 32 - pass * q.bits, lo = hi > q.bits ? hi - q.bits : 0;
+        const u32 bins = 1u << (hi - lo), himask = hi == 32 ? 0u : ~0u << hi;
+        if (q.lds)
+            hipLaunchKernelGGL((k_shed_sel_hist<true>), grid, block, head + (size_t)s * bins * sizeof(u64), st, assign, load, aff,
+                               n, m, s, map, pre, himask, lo, bins, stride, hist);
+        else
+            hipLaunchKernelGGL((k_shed_sel_hist<false>), grid, block, head, st, assign, load, aff, n, m, s, map, pre, himask, lo,
+                               bins, stride, hist);
+        hipLaunchKernelGGL(k_shed_sel_pick, dim3(s), block, 0, st, hist, bins, stride, lo, lo == 0, slot_node, slot_free, pre, thr);
+    }
+}
+
 ShPlan sh_plan(u64 n, u32 m, u32 s) {
     ShPlan p{};
     p.n = n; p.m = m; p.s = s;
@@ -6599,6 +6749,10 @@ ShPlan sh_plan(u64 n, u32 m, u32 s) {
     return p;
 }
 size_t shed_order_lds(u32 m) { return ((rank_tab_bytes(m) + 15) & ~(size_t)15) + ((size_t)m + 16) * sizeof(u64); }
+// k_shed_tile: the slots' sums, the node map and (load-ordered cut only) the nodes' thresholds
+static size_t shed_tile_lds(const ShPlan& p, const u32* thr) {
+    return (size_t)p.s * sizeof(u64) + (size_t)p.m * sizeof(u32) * (thr ? 2 : 1);
+}
 
 void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u64* used, u64* pin, hipStream_t s) {
     (void)hipMemsetAsync(used, 0, (size_t)m * sizeof(u64), s);
@@ -6608,21 +6762,21 @@ void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n,
                        assign, load, aff, n, m, used, pin);
 }
 void launch_shed_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
-                     const u64* slot_free, u64* mat, u32* cut, hipStream_t s) {
+                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, hipStream_t s) {
     launch_fill_u32(cut, p.m, kNone, s);
-    hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), (size_t)p.s * sizeof(u64) + (size_t)p.m * sizeof(u32), s, assign,
-                       load, aff, p, map, mat);
-    hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, cut);
+    hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), shed_tile_lds(p, thr), s, assign, load, aff, p, map, thr, mat);
+    hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, thr, cut);
 }
-void launch_shed_count(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, u32* tcnt, u64* acc,
-                       hipStream_t s) {
-    hipLaunchKernelGGL(k_shed_count, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32), s, assign, load, aff, p, cut, tcnt, acc);
+void launch_shed_count(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* thr,
+                       u32* tcnt, u64* acc, hipStream_t s) {
+    hipLaunchKernelGGL(k_shed_count, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32) * (thr ? 2 : 1), s, assign, load, aff, p,
+                       cut, thr, tcnt, acc);
     hipLaunchKernelGGL((k_shed_scan<u32>), dim3(1), dim3(kBlock), 0, s, tcnt, tcnt, (u64)p.nt, acc + kShAccSurplusRows, (const u64*)nullptr);
 }
-void launch_shed_pack(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* toff,
-                      u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s) {
-    hipLaunchKernelGGL(k_shed_pack, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32), s, assign, load, aff, p, cut, toff,
-                       budget, pk_row, pk_load, pk_node, used, acc);
+void launch_shed_pack(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* thr,
+                      const u32* toff, u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s) {
+    hipLaunchKernelGGL(k_shed_pack, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32) * (thr ? 2 : 1), s, assign, load, aff, p,
+                       cut, thr, toff, budget, pk_row, pk_load, pk_node, used, acc);
 }
 void launch_shed_round(u64 K, const u32* pk_load, u32* pk_node, const u64* tgt, u32 m, u64* used, u64* csum, u64* C, u32* ord,
                        u32* cntp, hipStream_t s) {
@@ -6804,9 +6958,10 @@ void launch_shrb_import_x(const ShrbImport& a, hipStream_t s) {
 void launch_shrb_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
                      const u64* slot_free, u64* mat, u32* cut, hipStream_t s) {
     if (!p.s || !p.n) return;
-    hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), (size_t)p.s * sizeof(u64) + (size_t)p.m * sizeof(u32), s, assign,
-                       load, aff, p, map, mat);
-    hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, cut);
+    const u32* const row_order = nullptr;  // (the load-ordered cut is not sharded)
+    hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), shed_tile_lds(p, row_order), s, assign, load, aff, p, map, row_order,
+                       mat);
+    hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, row_order, cut);
 }
 void launch_shrb_export_y(const u64* v, u32 m, const u64* a, u64 b, u64* Y, hipStream_t s) {
     hipLaunchKernelGGL(k_shrb_export_y, dim3(1), dim3(kBlock), 0, s, v, m, a, b, Y);

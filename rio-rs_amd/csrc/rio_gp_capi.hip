@@ -510,7 +510,8 @@ struct rio_gp {
     u32 ni_force_tile = 0;                 // lab builds: rows per tile (rio_gp_debug_set_node_index)
     // bounded rebalance (rio_gp_rebalance), grown on use: per-node arrays + counters, the (over node x tile) matrix, per-tile and
     // per-chunk counts, the packed rows (row | load | node), the host-pointer form's move listing (row | from | to)
-    DevBuf sh_nodes, sh_mat, sh_tile, sh_chunk, sh_pk, sh_mv;
+    // ... and the load-ordered cut's (slot x digit) histogram
+    DevBuf sh_nodes, sh_mat, sh_tile, sh_chunk, sh_pk, sh_mv, sh_sel;
     RbSession rb;  // row-sharded rebalance (rio_gp_shard_rebalance_*)
     // change feed (rio_gp_changes), allocated on first use: the checkpoint column B (cap_rows u32, RIO_GP_NONE to begin with), the
     // per-tile counts, the workgroup sums + total, a mapped word the total arrives in; the host-pointer form's staged listing
@@ -1408,7 +1409,7 @@ void rio_gp_destroy(rio_gp_t* h) {
     if (h->vrec.p) (void)hipFree(h->vrec.p);
     if (h->part.p) (void)hipFree(h->part.p);
     if (h->ni_rows.p) (void)hipFree(h->ni_rows.p);
-    for (DevBuf* b : {&h->sh_nodes, &h->sh_mat, &h->sh_tile, &h->sh_chunk, &h->sh_pk, &h->sh_mv})
+    for (DevBuf* b : {&h->sh_nodes, &h->sh_mat, &h->sh_tile, &h->sh_chunk, &h->sh_pk, &h->sh_mv, &h->sh_sel})
         if (b->p) (void)hipFree(b->p);
     if (h->chg_stage.p) (void)hipFree(h->chg_stage.p);
     if (h->h_ni) (void)hipHostFree(h->h_ni);
@@ -1748,10 +1749,34 @@ int rio_gp_rows_on_nodes_dev(rio_gp_t* h, const uint64_t* node_bitmap, uint64_t*
 
 // ---- bounded rebalance ----------------------------------------------------------------------
 
+// struct_size is the ABI guard of rio_gp_rebalance_cfg: the struct as it was before `order` (up to `target`) means row order and
+// its later fields are not read; the whole struct carries an order.  NULL, or what is wrong with the cfg.
+constexpr size_t kRebalanceCfgV1 = offsetof(rio_gp_rebalance_cfg, order);
+static const char* rebalance_cfg_order(const rio_gp_rebalance_cfg* cfg, u32* order) {
+    *order = RIO_GP_REBALANCE_ROW_ORDER;
+    if (!cfg) return "cfg missing";
+    if (cfg->struct_size == kRebalanceCfgV1) return nullptr;
+    if (cfg->struct_size != sizeof(rio_gp_rebalance_cfg)) return "struct_size differs";
+    if (cfg->order != RIO_GP_REBALANCE_ROW_ORDER && cfg->order != RIO_GP_REBALANCE_BY_LOAD) return "unknown order";
+    if (cfg->reserved != 0) return "reserved is not 0";
+    *order = cfg->order;
+    return nullptr;
+}
+
+// R1' (RIO_GP_REBALANCE_BY_LOAD): thr[j] of the S over nodes; slot_free becomes what is left for the candidates of that load
+static int rebalance_select(rio_gp* h, u32 S, const u32* map, const u32* slot_node, u64* slot_free, u32* pre, u32* thr) {
+    const ShSelPlan q = sh_sel_plan(S);
+    int rc;
+    if ((rc = ensure(h, h->sh_sel, ((size_t)S << q.bits) * sizeof(u64)))) return rc;
+    launch_shed_select(h->assign[h->cur], h->load, h->aff, h->n, h->m, S, map, slot_node, slot_free, pre, (u64*)h->sh_sel.p, thr,
+                       h->stream);
+    return RIO_GP_OK;
+}
+
 // The device-side work of rio_gp_rebalance[_dev] (validated, locked).  d_rows / d_from / d_to: device arrays of at least
 // `budget` entries, or all NULL.
-static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 rounds, u64 budget, rio_gp_rebalance_stats* st,
-                            u32* d_rows, u32* d_from, u32* d_to, uint64_t* n_moves) {
+static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 order, u32 rounds, u64 budget,
+                            rio_gp_rebalance_stats* st, u32* d_rows, u32* d_from, u32* d_to, uint64_t* n_moves) {
     rio_gp_rebalance_stats s{};
     if (n_moves) *n_moves = 0;
     HIPCHK(h, hipSetDevice(h->device));
@@ -1760,9 +1785,9 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 roun
     const u32 m = h->m, M = h->cap_nodes;
     const u64 n = h->n;
     // per-node arrays: pin | tgt (0 on dead nodes) | slot_free | C [M + 1] | acc [kShAcc] (u64), then map | slot_node | cut |
-    // ord | cnt (u32)
+    // ord | thr | pre | cnt (u32)
     int rc;
-    const size_t u64s = 4 * (size_t)M + 1 + kShAcc, u32s = 4 * (size_t)M + 4;
+    const size_t u64s = 4 * (size_t)M + 1 + kShAcc, u32s = 6 * (size_t)M + 4;
     if ((rc = ensure(h, h->sh_nodes, u64s * sizeof(u64) + u32s * sizeof(u32)))) return rc;
     u64* pin = (u64*)h->sh_nodes.p;
     u64* tgt = pin + M;
@@ -1773,7 +1798,11 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 roun
     u32* slot_node = map + M;
     u32* cut = slot_node + M;
     u32* ord = cut + M;
-    u32* cntp = ord + M;
+    u32* thr_buf = ord + M;
+    u32* pre = thr_buf + M;
+    u32* cntp = pre + M;
+    const bool by_load = order == RIO_GP_REBALANCE_BY_LOAD;
+    const u32* const thr = by_load ? thr_buf : nullptr;  // (nullptr: the k_shed_* kernels cut in row order)
     // the targets (the capacities by default) and the live nodes
     std::vector<u64> T(m ? m : 1), used(m ? m : 1), pn(m ? m : 1);
     if (cfg->target) memcpy(T.data(), cfg->target, (size_t)m * sizeof(u64));
@@ -1808,8 +1837,9 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 roun
             HIPCHK(h, hipMemcpyAsync(slot_node, snode.data(), (size_t)S * sizeof(u32), hipMemcpyHostToDevice, h->stream));
             HIPCHK(h, hipMemcpyAsync(slot_free, sfree.data(), (size_t)S * sizeof(u64), hipMemcpyHostToDevice, h->stream));
             HIPCHK(h, hipMemsetAsync(acc, 0, kShAcc * sizeof(u64), h->stream));
-            launch_shed_cut(h->assign[h->cur], h->load, h->aff, p, map, slot_node, slot_free, (u64*)h->sh_mat.p, cut, h->stream);
-            launch_shed_count(h->assign[h->cur], h->load, h->aff, p, cut, (u32*)h->sh_tile.p, acc, h->stream);
+            if (by_load && (rc = rebalance_select(h, S, map, slot_node, slot_free, pre, thr_buf))) return rc;
+            launch_shed_cut(h->assign[h->cur], h->load, h->aff, p, map, slot_node, slot_free, (u64*)h->sh_mat.p, cut, thr, h->stream);
+            launch_shed_count(h->assign[h->cur], h->load, h->aff, p, cut, thr, (u32*)h->sh_tile.p, acc, h->stream);
             HIPCHK(h, hipGetLastError());
             u64 a[kShAcc];
             HIPCHK(h, hipMemcpyAsync(a, acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
@@ -1830,8 +1860,10 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 roun
     HIPCHK(h, hipMemcpyAsync(slot_free, sfree.data(), (size_t)S * sizeof(u64), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(tgt, tl.data(), (size_t)m * sizeof(u64), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(acc, 0, kShAcc * sizeof(u64), h->stream));
-    launch_shed_cut(h->assign[h->cur], h->load, h->aff, p, map, slot_node, slot_free, (u64*)h->sh_mat.p, cut, h->stream);
-    launch_shed_count(h->assign[h->cur], h->load, h->aff, p, cut, (u32*)h->sh_tile.p, acc, h->stream);
+    // R1' first finds every over node's threshold: the cut below then falls among the candidates of exactly that load
+    if (by_load && (rc = rebalance_select(h, S, map, slot_node, slot_free, pre, thr_buf))) return rc;
+    launch_shed_cut(h->assign[h->cur], h->load, h->aff, p, map, slot_node, slot_free, (u64*)h->sh_mat.p, cut, thr, h->stream);
+    launch_shed_count(h->assign[h->cur], h->load, h->aff, p, cut, thr, (u32*)h->sh_tile.p, acc, h->stream);
     HIPCHK(h, hipGetLastError());
     u64 a[kShAcc];
     HIPCHK(h, hipMemcpyAsync(a, acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
@@ -1847,8 +1879,8 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 roun
         u32* pk_row = (u32*)h->sh_pk.p;
         u32* pk_load = pk_row + K;
         u32* pk_node = pk_load + K;
-        launch_shed_pack(h->assign[h->cur], h->load, h->aff, p, cut, (const u32*)h->sh_tile.p, K, pk_row, pk_load, pk_node, d_used,
-                         acc, h->stream);
+        launch_shed_pack(h->assign[h->cur], h->load, h->aff, p, cut, thr, (const u32*)h->sh_tile.p, K, pk_row, pk_load, pk_node,
+                         d_used, acc, h->stream);
         for (u32 r = 0; r < rounds; ++r)
             launch_shed_round(K, pk_load, pk_node, tgt, m, d_used, (u64*)h->sh_chunk.p, C, ord, cntp, h->stream);
         launch_shed_finish(K, pk_row, pk_load, pk_node, h->assign[h->cur], d_used, (u32*)h->sh_chunk.p, acc, d_rows, d_from, d_to,
@@ -1870,9 +1902,8 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 roun
 
 // checks shared by both forms: nothing is changed before they pass
 static int rebalance_args(rio_gp* h, const rio_gp_rebalance_cfg* cfg, const void* r, const void* f, const void* t, uint64_t cap,
-                          u32* rounds, u64* budget) {
-    if (!cfg || cfg->struct_size != sizeof(rio_gp_rebalance_cfg))
-        return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: cfg missing or struct_size differs");
+                          u32* order, u32* rounds, u64* budget) {
+    if (const char* why = rebalance_cfg_order(cfg, order)) return fail(h, RIO_GP_EINVAL, std::string("rio_gp_rebalance: ") + why);
     if (cfg->rounds > 8) return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: rounds above the solver limit (8)");
     if ((r != nullptr) != (f != nullptr) || (r != nullptr) != (t != nullptr))
         return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: out_rows / out_from / out_to are given together or not at all");
@@ -1888,10 +1919,10 @@ int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebala
                      uint32_t* out_from, uint32_t* out_to, uint64_t moves_cap, uint64_t* n_moves) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    u32 rounds;
+    u32 order, rounds;
     u64 budget;
     int rc;
-    if ((rc = rebalance_args(h, cfg, out_rows, out_from, out_to, moves_cap, &rounds, &budget))) return rc;
+    if ((rc = rebalance_args(h, cfg, out_rows, out_from, out_to, moves_cap, &order, &rounds, &budget))) return rc;
     // the listing is staged on the device (moves <= selected <= budget <= min(n, moves_cap))
     u32* d = nullptr;
     u64 stage = 0;
@@ -1901,7 +1932,8 @@ int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebala
         d = (u32*)h->sh_mv.p;
     }
     uint64_t nm = 0;
-    if ((rc = rebalance_locked(h, cfg, rounds, budget, st, d, d ? d + stage : nullptr, d ? d + 2 * stage : nullptr, &nm))) return rc;
+    if ((rc = rebalance_locked(h, cfg, order, rounds, budget, st, d, d ? d + stage : nullptr, d ? d + 2 * stage : nullptr, &nm)))
+        return rc;
     if (n_moves) *n_moves = nm;
     if (out_rows && nm) {
         HIPCHK(h, hipMemcpyAsync(out_rows, d, nm * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
@@ -1916,11 +1948,11 @@ int rio_gp_rebalance_dev(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_re
                          uint32_t* d_from, uint32_t* d_to, uint64_t moves_cap, uint64_t* n_moves) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    u32 rounds;
+    u32 order, rounds;
     u64 budget;
     int rc;
-    if ((rc = rebalance_args(h, cfg, d_rows, d_from, d_to, moves_cap, &rounds, &budget))) return rc;
-    return rebalance_locked(h, cfg, rounds, budget, st, d_rows, d_from, d_to, n_moves);
+    if ((rc = rebalance_args(h, cfg, d_rows, d_from, d_to, moves_cap, &order, &rounds, &budget))) return rc;
+    return rebalance_locked(h, cfg, order, rounds, budget, st, d_rows, d_from, d_to, n_moves);
 }
 
 // ---- change feed -----------------------------------------------------------------------------
@@ -3559,8 +3591,12 @@ int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, u
                                  uint64_t moves_cap, uint64_t* d_x, uint32_t* rounds_out) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    if (!cfg || cfg->struct_size != sizeof(rio_gp_rebalance_cfg))
+    u32 order;
+    if (rebalance_cfg_order(cfg, &order))
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: cfg missing or struct_size differs");
+    if (order != RIO_GP_REBALANCE_ROW_ORDER)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: the load-ordered cut (order = RIO_GP_REBALANCE_BY_LOAD) is not "
+                                      "implemented for a row-sharded table; use order = RIO_GP_REBALANCE_ROW_ORDER");
     if (cfg->rounds > 8) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: rounds above the solver limit (8)");
     if (!d_x || n_ranks == 0 || rank >= n_ranks) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: rank >= n_ranks, or no record");
     if (!list_moves && moves_cap) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: moves_cap without a move listing");
@@ -3636,7 +3672,7 @@ int rio_gp_shard_rebalance_cut(rio_gp_t* h, const uint64_t* d_xg, uint64_t* d_s,
             (rc = ensure(h, h->sh_tile, (size_t)p.nt * sizeof(u32))))
             return rc;
         launch_shrb_cut(h->assign[h->cur], h->load, h->aff, p, b.map, b.slot_node, b.slot_free, (u64*)h->sh_mat.p, b.cut, h->stream);
-        launch_shed_count(h->assign[h->cur], h->load, h->aff, p, b.cut, (u32*)h->sh_tile.p, b.acc, h->stream);
+        launch_shed_count(h->assign[h->cur], h->load, h->aff, p, b.cut, /*thr=*/nullptr, (u32*)h->sh_tile.p, b.acc, h->stream);
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(d_s, b.acc, 2 * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));  // surplus rows | load
     }
@@ -3673,8 +3709,8 @@ int rio_gp_shard_rebalance_select(rio_gp_t* h, const uint64_t* d_sg, uint64_t* d
         const u64 nc = (K + kShChunk - 1) / kShChunk;
         if ((rc = ensure(h, h->sh_pk, 3 * K * sizeof(u32))) || (rc = ensure(h, h->sh_chunk, nc * sizeof(u64)))) return rc;
         u32* pk_row = (u32*)h->sh_pk.p;
-        launch_shed_pack(h->assign[h->cur], h->load, h->aff, rb.plan, b.cut, (const u32*)h->sh_tile.p, K, pk_row, pk_row + K,
-                         pk_row + 2 * K, b.lu, b.acc, h->stream);
+        launch_shed_pack(h->assign[h->cur], h->load, h->aff, rb.plan, b.cut, /*thr=*/nullptr, (const u32*)h->sh_tile.p, K, pk_row,
+                         pk_row + K, pk_row + 2 * K, b.lu, b.acc, h->stream);
     }
     launch_shrb_export_y(b.lu, m, b.acc + kShAccSelectedLoad, K, reinterpret_cast<u64*>(d_y), h->stream);
     HIPCHK(h, hipGetLastError());

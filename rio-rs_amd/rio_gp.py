@@ -67,8 +67,13 @@ class LoadFoldStats(C.Structure):
         (k, C.c_uint32) for k in ("max_load_after", "reserved")]
 
 
+REBALANCE_ROW_ORDER, REBALANCE_BY_LOAD = 0, 1   # rio_gp_rebalance_cfg.order: R1 (row order) / R1' (the heaviest rows first)
+REBALANCE_CFG_V1_SIZE = 24                      # struct_size of the struct without `order`: accepted, means row order
+
+
 class RebalanceCfg(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("rounds", C.c_uint32), ("max_moves", C.c_uint64), ("target", C.c_void_p)]
+    _fields_ = [("struct_size", C.c_uint32), ("rounds", C.c_uint32), ("max_moves", C.c_uint64), ("target", C.c_void_p),
+                ("order", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class RebalanceStats(C.Structure):
@@ -500,19 +505,21 @@ class GpuPlacement:
         return map, self.remap_nodes(map)
 
     # -- bounded rebalance --
-    def _rebalance_cfg(self, target, max_moves, rounds):
+    def _rebalance_cfg(self, target, max_moves, rounds, order=REBALANCE_ROW_ORDER):
         t = None if target is None else np.ascontiguousarray(target, np.uint64)
         if t is not None and len(t) < self.num_nodes:
             raise ValueError("target needs one entry per node")
         cfg = RebalanceCfg(C.sizeof(RebalanceCfg), int(rounds), CAP_INF if max_moves is None else int(max_moves),
-                           None if t is None else t.ctypes.data)
+                           None if t is None else t.ctypes.data, int(order), 0)
         return cfg, t
 
-    def rebalance(self, target=None, max_moves=None, rounds=0, list_moves=True, moves_cap=None):
+    def rebalance(self, target=None, max_moves=None, rounds=0, list_moves=True, moves_cap=None, order=REBALANCE_ROW_ORDER):
         """rio_gp_rebalance: (stats dict, rows, from, to) — the moves in row order (uint32 arrays; empty with
         list_moves=False).  target: m u64 (None: the capacities); max_moves None: no limit; rounds 0: the handle's
-        spill_rounds.  moves_cap: the listing's capacity (default: max_moves bounded by the table size)."""
-        cfg, _keep = self._rebalance_cfg(target, max_moves, rounds)
+        spill_rounds.  moves_cap: the listing's capacity (default: max_moves bounded by the table size).  order:
+        REBALANCE_ROW_ORDER (R1: a node's candidates are cut in row order) or REBALANCE_BY_LOAD (R1': in (load, row) order, so
+        a node sheds its heaviest rows — the fewest rows that bring it under its target)."""
+        cfg, _keep = self._rebalance_cfg(target, max_moves, rounds, order)
         st, nm = RebalanceStats(), C.c_uint64(0)
         if list_moves:
             cap = moves_cap if moves_cap is not None else min(cfg.max_moves, self.num_objects)
@@ -526,10 +533,11 @@ class GpuPlacement:
         e = np.empty(0, np.uint32)
         return st.as_dict(), e, e, e
 
-    def rebalance_dev(self, d_rows=None, d_from=None, d_to=None, moves_cap=0, target=None, max_moves=None, rounds=0):
+    def rebalance_dev(self, d_rows=None, d_from=None, d_to=None, moves_cap=0, target=None, max_moves=None, rounds=0,
+                      order=REBALANCE_ROW_ORDER):
         """rio_gp_rebalance_dev: the moves into device arrays (ints, e.g. torch tensors' data_ptr(); all None: counts only).
-        Returns (stats dict, n_moves)."""
-        cfg, _keep = self._rebalance_cfg(target, max_moves, rounds)
+        order as in rebalance().  Returns (stats dict, n_moves)."""
+        cfg, _keep = self._rebalance_cfg(target, max_moves, rounds, order)
         st, nm = RebalanceStats(), C.c_uint64(0)
         self._chk(self._L.rio_gp_rebalance_dev(self._h, C.byref(cfg), C.byref(st), _vp(d_rows) if d_rows else None,
                                                _vp(d_from) if d_from else None, _vp(d_to) if d_to else None, int(moves_cap),
@@ -942,6 +950,7 @@ def _oplib():
                                        C.POINTER(C.POINTER(C.c_size_t)), C.POINTER(C.POINTER(C.c_char_p)),
                                        C.POINTER(C.POINTER(C.c_size_t)), C.POINTER(C.POINTER(C.c_char_p)),
                                        C.POINTER(C.POINTER(C.c_char_p))]
+        L.rio_op_rebalance_ordered.argtypes = [_vp, C.c_uint32] + L.rio_op_rebalance.argtypes[1:]
         bind_op_changes(L)
         bind_op_expire(L)
         bind_op_loads(L)
@@ -1249,14 +1258,19 @@ class GpuObjectPlacement:
         return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), addr[k].decode())
                 for k in range(n.value)]
 
-    def rebalance(self, max_moves=None):
-        """rio_op_rebalance: [(struct_name, object_id, from_address, to_address)] of the objects moved off servers over their
-        member capacity (max_moves None: no limit), in the dense layer's row order."""
+    def rebalance(self, max_moves=None, order=REBALANCE_ROW_ORDER):
+        """rio_op_rebalance / rio_op_rebalance_ordered: [(struct_name, object_id, from_address, to_address)] of the objects
+        moved off servers over their member capacity (max_moves None: no limit), in the dense layer's row order.  order =
+        REBALANCE_BY_LOAD: every such server sheds its heaviest objects first (after fold_loads: the fewest moves)."""
         n = C.c_uint64(0)
         ty, oid, fa, ta = (C.POINTER(C.c_char_p)() for _ in range(4))
         tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
-        self._chk(_oplib().rio_op_rebalance(self._h, CAP_INF if max_moves is None else int(max_moves), C.byref(n), C.byref(ty),
-                                            C.byref(tl), C.byref(oid), C.byref(il), C.byref(fa), C.byref(ta)))
+        B = CAP_INF if max_moves is None else int(max_moves)
+        out = (C.byref(n), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il), C.byref(fa), C.byref(ta))
+        if order == REBALANCE_ROW_ORDER:
+            self._chk(_oplib().rio_op_rebalance(self._h, B, *out))
+        else:
+            self._chk(_oplib().rio_op_rebalance_ordered(self._h, int(order), B, *out))
         tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
         return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), fa[k].decode(), ta[k].decode())
                 for k in range(n.value)]

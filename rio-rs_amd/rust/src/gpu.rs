@@ -108,6 +108,9 @@ extern "C" {
                               n_candidates: *mut u64, tys: *mut *const *const c_char, ty_lens: *mut *const usize,
                               ids: *mut *const *const c_char, id_lens: *mut *const usize, addrs: *mut *const *const c_char,
                               loads: *mut u32) -> c_int;
+    fn rio_op_rebalance_ordered(p: *mut c_void, order: u32, max_moves: u64, n_out: *mut u64, tys: *mut *const *const c_char,
+                                ty_lens: *mut *const usize, ids: *mut *const *const c_char, id_lens: *mut *const usize,
+                                from_addrs: *mut *const *const c_char, to_addrs: *mut *const *const c_char) -> c_int;
     fn rio_op_tick(p: *mut c_void, stats: *mut RioGpStats) -> c_int;
     fn rio_op_snapshot(p: *mut c_void, n_out: *mut u64, tys: *mut *const *const c_char, ids: *mut *const *const c_char,
                        addrs: *mut *const *const c_char) -> c_int;
@@ -372,6 +375,31 @@ impl GpuObjectPlacement {
                  if a.is_null() { None } else { Some(unsafe { CStr::from_ptr(a) }.to_string_lossy().into_owned()) }, loads[k])
             }).collect();
             Ok((out, cand))
+        })
+        .await
+    }
+
+    /// Bounded rebalance by load (`RIO_GP_REBALANCE_BY_LOAD`, rule R1' of `rio_gp_rebalance`): every server that holds more
+    /// load than its member capacity sheds its HEAVIEST objects first — the fewest objects that bring it under its capacity;
+    /// an object of load 0 never moves — onto servers with room; at most `max_moves` objects (`None`: no limit), taken in
+    /// the dense layer's row order among those to shed.  The call to make after `fold_loads`: a move is an actor
+    /// deactivated on one server and activated on another.  Returns `(object, from_address, to_address)` per moved object.
+    pub async fn rebalance_by_load(&self, max_moves: Option<u64>)
+        -> Result<Vec<(ObjectId, String, String)>, ObjectPlacementError> {
+        const RIO_GP_REBALANCE_BY_LOAD: u32 = 1;
+        let me = self.clone();
+        blocking(move || {
+            let mut n = 0u64;
+            let (mut ty, mut id, mut fa, mut ta) = (std::ptr::null(), std::ptr::null(), std::ptr::null(), std::ptr::null());
+            let (mut tl, mut il) = (std::ptr::null(), std::ptr::null());
+            check(unsafe { rio_op_rebalance_ordered(me.inner.0, RIO_GP_REBALANCE_BY_LOAD, max_moves.unwrap_or(u64::MAX), &mut n,
+                                                    &mut ty, &mut tl, &mut id, &mut il, &mut fa, &mut ta) }, &me)?;
+            // the arrays are this thread's until its next call: read them here, before anything else can run
+            let key = |p: *const *const c_char, l: *const usize, k: usize| unsafe {
+                String::from_utf8_lossy(std::slice::from_raw_parts(*p.add(k) as *const u8, *l.add(k))).into_owned()
+            };
+            let addr = |p: *const *const c_char, k: usize| unsafe { CStr::from_ptr(*p.add(k)) }.to_string_lossy().into_owned();
+            Ok((0..n as usize).map(|k| (ObjectId(key(ty, tl, k), key(id, il, k)), addr(fa, k), addr(ta, k))).collect())
         })
         .await
     }
