@@ -705,11 +705,36 @@ int rio_gp_shard_exchange(rio_gp_t* h, const uint64_t* d_in, uint64_t* d_out, ui
  *   every round is one water-fill round over this rank's selected rows whose prefix starts at the pending load of the ranks
  *   < r; `used` is rebuilt from the summed records between rounds.
  *
+ * The load-ordered cut (cfg->order = RIO_GP_REBALANCE_BY_LOAD, rule R1') is started with rio_gp_shard_rebalance_begin_ordered.
+ * A node's threshold tau_j depends on its candidates on every rank, so R1 becomes a radix selection whose histograms are summed
+ * over the ranks; R0, R2, R3 and R4 are as above:
+ *
+ *   begin_ordered -> [all-gather X] -> cut -> nodes_over == 0 ? finish
+ *         :  threshold_plan -> { threshold_hist(p) -> [all-gather H] -> threshold_pick(p) } for p = 0 .. passes - 1
+ *         -> [all-gather S] -> select -> ... as above
+ *
+ *   H (`words` u64 of rio_gp_shard_rebalance_threshold_plan): per over node, in ascending node order on every rank, the load of
+ *       this rank's candidates by the digit of the pass, among those that agree with the digits chosen so far.  words =
+ *       (nodes over) << (digit bits) <= rio_gp_shard_words1: the digit (11 bits at most) is narrowed until the record is no
+ *       longer than X, so whatever carries X carries H (a window row of rio_gp_shard_exchange included).  The digits are those
+ *       of ceil(32 / digit bits) passes from bit 32 down; the passes whose digit lies wholly above the largest load are not run.
+ *       For that, word 2m of X (the first of the eight) carries, in a load-ordered session, the largest load among this rank's
+ *       object rows on a node < m (0 without one; the row-order protocol leaves the word 0).  Digit, passes and words follow
+ *       from the gathered X alone: every rank derives the same plan.
+ *
+ *   R1' on rank r: every globally over node is searched on every rank (a rank without a candidate of it, or without rows, adds
+ *   zeros).  The pick sums the gathered histograms in rank order and takes the first digit whose inclusive sum passes what is
+ *   left of the GLOBAL free_j.  After the last pass the bin of tau_j in rank q's histogram is tau_j * ties_q[j], and with c_j =
+ *   floor(what is left / tau_j) rank r keeps its first clamp(c_j - ties of the ranks < r, 0, ties_r[j]) candidates of load tau_j
+ *   in row order; its other candidates of that load and every heavier one are surplus, every lighter one (the zero-load ones
+ *   included, on every rank) is kept.
+ *
  * Handle state changes as in rio_gp_rebalance (joins rio_gp_tick_async work, drops an uncommitted solve, counts as a change of
  * the inputs); `used` is the GLOBAL one of the new column on every rank after finish.  RIO_GP_EINVAL, nothing changed: bad cfg /
  * struct_size, rounds > 8, rank >= n_ranks, moves_cap without list_moves, rio_gp_shard_tick_async ticks in flight, a step
- * called out of order, or cfg->order != RIO_GP_REBALANCE_ROW_ORDER (the load-ordered cut R1' is not sharded: a node's
- * threshold depends on its candidates on every rank).  begin may be called at any step: it starts over.  Between begin and finish the handle belongs to the
+ * called out of order (a threshold pass out of order, threshold_* in a row-order session and select before the last pick of a
+ * load-ordered one included), or cfg->order != RIO_GP_REBALANCE_ROW_ORDER in rio_gp_shard_rebalance_begin.  begin and
+ * begin_ordered may be called at any step: they start over.  Between begin and finish the handle belongs to the
  * protocol: a call that changes an input of the solve (nodes, liveness, objects, CRUD, a solve, a tick, rio_gp_rebalance) or
  * reads `used` (rio_gp_get_nodes) ends it, and the next step answers RIO_GP_EINVAL (the column is written by finish alone, so it
  * is as it was).  d_* are DEVICE pointers owned by the caller.
@@ -718,9 +743,23 @@ int rio_gp_shard_exchange(rio_gp_t* h, const uint64_t* d_in, uint64_t* d_out, ui
  * *rounds_out (may be NULL) = the rounds that will run at most (cfg->rounds, 0 = the handle's spill_rounds).  Asynchronous. */
 int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, uint32_t rank, uint32_t n_ranks, int list_moves,
                                  uint64_t moves_cap, uint64_t* d_x, uint32_t* rounds_out);
+/* rio_gp_shard_rebalance_begin that also takes cfg->order = RIO_GP_REBALANCE_BY_LOAD; with RIO_GP_REBALANCE_ROW_ORDER it is
+ * rio_gp_shard_rebalance_begin itself. */
+int rio_gp_shard_rebalance_begin_ordered(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, uint32_t rank, uint32_t n_ranks,
+                                         int list_moves, uint64_t moves_cap, uint64_t* d_x, uint32_t* rounds_out);
 /* d_xg[n_ranks][words1] gathered -> the global `used`, the cuts that fall on this rank, its surplus; d_s[words2] = S.
- * *nodes_over = live nodes holding more candidate load than free_j, on all ranks: 0 ends the protocol (finish). */
+ * *nodes_over = live nodes holding more candidate load than free_j, on all ranks: 0 ends the protocol (finish).  In a
+ * load-ordered session the surplus is not known yet: d_s is zeroed, and with nodes over the threshold passes come next. */
 int rio_gp_shard_rebalance_cut(rio_gp_t* h, const uint64_t* d_xg, uint64_t* d_s, uint32_t* nodes_over);
+/* Load-ordered sessions, after cut reported nodes over: the number of threshold passes and the u64 words of one rank's
+ * histogram record (the same on every rank; words <= rio_gp_shard_words1). */
+int rio_gp_shard_rebalance_threshold_plan(rio_gp_t* h, uint32_t* passes, uint64_t* words);
+/* Pass `pass` (0, 1, ... in order): d_h[words] = this rank's histogram.  Asynchronous. */
+int rio_gp_shard_rebalance_threshold_hist(rio_gp_t* h, uint32_t pass, uint64_t* d_h);
+/* d_hg[n_ranks][words] = the gathered histograms of `pass` -> its digit of every threshold.  The last pass also places this
+ * rank's cuts and writes d_s[words2] = S as cut does in a row-order session (d_s may be NULL on the earlier passes).
+ * Asynchronous. */
+int rio_gp_shard_rebalance_threshold_pick(rio_gp_t* h, uint32_t pass, const uint64_t* d_hg, uint64_t* d_s);
 /* d_sg[n_ranks][words2] gathered -> R2, the selected rows packed; d_y[words2] = Y.  *selected_local sizes the move arrays of
  * finish; *selected_total = min(B, surplus rows of all ranks): 0 ends the protocol (finish). */
 int rio_gp_shard_rebalance_select(rio_gp_t* h, const uint64_t* d_sg, uint64_t* d_y, uint64_t* selected_local,

@@ -441,8 +441,10 @@ struct ShPlan {
 };
 ShPlan sh_plan(u64 n, u32 m, u32 s);
 size_t shed_order_lds(u32 m);
-// used, pin: m u64 each (zeroed here): the load of every row on node j, the load of the non-object rows on it
-void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u64* used, u64* pin, hipStream_t s);
+// used, pin: m u64 each (zeroed here): the load of every row on node j, the load of the non-object rows on it; maxl (may be
+// nullptr): one u32 -> the largest load of an object row on a node < m
+void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u64* used, u64* pin, hipStream_t s,
+                      u32* maxl = nullptr);
 // map: node -> slot (kNone: not over); slot_node / slot_free: per slot; mat: s * nt u64; cut: m u32 (kNone where nothing is cut).
 // thr (m u32, or nullptr = row order) in the four launches below: the load-ordered cut's threshold per node (kNone on a node
 // that is not over).  With it the cut walks only the candidates whose load == thr[node] — slot_free is then what
@@ -480,6 +482,7 @@ void launch_shed_finish(u64 K, const u32* pk_row, const u32* pk_load, const u32*
 
 // --- row-sharded rebalance (rio_gp_shard_rebalance_*): the k_shed_* passes over one rank's rows; k_shrb_* carry the rank offsets ---
 constexpr int kShrbOver = 0, kShrbSlots = 1, kShrbForced = 2, kShrbOverBefore = 3, kShrbInfo = 4;  // u32 counters of k_shrb_import_x
+constexpr int kShrbMaxLoad = kShrbInfo;  // one more word, written by k_shrb_import_slots alone: the largest load on any rank
 struct ShrbImport {
     const u64* Xg;     // [R][2m + 8] gathered X records: pinned load | candidate load | counters
     u32 rank, R, m;
@@ -492,14 +495,30 @@ struct ShrbImport {
     u64* slot_free;    // -> per slot: what the lower ranks' candidates left of free_j
     u32* cut;          // -> [m] 0 where the cut fell on a lower rank (every candidate here is surplus), kNone elsewhere; the
                        //    slots' nodes are filled in by k_shed_cut
-    u32* info;         // -> [kShrbInfo]
+    u32* info;         // -> [kShrbInfo] (k_shrb_import_slots: [kShrbInfo + 1])
 };
-// X = pin | used - pin | 8 counters (0; the last one 1, as in the solve's record)
-void launch_shrb_export_x(const u64* used, const u64* pin, u32 m, u64* X, hipStream_t s);
+// X = pin | used - pin | 8 words: *maxl (nullptr: 0), five zeros, 1 (as in the solve's record)
+void launch_shrb_export_x(const u64* used, const u64* pin, u32 m, const u32* maxl, u64* X, hipStream_t s);
 void launch_shrb_import_x(const ShrbImport& a, hipStream_t s);
-// launch_shed_cut without resetting `cut` (k_shrb_import_x wrote it)
+// launch_shed_cut without resetting `cut` (k_shrb_import_x / k_shrb_import_slots wrote it); thr as in launch_shed_cut
 void launch_shrb_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
-                     const u64* slot_free, u64* mat, u32* cut, hipStream_t s);
+                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, hipStream_t s);
+// The load-ordered cut, sharded (kernels: k_shrb_import_slots, k_shed_sel_hist, k_shrb_sel_pick).  The slots are the globally
+// over nodes in ascending node order, the same on every rank; the plan depends on (S, m) alone and its histogram record,
+// S << bits u64, is never longer than an X record (shard_words1(m)): the digit is narrowed until it fits.
+ShSelPlan shrb_sel_plan(u32 S, u32 m);
+// the first pass of plan q that can pick a digit other than 0 when no load exceeds max_load (0: unknown, pass 0)
+u32 shrb_sel_first_pass(const ShSelPlan& q, u32 max_load);
+// launch_shrb_import_x for the load-ordered cut: info[kShrbSlots] = info[kShrbOver], info[kShrbMaxLoad] = the largest word 2m of
+// the gathered X records, slot_free = the global free_j, pre[slot] = 0, cut = thr = kNone on every node
+void launch_shrb_import_slots(const ShrbImport& a, u32* pre, u32* thr, hipStream_t s);
+// H (S << bits u64, zeroed here) = this rank's histogram of pass `pass`
+void launch_shrb_sel_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u32 S, const u32* map, const u32* pre,
+                          const ShSelPlan& q, u32 pass, u64* H, hipStream_t s);
+// Hg[R][S << bits] gathered -> the digit of every slot: pre, slot_free as launch_shed_select's passes leave them.  The last pass
+// sets thr[slot_node] and turns slot_free into the load of the ties THIS rank keeps (launch_shrb_cut with thr places the cut).
+void launch_shrb_sel_pick(const u64* Hg, u32 rank, u32 R, u32 S, const ShSelPlan& q, u32 pass, const u32* slot_node,
+                          u64* slot_free, u32* pre, u32* thr, hipStream_t s);
 // Y = v[m] | *a | b
 void launch_shrb_export_y(const u64* v, u32 m, const u64* a, u64 b, u64* Y, hipStream_t s);
 // used = (first ? 0 : used) + sum of the gathered Y[q][0..m) in rank order; *base = sum of Y[q][m] over q < rank;

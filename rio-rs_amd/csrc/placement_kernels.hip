@@ -6205,14 +6205,20 @@ __device__ __forceinline__ bool shed_surplus(const u32* th, u32 l, u64 row, u32 
     return l > t || (l == t && row >= (u64)cut);
 }
 
+// MAX (the row-sharded load-ordered cut): also *maxl = the largest load of an object row on a node < m — no candidate of any
+// node weighs more, so no threshold has a bit above its highest one
+template <bool MAX>
 __global__ __launch_bounds__(kBlock) void k_shed_hist(const u32* __restrict__ assign, const u32* __restrict__ load,
                                                       const u32* __restrict__ aff, u64 n, u32 m, u64* __restrict__ used,
-                                                      u64* __restrict__ pin) {
+                                                      u64* __restrict__ pin, u32* __restrict__ maxl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64* hu = reinterpret_cast<u64*>(smem);  // [m]
     u64* hp = hu + m;                        // [m]
+    __shared__ u32 s_mx;  // MAX only
     const int tid = threadIdx.x;
+    u32 mx = 0;
     for (u32 k = tid; k < 2 * m; k += kBlock) hu[k] = 0;
+    if (MAX && tid == 0) s_mx = 0;
     __syncthreads();
     const u64 nvec = (n + 3) / 4;
     for (u64 v = (u64)blockIdx.x * kBlock + tid; v < nvec; v += (u64)gridDim.x * kBlock) {
@@ -6226,13 +6232,23 @@ __global__ __launch_bounds__(kBlock) void k_shed_hist(const u32* __restrict__ as
             if (i0 + k < n && cc[k] < m && ll[k]) {
                 atomicAdd(&hu[cc[k]], (u64)ll[k]);
                 if (aa[k] == kAffInactive) atomicAdd(&hp[cc[k]], (u64)ll[k]);
+                else if (MAX && ll[k] > mx) mx = ll[k];
             }
+    }
+    if (MAX) {  // one global atomic per workgroup: thousands of waves on the one word would queue for tens of microseconds
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const u32 o = (u32)__shfl_xor((int)mx, d, 64);
+            mx = o > mx ? o : mx;
+        }
+        if ((tid & 63) == 0 && mx) atomicMax(&s_mx, mx);
     }
     __syncthreads();
     for (u32 k = tid; k < m; k += kBlock) {
         if (hu[k]) atomicAdd(&used[k], hu[k]);
         if (hp[k]) atomicAdd(&pin[k], hp[k]);
     }
+    if (MAX && tid == 0 && s_mx) atomicMax(maxl, s_mx);
 }
 
 __global__ __launch_bounds__(kBlock) void k_shed_tile(const u32* __restrict__ assign, const u32* __restrict__ load,
@@ -6701,15 +6717,41 @@ __global__ __launch_bounds__(kBlock) void k_shed_sel_pick(u64* __restrict__ hist
     }
 }
 
-ShSelPlan sh_sel_plan(u32 s) {
+// the widest digit whose (slot x digit) histogram fits the form's room and `most` u64 words
+static ShSelPlan sh_sel_plan_within(u32 s, u64 most) {
     ShSelPlan q{};
     q.lds = s <= kShSelLdsSlots;
-    const u64 room = q.lds ? kShSelLdsBytes / sizeof(u64) : kShMaxEntries;
+    const u64 room = std::min<u64>(q.lds ? kShSelLdsBytes / sizeof(u64) : kShMaxEntries, most);
     u32 bits = 1;
     while (bits < 11 && ((u64)(s ? s : 1) << (bits + 1)) <= room) ++bits;
     q.bits = bits;
     q.passes = (32 + bits - 1) / bits;
     return q;
+}
+ShSelPlan sh_sel_plan(u32 s) { return sh_sel_plan_within(s, kShMaxEntries); }
+ShSelPlan shrb_sel_plan(u32 s, u32 m) { return sh_sel_plan_within(s, shard_words1(m)); }
+
+// the digit of pass `pass`: bits [lo, lo + log2 bins) of a load
+struct ShSelDigit {
+    u32 lo, bins, himask;
+};
+static ShSelDigit sh_sel_digit(const ShSelPlan& q, u32 pass) {
+    const u32 hi = 32 - pass * q.bits, lo = hi > q.bits ? hi - q.bits : 0;
+    return {lo, 1u << (hi - lo), hi == 32 ? 0u : ~0u << hi};
+}
+// one histogram pass of plan q over n > 0 rows, added into hist (s << q.bits u64, zero on entry)
+static void launch_shed_sel_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u32 s, const u32* map,
+                                 const u32* pre, const ShSelPlan& q, u32 pass, u64* hist, hipStream_t st) {
+    const ShSelDigit d = sh_sel_digit(q, pass);
+    const u32 stride = 1u << q.bits;
+    const dim3 grid(grid_for((n + 3) / 4, kBlock, 256)), block(kBlock);
+    const size_t head = (((size_t)m + s) * sizeof(u32) + 15) & ~(size_t)15;
+    if (q.lds)
+        hipLaunchKernelGGL((k_shed_sel_hist<true>), grid, block, head + (size_t)s * d.bins * sizeof(u64), st, assign, load, aff, n,
+                           m, s, map, pre, d.himask, d.lo, d.bins, stride, hist);
+    else
+        hipLaunchKernelGGL((k_shed_sel_hist<false>), grid, block, head, st, assign, load, aff, n, m, s, map, pre, d.himask, d.lo,
+                           d.bins, stride, hist);
 }
 
 void launch_shed_select(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u32 s, const u32* map,
@@ -6720,18 +6762,11 @@ void launch_shed_select(const u32* assign, const u32* load, const u32* aff, u64 
     const u32 stride = 1u << q.bits;
     (void)hipMemsetAsync(pre, 0, (size_t)s * sizeof(u32), st);
     (void)hipMemsetAsync(hist, 0, ((size_t)s << q.bits) * sizeof(u64), st);
-    const dim3 grid(grid_for((n + 3) / 4, kBlock, 256)), block(kBlock);
-    const size_t head = (((size_t)m + s) * sizeof(u32) + 15) & ~(size_t)15;
     for (u32 pass = 0; pass < q.passes; ++pass) {
-        const u32 hi = 32 - pass * q.bits, lo = hi > q.bits ? hi - q.bits : 0;
-        const u32 bins = 1u << (hi - lo), himask = hi == 32 ? 0u : ~0u << hi;
-        if (q.lds)
-            hipLaunchKernelGGL((k_shed_sel_hist<true>), grid, block, head + (size_t)s * bins * sizeof(u64), st, assign, load, aff,
-                               n, m, s, map, pre, himask, lo, bins, stride, hist);
-        else
-            hipLaunchKernelGGL((k_shed_sel_hist<false>), grid, block, head, st, assign, load, aff, n, m, s, map, pre, himask, lo,
-                               bins, stride, hist);
-        hipLaunchKernelGGL(k_shed_sel_pick, dim3(s), block, 0, st, hist, bins, stride, lo, lo == 0, slot_node, slot_free, pre, thr);
+        const ShSelDigit d = sh_sel_digit(q, pass);
+        launch_shed_sel_hist(assign, load, aff, n, m, s, map, pre, q, pass, hist, st);
+        hipLaunchKernelGGL(k_shed_sel_pick, dim3(s), dim3(kBlock), 0, st, hist, d.bins, stride, d.lo, d.lo == 0, slot_node,
+                           slot_free, pre, thr);
     }
 }
 
@@ -6754,12 +6789,16 @@ static size_t shed_tile_lds(const ShPlan& p, const u32* thr) {
     return (size_t)p.s * sizeof(u64) + (size_t)p.m * sizeof(u32) * (thr ? 2 : 1);
 }
 
-void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u64* used, u64* pin, hipStream_t s) {
+void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u64* used, u64* pin, hipStream_t s,
+                      u32* maxl) {
     (void)hipMemsetAsync(used, 0, (size_t)m * sizeof(u64), s);
     (void)hipMemsetAsync(pin, 0, (size_t)m * sizeof(u64), s);
+    if (maxl) (void)hipMemsetAsync(maxl, 0, sizeof(u32), s);
     if (!n || !m) return;
-    hipLaunchKernelGGL(k_shed_hist, dim3(grid_for((n + 3) / 4, kBlock, 256)), dim3(kBlock), 2 * (size_t)m * sizeof(u64), s,
-                       assign, load, aff, n, m, used, pin);
+    const dim3 grid(grid_for((n + 3) / 4, kBlock, 256)), block(kBlock);
+    const size_t lds = 2 * (size_t)m * sizeof(u64);
+    if (maxl) hipLaunchKernelGGL((k_shed_hist<true>), grid, block, lds, s, assign, load, aff, n, m, used, pin, maxl);
+    else hipLaunchKernelGGL((k_shed_hist<false>), grid, block, lds, s, assign, load, aff, n, m, used, pin, maxl);
 }
 void launch_shed_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
                      const u64* slot_free, u64* mat, u32* cut, const u32* thr, hipStream_t s) {
@@ -6810,14 +6849,15 @@ void launch_shed_finish(u64 K, const u32* pk_row, const u32* pk_load, const u32*
 // No kernel waits for another rank: the caller's all-gathers order everything.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_shrb_export_x(const u64* __restrict__ used, const u64* __restrict__ pin, u32 m,
-                                                          u64* __restrict__ X) {
+                                                          const u32* __restrict__ maxl, u64* __restrict__ X) {
     const int tid = threadIdx.x;
     for (u32 j = tid; j < m; j += kBlock) {
         const u64 p = pin[j];
         X[j] = p;
         X[(size_t)m + j] = used[j] - p;
     }
-    if (tid < 8) X[2 * (size_t)m + tid] = tid == 7 ? 1ull : 0ull;
+    // word 0 of the eight: k_shed_hist<true>'s largest load (load-ordered sessions; 0 otherwise); word 7 = 1 as in the solve's record
+    if (tid < 8) X[2 * (size_t)m + tid] = tid == 7 ? 1ull : (tid == 0 && maxl) ? (u64)*maxl : 0ull;
 }
 
 __global__ __launch_bounds__(kBlock) void k_shrb_import_x(const ShrbImport a) {
@@ -6949,19 +6989,17 @@ __global__ __launch_bounds__(kBlock) void k_shrb_fill(u64 K, const u32* __restri
     }
 }
 
-void launch_shrb_export_x(const u64* used, const u64* pin, u32 m, u64* X, hipStream_t s) {
-    hipLaunchKernelGGL(k_shrb_export_x, dim3(1), dim3(kBlock), 0, s, used, pin, m, X);
+void launch_shrb_export_x(const u64* used, const u64* pin, u32 m, const u32* maxl, u64* X, hipStream_t s) {
+    hipLaunchKernelGGL(k_shrb_export_x, dim3(1), dim3(kBlock), 0, s, used, pin, m, maxl, X);
 }
 void launch_shrb_import_x(const ShrbImport& a, hipStream_t s) {
     hipLaunchKernelGGL(k_shrb_import_x, dim3(1), dim3(kBlock), 0, s, a);
 }
 void launch_shrb_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
-                     const u64* slot_free, u64* mat, u32* cut, hipStream_t s) {
+                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, hipStream_t s) {
     if (!p.s || !p.n) return;
-    const u32* const row_order = nullptr;  // (the load-ordered cut is not sharded)
-    hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), shed_tile_lds(p, row_order), s, assign, load, aff, p, map, row_order,
-                       mat);
-    hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, row_order, cut);
+    hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), shed_tile_lds(p, thr), s, assign, load, aff, p, map, thr, mat);
+    hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, thr, cut);
 }
 void launch_shrb_export_y(const u64* v, u32 m, const u64* a, u64 b, u64* Y, hipStream_t s) {
     hipLaunchKernelGGL(k_shrb_export_y, dim3(1), dim3(kBlock), 0, s, v, m, a, b, Y);
@@ -6978,6 +7016,142 @@ void launch_shrb_round(u64 K, const u32* pk_row, const u32* pk_load, u32* pk_nod
     hipLaunchKernelGGL((k_shed_scan<u64>), dim3(1), dim3(kBlock), 0, s, csum, csum, (u64)nc, (u64*)nullptr, base);
     hipLaunchKernelGGL(k_shed_order, dim3(1), dim3(kBlock), shed_order_lds(m), s, tgt, used, m, C, ord, cntp);
     hipLaunchKernelGGL(k_shrb_fill, dim3(nc), dim3(kBlock), 0, s, K, pk_row, pk_load, pk_node, assign, csum, C, ord, cntp, last, m, Y);
+}
+
+// ---- the load-ordered cut (R1') of the row-sharded table --------------------------------------------------------------------
+// The threshold of an over node depends on its candidates on every rank, so every rank searches the thresholds of ALL over
+// nodes together: a pass is k_shed_sel_hist over this rank's rows (the slots are the globally over nodes), the caller gathers
+// the (slot x digit) histograms, and k_shrb_sel_pick picks every slot's digit from their sum in rank order — the same sum, the
+// same rem and the same pre on every rank, which is what one handle computes over the concatenated table.
+//   k_shrb_import_slots  k_shrb_import_x for this search: a slot per over node in ascending node order (a scan, not an atomic:
+//                        the slot index addresses the exchanged histogram and must be the same on every rank), slot_free =
+//                        the GLOBAL free_j, pre = 0; cut = thr = kNone everywhere.  It also takes the largest of the ranks' largest
+//                        loads (X word 2m, from k_shed_hist<true>): the passes whose digit lies wholly above it pick 0 on every
+//                        slot and are not run (shrb_sel_first_pass)
+//   k_shrb_sel_pick      k_shed_sel_pick over the gathered histograms.  After the last digit the bin of tau in rank q's histogram
+//                        is tau * (its candidates of load tau), so the ranks' tie counts are at hand: c = rem / tau ties are kept
+//                        in global row order, this rank keeps its first clamp(c - the lower ranks' ties, 0, its own), and
+//                        slot_free becomes tau * that — what k_shed_tile / k_shed_cut with thr walk the ties against: 0 cuts at
+//                        this rank's first tie (every tie here is surplus), its own tie load finds no cut row (none is)
+__global__ __launch_bounds__(kBlock) void k_shrb_import_slots(const ShrbImport a, u32* __restrict__ pre, u32* __restrict__ thr) {
+    __shared__ u64 part[16];
+    __shared__ u32 s_before;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_before = 0;
+    __syncthreads();
+    const size_t W = 2 * (size_t)a.m + 8;
+    const u32 per = (a.m + kBlock - 1) / kBlock;  // <= 8 consecutive nodes a lane: the scan below numbers the slots by node
+    u32 ov = 0, before = 0;  // (bit q: node tid * per + q is over)
+#pragma unroll 1
+    for (u32 q = 0; q < per; ++q) {
+        const u32 j = tid * per + q;
+        if (j >= a.m) break;
+        u64 P = 0, ctot = 0;
+        for (u32 r = 0; r < a.R; ++r) {
+            P += a.Xg[r * W + j];
+            ctot += a.Xg[r * W + a.m + j];
+        }
+        const bool lv = a.live[j] != 0;
+        const u64 T = lv ? a.T[j] : 0ull;
+        a.used[j] = P + ctot;
+        a.tgt[j] = T;
+        a.cut[j] = kNone;
+        thr[j] = kNone;
+        if (lv) {
+            before += P + ctot > T;
+            if (ctot > (T > P ? T - P : 0ull)) ov |= 1u << q;
+        }
+    }
+    u64 tot;
+    u32 sl = (u32)block_excl_scan_1024((u64)__popc(ov), false, part, &tot);
+#pragma unroll 1
+    for (u32 q = 0; q < per; ++q) {
+        const u32 j = tid * per + q;
+        if (j >= a.m) break;
+        const bool o = (ov >> q) & 1u;
+        a.map[j] = o ? sl : kNone;
+        if (o) {  // free_j again, from the pinned load of all ranks
+            u64 P = 0;
+            for (u32 r = 0; r < a.R; ++r) P += a.Xg[r * W + j];
+            const u64 T = a.T[j];
+            a.slot_node[sl] = j;
+            a.slot_free[sl] = T > P ? T - P : 0ull;
+            pre[sl] = 0;
+            ++sl;
+        }
+    }
+    before = wave_sum32(before);
+    if ((tid & 63) == 0 && before) atomicAdd(&s_before, before);
+    __syncthreads();
+    if (tid == 0) {
+        u64 mx = 0;  // the largest load any rank reported: no threshold is above it
+        for (u32 r = 0; r < a.R; ++r) mx = a.Xg[r * W + 2 * (size_t)a.m] > mx ? a.Xg[r * W + 2 * (size_t)a.m] : mx;
+        a.info[kShrbOver] = (u32)tot;
+        a.info[kShrbSlots] = (u32)tot;
+        a.info[kShrbForced] = 0;
+        a.info[kShrbOverBefore] = s_before;
+        a.info[kShrbMaxLoad] = mx > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)mx;
+    }
+}
+
+// One workgroup per slot over Hg[R][W], the gathered histograms of the pass (slot sl's bins at sl * stride of each record)
+__global__ __launch_bounds__(kBlock) void k_shrb_sel_pick(const u64* __restrict__ Hg, u64 W, u32 rank, u32 R, u32 bins, u32 stride,
+                                                          u32 shift, bool last, const u32* __restrict__ slot_node,
+                                                          u64* __restrict__ slot_free, u32* __restrict__ pre,
+                                                          u32* __restrict__ thr) {
+    __shared__ u64 part[16];
+    const int tid = threadIdx.x;
+    const u32 sl = blockIdx.x;
+    const u64* row = Hg + (size_t)sl * stride;
+    const u64 rem = slot_free[sl];
+    const u32 b0 = 2 * tid, b1 = b0 + 1;  // bins <= 2 * kBlock
+    u64 v0 = 0, v1 = 0;
+    for (u32 q = 0; q < R; ++q) {
+        if (b0 < bins) v0 += row[q * W + b0];
+        if (b1 < bins) v1 += row[q * W + b1];
+    }
+    const u64 ex = block_excl_scan_1024(v0 + v1, false, part, nullptr);
+    u32 d = kNone;
+    u64 below = 0;
+    if (ex <= rem && ex + v0 > rem) { d = b0; below = ex; }
+    else if (ex + v0 <= rem && ex + v0 + v1 > rem) { d = b1; below = ex + v0; }
+    if (d != kNone) {  // exactly one lane: the prefix never decreases and the global total is above rem
+        const u32 p = pre[sl] | (d << shift);
+        u64 left = rem - below;
+        pre[sl] = p;
+        if (last) {  // p = tau >= 1 (zero loads add nothing to any bin)
+            const u64 c = left / p;
+            u64 lower = 0;
+            for (u32 q = 0; q < rank; ++q) lower += row[q * W + d] / p;
+            const u64 mine = row[rank * W + d] / p;
+            left = (c > lower ? (c - lower < mine ? c - lower : mine) : 0ull) * p;
+            thr[slot_node[sl]] = p;
+        }
+        slot_free[sl] = left;
+    }
+}
+
+u32 shrb_sel_first_pass(const ShSelPlan& q, u32 max_load) {
+    const u32 top = max_load ? 32 - (u32)__builtin_clz(max_load) : 32;  // (0: nothing reported — the whole search)
+    u32 p = 0;
+    while (p + 1 < q.passes && sh_sel_digit(q, p).lo >= top) ++p;  // a digit wholly above every load is 0 on every slot
+    return p;
+}
+void launch_shrb_import_slots(const ShrbImport& a, u32* pre, u32* thr, hipStream_t s) {
+    hipLaunchKernelGGL(k_shrb_import_slots, dim3(1), dim3(kBlock), 0, s, a, pre, thr);
+}
+void launch_shrb_sel_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u32 S, const u32* map, const u32* pre,
+                          const ShSelPlan& q, u32 pass, u64* H, hipStream_t s) {
+    (void)hipMemsetAsync(H, 0, ((size_t)S << q.bits) * sizeof(u64), s);
+    if (!S || !n) return;
+    launch_shed_sel_hist(assign, load, aff, n, m, S, map, pre, q, pass, H, s);
+}
+void launch_shrb_sel_pick(const u64* Hg, u32 rank, u32 R, u32 S, const ShSelPlan& q, u32 pass, const u32* slot_node,
+                          u64* slot_free, u32* pre, u32* thr, hipStream_t s) {
+    if (!S) return;
+    const ShSelDigit d = sh_sel_digit(q, pass);
+    hipLaunchKernelGGL(k_shrb_sel_pick, dim3(S), dim3(kBlock), 0, s, Hg, (u64)S << q.bits, rank, R, d.bins, 1u << q.bits, d.lo,
+                       d.lo == 0, slot_node, slot_free, pre, thr);
 }
 
 

@@ -356,6 +356,12 @@ struct RbSession {
     u32 over = 0, over_before = 0;
     u64 epoch = 0;  // mut_epoch as rio_gp_shard_rebalance_begin left it: any other change of the inputs ends the protocol
     ShPlan plan{};
+    // the load-ordered cut (rio_gp_shard_rebalance_begin_ordered, order = RIO_GP_REBALANCE_BY_LOAD): between cut and select the
+    // threshold passes run in order, a histogram and then its pick
+    u32 order = 0, slots = 0, sel_first = 0, sel_pass = 0;  // (passes sel_first .. sel.passes - 1 of the plan run)
+    bool sel_hist_out = false;  // the histogram of pass sel_pass is out, its pick has not run
+    ShSelPlan sel{};
+    bool thresholds_pending() const { return order != 0 && over != 0 && sel_pass < sel.passes; }
     std::vector<u64> T;
     std::vector<u32> live;
     // A step continues the protocol only on the handle as begin left it: no call that changes an input of the solve (they all
@@ -3558,7 +3564,7 @@ int rio_gp_shard_finish(rio_gp_t* h, rio_gp_stats* local_stats) {
 namespace {
 struct RbBufs {
     u64 *pin, *tgt, *slot_free, *C, *acc, *lu, *tdev, *base;
-    u32 *map, *slot_node, *cut, *ord, *cntp, *live, *info;
+    u32 *map, *slot_node, *cut, *ord, *cntp, *live, *info, *maxl, *thr, *pre;
 };
 constexpr int kRbPend = 6;  // acc[6], acc[7]: rows / load pending on all ranks (k_shrb_merge)
 RbBufs rb_bufs(rio_gp* h) {
@@ -3579,27 +3585,32 @@ RbBufs rb_bufs(rio_gp* h) {
     b.cntp = b.ord + M;
     b.live = b.cntp + 4;
     b.info = b.live + M;
+    // the load-ordered cut: info has one more word (kShrbMaxLoad); this rank's largest load, the threshold per node, the digits
+    // chosen so far per slot
+    b.maxl = b.info + kShrbInfo + 1;
+    b.thr = b.maxl + 1;
+    b.pre = b.thr + M;
     return b;
 }
 int rb_ensure(rio_gp* h) {
     const size_t M = h->cap_nodes;
-    return ensure(h, h->sh_nodes, (6 * M + 2 + kShAcc) * sizeof(u64) + (5 * M + 4 + kShrbInfo) * sizeof(u32));
+    return ensure(h, h->sh_nodes, (6 * M + 2 + kShAcc) * sizeof(u64) + (7 * M + 4 + kShrbInfo + 2) * sizeof(u32));
 }
 }  // namespace
 
-int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, uint32_t rank, uint32_t n_ranks, int list_moves,
-                                 uint64_t moves_cap, uint64_t* d_x, uint32_t* rounds_out) {
-    if (!h) return RIO_GP_EINVAL;
-    Locked g(h);
+// rio_gp_shard_rebalance_begin (row order only: its protocol has no threshold passes) and rio_gp_shard_rebalance_begin_ordered
+static int shard_rebalance_begin(rio_gp* h, const char* who, bool ordered, const rio_gp_rebalance_cfg* cfg, uint32_t rank,
+                                 uint32_t n_ranks, int list_moves, uint64_t moves_cap, uint64_t* d_x, uint32_t* rounds_out) {
+    const std::string me = std::string(who) + ": ";
     u32 order;
-    if (rebalance_cfg_order(cfg, &order))
-        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: cfg missing or struct_size differs");
-    if (order != RIO_GP_REBALANCE_ROW_ORDER)
-        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: the load-ordered cut (order = RIO_GP_REBALANCE_BY_LOAD) is not "
-                                      "implemented for a row-sharded table; use order = RIO_GP_REBALANCE_ROW_ORDER");
-    if (cfg->rounds > 8) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: rounds above the solver limit (8)");
-    if (!d_x || n_ranks == 0 || rank >= n_ranks) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: rank >= n_ranks, or no record");
-    if (!list_moves && moves_cap) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_begin: moves_cap without a move listing");
+    if (rebalance_cfg_order(cfg, &order)) return fail(h, RIO_GP_EINVAL, me + "cfg missing or struct_size differs");
+    if (order != RIO_GP_REBALANCE_ROW_ORDER && !ordered)
+        return fail(h, RIO_GP_EINVAL, me + "the load-ordered cut (order = RIO_GP_REBALANCE_BY_LOAD) of a row-sharded table has "
+                                           "threshold passes between cut and select: start it with "
+                                           "rio_gp_shard_rebalance_begin_ordered");
+    if (cfg->rounds > 8) return fail(h, RIO_GP_EINVAL, me + "rounds above the solver limit (8)");
+    if (!d_x || n_ranks == 0 || rank >= n_ranks) return fail(h, RIO_GP_EINVAL, me + "rank >= n_ranks, or no record");
+    if (!list_moves && moves_cap) return fail(h, RIO_GP_EINVAL, me + "moves_cap without a move listing");
     int rc = may_start(h, Client::shard_rebalance_begin);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
@@ -3615,6 +3626,7 @@ int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, u
     fresh.T = std::move(h->rb.T);  // (in the last session's host arrays: a copy it enqueued may still be on its way into them)
     fresh.live = std::move(h->rb.live);
     fresh.rank = rank; fresh.R = n_ranks;
+    fresh.order = order;
     fresh.rounds = cfg->rounds ? cfg->rounds : h->rounds;
     fresh.list = list_moves != 0;
     fresh.budget = list_moves ? std::min<u64>(cfg->max_moves, moves_cap) : cfg->max_moves;
@@ -3632,12 +3644,46 @@ int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, u
     if (m) HIPCHK(h, hipMemcpyAsync(b.live, rb.live.data(), (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(b.acc, 0, kShAcc * sizeof(u64), h->stream));
     // R0 over this rank's rows: the load per node (kept in lu: it becomes used'_r in _select) and the pinned load
-    launch_shed_hist(h->assign[h->cur], h->load, h->aff, h->n, m, b.lu, b.pin, h->stream);
-    launch_shrb_export_x(b.lu, b.pin, m, reinterpret_cast<u64*>(d_x), h->stream);
+    u32* const maxl = order ? b.maxl : nullptr;  // (by load: X also carries this rank's largest load, where the search starts)
+    launch_shed_hist(h->assign[h->cur], h->load, h->aff, h->n, m, b.lu, b.pin, h->stream, maxl);
+    launch_shrb_export_x(b.lu, b.pin, m, maxl, reinterpret_cast<u64*>(d_x), h->stream);
     HIPCHK(h, hipGetLastError());
     if (rounds_out) *rounds_out = rb.rounds;
     rb.epoch = h->mut_epoch;
     rb.step = RbStep::begun;
+    return RIO_GP_OK;
+}
+
+int rio_gp_shard_rebalance_begin(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, uint32_t rank, uint32_t n_ranks, int list_moves,
+                                 uint64_t moves_cap, uint64_t* d_x, uint32_t* rounds_out) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    return shard_rebalance_begin(h, "rio_gp_shard_rebalance_begin", false, cfg, rank, n_ranks, list_moves, moves_cap, d_x, rounds_out);
+}
+
+int rio_gp_shard_rebalance_begin_ordered(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, uint32_t rank, uint32_t n_ranks,
+                                         int list_moves, uint64_t moves_cap, uint64_t* d_x, uint32_t* rounds_out) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    return shard_rebalance_begin(h, "rio_gp_shard_rebalance_begin_ordered", true, cfg, rank, n_ranks, list_moves, moves_cap, d_x,
+                                 rounds_out);
+}
+
+// R1 over this rank's rows behind the slots' free loads (and, by load, thresholds): the cut rows that fall here, the surplus per
+// tile; S = surplus rows | load | zeros
+static int shard_rebalance_surplus(rio_gp* h, const RbSession& rb, const RbBufs& b, bool forced, uint64_t* d_s) {
+    const ShPlan& p = rb.plan;
+    const u32* const thr = rb.order ? b.thr : nullptr;
+    HIPCHK(h, hipMemsetAsync(d_s, 0, ((size_t)h->m + 2) * sizeof(u64), h->stream));
+    if (!h->n || !(p.s || forced)) return RIO_GP_OK;
+    int rc;
+    if ((rc = ensure(h, h->sh_mat, (size_t)std::max<u32>(p.s, 1) * p.nt * sizeof(u64))) ||
+        (rc = ensure(h, h->sh_tile, (size_t)p.nt * sizeof(u32))))
+        return rc;
+    launch_shrb_cut(h->assign[h->cur], h->load, h->aff, p, b.map, b.slot_node, b.slot_free, (u64*)h->sh_mat.p, b.cut, thr, h->stream);
+    launch_shed_count(h->assign[h->cur], h->load, h->aff, p, b.cut, thr, (u32*)h->sh_tile.p, b.acc, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(d_s, b.acc, 2 * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));  // surplus rows | load
     return RIO_GP_OK;
 }
 
@@ -3655,29 +3701,81 @@ int rio_gp_shard_rebalance_cut(rio_gp_t* h, const uint64_t* d_xg, uint64_t* d_s,
     a.T = b.tdev; a.live = b.live;
     a.used = h->used.storage(); a.tgt = b.tgt; a.map = b.map; a.slot_node = b.slot_node; a.slot_free = b.slot_free; a.cut = b.cut;
     a.info = b.info;
-    launch_shrb_import_x(a, h->stream);
+    if (rb.order) launch_shrb_import_slots(a, b.pre, b.thr, h->stream);
+    else launch_shrb_import_x(a, h->stream);
     HIPCHK(h, hipGetLastError());
-    u32 info[kShrbInfo];
-    HIPCHK(h, hipMemcpyAsync(info, b.info, sizeof info, hipMemcpyDeviceToHost, h->stream));
+    u32 info[kShrbInfo + 1] = {};
+    HIPCHK(h, hipMemcpyAsync(info, b.info, (kShrbInfo + (rb.order ? 1 : 0)) * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     rb.over = info[kShrbOver];
     rb.over_before = info[kShrbOverBefore];
     const u32 S = info[kShrbSlots];
-    const ShPlan p = sh_plan(h->n, m, S);
-    rb.plan = p;
-    HIPCHK(h, hipMemsetAsync(d_s, 0, ((size_t)m + 2) * sizeof(u64), h->stream));
-    if (h->n && (S || info[kShrbForced])) {  // R1 over this rank's rows: the exact cuts that fall here, the surplus per tile
-        int rc;
-        if ((rc = ensure(h, h->sh_mat, (size_t)std::max<u32>(S, 1) * p.nt * sizeof(u64))) ||
-            (rc = ensure(h, h->sh_tile, (size_t)p.nt * sizeof(u32))))
+    rb.plan = sh_plan(h->n, m, S);
+    if (rb.order) {  // the surplus is known behind the thresholds: rio_gp_shard_rebalance_threshold_pick's last pass writes S
+        rb.slots = S;
+        rb.sel = shrb_sel_plan(S, m);
+        rb.sel_first = shrb_sel_first_pass(rb.sel, info[kShrbMaxLoad]);
+        rb.sel_pass = rb.sel_first;
+        rb.sel_hist_out = false;
+        int rc;  // (what the last pick needs, here: a pick that has run is not taken back)
+        if (S && h->n && ((rc = ensure(h, h->sh_mat, (size_t)S * rb.plan.nt * sizeof(u64))) ||
+                          (rc = ensure(h, h->sh_tile, (size_t)rb.plan.nt * sizeof(u32)))))
             return rc;
-        launch_shrb_cut(h->assign[h->cur], h->load, h->aff, p, b.map, b.slot_node, b.slot_free, (u64*)h->sh_mat.p, b.cut, h->stream);
-        launch_shed_count(h->assign[h->cur], h->load, h->aff, p, b.cut, /*thr=*/nullptr, (u32*)h->sh_tile.p, b.acc, h->stream);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(d_s, b.acc, 2 * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));  // surplus rows | load
+        HIPCHK(h, hipMemsetAsync(d_s, 0, ((size_t)m + 2) * sizeof(u64), h->stream));
+    } else if (int rc = shard_rebalance_surplus(h, rb, b, info[kShrbForced] != 0, d_s)) {
+        return rc;
     }
     if (nodes_over) *nodes_over = rb.over;
     rb.step = RbStep::cut;
+    return RIO_GP_OK;
+}
+
+int rio_gp_shard_rebalance_threshold_plan(rio_gp_t* h, uint32_t* passes, uint64_t* words) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    RbSession& rb = h->rb;
+    if (!rb.at(h, RbStep::cut) || !rb.order || !rb.over)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_threshold_plan: a load-ordered session behind rio_gp_shard_rebalance_cut "
+                                      "with nodes over only (rio_gp_shard_rebalance_begin_ordered)");
+    if (passes) *passes = rb.sel.passes - rb.sel_first;
+    if (words) *words = (u64)rb.slots << rb.sel.bits;
+    return RIO_GP_OK;
+}
+
+int rio_gp_shard_rebalance_threshold_hist(rio_gp_t* h, uint32_t pass, uint64_t* d_h) {
+    if (!h || !d_h) return RIO_GP_EINVAL;
+    Locked g(h);
+    RbSession& rb = h->rb;
+    if (!rb.at(h, RbStep::cut) || !rb.thresholds_pending() || pass != rb.sel_pass - rb.sel_first)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_threshold_hist: the passes of a load-ordered session run in order, "
+                                      "between rio_gp_shard_rebalance_cut (with nodes over) and rio_gp_shard_rebalance_select");
+    HIPCHK(h, hipSetDevice(h->device));
+    const RbBufs b = rb_bufs(h);
+    launch_shrb_sel_hist(h->assign[h->cur], h->load, h->aff, h->n, h->m, rb.slots, b.map, b.pre, rb.sel, rb.sel_pass,
+                         reinterpret_cast<u64*>(d_h), h->stream);
+    HIPCHK(h, hipGetLastError());
+    rb.sel_hist_out = true;
+    return RIO_GP_OK;
+}
+
+int rio_gp_shard_rebalance_threshold_pick(rio_gp_t* h, uint32_t pass, const uint64_t* d_hg, uint64_t* d_s) {
+    if (!h || !d_hg) return RIO_GP_EINVAL;
+    Locked g(h);
+    RbSession& rb = h->rb;
+    if (!rb.at(h, RbStep::cut) || !rb.thresholds_pending() || pass != rb.sel_pass - rb.sel_first || !rb.sel_hist_out)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_threshold_pick: call rio_gp_shard_rebalance_threshold_hist of the same "
+                                      "pass first; the passes run in order");
+    const bool last = rb.sel_pass + 1 == rb.sel.passes;
+    if (last && !d_s) return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_threshold_pick: the last pass writes the S record");
+    HIPCHK(h, hipSetDevice(h->device));
+    const RbBufs b = rb_bufs(h);
+    launch_shrb_sel_pick(reinterpret_cast<const u64*>(d_hg), rb.rank, rb.R, rb.slots, rb.sel, rb.sel_pass, b.slot_node, b.slot_free, b.pre,
+                         b.thr, h->stream);
+    HIPCHK(h, hipGetLastError());
+    if (last)
+        if (int rc = shard_rebalance_surplus(h, rb, b, false, d_s)) return rc;
+    rb.sel_hist_out = false;
+    ++rb.sel_pass;
     return RIO_GP_OK;
 }
 
@@ -3688,6 +3786,9 @@ int rio_gp_shard_rebalance_select(rio_gp_t* h, const uint64_t* d_sg, uint64_t* d
     RbSession& rb = h->rb;
     if (!rb.at(h, RbStep::cut) || !rb.over)
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_select: call rio_gp_shard_rebalance_cut first (and only when it reports nodes over)");
+    if (rb.thresholds_pending())
+        return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_select: the threshold passes of the load-ordered cut come first "
+                                      "(rio_gp_shard_rebalance_threshold_plan / _hist / _pick)");
     HIPCHK(h, hipSetDevice(h->device));
     const RbBufs b = rb_bufs(h);
     const u32 m = h->m, R = rb.R;
@@ -3709,7 +3810,7 @@ int rio_gp_shard_rebalance_select(rio_gp_t* h, const uint64_t* d_sg, uint64_t* d
         const u64 nc = (K + kShChunk - 1) / kShChunk;
         if ((rc = ensure(h, h->sh_pk, 3 * K * sizeof(u32))) || (rc = ensure(h, h->sh_chunk, nc * sizeof(u64)))) return rc;
         u32* pk_row = (u32*)h->sh_pk.p;
-        launch_shed_pack(h->assign[h->cur], h->load, h->aff, rb.plan, b.cut, /*thr=*/nullptr, (const u32*)h->sh_tile.p, K, pk_row,
+        launch_shed_pack(h->assign[h->cur], h->load, h->aff, rb.plan, b.cut, rb.order ? b.thr : nullptr, (const u32*)h->sh_tile.p, K, pk_row,
                          pk_row + K, pk_row + 2 * K, b.lu, b.acc, h->stream);
     }
     launch_shrb_export_y(b.lu, m, b.acc + kShAccSelectedLoad, K, reinterpret_cast<u64*>(d_y), h->stream);

@@ -72,6 +72,10 @@ def _lib():
         u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
         L.rio_gp_shard_rebalance_begin.argtypes = [vp, C.POINTER(rio_gp.RebalanceCfg), C.c_uint32, C.c_uint32, C.c_int,
                                                    C.c_uint64, vp, u32p]
+        L.rio_gp_shard_rebalance_begin_ordered.argtypes = L.rio_gp_shard_rebalance_begin.argtypes
+        L.rio_gp_shard_rebalance_threshold_plan.argtypes = [vp, u32p, u64p]
+        L.rio_gp_shard_rebalance_threshold_hist.argtypes = [vp, C.c_uint32, vp]
+        L.rio_gp_shard_rebalance_threshold_pick.argtypes = [vp, C.c_uint32, vp, vp]
         L.rio_gp_shard_rebalance_cut.argtypes = [vp, vp, vp, u32p]
         L.rio_gp_shard_rebalance_select.argtypes = [vp, vp, vp, u64p, u64p]
         L.rio_gp_shard_rebalance_merge.argtypes = [vp, vp, u64p, u64p]
@@ -168,15 +172,17 @@ class HipShardEngine:
             raise ValueError("record buffer of %d words, %d expected" % (t.numel(), need))
         return C.c_void_p(t.data_ptr())
 
-    def rebalance_begin(self, rank, n_ranks, target, max_moves, rounds, list_moves, x):
-        """R0 over this shard; x = its X record.  max_moves: the GLOBAL budget (an int; rio_gp.CAP_INF = no limit).  Returns
-        the number of water-fill rounds that run at most."""
+    def rebalance_begin(self, rank, n_ranks, target, max_moves, rounds, list_moves, x, order=rio_gp.REBALANCE_ROW_ORDER):
+        """R0 over this shard; x = its X record.  max_moves: the GLOBAL budget (an int; rio_gp.CAP_INF = no limit).  order:
+        rio_gp.REBALANCE_BY_LOAD starts a load-ordered session (rio_gp_shard_rebalance_begin_ordered: the threshold passes run
+        between rebalance_cut and rebalance_select).  Returns the number of water-fill rounds that run at most."""
         self._rb_R = n_ranks
-        cfg, _keep = self.g._rebalance_cfg(target, max_moves, rounds)
+        self._rb_hwords = 0
+        cfg, _keep = self.g._rebalance_cfg(target, max_moves, rounds, order)
         nr = C.c_uint32(0)
-        self.g._chk(_lib().rio_gp_shard_rebalance_begin(self.g.handle, C.byref(cfg), rank, n_ranks, int(bool(list_moves)),
-                                                        int(max_moves) if list_moves else 0, self._rb_words(x, 2),
-                                                        C.byref(nr)))
+        begin = _lib().rio_gp_shard_rebalance_begin_ordered if order else _lib().rio_gp_shard_rebalance_begin
+        self.g._chk(begin(self.g.handle, C.byref(cfg), rank, n_ranks, int(bool(list_moves)), int(max_moves) if list_moves else 0,
+                          self._rb_words(x, 2), C.byref(nr)))
         return int(nr.value)
 
     def rebalance_cut(self, xg, s):
@@ -184,6 +190,26 @@ class HipShardEngine:
         self.g._chk(_lib().rio_gp_shard_rebalance_cut(self.g.handle, self._rb_words(xg, 2, self._rb_R), self._rb_words(s, 1),
                                                       C.byref(over)))
         return int(over.value)
+
+    def rebalance_threshold_plan(self):
+        """(passes, words): the threshold passes of a load-ordered session and the u64 words of one shard's histogram record."""
+        p, w = C.c_uint32(0), C.c_uint64(0)
+        self.g._chk(_lib().rio_gp_shard_rebalance_threshold_plan(self.g.handle, C.byref(p), C.byref(w)))
+        self._rb_hwords = int(w.value)
+        return int(p.value), int(w.value)
+
+    def _rb_hist(self, t, n_ranks=1):
+        if t.numel() != n_ranks * self._rb_hwords:
+            raise ValueError("histogram buffer of %d words, %d expected" % (t.numel(), n_ranks * self._rb_hwords))
+        return C.c_void_p(t.data_ptr())
+
+    def rebalance_threshold_hist(self, p, hist):
+        self.g._chk(_lib().rio_gp_shard_rebalance_threshold_hist(self.g.handle, p, self._rb_hist(hist)))
+
+    def rebalance_threshold_pick(self, p, hg, s=None):
+        """hg: the gathered histograms of pass p; s (the last pass): this shard's S record."""
+        self.g._chk(_lib().rio_gp_shard_rebalance_threshold_pick(self.g.handle, p, self._rb_hist(hg, self._rb_R),
+                                                                 None if s is None else self._rb_words(s, 1)))
 
     def rebalance_select(self, sg, y):
         loc, tot = C.c_uint64(0), C.c_uint64(0)
@@ -460,17 +486,29 @@ class ShardedSolver:
         self.commit()
         return st
 
-    # -- bounded rebalance of the row-sharded table (rio_gp_shard_rebalance_*): 3 + rounds exchanges at most --
-    def rebalance(self, target=None, max_moves=None, rounds=0, list_moves=True):
+    # -- bounded rebalance of the row-sharded table (rio_gp_shard_rebalance_*): 3 + rounds exchanges at most, and one more per
+    #    threshold pass of the load-ordered cut --
+    def rebalance(self, target=None, max_moves=None, rounds=0, list_moves=True, order=rio_gp.REBALANCE_ROW_ORDER):
         """rio_gp_rebalance of the concatenated table: (stats, rows, from, to) — global counters; the moves of THIS process's
-        shards in row order with global row numbers (every shard's, ascending, under LocalExchange).  target, max_moves and
-        rounds as in GpuPlacement.rebalance, the same on every rank; max_moves is the budget of the whole table."""
+        shards in row order with global row numbers (every shard's, ascending, under LocalExchange).  target, max_moves, rounds
+        and order as in GpuPlacement.rebalance, the same on every rank; max_moves is the budget of the whole table."""
         B = rio_gp.CAP_INF if max_moves is None else int(max_moves)
         E = self.engines
-        nr = [e.rebalance_begin(r, self.R, target, B, rounds, list_moves, x) for e, r, x in zip(E, self.ranks, self.X)][0]
+        by_load = {"order": order} if order else {}   # (row order: the call every engine has always had)
+        nr = [e.rebalance_begin(r, self.R, target, B, rounds, list_moves, x, **by_load)
+              for e, r, x in zip(E, self.ranks, self.X)][0]
         xg = self._gather(self.X, out=self.XG[0])
         over = [e.rebalance_cut(xg, y) for e, y in zip(E, self.Y)][0]
         if over:
+            if order:   # R1': one exchange of the shards' histograms per digit of the thresholds; the last pick writes S
+                passes, words = [e.rebalance_threshold_plan() for e in E][0]
+                H = [e.new_buffer(words) for e in E]
+                for p in range(passes):
+                    for e, hb in zip(E, H):
+                        e.rebalance_threshold_hist(p, hb)
+                    hg = self._gather(H)
+                    for e, y in zip(E, self.Y):
+                        e.rebalance_threshold_pick(p, hg, y if p + 1 == passes else None)
             sg = self._gather(self.Y)
             total = [e.rebalance_select(sg, y) for e, y in zip(E, self.Y)][0][1]
             if total:
