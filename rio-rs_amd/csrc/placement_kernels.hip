@@ -7156,20 +7156,119 @@ void launch_shrb_sel_pick(const u64* Hg, u32 rank, u32 R, u32 S, const ShSelPlan
 
 
 // ------------------------------------------------------------------------------------------------
-// Change feed (rio_gp_changes): the rows r < n whose committed node A[r] differs from the consumer's checkpoint B[r].  Three
-// launches, and no workgroup ever waits for another (nor fences: a compaction needs neither):
-//   k_chg_count  every wave counts A != B over its tiles of kChgTile rows (dwordx4 loads of both columns, ballots over the
-//                lanes' counts) and stores the per-tile counts; every workgroup stores the sum of its tiles.
+// Ordered compaction over a ChgPlan: the first `limit` rows r < n that satisfy a predicate, in row order, each handed to a
+// per-row body with its position.  A wave takes a tile of kChgTile rows in four steps of 256, lane l the rows 4l .. 4l+3 of a
+// step.  Three launches, and no workgroup ever waits for another (nor fences: a compaction needs neither):
+//   a count pass (oc_count)   every wave counts the hits of its tiles (ballots over the lanes' counts) and stores the per-tile
+//                counts; every workgroup stores the sum of its tiles.
 //   k_chg_scan   one workgroup: the exclusive scan of the workgroup sums, in place; the total also into mapped pinned memory.
-//   k_chg_list   a workgroup whose changes are not all past `cap` scans its own tile counts in LDS and re-streams only the tiles
-//                that hold a change.  A changed row's position = its tile's offset + the changed rows of the lower lanes in the
-//                step (three ballots over each lane's 0..4) + those of its own lane in front of it; positions >= cap are dropped.
-//                Consuming, a lane that listed a row stores its four B words back (dwordx4) with the listed ones advanced.
+//   a list pass (oc_tile_offsets, oc_rank)   a workgroup whose hits are not all past the limit scans its own tile counts in LDS
+//                and re-streams only the tiles that hold a hit below the limit.  A hit's position = its tile's offset + the hits
+//                of the lower lanes in the step (three ballots over each lane's 0..4) + those of its own lane in front of it;
+//                the per-row body drops positions >= limit.
+// The change feed, idle expiry and the hot-object report's tie pass are a predicate and a body each over these pieces (the
+// feed's list pass ranks in a loop of its own: k_chg_list).
 // (A first form let the last workgroup of the count pass scan the sums behind an agent-scope ticket: the release / acquire
 //  around it wrote back and invalidated L2 once per workgroup, 53 us for the 80 MB of config 3.)
+// Whole tiles are read: every column holds cap_rows = max_objects rounded up to kTile plus 8 kTile (2 048 rows) of padding, so
+// every tile of kChgTile rows that starts below n lies inside them; the predicates mask rows >= n.
 // ------------------------------------------------------------------------------------------------
-// Whole tiles are read: both columns hold cap_rows = max_objects rounded up to kTile plus 8 kTile (2 048 rows) of padding, so
-// every tile of kChgTile rows that starts below n lies inside them; rows >= n are masked in chg_flags.
+// per_lane_count(lo, lane) -> the lane's 0 .. 16 hits among its rows of the tile at row lo (it loads what it needs itself)
+template <class Count>
+__device__ __forceinline__ void oc_count(const ChgPlan& p, u32* __restrict__ cnt, u32* __restrict__ gsum, Count&& per_lane_count) {
+    __shared__ u32 ws[kChgWaves];
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u32 t0 = blockIdx.x * p.tpg, t1 = t0 + p.tpg < p.nt ? t0 + p.tpg : p.nt;
+    u32 mine = 0;
+    for (u32 t = t0 + wv; t < t1; t += kChgWaves) {  // wave-uniform
+        const u32 c = per_lane_count((u64)t * kChgTile, lane);
+        u32 tc = 0;
+#pragma unroll
+        for (int bit = 0; bit < 5; ++bit) tc += (u32)__builtin_popcountll(__ballot((c >> bit) & 1u)) << bit;
+        if (lane == 0) cnt[t] = tc;
+        mine += tc;
+    }
+    if (lane == 0) ws[wv] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) gsum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+}
+
+// A workgroup's share of a listing: positions base .. base + tot - 1, over its k tiles.  go false: everything here lies past the
+// limit, or there is nothing here (uniform over the workgroup: it returns).
+template <class L>
+struct OcTiles {
+    bool go;
+    L base;
+    u32 k, tot;
+};
+// The exclusive scan of the workgroup's own tile counts into toff[0 .. k-1] (lds: 4 words).  The caller's __syncthreads() comes
+// after it, behind whatever else of LDS the caller sets up.
+template <class L>
+__device__ __forceinline__ OcTiles<L> oc_tile_offsets(const ChgPlan& p, const u32* __restrict__ cnt, const u32* __restrict__ gsum,
+                                                      L limit, u32* toff, u32* lds) {
+    const L base = gsum[blockIdx.x];
+    if (base >= limit || gsum[blockIdx.x + 1] == base) return {false, base, 0u, 0u};
+    const u32 t0 = blockIdx.x * p.tpg, k = p.tpg < p.nt - t0 ? p.tpg : p.nt - t0;
+    constexpr u32 per = kChgMaxTpg / (kChgWaves * 64);
+    u32 v[per], sum = 0;
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        const u32 i = threadIdx.x * per + q;
+        v[q] = i < k ? cnt[t0 + i] : 0u;
+        sum += v[q];
+    }
+    u32 tot;
+    u32 run = ni_block_excl(sum, lds, &tot);
+#pragma unroll
+    for (u32 q = 0; q < per; ++q) {
+        const u32 i = threadIdx.x * per + q;
+        if (i < k) toff[i] = run;
+        run += v[q];
+    }
+    return {true, base, k, tot};
+}
+
+// flags16(lo, lane) -> the lane's hits of the tile at row lo, a nibble per step (bit 4s + j: row lo + 256s + 4 lane + j);
+// emit(step, i0, f, r, limit) runs on the lanes with a hit in the step: f the step's nibble, i0 the lane's first row of the step,
+// r the position of its first hit (the next hit's is r + 1, ...; the body drops those >= limit).  Both may keep state between
+// the calls: flags16 of a tile comes before its emits.
+template <class L, class Flags, class Emit>
+__device__ __forceinline__ void oc_rank(const ChgPlan& p, const OcTiles<L>& tl, const u32* toff, L limit, Flags&& flags16,
+                                        Emit&& emit) {
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u32 t0 = blockIdx.x * p.tpg;
+    const u64 lt = (1ull << lane) - 1ull;
+    for (u32 i = wv; i < tl.k; i += kChgWaves) {  // wave-uniform
+        L off = tl.base + toff[i];
+        const u32 c = (i + 1 < tl.k ? toff[i + 1] : tl.tot) - toff[i];
+        if (c == 0 || off >= limit) continue;
+        const u64 lo = (u64)(t0 + i) * kChgTile;
+        const u32 fl = flags16(lo, lane);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const u32 f = (fl >> (4 * s)) & 15u;
+            const u32 lc = (u32)__builtin_popcount(f);  // 0 .. 4
+            u32 below = 0, all = 0;
+#pragma unroll
+            for (int bit = 0; bit < 3; ++bit) {
+                const u64 bb = __ballot((lc >> bit) & 1u);
+                below += (u32)__builtin_popcountll(bb & lt) << bit;
+                all += (u32)__builtin_popcountll(bb) << bit;
+            }
+            if (f) emit(s, lo + (u64)s * 256 + lane * 4, f, (L)(off + below), limit);
+            off += all;
+            if (off >= limit) break;  // (wave-uniform)
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Change feed (rio_gp_changes): the rows r < n whose committed node A[r] differs from the consumer's checkpoint B[r].
+//   k_chg_count  the count pass over A != B (dwordx4 loads of both columns).
+//   k_chg_list   the list pass: a listed row goes out as (row, B[row], A[row]); consuming, a lane that listed a row stores its
+//                four B words back (dwordx4) with the listed ones advanced.  The wave holds its tile of A and B across the
+//                listing (no quad is read twice) and keeps a ranking loop of its own for it, over oc_tile_offsets.
+// ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void chg_load(const u32* __restrict__ A, const u32* __restrict__ B, u64 lo, u32 lane, uint4 (&a)[4],
                                          uint4 (&b)[4]) {
 #pragma unroll
@@ -7187,26 +7286,14 @@ __device__ __forceinline__ u32 chg_flags(const uint4& a, const uint4& b, u64 i0,
 
 __global__ __launch_bounds__(kChgWaves * 64) void k_chg_count(const u32* __restrict__ A, const u32* __restrict__ B, const ChgPlan p,
                                                                u32* __restrict__ cnt, u32* __restrict__ gsum) {
-    __shared__ u32 ws[kChgWaves];
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const u32 t0 = blockIdx.x * p.tpg, t1 = t0 + p.tpg < p.nt ? t0 + p.tpg : p.nt;
-    u32 mine = 0;
-    for (u32 t = t0 + wv; t < t1; t += kChgWaves) {  // wave-uniform
-        const u64 lo = (u64)t * kChgTile;
+    oc_count(p, cnt, gsum, [&](u64 lo, u32 lane) {
         uint4 a[4], b[4];
         chg_load(A, B, lo, lane, a, b);
-        u32 c = 0;  // 0 .. 16
+        u32 c = 0;
 #pragma unroll
         for (int s = 0; s < 4; ++s) c += __builtin_popcount(chg_flags(a[s], b[s], lo + (u64)s * 256 + lane * 4, p.n));
-        u32 tc = 0;
-#pragma unroll
-        for (int bit = 0; bit < 5; ++bit) tc += (u32)__builtin_popcountll(__ballot((c >> bit) & 1u)) << bit;
-        if (lane == 0) cnt[t] = tc;
-        mine += tc;
-    }
-    if (lane == 0) ws[wv] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) gsum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+        return c;
+    });
 }
 
 // One workgroup: the exclusive scan of the G workgroup sums in place, gsum[G] = the total, also into the mapped word
@@ -7240,31 +7327,17 @@ __global__ __launch_bounds__(kChgWaves * 64) void k_chg_list(const u32* __restri
                                                               u32* __restrict__ new_node) {
     __shared__ u32 toff[kChgMaxTpg];
     __shared__ u32 lds[4];
-    const u64 base = gsum[blockIdx.x];
-    if (base >= cap || gsum[blockIdx.x + 1] == base) return;  // everything past the listing, or nothing here
-    const u32 t0 = blockIdx.x * p.tpg, k = p.tpg < p.nt - t0 ? p.tpg : p.nt - t0;
-    constexpr u32 per = kChgMaxTpg / (kChgWaves * 64);
-    u32 v[per], sum = 0;
-#pragma unroll
-    for (u32 q = 0; q < per; ++q) {
-        const u32 i = threadIdx.x * per + q;
-        v[q] = i < k ? cnt[t0 + i] : 0u;
-        sum += v[q];
-    }
-    u32 tot;
-    u32 run = ni_block_excl(sum, lds, &tot);
-#pragma unroll
-    for (u32 q = 0; q < per; ++q) {
-        const u32 i = threadIdx.x * per + q;
-        if (i < k) toff[i] = run;
-        run += v[q];
-    }
+    const OcTiles<u64> tl = oc_tile_offsets(p, cnt, gsum, cap, toff, lds);
+    if (!tl.go) return;
     __syncthreads();
+    // oc_rank's loop with the flags taken step by step from the tile in registers: through oc_rank (all four nibbles first) the
+    // compiler's code for the per-row body was longer, and ~10^4 changes over 10 M rows listed 3 % slower
     const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u32 t0 = blockIdx.x * p.tpg;
     const u64 lt = (1ull << lane) - 1ull;
-    for (u32 i = wv; i < k; i += kChgWaves) {  // wave-uniform
-        u64 off = base + toff[i];
-        const u32 c = (i + 1 < k ? toff[i + 1] : tot) - toff[i];
+    for (u32 i = wv; i < tl.k; i += kChgWaves) {  // wave-uniform
+        u64 off = tl.base + toff[i];
+        const u32 c = (i + 1 < tl.k ? toff[i + 1] : tl.tot) - toff[i];
         if (c == 0 || off >= cap) continue;
         const u64 lo = (u64)(t0 + i) * kChgTile;
         uint4 a[4], b[4];
@@ -7339,7 +7412,7 @@ void launch_chg_list(const u32* A, u32* B, const ChgPlan& p, const u32* cnt, con
 //   * a column's tile is stored (whole: 1 KiB per wave-instruction) only where the ballot says one of its values changed — the
 //     removal of one node of a thousand leaves most tiles of the assignment column and almost all of the other two alone, a pure
 //     permutation rewrites all three (8 or 12 B read per row, 0 .. 8 or 12 B written);
-//   * whole tiles are read and written: the columns are padded past max_objects (k_chg_count's note), and rows past `rows` hold
+//   * whole tiles are read and written: the columns are padded past max_objects (the ordered compaction's note), and rows past `rows` hold
 //     kNone, which maps to itself;
 //   * the evicted count (rows < n_count only: hidden rows are cleaned but are no objects of the table) is summed per wave, then
 //     per workgroup in LDS, and leaves as workgroup b's row of the per-workgroup counter rows blk[G][4] (the solve's blkstat: kept |
@@ -7408,16 +7481,16 @@ u32 launch_remap(u32* assign, u32* aff, u32* B, u64 rows, u64 n_count, u32 m, co
 
 // ------------------------------------------------------------------------------------------------
 // Idle expiry (rio_gp_touch_*, rio_gp_expire; DESIGN.md section 2 rule 9): a last-seen column S, one u32 per row, and the rows
-// r < n that are placed (A[r] != kNone, raw values) with S[r] < cutoff.  The shape is the change feed's — a count pass, the
-// one-workgroup scan (k_chg_scan itself), a pass over the tiles that hold a hit — with the same plan, the same per-tile counts
-// and workgroup sums, and no fence and no workgroup waiting on another:
-//   k_exp_count  k_chg_count with the idle predicate over (A, S); workgroup 0 also zeroes the freed-load word.
-//   k_exp_apply  k_chg_list's ranking (ballots over each lane's 0..4); a listed row is written out as (row, A[row]), loses its
-//                node (the lane stores its four A words back, dwordx4) and, under the row lifecycle, becomes a non-object; its
-//                load goes into the freed-load sum and, when `used` is maintained, off its node: per workgroup through an LDS
-//                histogram (m <= kExpLdsNodes: a workgroup's rows share few nodes' words), else straight to `used` (more nodes
-//                than that spread the atomics over as many addresses; the histogram would not fit next to the tile offsets).
-//                Integer sums: the order of the additions does not show.
+// r < n that are placed (A[r] != kNone, raw values) with S[r] < cutoff: an ordered compaction, on the feed's per-tile counts and
+// workgroup sums.
+//   k_exp_count  the count pass over the idle predicate on (A, S); workgroup 0 also zeroes the freed-load word.
+//   k_exp_apply  the list pass: a listed row is written out as (row, A[row]), loses its node (the lane stores its four A words
+//                back, dwordx4) and, under the row lifecycle, becomes a non-object; its load goes into the freed-load sum and,
+//                when `used` is maintained, off its node: per workgroup through an LDS histogram (m <= kExpLdsNodes: a
+//                workgroup's rows share few nodes' words), else straight to `used` (more nodes than that spread the atomics over
+//                as many addresses; the histogram would not fit next to the tile offsets).  Integer sums: the order of the
+//                additions does not show.  Only the tile's flags outlive its loads: a lane with a hit reads its quad of A again
+//                (a cache hit); holding the tile across the listing spilled to scratch at eight waves per SIMD.
 //   k_touch      S[idx[k]] = max(S[idx[k]], epoch), a scatter of atomic maxima: duplicates and order do not matter.
 //   k_seen_merge S[r] = max(S[r], stamps ? stamps[r] : epoch) for r < rows, four rows per lane; a quad is stored only where it
 //                rose.  S is padded like the other columns; `stamps` is the caller's and is read by quads only where whole quads
@@ -7432,29 +7505,15 @@ __device__ __forceinline__ u32 exp_flags(const uint4& a, const uint4& s, u32 cut
 __global__ __launch_bounds__(kChgWaves * 64, 8) void k_exp_count(const u32* __restrict__ A, const u32* __restrict__ S, const ChgPlan p,
                                                                u32 cutoff, u32* __restrict__ cnt, u32* __restrict__ gsum,
                                                                u64* __restrict__ freed) {
-    __shared__ u32 ws[kChgWaves];
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const u32 t0 = blockIdx.x * p.tpg, t1 = t0 + p.tpg < p.nt ? t0 + p.tpg : p.nt;
-    u32 mine = 0;
-    for (u32 t = t0 + wv; t < t1; t += kChgWaves) {  // wave-uniform
-        const u64 lo = (u64)t * kChgTile;
+    oc_count(p, cnt, gsum, [&](u64 lo, u32 lane) {
         uint4 a[4], sv[4];
         chg_load(A, S, lo, lane, a, sv);
-        u32 c = 0;  // 0 .. 16
+        u32 c = 0;
 #pragma unroll
         for (int s = 0; s < 4; ++s) c += __builtin_popcount(exp_flags(a[s], sv[s], cutoff, lo + (u64)s * 256 + lane * 4, p.n));
-        u32 tc = 0;
-#pragma unroll
-        for (int bit = 0; bit < 5; ++bit) tc += (u32)__builtin_popcountll(__ballot((c >> bit) & 1u)) << bit;
-        if (lane == 0) cnt[t] = tc;
-        mine += tc;
-    }
-    if (lane == 0) ws[wv] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        gsum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-        if (blockIdx.x == 0) *freed = 0;  // (k_exp_apply, a later launch, adds into it)
-    }
+        return c;
+    });
+    if (threadIdx.x == 0 && blockIdx.x == 0) *freed = 0;  // (k_exp_apply, a later launch, adds into it)
 }
 
 __global__ __launch_bounds__(kChgWaves * 64, 8) void k_exp_apply(u32* __restrict__ A, const u32* __restrict__ S, const ChgPlan p,
@@ -7468,86 +7527,47 @@ __global__ __launch_bounds__(kChgWaves * 64, 8) void k_exp_apply(u32* __restrict
     __shared__ u32 toff[kChgMaxTpg];
     __shared__ u32 lds[4];
     __shared__ u64 gfree;
-    const u64 base = gsum[blockIdx.x];
-    if (base >= cap || gsum[blockIdx.x + 1] == base) return;  // everything past the listing, or nothing here
-    const u32 t0 = blockIdx.x * p.tpg, k = p.tpg < p.nt - t0 ? p.tpg : p.nt - t0;
-    constexpr u32 per = kChgMaxTpg / (kChgWaves * 64);
-    u32 v[per], sum = 0;
-#pragma unroll
-    for (u32 q = 0; q < per; ++q) {
-        const u32 i = threadIdx.x * per + q;
-        v[q] = i < k ? cnt[t0 + i] : 0u;
-        sum += v[q];
-    }
-    u32 tot;
-    u32 run = ni_block_excl(sum, lds, &tot);
-#pragma unroll
-    for (u32 q = 0; q < per; ++q) {
-        const u32 i = threadIdx.x * per + q;
-        if (i < k) toff[i] = run;
-        run += v[q];
-    }
+    const OcTiles<u64> tl = oc_tile_offsets(p, cnt, gsum, cap, toff, lds);
+    if (!tl.go) return;
     if (hist)
         for (u32 j = threadIdx.x; j < m; j += kChgWaves * 64) rel[j] = 0;
     if (threadIdx.x == 0) gfree = 0;
     __syncthreads();
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const u64 lt = (1ull << lane) - 1ull;
     u64 fr = 0;
-    for (u32 i = wv; i < k; i += kChgWaves) {  // wave-uniform
-        u64 off = base + toff[i];
-        const u32 c = (i + 1 < k ? toff[i + 1] : tot) - toff[i];
-        if (c == 0 || off >= cap) continue;
-        const u64 lo = (u64)(t0 + i) * kChgTile;
-        u32 fl = 0;  // the four steps' flags, a nibble each; a lane with a hit reads its quad of A again (a cache hit), so that
-                     // no tile is held in registers across the listing (it spilled to scratch at eight waves per SIMD)
-        {
+    oc_rank(
+        p, tl, toff, cap,
+        [&](u64 lo, u32 lane) {
             uint4 a[4], sv[4];
             chg_load(A, S, lo, lane, a, sv);
+            u32 fl = 0;
 #pragma unroll
             for (int s = 0; s < 4; ++s) fl |= exp_flags(a[s], sv[s], cutoff, lo + (u64)s * 256 + lane * 4, p.n) << (4 * s);
-        }
+            return fl;
+        },
+        [&](int, u64 i0, u32 f, u64 r, u64 limit) {
+            const uint4 q =*reinterpret_cast<const uint4*>(A + i0);
+            u32 av[4] = {q.x, q.y, q.z, q.w};
+            bool listed = false;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const u64 i0 = lo + (u64)s * 256 + lane * 4;
-            const u32 f = (fl >> (4 * s)) & 15u;
-            const u32 lc = (u32)__builtin_popcount(f);  // 0 .. 4
-            u32 below = 0, all = 0;
-#pragma unroll
-            for (int bit = 0; bit < 3; ++bit) {
-                const u64 bb = __ballot((lc >> bit) & 1u);
-                below += (u32)__builtin_popcountll(bb & lt) << bit;
-                all += (u32)__builtin_popcountll(bb) << bit;
-            }
-            if (f) {
-                const uint4 q = *reinterpret_cast<const uint4*>(A + i0);
-                u32 av[4] = {q.x, q.y, q.z, q.w};
-                u64 r = off + below;
-                bool listed = false;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (!((f >> j) & 1u)) continue;
-                    if (r < cap) {
-                        const u32 li = load[i0 + j];
-                        rows[r] = (u32)(i0 + j);
-                        node[r] = av[j];
-                        fr += li;
-                        if (used && av[j] < m) {
-                            if (hist) atomicAdd(&rel[av[j]], (u64)li);
-                            else atomicAdd(&used[av[j]], (u64)0 - (u64)li);
-                        }
-                        if (aff_life) aff_life[i0 + j] = kAffInactive;  // row lifecycle: an expired row is no longer an object
-                        av[j] = kNone;
-                        listed = true;
+            for (int j = 0; j < 4; ++j) {
+                if (!((f >> j) & 1u)) continue;
+                if (r < limit) {
+                    const u32 li = load[i0 + j];
+                    rows[r] = (u32)(i0 + j);
+                    node[r] = av[j];
+                    fr += li;
+                    if (used && av[j] < m) {
+                        if (hist) atomicAdd(&rel[av[j]], (u64)li);
+                        else atomicAdd(&used[av[j]], (u64)0 - (u64)li);
                     }
-                    ++r;
+                    if (aff_life) aff_life[i0 + j] = kAffInactive;  // row lifecycle: an expired row is no longer an object
+                    av[j] = kNone;
+                    listed = true;
                 }
-                if (listed) *reinterpret_cast<uint4*>(A + i0) = make_uint4(av[0], av[1], av[2], av[3]);
+                ++r;
             }
-            off += all;
-            if (off >= cap) break;  // (wave-uniform)
-        }
-    }
+            if (listed) *reinterpret_cast<uint4*>(A + i0) = make_uint4(av[0], av[1], av[2], av[3]);
+        });
     if (fr) atomicAdd(&gfree, fr);
     __syncthreads();
     if (threadIdx.x == 0 && gfree) atomicAdd(freed, gfree);
@@ -7774,9 +7794,9 @@ void launch_load_fold(u32* load, u32* H, const u32* A, u64 n, u32 keep, u32 gain
 //                otherwise the digit whose bin holds rank `want` from the top, and the rank that remains inside that bin.  After
 //                the third digit `prefix` is the threshold T and `want` the number t of rows with K == T to list.
 //   k_top_collect  candidates with K > T (all of them under `all`) take a slot of `pairs` through an atomic cursor — their
-//                order does not matter — and the candidates with K == T are counted per tile and workgroup (k_chg_count's shape).
-//   k_chg_scan   the feed's one-workgroup scan of the workgroup sums.
-//   k_top_ties   k_chg_list's ranking over the tiles that hold a tie: the first t of them, by row, go behind the cap - t others.
+//                order does not matter — while the candidates with K == T are counted: the count pass of an ordered compaction.
+//   k_chg_scan   the one-workgroup scan of the workgroup sums.
+//   k_top_ties   its list pass: the first t ties, by row, go behind the cap - t others.  Only a tile's flags outlive its loads.
 //   k_top_sort   one workgroup sorts the at most 4 096 composites (K << 32) | ~row, descending, in LDS (a bitonic network over the
 //                next power of two) and writes rows, keys and A[row]: the output does not depend on the order of any atomic.
 // No workgroup waits for another; the host enqueues all of it and waits once.
@@ -7911,16 +7931,11 @@ __global__ __launch_bounds__(kChgWaves * 64, 8) void k_top_collect(const u32* __
                                                                  const ChgPlan p, u32 min_key, u32 filt, u32 node, u32 cap,
                                                                  TopScratch* __restrict__ sc, u32* __restrict__ cnt,
                                                                  u32* __restrict__ gsum) {
-    __shared__ u32 ws[kChgWaves];
     const u32 all = sc->all, T = sc->prefix;
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const u32 t0 = blockIdx.x * p.tpg, t1 = t0 + p.tpg < p.nt ? t0 + p.tpg : p.nt;
-    u32 mine = 0;
-    for (u32 t = t0 + wv; t < t1; t += kChgWaves) {  // wave-uniform
-        const u64 lo = (u64)t * kChgTile;
+    oc_count(p, cnt, gsum, [&](u64 lo, u32 lane) {
         uint4 k[4], a[4];
         top_load<FILT>(K, A, lo, lane, k, a);
-        u32 c = 0;  // 0 .. 16
+        u32 c = 0;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const u64 i0 = lo + (u64)s * 256 + lane * 4;
@@ -7937,15 +7952,8 @@ __global__ __launch_bounds__(kChgWaves * 64, 8) void k_top_collect(const u32* __
                 }
             }
         }
-        u32 tc = 0;
-#pragma unroll
-        for (int bit = 0; bit < 5; ++bit) tc += (u32)__builtin_popcountll(__ballot((c >> bit) & 1u)) << bit;
-        if (lane == 0) cnt[t] = tc;
-        mine += tc;
-    }
-    if (lane == 0) ws[wv] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) gsum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+        return c;
+    });
 }
 
 template <bool FILT>
@@ -7958,64 +7966,28 @@ __global__ __launch_bounds__(kChgWaves * 64, 8) void k_top_ties(const u32* __res
     if (sc->all) return;
     const u32 T = sc->prefix, ties = sc->want < cap ? sc->want : cap;  // the first `ties` rows with K == T are listed,
     const u32 first = cap - ties;                                      // behind the cap - ties rows with K > T
-    const u32 base = gsum[blockIdx.x];
-    if (base >= ties || gsum[blockIdx.x + 1] == base) return;  // everything past the listing, or nothing here
-    const u32 t0 = blockIdx.x * p.tpg, k = p.tpg < p.nt - t0 ? p.tpg : p.nt - t0;
-    constexpr u32 per = kChgMaxTpg / (kChgWaves * 64);
-    u32 v[per], sum = 0;
-#pragma unroll
-    for (u32 q = 0; q < per; ++q) {
-        const u32 i = threadIdx.x * per + q;
-        v[q] = i < k ? cnt[t0 + i] : 0u;
-        sum += v[q];
-    }
-    u32 tot;
-    u32 run = ni_block_excl(sum, lds, &tot);
-#pragma unroll
-    for (u32 q = 0; q < per; ++q) {
-        const u32 i = threadIdx.x * per + q;
-        if (i < k) toff[i] = run;
-        run += v[q];
-    }
+    const OcTiles<u32> tl = oc_tile_offsets(p, cnt, gsum, ties, toff, lds);
+    if (!tl.go) return;
     __syncthreads();
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const u64 lt = (1ull << lane) - 1ull;
-    for (u32 i = wv; i < k; i += kChgWaves) {  // wave-uniform
-        u32 off = base + toff[i];
-        const u32 c = (i + 1 < k ? toff[i + 1] : tot) - toff[i];
-        if (c == 0 || off >= ties) continue;
-        const u64 lo = (u64)(t0 + i) * kChgTile;
-        u32 fl = 0;  // the four steps' flags, a nibble each (k_exp_apply's form: no tile is held in registers across the listing)
-        {
+    oc_rank(
+        p, tl, toff, ties,
+        [&](u64 lo, u32 lane) {
             uint4 kq[4], a[4];
             top_load<FILT>(K, A, lo, lane, kq, a);
+            u32 fl = 0;
 #pragma unroll
             for (int s = 0; s < 4; ++s)
                 fl |= top_tie_flags<FILT>(kq[s], a[s], lo + (u64)s * 256 + lane * 4, p.n, min_key, filt, node, T) << (4 * s);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const u64 i0 = lo + (u64)s * 256 + lane * 4;
-            const u32 f = (fl >> (4 * s)) & 15u;
-            const u32 lc = (u32)__builtin_popcount(f);  // 0 .. 4
-            u32 below = 0, allc = 0;
-#pragma unroll
-            for (int bit = 0; bit < 3; ++bit) {
-                const u64 bb = __ballot((lc >> bit) & 1u);
-                below += (u32)__builtin_popcountll(bb & lt) << bit;
-                allc += (u32)__builtin_popcountll(bb) << bit;
-            }
-            u32 r = off + below;
+            return fl;
+        },
+        [&](int, u64 i0, u32 f, u32 r, u32 limit) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (!((f >> j) & 1u)) continue;
-                if (r < ties) sc->pairs[first + r] = ((u64)T << 32) | (u32)~(u32)(i0 + j);
+                if (r < limit) sc->pairs[first + r] = ((u64)T << 32) | (u32)~(u32)(i0 + j);
                 ++r;
             }
-            off += allc;
-            if (off >= ties) break;  // (wave-uniform)
-        }
-    }
+        });
 }
 
 // One workgroup: the L = min(n_candidates, cap) composites, descending, then rows / keys / nodes and the two sums for the host.

@@ -14,6 +14,7 @@
 #include <chrono>
 #include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -36,6 +37,13 @@ constexpr u32 kUsedRing = 4;  // `used` buffers (rio_gp::used_ring): two chained
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+};
+// A column of cap_rows u32 that a feature allocates and fills on its first use (lazy_fill).  It reads as nullptr until the fill
+// is enqueued: a call after a failed allocation or fill allocates only what is still missing.
+struct LazyColumn {
+    u32* mem = nullptr;  // allocated
+    bool filled = false;
+    operator u32*() const { return filled ? mem : nullptr; }
 };
 
 }  // namespace
@@ -522,18 +530,16 @@ struct rio_gp {
     // change feed (rio_gp_changes), allocated on first use: the checkpoint column B (cap_rows u32, RIO_GP_NONE to begin with), the
     // per-tile counts, the workgroup sums + total, a mapped word the total arrives in; the host-pointer form's staged listing
     // (row | old | new, grows to the largest listing)
-    u32 *chg_B = nullptr, *chg_cnt = nullptr, *chg_gsum = nullptr;
-    u32* chg_Bmem = nullptr;  // B's memory, allocated; chg_B is set once it has been filled
+    LazyColumn chg_B;
+    u32 *chg_cnt = nullptr, *chg_gsum = nullptr;
     u32 *h_chg = nullptr, *d_chg = nullptr;
     DevBuf chg_stage;
     // idle expiry (rio_gp_touch_*, rio_gp_expire), allocated on first use: the last-seen column S (cap_rows u32, 0 to begin with)
     // and the freed-load word; the passes use the feed's counts, sums and mapped words (no two calls overlap on the stream)
-    u32* exp_S = nullptr;
-    u32* exp_Smem = nullptr;  // S's memory, allocated; exp_S is set once it has been filled
+    LazyColumn exp_S;
     u64* exp_freed = nullptr;
     // measured load (rio_gp_hits_*, rio_gp_load_fold), allocated on first use: the hit column H (cap_rows u32, 0 to begin with)
-    u32* hits_H = nullptr;
-    u32* hits_Hmem = nullptr;  // H's memory, allocated; hits_H is set once it has been filled
+    LazyColumn hits_H;
     // hot-object report (rio_gp_top_rows), allocated on first use: the selection's device state, and pinned host memory for the
     // two sums and the host-pointer form's listing (16 + 12 * RIO_GP_TOP_MAX bytes); the per-tile counts are the feed's
     TopScratch* top_sc = nullptr;
@@ -656,6 +662,28 @@ int ensure(rio_gp* h, DevBuf& b, size_t bytes) {
     if (e != hipSuccess) return fail(h, e == hipErrorOutOfMemory ? RIO_GP_ENOMEM : RIO_GP_EUPSTREAM,
                                       std::string("hipMalloc(staging): ") + hipGetErrorString(e));
     b.bytes = bytes;
+    return RIO_GP_OK;
+}
+
+// first use of a lazily filled column: allocate (once), fill with `value`, publish
+int lazy_fill(rio_gp* h, LazyColumn& c, u32 value) {
+    if (c.filled) return RIO_GP_OK;
+    int rc;
+    if (!c.mem && (rc = dalloc(h, &c.mem, h->cap_rows))) return rc;
+    launch_fill_u32(c.mem, h->cap_rows, value, h->stream);
+    HIPCHK(h, hipGetLastError());
+    c.filled = true;  // (last: it is what says the column is complete)
+    return RIO_GP_OK;
+}
+
+// The host-pointer form of a listing: the first L words of each of the k arrays staged at d, d + stride, ... go into the
+// caller's k arrays; k async copies, one wait.
+int read_listing(rio_gp* h, const u32* d, u64 stride, u64 L, std::initializer_list<u32*> out) {
+    for (u32* o : out) {
+        HIPCHK(h, hipMemcpyAsync(o, d, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+        d += stride;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return RIO_GP_OK;
 }
 
@@ -929,8 +957,13 @@ int may_start(rio_gp* h, Client who) {
         why = "64 ticks in flight (call rio_gp_shard_tick_wait)";
     return why ? fail(h, RIO_GP_EINVAL, std::string(name[(int)who]) + ": " + why) : RIO_GP_OK;
 }
-// rio_gp_rebalance, rio_gp_changes, rio_gp_changes_reset and rio_gp_remap_nodes work on a whole table: not on one rank's rows
 bool row_sharded(const rio_gp* h) { return h->sc || h->p2p || h->ticks.count(TickRing::Owner::shard_ticks); }
+// The rebalance, the change feed, node removal, idle expiry, measured load and the hot-object report work on a whole table, not
+// on one rank's rows: `who` is refused on a handle of the row-sharded solve.
+int refuse_row_sharded(rio_gp* h, const char* who) {
+    if (!row_sharded(h)) return RIO_GP_OK;
+    return fail(h, RIO_GP_EINVAL, std::string(who) + ": not implemented on a handle of the row-sharded solve");
+}
 
 // the fix-up kernels of the next solve write their per-workgroup counter rows into pinned slot `slot` (0: synchronous
 // solves, 1 + k: asynchronous tick k)
@@ -1914,8 +1947,7 @@ static int rebalance_args(rio_gp* h, const rio_gp_rebalance_cfg* cfg, const void
     if ((r != nullptr) != (f != nullptr) || (r != nullptr) != (t != nullptr))
         return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: out_rows / out_from / out_to are given together or not at all");
     if (!r && cap) return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: moves_cap without a move listing");
-    if (row_sharded(h))
-        return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: not implemented on a handle of the row-sharded solve");
+    if (int rc = refuse_row_sharded(h, "rio_gp_rebalance")) return rc;
     *rounds = cfg->rounds ? cfg->rounds : h->rounds;
     *budget = r ? std::min<u64>(cfg->max_moves, cap) : cfg->max_moves;
     return RIO_GP_OK;
@@ -1941,12 +1973,7 @@ int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebala
     if ((rc = rebalance_locked(h, cfg, order, rounds, budget, st, d, d ? d + stage : nullptr, d ? d + 2 * stage : nullptr, &nm)))
         return rc;
     if (n_moves) *n_moves = nm;
-    if (out_rows && nm) {
-        HIPCHK(h, hipMemcpyAsync(out_rows, d, nm * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(out_from, d + stage, nm * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(out_to, d + 2 * stage, nm * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
+    if (out_rows && nm) return read_listing(h, d, stage, nm, {out_rows, out_from, out_to});
     return RIO_GP_OK;
 }
 
@@ -1986,11 +2013,7 @@ static int chg_scratch(rio_gp* h) {
     if (h->chg_B) return RIO_GP_OK;
     int rc;
     if ((rc = chg_counters(h))) return rc;
-    if (!h->chg_Bmem && (rc = dalloc(h, &h->chg_Bmem, h->cap_rows))) return rc;
-    launch_fill_u32(h->chg_Bmem, h->cap_rows, kNone, h->stream);
-    HIPCHK(h, hipGetLastError());
-    h->chg_B = h->chg_Bmem;  // (last: it is what says the state is complete)
-    return RIO_GP_OK;
+    return lazy_fill(h, h->chg_B, kNone);
 }
 
 // checks shared by both forms: nothing is changed before they pass
@@ -2000,9 +2023,7 @@ static int chg_args(rio_gp* h, uint32_t flags, const void* r, const void* o, con
     if ((r != nullptr) != (o != nullptr) || (r != nullptr) != (w != nullptr))
         return fail(h, RIO_GP_EINVAL, "rio_gp_changes: out_rows / out_old / out_new are given together or not at all");
     if (!r && cap) return fail(h, RIO_GP_EINVAL, "rio_gp_changes: cap without a listing");
-    if (row_sharded(h))
-        return fail(h, RIO_GP_EINVAL, "rio_gp_changes: not implemented on a handle of the row-sharded solve");
-    return RIO_GP_OK;
+    return refuse_row_sharded(h, "rio_gp_changes");
 }
 
 // The count pass over the committed column and B (rows 0 .. n-1); the total lands in the mapped word.  Nothing here touches the
@@ -2034,11 +2055,7 @@ int rio_gp_changes(rio_gp_t* h, uint32_t flags, uint32_t* out_rows, uint32_t* ou
     launch_chg_list(h->assign[h->cur], h->chg_B, p, h->chg_cnt, h->chg_gsum, L, !(flags & RIO_GP_CHANGES_PEEK), d, d + L, d + 2 * L,
                     h->stream);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out_rows, d, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(out_old, d + L, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(out_new, d + 2 * L, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return RIO_GP_OK;
+    return read_listing(h, d, L, L, {out_rows, out_old, out_new});
 }
 
 int rio_gp_changes_dev(rio_gp_t* h, uint32_t flags, uint32_t* d_rows, uint32_t* d_old, uint32_t* d_new, uint64_t cap,
@@ -2063,8 +2080,7 @@ int rio_gp_changes_dev(rio_gp_t* h, uint32_t flags, uint32_t* d_rows, uint32_t* 
 int rio_gp_changes_reset(rio_gp_t* h) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    if (row_sharded(h))
-        return fail(h, RIO_GP_EINVAL, "rio_gp_changes_reset: not implemented on a handle of the row-sharded solve");
+    if (int rc = refuse_row_sharded(h, "rio_gp_changes_reset")) return rc;
     if (!h->chg_B) return RIO_GP_OK;  // (never used: the first listing is complete anyway)
     HIPCHK(h, hipSetDevice(h->device));
     launch_fill_u32(h->chg_B, h->cap_rows, kNone, h->stream);
@@ -2081,15 +2097,11 @@ static int exp_scratch(rio_gp* h) {
     int rc;
     if ((rc = chg_counters(h))) return rc;
     if (!h->exp_freed && (rc = dalloc(h, &h->exp_freed, 1))) return rc;
-    if (!h->exp_Smem && (rc = dalloc(h, &h->exp_Smem, h->cap_rows))) return rc;
-    launch_fill_u32(h->exp_Smem, h->cap_rows, 0u, h->stream);
-    HIPCHK(h, hipGetLastError());
-    h->exp_S = h->exp_Smem;  // (last: it is what says the state is complete)
-    return RIO_GP_OK;
+    return lazy_fill(h, h->exp_S, 0u);
 }
 // what every call of the family does first (one rule: no last-seen column on a handle of the row-sharded solve)
 static int exp_begin(rio_gp* h, const char* who) {
-    if (row_sharded(h)) return fail(h, RIO_GP_EINVAL, std::string(who) + ": not implemented on a handle of the row-sharded solve");
+    if (int rc = refuse_row_sharded(h, who)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     return exp_scratch(h);
 }
@@ -2111,10 +2123,10 @@ int rio_gp_touch_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, uint3
 int rio_gp_touch_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, uint32_t epoch) {
     if (!h || (n && !idx)) return RIO_GP_EINVAL;
     Locked g(h);
-    if (row_sharded(h)) return fail(h, RIO_GP_EINVAL, "rio_gp_touch_batch: not implemented on a handle of the row-sharded solve");
+    int rc;
+    if ((rc = refuse_row_sharded(h, "rio_gp_touch_batch"))) return rc;
     for (uint64_t k = 0; k < n; ++k)
         if (idx[k] >= h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_touch_batch: object index out of range");
-    int rc;
     if ((rc = exp_begin(h, "rio_gp_touch_batch"))) return rc;
     if (!n) return RIO_GP_OK;
     if ((rc = ensure(h, h->stage[0], n * sizeof(u32)))) return rc;
@@ -2217,9 +2229,7 @@ int rio_gp_expire(rio_gp_t* h, uint32_t cutoff, uint32_t* out_rows, uint32_t* ou
     u32* d = (u32*)h->chg_stage.p;
     inputs_changed(h);  // from here on it is a rio_gp_remove_batch of the listed rows
     if ((rc = exp_apply(h, p, cutoff, L, d, d + L))) return rc;
-    HIPCHK(h, hipMemcpyAsync(out_rows, d, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(out_node, d + L, L * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = read_listing(h, d, L, L, {out_rows, out_node}))) return rc;
     if (load_freed) *load_freed = reinterpret_cast<const u64*>(h->h_chg)[1];
     return RIO_GP_OK;
 }
@@ -2251,21 +2261,12 @@ int rio_gp_expire_dev(rio_gp_t* h, uint32_t cutoff, uint32_t* d_rows, uint32_t* 
 
 // ---- measured load ----------------------------------------------------------------------------
 
-// The hit column on first use (0 everywhere).
-static int hits_scratch(rio_gp* h) {
-    if (h->hits_H) return RIO_GP_OK;
-    int rc;
-    if (!h->hits_Hmem && (rc = dalloc(h, &h->hits_Hmem, h->cap_rows))) return rc;
-    launch_fill_u32(h->hits_Hmem, h->cap_rows, 0u, h->stream);
-    HIPCHK(h, hipGetLastError());
-    h->hits_H = h->hits_Hmem;  // (last: it is what says the state is complete)
-    return RIO_GP_OK;
-}
-// what every call of the family does first (one rule: no hit column on a handle of the row-sharded solve)
+// what every call of the family does first (one rule: no hit column on a handle of the row-sharded solve): the hit column on
+// first use, 0 everywhere
 static int hits_begin(rio_gp* h, const char* who) {
-    if (row_sharded(h)) return fail(h, RIO_GP_EINVAL, std::string(who) + ": not implemented on a handle of the row-sharded solve");
+    if (int rc = refuse_row_sharded(h, who)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    return hits_scratch(h);
+    return lazy_fill(h, h->hits_H, 0u);
 }
 
 // The hits calls write H and nothing else: no inputs_changed, `used` and the solve in flight stay as they are.
@@ -2401,8 +2402,7 @@ static int top_args(rio_gp* h, uint32_t flags, uint32_t node, const void* r, con
     if ((r != nullptr) != (k != nullptr)) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: out_rows / out_key are given together or not at all");
     if (!r && (cap || o)) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: cap or out_node without a listing");
     if ((flags & RIO_GP_TOP_ON_NODE) && node >= h->m) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: node out of range");
-    if (row_sharded(h)) return fail(h, RIO_GP_EINVAL, "rio_gp_top_rows: not implemented on a handle of the row-sharded solve");
-    return RIO_GP_OK;
+    return refuse_row_sharded(h, "rio_gp_top_rows");
 }
 
 // Both forms: every pass enqueued behind whatever the handle has in flight, the two sums (and, for the host form, the listing
@@ -2739,8 +2739,7 @@ int rio_gp_remap_nodes(rio_gp_t* h, uint32_t m_new, const uint32_t* map, uint64_
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
     if (!map) return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: map is NULL");
-    if (row_sharded(h))
-        return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: not implemented on a handle of the row-sharded solve");
+    if (int rc = refuse_row_sharded(h, "rio_gp_remap_nodes")) return rc;
     const u32 m = h->m;
     if (m_new > m) return fail(h, RIO_GP_EINVAL, "rio_gp_remap_nodes: m_new exceeds the node count");
     std::vector<u32> from(m_new ? m_new : 1, kNone);  // new id -> old id

@@ -1,5 +1,5 @@
 """The compiler's own resource report of the kernels whose registers and scratch the design depends on, without a GPU
-(placement_kernels.hip compiled once for the module).
+(placement_kernels.hip compiled once for all the resource modules: tests/kernel_resource_usage.py).
 
 The chained scan of quiet ticks (k_scan<..., CHAIN>) waits, resident, for waves of the launch before it: that is free of deadlock
 only while TWO of its 1 024-thread workgroups fit a CU — 8 waves per SIMD, i.e. at most 64 vector registers and at most 80
@@ -9,34 +9,17 @@ whole quiet tick (the kept-load adds into `used` and the verdict rows are part o
 The committed tick's in-place scan (k_inc_scan) has one form, two tiles per wave-iteration, and spills nothing either.
 The change feed's kernels (k_chg_count, k_chg_scan, k_chg_list): the two passes stream two columns with dwordx4 loads and keep
 them in registers, the scan holds eight sums per thread; none may spill to scratch, all keep full occupancy."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kernel_resource_usage
 
 
 @pytest.fixture(scope="module")
-def recs(tmp_path_factory):
+def recs():
     """kernel (mangled name) -> {remark: value} from -Rpass-analysis=kernel-resource-usage"""
-    src = os.path.join(ROOT, "rio-rs_amd", "csrc", "placement_kernels.hip")
-    out = tmp_path_factory.mktemp("kres") / "pk.o"
-    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-c", src,
-                        "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(out)],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    recs, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = recs.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return recs
+    return kernel_resource_usage.records()
 
 
 def test_every_chained_scan_fits_twice_on_a_cu(recs):

@@ -4,34 +4,17 @@ resource remarks: no GPU needed.
 The merge and the fold stream one quad per lane and column with dwordx4 loads and do their arithmetic in 64 bits: they must spill
 nothing to scratch and stay within 64 vector registers, so that the 256-thread workgroups fill every SIMD's eight wave slots.
 The scatter is an atomic add with a fix-up: no scratch either."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kernel_resource_usage
 
 
 @pytest.fixture(scope="module")
-def recs(tmp_path_factory):
+def recs():
     """kernel (mangled name) -> {remark: value} from -Rpass-analysis=kernel-resource-usage"""
-    src = os.path.join(ROOT, "rio-rs_amd", "csrc", "placement_kernels.hip")
-    out = tmp_path_factory.mktemp("kres") / "pk.o"
-    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-c", src,
-                        "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(out)],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    recs, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = recs.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return recs
+    return kernel_resource_usage.records()
 
 
 def test_the_fold_and_merge_passes_use_no_scratch_and_at_most_64_registers(recs):

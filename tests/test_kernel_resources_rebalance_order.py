@@ -6,34 +6,17 @@ The streaming passes read one quad per lane and column with dwordx4 loads and mu
 node maps and thresholds live in DYNAMIC LDS sized by the launch, so the static LDS the compiler reports
 is only what the design states: nothing for the histogram passes and k_shed_tile, the 16 wave partials of the block scan (128 B)
 plus a few words for k_shed_sel_pick, k_shed_cut and k_shed_pack, two counters for k_shed_count."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kernel_resource_usage
 
 
 @pytest.fixture(scope="module")
-def recs(tmp_path_factory):
+def recs():
     """kernel (mangled name) -> {remark: value} from -Rpass-analysis=kernel-resource-usage"""
-    src = os.path.join(ROOT, "rio-rs_amd", "csrc", "placement_kernels.hip")
-    out = tmp_path_factory.mktemp("kres") / "pk.o"
-    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-c", src,
-                        "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(out)],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    recs, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = recs.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return recs
+    return kernel_resource_usage.records()
 
 
 def _pick(recs, pattern, count):
