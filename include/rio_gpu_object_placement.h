@@ -134,7 +134,8 @@ int rio_op_get_or_create_placement_batch(rio_op_t* p, uint64_t n, const char* co
 
 /* Durable twin of the table: every placed entry as (struct_name, object_id, server_address) —
  * the columns of the reference's object_placement table (migrations/0001-sqlite-init.sql:1-9; written by
- * sqlite.rs:68-85).  The arrays belong to the handle and stay valid until its next call.  Loading a snapshot is
+ * sqlite.rs:68-85).  The arrays are owned by the calling thread until its next call of this function (the addresses point
+ * into the node table: those strings stay until rio_op_release, as rio_op_node_address's do).  Loading a snapshot is
  * rio_op_update_batch.  rio-rs_amd/snapshot.py moves them to and from a SQLite file in that schema, so a GPU-backed
  * server can warm-start from, or write back to, the placement DB of a SqliteObjectPlacement deployment. */
 int rio_op_snapshot(rio_op_t* p, uint64_t* n_out, const char* const** struct_names, const char* const** object_ids,

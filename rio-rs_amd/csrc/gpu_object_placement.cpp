@@ -102,41 +102,9 @@ thread_local std::string t_err;
 // length of the address the calling thread's last rio_op_lookup / rio_op_get_or_create_placement produced
 // (rio_op_last_address_len): what a caller whose buffer was too small (RIO_GP_ERANGE) allocates before it asks again
 thread_local size_t t_addr_len = 0;
-// rio_op_snapshot's arrays: copies, owned by the calling thread until its next snapshot
-thread_local std::vector<std::string> t_snap_store;
-thread_local std::vector<const char*> t_snap_ty, t_snap_id, t_snap_addr;
-thread_local std::vector<size_t> t_snap_tylen, t_snap_idlen;
-
-// rio_op_objects_on_server's arrays, the same way
-thread_local std::vector<std::string> t_on_store;
-thread_local std::vector<const char*> t_on_ty, t_on_id;
-thread_local std::vector<size_t> t_on_tylen, t_on_idlen;
-thread_local std::vector<uint32_t> t_on_rows;
-
-// rio_op_rebalance's arrays, the same way (keys, then the two addresses, as copies)
-thread_local std::vector<std::string> t_rb_store;
-thread_local std::vector<const char*> t_rb_ty, t_rb_id, t_rb_from, t_rb_to;
-thread_local std::vector<size_t> t_rb_tylen, t_rb_idlen;
-thread_local std::vector<uint32_t> t_rb_rows, t_rb_src, t_rb_dst;
-
-// rio_op_changes' arrays, the same way (keys as copies; the addresses point into the node table, whose strings never change)
-thread_local std::vector<std::string> t_ch_store;
-thread_local std::vector<const char*> t_ch_ty, t_ch_id, t_ch_old, t_ch_new;
-thread_local std::vector<size_t> t_ch_tylen, t_ch_idlen;
-thread_local std::vector<uint32_t> t_ch_rows, t_ch_src, t_ch_dst;
-
-// rio_op_expire's arrays, the same way (keys as copies; the addresses point into the node table, whose strings never change)
-thread_local std::vector<std::string> t_ex_store;
-thread_local std::vector<const char*> t_ex_ty, t_ex_id, t_ex_addr;
-thread_local std::vector<size_t> t_ex_tylen, t_ex_idlen;
-thread_local std::vector<uint32_t> t_ex_rows, t_ex_node, t_ex_stamps;
-// rio_op_fold_loads' counters on their way to the device, and rio_op_get_object_load's copy of the load column
-thread_local std::vector<uint32_t> t_ld_hits, t_ld_col;
-// rio_op_hottest_objects' result: the strings stay valid until the calling thread's next call of that function
-thread_local std::vector<std::string> t_hot_store;
-thread_local std::vector<const char*> t_hot_ty, t_hot_id, t_hot_addr;
-thread_local std::vector<size_t> t_hot_tylen, t_hot_idlen;
-thread_local std::vector<uint32_t> t_hot_rows, t_hot_key, t_hot_node;
+// rio_op_expire's stamps and rio_op_fold_loads' counters on their way to the device, and rio_op_get_object_load's copy of the
+// load column
+thread_local std::vector<uint32_t> t_ex_stamps, t_ld_hits, t_ld_col;
 
 // One single-object call waiting for its device round trip (see run_combined).
 // One single-object call waiting for its device round trip (see run_combined).  The struct is a cache line of its own: its
@@ -519,6 +487,57 @@ int gp_fail(State* s, int rc) {  // only directly after the failing rio_gp_* cal
     const char* e = rio_gp_last_error(s->gp);
     t_err = e ? e : "";
     return rc;
+}
+
+// What a key-listing call hands out: entry k is (ty[k], tylen[k], id[k], idlen[k]) and up to two addresses.  The keys are
+// copies in `store` (two strings per entry): a key can be reclaimed as soon as the locks are released.  The addresses point into
+// the node table, whose strings stay until rio_op_release (NodeAddrs).  Every listing function has ONE instance per thread, so
+// its arrays are the calling thread's until its next call of that same function, whatever else the thread calls meanwhile.
+struct KeyListing {
+    std::vector<std::string> store;
+    std::vector<const char*> ty, id, a0, a1;
+    std::vector<size_t> tylen, idlen;
+    std::vector<uint32_t> rows, c1, c2;  // scratch the dense call fills: clear() leaves it, the next call sizes its first try from it
+    void clear() {
+        store.clear();
+        ty.clear(); id.clear(); a0.clear(); a1.clear(); tylen.clear(); idlen.clear();
+    }
+    void add(const std::pair<std::string, std::string>& key, const char* x0 = nullptr, const char* x1 = nullptr) {
+        store.push_back(key.first);
+        store.push_back(key.second);
+        a0.push_back(x0);
+        a1.push_back(x1);
+    }
+    // the key of a row the dense layer listed (imu held); false: the row has no key at the moment and is left out
+    bool add(const State* s, uint32_t row, const char* x0 = nullptr, const char* x1 = nullptr) {
+        if (row >= s->row_live.size() || !s->row_live[row]) return false;
+        add(s->row_key[row], x0, x1);
+        return true;
+    }
+    // After the locks are released, and only once `store` is complete (a string's bytes may move while it grows): the pointer
+    // and length arrays, and the caller's out-parameters (those it has).
+    void publish(uint64_t* n, const char* const** tys, const size_t** tyl, const char* const** ids, const size_t** idl,
+                 const char* const** x0 = nullptr, const char* const** x1 = nullptr) {
+        for (size_t k = 0; k + 1 < store.size(); k += 2) {
+            ty.push_back(store[k].c_str());
+            tylen.push_back(store[k].size());
+            id.push_back(store[k + 1].c_str());
+            idlen.push_back(store[k + 1].size());
+        }
+        *n = ty.size();
+        *tys = ty.data();
+        *ids = id.data();
+        if (tyl) *tyl = tylen.data();
+        if (idl) *idl = idlen.data();
+        if (x0) *x0 = a0.data();
+        if (x1) *x1 = a1.data();
+    }
+};
+thread_local KeyListing t_snap, t_on, t_rb, t_ch, t_ex, t_hot;
+
+// the address of a node id as the listings hand it out: into the node table, `none` for an id without an address
+const char* addr_of(const State* s, uint32_t nd, const char* none = nullptr) {
+    return nd < s->node_addr.size() ? s->node_addr[nd].c_str() : none;
 }
 
 // Bring the device's copy of the host tables up to date: the node table (any new address, liveness or capacity change)
@@ -1610,13 +1629,8 @@ int rio_op_get_or_create_placement_n(rio_op_t* p, const char* ty, size_t ty_len,
 
 int rio_op_snapshot_key_lengths(rio_op_t* p, const size_t** struct_name_lens, const size_t** object_id_lens) {
     if (!p || !struct_name_lens || !object_id_lens) return RIO_GP_EINVAL;
-    t_snap_tylen.clear(); t_snap_idlen.clear();
-    for (size_t k = 0; k + 2 < t_snap_store.size(); k += 3) {
-        t_snap_tylen.push_back(t_snap_store[k].size());
-        t_snap_idlen.push_back(t_snap_store[k + 1].size());
-    }
-    *struct_name_lens = t_snap_tylen.data();
-    *object_id_lens = t_snap_idlen.data();
+    *struct_name_lens = t_snap.tylen.data();
+    *object_id_lens = t_snap.idlen.data();
     return RIO_GP_OK;
 }
 
@@ -1624,8 +1638,7 @@ int rio_op_snapshot(rio_op_t* p, uint64_t* n_out, const char* const** struct_nam
                     const char* const** server_addresses) {
     if (!p || !n_out || !struct_names || !object_ids || !server_addresses) return RIO_GP_EINVAL;
     State* s = p->s;
-    t_snap_store.clear();
-    t_snap_ty.clear(); t_snap_id.clear(); t_snap_addr.clear();
+    t_snap.clear();
     {
         DevLock g(s);
         std::shared_lock<TableLock> gi(s->imu);
@@ -1634,24 +1647,10 @@ int rio_op_snapshot(rio_op_t* p, uint64_t* n_out, const char* const** struct_nam
         const uint64_t n = s->hi_rows;
         std::vector<uint32_t> assign(n ? n : 1);
         if ((rc = rio_gp_get_assign(s->gp, n, assign.data()))) return gp_fail(s, rc);
-        // copies: keys can be reclaimed and the tables can grow as soon as the locks are released
-        for (uint64_t row = 0; row < n; ++row) {
-            const uint32_t nd = assign[row];
-            if (!s->row_live[row] || nd == RIO_GP_NONE || nd >= s->node_addr.size()) continue;
-            t_snap_store.push_back(s->row_key[row].first);
-            t_snap_store.push_back(s->row_key[row].second);
-            t_snap_store.push_back(s->node_addr[nd]);
-        }
+        for (uint64_t row = 0; row < n; ++row)
+            if (const char* a = addr_of(s, assign[row])) t_snap.add(s, (uint32_t)row, a);  // (RIO_GP_NONE is no node id either)
     }
-    for (size_t k = 0; k + 2 < t_snap_store.size(); k += 3) {
-        t_snap_ty.push_back(t_snap_store[k].c_str());
-        t_snap_id.push_back(t_snap_store[k + 1].c_str());
-        t_snap_addr.push_back(t_snap_store[k + 2].c_str());
-    }
-    *n_out = t_snap_ty.size();
-    *struct_names = t_snap_ty.data();
-    *object_ids = t_snap_id.data();
-    *server_addresses = t_snap_addr.data();
+    t_snap.publish(n_out, struct_names, nullptr, object_ids, nullptr, server_addresses);  // (lengths: rio_op_snapshot_key_lengths)
     return RIO_GP_OK;
 }
 
@@ -1659,8 +1658,7 @@ int rio_op_objects_on_server(rio_op_t* p, const char* address, uint64_t* n_out, 
                              const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens) {
     if (!p || !address || !n_out || !struct_names || !struct_name_lens || !object_ids || !object_id_lens) return RIO_GP_EINVAL;
     State* s = p->s;
-    t_on_store.clear();
-    t_on_ty.clear(); t_on_id.clear(); t_on_tylen.clear(); t_on_idlen.clear();
+    t_on.clear();
     {
         DevLock g(s);
         std::shared_lock<TableLock> gi(s->imu);
@@ -1675,33 +1673,17 @@ int rio_op_objects_on_server(rio_op_t* p, const char* address, uint64_t* n_out, 
             uint64_t n = 0;
             // the thread's buffer from its last call first (an empty one: counts only); one more round with the exact size when
             // it is too small
-            rc = rio_gp_rows_on_nodes(s->gp, bitmap.data(), off.data(), t_on_rows.empty() ? nullptr : t_on_rows.data(),
-                                      t_on_rows.size(), &n);
-            if (rc == RIO_GP_ERANGE || (rc == RIO_GP_OK && n > t_on_rows.size())) {
-                t_on_rows.resize(n);
-                rc = rio_gp_rows_on_nodes(s->gp, bitmap.data(), off.data(), t_on_rows.data(), t_on_rows.size(), &n);
+            std::vector<uint32_t>& rows = t_on.rows;
+            rc = rio_gp_rows_on_nodes(s->gp, bitmap.data(), off.data(), rows.empty() ? nullptr : rows.data(), rows.size(), &n);
+            if (rc == RIO_GP_ERANGE || (rc == RIO_GP_OK && n > rows.size())) {
+                rows.resize(n);
+                rc = rio_gp_rows_on_nodes(s->gp, bitmap.data(), off.data(), rows.data(), rows.size(), &n);
             }
             if (rc) return gp_fail(s, rc);
-            // copies: keys can be reclaimed as soon as the locks are released
-            for (uint64_t k = 0; k < n; ++k) {
-                const uint32_t row = t_on_rows[k];
-                if (row >= s->row_live.size() || !s->row_live[row]) continue;
-                t_on_store.push_back(s->row_key[row].first);
-                t_on_store.push_back(s->row_key[row].second);
-            }
+            for (uint64_t k = 0; k < n; ++k) t_on.add(s, rows[k]);
         }
     }
-    for (size_t k = 0; k + 1 < t_on_store.size(); k += 2) {
-        t_on_ty.push_back(t_on_store[k].data());
-        t_on_tylen.push_back(t_on_store[k].size());
-        t_on_id.push_back(t_on_store[k + 1].data());
-        t_on_idlen.push_back(t_on_store[k + 1].size());
-    }
-    *n_out = t_on_ty.size();
-    *struct_names = t_on_ty.data();
-    *struct_name_lens = t_on_tylen.data();
-    *object_ids = t_on_id.data();
-    *object_id_lens = t_on_idlen.data();
+    t_on.publish(n_out, struct_names, struct_name_lens, object_ids, object_id_lens);
     return RIO_GP_OK;
 }
 
@@ -1720,8 +1702,7 @@ int rio_op_rebalance_ordered(rio_op_t* p, uint32_t order, uint64_t max_moves, ui
     if (order != RIO_GP_REBALANCE_ROW_ORDER && order != RIO_GP_REBALANCE_BY_LOAD)
         return fail(RIO_GP_EINVAL, "rio_op_rebalance_ordered: unknown order");
     State* s = p->s;
-    t_rb_store.clear();
-    t_rb_ty.clear(); t_rb_id.clear(); t_rb_from.clear(); t_rb_to.clear(); t_rb_tylen.clear(); t_rb_idlen.clear();
+    t_rb.clear();
     {
         DevLock g(s);
         std::lock_guard<TableLock> gi(s->imu);  // the write side: no lookup is answered while keys change their address
@@ -1730,40 +1711,19 @@ int rio_op_rebalance_ordered(rio_op_t* p, uint32_t order, uint64_t max_moves, ui
         if (!rio_gp_rebalance) return fail(RIO_GP_EUPSTREAM, "dense layer has no rebalance");
         // a move is a row that is handed out: at most as many as rows were ever interned
         const uint64_t cap = std::min<uint64_t>(max_moves, s->row_key.size());
-        t_rb_rows.resize(cap ? cap : 1); t_rb_src.resize(cap ? cap : 1); t_rb_dst.resize(cap ? cap : 1);
+        std::vector<uint32_t> &rows = t_rb.rows, &src = t_rb.c1, &dst = t_rb.c2;
+        rows.resize(cap ? cap : 1); src.resize(cap ? cap : 1); dst.resize(cap ? cap : 1);
         rio_gp_rebalance_cfg cfg{};
         cfg.struct_size = sizeof cfg;
         cfg.max_moves = cap;  // targets: the capacities of rio_op_set_member
         cfg.order = order;
         uint64_t n = 0;
-        rc = rio_gp_rebalance(s->gp, &cfg, nullptr, t_rb_rows.data(), t_rb_src.data(), t_rb_dst.data(), cap, &n);
+        rc = rio_gp_rebalance(s->gp, &cfg, nullptr, rows.data(), src.data(), dst.data(), cap, &n);
         s->shadow.invalidate_all();  // moved rows must not be answered from their old address (also when the call failed)
         if (rc) return gp_fail(s, rc);
-        // copies: keys can be reclaimed as soon as the locks are released
-        for (uint64_t k = 0; k < n; ++k) {
-            const uint32_t row = t_rb_rows[k];
-            if (row >= s->row_live.size() || !s->row_live[row]) continue;
-            t_rb_store.push_back(s->row_key[row].first);
-            t_rb_store.push_back(s->row_key[row].second);
-            t_rb_store.push_back(t_rb_src[k] < s->node_addr.size() ? s->node_addr[t_rb_src[k]] : std::string());
-            t_rb_store.push_back(t_rb_dst[k] < s->node_addr.size() ? s->node_addr[t_rb_dst[k]] : std::string());
-        }
+        for (uint64_t k = 0; k < n; ++k) t_rb.add(s, rows[k], addr_of(s, src[k], ""), addr_of(s, dst[k], ""));
     }
-    for (size_t k = 0; k + 3 < t_rb_store.size(); k += 4) {
-        t_rb_ty.push_back(t_rb_store[k].data());
-        t_rb_tylen.push_back(t_rb_store[k].size());
-        t_rb_id.push_back(t_rb_store[k + 1].data());
-        t_rb_idlen.push_back(t_rb_store[k + 1].size());
-        t_rb_from.push_back(t_rb_store[k + 2].c_str());
-        t_rb_to.push_back(t_rb_store[k + 3].c_str());
-    }
-    *n_out = t_rb_ty.size();
-    *struct_names = t_rb_ty.data();
-    *struct_name_lens = t_rb_tylen.data();
-    *object_ids = t_rb_id.data();
-    *object_id_lens = t_rb_idlen.data();
-    *from_addresses = t_rb_from.data();
-    *to_addresses = t_rb_to.data();
+    t_rb.publish(n_out, struct_names, struct_name_lens, object_ids, object_id_lens, from_addresses, to_addresses);
     return RIO_GP_OK;
 }
 
@@ -1778,8 +1738,7 @@ int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64
                   const size_t** object_id_lens, const char* const** addresses) {
     if (!p || !n_out || !struct_names || !struct_name_lens || !object_ids || !object_id_lens || !addresses) return RIO_GP_EINVAL;
     State* s = p->s;
-    t_ex_store.clear();
-    t_ex_ty.clear(); t_ex_id.clear(); t_ex_addr.clear(); t_ex_tylen.clear(); t_ex_idlen.clear();
+    t_ex.clear();
     *n_out = 0;
     if (n_idle) *n_idle = 0;
     {
@@ -1798,38 +1757,22 @@ int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64
             if ((rc = rio_gp_expire(s->gp, cutoff, nullptr, nullptr, 0, &idle, nullptr))) return gp_fail(s, rc);
             if (n_idle) *n_idle = idle;
         } else {
-            t_ex_rows.resize(cap); t_ex_node.resize(cap);
-            if ((rc = rio_gp_expire(s->gp, cutoff, t_ex_rows.data(), t_ex_node.data(), cap, &idle, nullptr))) {
+            std::vector<uint32_t> &rows = t_ex.rows, &node = t_ex.c1;
+            rows.resize(cap); node.resize(cap);
+            if ((rc = rio_gp_expire(s->gp, cutoff, rows.data(), node.data(), cap, &idle, nullptr))) {
                 s->shadow.invalidate_all();  // (nobody can tell which rows it un-placed before it failed)
                 return gp_fail(s, rc);
             }
             if (n_idle) *n_idle = idle;
             const uint64_t got = std::min(idle, cap);
-            const uint32_t m = (uint32_t)s->node_addr.size();
             // the shadow follows precisely: exactly the listed rows are un-placed; every other row's entry stands
             for (uint64_t k = 0; k < got; ++k) {
-                const uint32_t row = t_ex_rows[k];
-                s->shadow.put(row, RIO_GP_NONE);
-                if (row >= s->row_live.size() || !s->row_live[row]) continue;
-                // copies: keys can be reclaimed as soon as the locks are released
-                t_ex_store.push_back(s->row_key[row].first);
-                t_ex_store.push_back(s->row_key[row].second);
-                t_ex_addr.push_back(t_ex_node[k] < m ? s->node_addr[t_ex_node[k]].c_str() : nullptr);
+                s->shadow.put(rows[k], RIO_GP_NONE);
+                t_ex.add(s, rows[k], addr_of(s, node[k]));
             }
         }
     }
-    for (size_t k = 0; k + 1 < t_ex_store.size(); k += 2) {
-        t_ex_ty.push_back(t_ex_store[k].data());
-        t_ex_tylen.push_back(t_ex_store[k].size());
-        t_ex_id.push_back(t_ex_store[k + 1].data());
-        t_ex_idlen.push_back(t_ex_store[k + 1].size());
-    }
-    *n_out = t_ex_ty.size();
-    *struct_names = t_ex_ty.data();
-    *struct_name_lens = t_ex_tylen.data();
-    *object_ids = t_ex_id.data();
-    *object_id_lens = t_ex_idlen.data();
-    *addresses = t_ex_addr.data();
+    t_ex.publish(n_out, struct_names, struct_name_lens, object_ids, object_id_lens, addresses);
     return RIO_GP_OK;
 }
 
@@ -1903,8 +1846,7 @@ int rio_op_hottest_objects(rio_op_t* p, const char* address, uint32_t min_load, 
     if (!p || !n_out || !struct_names || !struct_name_lens || !object_ids || !object_id_lens || !addresses) return RIO_GP_EINVAL;
     if (max_objects_out && !loads) return RIO_GP_EINVAL;
     State* s = p->s;
-    t_hot_store.clear();
-    t_hot_ty.clear(); t_hot_id.clear(); t_hot_addr.clear(); t_hot_tylen.clear(); t_hot_idlen.clear();
+    t_hot.clear();
     *n_out = 0;
     if (n_candidates) *n_candidates = 0;
     if (max_objects_out > RIO_GP_TOP_MAX) return fail(RIO_GP_EINVAL, "rio_op_hottest_objects: max_objects_out above RIO_GP_TOP_MAX");
@@ -1931,42 +1873,23 @@ int rio_op_hottest_objects(rio_op_t* p, const char* address, uint32_t min_load, 
         if (known) {
             const uint64_t cap = max_objects_out;
             uint64_t cand = 0;
+            std::vector<uint32_t> &rows = t_hot.rows, &key = t_hot.c1, &on = t_hot.c2;
             if (!cap) {
                 rc = rio_gp_top_rows(s->gp, flags, node, min_load, nullptr, nullptr, nullptr, 0, &cand, nullptr);
             } else {
-                t_hot_rows.resize(cap); t_hot_key.resize(cap); t_hot_node.resize(cap);
-                rc = rio_gp_top_rows(s->gp, flags, node, min_load, t_hot_rows.data(), t_hot_key.data(), t_hot_node.data(), cap, &cand,
-                                     nullptr);
+                rows.resize(cap); key.resize(cap); on.resize(cap);
+                rc = rio_gp_top_rows(s->gp, flags, node, min_load, rows.data(), key.data(), on.data(), cap, &cand, nullptr);
             }
             if (rc) return gp_fail(s, rc);
             if (n_candidates) *n_candidates = cand;
             const uint64_t got = std::min(cand, cap);
-            const uint32_t m = (uint32_t)s->node_addr.size();
-            for (uint64_t k = 0; k < got; ++k) {
-                const uint32_t row = t_hot_rows[k];
-                // (a placed row has a key: rows on the free list are un-placed.  Were one ever not to, it is left out of the
-                //  listing, which then falls short of min(*n_candidates, max_objects_out).)
-                if (row >= s->row_live.size() || !s->row_live[row]) continue;
-                // copies: keys can be reclaimed as soon as the locks are released
-                t_hot_store.push_back(s->row_key[row].first);
-                t_hot_store.push_back(s->row_key[row].second);
-                t_hot_addr.push_back(t_hot_node[k] < m ? s->node_addr[t_hot_node[k]].c_str() : nullptr);
-                loads[listed++] = t_hot_key[k];
-            }
+            // (a placed row has a key: rows on the free list are un-placed.  Were one ever not to, it is left out of the
+            //  listing, which then falls short of min(*n_candidates, max_objects_out).)
+            for (uint64_t k = 0; k < got; ++k)
+                if (t_hot.add(s, rows[k], addr_of(s, on[k]))) loads[listed++] = key[k];
         }
     }
-    for (size_t k = 0; k + 1 < t_hot_store.size(); k += 2) {
-        t_hot_ty.push_back(t_hot_store[k].data());
-        t_hot_tylen.push_back(t_hot_store[k].size());
-        t_hot_id.push_back(t_hot_store[k + 1].data());
-        t_hot_idlen.push_back(t_hot_store[k + 1].size());
-    }
-    *n_out = listed;
-    *struct_names = t_hot_ty.data();
-    *struct_name_lens = t_hot_tylen.data();
-    *object_ids = t_hot_id.data();
-    *object_id_lens = t_hot_idlen.data();
-    *addresses = t_hot_addr.data();
+    t_hot.publish(n_out, struct_names, struct_name_lens, object_ids, object_id_lens, addresses);  // (*n_out == listed)
     return RIO_GP_OK;
 }
 
@@ -1977,10 +1900,7 @@ int rio_op_changes(rio_op_t* p, uint64_t* n_out, int* full, const char* const** 
         !new_addresses)
         return RIO_GP_EINVAL;
     State* s = p->s;
-    t_ch_store.clear();
-    t_ch_ty.clear(); t_ch_id.clear(); t_ch_old.clear(); t_ch_new.clear(); t_ch_tylen.clear(); t_ch_idlen.clear();
-    std::vector<const char*> del_old, up_old, up_new;  // addresses of the deletes / upserts (their keys: t_ch_store, deletes first)
-    std::vector<std::string> up_keys;
+    t_ch.clear();
     {
         // mu keeps every device change (and reclaim()) out until the listing is matched with its keys; the shared table lock keeps
         // the keys and the node table as they are
@@ -1998,14 +1918,15 @@ int rio_op_changes(rio_op_t* p, uint64_t* n_out, int* full, const char* const** 
             return gp_fail(s, code);
         };
         // every change, consumed: into the thread's buffers from its last call first, the rest (a second page) with the exact size
+        std::vector<uint32_t> &rows = t_ch.rows, &src = t_ch.c1, &dst = t_ch.c2;
         uint64_t total = 0, rest = 0;
-        uint64_t cap = std::max<uint64_t>(t_ch_rows.size(), 4096);
-        t_ch_rows.resize(cap); t_ch_src.resize(cap); t_ch_dst.resize(cap);
-        if ((rc = rio_gp_changes(s->gp, 0, t_ch_rows.data(), t_ch_src.data(), t_ch_dst.data(), cap, &total))) return lost(rc);
+        uint64_t cap = std::max<uint64_t>(rows.size(), 4096);
+        rows.resize(cap); src.resize(cap); dst.resize(cap);
+        if ((rc = rio_gp_changes(s->gp, 0, rows.data(), src.data(), dst.data(), cap, &total))) return lost(rc);
         uint64_t got = std::min(total, cap);
         if (total > got) {
-            t_ch_rows.resize(total); t_ch_src.resize(total); t_ch_dst.resize(total);
-            if ((rc = rio_gp_changes(s->gp, 0, t_ch_rows.data() + got, t_ch_src.data() + got, t_ch_dst.data() + got, total - got, &rest)))
+            rows.resize(total); src.resize(total); dst.resize(total);
+            if ((rc = rio_gp_changes(s->gp, 0, rows.data() + got, src.data() + got, dst.data() + got, total - got, &rest)))
                 return lost(rc);
             got += std::min(rest, total - got);
         }
@@ -2016,65 +1937,41 @@ int rio_op_changes(rio_op_t* p, uint64_t* n_out, int* full, const char* const** 
         {
             std::vector<uint32_t> miss;
             for (uint32_t r : rr)
-                if (!std::binary_search(t_ch_rows.begin(), t_ch_rows.begin() + got, r)) miss.push_back(r);
+                if (!std::binary_search(rows.begin(), rows.begin() + got, r)) miss.push_back(r);
             rr_node.assign(miss.size(), RIO_GP_NONE);
             if (!miss.empty() && (rc = rio_gp_lookup_batch(s->gp, miss.size(), miss.data(), rr_node.data()))) return lost(rc);
             rr.swap(miss);
         }
-        const uint32_t m = (uint32_t)s->node_addr.size();
-        auto addr = [&](uint32_t nd) -> const char* { return nd < m ? s->node_addr[nd].c_str() : nullptr; };
-        // one row: a retired row deletes the mirror's key and upserts its new key; any other row upserts or deletes its key
-        auto row = [&](uint32_t r, uint32_t from, uint32_t to) {
-            const char* a0 = addr(from);
-            const char* a1 = addr(to);
+        // one row: a retired row deletes the mirror's key and upserts its new key; any other row upserts or deletes its key.
+        // The listing takes the deletes in one pass over the rows and the upserts in a second one (ups).
+        auto row = [&](uint32_t r, uint32_t from, uint32_t to, bool ups) {
+            const char* a0 = addr_of(s, from);
+            const char* a1 = addr_of(s, to);
             // (RIO_GP_NODE_GONE: the mirror holds the key on an address that has been removed — placed, address no longer known)
             const bool was = a0 || from == RIO_GP_NODE_GONE;
             const auto it = s->retired.find(r);
             if (it != s->retired.end()) {
-                if (was) { t_ch_store.push_back(it->second.first); t_ch_store.push_back(it->second.second); del_old.push_back(a0); }
-                if (a1 && s->row_live[r]) {
-                    up_keys.push_back(s->row_key[r].first); up_keys.push_back(s->row_key[r].second);
-                    up_old.push_back(nullptr); up_new.push_back(a1);
-                }
+                if (!ups && was) t_ch.add(it->second, a0);
+                if (ups && a1) t_ch.add(s, r, nullptr, a1);
                 return;
             }
-            if (r >= s->row_live.size() || !s->row_live[r]) return;  // (a free row that was never the mirror's: unplaced on both sides)
-            if (a1) {
-                up_keys.push_back(s->row_key[r].first); up_keys.push_back(s->row_key[r].second);
-                up_old.push_back(a0); up_new.push_back(a1);
-            } else if (was) {
-                t_ch_store.push_back(s->row_key[r].first); t_ch_store.push_back(s->row_key[r].second); del_old.push_back(a0);
-            }
+            // (a row without a key here is a free row that was never the mirror's: unplaced on both sides)
+            if (ups ? a1 != nullptr : (!a1 && was)) t_ch.add(s, r, a0, a1);
         };
-        // both lists in row order
-        size_t k = 0;
-        for (uint64_t i = 0; i < got; ++i) {
-            for (; k < rr.size() && rr[k] < t_ch_rows[i]; ++k) row(rr[k], rr_node[k], rr_node[k]);
-            row(t_ch_rows[i], t_ch_src[i], t_ch_dst[i]);
+        // deletes first, then upserts, both in row order
+        for (int ups = 0; ups < 2; ++ups) {
+            size_t k = 0;
+            for (uint64_t i = 0; i < got; ++i) {
+                for (; k < rr.size() && rr[k] < rows[i]; ++k) row(rr[k], rr_node[k], rr_node[k], ups);
+                row(rows[i], src[i], dst[i], ups);
+            }
+            for (; k < rr.size(); ++k) row(rr[k], rr_node[k], rr_node[k], ups);
         }
-        for (; k < rr.size(); ++k) row(rr[k], rr_node[k], rr_node[k]);
         s->retired.clear();
         *full = s->feed_full ? 1 : 0;
         s->feed_full = false;
     }
-    // deletes first, then upserts
-    const size_t nd = del_old.size();
-    for (std::string& key : up_keys) t_ch_store.push_back(std::move(key));
-    for (size_t k = 0; k + 1 < t_ch_store.size(); k += 2) {
-        t_ch_ty.push_back(t_ch_store[k].data());
-        t_ch_tylen.push_back(t_ch_store[k].size());
-        t_ch_id.push_back(t_ch_store[k + 1].data());
-        t_ch_idlen.push_back(t_ch_store[k + 1].size());
-    }
-    for (size_t k = 0; k < nd; ++k) { t_ch_old.push_back(del_old[k]); t_ch_new.push_back(nullptr); }
-    for (size_t k = 0; k < up_new.size(); ++k) { t_ch_old.push_back(up_old[k]); t_ch_new.push_back(up_new[k]); }
-    *n_out = t_ch_ty.size();
-    *struct_names = t_ch_ty.data();
-    *struct_name_lens = t_ch_tylen.data();
-    *object_ids = t_ch_id.data();
-    *object_id_lens = t_ch_idlen.data();
-    *old_addresses = t_ch_old.data();
-    *new_addresses = t_ch_new.data();
+    t_ch.publish(n_out, struct_names, struct_name_lens, object_ids, object_id_lens, old_addresses, new_addresses);
     return RIO_GP_OK;
 }
 

@@ -964,51 +964,57 @@ def _oplib():
     return L
 
 
+_pp, _psz = C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_size_t))
+
+
+def _listing_out(k):
+    """The out-parameters of a key-listing call with k address columns: (n, struct_names, struct_name_lens, object_ids,
+    object_id_lens, k address arrays), to be passed by reference."""
+    return (C.c_uint64(0), C.POINTER(C.c_char_p)(), C.POINTER(C.c_size_t)(), C.POINTER(C.c_char_p)(), C.POINTER(C.c_size_t)()) + \
+        tuple(C.POINTER(C.c_char_p)() for _ in range(k))
+
+
+def _listing(out):
+    """What a successful call left in _listing_out's parameters: [(struct_name, object_id, k addresses)].  Key parts are read
+    with their lengths (c_char_p would stop at a NUL byte); an address is None where the library gave NULL."""
+    n, ty, tl, oid, il = out[:5]
+    tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
+    cols = out[5:]
+    return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode()) +
+            tuple(None if c[k] is None else c[k].decode() for c in cols) for k in range(n.value)]
+
+
 def bind_op_changes(L):
     """argtypes of rio_op_changes / rio_op_changes_reset on a library that has them (the product, or a stub-linked test build)."""
-    pp, psz = C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_size_t))
-    L.rio_op_changes.argtypes = [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), pp, psz, pp, psz, pp, pp]
+    L.rio_op_changes.argtypes = [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), _pp, _psz, _pp, _psz, _pp, _pp]
     L.rio_op_changes_reset.argtypes = [_vp]
 
 
 def op_changes(L, h):
     """One rio_op_changes call on handle h of library L: (rc, full, [(struct_name, object_id, old_address, new_address)]) —
     addresses None where the key was / is not placed; deletes first."""
-    n, full = C.c_uint64(0), C.c_int(0)
-    ty, oid, oa, na = (C.POINTER(C.c_char_p)() for _ in range(4))
-    tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
-    rc = L.rio_op_changes(h, C.byref(n), C.byref(full), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il), C.byref(oa),
-                          C.byref(na))
+    o, full = _listing_out(2), C.c_int(0)
+    rc = L.rio_op_changes(h, C.byref(o[0]), C.byref(full), *map(C.byref, o[1:]))
     if rc != OK:
         return rc, False, []
-    tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))   # (c_char_p would stop at a NUL)
-    out = [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(),
-            None if oa[k] is None else oa[k].decode(), None if na[k] is None else na[k].decode()) for k in range(n.value)]
-    return rc, bool(full.value), out
+    return rc, bool(full.value), _listing(o)
 
 
 def bind_op_expire(L):
     """argtypes of rio_op_set_clock / rio_op_expire on a library that has them (the product, or a stub-linked test build)."""
-    pp, psz = C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_size_t))
     L.rio_op_set_clock.argtypes = [_vp, C.c_uint32]
-    L.rio_op_expire.argtypes = [_vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), pp, psz, pp, psz, pp]
+    L.rio_op_expire.argtypes = [_vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _pp, _psz, _pp, _psz, _pp]
 
 
 def op_expire(L, h, cutoff, max_objects=None):
     """One rio_op_expire call on handle h of library L: (rc, [(struct_name, object_id, address)], n_idle) — the keys un-placed,
     in row order, with the address each was on (None: a node id without an address).  max_objects None: no limit; 0: count."""
-    n, idle = C.c_uint64(0), C.c_uint64(0)
-    ty, oid, ad = (C.POINTER(C.c_char_p)() for _ in range(3))
-    tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+    o, idle = _listing_out(1), C.c_uint64(0)
     cap = 0xFFFFFFFFFFFFFFFF if max_objects is None else int(max_objects)
-    rc = L.rio_op_expire(h, int(cutoff), cap, C.byref(n), C.byref(idle), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il),
-                         C.byref(ad))
+    rc = L.rio_op_expire(h, int(cutoff), cap, C.byref(o[0]), C.byref(idle), *map(C.byref, o[1:]))
     if rc != OK:
         return rc, [], 0
-    tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))   # (c_char_p would stop at a NUL)
-    out = [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(),
-            None if ad[k] is None else ad[k].decode()) for k in range(n.value)]
-    return rc, out, int(idle.value)
+    return rc, _listing(o), int(idle.value)
 
 
 def bind_op_loads(L):
@@ -1039,27 +1045,21 @@ def op_get_object_load(L, h, struct_name, object_id):
 
 def bind_op_top(L):
     """argtypes of rio_op_hottest_objects on a library that has it (the product, or a stub-linked test build)."""
-    pp, psz = C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_size_t))
     L.rio_op_hottest_objects.argtypes = [_vp, C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                                         pp, psz, pp, psz, pp, _vp]
+                                         _pp, _psz, _pp, _psz, _pp, _vp]
 
 
 def op_hottest_objects(L, h, address=None, min_load=0, max_objects=TOP_MAX):
     """One rio_op_hottest_objects call on handle h of library L: (rc, [(struct_name, object_id, address, load)], n_candidates)
     — the placed keys with the largest loads (on `address`; None: on every server), load descending.  max_objects 0: count."""
-    n, cand = C.c_uint64(0), C.c_uint64(0)
-    ty, oid, ad = (C.POINTER(C.c_char_p)() for _ in range(3))
-    tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+    o, cand = _listing_out(1), C.c_uint64(0)
     cap = int(max_objects)
     loads = (C.c_uint32 * max(min(cap, TOP_MAX), 1))()
-    rc = L.rio_op_hottest_objects(h, None if address is None else address.encode(), int(min_load), cap, C.byref(n),
-                                  C.byref(cand), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il), C.byref(ad), loads)
+    rc = L.rio_op_hottest_objects(h, None if address is None else address.encode(), int(min_load), cap, C.byref(o[0]),
+                                  C.byref(cand), *map(C.byref, o[1:]), loads)
     if rc != OK:
         return rc, [], 0
-    tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))   # (c_char_p would stop at a NUL)
-    out = [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(),
-            None if ad[k] is None else ad[k].decode(), int(loads[k])) for k in range(n.value)]
-    return rc, out, int(cand.value)
+    return rc, [e + (int(loads[k]),) for k, e in enumerate(_listing(o))], int(cand.value)
 
 
 def _cstrs(items):
@@ -1249,31 +1249,23 @@ class GpuObjectPlacement:
 
     def snapshot(self):
         """Every placed entry as (struct_name, object_id, server_address) — the reference's table columns."""
-        n = C.c_uint64(0)
-        ty, oid, addr = C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)()
-        self._chk(_oplib().rio_op_snapshot(self._h, C.byref(n), C.byref(ty), C.byref(oid), C.byref(addr)))
-        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
-        self._chk(_oplib().rio_op_snapshot_key_lengths(self._h, C.byref(tl), C.byref(il)))
-        tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))   # (c_char_p would stop at a NUL)
-        return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), addr[k].decode())
-                for k in range(n.value)]
+        o = _listing_out(1)
+        n, ty, tl, oid, il, addr = map(C.byref, o)
+        self._chk(_oplib().rio_op_snapshot(self._h, n, ty, oid, addr))
+        self._chk(_oplib().rio_op_snapshot_key_lengths(self._h, tl, il))
+        return _listing(o)
 
     def rebalance(self, max_moves=None, order=REBALANCE_ROW_ORDER):
         """rio_op_rebalance / rio_op_rebalance_ordered: [(struct_name, object_id, from_address, to_address)] of the objects
         moved off servers over their member capacity (max_moves None: no limit), in the dense layer's row order.  order =
         REBALANCE_BY_LOAD: every such server sheds its heaviest objects first (after fold_loads: the fewest moves)."""
-        n = C.c_uint64(0)
-        ty, oid, fa, ta = (C.POINTER(C.c_char_p)() for _ in range(4))
-        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
+        o = _listing_out(2)
         B = CAP_INF if max_moves is None else int(max_moves)
-        out = (C.byref(n), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il), C.byref(fa), C.byref(ta))
         if order == REBALANCE_ROW_ORDER:
-            self._chk(_oplib().rio_op_rebalance(self._h, B, *out))
+            self._chk(_oplib().rio_op_rebalance(self._h, B, *map(C.byref, o)))
         else:
-            self._chk(_oplib().rio_op_rebalance_ordered(self._h, int(order), B, *out))
-        tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
-        return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), fa[k].decode(), ta[k].decode())
-                for k in range(n.value)]
+            self._chk(_oplib().rio_op_rebalance_ordered(self._h, int(order), B, *map(C.byref, o)))
+        return _listing(o)
 
     def changes(self):
         """rio_op_changes: (full, [(struct_name, object_id, old_address, new_address)]) — every placement change since the last
@@ -1325,10 +1317,6 @@ class GpuObjectPlacement:
     def objects_on_server(self, address):
         """rio_op_objects_on_server: every (struct_name, object_id) placed on `address` (the reverse index; [] for an address
         never seen), key lengths read as snapshot() does."""
-        n = C.c_uint64(0)
-        ty, oid = C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)()
-        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
-        self._chk(_oplib().rio_op_objects_on_server(self._h, address.encode(), C.byref(n), C.byref(ty), C.byref(tl), C.byref(oid),
-                                                    C.byref(il)))
-        tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
-        return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode()) for k in range(n.value)]
+        o = _listing_out(0)
+        self._chk(_oplib().rio_op_objects_on_server(self._h, address.encode(), *map(C.byref, o)))
+        return _listing(o)

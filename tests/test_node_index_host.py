@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 import node_index_driver as drv
+import rio_gp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = 0xFFFFFFFFFFFFFFFF
@@ -74,22 +75,16 @@ class StubOp:
         return buf.value.decode() or None, flag.value
 
     def snapshot(self):
-        n = C.c_uint64(0)
-        ty, oid, addr = C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)()
-        assert self.L.rio_op_snapshot(self.h, C.byref(n), C.byref(ty), C.byref(oid), C.byref(addr)) == 0
-        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
-        assert self.L.rio_op_snapshot_key_lengths(self.h, C.byref(tl), C.byref(il)) == 0
-        tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
-        return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), addr[k].decode()) for k in range(n.value)]
+        o = rio_gp._listing_out(1)
+        n, ty, tl, oid, il, addr = map(C.byref, o)
+        assert self.L.rio_op_snapshot(self.h, n, ty, oid, addr) == 0
+        assert self.L.rio_op_snapshot_key_lengths(self.h, tl, il) == 0
+        return rio_gp._listing(o)
 
     def objects_on_server(self, addr):
-        n = C.c_uint64(0)
-        ty, oid = C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)()
-        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
-        assert self.L.rio_op_objects_on_server(self.h, addr.encode(), C.byref(n), C.byref(ty), C.byref(tl), C.byref(oid),
-                                               C.byref(il)) == 0
-        tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
-        return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode()) for k in range(n.value)]
+        o = rio_gp._listing_out(0)
+        assert self.L.rio_op_objects_on_server(self.h, addr.encode(), *map(C.byref, o)) == 0
+        return rio_gp._listing(o)
 
 
 @pytest.mark.parametrize("shadow", [True, False])

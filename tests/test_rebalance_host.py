@@ -8,6 +8,7 @@ import threading
 
 import pytest
 
+import rio_gp
 import spec_rebalance
 from test_node_index_host import StubOp
 
@@ -52,14 +53,9 @@ class RbOp(StubOp):
         return buf.value.decode() if found.value else None
 
     def rebalance(self, max_moves=INF):
-        n = C.c_uint64(0)
-        ty, oid, fa, ta = (C.POINTER(C.c_char_p)() for _ in range(4))
-        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
-        assert self.L.rio_op_rebalance(self.h, max_moves, C.byref(n), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il),
-                                       C.byref(fa), C.byref(ta)) == 0
-        tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
-        return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), fa[k].decode(), ta[k].decode())
-                for k in range(n.value)]
+        o = rio_gp._listing_out(2)
+        assert self.L.rio_op_rebalance(self.h, max_moves, *map(C.byref, o)) == 0
+        return rio_gp._listing(o)
 
 
 def _fill(op, addrs, keys, rng_pick):

@@ -58,18 +58,14 @@ class OrdOp(StubOp):
         return buf.value.decode() if found.value else None
 
     def rebalance(self, order=None, max_moves=INF, expect=0):
-        n = C.c_uint64(0)
-        ty, oid, fa, ta = (C.POINTER(C.c_char_p)() for _ in range(4))
-        tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
-        outs = (C.byref(n), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il), C.byref(fa), C.byref(ta))
+        o = rio_gp._listing_out(2)
+        outs = tuple(map(C.byref, o))
         rc = (self.L.rio_op_rebalance(self.h, max_moves, *outs) if order is None
               else self.L.rio_op_rebalance_ordered(self.h, order, max_moves, *outs))
         assert rc == expect
         if rc:
             return None
-        tyv, idv = C.cast(ty, C.POINTER(C.c_void_p)), C.cast(oid, C.POINTER(C.c_void_p))
-        return [(C.string_at(tyv[k], tl[k]).decode(), C.string_at(idv[k], il[k]).decode(), fa[k].decode(), ta[k].decode())
-                for k in range(n.value)]
+        return rio_gp._listing(o)
 
 
 def _setup(op, seed):
