@@ -1,5 +1,7 @@
 """A CPU stand-in for the rio_gp binding, FOR TESTS ONLY: the surface tests/test_gpu_fuzz.py's scenarios use, implemented over
-the CPU oracle (oracle/pyoracle.py), tests/rebalance_ref.py, tests/spec_changes.py and tests/spec_remap.py; idle expiry is restated here in plain numpy.  It lets the fuzz driver itself be tested
+the CPU oracle (oracle/pyoracle.py), tests/rebalance_ref.py, tests/rebalance_order_ref.py, tests/spec_changes.py, tests/spec_remap.py
+and tests/spec_top.py; idle expiry and measured load (the hit column and the fold, in uint64: the scenarios hold them against
+tests/spec_loads.py's Python integers) are restated here in plain numpy.  It lets the fuzz driver itself be tested
 without a GPU (tests/test_fuzz_driver.py): its bookkeeping (n, the feed's checkpoint, the mirror, the uncommitted solve) and its
 sensitivity — `fault=` makes exactly one behaviour of the handle wrong, and the scenarios must notice.
 
@@ -13,15 +15,20 @@ import types
 
 import numpy as np
 
+import rebalance_order_ref
 import rebalance_ref
 import spec_changes
 import spec_remap
+import spec_top
 
 NONE = 0xFFFFFFFF
 CAP_INF = 0xFFFFFFFFFFFFFFFF
 AFF_INACTIVE = 0xFFFFFFFE
 CFG_REF_SELF_ASSIGN = 2
 CHANGES_PEEK = 1
+TOP_BY_HITS, TOP_PLACED, TOP_ON_NODE, TOP_MAX = 1, 2, 4, 4096
+REBALANCE_ROW_ORDER, REBALANCE_BY_LOAD = 0, 1
+U32 = 0xFFFFFFFF
 OK, EINVAL, EUPSTREAM, ENODEV, ENOMEM, ERANGE, EAGAIN = range(7)
 
 FAULTS = (
@@ -52,6 +59,26 @@ FAULTS = (
     "touch_dev_stops_at_invalid",  # the _dev batch stops at its first invalid entry instead of skipping it
     "touch_drops_solve",           # a touch drops an uncommitted solve
     "remap_moves_seen",            # a node removal clears the stamps of the rows < n
+    "hits_add_wraps",              # the hit counters wrap at 2^32 instead of saturating
+    "hits_dev_stops_at_invalid",   # the _dev hits batch stops at its first invalid entry instead of skipping it
+    "hits_merge_past_rows",        # a merge of `rows` counters also counts for the rest of the quad behind `rows`
+    "hits_drop_solve",             # a hits call drops an uncommitted solve
+    "fold_past_n",                 # the fold rewrites the loads and zeroes the hits of the rows >= n too
+    "fold_keeps_hits",             # the fold leaves H as it was
+    "fold_clamps_before_gain",     # the fold clamps the decayed load and adds H * gain afterwards
+    "fold_stale_used",             # the fold leaves `used` of the old loads
+    "fold_keeps_solve",            # the fold keeps an uncommitted solve committable
+    "fold_refused_still_zeroes_hits",   # a refused fold zeroes H[:n]
+    "top_ties_to_highest_rows",    # the report orders equal keys by descending row
+    "top_lists_hidden_rows",       # rows >= n are candidates of the report
+    "top_key_sum_of_listed_only",  # key_sum covers the listed candidates only
+    "top_reads_solved",            # the report reads the uncommitted column
+    "top_writes_past_listing",     # the report writes one entry behind its listing
+    "top_drops_solve",             # the report drops an uncommitted solve
+    "top_hits_key_ignores_flag",   # under RIO_GP_TOP_BY_HITS the key is still the load
+    "by_load_is_row_order",        # cfg.order is ignored: the cut is R1
+    "by_load_ties_shed_first_rows",     # among candidates of equal load the cut sheds the lowest rows, not the highest
+    "by_load_sheds_zero_load",     # zero-load candidates are cut behind the loaded ones, so an over node sheds them
 )
 
 
@@ -139,6 +166,7 @@ class GpuPlacement:
         self._alive_seen = self._alive.copy()   # the liveness the "device" has consumed (a set_alive* only pushes)
         self._B = np.full(self._cap_rows, NONE, np.uint32)
         self._S = np.zeros(self._cap_rows, np.uint32)
+        self._H = np.zeros(self._cap_rows, np.uint32)
         self._solved = None
         self._stale_used = None
         self._stale_aff = None
@@ -422,12 +450,25 @@ class GpuPlacement:
         return OK, len(r)
 
     # ---- bounded rebalance
-    def _rebalance(self, target, budget, rounds):
+    def _rebalance(self, target, budget, rounds, order=REBALANCE_ROW_ORDER):
+        if order not in (REBALANCE_ROW_ORDER, REBALANCE_BY_LOAD):
+            raise _einval("rio_gp_rebalance: cfg.order")
         col, load, aff = self._view()
-        alive = self._alive_seen if self._fault == "rebalance_stale_alive" and len(self._alive_seen) == self._m else self._alive
+        f = self._fault
+        alive = self._alive_seen if f == "rebalance_stale_alive" and len(self._alive_seen) == self._m else self._alive
         before = self.get_nodes()[2]
         solved = self._solved
-        nxt, used, st, rows, frm, to = rebalance_ref.rebalance(col, load, aff, self._cap, alive, target, budget, rounds or self._rounds)
+        if order == REBALANCE_BY_LOAD and f != "by_load_is_row_order":
+            r, perm = np.arange(len(col)), None
+            if f == "by_load_ties_shed_first_rows":
+                perm = np.lexsort((-r, load))
+            elif f == "by_load_sheds_zero_load":
+                perm = np.lexsort((r, load, load == 0))
+            nxt, used, st, rows, frm, to = rebalance_order_ref.rebalance(col, load, aff, self._cap, alive, target, budget,
+                                                                         rounds or self._rounds, order=order, perm=perm)
+        else:
+            nxt, used, st, rows, frm, to = rebalance_ref.rebalance(col, load, aff, self._cap, alive, target, budget,
+                                                                   rounds or self._rounds)
         col[:] = nxt
         self._changed()
         if self._fault == "rebalance_keeps_solve":
@@ -436,21 +477,22 @@ class GpuPlacement:
             self._stale_used = before
         return st, rows, frm, to
 
-    def rebalance(self, target=None, max_moves=None, rounds=0, list_moves=True, moves_cap=None):
+    def rebalance(self, target=None, max_moves=None, rounds=0, list_moves=True, moves_cap=None, order=REBALANCE_ROW_ORDER):
         if list_moves:
             mm = CAP_INF if max_moves is None else int(max_moves)
             cap = int(moves_cap if moves_cap is not None else min(mm, self._n))
-            return self._rebalance(target, min(mm, cap), rounds)
-        st, _, _, _ = self._rebalance(target, max_moves, rounds)
+            return self._rebalance(target, min(mm, cap), rounds, order)
+        st, _, _, _ = self._rebalance(target, max_moves, rounds, order)
         e = np.empty(0, np.uint32)
         return st, e, e, e
 
-    def rebalance_dev(self, d_rows=None, d_from=None, d_to=None, moves_cap=0, target=None, max_moves=None, rounds=0):
+    def rebalance_dev(self, d_rows=None, d_from=None, d_to=None, moves_cap=0, target=None, max_moves=None, rounds=0,
+                      order=REBALANCE_ROW_ORDER):
         if bool(d_rows) != bool(d_from) or bool(d_rows) != bool(d_to) or (not d_rows and moves_cap):
             raise _einval("rio_gp_rebalance: the output rule")
         mm = CAP_INF if max_moves is None else int(max_moves)
         budget = min(mm, int(moves_cap)) if d_rows else (None if max_moves is None else mm)
-        st, rows, frm, to = self._rebalance(target, budget, rounds)
+        st, rows, frm, to = self._rebalance(target, budget, rounds, order)
         if d_rows:
             _at(d_rows, len(rows))[:] = rows
             _at(d_from, len(rows))[:] = frm
@@ -585,6 +627,147 @@ class GpuPlacement:
             out_rows[:len(rows)] = rows
             out_node[:len(rows)] = nodes
         return OK, n_idle
+
+    # ---- measured load
+    def _hits_add(self, idx, w):
+        """H[idx[k]] += w[k], saturating: the sums in uint64 (fewer than 2^31 entries of less than 2^32 each)."""
+        idx = np.asarray(idx, np.int64)
+        w = np.ones(len(idx), np.uint64) if w is None else np.asarray(w, np.uint32).astype(np.uint64)
+        s = self._H.astype(np.uint64)
+        np.add.at(s, idx, w)
+        self._H = (s & np.uint64(U32) if self._fault == "hits_add_wraps" else np.minimum(s, np.uint64(U32))).astype(np.uint32)
+        if self._fault == "hits_drop_solve":
+            self._changed()
+
+    def hits_add_raw(self, idx, n=None, weight=None):
+        idx = np.asarray(idx, np.uint32)
+        if len(idx) and int(idx.max()) >= self._n:
+            return EINVAL
+        self._hits_add(idx, weight)
+        return OK
+
+    def hits_add(self, idx, weight=None):
+        if self.hits_add_raw(idx, weight=weight) != OK:
+            raise _einval("rio_gp_hits_add_batch: object index out of range")
+
+    def hits_add_dev(self, d_idx, n, d_weight=None):
+        idx = _at(d_idx, n).copy()
+        w = _at(d_weight, n).copy() if d_weight else np.ones(n, np.uint32)
+        bad = idx >= self._n
+        ok = ~bad
+        if self._fault == "hits_dev_stops_at_invalid" and bad.any():
+            ok[int(np.argmax(bad)):] = False
+        self._hits_add(idx[ok], w[ok])
+        if bad.any():
+            raise _einval("rio_gp_hits_add_batch: invalid entries were skipped")
+
+    def hits_merge(self, counts):
+        counts = np.asarray(counts, np.uint32)
+        rows = len(counts)
+        if rows > self._n:
+            raise _einval("rio_gp_hits_merge: rows exceeds the object table")
+        self._hits_add(np.arange(rows), counts)
+        if self._fault == "hits_merge_past_rows" and rows % 4:
+            self._hits_add(np.arange(rows, min(rows + 4 - rows % 4, self._cap_rows)), None)
+
+    def hits_merge_dev(self, d_counts, rows):
+        if rows > self._n:
+            raise _einval("rio_gp_hits_merge: rows exceeds the object table")
+        self.hits_merge(_at(d_counts, rows).copy())
+
+    def get_hits(self):
+        return self._H[:self._n].copy()
+
+    def load_fold_raw(self, keep, gain, min_load, max_load, _stats=None):
+        f, n = self._fault, self._n
+        if keep > 65536 or min_load > max_load:
+            if f == "fold_refused_still_zeroes_hits":
+                self._H[:n] = 0
+            return EINVAL
+        rows = self._cap_rows if f == "fold_past_n" else n
+        old, h = self._load[:rows].astype(np.uint64), self._H[:rows].astype(np.uint64)
+        lo, hi = np.uint64(min_load), np.uint64(max_load)
+        x = (old * np.uint64(keep)) >> np.uint64(16)
+        if f == "fold_clamps_before_gain":
+            new = np.minimum(np.clip(x, lo, hi) + h * np.uint64(gain), np.uint64(U32))
+        else:
+            new = np.clip(x + h * np.uint64(gain), lo, hi)
+        if _stats is not None:
+            _stats.update(rows_changed=int((old[:n] != new[:n]).sum()), hits_folded=int(h[:n].sum()), load_before=int(old[:n].sum()),
+                          load_after=int(new[:n].sum()), max_load_after=int(new[:n].max()) if n else 0)
+        before, solved = self.get_nodes()[2], self._solved
+        self._load[:rows] = new.astype(np.uint32)
+        if f != "fold_keeps_hits":
+            self._H[:rows] = 0
+        self._changed()
+        if f == "fold_keeps_solve":
+            self._solved = solved
+        if f == "fold_stale_used":
+            self._stale_used = before
+        return OK
+
+    def load_fold(self, keep, gain, min_load=0, max_load=U32):
+        st = {}
+        if self.load_fold_raw(keep, gain, min_load, max_load, st) != OK:
+            raise _einval("rio_gp_load_fold: keep > 65536 or min_load > max_load")
+        return st
+
+    # ---- hot-object report
+    def _top(self, flags, node, min_key, cap):
+        """-> rc, rows, keys, nodes, n_candidates, key_sum"""
+        f, e = self._fault, np.empty(0, np.uint32)
+        if cap > TOP_MAX or flags & ~(TOP_BY_HITS | TOP_PLACED | TOP_ON_NODE) or (flags & TOP_ON_NODE and node >= self._m):
+            return EINVAL, e, e, e, 0, 0
+        A, n = self._col, self._n
+        if f == "top_reads_solved" and self._solved is not None and len(self._solved) == n:
+            A = self._solved
+        if f == "top_lists_hidden_rows":
+            n = self._cap_rows
+        kflags = flags & ~TOP_BY_HITS if f == "top_hits_key_ignores_flag" else flags
+        rows, keys, nodes, nc, ks = spec_top.top_rows(A, self._load, self._H, n, kflags, node, min_key, cap)
+        if f == "top_ties_to_highest_rows":
+            r, k, _, _, _ = spec_top.top_rows(A, self._load, self._H, n, kflags, node, min_key, n)
+            rows = r[np.lexsort((-r.astype(np.int64), -k.astype(np.int64)))][:int(cap)]
+            keys, nodes = (self._H if kflags & TOP_BY_HITS else self._load)[rows], A[rows]
+        if f == "top_key_sum_of_listed_only":
+            ks = int(keys.astype(np.uint64).sum())
+        if f == "top_drops_solve":
+            self._changed()
+        return OK, rows, keys, nodes, nc, ks
+
+    def _top_out(self, arrays, values, cap):
+        """The listing into the caller's arrays of cap entries (a missing one is skipped)."""
+        L = len(values[0])
+        for out, v in zip(arrays, values):
+            if out is not None:
+                out[:L] = v
+                if self._fault == "top_writes_past_listing" and L < len(out):
+                    out[L] = 0
+
+    def top_rows(self, cap, by_hits=False, placed=False, node=None, min_key=0, want_node=True):
+        flags = (TOP_BY_HITS if by_hits else 0) | (TOP_PLACED if placed else 0) | (TOP_ON_NODE if node is not None else 0)
+        rc, rows, keys, nodes, nc, ks = self._top(flags, int(node or 0), int(min_key), int(cap))
+        if rc != OK:
+            raise _einval("rio_gp_top_rows")
+        return rows, keys, (nodes if want_node else None), nc, ks
+
+    def top_rows_dev(self, flags, node, min_key, d_rows, d_key, d_node, cap):
+        if bool(d_rows) != bool(d_key) or (not d_rows and (cap or d_node)):
+            raise _einval("rio_gp_top_rows: the output rule")
+        rc, rows, keys, nodes, nc, ks = self._top(int(flags), int(node), int(min_key), int(cap))
+        if rc != OK:
+            raise _einval("rio_gp_top_rows")
+        if d_rows:    # (a "device" array of cap entries: the scenario's buffers are longer, as the host's are)
+            self._top_out([_at(p, cap + 1) if p else None for p in (d_rows, d_key, d_node)], (rows, keys, nodes), cap)
+        return nc, ks
+
+    def top_rows_raw(self, flags, node=0, min_key=0, out_rows=None, out_key=None, out_node=None, cap=0, want_n=True):
+        if not want_n or (out_rows is None) != (out_key is None) or (out_rows is None and (cap or out_node is not None)):
+            return EINVAL, 0
+        rc, rows, keys, nodes, nc, _ = self._top(int(flags), int(node), int(min_key), int(cap))
+        if rc == OK:
+            self._top_out((out_rows, out_key, out_node), (rows, keys, nodes), cap)
+        return rc, nc
 
     # ---- lab calls: no-ops
     def set_compact(self, *a, **k):

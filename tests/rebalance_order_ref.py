@@ -13,8 +13,9 @@ INF = 0xFFFFFFFFFFFFFFFF
 ROW_ORDER, BY_LOAD = 0, 1
 
 
-def surplus_mask(cur, load, aff, T, alive, order=BY_LOAD):
-    """(surplus, live, pinned, cand) boolean row masks: tick A."""
+def surplus_mask(cur, load, aff, T, alive, order=BY_LOAD, perm=None):
+    """(surplus, live, pinned, cand) boolean row masks: tick A.  perm: the claim order of tick A from a caller that wants a
+    wrong one (the faults of tests/fake_rio_gp.py); None: the order of the rule."""
     import pyoracle
     m = len(T)
     on = (cur != NONE) & (cur < m)
@@ -23,7 +24,8 @@ def surplus_mask(cur, load, aff, T, alive, order=BY_LOAD):
     obj = aff != INACTIVE
     pinned, cand = live & ~obj, live & obj
     n = len(cur)
-    perm = np.lexsort((np.arange(n), load)) if order == BY_LOAD else np.arange(n)
+    if perm is None:
+        perm = np.lexsort((np.arange(n), load)) if order == BY_LOAD else np.arange(n)
     cur_a = np.where(pinned, cur, NONE).astype(np.uint32)
     aff_a = np.where(cand, cur, INACTIVE).astype(np.uint32)
     nxt_p, _, _ = pyoracle.tick(np.ascontiguousarray(cur_a[perm]), np.ascontiguousarray(load[perm]),
@@ -33,8 +35,8 @@ def surplus_mask(cur, load, aff, T, alive, order=BY_LOAD):
     return cand & (nxt_a == NONE), live, pinned, cand
 
 
-def rebalance(cur, load, aff, cap, alive, target=None, max_moves=None, rounds=2, order=BY_LOAD):
-    """Returns (next column uint32, used uint64 [m], stats dict, rows, from, to) — moves in row order."""
+def rebalance(cur, load, aff, cap, alive, target=None, max_moves=None, rounds=2, order=BY_LOAD, perm=None):
+    """Returns (next column uint32, used uint64 [m], stats dict, rows, from, to) — moves in row order.  perm: see surplus_mask."""
     import pyoracle
     if order == ROW_ORDER:
         return rebalance_ref.rebalance(cur, load, aff, cap, alive, target, max_moves, rounds)
@@ -45,7 +47,7 @@ def rebalance(cur, load, aff, cap, alive, target=None, max_moves=None, rounds=2,
     alive = np.asarray(alive, np.uint8)
     m = len(cap)
     T = cap if target is None else np.asarray(target, np.uint64)
-    surplus, live, _, _ = surplus_mask(cur, load, aff, T, alive, order)
+    surplus, live, _, _ = surplus_mask(cur, load, aff, T, alive, order, perm)
     idx = np.flatnonzero(surplus)
     sel = np.zeros(len(cur), bool)
     sel[idx if max_moves is None else idx[:max_moves]] = True

@@ -1,6 +1,7 @@
 """Measured load restated with Python integers (include/rio_gpu_placement.h "measured load"; DESIGN.md section 2 rule 10): the hit
 column H under rio_gp_hits_add_batch and rio_gp_hits_merge, and what rio_gp_load_fold makes of load and H.  Every sum is taken
-in Python integers (no wrap) and cut to a u32 at the end, so the restatement shares no arithmetic with the kernels.  `used` is
+in Python integers (no wrap) and cut to a u32 at the end, so the restatement shares no arithmetic with the kernels; the merge and
+the fold evaluate their row rule once per distinct (load, hits) pair, which keeps a table of 10^5 rows a matter of milliseconds.  `used` is
 k_used in numpy.  String layer: which calls count a request, as a dict model keeps them."""
 import numpy as np
 
@@ -9,22 +10,34 @@ U32 = 0xFFFFFFFF
 KEEP_ONE = 65536
 
 
+def _per_pair(a, b, f):
+    """[f(a[r], b[r]) for every row r] as uint32, f called with Python integers once per DISTINCT pair: a table of 10^5 rows has
+    few of them, and the arithmetic stays f's.  (The pairs are packed into one u64 to find the distinct ones; f sees them unpacked.)"""
+    a, b = np.asarray(a, np.uint32), np.asarray(b, np.uint32)
+    if len(a) == 0:
+        return np.zeros(0, np.uint32)
+    uniq, inv = np.unique((a.astype(np.uint64) << np.uint64(32)) | b.astype(np.uint64), return_inverse=True)
+    return np.array([f(k >> 32, k & U32) for k in uniq.tolist()], np.uint32)[inv.ravel()]
+
+
 def hits_add(H, idx, weight=None):
     """rio_gp_hits_add_batch -> H': H[idx[k]] = min(H[idx[k]] + w[k], 2^32-1); duplicates sum; the order does not matter."""
-    out = [int(x) for x in np.asarray(H, np.uint32)]
-    idx = [int(i) for i in np.asarray(idx, np.int64)]
-    w = [1] * len(idx) if weight is None else [int(x) for x in np.asarray(weight, np.uint32)]
+    out = np.array(H, np.uint32, copy=True)
+    idx = np.asarray(idx, np.int64).tolist()
+    w = [1] * len(idx) if weight is None else np.asarray(weight, np.uint32).tolist()
+    add = {}     # row -> the sum of its weights (Python integers), so that only the rows the batch names are walked
     for i, x in zip(idx, w):
-        out[i] += x
-    return np.array([min(x, U32) for x in out], np.uint32)
+        add[i] = add.get(i, 0) + x
+    for i, x in add.items():
+        out[i] = min(int(out[i]) + x, U32)
+    return out
 
 
 def hits_merge(H, counts):
     """rio_gp_hits_merge -> H': H[r] = min(H[r] + counts[r], 2^32-1) for r < len(counts)."""
     H = np.array(H, np.uint32, copy=True)
     k = len(counts)
-    s = H[:k].astype(object) + np.asarray(counts, np.uint32).astype(object)
-    H[:k] = np.array([min(int(x), U32) for x in s], np.uint32)
+    H[:k] = _per_pair(H[:k], counts, lambda h, c: min(h + c, U32))
     return H
 
 
@@ -39,11 +52,11 @@ def load_fold(load, H, n, keep, gain, min_load, max_load):
     """rio_gp_load_fold -> (load', H', stats): rows r < n are folded and their H zeroed; rows >= n keep both."""
     load = np.array(load, np.uint32, copy=True)
     H = np.array(H, np.uint32, copy=True)
-    old = [int(x) for x in load[:n]]
-    new = [fold_one(l, h, keep, gain, min_load, max_load) for l, h in zip(old, H[:n])]
-    st = {"rows_changed": sum(a != b for a, b in zip(old, new)), "hits_folded": sum(int(h) for h in H[:n]),
+    folded = _per_pair(load[:n], H[:n], lambda l, h: fold_one(l, h, keep, gain, min_load, max_load))
+    old, hits, new = load[:n].tolist(), H[:n].tolist(), folded.tolist()    # (Python integers)
+    st = {"rows_changed": int(np.count_nonzero(folded != load[:n])), "hits_folded": sum(hits),
           "load_before": sum(old), "load_after": sum(new), "max_load_after": max(new) if new else 0}
-    load[:n] = np.array(new, np.uint32) if n else load[:0]
+    load[:n] = folded
     H[:n] = 0
     return load, H, st
 

@@ -56,6 +56,38 @@ FLOOR = (
     "touch with hidden rows",
     "touch_dev skipped invalid entries",
     "touch between tick_async and tick_wait",
+    "hits saturated exactly at 0xFFFFFFFF",
+    "hits_dev skipped invalid entries",
+    "hits merge from an unaligned device array",
+    "hits merge of rows not a multiple of 4",
+    "hits while a solve is uncommitted",
+    "hits with hidden rows holding hits",
+    "hits between tick_async and tick_wait",
+    "fold with used not valid",
+    "fold on more than 4 096 nodes",
+    "fold on a handle whose m is below max_nodes",
+    "fold with n not a multiple of 4 and hits in the quad behind n",
+    "fold changed no load",
+    "fold clamped every load to one value",
+    "fold while a solve is uncommitted",
+    "fold between tick_async and tick_wait",
+    "fold refused with a solve uncommitted",
+    "top by hits before any hits call",
+    "top cut inside a tie group spanning tiles",
+    "top listed all 4 096",
+    "top with cap above n_candidates",
+    "top between two pages of the feed",
+    "top right after an expire that listed rows",
+    "top while a solve is uncommitted",
+    "top between tick_async and tick_wait",
+    "top on a handle whose m is below max_nodes",
+    "top at n == 0",
+    "by-load cut moved rows",
+    "by-load cut after a fold made every load equal",
+    "by-load cut with more than 3 072 over nodes",
+    "by-load cut with zero-load candidates on an over node",
+    "by-load cut between tick_async and tick_wait",
+    "by-load cut on a handle whose m is below max_nodes",
 )
 
 # fault of the stand-in -> the operation the failure must name
@@ -87,6 +119,26 @@ FAULTS = {
     "touch_dev_stops_at_invalid": "touch",
     "touch_drops_solve": "touch",
     "remap_moves_seen": "remap",
+    "hits_add_wraps": "hits",
+    "hits_dev_stops_at_invalid": "hits",
+    "hits_merge_past_rows": "hits",
+    "hits_drop_solve": "hits",
+    "fold_past_n": "num_objects",
+    "fold_keeps_hits": "fold",
+    "fold_clamps_before_gain": "fold",
+    "fold_stale_used": "fold",
+    "fold_keeps_solve": "fold",
+    "fold_refused_still_zeroes_hits": "fold",
+    "top_ties_to_highest_rows": "top",
+    "top_lists_hidden_rows": "top",
+    "top_key_sum_of_listed_only": "top",
+    "top_reads_solved": "top",
+    "top_writes_past_listing": "top",
+    "top_drops_solve": "top",
+    "top_hits_key_ignores_flag": "top",
+    "by_load_is_row_order": "rebalance",
+    "by_load_ties_shed_first_rows": "rebalance",
+    "by_load_sheds_zero_load": "rebalance",
 }
 
 
@@ -105,7 +157,7 @@ def test_op_tables():
                                  ("clean", 2), ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
     assert fuzz.Scenario.OPS_EXT[:len(fuzz.Scenario.OPS)] == fuzz.Scenario.OPS
     assert [a for a, _ in fuzz.Scenario.OPS_EXT[len(fuzz.Scenario.OPS):]] == ["index", "rebalance", "changes", "changes_reset",
-                                                                            "num_objects", "remap", "touch", "expire"]
+                                                                            "num_objects", "remap", "touch", "expire", "hits", "fold", "top"]
 
 
 @pytest.fixture(scope="module")
@@ -126,7 +178,8 @@ def test_extended_seeds_run_clean_and_use_every_new_operation(clean_run):
     cov, count = clean_run
     for op in ("index", "rebalance", "changes", "changes_reset", "num_objects", "remap", "touch", "expire", "in flight: index",
                "in flight: changes", "in flight: rebalance", "in flight: remap", "in flight: touch", "in flight: expire",
-               "mid run: touch", "mid run: expire count", "mid run: expire"):
+               "mid run: touch", "mid run: expire count", "mid run: expire", "hits", "fold", "top", "in flight: hits",
+               "in flight: fold", "in flight: top", "mid run: hits", "mid run: fold", "mid run: top"):
         assert count.get(op, 0) > 0, (op, count)
 
 

@@ -41,6 +41,32 @@ uncommitted solve and ends a chained run, one that listed nothing (or only count
 between tick_async and tick_wait and in the middle of chained quiet runs; S is compared again when hidden rows come back and after
 every node removal (S names no node).
 
+Measured load, the hot-object report and the load-ordered rebalance cut are fuzzed the same way (the dense layer only: the string
+layer's calls are not in its fuzz yet).  The scenario keeps a model H of the hit column over every row the handle holds.  `hits`
+draws one of the family's writers (tests/spec_loads.py) — the host batch with and without weights, duplicates included (and one
+refused for an index >= n), the _dev batch (sometimes not 16-byte aligned; with invalid entries it applies the rest and reports
+RIO_GP_EINVAL), the merge host and _dev (rows 0, n, a boundary size, any, so every rows % 4; the _dev array sometimes behind 1-3
+words of padding) and a merge of n + 1 rows, refused; about one call in ten carries values that fill a counter exactly, miss
+0xFFFFFFFF by one, overshoot it, and plain 0xFFFFFFFF — and rio_gp_get_hits must equal H[:n] after each, an uncommitted solve
+still there.  `fold` draws (keep, gain, min_load, max_load) by kind (identity, replace, decay, one value for every row, a small
+max_load, a gain that takes H * gain past 2^32); the five statistics, the loads, H zero on [:n] and `used` of the new loads are
+exact, and every legal fold — the identity too — drops an uncommitted solve and ends a chained run; about one in ten is refused
+(keep 65537, min_load > max_load) and changes nothing.  A quarter of the folds call rio_gp_set_num_objects themselves right
+before, with nothing in between, so that `used` is not valid when the fold picks its kernel (the scenario's own check after every
+operation makes it valid again), sometimes onto a row that holds hits in the middle of its quad.  `top` draws all eight flag
+sets, a node (any, the fullest, an empty one, one >= m: refused under ON_NODE and ignored without), min_key (0, a key that occurs,
+the largest, one above, 0xFFFFFFFF), a cap (0, 1, small, n_candidates - 1 / n_candidates / n_candidates + 1, 4 096, one that cuts
+inside a group of equal keys lying in more than one tile of 1 024 rows) and a form (host with and without out_node, the call as
+given into sentinel-filled arrays, _dev with and without d_node, count-only host and _dev) against tests/spec_top.py, whose H is
+None until a call of the hits section has been made; cap 4 097 and an unknown flag bit are refused; rows, keys, nodes,
+n_candidates and key_sum are exact, nothing is written behind the listing, H and an uncommitted solve are as they were.
+`rebalance` draws its order: by load it goes through tests/rebalance_order_ref.py and, up to 4 096 rows, through
+tests/spec_rebalance_order.py, which must agree first; on more than 3 072 nodes half of those calls take all-zero targets.  All
+three new calls are also made between tick_async and tick_wait and in the middle of chained quiet runs (hits and top leave the
+run chained, a fold ends it), right behind an uncommitted solve, and — the report — right behind a sweep that listed rows and
+between two pages of the feed; H is compared again after every node removal and sweep, and H and the loads when hidden rows come
+back and, over every row, at the end.
+
     python tests/test_gpu_fuzz.py <seconds> [first_seed]     # a longer campaign: old and extended scenarios alternate
 """
 import os
@@ -141,6 +167,14 @@ class Scenario:
         self.clock = 0
         self.seen_used = self.expire_listed = False
         self.mids = 0              # quiet runs so far (op_async: which call goes into the middle of the next one)
+        self.flights = 0           # streams with a call between tick_async and tick_wait so far (op_async: which call is next)
+        # measured load: the model of the hit column (rows >= n keep their value), whether a call of the section has been made
+        # (the first one allocates H: until then the report's model has none), whether the last fold was refused, whether the
+        # last legal fold left every load equal; mark / after: what the last operation left behind for the one right after it
+        # ("expire listed": the sweep has just used the scratch the report shares)
+        self.H = np.zeros(n, np.uint32)
+        self.hits_used = self.fold_refused = self.fold_equal = False
+        self.mark = self.after = None
         self.cov = {}
 
     def _caps(self):
@@ -160,6 +194,8 @@ class Scenario:
 
     # ---- checks -------------------------------------------------------------------------------------------------------
     def check_table(self, what):
+        if self.in_flight:     # (the first look at the table since the ticks were enqueued: what they did wrong shows here)
+            what = "%s, behind tick_async" % what
         got, ref = self.g.get_assign(), self.ref[:self.n]
         assert np.array_equal(got, ref), (self.seed, what, self.log[-6:], np.flatnonzero(got != ref)[:8])
         used = self.oracle.recompute_used(ref, self.load[:self.n], self.m)
@@ -192,7 +228,7 @@ class Scenario:
         assert st == ost, (self.seed, "solve", self.log[-6:], st, ost)
         assert np.array_equal(got, want), (self.seed, "solve", self.log[-6:], np.flatnonzero(got != want)[:8])
         self.fresh_flip = False
-        if self.rng.random() < 0.5:
+        if self.rng.random() < (0.3 if self.ext else 0.5):   # (extended scenarios: more of the calls meet an uncommitted solve)
             self.g.commit()
             self._set_col(want)
             self.pending = None
@@ -202,19 +238,22 @@ class Scenario:
     def op_async(self):
         k = int(self.rng.integers(1, 5))
         # a longer stream without changes: verdicts land, the ticks chain (extended scenarios: more often, for the calls in its middle)
-        quiet_run = self.chain_small and self.rng.random() < (0.75 if self.ext else 0.5)
+        # (the first asynchronous stream of such an extended scenario always is one, and run() makes sure there is a stream: the
+        # default seeds hold more of these scenarios than there are calls to put into the middle of a run)
+        quiet_run = self.chain_small and (self.rng.random() < (0.75 if self.ext else 0.5) or (self.ext and self.mids == 0))
         if quiet_run:
             k += 6
         last_chained = False
         want_st = []
         # extended scenarios, a quiet run: a call in the middle of it (see _mid_call); any run: a call between the last tick_async
         # and tick_wait, whose answer reflects every enqueued tick
-        # (the calls take turns, from a start the seed sets: a dozen of the default seeds have such runs, and each call gets one)
+        # (the calls take turns, from a start the seed sets: sixteen of the default seeds have such runs, and each call gets one)
         mid = "none"
         if self.ext and quiet_run:
             mid = self.MID[(self.seed // 6 + self.mids) % len(self.MID)]
             self.mids += 1
         watch = None
+        self.after = None          # (the ticks below come between the operation before and the calls in flight)
         for i in range(k):
             if i and not quiet_run and self.rng.random() < 0.5:
                 self.op_flip()
@@ -229,8 +268,8 @@ class Scenario:
             if self.lab and mid != "none":
                 last_chained = self.g.chained_scans() - c0 == 1
                 if watch is not None and watch[0] in self.ENDS_CHAIN and i == k - 4:
-                    # a rebalance, a node removal (the identity map too) and a sweep that un-placed a row change the inputs: the
-                    # tick after does not chain
+                    # a rebalance, a node removal (the identity map too), a fold (the identity fold too) and a sweep that
+                    # un-placed a row change the inputs: the tick after does not chain
                     assert not last_chained, (self.seed, watch[0], "the tick after a %s chained" % watch[0], self.log[-6:])
             if self.rng.random() < 0.3 or (quiet_run and i < 3):
                 time.sleep(0.002)
@@ -240,10 +279,13 @@ class Scenario:
             c = self.g.chained_scans() - watch[2]
             assert c == 4, (self.seed, watch[0], "quiet ticks after the call did not stay chained", c, self.log[-6:])
             self.cov["chained across a call"] = self.cov.get("chained across a call", 0) + 1
-        if self.ext and self.rng.random() < 0.5:
+        self.mark = None           # (a call in the middle of the run is not "right before" what follows the ticks after it)
+        if self.ext and self.rng.random() < 0.7:
             self.in_flight = True
             try:
-                what = ("index", "changes", "rebalance", "remap", "touch", "expire")[int(self.rng.integers(6))]
+                # (the calls take turns, from a start the seed sets: each of them gets a few of the default seeds' streams)
+                what = ("index", "changes", "rebalance", "remap", "touch", "expire", "hits", "fold", "top")[(self.seed + self.flights) % 9]
+                self.flights += 1
                 self.log.append("in flight: " + what)
                 self.count["in flight: " + what] = self.count.get("in flight: " + what, 0) + 1
                 getattr(self, "op_" + what)()
@@ -256,7 +298,8 @@ class Scenario:
         """A call between the quiet asynchronous ticks of a run (lab build, every tick may chain).  The index and a consuming feed
         call change nothing a tick reads: if the tick before was a link of a chain, the ticks after are.  A rebalance ends the
         chain, and so does a node removal.  A touch, a count-only sweep and a sweep that lists nothing change nothing either; a
-        sweep that un-placed a row ends the chain ("expire" comes back as "expire count" when it listed nothing).
+        sweep that un-placed a row ends the chain ("expire" comes back as "expire count" when it listed nothing).  The hits calls
+        and the report change nothing; a legal fold ends the chain whatever it folds.
         -> (what, the tick before chained, chained_scans() after the call)"""
         self.log.append("mid run: " + what)
         self.count["mid run: " + what] = self.count.get("mid run: " + what, 0) + 1
@@ -268,6 +311,12 @@ class Scenario:
             self.op_rebalance()
         elif what == "touch":
             self.op_touch()
+        elif what == "hits":
+            self.op_hits()
+        elif what == "top":
+            self.op_top()
+        elif what == "fold":
+            self.op_fold(legal=True)      # (a refused fold changes nothing: only a legal one must end the chain)
         elif what == "expire count":
             self.op_expire(hit=False)
         elif what == "expire":
@@ -526,9 +575,14 @@ class Scenario:
         return kind, (np.zeros(m, np.uint64) if kind == "zero" else np.full(m, INF, np.uint64))
 
     def op_rebalance(self):
+        import rebalance_order_ref
         import rebalance_ref
         rng, m, n, g = self.rng, self.m, self.n, self.g
         kind, T = self._targets()
+        order = (rebalance_order_ref.ROW_ORDER, rebalance_order_ref.BY_LOAD)[int(rng.random() < (0.7 if self.in_flight else 0.5))]
+        by_load = order == rebalance_order_ref.BY_LOAD
+        if by_load and m > 3072 and rng.random() < 0.5:    # every node that holds load is over: the cut's histograms in global memory
+            kind, T = "zero", np.zeros(m, np.uint64)
         max_moves = (None, 0, 1, max(1, n * int(rng.integers(1, 6)) // 100))[int(rng.integers(4))]
         rounds = int(rng.integers(0, 4))
         form = ("host", "dev", "count", "dev count")[int(rng.integers(4))]
@@ -542,27 +596,35 @@ class Scenario:
             budget = cap if max_moves is None else min(max_moves, cap)
         had_solve, dead_unticked = self.pending is not None, self.fresh_flip and not self.alive.all()
         cur, load, aff = self.ref[:n], self.load[:n], self.aff[:n]
-        nxt, used, wst, wrows, wfrom, wto = rebalance_ref.rebalance(cur, load, aff, self.cap, self.alive, T, budget, rounds or self.rounds)
-        tag = (self.seed, "rebalance", kind, form, max_moves, moves_cap, rounds, self.log[-6:])
+        tag = (self.seed, "rebalance", "by load" if by_load else "row order", kind, form, max_moves, moves_cap, rounds, self.log[-6:])
+        if by_load:      # R1': the two-tick composition over the rows in (load, row) order
+            nxt, used, wst, wrows, wfrom, wto = rebalance_order_ref.rebalance(cur, load, aff, self.cap, self.alive, T, budget,
+                                                                              rounds or self.rounds, order=order)
+        else:
+            nxt, used, wst, wrows, wfrom, wto = rebalance_ref.rebalance(cur, load, aff, self.cap, self.alive, T, budget, rounds or self.rounds)
         if n <= 4096:    # the row-by-row restatement as well
-            import spec_rebalance
-            s_nxt, s_used, s_st, s_moves = spec_rebalance.rebalance([int(x) for x in cur], [int(x) for x in load], [int(x) for x in aff],
-                                                                    [int(x) for x in self.cap], [int(x) for x in self.alive],
-                                                                    None if T is None else [int(x) for x in T], budget, rounds or self.rounds)
+            ints = ([int(x) for x in cur], [int(x) for x in load], [int(x) for x in aff], [int(x) for x in self.cap],
+                    [int(x) for x in self.alive], None if T is None else [int(x) for x in T], budget, rounds or self.rounds)
+            if by_load:
+                import spec_rebalance_order
+                s_nxt, s_used, s_st, s_moves = spec_rebalance_order.rebalance(*ints, order=order)
+            else:
+                import spec_rebalance
+                s_nxt, s_used, s_st, s_moves = spec_rebalance.rebalance(*ints)
             assert s_st == wst and [int(x) for x in nxt] == s_nxt and [int(x) for x in used] == s_used, tag + ("the two references differ",)
             assert s_moves == [(int(r), int(f), int(t)) for r, f, t in zip(wrows, wfrom, wto)], tag + ("the two references differ",)
         if form == "host":
-            st, rows, frm, to = g.rebalance(T, max_moves, rounds, moves_cap=moves_cap)
+            st, rows, frm, to = g.rebalance(T, max_moves, rounds, moves_cap=moves_cap, order=order)
         elif form == "count":
-            st, rows, frm, to = g.rebalance(T, max_moves, rounds, list_moves=False)
+            st, rows, frm, to = g.rebalance(T, max_moves, rounds, list_moves=False, order=order)
         elif form == "dev count":
-            st, nm = g.rebalance_dev(target=T, max_moves=max_moves, rounds=rounds)
+            st, nm = g.rebalance_dev(target=T, max_moves=max_moves, rounds=rounds, order=order)
             assert nm == len(wrows), tag + (nm, len(wrows))
         else:
             DevBuf = self._devbuf()
             cap = int(cap)
             d = [DevBuf(np.full(cap + 2, 0xDEADBEEF, np.uint32)) for _ in range(3)]
-            st, nm = g.rebalance_dev(d[0].ptr, d[1].ptr, d[2].ptr, cap, target=T, max_moves=max_moves, rounds=rounds)
+            st, nm = g.rebalance_dev(d[0].ptr, d[1].ptr, d[2].ptr, cap, target=T, max_moves=max_moves, rounds=rounds, order=order)
             rows, frm, to = (x.to_host() for x in d)
             for x in d:
                 x.free()
@@ -584,6 +646,19 @@ class Scenario:
         self._hit("rebalance while a solve is uncommitted", had_solve)
         self._hit("rebalance between tick_async and tick_wait", self.in_flight)
         self._hit("rebalance on a handle whose m is below max_nodes", self.m < self.m0)
+        if by_load:
+            Tn = self.cap if T is None else np.asarray(T, np.uint64)
+            over = (self.alive != 0) & (self.oracle.recompute_used(cur, load, m) > Tn)
+            on = cur < m
+            zero = on & (load == 0) & (aff != AFF_INACTIVE)
+            zero[on] &= over[cur[on]]
+            self._hit("by-load cut moved rows", wst["moved_rows"] > 0)
+            self._hit("by-load cut after a fold made every load equal",
+                      self.fold_equal and n > 1 and bool((load == load[0]).all()) and wst["surplus_rows"] > 0)
+            self._hit("by-load cut with more than 3 072 over nodes", wst["nodes_over_before"] > 3072)
+            self._hit("by-load cut with zero-load candidates on an over node", bool(zero.any()))
+            self._hit("by-load cut between tick_async and tick_wait", self.in_flight)
+            self._hit("by-load cut on a handle whose m is below max_nodes", self.m < self.m0)
 
     def _feed(self, cap, peek, dev):
         import spec_changes
@@ -658,6 +733,8 @@ class Scenario:
             assert np.array_equal(aff, self.aff[:n]), tag + ("affinity", np.flatnonzero(aff != self.aff[:n])[:8])
         if grew and self.seen_used:    # the stamps of the rows that were hidden: no touch, sweep or remap in between moved them
             self._seen_check((self.seed, "num_objects", "the stamps of rows that were hidden", self.log[-6:]))
+        if grew and self.hits_used:    # their hits and loads: no hits call and no fold reaches a hidden row
+            self._hits_check((self.seed, "num_objects", "the hits and loads of rows that were hidden", self.log[-6:]), loads=True)
 
     def _remap_draw(self):
         """A legal map for rio_gp_remap_nodes, at least one node kept: identity | permutation | swap | drop one | drop several
@@ -775,6 +852,8 @@ class Scenario:
         self.check_table("remap")
         if self.seen_used:             # S names no node: it does not move with them
             self._seen_check(tag + ("the last-seen column changed",))
+        if self.hits_used:             # nor does H
+            self._hits_check(tag + ("the hit column changed",))
         if had_solve:
             self._dropped("remap")
         self._hit("remap removed nodes that held rows", ev > 0)
@@ -909,6 +988,8 @@ class Scenario:
         placed = np.flatnonzero(A[:n] != NONE)
         first, had_solve = not self.seen_used, self.pending is not None
         form = ("host", "dev", "host", "dev", "count", "dev count")[int(rng.integers(6))]
+        if hit is None and had_solve and rng.random() < 0.5:
+            hit = True                 # (a sweep that must drop the solve, not one of the many that list nothing)
         if hit is True:
             form = form if form in ("host", "dev") else ("host", "dev")[int(rng.integers(2))]
             lo = int(S[placed].min()) if len(placed) else 0
@@ -976,7 +1057,10 @@ class Scenario:
         self.ref = A2
         self.expire_listed = L > 0
         self._seen_check(tag)          # a sweep reads S and never writes it
+        if self.hits_used:             # and H is no business of its
+            self._hits_check(tag)
         if L > 0:
+            self.mark = "expire listed"
             self.pending = None
             if had_solve:
                 self._dropped("expire")
@@ -984,6 +1068,302 @@ class Scenario:
             self._read_only("expire")
         self.check_table("expire")
         return L
+
+    # ---- measured load and the hot-object report: tests/spec_loads.py and tests/spec_top.py --------------------------------
+    def _hits_check(self, tag, loads=False):
+        got = self.g.get_hits()
+        self.hits_used = True
+        assert np.array_equal(got, self.H[:self.n]), tag + ("get_hits differs from the model", np.flatnonzero(got != self.H[:self.n])[:8])
+        if loads:
+            got = self.g.get_objects()[0]
+            assert np.array_equal(got, self.load[:self.n]), tag + ("load differs from the model", np.flatnonzero(got != self.load[:self.n])[:8])
+
+    def _hit_values(self, rows, at):
+        """Weights or counts for the rows `rows` (distinct, or every other entry of a repeated row carries 0): mostly small, some
+        0; in about one call in ten up to four of them are what fills the row's counter exactly (0xFFFFFFFF - H), misses by one,
+        overshoots by one, and plain 0xFFFFFFFF.  at: the entries that may carry one.  -> (values, one filled its row exactly)"""
+        rng = self.rng
+        w = rng.integers(0, 6, len(rows)).astype(np.uint32)
+        if rng.random() < 0.3:
+            w[rng.random(len(rows)) < 0.2] = rng.integers(0, 100000)
+        exact = False
+        if len(at) and rng.random() < 0.12:
+            at = rng.permutation(at)[:4]
+            for j, k in enumerate(at):
+                room = 0xFFFFFFFF - int(self.H[rows[k]])
+                w[k] = (room, max(room - 1, 0), min(room + 1, 0xFFFFFFFF), 0xFFFFFFFF)[j]
+            exact = True
+        return w, exact
+
+    def op_hits(self):
+        """One call of the hits family against spec_loads.hits_add / hits_merge; rio_gp_get_hits must equal H[:n] after each, an
+        uncommitted solve still there."""
+        import spec_loads
+        rng, n, g = self.rng, self.n, self.g
+        form = ("host", "host weights", "host refused", "dev", "dev invalid", "merge", "merge dev", "merge refused")[int(rng.integers(8))]
+        tag = (self.seed, "hits", form, n, self.log[-6:])
+        self._hit("hits while a solve is uncommitted", self.pending is not None)
+        self._hit("hits with hidden rows holding hits", bool(self.H[n:].any()))
+        self._hit("hits between tick_async and tick_wait", self.in_flight)
+        bufs, exact = [], False
+
+        def batch(idx):
+            """weights for a batch (None: 1 each); the entries of a row that gets a filling weight are its only ones that count"""
+            if form == "host" or (form != "host weights" and rng.random() < 0.4):
+                return None, False
+            _, first = np.unique(idx, return_index=True)
+            w, ex = self._hit_values(idx, first)
+            if ex:
+                again = np.ones(len(idx), bool)
+                again[first] = False
+                w[again] = 0
+            return w, ex
+
+        if form in ("host", "host weights", "dev"):
+            idx = self._idx(big_ok=False) if n else np.zeros(0, np.uint32)
+            w, exact = batch(idx)
+            if form == "dev":
+                d, ptr = self._dev_offset(idx)
+                dw, wptr = self._dev_offset(w) if w is not None else (None, None)
+                bufs += [d] + ([dw] if dw is not None else [])
+                g.hits_add_dev(ptr, idx.size, wptr)
+            else:
+                g.hits_add(idx, w)
+            self.H = spec_loads.hits_add(self.H, idx, w)
+        elif form == "host refused":          # validated first: one index >= n, nothing changes
+            bad = np.append(self._idx(big_ok=False) if n else np.zeros(0, np.uint32), np.uint32(0))
+            bad[int(rng.integers(bad.size))] = self._beyond_n()
+            rc = g.hits_add_raw(bad, weight=None if rng.random() < 0.5 else np.ones(bad.size, np.uint32))
+            assert rc == self.gp.EINVAL, tag + (rc,)
+        elif form == "dev invalid":           # the valid entries are applied, the call reports RIO_GP_EINVAL
+            bad = np.append(self._idx(big_ok=False) if n else np.zeros(0, np.uint32), np.uint32(0))
+            for k in rng.integers(0, bad.size, int(rng.integers(1, 5))):
+                bad[int(k)] = self._beyond_n()
+            ok = bad < n
+            w, exact = batch(np.where(ok, bad, 0).astype(np.uint32))
+            exact = False                     # (a filling weight may sit on an invalid entry)
+            d, ptr = self._dev_offset(bad)
+            dw, wptr = self._dev_offset(w) if w is not None else (None, None)
+            bufs += [d] + ([dw] if dw is not None else [])
+            self._refused(lambda: g.hits_add_dev(ptr, bad.size, wptr), tag)
+            self.H = spec_loads.hits_add(self.H, bad[ok], None if w is None else w[ok])
+            self._hit("hits_dev skipped invalid entries")
+        elif form == "merge refused":         # rows = n + 1
+            counts = np.ones(n + 1, np.uint32)
+            if rng.random() < 0.5:
+                self._refused(lambda: g.hits_merge(counts), tag)
+            else:
+                d, ptr = self._dev_offset(counts)
+                bufs.append(d)
+                self._refused(lambda: g.hits_merge_dev(ptr, n + 1), tag)
+        else:
+            rows = (0, n, n, _pick(rng, _SIZES, n) if n else 0, int(rng.integers(0, n + 1)))[int(rng.integers(5))]
+            counts, exact = self._hit_values(np.arange(rows), np.arange(rows))
+            self._hit("hits merge of rows not a multiple of 4", rows % 4 != 0)
+            if form == "merge":
+                g.hits_merge(counts)
+            else:
+                d, ptr = self._dev_offset(counts)
+                bufs.append(d)
+                self._hit("hits merge from an unaligned device array", ptr != d.ptr)
+                g.hits_merge_dev(ptr, rows)
+            self.H = spec_loads.hits_merge(self.H, counts)
+        self._hit("hits saturated exactly at 0xFFFFFFFF", exact)
+        self._hits_check(tag)      # (it waits: rio_gp_hits_merge_dev does not, and its buffer is freed below)
+        for d in bufs:
+            d.free()
+        self._read_only("hits")
+        self.check_table("hits")
+
+    def _fold_draw(self):
+        """(kind, keep, gain, min_load, max_load) of a legal fold."""
+        rng = self.rng
+        kind = ("identity", "replace", "decay", "one value", "small max", "large gain")[int(rng.integers(6))]
+        small = int(rng.integers(0, 4))
+        if kind == "identity":
+            return kind, 65536, 0, 0, 0xFFFFFFFF
+        if kind == "replace":
+            lo = int(rng.integers(0, 3))
+            return kind, 0, int(rng.integers(0, 50)), lo, (0xFFFFFFFF, lo + int(rng.integers(0, 1000)))[int(rng.integers(2))]
+        if kind == "decay":
+            return kind, (32768, 1, 65535)[int(rng.integers(3))], small, 0, 0xFFFFFFFF
+        if kind == "one value":
+            v = (0, 1, 255, 256, 65535, 65536, 1 << 24, 0xFFFFFFFF)[int(rng.integers(8))]
+            return kind, (0, 32768, 65536)[int(rng.integers(3))], small, v, v
+        if kind == "small max":
+            return kind, (32768, 65536)[int(rng.integers(2))], small, 0, int(rng.integers(0, 8))
+        return kind, (0, 32768, 65536)[int(rng.integers(3))], int(rng.integers(1 << 16, 1 << 32)), 0, 0xFFFFFFFF
+
+    def op_fold(self, legal=False):
+        """rio_gp_load_fold against spec_loads.load_fold over the model's loads and hits: the five statistics, the loads, H zero on
+        [:n], `used` of the new loads; every legal fold drops an uncommitted solve, a refused one changes nothing."""
+        import spec_loads
+        rng, n, g = self.rng, self.n, self.g
+        kind, keep, gain, lo, hi = self._fold_draw()
+        had_solve = self.pending is not None
+        self.fold_refused = not legal and rng.random() < (0.4 if had_solve else 0.1)
+        if self.fold_refused:
+            if rng.random() < 0.5 or hi == 0:
+                keep = 65537 + int(rng.integers(0, 2)) * int(rng.integers(0, 1 << 20))
+            else:
+                lo, hi = hi, int(rng.integers(0, hi))
+            tag = (self.seed, "fold", "refused", keep, gain, lo, hi, n, self.log[-6:])
+            rc = g.load_fold_raw(keep, gain, lo, hi)
+            assert rc == self.gp.EINVAL, tag + (rc,)
+            self._hit("fold refused with a solve uncommitted", had_solve)
+            self._hits_check(tag, loads=True)
+            self._read_only("fold refused")
+            self.check_table("fold refused")
+            return
+        fresh_n = False
+        if not legal and not self.in_flight and not had_solve and rng.random() < 0.25:
+            # rio_gp_set_num_objects right before it, and nothing in between: `used` is not valid when the fold picks its form
+            # (after an operation of its own the scenario's check_table has made it valid again)
+            n = (self.nmax, _pick(rng, _SIZES, self.nmax), int(rng.integers(0, self.nmax + 1)), -1)[int(rng.integers(4))]
+            if n < 0:      # a row that holds hits and is not the first of its quad becomes the first hidden one
+                held = np.flatnonzero(self.H)
+                held = held[held % 4 != 0]
+                n = int(held[rng.integers(len(held))]) if len(held) else self.nmax
+            fresh_n = n != self.n
+            self._set_n(n)
+            self.page_writer = self.page_writer or fresh_n
+        tag = (self.seed, "fold", kind, keep, gain, lo, hi, n, fresh_n, self.log[-6:])
+        self._hit("fold with used not valid", fresh_n)
+        self._hit("fold on more than 4 096 nodes", self.m > 4096)
+        self._hit("fold on a handle whose m is below max_nodes", self.m < self.m0)
+        self._hit("fold with n not a multiple of 4 and hits in the quad behind n", n % 4 != 0 and bool(self.H[n:(n | 3) + 1].any()))
+        self._hit("fold while a solve is uncommitted", had_solve)
+        self._hit("fold between tick_async and tick_wait", self.in_flight)
+        self.load, self.H, want = spec_loads.load_fold(self.load, self.H, n, keep, gain, lo, hi)
+        st = g.load_fold(keep, gain, lo, hi)
+        self.pending = None
+        self.fold_equal = n > 1 and bool((self.load[:n] == self.load[0]).all())
+        self._hit("fold changed no load", want["rows_changed"] == 0)
+        self._hit("fold clamped every load to one value", self.fold_equal)
+        assert st == want, tag + ("statistics", st, want)
+        self._hits_check(tag, loads=True)     # (H is zero on [:n], the loads are the model's)
+        self.check_table("fold")              # (`used` is that of the new loads)
+        if had_solve:
+            self._dropped("fold")
+
+    def _top_cap(self, keys_all, rows_all):
+        """0 (count only) | 1 | a small number | n_cand - 1, n_cand, n_cand + 1 | 4 096 | a cap that cuts inside a group of equal
+        keys whose rows lie in more than one tile of 1 024 rows -> (cap, it is such a cut)"""
+        import spec_top
+        rng, nc = self.rng, len(rows_all)
+        k = int(rng.integers(9))
+        if k < 7:
+            return min(max((0, 1, int(rng.integers(2, 60)), nc - 1, nc, nc + 1, spec_top.TOP_MAX)[k], 0), spec_top.TOP_MAX), False
+        start = np.flatnonzero(np.concatenate([[True], keys_all[1:] != keys_all[:-1]])) if nc else np.zeros(0, np.int64)
+        end = np.append(start[1:], nc)
+        ok = np.flatnonzero((start + 1 <= np.minimum(end - 1, spec_top.TOP_MAX)) &
+                            (rows_all[start] // 1024 != rows_all[np.maximum(end - 1, 0)] // 1024)) if nc else start
+        if len(ok) == 0:
+            return spec_top.TOP_MAX, False
+        t = int(ok[rng.integers(len(ok))])
+        return int(rng.integers(start[t] + 1, min(end[t] - 1, spec_top.TOP_MAX) + 1)), True
+
+    def op_top(self):
+        """rio_gp_top_rows[_dev] against spec_top.top_rows over the model's column, loads and hits (none before the first call
+        of the hits section): rows, keys, nodes, n_candidates and key_sum exact, nothing written behind the listing, nothing
+        changed."""
+        import spec_top
+        rng, n, m, g = self.rng, self.n, self.m, self.g
+        flags = int(rng.integers(8))
+        H = self.H if self.hits_used else None
+        K = (self.H if flags & spec_top.BY_HITS else self.load)[:n]
+        A = self.ref[:n]
+        on = A[A < m]
+        count = np.bincount(on, minlength=m)
+        k = int(rng.integers(4))
+        if k == 0:
+            node = int(rng.integers(m))
+        elif k == 1:      # the node most rows are on
+            node = int(count.argmax())
+        elif k == 2:      # one that holds no row, if there is one
+            empty = np.flatnonzero(count == 0)
+            node = int(empty[rng.integers(len(empty))]) if len(empty) else int(rng.integers(m))
+        else:             # no node: refused under ON_NODE, ignored without it
+            node = int((m, m + 1, self.m0, NONE)[int(rng.integers(4))])
+        k = int(rng.choice(5, p=[0.4, 0.3, 0.1, 0.1, 0.1]))
+        top = int(K.max()) if n else 0
+        min_key = (0, int(K[rng.integers(n)]) if n else 0, top, min(top + 1, 0xFFFFFFFF), 0xFFFFFFFF)[k]
+        form = ("host", "host no node", "raw", "dev", "count", "dev count")[int(rng.integers(6))]
+        bad = (None, None, None, None, None, None, "cap", "flag")[int(rng.integers(8))]
+        if flags & spec_top.ON_NODE and node >= m:
+            bad = "node"
+        rows_all, keys_all, _, n_cand, _ = spec_top.top_rows(self.ref, self.load, H, n, flags, node, min_key, n)
+        cap, in_tie = self._top_cap(keys_all, rows_all)
+        if form in ("count", "dev count"):
+            cap = 0
+        wrows, wkeys, wnodes, wn, wsum = spec_top.top_rows(self.ref, self.load, H, n, flags, node, min_key, cap)
+        L = len(wrows)
+        assert wn == n_cand and L == min(n_cand, cap)
+        tag = (self.seed, "top", form, flags, node, min_key, cap, n, bad, self.log[-6:])
+        if bad is not None:      # cap above RIO_GP_TOP_MAX | an unknown flag bit | ON_NODE with a node >= m: refused
+            bflags = flags | (8, 16, 1 << 31)[int(rng.integers(3))] if bad == "flag" else flags
+            bcap = spec_top.TOP_MAX + 1 + int(rng.integers(0, 2)) * int(rng.integers(0, 5000)) if bad == "cap" else max(cap, 1)
+            if form in ("dev", "dev count"):
+                d = [self._devbuf()(np.full(bcap + 2, 0xDEADBEEF, np.uint32)) for _ in range(3)]
+                self._refused(lambda: g.top_rows_dev(bflags, node, min_key, d[0].ptr, d[1].ptr, d[2].ptr, bcap), tag)
+                for x in d:
+                    x.free()
+            else:
+                out = [np.full(bcap + 2, 0xDEADBEEF, np.uint32) for _ in range(3)]
+                rc, _ = g.top_rows_raw(bflags, node, min_key, out[0], out[1], out[2], bcap)
+                assert rc == self.gp.EINVAL, tag + (rc,)
+            self._read_only("top refused")
+            self.check_table("top refused")
+            return
+        self._hit("top by hits before any hits call", bool(flags & spec_top.BY_HITS) and not self.hits_used)
+        self._hit("top cut inside a tie group spanning tiles", in_tie and cap > 0)
+        self._hit("top listed all 4 096", L == spec_top.TOP_MAX)
+        self._hit("top with cap above n_candidates", cap > n_cand)
+        self._hit("top between two pages of the feed", self.page_open)
+        self._hit("top right after an expire that listed rows", self.after == "expire listed")
+        self._hit("top while a solve is uncommitted", self.pending is not None)
+        self._hit("top between tick_async and tick_wait", self.in_flight)
+        self._hit("top on a handle whose m is below max_nodes", self.m < self.m0)
+        self._hit("top at n == 0", n == 0)
+        by_hits, placed = bool(flags & spec_top.BY_HITS), bool(flags & spec_top.PLACED)
+        on_node = node if flags & spec_top.ON_NODE else None
+        nodes = key_sum = None
+        if form in ("host", "count"):
+            rows, keys, nodes, got_n, key_sum = g.top_rows(cap, by_hits, placed, on_node, min_key)
+        elif form == "host no node":
+            rows, keys, none, got_n, key_sum = g.top_rows(cap, by_hits, placed, on_node, min_key, want_node=False)
+            assert none is None, tag
+        elif form == "raw" and cap == 0:
+            rc, got_n = g.top_rows_raw(flags, node, min_key)
+            assert rc == self.gp.OK, tag + (rc,)
+            rows = keys = nodes = np.zeros(0, np.uint32)
+        elif form == "raw":       # the call as given, into sentinel-filled arrays of cap + 2, without key_sum
+            out = [np.full(cap + 2, 0xDEADBEEF, np.uint32) for _ in range(3)]
+            rc, got_n = g.top_rows_raw(flags, node, min_key, out[0], out[1], out[2], cap)
+            assert rc == self.gp.OK, tag + (rc,)
+            assert all((x[L:] == 0xDEADBEEF).all() for x in out), tag + ("written past the listing",)
+            rows, keys, nodes = (x[:L] for x in out)
+        elif cap == 0:
+            got_n, key_sum = g.top_rows_dev(flags, node, min_key, None, None, None, 0)
+            rows = keys = nodes = np.zeros(0, np.uint32)
+        else:
+            with_node = bool(rng.random() < 0.7)
+            d = [self._devbuf()(np.full(cap + 2, 0xDEADBEEF, np.uint32)) for _ in range(3)]
+            got_n, key_sum = g.top_rows_dev(flags, node, min_key, d[0].ptr, d[1].ptr, d[2].ptr if with_node else None, cap)
+            out = [x.to_host() for x in d]
+            for x in d:
+                x.free()
+            assert all((x[L:] == 0xDEADBEEF).all() for x in out), tag + ("written past the listing",)
+            assert with_node or (out[2] == 0xDEADBEEF).all(), tag + ("a node array that was not given was written",)
+            rows, keys, nodes = out[0][:L], out[1][:L], (out[2][:L] if with_node else None)
+        assert got_n == wn, tag + ("n_candidates", got_n, wn)
+        assert np.array_equal(rows, wrows) and np.array_equal(keys, wkeys), tag + (rows[:8], wrows[:8], keys[:8], wkeys[:8])
+        assert nodes is None or np.array_equal(nodes, wnodes), tag + ("nodes", nodes[:8], wnodes[:8])
+        assert key_sum is None or key_sum == wsum, tag + ("key_sum", key_sum, wsum)
+        if self.hits_used:
+            self._hits_check(tag)
+        self._read_only("top")
+        self.check_table("top")
 
     def finish_feed(self):
         """The end of an extended scenario: the rest of the feed is paged out — three small pages, then pages of a third of what
@@ -1002,26 +1382,34 @@ class Scenario:
 
     NEED_ROWS = ("update", "remove", "lookup", "place", "mixed", "attrs")                       # skipped while n == 0
     WRITERS = ("tick", "solve", "async", "update", "remove", "clean", "place", "mixed", "rebalance", "num_objects", "remap", "expire")
-    DROPS_SOLVE = ("tick", "rebalance", "update", "remove", "clean", "place", "mixed", "attrs", "caps", "num_objects", "remap", "expire")
-    MID = ("none", "index", "changes", "rebalance", "remap", "touch", "expire count", "expire")   # op_async: a call in a quiet run
-    ENDS_CHAIN = ("rebalance", "remap", "expire")    # ... after which the next tick must not chain (an "expire" un-placed a row)
+    DROPS_SOLVE = ("tick", "rebalance", "update", "remove", "clean", "place", "mixed", "attrs", "caps", "num_objects", "remap", "expire",
+                   "fold")     # (the fold rewrites loads, not the column: it drops the solve and is no writer of the feed)
+    MID = ("none", "index", "changes", "rebalance", "remap", "touch", "expire count", "expire", "hits", "top", "fold")   # op_async: a call in a quiet run
+    ENDS_CHAIN = ("rebalance", "remap", "expire", "fold")   # ... after which the next tick must not chain (an "expire" un-placed a row)
 
     OPS = (("tick", 5), ("solve", 2), ("async", 3), ("flip", 4), ("update", 2), ("remove", 2), ("lookup", 1), ("clean", 2),
            ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
 
     OPS_EXT = OPS + (("index", 3), ("rebalance", 6), ("changes", 5), ("changes_reset", 1), ("num_objects", 2), ("remap", 3),
-                     ("touch", 4), ("expire", 4))
+                     ("touch", 4), ("expire", 4), ("hits", 4), ("fold", 3), ("top", 4))
 
     def run(self):
         names = [a for a, w in (self.OPS_EXT if self.ext else self.OPS) for _ in range(w)]
         k = int(self.rng.integers(12, 31))
         try:
-            for _ in range(k):
+            for i in range(k):
                 op = names[int(self.rng.integers(len(names)))]
-                if self.ext and self.pending is not None and self.rng.random() < 0.5:
-                    # an uncommitted solve lives until the next writer: half the time the calls that must keep it, or must drop
-                    # it themselves, come right behind it (the table's weights alone bring them there a few times in 72 seeds)
-                    op = ("index", "remap", "rebalance", "remap", "touch", "expire", "expire")[int(self.rng.integers(7))]
+                if self.ext and self.chain_small and self.mids == 0 and i == k - 1:
+                    op = "async"       # (no quiet run yet: see op_async)
+                if self.ext and self.pending is not None and self.rng.random() < 0.75:
+                    # an uncommitted solve lives until the next writer: three times in four the calls that must keep it, or must drop
+                    # it themselves, come right behind it (the table's weights alone bring them there a few times in the default seeds)
+                    op = ("index", "remap", "rebalance", "remap", "touch", "expire", "expire", "hits", "top", "top", "fold", "fold",
+                          "fold")[int(self.rng.integers(13))]
+                elif self.ext and self.mark is not None and self.rng.random() < 0.3:
+                    # the report on the scratch a sweep has just used: right behind the sweep
+                    op = "top"
+                self.after, self.mark = self.mark, None
                 if self.ext and self.n == 0 and op in self.NEED_ROWS:
                     self.log.append("skipped: " + op)
                     continue
@@ -1032,12 +1420,12 @@ class Scenario:
                 if self.ext:
                     # (a sweep that listed nothing is treated as a refused remap is: it wrote nothing and drops nothing)
                     did = ((op != "mixed" or self.mixed_wrote) and (op != "remap" or not self.remap_refused) and
-                           (op != "expire" or self.expire_listed))
+                           (op != "expire" or self.expire_listed) and (op != "fold" or not self.fold_refused))
                     if op in self.WRITERS and (op not in ("remap", "expire") or did):
                         self.page_writer = True
                     if op in self.DROPS_SOLVE and did:
                         self.pending = None
-                        if had_solve and op not in ("rebalance", "remap", "expire"):    # (those three have asked already)
+                        if had_solve and op not in ("rebalance", "remap", "expire", "fold"):    # (those four have asked already)
                             self._dropped(op)
                     elif op in ("mixed", "lookup"):
                         self._read_only(op)
@@ -1045,10 +1433,12 @@ class Scenario:
             if self.ext:
                 self.finish_feed()
                 self.check_table("the end")
-                if (self.remapped or self.seen_used) and self.n < self.nmax:
-                    # the rows still hidden come back as the removals left them, with the stamps they had
+                if (self.remapped or self.seen_used or self.hits_used) and self.n < self.nmax:
+                    # the rows still hidden come back as the removals left them, with the stamps, hits and loads they had
                     self._set_n(self.nmax)
-                    self.check_table("the end, every row back")
+                    self.check_table("the end, every row back (num_objects)")
+                if self.hits_used:
+                    self._hits_check((self.seed, "the end", "hits and loads over every row", self.log[-6:]), loads=True)
             self.chained = self.g.chained_scans() if self.lab else 0
         finally:
             self.g.close()
@@ -1067,7 +1457,7 @@ def test_random_operation_sequences(gp, oracle, seed):
     Scenario(gp, oracle, seed).run()
 
 
-EXT_SEEDS = int(os.environ.get("RIO_FUZZ_EXT_SEEDS", "72"))
+EXT_SEEDS = int(os.environ.get("RIO_FUZZ_EXT_SEEDS", "96"))
 
 
 @pytest.mark.parametrize("seed", range(EXT_SEEDS))
