@@ -221,6 +221,35 @@ int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64
                   const char* const** struct_names, const size_t** struct_name_lens, const char* const** object_ids,
                   const size_t** object_id_lens, const char* const** addresses);
 
+/* Per-type idle limits and a census by type (the dense layer's object classes, DESIGN.md section 2 rule 12).  A key is
+ * ObjectId(struct_name, object_id) (object_placement/mod.rs:23-24); the layer numbers the struct_names it interns: the first
+ * distinct one is class 0, the next class 1, ... up to 254; every further type shares class RIO_OP_CLASS_OTHER.  Names are bytes
+ * with a length (a NUL is legal).  The table of types never shrinks.  A key's type is the struct_name it was FIRST interned
+ * with (the one rio_op_snapshot reports: ("a.b", "c") and ("a", "b.c") are one key); a row the table hands to a new key takes
+ * that key's class.  The device learns the classes lazily: each of the two calls below uploads what changed since the last
+ * upload (a range for new rows, a scatter for rows that changed hands), under the locks rio_op_expire takes.
+ *   - rio_op_set_type_idle_limit_n: keys of this type are idle after max_idle epochs without a stamp; RIO_OP_IDLE_NEVER: never.
+ *     A type never seen before gets its class by this call.  A type that lands in RIO_OP_CLASS_OTHER: RIO_GP_ERANGE, nothing
+ *     is set.
+ *   - rio_op_expire_by_type: rio_op_expire with a cutoff per type.  A type's limit L is its own, or default_max_idle without
+ *     one (RIO_OP_CLASS_OTHER always uses the default); its cutoff is now > L ? now - L : 0, so a key is idle iff stamp + L < now,
+ *     without wrap-around, and RIO_OP_IDLE_NEVER (or now <= L) finds nothing.  Stamping, locking, the host shadow's correction,
+ *     the listing and its ownership are rio_op_expire's.  A dense layer without the class calls: RIO_GP_EUPSTREAM, nothing
+ *     changed.
+ *   - rio_op_census: the placed keys and their load by type: one entry per non-empty class in class order; with by_server one
+ *     entry per non-empty (server, class) cell, servers in node order, classes in order within a server.  struct_names[k] is
+ *     NULL for RIO_OP_CLASS_OTHER, addresses[k] NULL without by_server.  Read-only on the device; it stamps nothing, counts no
+ *     request and leaves the host shadow alone.  The five arrays are owned by the calling thread until its next call of this
+ *     function.  RIO_GP_EUPSTREAM as above. */
+#define RIO_OP_CLASS_OTHER 255u
+#define RIO_OP_IDLE_NEVER 0xFFFFFFFFu
+int rio_op_set_type_idle_limit_n(rio_op_t* p, const char* struct_name, size_t len, uint32_t max_idle);
+int rio_op_expire_by_type(rio_op_t* p, uint32_t now, uint32_t default_max_idle, uint64_t max_objects_out, uint64_t* n_out,
+                          uint64_t* n_idle, const char* const** struct_names, const size_t** struct_name_lens,
+                          const char* const** object_ids, const size_t** object_id_lens, const char* const** addresses);
+int rio_op_census(rio_op_t* p, int by_server, uint64_t* n_out, const char* const** struct_names, const size_t** struct_name_lens,
+                  const char* const** addresses, const uint64_t** rows, const uint64_t** loads);
+
 /* Measured load (rio_gp_hits_merge + rio_gp_load_fold, DESIGN.md section 2 rule 10).  The reference's ObjectPlacementItem
  * (object_placement/mod.rs:23-24) carries no load and local.rs keeps none: load is this library's extension, and every key has
  * load 1 until rio_op_set_object_load says otherwise — one host call per key.  Tracking measures it instead.

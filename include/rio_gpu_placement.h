@@ -505,6 +505,63 @@ int rio_gp_top_rows(rio_gp_t* h, uint32_t flags, uint32_t node, uint32_t min_key
 int rio_gp_top_rows_dev(rio_gp_t* h, uint32_t flags, uint32_t node, uint32_t min_key, uint32_t* d_rows, uint32_t* d_key,
                         uint32_t* d_node /* may be NULL */, uint64_t cap, uint64_t* n_candidates, uint64_t* key_sum /* may be NULL */);
 
+/* ---- object classes: per-class idle limits and a census by class ------------------------------ */
+
+/* Every object of the reference has a type: its key is ObjectId(struct_name, object_id) (rio-rs/src/object_placement/mod.rs:23-24
+ * keeps both in ObjectPlacementItem), and the SQL backends store struct_name in a column of its own.  The handle keeps a class
+ * column K, one uint8_t per row of max_objects: the caller's number for the row's type, 0 to begin with.  K names no node and is
+ * written by the class setters only: ticks, the CRUD calls, rio_gp_place_pending, rio_gp_set_objects, rio_gp_set_num_objects,
+ * rio_gp_remap_nodes, the rebalance, rio_gp_expire and the load calls leave it alone.  DESIGN.md section 2 rule 12 (frozen;
+ * tests/spec_classes.py restates it):
+ *   - rio_gp_set_classes: K[first_row + k] = cls[k] for k < rows.  first_row + rows <= n, else RIO_GP_EINVAL and nothing changes.
+ *     Any alignment of first_row, rows and the pointer; no byte outside the range changes.
+ *   - rio_gp_set_class_batch: K[idx[k]] = cls[k], processed as if in batch order: of several entries for one row the LAST
+ *     wins (the election of rio_gp_update_batch).  The host form validates first (an idx[k] >= n is RIO_GP_EINVAL, nothing
+ *     changes); the _dev form skips invalid entries and reports RIO_GP_EINVAL, as rio_gp_touch_batch_dev does.
+ *   - rio_gp_get_classes: K[0 .. n-1]; n must be the row count, as for rio_gp_get_seen.
+ *   - The class setters are no inputs of any solve: `used`, an uncommitted rio_gp_solve and the quiet and chained tick state stay
+ *     as they were.  They order themselves on the handle's stream; rio_gp_set_classes_dev does not wait.
+ *
+ * rio_gp_expire_classes: rio_gp_expire with a cutoff per class.  Row r < n is IDLE iff A[r] != RIO_GP_NONE and K[r] < n_classes
+ * and S[r] < cutoffs[K[r]] (S: the last-seen column of the touch calls).  A row whose class is >= n_classes is never idle; a
+ * cutoff of 0 finds nothing in its class.  cutoffs is a HOST array of n_classes entries in both forms, 1 <= n_classes <=
+ * RIO_GP_MAX_CLASSES (else RIO_GP_EINVAL).  Everything else is rio_gp_expire's contract: the listing (ascending rows, paged by
+ * cap, never RIO_GP_ERANGE), *n_idle (every idle row, listed or not), the count-only form (no arrays, cap 0: nothing changes
+ * at all), *load_freed, the un-placing as rio_gp_remove_batch would do it (row lifecycle, `used`), the order behind
+ * rio_gp_tick_async work in flight, the uncommitted solve dropped only when a row was listed, the change feed, the refusal on a
+ * handle of the row-sharded solve.  idle_by_class (host, n_classes entries, may be NULL): [c] = every idle row of class c,
+ * listed or not.  On a handle whose classes are all 0, rio_gp_expire_classes(1, {cutoff}) is rio_gp_expire(cutoff).
+ *
+ * rio_gp_census: the placed rows by class.  A = the column rio_gp_get_assign returns at the point of the call.  For every
+ * r < n with A[r] != RIO_GP_NONE (raw values; affinity and lifecycle state are not consulted):
+ *   - K[r] >= n_classes: the row is counted in *n_other only;
+ *   - otherwise out_rows[K[r]] += 1 and out_load[K[r]] += load[r]; the arrays hold n_classes entries;
+ *   - under RIO_GP_CENSUS_BY_NODE the arrays are [m][n_classes], node-major, the row lands in cell (A[r], K[r]), and a placed
+ *     row whose node id is >= m is counted in *n_other only.  m * n_classes <= 2^20, else RIO_GP_EINVAL.
+ *   - RIO_GP_EINVAL: an unknown flag, n_classes outside 1 .. RIO_GP_MAX_CLASSES, a NULL among out_rows / out_load / n_other, a
+ *     handle of the row-sharded solve.
+ *   - Read-only: the table, `used`, K, an uncommitted rio_gp_solve (it stays committable) and the quiet and chained tick state
+ *     are as they were.  Like rio_gp_changes it orders itself behind rio_gp_tick_async work in flight.
+ *   - The _dev form takes the two arrays in device memory (n_other stays a host word); both forms wait once.
+ *   - Memory: K takes 1 B per row of max_objects, allocated (zero-filled) by the first call of this section and kept until
+ *     rio_gp_destroy, plus 3 KiB of tables; the host-pointer census stages its cells in device memory (16 B per cell).  A handle
+ *     that calls none of them pays nothing.
+ *   - Cost: the sweep's count pass streams A, S and K (9 B per row); the census streams A, K and load (9 B per row), once
+ *     for up to 4 096 cells and beyond 65 536, once per 4 096 cells in between. */
+#define RIO_GP_MAX_CLASSES 256u
+#define RIO_GP_CENSUS_BY_NODE 1u /* cells (node, class) instead of (class) */
+int rio_gp_set_classes(rio_gp_t* h, uint64_t first_row, uint64_t rows, const uint8_t* cls);
+int rio_gp_set_classes_dev(rio_gp_t* h, uint64_t first_row, uint64_t rows, const uint8_t* d_cls);
+int rio_gp_set_class_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint8_t* cls);
+int rio_gp_set_class_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, const uint8_t* d_cls);
+int rio_gp_get_classes(rio_gp_t* h, uint64_t n, uint8_t* out);
+int rio_gp_expire_classes(rio_gp_t* h, uint32_t n_classes, const uint32_t* cutoffs, uint32_t* out_rows, uint32_t* out_node,
+                          uint64_t cap, uint64_t* n_idle, uint64_t* load_freed, uint64_t* idle_by_class /* may be NULL */);
+int rio_gp_expire_classes_dev(rio_gp_t* h, uint32_t n_classes, const uint32_t* cutoffs, uint32_t* d_rows, uint32_t* d_node,
+                              uint64_t cap, uint64_t* n_idle, uint64_t* load_freed, uint64_t* idle_by_class /* may be NULL */);
+int rio_gp_census(rio_gp_t* h, uint32_t flags, uint32_t n_classes, uint64_t* out_rows, uint64_t* out_load, uint64_t* n_other);
+int rio_gp_census_dev(rio_gp_t* h, uint32_t flags, uint32_t n_classes, uint64_t* d_rows, uint64_t* d_load, uint64_t* n_other);
+
 /* ---- the placement policy, batched ------------------------------------------------------ */
 
 /* Service::get_or_create_placement + check_address_mismatch (service.rs:193-298) for a batch

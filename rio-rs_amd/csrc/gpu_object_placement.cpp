@@ -77,6 +77,15 @@ extern "C" int rio_gp_load_fold(rio_gp_t* h, uint32_t keep, uint32_t gain, uint3
 extern "C" int rio_gp_top_rows(rio_gp_t* h, uint32_t flags, uint32_t node, uint32_t min_key, uint32_t* out_rows, uint32_t* out_key,
                                uint32_t* out_node, uint64_t cap, uint64_t* n_candidates, uint64_t* key_sum) __attribute__((weak));
 
+// Weak for the same reason: object classes (rio_op_expire_by_type and rio_op_census report RIO_GP_EUPSTREAM without them).
+extern "C" int rio_gp_set_classes(rio_gp_t* h, uint64_t first_row, uint64_t rows, const uint8_t* cls) __attribute__((weak));
+extern "C" int rio_gp_set_class_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint8_t* cls) __attribute__((weak));
+extern "C" int rio_gp_expire_classes(rio_gp_t* h, uint32_t n_classes, const uint32_t* cutoffs, uint32_t* out_rows,
+                                     uint32_t* out_node, uint64_t cap, uint64_t* n_idle, uint64_t* load_freed,
+                                     uint64_t* idle_by_class) __attribute__((weak));
+extern "C" int rio_gp_census(rio_gp_t* h, uint32_t flags, uint32_t n_classes, uint64_t* out_rows, uint64_t* out_load,
+                             uint64_t* n_other) __attribute__((weak));
+
 namespace {
 
 // one spin-wait step that tells the core (and its sibling thread) that this is one
@@ -414,6 +423,18 @@ struct State {
     std::vector<uint8_t> row_keep;                    // key created by rio_op_set_object_load and not used since: its load is
                                                       // what the caller set, so reclaim() must not recycle (and reset) the row
     std::vector<uint32_t> free_rows;                  // reclaimed rows, ready for new keys
+    // object classes: the first distinct struct_name interned is class 0, the next 1, ... up to 254; every further one shares
+    // RIO_OP_CLASS_OTHER and is not remembered.  The table never shrinks (a deque: the strings never move, rio_op_census hands
+    // out pointers into them).  A row's class is that of row_key[row].first, set when the row is handed to a key.
+    std::unordered_map<std::string, uint8_t> type_id;
+    std::deque<std::string> type_name;
+    std::vector<uint32_t> type_limit;                 // rio_op_set_type_idle_limit_n, per type id
+    std::vector<uint8_t> type_has_limit;
+    std::vector<uint8_t> row_class;                   // row -> class
+    // (written under imu exclusive, read by the uploads under mu + imu exclusive) what the device's class column holds: rows
+    // [0, cls_uploaded) as of the last upload, except the rows in cls_dirty, which were handed to a key of another class since
+    uint64_t cls_uploaded = 0;
+    std::vector<uint32_t> cls_dirty;
     std::atomic<uint64_t> hi_rows{0};                 // rows ever handed out: every row id is < hi_rows (atomic: sync_device looks
                                                       // at it and at the two versions below without the table lock)
     std::unordered_map<std::string, uint32_t> nodes;  // address -> node id
@@ -610,6 +631,19 @@ int intern_node(State* s, const std::string& addr, bool create, uint32_t* out, b
     return RIO_GP_OK;
 }
 
+// the class of a struct_name, giving it the next id when it is new and one is left (imu held exclusively)
+uint8_t intern_type(State* s, const std::string& ty) {
+    auto it = s->type_id.find(ty);
+    if (it != s->type_id.end()) return it->second;
+    if (s->type_name.size() >= RIO_OP_CLASS_OTHER) return RIO_OP_CLASS_OTHER;
+    const uint8_t c = (uint8_t)s->type_name.size();
+    s->type_name.push_back(ty);
+    s->type_limit.push_back(0);
+    s->type_has_limit.push_back(0);
+    s->type_id.emplace(ty, c);
+    return c;
+}
+
 // find or create the row of a key (imu held).  kFull: no free row — the caller releases its locks, runs reclaim() and retries.
 // use: the call makes (or unmakes) an object of the key — update, get_or_create_placement, remove; a key whose row is
 // held for a load set ahead of its first use (row_keep) is an ordinary key from then on
@@ -638,11 +672,17 @@ int intern_row(State* s, const Part& ty, const Part& id, bool create, uint32_t* 
         s->row_key.emplace_back();
         s->row_live.push_back(0);
         s->row_keep.push_back(0);
+        s->row_class.push_back(0);
     } else {
         return kFull;
     }
     s->rows.emplace(key, row);
     s->row_key[row] = std::make_pair(ty.str(), id.str());
+    const uint8_t cls = intern_type(s, s->row_key[row].first);
+    if (cls != s->row_class[row]) {
+        s->row_class[row] = cls;
+        if (row < s->cls_uploaded) s->cls_dirty.push_back(row);  // (a reclaimed row: the device still holds its old key's class)
+    }
     s->row_live[row] = 1;
     s->row_keep[row] = use ? 0 : 1;  // created without a use: rio_op_set_object_load ahead of the first update / request
     *out = row;
@@ -1733,9 +1773,32 @@ int rio_op_set_clock(rio_op_t* p, uint32_t now) {
     return RIO_GP_OK;
 }
 
-int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64_t* n_out, uint64_t* n_idle,
-                  const char* const** struct_names, const size_t** struct_name_lens, const char* const** object_ids,
-                  const size_t** object_id_lens, const char* const** addresses) {
+// The device's class column follows the host's: a range for the rows handed out since the last upload, a scatter for the rows
+// that changed hands to a key of another class (mu + imu exclusive held, sync_device done: the device knows hi_rows rows).
+static int sync_classes(State* s) {
+    const uint64_t n = s->hi_rows;
+    int rc;
+    if (n > s->cls_uploaded) {
+        if ((rc = rio_gp_set_classes(s->gp, s->cls_uploaded, n - s->cls_uploaded, s->row_class.data() + s->cls_uploaded)))
+            return gp_fail(s, rc);
+        s->cls_uploaded = n;
+    }
+    if (!s->cls_dirty.empty()) {
+        std::vector<uint8_t> cls(s->cls_dirty.size());
+        for (size_t k = 0; k < cls.size(); ++k) cls[k] = s->row_class[s->cls_dirty[k]];  // (the row's class now: duplicates agree)
+        if ((rc = rio_gp_set_class_batch(s->gp, cls.size(), s->cls_dirty.data(), cls.data()))) return gp_fail(s, rc);
+        s->cls_dirty.clear();
+    }
+    return RIO_GP_OK;
+}
+
+// rio_op_expire and rio_op_expire_by_type: `sweep(rows, node, cap, &idle)` is the dense call, `ready()` what it needs on the
+// device first (it answers RIO_GP_EUPSTREAM before anything changes on a dense layer without the calls).
+extern "C++" {
+template <class Ready, class Sweep>
+static int expire_impl(rio_op_t* p, uint64_t max_objects_out, uint64_t* n_out, uint64_t* n_idle, const char* const** struct_names,
+                       const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens,
+                       const char* const** addresses, Ready&& ready, Sweep&& sweep) {
     if (!p || !n_out || !struct_names || !struct_name_lens || !object_ids || !object_id_lens || !addresses) return RIO_GP_EINVAL;
     State* s = p->s;
     t_ex.clear();
@@ -1748,18 +1811,18 @@ int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64
         std::lock_guard<TableLock> gi(s->imu);
         int rc;
         if ((rc = sync_device(s, true))) return rc;
-        if (!rio_gp_touch_merge || !rio_gp_expire) return fail(RIO_GP_EUPSTREAM, "dense layer has no idle expiry");
+        if ((rc = ready(s))) return rc;
         const uint64_t n = s->hi_rows;
         if (s->seen.gather(n, t_ex_stamps) && (rc = rio_gp_touch_merge(s->gp, n, t_ex_stamps.data()))) return gp_fail(s, rc);
         const uint64_t cap = std::min<uint64_t>(max_objects_out, n);  // a listed row is a row that is handed out
         uint64_t idle = 0;
         if (!cap) {  // count only: nothing changes
-            if ((rc = rio_gp_expire(s->gp, cutoff, nullptr, nullptr, 0, &idle, nullptr))) return gp_fail(s, rc);
+            if ((rc = sweep(s, nullptr, nullptr, 0, &idle))) return gp_fail(s, rc);
             if (n_idle) *n_idle = idle;
         } else {
             std::vector<uint32_t> &rows = t_ex.rows, &node = t_ex.c1;
             rows.resize(cap); node.resize(cap);
-            if ((rc = rio_gp_expire(s->gp, cutoff, rows.data(), node.data(), cap, &idle, nullptr))) {
+            if ((rc = sweep(s, rows.data(), node.data(), cap, &idle))) {
                 s->shadow.invalidate_all();  // (nobody can tell which rows it un-placed before it failed)
                 return gp_fail(s, rc);
             }
@@ -1773,6 +1836,104 @@ int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64
         }
     }
     t_ex.publish(n_out, struct_names, struct_name_lens, object_ids, object_id_lens, addresses);
+    return RIO_GP_OK;
+}
+}  // extern "C++"
+
+int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64_t* n_out, uint64_t* n_idle,
+                  const char* const** struct_names, const size_t** struct_name_lens, const char* const** object_ids,
+                  const size_t** object_id_lens, const char* const** addresses) {
+    return expire_impl(
+        p, max_objects_out, n_out, n_idle, struct_names, struct_name_lens, object_ids, object_id_lens, addresses,
+        [](State*) { return !rio_gp_touch_merge || !rio_gp_expire ? fail(RIO_GP_EUPSTREAM, "dense layer has no idle expiry") : RIO_GP_OK; },
+        [&](State* s, uint32_t* rows, uint32_t* node, uint64_t cap, uint64_t* idle) {
+            return rio_gp_expire(s->gp, cutoff, rows, node, cap, idle, nullptr);
+        });
+}
+
+static bool has_classes() { return rio_gp_touch_merge && rio_gp_set_classes && rio_gp_set_class_batch && rio_gp_expire_classes && rio_gp_census; }
+
+int rio_op_set_type_idle_limit_n(rio_op_t* p, const char* struct_name, size_t len, uint32_t max_idle) {
+    if (!p || (!struct_name && len)) return RIO_GP_EINVAL;
+    State* s = p->s;
+    std::lock_guard<TableLock> gi(s->imu);
+    const uint8_t c = intern_type(s, std::string(struct_name ? struct_name : "", len));
+    if (c == RIO_OP_CLASS_OTHER) return fail(RIO_GP_ERANGE, "rio_op_set_type_idle_limit_n: the type shares RIO_OP_CLASS_OTHER, which has no limit of its own");
+    s->type_limit[c] = max_idle;
+    s->type_has_limit[c] = 1;
+    return RIO_GP_OK;
+}
+
+int rio_op_expire_by_type(rio_op_t* p, uint32_t now, uint32_t default_max_idle, uint64_t max_objects_out, uint64_t* n_out,
+                          uint64_t* n_idle, const char* const** struct_names, const size_t** struct_name_lens,
+                          const char* const** object_ids, const size_t** object_id_lens, const char* const** addresses) {
+    uint32_t cutoffs[RIO_GP_MAX_CLASSES];
+    return expire_impl(
+        p, max_objects_out, n_out, n_idle, struct_names, struct_name_lens, object_ids, object_id_lens, addresses,
+        [&](State* s) {
+            if (!has_classes()) return fail(RIO_GP_EUPSTREAM, "dense layer has no object classes");
+            // a key is idle iff stamp + L < now, without wrap-around: cutoff = now - L where that is positive, else 0 (nothing);
+            // RIO_OP_IDLE_NEVER >= every now.  Types seen later than this call are not idle by it: they have the default too.
+            for (uint32_t c = 0; c < RIO_GP_MAX_CLASSES; ++c) {
+                const uint32_t L = c < s->type_has_limit.size() && s->type_has_limit[c] ? s->type_limit[c] : default_max_idle;
+                cutoffs[c] = now > L ? now - L : 0u;
+            }
+            return sync_classes(s);
+        },
+        [&](State* s, uint32_t* rows, uint32_t* node, uint64_t cap, uint64_t* idle) {
+            return rio_gp_expire_classes(s->gp, RIO_GP_MAX_CLASSES, cutoffs, rows, node, cap, idle, nullptr, nullptr);
+        });
+}
+
+// rio_op_census's listing: the calling thread's until its next call
+struct CensusListing {
+    std::vector<const char*> names, addrs;
+    std::vector<size_t> lens;
+    std::vector<uint64_t> rows, loads, cell_rows, cell_loads;
+};
+static thread_local CensusListing t_census;
+
+int rio_op_census(rio_op_t* p, int by_server, uint64_t* n_out, const char* const** struct_names, const size_t** struct_name_lens,
+                  const char* const** addresses, const uint64_t** rows, const uint64_t** loads) {
+    if (!p || !n_out || !struct_names || !struct_name_lens || !addresses || !rows || !loads) return RIO_GP_EINVAL;
+    State* s = p->s;
+    CensusListing& t = t_census;
+    t.names.clear(); t.addrs.clear(); t.lens.clear(); t.rows.clear(); t.loads.clear();
+    *n_out = 0;
+    {
+        // the locks of rio_op_expire: the class upload changes what the layer knows about the device
+        DevLock g(s);
+        std::lock_guard<TableLock> gi(s->imu);
+        int rc;
+        if ((rc = sync_device(s, true))) return rc;
+        if (!has_classes()) return fail(RIO_GP_EUPSTREAM, "dense layer has no object classes");
+        if ((rc = sync_classes(s))) return rc;
+        const uint32_t m = by_server ? (uint32_t)s->node_addr.size() : 1u;
+        const uint32_t dm = by_server ? s->pushed_nodes : 1u;  // (the device's node count: the cells it writes)
+        t.cell_rows.assign((size_t)std::max(m, dm) * RIO_GP_MAX_CLASSES + 1, 0);
+        t.cell_loads.assign((size_t)std::max(m, dm) * RIO_GP_MAX_CLASSES + 1, 0);
+        uint64_t other = 0;
+        if ((rc = rio_gp_census(s->gp, by_server ? RIO_GP_CENSUS_BY_NODE : 0u, RIO_GP_MAX_CLASSES, t.cell_rows.data(),
+                                t.cell_loads.data(), &other)))
+            return gp_fail(s, rc);
+        for (uint32_t j = 0; j < std::min(m, dm); ++j)
+            for (uint32_t c = 0; c < RIO_GP_MAX_CLASSES; ++c) {
+                const size_t cell = (size_t)j * RIO_GP_MAX_CLASSES + c;
+                if (!t.cell_rows[cell]) continue;
+                const bool named = c < s->type_name.size();
+                t.names.push_back(named ? s->type_name[c].data() : nullptr);
+                t.lens.push_back(named ? s->type_name[c].size() : 0);
+                t.addrs.push_back(by_server ? addr_of(s, j) : nullptr);
+                t.rows.push_back(t.cell_rows[cell]);
+                t.loads.push_back(t.cell_loads[cell]);
+            }
+    }
+    *n_out = t.rows.size();
+    *struct_names = t.names.data();
+    *struct_name_lens = t.lens.data();
+    *addresses = t.addrs.data();
+    *rows = t.rows.data();
+    *loads = t.loads.data();
     return RIO_GP_OK;
 }
 

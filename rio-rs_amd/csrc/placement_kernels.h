@@ -604,4 +604,30 @@ static_assert(kTopZeroWords * sizeof(u32) == offsetof(TopScratch, pairs), "TopSc
 void launch_top_rows(const u32* K, const u32* A, u64 n, u32 min_key, u32 filt, u32 node, u32 cap, TopScratch* sc, u32* cnt,
                      u32* gsum, u32* rows, u32* key, u32* nodes, hipStream_t s);
 
+// --- object classes (rio_gp_set_class*, rio_gp_expire_classes, rio_gp_census): a class column K, one byte per row ---
+constexpr u32 kClsMax = 256;           // = RIO_GP_MAX_CLASSES: the cutoff table and the per-class histogram, 1 KiB of LDS each
+constexpr u32 kClsSlots = 32;          // copies of the sweep's per-class counts the workgroups of k_expc_count spread their adds over
+constexpr u32 kCensusLdsCells = 4096;  // cells one workgroup of k_census accumulates in LDS (12 B a cell: 48 KiB): one slice
+constexpr u32 kCensusMaxSlices = 16;   // slices (passes over the columns) up to which the census stays in LDS; beyond: global adds
+struct ClsCutoffs {
+    u32 v[kClsMax];  // cutoff per class, 0 from n_classes on (a kernel argument: 1 KiB)
+};
+// K[idx[k]] = cls[k] for k < n, the last entry of a row wins; entries >= n_obj are skipped and counted in st->err.  pos: the
+// handle's all-ones position scratch (launch_update's), all-ones again afterwards.  n < 2^32 - 1.
+void launch_set_class_batch(unsigned char* K, u64 n_obj, const u32* idx, const unsigned char* cls, u64 n, u32* pos, DevStats* st,
+                            hipStream_t s);
+// launch_exp_count / launch_exp_apply with the idle predicate A[r] != kNone && S[r] < cutoffs.v[K[r]].  by_class: kClsSlots *
+// kClsMax u64 of device memory, zero between the calls (the caller zeroes them once); host_by_class: kClsMax u64 of mapped pinned
+// memory = the idle rows of every class when the stream has run
+void launch_expc_count(const u32* A, const u32* S, const unsigned char* K, const ChgPlan& p, const ClsCutoffs& cutoffs, u32* cnt,
+                       u32* gsum, u32* total, u64* by_class, u64* host_by_class, u64* freed, hipStream_t s);
+void launch_expc_apply(u32* A, const u32* S, const unsigned char* K, const ChgPlan& p, const ClsCutoffs& cutoffs, const u32* cnt, const u32* gsum, u64 cap, u32* rows, u32* node, u32* aff_life, const u32* load, u32 m,
+                       u64* used, u64* freed, hipStream_t s);
+// The placed rows r < n by class (by_node: by (A[r], K[r]), node-major): out_rows / out_load: (by_node ? m : 1) * n_classes u64
+// each, *other = the placed rows with K[r] >= n_classes (by_node: or A[r] >= m); all three in device memory, zeroed here.
+// Up to kCensusMaxSlices * kCensusLdsCells cells: LDS accumulators per workgroup, one pass over the columns per slice of
+// kCensusLdsCells cells; beyond: one pass, global adds per row.
+void launch_census(const u32* A, const unsigned char* K, const u32* load, u64 n, u32 m, u32 n_classes, bool by_node,
+                   u64* out_rows, u64* out_load, u64* other, hipStream_t s);
+
 }  // namespace riogp

@@ -8052,4 +8052,275 @@ void launch_top_rows(const u32* K, const u32* A, u64 n, u32 min_key, u32 filt, u
     hipLaunchKernelGGL(k_top_sort, dim3(1), dim3(1024), 0, s, sc, A, n, cap, rows, key, nodes);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Object classes (rio_gp_set_class*, rio_gp_expire_classes, rio_gp_census; DESIGN.md section 2 rule 12): a class column K, one
+// byte per row, padded and zero-filled like the other columns.  One dword of K holds the classes of the quad of rows a lane
+// handles in a step of a tile (Kw = K read as u32: byte j of Kw[i0 / 4] = K[i0 + j]).
+//   k_cls_elect / k_cls_apply   the scatter K[idx[k]] = cls[k] with sequential last-writer-wins: k_update_elect's election
+//                 in the handle's all-ones position scratch, then the winner stores its byte and puts the slot back.  Rows
+//                 share dwords of K but never bytes: a byte store needs no care for its neighbours.
+//   k_expc_count  k_exp_count with the cutoff looked up per row: the table of 256 cutoffs arrives as a kernel argument and
+//                 sits in LDS (0 from n_classes on: S < 0 never holds, so a row of such a class is never idle), and every idle
+//                 row is counted into a per-class LDS histogram that the workgroup adds once, non-zero words only, to one of
+//                 kClsSlots copies of the per-class counts (a thousand workgroups adding to the same eight words wait for each
+//                 other: rio_gp_count_placed shows what that costs).
+//   k_cls_publish one workgroup behind the count pass: the sum of the copies into mapped pinned memory, and the copies back to
+//                 zero for the next call (they are zero at rest: no fill in front of the count pass; a call that fails where
+//                 nobody can tell whether this launch ran has the host fill them before the next one).
+//   k_expc_apply  k_exp_apply over the same predicate.
+//   k_census      a streaming pass over A, K and load, four rows per lane: a placed row adds (1, load) to its cell.  LDSACC:
+//                 the cells [blockIdx.y * kCensusLdsCells, + kCensusLdsCells) are workgroup-private LDS accumulators (u32
+//                 rows, u64 load), flushed once as global adds of the non-zero words; a grid of several slices reads the
+//                 columns once per slice.  Otherwise every row adds to the global cells itself.  The sums are integers: the
+//                 order of the additions does not show.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_cls_elect(u64 n_obj, const u32* __restrict__ idx, u64 n, u32* __restrict__ pos,
+                                                   DevStats* st) {
+    u32 bad = 0;
+    for (u64 k = (u64)blockIdx.x * 256 + threadIdx.x; k < n; k += (u64)gridDim.x * 256) {
+        const u32 i = idx[k];
+        if (i < n_obj) atomicMin(&pos[i], (u32)(n - 1 - k));
+        else ++bad;
+    }
+    if (bad) atomicAdd(&st->err, (u64)bad);
+}
+__global__ __launch_bounds__(256) void k_cls_apply(unsigned char* __restrict__ K, u64 n_obj, const u32* __restrict__ idx,
+                                                   const unsigned char* __restrict__ cls, u64 n, u32* __restrict__ pos) {
+    for (u64 k = (u64)blockIdx.x * 256 + threadIdx.x; k < n; k += (u64)gridDim.x * 256) {
+        const u32 i = idx[k];
+        if (i < n_obj && pos[i] == (u32)(n - 1 - k)) {  // (one winner per row: it alone writes the byte and resets the slot)
+            K[i] = cls[k];
+            pos[i] = kNone;
+        }
+    }
+}
+
+static_assert(kClsMax == kChgWaves * 64, "the class tables are set up and flushed one entry per thread");
+// bit j: row i0 + j is idle by its class's cutoff (rows >= n never are); kw = the quad's classes, ct = the LDS cutoff table
+__device__ __forceinline__ u32 expc_flags(const uint4& a, const uint4& s, u32 kw, const u32* ct, u64 i0, u64 n) {
+    return (u32)(i0 < n && a.x != kNone && s.x < ct[kw & 255u]) | ((u32)(i0 + 1 < n && a.y != kNone && s.y < ct[(kw >> 8) & 255u]) << 1) |
+           ((u32)(i0 + 2 < n && a.z != kNone && s.z < ct[(kw >> 16) & 255u]) << 2) |
+           ((u32)(i0 + 3 < n && a.w != kNone && s.w < ct[kw >> 24]) << 3);
+}
+
+__global__ __launch_bounds__(kChgWaves * 64, 8) void k_expc_count(const u32* __restrict__ A, const u32* __restrict__ S,
+                                                                const u32* __restrict__ Kw, const ChgPlan p,
+                                                                const ClsCutoffs cutoffs, u32* __restrict__ cnt,
+                                                                u32* __restrict__ gsum, u64* __restrict__ by_class,
+                                                                u64* __restrict__ freed) {
+    __shared__ u32 ct[kClsMax], hist[kClsMax];
+    ct[threadIdx.x] = cutoffs.v[threadIdx.x];
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    oc_count(p, cnt, gsum, [&](u64 lo, u32 lane) {
+        uint4 a[4], sv[4];
+        chg_load(A, S, lo, lane, a, sv);
+        u32 c = 0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const u64 i0 = lo + (u64)s * 256 + lane * 4;
+            const u32 kw = Kw[i0 >> 2];
+            const u32 f = expc_flags(a[s], sv[s], kw, ct, i0, p.n);
+            c += __builtin_popcount(f);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if ((f >> j) & 1u) atomicAdd(&hist[(kw >> (8 * j)) & 255u], 1u);
+        }
+        return c;
+    });
+    // (oc_count ends behind a __syncthreads(): every wave's histogram adds are in)
+    if (hist[threadIdx.x]) atomicAdd(&by_class[(blockIdx.x % kClsSlots) * kClsMax + threadIdx.x], (u64)hist[threadIdx.x]);
+    if (threadIdx.x == 0 && blockIdx.x == 0) *freed = 0;  // (k_expc_apply, a later launch, adds into it)
+}
+
+__global__ __launch_bounds__(kClsMax) void k_cls_publish(u64* __restrict__ by_class, u64* __restrict__ host_out) {
+    u64 sum = 0;
+    for (u32 q = 0; q < kClsSlots; ++q) {
+        sum += by_class[q * kClsMax + threadIdx.x];
+        by_class[q * kClsMax + threadIdx.x] = 0;
+    }
+    host_out[threadIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(kChgWaves * 64, 8) void k_expc_apply(u32* __restrict__ A, const u32* __restrict__ S,
+                                                                const u32* __restrict__ Kw, const ChgPlan p,
+                                                                const ClsCutoffs cutoffs, const u32* __restrict__ cnt,
+                                                                const u32* __restrict__ gsum,
+                                                                u64 cap, u32* __restrict__ rows, u32* __restrict__ node,
+                                                                u32* __restrict__ aff_life, const u32* __restrict__ load, u32 m,
+                                                                u64* __restrict__ used, u32 hist, u64* __restrict__ freed) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64* rel = reinterpret_cast<u64*>(smem);  // [m] load released per node (hist only)
+    __shared__ u32 toff[kChgMaxTpg];
+    __shared__ u32 ct[kClsMax];
+    __shared__ u32 lds[4];
+    __shared__ u64 gfree;
+    const OcTiles<u64> tl = oc_tile_offsets(p, cnt, gsum, cap, toff, lds);
+    if (!tl.go) return;
+    ct[threadIdx.x] = cutoffs.v[threadIdx.x];
+    if (hist)
+        for (u32 j = threadIdx.x; j < m; j += kChgWaves * 64) rel[j] = 0;
+    if (threadIdx.x == 0) gfree = 0;
+    __syncthreads();
+    u64 fr = 0;
+    oc_rank(
+        p, tl, toff, cap,
+        [&](u64 lo, u32 lane) {
+            // (a step at a time: this pass re-reads only the tiles that hold a listed row, and a whole tile of A and S next to
+            //  the table look-ups spilled to scratch at eight waves per SIMD)
+            u32 fl = 0;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const u64 i0 = lo + (u64)s * 256 + lane * 4;
+                const uint4 a = *reinterpret_cast<const uint4*>(A + i0), sv = *reinterpret_cast<const uint4*>(S + i0);
+                fl |= expc_flags(a, sv, Kw[i0 >> 2], ct, i0, p.n) << (4 * s);
+            }
+            return fl;
+        },
+        [&](int, u64 i0, u32 f, u64 r, u64 limit) {  // (k_exp_apply's body: the class decides who is idle, not what happens then)
+            const uint4 q = *reinterpret_cast<const uint4*>(A + i0);
+            u32 av[4] = {q.x, q.y, q.z, q.w};
+            bool listed = false;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (!((f >> j) & 1u)) continue;
+                if (r < limit) {
+                    const u32 li = load[i0 + j];
+                    rows[r] = (u32)(i0 + j);
+                    node[r] = av[j];
+                    fr += li;
+                    if (used && av[j] < m) {
+                        if (hist) atomicAdd(&rel[av[j]], (u64)li);
+                        else atomicAdd(&used[av[j]], (u64)0 - (u64)li);
+                    }
+                    if (aff_life) aff_life[i0 + j] = kAffInactive;
+                    av[j] = kNone;
+                    listed = true;
+                }
+                ++r;
+            }
+            if (listed) *reinterpret_cast<uint4*>(A + i0) = make_uint4(av[0], av[1], av[2], av[3]);
+        });
+    if (fr) atomicAdd(&gfree, fr);
+    __syncthreads();
+    if (threadIdx.x == 0 && gfree) atomicAdd(freed, gfree);
+    if (hist)
+        for (u32 j = threadIdx.x; j < m; j += kChgWaves * 64)
+            if (rel[j]) atomicAdd(&used[j], (u64)0 - rel[j]);
+}
+
+constexpr u32 kCensusBlock = 1024;
+constexpr u32 kCensusCopies = 16;  // the totals form's copies of its cells in LDS: 16 * kClsMax = kCensusLdsCells
+static_assert(kCensusCopies * kClsMax <= kCensusLdsCells && kClsMax <= kCensusBlock, "k_census: the totals form's copies fit one slice");
+template <bool BY_NODE, bool LDSACC>
+__global__ __launch_bounds__(kCensusBlock) void k_census(const u32* __restrict__ A, const u32* __restrict__ Kw,
+                                                         const u32* __restrict__ load, u64 n, u32 m, u32 n_classes, u32 cells,
+                                                         u64* __restrict__ out_rows, u64* __restrict__ out_load,
+                                                         u64* __restrict__ other) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // LDSACC: this workgroup's slice of the cells, lo .. lo + span - 1
+    const u32 lo = LDSACC ? blockIdx.y * kCensusLdsCells : 0u;
+    const u32 span = LDSACC ? (cells - lo < kCensusLdsCells ? cells - lo : kCensusLdsCells) : 0u;
+    u64* lload = reinterpret_cast<u64*>(smem);            // [span]
+    u32* lrows = reinterpret_cast<u32*>(lload + span);    // [span]: a workgroup sees fewer than 2^32 rows
+    __shared__ u32 loth;
+    if (LDSACC)
+        for (u32 c = threadIdx.x; c < span; c += kCensusBlock) { lload[c] = 0; lrows[c] = 0; }
+    if (threadIdx.x == 0) loth = 0;
+    __syncthreads();
+    u32 oth = 0;
+    const u64 nvec = (n + 3) / 4;
+    for (u64 v = (u64)blockIdx.x * kCensusBlock + threadIdx.x; v < nvec; v += (u64)gridDim.x * kCensusBlock) {
+        const u64 i0 = v * 4;
+        const uint4 a = *reinterpret_cast<const uint4*>(A + i0);
+        const u32 kw = Kw[v];
+        const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
+        const u32 av[4] = {a.x, a.y, a.z, a.w}, lv[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (i0 + j >= n || av[j] == kNone) continue;
+            const u32 c = (kw >> (8 * j)) & 255u;
+            if (c >= n_classes || (BY_NODE && av[j] >= m)) { ++oth; continue; }
+            // (the totals form keeps kCensusCopies copies of its few cells, one per lane modulo: 64 lanes adding to a handful of
+            //  LDS words in one instruction take their turns, and measured slower than the by-node form over the same table)
+            const u32 cell = BY_NODE ? av[j] * n_classes + c : (threadIdx.x % kCensusCopies) * n_classes + c;
+            if (LDSACC) {
+                if (cell - lo >= span) continue;  // (another slice's)
+                atomicAdd(&lrows[cell - lo], 1u);
+                if (lv[j]) atomicAdd(&lload[cell - lo], (u64)lv[j]);
+            } else {
+                atomicAdd(&out_rows[cell], (u64)1);
+                if (lv[j]) atomicAdd(&out_load[cell], (u64)lv[j]);
+            }
+        }
+    }
+    oth = wave_sum32(oth);
+    if ((threadIdx.x & 63) == 0 && oth) atomicAdd(&loth, oth);
+    __syncthreads();
+    if (threadIdx.x == 0 && loth && blockIdx.y == 0) atomicAdd(other, (u64)loth);  // (every slice sees every such row)
+    if (LDSACC && BY_NODE)
+        for (u32 c = threadIdx.x; c < span; c += kCensusBlock) {
+            if (lrows[c]) atomicAdd(&out_rows[lo + c], (u64)lrows[c]);
+            if (lload[c]) atomicAdd(&out_load[lo + c], lload[c]);
+        }
+    if (LDSACC && !BY_NODE && threadIdx.x < n_classes) {
+        u64 r = 0, l = 0;
+        for (u32 q = 0; q < kCensusCopies; ++q) {
+            r += lrows[q * n_classes + threadIdx.x];
+            l += lload[q * n_classes + threadIdx.x];
+        }
+        if (r) atomicAdd(&out_rows[threadIdx.x], r);
+        if (l) atomicAdd(&out_load[threadIdx.x], l);
+    }
+}
+
+void launch_set_class_batch(unsigned char* K, u64 n_obj, const u32* idx, const unsigned char* cls, u64 n, u32* pos, DevStats* st,
+                            hipStream_t s) {
+    if (!n) return;
+    const unsigned g = grid_for(n, 256, 4096);
+    hipLaunchKernelGGL(k_cls_elect, dim3(g), dim3(256), 0, s, n_obj, idx, n, pos, st);
+    hipLaunchKernelGGL(k_cls_apply, dim3(g), dim3(256), 0, s, K, n_obj, idx, cls, n, pos);
+}
+void launch_expc_count(const u32* A, const u32* S, const unsigned char* K, const ChgPlan& p, const ClsCutoffs& cutoffs, u32* cnt,
+                       u32* gsum, u32* total, u64* by_class, u64* host_by_class, u64* freed, hipStream_t s) {
+    if (p.G) {
+        hipLaunchKernelGGL(k_expc_count, dim3(p.G), dim3(kChgWaves * 64), 0, s, A, S, reinterpret_cast<const u32*>(K), p, cutoffs,
+                           cnt, gsum, by_class, freed);
+        hipLaunchKernelGGL(k_chg_scan, dim3(1), dim3(kChgWaves * 64), 0, s, gsum, p.G, total);
+    }
+    hipLaunchKernelGGL(k_cls_publish, dim3(1), dim3(kClsMax), 0, s, by_class, host_by_class);
+}
+void launch_expc_apply(u32* A, const u32* S, const unsigned char* K, const ChgPlan& p, const ClsCutoffs& cutoffs, const u32* cnt, const u32* gsum, u64 cap, u32* rows, u32* node, u32* aff_life, const u32* load, u32 m,
+                       u64* used, u64* freed, hipStream_t s) {
+    if (!p.G || !cap) return;
+    const bool hist = used && m <= kExpLdsNodes;
+    hipLaunchKernelGGL(k_expc_apply, dim3(p.G), dim3(kChgWaves * 64), hist ? (size_t)m * sizeof(u64) : 0, s, A, S,
+                       reinterpret_cast<const u32*>(K), p, cutoffs, cnt, gsum, cap, rows, node, aff_life, load, m, used,
+                       hist ? 1u : 0u, freed);
+}
+void launch_census(const u32* A, const unsigned char* K, const u32* load, u64 n, u32 m, u32 n_classes, bool by_node,
+                   u64* out_rows, u64* out_load, u64* other, hipStream_t s) {
+    const u32 cells = (by_node ? m : 1u) * n_classes;
+    if (cells) {
+        (void)hipMemsetAsync(out_rows, 0, (size_t)cells * sizeof(u64), s);
+        (void)hipMemsetAsync(out_load, 0, (size_t)cells * sizeof(u64), s);
+    }
+    (void)hipMemsetAsync(other, 0, sizeof(u64), s);
+    if (!n) return;
+    const u32 slices = (cells + kCensusLdsCells - 1) / kCensusLdsCells;
+    const bool lds = slices <= kCensusMaxSlices;
+    // LDS form: one workgroup per compute unit and slice at most, so that the flush stays a small share of the pass
+    const dim3 g(grid_for((n + 3) / 4, kCensusBlock, lds ? 256 : 1024), lds ? slices : 1), b(kCensusBlock);
+    // (the kernel's `cells`: what it keeps in LDS slices, the totals form's copies included)
+    const u32 kc = by_node ? cells : kCensusCopies * n_classes;
+    const size_t sh = lds ? (size_t)std::min(kc, kCensusLdsCells) * (sizeof(u64) + sizeof(u32)) : 0;
+    const u32* Kw = reinterpret_cast<const u32*>(K);
+    if (by_node) {
+        if (lds) hipLaunchKernelGGL((k_census<true, true>), g, b, sh, s, A, Kw, load, n, m, n_classes, cells, out_rows, out_load, other);
+        else hipLaunchKernelGGL((k_census<true, false>), g, b, sh, s, A, Kw, load, n, m, n_classes, cells, out_rows, out_load, other);
+    } else {
+        hipLaunchKernelGGL((k_census<false, true>), g, b, sh, s, A, Kw, load, n, m, n_classes, kc, out_rows, out_load, other);
+    }
+}
+
 }  // namespace riogp

@@ -544,6 +544,15 @@ struct rio_gp {
     // two sums and the host-pointer form's listing (16 + 12 * RIO_GP_TOP_MAX bytes); the per-tile counts are the feed's
     TopScratch* top_sc = nullptr;
     unsigned char* h_top = nullptr;
+    // object classes (rio_gp_set_class*, rio_gp_expire_classes, rio_gp_census), allocated on first use: the class column K
+    // (cap_rows bytes, 0 to begin with; cls_ready: the fills are enqueued), the sweep's per-class idle counts (kClsSlots copies of
+    // kClsMax u64, zero between the calls) and the mapped pinned words their sum arrives in, and the host-pointer census's cells
+    // (rows | load | other, grown on use)
+    unsigned char* cls_K = nullptr;
+    u64 *cls_tab = nullptr, *h_cls = nullptr, *d_cls = nullptr;
+    bool cls_ready = false;
+    bool cls_tab_stale = false;  // a sweep failed where nobody can tell whether k_cls_publish ran: the copies are zeroed on next use
+    DevBuf cls_cells;
     std::vector<void*> allocs;
 };
 
@@ -1451,6 +1460,8 @@ void rio_gp_destroy(rio_gp_t* h) {
     for (DevBuf* b : {&h->sh_nodes, &h->sh_mat, &h->sh_tile, &h->sh_chunk, &h->sh_pk, &h->sh_mv, &h->sh_sel})
         if (b->p) (void)hipFree(b->p);
     if (h->chg_stage.p) (void)hipFree(h->chg_stage.p);
+    if (h->cls_cells.p) (void)hipFree(h->cls_cells.p);
+    if (h->h_cls) (void)hipHostFree(h->h_cls);
     if (h->h_ni) (void)hipHostFree(h->h_ni);
     if (h->h_chg) (void)hipHostFree(h->h_chg);
     if (h->h_top) (void)hipHostFree(h->h_top);
@@ -2256,6 +2267,242 @@ int rio_gp_expire_dev(rio_gp_t* h, uint32_t cutoff, uint32_t* d_rows, uint32_t* 
     HIPCHK(h, e);
     *n_idle = total;
     if (load_freed) *load_freed = apply ? reinterpret_cast<const u64*>(h->h_chg)[1] : 0;
+    return RIO_GP_OK;
+}
+
+// ---- object classes ---------------------------------------------------------------------------
+
+static_assert(RIO_GP_MAX_CLASSES == kClsMax, "object classes: the header's constant is the kernels'");
+
+// what every call of the family does first (one rule: no class column on a handle of the row-sharded solve): the class column
+// on first use, 0 everywhere, and the sweep's small tables
+static int cls_begin(rio_gp* h, const char* who) {
+    if (int rc = refuse_row_sharded(h, who)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->cls_ready && h->cls_tab_stale) {
+        HIPCHK(h, hipMemsetAsync(h->cls_tab, 0, (size_t)kClsSlots * kClsMax * sizeof(u64), h->stream));
+        h->cls_tab_stale = false;
+    }
+    if (h->cls_ready) return RIO_GP_OK;
+    int rc;
+    if (!h->cls_K && (rc = dalloc(h, &h->cls_K, h->cap_rows))) return rc;
+    if (!h->cls_tab && (rc = dalloc(h, &h->cls_tab, (size_t)kClsSlots * kClsMax))) return rc;
+    if (!h->h_cls) {
+        if (hipHostMalloc(reinterpret_cast<void**>(&h->h_cls), kClsMax * sizeof(u64), hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_cls), h->h_cls, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h->h_cls) (void)hipHostFree(h->h_cls);
+            h->h_cls = nullptr;
+            return fail(h, RIO_GP_ENOMEM, "hipHostMalloc(per-class counts) failed");
+        }
+    }
+    HIPCHK(h, hipMemsetAsync(h->cls_K, 0, h->cap_rows, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->cls_tab, 0, (size_t)kClsSlots * kClsMax * sizeof(u64), h->stream));
+    h->cls_ready = true;  // (last: it is what says the column is complete)
+    return RIO_GP_OK;
+}
+
+// The class setters write K and nothing else: no inputs_changed, `used` and the solve in flight stay as they are.
+static int cls_set_range(rio_gp* h, uint64_t first_row, uint64_t rows, const uint8_t* cls, bool dev) {
+    if (!h || (rows && !cls)) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = refuse_row_sharded(h, "rio_gp_set_classes"))) return rc;
+    if (first_row > h->n || rows > h->n - first_row) return fail(h, RIO_GP_EINVAL, "rio_gp_set_classes: the range exceeds the object table");
+    if ((rc = cls_begin(h, "rio_gp_set_classes"))) return rc;
+    if (!rows) return RIO_GP_OK;
+    HIPCHK(h, hipMemcpyAsync(h->cls_K + first_row, cls, rows, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (!dev) HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's array is read until here
+    return RIO_GP_OK;
+}
+int rio_gp_set_classes(rio_gp_t* h, uint64_t first_row, uint64_t rows, const uint8_t* cls) {
+    return cls_set_range(h, first_row, rows, cls, false);
+}
+int rio_gp_set_classes_dev(rio_gp_t* h, uint64_t first_row, uint64_t rows, const uint8_t* d_cls) {
+    return cls_set_range(h, first_row, rows, d_cls, true);
+}
+
+int rio_gp_set_class_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, const uint8_t* d_cls) {
+    if (!h || (n && (!d_idx || !d_cls))) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (n >= 0xFFFFFFFFull) return fail(h, RIO_GP_EINVAL, "rio_gp_set_class_batch: too many entries");
+    int rc;
+    if ((rc = cls_begin(h, "rio_gp_set_class_batch"))) return rc;
+    if (!n) return RIO_GP_OK;
+    if ((rc = zero_stats(h))) return rc;
+    launch_set_class_batch(h->cls_K, h->n, d_idx, d_cls, n, h->pos, h->dstats, h->stream);
+    if ((rc = read_stats(h))) return rc;
+    if (h->h_stats[0].err) return fail(h, RIO_GP_EINVAL, "rio_gp_set_class_batch: invalid entries were skipped");
+    return RIO_GP_OK;
+}
+
+int rio_gp_set_class_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint8_t* cls) {
+    if (!h || (n && (!idx || !cls))) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (n >= 0xFFFFFFFFull) return fail(h, RIO_GP_EINVAL, "rio_gp_set_class_batch: too many entries");
+    int rc;
+    if ((rc = refuse_row_sharded(h, "rio_gp_set_class_batch"))) return rc;
+    for (uint64_t k = 0; k < n; ++k)
+        if (idx[k] >= h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_set_class_batch: object index out of range");
+    if ((rc = cls_begin(h, "rio_gp_set_class_batch"))) return rc;
+    if (!n) return RIO_GP_OK;
+    if ((rc = ensure(h, h->stage[0], n * sizeof(u32))) || (rc = ensure(h, h->stage[1], n))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, idx, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->stage[1].p, cls, n, hipMemcpyHostToDevice, h->stream));
+    launch_set_class_batch(h->cls_K, h->n, (const u32*)h->stage[0].p, (const unsigned char*)h->stage[1].p, n, h->pos, h->dstats,
+                           h->stream);  // (validated: nothing is counted)
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's arrays are read until here
+    return RIO_GP_OK;
+}
+
+int rio_gp_get_classes(rio_gp_t* h, uint64_t n, uint8_t* out) {
+    if (!h || !out) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = refuse_row_sharded(h, "rio_gp_get_classes"))) return rc;
+    if (n != h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_get_classes: n differs from the object table");
+    if ((rc = cls_begin(h, "rio_gp_get_classes"))) return rc;
+    if (n) HIPCHK(h, hipMemcpyAsync(out, h->cls_K, n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RIO_GP_OK;
+}
+
+// checks and first-use work shared by both forms of the sweep: nothing is changed before the checks pass; then S and K are on
+// the device and ct holds the cutoffs (0 from n_classes on: a row of such a class is never idle)
+static int expc_begin(rio_gp* h, uint32_t n_classes, const uint32_t* cutoffs, const void* r, const void* o, uint64_t cap,
+                      const uint64_t* n_idle, ClsCutoffs& ct) {
+    if (n_classes < 1 || n_classes > RIO_GP_MAX_CLASSES || !cutoffs)
+        return fail(h, RIO_GP_EINVAL, "rio_gp_expire_classes: 1 .. RIO_GP_MAX_CLASSES cutoffs are needed");
+    int rc;
+    if ((rc = exp_args(h, r, o, cap, n_idle))) return rc;
+    if ((rc = exp_begin(h, "rio_gp_expire_classes")) || (rc = cls_begin(h, "rio_gp_expire_classes"))) return rc;
+    std::fill(std::copy(cutoffs, cutoffs + n_classes, ct.v), ct.v + kClsMax, 0u);
+    return RIO_GP_OK;
+}
+// The copies of the per-class counts are zero between the calls because k_cls_publish, the last launch of the count pass, leaves
+// them so.  A call that cannot tell whether that launch ran (a launch error, a failed wait) has the next call of the section
+// fill them again: a sweep after a failed one must not add to what the failed one left.
+static int expc_failed(rio_gp* h, const char* msg) {
+    h->cls_tab_stale = true;  // (cls_begin zeroes the copies before the next call of the section runs)
+    return fail(h, RIO_GP_EUPSTREAM, msg);
+}
+// The count pass over the committed column, S and K; the total lands in the mapped word, the per-class counts in h->h_cls
+// (mapped too: complete after the next wait).  It changes nothing of the table.
+static int expc_count(rio_gp* h, const ChgPlan& p, const ClsCutoffs& ct) {
+    *h->h_chg = 0;
+    launch_expc_count(h->assign[h->cur], h->exp_S, h->cls_K, p, ct, h->chg_cnt, h->chg_gsum, h->d_chg, h->cls_tab, h->d_cls,
+                      h->exp_freed, h->stream);
+    if (hipGetLastError() != hipSuccess) return expc_failed(h, "rio_gp_expire_classes: a launch of the count pass failed");
+    return RIO_GP_OK;
+}
+// exp_apply with the per-class predicate
+static int expc_apply(rio_gp* h, const ChgPlan& p, const ClsCutoffs& ct, u64 cap, u32* d_rows, u32* d_node) {
+    u64* const used = h->used.live();
+    launch_expc_apply(h->assign[h->cur], h->exp_S, h->cls_K, p, ct, h->chg_cnt, h->chg_gsum, cap, d_rows, d_node, aff_life(h),
+                      h->load, h->m, used, h->exp_freed, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(reinterpret_cast<u64*>(h->h_chg) + 1, h->exp_freed, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    return RIO_GP_OK;
+}
+
+int rio_gp_expire_classes(rio_gp_t* h, uint32_t n_classes, const uint32_t* cutoffs, uint32_t* out_rows, uint32_t* out_node,
+                          uint64_t cap, uint64_t* n_idle, uint64_t* load_freed, uint64_t* idle_by_class) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    ClsCutoffs ct;
+    if ((rc = expc_begin(h, n_classes, cutoffs, out_rows, out_node, cap, n_idle, ct))) return rc;
+    const ChgPlan p = chg_plan(h->n);
+    if ((rc = expc_count(h, p, ct))) return rc;
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return expc_failed(h, "rio_gp_expire_classes: the count pass failed");
+    const u64* const bc = h->h_cls;
+    const u64 total = p.G ? *h->h_chg : 0;
+    *n_idle = total;
+    if (idle_by_class) std::copy(bc, bc + n_classes, idle_by_class);
+    if (load_freed) *load_freed = 0;
+    const u64 L = std::min<u64>(total, cap);
+    if (!out_rows || L == 0) return RIO_GP_OK;
+    if ((rc = ensure(h, h->chg_stage, 2 * L * sizeof(u32)))) return rc;
+    u32* d = (u32*)h->chg_stage.p;
+    inputs_changed(h);  // from here on it is a rio_gp_remove_batch of the listed rows
+    if ((rc = expc_apply(h, p, ct, L, d, d + L))) return rc;
+    if ((rc = read_listing(h, d, L, L, {out_rows, out_node}))) return rc;
+    if (load_freed) *load_freed = reinterpret_cast<const u64*>(h->h_chg)[1];
+    return RIO_GP_OK;
+}
+
+int rio_gp_expire_classes_dev(rio_gp_t* h, uint32_t n_classes, const uint32_t* cutoffs, uint32_t* d_rows, uint32_t* d_node,
+                              uint64_t cap, uint64_t* n_idle, uint64_t* load_freed, uint64_t* idle_by_class) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    ClsCutoffs ct;
+    if ((rc = expc_begin(h, n_classes, cutoffs, d_rows, d_node, cap, n_idle, ct))) return rc;
+    const ChgPlan p = chg_plan(h->n);
+    if ((rc = expc_count(h, p, ct))) return rc;
+    const u64* const bc = h->h_cls;
+    // the apply pass reads the prefix the count pass left on the device and drops ranks >= cap itself: one wait for the call
+    const bool apply = d_rows && cap && p.G;
+    reinterpret_cast<u64*>(h->h_chg)[1] = 0;
+    if (apply && (rc = expc_apply(h, p, ct, cap, d_rows, d_node))) {
+        inputs_changed(h);
+        return rc;
+    }
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    const u64 total = p.G ? *h->h_chg : 0;
+    if (apply && (e != hipSuccess || total)) inputs_changed(h);  // something was un-placed (or nobody can tell)
+    if (e != hipSuccess) h->cls_tab_stale = true;
+    HIPCHK(h, e);
+    *n_idle = total;
+    if (idle_by_class) std::copy(bc, bc + n_classes, idle_by_class);
+    if (load_freed) *load_freed = apply ? reinterpret_cast<const u64*>(h->h_chg)[1] : 0;
+    return RIO_GP_OK;
+}
+
+// Read-only, like rio_gp_count_placed: the committed column, K and load; no inputs_changed.
+static int census_begin(rio_gp* h, uint32_t flags, uint32_t n_classes, const void* r, const void* l, const void* o) {
+    if (flags & ~RIO_GP_CENSUS_BY_NODE) return fail(h, RIO_GP_EINVAL, "rio_gp_census: unknown flags");
+    if (n_classes < 1 || n_classes > RIO_GP_MAX_CLASSES) return fail(h, RIO_GP_EINVAL, "rio_gp_census: n_classes out of range");
+    if (!r || !l || !o) return fail(h, RIO_GP_EINVAL, "rio_gp_census: out_rows, out_load and n_other are needed");
+    if ((flags & RIO_GP_CENSUS_BY_NODE) && (u64)h->m * n_classes > (1ull << 20))
+        return fail(h, RIO_GP_EINVAL, "rio_gp_census: more than 2^20 cells");
+    return cls_begin(h, "rio_gp_census");
+}
+
+int rio_gp_census(rio_gp_t* h, uint32_t flags, uint32_t n_classes, uint64_t* out_rows, uint64_t* out_load, uint64_t* n_other) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = census_begin(h, flags, n_classes, out_rows, out_load, n_other))) return rc;
+    const bool by_node = flags & RIO_GP_CENSUS_BY_NODE;
+    const u64 cells = (u64)(by_node ? h->m : 1u) * n_classes;
+    if ((rc = ensure(h, h->cls_cells, (2 * cells + 1) * sizeof(u64)))) return rc;
+    u64* const d = (u64*)h->cls_cells.p;
+    launch_census(h->assign[h->cur], h->cls_K, h->load, h->n, h->m, n_classes, by_node, d, d + cells, d + 2 * cells, h->stream);
+    HIPCHK(h, hipGetLastError());
+    if (cells) {
+        HIPCHK(h, hipMemcpyAsync(out_rows, d, cells * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(out_load, d + cells, cells * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(n_other, d + 2 * cells, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RIO_GP_OK;
+}
+
+int rio_gp_census_dev(rio_gp_t* h, uint32_t flags, uint32_t n_classes, uint64_t* d_rows, uint64_t* d_load, uint64_t* n_other) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    int rc;
+    if ((rc = census_begin(h, flags, n_classes, d_rows, d_load, n_other))) return rc;
+    if ((rc = ensure(h, h->cls_cells, sizeof(u64)))) return rc;
+    u64* const d = (u64*)h->cls_cells.p;
+    launch_census(h->assign[h->cur], h->cls_K, h->load, h->n, h->m, n_classes, flags & RIO_GP_CENSUS_BY_NODE, reinterpret_cast<u64*>(d_rows),
+                  reinterpret_cast<u64*>(d_load), d,
+                  h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(n_other, d, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return RIO_GP_OK;
 }
 

@@ -23,6 +23,7 @@ OP_CFG_LIVE_FIRST_TOUCH = 4     # RIO_OP_CFG_LIVE_FIRST_TOUCH (string layer, who
 FLAG_LOCAL, FLAG_REDIRECT, FLAG_PLACED, FLAG_SPILLED, FLAG_UNPLACED = range(5)
 FLAG_REPLACED = 0x10   # OR-ed on: the object was found on a dead server, cleaned and re-placed by this request
 FLAG_MASK = 0x0F
+CENSUS_BY_NODE, MAX_CLASSES = 1, 256   # RIO_GP_CENSUS_BY_NODE, RIO_GP_MAX_CLASSES
 CHANGES_PEEK = 1       # RIO_GP_CHANGES_PEEK: list the changes without advancing the checkpoint
 NODE_GONE = 0xFFFFFFFC  # RIO_GP_NODE_GONE: change feed, old node of a row whose last-told node has been removed
 OK, EINVAL, EUPSTREAM, ENODEV, ENOMEM, ERANGE, EAGAIN = range(7)
@@ -239,6 +240,15 @@ def _load(lab):
             getattr(L, nm).argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64)]
         L.rio_gp_remap_nodes.argtypes = [_vp, C.c_uint32, _vp, C.POINTER(C.c_uint64)]
+        if hasattr(L, "rio_gp_set_classes"):   # (an older build under RIO_GP_LIB, as for rio_gp_top_rows above)
+            for nm in ("rio_gp_set_classes", "rio_gp_set_classes_dev", "rio_gp_set_class_batch", "rio_gp_set_class_batch_dev"):
+                getattr(L, nm).argtypes = [_vp, C.c_uint64, _vp, _vp] if "batch" in nm else [_vp, C.c_uint64, C.c_uint64, _vp]
+            L.rio_gp_get_classes.argtypes = [_vp, C.c_uint64, _vp]
+            for nm in ("rio_gp_expire_classes", "rio_gp_expire_classes_dev"):
+                getattr(L, nm).argtypes = [_vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint64), _vp]
+            for nm in ("rio_gp_census", "rio_gp_census_dev"):
+                getattr(L, nm).argtypes = [_vp, C.c_uint32, C.c_uint32, _vp, _vp, C.POINTER(C.c_uint64)]
         if lab:
             L.rio_gp_debug_set_scan_nt.argtypes = [C.c_int]
             L.rio_gp_debug_set_scan_nt.restype = None
@@ -654,6 +664,100 @@ class GpuPlacement:
                                    C.byref(n) if want_n_idle else None, None)
         return rc, int(n.value)
 
+    # -- object classes --
+    def set_classes(self, first_row, cls):
+        """rio_gp_set_classes: K[first_row + k] = cls[k] (uint8)."""
+        cls = np.asarray(cls, np.uint8)
+        self._chk(self.set_classes_raw(first_row, cls))
+
+    def set_classes_raw(self, first_row, cls, rows=None):
+        """One rio_gp_set_classes call as given (cls: a uint8 array, any alignment): rc; no exception."""
+        return self._L.rio_gp_set_classes(self._h, int(first_row), len(cls) if rows is None else int(rows),
+                                          cls.ctypes.data if len(cls) else None)
+
+    def set_classes_dev(self, first_row, d_cls, rows):
+        """rio_gp_set_classes_dev: the same from a device array of `rows` bytes (an int, e.g. a torch tensor's data_ptr())."""
+        self._chk(self._L.rio_gp_set_classes_dev(self._h, int(first_row), int(rows), _vp(d_cls) if d_cls else None))
+
+    def set_class_batch(self, idx, cls):
+        """rio_gp_set_class_batch: K[idx[k]] = cls[k]; of several entries for one row the last wins."""
+        self._chk(self.set_class_batch_raw(idx, cls))
+
+    def set_class_batch_raw(self, idx, cls):
+        """One rio_gp_set_class_batch call as given: rc; no exception."""
+        idx, cls = _u32(idx), np.ascontiguousarray(cls, np.uint8)
+        return self._L.rio_gp_set_class_batch(self._h, len(idx), _ptr(idx), cls.ctypes.data if len(cls) else None)
+
+    def set_class_batch_dev_raw(self, d_idx, d_cls, n):
+        """One rio_gp_set_class_batch_dev call over device arrays of n entries (ints): rc; no exception."""
+        return self._L.rio_gp_set_class_batch_dev(self._h, int(n), _vp(d_idx) if d_idx else None, _vp(d_cls) if d_cls else None)
+
+    def get_classes(self):
+        """rio_gp_get_classes: the class column K[0 .. n-1] (uint8)."""
+        out = np.empty(self.num_objects, np.uint8)
+        self._chk(self._L.rio_gp_get_classes(self._h, len(out), out.ctypes.data if len(out) else _ptr(np.empty(1, np.uint8))))
+        return out
+
+    def expire_classes(self, cutoffs, cap=None, count_only=False):
+        """rio_gp_expire_classes: (rows, nodes, n_idle, load_freed, idle_by_class) — rio_gp_expire with cutoffs[K[r]] as row r's
+        cutoff; idle_by_class (uint64, one entry per cutoff) counts every idle row of the class, listed or not."""
+        cut = _u32(cutoffs)
+        n, fr = C.c_uint64(0), C.c_uint64(0)
+        by = np.zeros(len(cut), np.uint64)
+        cap = self.num_objects if cap is None else min(int(cap), self.num_objects)
+        if count_only or cap == 0:
+            self._chk(self._L.rio_gp_expire_classes(self._h, len(cut), _ptr(cut), None, None, 0, C.byref(n), C.byref(fr), _ptr(by)))
+            e = np.empty(0, np.uint32)
+            return e, e, int(n.value), 0, by
+        buf = np.empty((2, cap), np.uint32)
+        self._chk(self._L.rio_gp_expire_classes(self._h, len(cut), _ptr(cut), _ptr(buf[0]), _ptr(buf[1]), cap, C.byref(n),
+                                                C.byref(fr), _ptr(by)))
+        k = min(int(n.value), cap)
+        return buf[0, :k].copy(), buf[1, :k].copy(), int(n.value), int(fr.value), by
+
+    def expire_classes_dev(self, cutoffs, d_rows=None, d_node=None, cap=0):
+        """rio_gp_expire_classes_dev: the listing into device arrays (ints; both None with cap 0: count only).
+        Returns (n_idle, load_freed, idle_by_class)."""
+        cut = _u32(cutoffs)
+        n, fr = C.c_uint64(0), C.c_uint64(0)
+        by = np.zeros(len(cut), np.uint64)
+        self._chk(self._L.rio_gp_expire_classes_dev(self._h, len(cut), _ptr(cut), _vp(d_rows) if d_rows else None,
+                                                    _vp(d_node) if d_node else None, int(cap), C.byref(n), C.byref(fr), _ptr(by)))
+        return int(n.value), int(fr.value), by
+
+    def expire_classes_raw(self, n_classes, cutoffs, out_rows=None, out_node=None, cap=0, want_n_idle=True):
+        """One rio_gp_expire_classes call as given (tests of the argument checks): (rc, n_idle); no exception."""
+        n = C.c_uint64(0)
+        cut = None if cutoffs is None else _u32(cutoffs)
+        rc = self._L.rio_gp_expire_classes(self._h, int(n_classes), _ptr(cut), _ptr(out_rows), _ptr(out_node), int(cap),
+                                           C.byref(n) if want_n_idle else None, None, None)
+        return rc, int(n.value)
+
+    def census(self, n_classes, by_node=False):
+        """rio_gp_census: (rows, load, n_other) — the placed rows and their load by class (uint64 arrays of n_classes entries;
+        by_node: [m, n_classes]); n_other counts the placed rows of a class >= n_classes (by_node: or on a node id >= m)."""
+        rc, rows, load, other = self.census_raw(n_classes, by_node)
+        self._chk(rc)
+        return rows, load, other
+
+    def census_raw(self, n_classes, by_node=False, flags=None):
+        """One rio_gp_census call: (rc, rows, load, n_other); no exception."""
+        m = self.num_nodes if by_node else 1
+        shape = (m, int(n_classes)) if by_node else (int(n_classes),)
+        rows, load = np.zeros(max(1, m * int(n_classes)), np.uint64), np.zeros(max(1, m * int(n_classes)), np.uint64)
+        other = C.c_uint64(0)
+        fl = (CENSUS_BY_NODE if by_node else 0) if flags is None else int(flags)
+        rc = self._L.rio_gp_census(self._h, fl, int(n_classes), _ptr(rows), _ptr(load), C.byref(other))
+        k = m * int(n_classes)
+        return rc, rows[:k].reshape(shape), load[:k].reshape(shape), int(other.value)
+
+    def census_dev(self, n_classes, d_rows, d_load, by_node=False):
+        """rio_gp_census_dev: the cells into device arrays of uint64 (ints); returns n_other."""
+        other = C.c_uint64(0)
+        self._chk(self._L.rio_gp_census_dev(self._h, CENSUS_BY_NODE if by_node else 0, int(n_classes), _vp(d_rows), _vp(d_load),
+                                            C.byref(other)))
+        return other.value
+
     # -- measured load --
     def hits_add(self, idx, weight=None):
         """rio_gp_hits_add_batch: H[idx[k]] = min(H[idx[k]] + weight[k], 2^32-1); weight None: 1 each."""
@@ -953,6 +1057,7 @@ def _oplib():
         L.rio_op_rebalance_ordered.argtypes = [_vp, C.c_uint32] + L.rio_op_rebalance.argtypes[1:]
         bind_op_changes(L)
         bind_op_expire(L)
+        bind_op_classes(L)
         bind_op_loads(L)
         if hasattr(L, "rio_op_hottest_objects"):   # (as above)
             bind_op_top(L)
@@ -1015,6 +1120,52 @@ def op_expire(L, h, cutoff, max_objects=None):
     if rc != OK:
         return rc, [], 0
     return rc, _listing(o), int(idle.value)
+
+
+def bind_op_classes(L):
+    """argtypes of rio_op_set_type_idle_limit_n / rio_op_expire_by_type / rio_op_census on a library that has them."""
+    L.rio_op_set_type_idle_limit_n.argtypes = [_vp, C.c_char_p, C.c_size_t, C.c_uint32]
+    L.rio_op_expire_by_type.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                        _pp, _psz, _pp, _psz, _pp]
+    L.rio_op_census.argtypes = [_vp, C.c_int, C.POINTER(C.c_uint64), _pp, _psz, _pp, C.POINTER(C.POINTER(C.c_uint64)),
+                                C.POINTER(C.POINTER(C.c_uint64))]
+
+
+IDLE_NEVER = 0xFFFFFFFF   # RIO_OP_IDLE_NEVER
+CLASS_OTHER = 255         # RIO_OP_CLASS_OTHER
+
+
+def op_set_type_idle_limit(L, h, struct_name, max_idle):
+    """One rio_op_set_type_idle_limit_n call (struct_name: str or bytes, NUL bytes included): rc."""
+    b = struct_name if isinstance(struct_name, bytes) else struct_name.encode()
+    return L.rio_op_set_type_idle_limit_n(h, b, len(b), int(max_idle))
+
+
+def op_expire_by_type(L, h, now, default_max_idle, max_objects=None):
+    """One rio_op_expire_by_type call: (rc, [(struct_name, object_id, address)], n_idle), as op_expire."""
+    o, idle = _listing_out(1), C.c_uint64(0)
+    cap = 0xFFFFFFFFFFFFFFFF if max_objects is None else int(max_objects)
+    rc = L.rio_op_expire_by_type(h, int(now), int(default_max_idle), cap, C.byref(o[0]), C.byref(idle), *map(C.byref, o[1:]))
+    if rc != OK:
+        return rc, [], 0
+    return rc, _listing(o), int(idle.value)
+
+
+def op_census(L, h, by_server=False):
+    """One rio_op_census call: (rc, [(struct_name or None for OTHER, address or None, rows, load)]) — struct_name as bytes."""
+    n = C.c_uint64(0)
+    names, addrs = C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)()
+    lens = C.POINTER(C.c_size_t)()
+    rows, loads = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+    rc = L.rio_op_census(h, 1 if by_server else 0, C.byref(n), C.byref(names), C.byref(lens), C.byref(addrs), C.byref(rows),
+                         C.byref(loads))
+    if rc != OK:
+        return rc, []
+    out = []
+    for k in range(n.value):
+        nm = C.cast(names, C.POINTER(_vp))[k]
+        out.append((None if not nm else C.string_at(nm, lens[k]), addrs[k].decode() if addrs[k] else None, int(rows[k]), int(loads[k])))
+    return rc, out
 
 
 def bind_op_loads(L):
@@ -1289,6 +1440,22 @@ class GpuObjectPlacement:
         rc, out, idle = op_expire(_oplib(), self._h, cutoff, max_objects)
         self._chk(rc)
         return out, idle
+
+    def set_type_idle_limit(self, struct_name, max_idle):
+        """rio_op_set_type_idle_limit_n: keys of this type are idle after max_idle epochs without a stamp (IDLE_NEVER: never)."""
+        self._chk(op_set_type_idle_limit(_oplib(), self._h, struct_name, max_idle))
+
+    def expire_by_type(self, now, default_max_idle, max_objects=None):
+        """rio_op_expire_by_type: ([(struct_name, object_id, address)], n_idle) — rio_op_expire with every type's own limit."""
+        rc, out, idle = op_expire_by_type(_oplib(), self._h, now, default_max_idle, max_objects)
+        self._chk(rc)
+        return out, idle
+
+    def census(self, by_server=False):
+        """rio_op_census: [(struct_name (bytes; None: the types past 255), address (None without by_server), rows, load)]."""
+        rc, out = op_census(_oplib(), self._h, by_server)
+        self._chk(rc)
+        return out
 
     def set_load_tracking(self, on):
         """rio_op_set_load_tracking: count one request per call that answers or sets an address for a key (off at creation)."""

@@ -101,6 +101,10 @@ extern "C" {
     fn rio_op_expire(p: *mut c_void, cutoff: u32, max_objects_out: u64, n_out: *mut u64, n_idle: *mut u64,
                      tys: *mut *const *const c_char, ty_lens: *mut *const usize, ids: *mut *const *const c_char,
                      id_lens: *mut *const usize, addrs: *mut *const *const c_char) -> c_int;
+    fn rio_op_set_type_idle_limit_n(p: *mut c_void, ty: *const c_char, ty_len: usize, max_idle: u32) -> c_int;
+    fn rio_op_expire_by_type(p: *mut c_void, now: u32, default_max_idle: u32, max_objects_out: u64, n_out: *mut u64,
+                             n_idle: *mut u64, tys: *mut *const *const c_char, ty_lens: *mut *const usize,
+                             ids: *mut *const *const c_char, id_lens: *mut *const usize, addrs: *mut *const *const c_char) -> c_int;
     fn rio_op_set_load_tracking(p: *mut c_void, on: c_int) -> c_int;
     fn rio_op_fold_loads(p: *mut c_void, keep: u32, gain: u32, min_load: u32, max_load: u32, rows_changed: *mut u64,
                          hits_folded: *mut u64) -> c_int;
@@ -127,6 +131,14 @@ extern "C" {
                                               ids: *const *const c_char, id_lens: *const usize, self_addrs: *const *const c_char,
                                               out_node_ids: *mut u32, out_flags: *mut u32) -> c_int;
     fn rio_op_node_address(p: *mut c_void, node_id: u32) -> *const c_char;
+}
+
+// rio_op_census hands out two thread-owned arrays of u64 (`const uint64_t**` in the header): a block of its own next to the one
+// above.
+extern "C" {
+    fn rio_op_census(p: *mut c_void, by_server: c_int, n_out: *mut u64, tys: *mut *const *const c_char,
+                     ty_lens: *mut *const usize, addrs: *mut *const *const c_char, rows: *mut *const u64,
+                     loads: *mut *const u64) -> c_int;
 }
 
 /// One reference on the shared native state; `Drop` releases it (the HBM tables go with the last).
@@ -330,6 +342,62 @@ impl GpuObjectPlacement {
                  if a.is_null() { None } else { Some(unsafe { CStr::from_ptr(a) }.to_string_lossy().into_owned()) })
             }).collect();
             Ok((out, idle))
+        })
+        .await
+    }
+
+    /// Idle limit of one type, in the clock's units (`u32::MAX`: never idle).  `Err(OutOfRange)`-like answer (RIO_GP_ERANGE) for
+    /// a type past the first 255 the layer has seen: those share one class and the sweep's default.
+    pub fn set_type_idle_limit(&self, struct_name: &str, max_idle: u32) -> Result<(), ObjectPlacementError> {
+        check(unsafe { rio_op_set_type_idle_limit_n(self.inner.0, struct_name.as_ptr() as *const c_char, struct_name.len(), max_idle) },
+              self)
+    }
+
+    /// `expire` with every type's own limit: an object is idle when `stamp + limit < now`, `default_max_idle` for a type without
+    /// a limit.  Same listing as `expire`.
+    pub async fn expire_by_type(&self, now: u32, default_max_idle: u32, max_objects: Option<u64>)
+        -> Result<(Vec<(ObjectId, Option<String>)>, u64), ObjectPlacementError> {
+        let me = self.clone();
+        blocking(move || {
+            let (mut n, mut idle) = (0u64, 0u64);
+            let (mut ty, mut id, mut ad) = (std::ptr::null(), std::ptr::null(), std::ptr::null());
+            let (mut tl, mut il) = (std::ptr::null(), std::ptr::null());
+            check(unsafe { rio_op_expire_by_type(me.inner.0, now, default_max_idle, max_objects.unwrap_or(u64::MAX), &mut n,
+                                                 &mut idle, &mut ty, &mut tl, &mut id, &mut il, &mut ad) }, &me)?;
+            let key = |p: *const *const c_char, l: *const usize, k: usize| unsafe {
+                String::from_utf8_lossy(std::slice::from_raw_parts(*p.add(k) as *const u8, *l.add(k))).into_owned()
+            };
+            let out = (0..n as usize).map(|k| {
+                let a = unsafe { *ad.add(k) };
+                (ObjectId(key(ty, tl, k), key(id, il, k)),
+                 if a.is_null() { None } else { Some(unsafe { CStr::from_ptr(a) }.to_string_lossy().into_owned()) })
+            }).collect();
+            Ok((out, idle))
+        })
+        .await
+    }
+
+    /// The placed objects and their load by type — `(struct_name, address, objects, load)`, `struct_name` `None` for the types
+    /// past the first 255, `address` `None` unless `by_server` — what `GROUP BY struct_name[, server_address]` answers on the
+    /// SQL backends.
+    pub async fn census(&self, by_server: bool)
+        -> Result<Vec<(Option<String>, Option<String>, u64, u64)>, ObjectPlacementError> {
+        let me = self.clone();
+        blocking(move || {
+            let mut n = 0u64;
+            let (mut ty, mut ad) = (std::ptr::null(), std::ptr::null());
+            let mut tl = std::ptr::null();
+            let (mut rows, mut loads) = (std::ptr::null(), std::ptr::null());
+            check(unsafe { rio_op_census(me.inner.0, by_server as c_int, &mut n, &mut ty, &mut tl, &mut ad, &mut rows, &mut loads) },
+                  &me)?;
+            // the arrays are this thread's until its next call: read them here, before anything else can run
+            Ok((0..n as usize).map(|k| unsafe {
+                let (t, a) = (*ty.add(k), *ad.add(k));
+                (if t.is_null() { None }
+                 else { Some(String::from_utf8_lossy(std::slice::from_raw_parts(t as *const u8, *tl.add(k))).into_owned()) },
+                 if a.is_null() { None } else { Some(CStr::from_ptr(a).to_string_lossy().into_owned()) },
+                 *rows.add(k), *loads.add(k))
+            }).collect())
         })
         .await
     }
