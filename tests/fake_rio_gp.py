@@ -1,7 +1,8 @@
 """A CPU stand-in for the rio_gp binding, FOR TESTS ONLY: the surface tests/test_gpu_fuzz.py's scenarios use, implemented over
 the CPU oracle (oracle/pyoracle.py), tests/rebalance_ref.py, tests/rebalance_order_ref.py, tests/spec_changes.py, tests/spec_remap.py
 and tests/spec_top.py; idle expiry and measured load (the hit column and the fold, in uint64: the scenarios hold them against
-tests/spec_loads.py's Python integers) are restated here in plain numpy.  It lets the fuzz driver itself be tested
+tests/spec_loads.py's Python integers) and object classes (the class column, the per-class sweep and the census, which the scenarios
+hold against tests/spec_classes.py) are restated here in plain numpy.  It lets the fuzz driver itself be tested
 without a GPU (tests/test_fuzz_driver.py): its bookkeeping (n, the feed's checkpoint, the mirror, the uncommitted solve) and its
 sensitivity — `fault=` makes exactly one behaviour of the handle wrong, and the scenarios must notice.
 
@@ -28,6 +29,7 @@ CFG_REF_SELF_ASSIGN = 2
 CHANGES_PEEK = 1
 TOP_BY_HITS, TOP_PLACED, TOP_ON_NODE, TOP_MAX = 1, 2, 4, 4096
 REBALANCE_ROW_ORDER, REBALANCE_BY_LOAD = 0, 1
+CENSUS_BY_NODE, MAX_CLASSES = 1, 256
 U32 = 0xFFFFFFFF
 OK, EINVAL, EUPSTREAM, ENODEV, ENOMEM, ERANGE, EAGAIN = range(7)
 
@@ -79,6 +81,28 @@ FAULTS = (
     "by_load_is_row_order",        # cfg.order is ignored: the cut is R1
     "by_load_ties_shed_first_rows",     # among candidates of equal load the cut sheds the lowest rows, not the highest
     "by_load_sheds_zero_load",     # zero-load candidates are cut behind the loaded ones, so an over node sheds them
+    "classes_batch_first_wins",    # of several batch entries for one row the first wins
+    "classes_dev_batch_stops_at_invalid",   # the _dev class batch stops at its first invalid entry instead of skipping it
+    "classes_range_writes_past_end",    # the range setter writes one byte behind its last row
+    "classes_drop_solve",          # a class setter drops an uncommitted solve
+    "classes_batch_dirty_pos",     # a class batch leaves its rows marked in the position scratch: the next update batch skips them
+    "num_objects_clears_classes",  # set_num_objects zeroes the class column
+    "remap_clears_classes",        # a node removal zeroes the classes of the rows < n
+    "expc_cutoff_inclusive",       # class sweep: a row stamped exactly at its class's cutoff is idle
+    "expc_high_class_is_class_0",  # class sweep: a row of a class >= n_classes is swept under class 0's cutoff
+    "expc_by_class_listed_only",   # idle_by_class counts the listed rows only
+    "expc_by_class_accumulates",   # idle_by_class adds to what the sweep before left
+    "expc_unplaces_past_cap",      # a class sweep un-places every idle row, not only the listed ones
+    "expc_lists_hidden_rows",      # a class sweep finds rows >= n idle
+    "expc_keeps_solve",            # a class sweep that un-placed rows keeps an uncommitted solve committable
+    "expc_count_only_writes",      # a count-only class sweep un-places the idle rows
+    "census_counts_hidden_rows",   # the census counts rows >= n
+    "census_reads_solved",         # the census reads the uncommitted column
+    "census_uses_max_nodes",       # by node the census works on max_nodes nodes, not on m
+    "census_other_per_slice",      # between 4 097 and 65 536 cells a row that is counted in n_other is counted once per 4 096 cells
+    "census_dev_adds",             # the _dev census adds to what the arrays held
+    "census_drops_solve",          # the census drops an uncommitted solve
+    "census_skips_zero_load_rows", # a row of load 0 is left out of out_rows
 )
 
 
@@ -145,7 +169,7 @@ def _at(ptr, count, dtype=np.uint32):
     """The `count` entries at "device" address ptr, as a writable array."""
     if not count:
         return np.zeros(0, dtype)
-    ct = {np.uint32: C.c_uint32, np.uint64: C.c_uint64}[dtype]
+    ct = {np.uint8: C.c_uint8, np.uint32: C.c_uint32, np.uint64: C.c_uint64}[dtype]
     return np.ctypeslib.as_array((ct * int(count)).from_address(int(ptr)))
 
 
@@ -167,6 +191,10 @@ class GpuPlacement:
         self._B = np.full(self._cap_rows, NONE, np.uint32)
         self._S = np.zeros(self._cap_rows, np.uint32)
         self._H = np.zeros(self._cap_rows, np.uint32)
+        self._K = np.zeros(self._cap_rows, np.uint8)
+        self._by_acc = np.zeros(256, np.uint64)  # (fault expc_by_class_accumulates: what the sweeps so far counted)
+        self._pos_dirty = None                    # (fault classes_batch_dirty_pos: the rows the last class batch named)
+        self._chain_ok, self._chained = False, 0  # lab: nothing a tick reads has changed since the last tick_async; links so far
         self._solved = None
         self._stale_used = None
         self._stale_aff = None
@@ -181,6 +209,7 @@ class GpuPlacement:
         """Every call that changes an input of the solve: the uncommitted solve is dropped."""
         self._solved = None
         self._stale_used = None
+        self._chain_ok = False
 
     def _sync_alive(self):
         self._alive_seen = self._alive.copy()
@@ -255,6 +284,8 @@ class GpuPlacement:
         before = self.get_nodes()[2]
         self._n = int(n)
         self._changed()
+        if self._fault == "num_objects_clears_classes":
+            self._K[:] = 0
         if self._fault == "num_objects_stale_used":
             self._stale_used = before
 
@@ -278,6 +309,10 @@ class GpuPlacement:
         return _oracle().lookup_batch(self._view()[0], idx)
 
     def update_batch(self, idx, node):
+        if self._pos_dirty is not None:
+            idx, node = np.asarray(idx, np.uint32), np.asarray(node, np.uint32)
+            keep = ~np.isin(idx, self._pos_dirty)
+            idx, node, self._pos_dirty = idx[keep], node[keep], None
         if _oracle().update_batch(self._view()[0], self._m, idx, node):
             raise _einval("update_batch")
         self._changed()
@@ -359,7 +394,11 @@ class GpuPlacement:
         return st
 
     def tick_async(self):
+        # a quiet tick behind a quiet tick is a link of a chain (the lab build chains whatever the table's size): the stand-in
+        # has no verdicts to wait for, so every tick_async behind one with nothing changed in between counts
+        self._chained += int(self._lab and self._chain_ok)
         self._done.append(self.tick())
+        self._chain_ok = True
 
     def tick_wait(self, cap=4096):
         out, self._done = self._done[-cap:], []
@@ -391,6 +430,8 @@ class GpuPlacement:
             self._stale_aff = old_aff if self._stale_aff is None else self._stale_aff
         if f == "remap_moves_seen":
             self._S[:n] = 0
+        if f == "remap_clears_classes":
+            self._K[:n] = 0
         return OK, out["evicted"]
 
     def remap_nodes(self, map):
@@ -628,6 +669,182 @@ class GpuPlacement:
             out_node[:len(rows)] = nodes
         return OK, n_idle
 
+    # ---- object classes
+    def _classes_written(self):
+        if self._fault == "classes_drop_solve":
+            self._changed()
+
+    def set_classes_raw(self, first_row, cls, rows=None):
+        cls = np.asarray(cls, np.uint8)
+        rows = len(cls) if rows is None else int(rows)
+        if first_row > self._n or rows > self._n - first_row:
+            return EINVAL
+        self._K[first_row:first_row + rows] = cls[:rows]
+        if self._fault == "classes_range_writes_past_end" and rows and first_row + rows < self._cap_rows:
+            self._K[first_row + rows] = cls[rows - 1]
+        self._classes_written()
+        return OK
+
+    def set_classes(self, first_row, cls):
+        if self.set_classes_raw(first_row, cls) != OK:
+            raise _einval("rio_gp_set_classes: the range exceeds the object table")
+
+    def set_classes_dev(self, first_row, d_cls, rows):
+        if first_row > self._n or rows > self._n - first_row:
+            raise _einval("rio_gp_set_classes: the range exceeds the object table")
+        self.set_classes(first_row, _at(d_cls, rows, np.uint8).copy())
+
+    def _class_batch(self, idx, cls):
+        idx, cls = np.asarray(idx, np.int64), np.asarray(cls, np.uint8)
+        if self._fault == "classes_batch_first_wins":
+            idx, cls = idx[::-1], cls[::-1]
+        self._K[idx] = cls        # (numpy assigns in order: of a repeated index the last value stays)
+        if self._fault == "classes_batch_dirty_pos" and len(idx):
+            self._pos_dirty = np.unique(idx).astype(np.uint32)
+        self._classes_written()
+
+    def set_class_batch_raw(self, idx, cls):
+        idx = np.asarray(idx, np.uint32)
+        if len(idx) and int(idx.max()) >= self._n:
+            return EINVAL
+        self._class_batch(idx, cls)
+        return OK
+
+    def set_class_batch(self, idx, cls):
+        if self.set_class_batch_raw(idx, cls) != OK:
+            raise _einval("rio_gp_set_class_batch: object index out of range")
+
+    def set_class_batch_dev_raw(self, d_idx, d_cls, n):
+        idx, cls = _at(d_idx, n).copy(), _at(d_cls, n, np.uint8).copy()
+        bad = idx >= self._n
+        ok = ~bad
+        if self._fault == "classes_dev_batch_stops_at_invalid" and bad.any():
+            ok[int(np.argmax(bad)):] = False
+        self._class_batch(idx[ok], cls[ok])
+        return EINVAL if bad.any() else OK
+
+    def get_classes(self):
+        return self._K[:self._n].copy()
+
+    def _expire_classes(self, cutoffs, cap):
+        """cap None: count only.  -> rows, nodes, n_idle, load_freed, idle_by_class"""
+        f = self._fault
+        cut = np.asarray(cutoffs, np.uint32).astype(np.int64)
+        nc = len(cut)
+        if not 1 <= nc <= 256:
+            raise _einval("rio_gp_expire_classes: 1 .. RIO_GP_MAX_CLASSES cutoffs are needed")
+        n = self._cap_rows if f == "expc_lists_hidden_rows" else self._n
+        col, k = self._col, self._K[:n].astype(np.int64)
+        if f == "expc_high_class_is_class_0":
+            k = np.where(k >= nc, 0, k)
+        if f == "expc_cutoff_inclusive":
+            cut = cut + 1
+        limit = np.concatenate([cut, np.zeros(256 - nc, np.int64)])     # behind the given classes: nothing is older than 0
+        idle = np.flatnonzero((col[:n] != NONE) & (self._S[:n] < limit[k])).astype(np.uint32)
+        before, solved = self.get_nodes()[2], self._solved
+        e = np.empty(0, np.uint32)
+        if cap is None:
+            listed, gone = e, (idle if f == "expc_count_only_writes" else e)
+        else:
+            listed = idle[:int(cap)]
+            gone = idle if f == "expc_unplaces_past_cap" else listed
+        by = np.bincount(k[listed if f == "expc_by_class_listed_only" else idle], minlength=256)[:nc].astype(np.uint64)
+        if f == "expc_by_class_accumulates":
+            self._by_acc[:nc] += by
+            by = self._by_acc[:nc].copy()
+        nodes = col[listed].copy()
+        freed = int(self._load[listed].astype(np.uint64).sum())
+        col[gone] = NONE
+        if len(listed):        # as rio_gp_remove_batch of the listed rows
+            self._changed()
+            if f == "expc_keeps_solve":
+                self._solved = solved
+        return listed, nodes, len(idle), freed, by
+
+    def expire_classes(self, cutoffs, cap=None, count_only=False):
+        cap = self._n if cap is None else min(int(cap), self._n)
+        if count_only or cap == 0:
+            r = self._expire_classes(cutoffs, None)
+            return r[:3] + (0, r[4])
+        return self._expire_classes(cutoffs, cap)
+
+    def expire_classes_dev(self, cutoffs, d_rows=None, d_node=None, cap=0):
+        if bool(d_rows) != bool(d_node) or (not d_rows and cap):
+            raise _einval("rio_gp_expire: the output rule")
+        rows, nodes, n_idle, freed, by = self._expire_classes(cutoffs, int(cap) if d_rows and cap else None)
+        if len(rows):
+            _at(d_rows, len(rows))[:] = rows
+            _at(d_node, len(rows))[:] = nodes
+        return n_idle, freed, by
+
+    def expire_classes_raw(self, n_classes, cutoffs, out_rows=None, out_node=None, cap=0, want_n_idle=True):
+        if not 1 <= n_classes <= 256 or cutoffs is None:
+            return EINVAL, 0
+        if not want_n_idle or (out_rows is None) != (out_node is None) or (out_rows is None and cap):
+            return EINVAL, 0
+        rows, nodes, n_idle, _, _ = self._expire_classes(np.asarray(cutoffs, np.uint32)[:n_classes],
+                                                         int(cap) if out_rows is not None and cap else None)
+        if len(rows):
+            out_rows[:len(rows)] = rows
+            out_node[:len(rows)] = nodes
+        return OK, n_idle
+
+    def _census(self, flags, nc):
+        """-> rc, rows, load (flat uint64, node-major), n_other"""
+        f = self._fault
+        by_node = bool(flags & CENSUS_BY_NODE)
+        m = (self._cap_nodes if f == "census_uses_max_nodes" else self._m) if by_node else 1
+        if flags & ~CENSUS_BY_NODE or not 1 <= nc <= 256 or m * nc > 1 << 20:
+            return EINVAL, None, None, 0
+        n = self._cap_rows if f == "census_counts_hidden_rows" else self._n
+        A = self._col[:n]
+        if f == "census_reads_solved" and self._solved is not None and len(self._solved) == n:
+            A = self._solved
+        cells = m * nc
+        rows, load, other = np.zeros(cells, np.uint64), np.zeros(cells, np.uint64), 0
+        r = np.flatnonzero(A != NONE)
+        a, c = A[r].astype(np.int64), self._K[r].astype(np.int64)
+        out = (c >= nc) | (a >= m if by_node else False)
+        other = int(out.sum())
+        r, cell = r[~out], ((a * nc if by_node else 0) + c)[~out]
+        if len(r):             # the rows sorted by cell: each cell is one run, counted and summed in uint64
+            order = np.argsort(cell, kind="stable")
+            w = self._load[r[order]].astype(np.uint64)
+            u, start = np.unique(cell[order], return_index=True)
+            one = (w != 0) if f == "census_skips_zero_load_rows" else np.ones(len(w), bool)
+            rows[u] = np.add.reduceat(one.astype(np.uint64), start)
+            load[u] = np.add.reduceat(w, start)
+        if f == "census_other_per_slice" and 4096 < cells <= 65536:
+            other *= -(-cells // 4096)
+        if f == "census_drops_solve":
+            self._changed()
+        return OK, rows, load, other
+
+    def census_raw(self, n_classes, by_node=False, flags=None):
+        fl = (CENSUS_BY_NODE if by_node else 0) if flags is None else int(flags)
+        rc, rows, load, other = self._census(fl, int(n_classes))
+        if rc != OK:
+            e = np.zeros(0, np.uint64)
+            return rc, e, e, 0
+        shape = (len(rows) // int(n_classes), int(n_classes)) if by_node else (int(n_classes),)
+        return rc, rows.reshape(shape), load.reshape(shape), other
+
+    def census(self, n_classes, by_node=False):
+        rc, rows, load, other = self.census_raw(n_classes, by_node)
+        if rc != OK:
+            raise _einval("rio_gp_census")
+        return rows, load, other
+
+    def census_dev(self, n_classes, d_rows, d_load, by_node=False):
+        rc, rows, load, other = self._census(CENSUS_BY_NODE if by_node else 0, int(n_classes))
+        if rc != OK or not d_rows or not d_load:
+            raise _einval("rio_gp_census")
+        cells = (self._m if by_node else 1) * int(n_classes)     # (the caller's arrays hold m * n_classes cells)
+        for p, v in ((d_rows, rows), (d_load, load)):
+            out = _at(p, cells, np.uint64)
+            out[:] = (out + v[:cells]) if self._fault == "census_dev_adds" else v[:cells]
+        return other
+
     # ---- measured load
     def _hits_add(self, idx, w):
         """H[idx[k]] += w[k], saturating: the sums in uint64 (fewer than 2^31 entries of less than 2^32 each)."""
@@ -777,7 +994,7 @@ class GpuPlacement:
         return None
 
     def chained_scans(self):
-        return 0
+        return self._chained
 
 
 def module(fault=None):

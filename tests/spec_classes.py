@@ -91,7 +91,11 @@ def census_np(A, K, load, n, n_classes, m=None):
     cell = (A[ok] * n_classes if by_node else 0) + K[ok]
     cells = (m if by_node else 1) * n_classes
     rows = np.bincount(cell, minlength=cells).astype(np.uint64)
-    lsum = np.zeros(cells, np.int64)
-    np.add.at(lsum, cell, load[ok])
+    # the load sums as two weighted counts of 16-bit halves: every partial sum stays below 2^53, so float64 holds it exactly
+    # (fewer than 2^37 rows); one pass each, where np.add.at walks the rows one by one
+    w = load[ok]
+    lo = np.bincount(cell, weights=w & 0xFFFF, minlength=cells).astype(np.uint64)
+    hi = np.bincount(cell, weights=w >> 16, minlength=cells).astype(np.uint64)
+    lsum = lo + (hi << np.uint64(16))
     shape = (m, n_classes) if by_node else (n_classes,)
-    return rows.reshape(shape), lsum.astype(np.uint64).reshape(shape), int(placed.sum() - ok.sum())
+    return rows.reshape(shape), lsum.reshape(shape), int(placed.sum() - ok.sum())

@@ -3,7 +3,8 @@ handle (tests/fake_rio_gp.py).
 
   - replay: the old family's seeds draw the tables and operations they drew before the extended op table existed
     (tests/golden/fuzz_old_family_ops.json, recorded from the earlier Scenario against the same stand-in);
-  - the extended seeds run clean: the model's own bookkeeping (n, the feed's checkpoint, the mirror, the uncommitted solve) holds;
+  - the extended seeds run clean: the model's own bookkeeping (n, the feed's checkpoint, the mirror, the uncommitted solve, the
+    stamps, the hits and the classes) holds;
   - the coverage floor: what the extended family exists for does happen in its default seeds;
   - sensitivity: with exactly one behaviour of the stand-in made wrong, the default extended seeds fail, naming the operation.
 """
@@ -88,6 +89,42 @@ FLOOR = (
     "by-load cut with zero-load candidates on an over node",
     "by-load cut between tick_async and tick_wait",
     "by-load cut on a handle whose m is below max_nodes",
+    "classes batch with duplicates of one row",
+    "classes range with unaligned start and end",
+    "classes with hidden rows holding classes",
+    "classes while a solve is uncommitted",
+    "classes between tick_async and tick_wait",
+    "classes batch right before an update batch of the same rows",
+    "classes_dev batch skipped invalid entries",
+    "class sweep un-placed rows",
+    "class sweep capped below n_idle",
+    "class sweep with rows of a class >= n_classes",
+    "class sweep with a placed row stamped exactly at its class's cutoff",
+    "class sweep as the first call of the section",
+    "class sweep right behind a class sweep",
+    "class sweep right behind a top",
+    "class sweep listed rows while a solve was uncommitted",
+    "class sweep hit nothing while a solve was uncommitted",
+    "class sweep between two pages of the feed",
+    "class sweep on a handle whose m is below max_nodes",
+    "class sweep between tick_async and tick_wait",
+    "class sweep with hidden placed rows older than their cutoff",
+    "class sweep with one cutoff on an all-zero class column",
+    "class sweep under one cutoff against rio_gp_expire's count",
+    "top right after a class sweep that listed rows",
+    "census by node in one slice",
+    "census by node in several slices",
+    "census by node beyond 65 536 cells",
+    "census with n_other > 0 by class",
+    "census with n_other > 0 by node",
+    "census at n == 0",
+    "census with n not a multiple of 4 and a placed row in the quad behind n",
+    "census with a cell whose load exceeds 2^32",
+    "census between two pages of the feed",
+    "census on a handle whose m is below max_nodes",
+    "census while a solve is uncommitted",
+    "census between tick_async and tick_wait",
+    "chained across a census",
 )
 
 # fault of the stand-in -> the operation the failure must name
@@ -139,6 +176,28 @@ FAULTS = {
     "by_load_is_row_order": "rebalance",
     "by_load_ties_shed_first_rows": "rebalance",
     "by_load_sheds_zero_load": "rebalance",
+    "classes_batch_first_wins": "classes",
+    "classes_dev_batch_stops_at_invalid": "classes",
+    "classes_range_writes_past_end": "classes",
+    "classes_drop_solve": "classes",
+    "classes_batch_dirty_pos": "classes",
+    "num_objects_clears_classes": "num_objects",
+    "remap_clears_classes": "remap",
+    "expc_cutoff_inclusive": "expire_classes",
+    "expc_high_class_is_class_0": "expire_classes",
+    "expc_by_class_listed_only": "expire_classes",
+    "expc_by_class_accumulates": "expire_classes",
+    "expc_unplaces_past_cap": "expire_classes",
+    "expc_lists_hidden_rows": "expire_classes",
+    "expc_keeps_solve": "expire_classes",
+    "expc_count_only_writes": "expire_classes",
+    "census_counts_hidden_rows": "census",
+    "census_reads_solved": "census",
+    "census_uses_max_nodes": "census",
+    "census_other_per_slice": "census",
+    "census_dev_adds": "census",
+    "census_drops_solve": "census",
+    "census_skips_zero_load_rows": "census",
 }
 
 
@@ -157,7 +216,8 @@ def test_op_tables():
                                  ("clean", 2), ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
     assert fuzz.Scenario.OPS_EXT[:len(fuzz.Scenario.OPS)] == fuzz.Scenario.OPS
     assert [a for a, _ in fuzz.Scenario.OPS_EXT[len(fuzz.Scenario.OPS):]] == ["index", "rebalance", "changes", "changes_reset",
-                                                                            "num_objects", "remap", "touch", "expire", "hits", "fold", "top"]
+                                                                            "num_objects", "remap", "touch", "expire", "hits", "fold", "top",
+                                                                            "classes", "expire_classes", "census"]
 
 
 @pytest.fixture(scope="module")
@@ -179,7 +239,9 @@ def test_extended_seeds_run_clean_and_use_every_new_operation(clean_run):
     for op in ("index", "rebalance", "changes", "changes_reset", "num_objects", "remap", "touch", "expire", "in flight: index",
                "in flight: changes", "in flight: rebalance", "in flight: remap", "in flight: touch", "in flight: expire",
                "mid run: touch", "mid run: expire count", "mid run: expire", "hits", "fold", "top", "in flight: hits",
-               "in flight: fold", "in flight: top", "mid run: hits", "mid run: fold", "mid run: top"):
+               "in flight: fold", "in flight: top", "mid run: hits", "mid run: fold", "mid run: top", "classes", "expire_classes",
+               "census", "in flight: classes", "in flight: expire_classes", "in flight: census", "mid run: classes",
+               "mid run: expire_classes count", "mid run: expire_classes", "mid run: census"):
         assert count.get(op, 0) > 0, (op, count)
 
 

@@ -42,7 +42,7 @@ between tick_async and tick_wait and in the middle of chained quiet runs; S is c
 every node removal (S names no node).
 
 Measured load, the hot-object report and the load-ordered rebalance cut are fuzzed the same way (the dense layer only: the string
-layer's calls are not in its fuzz yet).  The scenario keeps a model H of the hit column over every row the handle holds.  `hits`
+layer's calls are not in its fuzz yet, and neither are its classes calls).  The scenario keeps a model H of the hit column over every row the handle holds.  `hits`
 draws one of the family's writers (tests/spec_loads.py) — the host batch with and without weights, duplicates included (and one
 refused for an index >= n), the _dev batch (sometimes not 16-byte aligned; with invalid entries it applies the rest and reports
 RIO_GP_EINVAL), the merge host and _dev (rows 0, n, a boundary size, any, so every rows % 4; the _dev array sometimes behind 1-3
@@ -66,6 +66,33 @@ three new calls are also made between tick_async and tick_wait and in the middle
 run chained, a fold ends it), right behind an uncommitted solve, and — the report — right behind a sweep that listed rows and
 between two pages of the feed; H is compared again after every node removal and sweep, and H and the loads when hidden rows come
 back and, over every row, at the end.
+
+Object classes are fuzzed the same way (the dense layer only, as said above).  The scenario keeps a model K of the class column
+over every row the handle holds; only the setters change it.  `classes` draws one call of the setter family (tests/spec_classes.py) — the host range (start and end each at 0, n, a boundary
+size or any row, on every residue mod 4, the source 0-3 bytes into its buffer), the _dev range (the array behind 0-3 bytes of
+padding), a range reaching n + 1 (refused), the host batch (sizes from _BATCHES, half the time its second half naming the rows of
+the first again with classes of its own: the last entry wins), one with an index >= n (refused), the _dev batch (with invalid
+entries it applies the rest and reports RIO_GP_EINVAL) and a batch of 0 entries; the classes are all one, a few small ones, uniform
+over 0 .. 255, small ones with 255 and values beyond the n_classes later calls pass, or four different ones in every quad of rows —
+and rio_gp_get_classes must equal K[:n] after each, `used` and an uncommitted solve as they were.  About one batch in four is
+followed at once by an update batch over some of its rows: the election borrows rio_gp_update_batch's position scratch.
+`expire_classes` is op_expire with a cutoff per class (spec_classes.expire_classes_np; up to 4 096 rows the Python-integer
+expire_classes must agree first): n_classes from 1, 2, 3, 8, 64, 255, 256 and the largest class present (whose rows are then never
+idle), each cutoff 0, a placed row's own stamp, one above the largest stamp or 0xFFFFFFFF — per class, one value for every class,
+or 0 for all but one class — op_expire's caps and forms, idle_by_class given or NULL: rows, nodes, n_idle, load_freed and
+idle_by_class (every idle row, listed or not: it sums to n_idle) are exact, nothing is written past the listing, S and K do not
+change; under one cutoff for all 256 classes the count equals rio_gp_expire's, and on an all-zero column one cutoff lists what
+tests/spec_expire.py lists; n_classes 0 and 257 are refused.  `census` draws totals or RIO_GP_CENSUS_BY_NODE, host or _dev (into
+sentinel-filled arrays: the call overwrites), n_classes from 1, 2, 16, 17, 255, 256 or, by node, so that m * n_classes lies on
+and next to the boundaries of the kernel's forms (4 096, 65 536 and 2^20 cells, the first value past 2^20 refused) against
+spec_classes.census_np (up to 4 096 rows the Python-integer census must agree first): out_rows, out_load (uint64) and n_other are
+exact and sum to the placed rows and their load, and K, H, the column, `used` and an uncommitted solve are as they were; an unknown
+flag bit and n_classes 0 and 257 are refused.  All three are also called between tick_async and tick_wait and in the middle of
+chained quiet runs (only a class sweep that un-placed a row ends the chain), right behind an uncommitted solve, and — the sweep —
+right behind a report, behind another class sweep with a different n_classes and between two pages of the feed; a sweep or a census
+comes right behind a setter and a census right behind a fold now and then.  K is compared again after every node removal (on a
+handle no call of the section has touched it must come back all 0), sweep and change of n and, over every row, at the end; once
+per row-sharded scenario a setter, a sweep and a census on a shard handle are refused.
 
     python tests/test_gpu_fuzz.py <seconds> [first_seed]     # a longer campaign: old and extended scenarios alternate
 """
@@ -175,6 +202,12 @@ class Scenario:
         self.H = np.zeros(n, np.uint32)
         self.hits_used = self.fold_refused = self.fold_equal = False
         self.mark = self.after = None
+        # object classes: the model of the class column (rows >= n keep their value), whether a call of the section has been made
+        # (the first one allocates K, all 0), the n_classes of the last class sweep, whether the last one un-placed anything;
+        # in_mid: the operation runs in the middle of a chained quiet run (op_classes adds no writer of its own there)
+        self.K = np.zeros(n, np.uint8)
+        self.cls_used = self.expc_listed = self.in_mid = False
+        self.last_nc = None
         self.cov = {}
 
     def _caps(self):
@@ -247,7 +280,8 @@ class Scenario:
         want_st = []
         # extended scenarios, a quiet run: a call in the middle of it (see _mid_call); any run: a call between the last tick_async
         # and tick_wait, whose answer reflects every enqueued tick
-        # (the calls take turns, from a start the seed sets: sixteen of the default seeds have such runs, and each call gets one)
+        # (the calls take turns, from a start the seed sets: eighteen of the default seeds have such runs, one start each, and MID
+        #  holds fifteen entries, so each call gets one)
         mid = "none"
         if self.ext and quiet_run:
             mid = self.MID[(self.seed // 6 + self.mids) % len(self.MID)]
@@ -279,12 +313,13 @@ class Scenario:
             c = self.g.chained_scans() - watch[2]
             assert c == 4, (self.seed, watch[0], "quiet ticks after the call did not stay chained", c, self.log[-6:])
             self.cov["chained across a call"] = self.cov.get("chained across a call", 0) + 1
+            self._hit("chained across a census", watch[0] == "census")
         self.mark = None           # (a call in the middle of the run is not "right before" what follows the ticks after it)
         if self.ext and self.rng.random() < 0.7:
             self.in_flight = True
             try:
                 # (the calls take turns, from a start the seed sets: each of them gets a few of the default seeds' streams)
-                what = ("index", "changes", "rebalance", "remap", "touch", "expire", "hits", "fold", "top")[(self.seed + self.flights) % 9]
+                what = self.IN_FLIGHT[(self.seed + self.flights) % len(self.IN_FLIGHT)]
                 self.flights += 1
                 self.log.append("in flight: " + what)
                 self.count["in flight: " + what] = self.count.get("in flight: " + what, 0) + 1
@@ -299,10 +334,19 @@ class Scenario:
         call change nothing a tick reads: if the tick before was a link of a chain, the ticks after are.  A rebalance ends the
         chain, and so does a node removal.  A touch, a count-only sweep and a sweep that lists nothing change nothing either; a
         sweep that un-placed a row ends the chain ("expire" comes back as "expire count" when it listed nothing).  The hits calls
-        and the report change nothing; a legal fold ends the chain whatever it folds.
+        and the report change nothing; a legal fold ends the chain whatever it folds.  The class setters, the census, a count-only
+        class sweep and one that lists nothing change nothing; a class sweep that un-placed a row ends the chain.
         -> (what, the tick before chained, chained_scans() after the call)"""
         self.log.append("mid run: " + what)
         self.count["mid run: " + what] = self.count.get("mid run: " + what, 0) + 1
+        self.in_mid = True
+        try:
+            what = self._mid_op(what)
+        finally:
+            self.in_mid = False
+        return what, last_chained, self.g.chained_scans() if self.lab else 0
+
+    def _mid_op(self, what):
         if what == "index":
             self.op_index()
         elif what == "changes":
@@ -322,9 +366,18 @@ class Scenario:
         elif what == "expire":
             if not self.op_expire(hit=True):
                 what = "expire count"
+        elif what == "classes":
+            self.op_classes()
+        elif what == "census":
+            self.op_census()
+        elif what == "expire_classes count":
+            self.op_expire_classes(hit=False)
+        elif what == "expire_classes":
+            if not self.op_expire_classes(hit=True):
+                what = "expire_classes count"
         else:
             self.op_remap(legal=True)     # (a refused map changes nothing: only a legal one must end the chain)
-        return what, last_chained, self.g.chained_scans() if self.lab else 0
+        return what
 
     def op_flip(self):
         rng, m = self.rng, self.m
@@ -735,6 +788,8 @@ class Scenario:
             self._seen_check((self.seed, "num_objects", "the stamps of rows that were hidden", self.log[-6:]))
         if grew and self.hits_used:    # their hits and loads: no hits call and no fold reaches a hidden row
             self._hits_check((self.seed, "num_objects", "the hits and loads of rows that were hidden", self.log[-6:]), loads=True)
+        if self.cls_used:              # K is per row of max_objects: a changing n leaves it alone, going down and coming back
+            self._cls_check((self.seed, "num_objects", "the classes of the rows below n", self.log[-6:]))
 
     def _remap_draw(self):
         """A legal map for rio_gp_remap_nodes, at least one node kept: identity | permutation | swap | drop one | drop several
@@ -854,6 +909,8 @@ class Scenario:
             self._seen_check(tag + ("the last-seen column changed",))
         if self.hits_used:             # nor does H
             self._hits_check(tag + ("the hit column changed",))
+        # nor does K (asked every time: on a handle no call of the section has touched, this is its first and returns zeros)
+        self._cls_check(tag + ("the class column changed",))
         if had_solve:
             self._dropped("remap")
         self._hit("remap removed nodes that held rows", ev > 0)
@@ -1059,6 +1116,8 @@ class Scenario:
         self._seen_check(tag)          # a sweep reads S and never writes it
         if self.hits_used:             # and H is no business of its
             self._hits_check(tag)
+        if self.cls_used:              # nor is K
+            self._cls_check(tag)
         if L > 0:
             self.mark = "expire listed"
             self.pending = None
@@ -1241,6 +1300,7 @@ class Scenario:
         self._hit("fold changed no load", want["rows_changed"] == 0)
         self._hit("fold clamped every load to one value", self.fold_equal)
         assert st == want, tag + ("statistics", st, want)
+        self.mark = "fold"         # (run() sends a census right behind now and then: it sums the loads the fold has just written)
         self._hits_check(tag, loads=True)     # (H is zero on [:n], the loads are the model's)
         self.check_table("fold")              # (`used` is that of the new loads)
         if had_solve:
@@ -1321,6 +1381,8 @@ class Scenario:
         self._hit("top with cap above n_candidates", cap > n_cand)
         self._hit("top between two pages of the feed", self.page_open)
         self._hit("top right after an expire that listed rows", self.after == "expire listed")
+        self._hit("top right after a class sweep that listed rows", self.after == "class sweep listed")
+        self.mark = "top"          # (the class sweep shares the report's scratch as well: run() sends one right behind)
         self._hit("top while a solve is uncommitted", self.pending is not None)
         self._hit("top between tick_async and tick_wait", self.in_flight)
         self._hit("top on a handle whose m is below max_nodes", self.m < self.m0)
@@ -1365,6 +1427,398 @@ class Scenario:
         self._read_only("top")
         self.check_table("top")
 
+    # ---- object classes: the setters, rio_gp_expire_classes and rio_gp_census against tests/spec_classes.py ---------------------
+    def _cls_check(self, tag):
+        got = self.g.get_classes()
+        if not self.cls_used and not self.K.any():      # no setter has run: this call, or the one before, allocated K, all 0
+            assert not got.any(), tag + ("the class column of an untouched handle is not zero", np.flatnonzero(got)[:8])
+        self.cls_used = True
+        assert np.array_equal(got, self.K[:self.n]), tag + ("get_classes differs from the model", np.flatnonzero(got != self.K[:self.n])[:8])
+
+    def _cls_values(self, rows):
+        """One class per entry of `rows` (the row each value goes to): all one class | a few small classes | uniform over
+        0 .. 255 | small ones, 255 and values beyond the n_classes later calls pass | four different classes in every quad of rows."""
+        rng, k = self.rng, len(rows)
+        kind = int(rng.integers(5))
+        if kind == 0:
+            return np.full(k, int(rng.integers(256)), np.uint8)
+        if kind == 1:
+            return rng.integers(0, 4, k).astype(np.uint8)
+        if kind == 2:
+            return rng.integers(0, 256, k).astype(np.uint8)
+        if kind == 3:
+            return rng.choice(np.array([0, 1, 2, 3, 7, 8, 15, 16, 17, 63, 64, 200, 254, 255], np.uint8), k)
+        base = rng.choice(256, 4, replace=False).astype(np.uint8)
+        return base[np.asarray(rows, np.int64) % 4]
+
+    def _row_edge(self):
+        """Where a range starts or ends: 0 | n | a boundary size | any row — half the time up to 3 rows beside it, so that every
+        residue mod 4 occurs at each of them."""
+        rng, n = self.rng, self.n
+        v = (0, n, _pick(rng, _SIZES, n) if n else 0, int(rng.integers(0, n + 1)))[int(rng.integers(4))]
+        if rng.random() < 0.5:
+            v += int(rng.integers(-3, 4))
+        return min(max(v, 0), n)
+
+    def op_classes(self):
+        """One call of the setter family against spec_classes.set_classes / set_class_batch; rio_gp_get_classes must equal K[:n]
+        after each, `used` and an uncommitted solve as they were.  About one batch in four is followed at once by an update batch
+        over some of its rows: the election borrows rio_gp_update_batch's position scratch and has to hand it back all ones."""
+        import spec_classes
+        rng, n, g = self.rng, self.n, self.g
+        form = ("range", "range", "range dev", "range refused", "batch", "batch", "batch refused", "batch dev", "batch dev",
+                "batch empty")[int(rng.integers(10))]
+        tag = (self.seed, "classes", form, n, self.log[-6:])
+        had_solve = self.pending is not None
+        self._hit("classes with hidden rows holding classes", bool(self.K[n:].any()))
+        self._hit("classes while a solve is uncommitted", had_solve)
+        self._hit("classes between tick_async and tick_wait", self.in_flight)
+        bufs, unaligned, dup, skipped, updated = [], False, False, False, False
+        if form in ("range", "range dev"):
+            a, b = sorted((self._row_edge(), self._row_edge()))
+            cls = self._cls_values(np.arange(a, b))
+            off = int(rng.integers(0, 4))            # the source 0 .. 3 bytes into its buffer
+            src = np.zeros(b - a + 3, np.uint8)
+            src[off:off + b - a] = cls
+            unaligned = a % 4 != 0 and b % 4 != 0 and b > a
+            if form == "range":
+                rc = g.set_classes_raw(a, src[off:off + b - a])
+                assert rc == self.gp.OK, tag + (a, b, rc)
+            else:
+                d = self._devbuf()(src)
+                bufs.append(d)
+                g.set_classes_dev(a, d.ptr + off, b - a)
+            self.K = spec_classes.set_classes(self.K, a, cls)
+        elif form == "range refused":         # first_row + rows = n + 1: nothing changes
+            a = int(rng.integers(0, n + 1))
+            cls = np.full(n + 1 - a, 1 + int(rng.integers(255)), np.uint8)
+            if rng.random() < 0.5:
+                rc = g.set_classes_raw(a, cls)
+                assert rc == self.gp.EINVAL, tag + (a, rc)
+            else:
+                d = self._devbuf()(cls)
+                bufs.append(d)
+                self._refused(lambda: g.set_classes_dev(a, d.ptr, len(cls)), tag)
+        elif form == "batch empty":
+            if rng.random() < 0.5:
+                rc = g.set_class_batch_raw(np.zeros(0, np.uint32), np.zeros(0, np.uint8))
+            else:
+                rc = g.set_class_batch_dev_raw(None, None, 0)
+            assert rc == self.gp.OK, tag + (rc,)
+        else:
+            idx = self._idx(big_ok=False) if n else np.zeros(0, np.uint32)
+            if idx.size > 1 and rng.random() < 0.5:      # the second half names the rows of the first again, with classes of its own
+                h = idx.size // 2
+                idx[idx.size - h:] = idx[:h]
+            cls = self._cls_values(idx)
+            if form == "batch refused":       # validated first: one index >= n, nothing changes
+                bad = np.append(idx, np.uint32(0))
+                bad[int(rng.integers(bad.size))] = self._beyond_n()
+                rc = g.set_class_batch_raw(bad, np.append(cls, np.uint8(1)))
+                assert rc == self.gp.EINVAL, tag + (rc,)
+            else:
+                if form == "batch dev":       # invalid entries among them: the rest is applied, the call reports RIO_GP_EINVAL
+                    if rng.random() < 0.7:
+                        idx, cls = np.append(idx, np.uint32(0)), np.append(cls, np.uint8(rng.integers(256)))
+                        for k in rng.integers(0, idx.size, int(rng.integers(1, 5))):
+                            idx[int(k)] = self._beyond_n()
+                    d, ptr = self._dev_offset(idx)
+                    off = int(rng.integers(0, 4))
+                    dc = self._devbuf()(np.concatenate([np.zeros(off, np.uint8), cls]))
+                    bufs += [d, dc]
+                    rc = g.set_class_batch_dev_raw(ptr, dc.ptr + off, idx.size)
+                    ok = idx < n
+                    skipped = not ok.all()
+                    assert rc == (self.gp.EINVAL if skipped else self.gp.OK), tag + (rc, skipped)
+                    idx, cls = idx[ok], cls[ok]
+                else:
+                    rc = g.set_class_batch_raw(idx, cls)
+                    assert rc == self.gp.OK, tag + (rc,)
+                K2 = spec_classes.set_class_batch(self.K, idx, cls)
+                if idx.size:                  # is there a row whose first entry carries another class than its last?
+                    first = np.zeros(self.nmax, np.uint8)
+                    first[idx[::-1]] = cls[::-1]
+                    u = np.unique(idx)
+                    dup = bool((first[u] != K2[u]).any())
+                self.K = K2
+                if idx.size and not (had_solve or self.in_flight or self.in_mid) and rng.random() < 0.3:
+                    # an update batch over some of the same rows, and nothing in between
+                    sub = idx[rng.random(idx.size) < 0.5]
+                    sub = sub if sub.size else idx[:1]
+                    node = rng.integers(0, self.m, sub.size).astype(np.uint32)
+                    node[rng.random(sub.size) < 0.05] = NONE
+                    g.update_batch(sub, node)
+                    self.oracle.update_batch(self.ref[:n], self.m, sub, node)
+                    self.page_writer = updated = True
+        self._hit("classes range with unaligned start and end", unaligned)
+        self._hit("classes batch with duplicates of one row", dup)
+        self._hit("classes_dev batch skipped invalid entries", skipped)
+        self._hit("classes batch right before an update batch of the same rows", updated)
+        self.mark = "classes"
+        self._cls_check(tag)       # (it waits: rio_gp_set_classes_dev does not, and its buffer is freed below)
+        for d in bufs:
+            d.free()
+        self._read_only("classes")
+        self.check_table("classes" + (" + update" if updated else ""))
+
+    def _class_cutoffs(self, nc, placed, hit):
+        """One cutoff per class -> (kind, cutoffs).  Each is 0 | the stamp of a placed row of the class (the comparison is
+        strict) | one above the largest stamp | 0xFFFFFFFF: drawn per class, or one value for every class, or 0 for every class
+        but one.  hit True: every class above every stamp but 0xFFFFFFFF."""
+        rng, n, S, K = self.rng, self.n, self.S, self.K
+        top = min(int(S[:n].max()) + 1 if n else 1, 0xFFFFFFFF)
+        if hit is True:
+            return "all idle", rng.choice(np.array([top, 0xFFFFFFFF], np.uint32), nc)
+        own = np.zeros(nc, np.uint32)
+        if len(placed):
+            p = placed[rng.integers(0, len(placed), min(len(placed), 2048))]
+            own[:] = S[p[0]]
+            sel = K[p] < nc
+            own[K[p][sel]] = S[p][sel]
+        kind = ("per class", "all equal", "one class")[int(rng.integers(3))]
+        if kind == "all equal":
+            return kind, np.full(nc, (0, int(own[rng.integers(nc)]), top, 0xFFFFFFFF)[int(rng.integers(4))], np.uint32)
+        if kind == "one class":
+            cut = np.zeros(nc, np.uint32)
+            here = np.unique(K[placed])
+            here = here[here < nc]
+            c = int(here[rng.integers(len(here))]) if len(here) else int(rng.integers(nc))
+            cut[c] = (top, 0xFFFFFFFF, max(int(own[c]), 1))[int(rng.integers(3))]
+            return kind, cut
+        pick = rng.integers(0, 4, nc)
+        return kind, np.array([0, 0, top, 0xFFFFFFFF], np.uint32)[pick] + own * (pick == 1).astype(np.uint32)
+
+    def op_expire_classes(self, hit=None):
+        """rio_gp_expire_classes[_dev] against spec_classes.expire_classes_np (up to 4 096 rows the Python-integer expire_classes
+        must agree with it first) over the model's column, stamps, classes and loads; the bookkeeping is op_expire's.  hit: None —
+        everything is drawn; True — a listing that un-places a row when any placed row can be idle; False — a count-only call or
+        every cutoff 0.  -> rows un-placed."""
+        import spec_classes
+        import spec_expire
+        rng, n, g = self.rng, self.n, self.g
+        S, A, K = self.S, self.ref, self.K
+        had_solve = self.pending is not None
+        if hit is None and rng.random() < (0.3 if had_solve else 0.1):      # n_classes 0 | 257: refused, nothing changes
+            nc = (0, 257)[int(rng.integers(2))]
+            tag = (self.seed, "expire_classes", "refused", nc, n, self.log[-6:])
+            out = [np.full(6, 0xDEADBEEF, np.uint32) for _ in range(2)]
+            if rng.random() < 0.5:
+                rc, _ = g.expire_classes_raw(nc, np.full(257, 0xFFFFFFFF, np.uint32))
+            else:
+                rc, _ = g.expire_classes_raw(nc, np.full(257, 0xFFFFFFFF, np.uint32), out[0], out[1], 4)
+            assert rc == self.gp.EINVAL and all((x == 0xDEADBEEF).all() for x in out), tag + (rc,)
+            self._hit("class sweep refused with a solve uncommitted", had_solve)
+            self.expc_listed = False
+            if self.cls_used:
+                self._cls_check(tag)
+            self._read_only("expire_classes refused")
+            self.check_table("expire_classes refused")
+            return 0
+        placed = np.flatnonzero(A[:n] != NONE)
+        first, zero = not self.cls_used, not K[:n].any()
+        nc = int((1, 2, 3, 8, 64, 255, 256, max(int(K[:n].max()) if n else 0, 1))[int(rng.integers(8))])
+        form = ("host", "dev", "host", "dev", "count", "dev count")[int(rng.integers(6))]
+        if hit is None and had_solve and rng.random() < 0.5:
+            hit = True                 # (a sweep that must drop the solve, not one of the many that list nothing)
+        behind = self.after in ("class sweep", "class sweep listed")
+        if hit is True:
+            form = form if form in ("host", "dev") else ("host", "dev")[int(rng.integers(2))]
+            nc = 256 if not behind or self.last_nc != 256 else 255
+        elif behind and nc == self.last_nc:   # right behind another sweep: a different n_classes, so that copies of the
+            nc = 256 if nc != 256 else 3      # per-class counts the sweep before did not zero are added to this one's
+        plain = hit is None and zero and rng.random() < 0.25
+        if plain:                      # every class is 0: one cutoff is rio_gp_expire's
+            nc = 1
+        kind, cut = self._class_cutoffs(nc, placed, hit)
+        if kind == "all equal" and not plain and rng.random() < 0.5:
+            nc, cut = 256, np.full(256, cut[0], np.uint32)
+        if hit is False:
+            if rng.random() < 0.5:
+                cut[:] = 0
+            else:
+                form = form if form in ("count", "dev count") else ("count", "dev count")[int(rng.integers(2))]
+        listing = form in ("host", "dev")
+        idle, _, n_idle, _, _, by_all = spec_classes.expire_classes_np(A, S, K, self.load, n, cut, None)
+        cap = self._expire_cap(idle, n_idle) if listing else None
+        if hit is True and cap == 0:
+            cap = 1
+        want_cap = cap if listing else 0
+        wrows, wnodes, w_idle, wfreed, A2, wby = spec_classes.expire_classes_np(A, S, K, self.load, n, cut, want_cap)
+        L = len(wrows)
+        tag = (self.seed, "expire_classes", form, nc, kind, cap, n, self.log[-6:])
+        assert w_idle == n_idle and np.array_equal(wby, by_all) and int(wby.sum()) == n_idle, tag + ("the reference counts by cap",)
+        if n <= 4096:      # the row-by-row restatement as well
+            p = spec_classes.expire_classes(A, S, K, self.load, n, [int(x) for x in cut], want_cap)
+            assert (np.array_equal(p[0], wrows) and np.array_equal(p[1], wnodes) and p[2:4] == (w_idle, wfreed) and
+                    np.array_equal(p[4], A2) and np.array_equal(p[5], wby)), tag + ("the two references differ",)
+        if nc == 1 and zero:           # ... and rio_gp_expire's own restatement
+            e = spec_expire.expire(A, S, self.load, n, int(cut[0]), want_cap)
+            assert (np.array_equal(e[0], wrows) and np.array_equal(e[1], wnodes) and tuple(e[2:4]) == (w_idle, wfreed) and
+                    np.array_equal(e[4], A2)), tag + ("spec_expire lists something else on an all-zero class column",)
+        Kp, Sp = K[placed], S[placed]
+        inside = Kp < nc
+        self._hit("class sweep un-placed rows", L > 0)
+        self._hit("class sweep capped below n_idle", 0 < L < n_idle)
+        self._hit("class sweep with rows of a class >= n_classes", bool((~inside).any()))
+        self._hit("class sweep with a placed row stamped exactly at its class's cutoff",
+                  bool(((cut[Kp[inside]] > 0) & (Sp[inside] == cut[Kp[inside]])).any()))
+        self._hit("class sweep as the first call of the section", first)
+        self._hit("class sweep right behind a class sweep", behind and self.last_nc != nc)
+        self._hit("class sweep right behind a top", self.after == "top")
+        self._hit("class sweep listed rows while a solve was uncommitted", had_solve and L > 0)
+        self._hit("class sweep hit nothing while a solve was uncommitted", had_solve and L == 0)
+        self._hit("class sweep between two pages of the feed", self.page_open)
+        self._hit("class sweep on a handle whose m is below max_nodes", self.m < self.m0)
+        self._hit("class sweep between tick_async and tick_wait", self.in_flight)
+        self._hit("class sweep with hidden placed rows older than their cutoff",
+                  bool(((A[n:] != NONE) & (K[n:] < nc) & (S[n:] < cut[np.minimum(K[n:], nc - 1)])).any()))
+        self._hit("class sweep with one cutoff on an all-zero class column", nc == 1 and zero)
+        if kind == "all equal" and nc == 256:
+            # every class under one cutoff c: as many idle rows as rio_gp_expire(c) counts (two count-only calls: nothing changes)
+            a = g.expire(int(cut[0]), count_only=True)[2]
+            b = g.expire_classes(cut, count_only=True)[2]
+            assert a == b == n_idle, tag + ("count-only rio_gp_expire and the class sweep under one cutoff differ", a, b, n_idle)
+            self._hit("class sweep under one cutoff against rio_gp_expire's count")
+        by = None
+        if form == "count":
+            rows, nodes, got_idle, freed, by = g.expire_classes(cut, count_only=True)
+        elif form == "dev count":
+            got_idle, freed, by = g.expire_classes_dev(cut)
+            rows = nodes = np.zeros(0, np.uint32)
+        elif form == "host" and (cap is None or rng.random() < 0.5):
+            rows, nodes, got_idle, freed, by = g.expire_classes(cut, cap)
+        elif form == "host":   # the call as given, into sentinel-filled arrays of cap + 2, without load_freed and idle_by_class
+            out = [np.full(cap + 2, 0xDEADBEEF, np.uint32) for _ in range(2)]
+            rc, got_idle = g.expire_classes_raw(nc, cut, out[0], out[1], cap)
+            assert rc == self.gp.OK, tag + (rc,)
+            assert all((x[L:] == 0xDEADBEEF).all() for x in out), tag + ("written past the listing",)
+            rows, nodes, freed = out[0][:L], out[1][:L], wfreed
+        else:
+            c = n if cap is None else int(cap)
+            d = [self._devbuf()(np.full(c + 2, 0xDEADBEEF, np.uint32)) for _ in range(2)]
+            got_idle, freed, by = g.expire_classes_dev(cut, d[0].ptr, d[1].ptr, c)
+            rows, nodes = (x.to_host() for x in d)
+            for x in d:
+                x.free()
+            assert all((x[L:] == 0xDEADBEEF).all() for x in (rows, nodes)), tag + ("written past the listing",)
+            rows, nodes = rows[:L], nodes[:L]
+        assert got_idle == n_idle, tag + ("n_idle", got_idle, n_idle)
+        assert np.array_equal(rows, wrows) and np.array_equal(nodes, wnodes), tag + (rows[:8], wrows[:8], nodes[:8], wnodes[:8])
+        assert freed == wfreed, tag + ("load_freed", freed, wfreed)
+        if by is not None:             # every idle row of the class, listed or not
+            assert len(by) == nc and np.array_equal(by, wby), tag + ("idle_by_class", np.flatnonzero(by != wby)[:8], by[:8], wby[:8])
+            assert int(by.sum()) == got_idle, tag + ("idle_by_class does not sum to n_idle", int(by.sum()), got_idle)
+        self.ref = A2
+        self.expc_listed, self.last_nc = L > 0, nc
+        self._seen_check(tag)          # a sweep reads S and K and never writes them (it is a call of the touch section too: S exists)
+        self._cls_check(tag)
+        if self.hits_used:
+            self._hits_check(tag)
+        if L > 0:
+            self.mark = "class sweep listed"
+            self.pending = None
+            if had_solve:
+                self._dropped("expire_classes")
+        else:
+            self.mark = "class sweep"
+            self._read_only("expire_classes")
+        self.check_table("expire_classes")
+        return L
+
+    def _census_classes(self, by_node):
+        """n_classes of a census: totals — 1, 2, 16, 17, 255, 256; by node — the last value on this side of each boundary of the
+        kernel's forms (4 096, 65 536 and 2^20 cells) and the first beyond it, as far as m leaves them inside 1 .. 256, or any."""
+        rng, m = self.rng, self.m
+        if not by_node:
+            return int((1, 2, 16, 17, 255, 256)[int(rng.integers(6))])
+        if (1 << 20) % m == 0 and (1 << 20) // m <= 256 and rng.random() < 0.3:
+            return (1 << 20) // m      # exactly 2^20 cells: the most the call takes
+        c = {int(rng.integers(1, 257))}
+        for lim in (4096, 65536, 1 << 20):
+            c.update((lim // m, lim // m + 1))
+        c = sorted(v for v in c if 1 <= v <= 256)
+        return int(c[rng.integers(len(c))])
+
+    def op_census(self):
+        """rio_gp_census[_dev] against spec_classes.census_np (up to 4 096 rows the Python-integer census must agree with it
+        first): out_rows, out_load and n_other exact, the _dev arrays overwritten, nothing changed."""
+        import spec_classes
+        rng, n, m, g = self.rng, self.n, self.m, self.g
+        A, K = self.ref, self.K
+        by_node, dev = bool(rng.random() < 0.6), bool(rng.random() < 0.4)
+        nc = self._census_classes(by_node)
+        if self.after == "fold" and rng.random() < 0.6:
+            # right behind a fold, which is what takes loads to 2^24 and beyond: few cells, so that one of them passes 2^32
+            by_node, nc = False, int(rng.integers(1, 3))
+        bad =("flag", "n_classes 0", "n_classes 257")[int(rng.integers(3))] if rng.random() < 0.12 else None
+        nc = {"n_classes 0": 0, "n_classes 257": 257}.get(bad, nc)
+        if bad is None and by_node and m * nc > 1 << 20:
+            bad = "cells"
+        cells = (m if by_node else 1) * nc
+        shape = (m, nc) if by_node else (nc,)
+        had_solve = self.pending is not None
+        tag = (self.seed, "census", "by node" if by_node else "totals", "dev" if dev else "host", nc, m, n, bad, self.log[-6:])
+        SENT = 0xDEADBEEFDEADBEEF
+        if bad is not None:      # an unknown flag bit | n_classes 0 or 257 | more than 2^20 cells: refused, nothing changes
+            if dev and bad != "flag":
+                d = [self._devbuf()(np.full(cells + 1, SENT, np.uint64)) for _ in range(2)]
+                self._refused(lambda: g.census_dev(nc, d[0].ptr, d[1].ptr, by_node), tag)
+                out = [x.to_host(np.uint64) for x in d]
+                for x in d:
+                    x.free()
+                assert all((x == SENT).all() for x in out), tag + ("a refused census wrote",)
+            else:
+                flags = int(by_node) | ((2, 4, 1 << 31)[int(rng.integers(3))] if bad == "flag" else 0)
+                rc = g.census_raw(nc, by_node, flags)[0]
+                assert rc == self.gp.EINVAL, tag + (rc,)
+            self._hit("census refused for more than 2^20 cells", bad == "cells")
+            self._read_only("census refused")
+            self.check_table("census refused")
+            return
+        wrows, wload, wother = spec_classes.census_np(A, K, self.load, n, nc, m if by_node else None)
+        if n <= 4096:      # the row-by-row restatement as well
+            p = spec_classes.census(A, K, self.load, n, nc, m if by_node else None)
+            assert p[0] == wrows.tolist() and p[1] == wload.tolist() and p[2] == wother, tag + ("the two references differ",)
+        on = A[:n] != NONE
+        counted = on & (K[:n] < nc)
+        self._hit("census by node in one slice", by_node and cells <= 4096)
+        self._hit("census by node in several slices", by_node and 4096 < cells <= 65536)
+        self._hit("census by node beyond 65 536 cells", by_node and cells > 65536)
+        self._hit("census by node of exactly 2^20 cells", by_node and cells == 1 << 20)
+        self._hit("census with n_other > 0 by class", not by_node and wother > 0)
+        self._hit("census with n_other > 0 by node", by_node and wother > 0)
+        self._hit("census at n == 0", n == 0)
+        self._hit("census with n not a multiple of 4 and a placed row in the quad behind n",
+                  n % 4 != 0 and bool((A[n:(n | 3) + 1] != NONE).any()))
+        self._hit("census with a cell whose load exceeds 2^32", bool(wload.size) and int(wload.max()) > 1 << 32)
+        self._hit("census as the first call of the section", not self.cls_used)
+        self._hit("census between two pages of the feed", self.page_open)
+        self._hit("census on a handle whose m is below max_nodes", m < self.m0)
+        self._hit("census while a solve is uncommitted", had_solve)
+        self._hit("census between tick_async and tick_wait", self.in_flight)
+        if dev:            # into arrays that hold a sentinel: the call overwrites every cell and nothing behind them
+            d = [self._devbuf()(np.full(cells + 1, SENT, np.uint64)) for _ in range(2)]
+            other = g.census_dev(nc, d[0].ptr, d[1].ptr, by_node)
+            rows, lsum = (x.to_host(np.uint64) for x in d)
+            for x in d:
+                x.free()
+            assert rows[cells] == SENT and lsum[cells] == SENT, tag + ("written past the cells",)
+            rows, lsum = rows[:cells].reshape(shape), lsum[:cells].reshape(shape)
+        else:
+            rc, rows, lsum, other = g.census_raw(nc, by_node)
+            assert rc == self.gp.OK, tag + (rc,)
+            assert rows.shape == shape and lsum.shape == shape, tag + ("the arrays are not [m][n_classes]", rows.shape, shape)
+        assert other == wother, tag + ("n_other", other, wother)
+        assert np.array_equal(rows, wrows), tag + ("out_rows", np.flatnonzero(rows.ravel() != wrows.ravel())[:8])
+        assert np.array_equal(lsum, wload), tag + ("out_load", np.flatnonzero(lsum.ravel() != wload.ravel())[:8])
+        assert int(rows.sum()) + other == int(on.sum()), tag + ("out_rows and n_other do not sum to the placed rows",)
+        assert int(lsum.sum()) == int(self.load[:n][counted].astype(np.uint64).sum()), tag + ("out_load does not sum to the counted rows' load",)
+        self._cls_check(tag)       # read-only: K, H, the column, `used` and an uncommitted solve are as they were
+        if self.hits_used:
+            self._hits_check(tag)
+        self._read_only("census")
+        self.check_table("census")
+
     def finish_feed(self):
         """The end of an extended scenario: the rest of the feed is paged out — three small pages, then pages of a third of what
         is left, so that a table of 10^5 changed rows does not take 10^4 calls — and the mirror equals the column on rows < n."""
@@ -1381,17 +1835,23 @@ class Scenario:
                                                            self.log[-6:], np.flatnonzero(self.mirror[:self.n] != got)[:8])
 
     NEED_ROWS = ("update", "remove", "lookup", "place", "mixed", "attrs")                       # skipped while n == 0
-    WRITERS = ("tick", "solve", "async", "update", "remove", "clean", "place", "mixed", "rebalance", "num_objects", "remap", "expire")
+    WRITERS = ("tick", "solve", "async", "update", "remove", "clean", "place", "mixed", "rebalance", "num_objects", "remap", "expire",
+               "expire_classes")
     DROPS_SOLVE = ("tick", "rebalance", "update", "remove", "clean", "place", "mixed", "attrs", "caps", "num_objects", "remap", "expire",
-                   "fold")     # (the fold rewrites loads, not the column: it drops the solve and is no writer of the feed)
-    MID = ("none", "index", "changes", "rebalance", "remap", "touch", "expire count", "expire", "hits", "top", "fold")   # op_async: a call in a quiet run
-    ENDS_CHAIN = ("rebalance", "remap", "expire", "fold")   # ... after which the next tick must not chain (an "expire" un-placed a row)
+                   "fold", "expire_classes")   # (the fold rewrites loads, not the column: it drops the solve and is no writer of the feed)
+    MID = ("none", "index", "changes", "rebalance", "remap", "touch", "expire count", "expire", "hits", "top", "fold",
+           "classes", "census", "expire_classes count", "expire_classes")   # op_async: a call in a quiet run
+    # ... after which the next tick must not chain (an "expire" or an "expire_classes" un-placed a row)
+    ENDS_CHAIN = ("rebalance", "remap", "expire", "fold", "expire_classes")
+    # op_async: the calls that take turns between the last tick_async and tick_wait
+    IN_FLIGHT = ("index", "changes", "rebalance", "remap", "touch", "expire", "hits", "fold", "top", "classes", "expire_classes", "census")
 
     OPS = (("tick", 5), ("solve", 2), ("async", 3), ("flip", 4), ("update", 2), ("remove", 2), ("lookup", 1), ("clean", 2),
            ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
 
     OPS_EXT = OPS + (("index", 3), ("rebalance", 6), ("changes", 5), ("changes_reset", 1), ("num_objects", 2), ("remap", 3),
-                     ("touch", 4), ("expire", 4), ("hits", 4), ("fold", 3), ("top", 4))
+                     ("touch", 4), ("expire", 4), ("hits", 4), ("fold", 3), ("top", 4), ("classes", 6), ("expire_classes", 4),
+                     ("census", 4))
 
     def run(self):
         names = [a for a, w in (self.OPS_EXT if self.ext else self.OPS) for _ in range(w)]
@@ -1401,14 +1861,18 @@ class Scenario:
                 op = names[int(self.rng.integers(len(names)))]
                 if self.ext and self.chain_small and self.mids == 0 and i == k - 1:
                     op = "async"       # (no quiet run yet: see op_async)
-                if self.ext and self.pending is not None and self.rng.random() < 0.75:
+                elif self.ext and self.pending is not None and self.rng.random() < 0.75:
                     # an uncommitted solve lives until the next writer: three times in four the calls that must keep it, or must drop
                     # it themselves, come right behind it (the table's weights alone bring them there a few times in the default seeds)
                     op = ("index", "remap", "rebalance", "remap", "touch", "expire", "expire", "hits", "top", "top", "fold", "fold",
-                          "fold")[int(self.rng.integers(13))]
+                          "fold", "classes", "classes", "expire_classes", "expire_classes", "census", "census")[int(self.rng.integers(19))]
                 elif self.ext and self.mark is not None and self.rng.random() < 0.3:
-                    # the report on the scratch a sweep has just used: right behind the sweep
-                    op = "top"
+                    # the report on the scratch a sweep has just used, right behind the sweep; a class sweep right behind the
+                    # report, and right behind another class sweep (the copies of the per-class counts it was to leave zero);
+                    # a sweep or a census right behind a setter, while the column is not all one class
+                    op = {"expire listed": "top", "class sweep listed": ("top", "expire_classes")[int(self.rng.integers(2))],
+                          "class sweep": "expire_classes", "top": "expire_classes", "fold": "census",
+                          "classes": ("expire_classes", "census")[int(self.rng.integers(2))]}[self.mark]
                 self.after, self.mark = self.mark, None
                 if self.ext and self.n == 0 and op in self.NEED_ROWS:
                     self.log.append("skipped: " + op)
@@ -1420,12 +1884,13 @@ class Scenario:
                 if self.ext:
                     # (a sweep that listed nothing is treated as a refused remap is: it wrote nothing and drops nothing)
                     did = ((op != "mixed" or self.mixed_wrote) and (op != "remap" or not self.remap_refused) and
-                           (op != "expire" or self.expire_listed) and (op != "fold" or not self.fold_refused))
-                    if op in self.WRITERS and (op not in ("remap", "expire") or did):
+                           (op != "expire" or self.expire_listed) and (op != "fold" or not self.fold_refused) and
+                           (op != "expire_classes" or self.expc_listed))
+                    if op in self.WRITERS and (op not in ("remap", "expire", "expire_classes") or did):
                         self.page_writer = True
                     if op in self.DROPS_SOLVE and did:
                         self.pending = None
-                        if had_solve and op not in ("rebalance", "remap", "expire", "fold"):    # (those four have asked already)
+                        if had_solve and op not in ("rebalance", "remap", "expire", "fold", "expire_classes"):    # (those have asked already)
                             self._dropped(op)
                     elif op in ("mixed", "lookup"):
                         self._read_only(op)
@@ -1433,12 +1898,14 @@ class Scenario:
             if self.ext:
                 self.finish_feed()
                 self.check_table("the end")
-                if (self.remapped or self.seen_used or self.hits_used) and self.n < self.nmax:
-                    # the rows still hidden come back as the removals left them, with the stamps, hits and loads they had
+                if (self.remapped or self.seen_used or self.hits_used or self.cls_used) and self.n < self.nmax:
+                    # the rows still hidden come back as the removals left them, with the stamps, hits, loads and classes they had
                     self._set_n(self.nmax)
                     self.check_table("the end, every row back (num_objects)")
                 if self.hits_used:
                     self._hits_check((self.seed, "the end", "hits and loads over every row", self.log[-6:]), loads=True)
+                if self.cls_used:
+                    self._cls_check((self.seed, "the end", "classes over every row", self.log[-6:]))
             self.chained = self.g.chained_scans() if self.lab else 0
         finally:
             self.g.close()
@@ -1457,7 +1924,7 @@ def test_random_operation_sequences(gp, oracle, seed):
     Scenario(gp, oracle, seed).run()
 
 
-EXT_SEEDS = int(os.environ.get("RIO_FUZZ_EXT_SEEDS", "96"))
+EXT_SEEDS = int(os.environ.get("RIO_FUZZ_EXT_SEEDS", "112"))
 
 
 @pytest.mark.parametrize("seed", range(EXT_SEEDS))
@@ -1511,6 +1978,19 @@ def _sharded_scenario(gp, oracle, seed):
                     alive[int(rng.integers(m))] ^= 1
                 for e in engines:
                     e.g.set_alive_all(alive)
+            if step == 1:
+                # once per scenario, between two ticks: a handle of the row-sharded solve (one that has exported its exchange
+                # window) refuses the class calls before any launch, and the ticks after it are what they are without them
+                import ctypes
+                g = engines[int(rng.integers(G))].g
+                L, h64 = sharded._lib(), (ctypes.c_char * 64)()
+                assert L.rio_gp_shard_p2p_export(g.handle, 1, h64) == gp.OK, (seed, "classes on a shard handle: export")
+                try:
+                    rc = (g.set_classes_raw(0, np.ones(1, np.uint8)) if rng.random() < 0.5 else g.set_class_batch_raw([0], [1]),
+                          g.expire_classes_raw(1, [0xFFFFFFFF])[0], g.census_raw(int(rng.integers(1, 257)), bool(rng.integers(2)))[0])
+                finally:
+                    assert L.rio_gp_shard_p2p_close(g.handle) == gp.OK, (seed, "classes on a shard handle: close")
+                assert rc == (gp.EINVAL,) * 3, (seed, "classes on a shard handle", rc)
             st = sol.tick()
             ref, used, ost = oracle.tick(ref, load, aff, cap, alive, rounds)
             got = np.concatenate([e.g.get_assign() if e.g.num_objects else np.zeros(0, np.uint32) for e in engines])
