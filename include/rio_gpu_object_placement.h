@@ -226,7 +226,10 @@ int rio_op_expire(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64
  * distinct one is class 0, the next class 1, ... up to 254; every further type shares class RIO_OP_CLASS_OTHER.  Names are bytes
  * with a length (a NUL is legal).  The table of types never shrinks.  A key's type is the struct_name it was FIRST interned
  * with (the one rio_op_snapshot reports: ("a.b", "c") and ("a", "b.c") are one key); a row the table hands to a new key takes
- * that key's class.  The device learns the classes lazily: each of the two calls below uploads what changed since the last
+ * that key's class.  A type gets its class when the first key of it gets its row (or by rio_op_set_type_idle_limit_n): a call
+ * that is refused after it interned keys (RIO_GP_EINVAL: the table or the node table ran full further down its batch) keeps
+ * those keys and the classes of their types; a call that creates no key (a lookup, a remove, an update without an address of a
+ * key never seen) numbers no type.  The device learns the classes lazily: each of the two calls below uploads what changed since the last
  * upload (a range for new rows, a scatter for rows that changed hands), under the locks rio_op_expire takes.
  *   - rio_op_set_type_idle_limit_n: keys of this type are idle after max_idle epochs without a stamp; RIO_OP_IDLE_NEVER: never.
  *     A type never seen before gets its class by this call.  A type that lands in RIO_OP_CLASS_OTHER: RIO_GP_ERANGE, nothing

@@ -2488,9 +2488,11 @@ __global__ __launch_bounds__(kBlock) void k_fill(const FillArgs a) {
         }
         uint4 ov = nv;  // the lane's four decisions leave as ONE 16-byte store (rows that stay pending keep their mark)
         uint4 wv = make_uint4(kKeepVal, kKeepVal, kKeepVal, kKeepVal);  // what goes into the real assignment column
-        if (hi_run == lo_run && run_end <= C[lo_run + 1]) {
+        if (hi_run == lo_run && run_end <= C[lo_run + 1] && run_end < F) {
             // The whole tile lies inside ONE node's interval (a node's free capacity is thousands of rows wide: nearly every
-            // tile): every marked row fits entirely, no per-row search, one atomic for the tile's admitted load.
+            // tile): every marked row fits entirely, no per-row search, one atomic for the tile's admitted load.  Not a tile
+            // that ends exactly at F (only the last interval can end at run_end: an inner C[k] <= run_end moves hi_run): its
+            // zero-load rows behind the exact fill have Q == F and stay unplaced, which the per-row rule below decides.
             const u32 nd0 = (u32)ord[lo_run];
             ov.x = mk0 ? nd0 : ov.x; ov.y = mk1 ? nd0 : ov.y; ov.z = mk2 ? nd0 : ov.z; ov.w = mk3 ? nd0 : ov.w;
             pl_sum += lsum;

@@ -10,7 +10,9 @@ It offers the surface the driver's adapter offers (op_layer_driver.RealProvider)
 import numpy as np
 
 import fake_rio_gp
-from fake_rio_gp import AFF_INACTIVE, CAP_INF, EAGAIN, EINVAL, ERANGE, NONE, OK
+from fake_rio_gp import AFF_INACTIVE, CAP_INF, EAGAIN, EINVAL, ERANGE, NONE, OK, TOP_MAX
+
+U32 = 0xFFFFFFFF
 
 CFG_LIVE_FIRST_TOUCH, CFG_NO_HOST_SHADOW = 4, 8
 FLAG_REPLACED = 0x10
@@ -33,6 +35,33 @@ FAULTS = (
     "expire_cutoff_inclusive",     # a key stamped exactly at the cutoff is idle
     "expire_listing_not_in_row_order",   # the listing comes out in reverse
     "stamps_not_uploaded_on_count_only",  # a count-only sweep does not hand the stamps to the dense layer
+    # measured load
+    "reclaim_keeps_counter",       # a reclaimed row keeps the requests counted for its previous key
+    "shadow_hit_not_counted",      # a lookup or request the shadow answers counts no request
+    "remove_counts_request",       # a remove counts a request
+    "tracking_per_clone",          # set_load_tracking through one clone does not reach the calls made through the other
+    "fold_leaves_free_rows",       # a fold leaves the rows on the free list at the folded value
+    "rows_changed_counts_free_rows",   # rows_changed counts rows that belong to no key
+    "refused_fold_drops_counters",  # a refused fold forgets the requests counted so far
+    "hits_folded_after_clamp",     # hits_folded is worked out from the clamped loads
+    "get_object_load_stamps",      # get_object_load stamps and counts like a lookup
+    # hot objects
+    "hottest_ties_by_key",         # keys of equal load come in key order, not row order
+    "hottest_ignores_min_load_per_server",   # min_load is ignored when an address is given
+    "hottest_lists_unplaced",      # keys that are not placed are listed
+    # the by-load cut
+    "by_load_runs_row_order",      # RIO_GP_REBALANCE_BY_LOAD is silently run as row order
+    "invalid_order_runs_row_order",  # an invalid order is not refused
+    # classes
+    "reclaimed_row_keeps_class",   # a row handed to a key of another type keeps its old key's class
+    "class_range_starts_late",     # the upload of the new rows' classes starts one row late
+    "class_from_current_spelling",  # a key's class follows the struct_name of the call, not the one it was first interned with
+    "type_256_gets_a_limit",       # a type in the shared class is given a limit of its own (it becomes the shared class's)
+    "type_cutoff_wraps",           # now - L wraps around where now < L
+    "idle_never_is_zero",          # RIO_OP_IDLE_NEVER is taken as a limit of 0
+    "census_lists_empty_cells",    # census by server lists the empty cells of the types a server does not hold
+    "census_names_shared_class",   # the shared class comes with a name
+    "expire_by_type_keeps_shadow_entry",   # a per-type sweep leaves the shadow's answer for the keys it listed
 )
 
 
@@ -108,6 +137,11 @@ class LifeDense(fake_rio_gp.GpuPlacement):
         self._aff[out[0]] = AFF_INACTIVE      # an expired row is no longer an object
         return out
 
+    def _expire_classes(self, cutoffs, cap):
+        out = super()._expire_classes(cutoffs, cap)
+        self._aff[out[0]] = AFF_INACTIVE
+        return out
+
     def count_placed(self):
         return int((self._col[:self._n] != NONE).sum())
 
@@ -120,7 +154,7 @@ class FakeObjectPlacement:
     def __init__(self, max_objects, max_nodes=32, spill_rounds=2, flags=0, fault=None, _s=None):
         if _s is not None:
             self.s = _s
-            self.own_now = 0
+            self.own_now, self.own_track = 0, False
             return
         assert fault is None or fault in FAULTS, fault
         s = self.s = _State()
@@ -139,7 +173,10 @@ class FakeObjectPlacement:
         s.trips = [0, 0]
         s.last_len = 0
         s.now, s.stamps = 0, np.zeros(s.max_objects, np.uint32)     # the clock every clone stamps with; one stamp per row
-        self.own_now = 0
+        s.track, s.hits = False, np.zeros(s.max_objects, np.uint64)  # the tracking switch the clones share; one counter per row
+        # struct_name -> class in the order of interning, limit by class, the class of every row, and what the device holds of it
+        s.types, s.type_names, s.type_limit, s.row_class, s.cls_uploaded, s.cls_dirty = {}, [], {}, [], 0, []
+        self.own_now, self.own_track = 0, False
 
     def clone(self):
         return FakeObjectPlacement(0, _s=self.s)
@@ -187,6 +224,8 @@ class FakeObjectPlacement:
             r = s.rows[k]
             if use:
                 s.row_keep[r] = 0
+            if s.fault == "class_from_current_spelling" and create:
+                self._set_class(r, self._type(ty))
             return r
         if not create:
             return NONE
@@ -197,14 +236,87 @@ class FakeObjectPlacement:
             s.row_key.append(None)
             s.row_live.append(0)
             s.row_keep.append(0)
+            s.row_class.append(0)
             s.stale_key.append((ty, oid))
         else:
             return "full"
+        c = self._type(ty)
+        if not (s.fault == "reclaimed_row_keeps_class" and r < s.cls_uploaded):
+            self._set_class(r, c)
         s.rows[k] = r
         s.row_key[r] = (ty, oid)
         s.row_live[r] = 1
         s.row_keep[r] = 0 if use else 1
         return r
+
+    # ---- classes
+    def _type(self, ty):
+        """The class of a struct_name: the next number when it is new and one is left, else the shared class."""
+        s = self.s
+        if ty not in s.types:
+            if len(s.type_names) >= 255:
+                return 255
+            s.types[ty] = len(s.type_names)
+            s.type_names.append(ty)
+        return s.types[ty]
+
+    def _set_class(self, r, c):
+        s = self.s
+        if s.row_class[r] != c:
+            s.row_class[r] = c
+            if r < s.cls_uploaded:
+                s.cls_dirty.append(r)
+
+    def _sync_classes(self):
+        """A range for the rows handed out since the last upload, a scatter for the rows that changed hands."""
+        s = self.s
+        n = len(s.row_key)
+        if n > s.cls_uploaded:
+            first = s.cls_uploaded + (1 if s.fault == "class_range_starts_late" else 0)
+            if n > first:
+                s.g.set_classes(first, np.array(s.row_class[first:n], np.uint8))
+            s.cls_uploaded = n
+        if s.cls_dirty:
+            s.g.set_class_batch(s.cls_dirty, [s.row_class[r] for r in s.cls_dirty])
+            s.cls_dirty = []
+
+    def set_type_idle_limit(self, ty, max_idle):
+        s = self.s
+        c = self._type(ty)
+        if c == 255 and s.fault != "type_256_gets_a_limit":
+            return ERANGE
+        s.type_limit[c] = int(max_idle)
+        return OK
+
+    def expire_by_type(self, now, default_max_idle, max_objects=None, mid=None):
+        """-> (rc, [(struct_name, object_id, address or None)], n_idle)"""
+        s = self.s
+        cut = []
+        for c in range(256):
+            L = s.type_limit.get(c, int(default_max_idle))
+            if L == U32 and s.fault == "idle_never_is_zero":
+                L = 0
+            cut.append((now - L) & U32 if s.fault == "type_cutoff_wraps" else now - L if now > L else 0)
+        return self._sweep(lambda cap: s.g.expire_classes(cut, cap, count_only=cap == 0)[:3], max_objects, mid, True)
+
+    def census(self, by_server=False, mid=None):
+        """-> (rc, [(struct_name or None, address or None, rows, load)])"""
+        s = self.s
+        self._sync()
+        self._sync_classes()
+        rows, load, _ = s.g.census(256, by_node=bool(by_server))
+        rows, load = rows.reshape(-1, 256), load.reshape(-1, 256)
+        out = []
+        for j in range(min(len(s.addr), len(rows)) if by_server else 1):
+            held = rows[j].any()
+            for c in range(256):
+                empty = s.fault == "census_lists_empty_cells" and by_server and held and c < len(s.type_names)
+                if rows[j][c] or empty:
+                    name = s.type_names[c] if c < len(s.type_names) else "other" if s.fault == "census_names_shared_class" else None
+                    out.append((name, s.addr[j] if by_server else None, int(rows[j][c]), int(load[j][c])))
+        if mid:
+            mid()
+        return OK, out
 
     def _reclaim(self):
         s = self.s
@@ -221,6 +333,8 @@ class FakeObjectPlacement:
                 s.shadow.pop(r, None)
                 if s.fault == "reclaim_resets_stamp":
                     s.stamps[r] = 0
+                if s.fault != "reclaim_keeps_counter":
+                    s.hits[r] = 0
                 s.free.append(r)
                 gone.append(r)
         if gone:
@@ -244,27 +358,109 @@ class FakeObjectPlacement:
 
     def _stamp(self, row, by_shadow=False):
         s = self.s
+        self._count(row, by_shadow)
         t = self.own_now if s.fault == "clone_has_its_own_clock" else s.now
         if t and not (by_shadow and s.fault == "shadow_hit_does_not_stamp"):
             s.stamps[row] = max(int(s.stamps[row]), t)
 
+    # ---- request counters (measured load)
+    def _count(self, row, by_shadow=False):
+        """One request for the row's key, at every site that stamps: whether or not the clock is set."""
+        s = self.s
+        on = self.own_track if s.fault == "tracking_per_clone" else s.track
+        if on and not (by_shadow and s.fault == "shadow_hit_not_counted"):
+            s.hits[row] = min(int(s.hits[row]) + 1, U32)
+
+    def set_load_tracking(self, on):
+        self.own_track = bool(on)
+        if self.s.fault != "tracking_per_clone":
+            self.s.track = bool(on)
+        return OK
+
+    def fold_loads(self, keep, gain, min_load=0, max_load=U32):
+        """-> (rc, rows_changed, hits_folded)"""
+        s = self.s
+        if keep > 65536 or min_load > max_load:
+            if s.fault == "refused_fold_drops_counters":
+                s.hits[:] = 0
+            return EINVAL, 0, 0
+        self._sync()
+        n = len(s.row_key)
+        if s.hits[:n].any():
+            s.g.hits_merge(s.hits[:n].astype(np.uint32))
+        s.hits[:] = 0
+        before, hits = s.g.get_objects()[0], s.g.get_hits()
+        st = s.g.load_fold(keep, gain, min_load, max_load)
+        changed, folded = st["rows_changed"], st["hits_folded"]
+        if s.fault == "hits_folded_after_clamp":
+            after = s.g.get_objects()[0]
+            folded = sum((int(a) - (int(b) * keep >> 16)) // gain for a, b, h in zip(after, before, hits)
+                         if h and gain and int(a) >= int(b) * keep >> 16)
+        # rows on the free list belong to no key: they leave the count and go back to load 1
+        free_load = max(min_load, min(max_load, 1 if keep == 65536 else 0))
+        if s.free and free_load != 1:
+            if s.fault != "rows_changed_counts_free_rows":
+                changed -= len(s.free)
+            if s.fault != "fold_leaves_free_rows":
+                s.g.set_object_attrs(s.free, load=np.ones(len(s.free), np.uint32))
+        return OK, changed, folded
+
+    def get_object_load(self, ty, oid):
+        """-> (rc, load or None)"""
+        s = self.s
+        r = s.rows.get(self._key(ty, oid))
+        if r is None:
+            return OK, None
+        self._sync()
+        if s.fault == "get_object_load_stamps":
+            self._stamp(r)
+        return OK, int(s.g.get_objects()[0][r])
+
+    def hottest_objects(self, address=None, min_load=0, max_objects=TOP_MAX, mid=None):
+        """-> (rc, [(struct_name, object_id, address or None, load)], n_candidates)"""
+        s = self.s
+        cap = int(max_objects)
+        if cap > TOP_MAX:
+            return EINVAL, [], 0
+        self._sync()
+        node = None
+        if address is not None:
+            if address not in s.nodes:
+                return OK, [], 0
+            node = s.nodes[address]
+        mk = 0 if s.fault == "hottest_ignores_min_load_per_server" and node is not None else int(min_load)
+        placed = s.fault != "hottest_lists_unplaced"
+        rows, keys, nodes, nc, _ = s.g.top_rows(cap, placed=placed, node=node, min_key=mk)
+        if s.fault == "hottest_ties_by_key":
+            rows, keys, nodes, _, _ = s.g.top_rows(TOP_MAX, placed=placed, node=node, min_key=mk)
+            order = sorted(range(len(rows)), key=lambda i: (-int(keys[i]), s.row_key[rows[i]] or ("", "")))[:cap]
+            rows, keys, nodes = rows[order], keys[order], nodes[order]
+        out = [s.row_key[r] + (s.addr[nd] if nd < len(s.addr) else None, int(k)) for r, k, nd in zip(rows, keys, nodes) if s.row_live[r]]
+        if mid:
+            mid()
+        return OK, out, nc
+
     def expire(self, cutoff, max_objects=None, mid=None):
         """-> (rc, [(struct_name, object_id, address or None)], n_idle)"""
         s = self.s
+        if s.fault == "expire_cutoff_inclusive":
+            cutoff = min(int(cutoff) + 1, 0xFFFFFFFF)
+        return self._sweep(lambda cap: s.g.expire(cutoff, cap, count_only=cap == 0)[:3], max_objects, mid, False)
+
+    def _sweep(self, dense, max_objects, mid, by_type):
+        """rio_op_expire and rio_op_expire_by_type: dense(cap) -> (rows, nodes, n_idle) is the dense call."""
+        s = self.s
         self._sync()
+        if by_type:
+            self._sync_classes()
         n = len(s.row_key)
         cap = n if max_objects is None else min(int(max_objects), n)
         if s.stamps.any() and not (cap == 0 and s.fault == "stamps_not_uploaded_on_count_only"):
             s.g.touch_merge(s.stamps[:n])
-        if s.fault == "expire_cutoff_inclusive":
-            cutoff = min(int(cutoff) + 1, 0xFFFFFFFF)
-        if cap == 0:
-            rows, nodes, n_idle, _ = s.g.expire(cutoff, count_only=True)
-        else:
-            rows, nodes, n_idle, _ = s.g.expire(cutoff, cap)
+        rows, nodes, n_idle = dense(cap)
         out = []
         for r, nd in zip(rows, nodes):
-            if s.fault != "expire_keeps_shadow_entry":
+            if s.fault != ("expire_by_type_keeps_shadow_entry" if by_type else "expire_keeps_shadow_entry"):
                 self._put(r, NONE)
             if s.row_live[r]:
                 out.append(s.row_key[r] + (s.addr[nd] if nd < len(s.addr) else None,))
@@ -388,6 +584,8 @@ class FakeObjectPlacement:
         self._put(r, NONE)
         if self.s.fault == "remove_stamps":
             self._stamp(r)
+        if self.s.fault == "remove_counts_request":
+            self._count(r)
         return OK
 
     def clean_server(self, addr):
@@ -618,11 +816,19 @@ class FakeObjectPlacement:
             mid()
         return OK, out
 
-    def rebalance(self, max_moves=None, mid=None):
+    def rebalance(self, max_moves=None, mid=None, order=None):
+        """order None: rio_op_rebalance; else rio_op_rebalance_ordered with that order."""
         s = self.s
+        order = 0 if order is None else int(order)
+        if order not in (0, 1):
+            if s.fault != "invalid_order_runs_row_order":
+                return EINVAL, []
+            order = 0
+        if s.fault == "by_load_runs_row_order":
+            order = 0
         self._sync()
         cap = min(CAP_INF if max_moves is None else int(max_moves), len(s.row_key))
-        _, rows, frm, to = s.g.rebalance(None, cap, 0, moves_cap=cap)
+        _, rows, frm, to = s.g.rebalance(None, cap, 0, moves_cap=cap, order=order)
         if s.fault != "rebalance_keeps_shadow":
             self._invalidate()
         out = [(s.row_key[r][0], s.row_key[r][1], s.addr[f], s.addr[t]) for r, f, t in zip(rows, frm, to) if s.row_live[r]]

@@ -24,6 +24,18 @@ column, `used` and the affinity are those of rio_gp_remove_batch of the listed r
 rio_op_dense handle equals the model's stamps (every sweep uploads them, a count-only one too), a listed key is gone through both
 clones and a key that was not listed is still answered from the shadow.
 
+Measured load, the hot-object report, the by-load cut and the classes are part of the sequence too.  The model keeps one request
+counter per ROW next to the stamp: it rises at the very sites that stamp, while tracking is on and whether or not the clock is
+set, and — unlike the stamp — goes back to 0 when the row is handed to a new key.  rio_op_fold_loads is compared with
+tests/spec_loads.py over the load column read before the call and those counters, row for row; before a fold the rows of the
+keys no listing has shown are learnt (the one row whose load changes under rio_op_set_object_load, put back at once), so every
+row without a key is a free row and must hold load 1 before and after.  rio_op_hottest_objects is tests/spec_top.py over the
+placed keys in row order, rio_op_rebalance_ordered by load tests/spec_rebalance_order.py (held to tests/rebalance_order_ref.py up
+to 4 096 rows).  Types are numbered in the order the header gives (a type gets its class when its first key gets its row,
+whatever becomes of the call); rio_op_expire_by_type is tests/spec_classes.py under cutoffs built per class, rio_op_census its
+census with 256 classes, and after each of the two rio_gp_get_classes on the dense handle equals the model's class column on
+every row whose key the model knows.
+
 The provider under test is given as make(max_objects, max_nodes, spill_rounds, flags): RealProvider.make over rio_gp (the GPU
 test, tests/test_gpu_op_layer_fuzz.py) or tests/fake_rio_op.py (the driver's own test, tests/test_op_layer_driver.py).
 """
@@ -32,9 +44,17 @@ import ctypes as C
 import numpy as np
 
 import spec_changes
+import spec_classes
 import spec_expire
+import spec_loads
+import spec_top
 
 NONE = 0xFFFFFFFF
+U32 = 0xFFFFFFFF
+KEEP_ONE = 65536
+TOP_MAX = 4096
+CLASS_OTHER = 255
+ROW_ORDER, BY_LOAD = 0, 1
 INF = 0xFFFFFFFFFFFFFFFF
 AFF_INACTIVE = 0xFFFFFFFE
 OK, EINVAL, EUPSTREAM, ENODEV, ENOMEM, ERANGE, EAGAIN = range(7)
@@ -61,6 +81,33 @@ FLOOR = (
     "an expired key's row was handed to a new key before the next feed read",
     "a sweep judged a key by a stamp its row's previous key left",
     "expire listed a key set aside by set_object_load",
+    # measured load
+    "a fold saw a row that had changed hands since the last fold, with requests counted for its previous key",
+    "a fold with a non-empty free list and a free-row result other than 1",
+    "a fold counted requests of shadow hits",
+    "a fold with the clock never set",
+    "a refused fold kept its counters for the next one",
+    "a fold changed no load",
+    "tracking switched off between two folds",
+    "get_object_load of a key never seen",
+    # hot objects
+    "hottest cut inside a tie group",
+    "hottest on an address never seen",
+    # the by-load cut
+    "a by-load rebalance moved keys",
+    "a by-load rebalance right after a fold",
+    "an invalid order was refused",
+    # classes
+    "a class upload held a range and a scatter in one call",
+    "a row changed hands twice between two class uploads",
+    "a row changed hands before its first class upload",
+    "a key of a type past 255 was swept by the default limit",
+    "a type limit refused with ERANGE",
+    "a per-type sweep listed keys of one type and spared older keys of another",
+    "IDLE_NEVER spared an idle key",
+    "a per-type sweep between two feed reads",
+    "census by server with a server seen only through update",
+    "census listed the shared class",
 )
 
 SIZES = ("tiny", "tiny", "edge", "tiny", "4096", "bulk")      # by seed % 6
@@ -210,12 +257,14 @@ class RealProvider:
         k = int(n.value)
         return OK, list(zip(self._strs(ty, tl, k), self._strs(oid, il, k)))
 
-    def rebalance(self, max_moves=None, mid=None):
+    def rebalance(self, max_moves=None, mid=None, order=None):
+        """order None: rio_op_rebalance; else rio_op_rebalance_ordered with that order (the two share the thread's arrays)."""
         n = C.c_uint64(0)
         ty, oid, fa, ta = (C.POINTER(C.c_char_p)() for _ in range(4))
         tl, il = C.POINTER(C.c_size_t)(), C.POINTER(C.c_size_t)()
-        rc = self.L.rio_op_rebalance(self.p._h, INF if max_moves is None else int(max_moves), C.byref(n), C.byref(ty), C.byref(tl),
-                                     C.byref(oid), C.byref(il), C.byref(fa), C.byref(ta))
+        out = (C.byref(n), C.byref(ty), C.byref(tl), C.byref(oid), C.byref(il), C.byref(fa), C.byref(ta))
+        B = INF if max_moves is None else int(max_moves)
+        rc = self.L.rio_op_rebalance(self.p._h, B, *out) if order is None else self.L.rio_op_rebalance_ordered(self.p._h, int(order), B, *out)
         if rc:
             return rc, []
         if mid:
@@ -257,6 +306,61 @@ class RealProvider:
         return OK, list(zip(self._strs(ty, tl, k), self._strs(oid, il, k),
                             [None if ad[q] is None else ad[q].decode() for q in range(k)])), int(idle.value)
 
+    def set_load_tracking(self, on):
+        return int(self.L.rio_op_set_load_tracking(self.p._h, 1 if on else 0))
+
+    def fold_loads(self, keep, gain, min_load=0, max_load=U32):
+        """-> (rc, rows_changed, hits_folded)"""
+        return self.gp.op_fold_loads(self.L, self.p._h, keep, gain, min_load, max_load)
+
+    def get_object_load(self, ty, oid):
+        """-> (rc, load or None for a key never seen)"""
+        return self.gp.op_get_object_load(self.L, self.p._h, ty, oid)
+
+    def hottest_objects(self, address=None, min_load=0, max_objects=4096, mid=None):
+        """-> (rc, [(struct_name, object_id, address or None, load)], n_candidates)"""
+        gp = self.gp
+        o, cand = gp._listing_out(1), C.c_uint64(0)
+        cap = int(max_objects)
+        loads = (C.c_uint32 * max(min(cap, 4096), 1))()
+        rc = self.L.rio_op_hottest_objects(self.p._h, None if address is None else address.encode(), int(min_load), cap, C.byref(o[0]),
+                                           C.byref(cand), *map(C.byref, o[1:]), loads)
+        if rc:
+            return rc, [], 0
+        if mid:
+            mid()
+        return OK, [e + (int(loads[k]),) for k, e in enumerate(gp._listing(o))], int(cand.value)
+
+    def set_type_idle_limit(self, ty, max_idle):
+        return int(self.gp.op_set_type_idle_limit(self.L, self.p._h, ty, max_idle))
+
+    def expire_by_type(self, now, default_max_idle, max_objects=None, mid=None):
+        """-> (rc, [(struct_name, object_id, address or None)], n_idle)"""
+        gp = self.gp
+        o, idle = gp._listing_out(1), C.c_uint64(0)
+        rc = self.L.rio_op_expire_by_type(self.p._h, int(now), int(default_max_idle), INF if max_objects is None else int(max_objects),
+                                          C.byref(o[0]), C.byref(idle), *map(C.byref, o[1:]))
+        if rc:
+            return rc, [], 0
+        if mid:
+            mid()
+        return OK, gp._listing(o), int(idle.value)
+
+    def census(self, by_server=False, mid=None):
+        """-> (rc, [(struct_name as str or None for the shared class, address or None, rows, load)])"""
+        n = C.c_uint64(0)
+        names, addrs, lens = C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)(), C.POINTER(C.c_size_t)()
+        rows, loads = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        rc = self.L.rio_op_census(self.p._h, 1 if by_server else 0, C.byref(n), C.byref(names), C.byref(lens), C.byref(addrs),
+                                  C.byref(rows), C.byref(loads))
+        if rc:
+            return rc, []
+        if mid:
+            mid()
+        nv = C.cast(names, C.POINTER(C.c_void_p))
+        return OK, [(C.string_at(nv[k], lens[k]).decode() if nv[k] else None, addrs[k].decode() if addrs[k] else None, int(rows[k]),
+                     int(loads[k])) for k in range(n.value)]
+
 
 class Key:
     """One interned key as the documentation describes its life: (ty, oid) as first handed over, its row once a listing showed
@@ -271,7 +375,9 @@ class Scenario:
     OPS = (("update", 8), ("update_none", 2), ("update_batch", 3), ("remove", 5), ("clean_server", 2), ("lookup", 6),
            ("lookup_batch", 2), ("request", 10), ("request_batch", 4), ("try_lookup", 4), ("try_request", 4), ("set_member", 5),
            ("set_object_load", 3), ("tick", 3), ("rebalance", 4), ("changes", 5), ("changes_reset", 1), ("invalidate_cache", 1),
-           ("objects_on_server", 2), ("snapshot", 2), ("len", 1), ("set_clock", 4), ("expire", 4))
+           ("objects_on_server", 2), ("snapshot", 2), ("len", 1), ("set_clock", 4), ("expire", 4),
+           ("set_load_tracking", 2), ("fold_loads", 4), ("get_object_load", 2), ("hottest_objects", 3),
+           ("set_type_idle_limit", 2), ("expire_by_type", 3), ("census", 2))
 
     def __init__(self, make, oracle, seed, steps=None):
         self.oracle, self.seed = oracle, seed
@@ -292,9 +398,14 @@ class Scenario:
         self.members = ["10.0.%d.%d:%d" % (seed % 200, k, 5000 + k) for k in range(nm)]
         self.odd = ["nocolon", "a-host-name-that-is-much-longer-than-thirty-two-bytes.example.org:65535"]
         self.crowd = ["10.9.0.%d:1" % k for k in range(40)] if seed % 5 == 3 else []     # more addresses than max_nodes holds
+        self.upd_only = ["10.8.%d.%d:9" % (seed % 200, k) for k in range(2)]             # addresses only rio_op_update carries
         nk = {"tiny": 3 * self.rows_max, "edge": 400, "4096": 1500, "bulk": 3000}[kind]
-        self.pool = [("T%d" % (k % 3), str(k)) for k in range(nk)] + [("a.b", "c"), ("a", "b.c"), ("T0", ""), ("nul\0ty", "x"),
-                                                                     ("T1", "i\0d"), ("T1", "i")]
+        self.many_types = seed % 6 == 4       # one seed in six: more types than there are classes (RIO_OP_CLASS_OTHER is reached)
+        tyname = (lambda k: "Y%d" % (k % 320)) if self.many_types else (lambda k: "T%d" % (k % 3))
+        self.pool = [(tyname(k), str(k)) for k in range(nk)] + [("a.b", "c"), ("a", "b.c"), ("T0", ""), ("nul\0ty", "x"),
+                                                               ("T1", "i\0d"), ("T1", "i")]
+        if self.many_types:
+            self.pool += [("", "e%d" % k) for k in range(3)] + [("Y\0%d" % k, "n") for k in range(4)]
         self.addr, self.aid, self.alive, self.cap = [], {}, [], []        # node table as documented: by id
         self.keys, self.row2key = {}, {}                                  # "ty.oid" -> Key ; row -> "ty.oid"
         self.handed = set()                                               # rows that have had more than one key
@@ -315,6 +426,22 @@ class Scenario:
         self.unknown_stamped = set()
         self.expired_since_feed = set()
         self.set_aside = set()
+        # measured load: the switch the clones share; one request counter per ROW next to S (Hs: the part shadow hits counted);
+        # keys counted while their row was unknown; rows whose counter a reclaim dropped since the last fold
+        self.tracking, self.track_off = False, False
+        self.Hc = np.zeros(self.rows_max, np.uint64)
+        self.Hs = np.zeros(self.rows_max, np.uint64)
+        self.unknown_hits = {}
+        self.lost_hits = set()
+        self.refused_fold = False
+        self.last_dropped = []
+        self.share = [0, 0]               # non-zero counters at a fold: on rows the model does not know, all of them
+        # classes: struct_name -> class in the order of interning (at most 255 of them), its limit, the class column by row,
+        # and what the next class upload will hold (the rows known to the device's class column end at cls_up)
+        self.types, self.limits, self.limit_clone = {}, {}, None
+        self.K = np.zeros(self.rows_max, np.uint8)
+        self.cls_up, self.cls_scatter, self.cls_handed, self.cls_early = 0, set(), {}, False
+        self.seen_by = {}                 # address -> the kinds of call that carried it
 
     # ---- small helpers ------------------------------------------------------------------------------------------------
     def fail(self, what, *more):
@@ -361,6 +488,12 @@ class Scenario:
         if self.crowd and r < odd + 0.25:
             return self.crowd[int(rng.integers(len(self.crowd)))]
         return self.members[int(rng.integers(len(self.members)))]
+
+    def carry(self, addrs, kind):
+        """The kinds of call that have carried an address (a server may be known through rio_op_update alone)."""
+        for a in addrs:
+            if a is not None:
+                self.seen_by.setdefault(a, set()).add(kind)
 
     def is_bad(self, a):
         c = a.find(":")
@@ -410,6 +543,7 @@ class Scenario:
                         break
                     k = self.keys[ks] = Key(key[0], key[1], not use)
                     self.created.append(ks)
+                    self.sight(key[0])    # (the type gets its class with the key's row, whatever becomes of the call)
                 if k is not None and use:
                     k.keep = False
                 if address is not None and address not in self.aid and address not in self.pending_addr:
@@ -430,6 +564,11 @@ class Scenario:
                     del self.row2key[k.row]
                     self.reset_rows.add(k.row)
                     self.own.discard(k.row)
+                    if self.Hc[k.row]:               # the row changes hands: its counter starts again at 0, the stamp stays
+                        self.lost_hits.add(k.row)
+                    self.Hc[k.row] = self.Hs[k.row] = 0
+                self.unknown_hits.pop(ks, None)
+                self.last_dropped.append((k.ty, k.oid))
                 self.unknown_stamped.discard(ks)     # (its row keeps the stamp: the next sweep's upload is compared as a whole)
                 self.dropped_since_feed.setdefault(ks, k.row)
             if self.feed_state == "open":
@@ -485,24 +624,50 @@ class Scenario:
     def new_row(self, k, ks, r):
         """A listing showed the row of key k.  The row keeps the stamp its previous key left (the header: "a row handed on keeps
         its stamp until its new key's first call")."""
+        c = self.cls_of(k.ty)
         if r in self.ever_rows:
             self.handed.add(r)
             self.own.discard(r)
             self.hit("an expired key's row was handed to a new key before the next feed read", r in self.expired_since_feed)
+            self.cls_handed[r] = self.cls_handed.get(r, 0) + 1
+            if r >= self.cls_up:
+                self.cls_early = True
+            elif c != int(self.K[r]):
+                self.cls_scatter.add(r)
         self.ever_rows.add(r)
         k.row = r
         self.row2key[r] = ks
+        self.K[r] = c
+        h = self.unknown_hits.pop(ks, 0)      # requests counted while the row was unknown
+        self.Hc[r] = min(int(self.Hc[r]) + h, U32)
+
+    def sight(self, ty):
+        """A struct_name is interned: the first distinct one is class 0, the next class 1, ... up to 254."""
+        if ty not in self.types and len(self.types) < CLASS_OTHER:
+            self.types[ty] = len(self.types)
+
+    def cls_of(self, ty):
+        return self.types.get(ty, CLASS_OTHER)
 
     # ---- the stamping rule (include/rio_gpu_object_placement.h, "idle deactivation") ------------------------------------------
     def stamp(self, key, shadow=False):
         """A call has answered or set an address for `key` (it returned RIO_GP_OK — an RIO_GP_ERANGE answer is a call that failed):
         with the clock non-zero the key's row is stamped, a maximum.  Called once the call's rows are learnt."""
-        if not self.clock:
+        if not self.clock and not self.tracking:
             return
         ks = self.kstr(key)
         k = self.keys.get(ks)
         if k is None:
             self.fail("a call answered with an address for a key the model does not hold", key)
+        if self.tracking:        # one request, at the very sites that stamp: whether or not the clock is set
+            if k.row is None:
+                self.unknown_hits[ks] = min(self.unknown_hits.get(ks, 0) + 1, U32)
+            else:
+                self.Hc[k.row] = min(int(self.Hc[k.row]) + 1, U32)
+                if shadow:
+                    self.Hs[k.row] += 1
+        if not self.clock:
+            return
         if k.row is None:        # (a batch that set the key's address and removed it again: see stamps_of_unknown_rows)
             self.unknown_stamped.add(ks)
             return
@@ -542,16 +707,17 @@ class Scenario:
     def virtual(self, st, klist):
         """Row indices for the reference: the known row, or one past the table's end per key whose row is unknown (unplaced,
         load 1).  -> (idx, col, load, extra keys in order)"""
-        extra, idx = [], []
+        extra, at, idx = [], {}, []
         for key in klist:
             k = self.keys.get(self.kstr(key))
             if k is not None and k.row is not None:
                 idx.append(k.row)
             else:
                 ks = self.kstr(key)
-                if ks not in extra:
+                if ks not in at:      # (the key's place in `extra`: a bulk load names 2^14 new keys)
+                    at[ks] = len(extra)
                     extra.append(ks)
-                idx.append(st["n"] + extra.index(ks))
+                idx.append(st["n"] + at[ks])
         col = np.concatenate([st["col"], np.full(len(extra), NONE, np.uint32)])
         load = np.concatenate([st["load"], np.ones(len(extra), np.uint32)])
         return np.array(idx, np.uint32), col, load, extra
@@ -619,6 +785,9 @@ class Scenario:
         p, other = self.h()
         key = self.pick_key(0.4)
         a = None if addr_none else self.pick_addr()
+        if a is not None and self.rng.random() < 0.08:      # a server no member list and no request ever names
+            a = self.upd_only[int(self.rng.integers(2))]
+        self.carry([a], "update")
         st = self.begin()
         ok = self.intern(st, [(key, a is not None, True, a, False)])
         rc = p.update(key[0], key[1], a)
@@ -654,6 +823,7 @@ class Scenario:
             for _ in range(max(1, n // 4)):
                 keys[int(rng.integers(n))] = keys[int(rng.integers(n))]
         addrs = [None if rng.random() < 0.1 else self.pick_addr(0.03) for _ in range(n)]
+        self.carry(addrs, "update")
         st = self.begin()
         ok = self.intern(st, [(k, a is not None, True, a, False) for k, a in zip(keys, addrs)])
         rc = p.update_batch(keys, addrs)
@@ -799,6 +969,7 @@ class Scenario:
     def op_request(self):
         p, other = self.h()
         key, me = self.pick_key(0.6), self.pick_addr(0.05)
+        self.carry([me], "request")
         st = self.begin()
         ok = self.intern(st, [(key, True, True, me, True)])
         cap = 512 if self.rng.random() < 0.85 else 8
@@ -847,6 +1018,7 @@ class Scenario:
         for _ in range(n // 5):
             keys[int(rng.integers(n))] = keys[int(rng.integers(n))]
         mes = [self.pick_addr(0.02) for _ in range(n)]
+        self.carry(mes, "request")
         st = self.begin()
         ok = self.intern(st, [(k, True, True, me, True) for k, me in zip(keys, mes)])
         rc, ids, flags = p.get_or_create_placement_batch(keys, mes)
@@ -889,6 +1061,7 @@ class Scenario:
         rng = self.rng
         a = self.pick_addr(0.08)
         active = bool(rng.random() < 0.65)
+        self.carry([a], "member")
         st = self.begin()
         total = int(st["load"][st["col"] != NONE].sum()) if st["n"] else 0
         capv = [INF, INF, max(1, total // max(1, len(self.members))), int(rng.integers(1, 6)), 0][int(rng.integers(5))]
@@ -974,7 +1147,8 @@ class Scenario:
                 self.check_lookup(st, p, self.handles[0], key, p.try_lookup, "try_lookup")
                 self.check_lookup(st, p, self.handles[0], key, p.lookup, "lookup")
 
-    def op_rebalance(self):
+    def op_rebalance(self, order="draw"):
+        """rio_op_rebalance, or rio_op_rebalance_ordered in row order, by load or with an order that does not exist."""
         import rebalance_ref
         p, other = self.h()
         rng = self.rng
@@ -982,12 +1156,39 @@ class Scenario:
         for ks in list(self.keys)[:6]:           # (the shadow holds answers a rebalance must void)
             self.plain_lookup(p, st, (self.keys[ks].ty, self.keys[ks].oid))
         mm = (None, 0, 1, int(rng.integers(2, 6)), int(rng.integers(2, 40)))[int(rng.integers(5))]
-        rc, moves = p.rebalance(mm, mid=lambda: other.len())
+        after_fold = order != "draw"
+        if order == "draw":
+            order = (None, ROW_ORDER, BY_LOAD, BY_LOAD, (2, 7, U32)[int(rng.integers(3))])[int(rng.integers(5))]
+        rc, moves = p.rebalance(mm, mid=lambda: other.len(), order=order)
+        if order not in (None, ROW_ORDER, BY_LOAD):
+            self.want(rc == EINVAL and moves == [], "an order that does not exist was not refused", order, rc, moves[:2])
+            self.hit("an invalid order was refused")
+            t0 = p.device_round_trips()
+            for ks in list(self.keys)[:6]:       # nothing changed: the shadow still holds the answers
+                key = (self.keys[ks].ty, self.keys[ks].oid)
+                self.check_lookup(st, p, other, key, p.lookup, "lookup")
+            self.want(self.flags & CFG_NO_HOST_SHADOW or p.device_round_trips() == t0, "a refused rebalance voided the shadow")
+            return self.unchanged(st, "rebalance with an invalid order")
         self.want(rc == OK, "rebalance failed", rc)
         self.ref_on = False
         cap, alive = self.node_arrays()
         budget = min(INF if mm is None else mm, st["n"])
-        if st["n"] and len(self.addr):
+        if st["n"] and len(self.addr) and order == BY_LOAD:
+            import rebalance_order_ref
+            import spec_rebalance_order
+            L = lambda a: [int(x) for x in a]
+            s_nxt, _, _, s_moves = spec_rebalance_order.rebalance(L(st["col"]), L(st["load"]), L(st["aff"]), L(cap), L(alive), None, budget,
+                                                                  self.rounds, order=BY_LOAD)
+            nxt = np.array(s_nxt, np.uint32)
+            rows, frm, to = ([m[q] for m in s_moves] for q in range(3))
+            if st["n"] <= 4096:
+                r_nxt, _, _, r_rows, r_frm, r_to = rebalance_order_ref.rebalance(st["col"], st["load"], st["aff"], cap, alive, None, budget,
+                                                                                  self.rounds, order=BY_LOAD)
+                self.want(s_nxt == L(r_nxt) and s_moves == [(int(r), int(f), int(t)) for r, f, t in zip(r_rows, r_frm, r_to)],
+                          "the two by-load rebalance references differ")
+            self.hit("a by-load rebalance moved keys", len(rows) > 0)
+            self.hit("a by-load rebalance right after a fold", after_fold)
+        elif st["n"] and len(self.addr):
             nxt, used, wst, rows, frm, to = rebalance_ref.rebalance(st["col"], st["load"], st["aff"], cap, alive, None, budget, self.rounds)
             if st["n"] <= 4096:
                 import spec_rebalance
@@ -1001,7 +1202,10 @@ class Scenario:
             k = self.keys[self.row2key[int(r)]]
             want.append((k.ty, k.oid, self.addr[f], self.addr[t]))
             self.hit("rebalance moved keys of rows that had changed hands", int(r) in self.handed)
-        self.want(moves == want, "rebalance: the moves are not the reference's, key for key in row order", moves[:4], want[:4])
+        self.want(moves == want, "rebalance: the moves are not the reference's, key for key in row order", order, moves[:4], want[:4])
+        if order is not None:      # the two calls share the thread's arrays: the listing above was read before this call, which
+            rc, none = p.rebalance(0)      # hands out an empty one and moves nothing (the column is compared below)
+            self.want(rc == OK and none == [], "rebalance with max_moves 0 after an ordered one", rc, none[:2])
         after = self.settle(st, nxt, [], "rebalance")
         self.probe(after, [self.row2key[int(r)] for r in rows[:4]])
         return after
@@ -1102,8 +1306,11 @@ class Scenario:
         bad = np.flatnonzero(seen != self.S[:len(seen)])
         self.want(bad.size == 0, what + ": the stamps on the device differ from the model's", bad[:8], seen[bad[:8]], self.S[bad[:8]])
 
-    def op_expire(self):
+    def op_expire(self, by_type=False):
+        """rio_op_expire, or (by_type) rio_op_expire_by_type: the same sweep with a cutoff per class."""
         p, other = self.h()
+        if by_type and self.limit_clone is not None:      # a limit set through one clone, the sweep through the other
+            p, other = self.handles[1 - self.limit_clone], self.handles[self.limit_clone]
         rng = self.rng
         st = self.begin()
         n, col = st["n"], st["col"]
@@ -1118,31 +1325,59 @@ class Scenario:
         first = not self.clock_ever and rng.random() < 0.5      # (while the clock has never been set: any cutoff > 0, no limit)
         if first:
             cutoff = (1, 0xFFFFFFFF)[int(rng.integers(2))]
-        _, _, n_idle, _, _ = spec_expire.expire(col, self.S, st["load"], n, cutoff, None)
+        if by_type:
+            # now below, at and above the limits (and 0), a default that matters; the cutoff of a class is now - L where that is
+            # positive, else 0 — L the type's own limit, or the default without one and for the shared class
+            Ls = sorted(set(self.limits.values()) - {U32})
+            L0 = Ls[int(rng.integers(len(Ls)))] if Ls else 0
+            dflt = (0, 1, int(rng.integers(0, self.clock_top + 2)), U32, L0)[int(rng.integers(5))]
+            c = self.clock
+            d0 = dflt if dflt != U32 else 0
+            now = (0, c, c + L0, c + L0 + 1, c + L0 + 1, max(c + L0 - 1, 0), c + d0 + 1, c + d0 + 1, int(rng.integers(0, self.clock_top + 12)),
+                   U32)[int(rng.integers(10))]
+            if self.many_types and rng.random() < 0.5:      # most keys are of the shared class: a sweep the default decides
+                dflt = int(rng.integers(2))
+                now = c + dflt + 1
+            now = min(now, U32)
+            cutoffs = [now - dflt if now > dflt else 0] * spec_classes.MAX_CLASSES
+            for ty, cl in self.types.items():
+                if ty in self.limits:
+                    cutoffs[cl] = now - self.limits[ty] if now > self.limits[ty] else 0
+            sweep = lambda cp: spec_classes.expire_classes(col, self.S, self.K, st["load"], n, cutoffs, cp)[:5]
+            cutoff, first = (now, dflt), False
+        else:
+            sweep = lambda cp: spec_expire.expire(col, self.S, st["load"], n, cutoff, cp)
+        idle_rows, _, n_idle, _, _ = sweep(None)
         cap = (None, 0, 1, int(rng.integers(2, 9)), max(n_idle - 1, 0), n_idle, n_idle + 1)[int(rng.integers(7))]
         if first:
             cap = None
-        rows, nodes, w_idle, _, A2 = spec_expire.expire(col, self.S, st["load"], n, cutoff, cap)
+        rows, nodes, w_idle, _, A2 = sweep(cap)
         want = []
         for r, nd in zip(rows, nodes):
             ks = self.row2key.get(int(r))
             if ks is None:
                 self.fail("a placed row has no key in the model", int(r))
             want.append((self.keys[ks].ty, self.keys[ks].oid, self.addr[nd] if nd < len(self.addr) else None))
-        rc, got, got_idle = p.expire(cutoff, cap, mid=lambda: other.len())
+        if by_type:
+            rc, got, got_idle = p.expire_by_type(now, dflt, cap, mid=lambda: other.len())
+        else:
+            rc, got, got_idle = p.expire(cutoff, cap, mid=lambda: other.len())
         self.want(rc == OK, "expire failed", rc)
         self.want(got == want, "expire: the listing is not the reference's, key for key in row order", cutoff, cap, got[:4], want[:4])
         self.want(got_idle == w_idle, "expire: n_idle", got_idle, w_idle)
         L = len(rows)
-        live = [r for r in placed if int(self.S[r]) >= cutoff]
-        self.hit("expire listed keys", L > 0)
-        self.hit("expire count only with idle keys", cap == 0 and n_idle > 0)
-        self.hit("expire capped below n_idle", 0 < L < n_idle)
-        self.hit("sweep with the clock never set listed everything placed", not self.clock_ever and cutoff > 0 and L == len(placed) > 0)
-        self.hit("a key stamped only by a shadow hit survived a sweep", cutoff > 0 and any(int(self.S_dev[r]) < cutoff for r in live))
-        self.hit("a sweep judged a key by a stamp its row's previous key left",
-                 cutoff > 0 and any(r not in self.own and self.S[r] > 0 for r in placed))
-        self.hit("expire listed a key set aside by set_object_load", any(self.row2key[int(r)] in self.set_aside for r in rows))
+        if by_type:
+            self.note_type_sweep(st, placed, set(int(r) for r in idle_rows), rows, cutoffs, now, dflt)
+        else:
+            live = [r for r in placed if int(self.S[r]) >= cutoff]
+            self.hit("expire listed keys", L > 0)
+            self.hit("expire count only with idle keys", cap == 0 and n_idle > 0)
+            self.hit("expire capped below n_idle", 0 < L < n_idle)
+            self.hit("sweep with the clock never set listed everything placed", not self.clock_ever and cutoff > 0 and L == len(placed) > 0)
+            self.hit("a key stamped only by a shadow hit survived a sweep", cutoff > 0 and any(int(self.S_dev[r]) < cutoff for r in live))
+            self.hit("a sweep judged a key by a stamp its row's previous key left",
+                     cutoff > 0 and any(r not in self.own and self.S[r] > 0 for r in placed))
+            self.hit("expire listed a key set aside by set_object_load", any(self.row2key[int(r)] in self.set_aside for r in rows))
         # the table: rio_op_remove of the listed keys, under the row lifecycle
         xcol = col.copy()
         if L:
@@ -1157,9 +1392,11 @@ class Scenario:
         xaff[rows] = AFF_INACTIVE
         self.want(np.array_equal(after["aff"][:n], xaff), "expire: the affinity column", np.flatnonzero(after["aff"][:n] != xaff)[:8])
         self.check_seen("expire")
+        if by_type:
+            self.class_upload("expire_by_type")
         self.expired_since_feed |= set(int(r) for r in rows)
-        if L:
-            self.probe(after, [self.row2key[int(rows[int(rng.integers(L))])]])
+        if L:      # (up to three of the listed keys, drawn with repetition)
+            self.probe(after, list(dict.fromkeys(self.row2key[int(rows[int(rng.integers(L))])] for _ in range(3))))
         if wit is not None and wit not in [(a, b) for a, b, _ in want]:
             # a key that was not listed is answered as before — with the shadow on, without a device round trip
             t0 = p.device_round_trips()
@@ -1167,6 +1404,313 @@ class Scenario:
             self.want(self.flags & CFG_NO_HOST_SHADOW or p.device_round_trips() == t0,
                       "expire: a key that was not listed lost its shadow entry", wit)
         return after
+
+    # ---- classes (include/rio_gpu_object_placement.h, "per-type idle limits and a census by type") ------------------------
+    def op_expire_by_type(self):
+        return self.op_expire(by_type=True)
+
+    def note_type_sweep(self, st, placed, idle, rows, cutoffs, now, dflt):
+        K, S = self.K, self.S
+        self.hit("a key of a type past 255 was swept by the default limit", any(int(K[r]) == CLASS_OTHER for r in rows))
+        self.hit("a per-type sweep between two feed reads", len(rows) > 0 and self.feed_state == "open")
+        young, old = {}, {}      # class -> the youngest stamp listed / the oldest stamp spared (idle rows past the cap are neither)
+        for r in rows:
+            young[int(K[r])] = max(young.get(int(K[r]), 0), int(S[r]))
+        for r in placed:
+            if r not in idle:
+                old[int(K[r])] = min(old.get(int(K[r]), U32), int(S[r]))
+        self.hit("a per-type sweep listed keys of one type and spared older keys of another",
+                 any(a != b and old[b] < young[a] for a in young for b in old))
+        dcut = now - dflt if now > dflt else 0
+        never = set(cl for ty, cl in self.types.items() if self.limits.get(ty) == U32)
+        self.hit("IDLE_NEVER spared an idle key", any(int(K[r]) in never and int(S[r]) < dcut for r in placed))
+        self.hit("a sweep judged a key by a stamp its row's previous key left",
+                 max(cutoffs) > 0 and any(r not in self.own and S[r] > 0 for r in placed))
+
+    def class_upload(self, what):
+        """rio_op_expire_by_type and rio_op_census upload the classes the device does not hold yet: afterwards rio_gp_get_classes
+        on the dense handle is the model's class column — row for row where the model knows the row's key; a row it cannot map
+        (free, or of a key no listing has shown) holds the class of some type."""
+        n = self.g.num_objects
+        self.hit("a class upload held a range and a scatter in one call", n > self.cls_up and bool(self.cls_scatter))
+        self.hit("a row changed hands twice between two class uploads", any(v >= 2 for v in self.cls_handed.values()))
+        self.hit("a row changed hands before its first class upload", self.cls_early)
+        self.cls_up, self.cls_scatter, self.cls_handed, self.cls_early = n, set(), {}, False
+        Kd = self.g.get_classes() if n else np.zeros(0, np.uint8)
+        self.want(len(Kd) == n, what + ": the class column's length", len(Kd), n)
+        rows = np.array(sorted(self.row2key), np.int64)
+        self.want(rows.size == 0 or int(rows[-1]) < n, what + ": the model holds a row past the table's end")
+        bad = rows[Kd[rows] != self.K[rows]]
+        self.want(bad.size == 0, what + ": the device's classes differ from the model's", bad[:8], Kd[bad[:8]], self.K[bad[:8]],
+                  [self.row2key[int(r)] for r in bad[:4]])
+        rest = np.ones(n, bool)
+        rest[rows] = False
+        top = len(self.types)
+        odd = np.flatnonzero(rest & (Kd >= top) & ((Kd != CLASS_OTHER) | (top < CLASS_OTHER)))
+        self.want(odd.size == 0, what + ": a row holds a class no type has", odd[:8], Kd[odd[:8]], top)
+
+    def op_set_type_idle_limit(self):
+        p, other = self.h()
+        rng = self.rng
+        kind = 2 if self.many_types and rng.random() < 0.4 else int(rng.integers(4))      # (2: past 255 types, often a shared-class one)
+        known = list(self.types)
+        if kind == 0 and known:
+            ty = known[int(rng.integers(len(known)))]
+        elif kind == 1 and self.keys:
+            ks = list(self.keys.values())
+            ty = ks[int(rng.integers(len(ks)))].ty        # (the type of a key: past 255 types it may be in the shared class)
+        elif kind == 2:
+            ty = self.pool[int(rng.integers(len(self.pool)))][0]
+            late = sorted(set(t for t, _ in self.pool if t not in self.types)) if self.many_types else []
+            if late:                                      # a type of the pool that has no class yet: past 255 types it never will
+                ty = late[int(rng.integers(len(late)))]
+        else:
+            ty = "N%d\0%d" % (self.seed, self.step) if rng.random() < 0.3 else "N%d.%d" % (self.seed, self.step)      # a new type
+        L = (0, 1, U32, U32, int(rng.integers(2, 12)))[int(rng.integers(5))]
+        st = self.begin()
+        rc = p.set_type_idle_limit(ty, L)
+        if ty in self.types or len(self.types) < CLASS_OTHER:
+            self.want(rc == OK, "set_type_idle_limit failed", rc, ty)
+            self.sight(ty)          # a type never seen before gets its class by this call
+            self.limits[ty] = L
+            self.limit_clone = self.handles.index(p)
+        else:                       # the type lands in the shared class, which has no limit of its own: nothing is set
+            self.want(rc == ERANGE, "set_type_idle_limit of a type in the shared class", rc, ty)
+            self.hit("a type limit refused with ERANGE")
+        self.unchanged(st, "set_type_idle_limit")
+
+    def feed_peek(self):
+        """What the dense feed would list, the checkpoint left where it is."""
+        if not self.g.num_objects:
+            return None
+        rows, old, new, total = self.g.changes(peek=True)
+        return rows.tolist(), old.tolist(), new.tolist(), int(total)
+
+    def witness(self, p, st):
+        """A placed key looked up right before a call that must leave the shadow alone."""
+        placed = np.flatnonzero(st["col"] != NONE)
+        if not placed.size:
+            return None
+        k = self.keys[self.row2key[int(placed[int(self.rng.integers(placed.size))])]]
+        self.plain_lookup(p, st, (k.ty, k.oid))
+        return (k.ty, k.oid)
+
+    def still_in_shadow(self, p, other, st, wit, what):
+        if wit is None:
+            return
+        t0 = p.device_round_trips()
+        self.check_lookup(st, p, other, wit, p.lookup, "lookup")
+        self.want(self.flags & CFG_NO_HOST_SHADOW or p.device_round_trips() == t0, what + ": a key lost its shadow entry", wit)
+
+    def op_census(self):
+        p, other = self.h()
+        st = self.begin()
+        by = bool(self.rng.random() < 0.6)
+        wit = self.witness(p, st)
+        feed = self.feed_peek()
+        rc, got = p.census(by, mid=lambda: other.len())
+        self.want(rc == OK, "census failed", rc)
+        n, m = st["n"], len(self.addr)
+        name = {cl: ty for ty, cl in self.types.items()}      # (the shared class has no name)
+        if by:
+            rows, lsum, _ = spec_classes.census(st["col"], self.K, st["load"], n, spec_classes.MAX_CLASSES, m)
+            want = [(name.get(c), self.addr[j], rows[j][c], lsum[j][c]) for j in range(m) for c in range(spec_classes.MAX_CLASSES) if rows[j][c]]
+        else:
+            rows, lsum, _ = spec_classes.census(st["col"], self.K, st["load"], n, spec_classes.MAX_CLASSES)
+            want = [(name.get(c), None, rows[c], lsum[c]) for c in range(spec_classes.MAX_CLASSES) if rows[c]]
+        self.want(got == want, "census: the entries are not the reference's, in server and class order", by,
+                  [(g, w) for g, w in zip(got, want) if g != w][:3], len(got), len(want))
+        self.want(sum(e[2] for e in got) == int((st["col"] != NONE).sum()), "census: the rows do not sum to the placed keys")
+        self.hit("census listed the shared class", any(e[0] is None for e in got))
+        self.hit("census by server with a server seen only through update", by and any(self.seen_by.get(e[1]) == {"update"} for e in got))
+        # read-only: the table, the feed and the shadow as they were (nothing stamped or counted: the model did neither, and the
+        # next sweep and the next fold compare the stamps and the counters as a whole)
+        self.unchanged(st, "census")
+        self.want(self.feed_peek() == feed, "census changed the feed")
+        self.still_in_shadow(p, other, st, wit, "census")
+        self.class_upload("census")
+
+    # ---- measured load (include/rio_gpu_object_placement.h, "measured load") ---------------------------------------------
+    def op_set_load_tracking(self):
+        p, other = self.h()
+        on = bool(self.rng.random() < 0.75)
+        self.want(p.set_load_tracking(on) == OK, "set_load_tracking failed")
+        self.tracking = on
+        self.track_off = self.track_off or not on
+
+    def op_get_object_load(self):
+        p, other = self.h()
+        rng = self.rng
+        st = self.begin()
+        kind = int(rng.integers(5))
+        if kind == 0:
+            key = ("never", "%d.%d" % (self.seed, self.step))
+        elif kind == 1 and self.last_dropped:
+            key = self.last_dropped[-1 - int(rng.integers(min(4, len(self.last_dropped))))]       # a key whose row was reclaimed
+        elif kind == 2:
+            key = (("a.b", "c"), ("a", "b.c"))[int(rng.integers(2))]
+        else:
+            key = self.pick_key(0.9)
+        rc, load = p.get_object_load(key[0], key[1])
+        self.want(rc == OK, "get_object_load failed", rc)
+        k = self.keys.get(self.kstr(key))
+        want = None if k is None else 1 if k.row is None or k.row >= st["n"] else int(st["load"][k.row])
+        self.want(load == want, "get_object_load: not the dense column's load at the key's row", key, load, want)
+        self.hit("get_object_load of a key never seen", k is None)
+        self.unchanged(st, "get_object_load")      # (it stamps and counts nothing: the next sweep and the next fold compare both)
+
+    def learn_unplaced_rows(self, p):
+        """The rows of the keys no listing has shown (they are not placed), so that a fold is compared key for key: the one row
+        whose load changes under rio_op_set_object_load, which is put back at once.  Such a key holds load 1 (a fresh or a
+        recycled row, and every earlier fold was preceded by this), and the requests counted for it move to its row."""
+        for ks, k in list(self.keys.items()):
+            if k.row is not None:
+                continue
+            rc, old = p.get_object_load(k.ty, k.oid)
+            self.want(rc == OK and old == 1, "get_object_load of a key that was never placed or loaded", ks, rc, old)
+            l0 = self.g.get_objects()[0]
+            self.want(p.set_object_load(k.ty, k.oid, 0) == OK, "set_object_load failed", ks)
+            l1 = self.g.get_objects()[0]
+            ch = [int(r) for r in np.flatnonzero(l1 != l0)] if len(l1) == len(l0) else []
+            self.want(len(ch) == 1 and ch[0] not in self.row2key, "set_object_load changed not exactly one row's load, a row without a key", ks, ch[:4])
+            self.want(p.set_object_load(k.ty, k.oid, 1) == OK, "set_object_load failed", ks)
+            self.new_row(k, ks, ch[0])
+
+    def op_fold_loads(self):
+        p, other = self.h()
+        rng = self.rng
+        self.learn_unplaced_rows(p)
+        st = self.begin()
+        wit = self.witness(p, st)
+        r = rng.random()
+        keeps, gains = (0, 1, 32768, 65535, KEEP_ONE), (0, 1, 7, U32)
+        if r < 0.3:
+            par = (KEEP_ONE, 1, 0, U32)          # every counter visible as load + requests
+        elif r < 0.42:
+            par = ((KEEP_ONE + 1, 1, 0, U32), (U32, 0, 0, U32), (KEEP_ONE, 1, 5, 4), (0, 7, U32, 0))[int(rng.integers(4))]
+        elif r < 0.7:
+            par = (keeps[int(rng.integers(5))], gains[int(rng.integers(4))], 0, U32)
+        else:                                    # clamps that bite from either side, and min_load == max_load
+            lo, hi = ((0, 3), (5, U32), (2, 2), (1, 1), (0, 0), (3, 9))[int(rng.integers(6))]
+            par = (keeps[int(rng.integers(5))], gains[int(rng.integers(4))], lo, hi)
+        keep, gain, lo, hi = par
+        self.want(not self.unknown_hits, "requests are left for keys without a row", list(self.unknown_hits)[:4])
+        total = int(self.Hc.sum())
+        seen0 = self.g.get_seen() if st["n"] else None
+        feed = self.feed_peek()
+        rc, changed, folded = p.fold_loads(keep, gain, lo, hi)
+        after = self.read()
+        n = after["n"]      # (rows a refused call interned reach the device with this call: fresh rows, load 1)
+        before = np.concatenate([st["load"], np.ones(n - st["n"], np.uint32)])
+        hits = self.g.get_hits() if n else np.zeros(0, np.uint32)
+        if keep > KEEP_ONE or lo > hi:
+            self.want(rc == EINVAL and (changed, folded) == (0, 0), "a fold that must be refused", par, rc, changed, folded)
+            self.want(np.array_equal(after["load"], before) and not hits.any(), "a refused fold changed the loads or the device's counters")
+            self.unchanged(st, "a refused fold")
+            self.refused_fold = self.refused_fold or total > 0      # (the counters stand: the next legal fold finds them)
+            if rng.random() < 0.5:
+                self.log.append("fold_loads (after a refusal)")
+                self.op_fold_loads()
+            return
+        self.want(rc == OK, "fold_loads failed", rc, par)
+        H = np.minimum(self.Hc[:n], U32).astype(np.uint32)
+        new, _, _ = spec_loads.load_fold(before, H, n, keep, gain, lo, hi)
+        mapped = np.array(sorted(self.row2key), np.int64)
+        self.want(mapped.size == 0 or int(mapped[-1]) < n, "the model holds a row past the table's end")
+        bad = mapped[after["load"][mapped] != new[mapped]]
+        self.want(bad.size == 0, "fold_loads: the loads are not load_fold's over the model's counters", par, bad[:8],
+                  before[bad[:8]], H[bad[:8]], after["load"][bad[:8]], new[bad[:8]])
+        # rows the model cannot map to a key belong to none (learn_unplaced_rows above): free rows, load 1 before and after,
+        # whatever keep and the clamps are
+        rest = np.ones(n, bool)
+        rest[mapped] = False
+        free = int(rest.sum())
+        self.want((before[rest] == 1).all() and (after["load"][rest] == 1).all(), "fold_loads: a row that belongs to no key does not hold load 1",
+                  par, np.flatnonzero(rest & ((before != 1) | (after["load"] != 1)))[:8], before[rest][:8], after["load"][rest][:8])
+        w_changed = int((new[mapped] != before[mapped]).sum())
+        self.want(changed == w_changed, "fold_loads: rows_changed counts the keys whose load differs", par, changed, w_changed, free)
+        self.want(folded == total, "fold_loads: hits_folded is not the requests the model counted", folded, total)
+        self.want(not hits.any(), "fold_loads left counters on the device", np.flatnonzero(hits)[:8])
+        used = spec_loads.used_of(after["col"], after["load"], n, after["m"]) if after["m"] else np.zeros(0, np.uint64)
+        self.want(np.array_equal(after["used"], used), "fold_loads: `used` differs", after["used"], used)
+        self.want(np.array_equal(after["col"][:st["n"]], st["col"]) and (after["col"][st["n"]:] == NONE).all() and
+                  np.array_equal(after["aff"][:st["n"]], st["aff"]), "fold_loads changed the column or the affinity")
+        self.want(seen0 is None or np.array_equal(self.g.get_seen()[:st["n"]], seen0), "fold_loads changed the stamps")
+        self.want(self.feed_peek() == feed, "fold_loads changed the feed")
+        self.share[1] += int((self.Hc[:n] != 0).sum())      # (share[0]: counters on rows the model does not know — none, see above)
+        free_load = max(lo, min(hi, 1 if keep == KEEP_ONE else 0))
+        self.hit("a fold saw a row that had changed hands since the last fold, with requests counted for its previous key",
+                 any(r in self.row2key for r in self.lost_hits))
+        self.hit("a fold with a non-empty free list and a free-row result other than 1", free > 0 and free_load != 1)
+        self.hit("a fold counted requests of shadow hits", bool(self.Hs.any()))
+        self.hit("a fold with the clock never set", not self.clock_ever and total > 0)
+        self.hit("a refused fold kept its counters for the next one", self.refused_fold)
+        self.hit("a fold changed no load", changed == 0)
+        self.hit("tracking switched off between two folds", self.track_off and self.count.get("fold_loads", 0) > 1)
+        self.Hc[:] = 0
+        self.Hs[:] = 0
+        self.unknown_hits, self.lost_hits, self.refused_fold, self.track_off = {}, set(), False, False
+        self.still_in_shadow(p, other, after, wit, "fold_loads")      # (a request of the next period)
+        if rng.random() < 0.25:      # the call to make after a fold: the loads are skewed now
+            self.log.append("rebalance (after fold)")
+            self.op_rebalance(order=BY_LOAD)
+
+    # ---- hot objects (include/rio_gpu_object_placement.h, "hot objects") ---------------------------------------------------
+    def op_hottest_objects(self):
+        p, other = self.h()
+        rng = self.rng
+        st = self.begin()
+        n, col, load = st["n"], st["col"], st["load"]
+        placed = [int(r) for r in np.flatnonzero(col != NONE)]
+        wit = self.witness(p, st)
+        only_update = [a for a in self.addr if self.seen_by.get(a) == {"update"}]
+        kind = int(rng.integers(10))
+        if kind < 4:
+            a = None                                        # every server
+        elif kind == 4 and only_update:
+            a = only_update[int(rng.integers(len(only_update)))]
+        elif kind == 5:
+            a = "10.251.%d.1:1" % (self.seed % 200)         # an address never seen
+        elif kind == 6:
+            a = self.odd[int(rng.integers(2))]              # a malformed one (a server like any other once it is known)
+        else:
+            a = self.members[int(rng.integers(len(self.members)))]
+        x = int(load[placed[int(rng.integers(len(placed)))]]) if placed else 1
+        min_load = (0, 1, x, min(x + 1, U32), U32)[int(rng.integers(5))]
+        keys, where, ld = [], {}, {}
+        for r in placed:
+            k = self.keys[self.row2key[r]]
+            keys.append((k.ty, k.oid))
+            where[(k.ty, k.oid)] = self.addr[col[r]] if col[r] < len(self.addr) else None
+            ld[(k.ty, k.oid)] = int(load[r])
+        if a is None:
+            full, nc = spec_top.op_hottest(keys, where, ld, None, min_load, len(keys) + 1)
+        else:          # (spec_top selects by address: an address nobody was given an id for holds nothing)
+            full, nc = spec_top.op_hottest(keys, where, ld, a, min_load, len(keys) + 1) if a in self.aid else ([], 0)
+        ties = [i for i in range(1, len(full)) if full[i - 1][3] == full[i][3] and i <= TOP_MAX]
+        tie = ties[int(rng.integers(len(ties)))] if ties else 1
+        cap = (0, 1, tie, tie, max(nc - 1, 0), nc, nc + 1, TOP_MAX, TOP_MAX + 1)[int(rng.integers(9))]
+        if cap != TOP_MAX + 1:
+            cap = min(cap, TOP_MAX)
+        rc, got, got_nc = p.hottest_objects(a, min_load, cap, mid=lambda: other.len())
+        if cap > TOP_MAX:
+            self.want(rc == EINVAL, "hottest_objects above RIO_GP_TOP_MAX was not refused", rc)
+            return self.unchanged(st, "a refused hottest_objects")
+        self.want(rc == OK, "hottest_objects failed", rc)
+        self.want(got == full[:cap], "hottest_objects: the listing is not the reference's (load descending, ties in row order)",
+                  a, min_load, cap, got[:4], full[:4])
+        self.want(got_nc == nc, "hottest_objects: n_candidates", got_nc, nc)
+        # ... and the dense layer's own restatement over the dense state
+        flags = spec_top.PLACED | (spec_top.ON_NODE if a is not None else 0)
+        if a is None or a in self.aid:
+            rows, kk, nodes, d_nc, _ = spec_top.top_rows(col, load, None, n, flags, self.aid.get(a, 0), min_load, cap)
+            dense = [(self.keys[self.row2key[int(r)]].ty, self.keys[self.row2key[int(r)]].oid,
+                      self.addr[nd] if nd < len(self.addr) else None, int(v)) for r, v, nd in zip(rows, kk, nodes)]
+            self.want(got == dense and got_nc == d_nc, "hottest_objects disagrees with top_rows over the dense state", got[:4], dense[:4])
+        self.hit("hottest cut inside a tie group", 0 < cap < nc and full[cap - 1][3] == full[cap][3])
+        self.hit("hottest on an address never seen", a is not None and a not in self.aid)
+        self.unchanged(st, "hottest_objects")       # read-only: nothing stamped or counted (the model did neither), the shadow intact
+        self.still_in_shadow(p, other, st, wit, "hottest_objects")
 
     # ---- the run ------------------------------------------------------------------------------------------------------
     def setup(self):
@@ -1177,6 +1721,7 @@ class Scenario:
         caps = int(rng.integers(3))      # 0: unbounded for a while (the reference cross-check), 1: tight from the start, 2: mixed
         for a in self.members:
             self.log.append("set_member")
+            self.carry([a], "member")
             st = self.begin()
             self.intern(st, [(("", ""), False, False, a, False)])
             capv = INF if caps == 0 else int(rng.integers(1, 5)) if caps == 1 else [INF, 3, 0][int(rng.integers(3))]
@@ -1202,6 +1747,18 @@ class Scenario:
             for k, a in zip(keys, addrs):
                 self.ref[0].update(k[0], k[1], a)
             self.settle(st, col, extra, "update_batch (bulk)")
+        if self.many_types:              # 280 keys of as many types in one batch: 255 numbered classes and the shared one
+            keys = self.pool[:280]
+            addrs = [self.members[k % len(self.members)] for k in range(len(keys))]
+            self.log.append("update_batch (types)")
+            st = self.begin()
+            self.intern(st, [(k, True, True, a, False) for k, a in zip(keys, addrs)])
+            self.want(self.handles[1].update_batch(keys, addrs) == OK, "the types' update_batch failed")
+            idx, col, load, extra = self.virtual(st, keys)
+            self.oracle.update_batch(col, len(self.addr), idx, [self.aid[a] for a in addrs])
+            for k, a in zip(keys, addrs):
+                self.ref[0].update(k[0], k[1], a)
+            self.settle(st, col, extra, "update_batch (types)")
 
     def run(self):
         names = [a for a, w in self.OPS for _ in range(w)]

@@ -4,9 +4,12 @@ driver).  The seeds are the ones tests/test_op_layer_driver.py holds to the cove
 
 Each seed ends with a short concurrent phase on a provider of its own: up to 8 threads, each with its own clone, its own keys and
 its own active requester with unbounded capacity — so the final table does not depend on the interleaving — beside one thread
-that alternates changes / objects_on_server / rebalance(max_moves=0) / tick.  At quiescence the model built per key from each
-thread's own log equals the snapshot, the feed's mirror equals the snapshot, and every listed change's old address was what the
-mirror held (spec_changes.apply, strict).
+that alternates changes / objects_on_server / rebalance(max_moves=0) / tick / fold_loads(65536, 1) / a count-only
+hottest_objects.  At quiescence the model built per key from each thread's own log equals the snapshot, the feed's mirror equals
+the snapshot, and every listed change's old address was what the mirror held (spec_changes.apply, strict).  Load tracking is on
+from before the threads start and each worker logs, per key, its calls that answered or set an address: after one final fold
+the hits_folded of all folds sum to the logged total and every key's load is 1 + its logged count — the header's "none is lost
+and none is counted twice" — and the census by type equals the snapshot's.
 
     python tests/test_gpu_op_layer_fuzz.py <seconds> [first_seed]     # a longer campaign; one JSON line
 """
@@ -20,7 +23,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SEEDS = int(os.environ.get("RIO_OP_FUZZ_SEEDS", "24"))
+SEEDS = int(os.environ.get("RIO_OP_FUZZ_SEEDS", "36"))
 
 
 def concurrent_phase(gp, seed, threads=6, steps=120):
@@ -28,16 +31,20 @@ def concurrent_phase(gp, seed, threads=6, steps=120):
     import spec_changes
     rng = np.random.default_rng(0xC0C00000 + seed)
     flags = drv.FLAGS[seed % 3]
-    p = drv.RealProvider.make(gp)(int(rng.choice([64 * threads, 4096])), 32, 2, flags)
+    rows_max = int(rng.choice([64 * threads, 4096]))
+    p = drv.RealProvider.make(gp)(rows_max, 32, 2, flags)
     addrs = ["10.7.%d.%d:7000" % (seed % 200, t) for t in range(threads)]
     for a in addrs:
         assert p.set_member(a, True, drv.INF) == drv.OK
+    assert p.set_load_tracking(True) == drv.OK
     final = [dict() for _ in range(threads)]
+    counted = [dict() for _ in range(threads)]     # per worker: key -> its calls that answered or set an address
+    folded = []
     errors = []
     stop = threading.Event()
 
     def worker(t):
-        mine, r, me, model = p.clone(), np.random.default_rng(seed * 100 + t), addrs[t], final[t]
+        mine, r, me, model, cnt = p.clone(), np.random.default_rng(seed * 100 + t), addrs[t], final[t], counted[t]
         try:
             for _ in range(steps):
                 key = ("C%d" % t, str(int(r.integers(40))))
@@ -48,10 +55,12 @@ def concurrent_phase(gp, seed, threads=6, steps=120):
                     assert rc == drv.OK and out == want, ("request", key, rc, out, want)
                     assert flag & 0xF == (drv.PLACED if key not in model else drv.LOCAL if want == me else drv.REDIRECT), ("flag", key, flag)
                     model[key] = want
+                    cnt[key] = cnt.get(key, 0) + 1
                 elif k < 0.6:
                     to = addrs[int(r.integers(threads))]
                     assert mine.update(key[0], key[1], to) == drv.OK
                     model[key] = to
+                    cnt[key] = cnt.get(key, 0) + 1
                 elif k < 0.75:
                     assert mine.remove(key[0], key[1]) == drv.OK
                     model.pop(key, None)
@@ -60,6 +69,8 @@ def concurrent_phase(gp, seed, threads=6, steps=120):
                     rc, found, out = fn(key[0], key[1], 64)
                     if rc != drv.EAGAIN:
                         assert rc == drv.OK and (out if found else None) == model.get(key), ("lookup", key, rc, found, out, model.get(key))
+                        if found:
+                            cnt[key] = cnt.get(key, 0) + 1
         except BaseException as e:
             errors.append((t, e))
         finally:
@@ -74,7 +85,14 @@ def concurrent_phase(gp, seed, threads=6, steps=120):
             k = 0
             while not stop.is_set():
                 k += 1
-                if k % 4 == 0:
+                if k % 6 == 4:
+                    rc, _, hf = mine.fold_loads(65536, 1)
+                    assert rc == drv.OK, ("fold_loads", rc)
+                    folded.append(hf)
+                elif k % 6 == 5:
+                    rc, objs, nc = mine.hottest_objects(None, 0, 0)
+                    assert rc == drv.OK and objs == [] and nc <= 40 * threads, ("hottest_objects", rc, nc)
+                elif k % 4 == 0:
                     rc, full, entries = mine.changes()
                     assert rc == drv.OK and full == first[0], ("changes", rc, full)
                     first[0] = False
@@ -114,6 +132,28 @@ def concurrent_phase(gp, seed, threads=6, steps=120):
         assert rc == drv.OK and full == first[0], (seed, "changes at quiescence", rc, full)
         mirror[0] = spec_changes.apply(mirror[0], full, entries, strict=True)
         assert mirror[0] == want, (seed, "the feed's mirror differs from the snapshot at quiescence")
+        # measured load: one final fold, then every request the workers logged is in exactly one fold and on its own key
+        rc, _, hf = p.fold_loads(65536, 1)
+        assert rc == drv.OK, (seed, "the final fold", rc)
+        total = {}
+        for c in counted:
+            total.update(c)        # (every worker has keys of its own)
+        assert sum(folded) + hf == sum(total.values()), (seed, "hits_folded over all folds", sum(folded) + hf, sum(total.values()))
+        created = set(total)       # (a key exists from its first request or update: both are logged)
+        assert len(created) <= rows_max and p.dense().num_objects == len(created), (seed, "the table of this phase never reclaims",
+                                                                                     len(created), rows_max, p.dense().num_objects)
+        for key in sorted(created):
+            rc, load = p.get_object_load(key[0], key[1])
+            assert rc == drv.OK and load == 1 + total[key], (seed, "a key's load is not 1 + its logged requests", key, load, total[key])
+        rc, cen = p.census()
+        by_rows, by_load = {}, {}
+        for (ty, _), a in want.items():
+            by_rows[ty] = by_rows.get(ty, 0) + 1
+        for key in want:
+            by_load[key[0]] = by_load.get(key[0], 0) + 1 + total[key]
+        # (class order is the order in which the workers' types were first interned: whichever thread came first)
+        assert rc == drv.OK and len(cen) == len(by_rows) and sorted(cen) == sorted((ty, None, by_rows[ty], by_load[ty]) for ty in by_rows), \
+            (seed, "the census by type differs from the snapshot's", cen, by_rows, by_load)
     finally:
         p.close()
     return threads * steps

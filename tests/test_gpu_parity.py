@@ -512,6 +512,32 @@ def test_tick_edge_shapes(gp, oracle):
                 np.full(3, 10, np.uint64), np.zeros(3, np.uint8))                        # no live node at all
 
 
+def test_tick_zero_load_rows_behind_an_exact_fill(gp, oracle):
+    """The water-fill places a row iff its exclusive prefix Q lies below the round's free capacity F and the row fits the node
+    whose interval holds Q.  A zero-load row behind rows that fill the cluster exactly has Q == F: it stays unplaced, also
+    where it shares a 256-row tile with the rows that filled it (the tile then lies inside one node's interval and ends at
+    F); a zero-load row at an inner boundary goes to the next node.  Every spilling row has a dead node for its affinity."""
+    ones = lambda k: np.ones(k, np.uint8)
+    dead = lambda m: np.concatenate([ones(m - 1), np.zeros(1, np.uint8)])
+    pend = lambda k: np.full(k, NONE, np.uint32)
+    L = lambda *v: np.array(v, np.uint32)
+    # one node, filled exactly by the first two rows: the zero-load rows behind them, and everything later, stay out
+    _check_tick(gp, oracle, pend(6), L(2, 3, 0, 0, 1, 0), np.full(6, 1, np.uint32), np.array([5, 9], np.uint64), dead(2))
+    # two nodes (the one with free 4 comes first in the fill order): a zero-load row at the inner boundary, two at the end
+    _check_tick(gp, oracle, pend(5), L(4, 0, 3, 0, 0), np.full(5, 2, np.uint32), np.array([3, 4, 9], np.uint64), dead(3))
+    # the fill ends inside the second tile: rows 256 .. 299 fill it, the zero-load rows of that tile and of the third stay out
+    _check_tick(gp, oracle, pend(600), np.concatenate([np.ones(300, np.uint32), np.zeros(300, np.uint32)]),
+                np.full(600, 1, np.uint32), np.array([300, 9], np.uint64), dead(2), rounds=3)
+    # the table on which the string layer's fuzz met it: rows 1, 16, 19 and 22 spill, node 3 has room for one unit of load
+    cur = L(3, NONE, 0, 2, 2, 0, 1, 3, 2, 0, 3, 2, 3, 2, 1, 0, 6, 0, 2, 4, 3, 2, NONE, 2, NONE, 3, 2, 1, 3, 1, NONE, 2, 2, 2,
+            NONE, NONE, NONE, NONE, NONE, NONE, 3, 2, 0)
+    load = L(1, 1, 4, *([0] * 21), 1, *([0] * 7), *([1] * 11))
+    off = 0xFFFFFFFE
+    aff = L(3, 4, 0, 2, 2, 0, 1, 3, 2, 0, 3, 2, 3, 2, 1, 0, 6, 0, 2, 4, 3, 2, 4, 2, off, 3, 2, 1, 3, 1, 3, 2, 0, 2, off, off, off,
+            off, off, off, 3, 2, 0)
+    _check_tick(gp, oracle, cur, load, aff, np.array([0, 0, 3, 3, INF, INF, INF], np.uint64), np.array([1, 1, 1, 1, 0, 0, 0], np.uint8))
+
+
 def test_tick_equals_reference_policy_capacity_infinite(gp, oracle):
     """cap = inf: the kernels reproduce service.rs:193-254 run object by object (string oracle)."""
     rng = np.random.default_rng(11)
