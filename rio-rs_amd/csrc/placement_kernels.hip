@@ -7486,13 +7486,15 @@ u32 launch_remap(u32* assign, u32* aff, u32* B, u64 rows, u64 n_count, u32 m, co
 // r < n that are placed (A[r] != kNone, raw values) with S[r] < cutoff: an ordered compaction, on the feed's per-tile counts and
 // workgroup sums.
 //   k_exp_count  the count pass over the idle predicate on (A, S); workgroup 0 also zeroes the freed-load word.
-//   k_exp_apply  the list pass: a listed row is written out as (row, A[row]), loses its node (the lane stores its four A words
-//                back, dwordx4) and, under the row lifecycle, becomes a non-object; its load goes into the freed-load sum and,
-//                when `used` is maintained, off its node: per workgroup through an LDS histogram (m <= kExpLdsNodes: a
-//                workgroup's rows share few nodes' words), else straight to `used` (more nodes than that spread the atomics over
-//                as many addresses; the histogram would not fit next to the tile offsets).  Integer sums: the order of the
-//                additions does not show.  Only the tile's flags outlive its loads: a lane with a hit reads its quad of A again
-//                (a cache hit); holding the tile across the listing spilled to scratch at eight waves per SIMD.
+//   exp_apply    the list pass, once for every idle predicate (`flags16`, oc_rank's): a listed row is written out as
+//                (row, A[row]), loses its node (the lane stores its four A words back, dwordx4) and, under the row lifecycle,
+//                becomes a non-object; its load goes into the freed-load sum and, when `used` is maintained, off its node: per
+//                workgroup through an LDS histogram (m <= kExpLdsNodes: a workgroup's rows share few nodes' words), else straight
+//                to `used` (more nodes than that spread the atomics over as many addresses; the histogram would not fit next to
+//                the tile offsets).  Integer sums: the order of the additions does not show.  Only the tile's flags outlive its
+//                loads: a lane with a hit reads its quad of A again (a cache hit); holding the tile across the listing spilled
+//                to scratch at eight waves per SIMD.  The predicate decides who is idle, not what happens then.
+//   k_exp_apply  exp_apply over the idle predicate of the count pass.
 //   k_touch      S[idx[k]] = max(S[idx[k]], epoch), a scatter of atomic maxima: duplicates and order do not matter.
 //   k_seen_merge S[r] = max(S[r], stamps ? stamps[r] : epoch) for r < rows, four rows per lane; a quad is stored only where it
 //                rose.  S is padded like the other columns; `stamps` is the caller's and is read by quads only where whole quads
@@ -7518,12 +7520,12 @@ __global__ __launch_bounds__(kChgWaves * 64, 8) void k_exp_count(const u32* __re
     if (threadIdx.x == 0 && blockIdx.x == 0) *freed = 0;  // (k_exp_apply, a later launch, adds into it)
 }
 
-__global__ __launch_bounds__(kChgWaves * 64, 8) void k_exp_apply(u32* __restrict__ A, const u32* __restrict__ S, const ChgPlan p,
-                                                               u32 cutoff, const u32* __restrict__ cnt,
-                                                               const u32* __restrict__ gsum, u64 cap, u32* __restrict__ rows,
-                                                               u32* __restrict__ node, u32* __restrict__ aff_life,
-                                                               const u32* __restrict__ load, u32 m, u64* __restrict__ used,
-                                                               u32 hist, u64* __restrict__ freed) {
+// What the caller's flags16 needs in LDS is written before the call: the barrier in front of the first flags pass is in here.
+// (No __restrict__ here: flags16 reads A through the kernel's own pointer; the kernels' qualifiers hold after inlining.)
+template <class Flags>
+__device__ __forceinline__ void exp_apply(u32* A, const ChgPlan& p, const u32* cnt, const u32* gsum, u64 cap, u32* rows, u32* node,
+                                          u32* aff_life, const u32* load, u32 m, u64* used, u32 hist, u64* freed,
+                                          Flags&& flags16) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64* rel = reinterpret_cast<u64*>(smem);  // [m] load released per node (hist only)
     __shared__ u32 toff[kChgMaxTpg];
@@ -7536,46 +7538,52 @@ __global__ __launch_bounds__(kChgWaves * 64, 8) void k_exp_apply(u32* __restrict
     if (threadIdx.x == 0) gfree = 0;
     __syncthreads();
     u64 fr = 0;
-    oc_rank(
-        p, tl, toff, cap,
-        [&](u64 lo, u32 lane) {
-            uint4 a[4], sv[4];
-            chg_load(A, S, lo, lane, a, sv);
-            u32 fl = 0;
+    oc_rank(p, tl, toff, cap, flags16, [&](int, u64 i0, u32 f, u64 r, u64 limit) {
+        const uint4 q = *reinterpret_cast<const uint4*>(A + i0);
+        u32 av[4] = {q.x, q.y, q.z, q.w};
+        bool listed = false;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) fl |= exp_flags(a[s], sv[s], cutoff, lo + (u64)s * 256 + lane * 4, p.n) << (4 * s);
-            return fl;
-        },
-        [&](int, u64 i0, u32 f, u64 r, u64 limit) {
-            const uint4 q =*reinterpret_cast<const uint4*>(A + i0);
-            u32 av[4] = {q.x, q.y, q.z, q.w};
-            bool listed = false;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (!((f >> j) & 1u)) continue;
-                if (r < limit) {
-                    const u32 li = load[i0 + j];
-                    rows[r] = (u32)(i0 + j);
-                    node[r] = av[j];
-                    fr += li;
-                    if (used && av[j] < m) {
-                        if (hist) atomicAdd(&rel[av[j]], (u64)li);
-                        else atomicAdd(&used[av[j]], (u64)0 - (u64)li);
-                    }
-                    if (aff_life) aff_life[i0 + j] = kAffInactive;  // row lifecycle: an expired row is no longer an object
-                    av[j] = kNone;
-                    listed = true;
+        for (int j = 0; j < 4; ++j) {
+            if (!((f >> j) & 1u)) continue;
+            if (r < limit) {
+                const u32 li = load[i0 + j];
+                rows[r] = (u32)(i0 + j);
+                node[r] = av[j];
+                fr += li;
+                if (used && av[j] < m) {
+                    if (hist) atomicAdd(&rel[av[j]], (u64)li);
+                    else atomicAdd(&used[av[j]], (u64)0 - (u64)li);
                 }
-                ++r;
+                if (aff_life) aff_life[i0 + j] = kAffInactive;  // row lifecycle: an expired row is no longer an object
+                av[j] = kNone;
+                listed = true;
             }
-            if (listed) *reinterpret_cast<uint4*>(A + i0) = make_uint4(av[0], av[1], av[2], av[3]);
-        });
+            ++r;
+        }
+        if (listed) *reinterpret_cast<uint4*>(A + i0) = make_uint4(av[0], av[1], av[2], av[3]);
+    });
     if (fr) atomicAdd(&gfree, fr);
     __syncthreads();
     if (threadIdx.x == 0 && gfree) atomicAdd(freed, gfree);
     if (hist)
         for (u32 j = threadIdx.x; j < m; j += kChgWaves * 64)
             if (rel[j]) atomicAdd(&used[j], (u64)0 - rel[j]);
+}
+
+__global__ __launch_bounds__(kChgWaves * 64, 8) void k_exp_apply(u32* __restrict__ A, const u32* __restrict__ S, const ChgPlan p,
+                                                               u32 cutoff, const u32* __restrict__ cnt,
+                                                               const u32* __restrict__ gsum, u64 cap, u32* __restrict__ rows,
+                                                               u32* __restrict__ node, u32* __restrict__ aff_life,
+                                                               const u32* __restrict__ load, u32 m, u64* __restrict__ used,
+                                                               u32 hist, u64* __restrict__ freed) {
+    exp_apply(A, p, cnt, gsum, cap, rows, node, aff_life, load, m, used, hist, freed, [&](u64 lo, u32 lane) {
+        uint4 a[4], sv[4];
+        chg_load(A, S, lo, lane, a, sv);
+        u32 fl = 0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) fl |= exp_flags(a[s], sv[s], cutoff, lo + (u64)s * 256 + lane * 4, p.n) << (4 * s);
+        return fl;
+    });
 }
 
 __global__ __launch_bounds__(256) void k_touch(u32* __restrict__ S, u64 n_obj, const u32* __restrict__ idx, u64 n, u32 epoch,
@@ -7615,12 +7623,17 @@ void launch_exp_count(const u32* A, const u32* S, const ChgPlan& p, u32 cutoff, 
     hipLaunchKernelGGL(k_exp_count, dim3(p.G), dim3(kChgWaves * 64), 0, s, A, S, p, cutoff, cnt, gsum, freed);
     hipLaunchKernelGGL(k_chg_scan, dim3(1), dim3(kChgWaves * 64), 0, s, gsum, p.G, total);
 }
-void launch_exp_apply(u32* A, const u32* S, const ChgPlan& p, u32 cutoff, const u32* cnt, const u32* gsum, u64 cap, u32* rows,
-                      u32* node, u32* aff_life, const u32* load, u32 m, u64* used, u64* freed, hipStream_t s) {
+// The launch of an apply kernel: `front...` are its arguments up to `used`; `hist` and `freed` follow them.
+template <class... KArgs, class... Args>
+static void launch_apply(void (*k)(KArgs...), const ChgPlan& p, u64 cap, u32 m, const u64* used, u64* freed, hipStream_t s,
+                         const Args&... front) {
     if (!p.G || !cap) return;
     const bool hist = used && m <= kExpLdsNodes;
-    hipLaunchKernelGGL(k_exp_apply, dim3(p.G), dim3(kChgWaves * 64), hist ? (size_t)m * sizeof(u64) : 0, s, A, S, p, cutoff, cnt,
-                       gsum, cap, rows, node, aff_life, load, m, used, hist ? 1u : 0u, freed);
+    hipLaunchKernelGGL(k, dim3(p.G), dim3(kChgWaves * 64), hist ? (size_t)m * sizeof(u64) : 0, s, front..., hist ? 1u : 0u, freed);
+}
+void launch_exp_apply(u32* A, const u32* S, const ChgPlan& p, u32 cutoff, const u32* cnt, const u32* gsum, u64 cap, u32* rows,
+                      u32* node, u32* aff_life, const u32* load, u32 m, u64* used, u64* freed, hipStream_t s) {
+    launch_apply(k_exp_apply, p, cap, m, used, freed, s, A, S, p, cutoff, cnt, gsum, cap, rows, node, aff_life, load, m, used);
 }
 void launch_touch(u32* S, u64 n_obj, const u32* idx, u64 n, u32 epoch, DevStats* st, hipStream_t s) {
     if (!n) return;
@@ -8069,7 +8082,7 @@ void launch_top_rows(const u32* K, const u32* A, u64 n, u32 min_key, u32 filt, u
 //   k_cls_publish one workgroup behind the count pass: the sum of the copies into mapped pinned memory, and the copies back to
 //                 zero for the next call (they are zero at rest: no fill in front of the count pass; a call that fails where
 //                 nobody can tell whether this launch ran has the host fill them before the next one).
-//   k_expc_apply  k_exp_apply over the same predicate.
+//   k_expc_apply  exp_apply over the same predicate.
 //   k_census      a streaming pass over A, K and load, four rows per lane: a placed row adds (1, load) to its cell.  LDSACC:
 //                 the cells [blockIdx.y * kCensusLdsCells, + kCensusLdsCells) are workgroup-private LDS accumulators (u32
 //                 rows, u64 load), flushed once as global adds of the non-zero words; a grid of several slices reads the
@@ -8151,64 +8164,20 @@ __global__ __launch_bounds__(kChgWaves * 64, 8) void k_expc_apply(u32* __restric
                                                                 u64 cap, u32* __restrict__ rows, u32* __restrict__ node,
                                                                 u32* __restrict__ aff_life, const u32* __restrict__ load, u32 m,
                                                                 u64* __restrict__ used, u32 hist, u64* __restrict__ freed) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    u64* rel = reinterpret_cast<u64*>(smem);  // [m] load released per node (hist only)
-    __shared__ u32 toff[kChgMaxTpg];
     __shared__ u32 ct[kClsMax];
-    __shared__ u32 lds[4];
-    __shared__ u64 gfree;
-    const OcTiles<u64> tl = oc_tile_offsets(p, cnt, gsum, cap, toff, lds);
-    if (!tl.go) return;
-    ct[threadIdx.x] = cutoffs.v[threadIdx.x];
-    if (hist)
-        for (u32 j = threadIdx.x; j < m; j += kChgWaves * 64) rel[j] = 0;
-    if (threadIdx.x == 0) gfree = 0;
-    __syncthreads();
-    u64 fr = 0;
-    oc_rank(
-        p, tl, toff, cap,
-        [&](u64 lo, u32 lane) {
-            // (a step at a time: this pass re-reads only the tiles that hold a listed row, and a whole tile of A and S next to
-            //  the table look-ups spilled to scratch at eight waves per SIMD)
-            u32 fl = 0;
+    ct[threadIdx.x] = cutoffs.v[threadIdx.x];  // (in front of exp_apply's barrier)
+    exp_apply(A, p, cnt, gsum, cap, rows, node, aff_life, load, m, used, hist, freed, [&](u64 lo, u32 lane) {
+        // (a step at a time: this pass re-reads only the tiles that hold a listed row, and a whole tile of A and S next to
+        //  the table look-ups spilled to scratch at eight waves per SIMD)
+        u32 fl = 0;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const u64 i0 = lo + (u64)s * 256 + lane * 4;
-                const uint4 a = *reinterpret_cast<const uint4*>(A + i0), sv = *reinterpret_cast<const uint4*>(S + i0);
-                fl |= expc_flags(a, sv, Kw[i0 >> 2], ct, i0, p.n) << (4 * s);
-            }
-            return fl;
-        },
-        [&](int, u64 i0, u32 f, u64 r, u64 limit) {  // (k_exp_apply's body: the class decides who is idle, not what happens then)
-            const uint4 q = *reinterpret_cast<const uint4*>(A + i0);
-            u32 av[4] = {q.x, q.y, q.z, q.w};
-            bool listed = false;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (!((f >> j) & 1u)) continue;
-                if (r < limit) {
-                    const u32 li = load[i0 + j];
-                    rows[r] = (u32)(i0 + j);
-                    node[r] = av[j];
-                    fr += li;
-                    if (used && av[j] < m) {
-                        if (hist) atomicAdd(&rel[av[j]], (u64)li);
-                        else atomicAdd(&used[av[j]], (u64)0 - (u64)li);
-                    }
-                    if (aff_life) aff_life[i0 + j] = kAffInactive;
-                    av[j] = kNone;
-                    listed = true;
-                }
-                ++r;
-            }
-            if (listed) *reinterpret_cast<uint4*>(A + i0) = make_uint4(av[0], av[1], av[2], av[3]);
-        });
-    if (fr) atomicAdd(&gfree, fr);
-    __syncthreads();
-    if (threadIdx.x == 0 && gfree) atomicAdd(freed, gfree);
-    if (hist)
-        for (u32 j = threadIdx.x; j < m; j += kChgWaves * 64)
-            if (rel[j]) atomicAdd(&used[j], (u64)0 - rel[j]);
+        for (int s = 0; s < 4; ++s) {
+            const u64 i0 = lo + (u64)s * 256 + lane * 4;
+            const uint4 a = *reinterpret_cast<const uint4*>(A + i0), sv = *reinterpret_cast<const uint4*>(S + i0);
+            fl |= expc_flags(a, sv, Kw[i0 >> 2], ct, i0, p.n) << (4 * s);
+        }
+        return fl;
+    });
 }
 
 constexpr u32 kCensusBlock = 1024;
@@ -8292,13 +8261,11 @@ void launch_expc_count(const u32* A, const u32* S, const unsigned char* K, const
     }
     hipLaunchKernelGGL(k_cls_publish, dim3(1), dim3(kClsMax), 0, s, by_class, host_by_class);
 }
-void launch_expc_apply(u32* A, const u32* S, const unsigned char* K, const ChgPlan& p, const ClsCutoffs& cutoffs, const u32* cnt, const u32* gsum, u64 cap, u32* rows, u32* node, u32* aff_life, const u32* load, u32 m,
-                       u64* used, u64* freed, hipStream_t s) {
-    if (!p.G || !cap) return;
-    const bool hist = used && m <= kExpLdsNodes;
-    hipLaunchKernelGGL(k_expc_apply, dim3(p.G), dim3(kChgWaves * 64), hist ? (size_t)m * sizeof(u64) : 0, s, A, S,
-                       reinterpret_cast<const u32*>(K), p, cutoffs, cnt, gsum, cap, rows, node, aff_life, load, m, used,
-                       hist ? 1u : 0u, freed);
+void launch_expc_apply(u32* A, const u32* S, const unsigned char* K, const ChgPlan& p, const ClsCutoffs& cutoffs, const u32* cnt,
+                       const u32* gsum, u64 cap, u32* rows, u32* node, u32* aff_life, const u32* load, u32 m, u64* used,
+                       u64* freed, hipStream_t s) {
+    launch_apply(k_expc_apply, p, cap, m, used, freed, s, A, S, reinterpret_cast<const u32*>(K), p, cutoffs, cnt, gsum, cap, rows,
+                 node, aff_life, load, m, used);
 }
 void launch_census(const u32* A, const unsigned char* K, const u32* load, u64 n, u32 m, u32 n_classes, bool by_node,
                    u64* out_rows, u64* out_load, u64* other, hipStream_t s) {

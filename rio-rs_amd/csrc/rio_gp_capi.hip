@@ -1255,6 +1255,49 @@ int read_stats(rio_gp* h) {
     return RIO_GP_OK;
 }
 
+// A `_dev` batch of a per-row column writer: its kernel skips the entries it cannot take and counts them in dstats.
+template <class Launch>
+int dev_batch(rio_gp* h, const char* who, Launch&& launch) {
+    int rc;
+    if ((rc = zero_stats(h))) return rc;
+    launch();
+    if ((rc = read_stats(h))) return rc;
+    if (h->h_stats[0].err) return fail(h, RIO_GP_EINVAL, std::string(who) + ": invalid entries were skipped");
+    return RIO_GP_OK;
+}
+
+// A host batch of a per-row column writer on its way to the device: `first` (n words) into stage[0] and, if given, `second` (n
+// elements of `elem` bytes) into stage[1]; d = the device pointers (null for n = 0: nothing is staged).  An index batch names
+// its family's `begin`, and the order is the rule: a row-sharded handle is refused, then every index is checked against h->n,
+// then the first-use allocation runs, so that a rejected call allocates nothing.  (A whole column, the merges', passes no
+// `begin`: its caller has checked its rows and begun.)  staged_done is the other end.
+struct Staged {
+    const u32* first;
+    const void* second;
+};
+int stage_batch(rio_gp* h, const char* who, int (*begin)(rio_gp*, const char*), uint64_t n, const uint32_t* first,
+                const void* second, size_t elem, Staged& d) {
+    int rc;
+    d = {nullptr, nullptr};
+    if (begin) {
+        if ((rc = refuse_row_sharded(h, who))) return rc;
+        for (uint64_t k = 0; k < n; ++k)
+            if (first[k] >= h->n) return fail(h, RIO_GP_EINVAL, std::string(who) + ": object index out of range");
+        if ((rc = begin(h, who))) return rc;
+    }
+    if (!n) return RIO_GP_OK;
+    if ((rc = ensure(h, h->stage[0], n * sizeof(u32))) || (second && (rc = ensure(h, h->stage[1], n * elem)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, first, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    if (second) HIPCHK(h, hipMemcpyAsync(h->stage[1].p, second, n * elem, hipMemcpyHostToDevice, h->stream));
+    d = {(const u32*)h->stage[0].p, second ? h->stage[1].p : nullptr};
+    return RIO_GP_OK;
+}
+int staged_done(rio_gp* h) {
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's arrays are read until here
+    return RIO_GP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2124,28 +2167,17 @@ int rio_gp_touch_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, uint3
     int rc;
     if ((rc = exp_begin(h, "rio_gp_touch_batch"))) return rc;
     if (!n) return RIO_GP_OK;
-    if ((rc = zero_stats(h))) return rc;
-    launch_touch(h->exp_S, h->n, d_idx, n, epoch, h->dstats, h->stream);
-    if ((rc = read_stats(h))) return rc;
-    if (h->h_stats[0].err) return fail(h, RIO_GP_EINVAL, "rio_gp_touch_batch: invalid entries were skipped");
-    return RIO_GP_OK;
+    return dev_batch(h, "rio_gp_touch_batch", [&] { launch_touch(h->exp_S, h->n, d_idx, n, epoch, h->dstats, h->stream); });
 }
 
 int rio_gp_touch_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, uint32_t epoch) {
     if (!h || (n && !idx)) return RIO_GP_EINVAL;
     Locked g(h);
     int rc;
-    if ((rc = refuse_row_sharded(h, "rio_gp_touch_batch"))) return rc;
-    for (uint64_t k = 0; k < n; ++k)
-        if (idx[k] >= h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_touch_batch: object index out of range");
-    if ((rc = exp_begin(h, "rio_gp_touch_batch"))) return rc;
-    if (!n) return RIO_GP_OK;
-    if ((rc = ensure(h, h->stage[0], n * sizeof(u32)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, idx, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-    launch_touch(h->exp_S, h->n, (const u32*)h->stage[0].p, n, epoch, h->dstats, h->stream);  // (validated: nothing is counted)
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's array is read until here
-    return RIO_GP_OK;
+    Staged d;
+    if ((rc = stage_batch(h, "rio_gp_touch_batch", exp_begin, n, idx, nullptr, 0, d)) || !n) return rc;
+    launch_touch(h->exp_S, h->n, d.first, n, epoch, h->dstats, h->stream);  // (validated: nothing is counted)
+    return staged_done(h);
 }
 
 int rio_gp_touch_all(rio_gp_t* h, uint32_t epoch) {
@@ -2175,13 +2207,10 @@ int rio_gp_touch_merge(rio_gp_t* h, uint64_t rows, const uint32_t* stamps) {
     if (rows > h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_touch_merge: rows exceeds the object table");
     int rc;
     if ((rc = exp_begin(h, "rio_gp_touch_merge"))) return rc;
-    if (!rows) return RIO_GP_OK;
-    if ((rc = ensure(h, h->stage[0], rows * sizeof(u32)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, stamps, rows * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-    launch_seen_merge(h->exp_S, (const u32*)h->stage[0].p, 0u, rows, h->stream);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's array is read until here
-    return RIO_GP_OK;
+    Staged d;
+    if ((rc = stage_batch(h, "rio_gp_touch_merge", nullptr, rows, stamps, nullptr, 0, d)) || !rows) return rc;
+    launch_seen_merge(h->exp_S, d.first, 0u, rows, h->stream);
+    return staged_done(h);
 }
 
 int rio_gp_get_seen(rio_gp_t* h, uint64_t n, uint32_t* out) {
@@ -2195,29 +2224,99 @@ int rio_gp_get_seen(rio_gp_t* h, uint64_t n, uint32_t* out) {
     return RIO_GP_OK;
 }
 
-// checks shared by both forms: nothing is changed before they pass
-static int exp_args(rio_gp* h, const void* r, const void* o, uint64_t cap, const uint64_t* n_idle) {
-    if (!n_idle) return fail(h, RIO_GP_EINVAL, "rio_gp_expire: n_idle is NULL");
-    if ((r != nullptr) != (o != nullptr))
-        return fail(h, RIO_GP_EINVAL, "rio_gp_expire: out_rows / out_node are given together or not at all");
-    if (!r && cap) return fail(h, RIO_GP_EINVAL, "rio_gp_expire: cap without a listing");
-    return RIO_GP_OK;
+// The idle sweep (rio_gp_expire*, rio_gp_expire_classes*): one driver behind the four calls.  What a call names idle:
+struct Sweep {
+    bool classes;             // false: S < cutoff for every row; the plain sweep never touches cls_*
+    u32 cutoff;
+    u32 n_classes;            // true: S < cutoffs[K[row]], K < n_classes (a row of a class from n_classes on is never idle) ...
+    const uint32_t* cutoffs;
+    uint64_t* idle_by_class;  // ... and the idle rows of every class are counted into here (may be NULL)
+};
+static int cls_begin(rio_gp* h, const char* who);  // (object classes, below)
+
+// The copies of the per-class counts are zero between the calls because k_cls_publish, the last launch of the count pass, leaves
+// them so.  A call that cannot tell whether that launch ran (a launch error, a failed wait) has the next call of the section
+// fill them again: a sweep after a failed one must not add to what the failed one left.
+static int expc_failed(rio_gp* h, const char* msg) {
+    h->cls_tab_stale = true;  // (cls_begin zeroes the copies before the next call of the section runs)
+    return fail(h, RIO_GP_EUPSTREAM, msg);
 }
-// The count pass over the committed column and S; the total lands in the mapped word.  It changes nothing of the table.
-static int exp_count(rio_gp* h, const ChgPlan& p, u32 cutoff) {
+// The count pass over the committed column and S (and K); the total lands in the mapped word, the per-class counts in h->h_cls
+// (mapped too: complete after the next wait).  It changes nothing of the table.
+static int sweep_count(rio_gp* h, const ChgPlan& p, const Sweep& w, const ClsCutoffs& ct) {
     *h->h_chg = 0;
-    launch_exp_count(h->assign[h->cur], h->exp_S, p, cutoff, h->chg_cnt, h->chg_gsum, h->d_chg, h->exp_freed, h->stream);
+    if (w.classes) {
+        launch_expc_count(h->assign[h->cur], h->exp_S, h->cls_K, p, ct, h->chg_cnt, h->chg_gsum, h->d_chg, h->cls_tab, h->d_cls,
+                          h->exp_freed, h->stream);
+        if (hipGetLastError() != hipSuccess) return expc_failed(h, "rio_gp_expire_classes: a launch of the count pass failed");
+        return RIO_GP_OK;
+    }
+    launch_exp_count(h->assign[h->cur], h->exp_S, p, w.cutoff, h->chg_cnt, h->chg_gsum, h->d_chg, h->exp_freed, h->stream);
     HIPCHK(h, hipGetLastError());
     return RIO_GP_OK;
 }
 // The apply pass for the first `cap` idle rows, and the freed load into the mapped line's second u64.  `used` follows the writes
 // when it is valid, as the remove kernels keep it.  The caller has not waited yet.
-static int exp_apply(rio_gp* h, const ChgPlan& p, u32 cutoff, u64 cap, u32* d_rows, u32* d_node) {
+static int sweep_apply(rio_gp* h, const ChgPlan& p, const Sweep& w, const ClsCutoffs& ct, u64 cap, u32* d_rows, u32* d_node) {
     u64* const used = h->used.live();
-    launch_exp_apply(h->assign[h->cur], h->exp_S, p, cutoff, h->chg_cnt, h->chg_gsum, cap, d_rows, d_node, aff_life(h), h->load,
-                     h->m, used, h->exp_freed, h->stream);
+    if (w.classes)
+        launch_expc_apply(h->assign[h->cur], h->exp_S, h->cls_K, p, ct, h->chg_cnt, h->chg_gsum, cap, d_rows, d_node, aff_life(h),
+                          h->load, h->m, used, h->exp_freed, h->stream);
+    else
+        launch_exp_apply(h->assign[h->cur], h->exp_S, p, w.cutoff, h->chg_cnt, h->chg_gsum, cap, d_rows, d_node, aff_life(h),
+                         h->load, h->m, used, h->exp_freed, h->stream);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(reinterpret_cast<u64*>(h->h_chg) + 1, h->exp_freed, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    return RIO_GP_OK;
+}
+
+// Both forms.  to_host: rows / node are the caller's host arrays: count, wait, clamp to cap, apply into chg_stage, read the
+// listing back.  Otherwise they are device arrays: the apply pass reads the prefix the count pass left on the device and drops
+// ranks >= cap itself, one wait for the call.
+static int sweep(rio_gp* h, const Sweep& w, bool to_host, uint32_t* rows, uint32_t* node, uint64_t cap, uint64_t* n_idle,
+                 uint64_t* load_freed) {
+    // the checks: nothing is allocated, launched or changed before they pass
+    if (w.classes && (w.n_classes < 1 || w.n_classes > RIO_GP_MAX_CLASSES || !w.cutoffs))
+        return fail(h, RIO_GP_EINVAL, "rio_gp_expire_classes: 1 .. RIO_GP_MAX_CLASSES cutoffs are needed");
+    if (!n_idle) return fail(h, RIO_GP_EINVAL, "rio_gp_expire: n_idle is NULL");
+    if ((rows != nullptr) != (node != nullptr))
+        return fail(h, RIO_GP_EINVAL, "rio_gp_expire: out_rows / out_node are given together or not at all");
+    if (!rows && cap) return fail(h, RIO_GP_EINVAL, "rio_gp_expire: cap without a listing");
+    int rc;
+    ClsCutoffs ct;  // (the class form's: 0 from n_classes on)
+    if ((rc = exp_begin(h, w.classes ? "rio_gp_expire_classes" : "rio_gp_expire"))) return rc;
+    if (w.classes) {
+        if ((rc = cls_begin(h, "rio_gp_expire_classes"))) return rc;
+        std::fill(std::copy(w.cutoffs, w.cutoffs + w.n_classes, ct.v), ct.v + kClsMax, 0u);
+    }
+    const ChgPlan p = chg_plan(h->n);
+    if ((rc = sweep_count(h, p, w, ct))) return rc;
+    u64* const freed = reinterpret_cast<u64*>(h->h_chg) + 1;
+    const bool apply = !to_host && rows && cap && p.G;  // (the host form's apply comes behind the wait)
+    if (!to_host) *freed = 0;
+    if (apply && (rc = sweep_apply(h, p, w, ct, cap, rows, node))) {
+        inputs_changed(h);
+        return rc;
+    }
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    const u64 total = p.G ? *h->h_chg : 0;
+    if (apply && (e != hipSuccess || total)) inputs_changed(h);  // something was un-placed (or nobody can tell)
+    if (e != hipSuccess && w.classes) {
+        if (to_host) return expc_failed(h, "rio_gp_expire_classes: the count pass failed");
+        h->cls_tab_stale = true;
+    }
+    HIPCHK(h, e);
+    *n_idle = total;
+    if (w.classes && w.idle_by_class) std::copy(h->h_cls, h->h_cls + w.n_classes, w.idle_by_class);
+    if (load_freed) *load_freed = apply ? *freed : 0;
+    const u64 L = std::min<u64>(total, cap);
+    if (!to_host || !rows || L == 0) return RIO_GP_OK;  // (a count-only call or no idle row: no inputs_changed)
+    if ((rc = ensure(h, h->chg_stage, 2 * L * sizeof(u32)))) return rc;
+    u32* d = (u32*)h->chg_stage.p;
+    inputs_changed(h);  // from here on it is a rio_gp_remove_batch of the listed rows
+    if ((rc = sweep_apply(h, p, w, ct, L, d, d + L))) return rc;
+    if ((rc = read_listing(h, d, L, L, {rows, node}))) return rc;
+    if (load_freed) *load_freed = *freed;
     return RIO_GP_OK;
 }
 
@@ -2225,49 +2324,14 @@ int rio_gp_expire(rio_gp_t* h, uint32_t cutoff, uint32_t* out_rows, uint32_t* ou
                   uint64_t* load_freed) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    int rc;
-    if ((rc = exp_args(h, out_rows, out_node, cap, n_idle))) return rc;
-    if ((rc = exp_begin(h, "rio_gp_expire"))) return rc;
-    const ChgPlan p = chg_plan(h->n);
-    if ((rc = exp_count(h, p, cutoff))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const u64 total = p.G ? *h->h_chg : 0;
-    *n_idle = total;
-    if (load_freed) *load_freed = 0;
-    const u64 L = std::min<u64>(total, cap);
-    if (!out_rows || L == 0) return RIO_GP_OK;
-    if ((rc = ensure(h, h->chg_stage, 2 * L * sizeof(u32)))) return rc;
-    u32* d = (u32*)h->chg_stage.p;
-    inputs_changed(h);  // from here on it is a rio_gp_remove_batch of the listed rows
-    if ((rc = exp_apply(h, p, cutoff, L, d, d + L))) return rc;
-    if ((rc = read_listing(h, d, L, L, {out_rows, out_node}))) return rc;
-    if (load_freed) *load_freed = reinterpret_cast<const u64*>(h->h_chg)[1];
-    return RIO_GP_OK;
+    return sweep(h, Sweep{false, cutoff, 0, nullptr, nullptr}, true, out_rows, out_node, cap, n_idle, load_freed);
 }
 
 int rio_gp_expire_dev(rio_gp_t* h, uint32_t cutoff, uint32_t* d_rows, uint32_t* d_node, uint64_t cap, uint64_t* n_idle,
                       uint64_t* load_freed) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    int rc;
-    if ((rc = exp_args(h, d_rows, d_node, cap, n_idle))) return rc;
-    if ((rc = exp_begin(h, "rio_gp_expire"))) return rc;
-    const ChgPlan p = chg_plan(h->n);
-    if ((rc = exp_count(h, p, cutoff))) return rc;
-    // the apply pass reads the prefix the count pass left on the device and drops ranks >= cap itself: one wait for the call
-    const bool apply = d_rows && cap && p.G;
-    reinterpret_cast<u64*>(h->h_chg)[1] = 0;
-    if (apply && (rc = exp_apply(h, p, cutoff, cap, d_rows, d_node))) {
-        inputs_changed(h);
-        return rc;
-    }
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    const u64 total = p.G ? *h->h_chg : 0;
-    if (apply && (e != hipSuccess || total)) inputs_changed(h);  // something was un-placed (or nobody can tell)
-    HIPCHK(h, e);
-    *n_idle = total;
-    if (load_freed) *load_freed = apply ? reinterpret_cast<const u64*>(h->h_chg)[1] : 0;
-    return RIO_GP_OK;
+    return sweep(h, Sweep{false, cutoff, 0, nullptr, nullptr}, false, d_rows, d_node, cap, n_idle, load_freed);
 }
 
 // ---- object classes ---------------------------------------------------------------------------
@@ -2329,11 +2393,8 @@ int rio_gp_set_class_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, c
     int rc;
     if ((rc = cls_begin(h, "rio_gp_set_class_batch"))) return rc;
     if (!n) return RIO_GP_OK;
-    if ((rc = zero_stats(h))) return rc;
-    launch_set_class_batch(h->cls_K, h->n, d_idx, d_cls, n, h->pos, h->dstats, h->stream);
-    if ((rc = read_stats(h))) return rc;
-    if (h->h_stats[0].err) return fail(h, RIO_GP_EINVAL, "rio_gp_set_class_batch: invalid entries were skipped");
-    return RIO_GP_OK;
+    return dev_batch(h, "rio_gp_set_class_batch",
+                     [&] { launch_set_class_batch(h->cls_K, h->n, d_idx, d_cls, n, h->pos, h->dstats, h->stream); });
 }
 
 int rio_gp_set_class_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint8_t* cls) {
@@ -2341,19 +2402,11 @@ int rio_gp_set_class_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const u
     Locked g(h);
     if (n >= 0xFFFFFFFFull) return fail(h, RIO_GP_EINVAL, "rio_gp_set_class_batch: too many entries");
     int rc;
-    if ((rc = refuse_row_sharded(h, "rio_gp_set_class_batch"))) return rc;
-    for (uint64_t k = 0; k < n; ++k)
-        if (idx[k] >= h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_set_class_batch: object index out of range");
-    if ((rc = cls_begin(h, "rio_gp_set_class_batch"))) return rc;
-    if (!n) return RIO_GP_OK;
-    if ((rc = ensure(h, h->stage[0], n * sizeof(u32))) || (rc = ensure(h, h->stage[1], n))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, idx, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->stage[1].p, cls, n, hipMemcpyHostToDevice, h->stream));
-    launch_set_class_batch(h->cls_K, h->n, (const u32*)h->stage[0].p, (const unsigned char*)h->stage[1].p, n, h->pos, h->dstats,
+    Staged d;
+    if ((rc = stage_batch(h, "rio_gp_set_class_batch", cls_begin, n, idx, cls, 1, d)) || !n) return rc;
+    launch_set_class_batch(h->cls_K, h->n, d.first, (const unsigned char*)d.second, n, h->pos, h->dstats,
                            h->stream);  // (validated: nothing is counted)
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's arrays are read until here
-    return RIO_GP_OK;
+    return staged_done(h);
 }
 
 int rio_gp_get_classes(rio_gp_t* h, uint64_t n, uint8_t* out) {
@@ -2368,96 +2421,18 @@ int rio_gp_get_classes(rio_gp_t* h, uint64_t n, uint8_t* out) {
     return RIO_GP_OK;
 }
 
-// checks and first-use work shared by both forms of the sweep: nothing is changed before the checks pass; then S and K are on
-// the device and ct holds the cutoffs (0 from n_classes on: a row of such a class is never idle)
-static int expc_begin(rio_gp* h, uint32_t n_classes, const uint32_t* cutoffs, const void* r, const void* o, uint64_t cap,
-                      const uint64_t* n_idle, ClsCutoffs& ct) {
-    if (n_classes < 1 || n_classes > RIO_GP_MAX_CLASSES || !cutoffs)
-        return fail(h, RIO_GP_EINVAL, "rio_gp_expire_classes: 1 .. RIO_GP_MAX_CLASSES cutoffs are needed");
-    int rc;
-    if ((rc = exp_args(h, r, o, cap, n_idle))) return rc;
-    if ((rc = exp_begin(h, "rio_gp_expire_classes")) || (rc = cls_begin(h, "rio_gp_expire_classes"))) return rc;
-    std::fill(std::copy(cutoffs, cutoffs + n_classes, ct.v), ct.v + kClsMax, 0u);
-    return RIO_GP_OK;
-}
-// The copies of the per-class counts are zero between the calls because k_cls_publish, the last launch of the count pass, leaves
-// them so.  A call that cannot tell whether that launch ran (a launch error, a failed wait) has the next call of the section
-// fill them again: a sweep after a failed one must not add to what the failed one left.
-static int expc_failed(rio_gp* h, const char* msg) {
-    h->cls_tab_stale = true;  // (cls_begin zeroes the copies before the next call of the section runs)
-    return fail(h, RIO_GP_EUPSTREAM, msg);
-}
-// The count pass over the committed column, S and K; the total lands in the mapped word, the per-class counts in h->h_cls
-// (mapped too: complete after the next wait).  It changes nothing of the table.
-static int expc_count(rio_gp* h, const ChgPlan& p, const ClsCutoffs& ct) {
-    *h->h_chg = 0;
-    launch_expc_count(h->assign[h->cur], h->exp_S, h->cls_K, p, ct, h->chg_cnt, h->chg_gsum, h->d_chg, h->cls_tab, h->d_cls,
-                      h->exp_freed, h->stream);
-    if (hipGetLastError() != hipSuccess) return expc_failed(h, "rio_gp_expire_classes: a launch of the count pass failed");
-    return RIO_GP_OK;
-}
-// exp_apply with the per-class predicate
-static int expc_apply(rio_gp* h, const ChgPlan& p, const ClsCutoffs& ct, u64 cap, u32* d_rows, u32* d_node) {
-    u64* const used = h->used.live();
-    launch_expc_apply(h->assign[h->cur], h->exp_S, h->cls_K, p, ct, h->chg_cnt, h->chg_gsum, cap, d_rows, d_node, aff_life(h),
-                      h->load, h->m, used, h->exp_freed, h->stream);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(reinterpret_cast<u64*>(h->h_chg) + 1, h->exp_freed, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-    return RIO_GP_OK;
-}
-
 int rio_gp_expire_classes(rio_gp_t* h, uint32_t n_classes, const uint32_t* cutoffs, uint32_t* out_rows, uint32_t* out_node,
                           uint64_t cap, uint64_t* n_idle, uint64_t* load_freed, uint64_t* idle_by_class) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    int rc;
-    ClsCutoffs ct;
-    if ((rc = expc_begin(h, n_classes, cutoffs, out_rows, out_node, cap, n_idle, ct))) return rc;
-    const ChgPlan p = chg_plan(h->n);
-    if ((rc = expc_count(h, p, ct))) return rc;
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return expc_failed(h, "rio_gp_expire_classes: the count pass failed");
-    const u64* const bc = h->h_cls;
-    const u64 total = p.G ? *h->h_chg : 0;
-    *n_idle = total;
-    if (idle_by_class) std::copy(bc, bc + n_classes, idle_by_class);
-    if (load_freed) *load_freed = 0;
-    const u64 L = std::min<u64>(total, cap);
-    if (!out_rows || L == 0) return RIO_GP_OK;
-    if ((rc = ensure(h, h->chg_stage, 2 * L * sizeof(u32)))) return rc;
-    u32* d = (u32*)h->chg_stage.p;
-    inputs_changed(h);  // from here on it is a rio_gp_remove_batch of the listed rows
-    if ((rc = expc_apply(h, p, ct, L, d, d + L))) return rc;
-    if ((rc = read_listing(h, d, L, L, {out_rows, out_node}))) return rc;
-    if (load_freed) *load_freed = reinterpret_cast<const u64*>(h->h_chg)[1];
-    return RIO_GP_OK;
+    return sweep(h, Sweep{true, 0, n_classes, cutoffs, idle_by_class}, true, out_rows, out_node, cap, n_idle, load_freed);
 }
 
 int rio_gp_expire_classes_dev(rio_gp_t* h, uint32_t n_classes, const uint32_t* cutoffs, uint32_t* d_rows, uint32_t* d_node,
                               uint64_t cap, uint64_t* n_idle, uint64_t* load_freed, uint64_t* idle_by_class) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    int rc;
-    ClsCutoffs ct;
-    if ((rc = expc_begin(h, n_classes, cutoffs, d_rows, d_node, cap, n_idle, ct))) return rc;
-    const ChgPlan p = chg_plan(h->n);
-    if ((rc = expc_count(h, p, ct))) return rc;
-    const u64* const bc = h->h_cls;
-    // the apply pass reads the prefix the count pass left on the device and drops ranks >= cap itself: one wait for the call
-    const bool apply = d_rows && cap && p.G;
-    reinterpret_cast<u64*>(h->h_chg)[1] = 0;
-    if (apply && (rc = expc_apply(h, p, ct, cap, d_rows, d_node))) {
-        inputs_changed(h);
-        return rc;
-    }
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    const u64 total = p.G ? *h->h_chg : 0;
-    if (apply && (e != hipSuccess || total)) inputs_changed(h);  // something was un-placed (or nobody can tell)
-    if (e != hipSuccess) h->cls_tab_stale = true;
-    HIPCHK(h, e);
-    *n_idle = total;
-    if (idle_by_class) std::copy(bc, bc + n_classes, idle_by_class);
-    if (load_freed) *load_freed = apply ? reinterpret_cast<const u64*>(h->h_chg)[1] : 0;
-    return RIO_GP_OK;
+    return sweep(h, Sweep{true, 0, n_classes, cutoffs, idle_by_class}, false, d_rows, d_node, cap, n_idle, load_freed);
 }
 
 // Read-only, like rio_gp_count_placed: the committed column, K and load; no inputs_changed.
@@ -2523,30 +2498,17 @@ int rio_gp_hits_add_batch_dev(rio_gp_t* h, uint64_t n, const uint32_t* d_idx, co
     int rc;
     if ((rc = hits_begin(h, "rio_gp_hits_add_batch"))) return rc;
     if (!n) return RIO_GP_OK;
-    if ((rc = zero_stats(h))) return rc;
-    launch_hits_add(h->hits_H, h->n, d_idx, d_weight, n, h->dstats, h->stream);
-    if ((rc = read_stats(h))) return rc;
-    if (h->h_stats[0].err) return fail(h, RIO_GP_EINVAL, "rio_gp_hits_add_batch: invalid entries were skipped");
-    return RIO_GP_OK;
+    return dev_batch(h, "rio_gp_hits_add_batch", [&] { launch_hits_add(h->hits_H, h->n, d_idx, d_weight, n, h->dstats, h->stream); });
 }
 
 int rio_gp_hits_add_batch(rio_gp_t* h, uint64_t n, const uint32_t* idx, const uint32_t* weight) {
     if (!h || (n && !idx)) return RIO_GP_EINVAL;
     Locked g(h);
     int rc;
-    if ((rc = hits_begin(h, "rio_gp_hits_add_batch"))) return rc;
-    for (uint64_t k = 0; k < n; ++k)
-        if (idx[k] >= h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_hits_add_batch: object index out of range");
-    if (!n) return RIO_GP_OK;
-    for (int q = 0; q < (weight ? 2 : 1); ++q)
-        if ((rc = ensure(h, h->stage[q], n * sizeof(u32)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, idx, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-    if (weight) HIPCHK(h, hipMemcpyAsync(h->stage[1].p, weight, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-    launch_hits_add(h->hits_H, h->n, (const u32*)h->stage[0].p, weight ? (const u32*)h->stage[1].p : nullptr, n, h->dstats,
-                    h->stream);  // (validated: nothing is counted)
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's arrays are read until here
-    return RIO_GP_OK;
+    Staged d;
+    if ((rc = stage_batch(h, "rio_gp_hits_add_batch", hits_begin, n, idx, weight, sizeof(u32), d)) || !n) return rc;
+    launch_hits_add(h->hits_H, h->n, d.first, (const u32*)d.second, n, h->dstats, h->stream);  // (validated: nothing is counted)
+    return staged_done(h);
 }
 
 int rio_gp_hits_merge_dev(rio_gp_t* h, uint64_t rows, const uint32_t* d_counts) {
@@ -2566,13 +2528,10 @@ int rio_gp_hits_merge(rio_gp_t* h, uint64_t rows, const uint32_t* counts) {
     int rc;
     if ((rc = hits_begin(h, "rio_gp_hits_merge"))) return rc;
     if (rows > h->n) return fail(h, RIO_GP_EINVAL, "rio_gp_hits_merge: rows exceeds the object table");
-    if (!rows) return RIO_GP_OK;
-    if ((rc = ensure(h, h->stage[0], rows * sizeof(u32)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->stage[0].p, counts, rows * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-    launch_hits_merge(h->hits_H, (const u32*)h->stage[0].p, rows, h->stream);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's array is read until here
-    return RIO_GP_OK;
+    Staged d;
+    if ((rc = stage_batch(h, "rio_gp_hits_merge", nullptr, rows, counts, nullptr, 0, d)) || !rows) return rc;
+    launch_hits_merge(h->hits_H, d.first, rows, h->stream);
+    return staged_done(h);
 }
 
 int rio_gp_get_hits(rio_gp_t* h, uint64_t n, uint32_t* out) {

@@ -10,6 +10,7 @@ before each run, not timed; S is never changed by an expiry).  S is laid out by 
   idle_10pct_cap_1e4    the same with cap = 10^4: the apply pass ends after the first workgroups
   idle_10pct_host       the host-pointer form: a wait after the count, the listing staged and copied out
   touch_batch_dev_1e6   10^6 random rows, rising epochs (every entry an atomic maximum)
+  touch_batch_host_16 / _1e5   rio_gp_touch_batch from a host array: the index check, the staging copy, the scatter, one wait
   touch_all             every row, rising epochs (4 B read + 4 B written per row), timed with the stream wait behind it
   host_route            what a host does without the calls: rio_gp_get_assign, a numpy pass over the column and its own stamps,
                         rio_gp_remove_batch of the idle rows (10 %)
@@ -94,6 +95,14 @@ def main(reps):
         g.touch_dev(idx.data_ptr(), 1_000_000, 10 + k)
         ts.append(time.perf_counter() - t0)
     out["touch_batch_dev_1e6"] = stat(ts[1:])
+    for name, cnt in (("touch_batch_host_16", 16), ("touch_batch_host_1e5", 100_000)):
+        hidx = rng.integers(0, n, cnt).astype(np.uint32)
+        ts = []
+        for k in range(reps + 1):
+            t0 = time.perf_counter()
+            g.touch(hidx, 50 + k)
+            ts.append(time.perf_counter() - t0)
+        out[name] = stat(ts[1:])
     ts = []
     for k in range(reps + 1):
         t0 = time.perf_counter()
