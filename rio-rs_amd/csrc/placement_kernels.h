@@ -449,8 +449,9 @@ void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n,
 // thr (m u32, or nullptr = row order) in the four launches below: the load-ordered cut's threshold per node (kNone on a node
 // that is not over).  With it the cut walks only the candidates whose load == thr[node] — slot_free is then what
 // launch_shed_select left — and a candidate is surplus iff load > thr[node] || (load == thr[node] && row >= cut[node]).
+// fill_cut: cut starts as kNone on every node (false: k_shrb_import_x / k_shrb_import_slots wrote it).  No slot or no row: no pass.
 void launch_shed_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
-                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, hipStream_t s);
+                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, bool fill_cut, hipStream_t s);
 // tcnt: nt u32 -> the exclusive scan of the per-tile surplus counts; acc[kShAccSurplusRows / SurplusLoad]
 void launch_shed_count(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* thr,
                        u32* tcnt, u64* acc, hipStream_t s);
@@ -500,9 +501,6 @@ struct ShrbImport {
 // X = pin | used - pin | 8 words: *maxl (nullptr: 0), five zeros, 1 (as in the solve's record)
 void launch_shrb_export_x(const u64* used, const u64* pin, u32 m, const u32* maxl, u64* X, hipStream_t s);
 void launch_shrb_import_x(const ShrbImport& a, hipStream_t s);
-// launch_shed_cut without resetting `cut` (k_shrb_import_x / k_shrb_import_slots wrote it); thr as in launch_shed_cut
-void launch_shrb_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
-                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, hipStream_t s);
 // The load-ordered cut, sharded (kernels: k_shrb_import_slots, k_shed_sel_hist, k_shrb_sel_pick).  The slots are the globally
 // over nodes in ascending node order, the same on every rank; the plan depends on (S, m) alone and its histogram record,
 // S << bits u64, is never longer than an X record (shard_words1(m)): the digit is narrowed until it fits.
@@ -516,7 +514,7 @@ void launch_shrb_import_slots(const ShrbImport& a, u32* pre, u32* thr, hipStream
 void launch_shrb_sel_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u32 S, const u32* map, const u32* pre,
                           const ShSelPlan& q, u32 pass, u64* H, hipStream_t s);
 // Hg[R][S << bits] gathered -> the digit of every slot: pre, slot_free as launch_shed_select's passes leave them.  The last pass
-// sets thr[slot_node] and turns slot_free into the load of the ties THIS rank keeps (launch_shrb_cut with thr places the cut).
+// sets thr[slot_node] and turns slot_free into the load of the ties THIS rank keeps (launch_shed_cut with thr places the cut).
 void launch_shrb_sel_pick(const u64* Hg, u32 rank, u32 R, u32 S, const ShSelPlan& q, u32 pass, const u32* slot_node,
                           u64* slot_free, u32* pre, u32* thr, hipStream_t s);
 // Y = v[m] | *a | b

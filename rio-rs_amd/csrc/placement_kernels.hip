@@ -6803,8 +6803,9 @@ void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n,
     else hipLaunchKernelGGL((k_shed_hist<false>), grid, block, lds, s, assign, load, aff, n, m, used, pin, maxl);
 }
 void launch_shed_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
-                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, hipStream_t s) {
-    launch_fill_u32(cut, p.m, kNone, s);
+                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, bool fill_cut, hipStream_t s) {
+    if (fill_cut) launch_fill_u32(cut, p.m, kNone, s);
+    if (!p.s || !p.n) return;
     hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), shed_tile_lds(p, thr), s, assign, load, aff, p, map, thr, mat);
     hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, thr, cut);
 }
@@ -6819,12 +6820,19 @@ void launch_shed_pack(const u32* assign, const u32* load, const u32* aff, const 
     hipLaunchKernelGGL(k_shed_pack, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32) * (thr ? 2 : 1), s, assign, load, aff, p,
                        cut, thr, toff, budget, pk_row, pk_load, pk_node, used, acc);
 }
-void launch_shed_round(u64 K, const u32* pk_load, u32* pk_node, const u64* tgt, u32 m, u64* used, u64* csum, u64* C, u32* ord,
-                       u32* cntp, hipStream_t s) {
+// What a round of either form starts with: the prefix of the pending rows' loads per chunk (from *base; nullptr: from 0) and the
+// nodes in the order of their free load.  Returns the chunks, the grid of the form's own fill kernel.
+static u32 shed_round_head(u64 K, const u32* pk_load, const u32* pk_node, const u64* tgt, u32 m, const u64* used, const u64* base,
+                           u64* csum, u64* C, u32* ord, u32* cntp, hipStream_t s) {
     const u32 nc = (u32)((K + kShChunk - 1) / kShChunk);
     hipLaunchKernelGGL(k_shed_csum, dim3(nc), dim3(kBlock), 0, s, K, pk_load, pk_node, csum);
-    hipLaunchKernelGGL((k_shed_scan<u64>), dim3(1), dim3(kBlock), 0, s, csum, csum, (u64)nc, nullptr, (const u64*)nullptr);
+    hipLaunchKernelGGL((k_shed_scan<u64>), dim3(1), dim3(kBlock), 0, s, csum, csum, (u64)nc, (u64*)nullptr, base);
     hipLaunchKernelGGL(k_shed_order, dim3(1), dim3(kBlock), shed_order_lds(m), s, tgt, used, m, C, ord, cntp);
+    return nc;
+}
+void launch_shed_round(u64 K, const u32* pk_load, u32* pk_node, const u64* tgt, u32 m, u64* used, u64* csum, u64* C, u32* ord,
+                       u32* cntp, hipStream_t s) {
+    const u32 nc = shed_round_head(K, pk_load, pk_node, tgt, m, used, nullptr, csum, C, ord, cntp, s);
     hipLaunchKernelGGL(k_shed_fill, dim3(nc), dim3(kBlock), 0, s, K, pk_load, pk_node, csum, C, ord, cntp, used);
 }
 void launch_shed_finish(u64 K, const u32* pk_row, const u32* pk_load, const u32* pk_node, u32* assign, u64* used, u32* mc,
@@ -6997,12 +7005,6 @@ void launch_shrb_export_x(const u64* used, const u64* pin, u32 m, const u32* max
 void launch_shrb_import_x(const ShrbImport& a, hipStream_t s) {
     hipLaunchKernelGGL(k_shrb_import_x, dim3(1), dim3(kBlock), 0, s, a);
 }
-void launch_shrb_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
-                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, hipStream_t s) {
-    if (!p.s || !p.n) return;
-    hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), shed_tile_lds(p, thr), s, assign, load, aff, p, map, thr, mat);
-    hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, thr, cut);
-}
 void launch_shrb_export_y(const u64* v, u32 m, const u64* a, u64 b, u64* Y, hipStream_t s) {
     hipLaunchKernelGGL(k_shrb_export_y, dim3(1), dim3(kBlock), 0, s, v, m, a, b, Y);
 }
@@ -7013,10 +7015,7 @@ void launch_shrb_round(u64 K, const u32* pk_row, const u32* pk_load, u32* pk_nod
                        const u64* used, const u64* base, bool last, u64* csum, u64* C, u32* ord, u32* cntp, u64* Y, hipStream_t s) {
     (void)hipMemsetAsync(Y, 0, ((size_t)m + 2) * sizeof(u64), s);
     if (!K) return;
-    const u32 nc = (u32)((K + kShChunk - 1) / kShChunk);
-    hipLaunchKernelGGL(k_shed_csum, dim3(nc), dim3(kBlock), 0, s, K, pk_load, pk_node, csum);
-    hipLaunchKernelGGL((k_shed_scan<u64>), dim3(1), dim3(kBlock), 0, s, csum, csum, (u64)nc, (u64*)nullptr, base);
-    hipLaunchKernelGGL(k_shed_order, dim3(1), dim3(kBlock), shed_order_lds(m), s, tgt, used, m, C, ord, cntp);
+    const u32 nc = shed_round_head(K, pk_load, pk_node, tgt, m, used, base, csum, C, ord, cntp, s);
     hipLaunchKernelGGL(k_shrb_fill, dim3(nc), dim3(kBlock), 0, s, K, pk_row, pk_load, pk_node, assign, csum, C, ord, cntp, last, m, Y);
 }
 

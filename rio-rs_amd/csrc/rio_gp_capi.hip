@@ -1856,58 +1856,169 @@ static const char* rebalance_cfg_order(const rio_gp_rebalance_cfg* cfg, u32* ord
     return nullptr;
 }
 
-// R1' (RIO_GP_REBALANCE_BY_LOAD): thr[j] of the S over nodes; slot_free becomes what is left for the candidates of that load
-static int rebalance_select(rio_gp* h, u32 S, const u32* map, const u32* slot_node, u64* slot_free, u32* pre, u32* thr) {
-    const ShSelPlan q = sh_sel_plan(S);
+// rio_gp_rebalance[_dev] (rebalance_locked) and the rio_gp_shard_rebalance_* session sequence the same phases, each written
+// once: rb_cfg (the cfg checks; rounds and budget), rb_surplus (R1: the cuts and the surplus per tile), rb_pack (R2, into an
+// RbPacked), rb_finish (R4, the column, the moves, the read-back, the stats).  R0 and a round of R3 are one launcher call each.
+
+// The node scratch of both forms: the only carving of h->sh_nodes.  Every array is rewritten by the call or session that reads
+// it, so the two forms may alternate on one handle.  lu, tdev, base, live, info and maxl are the session's alone: the single
+// form keeps its `used` in h->used.storage() and decides on the host what k_shrb_import_* decides from the others.
+namespace {
+struct RbBufs {
+    u64 *pin, *tgt, *slot_free, *C, *acc, *lu, *tdev, *base;
+    u32 *map, *slot_node, *cut, *ord, *cntp, *live, *info, *maxl, *thr, *pre;
+};
+constexpr int kRbPend = 6;  // acc[6], acc[7]: rows / load pending on all ranks (k_shrb_merge)
+RbBufs rb_bufs(rio_gp* h) {
+    const size_t M = h->cap_nodes;
+    RbBufs b;
+    b.pin = (u64*)h->sh_nodes.p;
+    b.tgt = b.pin + M;  // (0 on dead nodes)
+    b.slot_free = b.tgt + M;
+    b.C = b.slot_free + M;
+    b.acc = b.C + M + 1;
+    b.lu = b.acc + kShAcc;
+    b.tdev = b.lu + M;
+    b.base = b.tdev + M;
+    b.map = (u32*)(b.base + 1);
+    b.slot_node = b.map + M;
+    b.cut = b.slot_node + M;
+    b.ord = b.cut + M;
+    b.cntp = b.ord + M;
+    b.live = b.cntp + 4;
+    b.info = b.live + M;
+    // the load-ordered cut: info has one more word (kShrbMaxLoad); this rank's largest load, the threshold per node, the digits
+    // chosen so far per slot
+    b.maxl = b.info + kShrbInfo + 1;
+    b.thr = b.maxl + 1;
+    b.pre = b.thr + M;
+    return b;
+}
+int rb_ensure(rio_gp* h) {
+    const size_t M = h->cap_nodes;
+    return ensure(h, h->sh_nodes, (6 * M + 2 + kShAcc) * sizeof(u64) + (7 * M + 4 + kShrbInfo + 2) * sizeof(u32));
+}
+// the K packed rows of a call or session (h->sh_pk as rb_pack sized it): row | load | node
+struct RbPacked { u32 *row, *load, *node; };
+RbPacked rb_packed(rio_gp* h, u64 K) {
+    u32* const row = (u32*)h->sh_pk.p;
+    return {row, row + K, row + 2 * K};
+}
+}  // namespace
+
+// What both forms ask of a cfg; `who` keeps every message's text.  own: the calling form's complaint about its other arguments
+// (or NULL), reported where that form always reported it.  listing: the moves are listed, into at most `cap` entries.
+enum class RbForm { single, shard, shard_ordered };
+struct RbCfg { u32 order, rounds; u64 budget; };
+static int rb_cfg(rio_gp* h, const char* who, RbForm form, const rio_gp_rebalance_cfg* cfg, const char* own, bool listing, u64 cap,
+                  RbCfg* c) {
+    const std::string me = std::string(who) + ": ";
+    if (const char* why = rebalance_cfg_order(cfg, &c->order))
+        return fail(h, RIO_GP_EINVAL, me + (form == RbForm::single ? why : "cfg missing or struct_size differs"));
+    if (c->order != RIO_GP_REBALANCE_ROW_ORDER && form == RbForm::shard)
+        return fail(h, RIO_GP_EINVAL, me + "the load-ordered cut (order = RIO_GP_REBALANCE_BY_LOAD) of a row-sharded table has "
+                                           "threshold passes between cut and select: start it with "
+                                           "rio_gp_shard_rebalance_begin_ordered");
+    if (cfg->rounds > 8) return fail(h, RIO_GP_EINVAL, me + "rounds above the solver limit (8)");
+    if (own) return fail(h, RIO_GP_EINVAL, me + own);
+    if (!listing && cap) return fail(h, RIO_GP_EINVAL, me + "moves_cap without a move listing");
+    c->rounds = cfg->rounds ? cfg->rounds : h->rounds;
+    c->budget = listing ? std::min<u64>(cfg->max_moves, cap) : cfg->max_moves;
+    return RIO_GP_OK;
+}
+
+// the (slot x tile) matrix and the per-tile counts of a plan (a plan without slots still has one row: a forced pass)
+static int rb_plan_ensure(rio_gp* h, const ShPlan& p) {
+    if (int rc = ensure(h, h->sh_mat, (size_t)std::max<u32>(p.s, 1) * p.nt * sizeof(u64))) return rc;
+    return ensure(h, h->sh_tile, (size_t)p.nt * sizeof(u32));
+}
+
+// R1 behind map / slot_node / slot_free (and, by load, thr): the cut of every slot, the surplus per tile, acc's two surplus
+// words.  fill_cut: cut[] starts as kNone everywhere (the single form; in the session k_shrb_import_* wrote it).
+static int rb_surplus(rio_gp* h, const ShPlan& p, const RbBufs& b, const u32* thr, bool fill_cut) {
+    if (int rc = rb_plan_ensure(h, p)) return rc;
+    launch_shed_cut(h->assign[h->cur], h->load, h->aff, p, b.map, b.slot_node, b.slot_free, (u64*)h->sh_mat.p, b.cut, thr, fill_cut,
+                    h->stream);
+    launch_shed_count(h->assign[h->cur], h->load, h->aff, p, b.cut, thr, (u32*)h->sh_tile.p, b.acc, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return RIO_GP_OK;
+}
+
+// R2: the first K > 0 surplus rows into the packed columns, in row order; used[] -= their load, acc[kShAccSelectedLoad]
+static int rb_pack(rio_gp* h, const ShPlan& p, const RbBufs& b, const u32* thr, u64 K, u64* used) {
+    const u64 nc = (K + kShChunk - 1) / kShChunk;
     int rc;
-    if ((rc = ensure(h, h->sh_sel, ((size_t)S << q.bits) * sizeof(u64)))) return rc;
-    launch_shed_select(h->assign[h->cur], h->load, h->aff, h->n, h->m, S, map, slot_node, slot_free, pre, (u64*)h->sh_sel.p, thr,
-                       h->stream);
+    if ((rc = ensure(h, h->sh_pk, 3 * K * sizeof(u32))) || (rc = ensure(h, h->sh_chunk, nc * sizeof(u64)))) return rc;
+    const RbPacked pk = rb_packed(h, K);
+    launch_shed_pack(h->assign[h->cur], h->load, h->aff, p, b.cut, thr, (const u32*)h->sh_tile.p, K, pk.row, pk.load, pk.node, used,
+                     b.acc, h->stream);
+    return RIO_GP_OK;
+}
+
+// acc as the passes so far left it -> the counters of the stats; moved_* and stayed_rows only behind a finish pass that ran
+static void rb_counters(const u64* a, bool finished, rio_gp_rebalance_stats* s) {
+    s->surplus_rows = a[kShAccSurplusRows];
+    s->surplus_load = a[kShAccSurplusLoad];
+    s->selected_load = a[kShAccSelectedLoad];
+    if (!finished) return;
+    s->moved_rows = a[kShAccMovedRows];
+    s->moved_load = a[kShAccMovedLoad];
+    s->stayed_rows = a[kShAccStayed];
+}
+
+// R4 + the column + the moves of the K packed rows (K == 0: nothing to launch), then acc and the global `used` behind one wait:
+// the counters of *s and nodes_over_after against the targets T.  own_used: where the rows left without a node give their load
+// back, the vector rb_pack took it from; what is read back is h->used.storage(), the same vector in the single form, the sum
+// over the ranks in the session.  d_rows / d_from / d_to: K entries each, or NULL.
+static int rb_finish(rio_gp* h, const RbBufs& b, u64 K, u64* own_used, const u64* T, u32* d_rows, u32* d_from, u32* d_to,
+                     rio_gp_rebalance_stats* s) {
+    const u32 m = h->m;
+    if (K) {
+        const RbPacked pk = rb_packed(h, K);
+        launch_shed_finish(K, pk.row, pk.load, pk.node, h->assign[h->cur], own_used, (u32*)h->sh_chunk.p, b.acc, d_rows, d_from, d_to,
+                           h->stream);
+        HIPCHK(h, hipGetLastError());
+    }
+    u64 a[kShAcc];
+    std::vector<u64> used(m ? m : 1);
+    HIPCHK(h, hipMemcpyAsync(a, b.acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
+    if (m) HIPCHK(h, hipMemcpyAsync(used.data(), h->used.storage(), (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    rb_counters(a, K != 0, s);
+    s->nodes_over_after = 0;
+    for (u32 j = 0; j < m; ++j) s->nodes_over_after += h->h_alive[j] && used[j] > T[j];
     return RIO_GP_OK;
 }
 
 // The device-side work of rio_gp_rebalance[_dev] (validated, locked).  d_rows / d_from / d_to: device arrays of at least
-// `budget` entries, or all NULL.
-static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 order, u32 rounds, u64 budget,
-                            rio_gp_rebalance_stats* st, u32* d_rows, u32* d_from, u32* d_to, uint64_t* n_moves) {
+// `budget` entries, or all NULL.  Three host waits at the most, each the end of a phase: R0 (`used` and pin, from which the
+// host picks the slots), rb_surplus (acc: K), rb_finish.  The session of the row-sharded table (further down) ends the same
+// phases where its records leave for the other ranks.
+static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, const RbCfg& c, rio_gp_rebalance_stats* st, u32* d_rows,
+                            u32* d_from, u32* d_to, uint64_t* n_moves) {
     rio_gp_rebalance_stats s{};
     if (n_moves) *n_moves = 0;
     HIPCHK(h, hipSetDevice(h->device));
     // a change of the inputs, like every CRUD call: an uncommitted solve is dropped, the next tick is neither quiet nor chained
     inputs_changed(h);
-    const u32 m = h->m, M = h->cap_nodes;
+    const u32 m = h->m;
     const u64 n = h->n;
-    // per-node arrays: pin | tgt (0 on dead nodes) | slot_free | C [M + 1] | acc [kShAcc] (u64), then map | slot_node | cut |
-    // ord | thr | pre | cnt (u32)
     int rc;
-    const size_t u64s = 4 * (size_t)M + 1 + kShAcc, u32s = 6 * (size_t)M + 4;
-    if ((rc = ensure(h, h->sh_nodes, u64s * sizeof(u64) + u32s * sizeof(u32)))) return rc;
-    u64* pin = (u64*)h->sh_nodes.p;
-    u64* tgt = pin + M;
-    u64* slot_free = tgt + M;
-    u64* C = slot_free + M;
-    u64* acc = C + M + 1;
-    u32* map = (u32*)(acc + kShAcc);
-    u32* slot_node = map + M;
-    u32* cut = slot_node + M;
-    u32* ord = cut + M;
-    u32* thr_buf = ord + M;
-    u32* pre = thr_buf + M;
-    u32* cntp = pre + M;
-    const bool by_load = order == RIO_GP_REBALANCE_BY_LOAD;
-    const u32* const thr = by_load ? thr_buf : nullptr;  // (nullptr: the k_shed_* kernels cut in row order)
+    if ((rc = rb_ensure(h))) return rc;
+    const RbBufs b = rb_bufs(h);
+    const u32* const thr = c.order == RIO_GP_REBALANCE_BY_LOAD ? b.thr : nullptr;  // (nullptr: the k_shed_* kernels cut in row order)
     // the targets (the capacities by default) and the live nodes
     std::vector<u64> T(m ? m : 1), used(m ? m : 1), pn(m ? m : 1);
     if (cfg->target) memcpy(T.data(), cfg->target, (size_t)m * sizeof(u64));
     else if (m) HIPCHK(h, hipMemcpyAsync(T.data(), h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     // R0: one pass — every node's load (the `used` vector of this column, rebuilt: nothing left to fold) and its pinned load
     u64* const d_used = h->used.storage();
-    launch_shed_hist(h->assign[h->cur], h->load, h->aff, n, m, d_used, pin, h->stream);
+    launch_shed_hist(h->assign[h->cur], h->load, h->aff, n, m, d_used, b.pin, h->stream);
     HIPCHK(h, hipGetLastError());
     h->used.rebuilt();
     if (m) {
         HIPCHK(h, hipMemcpyAsync(used.data(), d_used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(pn.data(), pin, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(pn.data(), b.pin, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     // R1 on the host's side: which live nodes hold more candidate load than T -sat pinned
@@ -1921,111 +2032,71 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, u32 orde
         if (cand > fr) { hmap[j] = (u32)snode.size(); snode.push_back(j); sfree.push_back(fr); }
     }
     const u32 S = (u32)snode.size();
-    if (S == 0 || budget == 0) {  // nothing over target (or nothing may move): one pass, nothing changed
-        if (S) {  // (budget 0: the surplus is still counted)
-            const ShPlan p = sh_plan(n, m, S);
-            if ((rc = ensure(h, h->sh_mat, (size_t)S * p.nt * sizeof(u64))) || (rc = ensure(h, h->sh_tile, (size_t)p.nt * sizeof(u32))))
-                return rc;
-            HIPCHK(h, hipMemcpyAsync(map, hmap.data(), (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(slot_node, snode.data(), (size_t)S * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(slot_free, sfree.data(), (size_t)S * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemsetAsync(acc, 0, kShAcc * sizeof(u64), h->stream));
-            if (by_load && (rc = rebalance_select(h, S, map, slot_node, slot_free, pre, thr_buf))) return rc;
-            launch_shed_cut(h->assign[h->cur], h->load, h->aff, p, map, slot_node, slot_free, (u64*)h->sh_mat.p, cut, thr, h->stream);
-            launch_shed_count(h->assign[h->cur], h->load, h->aff, p, cut, thr, (u32*)h->sh_tile.p, acc, h->stream);
-            HIPCHK(h, hipGetLastError());
-            u64 a[kShAcc];
-            HIPCHK(h, hipMemcpyAsync(a, acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            s.surplus_rows = a[kShAccSurplusRows];
-            s.surplus_load = a[kShAccSurplusLoad];
+    const ShPlan p = sh_plan(n, m, S);
+    if (S) {
+        // R1 on the device: the exact cut of every over node; the surplus per tile (counted under a budget of 0 too; the
+        // targets are for the rounds)
+        HIPCHK(h, hipMemcpyAsync(b.map, hmap.data(), (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(b.slot_node, snode.data(), (size_t)S * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(b.slot_free, sfree.data(), (size_t)S * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+        if (c.budget) HIPCHK(h, hipMemcpyAsync(b.tgt, tl.data(), (size_t)m * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemsetAsync(b.acc, 0, kShAcc * sizeof(u64), h->stream));
+        if (thr) {  // R1' first finds every over node's threshold (slot_free: what is left for the candidates of exactly that
+                    // load): the cut below then falls among those
+            if ((rc = ensure(h, h->sh_sel, ((size_t)S << sh_sel_plan(S).bits) * sizeof(u64)))) return rc;
+            launch_shed_select(h->assign[h->cur], h->load, h->aff, n, m, S, b.map, b.slot_node, b.slot_free, b.pre, (u64*)h->sh_sel.p,
+                               b.thr, h->stream);
         }
+        if ((rc = rb_surplus(h, p, b, thr, true))) return rc;
+        u64 a[kShAcc];
+        HIPCHK(h, hipMemcpyAsync(a, b.acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        rb_counters(a, false, &s);
+    }
+    const u64 K = std::min<u64>(s.surplus_rows, c.budget);
+    s.selected_rows = K;
+    if (!K) {  // nothing over target, or nothing may move: nothing changed, and `used` is R0's
         s.nodes_over_after = s.nodes_over_before;
         if (st) *st = s;
         return RIO_GP_OK;
     }
-    // R1 on the device: the exact cut of every over node; the surplus per tile
-    const ShPlan p = sh_plan(n, m, S);
-    if ((rc = ensure(h, h->sh_mat, (size_t)S * p.nt * sizeof(u64))) || (rc = ensure(h, h->sh_tile, (size_t)p.nt * sizeof(u32))))
-        return rc;
-    HIPCHK(h, hipMemcpyAsync(map, hmap.data(), (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(slot_node, snode.data(), (size_t)S * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(slot_free, sfree.data(), (size_t)S * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(tgt, tl.data(), (size_t)m * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(acc, 0, kShAcc * sizeof(u64), h->stream));
-    // R1' first finds every over node's threshold: the cut below then falls among the candidates of exactly that load
-    if (by_load && (rc = rebalance_select(h, S, map, slot_node, slot_free, pre, thr_buf))) return rc;
-    launch_shed_cut(h->assign[h->cur], h->load, h->aff, p, map, slot_node, slot_free, (u64*)h->sh_mat.p, cut, thr, h->stream);
-    launch_shed_count(h->assign[h->cur], h->load, h->aff, p, cut, thr, (u32*)h->sh_tile.p, acc, h->stream);
-    HIPCHK(h, hipGetLastError());
-    u64 a[kShAcc];
-    HIPCHK(h, hipMemcpyAsync(a, acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    s.surplus_rows = a[kShAccSurplusRows];
-    s.surplus_load = a[kShAccSurplusLoad];
-    const u64 K = std::min<u64>(s.surplus_rows, budget);
-    s.selected_rows = K;
-    if (K) {
-        // R2: the first K surplus rows, packed in row order; R3: the water-fill rounds; R4 + the column + the moves
-        const u64 nc = (K + kShChunk - 1) / kShChunk;
-        if ((rc = ensure(h, h->sh_pk, 3 * K * sizeof(u32))) || (rc = ensure(h, h->sh_chunk, nc * sizeof(u64)))) return rc;
-        u32* pk_row = (u32*)h->sh_pk.p;
-        u32* pk_load = pk_row + K;
-        u32* pk_node = pk_load + K;
-        launch_shed_pack(h->assign[h->cur], h->load, h->aff, p, cut, thr, (const u32*)h->sh_tile.p, K, pk_row, pk_load, pk_node,
-                         d_used, acc, h->stream);
-        for (u32 r = 0; r < rounds; ++r)
-            launch_shed_round(K, pk_load, pk_node, tgt, m, d_used, (u64*)h->sh_chunk.p, C, ord, cntp, h->stream);
-        launch_shed_finish(K, pk_row, pk_load, pk_node, h->assign[h->cur], d_used, (u32*)h->sh_chunk.p, acc, d_rows, d_from, d_to,
-                           h->stream);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(a, acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(used.data(), d_used, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        s.selected_load = a[kShAccSelectedLoad];
-        s.moved_rows = a[kShAccMovedRows];
-        s.moved_load = a[kShAccMovedLoad];
-        s.stayed_rows = a[kShAccStayed];
-    }
-    for (u32 j = 0; j < m; ++j) s.nodes_over_after += h->h_alive[j] && used[j] > T[j];
+    // R2: the first K surplus rows, packed in row order; R3: the water-fill rounds; R4 + the column + the moves
+    if ((rc = rb_pack(h, p, b, thr, K, d_used))) return rc;
+    const RbPacked pk = rb_packed(h, K);
+    for (u32 r = 0; r < c.rounds; ++r)
+        launch_shed_round(K, pk.load, pk.node, b.tgt, m, d_used, (u64*)h->sh_chunk.p, b.C, b.ord, b.cntp, h->stream);
+    if ((rc = rb_finish(h, b, K, d_used, T.data(), d_rows, d_from, d_to, &s))) return rc;
     if (n_moves) *n_moves = s.moved_rows;
     if (st) *st = s;
     return RIO_GP_OK;
 }
 
-// checks shared by both forms: nothing is changed before they pass
+// the checks of both entry points: nothing is changed before they pass
 static int rebalance_args(rio_gp* h, const rio_gp_rebalance_cfg* cfg, const void* r, const void* f, const void* t, uint64_t cap,
-                          u32* order, u32* rounds, u64* budget) {
-    if (const char* why = rebalance_cfg_order(cfg, order)) return fail(h, RIO_GP_EINVAL, std::string("rio_gp_rebalance: ") + why);
-    if (cfg->rounds > 8) return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: rounds above the solver limit (8)");
-    if ((r != nullptr) != (f != nullptr) || (r != nullptr) != (t != nullptr))
-        return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: out_rows / out_from / out_to are given together or not at all");
-    if (!r && cap) return fail(h, RIO_GP_EINVAL, "rio_gp_rebalance: moves_cap without a move listing");
-    if (int rc = refuse_row_sharded(h, "rio_gp_rebalance")) return rc;
-    *rounds = cfg->rounds ? cfg->rounds : h->rounds;
-    *budget = r ? std::min<u64>(cfg->max_moves, cap) : cfg->max_moves;
-    return RIO_GP_OK;
+                          RbCfg* c) {
+    const bool together = (r != nullptr) == (f != nullptr) && (r != nullptr) == (t != nullptr);
+    const char* own = together ? nullptr : "out_rows / out_from / out_to are given together or not at all";
+    if (int rc = rb_cfg(h, "rio_gp_rebalance", RbForm::single, cfg, own, r != nullptr, cap, c)) return rc;
+    return refuse_row_sharded(h, "rio_gp_rebalance");
 }
 
 int rio_gp_rebalance(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_rebalance_stats* st, uint32_t* out_rows,
                      uint32_t* out_from, uint32_t* out_to, uint64_t moves_cap, uint64_t* n_moves) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    u32 order, rounds;
-    u64 budget;
+    RbCfg c;
     int rc;
-    if ((rc = rebalance_args(h, cfg, out_rows, out_from, out_to, moves_cap, &order, &rounds, &budget))) return rc;
+    if ((rc = rebalance_args(h, cfg, out_rows, out_from, out_to, moves_cap, &c))) return rc;
     // the listing is staged on the device (moves <= selected <= budget <= min(n, moves_cap))
     u32* d = nullptr;
     u64 stage = 0;
     if (out_rows) {
-        stage = std::min<u64>(budget, h->n);
+        stage = std::min<u64>(c.budget, h->n);
         if ((rc = ensure(h, h->sh_mv, 3 * std::max<u64>(stage, 1) * sizeof(u32)))) return rc;
         d = (u32*)h->sh_mv.p;
     }
     uint64_t nm = 0;
-    if ((rc = rebalance_locked(h, cfg, order, rounds, budget, st, d, d ? d + stage : nullptr, d ? d + 2 * stage : nullptr, &nm)))
-        return rc;
+    if ((rc = rebalance_locked(h, cfg, c, st, d, d ? d + stage : nullptr, d ? d + 2 * stage : nullptr, &nm))) return rc;
     if (n_moves) *n_moves = nm;
     if (out_rows && nm) return read_listing(h, d, stage, nm, {out_rows, out_from, out_to});
     return RIO_GP_OK;
@@ -2035,11 +2106,9 @@ int rio_gp_rebalance_dev(rio_gp_t* h, const rio_gp_rebalance_cfg* cfg, rio_gp_re
                          uint32_t* d_from, uint32_t* d_to, uint64_t moves_cap, uint64_t* n_moves) {
     if (!h) return RIO_GP_EINVAL;
     Locked g(h);
-    u32 order, rounds;
-    u64 budget;
-    int rc;
-    if ((rc = rebalance_args(h, cfg, d_rows, d_from, d_to, moves_cap, &order, &rounds, &budget))) return rc;
-    return rebalance_locked(h, cfg, order, rounds, budget, st, d_rows, d_from, d_to, n_moves);
+    RbCfg c;
+    if (int rc = rebalance_args(h, cfg, d_rows, d_from, d_to, moves_cap, &c)) return rc;
+    return rebalance_locked(h, cfg, c, st, d_rows, d_from, d_to, n_moves);
 }
 
 // ---- change feed -----------------------------------------------------------------------------
@@ -3762,62 +3831,24 @@ int rio_gp_shard_finish(rio_gp_t* h, rio_gp_stats* local_stats) {
 }
 
 // ---- row-sharded rebalance -------------------------------------------------------------------
-// The phases of rebalance_locked over one rank's rows, cut at the points where the single-handle call waits for the device: what
-// the host decided there from `used` and `pin` is decided here from the gathered records, on the device (k_shrb_import_x /
-// k_shrb_merge), in rank order.
-
-namespace {
-struct RbBufs {
-    u64 *pin, *tgt, *slot_free, *C, *acc, *lu, *tdev, *base;
-    u32 *map, *slot_node, *cut, *ord, *cntp, *live, *info, *maxl, *thr, *pre;
-};
-constexpr int kRbPend = 6;  // acc[6], acc[7]: rows / load pending on all ranks (k_shrb_merge)
-RbBufs rb_bufs(rio_gp* h) {
-    const size_t M = h->cap_nodes;
-    RbBufs b;
-    b.pin = (u64*)h->sh_nodes.p;
-    b.tgt = b.pin + M;
-    b.slot_free = b.tgt + M;
-    b.C = b.slot_free + M;
-    b.acc = b.C + M + 1;
-    b.lu = b.acc + kShAcc;
-    b.tdev = b.lu + M;
-    b.base = b.tdev + M;
-    b.map = (u32*)(b.base + 1);
-    b.slot_node = b.map + M;
-    b.cut = b.slot_node + M;
-    b.ord = b.cut + M;
-    b.cntp = b.ord + M;
-    b.live = b.cntp + 4;
-    b.info = b.live + M;
-    // the load-ordered cut: info has one more word (kShrbMaxLoad); this rank's largest load, the threshold per node, the digits
-    // chosen so far per slot
-    b.maxl = b.info + kShrbInfo + 1;
-    b.thr = b.maxl + 1;
-    b.pre = b.thr + M;
-    return b;
-}
-int rb_ensure(rio_gp* h) {
-    const size_t M = h->cap_nodes;
-    return ensure(h, h->sh_nodes, (6 * M + 2 + kShAcc) * sizeof(u64) + (7 * M + 4 + kShrbInfo + 2) * sizeof(u32));
-}
-}  // namespace
+// The phases of rebalance_locked (the helpers above it: rb_cfg, rb_surplus, rb_pack, rb_finish over the one RbBufs carving) over
+// one rank's rows, cut at the points where the single-handle call waits for the device: what the host decided there from `used`
+// and `pin` is decided here from the gathered records, on the device (k_shrb_import_x / k_shrb_merge), in rank order.
+//   _begin          rb_cfg, R0 into lu; the X record leaves (rebalance_locked: its first wait; the host picks the slots)
+//   _cut            k_shrb_import_* pick the slots; waits for info.  Row order: rb_surplus, the S record leaves
+//   _threshold_*    by load only: a histogram leaves per pass; the last pick runs rb_surplus, S leaves (launch_shed_select)
+//   _select         waits for the gathered S: K (rebalance_locked: its second wait, for acc); rb_pack against lu, Y leaves
+//   _merge / _fill  the global `used` from the gathered Y; _merge waits for the pending counts; a round per _fill
+//   _finish         rb_finish against lu, the global `used` read back: the last wait of either form; read_listing
 
 // rio_gp_shard_rebalance_begin (row order only: its protocol has no threshold passes) and rio_gp_shard_rebalance_begin_ordered
 static int shard_rebalance_begin(rio_gp* h, const char* who, bool ordered, const rio_gp_rebalance_cfg* cfg, uint32_t rank,
                                  uint32_t n_ranks, int list_moves, uint64_t moves_cap, uint64_t* d_x, uint32_t* rounds_out) {
-    const std::string me = std::string(who) + ": ";
-    u32 order;
-    if (rebalance_cfg_order(cfg, &order)) return fail(h, RIO_GP_EINVAL, me + "cfg missing or struct_size differs");
-    if (order != RIO_GP_REBALANCE_ROW_ORDER && !ordered)
-        return fail(h, RIO_GP_EINVAL, me + "the load-ordered cut (order = RIO_GP_REBALANCE_BY_LOAD) of a row-sharded table has "
-                                           "threshold passes between cut and select: start it with "
-                                           "rio_gp_shard_rebalance_begin_ordered");
-    if (cfg->rounds > 8) return fail(h, RIO_GP_EINVAL, me + "rounds above the solver limit (8)");
-    if (!d_x || n_ranks == 0 || rank >= n_ranks) return fail(h, RIO_GP_EINVAL, me + "rank >= n_ranks, or no record");
-    if (!list_moves && moves_cap) return fail(h, RIO_GP_EINVAL, me + "moves_cap without a move listing");
-    int rc = may_start(h, Client::shard_rebalance_begin);
-    if (rc) return rc;
+    RbCfg c;
+    int rc = rb_cfg(h, who, ordered ? RbForm::shard_ordered : RbForm::shard, cfg,
+                    !d_x || n_ranks == 0 || rank >= n_ranks ? "rank >= n_ranks, or no record" : nullptr, list_moves != 0, moves_cap, &c);
+    if (rc || (rc = may_start(h, Client::shard_rebalance_begin))) return rc;
+    const u32 order = c.order;
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = rb_ensure(h))) return rc;
     const RbBufs b = rb_bufs(h);
@@ -3832,9 +3863,9 @@ static int shard_rebalance_begin(rio_gp* h, const char* who, bool ordered, const
     fresh.live = std::move(h->rb.live);
     fresh.rank = rank; fresh.R = n_ranks;
     fresh.order = order;
-    fresh.rounds = cfg->rounds ? cfg->rounds : h->rounds;
+    fresh.rounds = c.rounds;
     fresh.list = list_moves != 0;
-    fresh.budget = list_moves ? std::min<u64>(cfg->max_moves, moves_cap) : cfg->max_moves;
+    fresh.budget = c.budget;
     fresh.T.assign(m ? m : 1, 0);
     fresh.live.assign(m ? m : 1, 0);
     for (u32 j = 0; j < m; ++j) fresh.live[j] = h->h_alive[j] ? 1u : 0u;
@@ -3881,13 +3912,7 @@ static int shard_rebalance_surplus(rio_gp* h, const RbSession& rb, const RbBufs&
     const u32* const thr = rb.order ? b.thr : nullptr;
     HIPCHK(h, hipMemsetAsync(d_s, 0, ((size_t)h->m + 2) * sizeof(u64), h->stream));
     if (!h->n || !(p.s || forced)) return RIO_GP_OK;
-    int rc;
-    if ((rc = ensure(h, h->sh_mat, (size_t)std::max<u32>(p.s, 1) * p.nt * sizeof(u64))) ||
-        (rc = ensure(h, h->sh_tile, (size_t)p.nt * sizeof(u32))))
-        return rc;
-    launch_shrb_cut(h->assign[h->cur], h->load, h->aff, p, b.map, b.slot_node, b.slot_free, (u64*)h->sh_mat.p, b.cut, thr, h->stream);
-    launch_shed_count(h->assign[h->cur], h->load, h->aff, p, b.cut, thr, (u32*)h->sh_tile.p, b.acc, h->stream);
-    HIPCHK(h, hipGetLastError());
+    if (int rc = rb_surplus(h, p, b, thr, false)) return rc;
     HIPCHK(h, hipMemcpyAsync(d_s, b.acc, 2 * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));  // surplus rows | load
     return RIO_GP_OK;
 }
@@ -3922,10 +3947,8 @@ int rio_gp_shard_rebalance_cut(rio_gp_t* h, const uint64_t* d_xg, uint64_t* d_s,
         rb.sel_first = shrb_sel_first_pass(rb.sel, info[kShrbMaxLoad]);
         rb.sel_pass = rb.sel_first;
         rb.sel_hist_out = false;
-        int rc;  // (what the last pick needs, here: a pick that has run is not taken back)
-        if (S && h->n && ((rc = ensure(h, h->sh_mat, (size_t)S * rb.plan.nt * sizeof(u64))) ||
-                          (rc = ensure(h, h->sh_tile, (size_t)rb.plan.nt * sizeof(u32)))))
-            return rc;
+        int rc;  // (what the last pick's rb_surplus needs, here: a pick that has run is not taken back)
+        if (S && h->n && (rc = rb_plan_ensure(h, rb.plan))) return rc;
         HIPCHK(h, hipMemsetAsync(d_s, 0, ((size_t)m + 2) * sizeof(u64), h->stream));
     } else if (int rc = shard_rebalance_surplus(h, rb, b, info[kShrbForced] != 0, d_s)) {
         return rc;
@@ -4010,14 +4033,8 @@ int rio_gp_shard_rebalance_select(rio_gp_t* h, const uint64_t* d_sg, uint64_t* d
     const u64 K = B > pre ? std::min<u64>(B - pre, mine) : 0;  // R2: this rank's share of the first B surplus rows
     rb.K = K;
     rb.sel_total = std::min<u64>(B, tot);
-    if (K) {
-        int rc;
-        const u64 nc = (K + kShChunk - 1) / kShChunk;
-        if ((rc = ensure(h, h->sh_pk, 3 * K * sizeof(u32))) || (rc = ensure(h, h->sh_chunk, nc * sizeof(u64)))) return rc;
-        u32* pk_row = (u32*)h->sh_pk.p;
-        launch_shed_pack(h->assign[h->cur], h->load, h->aff, rb.plan, b.cut, rb.order ? b.thr : nullptr, (const u32*)h->sh_tile.p, K, pk_row,
-                         pk_row + K, pk_row + 2 * K, b.lu, b.acc, h->stream);
-    }
+    if (K)
+        if (int rc = rb_pack(h, rb.plan, b, rb.order ? b.thr : nullptr, K, b.lu)) return rc;
     launch_shrb_export_y(b.lu, m, b.acc + kShAccSelectedLoad, K, reinterpret_cast<u64*>(d_y), h->stream);
     HIPCHK(h, hipGetLastError());
     if (selected_local) *selected_local = K;
@@ -4058,8 +4075,8 @@ int rio_gp_shard_rebalance_fill(rio_gp_t* h, uint32_t round, uint64_t* d_y) {
     HIPCHK(h, hipSetDevice(h->device));
     const RbBufs b = rb_bufs(h);
     const u64 K = rb.K;
-    u32* pk_row = (u32*)h->sh_pk.p;
-    launch_shrb_round(K, pk_row, pk_row + K, pk_row + 2 * K, h->assign[h->cur], b.tgt, h->m, h->used.storage(), b.base,
+    const RbPacked pk = rb_packed(h, K);
+    launch_shrb_round(K, pk.row, pk.load, pk.node, h->assign[h->cur], b.tgt, h->m, h->used.storage(), b.base,
                       round + 1 == rb.rounds, (u64*)h->sh_chunk.p, b.C, b.ord, b.cntp, reinterpret_cast<u64*>(d_y), h->stream);
     HIPCHK(h, hipGetLastError());
     ++rb.fills;
@@ -4083,43 +4100,18 @@ int rio_gp_shard_rebalance_finish(rio_gp_t* h, rio_gp_rebalance_stats* local_sta
         return fail(h, RIO_GP_EINVAL, "rio_gp_shard_rebalance_finish: moves_cap below this rank's selected rows (rio_gp_shard_rebalance_select)");
     HIPCHK(h, hipSetDevice(h->device));
     const RbBufs b = rb_bufs(h);
-    const u32 m = h->m;
     rio_gp_rebalance_stats s{};
     int rc;
     u32* d = nullptr;
-    if (K) {
-        if (out_rows) {
-            if ((rc = ensure(h, h->sh_mv, 3 * K * sizeof(u32)))) return rc;
-            d = (u32*)h->sh_mv.p;
-        }
-        u32* pk_row = (u32*)h->sh_pk.p;
-        // (the rows left without a node gave their load back in the last round's record: k_shed_mcount's returns go to scratch)
-        launch_shed_finish(K, pk_row, pk_row + K, pk_row + 2 * K, h->assign[h->cur], b.lu, (u32*)h->sh_chunk.p, b.acc, d,
-                           d ? d + K : nullptr, d ? d + 2 * K : nullptr, h->stream);
-        HIPCHK(h, hipGetLastError());
+    if (K && out_rows) {
+        if ((rc = ensure(h, h->sh_mv, 3 * K * sizeof(u32)))) return rc;
+        d = (u32*)h->sh_mv.p;
     }
-    u64 a[kShAcc];
-    std::vector<u64> used(m ? m : 1);
-    HIPCHK(h, hipMemcpyAsync(a, b.acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
-    if (m) HIPCHK(h, hipMemcpyAsync(used.data(), h->used.storage(), (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    s.surplus_rows = a[kShAccSurplusRows];
-    s.surplus_load = a[kShAccSurplusLoad];
     s.selected_rows = rb.selected_rows();
-    s.selected_load = a[kShAccSelectedLoad];
-    if (K) {
-        s.moved_rows = a[kShAccMovedRows];
-        s.moved_load = a[kShAccMovedLoad];
-        s.stayed_rows = a[kShAccStayed];
-    }
     s.nodes_over_before = rb.over_before;
-    for (u32 j = 0; j < m; ++j) s.nodes_over_after += h->h_alive[j] && used[j] > rb.T[j];
-    if (out_rows && s.moved_rows) {
-        HIPCHK(h, hipMemcpyAsync(out_rows, d, s.moved_rows * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(out_from, d + K, s.moved_rows * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(out_to, d + 2 * K, s.moved_rows * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
+    // (the rows left without a node gave their load back in the last round's record: k_shed_mcount's returns go to lu, scratch now)
+    if ((rc = rb_finish(h, b, K, b.lu, rb.T.data(), d, d ? d + K : nullptr, d ? d + 2 * K : nullptr, &s))) return rc;
+    if (out_rows && s.moved_rows && (rc = read_listing(h, d, K, s.moved_rows, {out_rows, out_from, out_to}))) return rc;
     if (n_moves) *n_moves = s.moved_rows;
     if (local_stats) *local_stats = s;
     h->used.rebuilt();  // the global `used` of the new column, on every rank
