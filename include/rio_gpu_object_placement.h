@@ -253,6 +253,23 @@ int rio_op_expire_by_type(rio_op_t* p, uint32_t now, uint32_t default_max_idle, 
 int rio_op_census(rio_op_t* p, int by_server, uint64_t* n_out, const char* const** struct_names, const size_t** struct_name_lens,
                   const char* const** addresses, const uint64_t** rows, const uint64_t** loads);
 
+/* Immovable types (the dense layer's rio_gp_set_class_movable, DESIGN.md section 2 rule 13): rio_op_rebalance and
+ * rio_op_rebalance_ordered leave the keys of an immovable type where they are — a type whose objects hold a client connection
+ * or a large state, a per-server singleton: what Orleans marks [Immovable].  Their load still counts against their server's
+ * capacity, so the movable keys around them are shed sooner; their server may still receive keys.  Only the rebalance looks:
+ * clean_server, removed members, expiry and every other call treat the keys as before.
+ *   - movable == 0 makes the type immovable, anything else movable again (every type is movable to begin with).  A type never
+ *     seen before gets its class by this call, as with rio_op_set_type_idle_limit_n.  A type that lands in RIO_OP_CLASS_OTHER:
+ *     RIO_GP_ERANGE, nothing is set (the shared class is always movable).  A dense layer without rio_gp_set_class_movable or
+ *     the class setters: RIO_GP_EUPSTREAM, nothing is set and no type is numbered.
+ *   - The call itself only notes the flag (the locking of rio_op_set_type_idle_limit_n).  A rebalance that finds an immovable
+ *     type uploads the classes that changed since the last upload (as rio_op_expire_by_type does) and the table when it changed,
+ *     then makes its dense call, all under the locks it holds anyway: a type made immovable before a rebalance took its locks
+ *     is protected in it.  With no immovable type a rebalance makes the dense calls it always made (after the last immovable
+ *     type became movable again, the next rebalance first resets the dense table, once).  A row the table hands to a key of
+ *     another type follows its new type. */
+int rio_op_set_type_movable_n(rio_op_t* p, const char* struct_name, size_t len, int movable);
+
 /* Measured load (rio_gp_hits_merge + rio_gp_load_fold, DESIGN.md section 2 rule 10).  The reference's ObjectPlacementItem
  * (object_placement/mod.rs:23-24) carries no load and local.rs keeps none: load is this library's extension, and every key has
  * load 1 until rio_op_set_object_load says otherwise — one host call per key.  Tracking measures it instead.

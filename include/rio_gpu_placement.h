@@ -562,6 +562,29 @@ int rio_gp_expire_classes_dev(rio_gp_t* h, uint32_t n_classes, const uint32_t* c
 int rio_gp_census(rio_gp_t* h, uint32_t flags, uint32_t n_classes, uint64_t* out_rows, uint64_t* out_load, uint64_t* n_other);
 int rio_gp_census_dev(rio_gp_t* h, uint32_t flags, uint32_t n_classes, uint64_t* d_rows, uint64_t* d_load, uint64_t* n_other);
 
+/* Immovable classes (DESIGN.md section 2 rule 13): the rebalance leaves the objects of chosen types where they are — what
+ * Orleans' [Immovable] attribute asks of its rebalancer.  The handle keeps a table I[RIO_GP_MAX_CLASSES] of flags, all
+ * "movable" to begin with.  In R0 of rio_gp_rebalance[_dev] a row r < n on a live node j < m is PINNED iff
+ * aff[r] == RIO_GP_AFF_INACTIVE or I[K[r]] says immovable (K: the class column above); otherwise it is a candidate.  Everything
+ * downstream is rule 6 verbatim: an immovable row's load counts against its node's target as a non-object's does, the row is
+ * never surplus, never selected, never moved and never listed, its node may still be a fill target, and the result is that of
+ * rule 6 on the same table with the affinity of every immovable object row read as RIO_GP_AFF_INACTIVE (the affinity column
+ * itself is not written).  With every class movable the call is the rebalance without the table, launch for launch.
+ *   - rio_gp_set_class_movable: movable[c] == 0 makes class c immovable for c < n_classes; the classes >= n_classes become
+ *     movable (n_classes = 0, movable = NULL: the table is reset).  RIO_GP_EINVAL, nothing changed: n_classes >
+ *     RIO_GP_MAX_CLASSES, a NULL array with n_classes > 0, a handle of the row-sharded solve.  Like the class setters it is no
+ *     input of any solve (`used`, an uncommitted rio_gp_solve, the quiet and chained tick state and the change feed stay as
+ *     they were) and it may allocate K, zero-filled.  rio_gp_remap_nodes, rio_gp_set_num_objects and the rebalance leave the
+ *     table alone.
+ *   - rio_gp_get_class_movable: out256[c] = 1 where class c is movable, 0 where it is not, for all RIO_GP_MAX_CLASSES classes.
+ *   - Only the rebalance consults the table: ticks, rio_gp_clean_server, node removal, expiry and the CRUD calls treat the rows
+ *     as before (a dead node's immovable objects are evicted like any others).
+ *   - rio_gp_shard_rebalance_begin[_ordered] on a handle whose table names an immovable class is RIO_GP_EINVAL: a rank's table
+ *     has no class column.
+ *   - Cost: with an immovable class the table passes of the rebalance read K too, 13 B per row instead of 12. */
+int rio_gp_set_class_movable(rio_gp_t* h, uint32_t n_classes, const uint8_t* movable);
+int rio_gp_get_class_movable(rio_gp_t* h, uint8_t* out256);
+
 /* ---- the placement policy, batched ------------------------------------------------------ */
 
 /* Service::get_or_create_placement + check_address_mismatch (service.rs:193-298) for a batch

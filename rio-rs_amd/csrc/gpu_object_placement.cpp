@@ -85,6 +85,8 @@ extern "C" int rio_gp_expire_classes(rio_gp_t* h, uint32_t n_classes, const uint
                                      uint64_t* idle_by_class) __attribute__((weak));
 extern "C" int rio_gp_census(rio_gp_t* h, uint32_t flags, uint32_t n_classes, uint64_t* out_rows, uint64_t* out_load,
                              uint64_t* n_other) __attribute__((weak));
+// Weak for the same reason: immovable classes (rio_op_set_type_movable_n reports RIO_GP_EUPSTREAM without it).
+extern "C" int rio_gp_set_class_movable(rio_gp_t* h, uint32_t n_classes, const uint8_t* movable) __attribute__((weak));
 
 namespace {
 
@@ -430,6 +432,12 @@ struct State {
     std::deque<std::string> type_name;
     std::vector<uint32_t> type_limit;                 // rio_op_set_type_idle_limit_n, per type id
     std::vector<uint8_t> type_has_limit;
+    // rio_op_set_type_movable_n, per type id: 1 = the rebalance leaves the type's keys where they are.  n_immovable: how many
+    // are; mv_dirty: the table changed since the dense layer last got it (read by the rebalance under mu + imu exclusive);
+    // mv_on_device: the dense table names an immovable class
+    std::vector<uint8_t> type_immovable;
+    uint32_t n_immovable = 0;
+    bool mv_dirty = false, mv_on_device = false;
     std::vector<uint8_t> row_class;                   // row -> class
     // (written under imu exclusive, read by the uploads under mu + imu exclusive) what the device's class column holds: rows
     // [0, cls_uploaded) as of the last upload, except the rows in cls_dirty, which were handed to a key of another class since
@@ -640,6 +648,7 @@ uint8_t intern_type(State* s, const std::string& ty) {
     s->type_name.push_back(ty);
     s->type_limit.push_back(0);
     s->type_has_limit.push_back(0);
+    s->type_immovable.push_back(0);
     s->type_id.emplace(ty, c);
     return c;
 }
@@ -1727,6 +1736,46 @@ int rio_op_objects_on_server(rio_op_t* p, const char* address, uint64_t* n_out, 
     return RIO_GP_OK;
 }
 
+// Immovable types ahead of a dense rebalance (mu + imu exclusive held, sync_device done).  With one: the class column follows the
+// host's, then the table where it changed.  Without one nothing is called — except once after the last one became movable
+// again, when the dense table is reset.
+static int sync_classes(State* s);
+static int sync_movable(State* s) {
+    int rc;
+    if (s->n_immovable) {
+        if ((rc = sync_classes(s))) return rc;
+        if (s->mv_dirty) {
+            uint8_t movable[RIO_GP_MAX_CLASSES];
+            for (uint32_t c = 0; c < RIO_GP_MAX_CLASSES; ++c) movable[c] = !(c < s->type_immovable.size() && s->type_immovable[c]);
+            if ((rc = rio_gp_set_class_movable(s->gp, RIO_GP_MAX_CLASSES, movable))) return gp_fail(s, rc);
+            s->mv_dirty = false;
+            s->mv_on_device = true;
+        }
+    } else if (s->mv_on_device) {
+        if ((rc = rio_gp_set_class_movable(s->gp, 0, nullptr))) return gp_fail(s, rc);
+        s->mv_dirty = false;
+        s->mv_on_device = false;
+    }
+    return RIO_GP_OK;
+}
+
+int rio_op_set_type_movable_n(rio_op_t* p, const char* struct_name, size_t len, int movable) {
+    if (!p || (!struct_name && len)) return RIO_GP_EINVAL;
+    if (!rio_gp_set_class_movable || !rio_gp_set_classes || !rio_gp_set_class_batch)
+        return fail(RIO_GP_EUPSTREAM, "dense layer has no immovable classes");
+    State* s = p->s;
+    std::lock_guard<TableLock> gi(s->imu);
+    const uint8_t c = intern_type(s, std::string(struct_name ? struct_name : "", len));
+    if (c == RIO_OP_CLASS_OTHER) return fail(RIO_GP_ERANGE, "rio_op_set_type_movable_n: the type shares RIO_OP_CLASS_OTHER, which is always movable");
+    const uint8_t imm = movable ? 0 : 1;
+    if (s->type_immovable[c] != imm) {
+        s->type_immovable[c] = imm;
+        if (imm) ++s->n_immovable; else --s->n_immovable;
+        s->mv_dirty = true;
+    }
+    return RIO_GP_OK;
+}
+
 int rio_op_rebalance(rio_op_t* p, uint64_t max_moves, uint64_t* n_out, const char* const** struct_names,
                      const size_t** struct_name_lens, const char* const** object_ids, const size_t** object_id_lens,
                      const char* const** from_addresses, const char* const** to_addresses) {
@@ -1749,6 +1798,7 @@ int rio_op_rebalance_ordered(rio_op_t* p, uint32_t order, uint64_t max_moves, ui
         int rc;
         if ((rc = sync_device(s, true))) return rc;
         if (!rio_gp_rebalance) return fail(RIO_GP_EUPSTREAM, "dense layer has no rebalance");
+        if ((rc = sync_movable(s))) return rc;
         // a move is a row that is handed out: at most as many as rows were ever interned
         const uint64_t cap = std::min<uint64_t>(max_moves, s->row_key.size());
         std::vector<uint32_t> &rows = t_rb.rows, &src = t_rb.c1, &dst = t_rb.c2;

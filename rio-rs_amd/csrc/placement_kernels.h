@@ -441,23 +441,33 @@ struct ShPlan {
 };
 ShPlan sh_plan(u64 n, u32 m, u32 s);
 size_t shed_order_lds(u32 m);
+// `cls` in the launches of the table passes below (rule 13; nullptr = no immovable class, the kernels without the table): the
+// class column and the immovable classes, one bit each.  With it a row of an immovable class counts as a pinned row in every
+// pass (kernels k_shedc_*: the quad of K beside the three columns, the bits in kShClsLds more bytes of dynamic LDS).
+struct ShCls {
+    const unsigned char* K;  // the class column, readable in whole quads up to the rows rounded up to 4
+    u32 imm[8];              // bit c: class c is immovable (8 x 32 = RIO_GP_MAX_CLASSES)
+};
+constexpr size_t kShClsLds = sizeof(ShCls::imm);
 // used, pin: m u64 each (zeroed here): the load of every row on node j, the load of the non-object rows on it; maxl (may be
 // nullptr): one u32 -> the largest load of an object row on a node < m
 void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u64* used, u64* pin, hipStream_t s,
-                      u32* maxl = nullptr);
+                      u32* maxl = nullptr, const ShCls* cls = nullptr);
 // map: node -> slot (kNone: not over); slot_node / slot_free: per slot; mat: s * nt u64; cut: m u32 (kNone where nothing is cut).
 // thr (m u32, or nullptr = row order) in the four launches below: the load-ordered cut's threshold per node (kNone on a node
 // that is not over).  With it the cut walks only the candidates whose load == thr[node] — slot_free is then what
 // launch_shed_select left — and a candidate is surplus iff load > thr[node] || (load == thr[node] && row >= cut[node]).
 // fill_cut: cut starts as kNone on every node (false: k_shrb_import_x / k_shrb_import_slots wrote it).  No slot or no row: no pass.
 void launch_shed_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
-                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, bool fill_cut, hipStream_t s);
+                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, bool fill_cut, hipStream_t s,
+                     const ShCls* cls = nullptr);
 // tcnt: nt u32 -> the exclusive scan of the per-tile surplus counts; acc[kShAccSurplusRows / SurplusLoad]
 void launch_shed_count(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* thr,
-                       u32* tcnt, u64* acc, hipStream_t s);
+                       u32* tcnt, u64* acc, hipStream_t s, const ShCls* cls = nullptr);
 // the first `budget` surplus rows into pk_* (row, load, node = kNone); used[j] -= their load; acc[kShAccSelectedLoad]
 void launch_shed_pack(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* thr,
-                      const u32* toff, u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s);
+                      const u32* toff, u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s,
+                      const ShCls* cls = nullptr);
 // The load-ordered cut (RIO_GP_REBALANCE_BY_LOAD; kernels: k_shed_sel_hist, k_shed_sel_pick): a segmented, weighted radix
 // selection, most significant digit first.  Per over node (slot) it finds the smallest load tau whose candidates, together with
 // every lighter one, weigh more than slot_free: thr[slot_node] = tau, slot_free[slot] -= the load of the candidates below tau.
@@ -473,7 +483,8 @@ struct ShSelPlan {
 ShSelPlan sh_sel_plan(u32 s);
 // pre: s u32 of scratch; hist: (s << bits) u64 of scratch; thr: m u32 (kNone where the node is not over)
 void launch_shed_select(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u32 s, const u32* map,
-                        const u32* slot_node, u64* slot_free, u32* pre, u64* hist, u32* thr, hipStream_t st);
+                        const u32* slot_node, u64* slot_free, u32* pre, u64* hist, u32* thr, hipStream_t st,
+                        const ShCls* cls = nullptr);
 // one water-fill round over the K packed rows against free = tgt -sat used; csum: ceil(K / kShChunk) u64; C: m + 1 u64; ord: m u32
 void launch_shed_round(u64 K, const u32* pk_load, u32* pk_node, const u64* tgt, u32 m, u64* used, u64* csum, u64* C, u32* ord,
                        u32* cntp, hipStream_t s);
@@ -604,6 +615,7 @@ void launch_top_rows(const u32* K, const u32* A, u64 n, u32 min_key, u32 filt, u
 
 // --- object classes (rio_gp_set_class*, rio_gp_expire_classes, rio_gp_census): a class column K, one byte per row ---
 constexpr u32 kClsMax = 256;           // = RIO_GP_MAX_CLASSES: the cutoff table and the per-class histogram, 1 KiB of LDS each
+static_assert(sizeof(ShCls::imm) * 8 == kClsMax, "rule 13: one bit per class");
 constexpr u32 kClsSlots = 32;          // copies of the sweep's per-class counts the workgroups of k_expc_count spread their adds over
 constexpr u32 kCensusLdsCells = 4096;  // cells one workgroup of k_census accumulates in LDS (12 B a cell: 48 KiB): one slice
 constexpr u32 kCensusMaxSlices = 16;   // slices (passes over the columns) up to which the census stays in LDS; beyond: global adds

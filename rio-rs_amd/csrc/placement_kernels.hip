@@ -6181,6 +6181,9 @@ void launch_ni_scatter(const u32* assign, const NiPlan& p, const u32* map, const
 //                  (dead nodes: T = 0), then the interval rule for every pending row
 //   k_shed_mcount + k_shed_scan + k_shed_finish   the rows the fill left without a node give their load back to their own node
 //                  (R4); the moved rows go into the column and, in row order, into the move list
+//   k_shedc_*      (rule 13, immovable classes) the class-aware form of the six table passes hist, sel_hist, tile, cut, count,
+//                  pack: a row of an immovable class counts as a pinned row.  One body per pass, a template on CLS; the
+//                  k_shed_* kernel is its CLS = false instantiation, the k_shedc_* kernel its CLS = true one (ShCls)
 // All sums are integers: the atomics make no result depend on scheduling.  Packed arrays are read with scalar loads (the
 // packed rows are a few percent of the table); the table passes stream `dwordx4`.
 // ------------------------------------------------------------------------------------------------
@@ -6207,20 +6210,45 @@ __device__ __forceinline__ bool shed_surplus(const u32* th, u32 l, u64 row, u32 
     return l > t || (l == t && row >= (u64)cut);
 }
 
+// Rule 13 (immovable classes): the table passes in their class-aware form (CLS; kernels k_shedc_*) read the quad of the class
+// column K beside the three dwordx4 (i0 is a multiple of 4: one u32 per lane) and take a row whose class is immovable for a
+// pinned row, which is all the rule says.  The table is a bitmask, one bit per class, staged from the kernel's arguments into 8
+// words of the dynamic LDS (`tab`) ahead of the prologue's barrier.
+template <bool CLS>
+__device__ __forceinline__ void shed_cls_stage(u32* tab, const ShCls& cls) {
+    if (CLS && threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 0; w < (int)(kClsMax / 32); ++w) tab[w] = cls.imm[w];
+    }
+}
+// the affinities of the quad at i0 as R0 reads them: kAffInactive in place of the affinity of an immovable class's row
+template <bool CLS>
+__device__ __forceinline__ void shed_cls_pin(u32 (&aa)[4], const ShCls& cls, const u32* tab, u64 i0) {
+    if (!CLS) return;
+    const u32 kq = *reinterpret_cast<const u32*>(cls.K + i0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const u32 c = (kq >> (8 * k)) & 255u;
+        if ((tab[c >> 5] >> (c & 31u)) & 1u) aa[k] = kAffInactive;
+    }
+}
+
 // MAX (the row-sharded load-ordered cut): also *maxl = the largest load of an object row on a node < m — no candidate of any
 // node weighs more, so no threshold has a bit above its highest one
-template <bool MAX>
-__global__ __launch_bounds__(kBlock) void k_shed_hist(const u32* __restrict__ assign, const u32* __restrict__ load,
-                                                      const u32* __restrict__ aff, u64 n, u32 m, u64* __restrict__ used,
-                                                      u64* __restrict__ pin, u32* __restrict__ maxl) {
+template <bool MAX, bool CLS>
+__device__ __forceinline__ void shed_hist_body(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                               const u32* __restrict__ aff, u64 n, u32 m, u64* __restrict__ used,
+                                               u64* __restrict__ pin, u32* __restrict__ maxl, const ShCls& cls) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64* hu = reinterpret_cast<u64*>(smem);  // [m]
     u64* hp = hu + m;                        // [m]
+    u32* tab = reinterpret_cast<u32*>(hp + m);  // [8], CLS only
     __shared__ u32 s_mx;  // MAX only
     const int tid = threadIdx.x;
     u32 mx = 0;
     for (u32 k = tid; k < 2 * m; k += kBlock) hu[k] = 0;
     if (MAX && tid == 0) s_mx = 0;
+    shed_cls_stage<CLS>(tab, cls);
     __syncthreads();
     const u64 nvec = (n + 3) / 4;
     for (u64 v = (u64)blockIdx.x * kBlock + tid; v < nvec; v += (u64)gridDim.x * kBlock) {
@@ -6228,7 +6256,9 @@ __global__ __launch_bounds__(kBlock) void k_shed_hist(const u32* __restrict__ as
         const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
         const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
         const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
-        const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
+        const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w};
+        u32 aa[4] = {a.x, a.y, a.z, a.w};
+        shed_cls_pin<CLS>(aa, cls, tab, i0);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (i0 + k < n && cc[k] < m && ll[k]) {
@@ -6252,20 +6282,35 @@ __global__ __launch_bounds__(kBlock) void k_shed_hist(const u32* __restrict__ as
     }
     if (MAX && tid == 0 && s_mx) atomicMax(maxl, s_mx);
 }
+template <bool MAX>
+__global__ __launch_bounds__(kBlock) void k_shed_hist(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                      const u32* __restrict__ aff, u64 n, u32 m, u64* __restrict__ used,
+                                                      u64* __restrict__ pin, u32* __restrict__ maxl) {
+    shed_hist_body<MAX, false>(assign, load, aff, n, m, used, pin, maxl, ShCls{});
+}
+template <bool MAX>
+__global__ __launch_bounds__(kBlock) void k_shedc_hist(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                       const u32* __restrict__ aff, u64 n, u32 m, u64* __restrict__ used,
+                                                       u64* __restrict__ pin, u32* __restrict__ maxl, ShCls cls) {
+    shed_hist_body<MAX, true>(assign, load, aff, n, m, used, pin, maxl, cls);
+}
 
-__global__ __launch_bounds__(kBlock) void k_shed_tile(const u32* __restrict__ assign, const u32* __restrict__ load,
-                                                      const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ map,
-                                                      const u32* __restrict__ thr, u64* __restrict__ mat) {
+template <bool CLS>
+__device__ __forceinline__ void shed_tile_body(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                               const u32* __restrict__ aff, const ShPlan& p, const u32* __restrict__ map,
+                                               const u32* __restrict__ thr, u64* __restrict__ mat, const ShCls& cls) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64* h = reinterpret_cast<u64*>(smem);           // [s]
     u32* mp = reinterpret_cast<u32*>(h + p.s);       // [m]
     u32* th = mp + p.m;                              // [m] with thr only
+    u32* tab = th + (thr ? p.m : 0u);                // [8], CLS only
     const int tid = threadIdx.x;
     const u32 t = blockIdx.x;
     for (u32 k = tid; k < p.s; k += kBlock) h[k] = 0;
     for (u32 k = tid; k < p.m; k += kBlock) mp[k] = map[k];
     if (thr)
         for (u32 k = tid; k < p.m; k += kBlock) th[k] = thr[k];
+    shed_cls_stage<CLS>(tab, cls);
     __syncthreads();
     const u64 lo = (u64)t * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
     for (u64 base = lo; base < hi; base += kShChunk) {
@@ -6274,7 +6319,9 @@ __global__ __launch_bounds__(kBlock) void k_shed_tile(const u32* __restrict__ as
         const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
         const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
         const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
-        const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
+        const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w};
+        u32 aa[4] = {a.x, a.y, a.z, a.w};
+        shed_cls_pin<CLS>(aa, cls, tab, i0);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (i0 + k < hi && cc[k] < p.m && aa[k] != kAffInactive && ll[k] && (!thr || ll[k] == th[cc[k]])) {
@@ -6285,11 +6332,24 @@ __global__ __launch_bounds__(kBlock) void k_shed_tile(const u32* __restrict__ as
     __syncthreads();
     for (u32 k = tid; k < p.s; k += kBlock) mat[(size_t)k * p.nt + t] = h[k];
 }
+__global__ __launch_bounds__(kBlock) void k_shed_tile(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                      const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ map,
+                                                      const u32* __restrict__ thr, u64* __restrict__ mat) {
+    shed_tile_body<false>(assign, load, aff, p, map, thr, mat, ShCls{});
+}
+__global__ __launch_bounds__(kBlock) void k_shedc_tile(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                       const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ map,
+                                                       const u32* __restrict__ thr, u64* __restrict__ mat, ShCls cls) {
+    shed_tile_body<true>(assign, load, aff, p, map, thr, mat, cls);
+}
 
-__global__ __launch_bounds__(kBlock) void k_shed_cut(const u32* __restrict__ assign, const u32* __restrict__ load,
-                                                     const u32* __restrict__ aff, ShPlan p, const u64* __restrict__ mat,
-                                                     const u32* __restrict__ slot_node, const u64* __restrict__ slot_free,
-                                                     const u32* __restrict__ thr, u32* __restrict__ cut) {
+template <bool CLS>
+__device__ __forceinline__ void shed_cut_body(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                              const u32* __restrict__ aff, const ShPlan& p, const u64* __restrict__ mat,
+                                              const u32* __restrict__ slot_node, const u64* __restrict__ slot_free,
+                                              const u32* __restrict__ thr, u32* __restrict__ cut, const ShCls& cls) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32* tab = reinterpret_cast<u32*>(smem);  // [8], CLS only (the one dynamic allocation of this pass)
     __shared__ u64 part[16];
     __shared__ u64 s_base;
     __shared__ u32 s_tile, s_row;
@@ -6299,6 +6359,7 @@ __global__ __launch_bounds__(kBlock) void k_shed_cut(const u32* __restrict__ ass
     const u64 fr = slot_free[sl];
     const u64* row = mat + (size_t)sl * p.nt;
     if (tid == 0) { s_tile = kNone; s_row = kNone; s_base = 0; }
+    shed_cls_stage<CLS>(tab, cls);
     __syncthreads();
     // the tile: the first inclusive prefix > free (the prefix never decreases: exactly one tile starts at or below free and ends
     // above it)
@@ -6325,7 +6386,9 @@ __global__ __launch_bounds__(kBlock) void k_shed_cut(const u32* __restrict__ ass
             const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
             const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
             const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
-            const u32 cc[4] = {c.x, c.y, c.z, c.w}, l4[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
+            const u32 cc[4] = {c.x, c.y, c.z, c.w}, l4[4] = {l.x, l.y, l.z, l.w};
+            u32 aa[4] = {a.x, a.y, a.z, a.w};
+            shed_cls_pin<CLS>(aa, cls, tab, i0);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 ll[k] = (i0 + k < hi && cc[k] == j && aa[k] != kAffInactive && (!thr || l4[k] == tj)) ? l4[k] : 0u;
@@ -6343,14 +6406,28 @@ __global__ __launch_bounds__(kBlock) void k_shed_cut(const u32* __restrict__ ass
     }
     if (tid == 0) cut[j] = s_row;
 }
+__global__ __launch_bounds__(kBlock) void k_shed_cut(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                     const u32* __restrict__ aff, ShPlan p, const u64* __restrict__ mat,
+                                                     const u32* __restrict__ slot_node, const u64* __restrict__ slot_free,
+                                                     const u32* __restrict__ thr, u32* __restrict__ cut) {
+    shed_cut_body<false>(assign, load, aff, p, mat, slot_node, slot_free, thr, cut, ShCls{});
+}
+__global__ __launch_bounds__(kBlock) void k_shedc_cut(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                      const u32* __restrict__ aff, ShPlan p, const u64* __restrict__ mat,
+                                                      const u32* __restrict__ slot_node, const u64* __restrict__ slot_free,
+                                                      const u32* __restrict__ thr, u32* __restrict__ cut, ShCls cls) {
+    shed_cut_body<true>(assign, load, aff, p, mat, slot_node, slot_free, thr, cut, cls);
+}
 
-__global__ __launch_bounds__(kBlock) void k_shed_count(const u32* __restrict__ assign, const u32* __restrict__ load,
-                                                       const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ cut,
-                                                       const u32* __restrict__ thr, u32* __restrict__ tcnt,
-                                                       u64* __restrict__ acc) {
+template <bool CLS>
+__device__ __forceinline__ void shed_count_body(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                const u32* __restrict__ aff, const ShPlan& p, const u32* __restrict__ cut,
+                                                const u32* __restrict__ thr, u32* __restrict__ tcnt, u64* __restrict__ acc,
+                                                const ShCls& cls) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32* ct = reinterpret_cast<u32*>(smem);  // [m]
     u32* th = ct + p.m;                      // [m] with thr only
+    u32* tab = th + (thr ? p.m : 0u);        // [8], CLS only
     __shared__ u64 s_sum;
     __shared__ u32 s_cnt;
     const int tid = threadIdx.x;
@@ -6359,6 +6436,7 @@ __global__ __launch_bounds__(kBlock) void k_shed_count(const u32* __restrict__ a
     if (thr)
         for (u32 k = tid; k < p.m; k += kBlock) th[k] = thr[k];
     if (tid == 0) { s_sum = 0; s_cnt = 0; }
+    shed_cls_stage<CLS>(tab, cls);
     __syncthreads();
     u64 sum = 0;
     u32 cnt = 0;
@@ -6369,7 +6447,9 @@ __global__ __launch_bounds__(kBlock) void k_shed_count(const u32* __restrict__ a
         const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
         const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
         const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
-        const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
+        const u32 cc[4] = {c.x, c.y, c.z, c.w}, ll[4] = {l.x, l.y, l.z, l.w};
+        u32 aa[4] = {a.x, a.y, a.z, a.w};
+        shed_cls_pin<CLS>(aa, cls, tab, i0);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (i0 + k < hi && cc[k] < p.m && aa[k] != kAffInactive &&
@@ -6383,6 +6463,18 @@ __global__ __launch_bounds__(kBlock) void k_shed_count(const u32* __restrict__ a
         tcnt[t] = s_cnt;
         if (s_sum) atomicAdd(&acc[kShAccSurplusLoad], s_sum);
     }
+}
+__global__ __launch_bounds__(kBlock) void k_shed_count(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                       const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ cut,
+                                                       const u32* __restrict__ thr, u32* __restrict__ tcnt,
+                                                       u64* __restrict__ acc) {
+    shed_count_body<false>(assign, load, aff, p, cut, thr, tcnt, acc, ShCls{});
+}
+__global__ __launch_bounds__(kBlock) void k_shedc_count(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                        const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ cut,
+                                                        const u32* __restrict__ thr, u32* __restrict__ tcnt,
+                                                        u64* __restrict__ acc, ShCls cls) {
+    shed_count_body<true>(assign, load, aff, p, cut, thr, tcnt, acc, cls);
 }
 
 // exclusive scan of len values (in may be out), one workgroup, starting at *init (NULL: 0); the total into *total
@@ -6413,14 +6505,16 @@ __global__ __launch_bounds__(kBlock) void k_shed_scan(const T* in, T* out, u64 l
     if (tid == 0 && total) *total = carry;
 }
 
-__global__ __launch_bounds__(kBlock) void k_shed_pack(const u32* __restrict__ assign, const u32* __restrict__ load,
-                                                      const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ cut,
-                                                      const u32* __restrict__ thr, const u32* __restrict__ toff, u64 budget,
-                                                      u32* __restrict__ pk_row, u32* __restrict__ pk_load,
-                                                      u32* __restrict__ pk_node, u64* __restrict__ used, u64* __restrict__ acc) {
+template <bool CLS>
+__device__ __forceinline__ void shed_pack_body(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                               const u32* __restrict__ aff, const ShPlan& p, const u32* __restrict__ cut,
+                                               const u32* __restrict__ thr, const u32* __restrict__ toff, u64 budget,
+                                               u32* __restrict__ pk_row, u32* __restrict__ pk_load, u32* __restrict__ pk_node,
+                                               u64* __restrict__ used, u64* __restrict__ acc, const ShCls& cls) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32* ct = reinterpret_cast<u32*>(smem);  // [m]
     u32* th = ct + p.m;                      // [m] with thr only
+    u32* tab = th + (thr ? p.m : 0u);        // [8], CLS only
     __shared__ u64 part[16];
     const int tid = threadIdx.x;
     const u32 t = blockIdx.x;
@@ -6429,6 +6523,7 @@ __global__ __launch_bounds__(kBlock) void k_shed_pack(const u32* __restrict__ as
     for (u32 k = tid; k < p.m; k += kBlock) ct[k] = cut[k];
     if (thr)
         for (u32 k = tid; k < p.m; k += kBlock) th[k] = thr[k];
+    shed_cls_stage<CLS>(tab, cls);
     __syncthreads();
     u64 sel = 0;
     const u64 lo = (u64)t * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
@@ -6440,7 +6535,9 @@ __global__ __launch_bounds__(kBlock) void k_shed_pack(const u32* __restrict__ as
             const uint4 c = *reinterpret_cast<const uint4*>(assign + i0);
             const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
             const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
-            const u32 c4[4] = {c.x, c.y, c.z, c.w}, l4[4] = {l.x, l.y, l.z, l.w}, aa[4] = {a.x, a.y, a.z, a.w};
+            const u32 c4[4] = {c.x, c.y, c.z, c.w}, l4[4] = {l.x, l.y, l.z, l.w};
+            u32 aa[4] = {a.x, a.y, a.z, a.w};
+            shed_cls_pin<CLS>(aa, cls, tab, i0);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 cc[k] = c4[k]; ll[k] = l4[k];
@@ -6466,6 +6563,21 @@ __global__ __launch_bounds__(kBlock) void k_shed_pack(const u32* __restrict__ as
     }
     sel = wave_sum(sel);
     if ((tid & 63) == 0 && sel) atomicAdd(&acc[kShAccSelectedLoad], sel);
+}
+__global__ __launch_bounds__(kBlock) void k_shed_pack(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                      const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ cut,
+                                                      const u32* __restrict__ thr, const u32* __restrict__ toff, u64 budget,
+                                                      u32* __restrict__ pk_row, u32* __restrict__ pk_load,
+                                                      u32* __restrict__ pk_node, u64* __restrict__ used, u64* __restrict__ acc) {
+    shed_pack_body<false>(assign, load, aff, p, cut, thr, toff, budget, pk_row, pk_load, pk_node, used, acc, ShCls{});
+}
+__global__ __launch_bounds__(kBlock) void k_shedc_pack(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                       const u32* __restrict__ aff, ShPlan p, const u32* __restrict__ cut,
+                                                       const u32* __restrict__ thr, const u32* __restrict__ toff, u64 budget,
+                                                       u32* __restrict__ pk_row, u32* __restrict__ pk_load,
+                                                       u32* __restrict__ pk_node, u64* __restrict__ used, u64* __restrict__ acc,
+                                                       ShCls cls) {
+    shed_pack_body<true>(assign, load, aff, p, cut, thr, toff, budget, pk_row, pk_load, pk_node, used, acc, cls);
 }
 
 // per chunk of kShChunk packed rows: the load of the rows still without a node
@@ -6643,20 +6755,22 @@ __global__ __launch_bounds__(kBlock) void k_shed_finish(u64 K, const u32* __rest
 //                           step and distinct (slot, digit).  ... a pass of this form cost ~460 us at the same 692 slots with
 //                           11-bit digits (not traced: a wave holds ~40 distinct slots, and every one is
 //                           a round of the aggregation loop), so it runs only where the LDS form cannot
-template <bool LDS>
-__global__ __launch_bounds__(kBlock) void k_shed_sel_hist(const u32* __restrict__ assign, const u32* __restrict__ load,
-                                                          const u32* __restrict__ aff, u64 n, u32 m, u32 S,
-                                                          const u32* __restrict__ map, const u32* __restrict__ pre, u32 himask,
-                                                          u32 shift, u32 bins, u32 stride, u64* __restrict__ hist) {
+template <bool LDS, bool CLS>
+__device__ __forceinline__ void shed_sel_hist_body(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                   const u32* __restrict__ aff, u64 n, u32 m, u32 S,
+                                                   const u32* __restrict__ map, const u32* __restrict__ pre, u32 himask,
+                                                   u32 shift, u32 bins, u32 stride, u64* __restrict__ hist, const ShCls& cls) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32* mp = reinterpret_cast<u32*>(smem);  // [m]
     u32* pr = mp + m;                        // [S]
     u64* h = reinterpret_cast<u64*>(smem + ((((size_t)m + S) * sizeof(u32) + 15) & ~(size_t)15));  // [S * bins], LDS form only
+    u32* tab = reinterpret_cast<u32*>(h + (LDS ? (size_t)S * bins : 0));  // [8], CLS only
     const int tid = threadIdx.x;
     for (u32 k = tid; k < m; k += kBlock) mp[k] = map[k];
     for (u32 k = tid; k < S; k += kBlock) pr[k] = pre[k];
     if (LDS)
         for (u32 k = tid; k < S * bins; k += kBlock) h[k] = 0;
+    shed_cls_stage<CLS>(tab, cls);
     __syncthreads();
     const u64 nvec = (n + 3) / 4;
     for (u64 v0 = (u64)blockIdx.x * kBlock; v0 < nvec; v0 += (u64)gridDim.x * kBlock) {  // (uniform: shed_agg_add needs the wave)
@@ -6669,6 +6783,7 @@ __global__ __launch_bounds__(kBlock) void k_shed_sel_hist(const u32* __restrict_
             cc[0] = c.x; cc[1] = c.y; cc[2] = c.z; cc[3] = c.w;
             ll[0] = l.x; ll[1] = l.y; ll[2] = l.z; ll[3] = l.w;
             aa[0] = a.x; aa[1] = a.y; aa[2] = a.z; aa[3] = a.w;
+            shed_cls_pin<CLS>(aa, cls, tab, i0);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -6690,6 +6805,20 @@ __global__ __launch_bounds__(kBlock) void k_shed_sel_hist(const u32* __restrict_
         for (u32 k = tid; k < S * bins; k += kBlock)
             if (h[k]) atomicAdd(&hist[(size_t)(k / bins) * stride + (k % bins)], h[k]);
     }
+}
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void k_shed_sel_hist(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                          const u32* __restrict__ aff, u64 n, u32 m, u32 S,
+                                                          const u32* __restrict__ map, const u32* __restrict__ pre, u32 himask,
+                                                          u32 shift, u32 bins, u32 stride, u64* __restrict__ hist) {
+    shed_sel_hist_body<LDS, false>(assign, load, aff, n, m, S, map, pre, himask, shift, bins, stride, hist, ShCls{});
+}
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void k_shedc_selhist(const u32* __restrict__ assign, const u32* __restrict__ load,
+                                                           const u32* __restrict__ aff, u64 n, u32 m, u32 S,
+                                                           const u32* __restrict__ map, const u32* __restrict__ pre, u32 himask,
+                                                           u32 shift, u32 bins, u32 stride, u64* __restrict__ hist, ShCls cls) {
+    shed_sel_hist_body<LDS, true>(assign, load, aff, n, m, S, map, pre, himask, shift, bins, stride, hist, cls);
 }
 
 // One workgroup per slot: the first bin whose inclusive sum passes rem is the next digit; the row of bins is left zeroed for
@@ -6743,12 +6872,19 @@ static ShSelDigit sh_sel_digit(const ShSelPlan& q, u32 pass) {
 }
 // one histogram pass of plan q over n > 0 rows, added into hist (s << q.bits u64, zero on entry)
 static void launch_shed_sel_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u32 s, const u32* map,
-                                 const u32* pre, const ShSelPlan& q, u32 pass, u64* hist, hipStream_t st) {
+                                 const u32* pre, const ShSelPlan& q, u32 pass, u64* hist, hipStream_t st,
+                                 const ShCls* cls = nullptr) {
     const ShSelDigit d = sh_sel_digit(q, pass);
     const u32 stride = 1u << q.bits;
     const dim3 grid(grid_for((n + 3) / 4, kBlock, 256)), block(kBlock);
     const size_t head = (((size_t)m + s) * sizeof(u32) + 15) & ~(size_t)15;
-    if (q.lds)
+    if (cls && q.lds)
+        hipLaunchKernelGGL((k_shedc_selhist<true>), grid, block, head + (size_t)s * d.bins * sizeof(u64) + kShClsLds, st, assign,
+                           load, aff, n, m, s, map, pre, d.himask, d.lo, d.bins, stride, hist, *cls);
+    else if (cls)
+        hipLaunchKernelGGL((k_shedc_selhist<false>), grid, block, head + kShClsLds, st, assign, load, aff, n, m, s, map, pre,
+                           d.himask, d.lo, d.bins, stride, hist, *cls);
+    else if (q.lds)
         hipLaunchKernelGGL((k_shed_sel_hist<true>), grid, block, head + (size_t)s * d.bins * sizeof(u64), st, assign, load, aff, n,
                            m, s, map, pre, d.himask, d.lo, d.bins, stride, hist);
     else
@@ -6757,7 +6893,7 @@ static void launch_shed_sel_hist(const u32* assign, const u32* load, const u32* 
 }
 
 void launch_shed_select(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u32 s, const u32* map,
-                        const u32* slot_node, u64* slot_free, u32* pre, u64* hist, u32* thr, hipStream_t st) {
+                        const u32* slot_node, u64* slot_free, u32* pre, u64* hist, u32* thr, hipStream_t st, const ShCls* cls) {
     launch_fill_u32(thr, m, kNone, st);
     if (!s || !n) return;
     const ShSelPlan q = sh_sel_plan(s);
@@ -6766,7 +6902,7 @@ void launch_shed_select(const u32* assign, const u32* load, const u32* aff, u64 
     (void)hipMemsetAsync(hist, 0, ((size_t)s << q.bits) * sizeof(u64), st);
     for (u32 pass = 0; pass < q.passes; ++pass) {
         const ShSelDigit d = sh_sel_digit(q, pass);
-        launch_shed_sel_hist(assign, load, aff, n, m, s, map, pre, q, pass, hist, st);
+        launch_shed_sel_hist(assign, load, aff, n, m, s, map, pre, q, pass, hist, st, cls);
         hipLaunchKernelGGL(k_shed_sel_pick, dim3(s), dim3(kBlock), 0, st, hist, d.bins, stride, d.lo, d.lo == 0, slot_node,
                            slot_free, pre, thr);
     }
@@ -6792,33 +6928,53 @@ static size_t shed_tile_lds(const ShPlan& p, const u32* thr) {
 }
 
 void launch_shed_hist(const u32* assign, const u32* load, const u32* aff, u64 n, u32 m, u64* used, u64* pin, hipStream_t s,
-                      u32* maxl) {
+                      u32* maxl, const ShCls* cls) {
     (void)hipMemsetAsync(used, 0, (size_t)m * sizeof(u64), s);
     (void)hipMemsetAsync(pin, 0, (size_t)m * sizeof(u64), s);
     if (maxl) (void)hipMemsetAsync(maxl, 0, sizeof(u32), s);
     if (!n || !m) return;
     const dim3 grid(grid_for((n + 3) / 4, kBlock, 256)), block(kBlock);
     const size_t lds = 2 * (size_t)m * sizeof(u64);
-    if (maxl) hipLaunchKernelGGL((k_shed_hist<true>), grid, block, lds, s, assign, load, aff, n, m, used, pin, maxl);
+    if (cls && maxl)
+        hipLaunchKernelGGL((k_shedc_hist<true>), grid, block, lds + kShClsLds, s, assign, load, aff, n, m, used, pin, maxl, *cls);
+    else if (cls)
+        hipLaunchKernelGGL((k_shedc_hist<false>), grid, block, lds + kShClsLds, s, assign, load, aff, n, m, used, pin, maxl, *cls);
+    else if (maxl) hipLaunchKernelGGL((k_shed_hist<true>), grid, block, lds, s, assign, load, aff, n, m, used, pin, maxl);
     else hipLaunchKernelGGL((k_shed_hist<false>), grid, block, lds, s, assign, load, aff, n, m, used, pin, maxl);
 }
 void launch_shed_cut(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* map, const u32* slot_node,
-                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, bool fill_cut, hipStream_t s) {
+                     const u64* slot_free, u64* mat, u32* cut, const u32* thr, bool fill_cut, hipStream_t s, const ShCls* cls) {
     if (fill_cut) launch_fill_u32(cut, p.m, kNone, s);
     if (!p.s || !p.n) return;
+    if (cls) {
+        hipLaunchKernelGGL(k_shedc_tile, dim3(p.nt), dim3(kBlock), shed_tile_lds(p, thr) + kShClsLds, s, assign, load, aff, p, map,
+                           thr, mat, *cls);
+        hipLaunchKernelGGL(k_shedc_cut, dim3(p.s), dim3(kBlock), kShClsLds, s, assign, load, aff, p, mat, slot_node, slot_free, thr,
+                           cut, *cls);
+        return;
+    }
     hipLaunchKernelGGL(k_shed_tile, dim3(p.nt), dim3(kBlock), shed_tile_lds(p, thr), s, assign, load, aff, p, map, thr, mat);
     hipLaunchKernelGGL(k_shed_cut, dim3(p.s), dim3(kBlock), 0, s, assign, load, aff, p, mat, slot_node, slot_free, thr, cut);
 }
 void launch_shed_count(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* thr,
-                       u32* tcnt, u64* acc, hipStream_t s) {
-    hipLaunchKernelGGL(k_shed_count, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32) * (thr ? 2 : 1), s, assign, load, aff, p,
-                       cut, thr, tcnt, acc);
+                       u32* tcnt, u64* acc, hipStream_t s, const ShCls* cls) {
+    if (cls)
+        hipLaunchKernelGGL(k_shedc_count, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32) * (thr ? 2 : 1) + kShClsLds, s, assign,
+                           load, aff, p, cut, thr, tcnt, acc, *cls);
+    else
+        hipLaunchKernelGGL(k_shed_count, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32) * (thr ? 2 : 1), s, assign, load, aff,
+                           p, cut, thr, tcnt, acc);
     hipLaunchKernelGGL((k_shed_scan<u32>), dim3(1), dim3(kBlock), 0, s, tcnt, tcnt, (u64)p.nt, acc + kShAccSurplusRows, (const u64*)nullptr);
 }
 void launch_shed_pack(const u32* assign, const u32* load, const u32* aff, const ShPlan& p, const u32* cut, const u32* thr,
-                      const u32* toff, u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s) {
-    hipLaunchKernelGGL(k_shed_pack, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32) * (thr ? 2 : 1), s, assign, load, aff, p,
-                       cut, thr, toff, budget, pk_row, pk_load, pk_node, used, acc);
+                      const u32* toff, u64 budget, u32* pk_row, u32* pk_load, u32* pk_node, u64* used, u64* acc, hipStream_t s,
+                      const ShCls* cls) {
+    if (cls)
+        hipLaunchKernelGGL(k_shedc_pack, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32) * (thr ? 2 : 1) + kShClsLds, s, assign,
+                           load, aff, p, cut, thr, toff, budget, pk_row, pk_load, pk_node, used, acc, *cls);
+    else
+        hipLaunchKernelGGL(k_shed_pack, dim3(p.nt), dim3(kBlock), (size_t)p.m * sizeof(u32) * (thr ? 2 : 1), s, assign, load, aff,
+                           p, cut, thr, toff, budget, pk_row, pk_load, pk_node, used, acc);
 }
 // What a round of either form starts with: the prefix of the pending rows' loads per chunk (from *base; nullptr: from 0) and the
 // nodes in the order of their free load.  Returns the chunks, the grid of the form's own fill kernel.

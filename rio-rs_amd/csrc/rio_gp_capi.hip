@@ -551,6 +551,9 @@ struct rio_gp {
     unsigned char* cls_K = nullptr;
     u64 *cls_tab = nullptr, *h_cls = nullptr, *d_cls = nullptr;
     bool cls_ready = false;
+    // rule 13: the immovable classes, one bit per class (rio_gp_set_class_movable); only the rebalance reads them
+    u32 cls_imm[kClsMax / 32] = {};
+    bool cls_any_imm = false;
     bool cls_tab_stale = false;  // a sweep failed where nobody can tell whether k_cls_publish ran: the copies are zeroed on next use
     DevBuf cls_cells;
     std::vector<void*> allocs;
@@ -1935,23 +1938,24 @@ static int rb_plan_ensure(rio_gp* h, const ShPlan& p) {
 
 // R1 behind map / slot_node / slot_free (and, by load, thr): the cut of every slot, the surplus per tile, acc's two surplus
 // words.  fill_cut: cut[] starts as kNone everywhere (the single form; in the session k_shrb_import_* wrote it).
-static int rb_surplus(rio_gp* h, const ShPlan& p, const RbBufs& b, const u32* thr, bool fill_cut) {
+// cls (here and in rb_pack): the immovable classes of rule 13, or nullptr (none; the session of the row-sharded table always)
+static int rb_surplus(rio_gp* h, const ShPlan& p, const RbBufs& b, const u32* thr, bool fill_cut, const ShCls* cls = nullptr) {
     if (int rc = rb_plan_ensure(h, p)) return rc;
     launch_shed_cut(h->assign[h->cur], h->load, h->aff, p, b.map, b.slot_node, b.slot_free, (u64*)h->sh_mat.p, b.cut, thr, fill_cut,
-                    h->stream);
-    launch_shed_count(h->assign[h->cur], h->load, h->aff, p, b.cut, thr, (u32*)h->sh_tile.p, b.acc, h->stream);
+                    h->stream, cls);
+    launch_shed_count(h->assign[h->cur], h->load, h->aff, p, b.cut, thr, (u32*)h->sh_tile.p, b.acc, h->stream, cls);
     HIPCHK(h, hipGetLastError());
     return RIO_GP_OK;
 }
 
 // R2: the first K > 0 surplus rows into the packed columns, in row order; used[] -= their load, acc[kShAccSelectedLoad]
-static int rb_pack(rio_gp* h, const ShPlan& p, const RbBufs& b, const u32* thr, u64 K, u64* used) {
+static int rb_pack(rio_gp* h, const ShPlan& p, const RbBufs& b, const u32* thr, u64 K, u64* used, const ShCls* cls = nullptr) {
     const u64 nc = (K + kShChunk - 1) / kShChunk;
     int rc;
     if ((rc = ensure(h, h->sh_pk, 3 * K * sizeof(u32))) || (rc = ensure(h, h->sh_chunk, nc * sizeof(u64)))) return rc;
     const RbPacked pk = rb_packed(h, K);
     launch_shed_pack(h->assign[h->cur], h->load, h->aff, p, b.cut, thr, (const u32*)h->sh_tile.p, K, pk.row, pk.load, pk.node, used,
-                     b.acc, h->stream);
+                     b.acc, h->stream, cls);
     return RIO_GP_OK;
 }
 
@@ -2007,13 +2011,20 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, const Rb
     if ((rc = rb_ensure(h))) return rc;
     const RbBufs b = rb_bufs(h);
     const u32* const thr = c.order == RIO_GP_REBALANCE_BY_LOAD ? b.thr : nullptr;  // (nullptr: the k_shed_* kernels cut in row order)
+    // rule 13: with an immovable class every table pass runs in its class-aware form (k_shedc_*); without one, as ever
+    ShCls cs{};
+    if (h->cls_any_imm) {
+        cs.K = h->cls_K;  // (rio_gp_set_class_movable made the column)
+        memcpy(cs.imm, h->cls_imm, sizeof cs.imm);
+    }
+    const ShCls* const cls = h->cls_any_imm ? &cs : nullptr;
     // the targets (the capacities by default) and the live nodes
     std::vector<u64> T(m ? m : 1), used(m ? m : 1), pn(m ? m : 1);
     if (cfg->target) memcpy(T.data(), cfg->target, (size_t)m * sizeof(u64));
     else if (m) HIPCHK(h, hipMemcpyAsync(T.data(), h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     // R0: one pass — every node's load (the `used` vector of this column, rebuilt: nothing left to fold) and its pinned load
     u64* const d_used = h->used.storage();
-    launch_shed_hist(h->assign[h->cur], h->load, h->aff, n, m, d_used, b.pin, h->stream);
+    launch_shed_hist(h->assign[h->cur], h->load, h->aff, n, m, d_used, b.pin, h->stream, nullptr, cls);
     HIPCHK(h, hipGetLastError());
     h->used.rebuilt();
     if (m) {
@@ -2045,9 +2056,9 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, const Rb
                     // load): the cut below then falls among those
             if ((rc = ensure(h, h->sh_sel, ((size_t)S << sh_sel_plan(S).bits) * sizeof(u64)))) return rc;
             launch_shed_select(h->assign[h->cur], h->load, h->aff, n, m, S, b.map, b.slot_node, b.slot_free, b.pre, (u64*)h->sh_sel.p,
-                               b.thr, h->stream);
+                               b.thr, h->stream, cls);
         }
-        if ((rc = rb_surplus(h, p, b, thr, true))) return rc;
+        if ((rc = rb_surplus(h, p, b, thr, true, cls))) return rc;
         u64 a[kShAcc];
         HIPCHK(h, hipMemcpyAsync(a, b.acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2061,7 +2072,7 @@ static int rebalance_locked(rio_gp* h, const rio_gp_rebalance_cfg* cfg, const Rb
         return RIO_GP_OK;
     }
     // R2: the first K surplus rows, packed in row order; R3: the water-fill rounds; R4 + the column + the moves
-    if ((rc = rb_pack(h, p, b, thr, K, d_used))) return rc;
+    if ((rc = rb_pack(h, p, b, thr, K, d_used, cls))) return rc;
     const RbPacked pk = rb_packed(h, K);
     for (u32 r = 0; r < c.rounds; ++r)
         launch_shed_round(K, pk.load, pk.node, b.tgt, m, d_used, (u64*)h->sh_chunk.p, b.C, b.ord, b.cntp, h->stream);
@@ -2487,6 +2498,29 @@ int rio_gp_get_classes(rio_gp_t* h, uint64_t n, uint8_t* out) {
     if ((rc = cls_begin(h, "rio_gp_get_classes"))) return rc;
     if (n) HIPCHK(h, hipMemcpyAsync(out, h->cls_K, n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RIO_GP_OK;
+}
+
+// Rule 13.  Like the class setters no input of any solve: no inputs_changed; the rebalance alone reads the table.
+int rio_gp_set_class_movable(rio_gp_t* h, uint32_t n_classes, const uint8_t* movable) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (n_classes > RIO_GP_MAX_CLASSES) return fail(h, RIO_GP_EINVAL, "rio_gp_set_class_movable: n_classes out of range");
+    if (n_classes && !movable) return fail(h, RIO_GP_EINVAL, "rio_gp_set_class_movable: no array");
+    if (int rc = cls_begin(h, "rio_gp_set_class_movable")) return rc;  // (refuses the row-sharded solve; the column, 0 everywhere)
+    u32 imm[kClsMax / 32] = {};
+    bool any = false;
+    for (u32 c = 0; c < n_classes; ++c)
+        if (!movable[c]) { imm[c >> 5] |= 1u << (c & 31); any = true; }
+    memcpy(h->cls_imm, imm, sizeof imm);
+    h->cls_any_imm = any;
+    return RIO_GP_OK;
+}
+
+int rio_gp_get_class_movable(rio_gp_t* h, uint8_t* out256) {
+    if (!h || !out256) return RIO_GP_EINVAL;
+    Locked g(h);
+    for (u32 c = 0; c < kClsMax; ++c) out256[c] = !((h->cls_imm[c >> 5] >> (c & 31)) & 1u);
     return RIO_GP_OK;
 }
 
@@ -3848,6 +3882,10 @@ static int shard_rebalance_begin(rio_gp* h, const char* who, bool ordered, const
     int rc = rb_cfg(h, who, ordered ? RbForm::shard_ordered : RbForm::shard, cfg,
                     !d_x || n_ranks == 0 || rank >= n_ranks ? "rank >= n_ranks, or no record" : nullptr, list_moves != 0, moves_cap, &c);
     if (rc || (rc = may_start(h, Client::shard_rebalance_begin))) return rc;
+    // rule 13: a rank's table has no class column, and moving a protected row is the one wrong answer
+    if (h->cls_any_imm)
+        return fail(h, RIO_GP_EINVAL, std::string(who) + ": the handle names an immovable class (rio_gp_set_class_movable) and the "
+                                                         "row-sharded rebalance has no class column: reset the table first");
     const u32 order = c.order;
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = rb_ensure(h))) return rc;

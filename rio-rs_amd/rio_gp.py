@@ -249,6 +249,9 @@ def _load(lab):
                                            C.POINTER(C.c_uint64), _vp]
             for nm in ("rio_gp_census", "rio_gp_census_dev"):
                 getattr(L, nm).argtypes = [_vp, C.c_uint32, C.c_uint32, _vp, _vp, C.POINTER(C.c_uint64)]
+        if hasattr(L, "rio_gp_set_class_movable"):   # (an older build under RIO_GP_LIB, as above)
+            L.rio_gp_set_class_movable.argtypes = [_vp, C.c_uint32, _vp]
+            L.rio_gp_get_class_movable.argtypes = [_vp, _vp]
         if lab:
             L.rio_gp_debug_set_scan_nt.argtypes = [C.c_int]
             L.rio_gp_debug_set_scan_nt.restype = None
@@ -698,6 +701,28 @@ class GpuPlacement:
         self._chk(self._L.rio_gp_get_classes(self._h, len(out), out.ctypes.data if len(out) else _ptr(np.empty(1, np.uint8))))
         return out
 
+    def set_class_movable(self, movable=None):
+        """rio_gp_set_class_movable: class c is immovable for the rebalance iff movable[c] == 0; the classes from len(movable)
+        on are movable (None or empty: every class is)."""
+        self._chk(self.set_class_movable_raw(movable))
+
+    def set_class_movable_raw(self, movable, n_classes=None):
+        """One rio_gp_set_class_movable call as given (movable: a uint8 array or None): rc; no exception."""
+        mv = None if movable is None else np.ascontiguousarray(movable, np.uint8)
+        k = (0 if mv is None else len(mv)) if n_classes is None else int(n_classes)
+        return self._L.rio_gp_set_class_movable(self._h, k, mv.ctypes.data if mv is not None and len(mv) else None)
+
+    def get_class_movable(self):
+        """rio_gp_get_class_movable: 256 flags (uint8), 1 = the rebalance may move the class's objects."""
+        rc, out = self.get_class_movable_raw()
+        self._chk(rc)
+        return out
+
+    def get_class_movable_raw(self):
+        """One rio_gp_get_class_movable call: (rc, flags); no exception."""
+        out = np.zeros(MAX_CLASSES, np.uint8)
+        return self._L.rio_gp_get_class_movable(self._h, out.ctypes.data), out
+
     def expire_classes(self, cutoffs, cap=None, count_only=False):
         """rio_gp_expire_classes: (rows, nodes, n_idle, load_freed, idle_by_class) — rio_gp_expire with cutoffs[K[r]] as row r's
         cutoff; idle_by_class (uint64, one entry per cutoff) counts every idle row of the class, listed or not."""
@@ -1061,6 +1086,8 @@ def _oplib():
         bind_op_loads(L)
         if hasattr(L, "rio_op_hottest_objects"):   # (as above)
             bind_op_top(L)
+        if hasattr(L, "rio_op_set_type_movable_n"):
+            bind_op_movable(L)
         L.rio_op_dense.argtypes = [_vp]
         L.rio_op_dense.restype = _vp
         L.rio_op_invalidate_cache.argtypes = [_vp]
@@ -1166,6 +1193,17 @@ def op_census(L, h, by_server=False):
         nm = C.cast(names, C.POINTER(_vp))[k]
         out.append((None if not nm else C.string_at(nm, lens[k]), addrs[k].decode() if addrs[k] else None, int(rows[k]), int(loads[k])))
     return rc, out
+
+
+def bind_op_movable(L):
+    """argtypes of rio_op_set_type_movable_n on a library that has it (the product, or a stub-linked test build)."""
+    L.rio_op_set_type_movable_n.argtypes = [_vp, C.c_char_p, C.c_size_t, C.c_int]
+
+
+def op_set_type_movable(L, h, struct_name, movable):
+    """One rio_op_set_type_movable_n call (struct_name: str or bytes, NUL bytes included): rc."""
+    b = struct_name.encode() if isinstance(struct_name, str) else struct_name
+    return L.rio_op_set_type_movable_n(h, b, len(b), 1 if movable else 0)
 
 
 def bind_op_loads(L):
@@ -1440,6 +1478,10 @@ class GpuObjectPlacement:
         rc, out, idle = op_expire(_oplib(), self._h, cutoff, max_objects)
         self._chk(rc)
         return out, idle
+
+    def set_type_movable(self, struct_name, movable):
+        """rio_op_set_type_movable_n: movable=False — rebalance() leaves the keys of this type where they are."""
+        self._chk(op_set_type_movable(_oplib(), self._h, struct_name, movable))
 
     def set_type_idle_limit(self, struct_name, max_idle):
         """rio_op_set_type_idle_limit_n: keys of this type are idle after max_idle epochs without a stamp (IDLE_NEVER: never)."""

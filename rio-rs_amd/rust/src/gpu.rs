@@ -105,6 +105,7 @@ extern "C" {
     fn rio_op_expire_by_type(p: *mut c_void, now: u32, default_max_idle: u32, max_objects_out: u64, n_out: *mut u64,
                              n_idle: *mut u64, tys: *mut *const *const c_char, ty_lens: *mut *const usize,
                              ids: *mut *const *const c_char, id_lens: *mut *const usize, addrs: *mut *const *const c_char) -> c_int;
+    fn rio_op_set_type_movable_n(p: *mut c_void, ty: *const c_char, ty_len: usize, movable: c_int) -> c_int;
     fn rio_op_set_load_tracking(p: *mut c_void, on: c_int) -> c_int;
     fn rio_op_fold_loads(p: *mut c_void, keep: u32, gain: u32, min_load: u32, max_load: u32, rows_changed: *mut u64,
                          hits_folded: *mut u64) -> c_int;
@@ -350,6 +351,15 @@ impl GpuObjectPlacement {
     /// a type past the first 255 the layer has seen: those share one class and the sweep's default.
     pub fn set_type_idle_limit(&self, struct_name: &str, max_idle: u32) -> Result<(), ObjectPlacementError> {
         check(unsafe { rio_op_set_type_idle_limit_n(self.inner.0, struct_name.as_ptr() as *const c_char, struct_name.len(), max_idle) },
+              self)
+    }
+
+    /// `movable = false`: `rebalance` and `rebalance_ordered` leave the objects of this type where they are (Orleans'
+    /// `[Immovable]`); their load still counts against their server's capacity.  RIO_GP_ERANGE for a type past the first 255
+    /// the layer has seen: those share one class, which is always movable.
+    pub fn set_type_movable(&self, struct_name: &str, movable: bool) -> Result<(), ObjectPlacementError> {
+        check(unsafe { rio_op_set_type_movable_n(self.inner.0, struct_name.as_ptr() as *const c_char, struct_name.len(),
+                                                 movable as c_int) },
               self)
     }
 
