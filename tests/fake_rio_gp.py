@@ -2,7 +2,8 @@
 the CPU oracle (oracle/pyoracle.py), tests/rebalance_ref.py, tests/rebalance_order_ref.py, tests/spec_changes.py, tests/spec_remap.py
 and tests/spec_top.py; idle expiry and measured load (the hit column and the fold, in uint64: the scenarios hold them against
 tests/spec_loads.py's Python integers) and object classes (the class column, the per-class sweep and the census, which the scenarios
-hold against tests/spec_classes.py) are restated here in plain numpy.  It lets the fuzz driver itself be tested
+hold against tests/spec_classes.py) are restated here in plain numpy; the table of immovable classes goes into the rebalance through
+the equivalence rule 13 states (the affinity of the immovable rows read as RIO_GP_AFF_INACTIVE).  It lets the fuzz driver itself be tested
 without a GPU (tests/test_fuzz_driver.py): its bookkeeping (n, the feed's checkpoint, the mirror, the uncommitted solve) and its
 sensitivity — `fault=` makes exactly one behaviour of the handle wrong, and the scenarios must notice.
 
@@ -47,7 +48,7 @@ FAULTS = (
     "remap_counts_hidden_rows",    # a node removal counts the rows >= n it un-places as evicted
     "remap_checkpoint_none_not_gone",   # a checkpoint naming a removed node becomes NONE, not RIO_GP_NODE_GONE
     "remap_stale_node_table",      # a node removal leaves cap and alive at their old ids
-    "remap_affinity_not_renumbered",    # the committed ticks read the affinity of before the removal (the getter does not)
+    "remap_affinity_not_renumbered",    # the synchronous committed ticks read the affinity of before the removal (the getter does not)
     "expire_cutoff_inclusive",     # a row stamped exactly at the cutoff is idle
     "expire_unplaces_past_cap",    # a sweep un-places every idle row, not only the listed ones
     "expire_lists_hidden_rows",    # a sweep finds rows >= n idle
@@ -103,6 +104,19 @@ FAULTS = (
     "census_dev_adds",             # the _dev census adds to what the arrays held
     "census_drops_solve",          # the census drops an uncommitted solve
     "census_skips_zero_load_rows", # a row of load 0 is left out of out_rows
+    "movable_ignored",             # the rebalance does not consult the table of immovable classes
+    "movable_pinned_load_not_counted",  # immovable rows are no candidates, but their load does not count against the target
+    "movable_counts_as_surplus",   # immovable rows are never moved, but surplus_rows / surplus_load count them
+    "movable_class_255_always_movable",      # the rebalance treats class 255 as movable whatever the table says
+    "movable_stale_classes",       # the rebalance reads the class column as it was at the last rio_gp_set_class_movable
+    "movable_writes_affinity",     # the rebalance leaves RIO_GP_AFF_INACTIVE in the affinity column of the immovable rows
+    "movable_hidden_quad",         # the immovable rows of the quad behind n count as pinned load of their node
+    "rebalance_resets_movable",    # a rebalance under a table resets it
+    "movable_short_table_keeps_old_flags",   # a table of n_classes flags leaves the classes >= n_classes as they were
+    "movable_refused_still_sets",  # a refused rio_gp_set_class_movable writes the table all the same
+    "movable_drops_solve",         # rio_gp_set_class_movable drops an uncommitted solve
+    "remap_resets_movable",        # a node removal resets the table of immovable classes
+    "num_objects_resets_movable",  # set_num_objects resets the table of immovable classes
 )
 
 
@@ -192,6 +206,8 @@ class GpuPlacement:
         self._S = np.zeros(self._cap_rows, np.uint32)
         self._H = np.zeros(self._cap_rows, np.uint32)
         self._K = np.zeros(self._cap_rows, np.uint8)
+        self._I = np.ones(MAX_CLASSES, np.uint8)  # rule 13: 1 = the rebalance may move the class's objects
+        self._K_at_I = self._K.copy()             # (fault movable_stale_classes: the column at the last set_class_movable)
         self._by_acc = np.zeros(256, np.uint64)  # (fault expc_by_class_accumulates: what the sweeps so far counted)
         self._pos_dirty = None                    # (fault classes_batch_dirty_pos: the rows the last class batch named)
         self._chain_ok, self._chained = False, 0  # lab: nothing a tick reads has changed since the last tick_async; links so far
@@ -286,6 +302,8 @@ class GpuPlacement:
         self._changed()
         if self._fault == "num_objects_clears_classes":
             self._K[:] = 0
+        if self._fault == "num_objects_resets_movable":
+            self._I[:] = 1
         if self._fault == "num_objects_stale_used":
             self._stale_used = before
 
@@ -397,7 +415,9 @@ class GpuPlacement:
         # a quiet tick behind a quiet tick is a link of a chain (the lab build chains whatever the table's size): the stand-in
         # has no verdicts to wait for, so every tick_async behind one with nothing changed in between counts
         self._chained += int(self._lab and self._chain_ok)
-        self._done.append(self.tick())
+        st = self.solve()      # (not tick(): the fault remap_affinity_not_renumbered is one of the synchronous tick alone)
+        self.commit()
+        self._done.append(st)
         self._chain_ok = True
 
     def tick_wait(self, cap=4096):
@@ -432,6 +452,8 @@ class GpuPlacement:
             self._S[:n] = 0
         if f == "remap_clears_classes":
             self._K[:n] = 0
+        if f == "remap_resets_movable":
+            self._I[:] = 1
         return OK, out["evicted"]
 
     def remap_nodes(self, map):
@@ -499,17 +521,50 @@ class GpuPlacement:
         alive = self._alive_seen if f == "rebalance_stale_alive" and len(self._alive_seen) == self._m else self._alive
         before = self.get_nodes()[2]
         solved = self._solved
-        if order == REBALANCE_BY_LOAD and f != "by_load_is_row_order":
-            r, perm = np.arange(len(col)), None
-            if f == "by_load_ties_shed_first_rows":
-                perm = np.lexsort((-r, load))
-            elif f == "by_load_sheds_zero_load":
-                perm = np.lexsort((r, load, load == 0))
-            nxt, used, st, rows, frm, to = rebalance_order_ref.rebalance(col, load, aff, self._cap, alive, target, budget,
-                                                                         rounds or self._rounds, order=order, perm=perm)
-        else:
-            nxt, used, st, rows, frm, to = rebalance_ref.rebalance(col, load, aff, self._cap, alive, target, budget,
-                                                                   rounds or self._rounds)
+        n, m = self._n, self._m
+        # rule 13 through the equivalence it states: rule 6 with the affinity of every immovable object row read as INACTIVE
+        I = self._I.copy()
+        if f == "movable_class_255_always_movable":
+            I[255] = 1
+        K = self._K_at_I if f == "movable_stale_classes" else self._K
+        imm = (I[K[:n]] == 0) & (f != "movable_ignored")
+        tabled = bool(imm.any())
+        if tabled:
+            aff = np.where(imm, np.uint32(AFF_INACTIVE), aff)
+        if f == "movable_pinned_load_not_counted" and tabled:
+            on = imm & (col < m)
+            extra = np.zeros(m, np.uint64)
+            np.add.at(extra, col[on].astype(np.int64), load[on].astype(np.uint64))
+            T = np.array(self._cap if target is None else target, np.uint64)
+            target = np.where(T > np.uint64(CAP_INF) - extra, np.uint64(CAP_INF), T + extra)
+        n4 = min(-(-n // 4) * 4, self._cap_rows)
+        if f == "movable_hidden_quad" and n4 > n and (I[self._K[n:n4]] == 0).any():
+            # the rows of the quad behind n: the immovable ones are pinned load, the others take no part
+            hid = I[self._K[n:n4]] == 0
+            col = np.concatenate([col, np.where(hid, self._col[n:n4], np.uint32(NONE))])
+            load = np.concatenate([load, self._load[n:n4]])
+            aff = np.concatenate([aff, np.full(n4 - n, AFF_INACTIVE, np.uint32)])
+
+        def run(col, aff, budget):
+            if order == REBALANCE_BY_LOAD and f != "by_load_is_row_order":
+                r, perm = np.arange(len(col)), None
+                if f == "by_load_ties_shed_first_rows":
+                    perm = np.lexsort((-r, load))
+                elif f == "by_load_sheds_zero_load":
+                    perm = np.lexsort((r, load, load == 0))
+                return rebalance_order_ref.rebalance(col, load, aff, self._cap, alive, target, budget, rounds or self._rounds,
+                                                     order=order, perm=perm)
+            return rebalance_ref.rebalance(col, load, aff, self._cap, alive, target, budget, rounds or self._rounds)
+
+        nxt, used, st, rows, frm, to = run(col, aff, budget)
+        if f == "movable_counts_as_surplus" and tabled:
+            st0 = run(col, self._aff[:n], 0)[2]
+            st = dict(st, surplus_rows=st0["surplus_rows"], surplus_load=st0["surplus_load"])
+        if f == "movable_writes_affinity" and tabled:
+            self._aff[:n] = aff[:n]
+        if f == "rebalance_resets_movable":
+            self._I[:] = 1
+        nxt, col = nxt[:n], self._col[:n]
         col[:] = nxt
         self._changed()
         if self._fault == "rebalance_keeps_solve":
@@ -725,6 +780,36 @@ class GpuPlacement:
 
     def get_classes(self):
         return self._K[:self._n].copy()
+
+    # ---- immovable classes (rule 13)
+    def set_class_movable_raw(self, movable, n_classes=None):
+        mv = None if movable is None or not len(movable) else np.asarray(movable, np.uint8)
+        k = (0 if mv is None else len(mv)) if n_classes is None else int(n_classes)
+        f = self._fault
+        if k > MAX_CLASSES or (k and mv is None):
+            if f == "movable_refused_still_sets":
+                self._I[:] = 1
+                if mv is not None:
+                    self._I[:] = mv[:MAX_CLASSES] != 0
+            return EINVAL
+        if f != "movable_short_table_keeps_old_flags":
+            self._I[:] = 1
+        if k:
+            self._I[:k] = mv[:k] != 0
+        self._K_at_I = self._K.copy()
+        if f == "movable_drops_solve":
+            self._changed()
+        return OK
+
+    def set_class_movable(self, movable=None):
+        if self.set_class_movable_raw(movable) != OK:
+            raise _einval("rio_gp_set_class_movable")
+
+    def get_class_movable_raw(self):
+        return OK, self._I.copy()
+
+    def get_class_movable(self):
+        return self._I.copy()
 
     def _expire_classes(self, cutoffs, cap):
         """cap None: count only.  -> rows, nodes, n_idle, load_freed, idle_by_class"""

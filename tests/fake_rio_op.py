@@ -1,6 +1,7 @@
 """A plain-Python stand-in for the string layer (rio_op_*, rio-rs_amd/csrc/gpu_object_placement.cpp), FOR TESTS ONLY: what
 include/rio_gpu_object_placement.h documents, over a row-lifecycle dense table built on tests/fake_rio_gp.py — a dict interner,
-lazy reclaim when the table runs full, rows kept for rio_op_set_object_load, a host shadow by stamp, the feed's retired rows.
+lazy reclaim when the table runs full, rows kept for rio_op_set_object_load, a host shadow by stamp, the feed's retired rows,
+the flags of immovable types and their lazy upload ahead of a rebalance.
 It lets tests/op_layer_driver.py be tested without a GPU (tests/test_op_layer_driver.py): `fault=` makes exactly one behaviour
 wrong, and the driver must notice.  It is not a CPU backend: nothing under rio-rs_amd/ imports it.
 
@@ -62,6 +63,15 @@ FAULTS = (
     "census_lists_empty_cells",    # census by server lists the empty cells of the types a server does not hold
     "census_names_shared_class",   # the shared class comes with a name
     "expire_by_type_keeps_shadow_entry",   # a per-type sweep leaves the shadow's answer for the keys it listed
+    # immovable types
+    "movable_classes_not_uploaded",   # a rebalance with an immovable type sends the table, the classes that changed it does not
+    "movable_table_uploaded_once",    # the table goes to the dense layer the first time only: later changes of a flag stay on the host
+    "movable_never_reset",         # after the last immovable type became movable again the dense table is left as it was
+    "movable_flag_per_clone",      # a flag set through one clone does not reach a rebalance made through the other
+    "movable_other_class_accepted",   # a type in the shared class is accepted: the shared class becomes immovable
+    "movable_unseen_type_not_numbered",   # the call does not number a type never seen before (and drops its flag)
+    "movable_ordered_call_ignores",   # rio_op_rebalance_ordered runs without the table
+    "movable_upload_clears_sweep_state",   # after a rebalance's class upload the next per-type sweep runs on the classes of before it
 )
 
 
@@ -154,7 +164,7 @@ class FakeObjectPlacement:
     def __init__(self, max_objects, max_nodes=32, spill_rounds=2, flags=0, fault=None, _s=None):
         if _s is not None:
             self.s = _s
-            self.own_now, self.own_track = 0, False
+            self.own_now, self.own_track, self.own_imm = 0, False, {}
             return
         assert fault is None or fault in FAULTS, fault
         s = self.s = _State()
@@ -176,7 +186,9 @@ class FakeObjectPlacement:
         s.track, s.hits = False, np.zeros(s.max_objects, np.uint64)  # the tracking switch the clones share; one counter per row
         # struct_name -> class in the order of interning, limit by class, the class of every row, and what the device holds of it
         s.types, s.type_names, s.type_limit, s.row_class, s.cls_uploaded, s.cls_dirty = {}, [], {}, [], 0, []
-        self.own_now, self.own_track = 0, False
+        # immovable types: the flag by class, whether the table changed since its last upload, whether the dense layer holds one
+        s.type_imm, s.mv_dirty, s.mv_on_device, s.mv_sent, s.stale_cls = {}, False, False, False, None
+        self.own_now, self.own_track, self.own_imm = 0, False, {}
 
     def clone(self):
         return FakeObjectPlacement(0, _s=self.s)
@@ -279,6 +291,48 @@ class FakeObjectPlacement:
         if s.cls_dirty:
             s.g.set_class_batch(s.cls_dirty, [s.row_class[r] for r in s.cls_dirty])
             s.cls_dirty = []
+
+    # ---- immovable types
+    def set_type_movable(self, ty, movable):
+        s = self.s
+        if s.fault == "movable_unseen_type_not_numbered" and ty not in s.types:
+            return OK
+        c = self._type(ty)
+        if c == 255 and s.fault != "movable_other_class_accepted":
+            return ERANGE
+        flags = self.own_imm if s.fault == "movable_flag_per_clone" else s.type_imm
+        imm = not movable
+        if bool(flags.get(c, False)) != imm:
+            flags[c] = imm
+            s.mv_dirty = True
+        return OK
+
+    def _sync_movable(self, ordered):
+        """Ahead of a dense rebalance: with an immovable type the classes that changed and, if it changed, the table; without
+        one nothing, except the one reset after the last immovable type became movable again."""
+        s = self.s
+        flags = self.own_imm if s.fault == "movable_flag_per_clone" else s.type_imm
+        imm = sorted(c for c, on in flags.items() if on)
+        if s.fault == "movable_flag_per_clone":
+            s.mv_dirty = True          # (each clone sends its own table)
+        if ordered and s.fault == "movable_ordered_call_ignores":
+            imm, s.mv_dirty = [], True
+        if imm:
+            before = s.g.get_classes() if s.fault == "movable_upload_clears_sweep_state" else None
+            if s.fault != "movable_classes_not_uploaded":
+                self._sync_classes()
+            if before is not None and not np.array_equal(before, s.g.get_classes()[:len(before)]):
+                s.stale_cls = before
+            if s.mv_dirty and not (s.fault == "movable_table_uploaded_once" and s.mv_sent):
+                table = np.ones(256, np.uint8)
+                table[imm] = 0
+                s.g.set_class_movable(table)
+                s.mv_dirty, s.mv_on_device, s.mv_sent = False, True, True
+        elif s.mv_on_device:
+            if s.fault != "movable_never_reset":
+                s.g.set_class_movable(None)
+            s.mv_on_device = False
+            s.mv_dirty = s.mv_dirty and s.fault == "movable_ordered_call_ignores"
 
     def set_type_idle_limit(self, ty, max_idle):
         s = self.s
@@ -453,6 +507,9 @@ class FakeObjectPlacement:
         self._sync()
         if by_type:
             self._sync_classes()
+            if s.stale_cls is not None:      # (fault movable_upload_clears_sweep_state)
+                s.g.set_classes(0, s.stale_cls)
+                s.stale_cls = None
         n = len(s.row_key)
         cap = n if max_objects is None else min(int(max_objects), n)
         if s.stamps.any() and not (cap == 0 and s.fault == "stamps_not_uploaded_on_count_only"):
@@ -819,6 +876,7 @@ class FakeObjectPlacement:
     def rebalance(self, max_moves=None, mid=None, order=None):
         """order None: rio_op_rebalance; else rio_op_rebalance_ordered with that order."""
         s = self.s
+        ordered = order is not None
         order = 0 if order is None else int(order)
         if order not in (0, 1):
             if s.fault != "invalid_order_runs_row_order":
@@ -827,6 +885,7 @@ class FakeObjectPlacement:
         if s.fault == "by_load_runs_row_order":
             order = 0
         self._sync()
+        self._sync_movable(ordered)
         cap = min(CAP_INF if max_moves is None else int(max_moves), len(s.row_key))
         _, rows, frm, to = s.g.rebalance(None, cap, 0, moves_cap=cap, order=order)
         if s.fault != "rebalance_keeps_shadow":

@@ -36,6 +36,19 @@ whatever becomes of the call); rio_op_expire_by_type is tests/spec_classes.py un
 census with 256 classes, and after each of the two rio_gp_get_classes on the dense handle equals the model's class column on
 every row whose key the model knows.
 
+Immovable types are part of the sequence as well.  The model keeps one flag per struct_name; rio_op_set_type_movable_n goes through
+either clone with the type of a placed key, any known type, one never seen (it gets its class by the call, so the order of
+interning follows, and the census order checks that; its first key may come with the very next call) or, past 255 types, one that
+lands in RIO_OP_CLASS_OTHER (RIO_GP_ERANGE, nothing set), and a flag that repeats or takes back what the type holds.  While a type
+is immovable a rebalance — made through the clone the last flag did not go through — is tests/spec_movable.py over the dense
+state read before the call, the model's own class column and the table built from the model's flags (up to 4 096 rows the
+vectorised reference on the affinity with RIO_GP_AFF_INACTIVE on the immovable rows must agree first); the moves are compared key
+for key, and afterwards rio_gp_get_class_movable on the dense handle is the model's table, rio_gp_get_classes the model's class
+column on every row whose key the model knows (the rebalance has uploaded what changed, as a per-type sweep would have: the sweep
+that sometimes follows at once must agree), and the keys of the immovable types answer from their old address through both clones.
+Once the last immovable type is movable again the next rebalance is the plain reference and leaves the dense table all 1.  Every
+other call treats the keys as before: ticks, clean_server, the sweeps, removal and the census are compared as they always were.
+
 The provider under test is given as make(max_objects, max_nodes, spill_rounds, flags): RealProvider.make over rio_gp (the GPU
 test, tests/test_gpu_op_layer_fuzz.py) or tests/fake_rio_op.py (the driver's own test, tests/test_op_layer_driver.py).
 """
@@ -108,6 +121,17 @@ FLOOR = (
     "a per-type sweep between two feed reads",
     "census by server with a server seen only through update",
     "census listed the shared class",
+    # immovable types
+    "a rebalance left a key of an immovable type on an over-capacity server and moved another",
+    "a by-load rebalance with an immovable type moved keys",
+    "a row changed hands to a key of an immovable type between two rebalances",
+    "a rebalance did the class upload a per-type sweep would have done, and the sweep right after it agreed",
+    "a type was made immovable before its first key",
+    "set_type_movable refused with ERANGE",
+    "the last immovable type became movable again and the next rebalance moved its keys",
+    "a flag set through one clone held in a rebalance through the other",
+    "tick or clean_server removed keys of an immovable type",
+    "a sweep listed a key of an immovable type",
 )
 
 SIZES = ("tiny", "tiny", "edge", "tiny", "4096", "bulk")      # by seed % 6
@@ -334,6 +358,9 @@ class RealProvider:
     def set_type_idle_limit(self, ty, max_idle):
         return int(self.gp.op_set_type_idle_limit(self.L, self.p._h, ty, max_idle))
 
+    def set_type_movable(self, ty, movable):
+        return int(self.gp.op_set_type_movable(self.L, self.p._h, ty, movable))
+
     def expire_by_type(self, now, default_max_idle, max_objects=None, mid=None):
         """-> (rc, [(struct_name, object_id, address or None)], n_idle)"""
         gp = self.gp
@@ -377,7 +404,7 @@ class Scenario:
            ("set_object_load", 3), ("tick", 3), ("rebalance", 4), ("changes", 5), ("changes_reset", 1), ("invalidate_cache", 1),
            ("objects_on_server", 2), ("snapshot", 2), ("len", 1), ("set_clock", 4), ("expire", 4),
            ("set_load_tracking", 2), ("fold_loads", 4), ("get_object_load", 2), ("hottest_objects", 3),
-           ("set_type_idle_limit", 2), ("expire_by_type", 3), ("census", 2))
+           ("set_type_idle_limit", 2), ("expire_by_type", 3), ("census", 2), ("set_type_movable", 4))
 
     def __init__(self, make, oracle, seed, steps=None):
         self.oracle, self.seed = oracle, seed
@@ -442,6 +469,14 @@ class Scenario:
         self.K = np.zeros(self.rows_max, np.uint8)
         self.cls_up, self.cls_scatter, self.cls_handed, self.cls_early = 0, set(), {}, False
         self.seen_by = {}                 # address -> the kinds of call that carried it
+        # immovable types: struct_name -> immovable, the clone the last flag went through, the types flagged before their first
+        # key, whether the dense table holds a flag (and of which classes), the rows handed to a new key since the last rebalance,
+        # and whether the rebalance of the step before uploaded classes
+        self.immovable, self.mv_clone, self.early_imm = {}, None, set()
+        self.mv_dev, self.was_imm = False, set()
+        self.handed_since_reb = set()
+        self.reb_upload_step = None
+        self.force_key = None
 
     # ---- small helpers ------------------------------------------------------------------------------------------------
     def fail(self, what, *more):
@@ -474,6 +509,9 @@ class Scenario:
 
     def pick_key(self, known=0.6):
         rng = self.rng
+        if self.force_key is not None:      # (the first key of a type that has just been made immovable)
+            key, self.force_key = self.force_key, None
+            return key
         if self.keys and rng.random() < known:
             ks = list(self.keys.values())
             k = ks[int(rng.integers(len(ks)))]
@@ -630,6 +668,7 @@ class Scenario:
             self.own.discard(r)
             self.hit("an expired key's row was handed to a new key before the next feed read", r in self.expired_since_feed)
             self.cls_handed[r] = self.cls_handed.get(r, 0) + 1
+            self.handed_since_reb.add(r)
             if r >= self.cls_up:
                 self.cls_early = True
             elif c != int(self.K[r]):
@@ -648,6 +687,10 @@ class Scenario:
 
     def cls_of(self, ty):
         return self.types.get(ty, CLASS_OTHER)
+
+    def imm_classes(self):
+        """The classes of the types that are immovable now."""
+        return set(self.types[ty] for ty, on in self.immovable.items() if on)
 
     # ---- the stamping rule (include/rio_gpu_object_placement.h, "idle deactivation") ------------------------------------------
     def stamp(self, key, shadow=False):
@@ -741,6 +784,10 @@ class Scenario:
                 exp[k.row] = nd
             if k is not None and k.row is None:
                 k.obj = self.extra_obj.get(ks, k.obj)
+        if what in ("tick", "clean_server") and self.imm_classes():
+            nb, imm = before["n"], self.imm_classes()
+            left = np.flatnonzero((before["col"] != NONE) & (after["col"][:nb] != before["col"]))
+            self.hit("tick or clean_server removed keys of an immovable type", any(int(self.K[r]) in imm for r in left))
         bad = np.flatnonzero(after["col"] != exp)
         self.want(bad.size == 0, what + ": the dense column differs from the reference's", bad[:8], after["col"][bad[:8]], exp[bad[:8]])
         self.check_nodes_and_load(before, after, what)
@@ -798,6 +845,8 @@ class Scenario:
         idx, col, load, extra = self.virtual(st, [key])
         if a is not None or self.kstr(key) in self.keys:
             self.want(self.oracle.update_batch(col, len(self.addr), idx, [NONE if a is None else self.aid[a]]) == 0, "reference refused")
+        if a is None and self.kstr(key) in self.keys and self.keys[self.kstr(key)].row is None:
+            self.extra_obj[self.kstr(key)] = False      # Option::None is a remove: a key whose row is unknown is no object after it
         self.ref_key(key)
         if self.ref_on:
             self.ref[0].update(key[0], key[1], a)
@@ -836,6 +885,10 @@ class Scenario:
         nodes = [NONE if addrs[q] is None else self.aid[addrs[q]] for q in sel]
         if sel:
             self.want(self.oracle.update_batch(col, len(self.addr), idx, nodes) == 0, "reference refused")
+        for q in sel:              # the last entry of a key whose row is unknown is a remove: the key is no object after the batch
+            k = self.keys.get(self.kstr(keys[q]))
+            if k is not None and k.row is None:
+                self.extra_obj[self.kstr(keys[q])] = False if addrs[q] is None else self.extra_obj.get(self.kstr(keys[q]), k.obj)
         for k in keys:
             self.ref_key(k)
         if self.ref_on:
@@ -1151,6 +1204,8 @@ class Scenario:
         """rio_op_rebalance, or rio_op_rebalance_ordered in row order, by load or with an order that does not exist."""
         import rebalance_ref
         p, other = self.h()
+        if self.mv_clone is not None and self.imm_classes():     # a flag set through one clone, the rebalance through the other
+            p, other = self.handles[1 - self.mv_clone], self.handles[self.mv_clone]
         rng = self.rng
         st = self.begin()
         for ks in list(self.keys)[:6]:           # (the shadow holds answers a rebalance must void)
@@ -1173,7 +1228,11 @@ class Scenario:
         self.ref_on = False
         cap, alive = self.node_arrays()
         budget = min(INF if mm is None else mm, st["n"])
-        if st["n"] and len(self.addr) and order == BY_LOAD:
+        imm = self.imm_classes()
+        self.check_movable_table(imm, "rebalance")      # (before the max_moves 0 call below goes through the same upload)
+        if imm and st["n"] and len(self.addr):
+            nxt, rows, frm, to = self.rebalance_immovable(st, imm, cap, alive, budget, order, after_fold)
+        elif st["n"] and len(self.addr) and order == BY_LOAD:
             import rebalance_order_ref
             import spec_rebalance_order
             L = lambda a: [int(x) for x in a]
@@ -1208,7 +1267,77 @@ class Scenario:
             self.want(rc == OK and none == [], "rebalance with max_moves 0 after an ordered one", rc, none[:2])
         after = self.settle(st, nxt, [], "rebalance")
         self.probe(after, [self.row2key[int(r)] for r in rows[:4]])
+        if imm:
+            # the rebalance has uploaded the classes that changed, as a per-type sweep would have; the keys of the immovable
+            # types are where they were, through both clones
+            self.reb_upload_step = self.step if self.g.num_objects > self.cls_up or self.cls_scatter else None
+            self.class_upload("rebalance")
+            held = [int(r) for r in np.flatnonzero(st["col"] != NONE) if int(self.K[r]) in imm]
+            self.want(all(after["col"][r] == st["col"][r] for r in held), "rebalance moved a key of an immovable type")
+            self.probe(after, [self.row2key[held[int(rng.integers(len(held)))]] for _ in range(3)] if held else [])
+        elif self.was_imm:
+            self.hit("the last immovable type became movable again and the next rebalance moved its keys",
+                     any(int(self.K[int(r)]) in self.was_imm for r in rows))
+            self.was_imm = set()
+        self.check_movable_table(imm, "after rebalance")
+        self.handed_since_reb = set()
         return after
+
+    def check_movable_table(self, imm, what):
+        """rio_gp_get_class_movable on the dense handle after a rebalance: the model's table while a type is immovable, all 1
+        from the first rebalance after the last one became movable again (and before the first flag)."""
+        got = self.g.get_class_movable()
+        want = np.ones(spec_classes.MAX_CLASSES, np.uint8)
+        want[sorted(imm)] = 0
+        self.want(np.array_equal(got, want), what + ": the dense table of immovable classes differs from the model's",
+                  np.flatnonzero(got != want)[:8], sorted(imm)[:8])
+        if imm:
+            self.mv_dev, self.was_imm = True, set(imm)
+        else:
+            self.mv_dev = False
+
+    def rebalance_immovable(self, st, imm, cap, alive, budget, order, after_fold):
+        """A rebalance while a type is immovable: tests/spec_movable.py over the dense state read before the call, the model's own
+        class column and the table built from the model's flags (up to 4 096 rows the vectorised reference on the affinity with
+        RIO_GP_AFF_INACTIVE on the immovable rows must agree first).  -> (next column, rows, from, to)"""
+        import rebalance_order_ref
+        import rebalance_ref
+        import spec_movable
+        n, col, load, aff = st["n"], st["col"], st["load"], st["aff"]
+        L = lambda a: [int(x) for x in a]
+        table = [0 if c in imm else 1 for c in range(spec_classes.MAX_CLASSES)]
+        K = self.K[:n]
+        o = BY_LOAD if order == BY_LOAD else ROW_ORDER
+        pinned = np.array([int(c) in imm for c in K], bool)
+        aff_t = np.where(pinned, np.uint32(AFF_INACTIVE), aff)
+        if n <= 4096:
+            if o == BY_LOAD:
+                r = rebalance_order_ref.rebalance(col, load, aff_t, cap, alive, None, budget, self.rounds, order=BY_LOAD)
+            else:
+                r = rebalance_ref.rebalance(col, load, aff_t, cap, alive, None, budget, self.rounds)
+        s_nxt, _, _, s_moves = spec_movable.rebalance(L(col), L(load), L(aff), L(K), table, L(cap), L(alive), None, budget, self.rounds, o)
+        if n <= 4096:
+            self.want(s_nxt == L(r[0]) and s_moves == [(int(a), int(b), int(c)) for a, b, c in zip(r[3], r[4], r[5])],
+                      "the two immovable rebalance references differ")
+        rows, frm, to = ([m[q] for m in s_moves] for q in range(3))
+        # the same call without the table: what it would have moved (for the coverage counters only)
+        plain = spec_movable.rebalance(L(col), L(load), L(aff), L(K), [1] * spec_classes.MAX_CLASSES, L(cap), L(alive), None, budget,
+                                       self.rounds, o)[3]
+        used = self.oracle.recompute_used(col, load, len(cap))
+        placed = np.flatnonzero(col != NONE)
+        over = set(j for j in range(len(cap)) if alive[j] and int(used[j]) > int(cap[j]))
+        kept_on = set(int(col[r]) for r in placed if pinned[r]) & over
+        self.hit("a rebalance left a key of an immovable type on an over-capacity server and moved another", any(f in kept_on for f in frm))
+        self.hit("a by-load rebalance with an immovable type moved keys", o == BY_LOAD and len(rows) > 0)
+        self.hit("a by-load rebalance moved keys", o == BY_LOAD and len(rows) > 0)
+        self.hit("a by-load rebalance right after a fold", o == BY_LOAD and after_fold)
+        self.hit("a row changed hands to a key of an immovable type between two rebalances",
+                 any(pinned[r] and col[r] != NONE for r in self.handed_since_reb if r < n))
+        self.hit("a type was made immovable before its first key",
+                 any(pinned[r] and self.keys[self.row2key[int(r)]].ty in self.early_imm for r in placed))
+        self.hit("a flag set through one clone held in a rebalance through the other",
+                 self.mv_clone is not None and any(pinned[m[0]] for m in plain))
+        return np.array(s_nxt, np.uint32), rows, frm, to
 
     def op_changes(self):
         p, other = self.h()
@@ -1366,7 +1495,11 @@ class Scenario:
         self.want(got == want, "expire: the listing is not the reference's, key for key in row order", cutoff, cap, got[:4], want[:4])
         self.want(got_idle == w_idle, "expire: n_idle", got_idle, w_idle)
         L = len(rows)
+        imm = self.imm_classes()
+        self.hit("a sweep listed a key of an immovable type", any(int(self.K[r]) in imm for r in rows))
         if by_type:
+            self.hit("a rebalance did the class upload a per-type sweep would have done, and the sweep right after it agreed",
+                     self.reb_upload_step is not None and self.reb_upload_step == self.step - 1)
             self.note_type_sweep(st, placed, set(int(r) for r in idle_rows), rows, cutoffs, now, dflt)
         else:
             live = [r for r in placed if int(self.S[r]) >= cutoff]
@@ -1478,6 +1611,52 @@ class Scenario:
             self.want(rc == ERANGE, "set_type_idle_limit of a type in the shared class", rc, ty)
             self.hit("a type limit refused with ERANGE")
         self.unchanged(st, "set_type_idle_limit")
+
+    def op_set_type_movable(self):
+        """rio_op_set_type_movable_n through either clone: the type of a placed key, any known type, one never seen (it gets its
+        class by this call) or — past 255 types — one that lands in the shared class (RIO_GP_ERANGE, nothing set); the flag is drawn,
+        repeats included.  The call only notes the flag: the table, the feed and the node table are as they were."""
+        p, other = self.h()
+        rng = self.rng
+        kind = 2 if self.many_types and rng.random() < 0.4 else int(rng.integers(4))
+        st = self.begin()
+        placed = [int(r) for r in np.flatnonzero(st["col"] != NONE)]
+        known = list(self.types)
+        if kind == 0 and placed:
+            ty = self.keys[self.row2key[placed[int(rng.integers(len(placed)))]]].ty
+        elif kind == 1 and known:
+            ty = known[int(rng.integers(len(known)))]
+        elif kind == 2:
+            ty = self.pool[int(rng.integers(len(self.pool)))][0]
+            late = sorted(set(t for t, _ in self.pool if t not in self.types)) if self.many_types else []
+            if late:                                      # a type of the pool that has no class yet: past 255 types it never will
+                ty = late[int(rng.integers(len(late)))]
+        else:
+            ty = "M%d\0%d" % (self.seed, self.step) if rng.random() < 0.3 else "M%d.%d" % (self.seed, self.step)      # a new type
+            unseen = [k for k in self.pool if k[0] not in self.types]
+            if unseen and rng.random() < 0.6:             # ... or one of the pool's, whose first key comes with the next call
+                self.force_key = unseen[int(rng.integers(len(unseen)))]
+                ty = self.force_key[0]
+        if self.immovable and rng.random() < 0.25:       # a flag some type holds already, given again or taken back
+            ty, self.force_key = list(self.immovable)[int(rng.integers(len(self.immovable)))], None
+        movable = bool(rng.random() < (0.6 if self.immovable.get(ty) else 0.45))
+        now = [t for t, on in self.immovable.items() if on]
+        if self.mv_dev and len(now) == 1 and rng.random() < 0.4:      # the last immovable type becomes movable again
+            ty, movable, self.force_key = now[0], True, None
+        if movable:
+            self.force_key = None
+        rc = p.set_type_movable(ty, movable)
+        if ty in self.types or len(self.types) < CLASS_OTHER:
+            self.want(rc == OK, "set_type_movable failed", rc, ty)
+            if ty not in self.types and not movable:
+                self.early_imm.add(ty)
+            self.sight(ty)          # a type never seen before gets its class by this call
+            self.immovable[ty] = not movable
+            self.mv_clone = self.handles.index(p)
+        else:                       # the type lands in the shared class, which is always movable: nothing is set
+            self.want(rc == ERANGE, "set_type_movable of a type in the shared class", rc, ty)
+            self.hit("set_type_movable refused with ERANGE")
+        self.unchanged(st, "set_type_movable")
 
     def feed_peek(self):
         """What the dense feed would list, the checkpoint left where it is."""
@@ -1766,6 +1945,12 @@ class Scenario:
             self.setup()
             for self.step in range(self.steps):
                 op = names[int(self.rng.integers(len(names)))]
+                if self.reb_upload_step is not None and self.reb_upload_step == self.step - 1 and self.rng.random() < 0.5:
+                    op = "expire_by_type"      # the sweep right behind a rebalance that did the class upload
+                elif self.force_key is not None:
+                    op = "update"              # the first key of a type that was made immovable before it
+                elif self.mv_dev and not self.imm_classes() and self.rng.random() < 0.5:
+                    op = "rebalance"           # the rebalance that resets the dense table
                 self.log.append(op)
                 self.count[op] = self.count.get(op, 0) + 1
                 getattr(self, "op_" + op)()

@@ -41,8 +41,7 @@ uncommitted solve and ends a chained run, one that listed nothing (or only count
 between tick_async and tick_wait and in the middle of chained quiet runs; S is compared again when hidden rows come back and after
 every node removal (S names no node).
 
-Measured load, the hot-object report and the load-ordered rebalance cut are fuzzed the same way (the dense layer only: the string
-layer's calls are not in its fuzz yet, and neither are its classes calls).  The scenario keeps a model H of the hit column over every row the handle holds.  `hits`
+Measured load, the hot-object report and the load-ordered rebalance cut are fuzzed the same way.  The scenario keeps a model H of the hit column over every row the handle holds.  `hits`
 draws one of the family's writers (tests/spec_loads.py) — the host batch with and without weights, duplicates included (and one
 refused for an index >= n), the _dev batch (sometimes not 16-byte aligned; with invalid entries it applies the rest and reports
 RIO_GP_EINVAL), the merge host and _dev (rows 0, n, a boundary size, any, so every rows % 4; the _dev array sometimes behind 1-3
@@ -61,13 +60,14 @@ given into sentinel-filled arrays, _dev with and without d_node, count-only host
 None until a call of the hits section has been made; cap 4 097 and an unknown flag bit are refused; rows, keys, nodes,
 n_candidates and key_sum are exact, nothing is written behind the listing, H and an uncommitted solve are as they were.
 `rebalance` draws its order: by load it goes through tests/rebalance_order_ref.py and, up to 4 096 rows, through
-tests/spec_rebalance_order.py, which must agree first; on more than 3 072 nodes half of those calls take all-zero targets.  All
+tests/spec_rebalance_order.py, which must agree first; on more than 3 072 nodes half of those calls take all-zero targets, and while
+more than 3 072 live nodes hold load four rebalances in five go by load and all of those take them.  All
 three new calls are also made between tick_async and tick_wait and in the middle of chained quiet runs (hits and top leave the
 run chained, a fold ends it), right behind an uncommitted solve, and — the report — right behind a sweep that listed rows and
 between two pages of the feed; H is compared again after every node removal and sweep, and H and the loads when hidden rows come
 back and, over every row, at the end.
 
-Object classes are fuzzed the same way (the dense layer only, as said above).  The scenario keeps a model K of the class column
+Object classes are fuzzed the same way.  The scenario keeps a model K of the class column
 over every row the handle holds; only the setters change it.  `classes` draws one call of the setter family (tests/spec_classes.py) — the host range (start and end each at 0, n, a boundary
 size or any row, on every residue mod 4, the source 0-3 bytes into its buffer), the _dev range (the array behind 0-3 bytes of
 padding), a range reaching n + 1 (refused), the host batch (sizes from _BATCHES, half the time its second half naming the rows of
@@ -93,6 +93,27 @@ right behind a report, behind another class sweep with a different n_classes and
 comes right behind a setter and a census right behind a fold now and then.  K is compared again after every node removal (on a
 handle no call of the section has touched it must come back all 0), sweep and change of n and, over every row, at the end; once
 per row-sharded scenario a setter, a sweep and a census on a shard handle are refused.
+
+Immovable classes (DESIGN.md section 2 rule 13) are fuzzed the same way.  The scenario keeps a model I of the handle's 256 flags, all
+movable to begin with; only a legal rio_gp_set_class_movable changes it.  `movable` draws one such call: a reset (NULL, or n_classes 0
+beside an array that is not read), or n_classes from 1, 2, 3, 8, 64, 255, 256 with every class movable, every class immovable, about
+half of them, only class 255, only the class most placed rows below n hold, only classes no row below n holds, or a table that ends
+below the largest class present, so that the classes from there on are movable again (a movable class's flag is any nonzero byte, and
+the array is sometimes longer than n_classes) — through the checked and the raw form; about one call in ten is refused (n_classes 257
+with an array that would change the table, a NULL array with n_classes > 0): RIO_GP_EINVAL and I as it was.  After every call
+rio_gp_get_class_movable equals I, the class column is the model's (the call may be the one that allocates it, all 0), and the column,
+`used` and an uncommitted solve are as they were; in the middle of a chained quiet run the ticks after it stay chained.  `rebalance`
+under a table that names an immovable class is compared with the same vectorised references on aff' — the affinity with
+RIO_GP_AFF_INACTIVE on every row below n whose class is immovable, the equivalence the rule states — and, up to 4 096 rows and within a
+bound on its cost (live nodes x selected rows x rounds <= 4 000 000: its R3 walks the nodes once per waiting row), with
+tests/spec_movable.py, which takes K[:n] and I themselves and must agree first; afterwards the affinity column is what it was, the table
+is I and no listed row is of an immovable class.  A third of the rebalances set a table themselves right before the call, with only
+the table's getter in between; the one in the middle of a quiet run and every one that sends the by-load cut to its histograms in
+global memory (more than 3 072 over nodes) always do.  A rebalance comes right behind a `movable`, right behind a setter that changed
+the class of a placed row and right behind a class sweep that listed rows now and then, and `movable` is among the calls made right
+behind an uncommitted solve, between tick_async and tick_wait and in the middle of quiet runs.  I is compared again after every change
+of n, after every legal and every refused node removal and at the end; once per row-sharded scenario the call is refused on a shard
+handle, whose table stays all 1.
 
     python tests/test_gpu_fuzz.py <seconds> [first_seed]     # a longer campaign: old and extended scenarios alternate
 """
@@ -194,6 +215,7 @@ class Scenario:
         self.clock = 0
         self.seen_used = self.expire_listed = False
         self.mids = 0              # quiet runs so far (op_async: which call goes into the middle of the next one)
+        self.behind = 0            # calls sent right behind an uncommitted solve so far (run(): which call is next)
         self.flights = 0           # streams with a call between tick_async and tick_wait so far (op_async: which call is next)
         # measured load: the model of the hit column (rows >= n keep their value), whether a call of the section has been made
         # (the first one allocates H: until then the report's model has none), whether the last fold was refused, whether the
@@ -208,6 +230,11 @@ class Scenario:
         self.K = np.zeros(n, np.uint8)
         self.cls_used = self.expc_listed = self.in_mid = False
         self.last_nc = None
+        # immovable classes: the model of the table (1: movable), the n_classes of the last legal call, the classes that were
+        # immovable at the last rebalance under a table (until the first plain rebalance after it)
+        self.I = np.ones(256, np.uint8)
+        self.mv_nc = 0
+        self.was_imm = np.zeros(256, bool)
         self.cov = {}
 
     def _caps(self):
@@ -281,7 +308,7 @@ class Scenario:
         # extended scenarios, a quiet run: a call in the middle of it (see _mid_call); any run: a call between the last tick_async
         # and tick_wait, whose answer reflects every enqueued tick
         # (the calls take turns, from a start the seed sets: eighteen of the default seeds have such runs, one start each, and MID
-        #  holds fifteen entries, so each call gets one)
+        #  holds sixteen entries, so each call gets one)
         mid = "none"
         if self.ext and quiet_run:
             mid = self.MID[(self.seed // 6 + self.mids) % len(self.MID)]
@@ -314,6 +341,7 @@ class Scenario:
             assert c == 4, (self.seed, watch[0], "quiet ticks after the call did not stay chained", c, self.log[-6:])
             self.cov["chained across a call"] = self.cov.get("chained across a call", 0) + 1
             self._hit("chained across a census", watch[0] == "census")
+            self._hit("chained across a movable", watch[0] == "movable")
         self.mark = None           # (a call in the middle of the run is not "right before" what follows the ticks after it)
         if self.ext and self.rng.random() < 0.7:
             self.in_flight = True
@@ -375,6 +403,8 @@ class Scenario:
         elif what == "expire_classes":
             if not self.op_expire_classes(hit=True):
                 what = "expire_classes count"
+        elif what == "movable":
+            self.op_movable()
         else:
             self.op_remap(legal=True)     # (a refused map changes nothing: only a legal one must end the chain)
         return what
@@ -633,9 +663,15 @@ class Scenario:
         rng, m, n, g = self.rng, self.m, self.n, self.g
         kind, T = self._targets()
         order = (rebalance_order_ref.ROW_ORDER, rebalance_order_ref.BY_LOAD)[int(rng.random() < (0.7 if self.in_flight else 0.5))]
+        # more than 3 072 live nodes hold load (few of the default seeds' tables do, and not for long): mostly by load, and then
+        # always under all-zero targets
+        wide = m > 3072 and int(np.count_nonzero((self.alive != 0) & (self.oracle.recompute_used(self.ref[:n], self.load[:n], m) > 0))) > 3072
+        if wide and rng.random() < 0.8:
+            order = rebalance_order_ref.BY_LOAD
         by_load = order == rebalance_order_ref.BY_LOAD
-        if by_load and m > 3072 and rng.random() < 0.5:    # every node that holds load is over: the cut's histograms in global memory
-            kind, T = "zero", np.zeros(m, np.uint64)
+        hist = False
+        if by_load and m > 3072 and (wide or rng.random() < 0.5):   # every node that holds load is over: the cut's histograms in global memory
+            kind, T, hist = "zero", np.zeros(m, np.uint64), True
         max_moves = (None, 0, 1, max(1, n * int(rng.integers(1, 6)) // 100))[int(rng.integers(4))]
         rounds = int(rng.integers(0, 4))
         form = ("host", "dev", "count", "dev count")[int(rng.integers(4))]
@@ -647,15 +683,43 @@ class Scenario:
         if listing:
             cap = moves_cap if moves_cap is not None else min(INF if max_moves is None else max_moves, n)
             budget = cap if max_moves is None else min(max_moves, cap)
+        # a third of the draws, and every draw that sends the cut to its histograms in global memory: the table of immovable
+        # classes is set right before the rebalance, with nothing but the table's own getter in between
+        # (and the one rebalance the default seeds put into the middle of a quiet run)
+        if rng.random() < 1 / 3 or hist or self.in_mid:
+            self.op_movable(inner=True, want_imm=hist or self.in_mid)
         had_solve, dead_unticked = self.pending is not None, self.fresh_flip and not self.alive.all()
         cur, load, aff = self.ref[:n], self.load[:n], self.aff[:n]
         tag = (self.seed, "rebalance", "by load" if by_load else "row order", kind, form, max_moves, moves_cap, rounds, self.log[-6:])
-        if by_load:      # R1': the two-tick composition over the rows in (load, row) order
-            nxt, used, wst, wrows, wfrom, wto = rebalance_order_ref.rebalance(cur, load, aff, self.cap, self.alive, T, budget,
-                                                                              rounds or self.rounds, order=order)
-        else:
-            nxt, used, wst, wrows, wfrom, wto = rebalance_ref.rebalance(cur, load, aff, self.cap, self.alive, T, budget, rounds or self.rounds)
-        if n <= 4096:    # the row-by-row restatement as well
+        # rule 13: with an immovable class the result is that of rule 6 on aff', the affinity of every object row of an immovable
+        # class read as RIO_GP_AFF_INACTIVE
+        tabled = bool((self.I == 0).any())
+        imm = self.I[self.K[:n]] == 0
+        aff_t = np.where(imm, np.uint32(AFF_INACTIVE), aff) if tabled else aff
+
+        def reference(a):
+            if by_load:      # R1': the two-tick composition over the rows in (load, row) order
+                return rebalance_order_ref.rebalance(cur, load, a, self.cap, self.alive, T, budget, rounds or self.rounds, order=order)
+            return rebalance_ref.rebalance(cur, load, a, self.cap, self.alive, T, budget, rounds or self.rounds)
+
+        nxt, used, wst, wrows, wfrom, wto = reference(aff_t)
+        agreed = False
+        if tabled and n <= 4096:
+            # tests/spec_movable.py, which takes the class column and the table themselves; its R3 walks the nodes once per waiting
+            # row, so it is consulted within a bound on that cost only (tests/test_fuzz_driver.py holds the share that is skipped)
+            import spec_movable
+            cost = int(np.count_nonzero(self.alive)) * wst["selected_rows"] * (rounds or self.rounds)
+            self._hit("immovable rebalance of at most 4 096 rows")
+            self._hit("immovable rebalance of at most 4 096 rows without the row-by-row restatement", cost > 4_000_000)
+            if cost <= 4_000_000:
+                s_nxt, s_used, s_st, s_moves = spec_movable.rebalance(
+                    [int(x) for x in cur], [int(x) for x in load], [int(x) for x in aff], [int(x) for x in self.K[:n]],
+                    [int(x) for x in self.I], [int(x) for x in self.cap], [int(x) for x in self.alive],
+                    None if T is None else [int(x) for x in T], budget, rounds or self.rounds, order)
+                assert s_st == wst and [int(x) for x in nxt] == s_nxt and [int(x) for x in used] == s_used, tag + ("the two references differ",)
+                assert s_moves == [(int(r), int(f), int(t)) for r, f, t in zip(wrows, wfrom, wto)], tag + ("the two references differ",)
+                agreed = True
+        elif n <= 4096:    # the row-by-row restatement as well
             ints = ([int(x) for x in cur], [int(x) for x in load], [int(x) for x in aff], [int(x) for x in self.cap],
                     [int(x) for x in self.alive], None if T is None else [int(x) for x in T], budget, rounds or self.rounds)
             if by_load:
@@ -687,10 +751,24 @@ class Scenario:
         assert st == wst, tag + (st, wst)
         if listing:
             assert np.array_equal(rows, wrows) and np.array_equal(frm, wfrom) and np.array_equal(to, wto), tag + (rows[:8], wrows[:8])
+        if listing:          # no listed row is of an immovable class
+            assert not imm[rows].any(), tag + ("a row of an immovable class was moved", rows[imm[rows]][:8])
         self.ref[:n] = nxt
         self.pending = None
+        if tabled or self.cls_used:
+            got = g.get_objects()[1]         # the rule reads the affinity as inactive: the column is not written
+            assert np.array_equal(got, aff), tag + ("the rebalance wrote the affinity column", np.flatnonzero(got != aff)[:8])
+        self._mv_check(tag)
         if had_solve:
             self._dropped("rebalance")
+        if tabled:
+            self._hit_movable(cur, load, aff, imm, T, wst, wrows, wto, by_load, had_solve, agreed, reference)
+            self.was_imm = self.I == 0      # the classes the last rebalance under a table held in place
+        elif self.was_imm.any():
+            # the first rebalance since: every class is movable again, and rows of those classes move
+            self._hit("plain rebalance after a reset moved rows of a class that had been immovable",
+                      bool(self.was_imm[self.K[:n][wrows]].any()))
+            self.was_imm = np.zeros(256, bool)
         self._hit("rebalance moved rows", wst["moved_rows"] > 0)
         self._hit("rebalance selected rows that all stayed", wst["selected_rows"] > 0 and wst["moved_rows"] == 0)
         self._hit("rebalance with max_moves 0 and a surplus", budget == 0 and wst["surplus_rows"] > 0)
@@ -712,6 +790,40 @@ class Scenario:
             self._hit("by-load cut with zero-load candidates on an over node", bool(zero.any()))
             self._hit("by-load cut between tick_async and tick_wait", self.in_flight)
             self._hit("by-load cut on a handle whose m is below max_nodes", self.m < self.m0)
+
+    def _hit_movable(self, cur, load, aff, imm, T, wst, wrows, wto, by_load, had_solve, agreed, reference):
+        """The coverage counters of a rebalance under a table that names an immovable class."""
+        n, m = self.n, self.m
+        Tn = self.cap if T is None else np.asarray(T, np.uint64)
+        on = imm & (aff != AFF_INACTIVE) & (cur < m)
+        pinned = np.zeros(m, np.uint64)
+        np.add.at(pinned, cur[on].astype(np.int64), load[on].astype(np.uint64))
+        plain = reference(aff)           # the same call without the table: for this counter only
+        n4 = min(-(-n // 4) * 4, self.nmax)
+        objects = aff != AFF_INACTIVE
+        self._hit("immovable rebalance moved rows", wst["moved_rows"] > 0)
+        self._hit("the table changed the moves", not (np.array_equal(plain[3], wrows) and np.array_equal(plain[5], wto)))
+        self._hit("immovable rebalance with a node whose pinned load alone exceeds its target",
+                  bool(((self.alive != 0) & (pinned > Tn)).any()))
+        self._hit("every class immovable with a node over target (surplus 0)",
+                  bool(objects.any() and imm[objects].all() and wst["nodes_over_before"] > 0 and wst["surplus_rows"] == 0))
+        self._hit("immovable by-load cut moved rows", by_load and wst["moved_rows"] > 0)
+        self._hit("immovable by-load cut with more than 3 072 over nodes", by_load and wst["nodes_over_before"] > 3072)
+        self._hit("immovable rebalance on more than 65 536 rows", n > 65536)
+        self._hit("immovable rebalance on more than 1 024 nodes", m > 1024)
+        self._hit("immovable rebalance with n not a multiple of 4 and an immovable class in the quad behind n",
+                  n4 > n and bool((self.I[self.K[n:n4]] == 0).any()))
+        self._hit("immovable rebalance with hidden placed rows of an immovable class",
+                  bool(((self.ref[n:] != NONE) & (self.I[self.K[n:]] == 0)).any()))
+        self._hit("immovable rebalance with a table shorter than a class present", n > 0 and int(self.K[:n].max()) >= self.mv_nc)
+        self._hit("immovable rebalance on a handle whose m is below max_nodes", m < self.m0)
+        self._hit("immovable rebalance while a solve is uncommitted", had_solve)
+        self._hit("immovable rebalance between tick_async and tick_wait", self.in_flight)
+        self._hit("immovable rebalance in the middle of a quiet run", self.in_mid)
+        self._hit("immovable rebalance right behind a setter that changed a placed row's class", self.after == "classes placed")
+        self._hit("immovable rebalance right behind a class sweep that listed rows", self.after == "class sweep listed")
+        self._hit("immovable rebalance right behind a movable", self.after == "movable")
+        self._hit("the row-by-row restatement agreed on an immovable rebalance that moved rows", agreed and wst["moved_rows"] > 0)
 
     def _feed(self, cap, peek, dev):
         import spec_changes
@@ -790,6 +902,7 @@ class Scenario:
             self._hits_check((self.seed, "num_objects", "the hits and loads of rows that were hidden", self.log[-6:]), loads=True)
         if self.cls_used:              # K is per row of max_objects: a changing n leaves it alone, going down and coming back
             self._cls_check((self.seed, "num_objects", "the classes of the rows below n", self.log[-6:]))
+        self._mv_check((self.seed, "num_objects", self.log[-6:]))      # nor the table of immovable classes
 
     def _remap_draw(self):
         """A legal map for rio_gp_remap_nodes, at least one node kept: identity | permutation | swap | drop one | drop several
@@ -862,6 +975,7 @@ class Scenario:
         assert self.g.num_nodes == m, tag + (self.g.num_nodes,)
         self.remap_refused = True
         self._hit("remap refused with a solve uncommitted", self.pending is not None)
+        self._mv_check(tag)
         self._read_only("remap refused")
         self.check_table("remap refused")
 
@@ -911,6 +1025,7 @@ class Scenario:
             self._hits_check(tag + ("the hit column changed",))
         # nor does K (asked every time: on a handle no call of the section has touched, this is its first and returns zeros)
         self._cls_check(tag + ("the class column changed",))
+        self._mv_check(tag)            # the table is per class: it names no node
         if had_solve:
             self._dropped("remap")
         self._hit("remap removed nodes that held rows", ev > 0)
@@ -1231,6 +1346,7 @@ class Scenario:
         self._hits_check(tag)      # (it waits: rio_gp_hits_merge_dev does not, and its buffer is freed below)
         for d in bufs:
             d.free()
+        self.mark = "hits"
         self._read_only("hits")
         self.check_table("hits")
 
@@ -1275,11 +1391,12 @@ class Scenario:
             self.check_table("fold refused")
             return
         fresh_n = False
-        if not legal and not self.in_flight and not had_solve and rng.random() < 0.25:
+        behind_hits = self.after == "hits"      # (run() sends a fold right behind a hits call now and then: H is not all zero)
+        if not legal and not self.in_flight and not had_solve and (rng.random() < 0.25 or behind_hits):
             # rio_gp_set_num_objects right before it, and nothing in between: `used` is not valid when the fold picks its form
             # (after an operation of its own the scenario's check_table has made it valid again)
             n = (self.nmax, _pick(rng, _SIZES, self.nmax), int(rng.integers(0, self.nmax + 1)), -1)[int(rng.integers(4))]
-            if n < 0:      # a row that holds hits and is not the first of its quad becomes the first hidden one
+            if n < 0 or behind_hits:      # a row that holds hits and is not the first of its quad becomes the first hidden one
                 held = np.flatnonzero(self.H)
                 held = held[held % 4 != 0]
                 n = int(held[rng.integers(len(held))]) if len(held) else self.nmax
@@ -1474,6 +1591,7 @@ class Scenario:
         self._hit("classes while a solve is uncommitted", had_solve)
         self._hit("classes between tick_async and tick_wait", self.in_flight)
         bufs, unaligned, dup, skipped, updated = [], False, False, False, False
+        K0, on0 = self.K, self.ref[:n] != NONE      # (the model functions return a new column)
         if form in ("range", "range dev"):
             a, b = sorted((self._row_edge(), self._row_edge()))
             cls = self._cls_values(np.arange(a, b))
@@ -1554,12 +1672,100 @@ class Scenario:
         self._hit("classes batch with duplicates of one row", dup)
         self._hit("classes_dev batch skipped invalid entries", skipped)
         self._hit("classes batch right before an update batch of the same rows", updated)
-        self.mark = "classes"
+        # (a rebalance under a table comes right behind a setter that changed the class of a placed row now and then)
+        self.mark = "classes placed" if (K0 is not self.K and bool(((K0[:n] != self.K[:n]) & on0).any())) else "classes"
         self._cls_check(tag)       # (it waits: rio_gp_set_classes_dev does not, and its buffer is freed below)
         for d in bufs:
             d.free()
         self._read_only("classes")
         self.check_table("classes" + (" + update" if updated else ""))
+
+    # ---- immovable classes: rio_gp_set_class_movable / rio_gp_get_class_movable; the rebalance under the table is op_rebalance's ----
+    def _mv_check(self, tag):
+        got = self.g.get_class_movable()
+        assert got.shape == (256,) and np.array_equal(got, self.I), tag + ("get_class_movable differs from the model",
+                                                                            np.flatnonzero(got != self.I)[:8])
+
+    def _movable_draw(self, want_imm=False):
+        """One table for rio_gp_set_class_movable -> (kind, n_classes, flags or None): a reset | n_classes from 1, 2, 3, 8, 64, 255,
+        256 with every class movable, every class immovable, about half of them, only class 255 (n_classes 256), only the class
+        most placed rows below n hold (n_classes at least that class + 1), only classes no row below n holds | a table shorter
+        than the largest class present, so that the classes from there on are movable again.  A movable class's flag is any
+        nonzero byte.  want_imm: one of the kinds that leave rows immovable."""
+        rng, n = self.rng, self.n
+        K = self.K[:n]
+        kinds = ("reset", "all movable", "all immovable", "half", "only 255", "the commonest class", "absent classes", "short")
+        kind = kinds[int(rng.integers(8))] if not want_imm else ("half", "half", "the commonest class", "short")[int(rng.integers(4))]
+        nc = int(rng.choice([1, 2, 3, 8, 64, 255, 256]))
+        if kind == "short":
+            nc = int(K.max()) if n else 0
+        if (kind == "reset" or nc == 0) and not want_imm:
+            return "reset", 0, None
+        if nc == 0:
+            return "all immovable", 256, np.zeros(256, np.uint8)
+        mv = rng.choice(np.array([1, 1, 2, 255], np.uint8), nc)
+        if kind == "all immovable":
+            mv[:] = 0
+        elif kind in ("half", "short"):
+            mv[rng.random(nc) < (0.5 if kind == "half" else 0.7)] = 0
+        elif kind == "only 255":
+            nc, mv = 256, rng.choice(np.array([1, 1, 2, 255], np.uint8), 256)
+            mv[255] = 0
+        elif kind == "the commonest class":
+            held = K[self.ref[:n] != NONE]
+            c = int(np.bincount(held, minlength=256).argmax()) if len(held) else 0
+            nc = max(nc, c + 1)
+            mv = rng.choice(np.array([1, 1, 2, 255], np.uint8), nc)
+            mv[c] = 0
+        elif kind == "absent classes":
+            here = np.zeros(256, bool)
+            here[K] = True
+            mv[~here[:nc]] = 0
+        if want_imm and not (mv[K[K < nc]] == 0).any():      # no row below n would be immovable: every class is
+            return "all immovable", 256, np.zeros(256, np.uint8)
+        return kind, nc, mv
+
+    def op_movable(self, inner=False, want_imm=False):
+        """One rio_gp_set_class_movable call: afterwards rio_gp_get_class_movable equals the model I, and the class column (which
+        the call may have allocated, all 0), the column, `used` and an uncommitted solve are as they were.  About one call in
+        ten is refused (n_classes 257, a NULL array with n_classes > 0): RIO_GP_EINVAL, I unchanged.  inner: op_rebalance's own
+        call right before its rebalance — the setter and the table's getter only."""
+        rng, g = self.rng, self.g
+        had_solve, first = self.pending is not None, not self.cls_used
+        if not inner and rng.random() < 0.1:
+            if rng.random() < 0.5:      # (an array that would change the table if it were read)
+                kind, rc = "n_classes 257", g.set_class_movable_raw((self.I[np.arange(257) % 256] == 0).astype(np.uint8), n_classes=257)
+            else:
+                kind, rc = "no array", g.set_class_movable_raw(None, n_classes=int(rng.choice([1, 8, 256])))
+            tag = (self.seed, "movable", "refused", kind, self.log[-6:])
+            assert rc == self.gp.EINVAL, tag + (rc,)
+            self._hit("movable refused")
+        else:
+            kind, nc, mv = self._movable_draw(want_imm)
+            tag = (self.seed, "movable", kind, nc, self.log[-6:])
+            k = int(rng.integers(3))
+            if k == 0 or (mv is None and k == 1):      # the checked form: n_classes is the array's length
+                g.set_class_movable(mv)
+            elif mv is None:                            # n_classes 0 with an array: it is not read
+                rc = g.set_class_movable_raw(np.zeros(4, np.uint8), n_classes=0)
+                assert rc == self.gp.OK, tag + (rc,)
+            else:                                       # the array longer than n_classes: the flags behind them are not read
+                rc = g.set_class_movable_raw(np.concatenate([mv, np.zeros(3, np.uint8)]), n_classes=nc)
+                assert rc == self.gp.OK, tag + (rc,)
+            self.I = np.ones(256, np.uint8)
+            if nc:
+                self.I[:nc] = mv != 0
+            self.mv_nc = nc
+        self._mv_check(tag)
+        if inner:
+            return
+        self._hit("movable as the first call of the section", first)
+        self._hit("movable while a solve is uncommitted", had_solve)
+        self._hit("movable between tick_async and tick_wait", self.in_flight)
+        self.mark = "movable"
+        self._cls_check(tag)
+        self._read_only("movable")
+        self.check_table("movable")
 
     def _class_cutoffs(self, nc, placed, hit):
         """One cutoff per class -> (kind, cutoffs).  Each is 0 | the stamp of a placed row of the class (the comparison is
@@ -1840,18 +2046,23 @@ class Scenario:
     DROPS_SOLVE = ("tick", "rebalance", "update", "remove", "clean", "place", "mixed", "attrs", "caps", "num_objects", "remap", "expire",
                    "fold", "expire_classes")   # (the fold rewrites loads, not the column: it drops the solve and is no writer of the feed)
     MID = ("none", "index", "changes", "rebalance", "remap", "touch", "expire count", "expire", "hits", "top", "fold",
-           "classes", "census", "expire_classes count", "expire_classes")   # op_async: a call in a quiet run
+           "classes", "census", "expire_classes count", "expire_classes", "movable")   # op_async: a call in a quiet run
     # ... after which the next tick must not chain (an "expire" or an "expire_classes" un-placed a row)
     ENDS_CHAIN = ("rebalance", "remap", "expire", "fold", "expire_classes")
     # op_async: the calls that take turns between the last tick_async and tick_wait
-    IN_FLIGHT = ("index", "changes", "rebalance", "remap", "touch", "expire", "hits", "fold", "top", "classes", "expire_classes", "census")
+    IN_FLIGHT = ("index", "changes", "rebalance", "remap", "touch", "expire", "hits", "fold", "top", "classes", "expire_classes", "census",
+                 "movable")
+
+    # run(): the calls that come right behind an uncommitted solve
+    BEHIND_SOLVE = ("index", "remap", "rebalance", "remap", "touch", "expire", "expire", "hits", "top", "top", "fold", "fold", "fold",
+                    "classes", "classes", "expire_classes", "expire_classes", "census", "census", "movable")
 
     OPS = (("tick", 5), ("solve", 2), ("async", 3), ("flip", 4), ("update", 2), ("remove", 2), ("lookup", 1), ("clean", 2),
            ("place", 4), ("mixed", 3), ("attrs", 1), ("caps", 1))
 
     OPS_EXT = OPS + (("index", 3), ("rebalance", 6), ("changes", 5), ("changes_reset", 1), ("num_objects", 2), ("remap", 3),
                      ("touch", 4), ("expire", 4), ("hits", 4), ("fold", 3), ("top", 4), ("classes", 6), ("expire_classes", 4),
-                     ("census", 4))
+                     ("census", 4), ("movable", 3))
 
     def run(self):
         names = [a for a, w in (self.OPS_EXT if self.ext else self.OPS) for _ in range(w)]
@@ -1864,15 +2075,22 @@ class Scenario:
                 elif self.ext and self.pending is not None and self.rng.random() < 0.75:
                     # an uncommitted solve lives until the next writer: three times in four the calls that must keep it, or must drop
                     # it themselves, come right behind it (the table's weights alone bring them there a few times in the default seeds)
-                    op = ("index", "remap", "rebalance", "remap", "touch", "expire", "expire", "hits", "top", "top", "fold", "fold",
-                          "fold", "classes", "classes", "expire_classes", "expire_classes", "census", "census")[int(self.rng.integers(19))]
+                    # (the calls take turns, from a start the seed sets, as MID's and IN_FLIGHT's do)
+                    op = self.BEHIND_SOLVE[(7 * self.seed + self.behind) % len(self.BEHIND_SOLVE)]
+                    self.behind += 1
                 elif self.ext and self.mark is not None and self.rng.random() < 0.3:
                     # the report on the scratch a sweep has just used, right behind the sweep; a class sweep right behind the
                     # report, and right behind another class sweep (the copies of the per-class counts it was to leave zero);
                     # a sweep or a census right behind a setter, while the column is not all one class
-                    op = {"expire listed": "top", "class sweep listed": ("top", "expire_classes")[int(self.rng.integers(2))],
+                    # a rebalance right behind a call that set the table, behind a setter that changed the class of a placed row and
+                    # behind a class sweep that listed rows
+                    j = int(self.rng.integers(2))
+                    op = {"expire listed": "top", "class sweep listed": ("top", "expire_classes")[j],
                           "class sweep": "expire_classes", "top": "expire_classes", "fold": "census",
-                          "classes": ("expire_classes", "census")[int(self.rng.integers(2))]}[self.mark]
+                          "classes": ("expire_classes", "census")[j], "classes placed": ("rebalance", "census")[j],
+                          "movable": "rebalance", "hits": "fold"}[self.mark]
+                    if self.mark == "class sweep listed" and (self.I == 0).any() and self.rng.random() < 0.5:
+                        op = "rebalance"
                 self.after, self.mark = self.mark, None
                 if self.ext and self.n == 0 and op in self.NEED_ROWS:
                     self.log.append("skipped: " + op)
@@ -1906,6 +2124,7 @@ class Scenario:
                     self._hits_check((self.seed, "the end", "hits and loads over every row", self.log[-6:]), loads=True)
                 if self.cls_used:
                     self._cls_check((self.seed, "the end", "classes over every row", self.log[-6:]))
+                self._mv_check((self.seed, "the end", "the table of immovable classes", self.log[-6:]))
             self.chained = self.g.chained_scans() if self.lab else 0
         finally:
             self.g.close()
@@ -1924,7 +2143,7 @@ def test_random_operation_sequences(gp, oracle, seed):
     Scenario(gp, oracle, seed).run()
 
 
-EXT_SEEDS = int(os.environ.get("RIO_FUZZ_EXT_SEEDS", "112"))
+EXT_SEEDS = int(os.environ.get("RIO_FUZZ_EXT_SEEDS", "120"))
 
 
 @pytest.mark.parametrize("seed", range(EXT_SEEDS))
@@ -1987,10 +2206,12 @@ def _sharded_scenario(gp, oracle, seed):
                 assert L.rio_gp_shard_p2p_export(g.handle, 1, h64) == gp.OK, (seed, "classes on a shard handle: export")
                 try:
                     rc = (g.set_classes_raw(0, np.ones(1, np.uint8)) if rng.random() < 0.5 else g.set_class_batch_raw([0], [1]),
-                          g.expire_classes_raw(1, [0xFFFFFFFF])[0], g.census_raw(int(rng.integers(1, 257)), bool(rng.integers(2)))[0])
+                          g.expire_classes_raw(1, [0xFFFFFFFF])[0], g.census_raw(int(rng.integers(1, 257)), bool(rng.integers(2)))[0],
+                          g.set_class_movable_raw(np.zeros(int(rng.choice([1, 8, 256])), np.uint8)))
                 finally:
                     assert L.rio_gp_shard_p2p_close(g.handle) == gp.OK, (seed, "classes on a shard handle: close")
-                assert rc == (gp.EINVAL,) * 3, (seed, "classes on a shard handle", rc)
+                assert rc == (gp.EINVAL,) * 4, (seed, "classes on a shard handle", rc)
+                assert g.get_class_movable().all(), (seed, "a refused set_class_movable on a shard handle changed the table")
             st = sol.tick()
             ref, used, ost = oracle.tick(ref, load, aff, cap, alive, rounds)
             got = np.concatenate([e.g.get_assign() if e.g.num_objects else np.zeros(0, np.uint32) for e in engines])

@@ -23,7 +23,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SEEDS = int(os.environ.get("RIO_OP_FUZZ_SEEDS", "36"))
+SEEDS = int(os.environ.get("RIO_OP_FUZZ_SEEDS", "42"))
 
 
 def concurrent_phase(gp, seed, threads=6, steps=120):

@@ -10,7 +10,7 @@ import pytest
 import fake_rio_op
 import op_layer_driver as drv
 
-SEEDS = 36     # (tests/test_gpu_op_layer_fuzz.py runs the same seeds on the GPU)
+SEEDS = 42     # (tests/test_gpu_op_layer_fuzz.py runs the same seeds on the GPU)
 
 
 @pytest.fixture(scope="module")
