@@ -270,6 +270,28 @@ int rio_op_census(rio_op_t* p, int by_server, uint64_t* n_out, const char* const
  *     another type follows its new type. */
 int rio_op_set_type_movable_n(rio_op_t* p, const char* struct_name, size_t len, int movable);
 
+/* Shedding under pressure (rio_gp_shed_idle, DESIGN.md section 2 rule 14; Orleans' activation shedding): on every server whose
+ * keys weigh more than its member capacity, un-place the keys nobody has asked for the longest, and only as many as bring the
+ * server back under it.  It is the call for a cluster that is over as a whole: rio_op_rebalance has nowhere to move the load
+ * to (the dense call reports stayed_rows), and rio_op_expire's one cutoff sheds everywhere or nowhere.
+ *   - A key may be shed only if it was last stamped before `cutoff` (never stamped counts as 0; rio_op_set_clock's rule says who
+ *     stamps), has a load of at least 1, and its type is neither immovable (rio_op_set_type_movable_n) nor one whose idle limit
+ *     is RIO_OP_IDLE_NEVER (rio_op_set_type_idle_limit_n); other idle limits play no part here.  Every other key on the server
+ *     counts against its capacity and stays.  Per server the keys that may go are taken most recently stamped first, then in
+ *     the dense layer's row order, and kept while they still fit; the rest is the SURPLUS.
+ *   - At most max_objects_out keys of the surplus are un-placed (~0: no limit; 0: count only, nothing changes), in row order,
+ *     and listed with the address each was on.  *n_out = keys listed; *n_surplus (may be NULL) = the whole surplus.  A budget
+ *     below the surplus sheds a row-order prefix of it; the next call cuts afresh.
+ *   - Stamps are uploaded first; the classes and the movable table are uploaded when a type needs them (as
+ *     rio_op_expire_by_type and the rebalance do).  Stamping, locking, the host shadow's correction for exactly the listed keys,
+ *     the listing and its ownership are rio_op_expire's: later lookups answer "none" for the listed keys, rio_op_changes lists
+ *     them as deletes.
+ *   - A dense layer without rio_gp_shed_idle (or without the class calls when a type needs them): RIO_GP_EUPSTREAM, nothing
+ *     changed. */
+int rio_op_shed_idle(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64_t* n_out, uint64_t* n_surplus,
+                     const char* const** struct_names, const size_t** struct_name_lens, const char* const** object_ids,
+                     const size_t** object_id_lens, const char* const** addresses);
+
 /* Measured load (rio_gp_hits_merge + rio_gp_load_fold, DESIGN.md section 2 rule 10).  The reference's ObjectPlacementItem
  * (object_placement/mod.rs:23-24) carries no load and local.rs keeps none: load is this library's extension, and every key has
  * load 1 until rio_op_set_object_load says otherwise — one host call per key.  Tracking measures it instead.

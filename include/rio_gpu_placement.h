@@ -577,13 +577,70 @@ int rio_gp_census_dev(rio_gp_t* h, uint32_t flags, uint32_t n_classes, uint64_t*
  *     they were) and it may allocate K, zero-filled.  rio_gp_remap_nodes, rio_gp_set_num_objects and the rebalance leave the
  *     table alone.
  *   - rio_gp_get_class_movable: out256[c] = 1 where class c is movable, 0 where it is not, for all RIO_GP_MAX_CLASSES classes.
- *   - Only the rebalance consults the table: ticks, rio_gp_clean_server, node removal, expiry and the CRUD calls treat the rows
+ *   - Only the rebalance and rio_gp_shed_idle (below: it never sheds such a row) consult the table: ticks, rio_gp_clean_server, node removal, expiry and the CRUD calls treat the rows
  *     as before (a dead node's immovable objects are evicted like any others).
  *   - rio_gp_shard_rebalance_begin[_ordered] on a handle whose table names an immovable class is RIO_GP_EINVAL: a rank's table
  *     has no class column.
  *   - Cost: with an immovable class the table passes of the rebalance read K too, 13 B per row instead of 12. */
 int rio_gp_set_class_movable(rio_gp_t* h, uint32_t n_classes, const uint8_t* movable);
 int rio_gp_get_class_movable(rio_gp_t* h, uint8_t* out256);
+
+/* Pressure shedding (DESIGN.md section 2 rule 14): on every over-target node, un-place the objects nobody has asked for the
+ * longest, and only as many as bring the node back to its target — Orleans' activation shedding under memory pressure.  It is
+ * the answer where rio_gp_rebalance leaves stayed_rows (the cluster as a whole is over: nothing can move) and rio_gp_expire's
+ * cluster-wide cutoff relieves nothing.  A = the column rio_gp_get_assign returns at the point of the call, S = the last-seen
+ * column (rule 9), K = the class column (rule 12), T[j] = cfg->target[j] (NULL: the capacities; ~0: never over).  Only rows
+ * r < n with A[r] = j < m and alive[j] take part; every other row (unplaced, on a dead node, on a node id >= m, r >= n) is left
+ * exactly as it is.
+ *   L0  candidates and pinned rows.  A participating row has an effective cutoff c(r): cfg->cutoff without class_cutoffs; with
+ *       them class_cutoffs[K[r]] for K[r] < n_classes and 0 for the classes from n_classes on (as rio_gp_expire_classes treats
+ *       them); and 0 for a row of an immovable class (rio_gp_set_class_movable) in either form: shedding deactivates, and rule
+ *       13's types are the ones that must not be.  The row is a CANDIDATE iff aff[r] != RIO_GP_AFF_INACTIVE, load[r] >= 1 and
+ *       S[r] < c(r); otherwise it is PINNED: its load counts against T[j] and it is never touched.
+ *   L1  the cut.  Per live node j: free_j = T[j] -sat (pinned load on j).  j's candidates are taken in the order (S descending,
+ *       then row ascending) and kept while the inclusive prefix of their loads stays <= free_j; the first that overflows and
+ *       every later one in that order are SURPLUS: the most recently seen stay, the longest idle go.  As a threshold, per over
+ *       node (sigma_j, cutrow_j): candidate i is surplus iff S[i] < sigma_j, or S[i] == sigma_j and i >= cutrow_j; sigma_j is the
+ *       stamp of the first overflowing candidate, rem_j = free_j - (load of j's candidates with S > sigma_j), and cutrow_j is
+ *       the first candidate of j with stamp sigma_j, in row order, whose inclusive load prefix among those ties exceeds rem_j
+ *       (rule R1 restricted to the ties).
+ *   L2  the budget.  The first B surplus rows in ascending row order are selected: B = cfg->max_rows, or min(max_rows,
+ *       rows_cap) with a listing — the listing always fits and the call never answers RIO_GP_ERANGE.  A budget below the
+ *       surplus sheds a row-order prefix of it (R2's caveat); the next call cuts afresh.
+ *   L3  the outcome.  Exactly the selected rows are un-placed as rio_gp_expire un-places its listed rows: A[r] := RIO_GP_NONE,
+ *       under RIO_GP_CFG_ROW_LIFECYCLE the row becomes a non-object, load, S and K stay; `used` follows; the change feed
+ *       lists them as (r, old, NONE).  out_rows[k] = r, out_node[k] = A_old[r], ascending by row; *n_rows = shed_rows.
+ *   Counters: surplus_rows / surplus_load (L1), shed_rows / shed_load (L3), nodes_over_before / nodes_over_after = the live
+ *       nodes with used[j] > T[j] on the old / the new column, as the rebalance counts them.
+ *   With shed_rows == 0 (nothing over, B == 0, cutoff 0) nothing changes at all: the column, `used`, S, the feed's checkpoint,
+ *       an uncommitted rio_gp_solve, the quiet and chained tick state.  With shed_rows > 0 the call behaves like
+ *       rio_gp_remove_batch: it drops an uncommitted solve and counts as a change of the inputs.  Either way it orders itself
+ *       behind rio_gp_tick_async work in flight.
+ *   RIO_GP_EINVAL, nothing changed or allocated: cfg NULL, struct_size != sizeof(rio_gp_shed_cfg), reserved != 0; n_classes
+ *       outside 1 .. RIO_GP_MAX_CLASSES with class_cutoffs, or non-zero without; out_rows / out_node not given together,
+ *       rows_cap != 0 without them; a handle of the row-sharded solve.  st and n_rows may both be NULL.
+ *   rio_gp_shed_idle_dev: out_rows / out_node are device arrays of rows_cap entries; the call waits for the node pass (the
+ *       host picks the over nodes) and once more at its end.  The host-pointer form also waits for the surplus count.
+ *   Cost: one pass over A, load, aff and S (16 B a row, 17 with classes) for the node pass, each digit of the selection (the
+ *       digits every candidate stamp shares are skipped), the tie walk and the count; nothing past the node pass when no
+ *       node is over. */
+typedef struct rio_gp_shed_cfg {
+    uint32_t struct_size;          /* = sizeof(rio_gp_shed_cfg) */
+    uint32_t cutoff;               /* a row may be shed only if S[r] < cutoff */
+    uint64_t max_rows;             /* B; ~0 = no limit; 0 = count the surplus, change nothing */
+    const uint64_t* target;        /* m u64, NULL = the capacities, ~0 = never over */
+    const uint32_t* class_cutoffs; /* NULL, or n_classes u32 in place of cutoff (rule L0) */
+    uint32_t n_classes;
+    uint32_t reserved;             /* 0 */
+} rio_gp_shed_cfg;
+typedef struct rio_gp_shed_stats {
+    uint64_t surplus_rows, surplus_load, shed_rows, shed_load;
+    uint32_t nodes_over_before, nodes_over_after;
+} rio_gp_shed_stats;
+int rio_gp_shed_idle(rio_gp_t* h, const rio_gp_shed_cfg* cfg, rio_gp_shed_stats* st, uint32_t* out_rows, uint32_t* out_node,
+                     uint64_t rows_cap, uint64_t* n_rows);
+int rio_gp_shed_idle_dev(rio_gp_t* h, const rio_gp_shed_cfg* cfg, rio_gp_shed_stats* st, uint32_t* d_rows, uint32_t* d_node,
+                         uint64_t rows_cap, uint64_t* n_rows);
 
 /* ---- the placement policy, batched ------------------------------------------------------ */
 

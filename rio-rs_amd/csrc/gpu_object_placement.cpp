@@ -87,6 +87,9 @@ extern "C" int rio_gp_census(rio_gp_t* h, uint32_t flags, uint32_t n_classes, ui
                              uint64_t* n_other) __attribute__((weak));
 // Weak for the same reason: immovable classes (rio_op_set_type_movable_n reports RIO_GP_EUPSTREAM without it).
 extern "C" int rio_gp_set_class_movable(rio_gp_t* h, uint32_t n_classes, const uint8_t* movable) __attribute__((weak));
+// Weak for the same reason: pressure shedding (rio_op_shed_idle reports RIO_GP_EUPSTREAM without it).
+extern "C" int rio_gp_shed_idle(rio_gp_t* h, const rio_gp_shed_cfg* cfg, rio_gp_shed_stats* st, uint32_t* out_rows, uint32_t* out_node,
+                                uint64_t rows_cap, uint64_t* n_rows) __attribute__((weak));
 
 namespace {
 
@@ -1932,6 +1935,44 @@ int rio_op_expire_by_type(rio_op_t* p, uint32_t now, uint32_t default_max_idle, 
         },
         [&](State* s, uint32_t* rows, uint32_t* node, uint64_t cap, uint64_t* idle) {
             return rio_gp_expire_classes(s->gp, RIO_GP_MAX_CLASSES, cutoffs, rows, node, cap, idle, nullptr, nullptr);
+        });
+}
+
+// Rule 14 over the members' capacities.  rio_op_expire's body with another dense call: the surplus takes the place of the idle
+// count, and the rows the call un-placed are its first min(surplus, cap).  Types that must never be deactivated go down as a
+// class-cutoff table (cutoff 0 for RIO_OP_IDLE_NEVER); immovable types follow from the dense rule once the table is uploaded.
+int rio_op_shed_idle(rio_op_t* p, uint32_t cutoff, uint64_t max_objects_out, uint64_t* n_out, uint64_t* n_surplus,
+                     const char* const** struct_names, const size_t** struct_name_lens, const char* const** object_ids,
+                     const size_t** object_id_lens, const char* const** addresses) {
+    uint32_t cutoffs[RIO_GP_MAX_CLASSES];
+    bool by_class = false;
+    return expire_impl(
+        p, max_objects_out, n_out, n_surplus, struct_names, struct_name_lens, object_ids, object_id_lens, addresses,
+        [&](State* s) {
+            if (!rio_gp_touch_merge || !rio_gp_shed_idle) return fail(RIO_GP_EUPSTREAM, "dense layer has no pressure shedding");
+            for (uint32_t c = 0; c < RIO_GP_MAX_CLASSES; ++c) {
+                const bool never = c < s->type_has_limit.size() && s->type_has_limit[c] && s->type_limit[c] == RIO_OP_IDLE_NEVER;
+                cutoffs[c] = never ? 0u : cutoff;
+                by_class = by_class || never;
+            }
+            const bool movable_table = s->n_immovable || s->mv_on_device;
+            if ((by_class || movable_table) && !has_classes()) return fail(RIO_GP_EUPSTREAM, "dense layer has no object classes");
+            if (movable_table && !rio_gp_set_class_movable) return fail(RIO_GP_EUPSTREAM, "dense layer has no immovable classes");
+            int rc;
+            if (by_class && (rc = sync_classes(s))) return rc;
+            return movable_table ? sync_movable(s) : RIO_GP_OK;
+        },
+        [&](State* s, uint32_t* rows, uint32_t* node, uint64_t cap, uint64_t* surplus) {
+            rio_gp_shed_cfg cfg{};
+            cfg.struct_size = sizeof cfg;
+            cfg.cutoff = cutoff;
+            cfg.max_rows = cap;  // targets: the capacities of rio_op_set_member
+            cfg.class_cutoffs = by_class ? cutoffs : nullptr;
+            cfg.n_classes = by_class ? RIO_GP_MAX_CLASSES : 0u;
+            rio_gp_shed_stats st{};
+            const int rc = rio_gp_shed_idle(s->gp, &cfg, &st, rows, node, cap, nullptr);
+            *surplus = st.surplus_rows;
+            return rc;
         });
 }
 

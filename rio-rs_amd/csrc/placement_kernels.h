@@ -640,4 +640,32 @@ void launch_expc_apply(u32* A, const u32* S, const unsigned char* K, const ChgPl
 void launch_census(const u32* A, const unsigned char* K, const u32* load, u64 n, u32 m, u32 n_classes, bool by_node,
                    u64* out_rows, u64* out_load, u64* other, hipStream_t s);
 
+// --- pressure shedding (rio_gp_shed_idle): un-place the longest-idle candidates of the over-target nodes (kernels: k_ish_*) ---
+// The columns a pass reads and the rule that names a candidate: an object of load >= 1 on a node < m with S < cutoff, or, with
+// cls, S < cls->v[K[row]] (kernels k_ishc_*; the caller folds "never shed" classes in as cutoff 0).
+struct IshCols {
+    const u32 *A, *load, *aff, *S;
+    u32 cutoff;
+    const unsigned char* K;  // with cls only: the class column, readable in whole quads
+    const ClsCutoffs* cls;   // nullptr: the plain form
+};
+// used, cand: m u64 each (zeroed here): the load of every row on node j, the load of its candidates; kmm: 2 u32 -> the smallest
+// and the largest key ~S of a candidate (kNone, 0 without one)
+void launch_ish_hist(const IshCols& c, u64 n, u32 m, u64* used, u64* cand, u32* kmm, hipStream_t s);
+// launch_shed_select with the key ~S and the weight load: thr[slot_node] = the smallest key under which the candidates up to and
+// including it weigh more than slot_free; slot_free -= the load of the candidates of a smaller key.  kmin / kmax: kmm as read
+// back; the passes over digits every candidate shares are skipped.  Returns the histogram passes it launched.
+u32 launch_ish_select(const IshCols& c, u64 n, u32 m, u32 s, const u32* map, const u32* slot_node, u64* slot_free, u32* pre,
+                      u64* hist, u32* thr, u32 kmin, u32 kmax, hipStream_t st);
+// the tie walk: cut[slot_node] = the first candidate of key thr[node], in row order, whose inclusive load prefix among those
+// passes slot_free (kNone on the other nodes); mat: s * nt u64
+void launch_ish_cut(const IshCols& c, const ShPlan& p, const u32* map, const u32* slot_node, const u64* slot_free, u64* mat,
+                    u32* cut, const u32* thr, hipStream_t s);
+// launch_exp_count / launch_exp_apply over the surplus predicate key > thr[node] || (key == thr[node] && row >= cut[node]);
+// acc[kShAccSurplusLoad] += the surplus rows' load (the caller zeroes acc)
+void launch_ish_count(const IshCols& c, const ChgPlan& p, u32 m, const u32* thr, const u32* cut, u32* cnt, u32* gsum, u32* total,
+                      u64* acc, u64* freed, hipStream_t s);
+void launch_ish_apply(u32* A, const IshCols& c, const ChgPlan& p, u32 m, const u32* thr, const u32* cut, const u32* cnt,
+                      const u32* gsum, u64 cap, u32* rows, u32* node, u32* aff_life, u64* used, u64* freed, hipStream_t s);
+
 }  // namespace riogp

@@ -8447,4 +8447,475 @@ void launch_census(const u32* A, const unsigned char* K, const u32* load, u64 n,
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Pressure shedding (rio_gp_shed_idle; DESIGN.md section 2 rule 14): on every over-target node the longest-idle candidates are
+// un-placed, as many as bring the node back to its target.  A candidate is an object of load >= 1 on a node < m whose stamp
+// S lies below its cutoff (one cutoff, or one per class: the host folds the immovable classes of rule 13 into that table as
+// cutoff 0, so the kernels know one rule); every other row on the node is pinned.  ish_quad gives a quad's rows as the passes
+// see them: the node, the raw load, the candidate weight w (the load of a candidate, 0 otherwise) and the key ~S, under which
+// ascending order is "most recently seen first".
+//   k_ish_hist      one streaming pass: per node the load of every row on it (what k_used gives) and the load of its
+//                   candidates; the smallest and largest candidate key of the table (the search skips the digits they share).
+//                   The host picks the over nodes into slots as the rebalance does.
+//   k_ish_key_hist + k_shed_sel_pick   the load-ordered cut's weighted radix selection with the KEY from another column than the
+//                   weight: per slot the smallest key tau under which the candidates up to and including it weigh more than
+//                   free_j (sigma_j = ~tau); slot_free keeps rem_j.  LDS histogram for few slots, aggregated global adds beyond
+//                   (sh_sel_plan); the pick kernel is the rebalance's as it stands.
+//   k_ish_tile + k_ish_cut   the tie walk: R1's row-order cut over the candidates of key tau against rem_j -> cut[j]
+//   k_ish_count     ordered compaction, count pass: a candidate is surplus iff key > thr[node] || (key == thr[node] && row >=
+//                   cut[node]) (both kNone on a node that is not over: never); their load goes into acc[kShAccSurplusLoad]
+//   k_ish_apply     exp_apply over the same predicate: the first B surplus rows are listed and un-placed, `used` following
+// The class forms (k_ishc_*) read the quad of K beside the four dwordx4 and keep the cutoff table in 1 KiB of LDS.
+// ------------------------------------------------------------------------------------------------
+template <bool CLS>
+__device__ __forceinline__ const u32* ish_stage(const ClsCutoffs& cq) {
+    if constexpr (CLS) {
+        __shared__ u32 ct[kClsMax];
+        for (u32 k = threadIdx.x; k < kClsMax; k += blockDim.x) ct[k] = cq.v[k];
+        return ct;  // (the caller's barrier follows)
+    } else {
+        return nullptr;
+    }
+}
+// the quad at i0 (a multiple of 4): rows >= n and rows on a node >= m get cc = kNone, ll = w = 0
+template <bool CLS>
+__device__ __forceinline__ void ish_quad(const u32* A, const u32* __restrict__ load, const u32* aff, const u32* __restrict__ S,
+                                         const u32* __restrict__ Kw, u32 cutoff, const u32* ct, u64 i0, u64 n, u32 m,
+                                         u32 (&cc)[4], u32 (&ll)[4], u32 (&w)[4], u32 (&key)[4]) {
+    const uint4 c = *reinterpret_cast<const uint4*>(A + i0);
+    const uint4 l = *reinterpret_cast<const uint4*>(load + i0);
+    const uint4 a = *reinterpret_cast<const uint4*>(aff + i0);
+    const uint4 s = *reinterpret_cast<const uint4*>(S + i0);
+    u32 kw = 0;
+    if constexpr (CLS) kw = Kw[i0 >> 2];
+    const u32 c4[4] = {c.x, c.y, c.z, c.w}, l4[4] = {l.x, l.y, l.z, l.w}, a4[4] = {a.x, a.y, a.z, a.w},
+              s4[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool in = i0 + k < n && c4[k] < m;
+        u32 lim = cutoff;
+        if constexpr (CLS) lim = ct[(kw >> (8 * k)) & 255u];
+        cc[k] = in ? c4[k] : kNone;
+        ll[k] = in ? l4[k] : 0u;
+        w[k] = (in && a4[k] != kAffInactive && s4[k] < lim) ? l4[k] : 0u;
+        key[k] = ~s4[k];
+    }
+}
+
+template <bool CLS>
+__device__ __forceinline__ void ish_hist_body(const u32* __restrict__ A, const u32* __restrict__ load, const u32* __restrict__ aff,
+                                              const u32* __restrict__ S, const u32* __restrict__ Kw, u32 cutoff,
+                                              const ClsCutoffs& cq, u64 n, u32 m, u64* __restrict__ used, u64* __restrict__ cand,
+                                              u32* __restrict__ kmm) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64* hu = reinterpret_cast<u64*>(smem);  // [m]
+    u64* hc = hu + m;                        // [m]
+    __shared__ u32 s_mn, s_mx;
+    const int tid = threadIdx.x;
+    const u32* ct = ish_stage<CLS>(cq);
+    for (u32 k = tid; k < 2 * m; k += kBlock) hu[k] = 0;
+    if (tid == 0) { s_mn = kNone; s_mx = 0; }
+    __syncthreads();
+    u32 mn = kNone, mx = 0;
+    const u64 nvec = (n + 3) / 4;
+    for (u64 v = (u64)blockIdx.x * kBlock + tid; v < nvec; v += (u64)gridDim.x * kBlock) {
+        u32 cc[4], ll[4], w[4], key[4];
+        ish_quad<CLS>(A, load, aff, S, Kw, cutoff, ct, v * 4, n, m, cc, ll, w, key);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (ll[k]) {
+                atomicAdd(&hu[cc[k]], (u64)ll[k]);
+                if (w[k]) {
+                    atomicAdd(&hc[cc[k]], (u64)w[k]);
+                    mn = key[k] < mn ? key[k] : mn;
+                    mx = key[k] > mx ? key[k] : mx;
+                }
+            }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {  // one global atomic per workgroup and bound
+        const u32 a = (u32)__shfl_xor((int)mn, d, 64), b = (u32)__shfl_xor((int)mx, d, 64);
+        mn = a < mn ? a : mn;
+        mx = b > mx ? b : mx;
+    }
+    if ((tid & 63) == 0 && mn <= mx) { atomicMin(&s_mn, mn); atomicMax(&s_mx, mx); }
+    __syncthreads();
+    for (u32 k = tid; k < m; k += kBlock) {
+        if (hu[k]) atomicAdd(&used[k], hu[k]);
+        if (hc[k]) atomicAdd(&cand[k], hc[k]);
+    }
+    if (tid == 0 && s_mn <= s_mx) { atomicMin(&kmm[0], s_mn); atomicMax(&kmm[1], s_mx); }
+}
+__global__ __launch_bounds__(kBlock) void k_ish_hist(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                     const u32* __restrict__ aff, const u32* __restrict__ S, u32 cutoff, u64 n, u32 m,
+                                                     u64* __restrict__ used, u64* __restrict__ cand, u32* __restrict__ kmm) {
+    ish_hist_body<false>(A, load, aff, S, nullptr, cutoff, ClsCutoffs{}, n, m, used, cand, kmm);
+}
+__global__ __launch_bounds__(kBlock) void k_ishc_hist(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                      const u32* __restrict__ aff, const u32* __restrict__ S,
+                                                      const u32* __restrict__ Kw, const ClsCutoffs cq, u64 n, u32 m,
+                                                      u64* __restrict__ used, u64* __restrict__ cand, u32* __restrict__ kmm) {
+    ish_hist_body<true>(A, load, aff, S, Kw, 0u, cq, n, m, used, cand, kmm);
+}
+
+// shed_sel_hist_body with the digit taken from the key and the weight from the load
+template <bool LDS, bool CLS>
+__device__ __forceinline__ void ish_key_hist_body(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                  const u32* __restrict__ aff, const u32* __restrict__ S,
+                                                  const u32* __restrict__ Kw, u32 cutoff, const ClsCutoffs& cq, u64 n, u32 m, u32 SL,
+                                                  const u32* __restrict__ map, const u32* __restrict__ pre, u32 himask, u32 shift,
+                                                  u32 bins, u32 stride, u64* __restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32* mp = reinterpret_cast<u32*>(smem);  // [m]
+    u32* pr = mp + m;                        // [SL]
+    u64* h = reinterpret_cast<u64*>(smem + ((((size_t)m + SL) * sizeof(u32) + 15) & ~(size_t)15));  // [SL * bins], LDS form only
+    const int tid = threadIdx.x;
+    const u32* ct = ish_stage<CLS>(cq);
+    for (u32 k = tid; k < m; k += kBlock) mp[k] = map[k];
+    for (u32 k = tid; k < SL; k += kBlock) pr[k] = pre[k];
+    if (LDS)
+        for (u32 k = tid; k < SL * bins; k += kBlock) h[k] = 0;
+    __syncthreads();
+    const u64 nvec = (n + 3) / 4;
+    for (u64 v0 = (u64)blockIdx.x * kBlock; v0 < nvec; v0 += (u64)gridDim.x * kBlock) {  // (uniform: shed_agg_add needs the wave)
+        const u64 v = v0 + tid;
+        u32 cc[4] = {kNone, kNone, kNone, kNone}, ll[4], w[4] = {0, 0, 0, 0}, key[4] = {0, 0, 0, 0};
+        if (v < nvec) ish_quad<CLS>(A, load, aff, S, Kw, cutoff, ct, v * 4, n, m, cc, ll, w, key);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            bool act = w[k] != 0;
+            u32 sl = kNone;
+            if (act) sl = mp[cc[k]];
+            act = act && sl != kNone;
+            if (act) act = (key[k] & himask) == pr[sl];
+            const u32 d = (key[k] >> shift) & (bins - 1);
+            if (LDS) {
+                if (act) atomicAdd(&h[sl * bins + d], (u64)w[k]);
+            } else {
+                shed_agg_add(hist, act ? sl * stride + d : 0u, (u64)w[k], act, false);
+            }
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        for (u32 k = tid; k < SL * bins; k += kBlock)
+            if (h[k]) atomicAdd(&hist[(size_t)(k / bins) * stride + (k % bins)], h[k]);
+    }
+}
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void k_ish_key_hist(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                         const u32* __restrict__ aff, const u32* __restrict__ S, u32 cutoff, u64 n,
+                                                         u32 m, u32 SL, const u32* __restrict__ map, const u32* __restrict__ pre,
+                                                         u32 himask, u32 shift, u32 bins, u32 stride, u64* __restrict__ hist) {
+    ish_key_hist_body<LDS, false>(A, load, aff, S, nullptr, cutoff, ClsCutoffs{}, n, m, SL, map, pre, himask, shift, bins, stride,
+                                  hist);
+}
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void k_ishc_key_hist(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                          const u32* __restrict__ aff, const u32* __restrict__ S,
+                                                          const u32* __restrict__ Kw, const ClsCutoffs cq, u64 n, u32 m, u32 SL,
+                                                          const u32* __restrict__ map, const u32* __restrict__ pre, u32 himask,
+                                                          u32 shift, u32 bins, u32 stride, u64* __restrict__ hist) {
+    ish_key_hist_body<LDS, true>(A, load, aff, S, Kw, 0u, cq, n, m, SL, map, pre, himask, shift, bins, stride, hist);
+}
+
+// per (slot x tile) the load of the ties: the candidates whose key is their node's threshold
+template <bool CLS>
+__device__ __forceinline__ void ish_tile_body(const u32* __restrict__ A, const u32* __restrict__ load, const u32* __restrict__ aff,
+                                              const u32* __restrict__ S, const u32* __restrict__ Kw, u32 cutoff,
+                                              const ClsCutoffs& cq, const ShPlan& p, const u32* __restrict__ map,
+                                              const u32* __restrict__ thr, u64* __restrict__ mat) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64* h = reinterpret_cast<u64*>(smem);      // [s]
+    u32* mp = reinterpret_cast<u32*>(h + p.s);  // [m]
+    u32* th = mp + p.m;                         // [m]
+    const int tid = threadIdx.x;
+    const u32 t = blockIdx.x;
+    const u32* ct = ish_stage<CLS>(cq);
+    for (u32 k = tid; k < p.s; k += kBlock) h[k] = 0;
+    for (u32 k = tid; k < p.m; k += kBlock) { mp[k] = map[k]; th[k] = thr[k]; }
+    __syncthreads();
+    const u64 lo = (u64)t * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
+    for (u64 base = lo; base < hi; base += kShChunk) {
+        const u64 i0 = base + (u64)tid * 4;
+        if (i0 >= hi) continue;
+        u32 cc[4], ll[4], w[4], key[4];
+        ish_quad<CLS>(A, load, aff, S, Kw, cutoff, ct, i0, hi, p.m, cc, ll, w, key);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (w[k] && key[k] == th[cc[k]]) {
+                const u32 sl = mp[cc[k]];
+                if (sl != kNone) atomicAdd(&h[sl], (u64)w[k]);
+            }
+    }
+    __syncthreads();
+    for (u32 k = tid; k < p.s; k += kBlock) mat[(size_t)k * p.nt + t] = h[k];
+}
+__global__ __launch_bounds__(kBlock) void k_ish_tile(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                     const u32* __restrict__ aff, const u32* __restrict__ S, u32 cutoff, ShPlan p,
+                                                     const u32* __restrict__ map, const u32* __restrict__ thr,
+                                                     u64* __restrict__ mat) {
+    ish_tile_body<false>(A, load, aff, S, nullptr, cutoff, ClsCutoffs{}, p, map, thr, mat);
+}
+__global__ __launch_bounds__(kBlock) void k_ishc_tile(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                      const u32* __restrict__ aff, const u32* __restrict__ S,
+                                                      const u32* __restrict__ Kw, const ClsCutoffs cq, ShPlan p,
+                                                      const u32* __restrict__ map, const u32* __restrict__ thr,
+                                                      u64* __restrict__ mat) {
+    ish_tile_body<true>(A, load, aff, S, Kw, 0u, cq, p, map, thr, mat);
+}
+
+// one workgroup per slot: shed_cut_body's two searches (the tile, then the row inside it) over the ties of the slot's node
+template <bool CLS>
+__device__ __forceinline__ void ish_cut_body(const u32* __restrict__ A, const u32* __restrict__ load, const u32* __restrict__ aff,
+                                             const u32* __restrict__ S, const u32* __restrict__ Kw, u32 cutoff,
+                                             const ClsCutoffs& cq, const ShPlan& p, const u64* __restrict__ mat,
+                                             const u32* __restrict__ slot_node, const u64* __restrict__ slot_free,
+                                             const u32* __restrict__ thr, u32* __restrict__ cut) {
+    __shared__ u64 part[16];
+    __shared__ u64 s_base;
+    __shared__ u32 s_tile, s_row;
+    const int tid = threadIdx.x;
+    const u32 sl = blockIdx.x, j = slot_node[sl];
+    const u32 tj = thr[j];
+    const u64 fr = slot_free[sl];
+    const u64* row = mat + (size_t)sl * p.nt;
+    const u32* ct = ish_stage<CLS>(cq);
+    if (tid == 0) { s_tile = kNone; s_row = kNone; s_base = 0; }
+    __syncthreads();
+    u64 carry = 0;
+    for (u32 t0 = 0; t0 < p.nt; t0 += kBlock) {
+        const u32 t = t0 + tid;
+        const u64 v = t < p.nt ? row[t] : 0ull;
+        u64 tot;
+        const u64 ex = carry + block_excl_scan_1024(v, false, part, &tot);
+        if (t < p.nt && ex <= fr && ex + v > fr) { s_tile = t; s_base = ex; }
+        carry += tot;
+        __syncthreads();
+        if (s_tile != kNone) break;
+    }
+    const u32 t = s_tile;
+    if (t == kNone) return;  // (the selection left rem below the ties' load: cannot happen)
+    carry = s_base;
+    const u64 lo = (u64)t * p.T, hi = lo + p.T < p.n ? lo + p.T : p.n;
+    for (u64 base = lo; base < hi; base += kShChunk) {
+        const u64 i0 = base + (u64)tid * 4;
+        u32 tw[4] = {0, 0, 0, 0};
+        if (i0 < hi) {
+            u32 cc[4], ll[4], w[4], key[4];
+            ish_quad<CLS>(A, load, aff, S, Kw, cutoff, ct, i0, hi, p.m, cc, ll, w, key);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) tw[k] = (cc[k] == j && key[k] == tj) ? w[k] : 0u;
+        }
+        u64 tot;
+        u64 run = carry + block_excl_scan_1024((u64)tw[0] + tw[1] + tw[2] + tw[3], false, part, &tot);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (run <= fr && run + tw[k] > fr) s_row = (u32)(i0 + k);
+            run += tw[k];
+        }
+        carry += tot;
+        __syncthreads();
+        if (s_row != kNone) break;
+    }
+    if (tid == 0) cut[j] = s_row;
+}
+__global__ __launch_bounds__(kBlock) void k_ish_cut(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                    const u32* __restrict__ aff, const u32* __restrict__ S, u32 cutoff, ShPlan p,
+                                                    const u64* __restrict__ mat, const u32* __restrict__ slot_node,
+                                                    const u64* __restrict__ slot_free, const u32* __restrict__ thr,
+                                                    u32* __restrict__ cut) {
+    ish_cut_body<false>(A, load, aff, S, nullptr, cutoff, ClsCutoffs{}, p, mat, slot_node, slot_free, thr, cut);
+}
+__global__ __launch_bounds__(kBlock) void k_ishc_cut(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                     const u32* __restrict__ aff, const u32* __restrict__ S,
+                                                     const u32* __restrict__ Kw, const ClsCutoffs cq, ShPlan p,
+                                                     const u64* __restrict__ mat, const u32* __restrict__ slot_node,
+                                                     const u64* __restrict__ slot_free, const u32* __restrict__ thr,
+                                                     u32* __restrict__ cut) {
+    ish_cut_body<true>(A, load, aff, S, Kw, 0u, cq, p, mat, slot_node, slot_free, thr, cut);
+}
+
+// the surplus rows of the lane's quad in step s of the tile at lo, a bit each; *sum += their load.  thr / cut are read only
+// for candidates (a gather from two tables of m words).
+template <bool CLS>
+__device__ __forceinline__ u32 ish_flags(const u32* A, const u32* __restrict__ load, const u32* aff, const u32* __restrict__ S,
+                                         const u32* __restrict__ Kw, u32 cutoff, const u32* ct, u64 i0, u64 n, u32 m,
+                                         const u32* __restrict__ thr, const u32* __restrict__ cut, u64* sum) {
+    u32 cc[4], ll[4], w[4], key[4];
+    ish_quad<CLS>(A, load, aff, S, Kw, cutoff, ct, i0, n, m, cc, ll, w, key);
+    u32 f = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (!w[k]) continue;
+        const u32 t = thr[cc[k]];
+        if (key[k] > t || (key[k] == t && i0 + k >= (u64)cut[cc[k]])) {
+            f |= 1u << k;
+            *sum += w[k];
+        }
+    }
+    return f;
+}
+template <bool CLS>
+__device__ __forceinline__ void ish_count_body(const u32* __restrict__ A, const u32* __restrict__ load, const u32* __restrict__ aff,
+                                               const u32* __restrict__ S, const u32* __restrict__ Kw, u32 cutoff,
+                                               const ClsCutoffs& cq, const ChgPlan& p, u32 m, const u32* __restrict__ thr,
+                                               const u32* __restrict__ cut, u32* __restrict__ cnt, u32* __restrict__ gsum,
+                                               u64* __restrict__ acc, u64* __restrict__ freed) {
+    const u32* ct = ish_stage<CLS>(cq);
+    if (CLS) __syncthreads();
+    u64 sum = 0;
+    oc_count(p, cnt, gsum, [&](u64 lo, u32 lane) {
+        u32 c = 0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            c += __builtin_popcount(ish_flags<CLS>(A, load, aff, S, Kw, cutoff, ct, lo + (u64)s * 256 + lane * 4, p.n, m, thr, cut, &sum));
+        return c;
+    });
+    sum = wave_sum(sum);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&acc[kShAccSurplusLoad], sum);
+    if (threadIdx.x == 0 && blockIdx.x == 0) *freed = 0;  // (k_ish_apply, a later launch, adds into it)
+}
+__global__ __launch_bounds__(kChgWaves * 64) void k_ish_count(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                              const u32* __restrict__ aff, const u32* __restrict__ S, u32 cutoff,
+                                                              const ChgPlan p, u32 m, const u32* __restrict__ thr,
+                                                              const u32* __restrict__ cut, u32* __restrict__ cnt,
+                                                              u32* __restrict__ gsum, u64* __restrict__ acc, u64* __restrict__ freed) {
+    ish_count_body<false>(A, load, aff, S, nullptr, cutoff, ClsCutoffs{}, p, m, thr, cut, cnt, gsum, acc, freed);
+}
+__global__ __launch_bounds__(kChgWaves * 64) void k_ishc_count(const u32* __restrict__ A, const u32* __restrict__ load,
+                                                               const u32* __restrict__ aff, const u32* __restrict__ S,
+                                                               const u32* __restrict__ Kw, const ClsCutoffs cq, const ChgPlan p,
+                                                               u32 m, const u32* __restrict__ thr, const u32* __restrict__ cut,
+                                                               u32* __restrict__ cnt, u32* __restrict__ gsum,
+                                                               u64* __restrict__ acc, u64* __restrict__ freed) {
+    ish_count_body<true>(A, load, aff, S, Kw, 0u, cq, p, m, thr, cut, cnt, gsum, acc, freed);
+}
+
+// (A and aff carry no __restrict__: under the row lifecycle aff_life is aff, and exp_apply stores into both columns)
+template <bool CLS>
+__device__ __forceinline__ void ish_apply_body(u32* A, const u32* __restrict__ load, const u32* aff, const u32* __restrict__ S,
+                                               const u32* __restrict__ Kw, u32 cutoff, const ClsCutoffs& cq, const ChgPlan& p, u32 m,
+                                               const u32* __restrict__ thr, const u32* __restrict__ cut, const u32* cnt,
+                                               const u32* gsum, u64 cap, u32* rows, u32* node, u32* aff_life, u64* used, u32 hist,
+                                               u64* freed) {
+    const u32* ct = ish_stage<CLS>(cq);  // (in front of exp_apply's barrier)
+    u64 unused = 0;
+    exp_apply(A, p, cnt, gsum, cap, rows, node, aff_life, load, m, used, hist, freed, [&](u64 lo, u32 lane) {
+        u32 fl = 0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            fl |= ish_flags<CLS>(A, load, aff, S, Kw, cutoff, ct, lo + (u64)s * 256 + lane * 4, p.n, m, thr, cut, &unused) << (4 * s);
+        return fl;
+    });
+}
+__global__ __launch_bounds__(kChgWaves * 64) void k_ish_apply(u32* A, const u32* __restrict__ load, const u32* aff,
+                                                              const u32* __restrict__ S, u32 cutoff, const ChgPlan p, u32 m,
+                                                              const u32* __restrict__ thr, const u32* __restrict__ cut,
+                                                              const u32* __restrict__ cnt, const u32* __restrict__ gsum, u64 cap,
+                                                              u32* __restrict__ rows, u32* __restrict__ node, u32* aff_life,
+                                                              u64* __restrict__ used, u32 hist, u64* __restrict__ freed) {
+    ish_apply_body<false>(A, load, aff, S, nullptr, cutoff, ClsCutoffs{}, p, m, thr, cut, cnt, gsum, cap, rows, node, aff_life, used,
+                          hist, freed);
+}
+__global__ __launch_bounds__(kChgWaves * 64) void k_ishc_apply(u32* A, const u32* __restrict__ load, const u32* aff,
+                                                               const u32* __restrict__ S, const u32* __restrict__ Kw,
+                                                               const ClsCutoffs cq, const ChgPlan p, u32 m,
+                                                               const u32* __restrict__ thr, const u32* __restrict__ cut,
+                                                               const u32* __restrict__ cnt, const u32* __restrict__ gsum, u64 cap,
+                                                               u32* __restrict__ rows, u32* __restrict__ node, u32* aff_life,
+                                                               u64* __restrict__ used, u32 hist, u64* __restrict__ freed) {
+    ish_apply_body<true>(A, load, aff, S, Kw, 0u, cq, p, m, thr, cut, cnt, gsum, cap, rows, node, aff_life, used, hist, freed);
+}
+
+void launch_ish_hist(const IshCols& c, u64 n, u32 m, u64* used, u64* cand, u32* kmm, hipStream_t s) {
+    (void)hipMemsetAsync(used, 0, (size_t)m * sizeof(u64), s);
+    (void)hipMemsetAsync(cand, 0, (size_t)m * sizeof(u64), s);
+    launch_fill_u32(kmm, 1, kNone, s);
+    (void)hipMemsetAsync(kmm + 1, 0, sizeof(u32), s);
+    if (!n || !m) return;
+    const dim3 grid(grid_for((n + 3) / 4, kBlock, 256)), block(kBlock);
+    const size_t lds = 2 * (size_t)m * sizeof(u64);
+    if (c.cls)
+        hipLaunchKernelGGL(k_ishc_hist, grid, block, lds, s, c.A, c.load, c.aff, c.S, reinterpret_cast<const u32*>(c.K), *c.cls, n, m,
+                           used, cand, kmm);
+    else hipLaunchKernelGGL(k_ish_hist, grid, block, lds, s, c.A, c.load, c.aff, c.S, c.cutoff, n, m, used, cand, kmm);
+}
+
+u32 launch_ish_select(const IshCols& c, u64 n, u32 m, u32 s, const u32* map, const u32* slot_node, u64* slot_free, u32* pre,
+                      u64* hist, u32* thr, u32 kmin, u32 kmax, hipStream_t st) {
+    launch_fill_u32(thr, m, kNone, st);
+    if (!s || !n) return 0;
+    const ShSelPlan q = sh_sel_plan(s);
+    const u32 stride = 1u << q.bits;
+    // the candidates' keys agree in every bit above the highest one in which the smallest and the largest differ: the passes
+    // whose digit lies above it would all pick the digit of kmin
+    const u32 x = kmin ^ kmax, hb = x ? 31u - (u32)__builtin_clz(x) : 0u;
+    u32 first = 0;
+    while (sh_sel_digit(q, first).lo > hb) ++first;
+    launch_fill_u32(pre, s, kmin & sh_sel_digit(q, first).himask, st);
+    (void)hipMemsetAsync(hist, 0, ((size_t)s << q.bits) * sizeof(u64), st);
+    const dim3 grid(grid_for((n + 3) / 4, kBlock, 256)), block(kBlock);
+    const size_t head = (((size_t)m + s) * sizeof(u32) + 15) & ~(size_t)15;
+    const u32* Kw = reinterpret_cast<const u32*>(c.K);
+    for (u32 pass = first; pass < q.passes; ++pass) {
+        const ShSelDigit d = sh_sel_digit(q, pass);
+        const size_t lds = head + (q.lds ? (size_t)s * d.bins * sizeof(u64) : 0);
+        if (c.cls && q.lds)
+            hipLaunchKernelGGL((k_ishc_key_hist<true>), grid, block, lds, st, c.A, c.load, c.aff, c.S, Kw, *c.cls, n, m, s, map, pre,
+                               d.himask, d.lo, d.bins, stride, hist);
+        else if (c.cls)
+            hipLaunchKernelGGL((k_ishc_key_hist<false>), grid, block, lds, st, c.A, c.load, c.aff, c.S, Kw, *c.cls, n, m, s, map, pre,
+                               d.himask, d.lo, d.bins, stride, hist);
+        else if (q.lds)
+            hipLaunchKernelGGL((k_ish_key_hist<true>), grid, block, lds, st, c.A, c.load, c.aff, c.S, c.cutoff, n, m, s, map, pre,
+                               d.himask, d.lo, d.bins, stride, hist);
+        else
+            hipLaunchKernelGGL((k_ish_key_hist<false>), grid, block, lds, st, c.A, c.load, c.aff, c.S, c.cutoff, n, m, s, map, pre,
+                               d.himask, d.lo, d.bins, stride, hist);
+        hipLaunchKernelGGL(k_shed_sel_pick, dim3(s), dim3(kBlock), 0, st, hist, d.bins, stride, d.lo, d.lo == 0, slot_node,
+                           slot_free, pre, thr);
+    }
+    return q.passes - first;
+}
+
+void launch_ish_cut(const IshCols& c, const ShPlan& p, const u32* map, const u32* slot_node, const u64* slot_free, u64* mat,
+                    u32* cut, const u32* thr, hipStream_t s) {
+    launch_fill_u32(cut, p.m, kNone, s);
+    if (!p.s || !p.n) return;
+    const size_t lds = (size_t)p.s * sizeof(u64) + 2 * (size_t)p.m * sizeof(u32);
+    if (c.cls) {
+        const u32* Kw = reinterpret_cast<const u32*>(c.K);
+        hipLaunchKernelGGL(k_ishc_tile, dim3(p.nt), dim3(kBlock), lds, s, c.A, c.load, c.aff, c.S, Kw, *c.cls, p, map, thr, mat);
+        hipLaunchKernelGGL(k_ishc_cut, dim3(p.s), dim3(kBlock), 0, s, c.A, c.load, c.aff, c.S, Kw, *c.cls, p, mat, slot_node,
+                           slot_free, thr, cut);
+        return;
+    }
+    hipLaunchKernelGGL(k_ish_tile, dim3(p.nt), dim3(kBlock), lds, s, c.A, c.load, c.aff, c.S, c.cutoff, p, map, thr, mat);
+    hipLaunchKernelGGL(k_ish_cut, dim3(p.s), dim3(kBlock), 0, s, c.A, c.load, c.aff, c.S, c.cutoff, p, mat, slot_node, slot_free, thr,
+                       cut);
+}
+
+void launch_ish_count(const IshCols& c, const ChgPlan& p, u32 m, const u32* thr, const u32* cut, u32* cnt, u32* gsum, u32* total,
+                      u64* acc, u64* freed, hipStream_t s) {
+    if (!p.G) return;
+    if (c.cls)
+        hipLaunchKernelGGL(k_ishc_count, dim3(p.G), dim3(kChgWaves * 64), 0, s, c.A, c.load, c.aff, c.S,
+                           reinterpret_cast<const u32*>(c.K), *c.cls, p, m, thr, cut, cnt, gsum, acc, freed);
+    else
+        hipLaunchKernelGGL(k_ish_count, dim3(p.G), dim3(kChgWaves * 64), 0, s, c.A, c.load, c.aff, c.S, c.cutoff, p, m, thr, cut, cnt,
+                           gsum, acc, freed);
+    hipLaunchKernelGGL(k_chg_scan, dim3(1), dim3(kChgWaves * 64), 0, s, gsum, p.G, total);
+}
+
+void launch_ish_apply(u32* A, const IshCols& c, const ChgPlan& p, u32 m, const u32* thr, const u32* cut, const u32* cnt,
+                      const u32* gsum, u64 cap, u32* rows, u32* node, u32* aff_life, u64* used, u64* freed, hipStream_t s) {
+    if (c.cls)
+        launch_apply(k_ishc_apply, p, cap, m, used, freed, s, A, c.load, c.aff, c.S, reinterpret_cast<const u32*>(c.K), *c.cls, p, m,
+                     thr, cut, cnt, gsum, cap, rows, node, aff_life, used);
+    else
+        launch_apply(k_ish_apply, p, cap, m, used, freed, s, A, c.load, c.aff, c.S, c.cutoff, p, m, thr, cut, cnt, gsum, cap, rows,
+                     node, aff_life, used);
+}
+
 }  // namespace riogp

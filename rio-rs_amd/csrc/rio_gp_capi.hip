@@ -2538,6 +2538,162 @@ int rio_gp_expire_classes_dev(rio_gp_t* h, uint32_t n_classes, const uint32_t* c
     return sweep(h, Sweep{true, 0, n_classes, cutoffs, idle_by_class}, false, d_rows, d_node, cap, n_idle, load_freed);
 }
 
+// ---- pressure shedding (rule 14) ---------------------------------------------------------------
+
+// the checks of both entry points: nothing is allocated, launched or changed before they pass
+static int shed_args(rio_gp* h, const rio_gp_shed_cfg* cfg, const void* r, const void* nd, uint64_t cap) {
+    const char* why = nullptr;
+    if (!cfg) why = "cfg is NULL";
+    else if (cfg->struct_size != sizeof(rio_gp_shed_cfg)) why = "struct_size differs";
+    else if (cfg->reserved != 0) why = "reserved is not 0";
+    else if (cfg->class_cutoffs && (cfg->n_classes < 1 || cfg->n_classes > RIO_GP_MAX_CLASSES))
+        why = "1 .. RIO_GP_MAX_CLASSES class cutoffs are needed";
+    else if (!cfg->class_cutoffs && cfg->n_classes) why = "n_classes without class_cutoffs";
+    else if ((r != nullptr) != (nd != nullptr)) why = "out_rows / out_node are given together or not at all";
+    else if (!r && cap) why = "rows_cap without a listing";
+    if (why) return fail(h, RIO_GP_EINVAL, std::string("rio_gp_shed_idle: ") + why);
+    return refuse_row_sharded(h, "rio_gp_shed_idle");
+}
+
+// Both forms, validated and locked.  to_host: rows / node are the caller's host arrays.  The phases are the rebalance's (R0 and
+// the host's slot pick behind a first wait, the cuts, the surplus per tile) with the expiries' apply pass in place of R2 - R4.
+// The node pass writes the call's own scratch (RbBufs::lu / pin), not the handle's `used`: a call that sheds nothing leaves
+// the committed vector, its pending parts and its validity exactly as they were.
+static int shed_locked(rio_gp* h, const rio_gp_shed_cfg* cfg, bool to_host, rio_gp_shed_stats* st, uint32_t* rows, uint32_t* node,
+                       uint64_t cap, uint64_t* n_rows) {
+    rio_gp_shed_stats s{};
+    int rc;
+    if ((rc = exp_begin(h, "rio_gp_shed_idle"))) return rc;
+    const bool classes = cfg->class_cutoffs || h->cls_any_imm;
+    ClsCutoffs ct;
+    if (classes) {  // L0 as one table: the caller's cutoffs (or the one cutoff for every class), 0 where a class is immovable
+        if ((rc = cls_begin(h, "rio_gp_shed_idle"))) return rc;
+        for (u32 c = 0; c < kClsMax; ++c) {
+            const u32 v = cfg->class_cutoffs ? (c < cfg->n_classes ? cfg->class_cutoffs[c] : 0u) : cfg->cutoff;
+            ct.v[c] = ((h->cls_imm[c >> 5] >> (c & 31)) & 1u) ? 0u : v;
+        }
+    }
+    if ((rc = rb_ensure(h))) return rc;
+    const RbBufs b = rb_bufs(h);
+    const u32 m = h->m;
+    const u64 n = h->n;
+    const u64 B = rows ? std::min<u64>(cfg->max_rows, cap) : cfg->max_rows;
+    const IshCols cols{h->assign[h->cur], h->load, h->aff, h->exp_S, cfg->cutoff, classes ? h->cls_K : nullptr,
+                       classes ? &ct : nullptr};
+    if (n_rows) *n_rows = 0;
+    std::vector<u64> T(m ? m : 1), used(m ? m : 1), cand(m ? m : 1);
+    if (cfg->target) memcpy(T.data(), cfg->target, (size_t)m * sizeof(u64));
+    else if (m) HIPCHK(h, hipMemcpyAsync(T.data(), h->cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    // the node pass: every node's load and its candidates' load; the range of the candidates' keys
+    u32 kmm[2] = {kNone, 0};
+    launch_ish_hist(cols, n, m, b.lu, b.pin, b.info, h->stream);
+    HIPCHK(h, hipGetLastError());
+    if (m) {
+        HIPCHK(h, hipMemcpyAsync(used.data(), b.lu, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(cand.data(), b.pin, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(kmm, b.info, sizeof kmm, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // L1 on the host's side: the live nodes whose candidates weigh more than T -sat pinned
+    std::vector<u32> hmap(m ? m : 1, kNone), snode;
+    std::vector<u64> sfree;
+    for (u32 j = 0; j < m; ++j) {
+        if (!h->h_alive[j]) continue;
+        s.nodes_over_before += used[j] > T[j];
+        const u64 pinned = used[j] - cand[j], fr = T[j] > pinned ? T[j] - pinned : 0;
+        if (cand[j] > fr) { hmap[j] = (u32)snode.size(); snode.push_back(j); sfree.push_back(fr); }
+    }
+    s.nodes_over_after = s.nodes_over_before;
+    const u32 S = (u32)snode.size();
+    const ChgPlan cp = chg_plan(n);
+    if (!S || !cp.G) {  // no node has anything to shed: nothing was changed
+        if (st) *st = s;
+        return RIO_GP_OK;
+    }
+    const ShPlan p = sh_plan(n, m, S);
+    if ((rc = rb_plan_ensure(h, p)) || (rc = ensure(h, h->sh_sel, ((size_t)S << sh_sel_plan(S).bits) * sizeof(u64)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(b.map, hmap.data(), (size_t)m * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(b.slot_node, snode.data(), (size_t)S * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(b.slot_free, sfree.data(), (size_t)S * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(b.acc, 0, kShAcc * sizeof(u64), h->stream));
+    // L1 on the device: sigma_j (as the key ~sigma_j in thr) and rem_j, then cutrow_j among the ties; the surplus per tile
+    (void)launch_ish_select(cols, n, m, S, b.map, b.slot_node, b.slot_free, b.pre, (u64*)h->sh_sel.p, b.thr, kmm[0], kmm[1],
+                            h->stream);
+    launch_ish_cut(cols, p, b.map, b.slot_node, b.slot_free, (u64*)h->sh_mat.p, b.cut, b.thr, h->stream);
+    *h->h_chg = 0;
+    launch_ish_count(cols, cp, m, b.thr, b.cut, h->chg_cnt, h->chg_gsum, h->d_chg, b.acc, h->exp_freed, h->stream);
+    HIPCHK(h, hipGetLastError());
+    u64 a[kShAcc] = {};
+    HIPCHK(h, hipMemcpyAsync(a, b.acc, sizeof a, hipMemcpyDeviceToHost, h->stream));
+    // L2 / L3.  The device form's apply pass reads the prefix the count pass left on the device and drops ranks >= B itself;
+    // the host form waits for the count first and stages exactly the listing.
+    u32 *d_rows = rows, *d_node = node;
+    u64 K = B;
+    if (to_host || !rows) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        K = std::min<u64>(*h->h_chg, B);
+        if (K) {  // (without a listing the ranks still need somewhere to go)
+            if ((rc = ensure(h, h->chg_stage, 2 * K * sizeof(u32)))) return rc;
+            d_rows = (u32*)h->chg_stage.p;
+            d_node = d_rows + K;
+        }
+    }
+    u64 freed = 0;
+    if (K) {
+        // the recount of the node pass follows the writes; it becomes the committed vector below if a row was shed
+        launch_ish_apply(h->assign[h->cur], cols, cp, m, b.thr, b.cut, h->chg_cnt, h->chg_gsum, K, d_rows, d_node, aff_life(h), b.lu,
+                         h->exp_freed, h->stream);
+        if (hipGetLastError() != hipSuccess) {
+            inputs_changed(h);  // (nobody can tell what ran)
+            h->used.invalidate();
+            return fail(h, RIO_GP_EUPSTREAM, "rio_gp_shed_idle: the launch of the apply pass failed");
+        }
+        const hipError_t e1 = hipMemcpyAsync(&freed, h->exp_freed, sizeof freed, hipMemcpyDeviceToHost, h->stream);
+        const hipError_t e2 = m ? hipMemcpyAsync(used.data(), b.lu, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+        const hipError_t e3 = hipStreamSynchronize(h->stream);
+        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+            inputs_changed(h);
+            h->used.invalidate();
+            HIPCHK(h, e1 != hipSuccess ? e1 : e2 != hipSuccess ? e2 : e3);
+        }
+    } else {
+        HIPCHK(h, hipStreamSynchronize(h->stream));  // (the counters; nothing was changed)
+    }
+    s.surplus_rows = *h->h_chg;
+    s.surplus_load = a[kShAccSurplusLoad];
+    s.shed_rows = std::min<u64>(s.surplus_rows, K);
+    s.shed_load = freed;
+    if (s.shed_rows) {
+        // from here on it is a rio_gp_remove_batch of the listed rows; `used` is the node pass's recount less what they weighed
+        inputs_changed(h);
+        h->used.invalidate();
+        if (m) HIPCHK(h, hipMemcpyAsync(h->used.storage(), b.lu, (size_t)m * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
+        h->used.rebuilt();
+        s.nodes_over_after = 0;
+        for (u32 j = 0; j < m; ++j) s.nodes_over_after += h->h_alive[j] && used[j] > T[j];
+        if (to_host && rows && (rc = read_listing(h, d_rows, K, s.shed_rows, {rows, node}))) return rc;
+    }
+    if (n_rows) *n_rows = s.shed_rows;
+    if (st) *st = s;
+    return RIO_GP_OK;
+}
+
+int rio_gp_shed_idle(rio_gp_t* h, const rio_gp_shed_cfg* cfg, rio_gp_shed_stats* st, uint32_t* out_rows, uint32_t* out_node,
+                     uint64_t rows_cap, uint64_t* n_rows) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (int rc = shed_args(h, cfg, out_rows, out_node, rows_cap)) return rc;
+    return shed_locked(h, cfg, true, st, out_rows, out_node, rows_cap, n_rows);
+}
+
+int rio_gp_shed_idle_dev(rio_gp_t* h, const rio_gp_shed_cfg* cfg, rio_gp_shed_stats* st, uint32_t* d_rows, uint32_t* d_node,
+                         uint64_t rows_cap, uint64_t* n_rows) {
+    if (!h) return RIO_GP_EINVAL;
+    Locked g(h);
+    if (int rc = shed_args(h, cfg, d_rows, d_node, rows_cap)) return rc;
+    return shed_locked(h, cfg, false, st, d_rows, d_node, rows_cap, n_rows);
+}
+
 // Read-only, like rio_gp_count_placed: the committed column, K and load; no inputs_changed.
 static int census_begin(rio_gp* h, uint32_t flags, uint32_t n_classes, const void* r, const void* l, const void* o) {
     if (flags & ~RIO_GP_CENSUS_BY_NODE) return fail(h, RIO_GP_EINVAL, "rio_gp_census: unknown flags");

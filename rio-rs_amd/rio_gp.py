@@ -86,6 +86,20 @@ class RebalanceStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class ShedCfg(C.Structure):
+    """rio_gp_shed_cfg (include/rio_gpu_placement.h, rule 14)."""
+    _fields_ = [("struct_size", C.c_uint32), ("cutoff", C.c_uint32), ("max_rows", C.c_uint64), ("target", C.c_void_p),
+                ("class_cutoffs", C.c_void_p), ("n_classes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ShedStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("surplus_rows", "surplus_load", "shed_rows", "shed_load")] + [
+        ("nodes_over_before", C.c_uint32), ("nodes_over_after", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 def balanced_targets(cap, used, alive, slack_permille=0):
     """Per-node targets for spreading onto live nodes that hold little (scale-out): every live node's capacity times the live
     nodes' mean utilisation (sum used / sum cap), plus slack_permille of it, never above its capacity.  With unbounded
@@ -216,6 +230,10 @@ def _load(lab):
         L.rio_gp_mixed_batch.argtypes = [_vp, C.POINTER(Mixed)]
         for nm in ("rio_gp_rows_on_nodes", "rio_gp_rows_on_nodes_dev"):
             getattr(L, nm).argtypes = [_vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        if hasattr(L, "rio_gp_shed_idle"):   # (an older build under RIO_GP_LIB, the A/B aid: a call then fails as any missing symbol does)
+            for nm in ("rio_gp_shed_idle", "rio_gp_shed_idle_dev"):
+                getattr(L, nm).argtypes = [_vp, C.POINTER(ShedCfg), C.POINTER(ShedStats), _vp, _vp, C.c_uint64,
+                                           C.POINTER(C.c_uint64)]
         for nm in ("rio_gp_rebalance", "rio_gp_rebalance_dev"):
             getattr(L, nm).argtypes = [_vp, C.POINTER(RebalanceCfg), C.POINTER(RebalanceStats), _vp, _vp, _vp, C.c_uint64,
                                        C.POINTER(C.c_uint64)]
@@ -563,6 +581,50 @@ class GpuPlacement:
         rc = self._L.rio_gp_rebalance(self._h, C.byref(cfg) if cfg is not None else None, C.byref(st), _ptr(out_rows),
                                       _ptr(out_from), _ptr(out_to), int(moves_cap), C.byref(nm))
         return rc, st.as_dict(), int(nm.value)
+
+    # -- pressure shedding (rule 14) --
+    def _shed_cfg(self, cutoff, target, max_rows, class_cutoffs):
+        t = None if target is None else np.ascontiguousarray(target, np.uint64)
+        if t is not None and t.size != self.num_nodes:
+            raise ValueError("target needs one entry per node")
+        cc = None if class_cutoffs is None else np.ascontiguousarray(class_cutoffs, np.uint32)
+        cfg = ShedCfg(C.sizeof(ShedCfg), int(cutoff), CAP_INF if max_rows is None else int(max_rows),
+                      None if t is None else t.ctypes.data, None if cc is None else cc.ctypes.data,
+                      0 if cc is None else int(cc.size), 0)
+        return cfg, (t, cc)
+
+    def shed_idle(self, cutoff, target=None, max_rows=None, class_cutoffs=None, list_rows=True, rows_cap=None):
+        """rio_gp_shed_idle: (stats dict, rows, nodes) — on every node over its target (None: the capacities) the longest-idle
+        objects with a stamp below `cutoff` (class_cutoffs: below their class's) are un-placed, as many as bring the node back
+        under; rows ascending with the node each one was on (uint32 arrays; empty with list_rows=False).  max_rows None: no
+        limit, 0: count the surplus only.  rows_cap: the listing's capacity (default: max_rows bounded by the table size); it
+        bounds the rows shed as well."""
+        cfg, _keep = self._shed_cfg(cutoff, target, max_rows, class_cutoffs)
+        st, nr = ShedStats(), C.c_uint64(0)
+        if list_rows:
+            cap = int(rows_cap if rows_cap is not None else min(cfg.max_rows, self.num_objects))
+            buf = np.empty((2, max(min(cap, self.num_objects), 1)), np.uint32)
+            self._chk(self._L.rio_gp_shed_idle(self._h, C.byref(cfg), C.byref(st), _ptr(buf[0]), _ptr(buf[1]), cap, C.byref(nr)))
+            k = int(nr.value)
+            return st.as_dict(), buf[0, :k].copy(), buf[1, :k].copy()
+        self._chk(self._L.rio_gp_shed_idle(self._h, C.byref(cfg), C.byref(st), None, None, 0, C.byref(nr)))
+        e = np.empty(0, np.uint32)
+        return st.as_dict(), e, e
+
+    def shed_idle_dev(self, cutoff, d_rows=None, d_node=None, rows_cap=0, target=None, max_rows=None, class_cutoffs=None):
+        """rio_gp_shed_idle_dev: the listing into device arrays (ints; both None: no listing).  Returns (stats dict, n_rows)."""
+        cfg, _keep = self._shed_cfg(cutoff, target, max_rows, class_cutoffs)
+        st, nr = ShedStats(), C.c_uint64(0)
+        self._chk(self._L.rio_gp_shed_idle_dev(self._h, C.byref(cfg), C.byref(st), _vp(d_rows) if d_rows else None,
+                                               _vp(d_node) if d_node else None, int(rows_cap), C.byref(nr)))
+        return st.as_dict(), int(nr.value)
+
+    def shed_idle_raw(self, cfg, out_rows=None, out_node=None, rows_cap=0):
+        """One rio_gp_shed_idle call as given (tests of the argument checks): (rc, stats dict, n_rows); no exception."""
+        st, nr = ShedStats(), C.c_uint64(0)
+        rc = self._L.rio_gp_shed_idle(self._h, C.byref(cfg) if cfg is not None else None, C.byref(st), _ptr(out_rows),
+                                      _ptr(out_node), int(rows_cap), C.byref(nr))
+        return rc, st.as_dict(), int(nr.value)
 
     # -- change feed --
     def changes(self, cap=None, peek=False):
@@ -1083,6 +1145,8 @@ def _oplib():
         bind_op_changes(L)
         bind_op_expire(L)
         bind_op_classes(L)
+        if hasattr(L, "rio_op_shed_idle"):   # (as above)
+            bind_op_shed(L)
         bind_op_loads(L)
         if hasattr(L, "rio_op_hottest_objects"):   # (as above)
             bind_op_top(L)
@@ -1147,6 +1211,22 @@ def op_expire(L, h, cutoff, max_objects=None):
     if rc != OK:
         return rc, [], 0
     return rc, _listing(o), int(idle.value)
+
+
+def bind_op_shed(L):
+    """argtypes of rio_op_shed_idle on a library that has it (the product, or a stub-linked test build)."""
+    L.rio_op_shed_idle.argtypes = [_vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _pp, _psz, _pp, _psz,
+                                   _pp]
+
+
+def op_shed_idle(L, h, cutoff, max_objects=None):
+    """One rio_op_shed_idle call: (rc, [(struct_name, object_id, address)], n_surplus), as op_expire."""
+    o, sur = _listing_out(1), C.c_uint64(0)
+    cap = 0xFFFFFFFFFFFFFFFF if max_objects is None else int(max_objects)
+    rc = L.rio_op_shed_idle(h, int(cutoff), cap, C.byref(o[0]), C.byref(sur), *map(C.byref, o[1:]))
+    if rc != OK:
+        return rc, [], 0
+    return rc, _listing(o), int(sur.value)
 
 
 def bind_op_classes(L):
@@ -1478,6 +1558,14 @@ class GpuObjectPlacement:
         rc, out, idle = op_expire(_oplib(), self._h, cutoff, max_objects)
         self._chk(rc)
         return out, idle
+
+    def shed_idle(self, cutoff, max_objects=None):
+        """rio_op_shed_idle: ([(struct_name, object_id, address)], n_surplus) — on every server over its member capacity the
+        longest-idle keys stamped before `cutoff` are un-placed, as many as bring it back under (at most max_objects; None: no
+        limit; 0: count only).  Immovable types and types whose idle limit is IDLE_NEVER are never shed."""
+        rc, out, sur = op_shed_idle(_oplib(), self._h, cutoff, max_objects)
+        self._chk(rc)
+        return out, sur
 
     def set_type_movable(self, struct_name, movable):
         """rio_op_set_type_movable_n: movable=False — rebalance() leaves the keys of this type where they are."""

@@ -101,6 +101,9 @@ extern "C" {
     fn rio_op_expire(p: *mut c_void, cutoff: u32, max_objects_out: u64, n_out: *mut u64, n_idle: *mut u64,
                      tys: *mut *const *const c_char, ty_lens: *mut *const usize, ids: *mut *const *const c_char,
                      id_lens: *mut *const usize, addrs: *mut *const *const c_char) -> c_int;
+    fn rio_op_shed_idle(p: *mut c_void, cutoff: u32, max_objects_out: u64, n_out: *mut u64, n_surplus: *mut u64,
+                        tys: *mut *const *const c_char, ty_lens: *mut *const usize, ids: *mut *const *const c_char,
+                        id_lens: *mut *const usize, addrs: *mut *const *const c_char) -> c_int;
     fn rio_op_set_type_idle_limit_n(p: *mut c_void, ty: *const c_char, ty_len: usize, max_idle: u32) -> c_int;
     fn rio_op_expire_by_type(p: *mut c_void, now: u32, default_max_idle: u32, max_objects_out: u64, n_out: *mut u64,
                              n_idle: *mut u64, tys: *mut *const *const c_char, ty_lens: *mut *const usize,
@@ -343,6 +346,34 @@ impl GpuObjectPlacement {
                  if a.is_null() { None } else { Some(unsafe { CStr::from_ptr(a) }.to_string_lossy().into_owned()) })
             }).collect();
             Ok((out, idle))
+        })
+        .await
+    }
+
+    /// Shedding under pressure (Orleans' activation shedding): on every server whose objects weigh more than its capacity, the
+    /// objects last stamped before `cutoff` are un-placed longest-idle first, only as many as bring the server back under it
+    /// and at most `max_objects` (`None`: no limit; `Some(0)`: count only).  Immovable types and types whose idle limit is
+    /// `u32::MAX` are never shed.  Returns the objects with the address each was on, plus the whole surplus.  The call for a
+    /// cluster that is over as a whole, where `rebalance` has nowhere to move the load to.
+    pub async fn shed_idle(&self, cutoff: u32, max_objects: Option<u64>)
+        -> Result<(Vec<(ObjectId, Option<String>)>, u64), ObjectPlacementError> {
+        let me = self.clone();
+        blocking(move || {
+            let (mut n, mut surplus) = (0u64, 0u64);
+            let (mut ty, mut id, mut ad) = (std::ptr::null(), std::ptr::null(), std::ptr::null());
+            let (mut tl, mut il) = (std::ptr::null(), std::ptr::null());
+            check(unsafe { rio_op_shed_idle(me.inner.0, cutoff, max_objects.unwrap_or(u64::MAX), &mut n, &mut surplus, &mut ty,
+                                            &mut tl, &mut id, &mut il, &mut ad) }, &me)?;
+            // the arrays are this thread's until its next call: read them here, before anything else can run
+            let key = |p: *const *const c_char, l: *const usize, k: usize| unsafe {
+                String::from_utf8_lossy(std::slice::from_raw_parts(*p.add(k) as *const u8, *l.add(k))).into_owned()
+            };
+            let out = (0..n as usize).map(|k| {
+                let a = unsafe { *ad.add(k) };
+                (ObjectId(key(ty, tl, k), key(id, il, k)),
+                 if a.is_null() { None } else { Some(unsafe { CStr::from_ptr(a) }.to_string_lossy().into_owned()) })
+            }).collect();
+            Ok((out, surplus))
         })
         .await
     }
